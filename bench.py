@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: batched centroidal-MPC solves (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: this script starts its own N ranks (one per GPU, `python -m torch.distributed.run` as a child process,
 BEFORE anything in this process touches the GPU) unless it is already running as a rank of such a launch
@@ -59,7 +59,13 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: more ranks than GPUs, ranks share the devices round-robin and the collective runs on "
                          "gloo (RCCL refuses two ranks on one device); the line is marked `rehearsal`")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step of the primary workload returned as DIR/<name>.npy "
+                         "(see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -262,7 +268,9 @@ class Runner:
         }
         if ag_ms is not None:
             m["allgather_ms"] = round(ag_ms, 4)
-        data = dict(cfg=cfg, P32=P32, X032=X032, X=dX.cpu().numpy(), info=info, kern_ms=kern_ms)
+        # gbuf: the all-gathered compact records of the last step (the all-gather timing loop above re-gathers the same dX, dInfo)
+        data = dict(cfg=cfg, P32=P32, X032=X032, X=dX.cpu().numpy(), info=info, kern_ms=kern_ms,
+                    gathered=gbuf.cpu().numpy() if self.coll else None)
         del solver, dP, dX0, dX, dInfo, cbuf, gbuf
         torch.cuda.empty_cache()
         return m, data
@@ -369,6 +377,34 @@ class Runner:
                 "warm_policy": "warm-started pass budget 14 iterations, then the problem starts again from the cold start inside the launch"}
 
 
+DUMP_LIMIT = 64 << 20     # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, data):
+    """--dump-outputs: what the timed path returned in its last timed step (every step solves the same problems from the same cold
+    start), float32, rank 0's problems:
+        x.npy         [B, nx]      the solutions
+        info.npy      [B, 7]       the info words (include/cmpc.h) without word 6, solve_cycles: a shader-clock count, not a result
+        gathered.npy  [sum B, W]   collective runs only: the compact records every rank received from the all-gather
+    The inputs are seeded (make_workload), so the same arguments give the same problems on every run.  Above DUMP_LIMIT in all,
+    every array keeps the same seeded sample of its rows, and <name>_rows.npy (float64) holds their indices."""
+    arrays = {"x": data["X"], "info": np.delete(data["info"], 6, axis=1)}
+    if data.get("gathered") is not None:
+        arrays["gathered"] = data["gathered"]
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT - (64 << 10):   # headroom for the .npy headers
+        frac = (DUMP_LIMIT - (64 << 10)) / sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())
+        for name in list(arrays):
+            a = arrays[name]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+            arrays[name] = a[rows]
+            arrays[f"{name}_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 # ---- the CPU leg: the only place the oracle (test infrastructure) is used, as baseline and as checker ------------
 def cpu_baseline(cfg, P32, X032, tol, mu_min, sample):
     """oracle/ipm_ref.c (float64 port of the same algorithm) on the host cores, OpenMP over a bounded sample of the
@@ -426,6 +462,8 @@ def main():
     R = Runner(args)
     sec_names = [s for s in args.secondary.split(",") if s and s != "none" and s != args.workload]
     m, data = R.run(args.workload, args.steps, args.warmup, args.batch)
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(args.dump_outputs, data)
     secondary = {}
     sec_data = {}
     for s in sec_names:

@@ -12,7 +12,6 @@ import cmpc_amd as cm
 from cmpc_amd.contacts import PlannedContact, sample_schedule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_INI = "/root/reference/src/centroidal-mpc-walking/config/robots"
 
 ERGOCUB_INI = """
 linear_solver                   "ma97"
@@ -62,11 +61,11 @@ def test_ini_reader_matches_preset():
     assert cfg.contacts[1].bounding_box_lower_limit == (-0.01, -0.05, 0.0)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INI), reason="reference tree not present")
 @pytest.mark.parametrize("robot,N", [("ergoCubGazeboV1", 20), ("ergoCubGazeboV1_1", 12), ("ergoCubSN000", 13),
                                      ("ergoCubSN001", 22), ("iCubGazeboV3", 15)])
-def test_reads_the_reference_ini_files(robot, N):
-    cfg = cm.config.from_ini(open(os.path.join(REF_INI, robot, "centroidal_mpc.ini")).read())
+def test_reads_the_reference_ini_files(robot, N, golden_dir):
+    # the reference's config/robots/<robot>/centroidal_mpc.ini, stored as test data
+    cfg = cm.config.from_ini(open(os.path.join(golden_dir, "ini", f"{robot}.ini")).read())
     assert cfg.N == N
     assert len(cfg.contacts) == 2 and all(len(c.corners) == 4 for c in cfg.contacts)
 

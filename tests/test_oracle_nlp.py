@@ -1,7 +1,8 @@
 """Pins oracle/nlp_ref.c (the float64 restatement) against the reference's generated NLP code:
 (a) the committed golden vectors made from it (tests/golden/make_nlp_golden.py), always;
-(b) oracle/_ref itself (tmp.c / jit_tmpComMiH.c compiled as is) on fresh seeds, when present.
-Reference: /root/reference/src/centroidal-mpc-walking/config/robots/ergoCubGazeboV1/tmp.c:62-67,
+(b) on fresh seeds, what tmp.c / jit_tmpComMiH.c compiled as is returned on them (tests/golden/make_nlp_seed7_golden.py),
+    always, and oracle/_ref itself (the same code compiled by oracle/Makefile) when it is built.
+Reference: src/centroidal-mpc-walking/config/robots/ergoCubGazeboV1/tmp.c:62-67,
 12430, 58926, 71962.
 """
 import os
@@ -57,31 +58,40 @@ def test_restatement_matches_golden(which, golden_dir):
 
 
 @pytest.mark.parametrize("which", ["tmp", "jit"])
-def test_restatement_matches_compiled_reference(which):
-    ref_nlp = pytest.importorskip("oracle.ref_nlp")
+def test_restatement_matches_compiled_reference(which, golden_dir):
+    from oracle import ref_nlp
+    d = np.load(os.path.join(golden_dir, f"nlp_seed7_{which}.npz"))
     try:
-        ref = ref_nlp.RefNLP(which)
-    except FileNotFoundError:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
+        live = ref_nlp.RefNLP(which)
+    except FileNotFoundError:   # oracle/_ref is built only where the reference sources are: the stored vectors stand in
+        live = None
     cfg = ol.make_cfg(12, 0.1, **WEIGHTS[which])
     nx, npar, ng, _, _ = ol.dims(cfg)
+    jcol = np.repeat(np.arange(nx), np.diff(d["jac_colind"]))
+    hcol = np.repeat(np.arange(nx), np.diff(d["hess_colind"]))
     rng = np.random.default_rng(7)
-    for _ in range(3):
+    for t in range(3):
         x, p = rng.normal(size=nx), rng.normal(size=npar)
         lf, lg = rng.normal(), rng.normal(size=ng)
-        f0, gf0, g0, J0 = ref.jac_fg(x, p)
-        H0 = ref.hess_l(x, p, lf, lg)
+        for k, v in (("x", x), ("p", p), ("lam_f", lf), ("lam_g", lg)):   # the stored vectors are those of these very draws
+            np.testing.assert_array_equal(d[k][t], v)
+        refs = [(d["f"][t], d["grad_f"][t], d["g"][t], _dense((ng, nx), d["jac_row"], jcol, d["jac_nnz"][t]),
+                 _dense((nx, nx), d["hess_row"], hcol, d["hess_nnz"][t]), d["grad_gamma_x"][t], d["grad_gamma_p"][t])]
+        if live is not None:
+            f0, gf0, g0, J0 = live.jac_fg(x, p)
+            _, _, gx0, gp0 = live.grad(x, p, lf, lg)
+            refs.append((f0, gf0, g0, J0, live.hess_l(x, p, lf, lg), gx0, gp0))
         f1, g1 = ol.nlp_fg(cfg, x, p)
-        assert abs(f0 - f1) <= 1e-12 * abs(f0)
-        np.testing.assert_allclose(g1, g0, atol=1e-12)
-        np.testing.assert_allclose(ol.nlp_grad_f(cfg, x, p), gf0, atol=1e-12 * np.abs(gf0).max())
-        np.testing.assert_allclose(_dense((ng, nx), *ol.nlp_jac(cfg, x, p)), J0, atol=1e-12)
-        np.testing.assert_allclose(_dense((nx, nx), *ol.nlp_hess(cfg, x, p, lf, lg)), H0,
-                                   atol=1e-12 * np.abs(H0).max())
-        _, _, gx0, gp0 = ref.grad(x, p, lf, lg)
         gx1, gp1 = ol.nlp_grad(cfg, x, p, lf, lg)
-        np.testing.assert_allclose(gx1, gx0, atol=1e-12 * np.abs(gx0).max())
-        np.testing.assert_allclose(gp1, gp0, atol=1e-12 * np.abs(gp0).max())
+        for f0, gf0, g0, J0, H0, gx0, gp0 in refs:
+            assert abs(f0 - f1) <= 1e-12 * abs(f0)
+            np.testing.assert_allclose(g1, g0, atol=1e-12)
+            np.testing.assert_allclose(ol.nlp_grad_f(cfg, x, p), gf0, atol=1e-12 * np.abs(gf0).max())
+            np.testing.assert_allclose(_dense((ng, nx), *ol.nlp_jac(cfg, x, p)), J0, atol=1e-12)
+            np.testing.assert_allclose(_dense((nx, nx), *ol.nlp_hess(cfg, x, p, lf, lg)), H0,
+                                       atol=1e-12 * np.abs(H0).max())
+            np.testing.assert_allclose(gx1, gx0, atol=1e-12 * np.abs(gx0).max())
+            np.testing.assert_allclose(gp1, gp0, atol=1e-12 * np.abs(gp0).max())
 
 
 def test_dims_generalise_in_N():
