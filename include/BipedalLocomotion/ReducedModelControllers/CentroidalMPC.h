@@ -80,7 +80,9 @@ public:
         if (!ptr->getParameter("contact_force_symmetry_weight", m_cfg.contact_force_symmetry_weight)) m_cfg.contact_force_symmetry_weight = 0.0;
         double tol = 0;
         int maxit = 0;
-        if (ptr->getParameter("ipopt_tolerance", tol) && tol > 0) m_cfg.tolerance = tol < 1e-6 ? tol : 1e-6;  // never looser than parity needs
+        // never looser than parity needs: the ini value only when it is tighter than the library's default for this horizon (0: that default)
+        m_cfg.tolerance = 0.0;
+        if (ptr->getParameter("ipopt_tolerance", tol) && tol > 0 && tol < cmpc_default_tolerance(steps)) m_cfg.tolerance = tol;
         if (ptr->getParameter("ipopt_max_iteration", maxit) && maxit > 0) m_cfg.max_iterations = maxit;
         ptr->getParameter("is_warm_start_enabled", m_warm);
         // [CONTACT_i] groups, ordered like the reference's std::map (by contact name)

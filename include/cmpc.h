@@ -88,7 +88,7 @@ typedef struct {
 #define CMPC_INFO 8
 /* info[b] = { iterations, kkt_error = max(primal_inf, max t*z), mu, safeguards, primal_inf,
  * status (0 ok, 1 iteration budget exhausted, 2 factorisation failed or a residual that is not finite -- NaN/inf in P or
- * X0: IPOPT's "invalid number"), solve_cycles (shader clock),
+ * X0: IPOPT's "invalid number", 3 outside the supported NLP subset, see below), solve_cycles (shader clock),
  * last_step (max-norm of the last Newton step taken inside the loop, forces relative to the largest force) }.
  * kkt_error, mu and primal_inf are those of the last iterate whose residuals were evaluated: the iterate the
  * termination test accepted.  With final_extrapolation the returned x is one affine-scaling step beyond it.
@@ -98,9 +98,21 @@ typedef struct {
  * as a failed factorisation -- the pass is repeated once unchanged.  Tests, the soak tool and bench.py assert / report that this digit is zero).
  * iterations counts both passes of a restarted warm start: it can reach 2 x max_iterations. */
 
+/* The supported NLP subset.  The solver keeps a foot's bounding-box row only in swing stages (there it bounds the landing offset); the
+ * row of a stance stage is dropped as a constant or a duplicate.  That is exact when, for each foot c and stage k:
+ *   1. Gamma_c,k is exactly 0 or 1;
+ *   2. if foot c is in stance at every stage 0..k: R_k^T (current_c - nominal_c,k+1) lies in [lower_k - 1e-6, upper_k + 1e-6]
+ *      (otherwise the reference NLP is infeasible);
+ *   3. if stage k is in stance after a swing, k' being the last swing stage before it: R_k, nominal_c,k+1, lower_k and upper_k are
+ *      bit-equal to R_k', nominal_c,k'+1, lower_k' and upper_k' (the row is then a duplicate of the landing row).
+ * A problem that breaks the rule is not iterated: it comes back at once with status 3 and its initial iterate as x; the other problems
+ * of the batch are untouched.  cmpc_set_contacts / cmpc_set_contact_lists write schedules inside the subset. */
 void cmpc_default_config(cmpc_config* cfg);                      /* ergoCubGazeboV1 values, N=20 */
 int cmpc_dims(int horizon, int* n_x, int* n_p, int* n_g, int* nnz_jac, int* nnz_hess);
 
+/* the tolerance cmpc_create uses when cmpc_config.tolerance <= 0: 1e-6 up to N = 20, 3e-7 beyond (parity with the float64 solve
+ * needs it).  A caller mapping the reference's ipopt_tolerance passes it only when it is tighter than this, and 0 otherwise. */
+double cmpc_default_tolerance(int horizon);
 int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out);
 int cmpc_destroy(cmpc_handle h);
 const char* cmpc_last_error(cmpc_handle h);                       /* h may be NULL */

@@ -146,6 +146,37 @@ static void setup(ws* w, const cmpc_nlp_cfg* cfg, const PREAL* p)
         }
 }
 
+/* the supported NLP subset (include/cmpc.h, status 3): Gamma binary; a stance stage's box row -- dropped by the stage structure -- a constant
+ * inside [lo - 1e-6, up + 1e-6] while the foot has been in stance since stage 0, and after a landing bit-equal to the last swing stage's */
+static int outside_subset(const ws* w)
+{
+    const int N = w->N;
+    const PREAL* p = w->p;
+    int c, k, j, i, a;
+    for (c = 0; c < 2; ++c)
+        for (k = 0; k < N; ++k) {
+            const REAL g = gam_of(w, c, k);
+            int kp = -1;
+            if (g == (REAL)0) continue;
+            if (g != (REAL)1) return 1;
+            for (j = k - 1; j >= 0 && kp < 0; --j) if (gam_of(w, c, j) < (REAL)0.5) kp = j;
+            if (kp < 0) {
+                const PREAL* R = p + w->L.p_R[c] + 9 * k;
+                for (i = 0; i < 3; ++i) {
+                    double v = 0;
+                    for (a = 0; a < 3; ++a)
+                        v += (double)RM(R, a, i) * ((double)p[w->L.p_cur[c] + a] - (double)p[w->L.p_nom[c] + 3 * (k + 1) + a]);
+                    if (!(v >= (double)p[w->L.p_lo[c] + 3 * k + i] - 1e-6 && v <= (double)p[w->L.p_up[c] + 3 * k + i] + 1e-6)) return 1;
+                }
+            } else if (memcmp(p + w->L.p_R[c] + 9 * k, p + w->L.p_R[c] + 9 * kp, 9 * sizeof(PREAL))
+                       || memcmp(p + w->L.p_nom[c] + 3 * (k + 1), p + w->L.p_nom[c] + 3 * (kp + 1), 3 * sizeof(PREAL))
+                       || memcmp(p + w->L.p_lo[c] + 3 * k, p + w->L.p_lo[c] + 3 * kp, 3 * sizeof(PREAL))
+                       || memcmp(p + w->L.p_up[c] + 3 * k, p + w->L.p_up[c] + 3 * kp, 3 * sizeof(PREAL)))
+                return 1;
+        }
+    return 0;
+}
+
 /* ---------------- stage functions ---------------- */
 /* dynamics s+ = phi_k(s,u); optionally the Jacobians A (15x15), B (15x30), row-major */
 static void dyn(const ws* w, int k, const REAL* s, const REAL* u, REAL* sn, MREAL* A, MREAL* B)
@@ -804,6 +835,12 @@ int FN(cmpc_ref_solve_one)(const cmpc_nlp_cfg* cfg, const cmpc_ipm_opts* opt, co
     if (!w || N > NMAX) { free(w); return -1; }
     setup(w, cfg, p);
     init_iterate(w, x0, (REAL)opt->mu_init);
+    if (outside_subset(w)) {   /* not iterated: the initial iterate, status 3 (as the HIP kernel) */
+        export_x(w, x);
+        if (info) { info[0] = 0; info[1] = 0; info[2] = opt->mu_init; info[3] = 0; info[4] = 0; info[5] = 3; }
+        free(w);
+        return 3;
+    }
     for (k = 0; k < N; ++k) for (i = 0; i < NI; ++i) nrow += row_active(w, k, i);
     for (it = 0; it < opt->max_iter; ++it) {
         REAL ap, ad, tau, lmax = 1, mu_aff = 0, sigma, mu_t;

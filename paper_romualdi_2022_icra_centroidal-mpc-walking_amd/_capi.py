@@ -60,7 +60,7 @@ EXPORTS = [
     "cmpc_contacts_sample_device", "cmpc_set_contact_lists", "cmpc_contacts_adjust", "cmpc_contacts_adjust_device",
     "cmpc_write_state_device", "cmpc_shift_solution_device", "cmpc_eval_nlp_grad_device", "cmpc_solve_device_warm", "cmpc_set_warm_policy",
     "cmpc_get_parameters", "cmpc_get_parameters_device", "cmpc_allgather_compact_device", "cmpc_sq_pass_barriers",
-    "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device",
+    "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device", "cmpc_default_tolerance",
 ]
 
 _lib = None
@@ -84,6 +84,8 @@ def lib():
         L.cmpc_default_config.argtypes = [C.POINTER(CmpcConfig)]
         L.cmpc_default_config.restype = None
         L.cmpc_dims.argtypes = [C.c_int, ip, ip, ip, ip, ip]
+        L.cmpc_default_tolerance.argtypes = [C.c_int]
+        L.cmpc_default_tolerance.restype = C.c_double
         L.cmpc_create.argtypes = [C.POINTER(CmpcConfig), C.c_int, C.c_int, C.POINTER(vp)]
         L.cmpc_destroy.argtypes = [vp]
         L.cmpc_last_error.argtypes = [vp]

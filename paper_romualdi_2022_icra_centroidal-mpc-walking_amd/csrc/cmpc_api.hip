@@ -143,6 +143,9 @@ const char* cmpc_last_error(cmpc_handle h) { return h ? h->err.c_str() : g_err.c
 int cmpc_batch(cmpc_handle h) { return h ? h->B : 0; }
 void* cmpc_stream(cmpc_handle h) { return h ? (void*)h->stream : nullptr; }
 
+// The one statement of the default tolerance rule (include/cmpc.h); the reasons are at its use in cmpc_create.
+double cmpc_default_tolerance(int horizon) { return horizon > 20 ? 3e-7 : 1e-6; }
+
 int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out)
 {
     if (!cfg || !out || batch < 1) return fail(nullptr, CMPC_ERR_ARG, "cmpc_create: null argument or batch < 1");
@@ -161,12 +164,12 @@ int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out)
     // complementarity products that still lag above the barrier floor at termination (max t z <= tolerance), and it grows with the number of stages behind the
     // first knots.  Config 5 (N = 30), worst of 5 unseen seeds x 512 problems against the float64 oracle (profiles/r04_accuracy_sweep.txt), barrier floor 5e-8:
     // tolerance 1e-6 -> 1.05e-4 (round 3), 5e-7 -> 9.3e-5, 4e-7 -> 9.3e-5, 3e-7 -> 6.8e-5 at 8.57 / 8.95 / 9.08 / 9.24 iterations on the mean.
-    if (!(h->cfg.tolerance > 0)) h->cfg.tolerance = h->cfg.horizon > 20 ? 3e-7 : 1e-6;
+    if (!(h->cfg.tolerance > 0)) h->cfg.tolerance = cmpc_default_tolerance(h->cfg.horizon);
     if (!(h->cfg.step_tolerance > 0)) h->cfg.step_tolerance = 100.0 * h->cfg.tolerance;
     // 0.05 x tolerance: the same iteration counts as tolerance / 10 (the barrier decreases superlinearly at the end)
     // at 0.7 x the sqrt(mu) bias of the nearly degenerate rows; float32 factorisations start to fail at 2e-8 (8 of 512
     // problems of config 5), 1e-8 loses most of config 3
-    // ... so the default floor never goes below 5e-8, whatever the tolerance (N > 20: tolerance 5e-7, floor 5e-8)
+    // ... so the default floor never goes below 5e-8, whatever the tolerance (N > 20: tolerance 3e-7, floor 5e-8)
     if (!(h->cfg.mu_min > 0)) h->cfg.mu_min = std::max(0.05 * h->cfg.tolerance, 5e-8);
     if (!(h->cfg.gravity > 0)) h->cfg.gravity = 9.80665;
     h->B = batch;
@@ -407,13 +410,18 @@ static int ensure_buffers(cmpc_handle h)
 
 static int check_status(cmpc_handle h, const std::vector<float>& info)
 {
-    int bad = 0, first = -1;
-    for (int b = 0; b < h->B; ++b)
-        if (info[(size_t)b * CMPC_INFO_N + 5] != 0.f) { if (first < 0) first = b; ++bad; }
+    int bad = 0, first = -1, outside = 0, first_out = -1;
+    for (int b = 0; b < h->B; ++b) {
+        const float st = info[(size_t)b * CMPC_INFO_N + 5];
+        if (st != 0.f) { if (first < 0) first = b; ++bad; }
+        if (st == 3.f) { if (first_out < 0) first_out = b; ++outside; }
+    }
     if (bad) {
-        char buf[160];
-        std::snprintf(buf, sizeof(buf), "%d of %d problems did not converge (first: %d, status %d, kkt %.3g)", bad, h->B, first,
-                      (int)info[(size_t)first * CMPC_INFO_N + 5], info[(size_t)first * CMPC_INFO_N + 1]);
+        char buf[240];
+        int n = std::snprintf(buf, sizeof(buf), "%d of %d problems did not converge (first: %d, status %d, kkt %.3g)", bad, h->B, first,
+                              (int)info[(size_t)first * CMPC_INFO_N + 5], info[(size_t)first * CMPC_INFO_N + 1]);
+        if (outside && n > 0 && n < (int)sizeof(buf))
+            std::snprintf(buf + n, sizeof(buf) - n, "; %d with status 3, outside the supported NLP subset (first: %d)", outside, first_out);
         return fail(h, CMPC_ERR_NOT_CONVERGED, buf);
     }
     return CMPC_OK;

@@ -348,6 +348,40 @@ __device__ inline bool qfree_compute(const Ctx& c, int k, int m)
     return gam_of(c, ct, k) < 0.5f && (hi - lo) > 1e-9f;
 }
 __device__ inline bool qfree(const Ctx& c, int k, int m) { return (c.qmask[k] >> m) & 1; }
+// the NLP subset the solver supports (include/cmpc.h, status 3), foot ct at stage k: Gamma binary; a stance stage drops its box row, which is a
+// constant inside [lo, up] while the foot has been in stance since stage 0, and after a landing a duplicate of the last swing stage's row
+__device__ inline bool outside_subset(const Ctx& c, int ct, int k)
+{
+    const float g = gam_of(c, ct, k);
+    if (g == 0.f) return false;
+    if (g != 1.f) return true;
+    int kp = -1;
+    for (int j = k - 1; j >= 0 && kp < 0; --j) if (gam_of(c, ct, j) < 0.5f) kp = j;
+    const float* R = c.sp + c.L.pR(ct) + 9 * k;
+    const float* nom = c.sp + c.L.pNom(ct) + 3 * (k + 1);
+    const float* lo = c.sp + c.L.pLo(ct) + 3 * k;
+    const float* up = c.sp + c.L.pUp(ct) + 3 * k;
+    if (kp < 0) {
+        const float* cur = c.sp + c.L.pCur(ct);
+        bool out = false;
+        for (int i = 0; i < 3; ++i) {
+            float v = 0.f;
+            for (int a = 0; a < 3; ++a) v += Rm(R, a, i) * (cur[a] - nom[a]);
+            out = out || !(v >= lo[i] - 1e-6f && v <= up[i] + 1e-6f);
+        }
+        return out;
+    }
+    const float* Rp = c.sp + c.L.pR(ct) + 9 * kp;
+    const float* nomp = c.sp + c.L.pNom(ct) + 3 * (kp + 1);
+    const float* lop = c.sp + c.L.pLo(ct) + 3 * kp;
+    const float* upp = c.sp + c.L.pUp(ct) + 3 * kp;
+    bool diff = false;
+    for (int a = 0; a < 9; ++a) diff = diff || __float_as_int(R[a]) != __float_as_int(Rp[a]);
+    for (int i = 0; i < 3; ++i)
+        diff = diff || __float_as_int(nom[i]) != __float_as_int(nomp[i]) || __float_as_int(lo[i]) != __float_as_int(lop[i])
+               || __float_as_int(up[i]) != __float_as_int(upp[i]);
+    return diff;
+}
 __device__ inline float qlo(const Ctx& c, int k, int m) { return c.sp[c.L.pLo(m / 3) + 3 * k + m % 3]; }
 __device__ inline float qhi(const Ctx& c, int k, int m) { return c.sp[c.L.pUp(m / 3) + 3 * k + m % 3]; }
 
@@ -3142,8 +3176,9 @@ __device__ __attribute__((noinline)) bool phase_finish(lds_t lds, int Nrt, float
 // ---- the remaining pieces of the driver, out of line for the same reason as the passes above: the kernel body below is control flow
 // over a dozen scalars and holds no LDS map of its own (with the ~45 pointers of Ctx live across every phase call the 168-register
 // variants spilled SGPRs into VGPR lanes and those VGPRs into scratch memory, reloaded in front of every use: -1.7 % on configs 3-5) ----
+// returns 1 (workgroup-uniform) when the problem lies outside the supported NLP subset (include/cmpc.h: status 3)
 template <int NT, int NC, bool FG>
-__device__ __attribute__((noinline)) void phase_setup(lds_t lds, int Nrt, float* fg_base, const float* gp)
+__device__ __attribute__((noinline)) int phase_setup(lds_t lds, int Nrt, float* fg_base, const float* gp)
 {
     CMPC_PHASE_PROLOGUE;
     float* spw = const_cast<float*>(c.sp);
@@ -3157,6 +3192,7 @@ __device__ __attribute__((noinline)) void phase_setup(lds_t lds, int Nrt, float*
     for (int e = tid; e < ID_STRIPS; e += NT) c.idstrip[e] = (e % ID_STRIP_LEN) == 32 + e / ID_STRIP_LEN ? 1.f : 0.f;
     // (zero blocks of the factor records: LDS was zeroed by the kernel; HBM scratch is zeroed once, at cmpc_create)
     for (int e = tid; e < c.L.np(); e += NT) spw[e] = gp[e];
+    if (tid == 0) c.flag[0] = 0;   // (the failure word of the backward passes, which reset it themselves: here the subset flag)
     __syncthreads();
     if (tid < N) {
         int m = 0;
@@ -3164,7 +3200,9 @@ __device__ __attribute__((noinline)) void phase_setup(lds_t lds, int Nrt, float*
         for (int q = 0; q < NQ; ++q) m |= qfree_compute(c, tid, q) ? (1 << q) : 0;
         c.qmask[tid] = m;
     }
+    if (tid < 2 * N && outside_subset(c, tid / N, tid % N)) c.flag[0] = 1;
     __syncthreads();
+    return __builtin_amdgcn_readfirstlane(c.flag[0]);
 }
 
 // initial iterate from x0 (or, cold: the cold start of SURVEY 8d built in place: CoM at com0, feet at nominal, f_z = g/8); returns the
@@ -3510,14 +3548,19 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
     float* const fg_base = FG ? kp.scratch + (size_t)b * kp.scratch_stride : nullptr;
     const CmpcIdx L{N};
     __syncthreads();
-    phase_setup<NT, NC, FG>(lds, N, fg_base, kp.P + (size_t)b * L.np());
+    const bool outside = phase_setup<NT, NC, FG>(lds, N, fg_base, kp.P + (size_t)b * L.np()) != 0;
     // Two passes at most: a warm-started solve (shifted previous solution) that exhausts its iteration budget is started
     // again from the cold start -- rare (a landing or lift-off tick, 1 in ~60000 solves of a walking roll-out) and cheaper than
     // failing the tick, which is all the caller could do (CentroidalMPCBlock.cpp:615-619 aborts).
     int status = 1, sg = 0, it_total = 0;   // sg: the safeguard word of info[3] (include/cmpc.h)
     float err = 0.f, ep = 0.f, mu_cur = 0.f, step_out = 0.f, step_prev = 0.f;
     float* const dq = kp.duals ? kp.duals + (size_t)b * (NS * (N + 1) + 2 * NI * N) : nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
+    if (outside) {
+        // outside the supported NLP subset (include/cmpc.h): no iteration; the initial iterate goes out with status 3
+        phase_init<NT, NC, FG>(lds, N, fg_base, kp.X0 + (size_t)b * L.nx(), dq, 0, kp.mu_init, kp.t_floor);
+        status = 3;
+    }
+    for (int pass = 0; pass < 2 && !outside; ++pass) {
         const float mu_init = pass ? 0.1f : kp.mu_init, t_floor = pass ? 1e-2f : kp.t_floor, mu_adapt = pass ? 3.5f : kp.mu_adapt;
         step_out = step_prev = 0.f;
         const bool use_duals = kp.warm && kp.warm_duals && kp.duals;

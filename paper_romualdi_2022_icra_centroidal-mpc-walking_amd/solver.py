@@ -38,7 +38,10 @@ def _c_config(cfg: CentroidalMPCConfig, tolerance=None, mu_min=None, max_iterati
     # the reference's ipopt_tolerance (1e-4 / 1e-2) is looser than the parity target; the GPU
     # solver always converges at least to 1e-6 so that its answer is reproducible to 1e-4
     # (0: the library's default -- 1e-6 up to N = 20, 3e-7 beyond; step tolerance and barrier floor follow it)
-    c.tolerance = tolerance if tolerance is not None else (cfg.ipopt_tolerance if cfg.ipopt_tolerance < 5e-7 else 0.0)
+    # (the ini value only when it is tighter than that default, as in the C++ facade)
+    if tolerance is None:
+        tolerance = cfg.ipopt_tolerance if 0 < cfg.ipopt_tolerance < _capi.lib().cmpc_default_tolerance(cfg.N) else 0.0
+    c.tolerance = tolerance
     c.step_tolerance = step_tolerance if step_tolerance is not None else 0.0
     c.mu_init = mu_init if mu_init is not None else 0.0   # <= 0: per problem, from its initial infeasibility
     c.mu_min = mu_min if mu_min is not None else 0.0

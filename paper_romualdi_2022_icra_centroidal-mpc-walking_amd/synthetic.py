@@ -67,25 +67,36 @@ def _walking_lists(cfg, swing_start, swing_len, step=0.1):
     return {cfg.contacts[0].contact_name: left, cfg.contacts[1].contact_name: right}
 
 
+def walking_push(cfg, B, push_N, push_stages, seed, swing=None, shard=None):
+    """Walking problems at cfg's own horizon, sampling time and weights: the left foot lifts at knot swing[0] for swing[1] knots
+    (default N // 3, N // 3) and lands 0.1 m ahead; perturbed initial state; an external push U(-push_N, push_N) N in x and y
+    (normalised by ROBOT_MASS) over stages 0 .. push_stages - 1.  Random draws in the order com0, dcom0, h0, push.
+    shard=(lo, hi): only problems [lo, hi) of the B-problem batch are built (the random draws are those of the whole batch, so a
+    shard equals the same rows of the unsharded batch bit for bit)."""
+    N = cfg.N
+    if swing is None:
+        swing = (N // 3, N // 3)
+    rng = np.random.default_rng(seed)
+    com0, dcom0, h0 = _perturbed_state(rng, B, (0.0, 0.0, 0.7))
+    push = rng.uniform(-push_N, push_N, (B, 2)) / ROBOT_MASS
+    if shard is not None:
+        lo, hi = shard
+        com0, dcom0, h0, push = com0[lo:hi], dcom0[lo:hi], h0[lo:hi], push[lo:hi]
+        B = hi - lo
+    sched = _tile(sample_schedule(cfg, _walking_lists(cfg, *swing)), B)
+    ref = np.broadcast_to(np.array([0.0, 0.0, 0.7]), (B, N + 1, 3)).copy()
+    f_ext = np.zeros((B, N, 3))
+    f_ext[:, :push_stages, :2] = push[:, None, :]
+    return _finish(cfg, sched, com0, dcom0, h0, ref, np.zeros((B, N + 1, 3)), f_ext)
+
+
 def config3_external_push(B=4096, N=20, seed=1, shard=None):
     """Walking schedule with a swing phase inside the horizon (left Gamma = 1x6, 0x8, 1x6) so the
     step adjustment is active, plus an external push U(-50,50) N in x,y over the first 0.2 s.
     shard=(lo, hi): only problems [lo, hi) of the B-problem batch are built (the random draws are those
     of the whole batch, so a shard equals the same rows of the unsharded batch bit for bit)."""
     cfg = _cfg.ergocub_gazebo_v1(N, 0.06)
-    rng = np.random.default_rng(seed)
-    com0, dcom0, h0 = _perturbed_state(rng, B, (0.0, 0.0, 0.7))
-    push = rng.uniform(-50.0, 50.0, (B, 2)) / ROBOT_MASS
-    if shard is not None:
-        lo, hi = shard
-        com0, dcom0, h0, push = com0[lo:hi], dcom0[lo:hi], h0[lo:hi], push[lo:hi]
-        B = hi - lo
-    sched = _tile(sample_schedule(cfg, _walking_lists(cfg, 6, 8)), B)
-    ref = np.broadcast_to(np.array([0.0, 0.0, 0.7]), (B, N + 1, 3)).copy()
-    f_ext = np.zeros((B, N, 3))
-    nk = int(np.ceil(0.2 / cfg.sampling_time))
-    f_ext[:, :nk, :2] = push[:, None, :]
-    return _finish(cfg, sched, com0, dcom0, h0, ref, np.zeros((B, N + 1, 3)), f_ext)
+    return walking_push(cfg, B, 50.0, int(np.ceil(0.2 / cfg.sampling_time)), seed, swing=(6, 8), shard=shard)
 
 
 def config4_monte_carlo(B=65536, N=20, seed=2, shard=None):
@@ -98,7 +109,13 @@ def config5_footstep_candidates(B=8192, N=30, seed=3):
     """ergoCubGazeboV1, horizon 30.  The reference's MANN generator cannot run here (no onnxruntime,
     model blob missing), so candidate schedules are synthetic: step length U(0,0.15) m, width
     0.16+-0.02 m, yaw U(-0.2,0.2) rad, step duration 0.6-0.9 s, double support 0.12-0.24 s."""
-    cfg = _cfg.ergocub_gazebo_v1(N, 0.06)
+    return footstep_candidates(_cfg.ergocub_gazebo_v1(N, 0.06), B, seed)
+
+
+def footstep_candidates(cfg, B, seed):
+    """config 5's candidate schedules (yawed footsteps, R != I) at cfg's own horizon, sampling time and weights: the horizon is
+    N x dt long, so a robot with a shorter horizon sees a shortened form of the same schedules."""
+    N = cfg.N
     rng = np.random.default_rng(seed)
     dt, t_end = cfg.sampling_time, N * cfg.sampling_time
     lists = []

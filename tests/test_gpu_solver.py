@@ -144,19 +144,9 @@ def test_every_shipped_horizon(N, dt, B):
     run-time-N variant; B = 400 > #CU takes the HBM-factor variant with run-time N (every horizon but 20 and 30, which have their own
     instantiations; 25 has its slacks and multipliers in HBM).  Walking problems with pushes, against the oracle."""
     cfg = cm.config.ergocub_gazebo_v1(N, dt)
-    base, P0, X00 = cm.synthetic.config3_external_push(B, N=N, seed=31 + N)
-    assert base.N == N
-    # config3's generator is written for dt = 0.06: rebuild the schedule for this sampling time through the class-level generator
-    from cmpc_amd.synthetic import _walking_lists, _tile, _finish, ROBOT_MASS
-    from cmpc_amd.contacts import sample_schedule
-    rng = np.random.default_rng(31 + N)
-    sched = _tile(sample_schedule(cfg, _walking_lists(cfg, N // 3, N // 3)), B)
-    com0 = np.array([0.0, 0.0, 0.7]) + rng.uniform(-0.02, 0.02, (B, 3))
-    dcom0, h0 = rng.uniform(-0.1, 0.1, (B, 3)), rng.uniform(-0.05, 0.05, (B, 3))
-    ref = np.broadcast_to(np.array([0.0, 0.0, 0.7]), (B, N + 1, 3)).copy()
-    f_ext = np.zeros((B, N, 3))
-    f_ext[:, :2, :2] = (rng.uniform(-30.0, 30.0, (B, 2)) / ROBOT_MASS)[:, None, :]
-    _, P, X0 = _finish(cfg, sched, com0, dcom0, h0, ref, np.zeros((B, N + 1, 3)), f_ext)
+    assert cm.synthetic.config3_external_push(2, N=N)[0].N == N
+    # config3's schedule at this sampling time: swing from knot N // 3 for N // 3 knots, 30 N pushes over two stages
+    _, P, X0 = cm.synthetic.walking_push(cfg, B, 30.0, 2, 31 + N)
     P32, X032 = P.astype(np.float32), X0.astype(np.float32)
     s = cm.BatchSolver(cfg, B)
     X, info, rc = s.solve_host(P32, X032)
@@ -527,3 +517,38 @@ def test_tail_polish_only_moves_the_tail(monkeypatch):
     # the polish is about the FORCES of the last knots (unloaded corners at the apex of their friction pyramid); the CoM velocity it leaves where the
     # tolerance put it: since the default tolerance beyond N = 20 is 3e-7 that is 3..5e-5 with and without the polish (it used to improve with it at 1e-6)
     assert wb["forces"] < wa["forces"] and wb["dcom"] < max(wa["dcom"], 0.6 * parity.TOL), (wa, wb)
+
+
+@pytest.mark.parametrize("B", [5, 1024])
+def test_problems_outside_the_supported_subset_are_flagged_not_solved(B):
+    """include/cmpc.h states the NLP subset the kernel supports.  A raw P through cmpc_solve_device with one problem per violation (Gamma = 0.5 at
+    one stage; a foot held 5 cm outside its box; a nominal position moved by 2 cm inside a stance phase): each comes back at once with status 3,
+    no iteration and a finite x; every other problem bit-identical, in x and in iterations, to a clean solve (resident variant at B = 5,
+    HBM-factor variant at B = 1024)."""
+    import torch
+    cfg, P, X0 = cm.synthetic.config3_external_push(B, seed=23)
+    P32, X032 = P.astype(np.float32), X0.astype(np.float32)
+    s = cm.BatchSolver(cfg, B)
+    dX1, dI1 = s.solve_device(torch.from_numpy(P32).cuda(), torch.from_numpy(X032).cuda())
+    torch.cuda.synchronize()
+    X1, info1 = dX1.cpu().numpy(), dI1.cpu().numpy()
+    assert (info1[:, 5] == 0).all()
+    bad = {"gamma": 0, "held": B // 2, "nominal": B - 1}
+    Pb = P32.copy()
+    for which, b in bad.items():
+        Pb[b] = parity.break_subset(cfg.N, P32[b], which)
+    dX2, dI2 = s.solve_device(torch.from_numpy(Pb).cuda(), torch.from_numpy(X032).cuda())
+    torch.cuda.synchronize()
+    X2, info2 = dX2.cpu().numpy(), dI2.cpu().numpy()
+    rows = list(bad.values())
+    assert (info2[rows, 5] == 3).all() and (info2[rows, 0] <= 1).all(), info2[rows]
+    assert np.isfinite(X2[rows]).all()
+    keep = np.setdiff1d(np.arange(B), rows)
+    assert (info2[keep, 5] == 0).all()
+    np.testing.assert_array_equal(X2[keep], X1[keep])
+    np.testing.assert_array_equal(info2[keep, 0], info1[keep, 0])
+    # the host entry point says so: CMPC_ERR_NOT_CONVERGED, and the error text names status 3
+    _, info3, rc = s.solve_host(Pb, X032)
+    assert rc == -3 and "status 3" in s.last_error and "outside the supported NLP subset" in s.last_error, s.last_error
+    np.testing.assert_array_equal(info3[:, 5], info2[:, 5])
+    s.close()

@@ -201,3 +201,58 @@ def test_structured_solver_equals_the_independent_solver_on_fresh_problems(gen, 
         assert r["status"] == 0
         e = parity.errors(cfg.N, P[b], Xs[b], r["x"])
         assert e["com"] < 1e-6 and e["dcom"] < 1e-5 and e["force0"] < 1e-6 and e["forces"] < 2e-5 and e["pos"] < 5e-6, e
+
+
+@pytest.mark.parametrize("robot", ["ergoCubSN000", "ergoCubSN001", "iCubGazeboV3"])
+def test_structured_solver_equals_the_independent_solver_with_footstep_boxes_active(robot, golden_dir):
+    """The same check in the regime the GPU robot matrix (tests/test_gpu_robots.py) relies on: the shipped robots' own weights (w_pos = 50 / 200,
+    not ergoCubGazeboV1's 2e3) and 150 N pushes put the landing on a face of its bounding box, so the q-bound rows are active at the optimum.
+    Four problems per robot whose float64 solution sits on a face, against the stage-agnostic generic solver."""
+    cfg = cm.config.from_ini(open(os.path.join(golden_dir, "ini", f"{robot}.ini")).read())
+    _, P, X0 = cm.synthetic.walking_push(cfg, 32, 150.0, 3, 7)
+    P, X0 = P.astype(np.float32).astype(np.float64), X0.astype(np.float32).astype(np.float64)
+    oc = problem_nlp.oracle_cfg(cfg)
+    Xs, info = ol.ref_solve_batch(oc, P, X0, ol.ipm_opts(tol=1e-9, mu_min=1e-10), nthreads=4)
+    assert (info[:, 5] == 0).all()
+    on_face = [b for b in range(32) if parity.box_faces(cfg.N, P[b], Xs[b])][:4]
+    assert len(on_face) == 4
+    for b in on_face:
+        lb, ub = problem_nlp.bounds(cfg, P[b])
+        r = ipm_generic.solve(oc, P[b], lb, ub, X0[b], tol=1e-9, max_iter=400)
+        assert r["status"] == 0
+        assert parity.box_faces(cfg.N, P[b], r["x"], tol=1e-6) == parity.box_faces(cfg.N, P[b], Xs[b]), b
+        e = parity.errors(cfg.N, P[b], Xs[b], r["x"])
+        assert e["com"] < 1e-6 and e["dcom"] < 1e-5 and e["force0"] < 1e-6 and e["forces"] < 2e-5 and e["pos"] < 5e-6, (b, e)
+
+
+
+@pytest.mark.parametrize("which", ["gamma", "held", "nominal"])
+def test_problems_outside_the_supported_subset_get_status_3(which):
+    """include/cmpc.h states the NLP subset the stage-structured solvers support; ipm_ref.c flags a problem outside it with status 3 and
+    returns the initial iterate, as the HIP kernel does.  Its neighbours in the batch are solved as before."""
+    cfg, P, X0 = cm.synthetic.config3_external_push(3, seed=5)
+    P, X0 = P.astype(np.float32).astype(np.float64), X0.astype(np.float32).astype(np.float64)
+    assert not any(parity.outside_subset(cfg.N, P[b]) for b in range(3))
+    Pb = P.copy()
+    Pb[1] = parity.break_subset(cfg.N, P[1], which)
+    assert parity.outside_subset(cfg.N, Pb[1])
+    oc = problem_nlp.oracle_cfg(cfg)
+    opts = ol.ipm_opts(tol=1e-9, mu_min=1e-10)
+    X1, info1 = ol.ref_solve_batch(oc, P, X0, opts)
+    X2, info2 = ol.ref_solve_batch(oc, Pb, X0, opts)
+    assert (info1[:, 5] == 0).all()
+    assert info2[1, 5] == 3 and info2[1, 0] == 0 and np.isfinite(X2[1]).all()
+    np.testing.assert_array_equal(X2[[0, 2]], X1[[0, 2]])
+
+
+def test_a_held_foot_outside_its_box_is_infeasible_for_the_reference_nlp():
+    """Status 3 for a foot held outside its box matches the reference: with every bounding-box row kept (ipm_generic states the NLP as CasADi
+    hands it to IPOPT) the problem has no feasible point -- the primal infeasibility stays far above any tolerance."""
+    cfg, P, X0 = cm.synthetic.config3_external_push(1, seed=5)
+    p = parity.break_subset(cfg.N, P[0].astype(np.float32).astype(np.float64), "held")
+    oc = problem_nlp.oracle_cfg(cfg)
+    lb, ub = problem_nlp.bounds(cfg, p)
+    r = ipm_generic.solve(oc, p, lb, ub, X0[0], tol=1e-9, max_iter=100)
+    _, g = ol.nlp_fg(oc, r["x"], p)
+    prim = max(np.maximum(g - ub, 0).max(), np.maximum(lb - g, 0).max())
+    assert r["status"] != 0 and prim > 1e-3, (r["status"], prim)
