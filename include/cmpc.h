@@ -235,6 +235,25 @@ int cmpc_allgather_compact_device(cmpc_handle h, void* nccl_comm, int world_size
  * ContactList::getActiveContact(t) = the contact with activation <= t < deactivation; getNextContact(t) = the first
  * one that activates after t (the two queries the reference makes, CentroidalMPCBlock.cpp:44, :61, :69). */
 
+/* ContactPhaseList::forceSampleTime(m_dT), CentroidalMPCBlock.cpp:586-592: the reference snaps the planner's lists to the MPC grid on every
+ * tick before the merge; the merge and the sampling below assume times on the grid.  The rule is BipedalLocomotionFramework's, whose source is not
+ * in the reference tree: PARITY UNPINNED.  Ours, on integer nanoseconds as the reference's clock (std::chrono::nanoseconds):
+ *   t_ns = llround(t 1e9), dt_ns = llround(dt 1e9);
+ *   every activation and deactivation time goes to the nearest multiple of dt_ns counted from time 0, ties to the later one:
+ *     q = floor((2 t_ns + dt_ns) / (2 dt_ns)) (floor division: right for negative times too), snapped time (q dt_ns) 1e-9 s;
+ *   a time on the grid (t_ns % dt_ns == 0) keeps its bits: snapping an on-grid list changes nothing;
+ *   |t| >= 1e9 s (the "never" of an open-ended contact) is kept;
+ *   poses are not touched; the rounding is monotone, so the order of a foot's contacts and their non-overlap are kept.
+ * Failure (the reference's `return false`, :588-592): a contact of positive duration whose snapped duration is zero, or a time that is not finite:
+ * ok[b] = 0 for that problem (its times are still written: the finite ones snapped, the others unchanged), the rest of the batch is processed; the
+ * function then returns CMPC_ERR_ARG.  Entries m >= n[b][c] are copied unchanged.  out_t may be t (in place).  dt <= 0 (or below 1 ns, or >= 1e9 s)
+ * and a list length outside 0..max_contacts are argument errors.  Host buffers; no handle, no GPU. */
+int cmpc_contacts_force_sample_time(int batch, int max_contacts, double dt, const double* t, const int* n, double* out_t, int* ok /* [B] or NULL */);
+/* same on the device (one thread per problem, foot and contact; bit-equal to the host); dOk[B] or NULL; dOutT may be dT; asynchronous on `stream`
+ * (NULL: the handle's).  A list length outside 0..max_contacts gives dOk = 0 and that foot's entries are neither read nor written. */
+int cmpc_contacts_force_sample_time_device(cmpc_handle h, int max_contacts, double dt, const double* dT, const int* dN, double* dOutT, int* dOk,
+                                           void* stream);
+
 /* updateContactPhaseList, CentroidalMPCBlock.cpp:32-110 (call site :594-607): out = the planner's future contacts
  * (activation > now), preceded -- when the MPC's previous list has an active contact -- by that contact with the pose
  * the MPC gave it and the timing of the planner's active contact (:79-82).  Where the planner has no active contact
@@ -278,9 +297,10 @@ int cmpc_contacts_adjust_device(cmpc_handle h, int max_contacts, double now, con
 int cmpc_write_state_device(cmpc_handle h, const float* dState, const float* dWrench, float* dP, void* stream);
 
 /* ONE receding-horizon tick of the whole batch as ONE call: what CentroidalMPCBlock::advance does between two solves
- * (CentroidalMPCBlock.cpp:594-626) and WholeBodyQPBlock::advance after it (WholeBodyQPBlock.cpp:1083-1150), chained on
+ * (CentroidalMPCBlock.cpp:586-626) and WholeBodyQPBlock::advance after it (WholeBodyQPBlock.cpp:1083-1150), chained on
  * `stream` (NULL: the handle's) without returning to the host in between:
- *   cmpc_contacts_merge_device (updateContactPhaseList :594-607) -> cmpc_contacts_sample_device (setContactPhaseList :609)
+ *   [io->force_sample_time: cmpc_contacts_force_sample_time_device (forceSampleTime :586-592) on the planner's lists, or on dList* on the first tick]
+ *   -> cmpc_contacts_merge_device (updateContactPhaseList :594-607) -> cmpc_contacts_sample_device (setContactPhaseList :609)
  *   -> cmpc_write_state_device (setState :407) -> cmpc_shift_solution_device (is_warm_start_enabled; warm != 0)
  *   -> cmpc_solve_device[_warm] (advance :615) -> cmpc_contacts_adjust_device (getOutput :626) -> cmpc_plant_step_device.
  * Every step is what the entry point of that name computes, with the same argument checks; the steps in front of the solve are ONE launch and so are the
@@ -310,6 +330,13 @@ typedef struct cmpc_tick_io {
      * the first one plan_t_offset seconds before `now`) -- the tick then writes comRef / hRef of dP itself (setReferenceTrajectory, CentroidalMPCBlock.cpp:525-579).
      * Both NULL: the reference rows of dP are the caller's. */
     const float* dPlanCom; const float* dPlanH; int plan_knots; double plan_dt, plan_t_offset, robot_mass, com_height;
+    /* 0 (a zero-initialised struct): the planner's times are used as given.  != 0: forceSampleTime (the rule at cmpc_contacts_force_sample_time, grid
+     * = the handle's sampling_time) first.  Merge ticks: the planner's lists are snapped (the caller's dPlanT is not written) before the merge; a foot whose
+     * snap fails is treated as an empty planner list: dOk = 0, its merged list is empty, dLand = -2, as a failed merge.  First tick: dListT is snapped in
+     * place (the reference passes the snapped list on) and dOk IS written; a failed foot's dListN becomes 0 and dLand = -2.  Up to max_contacts = 16
+     * the snap runs inside the front kernel (three launches per tick); beyond, one launch of the standalone kernel comes first (four launches; merge
+     * ticks snap into a buffer the handle allocates on first use). */
+    int force_sample_time;
 } cmpc_tick_io;
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream);
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm

@@ -44,7 +44,7 @@ class CmpcTickIO(C.Structure):
         "box_upper", "box_lower", "dState", "dWrench", "dP", "dX0", "dX", "dInfo", "dStateOut", "dZmp")] + [
         ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("zmp_half_x", C.c_double), ("zmp_half_y", C.c_double),
         ("dPlanCom", C.c_void_p), ("dPlanH", C.c_void_p), ("plan_knots", C.c_int), ("plan_dt", C.c_double), ("plan_t_offset", C.c_double),
-        ("robot_mass", C.c_double), ("com_height", C.c_double)]
+        ("robot_mass", C.c_double), ("com_height", C.c_double), ("force_sample_time", C.c_int)]
 
 
 FACTORS = {None: 0, "auto": 0, "lds": 1, "hbm": 2}   # cmpc_config.factor_storage
@@ -61,6 +61,7 @@ EXPORTS = [
     "cmpc_write_state_device", "cmpc_shift_solution_device", "cmpc_eval_nlp_grad_device", "cmpc_solve_device_warm", "cmpc_set_warm_policy",
     "cmpc_get_parameters", "cmpc_get_parameters_device", "cmpc_allgather_compact_device", "cmpc_sq_pass_barriers",
     "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device", "cmpc_default_tolerance",
+    "cmpc_contacts_force_sample_time", "cmpc_contacts_force_sample_time_device",
 ]
 
 _lib = None
@@ -119,6 +120,9 @@ def lib():
         d, i = C.c_double, C.c_int
         L.cmpc_contacts_merge.argtypes = [i, i, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmpc_contacts_merge_device.argtypes = [vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "cmpc_contacts_force_sample_time"):
+            L.cmpc_contacts_force_sample_time.argtypes = [i, i, d, vp, vp, vp, vp]
+            L.cmpc_contacts_force_sample_time_device.argtypes = [vp, i, d, vp, vp, vp, vp, vp]
         L.cmpc_contacts_sample.argtypes = [i, d, i, i, d, vp, vp, vp, vp, vp, vp, vp]
         L.cmpc_contacts_sample_device.argtypes = [vp, i, d, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmpc_set_contact_lists.argtypes = [vp, i, d, vp, vp, vp, vp, vp, vp]

@@ -200,3 +200,22 @@ def update_contact_phase_list(now: float, plan, mpc):
     if rc not in (0, -1):
         raise RuntimeError(f"cmpc_contacts_merge failed ({rc})")
     return (ot, op, on), ok.astype(bool)
+
+
+def force_sample_time(dt: float, t, n):
+    """ContactPhaseList::forceSampleTime(dT) (CentroidalMPCBlock.cpp:586-592) for a batch, through the C ABI (cmpc_contacts_force_sample_time): every
+    activation / deactivation time of t[B,2,M,2] to the nearest multiple of dt (integer nanoseconds from time 0, ties to the later one; on-grid times
+    and the 1e9 s "never" keep their bits -- the rule of include/cmpc.h).  Returns (snapped t, ok[B]): ok[b] is False where a contact of positive
+    duration collapses on the grid or a time is not finite (the reference's forceSampleTime returns false and the tick is aborted)."""
+    from . import _capi
+    tt, nn = np.ascontiguousarray(t, np.float64), np.ascontiguousarray(n, np.int32)
+    B, _, M, _ = tt.shape
+    assert nn.shape == (B, 2)
+    out = np.empty_like(tt)
+    ok = np.full(B, -1, np.int32)     # (an argument error writes nothing)
+    rc = _capi.lib().cmpc_contacts_force_sample_time(B, M, float(dt), _ptr(tt), _ptr(nn), _ptr(out), _ptr(ok))
+    if rc == -1 and (ok == -1).any():
+        raise ValueError(f"cmpc_contacts_force_sample_time: {_capi.lib().cmpc_last_error(None).decode()}")
+    if rc not in (0, -1):
+        raise RuntimeError(f"cmpc_contacts_force_sample_time failed ({rc})")
+    return out, ok.astype(bool)

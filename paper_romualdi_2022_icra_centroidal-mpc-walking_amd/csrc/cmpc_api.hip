@@ -36,7 +36,9 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, hipStream_t stream);
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, hipStream_t stream);
+extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
+                                             hipStream_t stream);
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
                                      const double* t, float* pose, const int* n, hipStream_t stream);
@@ -59,7 +61,10 @@ struct cmpc_handle_s {
     CmpcConsts* dConsts = nullptr;
     float* dScratch = nullptr;   // factor storage when the horizon's LDS image exceeds 160 KiB
     float* dBox = nullptr;       // bounding-box limits upper[2][3] | lower[2][3] of the schedule sampler
-    float* dDuals = nullptr;     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
+    float* dDuals = nullptr;
+    double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
+    int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
+    size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
     int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
     float hBox[12] = {0};
     bool box_set = false;
@@ -257,6 +262,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hXpin) hipHostFree(h->hXpin);
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -844,6 +850,46 @@ int cmpc_contacts_merge_device(cmpc_handle h, int max_contacts, double now, cons
     return CMPC_OK;
 }
 
+// forceSampleTime (CentroidalMPCBlock.cpp:586-592): dt in integer nanoseconds, or 0 if it is not a usable grid
+static long long snap_dt_ns(double dt)
+{
+    if (!(dt > 0) || !(dt < CMPC_TIME_NEVER)) return 0;
+    const long long dt_ns = llround(dt * 1e9);
+    return dt_ns >= 1 ? dt_ns : 0;
+}
+
+int cmpc_contacts_force_sample_time(int batch, int max_contacts, double dt, const double* t, const int* n, double* out_t, int* ok)
+{
+    const long long dt_ns = snap_dt_ns(dt);
+    if (batch < 1 || max_contacts < 1 || dt_ns < 1 || !t || !n || !out_t) return fail(nullptr, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time: bad argument");
+    const int M = max_contacts;
+    for (int e = 0; e < 2 * batch; ++e)
+        if (n[e] < 0 || n[e] > M) return fail(nullptr, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time: list length out of range");
+    int all = CMPC_OK;
+    for (int b = 0; b < batch; ++b) {
+        bool good = true;
+        for (int c = 0; c < 2; ++c) {
+            const size_t o = ((size_t)b * 2 + c) * M;
+            good = cmpc_force_sample_time_foot(t + 2 * o, n[2 * b + c], dt_ns, out_t + 2 * o) && good;
+            if (out_t != t) std::memcpy(out_t + 2 * (o + n[2 * b + c]), t + 2 * (o + n[2 * b + c]), sizeof(double) * 2 * (M - n[2 * b + c]));
+        }
+        if (ok) ok[b] = good ? 1 : 0;
+        if (!good) all = CMPC_ERR_ARG;
+    }
+    if (all != CMPC_OK) return fail(nullptr, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time: a time is not finite or a contact collapses on the grid");
+    return CMPC_OK;
+}
+
+int cmpc_contacts_force_sample_time_device(cmpc_handle h, int max_contacts, double dt, const double* dT, const int* dN, double* dOutT, int* dOk, void* stream)
+{
+    const long long dt_ns = snap_dt_ns(dt);
+    if (!h || max_contacts < 1 || dt_ns < 1 || !dT || !dN || !dOutT) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, dT, dN, dOutT, dOk, 0, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("forceSampleTime launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
 // the bounding boxes of the two contacts on the device (uploaded when they change)
 static int upload_box(cmpc_handle h, const float* box_upper, const float* box_lower, hipStream_t st)
 {
@@ -920,12 +966,37 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: bad planner trajectory");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    long long dt_ns = 0;
+    if (io->force_sample_time) {
+        dt_ns = snap_dt_ns(h->cfg.sampling_time);
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: force_sample_time needs a sampling time of at least 1 ns");
+    }
     int rc = upload_box(h, io->box_upper, io->box_lower, st);
     if (rc != CMPC_OK) return rc;
-    int lrc = cmpc_launch_tick_pre(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, merge ? 1 : 0, io->dPlanT, io->dPlanPose, io->dPlanN, io->dPrevT,
+    // forceSampleTime: inside the front kernel when the lists fit its LDS stage (cmpc_tick_pre_kernel, M <= 16); else one launch of the standalone kernel
+    // in front of it -- the planner's lists into the handle's dSnapT (merge ticks) or the caller's lists in place (first tick), per-foot status into dSnapOk
+    const double* plan_t = io->dPlanT;
+    const int* snap_ok = nullptr;
+    if (dt_ns > 0 && max_contacts > 16) {
+        const size_t need = (size_t)h->B * 2 * max_contacts * 2;
+        if (merge && need > h->snap_cap) {
+            HIPCHK(h, hipStreamSynchronize(st));
+            hipFree(h->dSnapT);
+            h->dSnapT = nullptr; h->snap_cap = 0;
+            HIPCHK(h, hipMalloc(&h->dSnapT, sizeof(double) * need));
+            h->snap_cap = need;
+        }
+        if (!h->dSnapOk) HIPCHK(h, hipMalloc(&h->dSnapOk, sizeof(int) * 2 * (size_t)h->B));
+        const int lrc = merge ? cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dPlanT, io->dPlanN, h->dSnapT, h->dSnapOk, 1, st)
+                              : cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dListT, io->dListN, io->dListT, h->dSnapOk, 1, st);
+        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (forceSampleTime) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (merge) plan_t = h->dSnapT;
+        snap_ok = h->dSnapOk;
+    }
+    int lrc = cmpc_launch_tick_pre(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, merge ? 1 : 0, plan_t, io->dPlanPose, io->dPlanN, io->dPrevT,
                                    io->dPrevPose, io->dPrevN, io->dListT, io->dListPose, io->dListN, io->dOk, io->dLand, h->dBox, io->dState, io->dWrench, io->dP,
                                    warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
-                                   io->com_height, st);
+                                   io->com_height, dt_ns, snap_ok, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
     rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
     if (rc != CMPC_OK) return rc;

@@ -13,6 +13,42 @@
 
 #define CMPC_TIME_EPS 1e-9
 
+// ContactPhaseList::forceSampleTime(dT) (CentroidalMPCBlock.cpp:586-592): the planner's times snapped to the MPC grid before the merge.  The rule
+// (include/cmpc.h, cmpc_contacts_force_sample_time; BLF's own is not in the reference tree: parity unpinned) on integer nanoseconds:
+// t_ns = llround(t 1e9); to the nearest multiple of dt_ns from time 0, ties to the later one; a time already on the grid keeps its bits; |t| >= 1e9 s
+// (the "never" sentinel) is kept.  Returns false for a non-finite time (*out = t).  dt_ns >= 1.
+#define CMPC_TIME_NEVER 1e9
+__host__ __device__ inline bool cmpc_snap_time(double t, long long dt_ns, double* out)
+{
+    *out = t;
+    if (!__builtin_isfinite(t)) return false;
+    if (fabs(t) >= CMPC_TIME_NEVER) return true;
+    const long long t_ns = llround(t * 1e9);   // |t_ns| < 1e18: 2 t_ns + dt_ns does not overflow for dt_ns < 1e18
+    if (t_ns % dt_ns == 0) return true;
+    const long long num = 2 * t_ns + dt_ns, den = 2 * dt_ns;
+    long long q = num / den;                   // C++ truncates towards zero: floor for a negative quotient
+    if (num % den != 0 && num < 0) --q;
+    *out = (double)(q * dt_ns) * 1e-9;
+    return true;
+}
+// one contact (activation, deactivation) of a list: in[] and out[] may alias.  False when a time is not finite or a contact of positive duration
+// collapses to zero duration (the reference's forceSampleTime returns false, :588-592).
+__host__ __device__ inline bool cmpc_snap_contact(const double* in, long long dt_ns, double* out)
+{
+    const double a = in[0], d = in[1];
+    double sa, sd;
+    const bool fa = cmpc_snap_time(a, dt_ns, &sa), fd = cmpc_snap_time(d, dt_ns, &sd);
+    out[0] = sa; out[1] = sd;
+    return fa && fd && !(d > a && sd == sa);
+}
+// one foot: the n contacts of t[n][2] into out[n][2] (may alias); false if any contact fails (all n are still written)
+__host__ __device__ inline bool cmpc_force_sample_time_foot(const double* t, int n, long long dt_ns, double* out)
+{
+    bool good = true;
+    for (int m = 0; m < n; ++m) good = cmpc_snap_contact(t + 2 * m, dt_ns, out + 2 * m) && good;
+    return good;
+}
+
 // ContactList::getActiveContact(t): activation <= t < deactivation (CentroidalMPCBlock.cpp:61, :69), or -1
 __host__ __device__ inline int cmpc_active_contact(const double* t, int n, double now)
 {

@@ -748,19 +748,25 @@ __global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, floa
 // (tests/test_gpu_rollout.py).
 // pre: one workgroup per problem.  All threads: setState and the warm-start shift; threads 0, 1: merge (updateContactPhaseList) of foot 0 / 1; then one thread per
 // (foot, stage): sampling (setContactPhaseList) of the merged lists; threads 0, 1: the landing knots.
+// snap_dt_ns > 0 (cmpc_tick_io.force_sample_time): forceSampleTime first -- one thread per list entry (cmpc_snap_contact) on the planner's lists staged in LDS
+// (merge ticks) or on the caller's lists (first tick, written back), behind a barrier.  Lists longer than the LDS stage were snapped by
+// cmpc_force_sample_time_kernel before this launch: snap_ok[2B] then holds its per-foot status words.  A foot whose snap fails is treated as an empty list:
+// its list is emptied, land = -2, ok = 0.
 __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose,
                                                             const int* plan_n, const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t,
                                                             float* list_pose, int* list_n, int* ok, int* land, const float* __restrict__ box,
                                                             const float* __restrict__ state, const float* __restrict__ wrench, float* P,
                                                             const float* __restrict__ Xprev, float* __restrict__ X0, const float* __restrict__ plan_com,
                                                             const float* __restrict__ plan_h, int plan_knots, double plan_dt, double plan_t_offset,
-                                                            double robot_mass, double com_height)
+                                                            double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     const CmpcIdx L{N};
     float* p = P + (size_t)b * L.np();
     __shared__ int okw;
+    __shared__ int foot_ok[2];   // forceSampleTime status of the two feet (1 when the flag is off)
     if (tid == 0) okw = 1;
+    if (tid < 2) foot_ok[tid] = snap_ok ? snap_ok[2 * b + tid] : 1;
     __syncthreads();
     // setState and the warm-start shift first (they depend on nothing the kernel computes: their memory traffic runs under the merge of threads 0, 1)
     for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e];
@@ -786,6 +792,13 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         for (int e = tid; e < 4 * M; e += 256) { st_[0][e] = plan_t[2 * o2 + e]; st_[1][e] = prev_t[2 * o2 + e]; }
         for (int e = tid; e < 14 * M; e += 256) { sp_[0][e] = plan_pose[7 * o2 + e]; sp_[1][e] = prev_pose[7 * o2 + e]; }
         __syncthreads();
+        if (snap_dt_ns > 0) {   // forceSampleTime on the staged planner lists ([foot][M][2]: entry e = foot * M + contact); the merge then reads them snapped
+            for (int e = tid; e < 2 * M; e += 256) {
+                const int c = e / M, pn = plan_n[2 * b + c];
+                if (pn >= 0 && pn <= M && e - c * M < pn && !cmpc_snap_contact(st_[0] + 2 * e, snap_dt_ns, st_[0] + 2 * e)) atomicAnd(&foot_ok[c], 0);
+            }
+            __syncthreads();
+        }
     }
     // this tick's lists live in LDS too (so_*): the merge writes them there, the sampling threads scan them there, and the workgroup copies them out
     __shared__ double so_t[2 * 2 * MS];
@@ -797,6 +810,21 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         for (int e = tid; e < 4 * M; e += 256) so_t[e] = list_t[2 * ob + e];
         for (int e = tid; e < 14 * M; e += 256) so_p[e] = list_pose[7 * ob + e];
         if (tid < 2) so_n[tid] = list_n[2 * b + tid];
+        if (snap_dt_ns > 0) {   // forceSampleTime on the caller's lists, written back: what the reference passes on (contactPhaseList = mannContactPhaseList)
+            __syncthreads();
+            for (int e = tid; e < 2 * M; e += 256) {
+                const int c = e / M, m = e - c * M, n = so_n[c];
+                if (n < 0 || n > M) { if (m == 0) atomicAnd(&foot_ok[c], 0); continue; }
+                if (m >= n) continue;
+                if (!cmpc_snap_contact(so_t + 2 * e, snap_dt_ns, so_t + 2 * e)) atomicAnd(&foot_ok[c], 0);
+                list_t[2 * ob + 2 * e] = so_t[2 * e]; list_t[2 * ob + 2 * e + 1] = so_t[2 * e + 1];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < 2 && !merge && !foot_ok[tid]) {   // (first tick, a failed snap: the foot's list is empty from here on)
+        if (lstaged) so_n[tid] = 0;
+        list_n[2 * b + tid] = 0;
     }
     if (tid < 2 && merge) {
         const int e = 2 * b + tid;
@@ -804,12 +832,13 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         const int pn = plan_n[e], mn = prev_n[e];
         const bool sane = pn >= 0 && pn <= M && mn >= 0 && mn <= M;
         int* on = lstaged ? &so_n[tid] : list_n + e;
-        if (!sane) *on = 0;
+        const bool snapped = foot_ok[tid] != 0;
+        if (!sane || !snapped) *on = 0;
         const double* pt = staged ? st_[0] + 2 * M * tid : plan_t + 2 * o;
         const double* mt = staged ? st_[1] + 2 * M * tid : prev_t + 2 * o;
         const float* pq = staged ? sp_[0] + 7 * M * tid : plan_pose + 7 * o;
         const float* mq = staged ? sp_[1] + 7 * M * tid : prev_pose + 7 * o;
-        const bool good = sane && cmpc_merge_foot(now, pt, pq, pn, mt, mq, mn, M, lstaged ? so_t + 2 * M * tid : list_t + 2 * o,
+        const bool good = sane && snapped && cmpc_merge_foot(now, pt, pq, pn, mt, mq, mn, M, lstaged ? so_t + 2 * M * tid : list_t + 2 * o,
                                                   lstaged ? so_p + 7 * M * tid : list_pose + 7 * o, on);
         if (!good) atomicAnd(&okw, 0);
     }
@@ -835,7 +864,7 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         const int e = 2 * b + tid, n = lstaged ? so_n[tid] : list_n[e];
         land[e] = (n < 1 || n > M) ? -2 : cmpc_landing_knot(N, [&](int k) { return acts[tid][k] != 0; });
     }
-    if (merge && ok && tid == 0) ok[b] = okw;
+    if ((merge || snap_dt_ns > 0) && ok && tid == 0) ok[b] = okw && foot_ok[0] && foot_ok[1];
 }
 
 // post: one thread per problem -- the plant step, then the step adjustment of its two feet (getOutput().contactPhaseList)
@@ -865,11 +894,11 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, hipStream_t stream)
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_tick_pre_kernel, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
                        list_t, list_pose, list_n, ok, land, box, state, wrench, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, plan_t_offset, robot_mass,
-                       com_height);
+                       com_height, snap_dt_ns, snap_ok);
     return (int)hipGetLastError();
 }
 

@@ -40,9 +40,12 @@ class WalkingRollout:
     warm_budget = iterations of the warm-started pass (0: the full budget; 14 = the library's default); retry = "kernel": such a problem starts again from the cold
     start inside the same launch (one workgroup holds its CU for two budgets); "launch": it comes back unconverged and the tick's few
     stragglers are solved again from the cold start in a small launch of their own (a CU each); None: they stay unconverged -- which is all
-    the reference can do: its advance() returns false and the tick is aborted (CentroidalMPCBlock.cpp:615-619)."""
+    the reference can do: its advance() returns false and the tick is aborted (CentroidalMPCBlock.cpp:615-619).
+    force_sample_time: every tick snaps the planner's lists to the MPC grid before the merge (forceSampleTime, CentroidalMPCBlock.cpp:586-592; the rule of
+    include/cmpc.h), on both tick paths and after a replan; a list that fails to snap aborts the tick like a failed merge (rec["merge_ok"])."""
 
-    def __init__(self, cfg, batch, plan=None, device=0, substeps=6, com_speed=None, warm_budget=14, retry="kernel", retry_batch=256, native_tick=True, **solver_opts):
+    def __init__(self, cfg, batch, plan=None, device=0, substeps=6, com_speed=None, warm_budget=14, retry="kernel", retry_batch=256, native_tick=True,
+                 force_sample_time=False, **solver_opts):
         import torch
         self.torch = torch
         self.cfg, self.B = cfg, batch
@@ -54,6 +57,7 @@ class WalkingRollout:
         # native_tick: a warm-started tick is ONE call of the C ABI (cmpc_rollout_tick_device: the same seven entry points chained inside the library, bit-identical
         # results) instead of seven; ticks that need the host between the steps (cold starts, retry="launch", the dump hook) take the step-by-step path
         self.native_tick = native_tick and retry != "launch"
+        self.force_sample_time = bool(force_sample_time)
         self.solver.set_warm_policy(warm_budget, restart_in_kernel=(retry == "kernel"))
         self.solver2 = BatchSolver(cfg, self.retry_batch, device=device, **solver_opts) if retry == "launch" else None
         plan = plan or walking_plan(cfg)
@@ -92,7 +96,14 @@ class WalkingRollout:
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         if mpc_prev is None:
             lists = tuple(a.clone() for a in self.plan)
-            ok = torch.ones((B,), dtype=torch.int32, device=dev)
+            if self.force_sample_time:     # (the snapped list is what the reference passes on: contactPhaseList = mannContactPhaseList)
+                _, ok = s.contacts_force_sample_time_device(lists[0], lists[2], out=lists[0])
+            else:
+                ok = torch.ones((B,), dtype=torch.int32, device=dev)
+        elif self.force_sample_time:
+            plan_t, ok_snap = s.contacts_force_sample_time_device(self.plan[0], self.plan[2])
+            lists, ok = s.contacts_merge_device(now, (plan_t, self.plan[1], self.plan[2]), mpc_prev)
+            ok = ok & ok_snap
         else:
             # (whether every merge succeeded is read by the host at the END of the tick, with the status words: a read here would drain the stream in the
             #  middle of the tick and leave the GPU idle while the host queues the six launches in front of the solve -- 0.17 ms of a 0.83 ms tick at
@@ -199,7 +210,7 @@ class WalkingRollout:
                         wrench[:, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
                     wr = wrench
                 s.rollout_tick_device(now, self.plan, mpc_prev, lists, ok, land, state, wr, dP, dX0, dX, dInfo, state, zmp, True,
-                                      step=dt / self.substeps, substeps=self.substeps, planner=planner(now))
+                                      step=dt / self.substeps, substeps=self.substeps, planner=planner(now), force_sample_time=self.force_sample_time)
                 mpc_prev = lists
                 nretry = 0
             else:

@@ -214,6 +214,19 @@ class BatchSolver:
             out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ok.data_ptr(), st))
         return out, ok
 
+    def contacts_force_sample_time_device(self, t, n, out=None, ok=None, dt=None):
+        """forceSampleTime (CentroidalMPCBlock.cpp:586-592) for the batch: t[B,2,M,2] float64 / n[B,2] int32 CUDA tensors snapped to the grid of dt
+        (default: the sampling time) into out (None: a new tensor; may be t itself).  Returns (out, ok[B] int32)."""
+        import torch
+        if out is None:
+            out = torch.empty_like(t)
+        if ok is None:
+            ok = torch.empty((self.batch,), dtype=torch.int32, device=t.device)
+        assert t.is_contiguous() and out.is_contiguous() and t.dtype == torch.float64 and n.dtype == torch.int32 and t.shape[0] == self.batch
+        self._launch(t.device, lambda st: self._lib.cmpc_contacts_force_sample_time_device(
+            self._h, t.shape[2], float(self.cfg.sampling_time if dt is None else dt), t.data_ptr(), n.data_ptr(), out.data_ptr(), ok.data_ptr(), st))
+        return out, ok
+
     def contacts_sample_device(self, now, lists, dP, land=None):
         """setContactPhaseList for the batch: samples `lists` at now + k dt into the contact blocks of dP[B,np]; returns
         land[B,2] (landing knots)."""
@@ -247,9 +260,11 @@ class BatchSolver:
             float("nan") if com_height is None else float(com_height), dP.data_ptr(), st))
 
     def rollout_tick_device(self, now, plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, warm,
-                            step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None):
+                            step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
         """cmpc_rollout_tick_device: merge -> sample -> setState -> shift -> solve -> step adjustment -> plant as ONE call (include/cmpc.h); plan / prev /
-        lists = (t, pose, n) CUDA tensors, prev None on the first tick (lists is then taken as filled by the caller); dWrench may be None."""
+        lists = (t, pose, n) CUDA tensors, prev None on the first tick (lists is then taken as filled by the caller); dWrench may be None.
+        force_sample_time: the planner's lists (the caller's lists on the first tick, in place) are snapped to the MPC grid first (forceSampleTime,
+        CentroidalMPCBlock.cpp:586-592); ok is then written on the first tick too."""
         from ._capi import CmpcTickIO
         if getattr(self, "_box", None) is None:
             self._box = (np.ascontiguousarray([c.bounding_box_upper_limit for c in self.cfg.contacts], np.float32),
@@ -264,6 +279,7 @@ class BatchSolver:
             pc, ph, pdt, poff, mass, height = planner
             io.dPlanCom, io.dPlanH, io.plan_knots, io.plan_dt, io.plan_t_offset = pc.data_ptr(), ph.data_ptr(), int(pc.shape[1]), float(pdt), float(poff)
             io.robot_mass, io.com_height = float(mass), float("nan") if height is None else float(height)
+        io.force_sample_time = 1 if force_sample_time else 0
         self._launch(dP.device, lambda st: self._lib.cmpc_rollout_tick_device(self._h, lists[0].shape[2], float(now), 1 if warm else 0, io, st))
 
     def shift_solution_device(self, dXprev, dX0):
