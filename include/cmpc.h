@@ -150,9 +150,6 @@ int cmpc_set_timing(cmpc_handle h, int enabled);
  * test can show that a solve does not depend on what an earlier workgroup or kernel left there.  No reference
  * counterpart. */
 int cmpc_test_poison_lds(cmpc_handle h);
-/* test hook (host only, no GPU): workgroup barriers one role of the streaming backward stage executes in a pass over stages N-1 .. k0 -- role 0 the
- * factorising wave, 1 the consumers -- counted on the loop skeleton both device loops are written with.  Unequal counts would hang a workgroup. */
-int cmpc_sq_pass_barriers(int horizon, int k0, int role);
 
 /* ---- NLP callbacks (what IPOPT evaluated through the generated code), batched on the device ----
  * any output pointer may be NULL.  dLamG[B][n_g], lam_f scalar (hess of lam_f f + lam_g^T g).

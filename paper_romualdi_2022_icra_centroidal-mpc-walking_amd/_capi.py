@@ -59,7 +59,7 @@ EXPORTS = [
     "cmpc_compact_output_device", "cmpc_contacts_merge", "cmpc_contacts_merge_device", "cmpc_contacts_sample",
     "cmpc_contacts_sample_device", "cmpc_set_contact_lists", "cmpc_contacts_adjust", "cmpc_contacts_adjust_device",
     "cmpc_write_state_device", "cmpc_shift_solution_device", "cmpc_eval_nlp_grad_device", "cmpc_solve_device_warm", "cmpc_set_warm_policy",
-    "cmpc_get_parameters", "cmpc_get_parameters_device", "cmpc_allgather_compact_device", "cmpc_sq_pass_barriers",
+    "cmpc_get_parameters", "cmpc_get_parameters_device", "cmpc_allgather_compact_device",
     "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device", "cmpc_default_tolerance",
     "cmpc_contacts_force_sample_time", "cmpc_contacts_force_sample_time_device",
 ]
@@ -135,7 +135,6 @@ def lib():
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]
             L.cmpc_allgather_compact_device.argtypes = [vp, vp, C.c_int, fp, fp, vp]
-            L.cmpc_sq_pass_barriers.argtypes = [C.c_int, C.c_int, C.c_int]
         if hasattr(L, "cmpc_rollout_tick_device"):
             L.cmpc_rollout_tick_device.argtypes = [vp, i, d, i, C.POINTER(CmpcTickIO), vp]
         if hasattr(L, "cmpc_write_reference_from_planner_device"):

@@ -90,12 +90,8 @@
 #define REC_WT 576
 #define REC_ZERO 572
 #define REC_N CMPC_REC_N
-#ifndef CMPC_DELTA_UNROLL
-#define CMPC_DELTA_UNROLL 4   // the same for the corrector sweep of the resident variants (2 -> 4: 354.9 k -> 356.2 k solves/s at B = 256, three rounds)
-#endif
-#ifndef CMPC_SWEEP_UNROLL
-#define CMPC_SWEEP_UNROLL 4   // stages per trip of the sweep loops in the resident variants (A/B: 1 / 2 / 4 / 10 -> 184.4 / 186.1 / 189.8 / 188.0 k solves/s)
-#endif
+constexpr int SWEEP_UNROLL = 4;   // stages per trip of the sweep loops in the resident variants (A/B: 1 / 2 / 4 / 10 -> 184.4 / 186.1 / 189.8 / 188.0 k solves/s)
+constexpr int DELTA_UNROLL = 4;   // the same for the corrector sweep of the resident variants (2 -> 4: 354.9 k -> 356.2 k solves/s at B = 256, three rounds)
 // The HBM-factor variants are compiled for three workgroups per CU (168 registers per lane): their LDS image fits three times into
 // a CU up to N = 30 (52 KB at N = 20 and at N = 30).  Measured at N = 12, B = 8192, where 2, 3 and 4 all fit: 22.4 / 17.1 /
 // 17.8 ms -- at four (128 registers) the spills of the factorisation and the sweeps cost more than the fourth workgroup brings.
@@ -1562,13 +1558,10 @@ __device__ __attribute__((noinline)) void stage_post_pre(lds_t lds, int Nrt, flo
 // needs no lane predicate), a count of the waves done with Y (3 per stage), and a count of those whose part of the assembly is complete (6 per stage).  Every wait is
 // bounded: a wave that gives up raises the failure flag AND the give-up word c.flag[1], which the driver reports in its own digit of info[3] (include/cmpc.h) -- a
 // stalled hand-off must never read as a bad pivot.
-// BARRIER INVARIANT: sq_factor_loop and sq_consume_loop each execute exactly 1 + (N - k0) workgroup barriers per backward pass (sq_pass_barriers), one per stage plus
-// the one behind the terminal assembly, with no early exit on either side; tests/test_host_logic.py holds the two counts together. ----
+// BARRIER INVARIANT: sq_factor_loop and sq_consume_loop execute the same workgroup barriers in a backward pass -- a mismatch hangs the workgroup.  Each takes
+// one before its stage loop and one per trip of `for (k = N - 1; k >= k0; --k)`, with no early exit and no other barrier in what it calls;
+// tests/test_host_logic.py checks the compiled code (two s_barrier and no call in every instantiation of either role) and that neither role's own code can leave its loop. ----
 #define SQ_Y_WAVES 3           // consumer waves that write Y (waves 5, 6, 7): the Y count advances by this per stage
-// the stage loop of a backward pass: BOTH roles iterate with this header and hold exactly one barrier per trip (plus SQ_PRE_BARRIERS before the loop)
-#define SQ_STAGE_LOOP(k, N, k0) for (int k = (N) - 1; k >= (k0); --k)
-#define SQ_PRE_BARRIERS 1
-__host__ __device__ constexpr int sq_pass_barriers(int N, int k0) { return SQ_PRE_BARRIERS + (N - k0); }
 // Hand-off words: release on the publishing side, acquire on the reading side, workgroup scope (relaxed accesses leaned on in-order LDS issue of one wave,
 // which is how the hardware behaves and not what the memory model promises; on LDS-only traffic the stronger orders cost an s_waitcnt lgkmcnt(0) the code had anyway).
 __device__ inline int lds_peek(const int* p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -1596,7 +1589,7 @@ __device__ __attribute__((noinline)) void sq_factor_loop(lds_t lds, int Nrt, flo
     int ord = 0;                                       // ordinal of the stage within the backward pass
     __builtin_amdgcn_s_setprio(3);
 #pragma unroll 1
-    SQ_STAGE_LOOP(k, N, k0) {                          // (sq_pass_barriers: one barrier per trip, no early exit)
+    for (int k = N - 1; k >= k0; --k) {                // (BARRIER INVARIANT: one barrier per trip, no early exit)
         ++ord;
         lds_t lk = lds;                                // (an opaque copy of the LDS base per stage: see sq_consume_loop)
         asm volatile("" : "+v"(lk));
@@ -2135,7 +2128,7 @@ __device__ __attribute__((noinline)) void sq_consume_loop(lds_t lds, int Nrt, fl
     __syncthreads();
     int ord = 0;
 #pragma unroll 1
-    SQ_STAGE_LOOP(k, N, k0) {                          // (sq_pass_barriers: one barrier per trip, no early exit)
+    for (int k = N - 1; k >= k0; --k) {                // (BARRIER INVARIANT: one barrier per trip, no early exit)
         ++ord;
         if (k > k0) sq_consume_stage(c, prm, pl, tid, N, k, k - 1, k - 2 >= k0 ? k - 2 : -1, ord, true, use_exact, reg, cmu);
         __syncthreads();
@@ -2663,11 +2656,11 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         bump(1);                     // to the stage below the trip
     }
 }
-template <int UNR, bool G, int PART = 0>
+// (no barrier: phase_delta takes it behind the sweep)
+template <int UNR, bool G>
 __device__ void riccati_delta(const Ctx& c, const CmpcConsts& prm, int tid)
 {
     if (tid < 64) delta_sweep<UNR, G>(c, prm, tid);
-    if (PART == 0) __syncthreads();
 }
 
 // largest step lengths keeping t, z positive (fraction tau to the boundary)
@@ -2707,7 +2700,7 @@ __device__ inline void costate_force_sums(const Ctx& c, int tid, int nth)
 // is triangular in the components: the angular-momentum rows depend on nothing else (A_hh = I: a suffix sum of terms known in advance), the CoM rows and the foot rows
 // take lam_h of the next stage through the cross products with the forces (a suffix sum, and one weighted by gam), the CoM-velocity rows take dt lam_com of the next stage.
 // Four dependent levels of scans (DPP row shifts + one read of each row's leader) instead of N serial stages of ~45 instructions with two broadcasts each: ~500
-// instructions against ~900 on a dependent chain.  Same terms as costate_recursion (which stays as the statement of the recursion and serves horizons beyond 63);
+// instructions against ~900 on a dependent chain.  Same terms as the serial recursion of oracle/ipm_ref.c, which the GPU tests hold the solver to;
 // sums are taken in scan order, so the float32 costates differ from the serial ones in the last bits. ----
 template <int CTRL>
 __device__ inline float dpp_keep(float old, float v) { return __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(old), __float_as_uint(v), CTRL, 0xF, 0xF, false)); }
@@ -2803,100 +2796,11 @@ __device__ inline void costate_scan(const Ctx& c, const CmpcConsts& prm, int lan
     }
 }
 
-#ifdef CMPC_COSTATE_SERIAL
-// The serial recursion the scans replace -- the statement of what they compute (oracle/ipm_ref.c states the same), compiled only into -DCMPC_COSTATE_SERIAL builds
-// (the A/B and the trace of profiles/r04_experiments_not_kept.txt, item 24).  One wave (tid < 64).  DEFER: the full-step costates go to vout (NS (N + 1) floats) and LAM is left alone -- the caller blends them in once
-// the step length is known (phase_final_post: the recursion runs beside the slack steps the step length comes from)
-template <bool DEFER>
-__device__ inline void costate_recursion(const Ctx& c, const CmpcConsts& prm, int tid, float ap, bool use_exact, float* vout)
-{
-    const int N = c.N;
-    {
-        // lane j < 15 owns costate component j.  Everything below is one formula with per-lane coefficients:
-        //   lam_j = w (s_j - ref_j + ds_j) + sj pv_j + ce pv_je + cg (pv_{6+a1} F_a2 - pv_{6+a2} F_a1)
-        //           + eg (dF_a1 lamh_a2 - dF_a2 lamh_a1)                       (exact Hessian only)
-        const bool own = tid < NS;
-        const int j = own ? tid : 0;
-        const int ja = j < 3 ? j : (j >= 9 ? (j - 9) % 3 : 0), ja1 = (ja + 1) % 3, ja2 = (ja + 2) % 3;
-        const int jct = j >= 12 ? 1 : 0;
-        const int roff = j < 3 ? c.L.pComref() + j : (j < 6 ? c.L.pComref() : (j < 9 ? c.L.pHref() + j - 6 : c.L.pNom(jct) + ja));
-        const float wc = j == 0 ? 2.f * prm.w_com0 : (j == 1 ? 2.f * prm.w_com1 : (j < 6 ? 0.f : (j < 9 ? 2.f * prm.w_h : 2.f * prm.w_pos)));
-        const int gfo = j < 3 ? 30 : 24 + 3 * jct;       // Fsum or Fc of the foot (geometry record)
-        const int dfo = j < 3 ? 6 : 3 * jct;             // total or per-foot force-step sum
-        const int gco = c.L.pGam(jct);
-        // per-lane coefficients: sj = sA + sB gam, cg = cgA + cgB gam, ce, eg; 0/1 masks picking components a1, a2 of a 3-vector
-        const float sA = j >= 9 ? 0.f : 1.f, sB = j >= 9 ? 1.f : 0.f;
-        const float cgA = j < 3 ? prm.dt : 0.f, cgB = j >= 9 ? -prm.dt : 0.f;
-        const float ce = (j >= 3 && j < 6) ? prm.dt : 0.f;
-        const float eg = !use_exact ? 0.f : (j < 3 ? -prm.dt : (j >= 9 ? prm.dt : 0.f));
-        const float m10 = ja1 == 0, m11 = ja1 == 1, m12 = ja1 == 2, m20 = ja2 == 0, m21 = ja2 == 1, m22 = ja2 == 2;
-        // The recursion runs in registers.  Per stage: the linear-momentum costates of stage k+1 reach the lanes of the CoM-velocity
-        // rows by a DPP row shift, its three angular-momentum costates (and, for the exact Hessian, the old ones the Hessian used)
-        // are broadcast with v_readlane and meet per-lane coefficient vectors built from the cross-product operands.  Everything
-        // that does not depend on the recursion (state, reference, step, forces, old costate) is fetched one stage ahead, two
-        // operand sets alternating -- a stage costs ~45 VALU instructions and no LDS round trip (it was two, in float64).
-        struct Ops { float s, ref, ds, F1, F2, dF1, dF2, gam, wz, lold; };
-        auto fetch = [&](int k) {
-            Ops o;
-            const float* geo = c.geoA + GEO * k;
-            o.s = c.S[NS * k + j]; o.ref = c.sp[roff + 3 * k]; o.ds = c.dS[NS * k + j];
-            o.F1 = geo[gfo + ja1]; o.F2 = geo[gfo + ja2];
-            o.dF1 = c.d[NS * k + dfo + ja1]; o.dF2 = c.d[NS * k + dfo + ja2];
-            o.gam = c.sp[gco + k];
-            o.wz = prm.wz2[k];
-            o.lold = c.LAM[NS * k + j];
-            return o;
-        };
-        float lold = c.LAM[NS * N + j];   // (lanes 6..8: lam_h,N as the Hessian used it)
-        float pvj = (j == 2 ? prm.wz2[N] : wc) * ((c.S[NS * N + j] - c.sp[roff + 3 * N]) + c.dS[NS * N + j]);
-        auto step = [&](int k, const Ops& o) {
-            // off the recursion: base term and coefficient vectors
-            const float base = (j == 2 ? o.wz : wc) * ((o.s - o.ref) + o.ds);
-            const float sj = fmaf(sB, o.gam, sA), cg = fmaf(cgB, o.gam, cgA);
-            const float cF1 = cg * o.F1, cF2 = cg * o.F2;
-            const float c0 = m10 * cF2 - m20 * cF1, c1 = m11 * cF2 - m21 * cF1, c2 = m12 * cF2 - m22 * cF1;
-            float v = base;
-            if (use_exact) {
-                const float eF1 = eg * o.dF1, eF2 = eg * o.dF2;
-                const float g0 = m20 * eF1 - m10 * eF2, g1 = m21 * eF1 - m11 * eF2, g2 = m22 * eF1 - m12 * eF2;
-                v += readlane_f(lold, 6) * g0 + readlane_f(lold, 7) * g1 + readlane_f(lold, 8) * g2;
-            }
-            // on it
-            const float pe = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(pvj), 0x113, 0xF, 0xF, true));  // row_shr:3
-            v += sj * pvj + ce * pe + readlane_f(pvj, 6) * c0 + readlane_f(pvj, 7) * c1 + readlane_f(pvj, 8) * c2;
-            lold = o.lold;
-            pvj = v;
-            if (own) {
-                if (DEFER) vout[NS * k + j] = v;
-                else c.LAM[NS * k + j] = lold + ap * (v - lold);
-            }
-        };
-        Ops oa = fetch(N > 1 ? N - 1 : 0), ob;
-        if (own) {
-            if (DEFER) vout[NS * N + j] = pvj;
-            else c.LAM[NS * N + j] = lold + ap * (pvj - lold);
-        }
-        int k = N - 1;
-#pragma unroll 1   // (left alone the compiler unrolls all N / 2 trips: 10 KB of straight-line code for a phase that runs once per iteration)
-        for (; k >= 2; k -= 2) {
-            ob = fetch(k - 1);
-            step(k, oa);
-            oa = fetch(k - 2);
-            step(k - 1, ob);
-        }
-        if (k == 1) step(1, oa);
-    }
-}
-#endif
 __device__ void costate_update(const Ctx& c, const CmpcConsts& prm, int tid, float ap, bool use_exact)
 {
     costate_force_sums(c, tid, blockDim.x);
     __syncthreads();
-#ifdef CMPC_COSTATE_SERIAL
-    if (tid < 64) costate_recursion<false>(c, prm, tid, ap, use_exact, nullptr);
-#else
     if (tid < 64) costate_scan<false>(c, prm, tid, ap, use_exact, nullptr);
-#endif
     __syncthreads();
 }
 
@@ -2905,30 +2809,21 @@ __device__ void costate_update(const Ctx& c, const CmpcConsts& prm, int tid, flo
 // every wave that ENTERS the function saves to and restores from scratch memory: with all four waves calling, 576 scratch operations per
 // workgroup and iteration -- 2.6 GB written and read back per 4096-problem launch, half of what the counters showed as "factor-record
 // traffic" (found in round 3: one saved register per call stood out in SQ_INSTS_VMEM_WR of the resident variant).  So only wave 0 calls the
-// sweep (CMPC_SWEEP_WAVE0_ONLY); the barrier and the element-wise part behind it are a function of their own that needs no callee-saved
+// sweep; the barrier and the element-wise part behind it are a function of their own that needs no callee-saved
 // register.  (Inlining the sweeps into the kernel body instead was measured: 101 VGPRs of the body spilled, some inside the stage loops.)
-#ifndef CMPC_SWEEP_WAVE0_ONLY
-#define CMPC_SWEEP_WAVE0_ONLY(FG) (1)
-#endif
-#ifndef CMPC_SWEEP_WAVE
-#define CMPC_SWEEP_WAVE 0   // which wave of an HBM-factor workgroup runs the sweeps (the sweep code sees tid - 64 * CMPC_SWEEP_WAVE)
-#endif
 template <int NT, int NC, bool FG, int PART>
 __device__ __attribute__((noinline)) void phase_forward_part(lds_t lds, int Nrt, float* fg_base, bool affine_in)
 {
     CMPC_PHASE_PROLOGUE;
     const bool affine = __builtin_amdgcn_readfirstlane((int)affine_in) != 0;
-    riccati_forward<NT, NC == 0 ? 1 : (FG ? 2 : CMPC_SWEEP_UNROLL), FG, PART>(c, prm, PART == 1 ? tid - 64 * CMPC_SWEEP_WAVE : tid, affine, 0);
+    riccati_forward<NT, NC == 0 ? 1 : (FG ? 2 : SWEEP_UNROLL), FG, PART>(c, prm, tid, affine, 0);
 }
 // the sweep alone, on its wave; what follows it -- a barrier and the slack steps -- is phase_forward_part<.., 2>, or fused with the passes behind it (phase_affine_post,
 // phase_final_post)
-#ifndef CMPC_FUSED_POST
-#define CMPC_FUSED_POST(NC) ((NC) > 0)
-#endif
 template <int NT, int NC, bool FG>
 __device__ __forceinline__ void phase_forward_sweep(lds_t lds, int Nrt, float* fg_base, bool affine_in)
 {
-    if ((threadIdx.x >> 6) == CMPC_SWEEP_WAVE) phase_forward_part<NT, NC, FG, 1>(lds, Nrt, fg_base, affine_in);
+    if (threadIdx.x < 64) phase_forward_part<NT, NC, FG, 1>(lds, Nrt, fg_base, affine_in);
 }
 template <int NT, int NC, bool FG>
 __device__ __attribute__((noinline)) void phase_forward_tail(lds_t lds, int Nrt, float* fg_base, bool affine_in, int k0_in)
@@ -2938,19 +2833,17 @@ __device__ __attribute__((noinline)) void phase_forward_tail(lds_t lds, int Nrt,
     const int k0 = __builtin_amdgcn_readfirstlane(k0_in);
     riccati_forward<NT, 1, FG>(c, prm, tid, affine, k0);
 }
-template <int NT, int NC, bool FG, int PART>
+template <int NT, int NC, bool FG>
 __device__ __attribute__((noinline)) void phase_delta_part(lds_t lds, int Nrt, float* fg_base)
 {
     CMPC_PHASE_PROLOGUE;
-    riccati_delta<NC == 0 ? 1 : (FG ? 2 : CMPC_DELTA_UNROLL), FG, PART>(c, prm, PART == 1 ? tid - 64 * CMPC_SWEEP_WAVE : tid);
+    riccati_delta<NC == 0 ? 1 : (FG ? 2 : DELTA_UNROLL), FG>(c, prm, tid);
 }
 template <int NT, int NC, bool FG>
 __device__ __forceinline__ void phase_delta(lds_t lds, int Nrt, float* fg_base)
 {
-    if constexpr (CMPC_SWEEP_WAVE0_ONLY(FG)) {
-        if ((threadIdx.x >> 6) == CMPC_SWEEP_WAVE) phase_delta_part<NT, NC, FG, 1>(lds, Nrt, fg_base);
-        __syncthreads();
-    } else phase_delta_part<NT, NC, FG, 0>(lds, Nrt, fg_base);
+    if (threadIdx.x < 64) phase_delta_part<NT, NC, FG>(lds, Nrt, fg_base);
+    __syncthreads();
 }
 template <int NT, int NC, bool FG>
 __device__ __attribute__((noinline)) void phase_costate(lds_t lds, int Nrt, float* fg_base, float ap, bool exact_in)
@@ -3421,11 +3314,7 @@ __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int N
     if (tid < 64) {
         costate_force_sums(c, tid, 64);
         wave_lds_sync();
-#ifdef CMPC_COSTATE_SERIAL
-        costate_recursion<true>(c, prm, tid, 0.f, use_exact, vbuf);
-#else
         costate_scan<true>(c, prm, tid, 0.f, use_exact, vbuf);
-#endif
 #pragma unroll
         for (int q = 0; q < R; ++q) { t[q] = 1.f; z[q] = 0.f; dt[q] = 0.f; dz[q] = 0.f; ei[q] = 0; st[q] = 0; }
     } else {
@@ -3658,7 +3547,8 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
                     break;
                 }
                 Centre ce;
-                if constexpr (CMPC_FUSED_POST(NC)) ce = phase_affine_post<NT, NC, FG>(lds, N, fg_base, mu_cur, nrow);
+                // (the fused passes hold a thread's rows in registers, RowSlots sized by the compile-time horizon: the runtime-N variants, NC == 0, take the separate passes)
+                if constexpr (NC > 0) ce = phase_affine_post<NT, NC, FG>(lds, N, fg_base, mu_cur, nrow);
                 else {
                     phase_forward_part<NT, NC, FG, 2>(lds, N, fg_base, true);
                     const StepLen sa = phase_step_lengths<NT, NC, FG>(lds, N, fg_base, 1.f);
@@ -3673,7 +3563,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
             PROF(15);
             // ---- slack steps, step lengths, costates, then the iterate ----
             float ap, ad, step;
-            if constexpr (CMPC_FUSED_POST(NC)) {
+            if constexpr (NC > 0) {
                 const FinalStep fs = phase_final_post<NT, NC, FG>(lds, N, fg_base, fmaxf(0.99f, 1.f - mu_t), exact);
                 ap = fs.ap; ad = fs.ad; step = fs.step;
                 PROF(16);
@@ -3715,16 +3605,6 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
 }
 
 }  // namespace
-
-// Workgroup barriers one role of the streaming stage executes in a backward pass over stages N-1 .. k0 (role 0: the factorising wave, sq_factor_loop; 1: the
-// consumers, sq_consume_loop), counted on the loop skeleton both device loops are written with.  A mismatch would be a hang of the whole workgroup on the GPU:
-// tests/test_host_logic.py holds the two together.
-extern "C" int cmpc_sq_pass_barriers(int N, int k0, int role)
-{
-    int n = SQ_PRE_BARRIERS;
-    SQ_STAGE_LOOP(k, N, k0) { (void)role; ++n; }
-    return n == sq_pass_barriers(N, k0) ? n : -1;
-}
 
 // LDS bytes the kernel needs for horizon N
 extern "C" size_t cmpc_solver_lds_bytes(int N, int factors_global)

@@ -125,15 +125,46 @@ def test_c_abi_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
-def test_streaming_stage_roles_hold_the_same_number_of_barriers():
+def _role_barriers(isa):
+    """{(role, NT, NC, FG): (s_barrier count, call count)} of every out-of-line instantiation of the two roles of the streaming stage in an ISA listing."""
+    out = {}
+    for m in re.finditer(r"^_Z\w*?(sq_factor_loop|sq_consume_loop)ILi(\d+)ELi(\d+)ELb([01])E\w*:(.*?)^\.Lfunc_end", isa, re.M | re.S):
+        body = m.group(5)
+        out[(m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4)))] = (
+            len(re.findall(r"^\s+s_barrier\b", body, re.M)), len(re.findall(r"^\s+s_(?:swappc|call)_b64\b", body, re.M)))
+    return out
+
+
+def test_streaming_stage_roles_compile_to_the_same_barriers(tmp_path):
     """The factorising wave and the consumer waves of the streaming backward stage run their stage loops in two different out-of-line functions
-    and meet at workgroup barriers: unequal counts would hang the workgroup (a GPU reset for everyone on the node), not fail a test.  Both loops are
-    written with one loop-header macro and hold one barrier per trip plus one before the loop; the library counts them on that skeleton (host code)."""
-    lib = cm._capi.lib()
-    for N in (2, 10, 12, 13, 15, 20, 22, 30, 40):
-        for k0 in sorted({0, 1, max(N - 3, 0), N - 1}):
-            a, b = lib.cmpc_sq_pass_barriers(N, k0, 0), lib.cmpc_sq_pass_barriers(N, k0, 1)
-            assert a == b == 1 + N - k0, (N, k0, a, b)
+    and meet at workgroup barriers: unequal counts would hang the workgroup (a GPU reset for everyone on the node), not fail a test.  Each takes one
+    barrier before its stage loop and one per trip.  Checked in the compiled code (a device-only compile to gfx950 assembly,
+    no GPU): every instantiation of either role, release and -DCMPC_PROFILE builds, holds exactly those two s_barrier and calls nothing that could
+    hide another, and neither role's own code has a way out of its loop."""
+    import subprocess
+    import __graft_entry__ as ge
+    flags = [f for f in ge.FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-S"]
+    src = os.path.join(ge.CSRC, "cmpc_solver.hip")
+    builds = {"release": [], "profile": ["-DCMPC_PROFILE"]}
+    procs = {name: subprocess.Popen([ge.HIPCC] + flags + extra + [src, "-o", str(tmp_path / (name + ".s"))],
+                                    stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for name, extra in builds.items()}
+    for name, p in procs.items():
+        log = p.communicate()[0].decode(errors="replace")
+        assert p.returncode == 0, (name, log[-2000:])
+    # a data-dependent exit keeps the count and skips barriers at run time: the role functions' own code has none (what they call may return)
+    text = open(src).read()
+    for role in ("sq_factor_loop", "sq_consume_loop"):
+        body = re.search(r"void " + role + r"\(.*?\n\{\n(.*?)\n\}\n", text, re.S).group(1)
+        code = re.sub(r"//[^\n]*", "", body)
+        assert not re.search(r"\b(break|continue|return|goto)\b", code), role
+    for name in builds:
+        roles = _role_barriers((tmp_path / (name + ".s")).read_text())
+        # the resident variants: the horizons of the shipped configurations, and the runtime-N variant (NC = 0)
+        assert {(nc, fg) for (r, nt, nc, fg) in roles if r == "sq_factor_loop"} == {(n, 0) for n in (0, 10, 12, 13, 15, 20, 22)}, (name, sorted(roles))
+        for (role, nt, nc, fg), (bar, calls) in roles.items():
+            other = roles[("sq_consume_loop" if role == "sq_factor_loop" else "sq_factor_loop", nt, nc, fg)]
+            assert bar == other[0] == 2, (name, role, nt, nc, fg, bar, other)
+            assert calls == 0, (name, role, nt, nc, fg, calls)
 
 
 def test_lds_images_fit_the_cu():
