@@ -106,7 +106,8 @@ typedef struct {
  *   3. if stage k is in stance after a swing, k' being the last swing stage before it: R_k, nominal_c,k+1, lower_k and upper_k are
  *      bit-equal to R_k', nominal_c,k'+1, lower_k' and upper_k' (the row is then a duplicate of the landing row).
  * A problem that breaks the rule is not iterated: it comes back at once with status 3 and its initial iterate as x; the other problems
- * of the batch are untouched.  cmpc_set_contacts / cmpc_set_contact_lists write schedules inside the subset. */
+ * of the batch are untouched.  cmpc_set_contacts / cmpc_set_contact_lists write schedules inside the subset.  So does a problem whose row of a
+ * per-problem model table set on the device breaks the model rule (cmpc_set_models_device, below: dOk[b] = 0). */
 void cmpc_default_config(cmpc_config* cfg);                      /* ergoCubGazeboV1 values, N=20 */
 int cmpc_dims(int horizon, int* n_x, int* n_p, int* n_g, int* nnz_jac, int* nnz_hess);
 
@@ -150,6 +151,37 @@ int cmpc_set_timing(cmpc_handle h, int enabled);
  * test can show that a solve does not depend on what an earlier workgroup or kernel left there.  No reference
  * counterpart. */
 int cmpc_test_poison_lds(cmpc_handle h);
+
+/* ---- per-problem models ----
+ * A problem's model is the part of cmpc_config a Monte-Carlo study randomises: friction, cost weights and foot corners.  Fields are named and
+ * ordered as in cmpc_config: 34 packed doubles.  Everything else stays per handle: horizon, sampling_time, gravity, every solver option
+ * (tolerances, budgets, mu_*, tail polish, factor_storage) and the warm policy (cmpc_set_warm_policy).
+ * The model rule: friction_coefficient > 0 and finite; every weight finite and >= 0; each force_rate_of_change_weight > 0 (the Levenberg shift and
+ * the float32 factorisations depend on it); corners finite. */
+typedef struct {
+    double friction_coefficient;
+    double com_weight[3];
+    double angular_momentum_weight;
+    double contact_position_weight;
+    double force_rate_of_change_weight[3];
+    double contact_force_symmetry_weight;
+    double corners[2][4][3];
+} cmpc_model;
+#define CMPC_MODEL_DOUBLES 34
+void cmpc_model_from_config(const cmpc_config* cfg, cmpc_model* model);
+/* checks models[0..batch) against the model rule on the host: CMPC_OK, or CMPC_ERR_ARG for the first failing problem, and cmpc_last_error(NULL) names
+ * its index and field ("model 7: friction_coefficient = 0 must be > 0 and finite").  No handle, no GPU. */
+int cmpc_check_models(const cmpc_model* models, int batch);
+/* models[B] (host): problem b of every later launch of the handle -- cmpc_solve_device[_warm], cmpc_solve, cmpc_advance, the NLP evaluations,
+ * cmpc_plant_step_device and cmpc_rollout_tick_device -- uses models[b] in place of the config's model.  The derived constants are bit-equal to those
+ * of a handle created with that model in its config.  models is checked first (cmpc_check_models); on failure the handle keeps its previous table.
+ * NULL returns the handle to its config's model for every problem.  Synchronous: waits for the device before the table is replaced. */
+int cmpc_set_models(cmpc_handle h, const cmpc_model* models);
+/* the same from a device table dModels[B] (e.g. randomised in a torch tensor), derived by a kernel on `stream` (NULL: the handle's); later launches
+ * must be ordered after it.  Records are bit-equal to those of cmpc_set_models.  A row that breaks the model rule is not an error: dOk[b] = 0 (dOk[B] or
+ * NULL; 1 otherwise), that problem's solves return status 3 and their initial iterate, and its NLP evaluations and plant steps use the config's model;
+ * every other problem is untouched. */
+int cmpc_set_models_device(cmpc_handle h, const cmpc_model* dModels, int* dOk, void* stream);
 
 /* ---- NLP callbacks (what IPOPT evaluated through the generated code), batched on the device ----
  * any output pointer may be NULL.  dLamG[B][n_g], lam_f scalar (hess of lam_f f + lam_g^T g).

@@ -47,6 +47,22 @@ class CmpcTickIO(C.Structure):
         ("robot_mass", C.c_double), ("com_height", C.c_double), ("force_sample_time", C.c_int)]
 
 
+class CmpcModel(C.Structure):
+    """mirror of cmpc_model (include/cmpc.h): the per-problem part of cmpc_config, 34 packed doubles"""
+    _fields_ = [
+        ("friction_coefficient", C.c_double),
+        ("com_weight", C.c_double * 3),
+        ("angular_momentum_weight", C.c_double),
+        ("contact_position_weight", C.c_double),
+        ("force_rate_of_change_weight", C.c_double * 3),
+        ("contact_force_symmetry_weight", C.c_double),
+        ("corners", C.c_double * 24),
+    ]
+
+
+MODEL_DOUBLES = 34   # CMPC_MODEL_DOUBLES
+
+
 FACTORS = {None: 0, "auto": 0, "lds": 1, "hbm": 2}   # cmpc_config.factor_storage
 
 
@@ -62,6 +78,7 @@ EXPORTS = [
     "cmpc_get_parameters", "cmpc_get_parameters_device", "cmpc_allgather_compact_device",
     "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device", "cmpc_default_tolerance",
     "cmpc_contacts_force_sample_time", "cmpc_contacts_force_sample_time_device",
+    "cmpc_model_from_config", "cmpc_check_models", "cmpc_set_models", "cmpc_set_models_device",
 ]
 
 _lib = None
@@ -139,5 +156,11 @@ def lib():
             L.cmpc_rollout_tick_device.argtypes = [vp, i, d, i, C.POINTER(CmpcTickIO), vp]
         if hasattr(L, "cmpc_write_reference_from_planner_device"):
             L.cmpc_write_reference_from_planner_device.argtypes = [vp, fp, fp, i, d, d, d, d, fp, vp]
+        if hasattr(L, "cmpc_set_models"):
+            L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
+            L.cmpc_model_from_config.restype = None
+            L.cmpc_check_models.argtypes = [vp, i]
+            L.cmpc_set_models.argtypes = [vp, vp]
+            L.cmpc_set_models_device.argtypes = [vp, vp, vp, vp]
         _lib = L
     return _lib

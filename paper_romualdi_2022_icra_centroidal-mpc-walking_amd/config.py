@@ -12,6 +12,8 @@ import dataclasses
 import re
 from typing import Dict, List, Sequence, Tuple
 
+import numpy as np
+
 GRAVITY = 9.80665  # BLF StandardAccelerationOfGravitation
 
 
@@ -93,6 +95,23 @@ def generated_code_weights(which: str = "tmp", horizon_steps: int = 12,
     else:
         cfg.com_weight, cfg.contact_force_symmetry_weight = (10.0, 100.0, 200.0), 100.0
     return cfg
+
+
+# ---------------------------------------------------------------- per-problem models (include/cmpc.h, cmpc_model)
+MODEL_DOUBLES = 34   # friction 1 | com_weight 3 | angular_momentum 1 | contact_position 1 | force_rate_of_change 3 | symmetry 1 | corners [2][4][3]
+
+
+def model_row(cfg: CentroidalMPCConfig) -> np.ndarray:
+    """The model of one configuration as cmpc_model's 34 packed doubles (contacts in the configuration's sorted order, as cmpc_config.corners)."""
+    return np.concatenate([
+        [cfg.static_friction_coefficient], np.asarray(cfg.com_weight, np.float64), [cfg.angular_momentum_weight, cfg.contact_position_weight],
+        np.asarray(cfg.force_rate_of_change_weight, np.float64), [cfg.contact_force_symmetry_weight],
+        np.asarray([c.corners for c in cfg.contacts], np.float64).reshape(-1)]).astype(np.float64)
+
+
+def model_array(cfgs: Sequence[CentroidalMPCConfig]) -> np.ndarray:
+    """[B, 34] float64: one model row per configuration (BatchSolver.set_models / set_models_device, WalkingRollout(models=...))."""
+    return np.ascontiguousarray(np.stack([model_row(c) for c in cfgs]))
 
 
 # ---------------------------------------------------------------- YARP .ini reader (key subset)

@@ -39,10 +39,10 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     double com_height, long long snap_dt_ns, const int* snap_ok, hipStream_t stream);
 extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
                                              hipStream_t stream);
-extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, const float* dX, const float* dP,
+extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
                                      const double* t, float* pose, const int* n, hipStream_t stream);
-extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, const float* dX, const float* dP,
+extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream);
 
@@ -59,6 +59,10 @@ struct cmpc_handle_s {
     float* dX = nullptr;
     float* dInfo = nullptr;
     CmpcConsts* dConsts = nullptr;
+    double hExpK[CMPC_NMAX + 1];  // exp(-k), k = 0..N: the one transcendental of a model's record, computed once here (cmpc_consts_apply_model)
+    double* dExpK = nullptr;      // ... and its device copy (cmpc_set_models_device)
+    CmpcConsts* dModels = nullptr;  // [B] per-problem records (cmpc_set_models*), allocated on first use
+    bool models_set = false;      // launches read dModels[b] instead of dConsts
     float* dScratch = nullptr;   // factor storage when the horizon's LDS image exceeds 160 KiB
     float* dBox = nullptr;       // bounding-box limits upper[2][3] | lower[2][3] of the schedule sampler
     float* dDuals = nullptr;
@@ -235,6 +239,9 @@ int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out)
     HIPCHK_CREATE(hipEventCreate(&h->ev1));
     HIPCHK_CREATE(hipMalloc(&h->dInfo, sizeof(float) * CMPC_INFO_N * (size_t)batch));
     HIPCHK_CREATE(hipMalloc(&h->dConsts, sizeof(CmpcConsts)));
+    for (int k = 0; k <= cfg->horizon; ++k) h->hExpK[k] = std::exp(-(double)k);
+    HIPCHK_CREATE(hipMalloc(&h->dExpK, sizeof(double) * (cfg->horizon + 1)));
+    HIPCHK_CREATE(hipMemcpy(h->dExpK, h->hExpK, sizeof(double) * (cfg->horizon + 1), hipMemcpyHostToDevice));
     HIPCHK_CREATE(hipMalloc(&h->dBox, sizeof(float) * 12));
     if (h->warm_duals) {
         const size_t nd = (size_t)batch * (CMPC_NS * (cfg->horizon + 1) + 2 * CMPC_NI * cfg->horizon);
@@ -262,7 +269,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hXpin) hipHostFree(h->hXpin);
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals);
-    hipFree(h->dSnapT); hipFree(h->dSnapOk);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -277,27 +284,15 @@ static void fill_consts(cmpc_handle h, CmpcConsts& q)
     q.N = c.horizon; q.max_iter = c.max_iterations;
     q.exact_hessian = c.exact_hessian; q.final_extrap = c.final_extrapolation;
     q.tail_stages = c.tail_stages; q.tail_iters = c.tail_iterations; q.tail_trigger = (float)c.tail_trigger;
-    q.dt = (float)c.sampling_time; q.mu_fr = (float)c.friction_coefficient; q.grav = (float)c.gravity;
-    q.w_com0 = (float)c.com_weight[0]; q.w_com1 = (float)c.com_weight[1];
-    q.w_h = (float)c.angular_momentum_weight; q.w_pos = (float)c.contact_position_weight;
-    q.w_sym = (float)c.contact_force_symmetry_weight;
-    for (int i = 0; i < 3; ++i) q.D[i] = (float)(2.0 * c.force_rate_of_change_weight[i]);
-    for (int ct = 0; ct < 2; ++ct)
-        for (int j = 0; j < 4; ++j)
-            for (int i = 0; i < 3; ++i) q.corners[12 * ct + 3 * j + i] = (float)c.corners[ct][j][i];
-    for (int k = 0; k <= c.horizon; ++k) {
-        const double wz = 0.5 * c.com_weight[2] * (1.0 + std::exp(-(double)k));
-        q.wz2[k] = (float)(2.0 * wz * wz);
-    }
+    q.dt = (float)c.sampling_time; q.grav = (float)c.gravity;
     q.tol = (float)c.tolerance; q.step_tol = (float)c.step_tolerance; q.mu_init = (float)c.mu_init; q.mu_min = (float)c.mu_min;
-    // Levenberg shift: 5e-5 of the smallest cost curvature (2 w_rate).  It does not move the fixed
-    // point (the right-hand side is exact); it keeps the stage Hessians factorisable in float32 along
-    // directions the cost does not see (measured on MI355X: 1e-5..1e-2 all converge in the same
-    // number of iterations, 1e-1 doubles it)
+    // the model: friction, weights (wz2: w_z(k) = (w_cz/2)(1+exp(-k))), corners, and the Levenberg shift reg: 5e-5 of the smallest cost curvature
+    // (2 w_rate).  The shift does not move the fixed point (the right-hand side is exact); it keeps the stage Hessians factorisable in float32 along
+    // directions the cost does not see (measured on MI355X: 1e-5..1e-2 all converge in the same number of iterations, 1e-1 doubles it)
     {
-        double dmin = 2.0 * c.force_rate_of_change_weight[0];
-        for (int i = 1; i < 3; ++i) dmin = std::min(dmin, 2.0 * c.force_rate_of_change_weight[i]);
-        q.reg = (float)std::max(1e-5, 5e-5 * dmin);
+        cmpc_model m;
+        cmpc_model_from_config(&c, &m);
+        cmpc_consts_apply_model(q, m, h->hExpK);
 #ifdef CMPC_PROFILE
         if (const char* e = std::getenv("CMPC_REG")) q.reg = (float)std::atof(e);
 #endif
@@ -313,10 +308,15 @@ static void fill_consts(cmpc_handle h, CmpcConsts& q)
 #endif
 }
 
+// the corners the plant step reads: problem 0's, and the distance in floats to the next problem's (0: one set for the batch).  Device pointer arithmetic only.
+static const float* model_corners(cmpc_handle h) { return h->models_set ? h->dModels->corners : h->dConsts->corners; }
+static int corners_stride(cmpc_handle h) { return h->models_set ? (int)(sizeof(CmpcConsts) / sizeof(float)) : 0; }
+
 static void fill_params(cmpc_handle h, CmpcParams& p)
 {
     std::memset(&p, 0, sizeof(p));
-    p.kc = h->dConsts; p.N = h->cfg.horizon; p.B = h->B;
+    p.kc = h->models_set ? h->dModels : h->dConsts; p.N = h->cfg.horizon; p.B = h->B;
+    p.kc_per_problem = h->models_set ? 1 : 0;
     p.scratch = h->dScratch; p.scratch_stride = h->scratch_stride;
     // cold start: a fixed initial barrier parameter if the configuration names one, else per problem
     // mu0 = clamp(3.5 ep0^2, 0.03, 0.5) from the initial primal infeasibility ep0 (measured on 4096-problem batches:
@@ -732,8 +732,7 @@ int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, cons
     if (!h || !dX || !dP || !dStateIn || !dStateOut || !(step > 0) || substeps < 1)
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    const float* corners = h->dConsts->corners;  // device pointer arithmetic only
-    int rc = cmpc_launch_plant_step(h->cfg.horizon, h->B, (float)h->cfg.gravity, corners, dX, dP, dStateIn, dStateOut, dZmp, (float)step,
+    int rc = cmpc_launch_plant_step(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, dStateOut, dZmp, (float)step,
                                     substeps, (float)zmp_half_x, (float)zmp_half_y, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant step launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
@@ -1000,7 +999,7 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
     rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
     if (rc != CMPC_OK) return rc;
-    lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, h->dConsts->corners, io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
+    lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
                                 (float)io->plant_step, io->plant_substeps, (float)io->zmp_half_x, (float)io->zmp_half_y, io->dLand, io->dListT, io->dListPose,
                                 io->dListN, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (back) launch: ") + hipGetErrorString((hipError_t)lrc));
@@ -1018,6 +1017,103 @@ int cmpc_set_contact_lists(cmpc_handle h, int max_contacts, double now, const do
         if (box_upper[c] < box_lower[c]) return fail(h, CMPC_ERR_ARG, "cmpc_set_contact_lists: bounding box upper < lower");
     rc = cmpc_contacts_sample(h->cfg.horizon, h->cfg.sampling_time, h->B, max_contacts, now, t, pose, n, box_upper, box_lower, h->hP.data(), land);
     if (rc) return fail(h, rc, g_err);
+    return CMPC_OK;
+}
+
+
+// ---- per-problem models (include/cmpc.h) ----
+void cmpc_model_from_config(const cmpc_config* cfg, cmpc_model* m)
+{
+    if (!cfg || !m) return;
+    m->friction_coefficient = cfg->friction_coefficient;
+    for (int i = 0; i < 3; ++i) m->com_weight[i] = cfg->com_weight[i];
+    m->angular_momentum_weight = cfg->angular_momentum_weight;
+    m->contact_position_weight = cfg->contact_position_weight;
+    for (int i = 0; i < 3; ++i) m->force_rate_of_change_weight[i] = cfg->force_rate_of_change_weight[i];
+    m->contact_force_symmetry_weight = cfg->contact_force_symmetry_weight;
+    std::memcpy(m->corners, cfg->corners, sizeof(m->corners));
+}
+
+static std::string model_field_name(int i)
+{
+    static const char* const scalar[] = {"friction_coefficient", "com_weight[0]", "com_weight[1]", "com_weight[2]", "angular_momentum_weight",
+                                         "contact_position_weight", "force_rate_of_change_weight[0]", "force_rate_of_change_weight[1]",
+                                         "force_rate_of_change_weight[2]", "contact_force_symmetry_weight"};
+    if (i < 10) return scalar[i];
+    const int e = i - 10;
+    return "corners[" + std::to_string(e / 12) + "][" + std::to_string(e / 3 % 4) + "][" + std::to_string(e % 3) + "]";
+}
+
+int cmpc_check_models(const cmpc_model* models, int batch)
+{
+    if (!models || batch < 1) return fail(nullptr, CMPC_ERR_ARG, "cmpc_check_models: null table or batch < 1");
+    for (int b = 0; b < batch; ++b) {
+        const int i = cmpc_model_first_bad(models[b]);
+        if (i < 0) continue;
+        const char* rule = i == 0 ? "must be > 0 and finite" : (i >= 6 && i <= 8) ? "must be > 0 and finite" : i < 10 ? "must be >= 0 and finite" : "must be finite";
+        char val[40];
+        std::snprintf(val, sizeof(val), "%.17g", (&models[b].friction_coefficient)[i]);
+        return fail(nullptr, CMPC_ERR_ARG, "model " + std::to_string(b) + ": " + model_field_name(i) + " = " + val + " " + rule);
+    }
+    return CMPC_OK;
+}
+
+static int ensure_models(cmpc_handle h)
+{
+    if (!h->dModels) HIPCHK(h, hipMalloc(&h->dModels, sizeof(CmpcConsts) * (size_t)h->B));
+    return CMPC_OK;
+}
+
+int cmpc_set_models(cmpc_handle h, const cmpc_model* models)
+{
+    if (!h) return fail(nullptr, CMPC_ERR_ARG, "cmpc_set_models: null handle");
+    if (!models) {
+        h->models_set = false;   // (the table stays allocated: launches already queued may still read it)
+        return CMPC_OK;
+    }
+    if (cmpc_check_models(models, h->B) != CMPC_OK) return fail(h, CMPC_ERR_ARG, "cmpc_set_models: " + g_err);
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcConsts base;
+    fill_consts(h, base);
+    std::vector<CmpcConsts> rec((size_t)h->B, base);
+    for (int b = 0; b < h->B; ++b) cmpc_consts_apply_model(rec[b], models[b], h->hExpK);
+    int rc = ensure_models(h);
+    if (rc) return rc;
+    HIPCHK(h, hipDeviceSynchronize());   // (launches queued on any stream may still read the previous table)
+    HIPCHK(h, hipMemcpy(h->dModels, rec.data(), sizeof(CmpcConsts) * rec.size(), hipMemcpyHostToDevice));
+    h->models_set = true;
+    return CMPC_OK;
+}
+
+namespace {
+// one thread per problem: the handle's record, then problem b's model over it (cmpc_consts_apply_model: the host's statement, bit-equal records).
+// A row that breaks the model rule keeps the handle's model and is flagged (the solve returns status 3).
+__global__ __launch_bounds__(256) void cmpc_models_kernel(int B, const CmpcConsts* __restrict__ base, const double* __restrict__ expk,
+                                                          const cmpc_model* __restrict__ models, CmpcConsts* __restrict__ out, int* __restrict__ ok)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int* src = reinterpret_cast<const int*>(base);
+    int* dst = reinterpret_cast<int*>(out + b);
+    for (int e = 0; e < (int)(sizeof(CmpcConsts) / 4); ++e) dst[e] = src[e];
+    const cmpc_model m = models[b];
+    const bool bad = cmpc_model_first_bad(m) >= 0;
+    if (!bad) cmpc_consts_apply_model(out[b], m, expk);
+    out[b].model_bad = bad ? 1 : 0;
+    if (ok) ok[b] = bad ? 0 : 1;
+}
+}  // namespace
+
+int cmpc_set_models_device(cmpc_handle h, const cmpc_model* dModels, int* dOk, void* stream)
+{
+    if (!h || !dModels) return fail(h, CMPC_ERR_ARG, "cmpc_set_models_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ensure_models(h);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cmpc_models_kernel, dim3((h->B + 255) / 256), dim3(256), 0, stream ? (hipStream_t)stream : h->stream, h->B, h->dConsts, h->dExpK,
+                       dModels, h->dModels, dOk);
+    HIPCHK(h, hipGetLastError());
+    h->models_set = true;
     return CMPC_OK;
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/cmpc.h"
+
 #define CMPC_NS 15   // stage state: com, dcom, h, posL, posR
 #define CMPC_NF 24   // corner forces (contact c, corner j, axis i -> 12c+3j+i)
 #define CMPC_NQ 6    // foot-frame landing offsets (3c+i)
@@ -63,7 +65,51 @@ struct CmpcConsts {
     float corners[24];           // [c][j][3]
     float wz2[CMPC_NMAX + 1];    // 2 w_z(k)^2, w_z(k) = (w_cz/2)(1+exp(-k))
     int hwid_probe;              // diagnostic build only: phase_export overwrites x[0..7] with the HW_ID of each wave
-};
+    int model_bad;               // a per-problem record whose model broke the model rule (cmpc_set_models_device): the solve returns status 3 at once
+};                               // (this field keeps the struct at 368 bytes after the 16-byte rounding of its LDS slot)
+
+// The model rule of include/cmpc.h: -1 if m satisfies it, else the index of the first failing double in cmpc_model's packed order.
+__host__ __device__ inline int cmpc_model_first_bad(const cmpc_model& m)
+{
+    const double* v = &m.friction_coefficient;
+    for (int i = 0; i < CMPC_MODEL_DOUBLES; ++i) {
+        const double x = v[i];
+        const bool ok = i == 0 ? (x > 0 && __builtin_isfinite(x))                      // friction
+                      : (i >= 6 && i <= 8) ? (x > 0 && __builtin_isfinite(x))          // force_rate_of_change_weight
+                      : i < 10 ? (x >= 0 && __builtin_isfinite(x))                     // the other weights
+                               : __builtin_isfinite(x);                                // corners
+        if (!ok) return i;
+    }
+    return -1;
+}
+
+// The model's part of a CmpcConsts record, one statement for the host (cmpc_create, cmpc_set_models) and the device (cmpc_set_models_device), so that
+// the records are bit-equal.  expk[k] = exp(-k), k = 0..q.N, computed once on the host in double (no device exp enters the record); only correctly
+// rounded double operations follow, and contraction into fma is off.
+__host__ __device__ inline void cmpc_consts_apply_model(CmpcConsts& q, const cmpc_model& m, const double* expk)
+{
+#pragma clang fp contract(off)
+    q.mu_fr = (float)m.friction_coefficient;
+    q.w_com0 = (float)m.com_weight[0]; q.w_com1 = (float)m.com_weight[1];
+    q.w_h = (float)m.angular_momentum_weight; q.w_pos = (float)m.contact_position_weight;
+    q.w_sym = (float)m.contact_force_symmetry_weight;
+    for (int i = 0; i < 3; ++i) q.D[i] = (float)(2.0 * m.force_rate_of_change_weight[i]);
+    for (int ct = 0; ct < 2; ++ct)
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < 3; ++i) q.corners[12 * ct + 3 * j + i] = (float)m.corners[ct][j][i];
+    for (int k = 0; k <= q.N; ++k) {
+        const double wz = 0.5 * m.com_weight[2] * (1.0 + expk[k]);
+        q.wz2[k] = (float)(2.0 * wz * wz);
+    }
+    // Levenberg shift: 5e-5 of the smallest cost curvature (2 w_rate), at least 1e-5 (the reasons: fill_consts, cmpc_api.hip)
+    double dmin = 2.0 * m.force_rate_of_change_weight[0];
+    for (int i = 1; i < 3; ++i) {
+        const double d = 2.0 * m.force_rate_of_change_weight[i];
+        dmin = d < dmin ? d : dmin;        // std::min
+    }
+    const double r = 5e-5 * dmin;
+    q.reg = (float)(1e-5 < r ? r : 1e-5);  // std::max(1e-5, r)
+}
 
 // The same layout as closed-form index functions.  Device code uses these: indexing the offset arrays
 // of CmpcLayout with a run-time contact/corner number forces the whole struct into scratch memory
@@ -113,4 +159,5 @@ struct CmpcParams {
     float* scratch;              // per-problem factor storage when it does not fit in LDS, else null
     long long scratch_stride;    // floats per problem
     int lds_words;               // 4-byte words of dynamic LDS the launch was given (set by cmpc_launch_solver)
+    int kc_per_problem;          // 0: kc is the batch's one record; 1: kc[B], one record per problem (cmpc_set_models)
 };

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void cmpc_nlp_eval_kernel(CmpcParams kp, const
     const int N = kp.N;
     CmpcConsts& K = *reinterpret_cast<CmpcConsts*>(smem);
     {
-        const int* src = reinterpret_cast<const int*>(kp.kc);
+        const int* src = reinterpret_cast<const int*>(kp.kc_per_problem ? kp.kc + b : kp.kc);
         int* dst = reinterpret_cast<int*>(smem);
         for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += NT) dst[e] = src[e];
     }
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void cmpc_nlp_grad_kernel(CmpcParams kp, const
     const int N = kp.N;
     CmpcConsts& K = *reinterpret_cast<CmpcConsts*>(smem);
     {
-        const int* src = reinterpret_cast<const int*>(kp.kc);
+        const int* src = reinterpret_cast<const int*>(kp.kc_per_problem ? kp.kc + b : kp.kc);
         int* dst = reinterpret_cast<int*>(smem);
         for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += NT) dst[e] = src[e];
     }
@@ -649,7 +649,8 @@ extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev
 namespace {
 
 // (problem b, one thread.  state_in / state_out may alias: everything is read before anything is written)
-__device__ inline void plant_step_problem(int N, int b, float grav, const float* __restrict__ corners, const float* __restrict__ X,
+// corners: [2][4][3] of problem 0; problem b's are corners_stride floats further on (0: one set for the batch; per-problem models: the stride of the records)
+__device__ inline void plant_step_problem(int N, int b, float grav, const float* __restrict__ corners, int corners_stride, const float* __restrict__ X,
                                           const float* __restrict__ P, const float* state_in, float* state_out, float* __restrict__ zmp, float h,
                                           int nsub, float zx, float zy)
 {
@@ -669,7 +670,7 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
         const bool on = p[L.pGam(c)] > 0.5f;
         double F[3] = {0, 0, 0}, T[3] = {0, 0, 0};
         for (int j = 0; j < 4; ++j) {
-            const float* cn = corners + 12 * c + 3 * j;
+            const float* cn = corners + (size_t)b * corners_stride + 12 * c + 3 * j;
             double fl[3];
             for (int i = 0; i < 3; ++i) {
                 cp[4 * c + j][i] = (double)x[L.oPos(c) + i] + (double)R[i] * cn[0] + (double)R[3 + i] * cn[1] + (double)R[6 + i] * cn[2];
@@ -731,14 +732,14 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
     }
 }
 
-__global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, float grav, const float* __restrict__ corners,
+__global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                               const float* __restrict__ X, const float* __restrict__ P,
                                                               const float* state_in, float* state_out,
                                                               float* __restrict__ zmp, float h, int nsub, float zx, float zy)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    plant_step_problem(N, b, grav, corners, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
+    plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
 }
 
 // ---- the two ends of a roll-out tick as ONE launch each (cmpc_rollout_tick_device).  At B <= 256 a tick is a 0.66 ms solve between nine launches of a
@@ -868,14 +869,14 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
 }
 
 // post: one thread per problem -- the plant step, then the step adjustment of its two feet (getOutput().contactPhaseList)
-__global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners,
+__global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy, const int* __restrict__ land,
                                                              const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    plant_step_problem(N, b, grav, corners, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
+    plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
     const CmpcIdx L{N};
     for (int c = 0; c < 2; ++c) {
         const int e = 2 * b + c, lk = land[e];
@@ -902,20 +903,20 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
     return (int)hipGetLastError();
 }
 
-extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, const float* dX, const float* dP,
+extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
                                      const double* t, float* pose, const int* n, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_tick_post_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, dX, dP, dStateIn, dStateOut, dZmp,
+    hipLaunchKernelGGL(cmpc_tick_post_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn, dStateOut, dZmp,
                        h, nsub, zx, zy, land, t, pose, n);
     return (int)hipGetLastError();
 }
 
-extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, const float* dX, const float* dP,
+extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, dX, dP, dStateIn,
+    hipLaunchKernelGGL(cmpc_plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn,
                        dStateOut, dZmp, h, nsub, zx, zy);
     return (int)hipGetLastError();
 }

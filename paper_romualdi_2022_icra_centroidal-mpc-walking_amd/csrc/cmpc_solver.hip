@@ -3421,9 +3421,9 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
         for (int e = tid; e < kp.lds_words; e += NT) z[e] = 0;
     }
     __syncthreads();
-    // constants first in LDS
+    // constants first in LDS (the problem's own record when the handle has per-problem models, cmpc_set_models)
     {
-        const int* src = reinterpret_cast<const int*>(kp.kc);
+        const int* src = reinterpret_cast<const int*>(kp.kc_per_problem ? kp.kc + b : kp.kc);
         int* dst = reinterpret_cast<int*>(smem);
         for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += NT) dst[e] = src[e];
     }
@@ -3437,7 +3437,8 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
     float* const fg_base = FG ? kp.scratch + (size_t)b * kp.scratch_stride : nullptr;
     const CmpcIdx L{N};
     __syncthreads();
-    const bool outside = phase_setup<NT, NC, FG>(lds, N, fg_base, kp.P + (size_t)b * L.np()) != 0;
+    // (model_bad: a per-problem model that broke the model rule, cmpc_set_models_device -- workgroup-uniform, as the subset flag)
+    const bool outside = (phase_setup<NT, NC, FG>(lds, N, fg_base, kp.P + (size_t)b * L.np()) != 0) | (prm.model_bad != 0);
     // Two passes at most: a warm-started solve (shifted previous solution) that exhausts its iteration budget is started
     // again from the cold start -- rare (a landing or lift-off tick, 1 in ~60000 solves of a walking roll-out) and cheaper than
     // failing the tick, which is all the caller could do (CentroidalMPCBlock.cpp:615-619 aborts).

@@ -13,7 +13,7 @@ from .config import GRAVITY
 
 from .contacts import PlannedContact, pack_lists
 from .layout import Layout
-from .solver import BatchSolver
+from .solver import BatchSolver, _model_array
 
 FOOT_Y = 0.08
 
@@ -42,10 +42,13 @@ class WalkingRollout:
     stragglers are solved again from the cold start in a small launch of their own (a CU each); None: they stay unconverged -- which is all
     the reference can do: its advance() returns false and the tick is aborted (CentroidalMPCBlock.cpp:615-619).
     force_sample_time: every tick snaps the planner's lists to the MPC grid before the merge (forceSampleTime, CentroidalMPCBlock.cpp:586-592; the rule of
-    include/cmpc.h), on both tick paths and after a replan; a list that fails to snap aborts the tick like a failed merge (rec["merge_ok"])."""
+    include/cmpc.h), on both tick paths and after a replan; a list that fails to snap aborts the tick like a failed merge (rec["merge_ok"]).
+    models: per-problem models (include/cmpc.h, cmpc_set_models) -- B configurations, a [B, 34] array (config.model_array), or a [B, 34] float64 CUDA
+    tensor (set on the device: a row that breaks the model rule gives its problem status 3 every tick, self.models_ok[b] = 0).  The horizon, sampling
+    time, contacts' bounding boxes and solver options stay cfg's.  retry="launch" solves the stragglers with their own models."""
 
     def __init__(self, cfg, batch, plan=None, device=0, substeps=6, com_speed=None, warm_budget=14, retry="kernel", retry_batch=256, native_tick=True,
-                 force_sample_time=False, **solver_opts):
+                 force_sample_time=False, models=None, **solver_opts):
         import torch
         self.torch = torch
         self.cfg, self.B = cfg, batch
@@ -60,6 +63,14 @@ class WalkingRollout:
         self.force_sample_time = bool(force_sample_time)
         self.solver.set_warm_policy(warm_budget, restart_in_kernel=(retry == "kernel"))
         self.solver2 = BatchSolver(cfg, self.retry_batch, device=device, **solver_opts) if retry == "launch" else None
+        self.models, self.models_ok = None, None
+        if models is not None:
+            if isinstance(models, torch.Tensor) and models.is_cuda:
+                self.models = models.to(self.dev, torch.float64).contiguous()
+                self.models_ok = self.solver.set_models_device(self.models)
+            else:
+                self.solver.set_models(models)
+                self.models = torch.from_numpy(_model_array(models, batch)).to(self.dev)
         plan = plan or walking_plan(cfg)
         t, pose, n = pack_lists(cfg, [plan])
         M = t.shape[2] + 1     # the merged list holds at most the current contact + the planner's future contacts
@@ -147,6 +158,8 @@ class WalkingRollout:
                     X02[:, L.pos[c]:L.pos[c] + 3 * (N + 1)] = P2[:, L.p_nom[c]:L.p_nom[c] + 3 * (N + 1)]
                     for j in range(4):
                         X02[:, L.f[c][j] + 2:L.f[c][j] + 3 * N:3] = GRAVITY / 8.0
+                if self.models is not None:     # (the retry handle's table: the stragglers' own models, row for row)
+                    self.solver2.set_models_device(self.models.index_select(0, idx))
                 X2, I2 = self.solver2.solve_device(P2, X02)
                 I2[:, 0] += dInfo.index_select(0, idx)[:, 0]     # iterations of both attempts
                 I2[:, 3] += 10000.0                              # safeguard word: solved again from the cold start

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .config import GRAVITY, CentroidalMPCConfig, from_ini
+from .config import GRAVITY, CentroidalMPCConfig, from_ini, model_array
 from .contacts import PlannedContact, pack_lists, sample_schedule, sample_schedule_batch
 from .layout import Layout
 
@@ -51,6 +51,17 @@ def _c_config(cfg: CentroidalMPCConfig, tolerance=None, mu_min=None, max_iterati
     c.tail_stages, c.tail_iterations, c.tail_trigger = int(tail_stages), int(tail_iterations), float(tail_trigger)
     c.factor_storage = _capi.FACTORS[factors]   # None / "auto": by batch size and horizon; "lds" / "hbm": the resident / the HBM-factor variant
     return c
+
+
+def _model_array(models, batch) -> np.ndarray:
+    """[B, 34] float64 C-contiguous host array from B configurations or an array of model rows"""
+    if isinstance(models, (list, tuple)) and models and isinstance(models[0], CentroidalMPCConfig):
+        a = model_array(models)
+    else:
+        a = np.ascontiguousarray(models.cpu().numpy() if hasattr(models, "cpu") else models, np.float64)
+    if a.shape != (batch, _capi.MODEL_DOUBLES):
+        raise ValueError(f"models: expected shape ({batch}, {_capi.MODEL_DOUBLES}), got {a.shape}")
+    return a
 
 
 class BatchSolver:
@@ -138,6 +149,31 @@ class BatchSolver:
         if rc not in (0, -3):
             raise RuntimeError(f"cmpc_solve failed ({rc}): {self.last_error}")
         return X, info, rc
+
+    def set_models(self, models):
+        """cmpc_set_models: per-problem models (include/cmpc.h) -- a list of B CentroidalMPCConfig (only their model fields are read: friction,
+        weights, corners), or an array [B, 34] float64 in cmpc_model's order (config.model_array); None: back to the handle's configuration.
+        Checked on the host: a row that breaks the model rule raises ValueError naming its index and field, and the previous table stays."""
+        if models is None:
+            rc = self._lib.cmpc_set_models(self._h, None)
+        else:
+            a = _model_array(models, self.batch)
+            rc = self._lib.cmpc_set_models(self._h, a.ctypes.data)
+            if rc == -1:
+                raise ValueError(self.last_error)
+        if rc != 0:
+            raise RuntimeError(f"cmpc_set_models failed ({rc}): {self.last_error}")
+
+    def set_models_device(self, models, ok=None):
+        """cmpc_set_models_device: models a [B, 34] float64 CUDA tensor (cmpc_model's order), the records derived by a kernel on torch's current
+        stream.  A row that breaks the model rule is not an error: ok[b] = 0 (int32 [B], returned) and that problem's solves return status 3."""
+        import torch
+        assert models.is_cuda and models.dtype == torch.float64 and models.is_contiguous() and tuple(models.shape) == (self.batch, _capi.MODEL_DOUBLES)
+        if ok is None:
+            ok = torch.empty((self.batch,), dtype=torch.int32, device=models.device)
+        assert ok.dtype == torch.int32 and ok.is_contiguous() and ok.numel() == self.batch
+        self._launch(models.device, lambda st: self._lib.cmpc_set_models_device(self._h, models.data_ptr(), ok.data_ptr(), st))
+        return ok
 
     def set_warm_policy(self, warm_budget: int = 0, restart_in_kernel: bool = True):
         """cmpc_set_warm_policy: iteration budget of a warm-started pass (0: max_iterations) and whether a warm start that does not
