@@ -197,6 +197,45 @@ int cmpc_nlp_sparsity(int horizon, int* jac_row, int* jac_col, int* hess_row, in
 int cmpc_eval_nlp_grad_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float lam_f,
                               float* dGradX, float* dGradP, void* stream);
 
+/* ---- multipliers of the reference NLP (what CasADi's Opti -> IPOPT hands back as lam_g), its KKT certificate and the gradient of the optimal cost ----
+ * cmpc_set_multiplier_output(h, 1): every later solve on the handle -- cmpc_solve, cmpc_solve_device[_warm], cmpc_advance, the solve inside
+ * cmpc_rollout_tick_device -- also writes the handle's dual record of each problem (costates, slacks and multipliers of the solver's stage form,
+ * [B][15 (N+1) + 88 N] floats, allocated on first use; ~8 KB per problem at N = 20), taken at the x the solve returns.  0 frees it.  Off (the default),
+ * no record exists and x / info are those of a handle that never turned it on.  The record is read only by the calls below, never by a solve.
+ *
+ * cmpc_get_multipliers_device: dLamG[B][n_g] of the LAST solve on the handle, whose dX / dP the caller passes again (the initial-condition rows are
+ * recovered from x and p).  n_g = 53N + 15, rows in the order of the reference's g (cmpc_nlp_sparsity): init[15] com[3N] dcom[3N] h[3N] pos_c[3N]
+ * (c = 0, 1) then per contact bbox_c[3N] fric_c[16N].  Sign convention of IPOPT and of the goldens: L = f + lam_g^T g, lam >= 0 at an active upper
+ * bound, <= 0 at an active lower bound.  Row by row (derivation: DESIGN.md, "Multipliers"):
+ *   com / dcom / h rows of stage k (x_{k+1} - phi_k(x_k, u_k)): minus the solver's costate of stage k+1, formed at the returned x;
+ *   pos_c rows of stage k: minus the foot's costate of stage k+1 in stance; exactly 0 in swing (vel is free and costs nothing: dL/dvel = 0);
+ *   bbox_c rows of stage k: in swing, zU - zL of the offset's upper and lower rows; a component with lower == upper (the solver eliminates it)
+ *     -(R_k^T lam_pos)_i from stationarity in the landing position; in stance exactly 0 -- the row duplicates the landing row (subset rule 3) and the
+ *     multiplier, not unique there, is put entirely on the landing row;
+ *   fric_c rows (upper bound 0): the solver's friction multipliers z;
+ *   init rows (Jacobian = identity on com_0 dcom_0 h_0 pos_0): lam_init = -grad_x (f + lam'^T g) on those columns, lam' = lam_g without them (nlp_grad).
+ * A problem with status 3 gets zeros; status 1 or 2 the values of the last iterate.  CMPC_ERR_ARG when the output is off.
+ * cmpc_get_multipliers: the same for the handle's own problem set after cmpc_advance, into host memory (synchronous). */
+int cmpc_set_multiplier_output(cmpc_handle h, int enabled);
+int cmpc_get_multipliers_device(cmpc_handle h, const float* dX, const float* dP, float* dLamG, void* stream);
+int cmpc_get_multipliers(cmpc_handle h, float* LamG);
+/* KKT certificate of the reference NLP at (x, lam_g), per problem, in double on the device (f, g and grad_x L from the restatement of the generated
+ * code above; bounds built from p: init rows = com0 dcom0 h0 currentPos, dynamics rows 0, box rows [lower, upper], friction rows (-inf, 0]).
+ * dCert[B][CMPC_CERT] = { stationarity  max|grad f + J^T lam| / scale,  scale = max(1, max|lam|),
+ *                         primal infeasibility  max(lbg - g, g - ubg, 0),
+ *                         complementarity  max |lam_i dist(g_i, nearer bound)| / scale over inequality rows (ubg - lbg > 1e-12),
+ *                         sign violation  max wrong-sign |lam_i| / scale (lam >= 0 on rows bounded above only, <= 0 below only, the sign of the nearer
+ *                           bound on two-sided rows),
+ *                         f,  status of the handle's last solve (-1 when the multiplier output is off),  scale,  max|grad f + J^T lam| }.
+ * Per-problem models (cmpc_set_models*) apply. */
+#define CMPC_CERT 8
+int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dCert, void* stream);
+/* Gradient of the optimal cost with respect to every parameter (envelope theorem) at a KKT point (x*, lam*): dGradP[B][n_p] = grad_p L(x, lam)
+ * (nlp_grad, lam_f = 1) plus the parameters that only enter the bounds: -lam_init on com0, dcom0, h0 and currentPos; -max(lam, 0) on upper and
+ * -min(lam, 0) on lower of each box row.  The entries of enabled (Gamma, binary) and R (constrained to rotations) are formal derivatives of the
+ * generated code, not derivatives along feasible perturbations.  No derivatives with respect to the per-problem model fields. */
+int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream);
+
 /* ---- class-shaped setters (host buffers -> the handle's own device P, X0) ----
  * batch-major float32; NULL keeps the previous value (zeros initially).
  *   state    [B][9]            com0, dcom0, h0 (h and wrench already mass-normalised,

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("CMPC_LIB", "libcmpc_hip.so"))   # (CMPC_LIB: developer knob, another build of the same library in the package directory)
 
 INFO = 8
+CERT = 8   # CMPC_CERT: fields of the KKT certificate (include/cmpc.h)
 
 
 class CmpcConfig(C.Structure):
@@ -79,6 +80,8 @@ EXPORTS = [
     "cmpc_rollout_tick_device", "cmpc_write_reference_from_planner_device", "cmpc_default_tolerance",
     "cmpc_contacts_force_sample_time", "cmpc_contacts_force_sample_time_device",
     "cmpc_model_from_config", "cmpc_check_models", "cmpc_set_models", "cmpc_set_models_device",
+    "cmpc_set_multiplier_output", "cmpc_get_multipliers_device", "cmpc_get_multipliers", "cmpc_kkt_certificate_device",
+    "cmpc_value_gradient_device",
 ]
 
 _lib = None
@@ -148,6 +151,11 @@ def lib():
         L.cmpc_write_state_device.argtypes = [vp, fp, fp, fp, vp]
         L.cmpc_shift_solution_device.argtypes = [vp, fp, fp, vp]
         L.cmpc_eval_nlp_grad_device.argtypes = [vp, fp, fp, fp, C.c_float, fp, fp, vp]
+        L.cmpc_set_multiplier_output.argtypes = [vp, C.c_int]
+        L.cmpc_get_multipliers_device.argtypes = [vp, fp, fp, fp, vp]
+        L.cmpc_get_multipliers.argtypes = [vp, fp]
+        L.cmpc_kkt_certificate_device.argtypes = [vp, fp, fp, fp, fp, vp]
+        L.cmpc_value_gradient_device.argtypes = [vp, fp, fp, fp, fp, vp]
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

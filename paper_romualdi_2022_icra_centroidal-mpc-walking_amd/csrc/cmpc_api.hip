@@ -20,6 +20,9 @@ extern "C" int cmpc_launch_nlp_eval(const CmpcParams* prm, const float* dX, cons
                                     hipStream_t stream);
 extern "C" int cmpc_launch_nlp_grad(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float lam_f, float* dGradX,
                                     float* dGradP, hipStream_t stream);
+extern "C" int cmpc_launch_multipliers(const CmpcParams* prm, const float* dX, const float* dP, float* dLamG, hipStream_t stream);
+extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dCert, hipStream_t stream);
+extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream);
 extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev, float* dX0, hipStream_t stream);
 extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double* plan_t, const float* plan_pose, const int* plan_n,
                                           const double* mpc_t, const float* mpc_pose, const int* mpc_n, double* out_t, float* out_pose,
@@ -65,7 +68,9 @@ struct cmpc_handle_s {
     bool models_set = false;      // launches read dModels[b] instead of dConsts
     float* dScratch = nullptr;   // factor storage when the horizon's LDS image exceeds 160 KiB
     float* dBox = nullptr;       // bounding-box limits upper[2][3] | lower[2][3] of the schedule sampler
-    float* dDuals = nullptr;
+    float* dDuals = nullptr;     // the dual record of the last solve [B][NS (N+1) + 2 NI N] (cmpc_set_multiplier_output, or the diagnostic knob below)
+    bool mult_out = false;       // cmpc_set_multiplier_output: every solve writes dDuals
+    float* dLamG = nullptr;      // [B][n_g] staging of cmpc_get_multipliers (allocated on first use)
     double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
     int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
@@ -268,7 +273,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->hXpin) hipHostFree(h->hXpin);
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
-    hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals);
+    hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG);
     hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -325,7 +330,7 @@ static void fill_params(cmpc_handle h, CmpcParams& p)
     p.mu_adapt = h->cfg.mu_init > 0 ? 0.f : h->mu_adapt;
     p.t_floor = 1e-2f;
     p.warm_budget = h->warm_budget; p.warm_no_restart = h->warm_no_restart;
-    p.duals = h->dDuals; p.warm_duals = h->warm_duals;
+    p.duals = (h->mult_out || h->warm_duals) ? h->dDuals : nullptr; p.warm_duals = h->warm_duals;
 }
 
 static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm)
@@ -687,6 +692,73 @@ int cmpc_eval_nlp_grad_device(cmpc_handle h, const float* dX, const float* dP, c
     fill_params(h, p);
     int rc = cmpc_launch_nlp_grad(&p, dX, dP, dLamG, lam_f, dGradX, dGradP, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("nlp grad launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+// ---- multipliers of the reference NLP (include/cmpc.h) ----
+int cmpc_set_multiplier_output(cmpc_handle h, int enabled)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_set_multiplier_output: null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (enabled && !h->dDuals) {
+        const size_t nd = (size_t)h->B * (CMPC_NS * (h->cfg.horizon + 1) + 2 * CMPC_NI * h->cfg.horizon);
+        HIPCHK(h, hipMalloc(&h->dDuals, sizeof(float) * nd));
+        HIPCHK(h, hipMemsetAsync(h->dDuals, 0, sizeof(float) * nd, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else if (!enabled && h->dDuals && !h->warm_duals) {   // (the diagnostic warm start with duals keeps its record)
+        HIPCHK(h, hipDeviceSynchronize());   // (a launch on any stream may still write the record)
+        HIPCHK(h, hipFree(h->dDuals));
+        h->dDuals = nullptr;
+    }
+    h->mult_out = enabled != 0;
+    return CMPC_OK;
+}
+
+int cmpc_get_multipliers_device(cmpc_handle h, const float* dX, const float* dP, float* dLamG, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG) return fail(h, CMPC_ERR_ARG, "cmpc_get_multipliers_device: null argument");
+    if (!h->mult_out || !h->dDuals) return fail(h, CMPC_ERR_ARG, "cmpc_get_multipliers_device: the multiplier output is off (cmpc_set_multiplier_output)");
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcParams p;
+    fill_params(h, p);
+    int rc = cmpc_launch_multipliers(&p, dX, dP, dLamG, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("multipliers launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_get_multipliers(cmpc_handle h, float* LamG)
+{
+    if (!h || !LamG) return fail(h, CMPC_ERR_ARG, "cmpc_get_multipliers: null argument");
+    if (!h->have_solution) return fail(h, CMPC_ERR_ARG, "cmpc_get_multipliers: no solution yet (cmpc_advance)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->B * h->L.ng;
+    if (!h->dLamG) HIPCHK(h, hipMalloc(&h->dLamG, sizeof(float) * n));
+    int rc = cmpc_get_multipliers_device(h, h->dX, h->dP, h->dLamG, nullptr);
+    if (rc != CMPC_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(LamG, h->dLamG, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CMPC_OK;
+}
+
+int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dCert, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dCert) return fail(h, CMPC_ERR_ARG, "cmpc_kkt_certificate_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcParams p;
+    fill_params(h, p);
+    int rc = cmpc_launch_kkt_certificate(&p, dX, dP, dLamG, dCert, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("kkt certificate launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradP) return fail(h, CMPC_ERR_ARG, "cmpc_value_gradient_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcParams p;
+    fill_params(h, p);
+    int rc = cmpc_launch_value_gradient(&p, dX, dP, dLamG, dGradP, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("value gradient launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
 }
 

@@ -2852,6 +2852,12 @@ __device__ __attribute__((noinline)) void phase_costate(lds_t lds, int Nrt, floa
     const bool use_exact = __builtin_amdgcn_readfirstlane((int)exact_in) != 0;
     costate_update(c, prm, tid, ap, use_exact);
 }
+// The multiplier of a row after the affine-scaling extrapolation (dual record only): the full affine step projected onto z >= 0, row by row, instead of
+// the common dual step length of the iterations, which one row whose multiplier goes to zero would cut short for every other row.  A row that leaves the
+// active set ends at 0.  (Measured against the common step length over 5 x 512 problems: worst stationarity 6.1e-5 / 9.2e-5 against 5.4e-5 / 8.3e-5 on configs 3 / 5 --
+// no gain in the worst case; kept because a per-row extrapolation does not depend on which row blocks the step.)
+__device__ inline float dual_extrapolate(float z, float dz) { return fmaxf(z + dz, 0.f); }
+
 // ---- tail polish (out of line: rare, and the driver keeps its register allocation).  Stages k0 .. N-1 with the state entering stage
 // k0 and the force before it held form a small problem of their own.  Why: the final extrapolation is exact to first order where the
 // central path is smooth in mu; rows that are (nearly) degenerate -- slack and multiplier both -> 0: the friction rows of an unloaded
@@ -2862,10 +2868,11 @@ __device__ __attribute__((noinline)) void phase_costate(lds_t lds, int Nrt, floa
 // (row_target: conditioning as in the main loop), then its own affine-scaling step.  Stated in oracle/ipm_ref.c:tail_polish.
 // Returns nothing: a factorisation that fails leaves the converged iterate of the pass before. ----
 template <int NT, int NC, bool FG>
-__device__ __attribute__((noinline)) void tail_polish(lds_t lds, int Nrt, float* fg_base, int k0_in)
+__device__ __attribute__((noinline)) void tail_polish(lds_t lds, int Nrt, float* fg_base, int k0_in, bool duals_in)
 {
     CMPC_PHASE_PROLOGUE;
     const int k0 = __builtin_amdgcn_readfirstlane(k0_in);
+    const bool duals = __builtin_amdgcn_readfirstlane((int)duals_in) != 0;
     // tail_iters Newton steps at least; while a step was blocked (a row on its way to becoming active: the multipliers need their
     // iterations) up to six more, then the affine-scaling step
     bool last = false, blocked = true;   // (step lengths come out of block reductions: uniform)
@@ -2898,8 +2905,15 @@ __device__ __attribute__((noinline)) void tail_polish(lds_t lds, int Nrt, float*
         blocked = ap < 0.9f || ad < 0.9f;
         for (int e = tid + NS * (k0 + 1); e < NS * (N + 1); e += NT) c.S[e] += ap * c.dS[e];
         for (int e = tid + NU * k0; e < NU * N; e += NT) c.U[e] += ap * c.dU[e];
+        // (the affine-scaling step moves the primal iterate only; with the dual record exported it moves the tail's slacks and multipliers as well, after
+        //  their last use -- the multipliers row by row, dual_extrapolate: they then belong to the returned x)
         if (!last)
             for (int e = tid + NI * k0; e < NI * N; e += NT) { c.T[e] += ap * c.dT[e]; c.Z[e] += ad * c.dZ[e]; }
+        else if (duals)
+            for (int e = tid + NI * k0; e < NI * N; e += NT) {
+                const float tn = c.T[e] + ap * c.dT[e], zn = dual_extrapolate(c.Z[e], c.dZ[e]);
+                if (fabsf(tn) < INFINITY && fabsf(zn) < INFINITY) { c.T[e] = tn; c.Z[e] = zn; }
+            }
         __syncthreads();
     }
 }
@@ -3028,11 +3042,14 @@ __device__ __attribute__((noinline)) float phase_update(lds_t lds, int Nrt, floa
 
 // ---- the last step of a converged solve (out of line: it runs once, and the driver keeps its register allocation): the affine-scaling
 // step that phase_forward(affine) has just computed is applied -- primal only -- and, where the tail asks for it, the tail is polished.
-// Returns true if the tail was polished. ----
+// Returns true if the tail was polished.  duals (the dual record is exported, cmpc_set_multiplier_output): the slacks and multipliers take the same
+// affine-scaling step (dT, dZ of the same sweep, dual step length ad), so that the record belongs to the returned x; stages of a polished tail take theirs
+// inside tail_polish.  Nothing the primal iterate depends on reads them afterwards (the tail's passes start at stage k0). ----
 template <int NT, int NC, bool FG>
-__device__ __attribute__((noinline)) bool phase_finish(lds_t lds, int Nrt, float* fg_base)
+__device__ __attribute__((noinline)) bool phase_finish(lds_t lds, int Nrt, float* fg_base, bool duals_in)
 {
     CMPC_PHASE_PROLOGUE;
+    const bool duals = __builtin_amdgcn_readfirstlane((int)duals_in) != 0;
     float ap, ad;
     step_lengths<NT>(c, tid, 0.999f, ap, ad);
     // size of the step: over everything (NaN-aware: a step that is not finite is not taken -- the converged iterate stands) and over
@@ -3060,9 +3077,14 @@ __device__ __attribute__((noinline)) bool phase_finish(lds_t lds, int Nrt, float
     if (k0 < N) step_lengths<NT>(c, tid, 0.999f, ap, ad, 0, k0);
     for (int e = tid; e < NS * (k0 < N ? k0 + 1 : N + 1); e += NT) c.S[e] += ap * c.dS[e];
     for (int e = tid; e < NU * k0; e += NT) c.U[e] += ap * c.dU[e];
+    if (duals)   // (a row whose step is not finite keeps its converged values: the check above covers the primal step only)
+        for (int e = tid; e < NI * k0; e += NT) {
+            const float tn = c.T[e] + ap * c.dT[e], zn = dual_extrapolate(c.Z[e], c.dZ[e]);
+            if (fabsf(tn) < INFINITY && fabsf(zn) < INFINITY) { c.T[e] = tn; c.Z[e] = zn; }
+        }
     __syncthreads();
     if (k0 == N) return false;
-    tail_polish<NT, NC, FG>(lds, N, fg_base, k0);
+    tail_polish<NT, NC, FG>(lds, N, fg_base, k0, duals);
     return true;
 }
 
@@ -3371,9 +3393,14 @@ __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int N
     return r;
 }
 
-// x in the reference layout (and, warm starts with duals, the costates, slacks and multipliers)
+// x in the reference layout and, where the handle keeps it (cmpc_set_multiplier_output; warm starts with duals in the diagnostic build), the dual record:
+// costates | slacks | multipliers.  The costates are formed again here, at the returned iterate: the recursion of costate_scan with a zero step
+//   lam_k = grad_s f(s_k) + A_k(x)^T lam_{k+1},   k = N .. 1
+// is stationarity of the Lagrangian in the states at x, exactly (float32 scans).  The ones the iterations carried belong to an earlier point: the
+// accepted iterate of the last Newton step (blended with its step length), not the affine-scaling extrapolation behind it nor a polished tail, which
+// never forms costates ("Multipliers").  Record word 0 (the stage-0 costate is never formed) holds the status of the solve.
 template <int NT, int NC, bool FG>
-__device__ __attribute__((noinline)) void phase_export(lds_t lds, int Nrt, float* fg_base, float* x, float* dq)
+__device__ __attribute__((noinline)) void phase_export(lds_t lds, int Nrt, float* fg_base, float* x, float* dq, int status_in)
 {
     CMPC_PHASE_PROLOGUE;
     for (int e = tid; e < NS * (N + 1); e += NT) {
@@ -3391,8 +3418,17 @@ __device__ __attribute__((noinline)) void phase_export(lds_t lds, int Nrt, float
         }
     }
     if (dq) {
+        const int status = __builtin_amdgcn_readfirstlane(status_in);
         __syncthreads();   // (the warm-start reads of this block's own record are long done; other blocks own other rows)
-        for (int e = tid; e < NS * (N + 1); e += NT) dq[e] = c.LAM[e];
+        if (status != 3) {
+            all_geo<NT>(c, prm, tid);
+            for (int e = tid; e < NS * (N + 1); e += NT) c.dS[e] = 0.f;
+            for (int e = tid; e < NS * N; e += NT) c.d[e] = 0.f;
+            __syncthreads();
+            if (tid < 64) costate_scan<true>(c, prm, tid, 0.f, false, c.LAM);
+            __syncthreads();
+        }
+        for (int e = tid; e < NS * (N + 1); e += NT) dq[e] = e < NS ? (e == 0 ? (float)status : 0.f) : c.LAM[e];
         for (int e = tid; e < NI * N; e += NT) { dq[NS * (N + 1) + e] = c.T[e]; dq[NS * (N + 1) + NI * N + e] = c.Z[e]; }
     }
 #ifdef CMPC_PROFILE
@@ -3543,7 +3579,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
                 if (finishing) {
                     // last step: affine-scaling extrapolation of the central path to mu = 0 (primal only), and the tail polish behind it
                     phase_forward_part<NT, NC, FG, 2>(lds, N, fg_base, true);
-                    if (phase_finish<NT, NC, FG>(lds, N, fg_base)) sg += 100000;
+                    if (phase_finish<NT, NC, FG>(lds, N, fg_base, dq != nullptr)) sg += 100000;
                     ++it;
                     break;
                 }
@@ -3597,7 +3633,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
         sg += 10000;
         __syncthreads();
     }
-    phase_export<NT, NC, FG>(lds, N, fg_base, kp.X + (size_t)b * L.nx(), dq);
+    phase_export<NT, NC, FG>(lds, N, fg_base, kp.X + (size_t)b * L.nx(), dq, status);
     if (kp.info && tid == 0) {
         float* inf = kp.info + (size_t)b * CMPC_INFO_N;
         inf[0] = (float)it_total; inf[1] = err; inf[2] = mu_cur; inf[3] = (float)sg; inf[4] = ep; inf[5] = (float)status;

@@ -206,6 +206,53 @@ class BatchSolver:
             cur.wait_stream(self._stream)
         return out
 
+    # ---- multipliers of the reference NLP, KKT certificate, gradient of the optimal cost (include/cmpc.h) ----
+    def set_multiplier_output(self, enabled: bool = True):
+        """cmpc_set_multiplier_output: every later solve on this handle also keeps its dual record (what multipliers_device maps)."""
+        rc = self._lib.cmpc_set_multiplier_output(self._h, 1 if enabled else 0)
+        if rc != 0:
+            raise RuntimeError(f"cmpc_set_multiplier_output failed ({rc}): {self.last_error}")
+
+    def _nlp_out(self, dX, dP, dLamG, out, width, fn, name):
+        import torch
+        L = self.layout
+        assert tuple(dX.shape) == (self.batch, L.nx) and tuple(dP.shape) == (self.batch, L.np)
+        for t in (dX, dP) + ((dLamG,) if dLamG is not None else ()):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        if dLamG is not None:
+            assert tuple(dLamG.shape) == (self.batch, L.ng)
+        if out is None:
+            out = torch.empty((self.batch, width), dtype=torch.float32, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, width) and out.dtype == torch.float32
+        st, cur = self._stream_pair(dX.device)
+        rc = fn(st)(out)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc}): {self.last_error}")
+        if cur is not None:
+            cur.wait_stream(self._stream)
+        return out
+
+    def multipliers_device(self, dX, dP, out=None):
+        """lam_g[B, n_g] of the last solve (dX, dP: its solution and parameters) in the reference's row order and IPOPT's sign convention."""
+        return self._nlp_out(dX, dP, None, out, self.layout.ng,
+                             lambda st: lambda o: self._lib.cmpc_get_multipliers_device(self._h, dX.data_ptr(), dP.data_ptr(), o.data_ptr(), st),
+                             "cmpc_get_multipliers_device")
+
+    def kkt_certificate_device(self, dX, dP, dLamG, out=None):
+        """[B, CMPC_CERT] KKT certificate of the reference NLP at (x, lam_g): stationarity, primal infeasibility, complementarity, sign violation,
+        f, status, scale, unscaled stationarity (include/cmpc.h)."""
+        return self._nlp_out(dX, dP, dLamG, out, _capi.CERT,
+                             lambda st: lambda o: self._lib.cmpc_kkt_certificate_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                        o.data_ptr(), st),
+                             "cmpc_kkt_certificate_device")
+
+    def value_gradient_device(self, dX, dP, dLamG, out=None):
+        """dV*/dp [B, n_p] at a KKT point (x*, lam*): grad_p L plus the terms of the parameters that only enter the bounds."""
+        return self._nlp_out(dX, dP, dLamG, out, self.layout.np,
+                             lambda st: lambda o: self._lib.cmpc_value_gradient_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                       o.data_ptr(), st),
+                             "cmpc_value_gradient_device")
+
     def plant_step_device(self, dX, dP, dState, dStateOut=None, dZmp=None, step=0.01, substeps=6,
                           zmp_half_x=0.08, zmp_half_y=0.03):
         """Closed-loop plant between two MPC ticks (WholeBodyQPBlock.cpp:805-873, 1083-1084, 1150): RK4 of the
@@ -480,6 +527,20 @@ class CentroidalMPC:
 
     def is_output_valid(self) -> bool:
         return self._valid
+
+    def set_multiplier_output(self, enabled: bool = True) -> bool:
+        """Keep the dual record of every later advance() (cmpc_set_multiplier_output), for get_multipliers()."""
+        if not self._need_init():
+            return False
+        return self._ok(self._lib.cmpc_set_multiplier_output(self._h, 1 if enabled else 0))
+
+    def get_multipliers(self):
+        """lam_g[B, n_g] of the last advance() (cmpc_get_multipliers; the multiplier output must be on), or None."""
+        L = Layout(self.cfg.N)
+        lam = np.empty((self._batch, L.ng), np.float32)
+        if not self._ok(self._lib.cmpc_get_multipliers(self._h, lam.ctypes.data)):
+            return None
+        return lam
 
     def get_solution(self):
         L = Layout(self.cfg.N)
