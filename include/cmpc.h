@@ -29,6 +29,8 @@
 #ifndef CMPC_H
 #define CMPC_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -235,6 +237,62 @@ int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP,
  * -min(lam, 0) on lower of each box row.  The entries of enabled (Gamma, binary) and R (constrained to rotations) are formal derivatives of the
  * generated code, not derivatives along feasible perturbations.  No derivatives with respect to the per-problem model fields. */
 int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream);
+
+/* ---- solution sensitivities: dx* / dp as JVP and VJP (derivation: DESIGN.md 7c) ----
+ * The derivative of the library's own solution map p -> x*(p) at a returned point, in the barrier form (as sIPOPT): inputs per problem are x, p and
+ * lam_g exactly as exported (cmpc_get_multipliers_device: layout, sign convention, duplicate rows credited to the landing row).
+ *   Equality rows E: the 15 initial rows, the com / dcom / h dynamics, the foot-position dynamics, swing-stage box components with lower == upper.
+ *   Inequality rows I: friction rows (z = max(lam, 0)); swing-stage box components with lower < upper, both sides (zU = max(lam, 0), zL = max(-lam, 0)).
+ *     Each side enters with Sigma_i = z_i / s_i, s_i = the distance of g_i(x) to that bound floored at CMPC_SENS_SMIN (at the returned x an active
+ *     row's slack is rounding noise and can be <= 0).
+ *   Not in the map: stance-stage box rows and stance vel columns (the stage form): their entries of dx are 0.
+ * With L = f + lam_g^T g and W = grad_xx L + sum_{i in I} J_i^T Sigma_i J_i (exact Hessian, with the bilinear momentum term):
+ *     [ W    J_E^T ] [ dx    ]      [ d_p(grad_x L) dp + sum_{i in I} J_i^T Sigma_i (d_p g_i dp - db_i) ]
+ *     [ J_E  0     ] [ dlam_E] = -  [ d_p g_E dp - db_E                                                ]
+ * b are the bounds as functions of p: com0, dcom0, h0, currentPos (initial rows), box lower / upper; an equality box component's bound is
+ * (lower + upper) / 2 (a perturbation that stays in the subset moves both).  JVP: dx.  VJP: the same symmetric system with right-hand side [v; 0],
+ * v = dl/dx, and dl/dp = -w^T r_p.
+ * Parameters covered: com0, dcom0, h0, currentPos, comRef, hRef, nominalPos, box upper / lower, fExt, tauExt.  Not covered: Gamma (enabled, discrete)
+ * and R (rotations; a tangent-space derivative is not provided): the JVP reads those entries of dp as zero, the VJP writes zeros there; nor the fields
+ * of the per-problem model.
+ * Tied entries (subset rule 3): a stance stage after a landing repeats the last swing stage's R, nominal, lower and upper.  Under this map a stance
+ * stage's lower / upper have zero derivative and a stance knot's nominalPos acts through the cost only; a perturbation that stays in the subset moves
+ * the whole group, and its derivative is the sum over the group.
+ * Internal-force direction: when both feet are in stance over the whole horizon, a constant internal force along currentPos_0 - currentPos_1 (left
+ * corners +e, right corners -e, every knot) is not determined by the NLP.  The JVP's dx has no component along it; the VJP
+ * treats v's component along it as zero.
+ * Weakly active rows (slack and multiplier both below CMPC_SENS_WEAK: an unloaded corner at the apex of its pyramid): the true
+ * map has a kink there and the barrier derivative is one value between its one-sided slopes.  They are counted, not hidden (dSens[2]).
+ * Linear algebra: the stage Riccati recursion of the solver's form in float64, one factorisation per problem shared by every right-hand side, the
+ * control Hessian shifted by CMPC_SENS_SHIFT on the force diagonal, two steps of float64 iterative refinement against the unshifted operator.
+ * dSens[B][CMPC_SENS] = { status: 0 ok, 1 a non-positive pivot of the reduced Hessian (no Gauss-Newton fallback: it would change the derivative),
+ *                           2 non-finite input or result, 3 outside the supported subset (the rule of solver status 3, or a model that broke the
+ *                           model rule);
+ *                         relative residual max|K s - rhs| / max|rhs| of the returned solution against the unshifted system (largest over the k columns);
+ *                         number of weakly active rows of loaded feet (friction rows of stance stages) and of box sides;  largest Sigma;
+ *                         1 if the internal-force direction exists (and was projected out);
+ *                         number of weakly active friction rows of swing stages (counted apart: a swing foot's forces enter no dynamics, and they
+ *                           sit near the apex because the costs pull them towards zero from inside the pyramid, not because a face binds);  0, 0 }.
+ * A flagged problem gets zero outputs; its neighbours are unaffected.  Per-problem models (cmpc_set_models*) apply; every horizon the handle supports.
+ * Workspace: per-handle HBM, allocated on first use and freed by cmpc_destroy, for min(B, CMPC_SENS_SUB_BATCH) problems (larger batches run in
+ * sub-batches): cmpc_sensitivity_workspace_bytes(N) per problem -- 8 (39^2 (N+1) + 2070 N + 8 (216 N + 117)) bytes, 0.85 MB at N = 20.
+ * Results depend on nothing but the problem's own inputs: not on its batch position, the batch size, the sub-batching or k (columns are processed
+ * in chunks of 8, bit for bit the same as one at a time).  The workspace is the handle's: a call on another stream than the previous call's waits
+ * for it (an event), so calls on one handle run one after the other whatever their streams.
+ * Slack floor: an active row's Sigma is capped at z / CMPC_SENS_SMIN, which biases the derivative along that row by about curvature x s_min / z
+ * relative (1e-4 for a landing-offset row with z ~ 0.1; 1e-6 for a loaded friction row). */
+#define CMPC_SENS 8
+#define CMPC_SENS_SMIN 5e-8
+#define CMPC_SENS_WEAK 1e-3
+#define CMPC_SENS_SHIFT 1e-7
+#define CMPC_SENS_SUB_BATCH 1024
+/* JVP: dDirP[B][k][n_p] directions (k >= 1) -> dDX[B][k][n_x]; dSens[B][CMPC_SENS] or NULL */
+int cmpc_solution_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, int k, float* dDX, float* dSens,
+                             void* stream);
+/* VJP: dGradX[B][n_x] = dl/dx -> dGradP[B][n_p] = dl/dp */
+int cmpc_solution_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP, float* dSens,
+                             void* stream);
+size_t cmpc_sensitivity_workspace_bytes(int horizon);
 
 /* ---- class-shaped setters (host buffers -> the handle's own device P, X0) ----
  * batch-major float32; NULL keeps the previous value (zeros initially).

@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("CMPC_LIB", "libcmpc_hip.so"))   #
 
 INFO = 8
 CERT = 8   # CMPC_CERT: fields of the KKT certificate (include/cmpc.h)
+SENS = 8   # CMPC_SENS: per-problem info words of the solution sensitivities (include/cmpc.h)
 
 
 class CmpcConfig(C.Structure):
@@ -81,7 +82,8 @@ EXPORTS = [
     "cmpc_contacts_force_sample_time", "cmpc_contacts_force_sample_time_device",
     "cmpc_model_from_config", "cmpc_check_models", "cmpc_set_models", "cmpc_set_models_device",
     "cmpc_set_multiplier_output", "cmpc_get_multipliers_device", "cmpc_get_multipliers", "cmpc_kkt_certificate_device",
-    "cmpc_value_gradient_device",
+    "cmpc_value_gradient_device", "cmpc_solution_jvp_device", "cmpc_solution_vjp_device",
+    "cmpc_sensitivity_workspace_bytes",
 ]
 
 _lib = None
@@ -156,6 +158,10 @@ def lib():
         L.cmpc_get_multipliers.argtypes = [vp, fp]
         L.cmpc_kkt_certificate_device.argtypes = [vp, fp, fp, fp, fp, vp]
         L.cmpc_value_gradient_device.argtypes = [vp, fp, fp, fp, fp, vp]
+        L.cmpc_solution_jvp_device.argtypes = [vp, fp, fp, fp, fp, C.c_int, fp, fp, vp]
+        L.cmpc_solution_vjp_device.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
+        L.cmpc_sensitivity_workspace_bytes.argtypes = [C.c_int]
+        L.cmpc_sensitivity_workspace_bytes.restype = C.c_size_t
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

@@ -23,6 +23,8 @@ extern "C" int cmpc_launch_nlp_grad(const CmpcParams* prm, const float* dX, cons
 extern "C" int cmpc_launch_multipliers(const CmpcParams* prm, const float* dX, const float* dP, float* dLamG, hipStream_t stream);
 extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dCert, hipStream_t stream);
 extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream);
+extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
+                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, hipStream_t stream);
 extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev, float* dX0, hipStream_t stream);
 extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double* plan_t, const float* plan_pose, const int* plan_n,
                                           const double* mpc_t, const float* mpc_pose, const int* mpc_n, double* out_t, float* out_pose,
@@ -71,6 +73,8 @@ struct cmpc_handle_s {
     float* dDuals = nullptr;     // the dual record of the last solve [B][NS (N+1) + 2 NI N] (cmpc_set_multiplier_output, or the diagnostic knob below)
     bool mult_out = false;       // cmpc_set_multiplier_output: every solve writes dDuals
     float* dLamG = nullptr;      // [B][n_g] staging of cmpc_get_multipliers (allocated on first use)
+    double* dSensWs = nullptr;   // workspace of the solution sensitivities, min(B, CMPC_SENS_SUB_BATCH) problems (allocated on first use)
+    hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
     double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
     int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
@@ -273,7 +277,8 @@ int cmpc_destroy(cmpc_handle h)
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->hXpin) hipHostFree(h->hXpin);
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
-    hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG);
+    hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG); hipFree(h->dSensWs);
+    if (h->sens_ev) hipEventDestroy(h->sens_ev);
     hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -760,6 +765,42 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
     int rc = cmpc_launch_value_gradient(&p, dX, dP, dLamG, dGradP, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("value gradient launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
+}
+
+// ---- solution sensitivities (include/cmpc.h; cmpc_sensitivity.hip) ----
+static int sensitivity(cmpc_handle h, const char* name, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const float* dGradX,
+                       int k, float* dOut, float* dSens, void* stream)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    const int N = h->cfg.horizon, sb = h->B < CMPC_SENS_SUB_BATCH ? h->B : CMPC_SENS_SUB_BATCH;
+    if (!h->dSensWs) HIPCHK(h, hipMalloc(&h->dSensWs, cmpc_sensitivity_workspace_bytes(N) * (size_t)sb));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const CmpcConsts* kc = h->models_set ? h->dModels : h->dConsts;
+    // the workspace is the handle's: a call on another stream than the previous one is ordered after it
+    if (!h->sens_ev) HIPCHK(h, hipEventCreateWithFlags(&h->sens_ev, hipEventDisableTiming));
+    else HIPCHK(h, hipStreamWaitEvent(st, h->sens_ev, 0));
+    for (int b0 = 0; b0 < h->B; b0 += sb) {
+        const int nb = h->B - b0 < sb ? h->B - b0 : sb;
+        int rc = cmpc_launch_sensitivity(kc, h->models_set ? 1 : 0, N, b0, nb, dX, dP, dLamG, dDirP, dGradX, k, dOut, dSens, h->dSensWs, st);
+        if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString((hipError_t)rc));
+    }
+    HIPCHK(h, hipEventRecord(h->sens_ev, st));
+    return CMPC_OK;
+}
+
+int cmpc_solution_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, int k, float* dDX, float* dSens,
+                             void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dDirP || !dDX) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_device: null argument");
+    if (k < 1) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_device: k must be >= 1");
+    return sensitivity(h, "cmpc_solution_jvp_device", dX, dP, dLamG, dDirP, nullptr, k, dDX, dSens, stream);
+}
+
+int cmpc_solution_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP, float* dSens,
+                             void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradX || !dGradP) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_device: null argument");
+    return sensitivity(h, "cmpc_solution_vjp_device", dX, dP, dLamG, nullptr, dGradX, 1, dGradP, dSens, stream);
 }
 
 // ---- 8f-3: planner references -> MPC knots (CentroidalMPCBlock.cpp:525-577): angular momentum / mass, CoM height

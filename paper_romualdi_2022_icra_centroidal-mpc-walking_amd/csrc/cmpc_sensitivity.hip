@@ -1,0 +1,1029 @@
+// Derivatives of the solution map p -> x*(p) at a returned point (include/cmpc.h, "solution sensitivities"; derivation: DESIGN.md 7c).
+//
+// The barrier form of sIPOPT: [W J_E^T; J_E 0] [dx; dlam_E] = -r(dp), W = grad_xx L + sum_I J_i^T Sigma_i J_i.  It is solved in the solver's
+// stage form: state 15 + the 24 previous forces (39), control = 24 forces + 6 landing offsets (30), swing feet land at
+// nom + R^-T q, stance vel columns and stance box rows do not exist.  One workgroup of 256 threads per problem, float64 throughout:
+//   1. one Riccati factorisation (backward), the control Hessian shifted by SENS_SHIFT on the force diagonal; per stage P_{k+1}, H^-1 and the
+//      gain K = -H^-1 G go to a per-handle HBM workspace (the stage matrices are rebuilt from x, p, lam_g wherever they are needed);
+//   2. per chunk of up to SENS_KC right-hand sides: a backward and a forward pass, then SENS_NREF steps of iterative refinement against the
+//      unshifted operator, then one pass that measures the relative residual.
+// No atomics: every reduction is a fixed tree or one thread's loop, so a problem's result depends on nothing but its own inputs.
+#include "cmpc_device.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int SX = CMPC_NXA;      // 39
+constexpr int SU = CMPC_NU;       // 30
+constexpr int SENS_KC = 8;        // right-hand sides per chunk
+constexpr int CS = 40;            // doubles per column slot in LDS (>= 39)
+constexpr int SENS_NREF = 2;      // refinement steps against the unshifted operator
+constexpr int SENS_NT = 256;
+constexpr double SENS_SMIN = CMPC_SENS_SMIN;
+constexpr double SENS_WEAK = CMPC_SENS_WEAK;
+constexpr double SENS_SHIFT = CMPC_SENS_SHIFT;
+
+// state / control indices
+__host__ __device__ constexpr int sCom() { return 0; }
+__host__ __device__ constexpr int sDcom() { return 3; }
+__host__ __device__ constexpr int sH() { return 6; }
+__host__ __device__ constexpr int sPos(int c) { return 9 + 3 * c; }
+__host__ __device__ constexpr int uF(int c, int j) { return 12 * c + 3 * j; }
+__host__ __device__ constexpr int uQ(int c) { return 24 + 3 * c; }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SENS_SYNC() __syncthreads()
+#else
+#define SENS_SYNC() ((void)0)
+#endif
+
+struct Team {
+    int tid, nt;
+    double* red;   // 4 doubles (device)
+};
+
+// max over the team (256 threads on the device: one wave reduction + four partials; the host team has one thread)
+__host__ __device__ inline double team_max(const Team& T, double v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((T.tid & 63) == 0) T.red[T.tid >> 6] = v;
+    __syncthreads();
+    const double r = fmax(fmax(T.red[0], T.red[1]), fmax(T.red[2], T.red[3]));
+    __syncthreads();
+    return r;
+#else
+    (void)T;
+    return v;
+#endif
+}
+
+// ---- the geometry of one stage: everything the stage matrices are made of ----
+struct Geo {
+    double gam[2];
+    double R[2][9];        // R(r, c) at 3 r + c
+    double Ri[2][9];       // R^-T: a swing foot lands at nom + Ri q
+    double rv[2][4][3];    // lever arms r = R corner + pos - com
+    double fs[2][4][3];    // corner forces
+    double lamh[3];        // lam_g of the angular-momentum rows of the stage
+    double afr[2][4][4][3];  // friction row normals a = R (sx, sy, -mu): g = a . f
+    double sfr[2][4][4];   // Sigma of the friction rows
+    double sU[2][3], sL[2][3];
+    int qm[2][3];          // 0: no such control (stance), 1: free offset, 2: fixed offset (lower == upper)
+    double hcom[3];        // curvature of the CoM cost at the knot
+    double dt, wh, wpos, wsym, D[3];
+    int k, N;
+    double weak, weak_swing, sigmax;   // (stage build: weakly active rows of loaded feet and box sides, of swing feet, largest Sigma)
+};
+
+struct Prob {
+    const CmpcConsts* K;
+    CmpcIdx L;
+    int gh;       // first g row of the angular-momentum dynamics
+    int gbox[2], gfric[2];
+    const float* x;
+    const float* p;
+    const float* lam;
+};
+
+__host__ __device__ inline double skewm(const double* v, int a, int b)   // [v]x (a, b)
+{
+    if (a == b) return 0.0;
+    const int o = 3 - a - b;
+    return ((b - a + 3) % 3 == 1) ? -v[o] : v[o];
+}
+
+// Geo of stage k (k == N: only the knot's costs).  Thread 0 does the scalar part; the rows are spread over the team.
+__host__ __device__ inline void build_geo(const Team& T, const Prob& P, int k, Geo& g)
+{
+    const CmpcConsts& K = *P.K;
+    const int N = P.L.N;
+    const CmpcIdx& L = P.L;
+    if (T.tid == 0) {
+        g.k = k; g.N = N;
+        g.dt = K.dt; g.wh = 2.0 * (double)K.w_h; g.wpos = 2.0 * (double)K.w_pos; g.wsym = 2.0 * (double)K.w_sym;
+        for (int i = 0; i < 3; ++i) g.D[i] = K.D[i];
+        g.hcom[0] = 2.0 * (double)K.w_com0; g.hcom[1] = 2.0 * (double)K.w_com1; g.hcom[2] = K.wz2[k];
+        g.weak = 0.0; g.weak_swing = 0.0; g.sigmax = 0.0;
+    }
+    if (k == N) { SENS_SYNC(); return; }
+    for (int e = T.tid; e < 2; e += T.nt) {
+        const int c = e;
+        g.gam[c] = P.p[L.pGam(c) + k];
+        const float* Rp = P.p + L.pR(c) + 9 * k;
+        double R[9];
+        for (int r = 0; r < 3; ++r)
+            for (int cc = 0; cc < 3; ++cc) R[3 * r + cc] = Rp[3 * cc + r];
+        for (int i = 0; i < 9; ++i) g.R[c][i] = R[i];
+        // R^-T = cof(R) / det(R)
+        double cof[9];
+        for (int r = 0; r < 3; ++r)
+            for (int cc = 0; cc < 3; ++cc) {
+                const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (cc + 1) % 3, c2 = (cc + 2) % 3;
+                cof[3 * r + cc] = R[3 * r1 + c1] * R[3 * r2 + c2] - R[3 * r1 + c2] * R[3 * r2 + c1];
+            }
+        const double det = R[0] * cof[0] + R[1] * cof[1] + R[2] * cof[2];
+        for (int i = 0; i < 9; ++i) g.Ri[c][i] = cof[i] / det;
+        for (int j = 0; j < 4; ++j) {
+            const float* cn = K.corners + 12 * c + 3 * j;
+            for (int i = 0; i < 3; ++i) {
+                g.rv[c][j][i] = R[3 * i] * cn[0] + R[3 * i + 1] * cn[1] + R[3 * i + 2] * cn[2] + (double)P.x[L.oPos(c) + 3 * k + i] -
+                                (double)P.x[L.oCom() + 3 * k + i];
+                g.fs[c][j][i] = P.x[L.oF(c, j) + 3 * k + i];
+            }
+        }
+    }
+    for (int e = T.tid; e < 3; e += T.nt) g.lamh[e] = P.lam[P.gh + 3 * k + e];
+    SENS_SYNC();
+    // friction rows: 32 per stage
+    for (int e = T.tid; e < 32; e += T.nt) {
+        const int c = e >> 4, j = (e >> 2) & 3, f = e & 3;
+        const double sx = (f == 0 || f == 3) ? 1.0 : -1.0, sy = (f < 2) ? 1.0 : -1.0, mu = K.mu_fr;
+        double a[3], gv = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            a[r] = g.R[c][3 * r] * sx + g.R[c][3 * r + 1] * sy - mu * g.R[c][3 * r + 2];
+            g.afr[c][j][f][r] = a[r];
+            gv += a[r] * g.fs[c][j][r];
+        }
+        const double z = fmax((double)P.lam[P.gfric[c] + 16 * k + 4 * j + f], 0.0);
+        const double s = -gv;
+        g.sfr[c][j][f] = z / fmax(s, SENS_SMIN);
+    }
+    // landing offsets of swing feet: 6 per stage
+    for (int e = T.tid; e < 6; e += T.nt) {
+        const int c = e / 3, i = e % 3;
+        const float lo = P.p[L.pLo(c) + 3 * k + i], up = P.p[L.pUp(c) + 3 * k + i];
+        g.sU[c][i] = 0.0; g.sL[c][i] = 0.0;
+        if (!(P.p[L.pGam(c) + k] < 0.5f)) { g.qm[c][i] = 0; continue; }
+        if (!((up - lo) > 1e-9f)) { g.qm[c][i] = 2; continue; }    // (the solver's rule, qfree_compute)
+        g.qm[c][i] = 1;
+        double v = 0.0;
+        for (int r = 0; r < 3; ++r)
+            v += g.R[c][3 * r + i] * ((double)P.x[L.oPos(c) + 3 * (k + 1) + r] - (double)P.p[L.pNom(c) + 3 * (k + 1) + r]);
+        const double l = P.lam[P.gbox[c] + 3 * k + i];
+        const double zU = fmax(l, 0.0), zL = fmax(-l, 0.0), sU = (double)up - v, sL = v - (double)lo;
+        g.sU[c][i] = zU / fmax(sU, SENS_SMIN);
+        g.sL[c][i] = zL / fmax(sL, SENS_SMIN);
+    }
+    SENS_SYNC();
+    if (T.tid == 0) {   // weakly active rows and the largest Sigma, in a fixed order
+        // (friction rows of a swing foot are counted apart: its forces enter no dynamics, and they sit near the apex because the symmetry and rate
+        // costs pull them towards zero from inside the pyramid, not because a face binds)
+        double w = 0.0, ws = 0.0, sm = 0.0;
+        for (int e = 0; e < 32; ++e) {
+            const int c = e >> 4, j = (e >> 2) & 3, f = e & 3;
+            double gv = 0.0;
+            for (int r = 0; r < 3; ++r) gv += g.afr[c][j][f][r] * g.fs[c][j][r];
+            const double z = fmax((double)P.lam[P.gfric[c] + 16 * k + 4 * j + f], 0.0);
+            if (z < SENS_WEAK && -gv < SENS_WEAK) {
+                if (g.gam[c] >= 0.5) w += 1.0;
+                else ws += 1.0;
+            }
+            sm = fmax(sm, g.sfr[c][j][f]);
+        }
+        for (int e = 0; e < 6; ++e) {
+            const int c = e / 3, i = e % 3;
+            if (g.qm[c][i] != 1) continue;
+            double v = 0.0;
+            for (int r = 0; r < 3; ++r)
+                v += g.R[c][3 * r + i] * ((double)P.x[L.oPos(c) + 3 * (k + 1) + r] - (double)P.p[L.pNom(c) + 3 * (k + 1) + r]);
+            const double l = P.lam[P.gbox[c] + 3 * k + i];
+            const double up = P.p[L.pUp(c) + 3 * k + i], lo = P.p[L.pLo(c) + 3 * k + i];
+            if (fmax(l, 0.0) < SENS_WEAK && up - v < SENS_WEAK) w += 1.0;
+            if (fmax(-l, 0.0) < SENS_WEAK && v - lo < SENS_WEAK) w += 1.0;
+            sm = fmax(sm, fmax(g.sU[c][i], g.sL[c][i]));
+        }
+        g.weak = w; g.weak_swing = ws; g.sigmax = sm;
+    }
+    SENS_SYNC();
+}
+
+// ---- stage matrices as entry functions ----
+__host__ __device__ inline double Qe(const Geo& g, int i, int j)   // knot k (k == N: terminal)
+{
+    if (i != j) return 0.0;
+    if (i < 3) return g.hcom[i];
+    if (i < 6) return 0.0;
+    if (i < 9) return g.wh;
+    if (i < 15) return g.wpos;
+    return (g.k >= 1 && g.k < g.N) ? g.D[(i - 15) % 3] : 0.0;
+}
+__host__ __device__ inline double Se(const Geo& g, int i, int j)   // control i, state j
+{
+    if (i >= 24) return 0.0;
+    const int c = i / 12, a = i % 3;
+    if (j >= 15) return (g.k >= 1 && j - 15 == i) ? -g.D[a] : 0.0;
+    if (j >= 9) {
+        if ((j - 9) / 3 != c) return 0.0;
+        return -g.dt * g.gam[c] * skewm(g.lamh, a, (j - 9) % 3);
+    }
+    if (j < 3) return g.dt * g.gam[c] * skewm(g.lamh, a, j);
+    return 0.0;
+}
+__host__ __device__ inline double Re(const Geo& g, int i, int j)   // control i, control j (unshifted)
+{
+    if (i >= 24 || j >= 24) {
+        if (i != j) return 0.0;
+        const int c = (i - 24) / 3, a = (i - 24) % 3;
+        return g.qm[c][a] == 1 ? g.sU[c][a] + g.sL[c][a] : 1.0;
+    }
+    const int c1 = i / 12, j1 = (i % 12) / 3, a1 = i % 3, c2 = j / 12, j2 = (j % 12) / 3, a2 = j % 3;
+    if (c1 != c2) return 0.0;
+    double v = 0.0;
+    if (a1 == a2) {
+        const double gm = g.gam[c1];
+        v += g.wsym * ((j1 == j2 ? 1.0 : 0.0) + (0.25 * gm * gm - 0.5 * gm));
+        if (j1 == j2 && g.k >= 1) v += g.D[a1];
+    }
+    if (j1 == j2)
+        for (int f = 0; f < 4; ++f) v += g.sfr[c1][j1][f] * g.afr[c1][j1][f][a1] * g.afr[c1][j1][f][a2];
+    return v;
+}
+__host__ __device__ inline double Ae(const Geo& g, int i, int j)
+{
+    if (i < 3) return i == j ? 1.0 : (j == 3 + i ? g.dt : 0.0);
+    if (i < 6) return i == j ? 1.0 : 0.0;
+    if (i < 9) {
+        const int a = i - 6;
+        if (j == i) return 1.0;
+        double v = 0.0;
+        if (j < 3) {
+            for (int c = 0; c < 2; ++c)
+                for (int jj = 0; jj < 4; ++jj) v += g.gam[c] * skewm(g.fs[c][jj], a, j);
+            return g.dt * v;
+        }
+        if (j >= 9 && j < 15) {
+            const int c = (j - 9) / 3;
+            for (int jj = 0; jj < 4; ++jj) v += skewm(g.fs[c][jj], a, (j - 9) % 3);
+            return -g.dt * g.gam[c] * v;
+        }
+        return 0.0;
+    }
+    if (i < 15) {
+        const int c = (i - 9) / 3;
+        return (i == j && g.gam[c] >= 0.5) ? 1.0 : 0.0;
+    }
+    return 0.0;
+}
+__host__ __device__ inline double Be(const Geo& g, int i, int j)
+{
+    if (i < 3) return 0.0;
+    if (j < 24) {
+        const int c = j / 12, jj = (j % 12) / 3, a = j % 3;
+        if (i < 6) return (i - 3 == a) ? g.dt * g.gam[c] : 0.0;
+        if (i < 9) return g.dt * g.gam[c] * skewm(g.rv[c][jj], i - 6, a);
+        if (i < 15) return 0.0;
+        return (i - 15 == j) ? 1.0 : 0.0;
+    }
+    const int c = (j - 24) / 3, a = (j - 24) % 3;
+    if (i >= 9 && i < 15 && (i - 9) / 3 == c && g.qm[c][a] == 1) return g.Ri[c][3 * ((i - 9) % 3) + a];
+    return 0.0;
+}
+
+// ---- workspace of one problem (doubles) ----
+struct Ws {
+    double* Pst;   // [N+1][39*39]  P_k
+    double* Hi;    // [N][30*30]    H_k^-1
+    double* Kg;    // [N][30*39]    K_k = -H_k^-1 G_k
+    double* col;   // [KC][colsz]
+    int N;
+    __host__ __device__ static long long colsz(int N) { return 3LL * SX * (N + 1) + 2LL * SU * N + (long long)SX * N; }
+    __host__ __device__ static long long doubles(int N) { return (long long)(N + 1) * SX * SX + (long long)N * (SU * SU + SU * SX) + SENS_KC * colsz(N); }
+    // per column: x~ [N+1][39], lam [N+1][39], p [N+1][39], u [N][30], kff [N][30], c [N][39]
+    __host__ __device__ double* xs(int j) const { return col + j * colsz(N); }
+    __host__ __device__ double* ls(int j) const { return xs(j) + SX * (N + 1); }
+    __host__ __device__ double* ps(int j) const { return ls(j) + SX * (N + 1); }
+    __host__ __device__ double* us(int j) const { return ps(j) + SX * (N + 1); }
+    __host__ __device__ double* kf(int j) const { return us(j) + SU * N; }
+    __host__ __device__ double* cs(int j) const { return kf(j) + SU * N; }
+};
+
+// LDS of the dense stage work (doubles)
+struct Lds {
+    double *P, *A, *Bm, *PA, *PB, *H, *G, *Y;   // factorisation
+    // column passes (overlay PA.. of the factorisation): per column 64-double slots
+    double *q, *r, *c, *pn, *t, *h, *kf, *xk, *uk, *xn, *ln, *lk;
+    Geo* g;
+    __host__ __device__ static int doubles() { return 3 * SX * SX + 3 * SX * SU + SU * SU + SU * SX; }
+};
+
+// One column's right-hand side at stage k (k == N: q only) -- the caller's definition
+struct Rhs {
+    int mode;          // 0: JVP direction dp; 1: VJP gradient v (already projected)
+    const float* dir;  // mode 0: [KC][np] rows of this chunk (stride np); mode 1: [nx]
+    long long stride;
+};
+
+// (q_k, r_k, c_k) of column j, written to q[39], r[30], c[39]; k == N: q only.  x0 (k == 0 only, if non-null): the initial state
+__host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs& R, int j, int k, int e, double* q, double* r, double* c, double* x0)
+{
+    const CmpcIdx& L = P.L;
+    const int N = L.N;
+    if (R.mode == 0) {
+        const float* d = R.dir + j * R.stride;
+        if (e < SX) {   // q and c entry e
+            double qv = 0.0;
+            if (e < 3) qv = -g.hcom[e] * d[L.pComref() + 3 * k + e];
+            else if (e >= 6 && e < 9) qv = -g.wh * d[L.pHref() + 3 * k + e - 6];
+            else if (e >= 9 && e < 15) qv = -g.wpos * d[L.pNom((e - 9) / 3) + 3 * k + (e - 9) % 3];
+            q[e] = qv;
+            if (x0) {
+                double v = 0.0;
+                if (e < 9) v = d[L.pCom0() + e];
+                else if (e < 15) v = d[L.pCur((e - 9) / 3) + (e - 9) % 3];
+                x0[e] = v;
+            }
+            if (k < N) {
+                double cv = 0.0;
+                if (e >= 3 && e < 6) cv = g.dt * d[L.pFext() + 3 * k + e - 3];
+                else if (e >= 6 && e < 9) cv = g.dt * d[L.pText() + 3 * k + e - 6];
+                else if (e >= 9 && e < 15) {
+                    const int cc = (e - 9) / 3, a = (e - 9) % 3;
+                    if (g.gam[cc] < 0.5) {
+                        cv = d[L.pNom(cc) + 3 * (k + 1) + a];
+                        for (int i = 0; i < 3; ++i)
+                            if (g.qm[cc][i] == 2)
+                                cv += g.Ri[cc][3 * a + i] * 0.5 * ((double)d[L.pLo(cc) + 3 * k + i] + (double)d[L.pUp(cc) + 3 * k + i]);
+                    }
+                }
+                c[e] = cv;
+            }
+        } else if (k < N) {   // r entry e - SX
+            const int i = e - SX;
+            double rv = 0.0;
+            if (i >= 24) {
+                const int cc = (i - 24) / 3, a = (i - 24) % 3;
+                if (g.qm[cc][a] == 1) rv = -(g.sU[cc][a] * d[L.pUp(cc) + 3 * k + a] + g.sL[cc][a] * d[L.pLo(cc) + 3 * k + a]);
+            }
+            r[i] = rv;
+        }
+    } else {
+        const float* v = R.dir;
+        if (e < SX) {
+            double qv = 0.0;
+            if (e < 9) qv = -(double)v[3 * (N + 1) * (e / 3) + 3 * k + e % 3];
+            else if (e < 15) {
+                const int cc = (e - 9) / 3, a = (e - 9) % 3;
+                qv = -(double)v[L.oPos(cc) + 3 * k + a];
+                // vel_k = (pos_k+1 - pos_k) / dt in swing stages
+                if (k < N && P.p[L.pGam(cc) + k] < 0.5f) qv += (double)v[L.oVel(cc) + 3 * k + a] / g.dt;
+                if (k >= 1 && P.p[L.pGam(cc) + k - 1] < 0.5f) qv -= (double)v[L.oVel(cc) + 3 * (k - 1) + a] / g.dt;
+            }
+            q[e] = qv;
+            if (x0) x0[e] = 0.0;
+            if (k < N) c[e] = 0.0;
+        } else if (k < N) {
+            const int i = e - SX;
+            r[i] = i < 24 ? -(double)v[L.oF(i / 12, (i % 12) / 3) + 3 * k + i % 3] : 0.0;
+        }
+    }
+}
+
+// copies n doubles global -> LDS / LDS -> global
+__host__ __device__ inline void tcopy(const Team& T, double* dst, const double* src, int n)
+{
+    for (int e = T.tid; e < n; e += T.nt) dst[e] = src[e];
+}
+
+// ---- 1. factorisation ----
+// returns 1 (team-uniform) on a non-positive pivot
+__host__ __device__ __attribute__((noinline)) int factorise(const Team& T, const Prob& P, const Ws& W, const Lds& S, double& weak, double& weak_swing,
+                                                              double& sigmax)
+{
+    const int N = P.L.N;
+    Geo& g = *S.g;
+    int bad = 0;
+    // P_N = Q_N
+    build_geo(T, P, N, g);
+    for (int e = T.tid; e < SX * SX; e += T.nt) S.P[e] = Qe(g, e / SX, e % SX);
+    SENS_SYNC();
+    tcopy(T, W.Pst + (size_t)N * SX * SX, S.P, SX * SX);
+    for (int k = N - 1; k >= 0; --k) {
+        build_geo(T, P, k, g);
+        weak += g.weak; weak_swing += g.weak_swing; sigmax = fmax(sigmax, g.sigmax);   // (every thread: g is shared)
+        for (int e = T.tid; e < SX * SX; e += T.nt) S.A[e] = Ae(g, e / SX, e % SX);
+        for (int e = T.tid; e < SX * SU; e += T.nt) S.Bm[e] = Be(g, e / SU, e % SU);
+        SENS_SYNC();
+        for (int e = T.tid; e < SX * SX; e += T.nt) {   // PA = P A
+            const int i = e / SX, j = e % SX;
+            double v = 0.0;
+            for (int m = 0; m < SX; ++m) v += S.P[i * SX + m] * S.A[m * SX + j];
+            S.PA[e] = v;
+        }
+        for (int e = T.tid; e < SX * SU; e += T.nt) {   // PB = P B
+            const int i = e / SU, j = e % SU;
+            double v = 0.0;
+            for (int m = 0; m < SX; ++m) v += S.P[i * SX + m] * S.Bm[m * SU + j];
+            S.PB[e] = v;
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < SU * SU; e += T.nt) {   // H = R + B^T P B + shift on the force diagonal
+            const int i = e / SU, j = e % SU;
+            double v = Re(g, i, j);
+            for (int m = 0; m < SX; ++m) v += S.Bm[m * SU + i] * S.PB[m * SU + j];
+            if (i == j && i < 24) v += SENS_SHIFT;
+            S.H[e] = v;
+        }
+        for (int e = T.tid; e < SU * SX; e += T.nt) {   // G = S + B^T P A
+            const int i = e / SX, j = e % SX;
+            double v = Se(g, i, j);
+            for (int m = 0; m < SX; ++m) v += S.Bm[m * SU + i] * S.PA[m * SX + j];
+            S.G[e] = v;
+        }
+        SENS_SYNC();
+        // Cholesky H = L L^T in place (lower triangle), column by column
+        for (int j = 0; j < SU; ++j) {
+            const double d = S.H[j * SU + j];
+            if (!(d > 0.0)) bad = 1;
+            const double ld = d > 0.0 ? sqrt(d) : 1.0;
+            SENS_SYNC();
+            for (int i = j + 1 + T.tid; i < SU; i += T.nt) S.H[i * SU + j] /= ld;
+            SENS_SYNC();
+            if (T.tid == 0) S.H[j * SU + j] = ld;
+            for (int e = T.tid; e < (SU - j - 1) * (SU - j - 1); e += T.nt) {
+                const int i = j + 1 + e / (SU - j - 1), l = j + 1 + e % (SU - j - 1);
+                if (l <= i) S.H[i * SU + l] -= S.H[i * SU + j] * S.H[l * SU + j];
+            }
+            SENS_SYNC();
+        }
+        // L^-1 into Y's first 900 entries (one column per thread: forward substitution)
+        double* Li = S.Y;
+        for (int j = T.tid; j < SU; j += T.nt) {
+            for (int i = 0; i < SU; ++i) {
+                double v = (i == j) ? 1.0 : 0.0;
+                for (int m = j; m < i; ++m) v -= S.H[i * SU + m] * Li[m * SU + j];
+                Li[i * SU + j] = i < j ? 0.0 : v / S.H[i * SU + i];
+            }
+        }
+        SENS_SYNC();
+        // H^-1 = L^-T L^-1 (into PB's space, which is free now), then K = -H^-1 G (into PA's space after P_k is formed)
+        double* Hinv = S.PB;
+        for (int e = T.tid; e < SU * SU; e += T.nt) {
+            const int i = e / SU, j = e % SU;
+            double v = 0.0;
+            for (int m = (i > j ? i : j); m < SU; ++m) v += Li[m * SU + i] * Li[m * SU + j];
+            Hinv[e] = v;
+        }
+        SENS_SYNC();
+        tcopy(T, W.Hi + (size_t)k * SU * SU, Hinv, SU * SU);
+        // P_k = Q + A^T P A + G^T K,  K = -H^-1 G  (written into P after P A is no longer needed below)
+        double* Kk = S.Y;   // (L^-1 is dead)
+        for (int e = T.tid; e < SU * SX; e += T.nt) {
+            const int i = e / SX, j = e % SX;
+            double v = 0.0;
+            for (int m = 0; m < SU; ++m) v -= Hinv[i * SU + m] * S.G[m * SX + j];
+            Kk[e] = v;
+        }
+        SENS_SYNC();
+        tcopy(T, W.Kg + (size_t)k * SU * SX, Kk, SU * SX);
+        for (int e = T.tid; e < SX * SX; e += T.nt) {
+            const int i = e / SX, j = e % SX;
+            double v = Qe(g, i, j);
+            for (int m = 0; m < SX; ++m) v += S.A[m * SX + i] * S.PA[m * SX + j];
+            for (int m = 0; m < SU; ++m) v += S.G[m * SX + i] * Kk[m * SX + j];
+            S.P[e] = v;
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < SX * SX; e += T.nt) {   // symmetrise
+            const int i = e / SX, j = e % SX;
+            if (i < j) { const double v = 0.5 * (S.P[e] + S.P[j * SX + i]); S.P[e] = v; S.P[j * SX + i] = v; }
+        }
+        SENS_SYNC();
+        tcopy(T, W.Pst + (size_t)k * SX * SX, S.P, SX * SX);
+        SENS_SYNC();
+    }
+    return bad;
+}
+
+// ---- 2. the passes of a chunk of nc columns ----
+// pass = 0: solve with the caller's right-hand side (write); 1: refinement step (residual as right-hand side, add the correction);
+// 2: measure the residual only.  Returns the largest residual (pass 2) and the largest right-hand side entry (all passes) in rn / bn.
+__host__ __device__ __attribute__((noinline)) void chunk_pass(const Team& T, const Prob& P, const Ws& W, const Lds& S, const Rhs& R, int nc, int pass, double& rn,
+                                           double& bn)
+{
+    const int N = P.L.N;
+    Geo& g = *S.g;
+    double rmax = 0.0, bmax = 0.0;
+    // backward sweep: k = N (terminal), then N-1 .. 0
+    for (int k = N; k >= 0; --k) {
+        build_geo(T, P, k, g);
+        if (k < N) {
+            for (int e = T.tid; e < SX * SX; e += T.nt) S.A[e] = Ae(g, e / SX, e % SX);
+            for (int e = T.tid; e < SX * SU; e += T.nt) S.Bm[e] = Be(g, e / SU, e % SU);
+        }
+        // the caller's right-hand side of this stage
+        for (int e = T.tid; e < nc * (SX + SU); e += T.nt) {
+            const int j = e / (SX + SU), i = e % (SX + SU);
+            rhs_entry(P, g, R, j, k, i, S.q + CS * j, S.r + CS * j, S.c + CS * j, k == 0 ? S.lk + CS * j : nullptr);
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * (SX + SU); e += T.nt) {
+            const int j = e / (SX + SU), i = e % (SX + SU);
+            double b = 0.0;
+            if (i < SX) {
+                b = fabs(S.q[CS * j + i]);
+                if (k < N) b = fmax(b, fabs(S.c[CS * j + i]));
+                if (k == 0) b = fmax(b, fabs(S.lk[CS * j + i]));
+            } else if (k < N) b = fabs(S.r[CS * j + i - SX]);
+            bmax = fmax(bmax, b);
+        }
+        if (pass > 0) {
+            // residual of the stored solution: rho_Sx, rho_Su, rho_E (stage k), rho_E0 at k == 0
+            for (int e = T.tid; e < nc * SX; e += T.nt) {
+                const int j = e / SX, i = e % SX;
+                S.xk[CS * j + i] = W.xs(j)[k * SX + i];
+                if (k < N) { S.xn[CS * j + i] = W.xs(j)[(k + 1) * SX + i]; S.ln[CS * j + i] = W.ls(j)[(k + 1) * SX + i]; }
+            }
+            for (int e = T.tid; e < nc * SU; e += T.nt) {
+                const int j = e / SU, i = e % SU;
+                if (k < N) S.uk[CS * j + i] = W.us(j)[k * SU + i];
+            }
+            SENS_SYNC();
+            for (int e = T.tid; e < nc * (SX + SU + SX); e += T.nt) {
+                const int j = e / (2 * SX + SU), i = e % (2 * SX + SU);
+                const double* xk = S.xk + CS * j;
+                const double* uk = S.uk + CS * j;
+                const double* xn = S.xn + CS * j;
+                const double* ln = S.ln + CS * j;
+                double v;
+                if (i < SX) {   // stationarity in x~_k
+                    v = S.q[CS * j + i] - W.ls(j)[k * SX + i];
+                    for (int m = 0; m < SX; ++m) v += Qe(g, i, m) * xk[m];
+                    if (k < N) {
+                        for (int m = 0; m < SU; ++m) v += Se(g, m, i) * uk[m];
+                        for (int m = 0; m < SX; ++m) v += S.A[m * SX + i] * ln[m];
+                    }
+                    S.t[CS * j + i] = v;
+                } else if (i < SX + SU) {   // stationarity in u_k
+                    const int a = i - SX;
+                    v = 0.0;
+                    if (k < N) {
+                        v = S.r[CS * j + a];
+                        for (int m = 0; m < SX; ++m) v += Se(g, a, m) * xk[m] + S.Bm[m * SU + a] * ln[m];
+                        for (int m = 0; m < SU; ++m) v += Re(g, a, m) * uk[m];
+                    }
+                    S.h[CS * j + a] = v;
+                } else {   // dynamics into k + 1
+                    const int a = i - SX - SU;
+                    v = 0.0;
+                    if (k < N) {
+                        v = S.c[CS * j + a] - xn[a];
+                        for (int m = 0; m < SX; ++m) v += S.A[a * SX + m] * xk[m];
+                        for (int m = 0; m < SU; ++m) v += S.Bm[a * SU + m] * uk[m];
+                    }
+                    S.kf[CS * j + a] = v;
+                }
+            }
+            SENS_SYNC();
+            for (int e = T.tid; e < nc * (2 * SX + SU); e += T.nt) {
+                const int j = e / (2 * SX + SU), i = e % (2 * SX + SU);
+                double v;
+                if (i < SX) { v = S.t[CS * j + i]; S.q[CS * j + i] = v; }
+                else if (i < SX + SU) { v = S.h[CS * j + i - SX]; if (k < N) S.r[CS * j + i - SX] = v; }
+                else { v = S.kf[CS * j + i - SX - SU]; if (k < N) S.c[CS * j + i - SX - SU] = v; }
+                if (k == 0 && i < SX) {   // rho_E0 = x0 - x~_0
+                    const double r0 = S.lk[CS * j + i] - S.xk[CS * j + i];
+                    S.lk[CS * j + i] = r0;
+                    v = fmax(fabs(v), fabs(r0));
+                }
+                rmax = fmax(rmax, fabs(v));
+            }
+            SENS_SYNC();
+        }
+        if (pass == 2) continue;
+        // Riccati: t = P_{k+1} c + p_{k+1}; h = r + B^T t; kff = -H^-1 h; p_k = q + A^T t + K^T h
+        if (k == N) {
+            for (int e = T.tid; e < nc * SX; e += T.nt) {
+                const int j = e / SX, i = e % SX;
+                S.pn[CS * j + i] = S.q[CS * j + i];
+                W.ps(j)[N * SX + i] = S.q[CS * j + i];
+            }
+            SENS_SYNC();
+            continue;
+        }
+        tcopy(T, S.P, W.Pst + (size_t)(k + 1) * SX * SX, SX * SX);
+        tcopy(T, S.H, W.Hi + (size_t)k * SU * SU, SU * SU);
+        tcopy(T, S.G, W.Kg + (size_t)k * SU * SX, SU * SX);
+        for (int e = T.tid; e < nc * SX; e += T.nt) {
+            const int j = e / SX, i = e % SX;
+            W.cs(j)[k * SX + i] = S.c[CS * j + i];
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * SX; e += T.nt) {
+            const int j = e / SX, i = e % SX;
+            double v = S.pn[CS * j + i];
+            for (int m = 0; m < SX; ++m) v += S.P[i * SX + m] * S.c[CS * j + m];
+            S.t[CS * j + i] = v;
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * SU; e += T.nt) {
+            const int j = e / SU, i = e % SU;
+            double v = S.r[CS * j + i];
+            for (int m = 0; m < SX; ++m) v += S.Bm[m * SU + i] * S.t[CS * j + m];
+            S.h[CS * j + i] = v;
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * (SU + SX); e += T.nt) {
+            const int j = e / (SU + SX), i = e % (SU + SX);
+            if (i < SU) {
+                double v = 0.0;
+                for (int m = 0; m < SU; ++m) v -= S.H[i * SU + m] * S.h[CS * j + m];
+                W.kf(j)[k * SU + i] = v;
+            } else {
+                const int a = i - SU;
+                double v = S.q[CS * j + a];
+                for (int m = 0; m < SX; ++m) v += S.A[m * SX + a] * S.t[CS * j + m];
+                for (int m = 0; m < SU; ++m) v += S.G[m * SX + a] * S.h[CS * j + m];
+                S.xn[CS * j + a] = v;   // p_k (staged)
+            }
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * SX; e += T.nt) {
+            const int j = e / SX, i = e % SX;
+            S.pn[CS * j + i] = S.xn[CS * j + i];
+            W.ps(j)[k * SX + i] = S.xn[CS * j + i];
+        }
+        SENS_SYNC();
+    }
+    if (pass == 2) { rn = team_max(T, rmax); bn = team_max(T, bmax); return; }
+    bn = team_max(T, bmax);
+    // forward sweep: x~_0 = x0 (lk holds it from k == 0 of the backward sweep); u = K x~ + kff; lam = P x~ + p; x~' = A x~ + B u + c
+    for (int e = T.tid; e < nc * SX; e += T.nt) S.xk[CS * (e / SX) + e % SX] = S.lk[CS * (e / SX) + e % SX];
+    SENS_SYNC();
+    for (int k = 0; k <= N; ++k) {
+        if (k < N) {
+            build_geo(T, P, k, g);
+            for (int e = T.tid; e < SX * SX; e += T.nt) S.A[e] = Ae(g, e / SX, e % SX);
+            for (int e = T.tid; e < SX * SU; e += T.nt) S.Bm[e] = Be(g, e / SU, e % SU);
+            tcopy(T, S.G, W.Kg + (size_t)k * SU * SX, SU * SX);
+        }
+        tcopy(T, S.P, W.Pst + (size_t)k * SX * SX, SX * SX);
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * (SX + SU); e += T.nt) {
+            const int j = e / (SX + SU), i = e % (SX + SU);
+            if (i < SX) {
+                double v = W.ps(j)[k * SX + i];
+                for (int m = 0; m < SX; ++m) v += S.P[i * SX + m] * S.xk[CS * j + m];
+                S.lk[CS * j + i] = v;
+            } else if (k < N) {
+                const int a = i - SX;
+                double v = W.kf(j)[k * SU + a];
+                for (int m = 0; m < SX; ++m) v += S.G[a * SX + m] * S.xk[CS * j + m];
+                S.uk[CS * j + a] = v;
+            }
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * (2 * SX + SU); e += T.nt) {   // store (or add) x~_k, lam_k, u_k
+            const int j = e / (2 * SX + SU), i = e % (2 * SX + SU);
+            double* dst;
+            double v;
+            if (i < SX) { dst = W.xs(j) + k * SX + i; v = S.xk[CS * j + i]; }
+            else if (i < 2 * SX) { dst = W.ls(j) + k * SX + i - SX; v = S.lk[CS * j + i - SX]; }
+            else { if (k == N) continue; dst = W.us(j) + k * SU + i - 2 * SX; v = S.uk[CS * j + i - 2 * SX]; }
+            *dst = pass == 0 ? v : *dst + v;
+        }
+        if (k == N) break;
+        for (int e = T.tid; e < nc * SX; e += T.nt) {
+            const int j = e / SX, i = e % SX;
+            double v = W.cs(j)[k * SX + i];
+            for (int m = 0; m < SX; ++m) v += S.A[i * SX + m] * S.xk[CS * j + m];
+            for (int m = 0; m < SU; ++m) v += S.Bm[i * SU + m] * S.uk[CS * j + m];
+            S.xn[CS * j + i] = v;
+        }
+        SENS_SYNC();
+        for (int e = T.tid; e < nc * SX; e += T.nt) S.xk[CS * (e / SX) + e % SX] = S.xn[CS * (e / SX) + e % SX];
+        SENS_SYNC();
+    }
+    SENS_SYNC();
+}
+
+// the direction along which the NLP does not determine the forces (both feet in stance over the whole horizon): left
+// corners +e, right corners -e at every knot, e along currentPos_0 - currentPos_1; returns false when there is none
+__host__ __device__ inline bool internal_dir(const Prob& P, double* e)
+{
+    const CmpcIdx& L = P.L;
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < L.N; ++k)
+            if (!(P.p[L.pGam(c) + k] > 0.5f)) return false;
+    double n2 = 0.0;
+    for (int i = 0; i < 3; ++i) { e[i] = (double)P.p[L.pCur(0) + i] - (double)P.p[L.pCur(1) + i]; n2 += e[i] * e[i]; }
+    const double s = 1.0 / sqrt(n2 * 8.0 * L.N);   // unit norm over the 24 N force entries
+    for (int i = 0; i < 3; ++i) e[i] *= s;
+    return n2 > 0.0;
+}
+
+// inner product of a force vector in x layout with the internal-force direction (one thread, fixed order)
+__host__ __device__ inline double internal_dot(const CmpcIdx& L, const double* e, const float* v)
+{
+    double s = 0.0;
+    for (int c = 0; c < 2; ++c)
+        for (int j = 0; j < 4; ++j)
+            for (int k = 0; k < L.N; ++k)
+                for (int i = 0; i < 3; ++i) s += (c == 0 ? e[i] : -e[i]) * (double)v[L.oF(c, j) + 3 * k + i];
+    return s;
+}
+
+__host__ __device__ inline unsigned fbits(float v)
+{
+    union { float f; unsigned u; } c;
+    c.f = v;
+    return c.u;
+}
+
+// subset rule of include/cmpc.h (the solver's outside_subset, restated on the staged p)
+__host__ __device__ inline bool sens_outside_subset(const Prob& P, int ct, int k)
+{
+    const CmpcIdx& L = P.L;
+    const float* p = P.p;
+    const float gm = p[L.pGam(ct) + k];
+    if (gm == 0.f) return false;
+    if (gm != 1.f) return true;
+    int kp = -1;
+    for (int j = k - 1; j >= 0 && kp < 0; --j) if (p[L.pGam(ct) + j] < 0.5f) kp = j;
+    const float* R = p + L.pR(ct) + 9 * k;
+    const float* nom = p + L.pNom(ct) + 3 * (k + 1);
+    const float* lo = p + L.pLo(ct) + 3 * k;
+    const float* up = p + L.pUp(ct) + 3 * k;
+    if (kp < 0) {
+        const float* cur = p + L.pCur(ct);
+        bool out = false;
+        for (int i = 0; i < 3; ++i) {
+            float v = 0.f;
+            for (int a = 0; a < 3; ++a) v += R[3 * i + a] * (cur[a] - nom[a]);
+            out = out || !(v >= lo[i] - 1e-6f && v <= up[i] + 1e-6f);
+        }
+        return out;
+    }
+    const float* Rp = p + L.pR(ct) + 9 * kp;
+    const float* nomp = p + L.pNom(ct) + 3 * (kp + 1);
+    const float* lop = p + L.pLo(ct) + 3 * kp;
+    const float* upp = p + L.pUp(ct) + 3 * kp;
+    bool diff = false;
+    for (int a = 0; a < 9; ++a) diff = diff || fbits(R[a]) != fbits(Rp[a]);
+    for (int a = 0; a < 3; ++a) diff = diff || fbits(nom[a]) != fbits(nomp[a]) || fbits(lo[a]) != fbits(lop[a]) || fbits(up[a]) != fbits(upp[a]);
+    return diff;
+}
+
+// ---- one problem: JVP (gx == null: k directions dir[k][np] -> out[k][nx]) or VJP (gx[nx] -> out[np]) ----
+__host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, const Prob& P, const Ws& W, const Lds& S, const float* dir, const float* gx, int kdir,
+                                            float* out, float* sens, float* vproj)
+{
+    const CmpcIdx& L = P.L;
+    const int N = L.N;
+    const bool vjp = gx != nullptr;
+    const int nout = vjp ? L.np() : kdir * L.nx();
+    // status 3: outside the supported subset, or a model that broke the model rule; status 2: input not finite
+    double flag3 = 0.0, flag2 = 0.0;
+    for (int e = T.tid; e < 2 * N; e += T.nt) if (sens_outside_subset(P, e / N, e % N)) flag3 = 1.0;
+    if (P.K->model_bad) flag3 = 1.0;
+    for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(P.x[e])) flag2 = 1.0;
+    for (int e = T.tid; e < L.np(); e += T.nt) if (!__builtin_isfinite(P.p[e])) flag2 = 1.0;
+    for (int e = T.tid; e < L.ng(); e += T.nt) if (!__builtin_isfinite(P.lam[e])) flag2 = 1.0;
+    if (vjp) { for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(gx[e])) flag2 = 1.0; }
+    else { for (long long e = T.tid; e < (long long)kdir * L.np(); e += T.nt) if (!__builtin_isfinite(dir[e])) flag2 = 1.0; }
+    flag3 = team_max(T, flag3);
+    flag2 = team_max(T, flag2);
+    double status = flag3 > 0.0 ? 3.0 : (flag2 > 0.0 ? 2.0 : 0.0);
+    double weak = 0.0, weak_swing = 0.0, sigmax = 0.0, resid = 0.0;
+    if (status == 0.0) {
+        if (factorise(T, P, W, S, weak, weak_swing, sigmax)) status = 1.0;
+        status = team_max(T, status);
+    }
+    double e3[3];
+    const bool has_e = internal_dir(P, e3);
+    double nonfinite = 0.0;
+    if (status == 0.0) {
+        Rhs R;
+        int nchunks = 1;
+        if (vjp) {   // v with no component along the internal-force direction
+            double s = 0.0;
+            if (has_e) s = internal_dot(L, e3, gx);
+            for (int e = T.tid; e < L.nx(); e += T.nt) vproj[e] = gx[e];
+            SENS_SYNC();
+            if (has_e)
+                for (int e = T.tid; e < 24 * N; e += T.nt) {
+                    const int c = e / (12 * N), j = (e / (3 * N)) % 4, r = e % (3 * N);
+                    vproj[L.oF(c, j) + r] -= s * (c == 0 ? e3[r % 3] : -e3[r % 3]);
+                }
+            SENS_SYNC();
+            R.mode = 1; R.dir = vproj; R.stride = 0;
+        } else {
+            R.mode = 0; R.stride = L.np();
+            nchunks = (kdir + SENS_KC - 1) / SENS_KC;
+        }
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const int nc = vjp ? 1 : (kdir - ch * SENS_KC < SENS_KC ? kdir - ch * SENS_KC : SENS_KC);
+            if (!vjp) R.dir = dir + (size_t)ch * SENS_KC * L.np();
+            double rn = 0.0, bn = 0.0;
+            chunk_pass(T, P, W, S, R, nc, 0, rn, bn);
+            for (int it = 0; it < SENS_NREF; ++it) chunk_pass(T, P, W, S, R, nc, 1, rn, bn);
+            chunk_pass(T, P, W, S, R, nc, 2, rn, bn);
+            resid = fmax(resid, bn > 0.0 ? rn / bn : 0.0);
+            // outputs of the chunk
+            if (!vjp) {
+                for (int e = T.tid; e < nc * L.nx(); e += T.nt) {
+                    const int j = e / L.nx(), o = e % L.nx();
+                    const double* xs = W.xs(j);
+                    const double* us = W.us(j);
+                    double v = 0.0;
+                    if (o < 9 * (N + 1)) { const int blk = o / (3 * (N + 1)), r = o % (3 * (N + 1)); v = xs[(r / 3) * SX + 3 * blk + r % 3]; }
+                    else {
+                        const int c = o < L.oPos(1) ? 0 : 1, r = o - L.oPos(c);
+                        if (r < 3 * (N + 1)) v = xs[(r / 3) * SX + sPos(c) + r % 3];
+                        else if (r < 3 * (N + 1) + 3 * N) {
+                            const int k = (r - 3 * (N + 1)) / 3, a = r % 3;
+                            if (P.p[L.pGam(c) + k] < 0.5f) v = (xs[(k + 1) * SX + sPos(c) + a] - xs[k * SX + sPos(c) + a]) / (double)P.K->dt;
+                        } else {
+                            const int rr = r - 3 * (N + 1) - 3 * N, j4 = rr / (3 * N), k = (rr % (3 * N)) / 3, a = rr % 3;
+                            v = us[k * SU + uF(c, j4) + a];
+                        }
+                    }
+                    if (!__builtin_isfinite(v)) nonfinite = 1.0;
+                    out[(size_t)(ch * SENS_KC + j) * L.nx() + o] = (float)v;
+                }
+                SENS_SYNC();
+                if (has_e)   // no component along the internal-force direction
+                    for (int j = T.tid; j < nc; j += T.nt) {
+                        float* o = out + (size_t)(ch * SENS_KC + j) * L.nx();
+                        const double s = internal_dot(L, e3, o);
+                        for (int c = 0; c < 2; ++c)
+                            for (int jj = 0; jj < 4; ++jj)
+                                for (int r = 0; r < 3 * N; ++r)
+                                    o[L.oF(c, jj) + r] = (float)((double)o[L.oF(c, jj) + r] - s * (c == 0 ? e3[r % 3] : -e3[r % 3]));
+                    }
+                SENS_SYNC();
+            } else {
+                const double* xs = W.xs(0);
+                const double* ls = W.ls(0);
+                const double* us = W.us(0);
+                const CmpcConsts& K = *P.K;
+                const double dt = K.dt;
+                for (int e = T.tid; e < L.np(); e += T.nt) {
+                    double v = 0.0;
+                    if (e >= L.pCom0()) {
+                        if (e < L.pComref()) v = -ls[e - L.pCom0()];
+                        else if (e < L.pHref()) {
+                            const int r = e - L.pComref(), k = r / 3, a = r % 3;
+                            const double hc = a == 0 ? 2.0 * (double)K.w_com0 : a == 1 ? 2.0 * (double)K.w_com1 : (double)K.wz2[k];
+                            v = hc * xs[k * SX + sCom() + a];
+                        } else if (e < L.pFext()) {
+                            const int r = e - L.pHref();
+                            v = 2.0 * (double)K.w_h * xs[(r / 3) * SX + sH() + r % 3];
+                        } else if (e < L.pText()) {
+                            const int r = e - L.pFext();
+                            v = -dt * ls[(r / 3 + 1) * SX + sDcom() + r % 3];
+                        } else {
+                            const int r = e - L.pText();
+                            v = -dt * ls[(r / 3 + 1) * SX + sH() + r % 3];
+                        }
+                    } else {
+                        const int c = e < L.pR(1) ? 0 : 1, r = e - L.pR(c);
+                        if (r >= 16 * N && r < 19 * N + 3) {   // nominalPos, knot kn
+                            const int kn = (r - 16 * N) / 3, a = (r - 16 * N) % 3;
+                            v = 2.0 * (double)K.w_pos * xs[kn * SX + sPos(c) + a];
+                            if (kn >= 1 && P.p[L.pGam(c) + kn - 1] < 0.5f) v -= ls[kn * SX + sPos(c) + a];
+                        } else if (r >= 19 * N + 3) v = -ls[sPos(c) + r - (19 * N + 3)];
+                        else if (r >= 9 * N && r < 15 * N) {   // upper (9N..12N) / lower (12N..15N)
+                            const bool upper = r < 12 * N;
+                            const int rr = upper ? r - 9 * N : r - 12 * N, k = rr / 3, i = rr % 3;
+                            if (P.p[L.pGam(c) + k] < 0.5f) {
+                                const float lo = P.p[L.pLo(c) + 3 * k + i], up = P.p[L.pUp(c) + 3 * k + i];
+                                if ((up - lo) > 1e-9f) {
+                                    // Sigma of the side (recomputed as build_geo does)
+                                    double g = 0.0;
+                                    for (int a = 0; a < 3; ++a)
+                                        g += (double)P.p[L.pR(c) + 9 * k + 3 * i + a] *
+                                             ((double)P.x[L.oPos(c) + 3 * (k + 1) + a] - (double)P.p[L.pNom(c) + 3 * (k + 1) + a]);
+                                    const double l = P.lam[P.gbox[c] + 3 * k + i];
+                                    const double sg = upper ? fmax(l, 0.0) / fmax((double)up - g, SENS_SMIN) : fmax(-l, 0.0) / fmax(g - (double)lo, SENS_SMIN);
+                                    v = sg * us[k * SU + uQ(c) + i];
+                                } else {
+                                    // fixed component: -1/2 (R^-T e_i) . lam_{k+1, pos}
+                                    const float* Rp = P.p + L.pR(c) + 9 * k;
+                                    double Rm[9], cof[9];
+                                    for (int a = 0; a < 3; ++a)
+                                        for (int b2 = 0; b2 < 3; ++b2) Rm[3 * a + b2] = Rp[3 * b2 + a];
+                                    for (int a = 0; a < 3; ++a)
+                                        for (int b2 = 0; b2 < 3; ++b2) {
+                                            const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, c1 = (b2 + 1) % 3, c2 = (b2 + 2) % 3;
+                                            cof[3 * a + b2] = Rm[3 * a1 + c1] * Rm[3 * a2 + c2] - Rm[3 * a1 + c2] * Rm[3 * a2 + c1];
+                                        }
+                                    const double det = Rm[0] * cof[0] + Rm[1] * cof[1] + Rm[2] * cof[2];
+                                    for (int a = 0; a < 3; ++a) v -= 0.5 * (cof[3 * a + i] / det) * ls[(k + 1) * SX + sPos(c) + a];
+                                }
+                            }
+                        }
+                    }
+                    if (!__builtin_isfinite(v)) nonfinite = 1.0;
+                    out[e] = (float)v;
+                }
+                SENS_SYNC();
+            }
+        }
+        if (!__builtin_isfinite(resid)) nonfinite = 1.0;
+        nonfinite = team_max(T, nonfinite);
+        if (nonfinite > 0.0) status = 2.0;
+    }
+    if (status != 0.0) {
+        for (long long e = T.tid; e < nout; e += T.nt) out[e] = 0.f;
+        resid = 0.0;
+    }
+    if (T.tid == 0 && sens) {
+        sens[0] = (float)status; sens[1] = (float)resid; sens[2] = (float)weak; sens[3] = (float)sigmax;
+        sens[4] = has_e ? 1.f : 0.f;
+        sens[5] = (float)weak_swing;
+        for (int i = 6; i < CMPC_SENS; ++i) sens[i] = 0.f;
+    }
+}
+
+// LDS of the kernel: constants | x | p | lam (floats) | v projected (floats) | Geo | dense doubles | 4 reduction doubles
+__host__ __device__ inline size_t sens_lds_floats(int N)
+{
+    const CmpcIdx L{N};
+    return ((sizeof(CmpcConsts) + 15) / 16) * 4 + ((L.nx() + 3) & ~3) + ((L.np() + 3) & ~3) + ((L.ng() + 3) & ~3) + ((L.nx() + 3) & ~3);
+}
+inline size_t sens_lds_bytes(int N)
+{
+    return sens_lds_floats(N) * 4 + ((sizeof(Geo) + 15) & ~(size_t)15) + 8 * (size_t)(Lds::doubles() + 4);
+}
+
+// carves the dense area: the factorisation's eight matrices; the column slots overlay PA, PB, Y (12 x 40 x 8 = 3840 doubles <= their 3861)
+__host__ __device__ inline Lds carve(double* base, Geo* g)
+{
+    Lds S;
+    S.g = g;
+    S.P = base; S.A = S.P + SX * SX; S.Bm = S.A + SX * SX; S.G = S.Bm + SX * SU; S.H = S.G + SU * SX;
+    S.PA = S.H + SU * SU; S.PB = S.PA + SX * SX; S.Y = S.PB + SX * SU;
+    // column slots: [12][KC][CS] over PA | PB | Y, which only the factorisation uses (the passes keep P, A, Bm, G, H)
+    double* cs = S.PA;
+    S.q = cs; S.r = cs + CS * SENS_KC; S.c = cs + 2 * CS * SENS_KC; S.pn = cs + 3 * CS * SENS_KC; S.t = cs + 4 * CS * SENS_KC;
+    S.h = cs + 5 * CS * SENS_KC; S.kf = cs + 6 * CS * SENS_KC; S.xk = cs + 7 * CS * SENS_KC; S.uk = cs + 8 * CS * SENS_KC;
+    S.xn = cs + 9 * CS * SENS_KC; S.ln = cs + 10 * CS * SENS_KC; S.lk = cs + 11 * CS * SENS_KC;
+    return S;
+}
+
+}  // namespace
+
+// ---- the kernel: one workgroup per problem of the sub-batch [b0, b0 + gridDim.x) ----
+__global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts* __restrict__ kc, int kc_per_problem, int N, int b0,
+                                                               const float* __restrict__ X, const float* __restrict__ Pp, const float* __restrict__ LamG,
+                                                               const float* __restrict__ Dir, const float* __restrict__ GradX, int kdir,
+                                                               float* __restrict__ Out, float* __restrict__ Sens, double* __restrict__ Wsp)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int bl = blockIdx.x, b = b0 + bl;
+    CmpcConsts& K = *reinterpret_cast<CmpcConsts*>(smem);
+    {
+        const int* src = reinterpret_cast<const int*>(kc_per_problem ? kc + b : kc);
+        int* dst = reinterpret_cast<int*>(smem);
+        for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += SENS_NT) dst[e] = src[e];
+    }
+    const CmpcIdx L{N};
+    float* x = reinterpret_cast<float*>(smem) + ((sizeof(CmpcConsts) + 15) / 16) * 4;
+    float* p = x + ((L.nx() + 3) & ~3);
+    float* lam = p + ((L.np() + 3) & ~3);
+    float* vproj = lam + ((L.ng() + 3) & ~3);
+    Geo* g = reinterpret_cast<Geo*>(smem + sens_lds_floats(N) * 4);
+    double* dense = reinterpret_cast<double*>(reinterpret_cast<char*>(g) + ((sizeof(Geo) + 15) & ~(size_t)15));
+    double* red = dense + Lds::doubles();
+    for (int e = tid; e < L.nx(); e += SENS_NT) x[e] = X[(size_t)b * L.nx() + e];
+    for (int e = tid; e < L.np(); e += SENS_NT) p[e] = Pp[(size_t)b * L.np() + e];
+    for (int e = tid; e < L.ng(); e += SENS_NT) lam[e] = LamG[(size_t)b * L.ng() + e];
+    __syncthreads();
+    Prob P;
+    P.K = &K; P.L = L; P.x = x; P.p = p; P.lam = lam;
+    P.gh = 15 + 6 * N;
+    for (int c = 0; c < 2; ++c) { P.gbox[c] = 15 + 15 * N + c * 19 * N; P.gfric[c] = P.gbox[c] + 3 * N; }
+    Ws W;
+    W.N = N;
+    W.Pst = Wsp + (size_t)bl * Ws::doubles(N);
+    W.Hi = W.Pst + (size_t)(N + 1) * SX * SX;
+    W.Kg = W.Hi + (size_t)N * SU * SU;
+    W.col = W.Kg + (size_t)N * SU * SX;
+    const Team T{tid, SENS_NT, red};
+    const Lds S = carve(dense, g);
+    if (GradX) sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * L.nx(), 1, Out + (size_t)b * L.np(), Sens ? Sens + (size_t)b * CMPC_SENS : nullptr, vproj);
+    else sens_problem(T, P, W, S, Dir + (size_t)b * kdir * L.np(), nullptr, kdir, Out + (size_t)b * kdir * L.nx(), Sens ? Sens + (size_t)b * CMPC_SENS : nullptr, vproj);
+}
+
+// workspace bytes per problem of the launch below
+extern "C" size_t cmpc_sensitivity_workspace_bytes(int N) { return sizeof(double) * (size_t)Ws::doubles(N); }
+
+// problems [b0, b0 + nb) of the batch; the workspace holds nb problems
+extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
+                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, hipStream_t stream)
+{
+    const size_t lds = sens_lds_bytes(N);
+    static int configured = 0;
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute((const void*)cmpc_sensitivity_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return (int)e;
+        configured = 1;
+    }
+    hipLaunchKernelGGL(cmpc_sensitivity_kernel, dim3(nb), dim3(SENS_NT), lds, stream, kc, kc_per_problem, N, b0, dX, dP, dLamG, dDir, dGradX, kdir, dOut,
+                       dSens, dWs);
+    return (int)hipGetLastError();
+}

@@ -253,6 +253,55 @@ class BatchSolver:
                                                                                        o.data_ptr(), st),
                              "cmpc_value_gradient_device")
 
+    # ---- solution sensitivities dx*/dp (include/cmpc.h) ----
+    def solution_jvp_device(self, dX, dP, dLamG, dDirP, out=None, sens=None):
+        """dx*/dp applied to k directions: dDirP[B, k, n_p] -> (dDX[B, k, n_x], sens[B, CMPC_SENS]) at the returned point (x, p, lam_g) of a solve.
+        sens = (status 0 ok / 1 non-positive pivot / 2 not finite / 3 outside the subset, relative residual, weakly active rows, largest Sigma, ...);
+        a flagged problem's outputs are zero."""
+        import torch
+        L = self.layout
+        assert dDirP.is_cuda and dDirP.dtype == torch.float32 and dDirP.is_contiguous() and dDirP.dim() == 3
+        assert tuple(dDirP.shape[::2]) == (self.batch, L.np) and dDirP.shape[1] >= 1
+        k = int(dDirP.shape[1])
+        if out is None:
+            out = torch.empty((self.batch, k, L.nx), dtype=torch.float32, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, k, L.nx) and out.dtype == torch.float32
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_jvp_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                     dDirP.data_ptr(), k, out.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_jvp_device")
+        return out, sens
+
+    def solution_vjp_device(self, dX, dP, dLamG, dGradX, out=None, sens=None):
+        """(dx*/dp)^T v: dGradX[B, n_x] = dl/dx -> (dl/dp [B, n_p], sens[B, CMPC_SENS])."""
+        import torch
+        L = self.layout
+        assert dGradX.is_cuda and dGradX.dtype == torch.float32 and dGradX.is_contiguous() and tuple(dGradX.shape) == (self.batch, L.nx)
+        if out is None:
+            out = torch.empty((self.batch, L.np), dtype=torch.float32, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, L.np) and out.dtype == torch.float32
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_vjp_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                     dGradX.data_ptr(), out.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_vjp_device")
+        return out, sens
+
+    def feedback_gain_device(self, dX, dP, dLamG):
+        """The linearised MPC policy: d(first-knot corner forces)/d(com0, dcom0, h0) -> (gain[B, 24, 9], sens[B, CMPC_SENS]); rows in the
+        order of Layout.first_forces (contact, corner, axis), columns com0 xyz, dcom0 xyz, h0 xyz.  One JVP with 9 directions."""
+        import torch
+        L = self.layout
+        dirs = torch.zeros((self.batch, 9, L.np), dtype=torch.float32, device=dX.device)
+        for i in range(9):
+            dirs[:, i, L.p_com0 + i] = 1.0
+        dDX, sens = self.solution_jvp_device(dX, dP, dLamG, dirs)
+        idx = torch.as_tensor(np.concatenate([np.arange(L.f[c][j], L.f[c][j] + 3) for c in range(2) for j in range(4)]), device=dX.device)
+        return dDX[:, :, idx].transpose(1, 2).contiguous(), sens
+
+    def workspace_bytes_per_problem(self) -> int:
+        """bytes of the sensitivity workspace per problem (cmpc_sensitivity_workspace_bytes)"""
+        return int(self._lib.cmpc_sensitivity_workspace_bytes(self.layout.N))
+
     def plant_step_device(self, dX, dP, dState, dStateOut=None, dZmp=None, step=0.01, substeps=6,
                           zmp_half_x=0.08, zmp_half_y=0.03):
         """Closed-loop plant between two MPC ticks (WholeBodyQPBlock.cpp:805-873, 1083-1084, 1150): RK4 of the
@@ -542,6 +591,29 @@ class CentroidalMPC:
             return None
         return lam
 
+    def get_feedback_gain(self):
+        """d(first-knot corner forces)/d(com0, dcom0, h0) [B, 24, 9] of the last advance() (BatchSolver.feedback_gain_device at its solution, its
+        parameters and its multipliers), or None.  Needs the multiplier output on before advance() (set_multiplier_output); a problem whose
+        sensitivity status is not 0 gets a zero gain (get_feedback_gain_info() returns the [B, CMPC_SENS] words)."""
+        import torch
+        if not self._need_init():
+            return None
+        X, _ = self.get_solution()
+        lam = self.get_multipliers()
+        if X is None or lam is None:
+            return None
+        L = Layout(self.cfg.N)
+        P = np.empty((self._batch, L.np), np.float32)
+        if not self._ok(self._lib.cmpc_get_parameters(self._h, P.ctypes.data)):
+            return None
+        dev = torch.device("cuda", self._device)
+        gain, sens = self._solver.feedback_gain_device(*(torch.from_numpy(a).to(dev) for a in (X, P, lam)))
+        self._gain_sens = sens.cpu().numpy()
+        return gain.cpu().numpy()
+
+    def get_feedback_gain_info(self):
+        return getattr(self, "_gain_sens", None)
+
     def get_solution(self):
         L = Layout(self.cfg.N)
         X = np.empty((self._batch, L.nx), np.float32)
@@ -549,3 +621,31 @@ class CentroidalMPC:
         if not self._ok(self._lib.cmpc_get_solution(self._h, X.ctypes.data, info.ctypes.data)):
             return None, None
         return X, info
+
+
+def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False):
+    """x*(P) as a torch.autograd.Function: forward solves (solve_device) and keeps (X, P, lam_g); backward returns P.grad by the VJP of
+    include/cmpc.h (cmpc_solution_vjp_device) and None for X0.  The multiplier output of `solver` is turned on if it is off (it stays on).
+    Problems whose sensitivity status is not 0 get zero rows of P.grad; solver.last_sensitivity_info holds the [B, CMPC_SENS] words of the
+    last backward, and solver.last_info the [B, CMPC_INFO] words of the last forward."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, P, X0):
+            solver.set_multiplier_output(True)
+            Pc, X0c = P.detach().contiguous(), X0.detach().contiguous()
+            X, info = solver.solve_device(Pc, X0c, warm=warm)
+            lam = solver.multipliers_device(X, Pc)
+            solver.last_info = info
+            ctx.save_for_backward(X, Pc, lam)
+            return X
+
+        @staticmethod
+        def backward(ctx, gX):
+            X, Pc, lam = ctx.saved_tensors
+            gP, sens = solver.solution_vjp_device(X, Pc, lam, gX.contiguous().to(torch.float32))
+            solver.last_sensitivity_info = sens
+            return gP, None
+
+    return _Fn.apply(P, X0)
