@@ -235,7 +235,8 @@ int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP,
 /* Gradient of the optimal cost with respect to every parameter (envelope theorem) at a KKT point (x*, lam*): dGradP[B][n_p] = grad_p L(x, lam)
  * (nlp_grad, lam_f = 1) plus the parameters that only enter the bounds: -lam_init on com0, dcom0, h0 and currentPos; -max(lam, 0) on upper and
  * -min(lam, 0) on lower of each box row.  The entries of enabled (Gamma, binary) and R (constrained to rotations) are formal derivatives of the
- * generated code, not derivatives along feasible perturbations.  No derivatives with respect to the per-problem model fields. */
+ * generated code, not derivatives along feasible perturbations.  The derivatives with respect to the per-problem model fields are
+ * cmpc_model_value_gradient_device (below, "model directions"). */
 int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream);
 
 /* ---- solution sensitivities: dx* / dp as JVP and VJP (derivation: DESIGN.md 7c) ----
@@ -253,8 +254,8 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
  * (lower + upper) / 2 (a perturbation that stays in the subset moves both).  JVP: dx.  VJP: the same symmetric system with right-hand side [v; 0],
  * v = dl/dx, and dl/dp = -w^T r_p.
  * Parameters covered: com0, dcom0, h0, currentPos, comRef, hRef, nominalPos, box upper / lower, fExt, tauExt.  Not covered: Gamma (enabled, discrete)
- * and R (rotations; a tangent-space derivative is not provided): the JVP reads those entries of dp as zero, the VJP writes zeros there; nor the fields
- * of the per-problem model.
+ * and R (rotations; a tangent-space derivative is not provided): the JVP reads those entries of dp as zero, the VJP writes zeros there.  The fields of
+ * the per-problem model are covered by the *_model_device entry points below ("model directions").
  * Tied entries (subset rule 3): a stance stage after a landing repeats the last swing stage's R, nominal, lower and upper.  Under this map a stance
  * stage's lower / upper have zero derivative and a stance knot's nominalPos acts through the cost only; a perturbation that stays in the subset moves
  * the whole group, and its derivative is the sum over the group.
@@ -272,7 +273,8 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
  *                         number of weakly active rows of loaded feet (friction rows of stance stages) and of box sides;  largest Sigma;
  *                         1 if the internal-force direction exists (and was projected out);
  *                         number of weakly active friction rows of swing stages (counted apart: a swing foot's forces enter no dynamics, and they
- *                           sit near the apex because the costs pull them towards zero from inside the pyramid, not because a face binds);  0, 0 }.
+ *                           sit near the apex because the costs pull them towards zero from inside the pyramid, not because a face binds);
+ *                         the removed relative component of model directions along the internal-force direction (0 here; "model directions");  0 }.
  * A flagged problem gets zero outputs; its neighbours are unaffected.  Per-problem models (cmpc_set_models*) apply; every horizon the handle supports.
  * Workspace: per-handle HBM, allocated on first use and freed by cmpc_destroy, for min(B, CMPC_SENS_SUB_BATCH) problems (larger batches run in
  * sub-batches): cmpc_sensitivity_workspace_bytes(N) per problem -- 8 (39^2 (N+1) + 2070 N + 8 (216 N + 117)) bytes, 0.85 MB at N = 20.
@@ -293,6 +295,48 @@ int cmpc_solution_jvp_device(cmpc_handle h, const float* dX, const float* dP, co
 int cmpc_solution_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP, float* dSens,
                              void* stream);
 size_t cmpc_sensitivity_workspace_bytes(int horizon);
+
+/* ---- model directions: derivatives with respect to the per-problem model (derivation: DESIGN.md 7c) ----
+ * theta = the 34 doubles of cmpc_model in its field order (0 friction, 1..3 com_weight, 4 angular_momentum_weight, 5 contact_position_weight,
+ * 6..8 force_rate_of_change_weight, 9 contact_force_symmetry_weight, 10 + 12 c + 3 j + b corner j of contact c, axis b).  No bound depends on theta.
+ * At fixed (x, lam) theta enters L = f + lam_g^T g as follows:
+ *   weights: linearly through f, except com_weight[2], which enters quadratically: the term is (w_z(k) (com_z - ref_z))^2 with
+ *     w_z(k) = (w_cz / 2)(1 + e^-k) (the solver's record wz2 = 2 w_z^2);  the symmetry and force-rate weights act on the corner forces, the rate
+ *     cost couples knots k and k+1 only;
+ *   friction: linearly through the friction rows, as -mu (R^T f)_z;
+ *   corners: linearly through the angular-momentum dynamics, (R cn + pos - com) x f, and so also through grad_x(lam^T g) on the force columns.
+ * In the barrier system of the solution sensitivities above, a model direction dtheta has the right-hand side
+ *     r_x = d_theta(grad_x L) dtheta + sum_{i in I} J_i^T Sigma_i d_theta g_i dtheta,     r_E = d_theta g_E dtheta
+ * (Sigma, the rows E / I, the slack floor, the shift, the refinement and dSens exactly as there).  JVP: dx = the first block of K^-1 (-r(dp, dtheta)),
+ * so p and theta directions combine in one column.  VJP: dl/dtheta = -w^T r_theta with the same w as cmpc_solution_vjp_device.  Value gradient:
+ * dV* / dtheta = d_theta f + lam^T d_theta g at (x, lam) (envelope theorem).
+ * The derivative is taken at the model the solve used: the float32 record that cmpc_create or cmpc_set_models* derived (d wz2 / d w_cz =
+ * sqrt(2 wz2(k)) (1 + e^-k)).  Without a model table theta is the config's model for every problem.  A row whose model broke the model rule gets
+ * status 3 and zero outputs.
+ * Internal force (both feet in stance over the whole horizon): K has a null vector whose primal part is n (left corners +e, right corners -e) and
+ * whose dual part sits on the foot-position rows, which no model field enters; a model right-hand side is consistent only if n^T r_x = 0.  The weights
+ * satisfy it up to rounding (the symmetry cost is blind to a force constant over a foot's corners, the rate terms telescope); friction leaves a
+ * component through Sigma (small, up to order one where the friction rows carry the load); a corner direction that moves the two feet's rotated
+ * corner sums differently gives the internal force a moment arm, and its component is sum_k lam_h,k . (R e_b x e): zero up to the solve's tolerance
+ * while the couples about x and z are free (no loaded friction row), large otherwise.  Along a direction with a component the true map has no
+ * derivative.  Rule: the JVP removes r_x's component along n before the solve; the VJP removes the same component from every r_t (it contracts with
+ * -w^T r_t + (n^T w)(n^T r_t): w can carry a component along n, since v is projected in float32 and the shifted system amplifies what is left), so the
+ * two stay adjoint.  The removed relative size |n^T r_x| / |r_x| (r_x in the NLP's x layout, of the model part of the column) is reported in dSens[6]:
+ * the largest over the k columns (JVP) or over the 34 fields (VJP); 0 without model directions or without n.  For the same reason the friction and
+ * corner entries of dV* / dtheta at such a point depend on the internal force the solve happened to return: not exact derivatives where that
+ * direction's dSens[6] is not small.
+ * No workspace beyond cmpc_sensitivity_workspace_bytes; sub-batches, the event ordering and the bit-for-bit independence of batch position, batch
+ * size, k and sub-batching as for the solution sensitivities.
+ * JVP: dDirP[B][k][n_p] float (NULL: zero), dDirModel[B][k][34] double (NULL: zero) -> dDX[B][k][n_x].  With dDirModel == NULL the result is
+ * cmpc_solution_jvp_device's, bit for bit. */
+int cmpc_solution_jvp_model_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const double* dDirModel, int k,
+                                   float* dDX, float* dSens, void* stream);
+/* VJP: dGradX[B][n_x] -> dGradP[B][n_p] (NULL: not written; otherwise cmpc_solution_vjp_device's output bit for bit) and dGradModel[B][34] double,
+ * from one adjoint solve */
+int cmpc_solution_vjp_model_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP,
+                                   double* dGradModel, float* dSens, void* stream);
+/* dV* / dtheta [B][34] double at (x, lam_g); zeros for a row whose model broke the model rule */
+int cmpc_model_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradModel, void* stream);
 
 /* ---- class-shaped setters (host buffers -> the handle's own device P, X0) ----
  * batch-major float32; NULL keeps the previous value (zeros initially).

@@ -83,7 +83,7 @@ EXPORTS = [
     "cmpc_model_from_config", "cmpc_check_models", "cmpc_set_models", "cmpc_set_models_device",
     "cmpc_set_multiplier_output", "cmpc_get_multipliers_device", "cmpc_get_multipliers", "cmpc_kkt_certificate_device",
     "cmpc_value_gradient_device", "cmpc_solution_jvp_device", "cmpc_solution_vjp_device",
-    "cmpc_sensitivity_workspace_bytes",
+    "cmpc_sensitivity_workspace_bytes", "cmpc_solution_jvp_model_device", "cmpc_solution_vjp_model_device", "cmpc_model_value_gradient_device",
 ]
 
 _lib = None
@@ -162,6 +162,10 @@ def lib():
         L.cmpc_solution_vjp_device.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
         L.cmpc_sensitivity_workspace_bytes.argtypes = [C.c_int]
         L.cmpc_sensitivity_workspace_bytes.restype = C.c_size_t
+        if hasattr(L, "cmpc_solution_jvp_model_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_solution_jvp_model_device.argtypes = [vp, fp, fp, fp, fp, vp, C.c_int, fp, fp, vp]
+            L.cmpc_solution_vjp_model_device.argtypes = [vp, fp, fp, fp, fp, fp, vp, fp, vp]
+            L.cmpc_model_value_gradient_device.argtypes = [vp, fp, fp, fp, vp, vp]
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

@@ -24,7 +24,10 @@ extern "C" int cmpc_launch_multipliers(const CmpcParams* prm, const float* dX, c
 extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dCert, hipStream_t stream);
 extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream);
 extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
-                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, hipStream_t stream);
+                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
+                                       double* dGradModel, hipStream_t stream);
+extern "C" int cmpc_launch_model_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradModel,
+                                                hipStream_t stream);
 extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev, float* dX0, hipStream_t stream);
 extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double* plan_t, const float* plan_pose, const int* plan_n,
                                           const double* mpc_t, const float* mpc_pose, const int* mpc_n, double* out_t, float* out_pose,
@@ -769,7 +772,7 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
 
 // ---- solution sensitivities (include/cmpc.h; cmpc_sensitivity.hip) ----
 static int sensitivity(cmpc_handle h, const char* name, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const float* dGradX,
-                       int k, float* dOut, float* dSens, void* stream)
+                       int k, float* dOut, float* dSens, void* stream, const double* dDirModel = nullptr, double* dGradModel = nullptr)
 {
     HIPCHK(h, hipSetDevice(h->device));
     const int N = h->cfg.horizon, sb = h->B < CMPC_SENS_SUB_BATCH ? h->B : CMPC_SENS_SUB_BATCH;
@@ -781,7 +784,8 @@ static int sensitivity(cmpc_handle h, const char* name, const float* dX, const f
     else HIPCHK(h, hipStreamWaitEvent(st, h->sens_ev, 0));
     for (int b0 = 0; b0 < h->B; b0 += sb) {
         const int nb = h->B - b0 < sb ? h->B - b0 : sb;
-        int rc = cmpc_launch_sensitivity(kc, h->models_set ? 1 : 0, N, b0, nb, dX, dP, dLamG, dDirP, dGradX, k, dOut, dSens, h->dSensWs, st);
+        int rc = cmpc_launch_sensitivity(kc, h->models_set ? 1 : 0, N, b0, nb, dX, dP, dLamG, dDirP, dGradX, k, dOut, dSens, h->dSensWs, dDirModel,
+                                         dGradModel, st);
         if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString((hipError_t)rc));
     }
     HIPCHK(h, hipEventRecord(h->sens_ev, st));
@@ -801,6 +805,33 @@ int cmpc_solution_vjp_device(cmpc_handle h, const float* dX, const float* dP, co
 {
     if (!h || !dX || !dP || !dLamG || !dGradX || !dGradP) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_device: null argument");
     return sensitivity(h, "cmpc_solution_vjp_device", dX, dP, dLamG, nullptr, dGradX, 1, dGradP, dSens, stream);
+}
+
+// ---- derivatives with respect to the per-problem model (include/cmpc.h, "model directions") ----
+int cmpc_solution_jvp_model_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const double* dDirModel, int k,
+                                   float* dDX, float* dSens, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dDX) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_model_device: null argument");
+    if (k < 1) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_model_device: k must be >= 1");
+    return sensitivity(h, "cmpc_solution_jvp_model_device", dX, dP, dLamG, dDirP, nullptr, k, dDX, dSens, stream, dDirModel, nullptr);
+}
+
+int cmpc_solution_vjp_model_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP,
+                                   double* dGradModel, float* dSens, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradX || !dGradModel) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_model_device: null argument");
+    return sensitivity(h, "cmpc_solution_vjp_model_device", dX, dP, dLamG, nullptr, dGradX, 1, dGradP, dSens, stream, nullptr, dGradModel);
+}
+
+int cmpc_model_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradModel, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradModel) return fail(h, CMPC_ERR_ARG, "cmpc_model_value_gradient_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcParams p;
+    fill_params(h, p);
+    int rc = cmpc_launch_model_value_gradient(&p, dX, dP, dLamG, dGradModel, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("model value gradient launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
 }
 
 // ---- 8f-3: planner references -> MPC knots (CentroidalMPCBlock.cpp:525-577): angular momentum / mass, CoM height

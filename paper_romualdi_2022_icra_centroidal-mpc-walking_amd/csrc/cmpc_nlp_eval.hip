@@ -730,6 +730,109 @@ __global__ __launch_bounds__(256) void cmpc_value_gradient_kernel(CmpcParams kp,
     }
 }
 
+// knot k's share of dV*/dtheta_t = d_theta f + lam^T d_theta g for field t of cmpc_model's packed order (include/cmpc.h, "model directions"): the
+// weights through f (com_weight[2] as wz2(k) = 2 w_z(k)^2, d wz2 / d w_cz = sqrt(2 wz2) (1 + e^-k), at the problem's float32 record), friction
+// through the friction rows (-(R^T f)_z), corner (c, j, b) through the angular-momentum rows (-dt gam (R e_b) x f)
+template <typename T>
+__device__ inline T nlp_model_grad_knot(const NlpView& V, int t, int k)
+{
+    const CmpcConsts& K = V.K;
+    const CmpcIdx& L = V.L;
+    const GLay& G = V.G;
+    const float *x = V.x, *p = V.p, *lam = V.lam;
+    const int N = L.N;
+    T v = T(0);
+    if (t >= 1 && t <= 3) {
+        const int i = t - 1;
+        const T ec = T(x[L.oCom() + 3 * k + i]) - T(p[L.pComref() + 3 * k + i]);
+        const T w = i < 2 ? T(1) : T(0.5) * T(sqrt(2.0 * (double)K.wz2[k]) * (1.0 + exp(-(double)k)));
+        return w * ec * ec;
+    }
+    if (t == 4 || t == 5) {
+        for (int i = 0; i < 3; ++i) {
+            if (t == 4) { const T e = T(x[L.oH() + 3 * k + i]) - T(p[L.pHref() + 3 * k + i]); v += e * e; }
+            else
+                for (int c = 0; c < 2; ++c) { const T e = T(x[L.oPos(c) + 3 * k + i]) - T(p[L.pNom(c) + 3 * k + i]); v += e * e; }
+        }
+        return v;
+    }
+    if (k >= N) return v;
+    if (t == 0) {   // lam_fric^T d g_fric / d mu = -sum lam (R^T f)_z
+        for (int c = 0; c < 2; ++c) {
+            const float* R = p + L.pR(c) + 9 * k;
+            for (int j = 0; j < 4; ++j) {
+                const float* f = x + L.oF(c, j) + 3 * k;
+                const T fl2 = T(R[6]) * T(f[0]) + T(R[7]) * T(f[1]) + T(R[8]) * T(f[2]);
+                const float* lf = lam + G.g_fric[c] + 16 * k + 4 * j;
+                v -= (T(lf[0]) + T(lf[1]) + T(lf[2]) + T(lf[3])) * fl2;
+            }
+        }
+        return v;
+    }
+    if (t >= 6 && t <= 9) {
+        for (int c = 0; c < 2; ++c)
+            for (int i = 0; i < 3; ++i) {
+                if (t < 9 && i != t - 6) continue;
+                T mean = T(0);
+                for (int j = 0; j < 4; ++j) mean += T(0.25f) * T(x[L.oF(c, j) + 3 * k + i]);
+                for (int j = 0; j < 4; ++j) {
+                    const T fv = T(x[L.oF(c, j) + 3 * k + i]);
+                    if (t == 9) { const T es = fv - T(V.gam(c, k)) * mean; v += es * es; }
+                    else if (k + 1 < N) { const T d = T(x[L.oF(c, j) + 3 * (k + 1) + i]) - fv; v += d * d; }
+                }
+            }
+        return v;
+    }
+    const int c = (t - 10) / 12, j = ((t - 10) % 12) / 3, b = (t - 10) % 3;   // corner (c, j), axis b
+    const float* R = p + L.pR(c) + 9 * k;
+    const T rb[3] = {T(R[3 * b]), T(R[3 * b + 1]), T(R[3 * b + 2])}, f[3] = {T(x[L.oF(c, j) + 3 * k]), T(x[L.oF(c, j) + 3 * k + 1]),
+                                                                           T(x[L.oF(c, j) + 3 * k + 2])};
+    for (int i = 0; i < 3; ++i) v -= T(lam[G.g_h + 3 * k + i]) * T(K.dt) * T(V.gam(c, k)) * crossc(rb, f, i);
+    return v;
+}
+
+// ---- dV*/dtheta of the per-problem model at (x, lam_g) (envelope theorem), double arithmetic, one workgroup per problem: items (field, knot) spread
+// over the team, partial sums in LDS after the staged lam_g, one thread per field adds its knots in order.  A record whose model broke the model rule
+// gets zeros. ----
+__global__ __launch_bounds__(256) void cmpc_model_value_gradient_kernel(CmpcParams kp, const float* __restrict__ X, const float* __restrict__ P,
+                                                                        const float* __restrict__ LamG, double* __restrict__ GradM)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, NT = 256;
+    const int b = blockIdx.x;
+    const int N = kp.N, M = CMPC_MODEL_DOUBLES, nk = N + 1;
+    CmpcConsts& K = *reinterpret_cast<CmpcConsts*>(smem);
+    {
+        const int* src = reinterpret_cast<const int*>(kp.kc_per_problem ? kp.kc + b : kp.kc);
+        int* dst = reinterpret_cast<int*>(smem);
+        for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += NT) dst[e] = src[e];
+    }
+    const CmpcIdx L{N};
+    GLay G;
+    glay_init(G, N);
+    float* x = reinterpret_cast<float*>(smem + ((sizeof(CmpcConsts) + 15) & ~15));
+    float* p = x + ((L.nx() + 3) & ~3);
+    float* lam = p + ((L.np() + 3) & ~3);
+    double* part = reinterpret_cast<double*>(lam + ((L.ng() + 3) & ~3) + 8);
+    for (int e = tid; e < L.nx(); e += NT) x[e] = X[(size_t)b * L.nx() + e];
+    for (int e = tid; e < L.np(); e += NT) p[e] = P[(size_t)b * L.np() + e];
+    for (int e = tid; e < L.ng(); e += NT) lam[e] = LamG[(size_t)b * L.ng() + e];
+    __syncthreads();
+    double* out = GradM + (size_t)b * M;
+    if (K.model_bad) {
+        for (int t = tid; t < M; t += NT) out[t] = 0.0;
+        return;
+    }
+    const NlpView V{K, L, G, x, p, lam};
+    for (int e = tid; e < M * nk; e += NT) part[e] = nlp_model_grad_knot<double>(V, e / nk, e % nk);
+    __syncthreads();
+    for (int t = tid; t < M; t += NT) {
+        double v = 0.0;
+        for (int k = 0; k < nk; ++k) v += part[t * nk + k];
+        out[t] = v;
+    }
+}
+
 // warm start: previous solution shifted by one knot (last knot repeated); is_warm_start_enabled of
 // the reference (ergoCubGazeboV1/centroidal_mpc.ini:9)
 // (one problem: xp -> x0, thread tid of nt)
@@ -925,6 +1028,14 @@ extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* d
 extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_value_gradient_kernel, dim3(prm->B), dim3(256), nlp_lds_bytes(prm->N), stream, *prm, dX, dP, dLamG, dGradP);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_model_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradModel,
+                                                hipStream_t stream)
+{
+    const size_t lds = nlp_lds_bytes(prm->N) + sizeof(double) * CMPC_MODEL_DOUBLES * (size_t)(prm->N + 1);
+    hipLaunchKernelGGL(cmpc_model_value_gradient_kernel, dim3(prm->B), dim3(256), lds, stream, *prm, dX, dP, dLamG, dGradModel);
     return (int)hipGetLastError();
 }
 

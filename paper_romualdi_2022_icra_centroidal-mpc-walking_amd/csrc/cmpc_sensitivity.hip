@@ -7,6 +7,8 @@
 //      gain K = -H^-1 G go to a per-handle HBM workspace (the stage matrices are rebuilt from x, p, lam_g wherever they are needed);
 //   2. per chunk of up to SENS_KC right-hand sides: a backward and a forward pass, then SENS_NREF steps of iterative refinement against the
 //      unshifted operator, then one pass that measures the relative residual.
+// Model directions (include/cmpc.h, "model directions"): the per-problem model theta adds right-hand-side terms (model_q / model_r / model_c) to the
+// JVP's columns, and the VJP contracts the same entries with its stored adjoint into 34 sums per problem (model_vjp).
 // No atomics: every reduction is a fixed tree or one thread's loop, so a problem's result depends on nothing but its own inputs.
 #include "cmpc_device.h"
 
@@ -309,11 +311,138 @@ struct Lds {
     __host__ __device__ static int doubles() { return 3 * SX * SX + 3 * SX * SU + SU * SU + SU * SX; }
 };
 
+// ---- the per-problem model as a direction (include/cmpc.h, "model directions") ----
+// Fields in cmpc_model's packed order: 0 friction, 1..3 com_weight, 4 angular momentum, 5 contact position, 6..8 force rate, 9 symmetry,
+// 10 + 12 c + 3 j + b the corner (c, j), axis b.  The derivative is taken at the problem's float32 record; com_weight[2] enters as
+// wz2(k) = 2 w_z(k)^2 = w_cz^2 (1 + e^-k)^2 / 2, so d wz2 / d w_cz = sqrt(2 wz2) (1 + e^-k).
+struct MDir {
+    const double* d;   // the caller's dtheta[34] (t < 0)
+    int t;             // or the unit vector of field t
+    __host__ __device__ double operator[](int i) const { return t >= 0 ? (i == t ? 1.0 : 0.0) : d[i]; }
+};
+
+__host__ __device__ inline double dwz2(const CmpcConsts& K, int k) { return sqrt(2.0 * (double)K.wz2[k]) * (1.0 + exp(-(double)k)); }
+
+// R(r, cc) of foot c at stage k at 3 r + cc (as build_geo)
+__host__ __device__ inline void stage_R(const Prob& P, int c, int k, double* R)
+{
+    const float* Rp = P.p + P.L.pR(c) + 9 * k;
+    for (int r = 0; r < 3; ++r)
+        for (int cc = 0; cc < 3; ++cc) R[3 * r + cc] = Rp[3 * cc + r];
+}
+
+// q entry e (state, 39) of the model right-hand side at knot k (k == N: terminal): the weights on com / h / pos, the force rate on the
+// previous-force part of the state (stages 1..N-1)
+__host__ __device__ inline double model_q(const Prob& P, int k, int e, const MDir& d)
+{
+    const CmpcConsts& K = *P.K;
+    const CmpcIdx& L = P.L;
+    if (e < 3) {
+        const double dw = e == 0 ? 2.0 * d[1] : e == 1 ? 2.0 * d[2] : dwz2(K, k) * d[3];
+        return dw * ((double)P.x[L.oCom() + 3 * k + e] - (double)P.p[L.pComref() + 3 * k + e]);
+    }
+    if (e < 6) return 0.0;
+    if (e < 9) return 2.0 * d[4] * ((double)P.x[L.oH() + 3 * k + e - 6] - (double)P.p[L.pHref() + 3 * k + e - 6]);
+    if (e < 15) {
+        const int c = (e - 9) / 3, a = (e - 9) % 3;
+        return 2.0 * d[5] * ((double)P.x[L.oPos(c) + 3 * k + a] - (double)P.p[L.pNom(c) + 3 * k + a]);
+    }
+    if (k < 1 || k >= L.N) return 0.0;
+    const int i = e - 15, c = i / 12, j = (i % 12) / 3, a = i % 3;
+    const float* f = P.x + L.oF(c, j) + 3 * k + a;
+    return -2.0 * d[6 + a] * ((double)f[0] - (double)f[-3]);
+}
+
+// r entry i (control, 30) of stage k < N: symmetry and force rate on the forces, friction through lam^T dg/dmu and the row's Sigma, the corners
+// through the angular-momentum rows' lam_h x (R e_b)
+__host__ __device__ inline double model_r(const Prob& P, int k, int i, const MDir& d)
+{
+    if (i >= 24) return 0.0;
+    const CmpcConsts& K = *P.K;
+    const CmpcIdx& L = P.L;
+    const int c = i / 12, j = (i % 12) / 3, a = i % 3;
+    const double gm = P.p[L.pGam(c) + k], dt = K.dt, mu = K.mu_fr;
+    double mean = 0.0;
+    for (int l = 0; l < 4; ++l) mean += 0.25 * (double)P.x[L.oF(c, l) + 3 * k + a];
+    const double fa = P.x[L.oF(c, j) + 3 * k + a];
+    const double es = fa - gm * mean, esum = 4.0 * mean * (1.0 - gm);
+    double v = 2.0 * d[9] * (es - 0.25 * gm * esum);
+    if (k >= 1) v += 2.0 * d[6 + a] * (fa - (double)P.x[L.oF(c, j) + 3 * (k - 1) + a]);
+    double R[9], f[3];
+    stage_R(P, c, k, R);
+    for (int m = 0; m < 3; ++m) f[m] = P.x[L.oF(c, j) + 3 * k + m];
+    const double fl2 = R[2] * f[0] + R[5] * f[1] + R[8] * f[2];   // (R^T f)_z
+    double fr = 0.0;
+    for (int face = 0; face < 4; ++face) {
+        const double sx = (face == 0 || face == 3) ? 1.0 : -1.0, sy = (face < 2) ? 1.0 : -1.0;
+        double gv = 0.0;   // Sigma of the row, as build_geo
+        for (int r = 0; r < 3; ++r) gv += (R[3 * r] * sx + R[3 * r + 1] * sy - mu * R[3 * r + 2]) * f[r];
+        const double l = P.lam[P.gfric[c] + 16 * k + 4 * j + face];
+        const double sg = fmax(l, 0.0) / fmax(-gv, SENS_SMIN);
+        const double aa = R[3 * a] * sx + R[3 * a + 1] * sy - mu * R[3 * a + 2];
+        fr += -l * R[3 * a + 2] - sg * aa * fl2;
+    }
+    v += d[0] * fr;
+    double lh[3];
+    for (int m = 0; m < 3; ++m) lh[m] = P.lam[P.gh + 3 * k + m];
+    const int a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+    for (int b = 0; b < 3; ++b)   // -dt gam (lam_h x R e_b)_a
+        v += d[10 + 12 * c + 3 * j + b] * (-dt * gm * (lh[a1] * R[3 * a2 + b] - lh[a2] * R[3 * a1 + b]));
+    return v;
+}
+
+// c entry e (39) of stage k < N: the corners in the angular-momentum dynamics, dt gam ((R e_b) x f)
+__host__ __device__ inline double model_c(const Prob& P, int k, int e, const MDir& d)
+{
+    if (e < 6 || e >= 9) return 0.0;
+    const CmpcConsts& K = *P.K;
+    const CmpcIdx& L = P.L;
+    const int a = e - 6, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+    const double dt = K.dt;
+    double v = 0.0;
+    for (int c = 0; c < 2; ++c) {
+        double R[9];
+        stage_R(P, c, k, R);
+        const double gm = P.p[L.pGam(c) + k];
+        for (int j = 0; j < 4; ++j) {
+            const float* f = P.x + L.oF(c, j) + 3 * k;
+            for (int b = 0; b < 3; ++b)
+                v += d[10 + 12 * c + 3 * j + b] * (dt * gm * (R[3 * a1 + b] * (double)f[a2] - R[3 * a2 + b] * (double)f[a1]));
+        }
+    }
+    return v;
+}
+
+// one knot's share of the model right-hand side's primal block r_x in the NLP's x layout (the force column of stage k gathers the stage form's
+// r_k entry and the force-rate share on x~_{k+1}'s previous forces): sum over the column of n r_x (n: the internal-force direction, e3 scaled as
+// internal_dir; null: none) and of r_x^2
+__host__ __device__ inline void model_rx_knot(const Prob& P, int k, const MDir& d, const double* e3, double& nr, double& rr)
+{
+    const int N = P.L.N;
+    double s = 0.0, q = 0.0;
+    for (int e = 0; e < 15; ++e) { const double v = model_q(P, k, e, d); q += v * v; }
+    if (k < N)
+        for (int i = 0; i < 24; ++i) {
+            const double v = model_r(P, k, i, d) + (k + 1 < N ? model_q(P, k + 1, 15 + i, d) : 0.0);
+            q += v * v;
+            if (e3) s += (i < 12 ? e3[i % 3] : -e3[i % 3]) * v;
+        }
+    nr = s; rr = q;
+}
+
+// a JVP direction's row of dp, or zeros (dDirP == NULL)
+struct PDir {
+    const float* d;
+    __host__ __device__ float operator[](int i) const { return d ? d[i] : 0.f; }
+};
+
 // One column's right-hand side at stage k (k == N: q only) -- the caller's definition
 struct Rhs {
     int mode;          // 0: JVP direction dp; 1: VJP gradient v (already projected)
     const float* dir;  // mode 0: [KC][np] rows of this chunk (stride np); mode 1: [nx]
     long long stride;
+    const double* dmod;   // mode 0: [KC][34] model directions of this chunk, or null
+    const double* proj;   // with dmod: e3 (3, as internal_dir) then the KC components n^T r_x removed from the columns' force entries; null: none
 };
 
 // (q_k, r_k, c_k) of column j, written to q[39], r[30], c[39]; k == N: q only.  x0 (k == 0 only, if non-null): the initial state
@@ -322,7 +451,7 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
     const CmpcIdx& L = P.L;
     const int N = L.N;
     if (R.mode == 0) {
-        const float* d = R.dir + j * R.stride;
+        const PDir d{R.dir ? R.dir + j * R.stride : nullptr};
         if (e < SX) {   // q and c entry e
             double qv = 0.0;
             if (e < 3) qv = -g.hcom[e] * d[L.pComref() + 3 * k + e];
@@ -348,14 +477,20 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
                                 cv += g.Ri[cc][3 * a + i] * 0.5 * ((double)d[L.pLo(cc) + 3 * k + i] + (double)d[L.pUp(cc) + 3 * k + i]);
                     }
                 }
+                if (R.dmod) cv += model_c(P, k, e, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
                 c[e] = cv;
             }
+            if (R.dmod) q[e] = qv + model_q(P, k, e, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
         } else if (k < N) {   // r entry e - SX
             const int i = e - SX;
             double rv = 0.0;
             if (i >= 24) {
                 const int cc = (i - 24) / 3, a = (i - 24) % 3;
                 if (g.qm[cc][a] == 1) rv = -(g.sU[cc][a] * d[L.pUp(cc) + 3 * k + a] + g.sL[cc][a] * d[L.pLo(cc) + 3 * k + a]);
+            }
+            if (R.dmod) {
+                rv += model_r(P, k, i, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
+                if (R.proj && i < 24) rv -= R.proj[3 + j] * (i < 12 ? R.proj[i % 3] : -R.proj[i % 3]);   // (no component along n)
             }
             r[i] = rv;
         }
@@ -766,14 +901,83 @@ __host__ __device__ inline bool sens_outside_subset(const Prob& P, int ct, int k
     return diff;
 }
 
-// ---- one problem: JVP (gx == null: k directions dir[k][np] -> out[k][nx]) or VJP (gx[nx] -> out[np]) ----
+// the model part of one problem's VJP after its adjoint solve (W column 0): gmod[t] = -w^T r_t for the 34 fields, each a sum over the knots in a
+// fixed order.  With the internal-force direction e3 (else null), r_t loses its component along n as the JVP's columns do: -w^T r_t + (n^T w)(n^T r_t)
+// (w itself can carry a component along n: v is projected in float32 and the shifted system amplifies what is left by 1 / CMPC_SENS_SHIFT), and the
+// largest relative component |n^T r_t| / |r_t| goes to rel.  Items (t, k) spread over the team, partial sums in the free dense area of LDS (part:
+// 3 x 34 (N+1) doubles).
+__host__ __device__ inline void model_vjp(const Team& T, const Prob& P, const Ws& W, const double* e3, double* part, double* gmod, double& rel,
+                                          double& nonfinite)
+{
+    const int N = P.L.N, nk = N + 1, M = CMPC_MODEL_DOUBLES;
+    const double* xs = W.xs(0);
+    const double* ls = W.ls(0);
+    const double* us = W.us(0);
+    for (int e = T.tid; e < M * nk; e += T.nt) {
+        const int t = e / nk, k = e % nk;
+        const MDir d{nullptr, t};
+        double v = 0.0;
+        for (int i = 0; i < SX; ++i) v += xs[k * SX + i] * model_q(P, k, i, d);
+        if (k < N) {
+            for (int i = 0; i < 24; ++i) v += us[k * SU + i] * model_r(P, k, i, d);
+            for (int i = 6; i < 9; ++i) v += ls[(k + 1) * SX + i] * model_c(P, k, i, d);
+        }
+        part[e] = v;
+        double nr = 0.0, rr = 0.0;
+        if (e3) model_rx_knot(P, k, d, e3, nr, rr);
+        part[M * nk + e] = nr;
+        part[2 * M * nk + e] = rr;
+    }
+    SENS_SYNC();
+    double r = 0.0;
+    for (int t = T.tid; t < M; t += T.nt) {
+        double v = 0.0, nr = 0.0, rr = 0.0;
+        for (int k = 0; k <= N; ++k) { v += part[t * nk + k]; nr += part[M * nk + t * nk + k]; rr += part[2 * M * nk + t * nk + k]; }
+        if (e3) {   // n^T w over the force entries u_k (one thread's loop, the same order in every thread)
+            double nw = 0.0;
+            for (int k = 0; k < N; ++k)
+                for (int i = 0; i < 24; ++i) nw += (i < 12 ? e3[i % 3] : -e3[i % 3]) * us[k * SU + i];
+            v -= nw * nr;
+        }
+        gmod[t] = -v;
+        if (!__builtin_isfinite(v)) nonfinite = 1.0;
+        if (rr > 0.0) r = fmax(r, fabs(nr) / sqrt(rr));
+    }
+    rel = team_max(T, r);
+}
+
+// the JVP's model columns of one chunk before its passes: proj[3 + j] = n^T r_x of column j's model direction (n: e3, removed from the column's
+// force entries by rhs_entry), and the largest relative size |n^T r_x| / |r_x| over the chunk into rel.  part: 2 x KC (N+1) doubles of free LDS.
+__host__ __device__ inline void model_jvp_proj(const Team& T, const Prob& P, const double* dmod, int nc, double* proj, double* part, double& rel)
+{
+    const int N = P.L.N, nk = N + 1;
+    for (int e = T.tid; e < nc * nk; e += T.nt) {
+        const int j = e / nk, k = e % nk;
+        double nr, rr;
+        model_rx_knot(P, k, MDir{dmod + j * CMPC_MODEL_DOUBLES, -1}, proj, nr, rr);
+        part[e] = nr;
+        part[SENS_KC * nk + e] = rr;
+    }
+    SENS_SYNC();
+    double r = 0.0;
+    for (int j = T.tid; j < nc; j += T.nt) {
+        double nr = 0.0, rr = 0.0;
+        for (int k = 0; k <= N; ++k) { nr += part[j * nk + k]; rr += part[SENS_KC * nk + j * nk + k]; }
+        proj[3 + j] = nr;
+        if (rr > 0.0) r = fmax(r, fabs(nr) / sqrt(rr));
+    }
+    rel = fmax(rel, team_max(T, r));   // (team_max synchronises: proj is complete for every thread)
+}
+
+// ---- one problem: JVP (gx == null: k directions dir[k][np] (and dmod[k][34], or null) -> out[k][nx]) or VJP (gx[nx] -> out[np] (or null) and
+// gmod[34] (or null)) ----
 __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, const Prob& P, const Ws& W, const Lds& S, const float* dir, const float* gx, int kdir,
-                                            float* out, float* sens, float* vproj)
+                                            float* out, float* sens, float* vproj, const double* dmod, double* gmod, double* proj)
 {
     const CmpcIdx& L = P.L;
     const int N = L.N;
     const bool vjp = gx != nullptr;
-    const int nout = vjp ? L.np() : kdir * L.nx();
+    const int nout = vjp ? (out ? L.np() : 0) : kdir * L.nx();
     // status 3: outside the supported subset, or a model that broke the model rule; status 2: input not finite
     double flag3 = 0.0, flag2 = 0.0;
     for (int e = T.tid; e < 2 * N; e += T.nt) if (sens_outside_subset(P, e / N, e % N)) flag3 = 1.0;
@@ -782,7 +986,8 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     for (int e = T.tid; e < L.np(); e += T.nt) if (!__builtin_isfinite(P.p[e])) flag2 = 1.0;
     for (int e = T.tid; e < L.ng(); e += T.nt) if (!__builtin_isfinite(P.lam[e])) flag2 = 1.0;
     if (vjp) { for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(gx[e])) flag2 = 1.0; }
-    else { for (long long e = T.tid; e < (long long)kdir * L.np(); e += T.nt) if (!__builtin_isfinite(dir[e])) flag2 = 1.0; }
+    else if (dir) { for (long long e = T.tid; e < (long long)kdir * L.np(); e += T.nt) if (!__builtin_isfinite(dir[e])) flag2 = 1.0; }
+    if (dmod) for (int e = T.tid; e < kdir * CMPC_MODEL_DOUBLES; e += T.nt) if (!__builtin_isfinite(dmod[e])) flag2 = 1.0;
     flag3 = team_max(T, flag3);
     flag2 = team_max(T, flag2);
     double status = flag3 > 0.0 ? 3.0 : (flag2 > 0.0 ? 2.0 : 0.0);
@@ -793,9 +998,10 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     }
     double e3[3];
     const bool has_e = internal_dir(P, e3);
-    double nonfinite = 0.0;
+    double nonfinite = 0.0, mrel = 0.0;
     if (status == 0.0) {
         Rhs R;
+        R.dmod = nullptr; R.proj = nullptr;
         int nchunks = 1;
         if (vjp) {   // v with no component along the internal-force direction
             double s = 0.0;
@@ -812,10 +1018,19 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
         } else {
             R.mode = 0; R.stride = L.np();
             nchunks = (kdir + SENS_KC - 1) / SENS_KC;
+            if (dmod && has_e) {   // the model columns lose their component along n: e3 first, then one n^T r_x per column
+                if (T.tid == 0) for (int i = 0; i < 3; ++i) proj[i] = e3[i];
+                SENS_SYNC();
+                R.proj = proj;
+            }
         }
         for (int ch = 0; ch < nchunks; ++ch) {
             const int nc = vjp ? 1 : (kdir - ch * SENS_KC < SENS_KC ? kdir - ch * SENS_KC : SENS_KC);
-            if (!vjp) R.dir = dir + (size_t)ch * SENS_KC * L.np();
+            if (!vjp) {
+                R.dir = dir ? dir + (size_t)ch * SENS_KC * L.np() : nullptr;
+                R.dmod = dmod ? dmod + (size_t)ch * SENS_KC * CMPC_MODEL_DOUBLES : nullptr;
+                if (R.proj) model_jvp_proj(T, P, R.dmod, nc, proj, S.P, mrel);
+            }
             double rn = 0.0, bn = 0.0;
             chunk_pass(T, P, W, S, R, nc, 0, rn, bn);
             for (int it = 0; it < SENS_NREF; ++it) chunk_pass(T, P, W, S, R, nc, 1, rn, bn);
@@ -917,9 +1132,10 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
                         }
                     }
                     if (!__builtin_isfinite(v)) nonfinite = 1.0;
-                    out[e] = (float)v;
+                    if (out) out[e] = (float)v;
                 }
                 SENS_SYNC();
+                if (gmod) model_vjp(T, P, W, has_e ? e3 : nullptr, S.P, gmod, mrel, nonfinite);
             }
         }
         if (!__builtin_isfinite(resid)) nonfinite = 1.0;
@@ -928,17 +1144,20 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     }
     if (status != 0.0) {
         for (long long e = T.tid; e < nout; e += T.nt) out[e] = 0.f;
+        if (gmod) for (int e = T.tid; e < CMPC_MODEL_DOUBLES; e += T.nt) gmod[e] = 0.0;
         resid = 0.0;
+        mrel = 0.0;
     }
     if (T.tid == 0 && sens) {
         sens[0] = (float)status; sens[1] = (float)resid; sens[2] = (float)weak; sens[3] = (float)sigmax;
         sens[4] = has_e ? 1.f : 0.f;
         sens[5] = (float)weak_swing;
-        for (int i = 6; i < CMPC_SENS; ++i) sens[i] = 0.f;
+        sens[6] = (float)mrel;
+        for (int i = 7; i < CMPC_SENS; ++i) sens[i] = 0.f;
     }
 }
 
-// LDS of the kernel: constants | x | p | lam (floats) | v projected (floats) | Geo | dense doubles | 4 reduction doubles
+// LDS of the kernel: constants | x | p | lam (floats) | v projected (floats) | Geo | dense doubles | 4 reduction doubles | KC + 3 projection doubles
 __host__ __device__ inline size_t sens_lds_floats(int N)
 {
     const CmpcIdx L{N};
@@ -946,7 +1165,7 @@ __host__ __device__ inline size_t sens_lds_floats(int N)
 }
 inline size_t sens_lds_bytes(int N)
 {
-    return sens_lds_floats(N) * 4 + ((sizeof(Geo) + 15) & ~(size_t)15) + 8 * (size_t)(Lds::doubles() + 4);
+    return sens_lds_floats(N) * 4 + ((sizeof(Geo) + 15) & ~(size_t)15) + 8 * (size_t)(Lds::doubles() + 4 + SENS_KC + 3);
 }
 
 // carves the dense area: the factorisation's eight matrices; the column slots overlay PA, PB, Y (12 x 40 x 8 = 3840 doubles <= their 3861)
@@ -970,7 +1189,8 @@ __host__ __device__ inline Lds carve(double* base, Geo* g)
 __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts* __restrict__ kc, int kc_per_problem, int N, int b0,
                                                                const float* __restrict__ X, const float* __restrict__ Pp, const float* __restrict__ LamG,
                                                                const float* __restrict__ Dir, const float* __restrict__ GradX, int kdir,
-                                                               float* __restrict__ Out, float* __restrict__ Sens, double* __restrict__ Wsp)
+                                                               float* __restrict__ Out, float* __restrict__ Sens, double* __restrict__ Wsp,
+                                                               const double* __restrict__ DirModel, double* __restrict__ GradModel)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -989,6 +1209,7 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
     Geo* g = reinterpret_cast<Geo*>(smem + sens_lds_floats(N) * 4);
     double* dense = reinterpret_cast<double*>(reinterpret_cast<char*>(g) + ((sizeof(Geo) + 15) & ~(size_t)15));
     double* red = dense + Lds::doubles();
+    double* proj = red + 4;
     for (int e = tid; e < L.nx(); e += SENS_NT) x[e] = X[(size_t)b * L.nx() + e];
     for (int e = tid; e < L.np(); e += SENS_NT) p[e] = Pp[(size_t)b * L.np() + e];
     for (int e = tid; e < L.ng(); e += SENS_NT) lam[e] = LamG[(size_t)b * L.ng() + e];
@@ -1005,16 +1226,23 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
     W.col = W.Kg + (size_t)N * SU * SX;
     const Team T{tid, SENS_NT, red};
     const Lds S = carve(dense, g);
-    if (GradX) sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * L.nx(), 1, Out + (size_t)b * L.np(), Sens ? Sens + (size_t)b * CMPC_SENS : nullptr, vproj);
-    else sens_problem(T, P, W, S, Dir + (size_t)b * kdir * L.np(), nullptr, kdir, Out + (size_t)b * kdir * L.nx(), Sens ? Sens + (size_t)b * CMPC_SENS : nullptr, vproj);
+    float* sens = Sens ? Sens + (size_t)b * CMPC_SENS : nullptr;
+    if (GradX)
+        sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * L.nx(), 1, Out ? Out + (size_t)b * L.np() : nullptr, sens, vproj, nullptr,
+                     GradModel ? GradModel + (size_t)b * CMPC_MODEL_DOUBLES : nullptr, proj);
+    else
+        sens_problem(T, P, W, S, Dir ? Dir + (size_t)b * kdir * L.np() : nullptr, nullptr, kdir, Out + (size_t)b * kdir * L.nx(), sens, vproj,
+                     DirModel ? DirModel + (size_t)b * kdir * CMPC_MODEL_DOUBLES : nullptr, nullptr, proj);
 }
 
 // workspace bytes per problem of the launch below
 extern "C" size_t cmpc_sensitivity_workspace_bytes(int N) { return sizeof(double) * (size_t)Ws::doubles(N); }
 
-// problems [b0, b0 + nb) of the batch; the workspace holds nb problems
+// problems [b0, b0 + nb) of the batch; the workspace holds nb problems.  JVP (dGradX null): dDir and dDirModel (each may be null), dOut = dx.
+// VJP: dOut = dl/dp (or null), dGradModel = dl/dtheta (or null).
 extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
-                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, hipStream_t stream)
+                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
+                                       double* dGradModel, hipStream_t stream)
 {
     const size_t lds = sens_lds_bytes(N);
     static int configured = 0;
@@ -1024,6 +1252,6 @@ extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem,
         configured = 1;
     }
     hipLaunchKernelGGL(cmpc_sensitivity_kernel, dim3(nb), dim3(SENS_NT), lds, stream, kc, kc_per_problem, N, b0, dX, dP, dLamG, dDir, dGradX, kdir, dOut,
-                       dSens, dWs);
+                       dSens, dWs, dDirModel, dGradModel);
     return (int)hipGetLastError();
 }

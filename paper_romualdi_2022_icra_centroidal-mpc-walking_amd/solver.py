@@ -298,6 +298,69 @@ class BatchSolver:
         idx = torch.as_tensor(np.concatenate([np.arange(L.f[c][j], L.f[c][j] + 3) for c in range(2) for j in range(4)]), device=dX.device)
         return dDX[:, :, idx].transpose(1, 2).contiguous(), sens
 
+    # ---- derivatives with respect to the per-problem model (include/cmpc.h, "model directions") ----
+    def solution_jvp_model_device(self, dX, dP, dLamG, dDirP=None, dDirModel=None, out=None, sens=None):
+        """dx*/d(p, theta) applied to k directions: dDirP[B, k, n_p] float32 and dDirModel[B, k, 34] float64 in cmpc_model's order (either may be
+        None: zero) -> (dDX[B, k, n_x], sens[B, CMPC_SENS]).  sens[:, 6]: the relative component of the model right-hand sides along the
+        internal-force direction that was removed (largest over the k columns).  dDirModel None gives solution_jvp_device's result bit for bit."""
+        import torch
+        L = self.layout
+        assert dDirP is not None or dDirModel is not None, "solution_jvp_model_device: no direction"
+        if dDirP is not None:
+            assert dDirP.is_cuda and dDirP.dtype == torch.float32 and dDirP.is_contiguous() and dDirP.dim() == 3
+            assert tuple(dDirP.shape[::2]) == (self.batch, L.np) and dDirP.shape[1] >= 1
+        if dDirModel is not None:
+            assert dDirModel.is_cuda and dDirModel.dtype == torch.float64 and dDirModel.is_contiguous() and dDirModel.dim() == 3
+            assert tuple(dDirModel.shape[::2]) == (self.batch, _capi.MODEL_DOUBLES) and dDirModel.shape[1] >= 1
+            assert dDirP is None or dDirP.shape[1] == dDirModel.shape[1]
+        k = int((dDirP if dDirP is not None else dDirModel).shape[1])
+        if out is None:
+            out = torch.empty((self.batch, k, L.nx), dtype=torch.float32, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, k, L.nx) and out.dtype == torch.float32
+        pp = dDirP.data_ptr() if dDirP is not None else None
+        pm = dDirModel.data_ptr() if dDirModel is not None else None
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_jvp_model_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                           pp, pm, k, out.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_jvp_model_device")
+        return out, sens
+
+    def solution_vjp_model_device(self, dX, dP, dLamG, dGradX, out_model=None, out_p=None, sens=None, grad_p=True):
+        """(dx*/d(p, theta))^T v from one adjoint solve: dGradX[B, n_x] = dl/dx -> (dl/dtheta [B, 34] float64, dl/dp [B, n_p] float32 or None
+        when grad_p is False, sens[B, CMPC_SENS]).  dl/dp equals solution_vjp_device's bit for bit; sens[:, 6]: the largest relative component
+        along the internal-force direction over the 34 fields."""
+        import torch
+        L = self.layout
+        assert dGradX.is_cuda and dGradX.dtype == torch.float32 and dGradX.is_contiguous() and tuple(dGradX.shape) == (self.batch, L.nx)
+        if out_model is None:
+            out_model = torch.empty((self.batch, _capi.MODEL_DOUBLES), dtype=torch.float64, device=dX.device)
+        assert out_model.is_contiguous() and tuple(out_model.shape) == (self.batch, _capi.MODEL_DOUBLES) and out_model.dtype == torch.float64
+        if grad_p and out_p is None:
+            out_p = torch.empty((self.batch, L.np), dtype=torch.float32, device=dX.device)
+        if out_p is not None:
+            assert out_p.is_contiguous() and tuple(out_p.shape) == (self.batch, L.np) and out_p.dtype == torch.float32
+        pp = out_p.data_ptr() if out_p is not None else None
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_vjp_model_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                           dGradX.data_ptr(), pp, out_model.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_vjp_model_device")
+        return out_model, out_p, sens
+
+    def model_value_gradient_device(self, dX, dP, dLamG, out=None):
+        """dV*/dtheta [B, 34] float64 at a KKT point (x*, lam*): d_theta f + lam^T d_theta g, at each problem's own model (zeros for a row whose model
+        broke the model rule).  At a double-support point the corner entries depend on the internal force the solve returned (include/cmpc.h)."""
+        import torch
+        L = self.layout
+        assert tuple(dX.shape) == (self.batch, L.nx) and tuple(dP.shape) == (self.batch, L.np) and tuple(dLamG.shape) == (self.batch, L.ng)
+        for t in (dX, dP, dLamG):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        if out is None:
+            out = torch.empty((self.batch, _capi.MODEL_DOUBLES), dtype=torch.float64, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, _capi.MODEL_DOUBLES) and out.dtype == torch.float64
+        self._launch(dX.device, lambda st: self._lib.cmpc_model_value_gradient_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                      out.data_ptr(), st))
+        return out
+
     def workspace_bytes_per_problem(self) -> int:
         """bytes of the sensitivity workspace per problem (cmpc_sensitivity_workspace_bytes)"""
         return int(self._lib.cmpc_sensitivity_workspace_bytes(self.layout.N))
@@ -623,29 +686,40 @@ class CentroidalMPC:
         return X, info
 
 
-def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False):
+def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False, models=None):
     """x*(P) as a torch.autograd.Function: forward solves (solve_device) and keeps (X, P, lam_g); backward returns P.grad by the VJP of
     include/cmpc.h (cmpc_solution_vjp_device) and None for X0.  The multiplier output of `solver` is turned on if it is off (it stays on).
     Problems whose sensitivity status is not 0 get zero rows of P.grad; solver.last_sensitivity_info holds the [B, CMPC_SENS] words of the
-    last backward, and solver.last_info the [B, CMPC_INFO] words of the last forward."""
+    last backward, and solver.last_info the [B, CMPC_INFO] words of the last forward.
+    models: None, or a [B, 34] float64 CUDA tensor of per-problem models (cmpc_model's order): forward installs it with set_models_device and
+    leaves it installed on `solver` (solver.last_models_ok holds the [B] ok words), and backward returns models.grad from the same adjoint solve
+    (cmpc_solution_vjp_model_device: P.grad is bit for bit that of the models=None path at the same models)."""
     import torch
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, P, X0):
+        def forward(ctx, P, X0, models):
             solver.set_multiplier_output(True)
+            if models is not None:
+                solver.last_models_ok = solver.set_models_device(models.detach().contiguous())
             Pc, X0c = P.detach().contiguous(), X0.detach().contiguous()
             X, info = solver.solve_device(Pc, X0c, warm=warm)
             lam = solver.multipliers_device(X, Pc)
             solver.last_info = info
+            ctx.with_models = models is not None
             ctx.save_for_backward(X, Pc, lam)
             return X
 
         @staticmethod
         def backward(ctx, gX):
             X, Pc, lam = ctx.saved_tensors
-            gP, sens = solver.solution_vjp_device(X, Pc, lam, gX.contiguous().to(torch.float32))
+            gX = gX.contiguous().to(torch.float32)
+            if not ctx.with_models:
+                gP, sens = solver.solution_vjp_device(X, Pc, lam, gX)
+                solver.last_sensitivity_info = sens
+                return gP, None, None
+            gM, gP, sens = solver.solution_vjp_model_device(X, Pc, lam, gX)
             solver.last_sensitivity_info = sens
-            return gP, None
+            return gP, None, gM
 
-    return _Fn.apply(P, X0)
+    return _Fn.apply(P, X0, models)
