@@ -385,6 +385,28 @@ int cmpc_write_reference_from_planner_device(cmpc_handle h, const float* dComIn,
 int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut,
                            float* dZmp, double step, int substeps, double zmp_half_x, double zmp_half_y, void* stream);
 
+/* ---- plant-step derivatives (derivation: DESIGN.md 7d) ----
+ * The map of cmpc_plant_step_device, (state, x, p, theta) -> state', differentiated at the float32 inputs in float64.  With the forces held the dynamics are
+ * affine and nilpotent, so the RK4 sweep equals the closed form over T = substeps * step (step rounded to float32, as the forward does):
+ *     com' = com + T dcom + T^2/2 a,  dcom' = dcom + T a,  h' = h + T tau0 - I x F,   I = T com + T^2/2 dcom + T^3/6 a,
+ *     a = F + fExt_0 - g e_z,  F = sum_q f_q,  tau0 = tauExt_0 + sum_q (pos_c,0 + R_c,0 corner_q) x f_q.
+ * Differentiated inputs: state [9]; from x the knot-0 foot positions pos_c,0 (6) and the knot-0 corner forces f_c,j,0 (24), gated by Gamma_c,0 exactly as
+ * the forward gates them (a foot with Gamma_c,0 <= 0.5 has zero force derivatives; its position derivative is then zero too, since no force acts there);
+ * from p the wrench of knot 0, fExt_0 and tauExt_0; from the model the 24 corner entries (theta indices 10..33), through R_c,0 corner.
+ * NOT differentiated: R and Gamma (as for the solution sensitivities), step, substeps, gravity, and the ZMP output (clipped; an output only).
+ * JVP and VJP apply one set of partials (T, F, I, the contact points and the gated forces), forwards and transposed term by term: adjoint by construction.
+ * One thread per problem; per-problem models (cmpc_set_models*) apply (a row that broke the model rule uses the config's corners, as the forward does);
+ * results depend on nothing but the problem's own inputs.  No status word: non-finite inputs give non-finite outputs.  Device pointers; asynchronous on
+ * `stream` (NULL: the handle's).
+ * JVP: dDirState[B][9] double, dDirX[B][n_x] float or NULL (zero; only the 30 entries above are read), dDirP[B][n_p] float or NULL (only fExt_0, tauExt_0),
+ * dDirModel[B][34] double or NULL (only the corners) -> dDirStateOut[B][9] double (may alias dDirState). */
+int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
+                               const float* dDirX, const float* dDirP, const double* dDirModel, double* dDirStateOut, void* stream);
+/* VJP: dGradStateOut[B][9] double -> dGradState[B][9] double (may alias dGradStateOut), dGradX[B][n_x] float (written whole: zero but for the 30 entries),
+ * dGradP[B][n_p] float or NULL (written whole: zero but for fExt_0, tauExt_0), dGradModel[B][34] double or NULL (written whole: entries 0..9 zero). */
+int cmpc_plant_step_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dGradStateOut,
+                               double* dGradState, float* dGradX, float* dGradP, double* dGradModel, void* stream);
+
 /* 8e, the record a Monte-Carlo driver gathers across GPUs (no reference counterpart: the reference runs one problem):
  * dOut[B][3(N+1) + 38] = CoM trajectory 3(N+1) | first-knot corner forces 24 | knot-0 and knot-1 foot positions 12 |
  * iterations | status, from dX[B][n_x] and dInfo[B][8].  Device pointers; asynchronous on `stream` (NULL: the handle's). */
@@ -509,6 +531,65 @@ typedef struct cmpc_tick_io {
     int force_sample_time;
 } cmpc_tick_io;
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream);
+/* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
+ * Adjoint of the list path of one tick in the contacts' POSITIONS; orientations and times are not differentiated.  The forward maps move positions
+ * through index maps that depend on the contact times only, so the adjoint needs the lists' times and counts, not their poses: the planner's lists, the
+ * previous tick's and this tick's merged list as cmpc_rollout_tick_device (or the seven calls) left them, and dLand / dOk of that tick.  The maps are
+ * re-derived with the forward's own functions (getActiveContact, getNextContact, the stage owner).  Gradients of list positions are double
+ * [B][2][max_contacts][3], laid out like the position part of pose.
+ *   adjust (phase bit 1; runs BEFORE the solution VJP, it adds to dGradX): where 0 <= land <= N and there is a next contact nx = getNextContact(now),
+ *     dGradX[pos_c + 3 land] += dGradListOut[c][nx], and nothing of dGradListOut[c][nx] flows on to the merged list (the pose was overwritten after the
+ *     sampling had read it; the sampling's own contribution to [c][nx] still does).  Every other entry passes through.
+ *   sample (phase bit 2; runs AFTER the solution VJP, it reads dGradP): list entry m receives the sum over the stages k it owns of dGradP[nominalPos_c,k+1],
+ *     and the owner of stage 0 also dGradP[nominalPos_c,0] + dGradP[currentPos_c] -- the "tied entries" sum of the solution sensitivities (subset rule 3).
+ *   merge (phase bit 2): merged entry 0, when the previous list has an active contact ma, sends its gradient to dGradPrevList[c][ma]; the entries copied from
+ *     the planner send theirs to dGradPlan[c][m] (optional, +=).  Entries at or beyond the list's length are not part of it and carry none.  First tick (dPrevT ==
+ *     dPrevN == NULL: no merge): dGradPrevList is the list's gradient itself.
+ * dGradPrevList is written whole.  Order of the float64 sums (one thread per problem and foot owns its entries, no atomics): the entry's own dGradListOut
+ * first, then the sampling's terms stage by stage, k = 0 .. N-1, within stage 0 nominalPos_0, currentPos, nominalPos_1.
+ * force_sample_time != 0: the planner's times are snapped first (the rule at cmpc_contacts_force_sample_time, grid = the handle's sampling_time), exactly
+ * as the forward tick does, so that the index maps are those the forward saw (the first tick's list was snapped in place by the forward).
+ * dOk[b] == 0 (a failed merge or snap; NULL: every problem is good): zero dGradPrevList, nothing added to dGradX or dGradPlan, dStatus[b] = 5; else
+ * dStatus[b] = 0 (dStatus [B] or NULL; written by the phase-2 part).  A foot that was not sampled (dLand = -2) passes nothing on.
+ * phase = 1, 2, or 3 (both parts in one launch: right when dGradP does not depend on dGradX).  dGradListOut NULL = zero; dGradP NULL = zero. */
+int cmpc_contacts_position_vjp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, const double* dPlanT, const int* dPlanN,
+                                      const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
+                                      const double* dGradListOut, const float* dGradP, float* dGradX, double* dGradPrevList, double* dGradPlan, int* dStatus,
+                                      void* stream);
+
+/* One tick in reverse.  What a forward tick left behind is a tape of read-only device pointers: the tick's solution, parameters and multipliers
+ * (cmpc_get_multipliers_device right after that tick's solve, with the multiplier output on -- x and info are bit-identical with it on, so a taped roll-out
+ * is bit-identical to an untaped one), the state that went IN (copy it before the tick: a roll-out may alias dState / dStateOut), dInfo, dOk, dLand, the
+ * times and counts of the planner's, the previous tick's (both NULL on the first tick) and the merged lists (copy the previous tick's before the tick if the
+ * roll-out alternates two list buffers), and the plant's step.  No new forward entry point is needed.
+ * Chain, on one stream: cmpc_plant_step_vjp_device -> the adjust part of cmpc_contacts_position_vjp_device -> cmpc_solution_vjp_model_device (called, not
+ * copied: its definition, its workspace and its dSens hold) -> gState += gP[com0, dcom0, h0] (cmpc_write_state_device in reverse) -> the sample + merge part.
+ * The solution map is taken as independent of x0: warm start, shift and cold restart carry no derivative.  The planner's reference rows are inputs of the
+ * tick, not functions of the state: their gradient arrives in dGradP for whoever wants it.
+ * Inputs: dGradStateOut[B][9] double, dGradListOut[B][2][max_contacts][3] double or NULL (zero), dGradX[B][n_x] float or NULL (a loss on this tick's solution).
+ * Outputs: dGradState[B][9] double (may alias dGradStateOut), dGradPrevList[B][2][max_contacts][3] double (must not alias dGradListOut), dGradWrench[B][N][6]
+ * float or NULL (the fExt / tauExt rows of gP, laid out as cmpc_write_state_device's dWrench), dGradPlan or NULL (+=), dGradModel[B][34] double or NULL (+=),
+ * dGradP[B][n_p] float or NULL (the tick's full dl/dp: the solve's, plus the plant's on fExt_0 / tauExt_0), dTickSens[B][CMPC_SENS] float: dSens of the
+ * solution VJP with word 0 replaced by the tick's status: 0 ok; 1..3 as the solution sensitivities; 4 the solve's status is not 0 (not converged, or flagged);
+ * 5 the merge failed (dOk == 0).  Precedence: 5, then 2 and 3 (they speak of the inputs), then 4, then 1.  A flagged problem gets zeros in every array (nothing is added to the += outputs); its
+ * neighbours are bit for bit what they are without it.  Workspace: per-handle HBM allocated on first use, 4 (n_x + 2 n_p) + 548 bytes per problem; calls on
+ * one handle run one after the other whatever their streams (an event, as for the solution sensitivities). */
+typedef struct cmpc_tick_tape {
+    const float* dX; const float* dP; const float* dLamG;   /* [B][n_x], [B][n_p], [B][n_g] of the tick's solve */
+    const float* dState;                                     /* [B][9] the state the tick started from */
+    const float* dInfo;                                      /* [B][CMPC_INFO] */
+    const int* dOk;                                          /* [B] merge status, or NULL (every problem good) */
+    const int* dLand;                                        /* [B][2] */
+    const double* dPlanT; const int* dPlanN;                 /* the planner's lists: times [B][2][M][2] and counts [B][2] (merge ticks) */
+    const double* dPrevT; const int* dPrevN;                 /* the previous tick's; both NULL on the first tick */
+    const double* dListT; const int* dListN;                 /* this tick's (merged) list */
+    double plant_step; int plant_substeps;                   /* as the forward tick's */
+    int force_sample_time;                                   /* as the forward tick's */
+} cmpc_tick_tape;
+int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                 const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                 double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, void* stream);
+
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */
 int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, void* stream);

@@ -49,6 +49,13 @@ class CmpcTickIO(C.Structure):
         ("robot_mass", C.c_double), ("com_height", C.c_double), ("force_sample_time", C.c_int)]
 
 
+class CmpcTickTape(C.Structure):
+    """mirror of cmpc_tick_tape (include/cmpc.h): what a forward tick left behind, read by cmpc_rollout_tick_vjp_device"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "dX", "dP", "dLamG", "dState", "dInfo", "dOk", "dLand", "dPlanT", "dPlanN", "dPrevT", "dPrevN", "dListT", "dListN")] + [
+        ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("force_sample_time", C.c_int)]
+
+
 class CmpcModel(C.Structure):
     """mirror of cmpc_model (include/cmpc.h): the per-problem part of cmpc_config, 34 packed doubles"""
     _fields_ = [
@@ -84,6 +91,7 @@ EXPORTS = [
     "cmpc_set_multiplier_output", "cmpc_get_multipliers_device", "cmpc_get_multipliers", "cmpc_kkt_certificate_device",
     "cmpc_value_gradient_device", "cmpc_solution_jvp_device", "cmpc_solution_vjp_device",
     "cmpc_sensitivity_workspace_bytes", "cmpc_solution_jvp_model_device", "cmpc_solution_vjp_model_device", "cmpc_model_value_gradient_device",
+    "cmpc_plant_step_jvp_device", "cmpc_plant_step_vjp_device", "cmpc_contacts_position_vjp_device", "cmpc_rollout_tick_vjp_device",
 ]
 
 _lib = None
@@ -166,6 +174,10 @@ def lib():
             L.cmpc_solution_jvp_model_device.argtypes = [vp, fp, fp, fp, fp, vp, C.c_int, fp, fp, vp]
             L.cmpc_solution_vjp_model_device.argtypes = [vp, fp, fp, fp, fp, fp, vp, fp, vp]
             L.cmpc_model_value_gradient_device.argtypes = [vp, fp, fp, fp, vp, vp]
+        L.cmpc_plant_step_jvp_device.argtypes = [vp, fp, fp, fp, d, i, vp, fp, fp, vp, vp, vp]
+        L.cmpc_plant_step_vjp_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp]
+        L.cmpc_contacts_position_vjp_device.argtypes = [vp, i, d, i, i] + [vp] * 15
+        L.cmpc_rollout_tick_vjp_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 11
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

@@ -91,6 +91,85 @@ __global__ __launch_bounds__(128) void cmpc_contacts_adjust_kernel(int B, int N,
     for (int i = 0; i < 3; ++i) pose[7 * (o + nx) + i] = x[i];
 }
 
+// Adjoint of the list path of one tick in the contacts' POSITIONS (include/cmpc.h, cmpc_contacts_position_vjp_device): adjust (phase bit 1), sample + merge
+// (phase bit 2).  One thread per (problem, foot); it owns that foot's entries of every output, so the sums need no atomics and their order is fixed:
+// an entry of g_prev / g_plan receives first the list's own gradient g_out, then the sampling's terms stage by stage, k = 0 .. N-1 (stage 0: nominalPos_0,
+// currentPos, nominalPos_1).  The index maps are re-derived from the TIMES with the forward's functions: cmpc_next_contact (adjust, merge),
+// cmpc_stage_owner (sample), cmpc_active_contact (merge); snap_dt_ns > 0: the planner's times pass through cmpc_snap_contact first, as in the forward tick.
+// Entries m >= list_n are not part of the list and carry no gradient.
+__global__ __launch_bounds__(128) void cmpc_contacts_position_vjp_kernel(int B, int N, int M, double dt, double now, int phase, long long snap_dt_ns,
+                                                                         const double* __restrict__ plan_t, const int* __restrict__ plan_n,
+                                                                         const double* __restrict__ prev_t, const int* __restrict__ prev_n,
+                                                                         const double* __restrict__ list_t, const int* __restrict__ list_n,
+                                                                         const int* __restrict__ land, const int* __restrict__ ok,
+                                                                         const double* __restrict__ g_out, const float* __restrict__ g_p, float* __restrict__ g_x,
+                                                                         double* __restrict__ g_prev, double* __restrict__ g_plan, int* __restrict__ status)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;   // problem * 2 + foot
+    if (e >= 2 * B) return;
+    const int b = e >> 1, c = e & 1;
+    const CmpcIdx L{N};
+    const size_t o = (size_t)e * M;
+    const bool merge = prev_t != nullptr;
+    const bool good = !ok || ok[b] != 0;
+    if ((phase & 2) && status && c == 0) status[b] = good ? 0 : 5;
+    if (phase & 2)
+        for (int m = 0; m < 3 * M; ++m) g_prev[3 * o + m] = 0.0;
+    if (!good) return;                                     // (a failed merge: the tick was discarded -- zero outputs, g_x and g_plan untouched)
+    const int n = list_n[e];
+    const bool sampled = n >= 1 && n <= M;
+    // adjust: the entry the step adjustment overwrote, or -1
+    int nx = -1;
+    const int lk = land ? land[e] : -1;
+    if (sampled && lk >= 0 && lk <= N) nx = cmpc_next_contact(list_t + 2 * o, n, now);
+    if ((phase & 1) && nx >= 0 && g_out)
+        for (int i = 0; i < 3; ++i) {
+            float* gx = g_x + (size_t)b * L.nx() + L.oPos(c) + 3 * lk + i;
+            *gx = (float)((double)*gx + g_out[3 * (o + nx) + i]);
+        }
+    if (!(phase & 2)) return;
+    // merge: where entry m of this tick's list came from
+    int ma = -1, first = -1;
+    if (merge) {
+        const int mn = prev_n[e], pn = plan_n[e];
+        if (mn >= 0 && mn <= M) ma = cmpc_active_contact(prev_t + 2 * o, mn, now);
+        if (pn >= 0 && pn <= M) {
+            if (snap_dt_ns > 0) {
+                for (int m = 0; m < pn && first < 0; ++m) {
+                    double s[2];
+                    cmpc_snap_contact(plan_t + 2 * (o + m), snap_dt_ns, s);
+                    if (cmpc_next_contact(s, 1, now) == 0) first = m;
+                }
+            } else first = cmpc_next_contact(plan_t + 2 * o, pn, now);
+        }
+    }
+    const int n0 = ma >= 0 ? 1 : 0;
+    auto dest = [&](int m) -> double* {                    // (null: the entry's gradient goes nowhere)
+        if (!merge) return g_prev + 3 * (o + m);
+        if (m < n0) return g_prev + 3 * (o + ma);
+        if (first < 0 || !g_plan || first + m - n0 >= M) return nullptr;
+        return g_plan + 3 * (o + first + m - n0);
+    };
+    const int nlist = n < 0 ? 0 : n > M ? M : n;
+    if (g_out)
+        for (int m = 0; m < nlist; ++m) {
+            double* d = dest(m);
+            if (!d || m == nx) continue;
+            for (int i = 0; i < 3; ++i) d[i] += g_out[3 * (o + m) + i];
+        }
+    if (!sampled || !g_p) return;
+    const float* gp = g_p + (size_t)b * L.np();
+    for (int k = 0; k < N; ++k) {
+        bool act;
+        double* d = dest(cmpc_stage_owner(list_t + 2 * o, n, now + k * dt, &act));
+        if (!d) continue;
+        for (int i = 0; i < 3; ++i) {
+            if (k == 0) d[i] += (double)gp[L.pNom(c) + i] + (double)gp[L.pCur(c) + i];
+            d[i] += (double)gp[L.pNom(c) + 3 * (k + 1) + i];
+        }
+    }
+}
+
 // measured state (and external wrench) into the parameter rows of every problem: setState on the device
 __global__ __launch_bounds__(128) void cmpc_write_state_kernel(int B, int N, const float* __restrict__ state, const float* __restrict__ wrench,
                                                                float* __restrict__ P)
@@ -165,5 +244,15 @@ extern "C" int cmpc_launch_contacts_adjust(int B, int N, int M, double now, cons
 extern "C" int cmpc_launch_write_state(int B, int N, const float* state, const float* wrench, float* P, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_write_state_kernel, dim3(B), dim3(128), 0, stream, B, N, state, wrench, P);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
+                                                 const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n,
+                                                 const int* land, const int* ok, const double* g_out, const float* g_p, float* g_x, double* g_prev,
+                                                 double* g_plan, int* status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_contacts_position_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, phase, snap_dt_ns, plan_t, plan_n,
+                       prev_t, prev_n, list_t, list_n, land, ok, g_out, g_p, g_x, g_prev, g_plan, status);
     return (int)hipGetLastError();
 }

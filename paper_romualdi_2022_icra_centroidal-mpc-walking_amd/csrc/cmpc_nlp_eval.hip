@@ -1149,6 +1149,164 @@ __global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, floa
     plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
 }
 
+// ---- derivatives of the plant step (include/cmpc.h, "plant-step derivatives") ----
+// With the forces held the dynamics above are affine and nilpotent (dcom' = a constant, h' = tau0 - com x F), so the Runge-Kutta sweep is exact and equals
+// the closed form over T = nsub h:
+//     com' = com + T v + T^2/2 a,   v' = v + T a,   h' = h + T tau0 - I x F,     I = T com + T^2/2 v + T^3/6 a,
+//     a = F + fExt_0 - g e_z,   F = sum_q f_q,   tau0 = tauExt_0 + sum_q cp_q x f_q,   cp_q = pos_c,0 + R_c,0 cn_q      (f_q = 0 where Gamma_c,0 is off).
+// The map is bilinear in (state, pos, corners, wrench) x forces; its partials are the point values below, read ONCE by plant_partials and applied forwards by
+// plant_jvp_problem and transposed, term by term in the same order, by plant_vjp_problem -- adjoint by construction.
+struct PlantPartials {
+    double T, F[3], I[3];      // horizon of the step, total force, time integral of the CoM
+    double cp[8][3], cf[8][3]; // contact points and (gated) corner forces
+    bool on[2];
+};
+
+__device__ inline void plant_partials(int N, int b, float grav, const float* __restrict__ corners, int corners_stride, const float* __restrict__ X,
+                                      const float* __restrict__ P, const float* __restrict__ state_in, float h, int nsub, PlantPartials& q)
+{
+    const CmpcIdx L{N};
+    const float* x = X + (size_t)b * L.nx();
+    const float* p = P + (size_t)b * L.np();
+    q.T = (double)nsub * (double)h;
+    for (int i = 0; i < 3; ++i) q.F[i] = 0;
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c);
+        q.on[c] = p[L.pGam(c)] > 0.5f;
+        for (int j = 0; j < 4; ++j) {
+            const float* cn = corners + (size_t)b * corners_stride + 12 * c + 3 * j;
+            for (int i = 0; i < 3; ++i) {
+                q.cp[4 * c + j][i] = (double)x[L.oPos(c) + i] + (double)R[i] * cn[0] + (double)R[3 + i] * cn[1] + (double)R[6 + i] * cn[2];
+                const float fv = x[L.oF(c, j) + i];
+                q.cf[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
+                q.F[i] += q.cf[4 * c + j][i];
+            }
+        }
+    }
+    const double T = q.T;
+    for (int i = 0; i < 3; ++i) {
+        const double a = q.F[i] + (double)p[L.pFext() + i] - (i == 2 ? (double)grav : 0.0);
+        q.I[i] = T * (double)state_in[(size_t)b * 9 + i] + 0.5 * T * T * (double)state_in[(size_t)b * 9 + 3 + i] + T * T * T / 6.0 * a;
+    }
+}
+
+__device__ inline void cross3(const double* a, const double* b, double* o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// forwards: (ds, dx, dp, dtheta) -> ds'.  Null direction groups are zero.
+__device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* __restrict__ dir_state,
+                                         const float* __restrict__ dir_x, const float* __restrict__ dir_p, const double* __restrict__ dir_model,
+                                         double* __restrict__ out)
+{
+    const CmpcIdx L{N};
+    const float* p = P + (size_t)b * L.np();
+    const double T = q.T;
+    double dc[3], dv[3], dh[3], dF[3] = {0, 0, 0}, dtau[3], da[3], dI[3], t[3];
+    for (int i = 0; i < 3; ++i) {
+        dc[i] = dir_state[(size_t)b * 9 + i]; dv[i] = dir_state[(size_t)b * 9 + 3 + i]; dh[i] = dir_state[(size_t)b * 9 + 6 + i];
+        dtau[i] = dir_p ? (double)dir_p[(size_t)b * L.np() + L.pText() + i] : 0.0;
+    }
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c);
+        for (int j = 0; j < 4; ++j) {
+            double dcp[3], df[3];
+            for (int i = 0; i < 3; ++i) {
+                dcp[i] = dir_x ? (double)dir_x[(size_t)b * L.nx() + L.oPos(c) + i] : 0.0;
+                if (dir_model) {
+                    const double* dn = dir_model + (size_t)b * CMPC_MODEL_DOUBLES + 10 + 12 * c + 3 * j;
+                    dcp[i] += (double)R[i] * dn[0] + (double)R[3 + i] * dn[1] + (double)R[6 + i] * dn[2];
+                }
+                df[i] = (dir_x && q.on[c]) ? (double)dir_x[(size_t)b * L.nx() + L.oF(c, j) + i] : 0.0;
+                dF[i] += df[i];
+            }
+            cross3(dcp, q.cf[4 * c + j], t);
+            for (int i = 0; i < 3; ++i) dtau[i] += t[i];
+            cross3(q.cp[4 * c + j], df, t);
+            for (int i = 0; i < 3; ++i) dtau[i] += t[i];
+        }
+    }
+    for (int i = 0; i < 3; ++i) {
+        da[i] = dF[i] + (dir_p ? (double)dir_p[(size_t)b * L.np() + L.pFext() + i] : 0.0);
+        dI[i] = T * dc[i] + 0.5 * T * T * dv[i] + T * T * T / 6.0 * da[i];
+    }
+    double u[3], w[3];
+    cross3(dI, q.F, u);
+    cross3(q.I, dF, w);
+    for (int i = 0; i < 3; ++i) {
+        out[(size_t)b * 9 + i] = dc[i] + T * dv[i] + 0.5 * T * T * da[i];
+        out[(size_t)b * 9 + 3 + i] = dv[i] + T * da[i];
+        out[(size_t)b * 9 + 6 + i] = dh[i] + T * dtau[i] - u[i] - w[i];
+    }
+}
+
+// transposed: gs' -> (gs, gx (the 30 entries it owns), gp (fExt_0, tauExt_0), gtheta (corners)).  grad_state may alias grad_out; null outputs are skipped.
+__device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* grad_out, double* grad_state,
+                                         float* __restrict__ grad_x, float* __restrict__ grad_p, double* __restrict__ grad_model)
+{
+    const CmpcIdx L{N};
+    const float* p = P + (size_t)b * L.np();
+    const double T = q.T;
+    double gc[3], gv[3], gh[3], gI[3], gF[3], ga[3];
+    for (int i = 0; i < 3; ++i) { gc[i] = grad_out[(size_t)b * 9 + i]; gv[i] = grad_out[(size_t)b * 9 + 3 + i]; gh[i] = grad_out[(size_t)b * 9 + 6 + i]; }
+    cross3(gh, q.F, gI);     // -<gh, dI x F> = <dI, gh x F>
+    cross3(q.I, gh, gF);     // -<gh, I x dF> = <dF, I x gh>
+    for (int i = 0; i < 3; ++i) {
+        ga[i] = 0.5 * T * T * gc[i] + T * gv[i] + T * T * T / 6.0 * gI[i];
+        gF[i] += ga[i];
+        grad_state[(size_t)b * 9 + i] = gc[i] + T * gI[i];
+        grad_state[(size_t)b * 9 + 3 + i] = T * gc[i] + gv[i] + 0.5 * T * T * gI[i];
+        grad_state[(size_t)b * 9 + 6 + i] = gh[i];
+        if (grad_p) { grad_p[(size_t)b * L.np() + L.pFext() + i] = (float)ga[i]; grad_p[(size_t)b * L.np() + L.pText() + i] = (float)(T * gh[i]); }
+    }
+    double gtau[3] = {T * gh[0], T * gh[1], T * gh[2]};
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c);
+        double gpos[3] = {0, 0, 0};
+        for (int j = 0; j < 4; ++j) {
+            double gcp[3], gf[3];
+            cross3(q.cf[4 * c + j], gtau, gcp);   // <gtau, dcp x f> = <dcp, f x gtau>
+            cross3(gtau, q.cp[4 * c + j], gf);    // <gtau, cp x df> = <df, gtau x cp>
+            for (int i = 0; i < 3; ++i) {
+                gpos[i] += gcp[i];
+                if (grad_x) grad_x[(size_t)b * L.nx() + L.oF(c, j) + i] = q.on[c] ? (float)(gf[i] + gF[i]) : 0.f;
+            }
+            if (grad_model)
+                for (int a = 0; a < 3; ++a)   // R^T gcp: column a of R (col-major) against gcp
+                    grad_model[(size_t)b * CMPC_MODEL_DOUBLES + 10 + 12 * c + 3 * j + a] = (double)R[3 * a] * gcp[0] + (double)R[3 * a + 1] * gcp[1] + (double)R[3 * a + 2] * gcp[2];
+        }
+        if (grad_x)
+            for (int i = 0; i < 3; ++i) grad_x[(size_t)b * L.nx() + L.oPos(c) + i] = (float)gpos[i];
+    }
+    if (grad_model)
+        for (int i = 0; i < 10; ++i) grad_model[(size_t)b * CMPC_MODEL_DOUBLES + i] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void cmpc_plant_jvp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
+                                                             const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
+                                                             float h, int nsub, const double* __restrict__ dir_state, const float* __restrict__ dir_x,
+                                                             const float* __restrict__ dir_p, const double* __restrict__ dir_model, double* __restrict__ out)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    PlantPartials q;
+    plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
+    plant_jvp_problem(N, b, P, q, dir_state, dir_x, dir_p, dir_model, out);
+}
+
+__global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
+                                                             const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
+                                                             float h, int nsub, const double* grad_out, double* grad_state, float* __restrict__ grad_x,
+                                                             float* __restrict__ grad_p, double* __restrict__ grad_model)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    PlantPartials q;
+    plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
+    plant_vjp_problem(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model);
+}
+
 // ---- the two ends of a roll-out tick as ONE launch each (cmpc_rollout_tick_device).  At B <= 256 a tick is a 0.66 ms solve between nine launches of a
 // few microseconds of work each, and the dispatch of a kernel behind another costs as much as they do (tools/gpu_rollout_tick_overhead.py): the steps in
 // front of the solve touch disjoint entries of P and X0 (contact blocks / state rows / the shifted solution) and so do the two behind it (the lists' poses /
@@ -1325,6 +1483,30 @@ extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCo
 {
     hipLaunchKernelGGL(cmpc_plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn,
                        dStateOut, dZmp, h, nsub, zx, zy);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
+                                     const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
+                                     const double* dDirModel, double* dOut, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_plant_jvp_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h, nsub,
+                       dDirState, dDirX, dDirP, dDirModel, dOut);
+    return (int)hipGetLastError();
+}
+
+// dGradX / dGradP: the whole rows are cleared first (the kernel writes the entries the plant reads, nothing else)
+extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
+                                     const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
+                                     double* dGradModel, hipStream_t stream)
+{
+    const CmpcIdx L{N};
+    hipError_t e = hipSuccess;
+    if (dGradX) e = hipMemsetAsync(dGradX, 0, sizeof(float) * (size_t)B * L.nx(), stream);
+    if (e == hipSuccess && dGradP) e = hipMemsetAsync(dGradP, 0, sizeof(float) * (size_t)B * L.np(), stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(cmpc_plant_vjp_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h, nsub,
+                       dGradOut, dGradState, dGradX, dGradP, dGradModel);
     return (int)hipGetLastError();
 }
 

@@ -169,13 +169,18 @@ class WalkingRollout:
         state, zmp = s.plant_step_device(dX, dP, state, step=dt / self.substeps, substeps=self.substeps)
         return ok, lists, land, nretry, state, zmp
 
-    def _run(self, ticks, com0, dcom0, h0, push=None, push_ticks=0, warm=True, dump=None, replan=None, slow=None, record="full", timing=True):
+    def _run(self, ticks, com0, dcom0, h0, push=None, push_ticks=0, warm=True, dump=None, replan=None, slow=None, record="full", timing=True, tape=False):
         """com0/dcom0/h0 [B,3] numpy; push [B,3] (mass-normalised force held for the first `push_ticks` ticks);
         replan {tick: (t, pose, n)}: the planner's lists from that tick on (the reference's generator re-plans while walking);
         slow (threshold, list): developer hook -- (tick, problem, P row, X0 row, info row) of every solve with more iterations;
         record "full": per-tick CoM, ZMP, landing offsets (host loops over the batch); "light": iteration statistics and the tick's
         wall-clock latency only (what bench.py times).  timing=False: without the library's event pair around every solve (cmpc_set_timing: an event record
         is a barrier packet on the stream, ~10 us of a tick each); rec["solve_ms"] is then NaN.
+        tape=True: rec["tape"] keeps what backward() needs, per tick, in device tensors: X, P, lam_g (the multiplier output is turned on: x and info
+        are bit-identical with it on, so a taped roll-out is bit-identical to an untaped one), the state that went in, info, ok, land and the times and
+        counts of the planner's, the previous tick's and the merged lists -- about 12 KB per problem and tick at N = 20 (x, p and lam_g are a thousand
+        floats each).  The state and the previous tick's list times are copied BEFORE the tick: the roll-out aliases dState / dStateOut and alternates two
+        list buffers.  rec["tape"]["state"] is the final state.  Not with retry="launch" (the stragglers' multipliers live on the retry handle).
         Returns a dict of per-tick numpy records."""
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt = cfg.sampling_time
@@ -201,6 +206,10 @@ class WalkingRollout:
                    tick_ms=[], retried=[], unconverged=[])
         mpc_prev, tick_bufs = None, None
         s.set_timing(timing)
+        if tape:
+            assert self.retry != "launch", "tape=True needs retry='kernel' or None"
+            s.set_multiplier_output(True)
+            rec["tape"] = dict(ticks=[], dt=dt, substeps=self.substeps, force_sample_time=self.force_sample_time, push_ticks=push_ticks if push is not None else 0)
         box_up = np.array([c.bounding_box_upper_limit for c in cfg.contacts])
         box_lo = np.array([c.bounding_box_lower_limit for c in cfg.contacts])
         for i in range(ticks):
@@ -209,6 +218,10 @@ class WalkingRollout:
             t_tick = time.perf_counter()
             if replan and i in replan:
                 self.plan = replan[i]
+            if tape:    # (before the tick: it overwrites the state in place, and the list buffer of two ticks ago)
+                tk = dict(now=now, state=state.clone(), plan_t=self.plan[0], plan_n=self.plan[2],
+                          prev_t=mpc_prev[0].clone() if mpc_prev is not None else None, prev_n=mpc_prev[2].clone() if mpc_prev is not None else None,
+                          push_knots=max(push_ticks - i, 1) if (dpush is not None and i < push_ticks) else 0)
             if self.native_tick and warm and mpc_prev is not None and not (dump is not None and i == dump[0]):
                 if tick_bufs is None:
                     tick_bufs = ([tuple(torch.zeros_like(a) for a in self.plan) for _ in range(2)], torch.empty((B, 2), dtype=torch.int32, device=dev),
@@ -229,6 +242,13 @@ class WalkingRollout:
             else:
                 ok, lists, land, nretry, state, zmp = self._tick_by_steps(i, now, mpc_prev, warm, dump, dP, dX0, dX, dInfo, state, wrench, dpush, push_ticks, planner(now))
                 mpc_prev = lists
+            if tape:
+                tk.update(X=dX.clone(), P=dP.clone(), lam_g=s.multipliers_device(dX, dP), info=dInfo.clone(), ok=ok.clone(), land=land.clone(),
+                          list_t=lists[0].clone(), list_n=lists[2].clone(), step=dt / self.substeps, substeps=self.substeps,
+                          force_sample_time=self.force_sample_time)
+                rec["tape"]["ticks"].append(tk)
+                rec["tape"]["state"] = state.clone()
+                rec["tape"]["lists"] = tuple(a.clone() for a in lists)
             torch.cuda.synchronize()
             tick_ms = (time.perf_counter() - t_tick) * 1e3
             if not bool(ok.cpu().numpy().all()):
@@ -274,3 +294,76 @@ class WalkingRollout:
         s.set_timing(True)
         rec["box_upper"], rec["box_lower"] = box_up, box_lo
         return rec
+
+    def backward(self, tape, grad_states, grad_X=None):
+        """The taped roll-out in reverse (cmpc_rollout_tick_vjp_device, one call per tick, last tick first).  tape = run(..., tape=True)["tape"];
+        grad_states[ticks + 1, B, 9] = dl / d state_i of the states BEFORE tick i (i = 0 .. ticks - 1) and of the final state (i = ticks), a CUDA tensor or
+        numpy; grad_X[ticks, B, n_x] float32 or None = dl / d x_i, a loss on the ticks' solutions.
+        -> dict(state0[B, 9], list0[B, 2, M, 3] (the positions of the first tick's lists), push[B, 3] (the sum of the wrench gradients over the ticks and
+        knots the push was written to), wrench[ticks, B, N, 6], models[B, 34], plan[B, 2, M, 3] (the planner's contact positions), status[ticks, B] int32:
+        0, or why that tick of that problem passed no gradient on -- include/cmpc.h), float64 but wrench (float32).  The solution map is taken as
+        independent of the warm start; contact times, orientations and the planner's CoM references are not differentiated."""
+        torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
+        ticks = tape["ticks"]
+        T = len(ticks)
+        as64 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, torch.float64).contiguous()
+        gS = as64(grad_states)
+        assert tuple(gS.shape) == (T + 1, B, 9)
+        gX = None
+        if grad_X is not None:
+            gX = (grad_X if isinstance(grad_X, torch.Tensor) else torch.from_numpy(np.asarray(grad_X))).to(self.dev, torch.float32).contiguous()
+            assert tuple(gX.shape) == (T, B, L.nx)
+        M = ticks[0]["list_t"].shape[2]
+        out = dict(push=torch.zeros((B, 3), dtype=torch.float64, device=self.dev), wrench=torch.zeros((T, B, N, 6), dtype=torch.float32, device=self.dev),
+                   models=torch.zeros((B, 34), dtype=torch.float64, device=self.dev), plan=torch.zeros((B, 2, M, 3), dtype=torch.float64, device=self.dev),
+                   status=torch.zeros((T, B), dtype=torch.int32, device=self.dev))
+        ls = self.solver.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            g, gl = gS[T].clone(), None
+            for i in reversed(range(T)):
+                tk = ticks[i]
+                r = self.solver.rollout_tick_vjp_device(tk["now"], tk, g, gl, None if gX is None else gX[i], dGradPlan=out["plan"], dGradModel=out["models"])
+                g = r["state"] + gS[i]
+                gl = r["prev_list"]
+                out["wrench"][i] = r["wrench"]
+                out["status"][i] = r["sens"][:, 0].to(torch.int32)
+                if tk["push_knots"] > 0:
+                    out["push"] += r["wrench"][:, :tk["push_knots"], :3].to(torch.float64).sum(1)
+            out["state0"], out["list0"] = g, gl
+        cur.wait_stream(ls)
+        return out
+
+
+def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0):
+    """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
+    state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
+    (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
+    tensor installed on the roll-out's solver (set_models_device) and left installed.  rollout.last_tape / rollout.last_backward hold the tape of the last
+    forward and the dict of the last backward (its status words say which ticks passed no gradient on)."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, state0, push, models):
+            if models is not None:
+                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
+                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
+            s0 = state0.detach().to(torch.float32).cpu().numpy()
+            rec = rollout.run(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(torch.float32).cpu().numpy(),
+                              push_ticks=push_ticks, record="light", tape=True)
+            tape = rec["tape"]
+            assert len(tape["ticks"]) == ticks, f"the roll-out stopped at tick {rec.get('aborted_tick')}"
+            rollout.last_tape = ctx.tape = tape
+            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
+            return torch.stack([tk["state"] for tk in tape["ticks"]] + [tape["state"]])
+
+        @staticmethod
+        def backward(ctx, gStates):
+            r = rollout.backward(ctx.tape, gStates)
+            rollout.last_backward = r
+            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
+                    r["models"] if ctx.needs_input_grad[2] else None)
+
+    return _Fn.apply(state0, push, models)

@@ -384,6 +384,117 @@ class BatchSolver:
         return dStateOut, dZmp
 
 
+    # ---- the roll-out tick in reverse (include/cmpc.h, "plant-step derivatives" and "the roll-out tick in reverse") ----
+    def _opt(self, t, dtype, shape, name):
+        """data_ptr of an optional CUDA tensor (None -> NULL), checked"""
+        if t is None:
+            return None
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{name}: expected {dtype} {tuple(shape)}"
+        return t.data_ptr()
+
+    def plant_step_jvp_device(self, dX, dP, dState, dDirState, dDirX=None, dDirP=None, dDirModel=None, step=0.01, substeps=6, out=None):
+        """d(plant step) applied to one direction per problem: dDirState[B, 9] float64, dDirX[B, n_x] / dDirP[B, n_p] float32 and dDirModel[B, 34]
+        float64 (None: zero) -> d state'[B, 9] float64.  What is and is not differentiated: include/cmpc.h."""
+        import torch
+        L, B = self.layout, self.batch
+        if out is None:
+            out = torch.empty((B, 9), dtype=torch.float64, device=dX.device)
+        ps = self._opt(dDirState, torch.float64, (B, 9), "dDirState")
+        px, pp = self._opt(dDirX, torch.float32, (B, L.nx), "dDirX"), self._opt(dDirP, torch.float32, (B, L.np), "dDirP")
+        pm, po = self._opt(dDirModel, torch.float64, (B, _capi.MODEL_DOUBLES), "dDirModel"), self._opt(out, torch.float64, (B, 9), "out")
+        self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_device(self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step),
+                                                                                int(substeps), ps, px, pp, pm, po, st))
+        return out
+
+    def plant_step_vjp_device(self, dX, dP, dState, dGradStateOut, step=0.01, substeps=6, grad_p=True, grad_model=True):
+        """(d plant step)^T g: dGradStateOut[B, 9] float64 -> (dGradState[B, 9] float64, dGradX[B, n_x] float32, dGradP[B, n_p] float32 or None,
+        dGradModel[B, 34] float64 or None); dGradX is zero but for the knot-0 positions and forces, dGradP but for fExt_0 / tauExt_0."""
+        import torch
+        L, B, dev = self.layout, self.batch, dX.device
+        pg = self._opt(dGradStateOut, torch.float64, (B, 9), "dGradStateOut")
+        gS = torch.empty((B, 9), dtype=torch.float64, device=dev)
+        gX = torch.empty((B, L.nx), dtype=torch.float32, device=dev)
+        gP = torch.empty((B, L.np), dtype=torch.float32, device=dev) if grad_p else None
+        gM = torch.empty((B, _capi.MODEL_DOUBLES), dtype=torch.float64, device=dev) if grad_model else None
+        self._launch(dev, lambda st: self._lib.cmpc_plant_step_vjp_device(
+            self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step), int(substeps), pg, gS.data_ptr(), gX.data_ptr(),
+            gP.data_ptr() if grad_p else None, gM.data_ptr() if grad_model else None, st))
+        return gS, gX, gP, gM
+
+    def contacts_position_vjp_device(self, now, list_t, list_n, land, plan=None, prev=None, ok=None, dGradListOut=None, dGradP=None, dGradX=None,
+                                     dGradPlan=None, phase=3, force_sample_time=False, out=None):
+        """Adjoint of the list path of one tick in the contacts' positions (cmpc_contacts_position_vjp_device): list_t[B,2,M,2] float64 / list_n[B,2]
+        int32 = this tick's (merged) list, plan / prev = (t, n) of the planner's and the previous tick's lists (prev None: first tick), land[B,2],
+        ok[B] or None.  phase 1: the adjust part (adds to dGradX in place); 2: sample + merge; 3: both.  dGradListOut[B,2,M,3] float64, dGradP[B,n_p]
+        float32, dGradPlan[B,2,M,3] float64 (+=, in place).  Returns (dGradPrevList[B,2,M,3] float64 or None for phase 1, status[B] int32 or None)."""
+        import torch
+        L, B, M, dev = self.layout, self.batch, list_t.shape[2], list_t.device
+        g3 = (B, 2, M, 3)
+        assert list_t.is_cuda and list_t.dtype == torch.float64 and list_t.is_contiguous() and tuple(list_t.shape) == (B, 2, M, 2)
+        gprev = status = None
+        if phase & 2:
+            gprev = out if out is not None else torch.empty(g3, dtype=torch.float64, device=dev)
+            status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tn = lambda pair: (None, None) if pair is None else (self._opt(pair[0], torch.float64, (B, 2, M, 2), "times"), self._opt(pair[1], torch.int32, (B, 2), "counts"))
+        (plt, pln), (pvt, pvn) = tn(plan), tn(prev)
+        args = (self._opt(list_n, torch.int32, (B, 2), "list_n"), self._opt(land, torch.int32, (B, 2), "land"), self._opt(ok, torch.int32, (B,), "ok"),
+                self._opt(dGradListOut, torch.float64, g3, "dGradListOut"), self._opt(dGradP, torch.float32, (B, L.np), "dGradP"),
+                self._opt(dGradX, torch.float32, (B, L.nx), "dGradX"), self._opt(gprev, torch.float64, g3, "out"),
+                self._opt(dGradPlan, torch.float64, g3, "dGradPlan"), status.data_ptr() if status is not None else None)
+        self._launch(dev, lambda st: self._lib.cmpc_contacts_position_vjp_device(
+            self._h, M, float(now), int(phase), 1 if force_sample_time else 0, plt, pln, pvt, pvn, list_t.data_ptr(), *args, st))
+        return gprev, status
+
+    def rollout_tick_vjp_device(self, now, tape, dGradStateOut, dGradListOut=None, dGradX=None, dGradPlan=None, dGradModel=None, wrench=True, grad_p=False):
+        """cmpc_rollout_tick_vjp_device: one tick in reverse.  tape: dict(X, P, lam_g, state, info, ok (or None), land, plan_t, plan_n, prev_t, prev_n
+        (both None on the first tick), list_t, list_n, step, substeps, force_sample_time) of CUDA tensors as the forward tick left them.
+        dGradStateOut[B,9] float64, dGradListOut[B,2,M,3] float64 or None, dGradX[B,n_x] float32 or None; dGradPlan / dGradModel: float64 tensors added to
+        in place, or None.  Returns dict(state[B,9], prev_list[B,2,M,3] float64, wrench[B,N,6] float32 or None, p[B,n_p] float32 or None,
+        sens[B,CMPC_SENS] float32 with the tick's status in word 0)."""
+        import torch
+        from ._capi import CmpcTickTape
+        L, B, N = self.layout, self.batch, self.cfg.N
+        lt = tape["list_t"]
+        M, dev = lt.shape[2], lt.device
+        g3 = (B, 2, M, 3)
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        tt, tn = (B, 2, M, 2), (B, 2)
+        ct = CmpcTickTape(self._opt(tape["X"], f32, (B, L.nx), "X"), self._opt(tape["P"], f32, (B, L.np), "P"), self._opt(tape["lam_g"], f32, (B, L.ng), "lam_g"),
+                          self._opt(tape["state"], f32, (B, 9), "state"), self._opt(tape["info"], f32, (B, _capi.INFO), "info"),
+                          self._opt(tape.get("ok"), i32, (B,), "ok"), self._opt(tape["land"], i32, tn, "land"),
+                          self._opt(tape.get("plan_t"), f64, tt, "plan_t"), self._opt(tape.get("plan_n"), i32, tn, "plan_n"),
+                          self._opt(tape.get("prev_t"), f64, tt, "prev_t"), self._opt(tape.get("prev_n"), i32, tn, "prev_n"),
+                          self._opt(lt, f64, tt, "list_t"), self._opt(tape["list_n"], i32, tn, "list_n"),
+                          float(tape["step"]), int(tape["substeps"]), 1 if tape.get("force_sample_time") else 0)
+        out = dict(state=torch.empty((B, 9), dtype=f64, device=dev), prev_list=torch.empty(g3, dtype=f64, device=dev),
+                   wrench=torch.empty((B, N, 6), dtype=f32, device=dev) if wrench else None,
+                   p=torch.empty((B, L.np), dtype=f32, device=dev) if grad_p else None, sens=torch.empty((B, _capi.SENS), dtype=f32, device=dev))
+        args = (self._opt(dGradStateOut, f64, (B, 9), "dGradStateOut"), self._opt(dGradListOut, f64, g3, "dGradListOut"),
+                self._opt(dGradX, f32, (B, L.nx), "dGradX"), out["state"].data_ptr(), out["prev_list"].data_ptr(),
+                out["wrench"].data_ptr() if wrench else None, self._opt(dGradPlan, f64, g3, "dGradPlan"),
+                self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"), out["p"].data_ptr() if grad_p else None, out["sens"].data_ptr())
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_device(self._h, M, float(now), ct, *args, st))
+        return out
+
+    def closed_loop_transition_device(self, dX, dP, dLamG, dState, step=0.01, substeps=6):
+        """A_cl[B, 9, 9] = d state' / d state of one tick (solve + plant, float64; row i = component i of state'): the nine-column JVP of
+        feedback_gain_device (dx* / d(com0, dcom0, h0)) pushed column by column through the plant JVP together with the plant's own d state' / d state.
+        The forward-mode cousin of rollout_tick_vjp_device.  Returns (A_cl, sens[B, CMPC_SENS]); a flagged problem's JVP columns are zero, so its A_cl is the
+        plant's own."""
+        import torch
+        L, B = self.layout, self.batch
+        dirs = torch.zeros((B, 9, L.np), dtype=torch.float32, device=dX.device)
+        for i in range(9):
+            dirs[:, i, L.p_com0 + i] = 1.0
+        dDX, sens = self.solution_jvp_device(dX, dP, dLamG, dirs)
+        A = torch.empty((B, 9, 9), dtype=torch.float64, device=dX.device)
+        for i in range(9):
+            e = torch.zeros((B, 9), dtype=torch.float64, device=dX.device)
+            e[:, i] = 1.0
+            A[:, :, i] = self.plant_step_jvp_device(dX, dP, dState, e, dDirX=dDX[:, i].contiguous(), step=step, substeps=substeps)
+        return A, sens
+
+
     # ---- SURVEY 8f-1 / 8f-2 on the device (torch CUDA tensors; everything stays in HBM) ----
     def _launch(self, dev, fn):
         """runs fn(raw_stream) on torch's current stream (the default stream: on the solver's side stream, ordered after it and joined back; _stream_pair)"""
