@@ -237,6 +237,61 @@ def single_support_end_n12(which="tmp", B=16, seed=44):
     return _finish(cfg, sched, com0, dcom0, h0, ref, np.zeros((B, N + 1, 3)), f_ext)
 
 
+def gait_cycle(cfg, per_phase, seed, displaced=False):
+    """Every phase of one period of the roll-out's periodic walk (rollout.walking_plan, times on cfg's grid) as the horizon's first stage:
+    -> (cfg, P, X0, phase) with B = period x per_phase problems, problem b at phase[b] = b // per_phase.  At dt = 0.06 the plan's defaults
+    (swing 8 stages, double support 2, period 20); at dt = 0.1 swing 0.5 s, double support 0.1 s, first lift 0.3 s (period 12).  Phase s samples the
+    plan at t0 = (s0 + s) dt, s0 = the landing of the first, half-length step (the contact pattern is periodic from there): over the period a foot is in
+    the air at stage 0, lands or lifts at stage 1, and swing phases enter and leave the horizon at its last stage.  Every planned footstep is yawed by
+    U(-0.2, 0.2) rad (one plan per batch, R != I).  Per problem: a perturbed state around the midpoint of the two nominal feet at knot 0 (height 0.7),
+    comRef the midpoints of the nominal feet knot by knot, hRef zero, a push U(-50, 50) N in x and y over the first ceil(0.2 / dt) stages.
+    Random draws in the order yaws, com0, dcom0, h0, push, displacements -- so displaced=True changes nothing but currentPos.
+    displaced=True: a foot in the air at stage 0 has currentPos = nominal_0 + R_0 d, d uniform in 0.8 x [lower, upper] of its box on x and y, 0 on z:
+    the state the step adjustment leaves behind (the tensor entry points accept it; the contact sampler never writes it)."""
+    from .rollout import walking_plan
+    N, dt = cfg.N, cfg.sampling_time
+    if abs(dt - 0.06) < 1e-9:
+        sw, ds, lift = 8, 2, 6
+    elif abs(dt - 0.1) < 1e-9:
+        sw, ds, lift = 5, 1, 3
+    else:
+        raise ValueError(f"gait_cycle: no gait on the grid of dt = {dt}")
+    period, s0 = 2 * (sw + ds), lift + sw
+    steps = -(-(s0 + period + N - lift) // (sw + ds)) + 2
+    plan = walking_plan(cfg, steps=steps, swing=sw * dt, double_support=ds * dt, first_lift=lift * dt)
+    rng = np.random.default_rng(seed)
+    for cc in cfg.contacts:
+        for ct in plan[cc.contact_name]:
+            ct.yaw = rng.uniform(-0.2, 0.2)
+    B = period * per_phase
+    phase = np.repeat(np.arange(period), per_phase)
+    scheds = [sample_schedule(cfg, plan, t0=(s0 + s) * dt) for s in range(period)]
+    sched = {k: np.stack([sc[k] for sc in scheds])[phase] for k in scheds[0]}
+    ref = 0.5 * (sched["nominal"][:, 0] + sched["nominal"][:, 1])
+    ref[:, :, 2] = 0.7
+    com0, dcom0, h0 = _perturbed_state(rng, B, (0.0, 0.0, 0.0))
+    com0 = ref[:, 0] + com0
+    f_ext = np.zeros((B, N, 3))
+    f_ext[:, :int(np.ceil(0.2 / dt)), :2] = (rng.uniform(-50.0, 50.0, (B, 2)) / ROBOT_MASS)[:, None, :]
+    if displaced:
+        for ci, cc in enumerate(cfg.contacts):
+            lo, up = 0.8 * np.asarray(cc.bounding_box_lower_limit, float), 0.8 * np.asarray(cc.bounding_box_upper_limit, float)
+            d = np.zeros((B, 3))
+            d[:, :2] = rng.uniform(lo[:2], up[:2], (B, 2))
+            air = sched["enabled"][:, ci, 0] < 0.5
+            sched["current"][air, ci] = sched["nominal"][air, ci, 0] + np.einsum("bij,bj->bi", sched["R"][air, ci, 0], d[air])
+    return _finish(cfg, sched, com0, dcom0, h0, ref, np.zeros((B, N + 1, 3)), f_ext) + (phase,)
+
+
+def gait_cycle_n12(which="tmp", seed=46):
+    """N = 12, dt = 0.1, generated-code weights: the 12 phases of gait_cycle, one aligned problem each (rows 0 .. 11) and the same problems with the
+    swinging foot's currentPos displaced (rows 12 .. 23)."""
+    cfg = _cfg.generated_code_weights(which, 12, 0.1)
+    _, Pa, Xa, _ = gait_cycle(cfg, 1, seed)
+    _, Pd, Xd, _ = gait_cycle(cfg, 1, seed, displaced=True)
+    return cfg, np.concatenate([Pa, Pd]), np.concatenate([Xa, Xd])
+
+
 def standing_n12(which="tmp", B=16, seed=45):
     """N = 12, dt = 0.1, generated-code weights: a batch of the standing problem of SURVEY 8c (iii) with perturbed initial states
     (config 2 at the horizon and weights of the reference's generated code)."""

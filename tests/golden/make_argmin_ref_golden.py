@@ -1,12 +1,13 @@
-"""Generates tests/golden/argmin_ref_{walk,yaw}_{tmp,jit}.npz: argmin vectors of N = 12 problems computed ON THE
+"""Generates tests/golden/argmin_ref_{walk,yaw,push,ssend,stand,gait}_{tmp,jit}.npz: argmin vectors of N = 12 problems computed ON THE
 REFERENCE'S OWN COMPILED NLP FUNCTIONS (oracle/_ref = tmp.c / jit_tmpComMiH.c compiled where they lie): the
 IPOPT-style solver oracle/ipm_generic.py is run with f, g, grad f, jac g and hess L taken from that code, i.e. it
 minimises exactly what IPOPT minimises in the reference (N = 12, dt = 0.1 and the weights are baked into that code).
 
-    python tests/golden/make_argmin_ref_golden.py          (build container only: needs /root/reference)
+    python tests/golden/make_argmin_ref_golden.py [family ...]   (needs the reference's sources, compiled into oracle/_ref; no family: all of them)
 
 Problems, 16 of each with both baked weight sets (160 in all): a swing phase with a push (step adjustment active), two yawed
-footsteps (R != I), push recovery with active friction rows, single support at the horizon end, the standing problem.  Stored: float32 inputs (P, X0), the float64 argmin, the multipliers of every constraint row, the
+footsteps (R != I), push recovery with active friction rows, single support at the horizon end, the standing problem; and the 12 phases of the gait cycle (synthetic.gait_cycle_n12: a foot in the air at
+stage 0, landings and lift-offs at the first and last stage), one aligned and one displaced problem per phase.  Stored: float32 inputs (P, X0), the float64 argmin, the multipliers of every constraint row, the
 objective, and the KKT residuals of the stored point evaluated with the reference's code (stationarity, feasibility,
 complementarity, smallest eigenvalue of the Hessian reduced to the null space of the active constraints).
 These are data (vectors), not reference source."""
@@ -76,10 +77,10 @@ def make(name, which, gen):
                         f_star=np.array(fs), kkt=np.array(reps), N=cfg.N, dt=cfg.sampling_time)
 
 
+FAMILIES = {"walk": cm.synthetic.walking_push_n12, "yaw": cm.synthetic.yawed_steps_n12, "push": cm.synthetic.push_recovery_n12,
+            "ssend": cm.synthetic.single_support_end_n12, "stand": cm.synthetic.standing_n12, "gait": cm.synthetic.gait_cycle_n12}
+
 if __name__ == "__main__":
     for which in ("tmp", "jit"):
-        make("walk", which, cm.synthetic.walking_push_n12)
-        make("yaw", which, cm.synthetic.yawed_steps_n12)
-        make("push", which, cm.synthetic.push_recovery_n12)
-        make("ssend", which, cm.synthetic.single_support_end_n12)
-        make("stand", which, cm.synthetic.standing_n12)
+        for name in sys.argv[1:] or FAMILIES:
+            make(name, which, FAMILIES[name])

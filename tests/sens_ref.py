@@ -128,9 +128,12 @@ class Sens:
         return np.concatenate([rx[self.keep], rE])
 
     def _solve(self, b):
-        """dense solve with one step of iterative refinement"""
-        y = np.linalg.solve(self.K, b)
-        return y + np.linalg.solve(self.K, b - self.K @ y)
+        """dense solve with one step of iterative refinement (b a vector or a matrix of columns); K is factorised once"""
+        from scipy.linalg import lu_factor, lu_solve
+        if getattr(self, "_lu", None) is None:
+            self._lu = lu_factor(self.K)
+        y = lu_solve(self._lu, b)
+        return y + lu_solve(self._lu, b - self.K @ y)
 
     def _full(self, d):
         out = np.zeros(self.L.nx)
@@ -143,14 +146,15 @@ class Sens:
             dx = dx - self.n * (self.n @ dx)
         return dx
 
-    def vjp(self, v):
+    def vjp(self, v, idx=None):
+        """idx: the entries of p to compute (the others stay 0); None: every covered one"""
         v = np.asarray(v, np.float64)
         if self.n is not None:
             v = v - self.n * (self.n @ v)
         w = self._solve(np.concatenate([v[self.keep], np.zeros(self.eq.size)]))
         m = covered_mask(self.N)
         out = np.zeros(self.L.np)
-        for j in np.nonzero(m)[0]:
+        for j in (np.nonzero(m)[0] if idx is None else [j for j in idx if m[j]]):
             e = np.zeros(self.L.np)
             e[j] = 1.0
             out[j] = -w @ self.rhs(e)

@@ -109,8 +109,8 @@ def test_hip_arithmetic_model_meets_tolerance(name, golden_dir):
 
 # ---- argmin vectors computed on the reference's own compiled NLP functions (tests/golden/make_argmin_ref_golden.py) ----
 REF_GEN = {"walk": cm.synthetic.walking_push_n12, "yaw": cm.synthetic.yawed_steps_n12, "push": cm.synthetic.push_recovery_n12,
-           "ssend": cm.synthetic.single_support_end_n12, "stand": cm.synthetic.standing_n12}
-REF_CASES = [(n, w) for n in REF_GEN for w in ("tmp", "jit")]        # 16 problems per type and baked weight set: 160 argmins
+           "ssend": cm.synthetic.single_support_end_n12, "stand": cm.synthetic.standing_n12, "gait": cm.synthetic.gait_cycle_n12}
+REF_CASES = [(n, w) for n in REF_GEN for w in ("tmp", "jit")]        # 16 problems per type (gait: 24) and baked weight set: 208 argmins
 
 
 @pytest.mark.parametrize("name,which", REF_CASES)
