@@ -235,8 +235,9 @@ int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP,
 /* Gradient of the optimal cost with respect to every parameter (envelope theorem) at a KKT point (x*, lam*): dGradP[B][n_p] = grad_p L(x, lam)
  * (nlp_grad, lam_f = 1) plus the parameters that only enter the bounds: -lam_init on com0, dcom0, h0 and currentPos; -max(lam, 0) on upper and
  * -min(lam, 0) on lower of each box row.  The entries of enabled (Gamma, binary) and R (constrained to rotations) are formal derivatives of the
- * generated code, not derivatives along feasible perturbations.  The derivatives with respect to the per-problem model fields are
- * cmpc_model_value_gradient_device (below, "model directions"). */
+ * generated code, not derivatives along feasible perturbations; the derivative along rotations is cmpc_rotation_value_gradient_device (below,
+ * "rotation directions").  The derivatives with respect to the per-problem model fields are cmpc_model_value_gradient_device (below, "model
+ * directions"). */
 int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream);
 
 /* ---- solution sensitivities: dx* / dp as JVP and VJP (derivation: DESIGN.md 7c) ----
@@ -253,9 +254,9 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
  * b are the bounds as functions of p: com0, dcom0, h0, currentPos (initial rows), box lower / upper; an equality box component's bound is
  * (lower + upper) / 2 (a perturbation that stays in the subset moves both).  JVP: dx.  VJP: the same symmetric system with right-hand side [v; 0],
  * v = dl/dx, and dl/dp = -w^T r_p.
- * Parameters covered: com0, dcom0, h0, currentPos, comRef, hRef, nominalPos, box upper / lower, fExt, tauExt.  Not covered: Gamma (enabled, discrete)
- * and R (rotations; a tangent-space derivative is not provided): the JVP reads those entries of dp as zero, the VJP writes zeros there.  The fields of
- * the per-problem model are covered by the *_model_device entry points below ("model directions").
+ * Parameters covered: com0, dcom0, h0, currentPos, comRef, hRef, nominalPos, box upper / lower, fExt, tauExt.  Not covered: Gamma (enabled, discrete):
+ * the JVP reads those entries of dp, and the entries of R, as zero, the VJP writes zeros there.  R is covered in its tangent space by the *_rot_device
+ * entry points below ("rotation directions"), the fields of the per-problem model by the *_model_device entry points ("model directions").
  * Tied entries (subset rule 3): a stance stage after a landing repeats the last swing stage's R, nominal, lower and upper.  Under this map a stance
  * stage's lower / upper have zero derivative and a stance knot's nominalPos acts through the cost only; a perturbation that stays in the subset moves
  * the whole group, and its derivative is the sum over the group.
@@ -274,7 +275,8 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
  *                         1 if the internal-force direction exists (and was projected out);
  *                         number of weakly active friction rows of swing stages (counted apart: a swing foot's forces enter no dynamics, and they
  *                           sit near the apex because the costs pull them towards zero from inside the pyramid, not because a face binds);
- *                         the removed relative component of model directions along the internal-force direction (0 here; "model directions");  0 }.
+ *                         the removed relative component of model and rotation directions along the internal-force direction (0 here; "model
+ *                           directions", "rotation directions");  0 }.
  * A flagged problem gets zero outputs; its neighbours are unaffected.  Per-problem models (cmpc_set_models*) apply; every horizon the handle supports.
  * Workspace: per-handle HBM, allocated on first use and freed by cmpc_destroy, for min(B, CMPC_SENS_SUB_BATCH) problems (larger batches run in
  * sub-batches): cmpc_sensitivity_workspace_bytes(N) per problem -- 8 (39^2 (N+1) + 2070 N + 8 (216 N + 117)) bytes, 0.85 MB at N = 20.
@@ -337,6 +339,55 @@ int cmpc_solution_vjp_model_device(cmpc_handle h, const float* dX, const float* 
                                    double* dGradModel, float* dSens, void* stream);
 /* dV* / dtheta [B][34] double at (x, lam_g); zeros for a row whose model broke the model rule */
 int cmpc_model_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradModel, void* stream);
+
+/* ---- rotation directions: derivatives with respect to the stage rotations R (derivation: DESIGN.md 7c) ----
+ * omega[c][k] in R^3, one per contact c in {0, 1} and stage k = 0..N-1, moves that stage's rotation along dR_{c,k} = R_{c,k} [omega_{c,k}]x: the right
+ * (body-frame) tangent, manif's rplus, which the reference's poses use; for a flat foot, yaw is omega = e_z in either frame.  R_{c,k} is the float32
+ * matrix as stored in p (column-major 3x3 at p_R(c) + 9 k), not re-orthonormalised.  Every term of the NLP is linear in the entries of R --
+ * (R corner + pos - com) x f, R^T (pos - nominalPos), A R^T f -- so the formal derivative of the NLP along dR is exact, and no bound depends on R.
+ * In the barrier system of the solution sensitivities a rotation direction has the right-hand side
+ *     r_x = d_omega(grad_x L) omega + sum_{i in I} J_i^T Sigma_i d_omega g_i omega,     r_E = d_omega g_E omega
+ * (Sigma, the rows E / I, the slack floor, the shift, the refinement and dSens exactly as there).  JVP: dx = the first block of
+ * K^-1 (-r(dp, dtheta, omega)), so p, model and rotation directions combine in one column.  VJP: dl/domega_{c,k} = -w^T r_{omega_{c,k}} with the same w
+ * as cmpc_solution_vjp_device.  Value gradient: dV* / domega = lam^T d_omega g at (x, lam_g) (envelope theorem; f does not depend on R).
+ * Where R enters: the angular-momentum rows of stage k through the lever arms (R [omega]x corner in place of the corner fields' R e_b); the friction
+ * rows of stage k, a_i^T R^T f, with d_omega g_i = a_i^T ([R^T f]x omega), through lam and through Sigma -- swing feet's rows too; the box rows of
+ * swing stages, R_k^T (pos_{k+1} - nominalPos_{k+1}) (index k of R pairs with knot k+1).  The stage form lands a swing foot at nominalPos + R^-T q, so
+ * its change of variables moves with R, d(R^-T) = R^-T [omega]x: the position dynamics get R^-T (omega x q) at the returned q = R^T (pos - nominalPos),
+ * free and fixed components alike, and the free offsets get omega x lam_box; dx comes out in the NLP's x layout as before.
+ * Tied entries (subset rule 3): a stance stage after a landing repeats the last swing stage's R.  The entries here are per stage; a perturbation that
+ * stays in the subset moves the whole group, and its derivative is the sum over the group (cmpc_contacts_rotation_vjp_device does that sum per list
+ * entry).
+ * Internal force (both feet in stance over the whole horizon): the rule of the model directions, unchanged -- rotating one foot gives the internal
+ * force a moment arm.  The JVP removes n (n^T r_x) from the rotation part of the column before the solve, the VJP removes the same component from
+ * every r_omega, and the removed relative size joins dSens[6] (the largest over the columns or the 6 N entries, combined with the model part's by
+ * max).  Without loaded friction rows it is at the solve's tolerance (<= 3e-7 on the config 2 goldens; up to 0.2 on synthetic config 2 problems whose friction rows carry load) and the derivative exists; with them (a push in
+ * double support: 0.11 .. 0.16 for a whole foot, 0.19 for the worst single entry) there is none, as for friction there.
+ * Swing feet: a rotation acts directly on the friction rows of swing feet, which sit at the apex of their pyramids (weakly active, counted in
+ * dSens[5]); for a group of stages that contains swing stages the barrier derivative and the true one differ by a small absolute amount (4e-6 ..
+ * 1.6e-5 in dx per radian on the goldens, 5e-4 of the effect where the effect is not itself that small) -- the effect the model directions state for
+ * the symmetry and force-rate weights.
+ * No workspace beyond cmpc_sensitivity_workspace_bytes; argument checks, sub-batches, the event ordering, per-problem models and the bit-for-bit
+ * independence of batch position, batch size, k and sub-batching as for the model directions.  A flagged problem (a non-finite omega: status 2) gets
+ * zeros, its neighbours keep their bits.
+ * JVP: dDirP[B][k][n_p] float, dDirModel[B][k][34] double, dDirRot[B][k][2][N][3] double (each NULL: zero) -> dDX[B][k][n_x].  With dDirRot == NULL the
+ * result is cmpc_solution_jvp_model_device's, bit for bit. */
+int cmpc_solution_jvp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const double* dDirModel,
+                                 const double* dDirRot, int k, float* dDX, float* dSens, void* stream);
+/* VJP: dGradX[B][n_x] -> dGradRot[B][2][N][3] double, dGradP[B][n_p] float and dGradModel[B][34] double from ONE adjoint solve (each may be NULL, not
+ * all three); dGradP and dGradModel are cmpc_solution_vjp_model_device's, bit for bit */
+int cmpc_solution_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP,
+                                 double* dGradModel, double* dGradRot, float* dSens, void* stream);
+/* dV* / domega [B][2][N][3] double at (x, lam_g); zeros for a row whose model broke the model rule.  At a double-support point the entries depend
+ * on the internal force the solve returned, as the corner entries of dV* / dtheta do. */
+int cmpc_rotation_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradRot, void* stream);
+/* Per stage -> per list entry: dGradListRot[B][2][max_contacts][3] double = for each entry m of the sampled lists (dT[B][2][max_contacts][2],
+ * dN[B][2], sampled at `now`), the sum over the stages k it owns of dGradRot[c][k] (cmpc_contacts_sample's owner rule: the active contact, else the
+ * next, else the last), in the body-frame tangent of the entry's quaternion, q <- q (x) exp(omega / 2): a sampled stage copies its owner's rotation, so
+ * omega_stage = omega_owner.  float64 sums in stage order, one thread per (problem, foot), no atomics.  Entries at or beyond n carry none; a foot
+ * that the sampling would not sample (an empty list, or n > max_contacts) gets zeros. */
+int cmpc_contacts_rotation_vjp_device(cmpc_handle h, int max_contacts, double now, const double* dT, const int* dN, const double* dGradRot,
+                                      double* dGradListRot, void* stream);
 
 /* ---- class-shaped setters (host buffers -> the handle's own device P, X0) ----
  * batch-major float32; NULL keeps the previous value (zeros initially).
@@ -532,7 +583,8 @@ typedef struct cmpc_tick_io {
 } cmpc_tick_io;
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
- * Adjoint of the list path of one tick in the contacts' POSITIONS; orientations and times are not differentiated.  The forward maps move positions
+ * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated, and of the orientations only the sampling is
+ * (cmpc_contacts_rotation_vjp_device, "rotation directions": not the merge, and not through this entry point).  The forward maps move positions
  * through index maps that depend on the contact times only, so the adjoint needs the lists' times and counts, not their poses: the planner's lists, the
  * previous tick's and this tick's merged list as cmpc_rollout_tick_device (or the seven calls) left them, and dLand / dOk of that tick.  The maps are
  * re-derived with the forward's own functions (getActiveContact, getNextContact, the stage owner).  Gradients of list positions are double

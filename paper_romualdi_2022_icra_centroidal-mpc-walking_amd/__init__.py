@@ -9,4 +9,4 @@ from . import _capi, config, contacts, distributed, layout, rollout, solver, syn
 from .config import CentroidalMPCConfig, ContactConfig  # noqa: F401
 from .layout import Layout, cold_start, pack_parameters  # noqa: F401
 from .rollout import WalkingRollout, rollout_differentiable  # noqa: F401
-from .solver import BatchSolver, CentroidalMPC, solve_differentiable  # noqa: F401
+from .solver import BatchSolver, CentroidalMPC, rotate_parameters, solve_differentiable  # noqa: F401

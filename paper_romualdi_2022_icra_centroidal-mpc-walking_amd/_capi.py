@@ -92,6 +92,7 @@ EXPORTS = [
     "cmpc_value_gradient_device", "cmpc_solution_jvp_device", "cmpc_solution_vjp_device",
     "cmpc_sensitivity_workspace_bytes", "cmpc_solution_jvp_model_device", "cmpc_solution_vjp_model_device", "cmpc_model_value_gradient_device",
     "cmpc_plant_step_jvp_device", "cmpc_plant_step_vjp_device", "cmpc_contacts_position_vjp_device", "cmpc_rollout_tick_vjp_device",
+    "cmpc_solution_jvp_rot_device", "cmpc_solution_vjp_rot_device", "cmpc_rotation_value_gradient_device", "cmpc_contacts_rotation_vjp_device",
 ]
 
 _lib = None
@@ -174,6 +175,11 @@ def lib():
             L.cmpc_solution_jvp_model_device.argtypes = [vp, fp, fp, fp, fp, vp, C.c_int, fp, fp, vp]
             L.cmpc_solution_vjp_model_device.argtypes = [vp, fp, fp, fp, fp, fp, vp, fp, vp]
             L.cmpc_model_value_gradient_device.argtypes = [vp, fp, fp, fp, vp, vp]
+        if hasattr(L, "cmpc_solution_jvp_rot_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_solution_jvp_rot_device.argtypes = [vp, fp, fp, fp, fp, vp, vp, C.c_int, fp, fp, vp]
+            L.cmpc_solution_vjp_rot_device.argtypes = [vp, fp, fp, fp, fp, fp, vp, vp, fp, vp]
+            L.cmpc_rotation_value_gradient_device.argtypes = [vp, fp, fp, fp, vp, vp]
+            L.cmpc_contacts_rotation_vjp_device.argtypes = [vp, i, d, vp, vp, vp, vp, vp]
         L.cmpc_plant_step_jvp_device.argtypes = [vp, fp, fp, fp, d, i, vp, fp, fp, vp, vp, vp]
         L.cmpc_plant_step_vjp_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp]
         L.cmpc_contacts_position_vjp_device.argtypes = [vp, i, d, i, i] + [vp] * 15

@@ -25,9 +25,13 @@ extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* d
 extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream);
 extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
                                        const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
-                                       double* dGradModel, hipStream_t stream);
+                                       double* dGradModel, const double* dDirRot, double* dGradRot, hipStream_t stream);
 extern "C" int cmpc_launch_model_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradModel,
                                                 hipStream_t stream);
+extern "C" int cmpc_launch_rotation_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradRot,
+                                                   hipStream_t stream);
+extern "C" int cmpc_launch_contacts_rotation_vjp(int B, int N, int M, double dt, double now, const double* list_t, const int* list_n, const double* g_rot,
+                                                 double* g_list, hipStream_t stream);
 extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev, float* dX0, hipStream_t stream);
 extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double* plan_t, const float* plan_pose, const int* plan_n,
                                           const double* mpc_t, const float* mpc_pose, const int* mpc_n, double* out_t, float* out_pose,
@@ -786,7 +790,8 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
 
 // ---- solution sensitivities (include/cmpc.h; cmpc_sensitivity.hip) ----
 static int sensitivity(cmpc_handle h, const char* name, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const float* dGradX,
-                       int k, float* dOut, float* dSens, void* stream, const double* dDirModel = nullptr, double* dGradModel = nullptr)
+                       int k, float* dOut, float* dSens, void* stream, const double* dDirModel = nullptr, double* dGradModel = nullptr,
+                       const double* dDirRot = nullptr, double* dGradRot = nullptr)
 {
     HIPCHK(h, hipSetDevice(h->device));
     const int N = h->cfg.horizon, sb = h->B < CMPC_SENS_SUB_BATCH ? h->B : CMPC_SENS_SUB_BATCH;
@@ -799,7 +804,7 @@ static int sensitivity(cmpc_handle h, const char* name, const float* dX, const f
     for (int b0 = 0; b0 < h->B; b0 += sb) {
         const int nb = h->B - b0 < sb ? h->B - b0 : sb;
         int rc = cmpc_launch_sensitivity(kc, h->models_set ? 1 : 0, N, b0, nb, dX, dP, dLamG, dDirP, dGradX, k, dOut, dSens, h->dSensWs, dDirModel,
-                                         dGradModel, st);
+                                         dGradModel, dDirRot, dGradRot, st);
         if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString((hipError_t)rc));
     }
     HIPCHK(h, hipEventRecord(h->sens_ev, st));
@@ -845,6 +850,45 @@ int cmpc_model_value_gradient_device(cmpc_handle h, const float* dX, const float
     fill_params(h, p);
     int rc = cmpc_launch_model_value_gradient(&p, dX, dP, dLamG, dGradModel, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("model value gradient launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+// ---- derivatives with respect to the stage rotations (include/cmpc.h, "rotation directions") ----
+int cmpc_solution_jvp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dDirP, const double* dDirModel,
+                                 const double* dDirRot, int k, float* dDX, float* dSens, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dDX) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_rot_device: null argument");
+    if (k < 1) return fail(h, CMPC_ERR_ARG, "cmpc_solution_jvp_rot_device: k must be >= 1");
+    return sensitivity(h, "cmpc_solution_jvp_rot_device", dX, dP, dLamG, dDirP, nullptr, k, dDX, dSens, stream, dDirModel, nullptr, dDirRot, nullptr);
+}
+
+int cmpc_solution_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP,
+                                 double* dGradModel, double* dGradRot, float* dSens, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradX) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_rot_device: null argument");
+    if (!dGradP && !dGradModel && !dGradRot) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_rot_device: no output requested");
+    return sensitivity(h, "cmpc_solution_vjp_rot_device", dX, dP, dLamG, nullptr, dGradX, 1, dGradP, dSens, stream, nullptr, dGradModel, nullptr, dGradRot);
+}
+
+int cmpc_rotation_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradRot, void* stream)
+{
+    if (!h || !dX || !dP || !dLamG || !dGradRot) return fail(h, CMPC_ERR_ARG, "cmpc_rotation_value_gradient_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    CmpcParams p;
+    fill_params(h, p);
+    int rc = cmpc_launch_rotation_value_gradient(&p, dX, dP, dLamG, dGradRot, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("rotation value gradient launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_contacts_rotation_vjp_device(cmpc_handle h, int max_contacts, double now, const double* dT, const int* dN, const double* dGradRot,
+                                      double* dGradListRot, void* stream)
+{
+    if (!h || max_contacts < 1 || !dT || !dN || !dGradRot || !dGradListRot) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_rotation_vjp_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_contacts_rotation_vjp(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, dT, dN, dGradRot, dGradListRot,
+                                               stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact rotation adjoint launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
 }
 

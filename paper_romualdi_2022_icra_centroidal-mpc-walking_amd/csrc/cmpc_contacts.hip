@@ -170,6 +170,29 @@ __global__ __launch_bounds__(128) void cmpc_contacts_position_vjp_kernel(int B, 
     }
 }
 
+// Adjoint of the sampling in the contacts' ORIENTATIONS (include/cmpc.h, cmpc_contacts_rotation_vjp_device): a sampled stage copies its owner's rotation, so
+// in the body-frame tangent omega_stage = omega_owner and entry m receives the sum of g_rot over the stages it owns.  One thread per (problem, foot), the
+// float64 sum in stage order k = 0 .. N-1 with the forward's own cmpc_stage_owner: no atomics, a fixed order.  Entries at or beyond n carry none; a foot
+// that the sampling would not sample (empty list, or longer than M) gets zeros.
+__global__ __launch_bounds__(128) void cmpc_contacts_rotation_vjp_kernel(int B, int N, int M, double dt, double now, const double* __restrict__ list_t,
+                                                                         const int* __restrict__ list_n, const double* __restrict__ g_rot,
+                                                                         double* __restrict__ g_list)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;   // problem * 2 + foot
+    if (e >= 2 * B) return;
+    const size_t o = (size_t)e * M;
+    double* out = g_list + 3 * o;
+    for (int m = 0; m < 3 * M; ++m) out[m] = 0.0;
+    const int n = list_n[e];
+    if (n < 1 || n > M) return;
+    const double* g = g_rot + (size_t)e * 3 * N;
+    for (int k = 0; k < N; ++k) {
+        bool act;
+        const int m = cmpc_stage_owner(list_t + 2 * o, n, now + k * dt, &act);
+        for (int i = 0; i < 3; ++i) out[3 * m + i] += g[3 * k + i];
+    }
+}
+
 // measured state (and external wrench) into the parameter rows of every problem: setState on the device
 __global__ __launch_bounds__(128) void cmpc_write_state_kernel(int B, int N, const float* __restrict__ state, const float* __restrict__ wrench,
                                                                float* __restrict__ P)
@@ -254,5 +277,12 @@ extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt,
 {
     hipLaunchKernelGGL(cmpc_contacts_position_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, phase, snap_dt_ns, plan_t, plan_n,
                        prev_t, prev_n, list_t, list_n, land, ok, g_out, g_p, g_x, g_prev, g_plan, status);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_contacts_rotation_vjp(int B, int N, int M, double dt, double now, const double* list_t, const int* list_n, const double* g_rot,
+                                                 double* g_list, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_contacts_rotation_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, list_t, list_n, g_rot, g_list);
     return (int)hipGetLastError();
 }

@@ -833,6 +833,79 @@ __global__ __launch_bounds__(256) void cmpc_model_value_gradient_kernel(CmpcPara
     }
 }
 
+// dV*/domega_{c,k} = lam^T d_omega g (axis a) for the rotation direction dR_{c,k} = R_{c,k} [omega]x (include/cmpc.h, "rotation directions"; f does not
+// depend on R).  g is linear in R's entries, so the row's derivative is the row itself with R [e_a]x in R's place: the angular-momentum rows through
+// the lever arm, -dt gam (R (e_a x cn)) x f; the friction rows, al . (R^T f x e_a); the box rows (every stage: stance rows carry lam = 0 under the
+// export convention), -(e_a x R^T (pos_{k+1} - nom_{k+1}))
+template <typename T>
+__device__ inline T nlp_rot_grad(const NlpView& V, int c, int k, int a)
+{
+    const CmpcConsts& K = V.K;
+    const CmpcIdx& L = V.L;
+    const GLay& G = V.G;
+    const float *x = V.x, *p = V.p, *lam = V.lam;
+    const float* R = p + L.pR(c) + 9 * k;   // column-major: R(r, m) = R[3 m + r]
+    T ea[3] = {T(0), T(0), T(0)};
+    ea[a] = T(1);
+    T v = T(0);
+    T lh[3];
+    for (int i = 0; i < 3; ++i) lh[i] = T(lam[G.g_h + 3 * k + i]);
+    for (int j = 0; j < 4; ++j) {
+        const float* cn = K.corners + 12 * c + 3 * j;
+        const float* fp = x + L.oF(c, j) + 3 * k;
+        const T f[3] = {T(fp[0]), T(fp[1]), T(fp[2])};
+        const T cnT[3] = {T(cn[0]), T(cn[1]), T(cn[2])};
+        T wc[3], rw[3], fl[3], flw[3];
+        for (int i = 0; i < 3; ++i) wc[i] = crossc(ea, cnT, i);
+        for (int i = 0; i < 3; ++i) rw[i] = T(R[i]) * wc[0] + T(R[3 + i]) * wc[1] + T(R[6 + i]) * wc[2];
+        for (int i = 0; i < 3; ++i) v -= lh[i] * T(K.dt) * T(V.gam(c, k)) * crossc(rw, f, i);
+        for (int m = 0; m < 3; ++m) fl[m] = T(R[3 * m]) * f[0] + T(R[3 * m + 1]) * f[1] + T(R[3 * m + 2]) * f[2];
+        for (int i = 0; i < 3; ++i) flw[i] = crossc(fl, ea, i);
+        const float* lf = lam + G.g_fric[c] + 16 * k + 4 * j;
+        for (int face = 0; face < 4; ++face) {
+            const T sx = (face == 0 || face == 3) ? T(1) : T(-1), sy = face < 2 ? T(1) : T(-1);
+            v += T(lf[face]) * (sx * flw[0] + sy * flw[1] - T(K.mu_fr) * flw[2]);
+        }
+    }
+    T q[3];
+    for (int i = 0; i < 3; ++i) {
+        q[i] = T(0);
+        for (int r = 0; r < 3; ++r) q[i] += T(R[3 * i + r]) * (T(x[L.oPos(c) + 3 * (k + 1) + r]) - T(p[L.pNom(c) + 3 * (k + 1) + r]));
+    }
+    for (int i = 0; i < 3; ++i) v -= T(lam[G.g_bbox[c] + 3 * k + i]) * crossc(ea, q, i);
+    return v;
+}
+
+// ---- dV*/domega of the stage rotations at (x, lam_g) (envelope theorem), double arithmetic, one workgroup per problem, one item per (foot, stage, axis):
+// out[2][N][3].  A record whose model broke the model rule gets zeros. ----
+__global__ __launch_bounds__(256) void cmpc_rotation_value_gradient_kernel(CmpcParams kp, const float* __restrict__ X, const float* __restrict__ P,
+                                                                           const float* __restrict__ LamG, double* __restrict__ GradR)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, NT = 256;
+    const int b = blockIdx.x;
+    const int N = kp.N;
+    CmpcConsts& K = *reinterpret_cast<CmpcConsts*>(smem);
+    {
+        const int* src = reinterpret_cast<const int*>(kp.kc_per_problem ? kp.kc + b : kp.kc);
+        int* dst = reinterpret_cast<int*>(smem);
+        for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += NT) dst[e] = src[e];
+    }
+    const CmpcIdx L{N};
+    GLay G;
+    glay_init(G, N);
+    float* x = reinterpret_cast<float*>(smem + ((sizeof(CmpcConsts) + 15) & ~15));
+    float* p = x + ((L.nx() + 3) & ~3);
+    float* lam = p + ((L.np() + 3) & ~3);
+    for (int e = tid; e < L.nx(); e += NT) x[e] = X[(size_t)b * L.nx() + e];
+    for (int e = tid; e < L.np(); e += NT) p[e] = P[(size_t)b * L.np() + e];
+    for (int e = tid; e < L.ng(); e += NT) lam[e] = LamG[(size_t)b * L.ng() + e];
+    __syncthreads();
+    double* out = GradR + (size_t)b * 6 * N;
+    const NlpView V{K, L, G, x, p, lam};
+    for (int e = tid; e < 6 * N; e += NT) out[e] = K.model_bad ? 0.0 : nlp_rot_grad<double>(V, e / (3 * N), (e / 3) % N, e % 3);
+}
+
 // warm start: previous solution shifted by one knot (last knot repeated); is_warm_start_enabled of
 // the reference (ergoCubGazeboV1/centroidal_mpc.ini:9)
 // (one problem: xp -> x0, thread tid of nt)
@@ -1036,6 +1109,13 @@ extern "C" int cmpc_launch_model_value_gradient(const CmpcParams* prm, const flo
 {
     const size_t lds = nlp_lds_bytes(prm->N) + sizeof(double) * CMPC_MODEL_DOUBLES * (size_t)(prm->N + 1);
     hipLaunchKernelGGL(cmpc_model_value_gradient_kernel, dim3(prm->B), dim3(256), lds, stream, *prm, dX, dP, dLamG, dGradModel);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_rotation_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradRot,
+                                                   hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_rotation_value_gradient_kernel, dim3(prm->B), dim3(256), nlp_lds_bytes(prm->N), stream, *prm, dX, dP, dLamG, dGradRot);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,8 @@
 //      unshifted operator, then one pass that measures the relative residual.
 // Model directions (include/cmpc.h, "model directions"): the per-problem model theta adds right-hand-side terms (model_q / model_r / model_c) to the
 // JVP's columns, and the VJP contracts the same entries with its stored adjoint into 34 sums per problem (model_vjp).
+// Rotation directions (include/cmpc.h, "rotation directions"): one omega per foot and stage moves R along R [omega]x; rot_r / rot_c add its terms to the
+// JVP's columns, and the VJP contracts the same entries with its stored adjoint into 6 N sums per problem (rot_vjp).
 // No atomics: every reduction is a fixed tree or one thread's loop, so a problem's result depends on nothing but its own inputs.
 #include "cmpc_device.h"
 
@@ -430,6 +432,127 @@ __host__ __device__ inline void model_rx_knot(const Prob& P, int k, const MDir& 
     nr = s; rr = q;
 }
 
+// ---- the stage rotations as a direction (include/cmpc.h, "rotation directions") ----
+// omega[2][N][3] moves R_{c,k} along dR = R [omega_{c,k}]x.  Every term of the NLP is linear in R's entries, so these are exact.  No state entry (q):
+// f does not depend on R, and the lever arm R cn + pos - com enters grad_x L on pos / com through f x lam_h alone.
+struct RDir {
+    const double* d;   // the caller's omega[2][N][3] (t < 0)
+    int t;             // or the unit vector of entry t = 3 (c N + k) + a
+    __host__ __device__ void get(int N, int c, int k, double* w) const
+    {
+        const int o = 3 * (c * N + k);
+        for (int a = 0; a < 3; ++a) w[a] = t >= 0 ? (o + a == t ? 1.0 : 0.0) : d[o + a];
+    }
+};
+
+__host__ __device__ inline void cross3(const double* a, const double* b, double* o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// r entry i (control, 30) of stage k < N.  Forces: the lever arm in the angular-momentum rows, -dt gam (lam_h x R (omega x cn)); the friction rows
+// g = al . R^T f (al = (sx, sy, -mu)) through lam, R (omega x al), and through their Sigma, d g = al . (R^T f x omega) -- swing feet's rows too.
+// Free landing offsets: the stage form lands a swing foot at nom + R^-T q and d(R^-T) = R^-T [omega]x, so the position costate R^-T^T lam_pos = -lam_box
+// (stationarity in q at the returned point) leaves omega x lam_box
+__host__ __device__ inline double rot_r(const Prob& P, int k, int i, const RDir& d)
+{
+    const CmpcConsts& K = *P.K;
+    const CmpcIdx& L = P.L;
+    const int c = i < 24 ? i / 12 : (i - 24) / 3;
+    double w[3];
+    d.get(L.N, c, k, w);
+    if (w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0) return 0.0;
+    if (i >= 24) {
+        const int a = (i - 24) % 3;
+        if (!(P.p[L.pGam(c) + k] < 0.5f) || !((P.p[L.pUp(c) + 3 * k + a] - P.p[L.pLo(c) + 3 * k + a]) > 1e-9f)) return 0.0;
+        const int a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+        return w[a1] * (double)P.lam[P.gbox[c] + 3 * k + a2] - w[a2] * (double)P.lam[P.gbox[c] + 3 * k + a1];
+    }
+    const int j = (i % 12) / 3, a = i % 3, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+    const double gm = P.p[L.pGam(c) + k], dt = K.dt, mu = K.mu_fr;
+    double R[9], f[3], fl[3], flw[3], cn[3], wc[3], lh[3];
+    stage_R(P, c, k, R);
+    for (int m = 0; m < 3; ++m) { f[m] = P.x[L.oF(c, j) + 3 * k + m]; cn[m] = K.corners[12 * c + 3 * j + m]; lh[m] = P.lam[P.gh + 3 * k + m]; }
+    for (int m = 0; m < 3; ++m) fl[m] = R[m] * f[0] + R[3 + m] * f[1] + R[6 + m] * f[2];   // R^T f
+    cross3(fl, w, flw);
+    cross3(w, cn, wc);
+    double rw1 = 0.0, rw2 = 0.0;   // (R (omega x cn)) at a1, a2
+    for (int m = 0; m < 3; ++m) { rw1 += R[3 * a1 + m] * wc[m]; rw2 += R[3 * a2 + m] * wc[m]; }
+    double v = -dt * gm * (lh[a1] * rw2 - lh[a2] * rw1);
+    for (int face = 0; face < 4; ++face) {
+        const double al[3] = {(face == 0 || face == 3) ? 1.0 : -1.0, (face < 2) ? 1.0 : -1.0, -mu};
+        double wa[3], gv = 0.0, dg = 0.0, ra = 0.0, rwa = 0.0;
+        cross3(w, al, wa);
+        for (int m = 0; m < 3; ++m) { gv += al[m] * fl[m]; dg += al[m] * flw[m]; ra += R[3 * a + m] * al[m]; rwa += R[3 * a + m] * wa[m]; }
+        const double l = P.lam[P.gfric[c] + 16 * k + 4 * j + face];
+        const double sg = fmax(l, 0.0) / fmax(-gv, SENS_SMIN);   // Sigma of the row, as build_geo
+        v += l * rwa + sg * ra * dg;
+    }
+    return v;
+}
+
+// c entry e (39) of stage k < N: the lever arms in the angular-momentum dynamics, dt gam (R (omega x cn)) x f, and a swing foot's landing
+// nom + R^-T q at the returned q = R^T (pos_{k+1} - nom_{k+1}): R^-T (omega x q), free and fixed components alike
+__host__ __device__ inline double rot_c(const Prob& P, int k, int e, const RDir& d)
+{
+    if (e < 6 || e >= 15) return 0.0;
+    const CmpcConsts& K = *P.K;
+    const CmpcIdx& L = P.L;
+    if (e < 9) {
+        const int a = e - 6, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+        const double dt = K.dt;
+        double v = 0.0;
+        for (int c = 0; c < 2; ++c) {
+            double w[3], R[9];
+            d.get(L.N, c, k, w);
+            if (w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0) continue;
+            stage_R(P, c, k, R);
+            const double gm = P.p[L.pGam(c) + k];
+            for (int j = 0; j < 4; ++j) {
+                const float* f = P.x + L.oF(c, j) + 3 * k;
+                double cn[3], wc[3], rw1 = 0.0, rw2 = 0.0;
+                for (int m = 0; m < 3; ++m) cn[m] = K.corners[12 * c + 3 * j + m];
+                cross3(w, cn, wc);
+                for (int m = 0; m < 3; ++m) { rw1 += R[3 * a1 + m] * wc[m]; rw2 += R[3 * a2 + m] * wc[m]; }
+                v += dt * gm * (rw1 * (double)f[a2] - rw2 * (double)f[a1]);
+            }
+        }
+        return v;
+    }
+    const int c = (e - 9) / 3, a = (e - 9) % 3;
+    if (!(P.p[L.pGam(c) + k] < 0.5f)) return 0.0;
+    double w[3], R[9], q[3], wq[3], cof[3];
+    d.get(L.N, c, k, w);
+    if (w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0) return 0.0;
+    stage_R(P, c, k, R);
+    for (int i = 0; i < 3; ++i) {
+        q[i] = 0.0;
+        for (int r = 0; r < 3; ++r) q[i] += R[3 * r + i] * ((double)P.x[L.oPos(c) + 3 * (k + 1) + r] - (double)P.p[L.pNom(c) + 3 * (k + 1) + r]);
+    }
+    cross3(w, q, wq);
+    // row a of R^-T = cof(R) / det(R) (as build_geo)
+    const int r1 = (a + 1) % 3, r2 = (a + 2) % 3;
+    for (int cc = 0; cc < 3; ++cc) {
+        const int c1 = (cc + 1) % 3, c2 = (cc + 2) % 3;
+        cof[cc] = R[3 * r1 + c1] * R[3 * r2 + c2] - R[3 * r1 + c2] * R[3 * r2 + c1];
+    }
+    const double det = R[3 * a] * cof[0] + R[3 * a + 1] * cof[1] + R[3 * a + 2] * cof[2];
+    return (cof[0] * wq[0] + cof[1] * wq[1] + cof[2] * wq[2]) / det;
+}
+
+// stage k's share of a rotation right-hand side's primal block r_x in the NLP's x layout, with both feet in stance over the whole horizon (the only
+// case with an internal-force direction: no landing offsets, r_x sits on the force columns): sum of n r_x (n: e3 scaled as internal_dir) and of r_x^2
+__host__ __device__ inline void rot_rx_stage(const Prob& P, int k, const RDir& d, const double* e3, double& nr, double& rr)
+{
+    double s = 0.0, q = 0.0;
+    for (int i = 0; i < 24; ++i) {
+        const double v = rot_r(P, k, i, d);
+        q += v * v;
+        s += (i < 12 ? e3[i % 3] : -e3[i % 3]) * v;
+    }
+    nr = s; rr = q;
+}
+
 // a JVP direction's row of dp, or zeros (dDirP == NULL)
 struct PDir {
     const float* d;
@@ -442,7 +565,8 @@ struct Rhs {
     const float* dir;  // mode 0: [KC][np] rows of this chunk (stride np); mode 1: [nx]
     long long stride;
     const double* dmod;   // mode 0: [KC][34] model directions of this chunk, or null
-    const double* proj;   // with dmod: e3 (3, as internal_dir) then the KC components n^T r_x removed from the columns' force entries; null: none
+    const double* drot;   // mode 0: [KC][2][N][3] rotation directions of this chunk, or null
+    const double* proj;   // with dmod or drot: e3 (3, as internal_dir) then the KC components n^T r_x removed from the columns' force entries; null: none
 };
 
 // (q_k, r_k, c_k) of column j, written to q[39], r[30], c[39]; k == N: q only.  x0 (k == 0 only, if non-null): the initial state
@@ -478,6 +602,7 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
                     }
                 }
                 if (R.dmod) cv += model_c(P, k, e, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
+                if (R.drot) cv += rot_c(P, k, e, RDir{R.drot + (size_t)j * 6 * N, -1});
                 c[e] = cv;
             }
             if (R.dmod) q[e] = qv + model_q(P, k, e, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
@@ -488,10 +613,9 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
                 const int cc = (i - 24) / 3, a = (i - 24) % 3;
                 if (g.qm[cc][a] == 1) rv = -(g.sU[cc][a] * d[L.pUp(cc) + 3 * k + a] + g.sL[cc][a] * d[L.pLo(cc) + 3 * k + a]);
             }
-            if (R.dmod) {
-                rv += model_r(P, k, i, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
-                if (R.proj && i < 24) rv -= R.proj[3 + j] * (i < 12 ? R.proj[i % 3] : -R.proj[i % 3]);   // (no component along n)
-            }
+            if (R.dmod) rv += model_r(P, k, i, MDir{R.dmod + j * CMPC_MODEL_DOUBLES, -1});
+            if (R.drot) rv += rot_r(P, k, i, RDir{R.drot + (size_t)j * 6 * N, -1});
+            if (R.proj && i < 24) rv -= R.proj[3 + j] * (i < 12 ? R.proj[i % 3] : -R.proj[i % 3]);   // (no component along n)
             r[i] = rv;
         }
     } else {
@@ -969,10 +1093,69 @@ __host__ __device__ inline void model_jvp_proj(const Team& T, const Prob& P, con
     rel = fmax(rel, team_max(T, r));   // (team_max synchronises: proj is complete for every thread)
 }
 
+// the rotation part of one problem's VJP after its adjoint solve (W column 0): grot[c][k][a] = -w^T r of the unit direction, one item per (foot, stage,
+// axis), each a fixed-order loop over the foot's 12 + 3 control entries and the stage's 9 dynamics entries.  With the internal-force direction e3 (else null) every r loses
+// its component along n, as model_vjp's do, and the largest relative component goes to rel.
+__host__ __device__ inline void rot_vjp(const Team& T, const Prob& P, const Ws& W, const double* e3, double* grot, double& rel, double& nonfinite)
+{
+    const int N = P.L.N;
+    const double* ls = W.ls(0);
+    const double* us = W.us(0);
+    double nw = 0.0;
+    if (e3)   // n^T w over the force entries u_k (one thread's loop, the same order in every thread)
+        for (int k = 0; k < N; ++k)
+            for (int i = 0; i < 24; ++i) nw += (i < 12 ? e3[i % 3] : -e3[i % 3]) * us[k * SU + i];
+    double r = 0.0;
+    for (int e = T.tid; e < 6 * N; e += T.nt) {
+        const int c = e / (3 * N), k = (e / 3) % N;
+        const RDir d{nullptr, e};
+        double v = 0.0, nr = 0.0, rr = 0.0;
+        for (int i = 12 * c; i < 12 * c + 12; ++i) {   // (the other foot's entries of a one-foot direction are zero) each r once: contraction, n^T r, |r|^2
+            const double rv = rot_r(P, k, i, d);
+            v += us[k * SU + i] * rv;
+            if (e3) nr += (c == 0 ? e3[i % 3] : -e3[i % 3]) * rv;
+            rr += rv * rv;
+        }
+        for (int i = uQ(c); i < uQ(c) + 3; ++i) v += us[k * SU + i] * rot_r(P, k, i, d);
+        for (int i = 6; i < 15; ++i) v += ls[(k + 1) * SX + i] * rot_c(P, k, i, d);
+        if (e3) {
+            v -= nw * nr;
+            if (rr > 0.0) r = fmax(r, fabs(nr) / sqrt(rr));
+        }
+        grot[e] = -v;
+        if (!__builtin_isfinite(v)) nonfinite = 1.0;
+    }
+    rel = fmax(rel, team_max(T, r));
+}
+
+// the JVP's rotation columns of one chunk before its passes: n^T r_x of column j's rotation direction joins proj[3 + j] (add: the model part is
+// there already), and the largest relative size |n^T r_x| / |r_x| over the chunk joins rel.  part: 2 x KC N doubles of free LDS.
+__host__ __device__ inline void rot_jvp_proj(const Team& T, const Prob& P, const double* drot, int nc, bool add, double* proj, double* part, double& rel)
+{
+    const int N = P.L.N;
+    for (int e = T.tid; e < nc * N; e += T.nt) {
+        const int j = e / N, k = e % N;
+        double nr, rr;
+        rot_rx_stage(P, k, RDir{drot + (size_t)j * 6 * N, -1}, proj, nr, rr);
+        part[e] = nr;
+        part[SENS_KC * N + e] = rr;
+    }
+    SENS_SYNC();
+    double r = 0.0;
+    for (int j = T.tid; j < nc; j += T.nt) {
+        double nr = 0.0, rr = 0.0;
+        for (int k = 0; k < N; ++k) { nr += part[j * N + k]; rr += part[SENS_KC * N + j * N + k]; }
+        proj[3 + j] = add ? proj[3 + j] + nr : nr;
+        if (rr > 0.0) r = fmax(r, fabs(nr) / sqrt(rr));
+    }
+    rel = fmax(rel, team_max(T, r));   // (team_max synchronises: proj is complete for every thread)
+}
+
 // ---- one problem: JVP (gx == null: k directions dir[k][np] (and dmod[k][34], or null) -> out[k][nx]) or VJP (gx[nx] -> out[np] (or null) and
-// gmod[34] (or null)) ----
+// gmod[34] (or null)); drot[k][2][N][3] (or null) joins the JVP's columns, grot[2][N][3] (or null) comes from the VJP's one adjoint solve ----
 __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, const Prob& P, const Ws& W, const Lds& S, const float* dir, const float* gx, int kdir,
-                                            float* out, float* sens, float* vproj, const double* dmod, double* gmod, double* proj)
+                                            float* out, float* sens, float* vproj, const double* dmod, double* gmod, double* proj,
+                                            const double* drot, double* grot)
 {
     const CmpcIdx& L = P.L;
     const int N = L.N;
@@ -988,6 +1171,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     if (vjp) { for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(gx[e])) flag2 = 1.0; }
     else if (dir) { for (long long e = T.tid; e < (long long)kdir * L.np(); e += T.nt) if (!__builtin_isfinite(dir[e])) flag2 = 1.0; }
     if (dmod) for (int e = T.tid; e < kdir * CMPC_MODEL_DOUBLES; e += T.nt) if (!__builtin_isfinite(dmod[e])) flag2 = 1.0;
+    if (drot) for (int e = T.tid; e < kdir * 6 * N; e += T.nt) if (!__builtin_isfinite(drot[e])) flag2 = 1.0;
     flag3 = team_max(T, flag3);
     flag2 = team_max(T, flag2);
     double status = flag3 > 0.0 ? 3.0 : (flag2 > 0.0 ? 2.0 : 0.0);
@@ -1001,7 +1185,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     double nonfinite = 0.0, mrel = 0.0;
     if (status == 0.0) {
         Rhs R;
-        R.dmod = nullptr; R.proj = nullptr;
+        R.dmod = nullptr; R.drot = nullptr; R.proj = nullptr;
         int nchunks = 1;
         if (vjp) {   // v with no component along the internal-force direction
             double s = 0.0;
@@ -1018,7 +1202,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
         } else {
             R.mode = 0; R.stride = L.np();
             nchunks = (kdir + SENS_KC - 1) / SENS_KC;
-            if (dmod && has_e) {   // the model columns lose their component along n: e3 first, then one n^T r_x per column
+            if ((dmod || drot) && has_e) {   // the model and rotation columns lose their component along n: e3 first, then one n^T r_x per column
                 if (T.tid == 0) for (int i = 0; i < 3; ++i) proj[i] = e3[i];
                 SENS_SYNC();
                 R.proj = proj;
@@ -1029,7 +1213,9 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
             if (!vjp) {
                 R.dir = dir ? dir + (size_t)ch * SENS_KC * L.np() : nullptr;
                 R.dmod = dmod ? dmod + (size_t)ch * SENS_KC * CMPC_MODEL_DOUBLES : nullptr;
-                if (R.proj) model_jvp_proj(T, P, R.dmod, nc, proj, S.P, mrel);
+                R.drot = drot ? drot + (size_t)ch * SENS_KC * 6 * N : nullptr;
+                if (R.proj && R.dmod) model_jvp_proj(T, P, R.dmod, nc, proj, S.P, mrel);
+                if (R.proj && R.drot) rot_jvp_proj(T, P, R.drot, nc, R.dmod != nullptr, proj, S.P, mrel);
             }
             double rn = 0.0, bn = 0.0;
             chunk_pass(T, P, W, S, R, nc, 0, rn, bn);
@@ -1136,6 +1322,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
                 }
                 SENS_SYNC();
                 if (gmod) model_vjp(T, P, W, has_e ? e3 : nullptr, S.P, gmod, mrel, nonfinite);
+                if (grot) rot_vjp(T, P, W, has_e ? e3 : nullptr, grot, mrel, nonfinite);
             }
         }
         if (!__builtin_isfinite(resid)) nonfinite = 1.0;
@@ -1145,6 +1332,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     if (status != 0.0) {
         for (long long e = T.tid; e < nout; e += T.nt) out[e] = 0.f;
         if (gmod) for (int e = T.tid; e < CMPC_MODEL_DOUBLES; e += T.nt) gmod[e] = 0.0;
+        if (grot) for (int e = T.tid; e < 6 * N; e += T.nt) grot[e] = 0.0;
         resid = 0.0;
         mrel = 0.0;
     }
@@ -1190,7 +1378,8 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
                                                                const float* __restrict__ X, const float* __restrict__ Pp, const float* __restrict__ LamG,
                                                                const float* __restrict__ Dir, const float* __restrict__ GradX, int kdir,
                                                                float* __restrict__ Out, float* __restrict__ Sens, double* __restrict__ Wsp,
-                                                               const double* __restrict__ DirModel, double* __restrict__ GradModel)
+                                                               const double* __restrict__ DirModel, double* __restrict__ GradModel,
+                                                               const double* __restrict__ DirRot, double* __restrict__ GradRot)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -1229,20 +1418,21 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
     float* sens = Sens ? Sens + (size_t)b * CMPC_SENS : nullptr;
     if (GradX)
         sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * L.nx(), 1, Out ? Out + (size_t)b * L.np() : nullptr, sens, vproj, nullptr,
-                     GradModel ? GradModel + (size_t)b * CMPC_MODEL_DOUBLES : nullptr, proj);
+                     GradModel ? GradModel + (size_t)b * CMPC_MODEL_DOUBLES : nullptr, proj, nullptr, GradRot ? GradRot + (size_t)b * 6 * N : nullptr);
     else
         sens_problem(T, P, W, S, Dir ? Dir + (size_t)b * kdir * L.np() : nullptr, nullptr, kdir, Out + (size_t)b * kdir * L.nx(), sens, vproj,
-                     DirModel ? DirModel + (size_t)b * kdir * CMPC_MODEL_DOUBLES : nullptr, nullptr, proj);
+                     DirModel ? DirModel + (size_t)b * kdir * CMPC_MODEL_DOUBLES : nullptr, nullptr, proj,
+                     DirRot ? DirRot + (size_t)b * kdir * 6 * N : nullptr, nullptr);
 }
 
 // workspace bytes per problem of the launch below
 extern "C" size_t cmpc_sensitivity_workspace_bytes(int N) { return sizeof(double) * (size_t)Ws::doubles(N); }
 
 // problems [b0, b0 + nb) of the batch; the workspace holds nb problems.  JVP (dGradX null): dDir and dDirModel (each may be null), dOut = dx.
-// VJP: dOut = dl/dp (or null), dGradModel = dl/dtheta (or null).
+// VJP: dOut = dl/dp (or null), dGradModel = dl/dtheta (or null), dGradRot = dl/domega (or null).  dDirRot: the JVP's rotation directions (or null).
 extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
                                        const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
-                                       double* dGradModel, hipStream_t stream)
+                                       double* dGradModel, const double* dDirRot, double* dGradRot, hipStream_t stream)
 {
     const size_t lds = sens_lds_bytes(N);
     static int configured = 0;
@@ -1252,6 +1442,6 @@ extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem,
         configured = 1;
     }
     hipLaunchKernelGGL(cmpc_sensitivity_kernel, dim3(nb), dim3(SENS_NT), lds, stream, kc, kc_per_problem, N, b0, dX, dP, dLamG, dDir, dGradX, kdir, dOut,
-                       dSens, dWs, dDirModel, dGradModel);
+                       dSens, dWs, dDirModel, dGradModel, dDirRot, dGradRot);
     return (int)hipGetLastError();
 }

@@ -361,6 +361,87 @@ class BatchSolver:
                                                                                       out.data_ptr(), st))
         return out
 
+    # ---- derivatives with respect to the stage rotations (include/cmpc.h, "rotation directions") ----
+    def solution_jvp_rot_device(self, dX, dP, dLamG, dDirP=None, dDirModel=None, dDirRot=None, out=None, sens=None):
+        """dx*/d(p, theta, omega) applied to k directions: dDirP[B, k, n_p] float32, dDirModel[B, k, 34] float64 and dDirRot[B, k, 2, N, 3] float64
+        (omega moves R_{c,k} along R [omega]x; any may be None: zero) -> (dDX[B, k, n_x], sens[B, CMPC_SENS]).  sens[:, 6]: the largest relative
+        component of the model and rotation right-hand sides along the internal-force direction that was removed.  dDirRot None gives
+        solution_jvp_model_device's result bit for bit."""
+        import torch
+        L = self.layout
+        shapes = ((dDirP, torch.float32, (L.np,)), (dDirModel, torch.float64, (_capi.MODEL_DOUBLES,)), (dDirRot, torch.float64, (2, L.N, 3)))
+        ks = set()
+        for t, dt, tail in shapes:
+            if t is not None:
+                assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == 2 + len(tail)
+                assert t.shape[0] == self.batch and tuple(t.shape[2:]) == tail and t.shape[1] >= 1
+                ks.add(int(t.shape[1]))
+        assert len(ks) == 1, "solution_jvp_rot_device: no direction, or directions of different k"
+        k = ks.pop()
+        if out is None:
+            out = torch.empty((self.batch, k, L.nx), dtype=torch.float32, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, k, L.nx) and out.dtype == torch.float32
+        pp, pm, pr = (t.data_ptr() if t is not None else None for t in (dDirP, dDirModel, dDirRot))
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_jvp_rot_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                         pp, pm, pr, k, out.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_jvp_rot_device")
+        return out, sens
+
+    def solution_vjp_rot_device(self, dX, dP, dLamG, dGradX, out_rot=None, out_model=None, out_p=None, sens=None, grad_p=True, grad_model=True):
+        """(dx*/d(p, theta, omega))^T v from one adjoint solve: dGradX[B, n_x] = dl/dx -> (dl/domega [B, 2, N, 3] float64, dl/dtheta [B, 34]
+        float64 or None, dl/dp [B, n_p] float32 or None, sens[B, CMPC_SENS]).  dl/dp and dl/dtheta equal solution_vjp_model_device's bit for bit."""
+        import torch
+        L = self.layout
+        assert dGradX.is_cuda and dGradX.dtype == torch.float32 and dGradX.is_contiguous() and tuple(dGradX.shape) == (self.batch, L.nx)
+        if out_rot is None:
+            out_rot = torch.empty((self.batch, 2, L.N, 3), dtype=torch.float64, device=dX.device)
+        assert out_rot.is_contiguous() and tuple(out_rot.shape) == (self.batch, 2, L.N, 3) and out_rot.dtype == torch.float64
+        if grad_model and out_model is None:
+            out_model = torch.empty((self.batch, _capi.MODEL_DOUBLES), dtype=torch.float64, device=dX.device)
+        if out_model is not None:
+            assert out_model.is_contiguous() and tuple(out_model.shape) == (self.batch, _capi.MODEL_DOUBLES) and out_model.dtype == torch.float64
+        if grad_p and out_p is None:
+            out_p = torch.empty((self.batch, L.np), dtype=torch.float32, device=dX.device)
+        if out_p is not None:
+            assert out_p.is_contiguous() and tuple(out_p.shape) == (self.batch, L.np) and out_p.dtype == torch.float32
+        pp = out_p.data_ptr() if out_p is not None else None
+        pm = out_model.data_ptr() if out_model is not None else None
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_vjp_rot_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                         dGradX.data_ptr(), pp, pm, out_rot.data_ptr(), o.data_ptr(), st),
+                             "cmpc_solution_vjp_rot_device")
+        return out_rot, out_model, out_p, sens
+
+    def rotation_value_gradient_device(self, dX, dP, dLamG, out=None):
+        """dV*/domega [B, 2, N, 3] float64 at a KKT point (x*, lam*): lam^T d_omega g (the cost does not depend on R).  At a double-support point
+        the entries depend on the internal force the solve returned (include/cmpc.h)."""
+        import torch
+        L = self.layout
+        assert tuple(dX.shape) == (self.batch, L.nx) and tuple(dP.shape) == (self.batch, L.np) and tuple(dLamG.shape) == (self.batch, L.ng)
+        for t in (dX, dP, dLamG):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        if out is None:
+            out = torch.empty((self.batch, 2, L.N, 3), dtype=torch.float64, device=dX.device)
+        assert out.is_contiguous() and tuple(out.shape) == (self.batch, 2, L.N, 3) and out.dtype == torch.float64
+        self._launch(dX.device, lambda st: self._lib.cmpc_rotation_value_gradient_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                         out.data_ptr(), st))
+        return out
+
+    def contacts_rotation_vjp_device(self, now, list_t, list_n, dGradRot, out=None):
+        """Per-stage -> per-list-entry (cmpc_contacts_rotation_vjp_device): list_t[B,2,M,2] float64 / list_n[B,2] int32 = the sampled lists,
+        dGradRot[B,2,N,3] float64 -> dGradListRot[B,2,M,3] float64: entry m receives the sum of dGradRot over the stages it owns, in the body-frame
+        tangent of its quaternion (q <- q (x) exp(omega / 2))."""
+        import torch
+        L, B, M, dev = self.layout, self.batch, list_t.shape[2], list_t.device
+        assert list_t.is_cuda and list_t.dtype == torch.float64 and list_t.is_contiguous() and tuple(list_t.shape) == (B, 2, M, 2)
+        if out is None:
+            out = torch.empty((B, 2, M, 3), dtype=torch.float64, device=dev)
+        args = (self._opt(list_n, torch.int32, (B, 2), "list_n"), self._opt(dGradRot, torch.float64, (B, 2, L.N, 3), "dGradRot"),
+                self._opt(out, torch.float64, (B, 2, M, 3), "out"))
+        self._launch(dev, lambda st: self._lib.cmpc_contacts_rotation_vjp_device(self._h, M, float(now), list_t.data_ptr(), *args, st))
+        return out
+
     def workspace_bytes_per_problem(self) -> int:
         """bytes of the sensitivity workspace per problem (cmpc_sensitivity_workspace_bytes)"""
         return int(self._lib.cmpc_sensitivity_workspace_bytes(self.layout.N))
@@ -797,27 +878,60 @@ class CentroidalMPC:
         return X, info
 
 
-def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False, models=None):
+def rotate_parameters(P, rot, N):
+    """P[B, n_p] float32 with every R_{c,k} replaced by float32(R_{c,k} exp([rot_{c,k}]x)) (Rodrigues, float64, on P's device); rot[B, 2, N, 3]
+    float64.  A stage whose rot is zero keeps its bits."""
+    import torch
+    from .layout import Layout
+    L = Layout(N)
+    B = P.shape[0]
+    w = rot.detach().to(torch.float64)
+    th2 = (w * w).sum(-1, keepdim=True)
+    th = th2.sqrt()
+    small = th < 1e-4
+    ths = torch.where(small, torch.ones_like(th), th)
+    a = torch.where(small, 1.0 - th2 / 6.0, torch.sin(ths) / ths)[..., None]
+    b = torch.where(small, 0.5 - th2 / 24.0, (1.0 - torch.cos(ths)) / (ths * ths))[..., None]
+    K = torch.zeros((B, 2, N, 3, 3), dtype=torch.float64, device=P.device)
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0] = -w[..., 2], w[..., 1], w[..., 2]
+    K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -w[..., 0], -w[..., 1], w[..., 0]
+    E = torch.eye(3, dtype=torch.float64, device=P.device) + a * K + b * (K @ K)
+    out = P.clone()
+    moved = (w != 0).any(-1)                                                      # [B, 2, N]
+    for c in range(2):
+        blk = P[:, L.p_R[c]:L.p_R[c] + 9 * N].reshape(B, N, 3, 3)                  # column-major: [.., col, row]
+        Rn = (blk.to(torch.float64).transpose(-1, -2) @ E[:, c]).transpose(-1, -2).to(torch.float32)
+        out[:, L.p_R[c]:L.p_R[c] + 9 * N] = torch.where(moved[:, c, :, None, None], Rn, blk).reshape(B, 9 * N)
+    return out
+
+
+def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False, models=None, rot=None):
     """x*(P) as a torch.autograd.Function: forward solves (solve_device) and keeps (X, P, lam_g); backward returns P.grad by the VJP of
     include/cmpc.h (cmpc_solution_vjp_device) and None for X0.  The multiplier output of `solver` is turned on if it is off (it stays on).
     Problems whose sensitivity status is not 0 get zero rows of P.grad; solver.last_sensitivity_info holds the [B, CMPC_SENS] words of the
     last backward, and solver.last_info the [B, CMPC_INFO] words of the last forward.
     models: None, or a [B, 34] float64 CUDA tensor of per-problem models (cmpc_model's order): forward installs it with set_models_device and
     leaves it installed on `solver` (solver.last_models_ok holds the [B] ok words), and backward returns models.grad from the same adjoint solve
-    (cmpc_solution_vjp_model_device: P.grad is bit for bit that of the models=None path at the same models)."""
+    (cmpc_solution_vjp_model_device: P.grad is bit for bit that of the models=None path at the same models).
+    rot: None, or a [B, 2, N, 3] float64 CUDA tensor of stage rotations: forward solves with R_{c,k} <- float32(R_{c,k} exp([rot_{c,k}]x))
+    (rotate_parameters; rot = 0 leaves P's bits unchanged), and backward fills rot.grad with the rotation VJP (cmpc_solution_vjp_rot_device) at the
+    rotated R.  That is the gradient in the local body-frame tangent at the rotated R -- the usual retraction convention -- and the plain gradient
+    at rot = 0; P.grad (and models.grad) are taken at the rotated P, bit for bit those of the rot=None path there."""
     import torch
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, P, X0, models):
+        def forward(ctx, P, X0, models, rot):
             solver.set_multiplier_output(True)
             if models is not None:
                 solver.last_models_ok = solver.set_models_device(models.detach().contiguous())
             Pc, X0c = P.detach().contiguous(), X0.detach().contiguous()
+            if rot is not None:
+                Pc = rotate_parameters(Pc, rot, solver.layout.N)
             X, info = solver.solve_device(Pc, X0c, warm=warm)
             lam = solver.multipliers_device(X, Pc)
             solver.last_info = info
-            ctx.with_models = models is not None
+            ctx.with_models, ctx.with_rot = models is not None, rot is not None
             ctx.save_for_backward(X, Pc, lam)
             return X
 
@@ -825,12 +939,16 @@ def solve_differentiable(solver: BatchSolver, P, X0, warm: bool = False, models=
         def backward(ctx, gX):
             X, Pc, lam = ctx.saved_tensors
             gX = gX.contiguous().to(torch.float32)
+            if ctx.with_rot:
+                gR, gM, gP, sens = solver.solution_vjp_rot_device(X, Pc, lam, gX, grad_model=ctx.with_models)
+                solver.last_sensitivity_info = sens
+                return gP, None, gM, gR
             if not ctx.with_models:
                 gP, sens = solver.solution_vjp_device(X, Pc, lam, gX)
                 solver.last_sensitivity_info = sens
-                return gP, None, None
+                return gP, None, None, None
             gM, gP, sens = solver.solution_vjp_model_device(X, Pc, lam, gX)
             solver.last_sensitivity_info = sens
-            return gP, None, gM
+            return gP, None, gM, None
 
-    return _Fn.apply(P, X0, models)
+    return _Fn.apply(P, X0, models, rot)

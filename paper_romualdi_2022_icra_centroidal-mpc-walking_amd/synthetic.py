@@ -112,12 +112,9 @@ def config5_footstep_candidates(B=8192, N=30, seed=3):
     return footstep_candidates(_cfg.ergocub_gazebo_v1(N, 0.06), B, seed)
 
 
-def footstep_candidates(cfg, B, seed):
-    """config 5's candidate schedules (yawed footsteps, R != I) at cfg's own horizon, sampling time and weights: the horizon is
-    N x dt long, so a robot with a shorter horizon sees a shortened form of the same schedules."""
-    N = cfg.N
-    rng = np.random.default_rng(seed)
-    dt, t_end = cfg.sampling_time, N * cfg.sampling_time
+def _candidate_lists(cfg, B, rng):
+    """the contact lists of footstep_candidates, drawn from rng (B problems, in order)"""
+    t_end = cfg.N * cfg.sampling_time
     lists = []
     for _ in range(B):  # the random draws only (their order defines the batch); the sampling below is vectorised
         step_T = rng.uniform(0.6, 0.9)
@@ -143,6 +140,20 @@ def footstep_candidates(cfg, B, seed):
                 if a.deactivation_time <= a.activation_time:
                     a.deactivation_time = b.activation_time - (step_T - ds)
         lists.append({cfg.contacts[0].contact_name: feet[True], cfg.contacts[1].contact_name: feet[False]})
+    return lists
+
+
+def footstep_candidate_lists(cfg, B, seed):
+    """the packed contact lists (t[B,2,M,2], pose[B,2,M,7], n[B,2]) that footstep_candidates(cfg, B, seed) samples its schedules from"""
+    return pack_lists(cfg, _candidate_lists(cfg, B, np.random.default_rng(seed)))
+
+
+def footstep_candidates(cfg, B, seed):
+    """config 5's candidate schedules (yawed footsteps, R != I) at cfg's own horizon, sampling time and weights: the horizon is
+    N x dt long, so a robot with a shorter horizon sees a shortened form of the same schedules."""
+    N = cfg.N
+    rng = np.random.default_rng(seed)
+    lists = _candidate_lists(cfg, B, rng)
     sched, _ = sample_schedule_batch(cfg, *pack_lists(cfg, lists))
     sched = {k: v.astype(np.float64) for k, v in sched.items()}
     com0, dcom0, h0 = _perturbed_state(rng, B, (0.0, 0.0, 0.7))
