@@ -187,6 +187,21 @@ __device__ inline float4 lds_ld4(ldsf_t p)
     const v4f v = *reinterpret_cast<__attribute__((address_space(3))) const v4f*>(p);
     return make_float4(v[0], v[1], v[2], v[3]);
 }
+// Four consecutive 16-byte reads issued back to back behind ONE wait.  Left to the scheduler, a consumer that takes the four in turn gets each read behind a full
+// wait of its own, in the same destination registers: four dependent LDS round trips where one is needed.  (The wait inside also orders the reads behind every
+// earlier LDS operation of the wave and fences the compiler: no wave_lds_sync is needed in front of it.)
+__device__ inline void lds_ld4x4(ldsf_t p, float4 (&out)[4])
+{
+    v4f a, b, c, d;
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
+                 : "v"(p)
+                 : "memory");
+    out[0] = make_float4(a[0], a[1], a[2], a[3]);
+    out[1] = make_float4(b[0], b[1], b[2], b[3]);
+    out[2] = make_float4(c[0], c[1], c[2], c[3]);
+    out[3] = make_float4(d[0], d[1], d[2], d[3]);
+}
 
 // ---- access to the per-stage factor records.  LDS in the resident variants.  In the HBM-factor variants they sit in global
 // scratch and go through a buffer descriptor built once per phase from the wave-uniform base (a pointer argument of an
@@ -2223,7 +2238,10 @@ __device__ int riccati_backward(lds_t lds, const Ctx& c, const CmpcConsts& prm, 
 // Matrix operands do not depend on the recursion: they are read at the top of the stage. ----
 // k0 > 0 (tail polish): the sweep starts at stage k0 with ds_k0 = 0 and the force step before it zero.
 // PART 0: the whole of it; 1: the sweep alone (wave 0, no barrier); 2: the barrier and the element-wise part (all threads).
-// The sweep itself (one wave).  A wave executes one instruction of any kind per four cycles, so the sweep is as long as its instruction count: everything that
+// The sweep itself (one wave).  A wave executes one instruction of any kind per four cycles, so the sweep is as long as its instruction count PLUS the LDS round
+// trips it waits out in full (~160 instructions per stage are ~650 cycles of issue against 990 / 1 235 measured: the rest were waits -- the row of y read as four
+// dependent round trips, and the first stage of a trip taking its operands two at a time; tools/lds_wait_census.py shows both, profiles/forward_sweep_lds_waits.txt
+// what removing them gave).  Reads that belong together are issued together and waited for once; everything that
 // does not change from stage to stage -- per-lane operand addresses, role masks -- is set up once; a trip of UNR stages addresses its operands as pointer + immediate
 // and bumps the pointers once; results of lanes without a task go to words of the staging buffer nobody reads instead of being masked off (round 4: 340 -> ~170
 // instructions per stage).
@@ -2365,8 +2383,12 @@ __device__ __forceinline__ void forward_sweep(const Ctx& c, const CmpcConsts& pr
         wave_lds_sync();
         PROF2(21);
         float4 yv[4];
+        if (G) {
+            // (records in HBM: sixteen live registers for y at once push the sweep, held to 168 registers, into 26 more callee-saved ones -- 52 more scratch
+            //  instructions per call; this form keeps its two round trips)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) yv[q] = lds_ld4(yvp + 4 * q);
+            for (int q = 0; q < 4; ++q) yv[q] = lds_ld4(yvp + 4 * q);
+        } else lds_ld4x4(yvp, yv);      // (one round trip for the row of y, not four)
         float wsum;
         {
             // two packed multiply-add chains (v_pk_fma_f32: two lanes' worth per instruction; both operands come in register pairs out of 16-byte loads)
@@ -2414,6 +2436,12 @@ __device__ __forceinline__ void forward_sweep(const Ctx& c, const CmpcConsts& pr
             for (int t = 0; t < 20; ++t) yp[t] += REC_N * n;
 #pragma unroll
             for (int t = 0; t < 4; ++t) upp[t] += REC_N * n;
+            // (opaque again: otherwise the optimiser keeps the stage-k0 pointers and re-adds a trip offset to all 24 at the head of every trip -- 24 more live
+            //  registers there, under which the scheduler takes the first stage's operands two at a time, each pair behind a full wait)
+#pragma unroll
+            for (int t = 0; t < 20; ++t) asm volatile("" : "+v"(yp[t]));
+#pragma unroll
+            for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(upp[t]));
         }
         gr1 += GEO * n; gr2 += GEO * n; gf1 += GEO * n; gf2 += GEO * n; gm0 += n; gm1 += n; rp += 9 * n; dp += NS * n;
         du0p += NU * n; du1p += NU * n; du2p += NU * n; dqp += NU * n;
