@@ -444,7 +444,8 @@ int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, cons
  * Differentiated inputs: state [9]; from x the knot-0 foot positions pos_c,0 (6) and the knot-0 corner forces f_c,j,0 (24), gated by Gamma_c,0 exactly as
  * the forward gates them (a foot with Gamma_c,0 <= 0.5 has zero force derivatives; its position derivative is then zero too, since no force acts there);
  * from p the wrench of knot 0, fExt_0 and tauExt_0; from the model the 24 corner entries (theta indices 10..33), through R_c,0 corner.
- * NOT differentiated: R and Gamma (as for the solution sensitivities), step, substeps, gravity, and the ZMP output (clipped; an output only).
+ * NOT differentiated by the first pair: R and Gamma (as for the solution sensitivities), step, substeps, gravity, and the ZMP output (clipped; an output
+ * only).  The *_rot_* pair below adds R_c,0.
  * JVP and VJP apply one set of partials (T, F, I, the contact points and the gated forces), forwards and transposed term by term: adjoint by construction.
  * One thread per problem; per-problem models (cmpc_set_models*) apply (a row that broke the model rule uses the config's corners, as the forward does);
  * results depend on nothing but the problem's own inputs.  No status word: non-finite inputs give non-finite outputs.  Device pointers; asynchronous on
@@ -457,6 +458,17 @@ int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, 
  * dGradP[B][n_p] float or NULL (written whole: zero but for fExt_0, tauExt_0), dGradModel[B][34] double or NULL (written whole: entries 0..9 zero). */
 int cmpc_plant_step_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dGradStateOut,
                                double* dGradState, float* dGradX, float* dGradP, double* dGradModel, void* stream);
+/* The same pair with the knot-0 rotations R_c,0 differentiated, in the tangent of the rotation directions above: omega_c in R^3 per foot moves
+ * dR_c,0 = R_c,0 [omega_c]x, R_c,0 the float32 matrix stored in p, not re-orthonormalised.  Only h' depends on R, through the lever arms
+ * pos_c,0 + R_c,0 corner_q:  d h' = T sum_q (R_c,0 (omega_c x corner_q)) x f_q,  so  d h' / d omega_c = T sum_q [f_q]x R_c,0 [corner_q]x  with the forces gated
+ * by Gamma_c,0 as everywhere above (a gated-off foot has zero dGradRot0) and the float32 corners of the problem's model.  The term joins the one set of
+ * partials; JVP and VJP apply it forwards and transposed like the others.  dDirRot0[B][2][3] double (NULL: zero), dGradRot0[B][2][3] double (may be NULL);
+ * with the pointer NULL the results are the first pair's bit for bit (the first pair calls these with NULL). */
+int cmpc_plant_step_jvp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
+                                   const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0, double* dDirStateOut, void* stream);
+int cmpc_plant_step_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
+                                   const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
+                                   void* stream);
 
 /* 8e, the record a Monte-Carlo driver gathers across GPUs (no reference counterpart: the reference runs one problem):
  * dOut[B][3(N+1) + 38] = CoM trajectory 3(N+1) | first-knot corner forces 24 | knot-0 and knot-1 foot positions 12 |
@@ -583,8 +595,8 @@ typedef struct cmpc_tick_io {
 } cmpc_tick_io;
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
- * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated, and of the orientations only the sampling is
- * (cmpc_contacts_rotation_vjp_device, "rotation directions": not the merge, and not through this entry point).  The forward maps move positions
+ * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated; the orientations have their own entry point below
+ * (cmpc_contacts_orientation_vjp_device).  The forward maps move positions
  * through index maps that depend on the contact times only, so the adjoint needs the lists' times and counts, not their poses: the planner's lists, the
  * previous tick's and this tick's merged list as cmpc_rollout_tick_device (or the seven calls) left them, and dLand / dOk of that tick.  The maps are
  * re-derived with the forward's own functions (getActiveContact, getNextContact, the stage owner).  Gradients of list positions are double
@@ -609,6 +621,25 @@ int cmpc_contacts_position_vjp_device(cmpc_handle h, int max_contacts, double no
                                       const double* dGradListOut, const float* dGradP, float* dGradX, double* dGradPrevList, double* dGradPlan, int* dStatus,
                                       void* stream);
 
+/* The orientation counterpart of the sample + merge part, with the same tape arguments.  Gradients are double [B][2][max_contacts][3] in the body-frame
+ * tangent of each entry's quaternion, q <- q (x) exp(omega / 2) (the convention of cmpc_contacts_rotation_vjp_device).  The forward maps copy quaternions,
+ * and in this tangent every copy is the identity: no pose is needed, the index maps come from the times.
+ *   entry gradient: every entry m < n of this tick's list carries dGradListRotOut[c][m] -- NO entry is cut: the step adjustment overwrites positions only, so
+ *     the landing entry's orientation passes through to the next tick.
+ *   sample: entry o receives the sum over the stages k it owns (cmpc_stage_owner) of dGradRot[c][k], in stage order k = 0 .. N-1 -- what
+ *     cmpc_contacts_rotation_vjp_device computes.
+ *   merge: merged entry 0, when the previous list has an active contact ma, sends its gradient to dGradPrevListRot[c][ma]; the entries copied from the planner
+ *     send theirs to dGradPlanRot[c][first + m - n0] (optional, +=).  First tick (dPrevT == dPrevN == NULL): dGradPrevListRot is the list's gradient itself, and
+ *     with dGradListRotOut == NULL it equals cmpc_contacts_rotation_vjp_device's result bit for bit.
+ * dGradPrevListRot is written whole; entries at or beyond n carry nothing; a foot that was not sampled (dLand = -2, an empty list, n > max_contacts) passes
+ * nothing on; dOk[b] == 0 gives zeros, adds nothing to dGradPlanRot and sets dStatus[b] = 5 (else 0; dStatus [B] or NULL); force_sample_time as above.  One
+ * thread per (problem, foot) owns its outputs; float64 sums in the order stated (the entry's own gradient, then the stages); no atomics.  dGradRot
+ * [B][2][N][3] NULL = zero, dGradListRotOut NULL = zero, dLand may be NULL. */
+int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double now, int force_sample_time, const double* dPlanT, const int* dPlanN,
+                                         const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
+                                         const double* dGradListRotOut, const double* dGradRot, double* dGradPrevListRot, double* dGradPlanRot, int* dStatus,
+                                         void* stream);
+
 /* One tick in reverse.  What a forward tick left behind is a tape of read-only device pointers: the tick's solution, parameters and multipliers
  * (cmpc_get_multipliers_device right after that tick's solve, with the multiplier output on -- x and info are bit-identical with it on, so a taped roll-out
  * is bit-identical to an untaped one), the state that went IN (copy it before the tick: a roll-out may alias dState / dStateOut), dInfo, dOk, dLand, the
@@ -624,8 +655,9 @@ int cmpc_contacts_position_vjp_device(cmpc_handle h, int max_contacts, double no
  * dGradP[B][n_p] float or NULL (the tick's full dl/dp: the solve's, plus the plant's on fExt_0 / tauExt_0), dTickSens[B][CMPC_SENS] float: dSens of the
  * solution VJP with word 0 replaced by the tick's status: 0 ok; 1..3 as the solution sensitivities; 4 the solve's status is not 0 (not converged, or flagged);
  * 5 the merge failed (dOk == 0).  Precedence: 5, then 2 and 3 (they speak of the inputs), then 4, then 1.  A flagged problem gets zeros in every array (nothing is added to the += outputs); its
- * neighbours are bit for bit what they are without it.  Workspace: per-handle HBM allocated on first use, 4 (n_x + 2 n_p) + 548 bytes per problem; calls on
- * one handle run one after the other whatever their streams (an event, as for the solution sensitivities). */
+ * neighbours are bit for bit what they are without it.  Workspace: per-handle HBM allocated on first use by whichever of the two tick entry points runs
+ * first, 4 (n_x + 2 n_p) + 48 N + 596 bytes per problem (the rotation entry's arrays, 48 N + 48, included); calls on one handle run one after the other
+ * whatever their streams (an event, as for the solution sensitivities). */
 typedef struct cmpc_tick_tape {
     const float* dX; const float* dP; const float* dLamG;   /* [B][n_x], [B][n_p], [B][n_g] of the tick's solve */
     const float* dState;                                     /* [B][9] the state the tick started from */
@@ -641,6 +673,19 @@ typedef struct cmpc_tick_tape {
 int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
                                  const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
                                  double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, void* stream);
+/* The same tick with the contacts' ORIENTATIONS carried along (the tangents above).  Further arguments: dGradListRotOut[B][2][max_contacts][3] double or NULL
+ * (zero): dl / d(orientations of this tick's outgoing list); dGradPrevListRot[B][2][max_contacts][3] double (written whole; must not alias dGradListRotOut);
+ * dGradPlanRot or NULL (+=); dGradRot[B][2][N][3] double or NULL: the tick's full per-stage dl/domega -- the solve's, plus the plant's dGradRot0 on stage 0.
+ * Chain, on one stream: cmpc_plant_step_vjp_rot_device -> the adjust part -> cmpc_solution_vjp_rot_device (called, not copied: ONE adjoint solve for p, model
+ * and rotations; its dGradP and dGradModel are cmpc_solution_vjp_model_device's bit for bit) -> the combine kernel (also stage 0 += dGradRot0, and zeros in the
+ * rotation arrays of a flagged problem) -> the position sample + merge part -> cmpc_contacts_orientation_vjp_device: one launch more than the entry above.
+ * Every output the entry above also has is bit-identical to it on the same tape.  dTickSens is the rotation VJP's dSens (word 0 replaced as above): words 5
+ * and 6 and the internal-force removal are those of "rotation directions" -- a double-support tick under load has no orientation derivative and says so in
+ * word 6.  Status codes and precedence as above; a flagged problem gets zeros in the rotation outputs and adds nothing to dGradPlanRot. */
+int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                     const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                     double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
+                                     double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream);
 
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */

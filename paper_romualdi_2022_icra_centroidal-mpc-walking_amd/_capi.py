@@ -93,6 +93,7 @@ EXPORTS = [
     "cmpc_sensitivity_workspace_bytes", "cmpc_solution_jvp_model_device", "cmpc_solution_vjp_model_device", "cmpc_model_value_gradient_device",
     "cmpc_plant_step_jvp_device", "cmpc_plant_step_vjp_device", "cmpc_contacts_position_vjp_device", "cmpc_rollout_tick_vjp_device",
     "cmpc_solution_jvp_rot_device", "cmpc_solution_vjp_rot_device", "cmpc_rotation_value_gradient_device", "cmpc_contacts_rotation_vjp_device",
+    "cmpc_plant_step_jvp_rot_device", "cmpc_plant_step_vjp_rot_device", "cmpc_contacts_orientation_vjp_device", "cmpc_rollout_tick_vjp_rot_device",
 ]
 
 _lib = None
@@ -184,6 +185,11 @@ def lib():
         L.cmpc_plant_step_vjp_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp]
         L.cmpc_contacts_position_vjp_device.argtypes = [vp, i, d, i, i] + [vp] * 15
         L.cmpc_rollout_tick_vjp_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 11
+        if hasattr(L, "cmpc_rollout_tick_vjp_rot_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_plant_step_jvp_rot_device.argtypes = [vp, fp, fp, fp, d, i, vp, fp, fp, vp, vp, vp, vp]
+            L.cmpc_plant_step_vjp_rot_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp, vp]
+            L.cmpc_contacts_orientation_vjp_device.argtypes = [vp, i, d, i] + [vp] * 14
+            L.cmpc_rollout_tick_vjp_rot_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 15
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

@@ -60,10 +60,14 @@ extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCo
 
 extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
-                                     const double* dDirModel, double* dOut, hipStream_t stream);
+                                     const double* dDirModel, const double* dDirRot0, double* dOut, hipStream_t stream);
 extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
-                                     double* dGradModel, hipStream_t stream);
+                                     double* dGradModel, double* dGradRot0, hipStream_t stream);
+extern "C" int cmpc_launch_contacts_orientation_vjp(int B, int N, int M, double dt, double now, long long snap_dt_ns, const double* plan_t, const int* plan_n,
+                                                    const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
+                                                    const int* ok, const double* g_out, const double* g_rot, double* g_prev, double* g_plan, int* status,
+                                                    hipStream_t stream);
 extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
                                                  const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n,
                                                  const int* land, const int* ok, const double* g_out, const float* g_p, float* g_x, double* g_prev,
@@ -95,8 +99,9 @@ struct cmpc_handle_s {
     hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
     double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
     int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
-    char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp_device (allocated on first use): gX[B][n_x] | gP of the solve [B][n_p] | gP of the plant
-                                 // [B][n_p] (float) | model gradients of the solve and of the plant [B][34] each (double) | the tick's ok words [B] (int)
+    char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp[_rot]_device (allocated on first use, sized for both): model gradients of the solve and of
+                                 // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] (double) | gX[B][n_x] | gP of
+                                 // the solve [B][n_p] | gP of the plant [B][n_p] (float) | the tick's ok words [B] (int)
     hipEvent_t tick_ev = nullptr; // recorded after the last kernel of a tick VJP: the next one, on any stream, waits for it (one workspace)
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
     int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
@@ -941,28 +946,41 @@ int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, cons
 }
 
 // ---- plant-step derivatives (include/cmpc.h; cmpc_plant_jvp_kernel / cmpc_plant_vjp_kernel, next to the plant kernel) ----
-int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
-                               const float* dDirX, const float* dDirP, const double* dDirModel, double* dDirStateOut, void* stream)
+int cmpc_plant_step_jvp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
+                                   const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0, double* dDirStateOut, void* stream)
 {
     if (!h || !dX || !dP || !dStateIn || !dDirState || !dDirStateOut || !(step > 0) || substeps < 1)
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_jvp_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_jvp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                   dDirState, dDirX, dDirP, dDirModel, dDirStateOut, stream ? (hipStream_t)stream : h->stream);
+                                   dDirState, dDirX, dDirP, dDirModel, dDirRot0, dDirStateOut, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant JVP launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
+                               const float* dDirX, const float* dDirP, const double* dDirModel, double* dDirStateOut, void* stream)
+{
+    return cmpc_plant_step_jvp_rot_device(h, dX, dP, dStateIn, step, substeps, dDirState, dDirX, dDirP, dDirModel, nullptr, dDirStateOut, stream);
+}
+
+int cmpc_plant_step_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
+                                   const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
+                                   void* stream)
+{
+    if (!h || !dX || !dP || !dStateIn || !dGradStateOut || !dGradState || !dGradX || !(step > 0) || substeps < 1)
+        return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_vjp_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_plant_vjp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
+                                   dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant VJP launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
 }
 
 int cmpc_plant_step_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dGradStateOut,
                                double* dGradState, float* dGradX, float* dGradP, double* dGradModel, void* stream)
 {
-    if (!h || !dX || !dP || !dStateIn || !dGradStateOut || !dGradState || !dGradX || !(step > 0) || substeps < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_vjp_device: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_plant_vjp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                   dGradStateOut, dGradState, dGradX, dGradP, dGradModel, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant VJP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    return cmpc_plant_step_vjp_rot_device(h, dX, dP, dStateIn, step, substeps, dGradStateOut, dGradState, dGradX, dGradP, dGradModel, nullptr, stream);
 }
 
 // ---- 8e: compact per-problem output for the all-gather (see cmpc_compact_kernel) ----
@@ -1141,6 +1159,29 @@ int cmpc_contacts_position_vjp_device(cmpc_handle h, int max_contacts, double no
     return CMPC_OK;
 }
 
+// ---- ... and in their orientations (include/cmpc.h; cmpc_contacts_orientation_vjp_kernel) ----
+int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double now, int force_sample_time, const double* dPlanT, const int* dPlanN,
+                                         const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
+                                         const double* dGradListRotOut, const double* dGradRot, double* dGradPrevListRot, double* dGradPlanRot, int* dStatus,
+                                         void* stream)
+{
+    if (!h || max_contacts < 1 || !dListT || !dListN || !dGradPrevListRot) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_orientation_vjp_device: bad argument");
+    const bool merge = dPrevT || dPrevN;
+    if (merge && (!dPrevT || !dPrevN || !dPlanT || !dPlanN))
+        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_orientation_vjp_device: a merge tick needs the planner's and the previous tick's times and counts");
+    long long dt_ns = 0;
+    if (force_sample_time) {
+        dt_ns = snap_dt_ns(h->cfg.sampling_time);
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_orientation_vjp_device: force_sample_time needs a sampling time of at least 1 ns");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_contacts_orientation_vjp(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
+                                                  dListN, dLand, dOk, dGradListRotOut, dGradRot, dGradPrevListRot, dGradPlanRot, dStatus,
+                                                  stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact orientation VJP launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
 // the bounding boxes of the two contacts on the device (uploaded when they change)
 static int upload_box(cmpc_handle h, const float* box_upper, const float* box_lower, hipStream_t st)
 {
@@ -1259,17 +1300,19 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
 }
 
 // ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags
-// (cmpc_tick_vjp_combine_kernel) -> sample + merge part of the list VJP, on one stream ----
+// (cmpc_tick_vjp_combine_kernel) -> sample + merge part of the list VJP [-> the orientation list VJP], on one stream ----
 namespace {
 // one workgroup per problem.  Flags first: 5 merge failed, else the sensitivity's 2 / 3 (about the inputs), else 4 when the solve's status is not 0, else the
 // sensitivity's 1; a flagged problem gets zeros
 // in every array written here and ok = 0 (the list kernel behind this one then writes zeros too and adds nothing to g_plan).  Otherwise
 // gP = gP(solve) + gP(plant: fExt_0, tauExt_0), gState += gP[com0, dcom0, h0], gWrench = the fExt / tauExt rows of gP, gModel += solve's + plant's.
+// g_rot (the rotation entry; null otherwise) holds the solve's dl/domega [B][2][N][3] and receives the plant's g_rot0[B][2][3] on stage 0.
 __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N, const float* __restrict__ info, const int* __restrict__ ok,
                                                                     const float* __restrict__ gp_sol, const float* __restrict__ gp_plant,
                                                                     const double* __restrict__ gm_sol, const double* __restrict__ gm_plant,
                                                                     double* __restrict__ g_state, float* __restrict__ g_wrench, double* __restrict__ g_model,
-                                                                    float* __restrict__ g_p, float* __restrict__ sens, int* __restrict__ ok_out)
+                                                                    float* __restrict__ g_p, float* __restrict__ sens, int* __restrict__ ok_out,
+                                                                    const double* __restrict__ g_rot0, double* __restrict__ g_rot)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     const CmpcIdx L{N};
@@ -1285,6 +1328,7 @@ __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N
         for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] = 0.0;
         if (g_wrench) for (int e = tid; e < 6 * N; e += 128) g_wrench[(size_t)b * 6 * N + e] = 0.f;
         if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = 0.f;
+        if (g_rot) for (int e = tid; e < 6 * N; e += 128) g_rot[(size_t)b * 6 * N + e] = 0.0;
     } else {
         for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] += (double)gs[L.pCom0() + e];
         if (g_wrench)
@@ -1296,6 +1340,7 @@ __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N
         if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = gs[e] + gq[e];
         if (g_model) for (int e = tid; e < CMPC_MODEL_DOUBLES; e += 128)
             g_model[(size_t)b * CMPC_MODEL_DOUBLES + e] += gm_sol[(size_t)b * CMPC_MODEL_DOUBLES + e] + gm_plant[(size_t)b * CMPC_MODEL_DOUBLES + e];
+        if (g_rot) for (int e = tid; e < 6; e += 128) g_rot[((size_t)b * 2 + e / 3) * 3 * N + e % 3] += g_rot0[(size_t)b * 6 + e];
     }
     if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
 }
@@ -1307,11 +1352,13 @@ __global__ __launch_bounds__(256) void cmpc_axpy_float_kernel(size_t n, const fl
 }
 }  // namespace
 
-int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
-                                 const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
-                                 double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, void* stream)
+// rot: the rotation entry -- the plant VJP also gives dGradRot0, the solve's VJP is cmpc_solution_vjp_rot_device (its dGradP and dGradModel are
+// cmpc_solution_vjp_model_device's bit for bit), the combine kernel adds the plant's part to stage 0, and the orientation list VJP runs last
+static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut, const double* dGradListOut,
+                    const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench, double* dGradPlan, double* dGradModel, float* dGradP,
+                    float* dTickSens, const double* dGradListRotOut, double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream)
 {
-    if (!h || !tape || max_contacts < 1 || !dGradStateOut || !dGradState || !dGradPrevList || !dTickSens)
+    if (!h || !tape || max_contacts < 1 || !dGradStateOut || !dGradState || !dGradPrevList || !dTickSens || (rot && !dGradPrevListRot))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: null argument");
     if (!tape->dX || !tape->dP || !tape->dLamG || !tape->dState || !tape->dInfo || !tape->dLand || !tape->dListT || !tape->dListN ||
         !(tape->plant_step > 0) || tape->plant_substeps < 1)
@@ -1328,17 +1375,22 @@ int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, co
     const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const int B = h->B, N = h->cfg.horizon;
     const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, nm = (size_t)B * CMPC_MODEL_DOUBLES;
-    if (!h->dTickWs) HIPCHK(h, hipMalloc(&h->dTickWs, sizeof(double) * 2 * nm + sizeof(float) * (nx + 2 * np) + sizeof(int) * (size_t)B));
+    const size_t nr = (size_t)B * 6 * N, nr0 = (size_t)B * 6;
+    if (!h->dTickWs)     // (sized for the rotation entry whichever entry runs first)
+        HIPCHK(h, hipMalloc(&h->dTickWs, sizeof(double) * (2 * nm + nr + nr0) + sizeof(float) * (nx + 2 * np) + sizeof(int) * (size_t)B));
     double* gmSol = reinterpret_cast<double*>(h->dTickWs);
     double* gmPlant = gmSol + nm;
-    float* gX = reinterpret_cast<float*>(gmPlant + nm);
+    double* grSol = gmPlant + nm;
+    double* grPlant = grSol + nr;
+    float* gX = reinterpret_cast<float*>(grPlant + nr0);
+    if (rot && dGradRot) grSol = dGradRot;     // (the solve's VJP writes the caller's array; the combine kernel finishes it in place)
     float* gpSol = gX + nx;
     float* gpPlant = gpSol + np;
     int* okTick = reinterpret_cast<int*>(gpPlant + np);
     if (!h->tick_ev) HIPCHK(h, hipEventCreateWithFlags(&h->tick_ev, hipEventDisableTiming));
     else HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));
     int rc = cmpc_launch_plant_vjp(N, B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
-                                   tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, st);
+                                   tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, rot ? grPlant : nullptr, st);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
     if (dGradX) {
         hipLaunchKernelGGL(cmpc_axpy_float_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, nx, dGradX, gX);
@@ -1349,16 +1401,40 @@ int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, co
                                                tape->dListT, tape->dListN, tape->dLand, tape->dOk, dGradListOut, nullptr, gX, nullptr, nullptr, nullptr, st);
         if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (adjust) launch: ") + hipGetErrorString((hipError_t)rc));
     }
-    rc = cmpc_solution_vjp_model_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, dTickSens, stream);
+    rc = rot ? cmpc_solution_vjp_rot_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, grSol, dTickSens, stream)
+             : cmpc_solution_vjp_model_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, dTickSens, stream);
     if (rc != CMPC_OK) return rc;
     hipLaunchKernelGGL(cmpc_tick_vjp_combine_kernel, dim3(B), dim3(128), 0, st, B, N, tape->dInfo, tape->dOk, gpSol, gpPlant, gmSol, gmPlant, dGradState,
-                       dGradWrench, dGradModel, dGradP, dTickSens, okTick);
+                       dGradWrench, dGradModel, dGradP, dTickSens, okTick, rot ? grPlant : nullptr, rot ? grSol : nullptr);
     HIPCHK(h, hipGetLastError());
     rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 2, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                            tape->dListT, tape->dListN, tape->dLand, okTick, dGradListOut, gpSol, nullptr, dGradPrevList, dGradPlan, nullptr, st);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (sample + merge) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (rot) {
+        rc = cmpc_launch_contacts_orientation_vjp(B, N, max_contacts, h->cfg.sampling_time, now, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
+                                                  tape->dListT, tape->dListN, tape->dLand, okTick, dGradListRotOut, grSol, dGradPrevListRot, dGradPlanRot,
+                                                  nullptr, st);
+        if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (orientations) launch: ") + hipGetErrorString((hipError_t)rc));
+    }
     HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return CMPC_OK;
+}
+
+int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                 const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                 double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, void* stream)
+{
+    return tick_vjp(h, false, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
+                    dGradP, dTickSens, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                     const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                     double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
+                                     double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream)
+{
+    return tick_vjp(h, true, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
+                    dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream);
 }
 
 // the handle's own contact blocks from contact lists (what the class facade's setContactPhaseList calls)

@@ -91,6 +91,25 @@ __global__ __launch_bounds__(128) void cmpc_contacts_adjust_kernel(int B, int N,
     for (int i = 0; i < 3; ++i) pose[7 * (o + nx) + i] = x[i];
 }
 
+// Where the entries of a merged list came from (cmpc_merge_foot in reverse, from the times alone): ma = the previous list's active contact, which became merged
+// entry 0, or -1; first = the planner's first future contact, which became merged entry n0 = (ma >= 0), or -1.  snap_dt_ns > 0: the planner's times pass
+// through cmpc_snap_contact first, as in the forward tick.  Shared by the position and the orientation adjoint.
+__device__ inline void cmpc_merge_sources(int M, double now, long long snap_dt_ns, const double* __restrict__ plan_t, int pn, const double* __restrict__ prev_t,
+                                          int mn, int& ma, int& first)
+{
+    ma = -1; first = -1;
+    if (mn >= 0 && mn <= M) ma = cmpc_active_contact(prev_t, mn, now);
+    if (pn >= 0 && pn <= M) {
+        if (snap_dt_ns > 0) {
+            for (int m = 0; m < pn && first < 0; ++m) {
+                double s[2];
+                cmpc_snap_contact(plan_t + 2 * m, snap_dt_ns, s);
+                if (cmpc_next_contact(s, 1, now) == 0) first = m;
+            }
+        } else first = cmpc_next_contact(plan_t, pn, now);
+    }
+}
+
 // Adjoint of the list path of one tick in the contacts' POSITIONS (include/cmpc.h, cmpc_contacts_position_vjp_device): adjust (phase bit 1), sample + merge
 // (phase bit 2).  One thread per (problem, foot); it owns that foot's entries of every output, so the sums need no atomics and their order is fixed:
 // an entry of g_prev / g_plan receives first the list's own gradient g_out, then the sampling's terms stage by stage, k = 0 .. N-1 (stage 0: nominalPos_0,
@@ -130,19 +149,7 @@ __global__ __launch_bounds__(128) void cmpc_contacts_position_vjp_kernel(int B, 
     if (!(phase & 2)) return;
     // merge: where entry m of this tick's list came from
     int ma = -1, first = -1;
-    if (merge) {
-        const int mn = prev_n[e], pn = plan_n[e];
-        if (mn >= 0 && mn <= M) ma = cmpc_active_contact(prev_t + 2 * o, mn, now);
-        if (pn >= 0 && pn <= M) {
-            if (snap_dt_ns > 0) {
-                for (int m = 0; m < pn && first < 0; ++m) {
-                    double s[2];
-                    cmpc_snap_contact(plan_t + 2 * (o + m), snap_dt_ns, s);
-                    if (cmpc_next_contact(s, 1, now) == 0) first = m;
-                }
-            } else first = cmpc_next_contact(plan_t + 2 * o, pn, now);
-        }
-    }
+    if (merge) cmpc_merge_sources(M, now, snap_dt_ns, plan_t + 2 * o, plan_n[e], prev_t + 2 * o, prev_n[e], ma, first);
     const int n0 = ma >= 0 ? 1 : 0;
     auto dest = [&](int m) -> double* {                    // (null: the entry's gradient goes nowhere)
         if (!merge) return g_prev + 3 * (o + m);
@@ -190,6 +197,55 @@ __global__ __launch_bounds__(128) void cmpc_contacts_rotation_vjp_kernel(int B, 
         bool act;
         const int m = cmpc_stage_owner(list_t + 2 * o, n, now + k * dt, &act);
         for (int i = 0; i < 3; ++i) out[3 * m + i] += g[3 * k + i];
+    }
+}
+
+// Adjoint of the list path of one tick in the contacts' ORIENTATIONS (include/cmpc.h, cmpc_contacts_orientation_vjp_device): the counterpart of the sample +
+// merge part above, in the body-frame tangent of each entry's quaternion, where every copy the forward makes is the identity.  Entry m of this tick's list
+// carries first its own g_out[m] -- ALL of them: the step adjustment overwrites positions only, so the landing entry's orientation passes through -- then
+// the sampling's terms, g_rot of the stages it owns, stage by stage, k = 0 .. N-1 (cmpc_stage_owner); the merge transposed sends entry 0 to the previous
+// list's active contact and the rest to the planner's entries (+=).  One thread per (problem, foot) owns its outputs: no atomics, a fixed order.  A foot
+// that was not sampled (an empty list, one longer than M, land = -2) passes nothing on.
+__global__ __launch_bounds__(128) void cmpc_contacts_orientation_vjp_kernel(int B, int N, int M, double dt, double now, long long snap_dt_ns,
+                                                                            const double* __restrict__ plan_t, const int* __restrict__ plan_n,
+                                                                            const double* __restrict__ prev_t, const int* __restrict__ prev_n,
+                                                                            const double* __restrict__ list_t, const int* __restrict__ list_n,
+                                                                            const int* __restrict__ land, const int* __restrict__ ok,
+                                                                            const double* __restrict__ g_out, const double* __restrict__ g_rot,
+                                                                            double* __restrict__ g_prev, double* __restrict__ g_plan, int* __restrict__ status)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;   // problem * 2 + foot
+    if (e >= 2 * B) return;
+    const int b = e >> 1, c = e & 1;
+    const size_t o = (size_t)e * M;
+    const bool merge = prev_t != nullptr;
+    const bool good = !ok || ok[b] != 0;
+    if (status && c == 0) status[b] = good ? 0 : 5;
+    for (int m = 0; m < 3 * M; ++m) g_prev[3 * o + m] = 0.0;
+    const int n = list_n[e];
+    if (!good || n < 1 || n > M || (land && land[e] == -2)) return;
+    int ma = -1, first = -1;
+    if (merge) cmpc_merge_sources(M, now, snap_dt_ns, plan_t + 2 * o, plan_n[e], prev_t + 2 * o, prev_n[e], ma, first);
+    const int n0 = ma >= 0 ? 1 : 0;
+    auto dest = [&](int m) -> double* {                    // (null: the entry's gradient goes nowhere)
+        if (!merge) return g_prev + 3 * (o + m);
+        if (m < n0) return g_prev + 3 * (o + ma);
+        if (first < 0 || !g_plan || first + m - n0 >= M) return nullptr;
+        return g_plan + 3 * (o + first + m - n0);
+    };
+    if (g_out)
+        for (int m = 0; m < n; ++m) {
+            double* d = dest(m);
+            if (!d) continue;
+            for (int i = 0; i < 3; ++i) d[i] += g_out[3 * (o + m) + i];
+        }
+    if (!g_rot) return;
+    const double* g = g_rot + (size_t)e * 3 * N;
+    for (int k = 0; k < N; ++k) {
+        bool act;
+        double* d = dest(cmpc_stage_owner(list_t + 2 * o, n, now + k * dt, &act));
+        if (!d) continue;
+        for (int i = 0; i < 3; ++i) d[i] += g[3 * k + i];
     }
 }
 
@@ -284,5 +340,15 @@ extern "C" int cmpc_launch_contacts_rotation_vjp(int B, int N, int M, double dt,
                                                  double* g_list, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_contacts_rotation_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, list_t, list_n, g_rot, g_list);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_contacts_orientation_vjp(int B, int N, int M, double dt, double now, long long snap_dt_ns, const double* plan_t, const int* plan_n,
+                                                    const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
+                                                    const int* ok, const double* g_out, const double* g_rot, double* g_prev, double* g_plan, int* status,
+                                                    hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_contacts_orientation_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, snap_dt_ns, plan_t, plan_n,
+                       prev_t, prev_n, list_t, list_n, land, ok, g_out, g_rot, g_prev, g_plan, status);
     return (int)hipGetLastError();
 }

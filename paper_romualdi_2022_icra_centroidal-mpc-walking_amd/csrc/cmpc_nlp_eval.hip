@@ -1239,6 +1239,7 @@ __global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, floa
 struct PlantPartials {
     double T, F[3], I[3];      // horizon of the step, total force, time integral of the CoM
     double cp[8][3], cf[8][3]; // contact points and (gated) corner forces
+    double cn[8][3];           // the corners themselves (rotation directions: d cp_q = R_c,0 (omega_c x cn_q))
     bool on[2];
 };
 
@@ -1260,6 +1261,7 @@ __device__ inline void plant_partials(int N, int b, float grav, const float* __r
                 const float fv = x[L.oF(c, j) + i];
                 q.cf[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
                 q.F[i] += q.cf[4 * c + j][i];
+                q.cn[4 * c + j][i] = (double)cn[i];
             }
         }
     }
@@ -1275,10 +1277,13 @@ __device__ inline void cross3(const double* a, const double* b, double* o)
     o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// forwards: (ds, dx, dp, dtheta) -> ds'.  Null direction groups are zero.
+// forwards: (ds, dx, dp, dtheta, omega_0) -> ds'.  Null direction groups are zero.  ROT: with the rotation direction of knot 0, dir_rot[B][2][3] in the
+// body-frame tangent dR_c,0 = R_c,0 [omega_c]x -- the contact points move by R_c,0 (omega_c x cn_q), so only the torque sees it.  ROT = false is the kernel
+// without it, instruction for instruction.
+template <bool ROT>
 __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* __restrict__ dir_state,
                                          const float* __restrict__ dir_x, const float* __restrict__ dir_p, const double* __restrict__ dir_model,
-                                         double* __restrict__ out)
+                                         const double* __restrict__ dir_rot, double* __restrict__ out)
 {
     const CmpcIdx L{N};
     const float* p = P + (size_t)b * L.np();
@@ -1291,13 +1296,15 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
     for (int c = 0; c < 2; ++c) {
         const float* R = p + L.pR(c);
         for (int j = 0; j < 4; ++j) {
-            double dcp[3], df[3];
+            double dcp[3], df[3], wn[3];
+            if (ROT) cross3(dir_rot + ((size_t)b * 2 + c) * 3, q.cn[4 * c + j], wn);
             for (int i = 0; i < 3; ++i) {
                 dcp[i] = dir_x ? (double)dir_x[(size_t)b * L.nx() + L.oPos(c) + i] : 0.0;
                 if (dir_model) {
                     const double* dn = dir_model + (size_t)b * CMPC_MODEL_DOUBLES + 10 + 12 * c + 3 * j;
                     dcp[i] += (double)R[i] * dn[0] + (double)R[3 + i] * dn[1] + (double)R[6 + i] * dn[2];
                 }
+                if (ROT) dcp[i] += (double)R[i] * wn[0] + (double)R[3 + i] * wn[1] + (double)R[6 + i] * wn[2];
                 df[i] = (dir_x && q.on[c]) ? (double)dir_x[(size_t)b * L.nx() + L.oF(c, j) + i] : 0.0;
                 dF[i] += df[i];
             }
@@ -1321,9 +1328,13 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
     }
 }
 
-// transposed: gs' -> (gs, gx (the 30 entries it owns), gp (fExt_0, tauExt_0), gtheta (corners)).  grad_state may alias grad_out; null outputs are skipped.
+// transposed: gs' -> (gs, gx (the 30 entries it owns), gp (fExt_0, tauExt_0), gtheta (corners), gomega_0).  grad_state may alias grad_out; null outputs are
+// skipped.  ROT: grad_rot[B][2][3], the transpose of the JVP's rotation term: <gcp, R (omega x cn)> = <omega, cn x R^T gcp>, summed over the foot's corners
+// in corner order (a gated-off foot has gcp = 0: zeros).
+template <bool ROT>
 __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* grad_out, double* grad_state,
-                                         float* __restrict__ grad_x, float* __restrict__ grad_p, double* __restrict__ grad_model)
+                                         float* __restrict__ grad_x, float* __restrict__ grad_p, double* __restrict__ grad_model,
+                                         double* __restrict__ grad_rot)
 {
     const CmpcIdx L{N};
     const float* p = P + (size_t)b * L.np();
@@ -1343,7 +1354,7 @@ __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__
     double gtau[3] = {T * gh[0], T * gh[1], T * gh[2]};
     for (int c = 0; c < 2; ++c) {
         const float* R = p + L.pR(c);
-        double gpos[3] = {0, 0, 0};
+        double gpos[3] = {0, 0, 0}, grot[3] = {0, 0, 0};
         for (int j = 0; j < 4; ++j) {
             double gcp[3], gf[3];
             cross3(q.cf[4 * c + j], gtau, gcp);   // <gtau, dcp x f> = <dcp, f x gtau>
@@ -1355,36 +1366,47 @@ __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__
             if (grad_model)
                 for (int a = 0; a < 3; ++a)   // R^T gcp: column a of R (col-major) against gcp
                     grad_model[(size_t)b * CMPC_MODEL_DOUBLES + 10 + 12 * c + 3 * j + a] = (double)R[3 * a] * gcp[0] + (double)R[3 * a + 1] * gcp[1] + (double)R[3 * a + 2] * gcp[2];
+            if (ROT) {
+                double rg[3], t[3];
+                for (int a = 0; a < 3; ++a) rg[a] = (double)R[3 * a] * gcp[0] + (double)R[3 * a + 1] * gcp[1] + (double)R[3 * a + 2] * gcp[2];
+                cross3(q.cn[4 * c + j], rg, t);
+                for (int a = 0; a < 3; ++a) grot[a] += t[a];
+            }
         }
         if (grad_x)
             for (int i = 0; i < 3; ++i) grad_x[(size_t)b * L.nx() + L.oPos(c) + i] = (float)gpos[i];
+        if (ROT)
+            for (int a = 0; a < 3; ++a) grad_rot[((size_t)b * 2 + c) * 3 + a] = grot[a];
     }
     if (grad_model)
         for (int i = 0; i < 10; ++i) grad_model[(size_t)b * CMPC_MODEL_DOUBLES + i] = 0.0;
 }
 
+template <bool ROT>
 __global__ __launch_bounds__(256) void cmpc_plant_jvp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
                                                              float h, int nsub, const double* __restrict__ dir_state, const float* __restrict__ dir_x,
-                                                             const float* __restrict__ dir_p, const double* __restrict__ dir_model, double* __restrict__ out)
+                                                             const float* __restrict__ dir_p, const double* __restrict__ dir_model,
+                                                             const double* __restrict__ dir_rot, double* __restrict__ out)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     PlantPartials q;
     plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
-    plant_jvp_problem(N, b, P, q, dir_state, dir_x, dir_p, dir_model, out);
+    plant_jvp_problem<ROT>(N, b, P, q, dir_state, dir_x, dir_p, dir_model, dir_rot, out);
 }
 
+template <bool ROT>
 __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
                                                              float h, int nsub, const double* grad_out, double* grad_state, float* __restrict__ grad_x,
-                                                             float* __restrict__ grad_p, double* __restrict__ grad_model)
+                                                             float* __restrict__ grad_p, double* __restrict__ grad_model, double* __restrict__ grad_rot)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     PlantPartials q;
     plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
-    plant_vjp_problem(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model);
+    plant_vjp_problem<ROT>(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model, grad_rot);
 }
 
 // ---- the two ends of a roll-out tick as ONE launch each (cmpc_rollout_tick_device).  At B <= 256 a tick is a 0.66 ms solve between nine launches of a
@@ -1566,27 +1588,36 @@ extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCo
     return (int)hipGetLastError();
 }
 
+// dDirRot0 / dGradRot0 NULL: the instantiation without the rotation term, which is the kernel as it was before that term existed
 extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
-                                     const double* dDirModel, double* dOut, hipStream_t stream)
+                                     const double* dDirModel, const double* dDirRot0, double* dOut, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_plant_jvp_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h, nsub,
-                       dDirState, dDirX, dDirP, dDirModel, dOut);
+    if (dDirRot0)
+        hipLaunchKernelGGL(cmpc_plant_jvp_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOut);
+    else
+        hipLaunchKernelGGL(cmpc_plant_jvp_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOut);
     return (int)hipGetLastError();
 }
 
 // dGradX / dGradP: the whole rows are cleared first (the kernel writes the entries the plant reads, nothing else)
 extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
-                                     double* dGradModel, hipStream_t stream)
+                                     double* dGradModel, double* dGradRot0, hipStream_t stream)
 {
     const CmpcIdx L{N};
     hipError_t e = hipSuccess;
     if (dGradX) e = hipMemsetAsync(dGradX, 0, sizeof(float) * (size_t)B * L.nx(), stream);
     if (e == hipSuccess && dGradP) e = hipMemsetAsync(dGradP, 0, sizeof(float) * (size_t)B * L.np(), stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cmpc_plant_vjp_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h, nsub,
-                       dGradOut, dGradState, dGradX, dGradP, dGradModel);
+    if (dGradRot0)
+        hipLaunchKernelGGL(cmpc_plant_vjp_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dGradOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0);
+    else
+        hipLaunchKernelGGL(cmpc_plant_vjp_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dGradOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0);
     return (int)hipGetLastError();
 }
 

@@ -295,14 +295,18 @@ class WalkingRollout:
         rec["box_upper"], rec["box_lower"] = box_up, box_lo
         return rec
 
-    def backward(self, tape, grad_states, grad_X=None):
+    def backward(self, tape, grad_states, grad_X=None, rot=False):
         """The taped roll-out in reverse (cmpc_rollout_tick_vjp_device, one call per tick, last tick first).  tape = run(..., tape=True)["tape"];
         grad_states[ticks + 1, B, 9] = dl / d state_i of the states BEFORE tick i (i = 0 .. ticks - 1) and of the final state (i = ticks), a CUDA tensor or
         numpy; grad_X[ticks, B, n_x] float32 or None = dl / d x_i, a loss on the ticks' solutions.
         -> dict(state0[B, 9], list0[B, 2, M, 3] (the positions of the first tick's lists), push[B, 3] (the sum of the wrench gradients over the ticks and
         knots the push was written to), wrench[ticks, B, N, 6], models[B, 34], plan[B, 2, M, 3] (the planner's contact positions), status[ticks, B] int32:
         0, or why that tick of that problem passed no gradient on -- include/cmpc.h), float64 but wrench (float32).  The solution map is taken as
-        independent of the warm start; contact times, orientations and the planner's CoM references are not differentiated."""
+        independent of the warm start; contact times and the planner's CoM references are not differentiated.
+        rot=True (cmpc_rollout_tick_vjp_rot_device per tick): the contacts' orientations too, in the body-frame tangent of their quaternions
+        (q <- q (x) exp(omega / 2)): the dict also holds list_rot0[B, 2, M, 3] (the first tick's lists), plan_rot[B, 2, M, 3] (the planner's contacts) and
+        rot[ticks, B, 2, N, 3] (each tick's per-stage dl/domega), float64; every other entry is bit-equal to rot=False.  A double-support tick under load
+        has no orientation derivative (include/cmpc.h, "rotation directions"): out["removed"][ticks, B] is word 6 of each tick's dSens."""
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         ticks = tape["ticks"]
         T = len(ticks)
@@ -317,14 +321,24 @@ class WalkingRollout:
         out = dict(push=torch.zeros((B, 3), dtype=torch.float64, device=self.dev), wrench=torch.zeros((T, B, N, 6), dtype=torch.float32, device=self.dev),
                    models=torch.zeros((B, 34), dtype=torch.float64, device=self.dev), plan=torch.zeros((B, 2, M, 3), dtype=torch.float64, device=self.dev),
                    status=torch.zeros((T, B), dtype=torch.int32, device=self.dev))
+        if rot:
+            out.update(plan_rot=torch.zeros((B, 2, M, 3), dtype=torch.float64, device=self.dev), rot=torch.zeros((T, B, 2, N, 3), dtype=torch.float64, device=self.dev),
+                       removed=torch.zeros((T, B), dtype=torch.float32, device=self.dev))
         ls = self.solver.launch_stream
         cur = torch.cuda.current_stream(self.dev)
         ls.wait_stream(cur)
         with torch.cuda.stream(ls):
-            g, gl = gS[T].clone(), None
+            g, gl, glr = gS[T].clone(), None, None
             for i in reversed(range(T)):
                 tk = ticks[i]
-                r = self.solver.rollout_tick_vjp_device(tk["now"], tk, g, gl, None if gX is None else gX[i], dGradPlan=out["plan"], dGradModel=out["models"])
+                if rot:
+                    r = self.solver.rollout_tick_vjp_device(tk["now"], tk, g, gl, None if gX is None else gX[i], dGradPlan=out["plan"], dGradModel=out["models"],
+                                                            dGradListRotOut=glr, rot=True, dGradPlanRot=out["plan_rot"])
+                    glr = r["prev_list_rot"]
+                    out["rot"][i] = r["rot"]
+                    out["removed"][i] = r["sens"][:, 6]
+                else:
+                    r = self.solver.rollout_tick_vjp_device(tk["now"], tk, g, gl, None if gX is None else gX[i], dGradPlan=out["plan"], dGradModel=out["models"])
                 g = r["state"] + gS[i]
                 gl = r["prev_list"]
                 out["wrench"][i] = r["wrench"]
@@ -332,27 +346,55 @@ class WalkingRollout:
                 if tk["push_knots"] > 0:
                     out["push"] += r["wrench"][:, :tk["push_knots"], :3].to(torch.float64).sum(1)
             out["state0"], out["list0"] = g, gl
+            if rot:
+                out["list_rot0"] = glr
         cur.wait_stream(ls)
         return out
 
 
-def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0):
+def yaw_plan_poses(pose, plan_yaw):
+    """pose[B, 2, M, 7] float32 (x y z, quaternion w x y z) with every contact yawed about its own z axis by plan_yaw[B, 2, M] float64:
+    q <- q (x) (cos(psi / 2), 0, 0, sin(psi / 2)), formed in float64; an entry with psi == 0 keeps its bits."""
+    import torch
+    q = pose[..., 3:7].to(torch.float64)
+    w, x, y, z = q.unbind(-1)
+    c, s = torch.cos(0.5 * plan_yaw), torch.sin(0.5 * plan_yaw)
+    qr = torch.stack([w * c - z * s, x * c + y * s, y * c - x * s, z * c + w * s], -1).to(torch.float32)
+    out = pose.clone()
+    out[..., 3:7] = torch.where((plan_yaw == 0)[..., None], pose[..., 3:7], qr)
+    return out
+
+
+def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None):
     """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
     state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
     (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
     tensor installed on the roll-out's solver (set_models_device) and left installed.  rollout.last_tape / rollout.last_backward hold the tape of the last
-    forward and the dict of the last backward (its status words say which ticks passed no gradient on)."""
+    forward and the dict of the last backward (its status words say which ticks passed no gradient on).
+    plan_yaw: None, or a [B, 2, M] float64 CUDA tensor: entry (b, c, m) yaws the planner's contact m of foot c about its own z axis before the run
+    (yaw_plan_poses, on a copy of rollout.plan's poses made for this call; rollout.plan is left as it was).  backward then runs with rot=True and
+    plan_yaw.grad = the e_z component of plan_rot + list_rot0: the first tick's list is the planner's list entry for entry, and every later tick reads the
+    planner's entries through the merge; rotations about one axis commute, so the body-frame tangent at the yawed quaternion is d psi e_z."""
     import torch
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, state0, push, models):
+        def forward(ctx, state0, push, models, plan_yaw):
             if models is not None:
                 rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
             s0 = state0.detach().to(torch.float32).cpu().numpy()
-            rec = rollout.run(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(torch.float32).cpu().numpy(),
-                              push_ticks=push_ticks, record="light", tape=True)
+            plan = rollout.plan
+            if plan_yaw is not None:
+                psi = plan_yaw.detach().to(rollout.dev, torch.float64)
+                assert tuple(psi.shape) == tuple(plan[1].shape[:3]), f"plan_yaw: expected {tuple(plan[1].shape[:3])}"
+                rollout.plan = (plan[0], yaw_plan_poses(plan[1], psi), plan[2])
+            try:
+                rec = rollout.run(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(torch.float32).cpu().numpy(),
+                                  push_ticks=push_ticks, record="light", tape=True)
+            finally:
+                rollout.plan = plan
+            ctx.rot = plan_yaw is not None
             tape = rec["tape"]
             assert len(tape["ticks"]) == ticks, f"the roll-out stopped at tick {rec.get('aborted_tick')}"
             rollout.last_tape = ctx.tape = tape
@@ -361,9 +403,10 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
 
         @staticmethod
         def backward(ctx, gStates):
-            r = rollout.backward(ctx.tape, gStates)
+            r = rollout.backward(ctx.tape, gStates, rot=ctx.rot)
             rollout.last_backward = r
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
-                    r["models"] if ctx.needs_input_grad[2] else None)
+                    r["models"] if ctx.needs_input_grad[2] else None,
+                    (r["plan_rot"][..., 2] + r["list_rot0"][..., 2]) if ctx.rot and ctx.needs_input_grad[3] else None)
 
-    return _Fn.apply(state0, push, models)
+    return _Fn.apply(state0, push, models, plan_yaw)

@@ -473,9 +473,10 @@ class BatchSolver:
         assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{name}: expected {dtype} {tuple(shape)}"
         return t.data_ptr()
 
-    def plant_step_jvp_device(self, dX, dP, dState, dDirState, dDirX=None, dDirP=None, dDirModel=None, step=0.01, substeps=6, out=None):
-        """d(plant step) applied to one direction per problem: dDirState[B, 9] float64, dDirX[B, n_x] / dDirP[B, n_p] float32 and dDirModel[B, 34]
-        float64 (None: zero) -> d state'[B, 9] float64.  What is and is not differentiated: include/cmpc.h."""
+    def plant_step_jvp_device(self, dX, dP, dState, dDirState, dDirX=None, dDirP=None, dDirModel=None, step=0.01, substeps=6, out=None, dDirRot0=None):
+        """d(plant step) applied to one direction per problem: dDirState[B, 9] float64, dDirX[B, n_x] / dDirP[B, n_p] float32, dDirModel[B, 34]
+        float64 and dDirRot0[B, 2, 3] float64 (the knot-0 rotations, dR = R [omega]x; cmpc_plant_step_jvp_rot_device) (None: zero) -> d state'[B, 9]
+        float64.  What is and is not differentiated: include/cmpc.h."""
         import torch
         L, B = self.layout, self.batch
         if out is None:
@@ -483,13 +484,19 @@ class BatchSolver:
         ps = self._opt(dDirState, torch.float64, (B, 9), "dDirState")
         px, pp = self._opt(dDirX, torch.float32, (B, L.nx), "dDirX"), self._opt(dDirP, torch.float32, (B, L.np), "dDirP")
         pm, po = self._opt(dDirModel, torch.float64, (B, _capi.MODEL_DOUBLES), "dDirModel"), self._opt(out, torch.float64, (B, 9), "out")
-        self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_device(self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step),
-                                                                                int(substeps), ps, px, pp, pm, po, st))
+        if dDirRot0 is None:
+            self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_device(self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step),
+                                                                                    int(substeps), ps, px, pp, pm, po, st))
+        else:
+            pr = self._opt(dDirRot0, torch.float64, (B, 2, 3), "dDirRot0")
+            self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_rot_device(self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step),
+                                                                                        int(substeps), ps, px, pp, pm, pr, po, st))
         return out
 
-    def plant_step_vjp_device(self, dX, dP, dState, dGradStateOut, step=0.01, substeps=6, grad_p=True, grad_model=True):
+    def plant_step_vjp_device(self, dX, dP, dState, dGradStateOut, step=0.01, substeps=6, grad_p=True, grad_model=True, grad_rot=False):
         """(d plant step)^T g: dGradStateOut[B, 9] float64 -> (dGradState[B, 9] float64, dGradX[B, n_x] float32, dGradP[B, n_p] float32 or None,
-        dGradModel[B, 34] float64 or None); dGradX is zero but for the knot-0 positions and forces, dGradP but for fExt_0 / tauExt_0."""
+        dGradModel[B, 34] float64 or None); dGradX is zero but for the knot-0 positions and forces, dGradP but for fExt_0 / tauExt_0.
+        grad_rot=True (cmpc_plant_step_vjp_rot_device): a fifth result, dGradRot0[B, 2, 3] float64 = dl / d omega of the knot-0 rotations."""
         import torch
         L, B, dev = self.layout, self.batch, dX.device
         pg = self._opt(dGradStateOut, torch.float64, (B, 9), "dGradStateOut")
@@ -497,10 +504,34 @@ class BatchSolver:
         gX = torch.empty((B, L.nx), dtype=torch.float32, device=dev)
         gP = torch.empty((B, L.np), dtype=torch.float32, device=dev) if grad_p else None
         gM = torch.empty((B, _capi.MODEL_DOUBLES), dtype=torch.float64, device=dev) if grad_model else None
-        self._launch(dev, lambda st: self._lib.cmpc_plant_step_vjp_device(
-            self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step), int(substeps), pg, gS.data_ptr(), gX.data_ptr(),
-            gP.data_ptr() if grad_p else None, gM.data_ptr() if grad_model else None, st))
-        return gS, gX, gP, gM
+        args = (self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step), int(substeps), pg, gS.data_ptr(), gX.data_ptr(),
+                gP.data_ptr() if grad_p else None, gM.data_ptr() if grad_model else None)
+        if not grad_rot:
+            self._launch(dev, lambda st: self._lib.cmpc_plant_step_vjp_device(*args, st))
+            return gS, gX, gP, gM
+        gR = torch.empty((B, 2, 3), dtype=torch.float64, device=dev)
+        self._launch(dev, lambda st: self._lib.cmpc_plant_step_vjp_rot_device(*args, gR.data_ptr(), st))
+        return gS, gX, gP, gM, gR
+
+    def contacts_orientation_vjp_device(self, now, list_t, list_n, land=None, plan=None, prev=None, ok=None, dGradListRotOut=None, dGradRot=None,
+                                        dGradPlanRot=None, force_sample_time=False, out=None):
+        """Adjoint of the list path of one tick in the contacts' orientations (cmpc_contacts_orientation_vjp_device), the counterpart of phase 2 of
+        contacts_position_vjp_device with the same tape arguments.  dGradListRotOut[B,2,M,3] / dGradRot[B,2,N,3] float64 (None: zero), dGradPlanRot
+        [B,2,M,3] float64 (+=, in place), all in the body-frame tangent of the quaternions.  Returns (dGradPrevListRot[B,2,M,3] float64, status[B] int32)."""
+        import torch
+        L, B, M, dev = self.layout, self.batch, list_t.shape[2], list_t.device
+        g3 = (B, 2, M, 3)
+        assert list_t.is_cuda and list_t.dtype == torch.float64 and list_t.is_contiguous() and tuple(list_t.shape) == (B, 2, M, 2)
+        gprev = out if out is not None else torch.empty(g3, dtype=torch.float64, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tn = lambda pair: (None, None) if pair is None else (self._opt(pair[0], torch.float64, (B, 2, M, 2), "times"), self._opt(pair[1], torch.int32, (B, 2), "counts"))
+        (plt, pln), (pvt, pvn) = tn(plan), tn(prev)
+        args = (self._opt(list_n, torch.int32, (B, 2), "list_n"), self._opt(land, torch.int32, (B, 2), "land"), self._opt(ok, torch.int32, (B,), "ok"),
+                self._opt(dGradListRotOut, torch.float64, g3, "dGradListRotOut"), self._opt(dGradRot, torch.float64, (B, 2, L.N, 3), "dGradRot"),
+                self._opt(gprev, torch.float64, g3, "out"), self._opt(dGradPlanRot, torch.float64, g3, "dGradPlanRot"), status.data_ptr())
+        self._launch(dev, lambda st: self._lib.cmpc_contacts_orientation_vjp_device(
+            self._h, M, float(now), 1 if force_sample_time else 0, plt, pln, pvt, pvn, list_t.data_ptr(), *args, st))
+        return gprev, status
 
     def contacts_position_vjp_device(self, now, list_t, list_n, land, plan=None, prev=None, ok=None, dGradListOut=None, dGradP=None, dGradX=None,
                                      dGradPlan=None, phase=3, force_sample_time=False, out=None):
@@ -526,12 +557,17 @@ class BatchSolver:
             self._h, M, float(now), int(phase), 1 if force_sample_time else 0, plt, pln, pvt, pvn, list_t.data_ptr(), *args, st))
         return gprev, status
 
-    def rollout_tick_vjp_device(self, now, tape, dGradStateOut, dGradListOut=None, dGradX=None, dGradPlan=None, dGradModel=None, wrench=True, grad_p=False):
+    def rollout_tick_vjp_device(self, now, tape, dGradStateOut, dGradListOut=None, dGradX=None, dGradPlan=None, dGradModel=None, wrench=True, grad_p=False,
+                                dGradListRotOut=None, rot=False, dGradPlanRot=None):
         """cmpc_rollout_tick_vjp_device: one tick in reverse.  tape: dict(X, P, lam_g, state, info, ok (or None), land, plan_t, plan_n, prev_t, prev_n
         (both None on the first tick), list_t, list_n, step, substeps, force_sample_time) of CUDA tensors as the forward tick left them.
         dGradStateOut[B,9] float64, dGradListOut[B,2,M,3] float64 or None, dGradX[B,n_x] float32 or None; dGradPlan / dGradModel: float64 tensors added to
         in place, or None.  Returns dict(state[B,9], prev_list[B,2,M,3] float64, wrench[B,N,6] float32 or None, p[B,n_p] float32 or None,
-        sens[B,CMPC_SENS] float32 with the tick's status in word 0)."""
+        sens[B,CMPC_SENS] float32 with the tick's status in word 0).
+        rot=True (cmpc_rollout_tick_vjp_rot_device): the contacts' orientations are carried along, in the body-frame tangent of their quaternions --
+        dGradListRotOut[B,2,M,3] float64 or None, dGradPlanRot[B,2,M,3] float64 added to in place or None; the dict also holds prev_list_rot[B,2,M,3] and
+        rot[B,2,N,3] float64 (the tick's per-stage dl/domega: the solve's, plus the plant's on stage 0), every other entry bit-equal to rot=False but
+        sens, which is the rotation VJP's."""
         import torch
         from ._capi import CmpcTickTape
         L, B, N = self.layout, self.batch, self.cfg.N
@@ -554,7 +590,15 @@ class BatchSolver:
                 self._opt(dGradX, f32, (B, L.nx), "dGradX"), out["state"].data_ptr(), out["prev_list"].data_ptr(),
                 out["wrench"].data_ptr() if wrench else None, self._opt(dGradPlan, f64, g3, "dGradPlan"),
                 self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"), out["p"].data_ptr() if grad_p else None, out["sens"].data_ptr())
-        self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_device(self._h, M, float(now), ct, *args, st))
+        if not rot:
+            assert dGradListRotOut is None and dGradPlanRot is None, "orientation gradients need rot=True"
+            self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_device(self._h, M, float(now), ct, *args, st))
+            return out
+        out["prev_list_rot"] = torch.empty(g3, dtype=f64, device=dev)
+        out["rot"] = torch.empty((B, 2, N, 3), dtype=f64, device=dev)
+        rargs = (self._opt(dGradListRotOut, f64, g3, "dGradListRotOut"), out["prev_list_rot"].data_ptr(), self._opt(dGradPlanRot, f64, g3, "dGradPlanRot"),
+                 out["rot"].data_ptr())
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_rot_device(self._h, M, float(now), ct, *args, *rargs, st))
         return out
 
     def closed_loop_transition_device(self, dX, dP, dLamG, dState, step=0.01, substeps=6):
