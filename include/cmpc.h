@@ -687,6 +687,72 @@ int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now
                                      double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
                                      double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream);
 
+/* ---- the roll-out tick FORWARDS, in k directions (derivation: DESIGN.md 7d, "Forwards") ----
+ * The transposes of the entry points above: the same linear maps at the same tape, applied to k direction columns per problem instead of one cotangent.
+ * Every direction array carries a column axis right behind the batch axis, [B][k][...].
+ *
+ * The plant JVP with k columns: one thread per (problem, column) runs the partials and the JVP of cmpc_plant_step_jvp_rot_device.  dDirState[B][k][9]
+ * double, dDirX[B][k][n_x] float, dDirP[B][k][n_p] float, dDirModel[B][k][34] double, dDirRot0[B][k][2][3] double -> dDirStateOut[B][k][9] double (may
+ * alias dDirState).  NULL rules as cmpc_plant_step_jvp_rot_device (dDirState is required; dDirRot0 NULL is the kernel without the rotation term).  Column j
+ * is bit-equal to that entry point on column j alone. */
+int cmpc_plant_step_jvp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
+                                    const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
+                                    double* dDirStateOut, void* stream);
+/* The list path of one tick forwards, positions and orientations together, with the tape arguments of cmpc_contacts_position_vjp_device /
+ * cmpc_contacts_orientation_vjp_device; the index maps are re-derived from the times with the forward's own functions.  One thread per (problem, foot,
+ * column) owns its outputs: copies only, no atomics.  List directions are double [B][k][2][max_contacts][3], orientations in the body-frame tangent.
+ *   merge + sample (phase bit 1; runs BEFORE the solution JVP): merged entry 0 takes the direction of the previous list's active contact,
+ *     dDirPrevList[c][ma]; the entries copied from the planner take dDirPlan[c][first + m - n0] (zero when that lies beyond the array); first tick (dPrevT ==
+ *     dPrevN == NULL): the list's direction is dDirPrevList itself and the planner's directions are not read.  The owner of stage k writes its position
+ *     direction to nominalPos_{c,k+1} of column j of dDirP[B][k][n_p] float (stage 0 also to nominalPos_{c,0} and currentPos_c: 6 (N + 2) rows per column
+ *     are written, the others are left alone) and its orientation direction to omega_{c,k} of dDirRot[B][k][2][N][3] double.  The list's orientation
+ *     direction goes out unchanged: no entry is cut.  dDirList, dDirListRot, the rows of dDirP and dDirRot are written whole; entries at or beyond n are 0.
+ *   adjust (phase bit 2; runs AFTER the solution JVP, it reads dDirX[B][k][n_x] float): where 0 <= land <= N and there is a next contact nx,
+ *     dDirList[c][nx] is OVERWRITTEN with dDirX[pos_c + 3 land] -- the transpose of "nothing of dGradListOut[c][nx] flows on".
+ * A foot that was not sampled (dLand = -2, an empty list, n > max_contacts) passes nothing on.  dOk[b] == 0 gives zeros (phase 2 alone zeroes the list
+ * directions) and dStatus[b] = 5, else 0 (dStatus[B] or NULL).  force_sample_time as above.  phase = 1, 2 or 3.  dDirList is required and must not alias
+ * dDirPrevList; every other direction pointer may be NULL (inputs: zero; outputs: not written). */
+int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, int k, const double* dPlanT, const int* dPlanN,
+                             const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
+                             const double* dDirPrevList, const double* dDirPrevListRot, const double* dDirPlan, const double* dDirPlanRot, const float* dDirX,
+                             double* dDirList, double* dDirListRot, float* dDirP, double* dDirRot, int* dStatus, void* stream);
+/* One tick forwards in k directions, on the tape of cmpc_rollout_tick_vjp_device: no new forward entry point, no change to the tape.
+ * Chain, on one stream: the merge + sample part of cmpc_contacts_jvp_device -> the p direction of every column assembled in float32 (the list's rows; the
+ * state direction on com0 / dcom0 / h0, cmpc_write_state_device's rows; the wrench direction on the fExt / tauExt rows; plus the caller's dDirP) ->
+ * cmpc_solution_jvp_rot_device (called, not copied: its definition, its chunks of eight columns, its workspace, its internal-force rule and its dSens hold) ->
+ * the tick's flags -> the adjust part -> cmpc_plant_step_jvp_cols_device, which reads dDirX, the knot-0 wrench rows of the assembled p direction, dDirModel
+ * and stage 0 of the rotation direction.  The state direction reaches the plant in double and the solve rounded to float32.  As in reverse, the solution map
+ * is taken as independent of x0, and the planner's reference rows are inputs (their direction enters through dDirP).
+ * cmpc_tick_dirs: every pointer may be NULL (zero; `in` itself may be NULL).  With dDirPrevListRot == dDirPlanRot == NULL no rotation direction exists: the
+ * solve and the plant run without one, bit for bit cmpc_solution_jvp_model_device / cmpc_plant_step_jvp_device.
+ * cmpc_tick_dirs_out: dDirStateOut and dDirList are required; dDirList is the next tick's dDirPrevList and must not alias it (nor dDirListRot
+ * dDirPrevListRot).
+ * dTickSens[B][CMPC_SENS] float: dSens of the solution JVP with word 0 replaced by the tick's status, codes and precedence as cmpc_rollout_tick_vjp_device
+ * (5, then 2 and 3, then 4, then 1; a non-finite tape state gives 2, as it does in reverse through the plant VJP).  A flagged problem gets zeros in every output of every column (the transpose of the VJP's zero map); its neighbours
+ * are bit for bit what they are without it.  Results depend on nothing but the problem's own inputs and the column: not on k, the batch position or the
+ * batch size.  Workspace: per-handle HBM allocated on first use and grown when a larger k arrives (that call waits for the device),
+ * 4 (n_x + n_p) + 48 N + 120 bytes per problem and column, plus 4 bytes per problem; calls on one handle run one after the other whatever their streams
+ * (the event of the tick VJP). */
+typedef struct cmpc_tick_dirs {
+    const double* dDirState;                                  /* [B][k][9] */
+    const double* dDirPrevList; const double* dDirPrevListRot; /* [B][k][2][max_contacts][3]: the previous tick's list (first tick: the list itself) */
+    const double* dDirPlan; const double* dDirPlanRot;         /* [B][k][2][max_contacts][3]: the planner's contacts (not read on a first tick) */
+    const float* dDirWrench;                                  /* [B][k][N][6], laid out as cmpc_write_state_device's dWrench */
+    const double* dDirModel;                                  /* [B][k][34] */
+    const float* dDirP;                                       /* [B][k][n_p], added to the assembled p direction: reference rows, boxes.  Entries of R and
+                                                                 Gamma are read as zero, as the solution JVP reads them */
+} cmpc_tick_dirs;
+typedef struct cmpc_tick_dirs_out {
+    double* dDirStateOut;                                     /* [B][k][9], required; may alias dDirState */
+    double* dDirList;                                         /* [B][k][2][max_contacts][3], required */
+    double* dDirListRot;                                      /* [B][k][2][max_contacts][3] or NULL */
+    float* dDirX;                                             /* [B][k][n_x] or NULL: the solution's direction */
+    double* dDirRot;                                          /* [B][k][2][N][3] or NULL: the per-stage rotation direction the solve was given */
+    float* dDirPFull;                                         /* [B][k][n_p] or NULL: the assembled p direction the solve was given */
+} cmpc_tick_dirs_out;
+int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
+                                 const cmpc_tick_dirs_out* out, float* dTickSens, void* stream);
+
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */
 int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, void* stream);

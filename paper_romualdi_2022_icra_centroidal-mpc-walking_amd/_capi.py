@@ -56,6 +56,17 @@ class CmpcTickTape(C.Structure):
         ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("force_sample_time", C.c_int)]
 
 
+class CmpcTickDirs(C.Structure):
+    """mirror of cmpc_tick_dirs (include/cmpc.h): the k direction columns that go into cmpc_rollout_tick_jvp_device, each pointer NULL = zero"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "dDirState", "dDirPrevList", "dDirPrevListRot", "dDirPlan", "dDirPlanRot", "dDirWrench", "dDirModel", "dDirP")]
+
+
+class CmpcTickDirsOut(C.Structure):
+    """mirror of cmpc_tick_dirs_out (include/cmpc.h): what cmpc_rollout_tick_jvp_device writes (the first two required)"""
+    _fields_ = [(k, C.c_void_p) for k in ("dDirStateOut", "dDirList", "dDirListRot", "dDirX", "dDirRot", "dDirPFull")]
+
+
 class CmpcModel(C.Structure):
     """mirror of cmpc_model (include/cmpc.h): the per-problem part of cmpc_config, 34 packed doubles"""
     _fields_ = [
@@ -94,6 +105,7 @@ EXPORTS = [
     "cmpc_plant_step_jvp_device", "cmpc_plant_step_vjp_device", "cmpc_contacts_position_vjp_device", "cmpc_rollout_tick_vjp_device",
     "cmpc_solution_jvp_rot_device", "cmpc_solution_vjp_rot_device", "cmpc_rotation_value_gradient_device", "cmpc_contacts_rotation_vjp_device",
     "cmpc_plant_step_jvp_rot_device", "cmpc_plant_step_vjp_rot_device", "cmpc_contacts_orientation_vjp_device", "cmpc_rollout_tick_vjp_rot_device",
+    "cmpc_plant_step_jvp_cols_device", "cmpc_contacts_jvp_device", "cmpc_rollout_tick_jvp_device",
 ]
 
 _lib = None
@@ -190,6 +202,10 @@ def lib():
             L.cmpc_plant_step_vjp_rot_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp, vp]
             L.cmpc_contacts_orientation_vjp_device.argtypes = [vp, i, d, i] + [vp] * 14
             L.cmpc_rollout_tick_vjp_rot_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 15
+        if hasattr(L, "cmpc_rollout_tick_jvp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_plant_step_jvp_cols_device.argtypes = [vp, fp, fp, fp, d, i, i, vp, fp, fp, vp, vp, vp, vp]
+            L.cmpc_contacts_jvp_device.argtypes = [vp, i, d, i, i, i] + [vp] * 19
+            L.cmpc_rollout_tick_jvp_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape), i, C.POINTER(CmpcTickDirs), C.POINTER(CmpcTickDirsOut), vp, vp]
         if hasattr(L, "cmpc_get_parameters"):   # (absent from earlier rounds' builds of the library, which tools/ab_multi.sh may load as a baseline)
             L.cmpc_get_parameters.argtypes = [vp, fp]
             L.cmpc_get_parameters_device.argtypes = [vp, C.POINTER(vp)]

@@ -73,6 +73,14 @@ extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt,
                                                  const int* land, const int* ok, const double* g_out, const float* g_p, float* g_x, double* g_prev,
                                                  double* g_plan, int* status, hipStream_t stream);
 
+extern "C" int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
+                                          const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
+                                          const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream);
+extern "C" int cmpc_launch_contacts_jvp(int B, int N, int M, int K, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
+                                        const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
+                                        const int* ok, const double* d_prev, const double* d_prev_rot, const double* d_plan, const double* d_plan_rot,
+                                        const float* d_x, double* d_list, double* d_list_rot, float* d_p, double* d_rot, int* status, hipStream_t stream);
+
 struct cmpc_handle_s {
     cmpc_config cfg;
     CmpcLayout L;
@@ -102,7 +110,10 @@ struct cmpc_handle_s {
     char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp[_rot]_device (allocated on first use, sized for both): model gradients of the solve and of
                                  // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] (double) | gX[B][n_x] | gP of
                                  // the solve [B][n_p] | gP of the plant [B][n_p] (float) | the tick's ok words [B] (int)
-    hipEvent_t tick_ev = nullptr; // recorded after the last kernel of a tick VJP: the next one, on any stream, waits for it (one workspace)
+    hipEvent_t tick_ev = nullptr; // recorded after the last kernel of a tick VJP or JVP: the next one, on any stream, waits for it (one workspace each)
+    char* dTickJvpWs = nullptr;  // workspace of cmpc_rollout_tick_jvp_device for tick_jvp_cols columns per problem (allocated on first use, grown when a larger k
+    int tick_jvp_cols = 0;       // arrives): rotation direction [B][k][2][N][3] | its stage 0 [B][k][2][3] | a zero state direction [B][k][9] (double) |
+                                 // dx [B][k][n_x] | the assembled p direction [B][k][n_p] (float) | the tick's ok words [B] (int)
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
     int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
     float hBox[12] = {0};
@@ -305,7 +316,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG); hipFree(h->dSensWs);
     if (h->sens_ev) hipEventDestroy(h->sens_ev);
-    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1435,6 +1446,171 @@ int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now
 {
     return tick_vjp(h, true, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
                     dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream);
+}
+
+// ---- one tick FORWARDS in k directions (include/cmpc.h): list JVP (merge + sample) -> the p direction assembled (cmpc_tick_jvp_assemble_kernel) ->
+// cmpc_solution_jvp_rot_device -> the flags (cmpc_tick_jvp_flag_kernel) -> list JVP (adjust) -> the k-column plant JVP, on one stream ----
+namespace {
+// one workgroup per (problem, column): the column's p direction, float32.  The list kernel has written the nominalPos / currentPos rows; here the state
+// direction goes to com0 / dcom0 / h0 (cmpc_write_state_device's rows, rounded to float32), the wrench direction to the fExt / tauExt rows, every other row
+// is zero, and the caller's extra p direction is added to all of them.
+__global__ __launch_bounds__(128) void cmpc_tick_jvp_assemble_kernel(int N, const double* __restrict__ d_state, const float* __restrict__ d_wrench,
+                                                                     const float* __restrict__ d_extra, float* __restrict__ d_p)
+{
+    const size_t col = blockIdx.x;
+    const CmpcIdx L{N};
+    const int np = L.np();
+    float* dp = d_p + col * np;
+    for (int e = threadIdx.x; e < np; e += 128) {
+        float v = 0.f;
+        const bool listed = (e >= L.pNom(0) && e < L.pNom(0) + 3 * N + 6) || (e >= L.pNom(1) && e < L.pNom(1) + 3 * N + 6);
+        if (listed) v = dp[e];
+        else if (e >= L.pCom0() && e < L.pCom0() + 9) v = d_state ? (float)d_state[col * 9 + (e - L.pCom0())] : 0.f;
+        else if (d_wrench && e >= L.pFext() && e < L.pText()) { const int q = e - L.pFext(); v = d_wrench[(col * N + q / 3) * 6 + q % 3]; }
+        else if (d_wrench && e >= L.pText()) { const int q = e - L.pText(); v = d_wrench[(col * N + q / 3) * 6 + 3 + q % 3]; }
+        dp[e] = d_extra ? v + d_extra[col * np + e] : v;
+    }
+}
+
+// one workgroup per problem, after the solve: the tick's status with the VJP's codes and precedence (cmpc_tick_vjp_combine_kernel; 2 also for a non-finite
+// tape state).  A flagged problem gets
+// zeros in every column of dx, of the p direction and of the rotation direction, and ok = 0 (the adjust part of the list kernel and the plant kernel behind
+// this one then write zeros too); otherwise stage 0 of the rotation direction is gathered for the plant.
+__global__ __launch_bounds__(128) void cmpc_tick_jvp_flag_kernel(int N, int K, const float* __restrict__ info, const int* __restrict__ ok,
+                                                                 const float* __restrict__ state_in, float* __restrict__ sens, float* __restrict__ d_x,
+                                                                 float* __restrict__ d_p, double* __restrict__ d_rot, double* __restrict__ d_rot0,
+                                                                 int* __restrict__ ok_out)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const CmpcIdx L{N};
+    const float s0 = sens[(size_t)b * CMPC_SENS];
+    int status = s0 == s0 ? (int)s0 : 2;
+    // (the state the tick started from is an input of the plant alone here: in reverse a non-finite one reaches the solve through the plant VJP and comes
+    //  back as status 2; forwards it is looked at directly, for the same word)
+    bool finite = true;
+    for (int e = 0; e < 9; ++e) finite = finite && __builtin_isfinite(state_in[(size_t)b * 9 + e]);
+    if (status < 2 && !finite) status = 2;
+    if (status < 2 && info[(size_t)b * CMPC_INFO_N + 5] != 0.f) status = 4;
+    if (ok && ok[b] == 0) status = 5;
+    __syncthreads();   // (every thread has read the status word before thread 0 rewrites it)
+    if (status != 0) {
+        for (size_t e = tid; e < (size_t)K * L.nx(); e += 128) d_x[(size_t)b * K * L.nx() + e] = 0.f;
+        for (size_t e = tid; e < (size_t)K * L.np(); e += 128) d_p[(size_t)b * K * L.np() + e] = 0.f;
+        if (d_rot) for (size_t e = tid; e < (size_t)K * 6 * N; e += 128) d_rot[(size_t)b * K * 6 * N + e] = 0.0;
+        if (d_rot) for (int e = tid; e < K * 6; e += 128) d_rot0[(size_t)b * K * 6 + e] = 0.0;
+    } else if (d_rot) {
+        for (int e = tid; e < K * 6; e += 128)     // e = (column * 2 + foot) * 3 + axis
+            d_rot0[(size_t)b * K * 6 + e] = d_rot[((size_t)b * K * 2 + e / 3) * 3 * N + e % 3];
+    }
+    if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
+}
+}  // namespace
+
+int cmpc_plant_step_jvp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
+                                    const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
+                                    double* dDirStateOut, void* stream)
+{
+    if (!h || !dX || !dP || !dStateIn || !dDirState || !dDirStateOut || !(step > 0) || substeps < 1 || k < 1)
+        return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_jvp_cols_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_plant_jvp_cols(h->cfg.horizon, h->B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
+                                        dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant JVP (columns) launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, int k, const double* dPlanT, const int* dPlanN,
+                             const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
+                             const double* dDirPrevList, const double* dDirPrevListRot, const double* dDirPlan, const double* dDirPlanRot, const float* dDirX,
+                             double* dDirList, double* dDirListRot, float* dDirP, double* dDirRot, int* dStatus, void* stream)
+{
+    if (!h || max_contacts < 1 || phase < 1 || phase > 3 || k < 1 || !dListT || !dListN || !dDirList)
+        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: bad argument");
+    const bool merge = dPrevT || dPrevN;
+    if ((phase & 1) && merge && (!dPrevT || !dPrevN || !dPlanT || !dPlanN))
+        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: a merge tick needs the planner's and the previous tick's times and counts");
+    if (dDirList == dDirPrevList || (dDirListRot && dDirListRot == dDirPrevListRot))
+        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: the outgoing list's directions must not alias the previous list's");
+    long long dt_ns = 0;
+    if (force_sample_time) {
+        dt_ns = snap_dt_ns(h->cfg.sampling_time);
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: force_sample_time needs a sampling time of at least 1 ns");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = cmpc_launch_contacts_jvp(h->B, h->cfg.horizon, max_contacts, k, h->cfg.sampling_time, now, phase, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
+                                      dListN, dLand, dOk, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirX, dDirList, dDirListRot, dDirP, dDirRot,
+                                      dStatus, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("list JVP launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
+                                 const cmpc_tick_dirs_out* out, float* dTickSens, void* stream)
+{
+    if (!h || !tape || max_contacts < 1 || k < 1 || !out || !out->dDirStateOut || !out->dDirList || !dTickSens)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: null argument");
+    if (!tape->dX || !tape->dP || !tape->dLamG || !tape->dState || !tape->dInfo || !tape->dLand || !tape->dListT || !tape->dListN ||
+        !(tape->plant_step > 0) || tape->plant_substeps < 1)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: incomplete tape");
+    const bool merge = tape->dPrevT || tape->dPrevN;
+    if (merge && (!tape->dPrevT || !tape->dPrevN || !tape->dPlanT || !tape->dPlanN))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: a merge tick's tape needs the planner's and the previous tick's times and counts");
+    const cmpc_tick_dirs none = {};
+    if (!in) in = &none;
+    if (out->dDirList == in->dDirPrevList || (out->dDirListRot && out->dDirListRot == in->dDirPrevListRot))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: the outgoing list's directions must not alias the previous list's");
+    long long dt_ns = 0;
+    if (tape->force_sample_time) {
+        dt_ns = snap_dt_ns(h->cfg.sampling_time);
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: force_sample_time needs a sampling time of at least 1 ns");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int B = h->B, N = h->cfg.horizon;
+    const size_t cols = (size_t)B * k, nx = h->L.nx, np = h->L.np;
+    if (k > h->tick_jvp_cols) {     // (hipFree waits for the device: no earlier call still reads the smaller workspace)
+        if (h->dTickJvpWs) HIPCHK(h, hipFree(h->dTickJvpWs));
+        h->dTickJvpWs = nullptr; h->tick_jvp_cols = 0;
+        HIPCHK(h, hipMalloc(&h->dTickJvpWs, cols * (sizeof(double) * (6 * (size_t)N + 15) + sizeof(float) * (nx + np)) + sizeof(int) * (size_t)B));
+        h->tick_jvp_cols = k;
+    }
+    // (carved for this call's k: the arrays are [B][k][...] without gaps)
+    double* wsRot = reinterpret_cast<double*>(h->dTickJvpWs);
+    double* wsRot0 = wsRot + cols * 6 * N;
+    double* wsState = wsRot0 + cols * 6;
+    float* wsX = reinterpret_cast<float*>(wsState + cols * 9);
+    float* wsP = wsX + cols * nx;
+    int* okTick = reinterpret_cast<int*>(wsP + cols * np);
+    const bool rot = in->dDirPrevListRot || in->dDirPlanRot;
+    double* dRot = !rot ? nullptr : out->dDirRot ? out->dDirRot : wsRot;
+    float* dDX = out->dDirX ? out->dDirX : wsX;
+    float* dPF = out->dDirPFull ? out->dDirPFull : wsP;
+    if (!h->tick_ev) HIPCHK(h, hipEventCreateWithFlags(&h->tick_ev, hipEventDisableTiming));
+    else HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));
+    const double* dState = in->dDirState;
+    if (!dState) {
+        HIPCHK(h, hipMemsetAsync(wsState, 0, sizeof(double) * cols * 9, st));
+        dState = wsState;
+    }
+    if (!rot && out->dDirRot) HIPCHK(h, hipMemsetAsync(out->dDirRot, 0, sizeof(double) * cols * 6 * N, st));
+    int rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 1, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
+                                      tape->dListT, tape->dListN, tape->dLand, tape->dOk, in->dDirPrevList, in->dDirPrevListRot, in->dDirPlan, in->dDirPlanRot,
+                                      nullptr, out->dDirList, out->dDirListRot, dPF, dRot, nullptr, st);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (merge + sample) launch: ") + hipGetErrorString((hipError_t)rc));
+    hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, st, N, in->dDirState, in->dDirWrench, in->dDirP, dPF);
+    HIPCHK(h, hipGetLastError());
+    rc = cmpc_solution_jvp_rot_device(h, tape->dX, tape->dP, tape->dLamG, dPF, in->dDirModel, dRot, k, dDX, dTickSens, stream);
+    if (rc != CMPC_OK) return rc;
+    hipLaunchKernelGGL(cmpc_tick_jvp_flag_kernel, dim3(B), dim3(128), 0, st, N, k, tape->dInfo, tape->dOk, tape->dState, dTickSens, dDX, dPF, dRot, wsRot0, okTick);
+    HIPCHK(h, hipGetLastError());
+    rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 2, dt_ns, nullptr, nullptr, nullptr, nullptr, tape->dListT, tape->dListN,
+                                  tape->dLand, okTick, nullptr, nullptr, nullptr, nullptr, dDX, out->dDirList, out->dDirListRot, nullptr, nullptr, nullptr, st);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (adjust) launch: ") + hipGetErrorString((hipError_t)rc));
+    rc = cmpc_launch_plant_jvp_cols(N, B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
+                                    tape->plant_substeps, dState, dDX, dPF, in->dDirModel, rot ? wsRot0 : nullptr, okTick, out->dDirStateOut, st);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
+    HIPCHK(h, hipEventRecord(h->tick_ev, st));
+    return CMPC_OK;
 }
 
 // the handle's own contact blocks from contact lists (what the class facade's setContactPhaseList calls)

@@ -249,6 +249,92 @@ __global__ __launch_bounds__(128) void cmpc_contacts_orientation_vjp_kernel(int 
     }
 }
 
+// The list path of one tick FORWARDS, positions and orientations together (include/cmpc.h, cmpc_contacts_jvp_device): the transpose of the position and the
+// orientation VJP above, with their tape arguments and the same index maps (cmpc_merge_sources, cmpc_stage_owner, cmpc_next_contact).  One thread per
+// (problem, foot, column) owns its outputs -- the foot's entries of the list directions, its nominalPos / currentPos rows of the column's p direction and
+// its stages of the rotation direction: copies only, no sums, no atomics.  Phase bit 1 (before the solve): merge + sample, every output written whole;
+// phase bit 2 (after it): the entry the step adjustment overwrote takes the solution's direction at the landing knot.  Directions are [B][K][...].
+__global__ __launch_bounds__(128) void cmpc_contacts_jvp_kernel(int B, int N, int M, int K, double dt, double now, int phase, long long snap_dt_ns,
+                                                                const double* __restrict__ plan_t, const int* __restrict__ plan_n,
+                                                                const double* __restrict__ prev_t, const int* __restrict__ prev_n,
+                                                                const double* __restrict__ list_t, const int* __restrict__ list_n,
+                                                                const int* __restrict__ land, const int* __restrict__ ok,
+                                                                const double* __restrict__ d_prev, const double* __restrict__ d_prev_rot,
+                                                                const double* __restrict__ d_plan, const double* __restrict__ d_plan_rot,
+                                                                const float* __restrict__ d_x, double* __restrict__ d_list, double* __restrict__ d_list_rot,
+                                                                float* __restrict__ d_p, double* __restrict__ d_rot, int* __restrict__ status)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (problem * 2 + foot) * K + column
+    if (i >= 2LL * B * K) return;
+    const int e = (int)(i / K), j = (int)(i - (long long)e * K);
+    const int b = e >> 1, c = e & 1;
+    const CmpcIdx L{N};
+    const size_t o = (size_t)e * M;                            // the foot's times
+    const size_t od = (((size_t)b * K + j) * 2 + c) * M;       // the foot's entries of column j
+    const bool merge = prev_t != nullptr;
+    const bool good = !ok || ok[b] != 0;
+    if (status && c == 0 && j == 0) status[b] = good ? 0 : 5;
+    const int n = list_n[e];
+    const bool sampled = good && n >= 1 && n <= M && !(land && land[e] == -2);
+    if (phase & 1) {
+        int ma = -1, first = -1;
+        if (sampled && merge) cmpc_merge_sources(M, now, snap_dt_ns, plan_t + 2 * o, plan_n[e], prev_t + 2 * o, prev_n[e], ma, first);
+        const int n0 = ma >= 0 ? 1 : 0;
+        auto src = [&](const double* dv, const double* dl, int m) -> const double* {    // (null: the entry's direction is zero)
+            if (!merge) return dv ? dv + 3 * (od + m) : nullptr;
+            if (m < n0) return dv ? dv + 3 * (od + ma) : nullptr;
+            if (first < 0 || !dl || first + m - n0 >= M) return nullptr;
+            return dl + 3 * (od + first + m - n0);
+        };
+        for (int m = 0; m < M; ++m) {
+            const bool in = sampled && m < n;
+            const double* sp = in ? src(d_prev, d_plan, m) : nullptr;
+            const double* sr = in ? src(d_prev_rot, d_plan_rot, m) : nullptr;
+            for (int a = 0; a < 3; ++a) {
+                if (d_list) d_list[3 * (od + m) + a] = sp ? sp[a] : 0.0;
+                if (d_list_rot) d_list_rot[3 * (od + m) + a] = sr ? sr[a] : 0.0;
+            }
+        }
+        if (d_p || d_rot) {
+            float* dp = d_p ? d_p + ((size_t)b * K + j) * L.np() : nullptr;
+            double* dr = d_rot ? d_rot + (((size_t)b * K + j) * 2 + c) * 3 * N : nullptr;
+            for (int k = 0; k < N; ++k) {
+                const double* sp = nullptr;
+                const double* sr = nullptr;
+                if (sampled) {
+                    bool act;
+                    const int w = cmpc_stage_owner(list_t + 2 * o, n, now + k * dt, &act);
+                    sp = src(d_prev, d_plan, w);
+                    sr = src(d_prev_rot, d_plan_rot, w);
+                }
+                for (int a = 0; a < 3; ++a) {
+                    const float v = sp ? (float)sp[a] : 0.f;
+                    if (dp) {
+                        if (k == 0) { dp[L.pNom(c) + a] = v; dp[L.pCur(c) + a] = v; }
+                        dp[L.pNom(c) + 3 * (k + 1) + a] = v;
+                    }
+                    if (dr) dr[3 * k + a] = sr ? sr[a] : 0.0;
+                }
+            }
+        }
+    }
+    if (phase & 2) {
+        if (!good) {                                           // (a flagged tick: nothing of it goes on)
+            for (int m = 0; m < 3 * M; ++m) {
+                if (d_list) d_list[3 * od + m] = 0.0;
+                if (d_list_rot) d_list_rot[3 * od + m] = 0.0;
+            }
+            return;
+        }
+        const int lk = land ? land[e] : -1;
+        if (!sampled || lk < 0 || lk > N || !d_list) return;
+        const int nx = cmpc_next_contact(list_t + 2 * o, n, now);
+        if (nx < 0) return;
+        for (int a = 0; a < 3; ++a)
+            d_list[3 * (od + nx) + a] = d_x ? (double)d_x[((size_t)b * K + j) * L.nx() + L.oPos(c) + 3 * lk + a] : 0.0;
+    }
+}
+
 // measured state (and external wrench) into the parameter rows of every problem: setState on the device
 __global__ __launch_bounds__(128) void cmpc_write_state_kernel(int B, int N, const float* __restrict__ state, const float* __restrict__ wrench,
                                                                float* __restrict__ P)
@@ -333,6 +419,17 @@ extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt,
 {
     hipLaunchKernelGGL(cmpc_contacts_position_vjp_kernel, dim3((2 * B + 127) / 128), dim3(128), 0, stream, B, N, M, dt, now, phase, snap_dt_ns, plan_t, plan_n,
                        prev_t, prev_n, list_t, list_n, land, ok, g_out, g_p, g_x, g_prev, g_plan, status);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_contacts_jvp(int B, int N, int M, int K, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
+                                        const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
+                                        const int* ok, const double* d_prev, const double* d_prev_rot, const double* d_plan, const double* d_plan_rot,
+                                        const float* d_x, double* d_list, double* d_list_rot, float* d_p, double* d_rot, int* status, hipStream_t stream)
+{
+    const long long threads = 2LL * B * K;
+    hipLaunchKernelGGL(cmpc_contacts_jvp_kernel, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, stream, B, N, M, K, dt, now, phase, snap_dt_ns, plan_t,
+                       plan_n, prev_t, prev_n, list_t, list_n, land, ok, d_prev, d_prev_rot, d_plan, d_plan_rot, d_x, d_list, d_list_rot, d_p, d_rot, status);
     return (int)hipGetLastError();
 }
 

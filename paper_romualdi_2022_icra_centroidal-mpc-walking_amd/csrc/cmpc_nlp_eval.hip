@@ -1396,6 +1396,32 @@ __global__ __launch_bounds__(256) void cmpc_plant_jvp_kernel(int N, int B, float
     plant_jvp_problem<ROT>(N, b, P, q, dir_state, dir_x, dir_p, dir_model, dir_rot, out);
 }
 
+// k columns per problem (include/cmpc.h, cmpc_plant_step_jvp_cols_device): one thread per (problem, column), the same two device functions on direction
+// arrays [B][K][...] -- plant_jvp_problem indexes its directions by problem, so column j of problem b is handed over as the array moved by b (K - 1) + j
+// rows: entry b of that is entry b K + j of the caller's.  ok (the tick JVP's flags; null otherwise): a problem whose word is 0 gets zeros.
+template <bool ROT>
+__global__ __launch_bounds__(256) void cmpc_plant_jvp_cols_kernel(int N, int B, int K, float grav, const float* __restrict__ corners, int corners_stride,
+                                                                  const float* __restrict__ X, const float* __restrict__ P,
+                                                                  const float* __restrict__ state_in, float h, int nsub, const double* dir_state,
+                                                                  const float* __restrict__ dir_x, const float* __restrict__ dir_p,
+                                                                  const double* __restrict__ dir_model, const double* __restrict__ dir_rot,
+                                                                  const int* __restrict__ ok, double* out)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * K) return;
+    const int b = (int)(i / K), j = (int)(i - (long long)b * K);
+    const size_t col = (size_t)b * (K - 1) + j;
+    if (ok && ok[b] == 0) {
+        for (int e = 0; e < 9; ++e) out[((size_t)b * K + j) * 9 + e] = 0.0;
+        return;
+    }
+    const CmpcIdx L{N};
+    PlantPartials q;
+    plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
+    plant_jvp_problem<ROT>(N, b, P, q, dir_state + col * 9, dir_x ? dir_x + col * L.nx() : nullptr, dir_p ? dir_p + col * L.np() : nullptr,
+                           dir_model ? dir_model + col * CMPC_MODEL_DOUBLES : nullptr, ROT ? dir_rot + col * 6 : nullptr, out + col * 9);
+}
+
 template <bool ROT>
 __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
@@ -1599,6 +1625,21 @@ extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCor
     else
         hipLaunchKernelGGL(cmpc_plant_jvp_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
                            nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOut);
+    return (int)hipGetLastError();
+}
+
+// the same with K columns per problem, directions [B][K][...]; dOk [B] or null (a problem whose word is 0 gets zeros)
+extern "C" int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
+                                          const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
+                                          const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream)
+{
+    const unsigned blocks = (unsigned)(((long long)B * K + 255) / 256);
+    if (dDirRot0)
+        hipLaunchKernelGGL(cmpc_plant_jvp_cols_kernel<true>, dim3(blocks), dim3(256), 0, stream, N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOk, dOut);
+    else
+        hipLaunchKernelGGL(cmpc_plant_jvp_cols_kernel<false>, dim3(blocks), dim3(256), 0, stream, N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
+                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOk, dOut);
     return (int)hipGetLastError();
 }
 

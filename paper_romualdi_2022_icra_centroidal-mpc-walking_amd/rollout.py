@@ -351,6 +351,66 @@ class WalkingRollout:
         cur.wait_stream(ls)
         return out
 
+    def forward_sensitivity(self, tape, dir_state0=None, dir_list0=None, dir_list_rot0=None, dir_plan=None, dir_plan_rot=None, dir_push=None, dir_models=None,
+                            dir_wrench=None, solutions=False):
+        """The taped roll-out in forward mode (cmpc_rollout_tick_jvp_device, one call per tick, first tick first): how the whole trajectory moves along k
+        input directions at once -- the transpose of backward(rot=True), input for output.  Every direction carries a column axis k right after B (CUDA
+        tensors or numpy; None: zero): dir_state0[B, k, 9]; dir_list0 / dir_list_rot0[B, k, 2, M, 3], the positions and orientations (body-frame tangent)
+        of the first tick's lists; dir_plan / dir_plan_rot[B, k, 2, M, 3], the planner's contacts, read by every merge; dir_push[B, k, 3], which enters
+        the wrench rows of the knots and ticks the push was written to (the transpose of backward's push sum); dir_models[B, k, 34];
+        dir_wrench[ticks, B, k, N, 6] float32.
+        -> dict(states[ticks + 1, B, k, 9] float64: the directions of the states before each tick and of the final state; list, list_rot[B, k, 2, M, 3]:
+        the final lists' directions; X[ticks, B, k, n_x] float32 when solutions=True; status[ticks, B] int32: 0, or why that tick of that problem passed
+        nothing on; removed[ticks, B]: word 6 of each tick's dSens -- include/cmpc.h)."""
+        torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
+        ticks = tape["ticks"]
+        T = len(ticks)
+        M = ticks[0]["list_t"].shape[2]
+
+        def as_dir(a, dtype, tail, lead=()):
+            if a is None:
+                return None
+            a = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, dtype).contiguous()
+            assert a.dim() == len(lead) + 2 + len(tail) and tuple(a.shape[:len(lead) + 1]) == lead + (B,) and tuple(a.shape[len(lead) + 2:]) == tail, \
+                f"direction of shape {tuple(a.shape)}: expected {lead + (B, 'k') + tail}"
+            return a
+        f32, f64 = torch.float32, torch.float64
+        ds, dl, dlr = as_dir(dir_state0, f64, (9,)), as_dir(dir_list0, f64, (2, M, 3)), as_dir(dir_list_rot0, f64, (2, M, 3))
+        dpl, dplr = as_dir(dir_plan, f64, (2, M, 3)), as_dir(dir_plan_rot, f64, (2, M, 3))
+        dpush, dmod, dwr = as_dir(dir_push, f32, (3,)), as_dir(dir_models, f64, (34,)), as_dir(dir_wrench, f32, (N, 6), lead=(T,))
+        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod) if a is not None} | ({int(dwr.shape[2])} if dwr is not None else set())
+        assert len(ks) == 1, "forward_sensitivity: no direction, or directions of different k"
+        k = ks.pop()
+        rot = dlr is not None or dplr is not None
+        out = dict(states=torch.zeros((T + 1, B, k, 9), dtype=f64, device=self.dev), status=torch.zeros((T, B), dtype=torch.int32, device=self.dev),
+                   removed=torch.zeros((T, B), dtype=f32, device=self.dev))
+        if solutions:
+            out["X"] = torch.zeros((T, B, k, L.nx), dtype=f32, device=self.dev)
+        ls = self.solver.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            if ds is not None:
+                out["states"][0] = ds
+            for i, tk in enumerate(ticks):
+                w = None if dwr is None else dwr[i]
+                if dpush is not None and tk["push_knots"] > 0:
+                    w = torch.zeros((B, k, N, 6), dtype=f32, device=self.dev) if w is None else w.clone()
+                    w[:, :, :tk["push_knots"], :3] += dpush[:, :, None, :]
+                r = self.solver.rollout_tick_jvp_device(tk["now"], tk, k, dDirState=ds, dDirPrevList=dl, dDirPrevListRot=dlr, dDirPlan=dpl, dDirPlanRot=dplr,
+                                                        dDirWrench=w, dDirModel=dmod, x=solutions, out_state=out["states"][i + 1])
+                ds, dl = r["state"], r["list"]
+                if rot:
+                    dlr = r["list_rot"]
+                if solutions:
+                    out["X"][i] = r["x"]
+                out["status"][i] = r["sens"][:, 0].to(torch.int32)
+                out["removed"][i] = r["sens"][:, 6]
+            out["list"] = dl
+            out["list_rot"] = dlr if rot else torch.zeros((B, k, 2, M, 3), dtype=f64, device=self.dev)
+        cur.wait_stream(ls)
+        return out
+
 
 def yaw_plan_poses(pose, plan_yaw):
     """pose[B, 2, M, 7] float32 (x y z, quaternion w x y z) with every contact yawed about its own z axis by plan_yaw[B, 2, M] float64:
@@ -408,5 +468,21 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
                     r["models"] if ctx.needs_input_grad[2] else None,
                     (r["plan_rot"][..., 2] + r["list_rot0"][..., 2]) if ctx.rot and ctx.needs_input_grad[3] else None)
+
+        @staticmethod
+        def jvp(ctx, t_state0, t_push, t_models, t_yaw):
+            """torch.autograd.forward_ad: forward_sensitivity at k = 1 on the tape the forward left.  A yaw tangent is d psi e_z on the planner's
+            orientations and on the first tick's list, the transpose of what backward returns for plan_yaw."""
+            col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
+            yaw = None
+            if t_yaw is not None:
+                yaw = torch.zeros(tuple(t_yaw.shape[:1]) + (1,) + tuple(t_yaw.shape[1:]) + (3,), dtype=torch.float64, device=rollout.dev)
+                yaw[..., 2] = t_yaw.detach().to(rollout.dev, torch.float64)[:, None]
+            if all(t is None for t in (t_state0, t_push, t_models, t_yaw)):
+                return torch.zeros((len(ctx.tape["ticks"]) + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
+            r = rollout.forward_sensitivity(ctx.tape, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
+                                            dir_models=col(t_models, torch.float64), dir_plan_rot=yaw, dir_list_rot0=yaw)
+            rollout.last_forward = r
+            return r["states"][:, :, 0].to(torch.float32)
 
     return _Fn.apply(state0, push, models, plan_yaw)

@@ -601,6 +601,89 @@ class BatchSolver:
         self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_rot_device(self._h, M, float(now), ct, *args, *rargs, st))
         return out
 
+    # ---- the roll-out tick forwards, in k directions (include/cmpc.h, "the roll-out tick FORWARDS") ----
+    def plant_step_jvp_cols_device(self, dX, dP, dState, dDirState, dDirX=None, dDirP=None, dDirModel=None, dDirRot0=None, step=0.01, substeps=6, out=None):
+        """cmpc_plant_step_jvp_cols_device: plant_step_jvp_device with k columns per problem -- dDirState[B, k, 9] float64, dDirX[B, k, n_x] /
+        dDirP[B, k, n_p] float32, dDirModel[B, k, 34] and dDirRot0[B, k, 2, 3] float64 (None: zero) -> d state'[B, k, 9] float64; column j is bit-equal to
+        plant_step_jvp_device on column j."""
+        import torch
+        L, B = self.layout, self.batch
+        assert dDirState.dim() == 3
+        k = int(dDirState.shape[1])
+        if out is None:
+            out = torch.empty((B, k, 9), dtype=torch.float64, device=dX.device)
+        args = (self._opt(dDirState, torch.float64, (B, k, 9), "dDirState"), self._opt(dDirX, torch.float32, (B, k, L.nx), "dDirX"),
+                self._opt(dDirP, torch.float32, (B, k, L.np), "dDirP"), self._opt(dDirModel, torch.float64, (B, k, _capi.MODEL_DOUBLES), "dDirModel"),
+                self._opt(dDirRot0, torch.float64, (B, k, 2, 3), "dDirRot0"), self._opt(out, torch.float64, (B, k, 9), "out"))
+        self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_cols_device(self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step),
+                                                                                     int(substeps), k, *args, st))
+        return out
+
+    def contacts_jvp_device(self, now, list_t, list_n, land, k, plan=None, prev=None, ok=None, dDirPrevList=None, dDirPrevListRot=None, dDirPlan=None,
+                            dDirPlanRot=None, dDirX=None, phase=3, force_sample_time=False, out=None, out_rot=None, dDirP=None, rot=True):
+        """The list path of one tick forwards (cmpc_contacts_jvp_device), the transpose of contacts_position_vjp_device + contacts_orientation_vjp_device
+        with their tape arguments: directions [B, k, 2, M, 3] float64 of the previous list's and the planner's positions and orientations (None: zero),
+        dDirX[B, k, n_x] float32 (phase bit 2: the landing entry takes the solution's direction).  phase 1: merge + sample; 2: adjust (out / out_rot
+        are then the phase-1 results, updated in place); 3: both.  -> dict(list, list_rot [B, k, 2, M, 3] float64, p[B, k, n_p] float32 (dDirP or a
+        zero tensor: only the nominalPos / currentPos rows are written), rot[B, k, 2, N, 3] float64 (rot=False: None), status[B] int32)."""
+        import torch
+        L, B, M, dev = self.layout, self.batch, list_t.shape[2], list_t.device
+        g3 = (B, k, 2, M, 3)
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        assert list_t.is_cuda and list_t.dtype == f64 and list_t.is_contiguous() and tuple(list_t.shape) == (B, 2, M, 2)
+        res = dict(list=out if out is not None else torch.zeros(g3, dtype=f64, device=dev),
+                   list_rot=out_rot if out_rot is not None else torch.zeros(g3, dtype=f64, device=dev), p=None, rot=None,
+                   status=torch.empty((B,), dtype=i32, device=dev))
+        if phase & 1:
+            res["p"] = dDirP if dDirP is not None else torch.zeros((B, k, L.np), dtype=f32, device=dev)
+            res["rot"] = torch.empty((B, k, 2, L.N, 3), dtype=f64, device=dev) if rot else None
+        tn = lambda pair: (None, None) if pair is None else (self._opt(pair[0], f64, (B, 2, M, 2), "times"), self._opt(pair[1], i32, (B, 2), "counts"))
+        (plt, pln), (pvt, pvn) = tn(plan), tn(prev)
+        args = (self._opt(list_n, i32, (B, 2), "list_n"), self._opt(land, i32, (B, 2), "land"), self._opt(ok, i32, (B,), "ok"),
+                self._opt(dDirPrevList, f64, g3, "dDirPrevList"), self._opt(dDirPrevListRot, f64, g3, "dDirPrevListRot"),
+                self._opt(dDirPlan, f64, g3, "dDirPlan"), self._opt(dDirPlanRot, f64, g3, "dDirPlanRot"), self._opt(dDirX, f32, (B, k, L.nx), "dDirX"),
+                self._opt(res["list"], f64, g3, "out"), self._opt(res["list_rot"], f64, g3, "out_rot"), self._opt(res["p"], f32, (B, k, L.np), "dDirP"),
+                self._opt(res["rot"], f64, (B, k, 2, L.N, 3), "rot"), res["status"].data_ptr())
+        self._launch(dev, lambda st: self._lib.cmpc_contacts_jvp_device(
+            self._h, M, float(now), int(phase), 1 if force_sample_time else 0, int(k), plt, pln, pvt, pvn, list_t.data_ptr(), *args, st))
+        return res
+
+    def rollout_tick_jvp_device(self, now, tape, k, dDirState=None, dDirPrevList=None, dDirPrevListRot=None, dDirPlan=None, dDirPlanRot=None, dDirWrench=None,
+                                dDirModel=None, dDirP=None, x=False, rot=False, p_full=False, out_state=None):
+        """cmpc_rollout_tick_jvp_device: one tick forwards in k directions, on the tape of rollout_tick_vjp_device.  Directions (each None: zero), with the
+        column axis behind the batch axis: dDirState[B,k,9], dDirPrevList / dDirPrevListRot / dDirPlan / dDirPlanRot[B,k,2,M,3], dDirModel[B,k,34] float64;
+        dDirWrench[B,k,N,6], dDirP[B,k,n_p] float32.  Returns dict(state[B,k,9], list[B,k,2,M,3], list_rot[B,k,2,M,3] float64, x[B,k,n_x] float32 (x=True),
+        rot[B,k,2,N,3] float64 (rot=True), p[B,k,n_p] float32 (p_full=True: the assembled p direction), sens[B,CMPC_SENS] float32 with the tick's status
+        in word 0) -- the keys of rollout_tick_vjp_device's dict, each holding the direction of what that one holds the gradient of."""
+        import torch
+        from ._capi import CmpcTickDirs, CmpcTickDirsOut, CmpcTickTape
+        L, B, N = self.layout, self.batch, self.cfg.N
+        lt = tape["list_t"]
+        M, dev = lt.shape[2], lt.device
+        k = int(k)
+        g3 = (B, k, 2, M, 3)
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        tt, tn = (B, 2, M, 2), (B, 2)
+        ct = CmpcTickTape(self._opt(tape["X"], f32, (B, L.nx), "X"), self._opt(tape["P"], f32, (B, L.np), "P"), self._opt(tape["lam_g"], f32, (B, L.ng), "lam_g"),
+                          self._opt(tape["state"], f32, (B, 9), "state"), self._opt(tape["info"], f32, (B, _capi.INFO), "info"),
+                          self._opt(tape.get("ok"), i32, (B,), "ok"), self._opt(tape["land"], i32, tn, "land"),
+                          self._opt(tape.get("plan_t"), f64, tt, "plan_t"), self._opt(tape.get("plan_n"), i32, tn, "plan_n"),
+                          self._opt(tape.get("prev_t"), f64, tt, "prev_t"), self._opt(tape.get("prev_n"), i32, tn, "prev_n"),
+                          self._opt(lt, f64, tt, "list_t"), self._opt(tape["list_n"], i32, tn, "list_n"),
+                          float(tape["step"]), int(tape["substeps"]), 1 if tape.get("force_sample_time") else 0)
+        din = CmpcTickDirs(self._opt(dDirState, f64, (B, k, 9), "dDirState"), self._opt(dDirPrevList, f64, g3, "dDirPrevList"),
+                           self._opt(dDirPrevListRot, f64, g3, "dDirPrevListRot"), self._opt(dDirPlan, f64, g3, "dDirPlan"),
+                           self._opt(dDirPlanRot, f64, g3, "dDirPlanRot"), self._opt(dDirWrench, f32, (B, k, N, 6), "dDirWrench"),
+                           self._opt(dDirModel, f64, (B, k, _capi.MODEL_DOUBLES), "dDirModel"), self._opt(dDirP, f32, (B, k, L.np), "dDirP"))
+        out = dict(state=out_state if out_state is not None else torch.empty((B, k, 9), dtype=f64, device=dev), list=torch.empty(g3, dtype=f64, device=dev),
+                   list_rot=torch.empty(g3, dtype=f64, device=dev), x=torch.empty((B, k, L.nx), dtype=f32, device=dev) if x else None,
+                   rot=torch.empty((B, k, 2, N, 3), dtype=f64, device=dev) if rot else None,
+                   p=torch.empty((B, k, L.np), dtype=f32, device=dev) if p_full else None, sens=torch.empty((B, _capi.SENS), dtype=f32, device=dev))
+        dout = CmpcTickDirsOut(self._opt(out["state"], f64, (B, k, 9), "out_state"), out["list"].data_ptr(), out["list_rot"].data_ptr(),
+                               out["x"].data_ptr() if x else None, out["rot"].data_ptr() if rot else None, out["p"].data_ptr() if p_full else None)
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_jvp_device(self._h, M, float(now), ct, k, din, dout, out["sens"].data_ptr(), st))
+        return out
+
     def closed_loop_transition_device(self, dX, dP, dLamG, dState, step=0.01, substeps=6):
         """A_cl[B, 9, 9] = d state' / d state of one tick (solve + plant, float64; row i = component i of state'): the nine-column JVP of
         feedback_gain_device (dx* / d(com0, dcom0, h0)) pushed column by column through the plant JVP together with the plant's own d state' / d state.
