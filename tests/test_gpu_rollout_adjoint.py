@@ -51,8 +51,12 @@ def _plant_inputs(cfg, B, seed):
 def test_plant_jvp_vjp_kernels_match_the_restatement():
     """Both sides compute in float64 from identical float32 inputs: double outputs <= 1e-12 relative, dGradX / dGradP (float32) to one rounding; the adjoint
     identity on device outputs <= ADJ; per-problem models; bit-identical across batch position and batch size."""
+    _check_plant_kernels(cm.config.ergocub_gazebo_v1(20, 0.06))
+
+
+def _check_plant_kernels(cfg):
+    """the body of test_plant_jvp_vjp_kernels_match_the_restatement at cfg's horizon (tests/test_gpu_rollout_horizons.py runs it at others)"""
     import torch
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
     L = cm.Layout(cfg.N)
     B, step, nsub = 16, 0.01, 6
     X, P, state, models = _plant_inputs(cfg, B, 4)
@@ -90,7 +94,7 @@ def test_plant_jvp_vjp_kernels_match_the_restatement():
             lhs = g[b] @ out[b]
             rhs = gS[b] @ dS[b] + gX[b].astype(np.float64) @ dX[b] + gP[b].astype(np.float64) @ dP[b] + gM[b] @ dM[b]
             worst["adjoint"] = max(worst["adjoint"], abs(lhs - rhs) / max(abs(lhs), abs(rhs)))
-    print("\nplant kernels against the restatement: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()) +
+    print(f"\nplant kernels N = {cfg.N} against the restatement: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()) +
           f"  (bounds: float64 groups {F64:.0e}, float32 groups one rounding {ULP32:.2e}, adjoint {ADJ:.0e})")
     assert worst["jvp"] <= F64 and worst["g_state"] <= F64 and worst["g_model"] <= F64 and worst["adjoint"] <= ADJ
     assert not np.array_equal(outs[False][0], outs[True][0])          # the model table is read
@@ -144,8 +148,12 @@ def test_list_adjoint_kernel_equals_the_restatement(M, first_tick, now_k, snap):
     """float64 sums of float32-exact inputs in a fixed order (the entry's own dGradListOut, then the sampling's terms stage by stage, k = 0 .. N-1, within
     stage 0 nominalPos_0, currentPos, nominalPos_1): equal to the restatement to 1e-12; the first tick, a failed merge (zero outputs, status 5) and
     max_contacts above 16 included, and off-grid planner times with force_sample_time."""
+    _check_list_adjoint(cm.config.ergocub_gazebo_v1(20, 0.06), M, first_tick, now_k, snap)
+
+
+def _check_list_adjoint(cfg, M, first_tick, now_k, snap):
+    """the body of test_list_adjoint_kernel_equals_the_restatement at cfg's horizon and sampling time"""
     import torch
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
     L = cm.Layout(cfg.N)
     B = 24
     now = cfg.sampling_time * now_k
@@ -182,7 +190,7 @@ def test_list_adjoint_kernel_equals_the_restatement(M, first_tick, now_k, snap):
             worst = max(worst, float(np.abs(got - ref).max() / scale))
         assert np.array_equal(gx[b], (gx0[b].astype(np.float64) + r["x"]).astype(np.float32))     # one float32 sum per entry: exact
         adjusted += int(r["x"].any())
-    print(f"\nlist adjoint kernel M={M} first_tick={first_tick} now={now:.2f}: worst gap {worst:.2e} (bound {F64:.0e}), feet adjusted in {adjusted} problems")
+    print(f"\nlist adjoint kernel N={cfg.N} dt={cfg.sampling_time} M={M} first_tick={first_tick} now={now:.2f}: worst gap {worst:.2e} (bound {F64:.0e}), feet adjusted in {adjusted} problems")
     assert worst <= F64
     if not first_tick:
         assert status[5] == 5 and okh[5] == 0 and not gprev[5].any() and np.array_equal(gx[5], gx0[5]) and np.array_equal(gplan[5], gplan0[5])
@@ -191,16 +199,17 @@ def test_list_adjoint_kernel_equals_the_restatement(M, first_tick, now_k, snap):
 
 
 # ---------------------------------------------------------------------------------------------------------------- ticks
-def _walk(B, ticks, seed=5, tape=True, **kw):
-    """the walk of tests/test_gpu_rollout.py (pushed for three ticks), taped"""
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
+def _walk(B, ticks, seed=5, tape=True, cfg=None, plan=None, push_newton=20.0, **kw):
+    """the walk of tests/test_gpu_rollout.py (pushed for three ticks), taped; cfg / plan: another configuration and gait (tests/test_gpu_rollout_horizons.py),
+    push_newton: the pushes are U(-push_newton, push_newton) N in x and y"""
+    cfg = cm.config.ergocub_gazebo_v1(20, 0.06) if cfg is None else cfg
     rng = np.random.default_rng(seed)
     com0 = np.array([0.0, 0.0, 0.7]) + rng.uniform(-0.01, 0.01, (B, 3))
     dcom0 = rng.uniform(-0.05, 0.05, (B, 3))
     h0 = rng.uniform(-0.02, 0.02, (B, 3))
     push = np.zeros((B, 3))
-    push[:, :2] = rng.uniform(-20.0, 20.0, (B, 2)) / cm.synthetic.ROBOT_MASS
-    ro = cm.rollout.WalkingRollout(cfg, B, **kw)
+    push[:, :2] = rng.uniform(-push_newton, push_newton, (B, 2)) / cm.synthetic.ROBOT_MASS
+    ro = cm.rollout.WalkingRollout(cfg, B, plan=plan, **kw)
     rec = ro.run(ticks, com0, dcom0, h0, push=push, push_ticks=3, tape=tape)
     return cfg, ro, rec
 

@@ -35,8 +35,12 @@ def _gap(lhs, rhs):
 def test_plant_columns_are_bit_equal_to_the_single_column_entry():
     """B = 16, N = 20, the inputs of the plant test, k = 3: every column of cmpc_plant_step_jvp_cols_device is bit-equal to plant_step_jvp_device on that
     column, with the rotation direction and without; a batch of 5 holding problems 11, 3, 7, 0, 15 is bit-identical."""
+    _check_plant_columns(cm.config.ergocub_gazebo_v1(20, 0.06))
+
+
+def _check_plant_columns(cfg):
+    """the body of test_plant_columns_are_bit_equal_to_the_single_column_entry at cfg's horizon"""
     import torch
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
     L = cm.Layout(cfg.N)
     B, k, kw = 16, 3, dict(step=0.01, substeps=6)
     X, P, state, models = _plant_inputs(cfg, B, 4)
@@ -71,8 +75,12 @@ def test_list_jvp_kernel_equals_the_restatement_and_is_the_transpose_of_the_list
     rollout_jvp_ref.list_jvp to F64 (the kernel copies; the p rows are one rounding to float32 of an exact value); the two phases apart give the bits of both
     at once; the failed merge gives zeros and status 5; and <g, J d> = <J^T g, d> on the device against contacts_position_vjp_device (phase 3) plus
     contacts_orientation_vjp_device on the same tape, per problem and column, to F64."""
+    _check_list_jvp(cm.config.ergocub_gazebo_v1(20, 0.06), M, first_tick, now_k, snap)
+
+
+def _check_list_jvp(cfg, M, first_tick, now_k, snap):
+    """the body of test_list_jvp_kernel_equals_the_restatement_and_is_the_transpose_of_the_list_adjoints at cfg's horizon and sampling time"""
     import torch
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
     L, N = cm.Layout(cfg.N), cfg.N
     B, k = 24, 2
     now = cfg.sampling_time * now_k
@@ -121,7 +129,7 @@ def test_list_jvp_kernel_equals_the_restatement_and_is_the_transpose_of_the_list
                 worst_adj = max(worst_adj, _gap(lhs, rhs))
             else:
                 assert lhs == 0.0 and rhs == 0.0
-    print(f"\nlist JVP kernel M={M} first_tick={first_tick} now={now:.2f} snap={snap}: worst gap to the restatement {worst:.2e}, adjoint identity on the "
+    print(f"\nlist JVP kernel N={cfg.N} dt={cfg.sampling_time} M={M} first_tick={first_tick} now={now:.2f} snap={snap}: worst gap to the restatement {worst:.2e}, adjoint identity on the "
           f"device {worst_adj:.2e} (bound {F64:.0e} each), landing entries overwritten {landings}")
     assert worst <= F64 and worst_adj <= F64
     if not first_tick:

@@ -105,8 +105,12 @@ def test_list_orientation_kernel_equals_the_restatement(M, first_tick, now_k, sn
     stages it owns, k = 0 .. N-1): equal to list_orientation_vjp to F64.  The failed merge gives zeros, status 5, and leaves dGradPlanRot untouched.
     The landing entry's gradient DOES reach the output, where the position kernel cuts it.  With dGradListRotOut = None and a one-tick list the result
     is bit-equal to cmpc_contacts_rotation_vjp_device's."""
+    _check_list_orientation(cm.config.ergocub_gazebo_v1(20, 0.06), M, first_tick, now_k, snap)
+
+
+def _check_list_orientation(cfg, M, first_tick, now_k, snap):
+    """the body of test_list_orientation_kernel_equals_the_restatement at cfg's horizon and sampling time"""
     import torch
-    cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
     L, N = cm.Layout(cfg.N), cfg.N
     B = 24
     now = cfg.sampling_time * now_k
@@ -145,7 +149,7 @@ def test_list_orientation_kernel_equals_the_restatement(M, first_tick, now_k, sn
                 ro = rrr.list_orientation_vjp(L, cfg.sampling_time, now, lt[b], ln[b], ld[b], g_out=only, **hk)
                 assert ro["prev"].any() or ro["plan"].any()
                 assert np.abs(cut[b, c]).max() > 0 and np.abs(cut[b, c] - (ro["prev"][c] + ro["plan"][c])).max() <= F64 * np.abs(gout).max(), (b, c)
-    print(f"\nlist orientation kernel M={M} first_tick={first_tick} now={now:.2f} snap={snap}: worst gap {worst:.2e} (bound {F64:.0e}), "
+    print(f"\nlist orientation kernel N={cfg.N} dt={cfg.sampling_time} M={M} first_tick={first_tick} now={now:.2f} snap={snap}: worst gap {worst:.2e} (bound {F64:.0e}), "
           f"feet with a landing entry passed through: {landing}")
     assert worst <= F64
     if not first_tick:

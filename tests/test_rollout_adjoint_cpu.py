@@ -119,6 +119,56 @@ def _list_forward(cfg, now, plan, prev, xland, snap):
     return nominal, current, outp, land, mt, mn
 
 
+def _brute_force_list_matrix(cfg, label, now, t_b, pose_b, n_b, ts, first_tick, snap, rng):
+    """one problem of test_list_adjoint_is_the_transposed_brute_force_matrix: t_b / pose_b / n_b the planner's lists, ts the previous tick's times"""
+    N, dt = cfg.N, cfg.sampling_time
+    L = cm.Layout(N)
+    M = t_b.shape[1]
+    plan = None if first_tick else (t_b, pose_b, n_b)
+    prev_pose = pose_b.astype(np.float64).copy()
+    prev_pose[..., :3] += rng.uniform(-0.01, 0.01, prev_pose[..., :3].shape)
+    prev = (ts if not first_tick else t_b, prev_pose, n_b)
+    xland = rng.normal(0, 0.1, (2, 3))
+
+    def fwd(prev_pos, plan_pos, xl):
+        pv = (prev[0], np.concatenate([prev_pos, prev[1][..., 3:]], -1), prev[2])
+        pl = None if plan is None else (plan[0], np.concatenate([plan_pos, plan[1][..., 3:]], -1), plan[2])
+        nom, cur, outp, land, mt, mn = _list_forward(cfg, now, pl, pv, xl, snap)
+        return np.concatenate([nom.ravel(), cur.ravel(), outp.ravel()]), land, mt, mn
+    base_in = [prev[1][..., :3].copy(), pose_b[..., :3].astype(np.float64), xland]
+    y0, land, mt, mn = fwd(*base_in)
+    nin = [a.size for a in base_in]
+    A = np.zeros((y0.size, sum(nin)))
+    col = 0
+    for gi, a in enumerate(base_in):
+        for e in range(a.size):
+            ins = [v.copy() for v in base_in]
+            ins[gi].reshape(-1)[e] += 1.0
+            A[:, col] = fwd(*ins)[0] - y0
+            col += 1
+    # the restated adjoint, one unit cotangent per output entry
+    At = np.zeros_like(A.T)
+    n_nom = 2 * (N + 1) * 3
+    for r in range(y0.size):
+        gp, gout = np.zeros(L.np), np.zeros((2, M, 3))
+        if r < n_nom:
+            c, e = divmod(r, (N + 1) * 3)
+            gp[L.p_nom[c] + e] = 1.0
+        elif r < n_nom + 6:
+            c, e = divmod(r - n_nom, 3)
+            gp[L.p_cur[c] + e] = 1.0
+        else:
+            gout.reshape(-1)[r - n_nom - 6] = 1.0
+        res = rar.list_position_vjp(L, dt, now, mt, mn, land, plan=None if plan is None else (plan[0], plan[2]),
+                                    prev=None if plan is None else (prev[0], prev[2]), g_out=gout, g_p=gp, force_sample_time=snap)
+        gxl = np.array([res["x"][L.pos[c] + 3 * land[c]:L.pos[c] + 3 * land[c] + 3] if 0 <= land[c] <= N else np.zeros(3) for c in range(2)])
+        At[:, r] = np.concatenate([res["prev"].ravel(), res["plan"].ravel(), gxl.ravel()])
+    gap = np.abs(At - A.T).max()
+    assert gap <= LIST_EXACT, (label, gap)
+    # (whether the adjustment wrote a landing position into the outgoing list, whether planner positions reached the outputs)
+    return int(A[n_nom + 6:, nin[0] + nin[1]:].any()), int(A[:, nin[0]:nin[0] + nin[1]].any())
+
+
 @pytest.mark.parametrize("case", ["before_lift_off", "in_swing", "landing_tick", "after_landing", "first_tick", "off_grid_snapped", "late"])
 def test_list_adjoint_is_the_transposed_brute_force_matrix(case):
     """The forward list maps are linear in the positions: every position entry of random lists is perturbed through the oracle's merge -> sample and
@@ -145,54 +195,29 @@ def test_list_adjoint_is_the_transposed_brute_force_matrix(case):
         now = dict(before_lift_off=max(lift - 3 * dt, 0.0), in_swing=lift + dt, landing_tick=landing, after_landing=landing + 2 * dt, first_tick=0.0,
                    off_grid_snapped=lift + dt, late=2.4)[case]
         now = round(now / dt) * dt
-        plan = None if case == "first_tick" else (t[b], pose[b], n[b])
-        prev_pose = pose[b].astype(np.float64).copy()
-        prev_pose[..., :3] += rng.uniform(-0.01, 0.01, prev_pose[..., :3].shape)
-        prev = (ts if case != "first_tick" else t[b], prev_pose, n[b])
-        xland = rng.normal(0, 0.1, (2, 3))
-
-        def fwd(prev_pos, plan_pos, xl):
-            pv = (prev[0], np.concatenate([prev_pos, prev[1][..., 3:]], -1), prev[2])
-            pl = None if plan is None else (plan[0], np.concatenate([plan_pos, plan[1][..., 3:]], -1), plan[2])
-            nom, cur, outp, land, mt, mn = _list_forward(cfg, now, pl, pv, xl, snap)
-            return np.concatenate([nom.ravel(), cur.ravel(), outp.ravel()]), land, mt, mn
-        base_in = [prev[1][..., :3].copy(), pose[b][..., :3].astype(np.float64), xland]
-        y0, land, mt, mn = fwd(*base_in)
-        nin = [a.size for a in base_in]
-        A = np.zeros((y0.size, sum(nin)))
-        col = 0
-        for gi, a in enumerate(base_in):
-            for e in range(a.size):
-                ins = [v.copy() for v in base_in]
-                ins[gi].reshape(-1)[e] += 1.0
-                A[:, col] = fwd(*ins)[0] - y0
-                col += 1
-        # the restated adjoint, one unit cotangent per output entry
-        At = np.zeros_like(A.T)
-        n_nom = 2 * (N + 1) * 3
-        for r in range(y0.size):
-            gp, gout = np.zeros(L.np), np.zeros((2, M, 3))
-            if r < n_nom:
-                c, e = divmod(r, (N + 1) * 3)
-                gp[L.p_nom[c] + e] = 1.0
-            elif r < n_nom + 6:
-                c, e = divmod(r - n_nom, 3)
-                gp[L.p_cur[c] + e] = 1.0
-            else:
-                gout.reshape(-1)[r - n_nom - 6] = 1.0
-            res = rar.list_position_vjp(L, dt, now, mt, mn, land, plan=None if plan is None else (plan[0], plan[2]),
-                                        prev=None if plan is None else (prev[0], prev[2]), g_out=gout, g_p=gp, force_sample_time=snap)
-            gxl = np.array([res["x"][L.pos[c] + 3 * land[c]:L.pos[c] + 3 * land[c] + 3] if 0 <= land[c] <= N else np.zeros(3) for c in range(2)])
-            At[:, r] = np.concatenate([res["prev"].ravel(), res["plan"].ravel(), gxl.ravel()])
-        gap = np.abs(At - A.T).max()
-        assert gap <= LIST_EXACT, (case, b, gap)
-        checked_landing += int(A[n_nom + 6:, nin[0] + nin[1]:].any())      # the adjustment wrote a landing position into the outgoing list
-        checked_merge += int(A[:, nin[0]:nin[0] + nin[1]].any())           # planner positions reached the outputs
+        landed, merged = _brute_force_list_matrix(cfg, (case, b), now, t[b], pose[b], n[b], ts, case == "first_tick", snap, rng)
+        checked_landing += landed
+        checked_merge += merged
     print(f"list adjoint {case}: {B} problems, landing adjusted in {checked_landing}, planner entries used in {checked_merge}")
     if case in ("in_swing", "off_grid_snapped"):
         assert checked_landing == B
     if case != "first_tick":
         assert checked_merge == B
+
+
+@pytest.mark.parametrize("i", [3, 8, 9, 14])
+def test_list_adjoint_is_the_transposed_brute_force_matrix_at_dt_01(i):
+    """The same at N = 8, dt = 0.1 on the gait the GPU tests walk on that grid, at now = i * dt for the landing tick 8 and for ticks 3, 9 and 14, whose time
+    differs from the plan's (0.3, 0.3 + 0.5 + 0.1, ...) in its last bits (asserted): the oracle's merge and sampling on the plan's own doubles against
+    the restatement's integer-nanosecond clock."""
+    cfg = cm.config.ergocub_gazebo_v1(8, 0.1)
+    plan = cm.rollout.walking_plan(cfg, **GAIT_DT01)
+    if i != 8:
+        assert_tick_time_differs_from_the_plans(plan, cfg.sampling_time, i)
+    t, pose, n = pack_lists(cfg, [plan])
+    landed, merged = _brute_force_list_matrix(cfg, ("dt_01", i), i * cfg.sampling_time, t[0], pose[0], n[0], t[0], False, False, np.random.default_rng(i))
+    print(f"list adjoint at dt = 0.1, tick {i}: landing adjusted {landed}, planner entries used {merged}")
+    assert landed == 1 and merged == 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- solve + plant
@@ -364,8 +389,33 @@ def test_reverse_sweep_is_the_product_of_its_ticks():
     restatement's forward mode, to 1e-10: this pins the bookkeeping (which gradient goes where between ticks), not the solver."""
     cfg = cm.config.ergocub_gazebo_v1(8, 0.06)
     plan = cm.rollout.walking_plan(cfg, steps=4, step_length=0.1, swing=0.24, double_support=0.12, first_lift=0.06)
+    _check_reverse_sweep_is_the_product_of_its_ticks(cfg, plan, first_tick=3, ticks=3)
+
+
+GAIT_DT01 = dict(swing=0.5, double_support=0.1, first_lift=0.3)       # (synthetic.gait_cycle's gait on the grid of dt = 0.1)
+
+
+def assert_tick_time_differs_from_the_plans(plan, dt, i):
+    """tick i falls on a time of the plan on the nanosecond grid, and i * dt is another double than the plan's: the case CMPC_TIME_EPS is there for"""
+    same = {t for lst in plan.values() for ct in lst for t in (ct.activation_time, ct.deactivation_time) if rar._ns(t) == i * rar._ns(dt)}
+    assert len(same) == 1 and same.pop() != i * dt, (i, same)
+
+
+def test_reverse_sweep_is_the_product_of_its_ticks_at_dt_01():
+    """The same at N = 8, dt = 0.1 on the gait the GPU tests walk on that grid (lift-off at tick 3, landing at tick 8), ticks 6 .. 9: tick 7 has the
+    landing at knot 1, tick 8 is the landing tick and merges the landed contact, and tick 9 -- the other foot's lift-off -- is a tick whose time 9 * dt
+    differs from the plan's 0.3 + 0.5 + 0.1 in its last bits (asserted): the restatement's integer-nanosecond clock and the package's merge and sampling,
+    which the oracle loop runs, must name the same contacts there."""
+    cfg = cm.config.ergocub_gazebo_v1(8, 0.1)
+    plan = cm.rollout.walking_plan(cfg, **GAIT_DT01)
+    assert_tick_time_differs_from_the_plans(plan, cfg.sampling_time, 9)
+    _check_reverse_sweep_is_the_product_of_its_ticks(cfg, plan, first_tick=6, ticks=4)
+
+
+def _check_reverse_sweep_is_the_product_of_its_ticks(cfg, plan, first_tick, ticks):
+    """the second taped tick has the landing at knot 1, the third is the landing tick"""
     state0 = np.array([0.01, -0.02, 0.7, 0.05, 0.0, 0.0, 0.0, 0.0, 0.0])
-    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=3, ticks=3, com_speed=0.1)
+    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=first_tick, ticks=ticks, com_speed=0.1)
     assert tapes[1]["land"][0] == 1 and tapes[2]["prev"] is not None
     M = tapes[0]["list_t"].shape[1]
     nz = 9 + 2 * M * 3
@@ -381,15 +431,16 @@ def test_reverse_sweep_is_the_product_of_its_ticks():
         Js.append(J)
     assert np.abs(Js[2][:9, 9:]).max() > 1e-6 and np.abs(Js[1][9:, :9]).max() > 1e-6     # the lists and the states do talk to each other
     rng = np.random.default_rng(8)
-    gS = rng.normal(size=(4, 9))
+    gS = rng.normal(size=(ticks + 1, 9))
     out = rar.reverse_sweep(cfg, tapes, nows, gS)
-    g = np.concatenate([gS[3], np.zeros(nz - 9)])
-    for i in (2, 1, 0):
+    g = np.concatenate([gS[ticks], np.zeros(nz - 9)])
+    for i in reversed(range(ticks)):
         g = Js[i].T @ g
         g[:9] += gS[i]
     got = np.concatenate([out["state0"], out["list0"].ravel()])
     gap = np.abs(got - g).max() / np.abs(g).max()
-    print(f"\nreverse sweep against the product of the per-tick Jacobians: {gap:.2e} (bound 1e-10)")
+    print(f"\nreverse sweep over ticks {first_tick} .. {first_tick + ticks - 1} at dt = {cfg.sampling_time} against the product of the per-tick Jacobians: "
+          f"{gap:.2e} (bound 1e-10)")
     assert gap <= 1e-10
 
 

@@ -18,7 +18,7 @@ from tests import sens_model_ref as smr, snap_ref
 from tests import sens_rot_ref as srr
 from tests.test_contacts_cpu import _random_walks
 from tests.test_gpu_rollout_adjoint import F64
-from tests.test_rollout_adjoint_cpu import _list_forward, _oracle_ticks
+from tests.test_rollout_adjoint_cpu import GAIT_DT01, _list_forward, _oracle_ticks, assert_tick_time_differs_from_the_plans
 from tests.test_rollout_rot_adjoint_cpu import TICK_ADJ
 from tests.test_sensitivity_cpu import FD_CLEAN
 
@@ -88,20 +88,31 @@ def test_list_jvp_is_the_exact_transpose_of_the_restated_list_adjoints(case):
         assert landings >= B
 
 
-def _yawed_ticks():
-    cfg = cm.config.ergocub_gazebo_v1(8, 0.06)
-    plan = cm.rollout.walking_plan(cfg, steps=4, step_length=0.1, swing=0.24, double_support=0.12, first_lift=0.06)
+def _yawed_ticks(dt=0.06):
+    """three oracle ticks of a yawed walk at N = 8: ticks 3, 4, 5 of the short-stepping plan at dt = 0.06; at dt = 0.1 ticks 7, 8, 9 of the gait the GPU
+    tests walk on that grid (lift-off at tick 3, landing at tick 8; 9 * dt differs from the plan's 0.3 + 0.5 + 0.1 in its last bits -- asserted)"""
+    cfg = cm.config.ergocub_gazebo_v1(8, dt)
+    if dt == 0.06:
+        plan, first = cm.rollout.walking_plan(cfg, steps=4, step_length=0.1, swing=0.24, double_support=0.12, first_lift=0.06), 3
+    else:
+        plan, first = cm.rollout.walking_plan(cfg, **GAIT_DT01), 7
+        assert_tick_time_differs_from_the_plans(plan, dt, 9)
     for c, lst in enumerate(plan.values()):
         for m, ct in enumerate(lst):
             ct.yaw = (0.15 if c == 0 else -0.1) * (m + 1) / 2
     state0 = np.array([0.01, -0.02, 0.7, 0.05, 0.0, 0.0, 0.0, 0.0, 0.0])
-    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=3, ticks=3, com_speed=0.1)
+    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=first, ticks=3, com_speed=0.1)
     return cfg, tapes, nows
 
 
 @pytest.fixture(scope="module")
 def yawed_ticks():
     return _yawed_ticks()
+
+
+@pytest.fixture(scope="module")
+def yawed_ticks_dt01():
+    return _yawed_ticks(0.1)
 
 
 def _directions(rng, cfg, M):
@@ -115,12 +126,24 @@ def test_restated_tick_jvp_is_the_transpose_of_the_restated_tick_vjp(yawed_ticks
     """<g, J d> = <J^T g, d> of one whole tick with all eight input groups (state, previous list positions / orientations, planner positions /
     orientations, wrench, model, extra p) and all four output groups (state', list, list orientations, x) random at once, on tick 3 (swing, landing inside
     the horizon) and tick 5 (the landing tick: the merge takes the landed contact) of the yawed walk on the float64 oracle: to TICK_ADJ."""
-    cfg, tapes, nows = yawed_ticks
+    _check_restated_tick_jvp_is_the_transpose(yawed_ticks, (0, 2), 3)
+
+
+def test_restated_tick_jvp_and_forward_sweep_are_the_transposes_at_dt_01(yawed_ticks_dt01):
+    """The two tests around this one at N = 8, dt = 0.1, on ticks 7 (in swing, the landing inside the horizon), 8 (the landing tick) and 9 (a tick whose
+    time differs from the plan's in its last bits, at which the other foot lifts) of the yawed walk on the float64 oracle: tick JVP against tick VJP on
+    each of the three, the forward sweep against the reverse sweep over the three, to TICK_ADJ."""
+    _check_restated_tick_jvp_is_the_transpose(yawed_ticks_dt01, (0, 1, 2), 7)
+    _check_forward_sweep_is_the_contraction(yawed_ticks_dt01)
+
+
+def _check_restated_tick_jvp_is_the_transpose(ticks, which, first_tick):
+    cfg, tapes, nows = ticks
     L = cm.Layout(cfg.N)
     M = tapes[0]["list_t"].shape[1]
     rng = np.random.default_rng(23)
     assert 0 < tapes[0]["land"][0] <= cfg.N and tapes[2]["prev"] is not None
-    for i in (0, 2):
+    for i in which:
         tp, now = tapes[i], nows[i]
         RS = srr.RotSens(cfg, tp["X"], tp["P"], tp["lam_g"])
         assert RS.n is None
@@ -135,7 +158,8 @@ def test_restated_tick_jvp_is_the_transpose_of_the_restated_tick_vjp(yawed_ticks
                      model=r["model"] @ d["model"], p=r["p"] @ d["p"])
         rhs = sum(terms.values())
         gap = _gap(lhs, rhs)
-        print(f"\ntick {3 + i} land {tp['land'].tolist()}: <g, J d> = {lhs:.12e}, <J^T g, d> = {rhs:.12e}, relative gap {gap:.2e} (bound {TICK_ADJ:.0e}); "
+        print(f"\ntick {first_tick + i} dt = {cfg.sampling_time} land {tp['land'].tolist()}: <g, J d> = {lhs:.12e}, <J^T g, d> = {rhs:.12e}, relative gap {gap:.2e} "
+              f"(bound {TICK_ADJ:.0e}); "
               "terms " + " ".join(f"{k} {v:.2e}" for k, v in terms.items()))
         assert gap <= TICK_ADJ
         merge = tp["prev"] is not None
@@ -145,7 +169,11 @@ def test_restated_tick_jvp_is_the_transpose_of_the_restated_tick_vjp(yawed_ticks
 def test_restated_forward_sweep_is_the_contraction_of_the_restated_reverse_sweep(yawed_ticks):
     """Three oracle ticks of the yawed walk (3, 4, 5): sum_i <gS_i, d state_i> + <gX_i, d x_i> of rollout_jvp_ref.forward_sweep equals the contraction of
     rrr.reverse_sweep's state0, list0, list_rot0, plan, plan_rot, models and wrench with the directions, to TICK_ADJ."""
-    cfg, tapes, nows = yawed_ticks
+    _check_forward_sweep_is_the_contraction(yawed_ticks)
+
+
+def _check_forward_sweep_is_the_contraction(ticks):
+    cfg, tapes, nows = ticks
     L = cm.Layout(cfg.N)
     T = len(tapes)
     M = tapes[0]["list_t"].shape[1]
@@ -160,7 +188,7 @@ def test_restated_forward_sweep_is_the_contraction_of_the_restated_reverse_sweep
     rhs = (out["state0"] @ d["state"] + (out["list0"] * d["list"]).sum() + (out["list_rot0"] * d["list_rot"]).sum() + (out["plan"] * d["plan"]).sum() +
            (out["plan_rot"] * d["plan_rot"]).sum() + out["models"] @ d["model"] + (out["wrench"] * dw).sum())
     gap = _gap(lhs, rhs)
-    print(f"\nforward sweep against the reverse sweep over three ticks: {lhs:.12e} vs {rhs:.12e}, relative gap {gap:.2e} (bound {TICK_ADJ:.0e})")
+    print(f"\nforward sweep against the reverse sweep over three ticks at dt = {cfg.sampling_time}: {lhs:.12e} vs {rhs:.12e}, relative gap {gap:.2e} (bound {TICK_ADJ:.0e})")
     assert gap <= TICK_ADJ
 
 

@@ -186,16 +186,31 @@ def test_restated_tick_with_orientations_is_adjoint():
     and orientations: <g, J d> = <J^T g, d> to 1e-9 relative."""
     cfg = cm.config.ergocub_gazebo_v1(8, 0.06)
     plan = cm.rollout.walking_plan(cfg, steps=4, step_length=0.1, swing=0.24, double_support=0.12, first_lift=0.06)
+    _check_restated_tick_with_orientations_is_adjoint(cfg, plan, first_tick=3, which=(0, 2))
+
+
+def test_restated_tick_with_orientations_is_adjoint_at_dt_01():
+    """The same at N = 8, dt = 0.1 on the gait the GPU tests walk on that grid (lift-off at tick 3, landing at tick 8): tick 7 (in swing, the landing
+    inside the horizon), tick 8 (the landing tick) and tick 9, whose time 9 * dt differs from the plan's 0.3 + 0.5 + 0.1 in its last bits (asserted) and at
+    which the other foot lifts."""
+    from tests.test_rollout_adjoint_cpu import GAIT_DT01, assert_tick_time_differs_from_the_plans
+    cfg = cm.config.ergocub_gazebo_v1(8, 0.1)
+    plan = cm.rollout.walking_plan(cfg, **GAIT_DT01)
+    assert_tick_time_differs_from_the_plans(plan, cfg.sampling_time, 9)
+    _check_restated_tick_with_orientations_is_adjoint(cfg, plan, first_tick=7, which=(0, 1, 2))
+
+
+def _check_restated_tick_with_orientations_is_adjoint(cfg, plan, first_tick, which):
     for c, lst in enumerate(plan.values()):
         for m, ct in enumerate(lst):
             ct.yaw = (0.15 if c == 0 else -0.1) * (m + 1) / 2
     state0 = np.array([0.01, -0.02, 0.7, 0.05, 0.0, 0.0, 0.0, 0.0, 0.0])
-    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=3, ticks=3, com_speed=0.1)
+    tapes, nows, _ = _oracle_ticks(cfg, plan, state0, first_tick=first_tick, ticks=3, com_speed=0.1)
     assert 0 < tapes[0]["land"][0] <= cfg.N and tapes[2]["prev"] is not None
     L = cm.Layout(cfg.N)
     M = tapes[0]["list_t"].shape[1]
     rng = np.random.default_rng(14)
-    for i in (0, 2):
+    for i in which:
         tp, now = tapes[i], nows[i]
         p = np.asarray(tp["P"])
         assert len({(c,) + tuple(np.round(srr.stage_R(L, p, c, k).ravel(), 6)) for c in range(2) for k in range(cfg.N)}) >= 3   # a yawed footstep ahead
@@ -211,7 +226,8 @@ def test_restated_tick_with_orientations_is_adjoint():
         lhs = g_state @ o_state + (g_list * o_list).sum() + (g_lrot * o_lrot).sum()
         rhs = r["state"] @ d_state + (r["prev_list"] * d_list).sum() + (r["prev_list_rot"] * d_lrot).sum() + (r["plan_rot"] * d_prot).sum()
         gap = abs(lhs - rhs) / max(abs(lhs), abs(rhs))
-        print(f"\ntick {3 + i} land {tp['land'].tolist()}: <g, J d> = {lhs:.12e}, <J^T g, d> = {rhs:.12e}, relative gap {gap:.2e} (bound {TICK_ADJ:.0e})")
+        print(f"\ntick {first_tick + i} dt = {cfg.sampling_time} land {tp['land'].tolist()}: <g, J d> = {lhs:.12e}, <J^T g, d> = {rhs:.12e}, relative gap {gap:.2e} "
+              f"(bound {TICK_ADJ:.0e})")
         assert gap <= TICK_ADJ
 
 
