@@ -594,6 +594,85 @@ typedef struct cmpc_tick_io {
     int force_sample_time;
 } cmpc_tick_io;
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream);
+
+/* ---- a walk of the whole batch on the device: per-problem outcomes, the trace and the batch statistics written by a kernel ----
+ * The reference runs one robot and ends its tick when updateContactPhaseList or advance fail (CentroidalMPCBlock.cpp:603-607, :615-619).  In a batch
+ * every problem ends on its own terms: the record kernel runs behind a tick (one thread per problem), reads what the tick left and keeps, per problem,
+ * whether and why it has ended.  Nothing is read back between the ticks.
+ * Tick code, one int per problem and tick, first match wins:
+ *     -1  the problem had ended before this tick
+ *      1  the merge (or the snap of force_sample_time) failed: dOk[b] == 0
+ *  1 + s  the solve's status s != 0 (dInfo word 5): 2 budget exhausted, 3 factorisation failed / not finite, 4 outside the supported subset
+ *      5  an entry of dStateOut[b] is not finite
+ *      0  none of the above
+ * stop_mask says which codes END a problem: bit 0 code 1 (always honoured, set or not: such a tick solved a stale problem), bit 1 codes 2..4, bit 2
+ * code 5.  A code whose bit is off is recorded and the problem walks on; that tick is a good tick like one with code 0.
+ * Trace, row `row` of arrays with `rows` rows; every pointer may be NULL:
+ *     dCom[rows][B][3], dZmp[rows][B][2]   float: bit copies of dStateOut[b][0..2] and dZmp[b]
+ *     dLand[rows][B][2]                    int: dLand of the tick
+ *     dLandingOffset[rows][B][2][3]        double: R^T (pos_k - nominalPos_k) of a foot whose landing knot k = dLand[b][c] has 0 < k <= N, zero otherwise;
+ *                                          R = the column-major block of stage k - 1 in dP; the differences, products and three-term sums (left to
+ *                                          right, not contracted) in double from the float values: the offset the NLP's box rows bound
+ *     dIterations[rows][B], dCode[rows][B] int: dInfo word 0; the tick code
+ * Rows of a problem that has ended, the ending tick included: NaN in the float and double arrays, -2 in dLand, 0 in dIterations; dCode holds the ending
+ * code on the ending tick and -1 on later ticks.
+ * Outcome, per problem, carried from call to call (all required; set up by cmpc_rollout_outcome_init_device):
+ *     dEndTick[B]        int: -1 while walking, else `tick` of the call that ended it;  dEndCode[B] int: 0 while walking, else that tick's code
+ *     dIterationsSum[B], dIterationsMax[B]  int: over its good ticks
+ *     dFinalState[B][9]  float: dStateOut of its last good tick, or the initial state if it had none (kept here because a tick may run in place)
+ *     dBoxSlackMin[B]    float, from +inf: the least of upper - off and off - lower over its good ticks, landing feet (0 < k <= N) and axes, off as in
+ *                        dLandingOffset, the limits the handle's box (the last one a sampling or a tick uploaded), each slack formed in double and
+ *                        rounded to float
+ * Batch statistics, dStats[rows][6] int or NULL, row `row`: { problems not ended before the tick, problems ended by it, sum and max of dIterations over
+ * the tick's good problems, problems not ended before the tick whose code is 2..4, 0 }: what a reduction of the trace row gives.  Integer atomics, so
+ * the result does not depend on the order: each wave reduces first, then adds once per word; lanes past B and lanes of ended problems contribute the
+ * identity.  The call clears the row first.
+ * Isolation: the record writes nothing a tick reads, so a recorded walk is bit-identical to an unrecorded one.  An ended problem is NOT taken out of
+ * the batch: it keeps running unobserved, holds its CU in every solve, and a failed merge keeps failing. */
+typedef struct cmpc_walk_record {
+    int rows;                /* rows of the trace arrays and of dStats */
+    int stop_mask;
+    float* dCom; float* dZmp; int* dLand; double* dLandingOffset; int* dIterations; int* dCode;                            /* trace */
+    int* dEndTick; int* dEndCode; int* dIterationsSum; int* dIterationsMax; float* dFinalState; float* dBoxSlackMin;    /* outcome */
+    int* dStats;
+} cmpc_walk_record;
+/* the outcome arrays at their start: dEndTick -1, dEndCode 0, the iteration words 0, dFinalState = dState0[B][9], dBoxSlackMin +inf (the trace and
+ * dStats are not touched).  Asynchronous on `stream` (NULL: the handle's). */
+int cmpc_rollout_outcome_init_device(cmpc_handle h, const float* dState0, const cmpc_walk_record* rec, void* stream);
+/* the record of one tick (`tick`: the number dEndTick takes; 0 <= row < rec->rows) from what that tick left: dX, dP, dInfo, dOk (NULL: every merge
+ * good -- a first tick without force_sample_time leaves dOk alone), dLand, dStateOut, dZmp (NULL only with rec->dZmp NULL).  Device pointers;
+ * asynchronous on `stream` (NULL: the handle's); CMPC_ERR_ARG before any sampling or tick has given the handle its box. */
+int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
+                               const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, void* stream);
+/* the same on the host: host buffers throughout (rec's pointers too), box_upper / box_lower [2][3]; no handle, no GPU.  Bit-equal to the kernel. */
+int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
+                        const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec);
+
+/* The cold start of cmpc_set_initial_guess with x0 == NULL as a kernel, from the caller's dP[B][n_p] into dX0[B][n_x]: CoM at com0 on every knot, feet at
+ * nominalPos, f_z = (float)(gravity / 8) per corner and stage, every other entry zero; bit-equal to the host form.  Asynchronous on `stream` (NULL:
+ * the handle's). */
+int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* stream);
+
+/* `ticks` ticks, numbers tick0 .. tick0 + ticks - 1, queued on `stream` (NULL: the handle's) with no host wait: tick i runs at
+ * now = (double)(tick0 + i) * sampling_time as the three launches of cmpc_rollout_tick_device plus the record launch, row row0 + i, tick number tick0 + i.
+ * Every tick is bit-identical to the same calls made one by one.
+ * io->tick: the buffers of cmpc_tick_io, with these differences.  dPrev* are not read: the lists alternate between two sets, set 0 = tick.dList*, set 1 =
+ * dListTB / dListPoseB / dListNB.  `lists_in` (0 or 1) names the set that holds the lists of the tick before tick0; a tick merges into the other set,
+ * and *lists_out (may be NULL) receives the set of the last tick's lists.  dState is read by the first tick only; later ticks run in place on dStateOut.
+ * plan_t_offset is not read: tick i passes now - plan_t_first.  dWrenchTicks[wrench_ticks][B][N][6] (or NULL): tick i < wrench_ticks writes row i
+ * into dP, later ticks leave the wrench rows alone, and tick.dWrench is not read; with dWrenchTicks NULL every tick writes tick.dWrench (NULL: none).
+ * cold_first != 0: tick 0 of the call is a first tick -- no merge, set `lists_in` taken as the caller filled it (and kept: the next tick merges into the
+ * other set), started from cmpc_cold_start_device launched between the front kernel and the solve (five launches), its record reads dOk only with
+ * force_sample_time.  Every other tick is a warm merge tick.  The box is uploaded once; the event pair of cmpc_set_timing is left off for the call and
+ * the setting restored.  rec may be NULL (no record launches).  On an error the ticks queued so far stay queued. */
+typedef struct cmpc_walk_io {
+    cmpc_tick_io tick;
+    double* dListTB; float* dListPoseB; int* dListNB;   /* the second set of list buffers */
+    double plan_t_first;                                /* time of the planner trajectories' first knot (with tick.dPlanCom / dPlanH) */
+    const float* dWrenchTicks; int wrench_ticks;
+} cmpc_walk_io;
+int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                             int row0, int lists_in, int* lists_out, void* stream);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
  * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated; the orientations have their own entry point below
  * (cmpc_contacts_orientation_vjp_device).  The forward maps move positions

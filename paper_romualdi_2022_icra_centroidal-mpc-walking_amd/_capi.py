@@ -49,6 +49,22 @@ class CmpcTickIO(C.Structure):
         ("robot_mass", C.c_double), ("com_height", C.c_double), ("force_sample_time", C.c_int)]
 
 
+class CmpcWalkRecord(C.Structure):
+    """mirror of cmpc_walk_record (include/cmpc.h): the trace, outcome and statistics arrays of cmpc_rollout_record[_device] / cmpc_rollout_walk_device"""
+    _fields_ = [("rows", C.c_int), ("stop_mask", C.c_int)] + [(k, C.c_void_p) for k in (
+        "dCom", "dZmp", "dLand", "dLandingOffset", "dIterations", "dCode", "dEndTick", "dEndCode", "dIterationsSum", "dIterationsMax", "dFinalState",
+        "dBoxSlackMin", "dStats")]
+
+
+class CmpcWalkIO(C.Structure):
+    """mirror of cmpc_walk_io (include/cmpc.h): the buffers of cmpc_rollout_walk_device"""
+    _fields_ = [("tick", CmpcTickIO), ("dListTB", C.c_void_p), ("dListPoseB", C.c_void_p), ("dListNB", C.c_void_p), ("plan_t_first", C.c_double),
+                ("dWrenchTicks", C.c_void_p), ("wrench_ticks", C.c_int)]
+
+
+STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
+
+
 class CmpcTickTape(C.Structure):
     """mirror of cmpc_tick_tape (include/cmpc.h): what a forward tick left behind, read by cmpc_rollout_tick_vjp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -106,6 +122,7 @@ EXPORTS = [
     "cmpc_solution_jvp_rot_device", "cmpc_solution_vjp_rot_device", "cmpc_rotation_value_gradient_device", "cmpc_contacts_rotation_vjp_device",
     "cmpc_plant_step_jvp_rot_device", "cmpc_plant_step_vjp_rot_device", "cmpc_contacts_orientation_vjp_device", "cmpc_rollout_tick_vjp_rot_device",
     "cmpc_plant_step_jvp_cols_device", "cmpc_contacts_jvp_device", "cmpc_rollout_tick_jvp_device",
+    "cmpc_rollout_record", "cmpc_rollout_record_device", "cmpc_rollout_outcome_init_device", "cmpc_cold_start_device", "cmpc_rollout_walk_device",
 ]
 
 _lib = None
@@ -214,6 +231,13 @@ def lib():
             L.cmpc_rollout_tick_device.argtypes = [vp, i, d, i, C.POINTER(CmpcTickIO), vp]
         if hasattr(L, "cmpc_write_reference_from_planner_device"):
             L.cmpc_write_reference_from_planner_device.argtypes = [vp, fp, fp, i, d, d, d, d, fp, vp]
+        if hasattr(L, "cmpc_rollout_walk_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            rp = C.POINTER(CmpcWalkRecord)
+            L.cmpc_rollout_record.argtypes = [i, i, i, i] + [vp] * 9 + [rp]
+            L.cmpc_rollout_record_device.argtypes = [vp, i, i] + [vp] * 7 + [rp, vp]
+            L.cmpc_rollout_outcome_init_device.argtypes = [vp, vp, rp, vp]
+            L.cmpc_cold_start_device.argtypes = [vp, fp, fp, vp]
+            L.cmpc_rollout_walk_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), rp, i, i, ip, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

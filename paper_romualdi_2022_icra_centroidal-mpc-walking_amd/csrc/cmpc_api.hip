@@ -54,6 +54,10 @@ extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, cons
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
                                      const double* t, float* pose, const int* n, hipStream_t stream);
+extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream);
+extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
+                                        float* slack_min, hipStream_t stream);
+extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, hipStream_t stream);
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream);
@@ -1253,7 +1257,9 @@ int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, v
 // ---- 8f-1 .. 8f-4 chained: one tick of the receding-horizon loop in one call (include/cmpc.h): the steps of the entry points above in the reference's order, with the
 // same argument checks, as THREE launches -- everything in front of the solve, the solve, everything behind it (cmpc_tick_pre_kernel / cmpc_tick_post_kernel call the same
 // per-problem functions as the single kernels; results identical to the last bit). ----
-int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream)
+// cold: the solve starts from cmpc_cold_start_kernel, launched between the front kernel and the solve (the first tick of cmpc_rollout_walk_device; needs
+// warm == 0).  box_done: the caller has uploaded the box already.
+static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream, bool cold, bool box_done)
 {
     if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: null argument");
     if (!io->dLand || !io->dInfo) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: dLand and dInfo are needed");
@@ -1274,7 +1280,7 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
         dt_ns = snap_dt_ns(h->cfg.sampling_time);
         if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: force_sample_time needs a sampling time of at least 1 ns");
     }
-    int rc = upload_box(h, io->box_upper, io->box_lower, st);
+    int rc = box_done ? CMPC_OK : upload_box(h, io->box_upper, io->box_lower, st);
     if (rc != CMPC_OK) return rc;
     // forceSampleTime: inside the front kernel when the lists fit its LDS stage (cmpc_tick_pre_kernel, M <= 16); else one launch of the standalone kernel
     // in front of it -- the planner's lists into the handle's dSnapT (merge ticks) or the caller's lists in place (first tick), per-foot status into dSnapOk
@@ -1301,6 +1307,10 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
                                    warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
                                    io->com_height, dt_ns, snap_ok, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
+    if (cold) {
+        lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, st);
+        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (cold start) launch: ") + hipGetErrorString((hipError_t)lrc));
+    }
     rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
     if (rc != CMPC_OK) return rc;
     lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
@@ -1308,6 +1318,132 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
                                 io->dListN, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (back) launch: ") + hipGetErrorString((hipError_t)lrc));
     return CMPC_OK;
+}
+
+int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream)
+{
+    return rollout_tick_impl(h, max_contacts, now, warm, io, stream, false, false);
+}
+
+// ---- the walk (include/cmpc.h): the record behind a tick, the cold start as a kernel, and `ticks` ticks queued in one call ----
+static bool record_args(int N, int B, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
+                        const float* state_out, const float* zmp, const float* box, const cmpc_walk_record* rec, CmpcRecordArgs& a)
+{
+    if (N < 1 || B < 1 || !X || !P || !info || !land || !state_out || !box || !rec || row < 0 || row >= rec->rows || (rec->dZmp && !zmp)) return false;
+    if (!rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin) return false;
+    a = CmpcRecordArgs{N, B, tick, row, rec->stop_mask, X, P, info, ok, land, state_out, zmp, box, rec->dCom, rec->dZmp, rec->dLand, rec->dLandingOffset,
+                       rec->dIterations, rec->dCode, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
+                       rec->dBoxSlackMin};
+    return true;
+}
+
+int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
+                        const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec)
+{
+    float box[12];
+    CmpcRecordArgs a;
+    if (!box_upper || !box_lower || !record_args(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box, rec, a))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record: bad argument");
+    std::memcpy(box, box_upper, sizeof(float) * 6);
+    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
+    int st[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < batch; ++b) {
+        int t[5];
+        cmpc_record_problem(a, b, t);
+        st[0] += t[0]; st[1] += t[1]; st[2] += t[2]; st[3] = std::max(st[3], t[3]); st[4] += t[4];
+    }
+    if (rec->dStats) std::memcpy(rec->dStats + 6 * (size_t)row, st, sizeof(st));
+    return CMPC_OK;
+}
+
+// the record launch of one tick; clear_row: the statistics row is cleared here (the walk clears all its rows at once)
+static int rollout_record_impl(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
+                               const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, hipStream_t st, bool clear_row)
+{
+    CmpcRecordArgs a;
+    if (!h || !h->box_set || !record_args(h->cfg.horizon, h->B, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, h->dBox, rec, a))
+        return fail(h, CMPC_ERR_ARG, h && !h->box_set ? "cmpc_rollout_record_device: the handle has no box yet (a sampling or a tick uploads it)"
+                                                      : "cmpc_rollout_record_device: bad argument");
+    int* stats = rec->dStats ? rec->dStats + 6 * (size_t)row : nullptr;
+    if (stats && clear_row) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(int) * 6, st));
+    const int lrc = cmpc_launch_rollout_record(&a, stats, st);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("roll-out record launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
+                               const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_record_device: null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    return rollout_record_impl(h, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, rec, stream ? (hipStream_t)stream : h->stream, true);
+}
+
+int cmpc_rollout_outcome_init_device(cmpc_handle h, const float* dState0, const cmpc_walk_record* rec, void* stream)
+{
+    if (!h || !dState0 || !rec || !rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_outcome_init_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_outcome_init(h->B, dState0, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
+                                             rec->dBoxSlackMin, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("outcome init launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* stream)
+{
+    if (!h || !dP || !dX0) return fail(h, CMPC_ERR_ARG, "cmpc_cold_start_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("cold start launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                             int row0, int lists_in, int* lists_out, void* stream)
+{
+    if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: null argument");
+    if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !io->tick.dListT || !io->tick.dListPose ||
+        !io->tick.dListN || !io->tick.box_upper || !io->tick.box_lower || !io->tick.dState || !io->tick.dStateOut || (io->dWrenchTicks && io->wrench_ticks < 1))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: bad argument");
+    if (io->dListTB == io->tick.dListT || io->dListPoseB == io->tick.dListPose || io->dListNB == io->tick.dListN)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the two sets of list buffers must not alias");
+    if (rec && (row0 < 0 || (long long)row0 + ticks > rec->rows)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the record has too few rows");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    int rc = upload_box(h, io->tick.box_upper, io->tick.box_lower, st);
+    if (rc != CMPC_OK) return rc;
+    if (rec && rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
+    const bool timing = h->timing;   // (an event record is a barrier packet on the stream: cmpc_set_timing)
+    h->timing = false; h->timed = false;
+    double* const set_t[2] = {io->tick.dListT, io->dListTB};
+    float* const set_p[2] = {io->tick.dListPose, io->dListPoseB};
+    int* const set_n[2] = {io->tick.dListN, io->dListNB};
+    const size_t wrench_row = (size_t)h->B * h->cfg.horizon * 6;
+    int cur = lists_in;
+    rc = CMPC_OK;
+    for (int i = 0; i < ticks && rc == CMPC_OK; ++i) {
+        const bool cold = cold_first && i == 0;
+        const double now = (double)(tick0 + i) * h->cfg.sampling_time;
+        cmpc_tick_io t = io->tick;
+        if (cold) {
+            t.dPrevT = nullptr; t.dPrevPose = nullptr; t.dPrevN = nullptr;
+        } else {
+            t.dPrevT = set_t[cur]; t.dPrevPose = set_p[cur]; t.dPrevN = set_n[cur];
+            cur = 1 - cur;
+        }
+        t.dListT = set_t[cur]; t.dListPose = set_p[cur]; t.dListN = set_n[cur];
+        if (i > 0) t.dState = io->tick.dStateOut;
+        if (io->dWrenchTicks) t.dWrench = i < io->wrench_ticks ? io->dWrenchTicks + wrench_row * i : nullptr;
+        t.plan_t_offset = now - io->plan_t_first;
+        rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true);
+        if (rc == CMPC_OK && rec)
+            rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, (cold && !t.force_sample_time) ? nullptr : t.dOk, t.dLand, t.dStateOut, t.dZmp,
+                                     rec, st, false);
+    }
+    h->timing = timing;
+    if (rc == CMPC_OK && lists_out) *lists_out = cur;
+    return rc;
 }
 
 // ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags

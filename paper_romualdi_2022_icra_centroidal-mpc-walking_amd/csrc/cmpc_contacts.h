@@ -176,3 +176,90 @@ __host__ __device__ inline void cmpc_resample_reference_knot(const float* ci, co
         h_out[a] = (float)(((1 - w) * hi[3 * i0 + a] + w * hi[3 * (i0 + 1) + a]) / robot_mass);
     }
 }
+
+// ---- the walk's record (include/cmpc.h, cmpc_rollout_record): what one tick left of one problem -> its trace row, its outcome and its share of the batch
+// statistics.  One statement for the host form and the kernel, so that the two are bit-equal (contraction into fma is off: the offsets are sums of
+// double products).  Plain pointers, host or device alike.
+struct CmpcRecordArgs {
+    int N, B, tick, row, stop_mask;
+    const float* X; const float* P; const float* info; const int* ok; const int* land; const float* state_out; const float* zmp;
+    const float* box;                                                                   // upper[2][3] | lower[2][3]
+    float* t_com; float* t_zmp; int* t_land; double* t_off; int* t_iters; int* t_code;  // trace (each may be null)
+    int* end_tick; int* end_code; int* it_sum; int* it_max; float* final_state; float* slack_min;
+};
+// tally[5]: this problem's terms of the statistics row -- not ended before the tick, ended by it, iterations (for the sum and for the max: 0 unless the
+// tick is a good one), code 2..4
+__host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, int b, int* tally)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{a.N};
+    const int N = a.N;
+    const float* so = a.state_out + 9 * (size_t)b;
+    const float* inf = a.info + (size_t)b * CMPC_INFO_N;
+    const bool before = a.end_tick[b] >= 0;
+    int code = -1;
+    bool ends = false;
+    if (!before) {
+        bool finite = true;
+        for (int i = 0; i < 9; ++i) finite = finite && __builtin_isfinite(so[i]);
+        code = (a.ok && !a.ok[b]) ? 1 : inf[5] != 0.f ? 1 + (int)inf[5] : !finite ? 5 : 0;
+        ends = code == 1 || (code >= 2 && code <= 4 && (a.stop_mask & 2)) || (code == 5 && (a.stop_mask & 4));
+    }
+    const bool good = !before && !ends;
+    const int it = good ? (int)inf[0] : 0;
+    const size_t r = (size_t)a.row * a.B + b;
+    const float qnan = __builtin_nanf("");
+    if (a.t_code) a.t_code[r] = code;
+    if (a.t_iters) a.t_iters[r] = it;
+    if (a.t_com)
+        for (int i = 0; i < 3; ++i) a.t_com[3 * r + i] = good ? so[i] : qnan;
+    if (a.t_zmp)
+        for (int i = 0; i < 2; ++i) a.t_zmp[2 * r + i] = good ? a.zmp[2 * (size_t)b + i] : qnan;
+    float slack = a.slack_min[b];
+    for (int c = 0; c < 2; ++c) {
+        const int k = good ? a.land[2 * b + c] : -2;
+        if (a.t_land) a.t_land[2 * r + c] = k;
+        double off[3] = {0.0, 0.0, 0.0};
+        if (!good) off[0] = off[1] = off[2] = (double)qnan;
+        else if (k > 0 && k <= N) {
+            const float* x = a.X + (size_t)b * L.nx() + L.oPos(c) + 3 * k;
+            const float* p = a.P + (size_t)b * L.np();
+            const float* R = p + L.pR(c) + 9 * (k - 1);   // column-major: R^T's row i is R[3 i .. 3 i + 2]
+            double d[3];
+            for (int i = 0; i < 3; ++i) d[i] = (double)x[i] - (double)p[L.pNom(c) + 3 * k + i];
+            for (int i = 0; i < 3; ++i) {
+                off[i] = ((double)R[3 * i] * d[0] + (double)R[3 * i + 1] * d[1]) + (double)R[3 * i + 2] * d[2];
+                const double up = (double)a.box[3 * c + i] - off[i], lo = off[i] - (double)a.box[6 + 3 * c + i];
+                const float s = (float)(up < lo ? up : lo);
+                if (s < slack) slack = s;
+            }
+        }
+        if (a.t_off)
+            for (int i = 0; i < 3; ++i) a.t_off[(2 * r + c) * 3 + i] = off[i];
+    }
+    if (ends) { a.end_tick[b] = a.tick; a.end_code[b] = code; }
+    if (good) {
+        a.it_sum[b] += it;
+        if (it > a.it_max[b]) a.it_max[b] = it;
+        for (int i = 0; i < 9; ++i) a.final_state[9 * (size_t)b + i] = so[i];
+        a.slack_min[b] = slack;
+    }
+    tally[0] = before ? 0 : 1;
+    tally[1] = ends ? 1 : 0;
+    tally[2] = it;
+    tally[3] = it;
+    tally[4] = (!before && code >= 2 && code <= 4) ? 1 : 0;
+}
+
+// the cold start (cmpc_api.hip, cold_start): entry e of one problem's x from its p -- CoM at com0, feet at nominalPos, f_z = g8 per corner and
+// stage, zero elsewhere
+__host__ __device__ inline float cmpc_cold_start_entry(int N, int e, const float* p, float g8)
+{
+    const CmpcIdx L{N};
+    if (e < 3 * (N + 1)) return p[L.pCom0() + e % 3];
+    if (e < L.oPos(0)) return 0.f;
+    const int c = e >= L.oPos(1) ? 1 : 0, q = e - L.oPos(c);
+    if (q < 3 * (N + 1)) return p[L.pNom(c) + q];
+    if (q < 3 * (N + 1) + 3 * N) return 0.f;          // the foot's velocity block
+    return (q - 3 * (N + 1)) % 3 == 2 ? g8 : 0.f;     // corner forces [j][k][3]: 3 (N + 1) and 3 N are multiples of three
+}

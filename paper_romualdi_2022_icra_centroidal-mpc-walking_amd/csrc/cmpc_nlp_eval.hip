@@ -1582,7 +1582,73 @@ __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M
     }
 }
 
+// ---- the walk (cmpc_rollout_walk_device): the record behind a tick, the outcome arrays at their start, and the cold start in front of a first solve ----
+// record: one thread per problem (cmpc_record_problem, the host form's function).  The statistics row: every lane holds its problem's five terms (zeros, the
+// identity of the sums and of the max of non-negative counts, for lanes past B and for ended problems), the wave reduces them by butterflies -- all 256 threads
+// reach the shuffles: no lane leaves before them -- and lane 0 adds its wave's terms to the row, one integer atomic per non-zero word.
+__global__ __launch_bounds__(256) void cmpc_rollout_record_kernel(CmpcRecordArgs a, int* __restrict__ stats)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    int t[5] = {0, 0, 0, 0, 0};
+    if (b < a.B) cmpc_record_problem(a, b, t);
+    if (!stats) return;   // (uniform)
+    for (int o = warpSize / 2; o > 0; o >>= 1) {
+        t[0] += __shfl_xor(t[0], o);
+        t[1] += __shfl_xor(t[1], o);
+        t[2] += __shfl_xor(t[2], o);
+        t[3] = max(t[3], __shfl_xor(t[3], o));
+        t[4] += __shfl_xor(t[4], o);
+    }
+    if ((threadIdx.x & (warpSize - 1)) == 0) {
+        if (t[0]) atomicAdd(stats + 0, t[0]);
+        if (t[1]) atomicAdd(stats + 1, t[1]);
+        if (t[2]) atomicAdd(stats + 2, t[2]);
+        if (t[3]) atomicMax(stats + 3, t[3]);
+        if (t[4]) atomicAdd(stats + 4, t[4]);
+    }
+}
+
+__global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const float* __restrict__ state0, int* __restrict__ end_tick, int* __restrict__ end_code,
+                                                                int* __restrict__ it_sum, int* __restrict__ it_max, float* __restrict__ final_state,
+                                                                float* __restrict__ slack_min)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    end_tick[b] = -1; end_code[b] = 0; it_sum[b] = 0; it_max[b] = 0;
+    for (int i = 0; i < 9; ++i) final_state[9 * (size_t)b + i] = state0[9 * (size_t)b + i];
+    slack_min[b] = __builtin_inff();
+}
+
+// cold start: one workgroup per problem, one thread per entry of x (cmpc_cold_start_entry)
+__global__ __launch_bounds__(256) void cmpc_cold_start_kernel(int N, float g8, const float* __restrict__ P, float* __restrict__ X0)
+{
+    const CmpcIdx L{N};
+    const float* p = P + (size_t)blockIdx.x * L.np();
+    float* x = X0 + (size_t)blockIdx.x * L.nx();
+    for (int e = threadIdx.x; e < L.nx(); e += 256) x[e] = cmpc_cold_start_entry(N, e, p, g8);
+}
+
 }  // namespace
+
+extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_rollout_record_kernel, dim3((a->B + 255) / 256), dim3(256), 0, stream, *a, stats);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
+                                        float* slack_min, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_outcome_init_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, state0, end_tick, end_code, it_sum, it_max, final_state,
+                       slack_min);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_cold_start_kernel, dim3(B), dim3(256), 0, stream, N, g8, dP, dX0);
+    return (int)hipGetLastError();
+}
 
 extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose, const int* plan_n,
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,

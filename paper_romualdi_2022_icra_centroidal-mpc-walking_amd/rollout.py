@@ -101,6 +101,72 @@ class WalkingRollout:
         finally:
             cur.wait_stream(ls)
 
+    def walk_device(self, ticks, com0, dcom0, h0, push=None, push_ticks=0, replan=None, trace=True, stop=("merge", "solver", "nonfinite")):
+        """The walk of run() queued on the device (cmpc_rollout_walk_device, include/cmpc.h): no host read and no synchronisation inside, the first tick
+        started cold by a kernel, and every tick followed by the record kernel -- a problem whose merge fails (or, per `stop`, whose solve does not converge
+        or whose state is not finite) ENDS on its own and the others walk on, where run() aborts the whole batch.  An ended problem stays in the launches,
+        unobserved.  com0 / dcom0 / h0 [B, 3] and push [B, 3]: numpy or CUDA tensors; replan {tick: (t, pose, n)} splits the walk into one call per
+        segment (self.plan is left as it was); force_sample_time and models as in run(); not with retry="launch".
+        -> dict of CUDA tensors, valid once the solver's launch stream has run (torch's current stream is made to wait for it): with trace=True the trace
+        com[ticks, B, 3], zmp[ticks, B, 2], land[ticks, B, 2], landing_offset[ticks, B, 2, 3] (float64), iterations[ticks, B], code[ticks, B]; the outcome
+        end_tick[B] (-1: walked to the end), end_code[B], iterations_sum[B], iterations_max[B], final_state[B, 9], box_slack_min[B]; stats[ticks, 6];
+        lists (t, pose, n) of the last tick; X, P, info of the last tick; state[B, 9], the batch's state buffer after the last tick (ended problems
+        included, unlike final_state)."""
+        torch = self.torch
+        assert self.retry != "launch", "walk_device needs retry='kernel' or None"
+        ls = self.solver.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        try:
+            with torch.cuda.stream(ls):
+                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop)
+        finally:
+            cur.wait_stream(ls)
+
+    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop):
+        torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
+        dt, dev, s = cfg.sampling_time, self.dev, self.solver
+        # (a numpy input is uploaded without the host waiting for the copy; a CUDA tensor is used as it is)
+        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
+
+        def up(a):
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, torch.float32)
+            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+            return hold[-1].to(dev, non_blocking=True)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
+        state = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
+        ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
+        wrench_ticks = None
+        if push is not None:    # run()'s schedule: the push on the first max(push_ticks - i, 1) knots of tick i < push_ticks, zeros once at tick push_ticks
+            dpush = up(push)
+            wrench_ticks = z((push_ticks + 1, B, N, 6))
+            for i in range(push_ticks):
+                wrench_ticks[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
+        # the planner's references as in run(): a straight line at the plan's mean speed, a knot every dt from time zero
+        n_plan = ticks + N + 2
+        plan_com = z((B, n_plan, 3))
+        plan_com[:, :, 0] = (self.com_speed * dt * torch.arange(n_plan, dtype=torch.float64, device=dev)).to(torch.float32)[None, :]
+        plan_h = torch.zeros_like(plan_com)
+        rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
+        s.outcome_init_device(state, rec)
+        replan = dict(replan or {})
+        plan = replan.get(0, self.plan)
+        sets = [tuple(a.clone() for a in plan), tuple(torch.zeros_like(a) for a in plan)]
+        starts = sorted({0} | {t for t in replan if 0 < t < ticks})
+        cur = 0
+        for j, t0 in enumerate(starts):
+            t1 = starts[j + 1] if j + 1 < len(starts) else ticks
+            plan = replan.get(t0, plan)
+            wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
+            cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
+                                        wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=(plan_com, plan_h, dt, 0.0, 1.0, 0.7),
+                                        force_sample_time=self.force_sample_time)
+        del rec["_c"]
+        rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
+        return rec
+
     def _tick_by_steps(self, i, now, mpc_prev, warm, dump, dP, dX0, dX, dInfo, state, wrench, dpush, push_ticks, planner):
         """one tick as seven calls of the C ABI with the host between them (cold starts, retry="launch", the dump hook; native_tick=False)"""
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N

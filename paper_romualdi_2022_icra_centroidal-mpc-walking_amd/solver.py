@@ -773,12 +773,9 @@ class BatchSolver:
             self._h, dComIn.data_ptr(), dHIn.data_ptr(), int(dComIn.shape[1]), float(in_dt), float(t_offset), float(robot_mass),
             float("nan") if com_height is None else float(com_height), dP.data_ptr(), st))
 
-    def rollout_tick_device(self, now, plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, warm,
-                            step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
-        """cmpc_rollout_tick_device: merge -> sample -> setState -> shift -> solve -> step adjustment -> plant as ONE call (include/cmpc.h); plan / prev /
-        lists = (t, pose, n) CUDA tensors, prev None on the first tick (lists is then taken as filled by the caller); dWrench may be None.
-        force_sample_time: the planner's lists (the caller's lists on the first tick, in place) are snapped to the MPC grid first (forceSampleTime,
-        CentroidalMPCBlock.cpp:586-592); ok is then written on the first tick too."""
+    def _tick_io(self, plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                 force_sample_time):
+        """the cmpc_tick_io of one tick (include/cmpc.h) from torch CUDA tensors; the box limits are the configuration's"""
         from ._capi import CmpcTickIO
         if getattr(self, "_box", None) is None:
             self._box = (np.ascontiguousarray([c.bounding_box_upper_limit for c in self.cfg.contacts], np.float32),
@@ -794,7 +791,82 @@ class BatchSolver:
             io.dPlanCom, io.dPlanH, io.plan_knots, io.plan_dt, io.plan_t_offset = pc.data_ptr(), ph.data_ptr(), int(pc.shape[1]), float(pdt), float(poff)
             io.robot_mass, io.com_height = float(mass), float("nan") if height is None else float(height)
         io.force_sample_time = 1 if force_sample_time else 0
+        return io
+
+    def rollout_tick_device(self, now, plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, warm,
+                            step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+        """cmpc_rollout_tick_device: merge -> sample -> setState -> shift -> solve -> step adjustment -> plant as ONE call (include/cmpc.h); plan / prev /
+        lists = (t, pose, n) CUDA tensors, prev None on the first tick (lists is then taken as filled by the caller); dWrench may be None.
+        force_sample_time: the planner's lists (the caller's lists on the first tick, in place) are snapped to the MPC grid first (forceSampleTime,
+        CentroidalMPCBlock.cpp:586-592); ok is then written on the first tick too."""
+        io = self._tick_io(plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                           force_sample_time)
         self._launch(dP.device, lambda st: self._lib.cmpc_rollout_tick_device(self._h, lists[0].shape[2], float(now), 1 if warm else 0, io, st))
+
+    # ---- the walk on the device (include/cmpc.h, "a walk of the whole batch on the device") ----
+    def walk_record(self, rows, stop=("merge", "solver", "nonfinite"), trace=True, device=None):
+        """The arrays of a cmpc_walk_record as a dict of CUDA tensors (trace arrays only with trace=True) plus "_c", the C struct that points at them.
+        stop: which tick codes end a problem, names of _capi.STOP_BITS ("merge" is always honoured).  The outcome is NOT set up: outcome_init_device."""
+        import torch
+        B = self.batch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        r = dict(end_tick=z((B,), torch.int32), end_code=z((B,), torch.int32), iterations_sum=z((B,), torch.int32), iterations_max=z((B,), torch.int32),
+                 final_state=z((B, 9), torch.float32), box_slack_min=z((B,), torch.float32), stats=z((rows, 6), torch.int32))
+        if trace:
+            r.update(com=z((rows, B, 3), torch.float32), zmp=z((rows, B, 2), torch.float32), land=z((rows, B, 2), torch.int32),
+                     landing_offset=z((rows, B, 2, 3), torch.float64), iterations=z((rows, B), torch.int32), code=z((rows, B), torch.int32))
+        ptr = lambda k: r[k].data_ptr() if k in r else None
+        mask = 0
+        for name in stop:
+            mask |= _capi.STOP_BITS[name]
+        r["_c"] = _capi.CmpcWalkRecord(int(rows), mask, ptr("com"), ptr("zmp"), ptr("land"), ptr("landing_offset"), ptr("iterations"), ptr("code"),
+                                       ptr("end_tick"), ptr("end_code"), ptr("iterations_sum"), ptr("iterations_max"), ptr("final_state"),
+                                       ptr("box_slack_min"), ptr("stats"))
+        return r
+
+    def outcome_init_device(self, dState0, rec):
+        """cmpc_rollout_outcome_init_device: the outcome arrays of rec (walk_record) at their start, final_state = dState0[B, 9]."""
+        assert dState0.is_contiguous() and tuple(dState0.shape) == (self.batch, 9)
+        self._launch(dState0.device, lambda st: self._lib.cmpc_rollout_outcome_init_device(self._h, dState0.data_ptr(), rec["_c"], st))
+
+    def rollout_record_device(self, tick, row, dX, dP, dInfo, ok, land, dStateOut, dZmp, rec):
+        """cmpc_rollout_record_device: the record of one tick into row `row` of rec (walk_record) from what the tick left; ok / dZmp may be None."""
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        self._launch(dX.device, lambda st: self._lib.cmpc_rollout_record_device(
+            self._h, int(tick), int(row), dX.data_ptr(), dP.data_ptr(), dInfo.data_ptr(), ptr(ok), land.data_ptr(), dStateOut.data_ptr(), ptr(dZmp),
+            rec["_c"], st))
+
+    def cold_start_device(self, dP, dX0=None):
+        """cmpc_cold_start_device: the cold start (CoM at com0, feet at nominal, f_z = g / 8 per corner) of dP[B, np] into dX0[B, nx]."""
+        import torch
+        L = self.layout
+        assert dP.is_contiguous() and dP.dtype == torch.float32 and tuple(dP.shape) == (self.batch, L.np)
+        if dX0 is None:
+            dX0 = torch.empty((self.batch, L.nx), dtype=torch.float32, device=dP.device)
+        assert dX0.is_contiguous() and dX0.dtype == torch.float32 and tuple(dX0.shape) == (self.batch, L.nx)
+        self._launch(dP.device, lambda st: self._lib.cmpc_cold_start_device(self._h, dP.data_ptr(), dX0.data_ptr(), st))
+        return dX0
+
+    def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
+                            wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+        """cmpc_rollout_walk_device: `ticks` ticks from tick number tick0 queued in one call, each followed by its record (rec: walk_record, or None), in
+        place on dState.  lists / lists_b: the two sets of list buffers (t, pose, n), lists_in the one that holds the previous tick's lists (the first
+        tick's own with cold_first); returns the set that holds the last tick's.  wrench_ticks[T, B, N, 6]: tick i < T of the call writes row i.
+        planner = (dComIn, dHIn, in_dt, t_first, robot_mass, com_height), t_first the time of the trajectories' first knot."""
+        io = _capi.CmpcWalkIO()
+        io.tick = self._tick_io(plan, None, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                force_sample_time)
+        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
+        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        if wrench_ticks is not None:
+            assert wrench_ticks.is_contiguous() and tuple(wrench_ticks.shape[1:]) == (self.batch, self.cfg.N, 6)
+            io.dWrenchTicks, io.wrench_ticks = wrench_ticks.data_ptr(), int(wrench_ticks.shape[0])
+        out = C.c_int(-1)
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_device(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
+            int(lists_in), C.byref(out), st))
+        return out.value
 
     def shift_solution_device(self, dXprev, dX0):
         """is_warm_start_enabled: dX0 = dXprev shifted by one knot; solve from it with solve_device(..., warm=True)."""
