@@ -627,8 +627,15 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
  * the tick's good problems, problems not ended before the tick whose code is 2..4, 0 }: what a reduction of the trace row gives.  Integer atomics, so
  * the result does not depend on the order: each wave reduces first, then adds once per word; lanes past B and lanes of ended problems contribute the
  * identity.  The call clears the row first.
- * Isolation: the record writes nothing a tick reads, so a recorded walk is bit-identical to an unrecorded one.  An ended problem is NOT taken out of
- * the batch: it keeps running unobserved, holds its CU in every solve, and a failed merge keeps failing. */
+ * Isolation: the record writes nothing a tick reads, so a recorded walk is bit-identical to an unrecorded one.  By default an ended problem stays in
+ * every launch: it keeps running unobserved, holds its CU in every solve, a failed merge keeps failing, and its buffers go on being overwritten (only
+ * dFinalState keeps a state of it worth reading).  cmpc_set_ended_device (below) takes it out:
+ *   - with the mask set, everything a tick writes for an ended problem -- its rows of dP, dX0, dX, dInfo, dOk, dLand, dStateOut, dZmp, of both list
+ *     sets and of the multiplier record -- holds, after any number of further ticks, exactly what it held after the problem's ending tick (the ending
+ *     tick itself ran in full: the record that ends a problem runs behind it.  dStateOut of a problem ended at tick i is therefore what tick i left,
+ *     one plant step past dFinalState, the state after its last GOOD tick);
+ *   - every walking problem is bit-identical to the same walk without the mask;
+ *   - with the mask NULL every entry point behaves as it does without this setting. */
 typedef struct cmpc_walk_record {
     int rows;                /* rows of the trace arrays and of dStats */
     int stop_mask;
@@ -673,6 +680,23 @@ typedef struct cmpc_walk_io {
 } cmpc_walk_io;
 int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                              int row0, int lists_in, int* lists_out, void* stream);
+/* Ended problems out of the launches.  dEndTick: [B] device ints in the convention of cmpc_walk_record.dEndTick -- -1 a walking problem, >= 0 an ended
+ * one -- or NULL: off (the default).  Sticky on the handle, like cmpc_set_warm_policy and cmpc_set_multiplier_output.  Only the pointer is kept: the words
+ * are read on the device by each launch when that launch runs, so what the record kernel of tick i wrote is what tick i + 1 on the same stream sees, and a
+ * walk passes rec->dEndTick itself:
+ *     cmpc_set_ended_device(h, rec->dEndTick);  cmpc_rollout_walk_device(h, ...);  cmpc_set_ended_device(h, NULL);
+ * (or the same around cmpc_rollout_tick_device + cmpc_rollout_record_device called tick by tick).  The pointer is captured when a launch is queued:
+ * clearing the setting behind a queued walk does not affect the queued ticks, and the array must stay allocated until they have run.
+ * While it is set, a problem whose word is >= 0 is left out of -- none of its data is written by --
+ *   - the solve, whichever call launches it through the handle (cmpc_solve_device[_warm], cmpc_solve, cmpc_advance, the tick, the walk; both factor
+ *     storages): no dX, no dInfo, no multiplier record, no factor scratch; its workgroup returns before it touches LDS and frees its CU at once
+ *     (cmpc_solve / cmpc_advance still copy such a problem's rows back and judge its status words as they find them);
+ *   - the front kernel of a tick (no merge, snap, sample, state, wrench or reference rows, no warm shift into dX0, no dOk, no dLand), the standalone
+ *     snap launch a tick issues for max_contacts > 16, the cold start (of a walk's first tick and of cmpc_cold_start_device);
+ *   - the back kernel of a tick (no dStateOut, no dZmp, no step adjustment of the list).
+ * The record kernel needs nothing: it treats an ended problem from dEndTick alone.  No kernel gains a barrier and no tick gains a launch.  Every other
+ * entry point (the single-step kernels, the NLP evaluations, the sensitivities) does not read the mask.  CMPC_ERR_ARG for a NULL handle. */
+int cmpc_set_ended_device(cmpc_handle h, const int* dEndTick);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
  * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated; the orientations have their own entry point below
  * (cmpc_contacts_orientation_vjp_device).  The forward maps move positions

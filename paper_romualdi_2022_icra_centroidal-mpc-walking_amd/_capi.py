@@ -123,6 +123,7 @@ EXPORTS = [
     "cmpc_plant_step_jvp_rot_device", "cmpc_plant_step_vjp_rot_device", "cmpc_contacts_orientation_vjp_device", "cmpc_rollout_tick_vjp_rot_device",
     "cmpc_plant_step_jvp_cols_device", "cmpc_contacts_jvp_device", "cmpc_rollout_tick_jvp_device",
     "cmpc_rollout_record", "cmpc_rollout_record_device", "cmpc_rollout_outcome_init_device", "cmpc_cold_start_device", "cmpc_rollout_walk_device",
+    "cmpc_set_ended_device",
 ]
 
 _lib = None
@@ -238,6 +239,8 @@ def lib():
             L.cmpc_rollout_outcome_init_device.argtypes = [vp, vp, rp, vp]
             L.cmpc_cold_start_device.argtypes = [vp, fp, fp, vp]
             L.cmpc_rollout_walk_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), rp, i, i, ip, vp]
+        if hasattr(L, "cmpc_set_ended_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_set_ended_device.argtypes = [vp, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -48,16 +48,16 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, long long snap_dt_ns, const int* snap_ok, hipStream_t stream);
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
-                                             hipStream_t stream);
+                                             const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
-                                     const double* t, float* pose, const int* n, hipStream_t stream);
+                                     const double* t, float* pose, const int* n, const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream);
 extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                                         float* slack_min, hipStream_t stream);
-extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, hipStream_t stream);
+extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream);
@@ -106,6 +106,7 @@ struct cmpc_handle_s {
     float* dBox = nullptr;       // bounding-box limits upper[2][3] | lower[2][3] of the schedule sampler
     float* dDuals = nullptr;     // the dual record of the last solve [B][NS (N+1) + 2 NI N] (cmpc_set_multiplier_output, or the diagnostic knob below)
     bool mult_out = false;       // cmpc_set_multiplier_output: every solve writes dDuals
+    const int* dEnded = nullptr; // cmpc_set_ended_device: the caller's [B] words, read by the launches on the device (>= 0: the problem is left out); null: off
     float* dLamG = nullptr;      // [B][n_g] staging of cmpc_get_multipliers (allocated on first use)
     double* dSensWs = nullptr;   // workspace of the solution sensitivities, min(B, CMPC_SENS_SUB_BATCH) problems (allocated on first use)
     hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
@@ -377,6 +378,7 @@ static void fill_params(cmpc_handle h, CmpcParams& p)
     p.t_floor = 1e-2f;
     p.warm_budget = h->warm_budget; p.warm_no_restart = h->warm_no_restart;
     p.duals = (h->mult_out || h->warm_duals) ? h->dDuals : nullptr; p.warm_duals = h->warm_duals;
+    p.ended = h->dEnded;
 }
 
 static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm)
@@ -414,6 +416,13 @@ int cmpc_set_warm_policy(cmpc_handle h, int warm_budget, int restart_in_kernel)
 int cmpc_solve_device_warm(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream)
 {
     return solve_device_impl(h, dP, dX0, dX, dInfo, stream, true);
+}
+
+int cmpc_set_ended_device(cmpc_handle h, const int* dEndTick)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_set_ended_device: null handle");
+    h->dEnded = dEndTick;   // (only the pointer is kept: the words are read on the device, by each launch when it runs)
+    return CMPC_OK;
 }
 
 namespace {
@@ -1144,7 +1153,7 @@ int cmpc_contacts_force_sample_time_device(cmpc_handle h, int max_contacts, doub
     const long long dt_ns = snap_dt_ns(dt);
     if (!h || max_contacts < 1 || dt_ns < 1 || !dT || !dN || !dOutT) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, dT, dN, dOutT, dOk, 0, stream ? (hipStream_t)stream : h->stream);
+    int rc = cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, dT, dN, dOutT, dOk, 0, nullptr, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("forceSampleTime launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
 }
@@ -1275,6 +1284,7 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: bad planner trajectory");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int* const ended = h->dEnded;   // cmpc_set_ended_device: every launch of the tick leaves out the problems it names (the solve reads it through fill_params)
     long long dt_ns = 0;
     if (io->force_sample_time) {
         dt_ns = snap_dt_ns(h->cfg.sampling_time);
@@ -1296,8 +1306,8 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
             h->snap_cap = need;
         }
         if (!h->dSnapOk) HIPCHK(h, hipMalloc(&h->dSnapOk, sizeof(int) * 2 * (size_t)h->B));
-        const int lrc = merge ? cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dPlanT, io->dPlanN, h->dSnapT, h->dSnapOk, 1, st)
-                              : cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dListT, io->dListN, io->dListT, h->dSnapOk, 1, st);
+        const int lrc = merge ? cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dPlanT, io->dPlanN, h->dSnapT, h->dSnapOk, 1, ended, st)
+                              : cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dListT, io->dListN, io->dListT, h->dSnapOk, 1, ended, st);
         if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (forceSampleTime) launch: ") + hipGetErrorString((hipError_t)lrc));
         if (merge) plan_t = h->dSnapT;
         snap_ok = h->dSnapOk;
@@ -1305,17 +1315,17 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
     int lrc = cmpc_launch_tick_pre(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, merge ? 1 : 0, plan_t, io->dPlanPose, io->dPlanN, io->dPrevT,
                                    io->dPrevPose, io->dPrevN, io->dListT, io->dListPose, io->dListN, io->dOk, io->dLand, h->dBox, io->dState, io->dWrench, io->dP,
                                    warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
-                                   io->com_height, dt_ns, snap_ok, st);
+                                   io->com_height, dt_ns, snap_ok, ended, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
     if (cold) {
-        lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, st);
+        lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, ended, st);
         if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (cold start) launch: ") + hipGetErrorString((hipError_t)lrc));
     }
     rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
     if (rc != CMPC_OK) return rc;
     lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
                                 (float)io->plant_step, io->plant_substeps, (float)io->zmp_half_x, (float)io->zmp_half_y, io->dLand, io->dListT, io->dListPose,
-                                io->dListN, st);
+                                io->dListN, ended, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (back) launch: ") + hipGetErrorString((hipError_t)lrc));
     return CMPC_OK;
 }
@@ -1394,7 +1404,7 @@ int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* str
 {
     if (!h || !dP || !dX0) return fail(h, CMPC_ERR_ARG, "cmpc_cold_start_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, stream ? (hipStream_t)stream : h->stream);
+    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, h->dEnded, stream ? (hipStream_t)stream : h->stream);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("cold start launch: ") + hipGetErrorString((hipError_t)lrc));
     return CMPC_OK;
 }

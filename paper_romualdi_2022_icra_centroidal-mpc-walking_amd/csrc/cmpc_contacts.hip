@@ -26,12 +26,14 @@ __global__ __launch_bounds__(128) void cmpc_contacts_merge_kernel(int B, int M, 
 // forceSampleTime (CentroidalMPCBlock.cpp:586-592): one thread per (problem, foot, contact), cmpc_snap_contact.  Entries m >= n are copied unchanged
 // (a no-op in place).  A list length outside 0..M or a failed contact clears the foot's status word: ok[problem] (ok_per_foot = 0, as the merge kernel)
 // or ok[problem * 2 + foot] (ok_per_foot = 1: the roll-out tick, which empties only that foot); a foot whose length is out of range is not read or written.
+// ended (the roll-out tick under cmpc_set_ended_device, else null): the entries of a problem whose word is >= 0 are neither read nor written.
 __global__ __launch_bounds__(128) void cmpc_force_sample_time_kernel(int B, int M, long long dt_ns, const double* t, const int* __restrict__ n, double* out_t,
-                                                                     int* __restrict__ ok, int ok_per_foot)
+                                                                     int* __restrict__ ok, int ok_per_foot, const int* __restrict__ ended)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (problem * 2 + foot) * M + contact
     if (i >= 2LL * B * M) return;
     const int e = (int)(i / M), m = (int)(i - (long long)e * M);
+    if (ended && ended[e >> 1] >= 0) return;
     const int ne = n[e];
     bool good = ne >= 0 && ne <= M;
     if (good) {
@@ -384,11 +386,11 @@ extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double
 }
 
 extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
-                                             hipStream_t stream)
+                                             const int* ended, hipStream_t stream)
 {
     if (ok) hipLaunchKernelGGL(cmpc_fill_int_kernel, dim3((B * (ok_per_foot ? 2 : 1) + 127) / 128), dim3(128), 0, stream, B * (ok_per_foot ? 2 : 1), 1, ok);
     const long long threads = 2LL * B * M;
-    hipLaunchKernelGGL(cmpc_force_sample_time_kernel, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, stream, B, M, dt_ns, t, n, out_t, ok, ok_per_foot);
+    hipLaunchKernelGGL(cmpc_force_sample_time_kernel, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, stream, B, M, dt_ns, t, n, out_t, ok, ok_per_foot, ended);
     return (int)hipGetLastError();
 }
 

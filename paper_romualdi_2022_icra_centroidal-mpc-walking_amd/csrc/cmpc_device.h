@@ -160,4 +160,5 @@ struct CmpcParams {
     long long scratch_stride;    // floats per problem
     int lds_words;               // 4-byte words of dynamic LDS the launch was given (set by cmpc_launch_solver)
     int kc_per_problem;          // 0: kc is the batch's one record; 1: kc[B], one record per problem (cmpc_set_models)
+    const int* ended;            // [B] or null (cmpc_set_ended_device): a problem whose word is >= 0 is left out of the solve -- its workgroup returns first thing
 };

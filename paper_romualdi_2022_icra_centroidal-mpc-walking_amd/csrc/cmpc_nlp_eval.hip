@@ -1452,9 +1452,11 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
                                                             const float* __restrict__ state, const float* __restrict__ wrench, float* P,
                                                             const float* __restrict__ Xprev, float* __restrict__ X0, const float* __restrict__ plan_com,
                                                             const float* __restrict__ plan_h, int plan_knots, double plan_dt, double plan_t_offset,
-                                                            double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok)
+                                                            double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok,
+                                                            const int* __restrict__ ended)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device: the whole workgroup, ahead of its first barrier -- nothing of the problem is written)
     const CmpcIdx L{N};
     float* p = P + (size_t)b * L.np();
     __shared__ int okw;
@@ -1565,10 +1567,12 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
 __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy, const int* __restrict__ land,
-                                                             const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n)
+                                                             const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n,
+                                                             const int* __restrict__ ended)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
+    if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device; per lane, as the line above: nothing behind it needs the whole wave)
     plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
     const CmpcIdx L{N};
     for (int c = 0; c < 2; ++c) {
@@ -1620,8 +1624,10 @@ __global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const flo
 }
 
 // cold start: one workgroup per problem, one thread per entry of x (cmpc_cold_start_entry)
-__global__ __launch_bounds__(256) void cmpc_cold_start_kernel(int N, float g8, const float* __restrict__ P, float* __restrict__ X0)
+__global__ __launch_bounds__(256) void cmpc_cold_start_kernel(int N, float g8, const float* __restrict__ P, float* __restrict__ X0,
+                                                              const int* __restrict__ ended)
 {
+    if (ended && ended[blockIdx.x] >= 0) return;   // (cmpc_set_ended_device)
     const CmpcIdx L{N};
     const float* p = P + (size_t)blockIdx.x * L.np();
     float* x = X0 + (size_t)blockIdx.x * L.nx();
@@ -1644,9 +1650,9 @@ extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tic
     return (int)hipGetLastError();
 }
 
-extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, hipStream_t stream)
+extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_cold_start_kernel, dim3(B), dim3(256), 0, stream, N, g8, dP, dX0);
+    hipLaunchKernelGGL(cmpc_cold_start_kernel, dim3(B), dim3(256), 0, stream, N, g8, dP, dX0, ended);
     return (int)hipGetLastError();
 }
 
@@ -1654,20 +1660,20 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, long long snap_dt_ns, const int* snap_ok, hipStream_t stream)
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_tick_pre_kernel, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
                        list_t, list_pose, list_n, ok, land, box, state, wrench, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, plan_t_offset, robot_mass,
-                       com_height, snap_dt_ns, snap_ok);
+                       com_height, snap_dt_ns, snap_ok, ended);
     return (int)hipGetLastError();
 }
 
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
-                                     const double* t, float* pose, const int* n, hipStream_t stream)
+                                     const double* t, float* pose, const int* n, const int* ended, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_tick_post_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn, dStateOut, dZmp,
-                       h, nsub, zx, zy, land, t, pose, n);
+                       h, nsub, zx, zy, land, t, pose, n, ended);
     return (int)hipGetLastError();
 }
 

@@ -3475,6 +3475,9 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x;
+    // an ended problem (cmpc_set_ended_device) is left out: its workgroup returns here, ahead of the LDS clear and of every barrier -- uniform over the
+    // workgroup (a scalar load at blockIdx.x), nothing of the problem written, and the CU free for the next workgroup at once
+    if (kp.ended && kp.ended[b] >= 0) return;
     const int tid = threadIdx.x;
     const int N = NC > 0 ? NC : kp.N;
     // The whole LDS image starts at zero.  LDS arrives with whatever the previous workgroup -- or the previous

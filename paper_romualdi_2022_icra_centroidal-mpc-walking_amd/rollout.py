@@ -101,11 +101,19 @@ class WalkingRollout:
         finally:
             cur.wait_stream(ls)
 
-    def walk_device(self, ticks, com0, dcom0, h0, push=None, push_ticks=0, replan=None, trace=True, stop=("merge", "solver", "nonfinite")):
+    def walk_device(self, ticks, com0, dcom0, h0, push=None, push_ticks=0, replan=None, trace=True, stop=("merge", "solver", "nonfinite"),
+                    skip_ended=False):
         """The walk of run() queued on the device (cmpc_rollout_walk_device, include/cmpc.h): no host read and no synchronisation inside, the first tick
         started cold by a kernel, and every tick followed by the record kernel -- a problem whose merge fails (or, per `stop`, whose solve does not converge
-        or whose state is not finite) ENDS on its own and the others walk on, where run() aborts the whole batch.  An ended problem stays in the launches,
-        unobserved.  com0 / dcom0 / h0 [B, 3] and push [B, 3]: numpy or CUDA tensors; replan {tick: (t, pose, n)} splits the walk into one call per
+        or whose state is not finite) ENDS on its own and the others walk on, where run() aborts the whole batch.
+        skip_ended=False (the default): an ended problem stays in the launches, unobserved -- it holds its CU in every later solve, and its rows of state,
+        X, P, info and lists are whatever the ticks behind its end made of them (final_state alone keeps the state after its last good tick).
+        skip_ended=True: the record's end_tick is the handle's mask (cmpc_set_ended_device) around the queued segments, cleared again before the call
+        returns (a later run() on this object is untouched): an ended problem is left out of every launch behind its ending tick, and its rows of state, X,
+        P, info and of both list sets stay exactly what the ending tick left -- state is that tick's plant step from its (discarded) solve, one step past
+        final_state (the list sets alternate from tick to tick, so an ended problem's rows of the returned `lists` are its ending tick's or the tick before's,
+        as the parity of the remaining ticks has it).  The walking problems are bit-identical either way; still one call per segment, no host read, no synchronisation.
+        com0 / dcom0 / h0 [B, 3] and push [B, 3]: numpy or CUDA tensors; replan {tick: (t, pose, n)} splits the walk into one call per
         segment (self.plan is left as it was); force_sample_time and models as in run(); not with retry="launch".
         -> dict of CUDA tensors, valid once the solver's launch stream has run (torch's current stream is made to wait for it): with trace=True the trace
         com[ticks, B, 3], zmp[ticks, B, 2], land[ticks, B, 2], landing_offset[ticks, B, 2, 3] (float64), iterations[ticks, B], code[ticks, B]; the outcome
@@ -119,11 +127,11 @@ class WalkingRollout:
         ls.wait_stream(cur)
         try:
             with torch.cuda.stream(ls):
-                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop)
+                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
         finally:
             cur.wait_stream(ls)
 
-    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop):
+    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         # (a numpy input is uploaded without the host waiting for the copy; a CUDA tensor is used as it is)
@@ -156,13 +164,19 @@ class WalkingRollout:
         sets = [tuple(a.clone() for a in plan), tuple(torch.zeros_like(a) for a in plan)]
         starts = sorted({0} | {t for t in replan if 0 < t < ticks})
         cur = 0
-        for j, t0 in enumerate(starts):
-            t1 = starts[j + 1] if j + 1 < len(starts) else ticks
-            plan = replan.get(t0, plan)
-            wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
-            cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
-                                        wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=(plan_com, plan_h, dt, 0.0, 1.0, 0.7),
-                                        force_sample_time=self.force_sample_time)
+        if skip_ended:    # (the queued launches keep the pointer; rec["end_tick"] goes back to the caller and outlives them)
+            s.set_ended_device(rec["end_tick"])
+        try:
+            for j, t0 in enumerate(starts):
+                t1 = starts[j + 1] if j + 1 < len(starts) else ticks
+                plan = replan.get(t0, plan)
+                wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
+                cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
+                                            wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=(plan_com, plan_h, dt, 0.0, 1.0, 0.7),
+                                            force_sample_time=self.force_sample_time)
+        finally:
+            if skip_ended:
+                s.set_ended_device(None)
         del rec["_c"]
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
         return rec

@@ -182,6 +182,21 @@ class BatchSolver:
         if rc != 0:
             raise RuntimeError(f"cmpc_set_warm_policy failed ({rc}): {self.last_error}")
 
+    def set_ended_device(self, end_tick=None):
+        """cmpc_set_ended_device: end_tick an int32 CUDA tensor [B] in the convention of a walk record's end_tick (-1 walking, >= 0 ended), read on the
+        device by every later solve, tick and cold start on this handle when it runs: a problem whose word is >= 0 is left out of those launches and none
+        of its data is written (include/cmpc.h).  None: off (the default).  The tensor is referenced from here while it is set; launches already queued
+        keep the pointer they were queued with, so a caller who clears the setting keeps the tensor alive until they have run."""
+        if not hasattr(self._lib, "cmpc_set_ended_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_set_ended_device")
+        if end_tick is not None:
+            import torch
+            assert end_tick.is_cuda and end_tick.dtype == torch.int32 and end_tick.is_contiguous() and tuple(end_tick.shape) == (self.batch,)
+        rc = self._lib.cmpc_set_ended_device(self._h, end_tick.data_ptr() if end_tick is not None else None)
+        if rc != 0:
+            raise RuntimeError(f"cmpc_set_ended_device failed ({rc}): {self.last_error}")
+        self._ended = end_tick
+
     def last_solve_ms(self) -> float:
         return float(self._lib.cmpc_last_solve_ms(self._h))
 
