@@ -856,6 +856,96 @@ typedef struct cmpc_tick_dirs_out {
 int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
                                  const cmpc_tick_dirs_out* out, float* dTickSens, void* stream);
 
+/* ---- the device walk taped and run in reverse, per-problem endings kept (derivation and the rule: DESIGN.md 7f) ----
+ * cmpc_walk_tape: what cmpc_rollout_tick_vjp_device needs of `rows` ticks, in device arrays the caller owns (BatchSolver.walk_tape allocates them), row
+ * after row laid out like the fields of cmpc_tick_tape; M = max_contacts:
+ *     dX[rows][B][n_x], dP[rows][B][n_p], dLamG[rows][B][n_g], dInfo[rows][B][CMPC_INFO]   float
+ *     dStates[rows + 1][B][9]                                                              float: row r the state tick r started from, row r + 1 what it left
+ *     dOk[rows][B], dLand[rows][B][2]                                                      int
+ *     dPlanT, dListT[rows][B][2][M][2]                                                     double: the planner's and the merged lists' times
+ *     dPlanN, dListN[rows][B][2]                                                           int
+ * The previous tick's list of row r is row r - 1's dListT / dListN: no second copy is kept.  The planner's times are copied per row, so that a replanned
+ * walk tapes correctly and the tape does not depend on the caller's buffers staying alive.  Host scalars: plant_step, plant_substeps, force_sample_time as
+ * the forward ticks'; first_row_is_first_tick != 0: row 0 is a first tick (no merge, no previous list) -- otherwise row 0 cannot be reversed.
+ * Size: 4 (n_x + n_p + n_g) + 64 M + 96 bytes per problem and tick (the three wide rows, then 2 x 32 M of times, info 32, state 36, ok 4, land and the two
+ * counts 8 each), about 12 KB at N = 20 (x, p and lam_g are a thousand floats each).
+ * Out of scope here: the orientation (_rot) chain and the forward-mode (_jvp) walk on this tape -- both can follow on the same layout.  Contact times and
+ * Gamma stay undifferentiated, as everywhere. */
+typedef struct cmpc_walk_tape {
+    int rows;
+    float* dX; float* dP; float* dLamG; float* dInfo; float* dStates;
+    int* dOk; int* dLand;
+    double* dPlanT; double* dListT; int* dPlanN; int* dListN;
+    double plant_step; int plant_substeps; int force_sample_time; int first_row_is_first_tick;
+} cmpc_walk_tape;
+/* One row of the tape from what a tick left, in two parts (`parts`: 1, 2 or 3 = both):
+ *   part 1, BEFORE the tick: dStateIn[B][9] -> dStates[row].  Needed for the first taped tick only (every later row was written by part 2 of the row before);
+ *     it exists because a roll-out runs in place (dState == dStateOut): the state a tick started from is gone once it has run.
+ *   part 2, BEHIND the tick: one launch of cmpc_rollout_tape_kernel makes bit copies of dX, dP, dInfo, dOk (NULL -- a first tick without force_sample_time
+ *     leaves dOk alone -- gives dOk = 1 for every problem, as the record treats it), dLand, dPlanT / dPlanN (NULL on a first tick: the row is left alone),
+ *     dListT / dListN, and dStateOut -> dStates[row + 1]; then cmpc_get_multipliers_device (called, not copied) writes the row's dLamG.
+ * parts = 3 does both behind a tick that did NOT run in place.  cmpc_rollout_walk_taped_device uses part 1 in front of its first tick and part 2 behind every tick.
+ * The multiplier output must be on already (cmpc_set_multiplier_output: turning it on synchronises, so it is not done here): else CMPC_ERR_ARG.  x and info
+ * are bit-identical with it on.  Device pointers; asynchronous on `stream` (NULL: the handle's).  With cmpc_set_ended_device set nothing changes here: an ended
+ * problem's buffers are frozen, so its later rows hold its ending tick's data. */
+int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts, const float* dX, const float* dP, const float* dInfo, const int* dOk,
+                             const int* dLand, const float* dStateIn, const float* dStateOut, const double* dPlanT, const int* dPlanN, const double* dListT,
+                             const int* dListN, const cmpc_walk_tape* tape, void* stream);
+/* cmpc_rollout_walk_device with the tape part behind every tick: tick i of the call writes row tape_row0 + i (part 1 in front of tick 0 of the call, part 2
+ * and the multipliers behind each tick: two launches more per tick).  Every tick is bit-identical to the untaped walk's and the record is unchanged.  tape's
+ * scalars must agree with io (plant_step, plant_substeps, force_sample_time; first_row_is_first_tick with cold_first when tape_row0 == 0) and the multiplier
+ * output must be on: else CMPC_ERR_ARG. */
+int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                   int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream);
+/* The reverse walk: `ticks` calls of cmpc_rollout_tick_vjp_device (called, not copied: its workspace, statuses and zero rule for flagged problems hold),
+ * last row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of cmpc_walk_vjp_gate_kernel).  Tick number tick0 + i is row
+ * row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time.
+ * The fields of cmpc_walk_grads, device pointers all:
+ *     dGradStates[rows + 1][B][9] double   in: the seeds G on the states (row r: the state tick r started from)
+ *     dGradX[rows][B][n_x] float or NULL   in: the seeds GX on the solutions
+ *     dCarryState[B][9] double             in: the carry entering the last row of the call; out: the carry leaving its first row
+ *     dCarryList[B][2][M][3] double        the same for the lists' positions
+ *     dGradWrench[rows][B][N][6] float or NULL, dGradP[rows][B][n_p] float or NULL   out, per row
+ *     dGradPlan[B][2][M][3] double or NULL, dGradModel[B][34] double or NULL        out, +=
+ *     dStatus[rows][B] int                 out: word 0 of the tick's dTickSens, or 6: the problem had ended
+ * A walk is reversed in segments through the two carry buffers (a replanned walk may pass a different dGradPlan per segment).  A call over the whole walk
+ * with dCarryState = dGradStates[rows] and dCarryList = 0 leaves dl/dstate_0 and dl/dlist_0 in them.
+ * Ended problems (dEndTick[B] in the convention of cmpc_walk_record, tick numbers; NULL: none).  Let e = dEndTick[b], -1 read as never.  The good ticks are
+ * i < e; the states s_0 .. s_e exist (s_e = dFinalState); the loss is sum_{i <= e} <G_i, s_i> + sum_{i < e} <GX_i, x_i>, and seeds of rows past e are not read
+ * for that problem.  Carry: c_i = [i < e] J_i^T c_{i+1} + [i <= e] G_i.  For a tick i >= e the gate feeds the tick VJP a zero state carry, a zero list carry,
+ * a zero dGradX row and dOk = 0 (gated copies in handle workspace; the tick then flags the problem -- its status 5 -- and adds nothing to the += outputs), and
+ * behind the tick it SELECTS zero for the carries, the wrench row and the dGradP row and writes dStatus = 6: it selects and does not multiply, so stale or
+ * non-finite data of an ended problem cannot leak.  For i < e the gate's add is carry = the tick's dGradState + G_i in double.  The rule is one
+ * __host__ __device__ function (cmpc_walk_gate_problem / cmpc_walk_gate_wide); the gate has no barrier and no atomics; lanes past B do nothing.
+ * No host wait beyond the first call's workspace allocation (4 n_x + 48 M + 108 bytes per problem: the tick's dGradState and dGradPrevList, the gated dGradX row and dOk, the tick's dTickSens; grown when a larger
+ * max_contacts arrives, and that call waits for the device); calls on one handle run one after the other whatever their streams (the tick VJP's event). */
+typedef struct cmpc_walk_grads {
+    const double* dGradStates; const float* dGradX;
+    double* dCarryState; double* dCarryList;
+    float* dGradWrench; float* dGradP; double* dGradPlan; double* dGradModel;
+    int* dStatus;
+} cmpc_walk_grads;
+int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                 const cmpc_walk_grads* g, void* stream);
+/* One gate step on the host (host buffers; no handle, no GPU; bit-equal to the kernel): the POST part finishes tick `tick_post` from what the tick VJP left
+ * (tick_state[B][9], tick_list[B][2][M][3], tick_sens[B][CMPC_SENS]) and the seed row seed_state[B][9] into carry_state / carry_list, and selects zero in
+ * wrench_row[B][N][6] / grad_p_row[B][n_p] (either may be NULL) and writes status_row[B]; the PRE part prepares tick `tick_pre`: ok_out[B] from ok_row (NULL:
+ * ones), grad_x_out[B][n_x] from grad_x_row (both NULL: none), and with first != 0 (the first step of a call) zero is selected in the caller's carries too.
+ * A step between two reverse ticks has both parts (tick_pre = tick_post - 1); the first step of a call has PRE only, the last POST only. */
+typedef struct cmpc_walk_gate {
+    int batch, max_contacts, horizon;
+    const int* end_tick;
+    int do_post, tick_post;
+    const double* seed_state; const double* tick_state; const double* tick_list; const float* tick_sens;
+    double* carry_state; double* carry_list; float* wrench_row; float* grad_p_row; int* status_row;
+    int do_pre, tick_pre, first;
+    const int* ok_row; const float* grad_x_row; int* ok_out; float* grad_x_out;
+} cmpc_walk_gate;
+int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g);
+/* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what cmpc_rollout_walk_vjp_device queues
+ * between its ticks, for a caller who reverses a walk tick by tick.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
+int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream);
+
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */
 int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, void* stream);

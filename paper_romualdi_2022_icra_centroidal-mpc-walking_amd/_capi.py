@@ -72,6 +72,26 @@ class CmpcTickTape(C.Structure):
         ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("force_sample_time", C.c_int)]
 
 
+class CmpcWalkTape(C.Structure):
+    """mirror of cmpc_walk_tape (include/cmpc.h): the device tape of a walk, `rows` rows laid out like the fields of cmpc_tick_tape"""
+    _fields_ = [("rows", C.c_int)] + [(k, C.c_void_p) for k in (
+        "dX", "dP", "dLamG", "dInfo", "dStates", "dOk", "dLand", "dPlanT", "dListT", "dPlanN", "dListN")] + [
+        ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("force_sample_time", C.c_int), ("first_row_is_first_tick", C.c_int)]
+
+
+class CmpcWalkGrads(C.Structure):
+    """mirror of cmpc_walk_grads (include/cmpc.h): the seeds, carries and outputs of cmpc_rollout_walk_vjp_device"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "dGradStates", "dGradX", "dCarryState", "dCarryList", "dGradWrench", "dGradP", "dGradPlan", "dGradModel", "dStatus")]
+
+
+class CmpcWalkGate(C.Structure):
+    """mirror of cmpc_walk_gate (include/cmpc.h): one gate step of the reverse walk on the host, cmpc_rollout_walk_vjp_gate"""
+    _fields_ = [("batch", C.c_int), ("max_contacts", C.c_int), ("horizon", C.c_int), ("end_tick", C.c_void_p), ("do_post", C.c_int), ("tick_post", C.c_int)] + [
+        (k, C.c_void_p) for k in ("seed_state", "tick_state", "tick_list", "tick_sens", "carry_state", "carry_list", "wrench_row", "grad_p_row", "status_row")] + [
+        ("do_pre", C.c_int), ("tick_pre", C.c_int), ("first", C.c_int)] + [(k, C.c_void_p) for k in ("ok_row", "grad_x_row", "ok_out", "grad_x_out")]
+
+
 class CmpcTickDirs(C.Structure):
     """mirror of cmpc_tick_dirs (include/cmpc.h): the k direction columns that go into cmpc_rollout_tick_jvp_device, each pointer NULL = zero"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -124,6 +144,8 @@ EXPORTS = [
     "cmpc_plant_step_jvp_cols_device", "cmpc_contacts_jvp_device", "cmpc_rollout_tick_jvp_device",
     "cmpc_rollout_record", "cmpc_rollout_record_device", "cmpc_rollout_outcome_init_device", "cmpc_cold_start_device", "cmpc_rollout_walk_device",
     "cmpc_set_ended_device",
+    "cmpc_rollout_tape_device", "cmpc_rollout_walk_taped_device", "cmpc_rollout_walk_vjp_device", "cmpc_rollout_walk_vjp_gate",
+    "cmpc_rollout_walk_vjp_gate_device",
 ]
 
 _lib = None
@@ -241,6 +263,13 @@ def lib():
             L.cmpc_rollout_walk_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), rp, i, i, ip, vp]
         if hasattr(L, "cmpc_set_ended_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             L.cmpc_set_ended_device.argtypes = [vp, vp]
+        if hasattr(L, "cmpc_rollout_walk_vjp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            tp = C.POINTER(CmpcWalkTape)
+            L.cmpc_rollout_tape_device.argtypes = [vp, i, i, i] + [vp] * 11 + [tp, vp]
+            L.cmpc_rollout_walk_taped_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), C.POINTER(CmpcWalkRecord), i, i, ip, tp, i, vp]
+            L.cmpc_rollout_walk_vjp_device.argtypes = [vp, i, i, i, tp, i, vp, C.POINTER(CmpcWalkGrads), vp]
+            L.cmpc_rollout_walk_vjp_gate.argtypes = [C.POINTER(CmpcWalkGate)]
+            L.cmpc_rollout_walk_vjp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkGate), vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -58,6 +58,9 @@ extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, h
 extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                                         float* slack_min, hipStream_t stream);
 extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);
+extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
+extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
+extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a);
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream);
@@ -119,6 +122,9 @@ struct cmpc_handle_s {
     char* dTickJvpWs = nullptr;  // workspace of cmpc_rollout_tick_jvp_device for tick_jvp_cols columns per problem (allocated on first use, grown when a larger k
     int tick_jvp_cols = 0;       // arrives): rotation direction [B][k][2][N][3] | its stage 0 [B][k][2][3] | a zero state direction [B][k][9] (double) |
                                  // dx [B][k][n_x] | the assembled p direction [B][k][n_p] (float) | the tick's ok words [B] (int)
+    char* dWalkWs = nullptr;     // workspace of cmpc_rollout_walk_vjp_device for lists of walk_ws_M contacts (allocated on first use, grown when a larger
+    int walk_ws_M = 0;           // max_contacts arrives): the tick's dGradState [B][9] | its dGradPrevList [B][2][M][3] (double) | the gated dGradX row [B][n_x] |
+                                 // the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
     int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
     float hBox[12] = {0};
@@ -321,7 +327,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG); hipFree(h->dSensWs);
     if (h->sens_ev) hipEventDestroy(h->sens_ev);
-    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); hipFree(h->dWalkWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1409,8 +1415,69 @@ int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* str
     return CMPC_OK;
 }
 
+// ---- the device tape (include/cmpc.h, cmpc_walk_tape): one row from what a tick left ----
+static bool tape_complete(const cmpc_walk_tape* t)
+{
+    return t && t->rows >= 1 && t->dX && t->dP && t->dLamG && t->dInfo && t->dStates && t->dOk && t->dLand && t->dPlanT && t->dListT && t->dPlanN && t->dListN &&
+           t->plant_step > 0 && t->plant_substeps >= 1;
+}
+
+static int rollout_tape_impl(cmpc_handle h, int max_contacts, int row, int parts, const float* dX, const float* dP, const float* dInfo, const int* dOk,
+                             const int* dLand, const float* dStateIn, const float* dStateOut, const double* dPlanT, const int* dPlanN, const double* dListT,
+                             const int* dListN, const cmpc_walk_tape* tape, void* stream)
+{
+    if (!h || !tape_complete(tape) || max_contacts < 1 || row < 0 || row >= tape->rows || parts < 1 || parts > 3)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: bad argument");
+    if (((parts & 1) && !dStateIn) || ((parts & 2) && (!dX || !dP || !dInfo || !dLand || !dStateOut || !dListT || !dListN || (!dPlanT != !dPlanN))))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: null argument");
+    if (parts == 3 && dStateIn == dStateOut)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: a tick that ran in place needs part 1 in front of it");
+    if ((parts & 2) && (!h->mult_out || !h->dDuals))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: the multiplier output is off (cmpc_set_multiplier_output before the ticks)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const CmpcTapeArgs a{h->B, max_contacts, h->L.nx, h->L.np, row, parts, dX, dP, dInfo, dOk, dLand, dStateIn, dStateOut, dPlanT, dPlanN, dListT, dListN,
+                         tape->dX, tape->dP, tape->dInfo, tape->dStates, tape->dOk, tape->dLand, tape->dPlanT, tape->dListT, tape->dPlanN, tape->dListN};
+    const int lrc = cmpc_launch_rollout_tape(&a, st);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("roll-out tape launch: ") + hipGetErrorString((hipError_t)lrc));
+    if (parts & 2) return cmpc_get_multipliers_device(h, dX, dP, tape->dLamG + (size_t)row * h->B * h->L.ng, stream);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts, const float* dX, const float* dP, const float* dInfo, const int* dOk,
+                             const int* dLand, const float* dStateIn, const float* dStateOut, const double* dPlanT, const int* dPlanN, const double* dListT,
+                             const int* dListN, const cmpc_walk_tape* tape, void* stream)
+{
+    return rollout_tape_impl(h, max_contacts, row, parts, dX, dP, dInfo, dOk, dLand, dStateIn, dStateOut, dPlanT, dPlanN, dListT, dListN, tape, stream);
+}
+
+static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream);
+
 int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                              int row0, int lists_in, int* lists_out, void* stream)
+{
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream);
+}
+
+int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                   int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
+{
+    if (!h || !io || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: null argument or incomplete tape");
+    if (ticks < 1 || tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape has too few rows");
+    if (tape->plant_step != io->tick.plant_step || tape->plant_substeps != io->tick.plant_substeps ||
+        (tape->force_sample_time != 0) != (io->tick.force_sample_time != 0) ||
+        (tape_row0 == 0 ? (tape->first_row_is_first_tick != 0) != (cold_first != 0) : cold_first != 0))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape's scalars do not agree with the walk (or a first tick beyond row 0)");
+    if (!h->mult_out || !h->dDuals)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream);
+}
+
+// tape != null: the tape part around the ticks (cmpc_rollout_walk_taped_device, which has checked it); null: the launches of cmpc_rollout_walk_device
+static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
 {
     if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: null argument");
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !io->tick.dListT || !io->tick.dListPose ||
@@ -1446,10 +1513,16 @@ int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int tic
         if (i > 0) t.dState = io->tick.dStateOut;
         if (io->dWrenchTicks) t.dWrench = i < io->wrench_ticks ? io->dWrenchTicks + wrench_row * i : nullptr;
         t.plan_t_offset = now - io->plan_t_first;
-        rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true);
+        const int* const ok_read = (cold && !t.force_sample_time) ? nullptr : t.dOk;
+        if (tape && i == 0)   // (the ticks run in place: the state the first one starts from is copied in front of it)
+            rc = rollout_tape_impl(h, max_contacts, tape_row0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, t.dState, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   tape, stream);
+        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true);
         if (rc == CMPC_OK && rec)
-            rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, (cold && !t.force_sample_time) ? nullptr : t.dOk, t.dLand, t.dStateOut, t.dZmp,
-                                     rec, st, false);
+            rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, ok_read, t.dLand, t.dStateOut, t.dZmp, rec, st, false);
+        if (rc == CMPC_OK && tape)
+            rc = rollout_tape_impl(h, max_contacts, tape_row0 + i, 2, t.dX, t.dP, t.dInfo, ok_read, t.dLand, nullptr, t.dStateOut, cold ? nullptr : t.dPlanT,
+                                   cold ? nullptr : t.dPlanN, t.dListT, t.dListN, tape, stream);
     }
     h->timing = timing;
     if (rc == CMPC_OK && lists_out) *lists_out = cur;
@@ -1592,6 +1665,124 @@ int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now
 {
     return tick_vjp(h, true, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
                     dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream);
+}
+
+// ---- the reverse walk on the device tape (include/cmpc.h, cmpc_rollout_walk_vjp_device): gate, tick VJP, gate, ..., gate ----
+static CmpcGateArgs gate_args_of(const cmpc_walk_gate* g, int nx, int np)
+{
+    return CmpcGateArgs{g->batch, g->max_contacts, g->horizon, nx, np, g->end_tick, g->do_post, g->tick_post, g->seed_state, g->tick_state, g->tick_list,
+                        g->tick_sens, g->carry_state, g->carry_list, g->wrench_row, g->grad_p_row, g->status_row, g->do_pre, g->tick_pre, g->first, g->ok_row,
+                        g->grad_x_row, g->ok_out, g->grad_x_out};
+}
+
+static int gate_check(const cmpc_walk_gate* g);
+
+int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: null handle");
+    const int rc = gate_check(g);
+    if (rc != CMPC_OK) return rc;
+    if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: batch and horizon must be the handle's");
+    HIPCHK(h, hipSetDevice(h->device));
+    const CmpcGateArgs a = gate_args_of(g, h->L.nx, h->L.np);
+    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+static int gate_check(const cmpc_walk_gate* g)
+{
+    if (!g || g->batch < 1 || g->max_contacts < 1 || g->horizon < 1 || g->horizon > CMPC_NMAX || (!g->do_post && !g->do_pre) || !g->carry_state || !g->carry_list)
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: bad argument");
+    if (g->do_post && (!g->seed_state || !g->tick_state || !g->tick_list || !g->tick_sens || !g->status_row))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: the POST part needs the seed row, the tick's outputs and the status row");
+    if (g->do_pre && (!g->ok_out || (!g->grad_x_row != !g->grad_x_out)))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: the PRE part needs ok_out, and grad_x_row and grad_x_out together");
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g)
+{
+    const int rc = gate_check(g);
+    if (rc != CMPC_OK) return rc;
+    CmpcLayout L;
+    cmpc_layout_init(L, g->horizon);
+    const CmpcGateArgs a = gate_args_of(g, L.nx, L.np);
+    for (int b = 0; b < g->batch; ++b) cmpc_walk_gate_problem(a, b);
+    const size_t wide = cmpc_walk_gate_wide_entries(&a);
+    for (size_t e = 0; e < wide; ++e) cmpc_walk_gate_wide(a, e);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                 const cmpc_walk_grads* g, void* stream)
+{
+    if (!h || !g || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: null argument or incomplete tape");
+    if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: bad argument (the rows must lie inside the tape)");
+    if (!g->dGradStates || !g->dCarryState || !g->dCarryList || !g->dStatus)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: dGradStates, the two carries and dStatus are needed");
+    if (row0 == 0 && !tape->first_row_is_first_tick)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: row 0 is not a first tick and has no row before it to take the previous lists from");
+    HIPCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int B = h->B, N = h->cfg.horizon, M = max_contacts;
+    const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nl = (size_t)B * 6 * M, nt = (size_t)B * 4 * M;
+    if (!h->dWalkWs || h->walk_ws_M < M) {
+        if (h->dWalkWs) {   // (a larger max_contacts: launches that read the old workspace may still be queued)
+            HIPCHK(h, hipDeviceSynchronize());
+            hipFree(h->dWalkWs);
+            h->dWalkWs = nullptr; h->walk_ws_M = 0;
+        }
+        HIPCHK(h, hipMalloc(&h->dWalkWs, sizeof(double) * ((size_t)B * 9 + nl) + sizeof(float) * (nx + (size_t)B * CMPC_SENS) + sizeof(int) * (size_t)B));
+        h->walk_ws_M = M;
+    }
+    double* wsState = reinterpret_cast<double*>(h->dWalkWs);
+    double* wsList = wsState + (size_t)B * 9;
+    float* wsGx = reinterpret_cast<float*>(wsList + (size_t)B * 6 * h->walk_ws_M);
+    float* wsSens = wsGx + nx;
+    int* wsOk = reinterpret_cast<int*>(wsSens + (size_t)B * CMPC_SENS);
+    if (h->tick_ev) HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));   // (the gate writes workspace an earlier call on another stream may still read)
+    CmpcGateArgs a{};
+    a.B = B; a.M = M; a.N = N; a.nx = h->L.nx; a.np = h->L.np;
+    a.end_tick = dEndTick;
+    a.t_state = wsState; a.t_list = wsList; a.t_sens = wsSens;
+    a.carry_state = g->dCarryState; a.carry_list = g->dCarryList;
+    a.ok_out = wsOk; a.gx_out = g->dGradX ? wsGx : nullptr;
+    int rc = CMPC_OK;
+    for (int i = ticks; i >= 0 && rc == CMPC_OK; --i) {
+        // the gate step between tick i (POST: i < ticks) and tick i - 1 (PRE: i > 0), fused into one launch
+        const size_t rq = (size_t)(row0 + i), rp = (size_t)(row0 + i - 1);
+        a.do_post = i < ticks; a.tick_post = tick0 + i;
+        if (a.do_post) {
+            a.seed_state = g->dGradStates + rq * B * 9;
+            a.wrench_row = g->dGradWrench ? g->dGradWrench + rq * B * 6 * N : nullptr;
+            a.gp_row = g->dGradP ? g->dGradP + rq * np : nullptr;
+            a.status_row = g->dStatus + rq * B;
+        }
+        a.do_pre = i > 0; a.tick_pre = tick0 + i - 1; a.first = i == ticks;
+        if (a.do_pre) {
+            a.ok_row = tape->dOk + rp * B;
+            a.gx_row = g->dGradX ? g->dGradX + rp * nx : nullptr;
+        }
+        const int lrc = cmpc_launch_walk_vjp_gate(&a, st);
+        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (i == 0) break;
+        const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
+        cmpc_tick_tape tt{};
+        tt.dX = tape->dX + rp * nx; tt.dP = tape->dP + rp * np; tt.dLamG = tape->dLamG + rp * ng;
+        tt.dState = tape->dStates + rp * B * 9; tt.dInfo = tape->dInfo + rp * B * CMPC_INFO;
+        tt.dOk = wsOk; tt.dLand = tape->dLand + rp * B * 2;
+        tt.dPlanT = tape->dPlanT + rp * nt; tt.dPlanN = tape->dPlanN + rp * B * 2;
+        tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
+        tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
+        tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
+        rc = tick_vjp(h, false, M, (double)(tick0 + i - 1) * h->cfg.sampling_time, &tt, g->dCarryState, g->dCarryList, a.gx_out, wsState, wsList,
+                      g->dGradWrench ? g->dGradWrench + rp * B * 6 * N : nullptr, g->dGradPlan, g->dGradModel, g->dGradP ? g->dGradP + rp * np : nullptr, wsSens,
+                      nullptr, nullptr, nullptr, nullptr, stream);
+    }
+    if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
+    return rc;
 }
 
 // ---- one tick FORWARDS in k directions (include/cmpc.h): list JVP (merge + sample) -> the p direction assembled (cmpc_tick_jvp_assemble_kernel) ->

@@ -263,3 +263,74 @@ __host__ __device__ inline float cmpc_cold_start_entry(int N, int e, const float
     if (q < 3 * (N + 1) + 3 * N) return 0.f;          // the foot's velocity block
     return (q - 3 * (N + 1)) % 3 == 2 ? g8 : 0.f;     // corner forces [j][k][3]: 3 (N + 1) and 3 N are multiples of three
 }
+
+// ---- the device tape of a walk (include/cmpc.h, cmpc_walk_tape): one row from what a tick left.  Bit copies only; one argument block for the kernel.
+// Part 1 (before a tick that runs in place): state_in -> states[row].  Part 2 (behind the tick): everything else, state_out -> states[row + 1].
+struct CmpcTapeArgs {
+    int B, M, nx, np, row, parts;
+    const float* X; const float* P; const float* info; const int* ok; const int* land; const float* state_in; const float* state_out;
+    const double* plan_t; const int* plan_n; const double* list_t; const int* list_n;
+    float* t_X; float* t_P; float* t_info; float* t_states; int* t_ok; int* t_land; double* t_plan_t; double* t_list_t; int* t_plan_n; int* t_list_n;
+};
+
+// ---- the reverse walk's rule for ended problems (include/cmpc.h, cmpc_rollout_walk_vjp_device).  One statement for the host form and the
+// kernel (contraction off: the one sum is a plain double add).  A gate step sits between two reverse ticks: its POST part finishes tick `tick_post`
+// (row_post) from what cmpc_rollout_tick_vjp_device left, its PRE part prepares tick `tick_pre` (row_pre).  Either part may be absent (do_post / do_pre).
+// A problem b has ended at tick t when e = end_tick[b] >= 0 and t >= e (end_tick null: nobody has).  Ended: everything is SELECTED to zero -- never
+// multiplied, so that stale or non-finite data of an ended problem cannot reach an output.
+struct CmpcGateArgs {
+    int B, M, N, nx, np;
+    const int* end_tick;
+    int do_post, tick_post;
+    const double* seed_state;     // [B][9]: G of row_post
+    const double* t_state;        // [B][9]: the tick's dGradState
+    const double* t_list;         // [B][2][M][3]: the tick's dGradPrevList
+    const float* t_sens;          // [B][CMPC_SENS]: the tick's dTickSens
+    double* carry_state; double* carry_list;          // out (POST) / sanitised in place (PRE with `first`)
+    float* wrench_row; float* gp_row; int* status_row; // rows of row_post; wrench_row / gp_row may be null
+    int do_pre, tick_pre, first;  // first: the PRE part of the call's first gate step also selects zero in the caller's carries
+    const int* ok_row;            // [B] tape row of row_pre
+    const float* gx_row;          // [B][nx] seeds of row_pre, or null
+    int* ok_out; float* gx_out;   // the gated copies the tick VJP reads (gx_out null with gx_row null)
+};
+__host__ __device__ inline bool cmpc_gate_ended(const int* end_tick, int b, int tick)
+{
+    const int e = end_tick ? end_tick[b] : -1;
+    return e >= 0 && tick >= e;
+}
+// the small arrays of problem b
+__host__ __device__ inline void cmpc_walk_gate_problem(const CmpcGateArgs& a, int b)
+{
+#pragma clang fp contract(off)
+    const size_t nl = (size_t)6 * a.M;
+    if (a.do_post) {
+        const int e = a.end_tick ? a.end_tick[b] : -1;
+        const bool ended = e >= 0 && a.tick_post >= e;
+        for (int i = 0; i < 9; ++i) {
+            const size_t o = 9 * (size_t)b + i;
+            // c_i = [i < e] J_i^T c_{i+1} + [i <= e] G_i: the ending tick keeps its seed (s_e exists), later rows carry nothing
+            a.carry_state[o] = !ended ? a.t_state[o] + a.seed_state[o] : a.tick_post == e ? a.seed_state[o] : 0.0;
+        }
+        for (size_t i = 0; i < nl; ++i) a.carry_list[nl * b + i] = ended ? 0.0 : a.t_list[nl * b + i];
+        a.status_row[b] = ended ? 6 : (int)a.t_sens[(size_t)b * CMPC_SENS];
+    }
+    if (a.do_pre) {
+        const bool ended = cmpc_gate_ended(a.end_tick, b, a.tick_pre);
+        a.ok_out[b] = ended ? 0 : (a.ok_row ? a.ok_row[b] : 1);
+        if (a.first && ended) {
+            for (int i = 0; i < 9; ++i) a.carry_state[9 * (size_t)b + i] = 0.0;
+            for (size_t i = 0; i < nl; ++i) a.carry_list[nl * b + i] = 0.0;
+        }
+    }
+}
+// entry idx of the wide rows: [B][nx] (the gated dGradX copy), [B][N][6] (the wrench row) and [B][np] (the dGradP row); idx runs to B max(nx, np)
+__host__ __device__ inline void cmpc_walk_gate_wide(const CmpcGateArgs& a, size_t idx)
+{
+    if (a.do_pre && a.gx_out && idx < (size_t)a.B * a.nx)
+        a.gx_out[idx] = cmpc_gate_ended(a.end_tick, (int)(idx / a.nx), a.tick_pre) ? 0.f : a.gx_row[idx];
+    if (a.do_post) {
+        const size_t nw = (size_t)6 * a.N;
+        if (a.wrench_row && idx < (size_t)a.B * nw && cmpc_gate_ended(a.end_tick, (int)(idx / nw), a.tick_post)) a.wrench_row[idx] = 0.f;
+        if (a.gp_row && idx < (size_t)a.B * a.np && cmpc_gate_ended(a.end_tick, (int)(idx / a.np), a.tick_post)) a.gp_row[idx] = 0.f;
+    }
+}

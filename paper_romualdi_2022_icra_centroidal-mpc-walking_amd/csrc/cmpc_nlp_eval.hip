@@ -1634,7 +1634,71 @@ __global__ __launch_bounds__(256) void cmpc_cold_start_kernel(int N, float g8, c
     for (int e = threadIdx.x; e < L.nx(); e += 256) x[e] = cmpc_cold_start_entry(N, e, p, g8);
 }
 
+// ---- the device tape (cmpc_rollout_tape_device) and the gate of the reverse walk (cmpc_rollout_walk_vjp_device) ----
+// tape: bit copies, grid-stride, one array after the other (every thread walks every array: the arrays are rows of one batch, coalesced).  No barrier.
+template <typename T>
+__device__ inline void tape_copy(T* __restrict__ dst, const T* __restrict__ src, size_t n, size_t tid, size_t stride)
+{
+    for (size_t e = tid; e < n; e += stride) dst[e] = src[e];
+}
+__global__ __launch_bounds__(256) void cmpc_rollout_tape_kernel(CmpcTapeArgs a)
+{
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const size_t B = (size_t)a.B, r = (size_t)a.row;
+    if (a.parts & 1) tape_copy(a.t_states + r * B * 9, a.state_in, B * 9, tid, stride);
+    if (!(a.parts & 2)) return;   // (uniform)
+    tape_copy(a.t_X + r * B * a.nx, a.X, B * a.nx, tid, stride);
+    tape_copy(a.t_P + r * B * a.np, a.P, B * a.np, tid, stride);
+    tape_copy(a.t_info + r * B * CMPC_INFO_N, a.info, B * CMPC_INFO_N, tid, stride);
+    tape_copy(a.t_states + (r + 1) * B * 9, a.state_out, B * 9, tid, stride);
+    tape_copy(a.t_land + r * B * 2, a.land, B * 2, tid, stride);
+    if (a.ok) tape_copy(a.t_ok + r * B, a.ok, B, tid, stride);
+    else for (size_t e = tid; e < B; e += stride) a.t_ok[r * B + e] = 1;   // (a first tick without force_sample_time leaves dOk alone: every merge good)
+    const size_t nt = B * 4 * a.M;
+    if (a.plan_t) tape_copy(a.t_plan_t + r * nt, a.plan_t, nt, tid, stride);
+    if (a.plan_n) tape_copy(a.t_plan_n + r * B * 2, a.plan_n, B * 2, tid, stride);
+    tape_copy(a.t_list_t + r * nt, a.list_t, nt, tid, stride);
+    tape_copy(a.t_list_n + r * B * 2, a.list_n, B * 2, tid, stride);
+}
+
+// gate: one thread per problem for the small arrays (cmpc_walk_gate_problem; lanes past B do nothing), then every thread strides over the wide rows
+// (cmpc_walk_gate_wide).  The two parts touch disjoint arrays: no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_walk_vjp_gate_kernel(CmpcGateArgs a, size_t wide)
+{
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    if (tid < (size_t)a.B) cmpc_walk_gate_problem(a, (int)tid);
+    for (size_t e = tid; e < wide; e += stride) cmpc_walk_gate_wide(a, e);
+}
+
 }  // namespace
+
+static unsigned stride_blocks(size_t least_threads, size_t work)
+{
+    size_t nb = (work + 255) / 256;
+    if (nb > 2048) nb = 2048;
+    const size_t lb = (least_threads + 255) / 256;
+    return (unsigned)(nb > lb ? nb : lb);
+}
+
+extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream)
+{
+    const size_t work = (a->parts & 2) ? (size_t)a->B * (a->nx > a->np ? a->nx : a->np) : (size_t)a->B * 9;
+    hipLaunchKernelGGL(cmpc_rollout_tape_kernel, dim3(stride_blocks(1, work)), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a)
+{
+    const int w = a->nx > a->np ? a->nx : a->np;   // (6 N < n_p)
+    return (size_t)a->B * w;
+}
+
+extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream)
+{
+    const size_t wide = cmpc_walk_gate_wide_entries(a);
+    hipLaunchKernelGGL(cmpc_walk_vjp_gate_kernel, dim3(stride_blocks((size_t)a->B, wide)), dim3(256), 0, stream, *a, wide);
+    return (int)hipGetLastError();
+}
 
 extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream)
 {

@@ -7,6 +7,8 @@ first-knot forces until the next tick (WholeBodyQPBlock.cpp:1083-1150) -- as sev
 C ABI (include/cmpc.h); torch only owns the buffers.  SURVEY 8f-1 .. 8f-4 chained."""
 from __future__ import annotations
 
+import inspect
+
 import numpy as np
 
 from .config import GRAVITY
@@ -119,7 +121,21 @@ class WalkingRollout:
         com[ticks, B, 3], zmp[ticks, B, 2], land[ticks, B, 2], landing_offset[ticks, B, 2, 3] (float64), iterations[ticks, B], code[ticks, B]; the outcome
         end_tick[B] (-1: walked to the end), end_code[B], iterations_sum[B], iterations_max[B], final_state[B, 9], box_slack_min[B]; stats[ticks, 6];
         lists (t, pose, n) of the last tick; X, P, info of the last tick; state[B, 9], the batch's state buffer after the last tick (ended problems
-        included, unlike final_state)."""
+        included, unlike final_state).  The same walk with a device tape for backward_device(): walk_device_taped()."""
+        return self._walk_on_launch_stream(False, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
+
+    def walk_device_taped(self, ticks, com0, dcom0, h0, **kwargs):
+        """walk_device(ticks, com0, dcom0, h0, **kwargs) through cmpc_rollout_walk_taped_device: every tick also writes its row of a device tape -- what
+        backward_device() needs; about 12 KB per problem and tick at N = 20 -- and the dict gains "tape": the stacked tensors X, P, lam_g, info
+        [ticks, B, ..], states[ticks + 1, B, 9] (row i the state tick i started from), ok, land, plan_t, list_t, plan_n, list_n, and dt, substeps,
+        force_sample_time, push_ticks, segments (the first tick of each call).  The multiplier output is turned on first, as run(tape=True) does (x and info
+        are bit-identical with it on): every other returned array is bit-identical to walk_device's.  Still no host read; works with replan and skip_ended
+        (an ended problem's later rows then hold its ending tick's data).  (A method of its own and not an argument of walk_device: that signature is pinned.)"""
+        args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
+        args.apply_defaults()
+        return self._walk_on_launch_stream(True, *args.args, **args.kwargs)
+
+    def _walk_on_launch_stream(self, tape, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended):
         torch = self.torch
         assert self.retry != "launch", "walk_device needs retry='kernel' or None"
         ls = self.solver.launch_stream
@@ -127,11 +143,11 @@ class WalkingRollout:
         ls.wait_stream(cur)
         try:
             with torch.cuda.stream(ls):
-                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
+                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, tape)
         finally:
             cur.wait_stream(ls)
 
-    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False):
+    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False, tape=False):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         # (a numpy input is uploaded without the host waiting for the copy; a CUDA tensor is used as it is)
@@ -159,6 +175,10 @@ class WalkingRollout:
         plan_h = torch.zeros_like(plan_com)
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         s.outcome_init_device(state, rec)
+        tp = None
+        if tape:    # (as run(tape=True): the multiplier output on before anything is queued)
+            s.set_multiplier_output(True)
+            tp = s.walk_tape(ticks, self.M, step=dt / self.substeps, substeps=self.substeps, force_sample_time=self.force_sample_time, device=dev)
         replan = dict(replan or {})
         plan = replan.get(0, self.plan)
         sets = [tuple(a.clone() for a in plan), tuple(torch.zeros_like(a) for a in plan)]
@@ -173,11 +193,14 @@ class WalkingRollout:
                 wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
                 cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
                                             wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=(plan_com, plan_h, dt, 0.0, 1.0, 0.7),
-                                            force_sample_time=self.force_sample_time)
+                                            force_sample_time=self.force_sample_time, tape=tp)
         finally:
             if skip_ended:
                 s.set_ended_device(None)
         del rec["_c"]
+        if tp is not None:
+            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, segments=starts)
+            rec["tape"] = tp
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
         return rec
 
@@ -431,6 +454,42 @@ class WalkingRollout:
         cur.wait_stream(ls)
         return out
 
+    def backward_device(self, w, grad_states, grad_X=None):
+        """The device walk in reverse (cmpc_rollout_walk_vjp_device): ONE call per replan segment, last segment first, no host read and no synchronisation.
+        w = walk_device_taped(...); grad_states[ticks + 1, B, 9] and grad_X[ticks, B, n_x] (or None) as in backward(), CUDA tensors or numpy.
+        -> the keys of backward() -- state0, list0, wrench, push, models, plan, status -- and end_tick (w's).  A problem that ended at tick e
+        (w["end_tick"]) contributes the loss over its states 0 .. e and its solutions 0 .. e - 1 (include/cmpc.h: the seeds of its later rows are not read,
+        not even when they are not finite); its rows e .. of wrench are zero and of status 6.  Where nothing ended every entry is bit-equal to
+        run(tape=True) + backward()."""
+        torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
+        tape = w["tape"]
+        T, M, s = tape["rows"], tape["max_contacts"], self.solver
+        as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, dt).contiguous()
+        gS = as_t(grad_states, torch.float64)
+        assert tuple(gS.shape) == (T + 1, B, 9)
+        gX = None
+        if grad_X is not None:
+            gX = as_t(grad_X, torch.float32)
+            assert tuple(gX.shape) == (T, B, L.nx)
+        z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=self.dev)
+        out = dict(push=z((B, 3)), wrench=z((T, B, N, 6), torch.float32), models=z((B, 34)), plan=z((B, 2, M, 3)), status=z((T, B), torch.int32),
+                   end_tick=w["end_tick"])
+        starts = list(tape["segments"])
+        ls = s.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            g, gl = gS[T].clone(), z((B, 2, M, 3))    # (the gate in front of the last tick selects zero where the problem has ended)
+            for j in reversed(range(len(starts))):
+                t0, t1 = starts[j], starts[j + 1] if j + 1 < len(starts) else T
+                s.rollout_walk_vjp_device(t0, t1 - t0, tape, t0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, wrench=out["wrench"],
+                                          dGradPlan=out["plan"], dGradModel=out["models"])
+            for i in reversed(range(min(T, tape["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
+                out["push"] += out["wrench"][i][:, :max(tape["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
+            out["state0"], out["list0"] = g, gl
+        cur.wait_stream(ls)
+        return out
+
     def forward_sensitivity(self, tape, dir_state0=None, dir_list0=None, dir_list_rot0=None, dir_plan=None, dir_plan_rot=None, dir_push=None, dir_models=None,
                             dir_wrench=None, solutions=False):
         """The taped roll-out in forward mode (cmpc_rollout_tick_jvp_device, one call per tick, first tick first): how the whole trajectory moves along k
@@ -505,7 +564,7 @@ def yaw_plan_poses(pose, plan_yaw):
     return out
 
 
-def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None):
+def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None, device_walk=False, replan=None):
     """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
     state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
     (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
@@ -514,8 +573,20 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     plan_yaw: None, or a [B, 2, M] float64 CUDA tensor: entry (b, c, m) yaws the planner's contact m of foot c about its own z axis before the run
     (yaw_plan_poses, on a copy of rollout.plan's poses made for this call; rollout.plan is left as it was).  backward then runs with rot=True and
     plan_yaw.grad = the e_z component of plan_rot + list_rot0: the first tick's list is the planner's list entry for entry, and every later tick reads the
-    planner's entries through the merge; rotations about one axis commute, so the body-frame tangent at the yawed quaternion is d psi e_z."""
+    planner's entries through the merge; rotations about one axis commute, so the body-frame tangent at the yawed quaternion is d psi e_z.
+    device_walk=True: forward is rollout.walk_device_taped (replan: its argument; only here) and backward is WalkingRollout.backward_device -- no
+    host read in either, and a problem may END (a failed merge, a solve that does not converge, a non-finite state) without taking the batch's gradient
+    with it: nothing asserts that every tick ran.  For a problem that ended at tick e the returned states hold final_state in rows > e (row e is
+    final_state already), and backward first folds the cotangents of those rows into row e, which is the derivative of the function as returned.
+    rollout.last_walk is the walk's dict (end_tick says who ended and when).  Not with plan_yaw (NotImplementedError), and no forward mode."""
     import torch
+
+    if device_walk:
+        if plan_yaw is not None:
+            raise NotImplementedError("rollout_differentiable(device_walk=True): the orientation chain on the device tape is not built yet")
+        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan)
+    if replan is not None:
+        raise NotImplementedError("rollout_differentiable: replan needs device_walk=True")
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -566,3 +637,37 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
             return r["states"][:, :, 0].to(torch.float32)
 
     return _Fn.apply(state0, push, models, plan_yaw)
+
+
+def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan):
+    """rollout_differentiable(device_walk=True)"""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, state0, push, models):
+            if models is not None:
+                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
+                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
+            s0 = state0.detach().to(rollout.dev, torch.float32)
+            w = rollout.walk_device_taped(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(rollout.dev, torch.float32),
+                                          push_ticks=push_ticks, replan=replan, trace=False)
+            rollout.last_walk = ctx.walk = w
+            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
+            e = w["end_tick"]
+            row = torch.arange(ticks + 1, device=rollout.dev)[:, None]
+            ctx.past = (e[None, :] >= 0) & (row > e[None, :])         # [ticks + 1, B]: rows behind a problem's end
+            ctx.last = row == e[None, :]                                # the row its final state sits in
+            return torch.where(ctx.past[..., None], w["final_state"][None], w["tape"]["states"])
+
+        @staticmethod
+        def backward(ctx, gStates):
+            g = gStates.to(rollout.dev, torch.float64)
+            folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
+            g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
+            r = rollout.backward_device(ctx.walk, g)
+            rollout.last_backward = r
+            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
+                    r["models"] if ctx.needs_input_grad[2] else None)
+
+    return _Fn.apply(state0, push, models)

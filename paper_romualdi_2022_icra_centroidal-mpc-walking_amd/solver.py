@@ -863,12 +863,66 @@ class BatchSolver:
         self._launch(dP.device, lambda st: self._lib.cmpc_cold_start_device(self._h, dP.data_ptr(), dX0.data_ptr(), st))
         return dX0
 
+    def walk_tape(self, rows, max_contacts, step=0.01, substeps=6, force_sample_time=False, first_row_is_first_tick=True, device=None):
+        """The arrays of a cmpc_walk_tape (include/cmpc.h) as a dict of CUDA tensors stacked over `rows` ticks -- X, P, lam_g, info, states[rows + 1], ok,
+        land, plan_t, list_t, plan_n, list_n -- plus the host scalars (step, substeps, force_sample_time) and "_c", the C struct that points at them."""
+        import torch
+        B, L, M = self.batch, self.layout, int(max_contacts)
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        t = dict(X=z((rows, B, L.nx), f32), P=z((rows, B, L.np), f32), lam_g=z((rows, B, L.ng), f32), info=z((rows, B, _capi.INFO), f32),
+                 states=z((rows + 1, B, 9), f32), ok=z((rows, B), i32), land=z((rows, B, 2), i32), plan_t=z((rows, B, 2, M, 2), f64),
+                 list_t=z((rows, B, 2, M, 2), f64), plan_n=z((rows, B, 2), i32), list_n=z((rows, B, 2), i32))
+        t["_c"] = _capi.CmpcWalkTape(int(rows), *(t[k].data_ptr() for k in ("X", "P", "lam_g", "info", "states", "ok", "land", "plan_t", "list_t", "plan_n",
+                                                                            "list_n")), float(step), int(substeps), 1 if force_sample_time else 0,
+                                     1 if first_row_is_first_tick else 0)
+        t.update(rows=int(rows), max_contacts=M, step=float(step), substeps=int(substeps), force_sample_time=bool(force_sample_time))
+        return t
+
+    def rollout_tape_device(self, row, tape, dX, dP, dInfo, ok, land, dStateIn, dStateOut, plan, lists, parts=3):
+        """cmpc_rollout_tape_device: row `row` of tape (walk_tape) from what a tick left.  parts 1: dStateIn -> states[row], BEFORE a tick that runs in place;
+        2: everything else behind the tick (the multiplier output must be on); 3: both, behind a tick that did not run in place.  ok may be None (a first
+        tick without force_sample_time), plan = (t, pose, n) or None on a first tick; lists = (t, pose, n) of the tick."""
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        dev = (dStateIn if dStateIn is not None else dX).device
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_tape_device(
+            self._h, int(tape["max_contacts"]), int(row), int(parts), ptr(dX), ptr(dP), ptr(dInfo), ptr(ok), ptr(land), ptr(dStateIn), ptr(dStateOut),
+            ptr(plan[0]) if plan is not None else None, ptr(plan[2]) if plan is not None else None, ptr(lists[0]) if lists is not None else None,
+            ptr(lists[2]) if lists is not None else None, tape["_c"], st))
+
+    def rollout_walk_vjp_device(self, tick0, ticks, tape, row0, end_tick, grad_states, carry_state, carry_list, status, grad_X=None, wrench=None, grad_p=None,
+                                dGradPlan=None, dGradModel=None):
+        """cmpc_rollout_walk_vjp_device: rows row0 .. row0 + ticks - 1 of tape (walk_tape) in reverse in ONE call.  grad_states[rows + 1, B, 9] float64 and
+        grad_X[rows, B, n_x] float32 (or None) are the seeds; carry_state[B, 9] / carry_list[B, 2, M, 3] float64 go in as the carry entering the last row
+        and come back as the carry leaving the first; wrench[rows, B, N, 6] / grad_p[rows, B, n_p] float32 (or None) and status[rows, B] int32 are written
+        row by row; dGradPlan[B, 2, M, 3] / dGradModel[B, 34] float64 are added to in place.  end_tick: int32 [B] (a walk record's) or None."""
+        import torch
+        L, B, N, M, R = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"]), int(tape["rows"])
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        g = _capi.CmpcWalkGrads(self._opt(grad_states, f64, (R + 1, B, 9), "grad_states"), self._opt(grad_X, f32, (R, B, L.nx), "grad_X"),
+                                self._opt(carry_state, f64, (B, 9), "carry_state"), self._opt(carry_list, f64, (B, 2, M, 3), "carry_list"),
+                                self._opt(wrench, f32, (R, B, N, 6), "wrench"), self._opt(grad_p, f32, (R, B, L.np), "grad_p"),
+                                self._opt(dGradPlan, f64, (B, 2, M, 3), "dGradPlan"), self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"),
+                                self._opt(status, i32, (R, B), "status"))
+        e = self._opt(end_tick, i32, (B,), "end_tick")
+        self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, st))
+
+    def rollout_walk_vjp_gate_device(self, gate, device=None):
+        """cmpc_rollout_walk_vjp_gate_device: one gate step of the reverse walk as one launch; gate: a _capi.CmpcWalkGate of device pointers."""
+        import torch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_vjp_gate_device(self._h, C.byref(gate), st))
+
     def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
-                            wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+                            wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
+                            tape=None, tape_row0=None):
         """cmpc_rollout_walk_device: `ticks` ticks from tick number tick0 queued in one call, each followed by its record (rec: walk_record, or None), in
         place on dState.  lists / lists_b: the two sets of list buffers (t, pose, n), lists_in the one that holds the previous tick's lists (the first
         tick's own with cold_first); returns the set that holds the last tick's.  wrench_ticks[T, B, N, 6]: tick i < T of the call writes row i.
-        planner = (dComIn, dHIn, in_dt, t_first, robot_mass, com_height), t_first the time of the trajectories' first knot."""
+        planner = (dComIn, dHIn, in_dt, t_first, robot_mass, com_height), t_first the time of the trajectories' first knot.
+        tape (walk_tape): cmpc_rollout_walk_taped_device -- tick i of the call also writes row tape_row0 + i (default: row0 + i) of the tape; the
+        multiplier output must be on."""
         io = _capi.CmpcWalkIO()
         io.tick = self._tick_io(plan, None, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
                                 force_sample_time)
@@ -878,6 +932,11 @@ class BatchSolver:
             assert wrench_ticks.is_contiguous() and tuple(wrench_ticks.shape[1:]) == (self.batch, self.cfg.N, 6)
             io.dWrenchTicks, io.wrench_ticks = wrench_ticks.data_ptr(), int(wrench_ticks.shape[0])
         out = C.c_int(-1)
+        if tape is not None:
+            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_taped_device(
+                self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
+                int(lists_in), C.byref(out), tape["_c"], int(row0 if tape_row0 is None else tape_row0), st))
+            return out.value
         self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_device(
             self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
             int(lists_in), C.byref(out), st))
