@@ -869,8 +869,8 @@ int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, co
  * the forward ticks'; first_row_is_first_tick != 0: row 0 is a first tick (no merge, no previous list) -- otherwise row 0 cannot be reversed.
  * Size: 4 (n_x + n_p + n_g) + 64 M + 96 bytes per problem and tick (the three wide rows, then 2 x 32 M of times, info 32, state 36, ok 4, land and the two
  * counts 8 each), about 12 KB at N = 20 (x, p and lam_g are a thousand floats each).
- * Out of scope here: the orientation (_rot) chain and the forward-mode (_jvp) walk on this tape -- both can follow on the same layout.  Contact times and
- * Gamma stay undifferentiated, as everywhere. */
+ * Out of scope here: the orientation (_rot) chain of the REVERSE walk on this tape -- it can follow on the same layout (the forward-mode walk below
+ * carries the orientations already).  Contact times and Gamma stay undifferentiated, as everywhere. */
 typedef struct cmpc_walk_tape {
     int rows;
     float* dX; float* dP; float* dLamG; float* dInfo; float* dStates;
@@ -945,6 +945,71 @@ int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g);
 /* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what cmpc_rollout_walk_vjp_device queues
  * between its ticks, for a caller who reverses a walk tick by tick.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
 int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream);
+
+/* ---- the device walk FORWARDS on the same tape, k direction columns, per-problem endings kept (derivation and the rule: DESIGN.md 7f, "Forwards") ----
+ * The forward walk: `ticks` calls of cmpc_rollout_tick_jvp_device (called, not copied: its chunks of eight columns, its workspace, its internal-force rule,
+ * its statuses and its zero rule for flagged problems hold), first row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of
+ * cmpc_walk_jvp_gate_kernel).  Tick number tick0 + i is row row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time; each
+ * row's cmpc_tick_tape is built as the reverse walk builds it (the previous lists are row - 1's, NULL on row 0 of a tape whose first row is a first tick).
+ * The fields of cmpc_walk_dirs, device pointers all, the column axis right behind the batch axis:
+ *     dDirStates[rows + 1][B][k][9] double    row row0 is read (t of the first tick of the call), rows row0 + 1 .. row0 + ticks are written
+ *     dCarryList, dCarryListRot[B][k][2][M][3] double   in: the list directions entering the first row of the call; out: those leaving its last row,
+ *                                             whatever the parity of `ticks` (the tick needs in != out: the walk alternates with a workspace buffer).
+ *                                             dCarryListRot and dDirPlanRot both NULL: no rotation chain (the tick's NULL rule; results are then bit for
+ *                                             bit those without it); dDirPlanRot without dCarryListRot is CMPC_ERR_ARG
+ *     dDirPlan, dDirPlanRot[B][k][2][M][3] double or NULL   read by every merge tick of the call (a replanned walk passes other ones per segment)
+ *     dDirWrench[rows][B][k][N][6] float or NULL, dDirModel[B][k][34] double or NULL, dDirP[rows][B][k][n_p] float or NULL (the tick's extra p direction)
+ *     dDirX[rows][B][k][n_x] float or NULL    out: the solutions' directions
+ *     dStatus[rows][B] int                    out: word 0 of the tick's dTickSens, or 6: the problem had ended
+ *     dRemoved[rows][B] float or NULL         out: word 6 of the tick's dTickSens, 0 for an ended problem
+ * Segments compose through dDirStates and the two carries: rows 8 .. 15 behind rows 0 .. 7 equal one call over 0 .. 15 to the bit.
+ * Ended problems (dEndTick[B] as in the reverse walk; NULL: none).  Let e = dEndTick[b], -1 read as never; t_i is the direction of the state tick i starts
+ * from, l_i that of the lists (positions and orientations).  The rule, the exact transpose of c_i = [i < e] J_i^T c_{i+1} + [i <= e] G_i:
+ *     t_{i+1} = [i < e] (the tick's dDirStateOut), l_{i+1} = [i < e] (the tick's dDirList / dDirListRot);
+ *     row i of dDirX is the tick's when i < e, zero otherwise; dStatus[i] is word 0 of dTickSens when i < e and 6 when i >= e; dRemoved[i] is word 6
+ *     when i < e and 0 when i >= e.
+ * The directions t_0 .. t_e exist; everything behind the end is zero.  For a tick i >= e the gate feeds the tick dOk = 0 (a gated copy in handle
+ * workspace); the tick then flags the problem -- its status 5 -- and writes zeros, and behind the tick the gate still SELECTS zero for that problem in
+ * every array the tick wrote for the row: it never multiplies, so stale or non-finite data of an ended problem -- in its tape rows, in its rows of the
+ * caller's direction arrays, in what the tick left -- cannot leak.  The first gate step of a call also selects zero in dDirStates[row0] and in the
+ * carries of a problem with e < tick0.  A problem that has not ended but whose tick is flagged (status 1 .. 5) passes zeros on, as the tick JVP does:
+ * the transpose of the reverse walk there.  The rule is one __host__ __device__ function pair (cmpc_walk_jvp_gate_column / cmpc_walk_jvp_gate_wide); the
+ * gate has no LDS, no barrier and no atomics; lanes past B k do nothing.
+ * No host wait beyond the workspace allocation: per-handle HBM, 96 M bytes per problem and column (the second buffers of the two list directions) plus
+ * 36 bytes per problem (dTickSens and the gated dOk), allocated on first use, grown when a larger k or max_contacts arrives (that call waits for the
+ * device), freed with the handle; calls on one handle run one after the other whatever their streams (the tick VJP's event).
+ * CMPC_ERR_ARG: a NULL handle, tape or d, k < 1, rows outside the tape, row 0 of a tape whose first row is not a first tick, dDirStates, dCarryList or
+ * dStatus missing. */
+typedef struct cmpc_walk_dirs {
+    double* dDirStates;
+    double* dCarryList; double* dCarryListRot;
+    const double* dDirPlan; const double* dDirPlanRot;
+    const float* dDirWrench; const double* dDirModel; const float* dDirP;
+    float* dDirX; int* dStatus; float* dRemoved;
+} cmpc_walk_dirs;
+int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
+                                 const cmpc_walk_dirs* d, void* stream);
+/* One gate step of the forward walk on the host (host buffers; no handle, no GPU; bit-equal to the kernel).  The POST part finishes tick `tick_post` IN
+ * PLACE on what the tick JVP wrote -- state_out[B][k][9] (its dDirStateOut), list_out / list_rot_out[B][k][2][M][3] (list_rot_out may be NULL),
+ * x_row[B][k][n_x] (may be NULL): zero is selected where the problem has ended -- and writes status_row[B] and removed_row[B] (may be NULL) from
+ * tick_sens[B][CMPC_SENS].  The PRE part prepares tick `tick_pre`: ok_out[B] from ok_row (NULL: ones); with first != 0 (the first step of a call) zero is
+ * selected in first_state[B][k][9], first_list and first_list_rot[B][k][2][M][3] (each may be NULL) of a problem that ended before tick_pre.  A step
+ * between two forward ticks has both parts (tick_pre = tick_post + 1); the first step of a call has PRE only, the last POST only.  The two parts touch
+ * disjoint arrays. */
+typedef struct cmpc_walk_jvp_gate {
+    int batch, max_contacts, horizon, k;
+    const int* end_tick;
+    int do_post, tick_post;
+    const float* tick_sens;
+    double* state_out; double* list_out; double* list_rot_out; float* x_row; int* status_row; float* removed_row;
+    int do_pre, tick_pre, first;
+    const int* ok_row; int* ok_out;
+    double* first_state; double* first_list; double* first_list_rot;
+} cmpc_walk_jvp_gate;
+int cmpc_rollout_walk_jvp_gate(const cmpc_walk_jvp_gate* g);
+/* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what the forward walk queues between its
+ * ticks.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
+int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g, void* stream);
 
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */

@@ -92,6 +92,21 @@ class CmpcWalkGate(C.Structure):
         ("do_pre", C.c_int), ("tick_pre", C.c_int), ("first", C.c_int)] + [(k, C.c_void_p) for k in ("ok_row", "grad_x_row", "ok_out", "grad_x_out")]
 
 
+class CmpcWalkDirs(C.Structure):
+    """mirror of cmpc_walk_dirs (include/cmpc.h): the direction columns, carries and outputs of cmpc_rollout_walk_jvp_device"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "dDirStates", "dCarryList", "dCarryListRot", "dDirPlan", "dDirPlanRot", "dDirWrench", "dDirModel", "dDirP", "dDirX", "dStatus", "dRemoved")]
+
+
+class CmpcWalkJvpGate(C.Structure):
+    """mirror of cmpc_walk_jvp_gate (include/cmpc.h): one gate step of the forward walk, cmpc_rollout_walk_jvp_gate[_device]"""
+    _fields_ = [("batch", C.c_int), ("max_contacts", C.c_int), ("horizon", C.c_int), ("k", C.c_int), ("end_tick", C.c_void_p), ("do_post", C.c_int),
+                ("tick_post", C.c_int)] + [(k, C.c_void_p) for k in (
+                    "tick_sens", "state_out", "list_out", "list_rot_out", "x_row", "status_row", "removed_row")] + [
+        ("do_pre", C.c_int), ("tick_pre", C.c_int), ("first", C.c_int)] + [(k, C.c_void_p) for k in (
+            "ok_row", "ok_out", "first_state", "first_list", "first_list_rot")]
+
+
 class CmpcTickDirs(C.Structure):
     """mirror of cmpc_tick_dirs (include/cmpc.h): the k direction columns that go into cmpc_rollout_tick_jvp_device, each pointer NULL = zero"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -146,6 +161,7 @@ EXPORTS = [
     "cmpc_set_ended_device",
     "cmpc_rollout_tape_device", "cmpc_rollout_walk_taped_device", "cmpc_rollout_walk_vjp_device", "cmpc_rollout_walk_vjp_gate",
     "cmpc_rollout_walk_vjp_gate_device",
+    "cmpc_rollout_walk_jvp_device", "cmpc_rollout_walk_jvp_gate", "cmpc_rollout_walk_jvp_gate_device",
 ]
 
 _lib = None
@@ -270,6 +286,10 @@ def lib():
             L.cmpc_rollout_walk_vjp_device.argtypes = [vp, i, i, i, tp, i, vp, C.POINTER(CmpcWalkGrads), vp]
             L.cmpc_rollout_walk_vjp_gate.argtypes = [C.POINTER(CmpcWalkGate)]
             L.cmpc_rollout_walk_vjp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkGate), vp]
+        if hasattr(L, "cmpc_rollout_walk_jvp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_rollout_walk_jvp_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs), vp]
+            L.cmpc_rollout_walk_jvp_gate.argtypes = [C.POINTER(CmpcWalkJvpGate)]
+            L.cmpc_rollout_walk_jvp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkJvpGate), vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -61,6 +61,8 @@ extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, f
 extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
 extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a);
+extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t stream);
+extern "C" size_t cmpc_walk_jvp_gate_wide_entries(const CmpcJvpGateArgs* a);
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                       hipStream_t stream);
@@ -125,6 +127,9 @@ struct cmpc_handle_s {
     char* dWalkWs = nullptr;     // workspace of cmpc_rollout_walk_vjp_device for lists of walk_ws_M contacts (allocated on first use, grown when a larger
     int walk_ws_M = 0;           // max_contacts arrives): the tick's dGradState [B][9] | its dGradPrevList [B][2][M][3] (double) | the gated dGradX row [B][n_x] |
                                  // the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
+    char* dWalkJvpWs = nullptr;  // workspace of cmpc_rollout_walk_jvp_device for walk_jvp_cols columns and lists of walk_jvp_M contacts (allocated on first use,
+    int walk_jvp_cols = 0;       // grown when a larger k or max_contacts arrives): the second buffers of the list directions, positions and orientations
+    int walk_jvp_M = 0;          // [B][k][2][M][3] each (double) | the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
     size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
     int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
     float hBox[12] = {0};
@@ -327,7 +332,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG); hipFree(h->dSensWs);
     if (h->sens_ev) hipEventDestroy(h->sens_ev);
-    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); hipFree(h->dWalkWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); hipFree(h->dWalkWs); hipFree(h->dWalkJvpWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1881,8 +1886,9 @@ int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int ph
     return CMPC_OK;
 }
 
-int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
-                                 const cmpc_tick_dirs_out* out, float* dTickSens, void* stream)
+// (shared by the public entry point and the forward walk, as tick_vjp is)
+static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in, const cmpc_tick_dirs_out* out,
+                    float* dTickSens, void* stream)
 {
     if (!h || !tape || max_contacts < 1 || k < 1 || !out || !out->dDirStateOut || !out->dDirList || !dTickSens)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: null argument");
@@ -1948,6 +1954,147 @@ int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, co
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
     HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return CMPC_OK;
+}
+
+int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
+                                 const cmpc_tick_dirs_out* out, float* dTickSens, void* stream)
+{
+    return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream);
+}
+
+// ---- the forward walk on the device tape (include/cmpc.h, cmpc_rollout_walk_jvp_device): gate, tick JVP, gate, ..., gate ----
+static CmpcJvpGateArgs jvp_gate_args_of(const cmpc_walk_jvp_gate* g, int nx)
+{
+    return CmpcJvpGateArgs{g->batch, g->max_contacts, g->k, nx, g->end_tick, g->do_post, g->tick_post, g->tick_sens, g->state_out, g->list_out,
+                           g->list_rot_out, g->x_row, g->status_row, g->removed_row, g->do_pre, g->tick_pre, g->first, g->ok_row, g->ok_out, g->first_state,
+                           g->first_list, g->first_list_rot};
+}
+
+static int jvp_gate_check(const cmpc_walk_jvp_gate* g)
+{
+    if (!g || g->batch < 1 || g->max_contacts < 1 || g->horizon < 1 || g->horizon > CMPC_NMAX || g->k < 1 || (!g->do_post && !g->do_pre))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: bad argument");
+    if (g->do_post && (!g->tick_sens || !g->state_out || !g->list_out || !g->status_row))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: the POST part needs the tick's dTickSens, state and list directions and the status row");
+    if (g->do_pre && !g->ok_out) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: the PRE part needs ok_out");
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_jvp_gate(const cmpc_walk_jvp_gate* g)
+{
+    const int rc = jvp_gate_check(g);
+    if (rc != CMPC_OK) return rc;
+    CmpcLayout L;
+    cmpc_layout_init(L, g->horizon);
+    const CmpcJvpGateArgs a = jvp_gate_args_of(g, L.nx);
+    for (size_t c = 0; c < (size_t)g->batch * g->k; ++c) cmpc_walk_jvp_gate_column(a, c);
+    const size_t wide = cmpc_walk_jvp_gate_wide_entries(&a);
+    for (size_t e = 0; e < wide; ++e) cmpc_walk_jvp_gate_wide(a, e);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate_device: null handle");
+    const int rc = jvp_gate_check(g);
+    if (rc != CMPC_OK) return rc;
+    if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate_device: batch and horizon must be the handle's");
+    HIPCHK(h, hipSetDevice(h->device));
+    const CmpcJvpGateArgs a = jvp_gate_args_of(g, h->L.nx);
+    const int lrc = cmpc_launch_walk_jvp_gate(&a, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("forward walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
+                                 const cmpc_walk_dirs* d, void* stream)
+{
+    if (!h || !d || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: null argument or incomplete tape");
+    if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows || k < 1)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: bad argument (k >= 1, and the rows must lie inside the tape)");
+    if (!d->dDirStates || !d->dCarryList || !d->dStatus)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: dDirStates, dCarryList and dStatus are needed");
+    if (d->dDirPlanRot && !d->dCarryListRot)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: the planner's orientation directions need dCarryListRot to carry them");
+    if (row0 == 0 && !tape->first_row_is_first_tick)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: row 0 is not a first tick and has no row before it to take the previous lists from");
+    HIPCHK(h, hipSetDevice(h->device));
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const int B = h->B, N = h->cfg.horizon, M = max_contacts;
+    const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nt = (size_t)B * 4 * M;
+    const size_t cols = (size_t)B * k, nl = cols * 6 * M;
+    if (!h->dWalkJvpWs || h->walk_jvp_cols < k || h->walk_jvp_M < M) {
+        const int kk = k > h->walk_jvp_cols ? k : h->walk_jvp_cols, mm = M > h->walk_jvp_M ? M : h->walk_jvp_M;
+        if (h->dWalkJvpWs) {   // (a larger k or max_contacts: launches that read the old workspace may still be queued)
+            HIPCHK(h, hipDeviceSynchronize());
+            hipFree(h->dWalkJvpWs);
+            h->dWalkJvpWs = nullptr; h->walk_jvp_cols = 0; h->walk_jvp_M = 0;
+        }
+        HIPCHK(h, hipMalloc(&h->dWalkJvpWs, sizeof(double) * 2 * (size_t)B * kk * 6 * mm + sizeof(float) * (size_t)B * CMPC_SENS + sizeof(int) * (size_t)B));
+        h->walk_jvp_cols = kk; h->walk_jvp_M = mm;
+    }
+    // (the two list buffers carved for this call's k and M; the per-problem words sit behind the full allocation)
+    double* wsList = reinterpret_cast<double*>(h->dWalkJvpWs);
+    double* wsListRot = wsList + nl;
+    float* wsSens = reinterpret_cast<float*>(wsList + 2 * (size_t)B * h->walk_jvp_cols * 6 * h->walk_jvp_M);
+    int* wsOk = reinterpret_cast<int*>(wsSens + (size_t)B * CMPC_SENS);
+    if (h->tick_ev) HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));   // (the gate writes workspace an earlier call on another stream may still read)
+    const bool rot = d->dCarryListRot || d->dDirPlanRot;
+    double* cur = d->dCarryList;  double* other = wsList;               // cur: the list directions entering the next tick; the tick writes `other`
+    double* curRot = rot ? d->dCarryListRot : nullptr;  double* otherRot = rot ? wsListRot : nullptr;
+    CmpcJvpGateArgs a{};
+    a.B = B; a.M = M; a.K = k; a.nx = h->L.nx;
+    a.end_tick = dEndTick;
+    a.t_sens = wsSens; a.ok_out = wsOk;
+    int rc = CMPC_OK;
+    for (int i = 0; i <= ticks && rc == CMPC_OK; ++i) {
+        // the gate step between tick i - 1 (POST: i > 0) and tick i (PRE: i < ticks), fused into one launch
+        const size_t rq = (size_t)(row0 + i - 1), rp = (size_t)(row0 + i);
+        a.do_post = i > 0; a.tick_post = tick0 + i - 1;
+        if (a.do_post) {
+            a.state_out = d->dDirStates + (rq + 1) * cols * 9;
+            a.list_out = cur; a.list_rot_out = curRot;     // (what tick i - 1 wrote: the buffers were swapped behind it)
+            a.x_row = d->dDirX ? d->dDirX + rq * (size_t)k * nx : nullptr;
+            a.status_row = d->dStatus + rq * B;
+            a.removed_row = d->dRemoved ? d->dRemoved + rq * B : nullptr;
+        }
+        a.do_pre = i < ticks; a.tick_pre = tick0 + i; a.first = i == 0;
+        a.ok_row = a.do_pre ? tape->dOk + rp * B : nullptr;
+        a.first_state = a.first ? d->dDirStates + rp * cols * 9 : nullptr;
+        a.first_list = a.first ? d->dCarryList : nullptr;
+        a.first_list_rot = a.first ? curRot : nullptr;
+        const int lrc = cmpc_launch_walk_jvp_gate(&a, st);
+        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("forward walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (i == ticks) break;
+        const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
+        cmpc_tick_tape tt{};
+        tt.dX = tape->dX + rp * nx; tt.dP = tape->dP + rp * np; tt.dLamG = tape->dLamG + rp * ng;
+        tt.dState = tape->dStates + rp * B * 9; tt.dInfo = tape->dInfo + rp * B * CMPC_INFO;
+        tt.dOk = wsOk; tt.dLand = tape->dLand + rp * B * 2;
+        tt.dPlanT = tape->dPlanT + rp * nt; tt.dPlanN = tape->dPlanN + rp * B * 2;
+        tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
+        tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
+        tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
+        cmpc_tick_dirs in{};
+        in.dDirState = d->dDirStates + rp * cols * 9;
+        in.dDirPrevList = cur; in.dDirPrevListRot = curRot;
+        in.dDirPlan = d->dDirPlan; in.dDirPlanRot = d->dDirPlanRot;
+        in.dDirWrench = d->dDirWrench ? d->dDirWrench + rp * cols * 6 * N : nullptr;
+        in.dDirModel = d->dDirModel;
+        in.dDirP = d->dDirP ? d->dDirP + rp * (size_t)k * np : nullptr;
+        cmpc_tick_dirs_out out{};
+        out.dDirStateOut = d->dDirStates + (rp + 1) * cols * 9;
+        out.dDirList = other; out.dDirListRot = otherRot;
+        out.dDirX = d->dDirX ? d->dDirX + rp * (size_t)k * nx : nullptr;
+        rc = tick_jvp(h, M, (double)(tick0 + i) * h->cfg.sampling_time, &tt, k, &in, &out, wsSens, stream);
+        std::swap(cur, other); std::swap(curRot, otherRot);
+    }
+    if (rc == CMPC_OK && cur != d->dCarryList) {     // (an odd number of ticks: the lists leaving the last row sit in the workspace)
+        HIPCHK(h, hipMemcpyAsync(d->dCarryList, cur, sizeof(double) * nl, hipMemcpyDeviceToDevice, st));
+        if (rot) HIPCHK(h, hipMemcpyAsync(d->dCarryListRot, curRot, sizeof(double) * nl, hipMemcpyDeviceToDevice, st));
+    }
+    if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
+    return rc;
 }
 
 // the handle's own contact blocks from contact lists (what the class facade's setContactPhaseList calls)

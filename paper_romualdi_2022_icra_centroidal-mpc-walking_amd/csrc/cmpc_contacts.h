@@ -334,3 +334,54 @@ __host__ __device__ inline void cmpc_walk_gate_wide(const CmpcGateArgs& a, size_
         if (a.gp_row && idx < (size_t)a.B * a.np && cmpc_gate_ended(a.end_tick, (int)(idx / a.np), a.tick_post)) a.gp_row[idx] = 0.f;
     }
 }
+
+// ---- the forward walk's rule for ended problems (include/cmpc.h, cmpc_rollout_walk_jvp_device; DESIGN.md 7f, "Forwards"): the transpose of the rule
+// above.  One statement for the host form and the kernel (contraction off, although nothing here is arithmetic: every line is a selection).  A gate step sits
+// between two forward ticks: its POST part finishes tick `tick_post` in place on what cmpc_rollout_tick_jvp_device wrote, its PRE part prepares tick
+// `tick_pre`.  t_{i+1} = [i < e] (the tick's state direction), the same for the lists and for the row of dx; status 6 and removed 0 for i >= e.  With
+// `first` the PRE part also selects zero in the directions that enter the call for a problem with e < tick_pre (t_e and l_e exist, later ones are zero).
+struct CmpcJvpGateArgs {
+    int B, M, K, nx;
+    const int* end_tick;
+    int do_post, tick_post;
+    const float* t_sens;                              // [B][CMPC_SENS]: the tick's dTickSens
+    double* state_out; double* list_out; double* list_rot_out;   // [B][K][9], [B][K][2][M][3] (list_rot_out may be null): what the tick wrote
+    float* x_row;                                     // [B][K][nx] or null
+    int* status_row; float* removed_row;              // [B]; removed_row may be null
+    int do_pre, tick_pre, first;
+    const int* ok_row; int* ok_out;                   // [B] tape row of tick_pre (null: ones) and the gated copy the tick JVP reads
+    double* first_state; double* first_list; double* first_list_rot;   // with `first`: what enters the call (each may be null)
+};
+// the small arrays of column col = b K + j; the per-problem words go with column 0
+__host__ __device__ inline void cmpc_walk_jvp_gate_column(const CmpcJvpGateArgs& a, size_t col)
+{
+#pragma clang fp contract(off)
+    const int b = (int)(col / (size_t)a.K);
+    const bool col0 = col % (size_t)a.K == 0;
+    const size_t nl = (size_t)6 * a.M;
+    if (a.do_post) {
+        const bool ended = cmpc_gate_ended(a.end_tick, b, a.tick_post);
+        if (ended) {
+            for (int i = 0; i < 9; ++i) a.state_out[9 * col + i] = 0.0;
+            for (size_t i = 0; i < nl; ++i) a.list_out[nl * col + i] = 0.0;
+            if (a.list_rot_out) for (size_t i = 0; i < nl; ++i) a.list_rot_out[nl * col + i] = 0.0;
+        }
+        if (col0) {
+            a.status_row[b] = ended ? 6 : (int)a.t_sens[(size_t)b * CMPC_SENS];
+            if (a.removed_row) a.removed_row[b] = ended ? 0.f : a.t_sens[(size_t)b * CMPC_SENS + 6];
+        }
+    }
+    if (a.do_pre) {
+        if (col0) a.ok_out[b] = cmpc_gate_ended(a.end_tick, b, a.tick_pre) ? 0 : (a.ok_row ? a.ok_row[b] : 1);
+        if (a.first && cmpc_gate_ended(a.end_tick, b, a.tick_pre - 1)) {     // e < tick_pre: nothing enters
+            if (a.first_state) for (int i = 0; i < 9; ++i) a.first_state[9 * col + i] = 0.0;
+            if (a.first_list) for (size_t i = 0; i < nl; ++i) a.first_list[nl * col + i] = 0.0;
+            if (a.first_list_rot) for (size_t i = 0; i < nl; ++i) a.first_list_rot[nl * col + i] = 0.0;
+        }
+    }
+}
+// entry idx of the wide row [B][K][nx]: the solutions' directions of tick_post
+__host__ __device__ inline void cmpc_walk_jvp_gate_wide(const CmpcJvpGateArgs& a, size_t idx)
+{
+    if (a.do_post && a.x_row && idx < (size_t)a.B * a.K * a.nx && cmpc_gate_ended(a.end_tick, (int)(idx / ((size_t)a.K * a.nx)), a.tick_post)) a.x_row[idx] = 0.f;
+}

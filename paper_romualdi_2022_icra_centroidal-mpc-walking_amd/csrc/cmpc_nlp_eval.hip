@@ -1670,6 +1670,15 @@ __global__ __launch_bounds__(256) void cmpc_walk_vjp_gate_kernel(CmpcGateArgs a,
     for (size_t e = tid; e < wide; e += stride) cmpc_walk_gate_wide(a, e);
 }
 
+// gate of the forward walk: one thread per (problem, column) for the small arrays (cmpc_walk_jvp_gate_column; lanes past B k do nothing), then every
+// thread strides over the wide row [B][k][n_x] (cmpc_walk_jvp_gate_wide).  The two parts touch disjoint arrays: no LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_walk_jvp_gate_kernel(CmpcJvpGateArgs a, size_t cols, size_t wide)
+{
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    if (tid < cols) cmpc_walk_jvp_gate_column(a, tid);
+    for (size_t e = tid; e < wide; e += stride) cmpc_walk_jvp_gate_wide(a, e);
+}
+
 }  // namespace
 
 static unsigned stride_blocks(size_t least_threads, size_t work)
@@ -1697,6 +1706,18 @@ extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stre
 {
     const size_t wide = cmpc_walk_gate_wide_entries(a);
     hipLaunchKernelGGL(cmpc_walk_vjp_gate_kernel, dim3(stride_blocks((size_t)a->B, wide)), dim3(256), 0, stream, *a, wide);
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t cmpc_walk_jvp_gate_wide_entries(const CmpcJvpGateArgs* a)
+{
+    return a->do_post && a->x_row ? (size_t)a->B * a->K * a->nx : 0;
+}
+
+extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t stream)
+{
+    const size_t cols = (size_t)a->B * a->K, wide = cmpc_walk_jvp_gate_wide_entries(a);
+    hipLaunchKernelGGL(cmpc_walk_jvp_gate_kernel, dim3(stride_blocks(cols, wide)), dim3(256), 0, stream, *a, cols, wide);
     return (int)hipGetLastError();
 }
 

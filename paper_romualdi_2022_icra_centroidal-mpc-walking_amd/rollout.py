@@ -550,6 +550,61 @@ class WalkingRollout:
         cur.wait_stream(ls)
         return out
 
+    def forward_sensitivity_device(self, w, dir_state0=None, dir_list0=None, dir_list_rot0=None, dir_plan=None, dir_plan_rot=None, dir_push=None,
+                                   dir_models=None, dir_wrench=None, solutions=False):
+        """The device walk in forward mode (cmpc_rollout_walk_jvp_device): ONE call per replan segment, first segment first, no host read and no
+        synchronisation -- the transpose of backward_device(), input for output, with the orientations carried along.  w = walk_device_taped(...); the
+        directions and the returned dict as forward_sensitivity() (k columns right behind B; dir_plan / dir_plan_rot are read by every segment), plus
+        end_tick (w's).  A problem that ended at tick e (w["end_tick"]) keeps the directions of its states 0 .. e and of its solutions 0 .. e - 1
+        (include/cmpc.h): its rows e + 1 .. of states, e .. of X and its final list directions are exactly zero, its rows e .. of status 6 and of removed 0,
+        whatever its later tape rows or its rows of the directions hold -- not even NaN leaks.  Where nothing ended every entry is bit-equal to
+        run(tape=True) + forward_sensitivity()."""
+        torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
+        tape = w["tape"]
+        T, M, s = tape["rows"], tape["max_contacts"], self.solver
+
+        def as_dir(a, dtype, tail, lead=()):
+            if a is None:
+                return None
+            a = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, dtype).contiguous()
+            assert a.dim() == len(lead) + 2 + len(tail) and tuple(a.shape[:len(lead) + 1]) == lead + (B,) and tuple(a.shape[len(lead) + 2:]) == tail, \
+                f"direction of shape {tuple(a.shape)}: expected {lead + (B, 'k') + tail}"
+            return a
+        f32, f64 = torch.float32, torch.float64
+        ds, dl, dlr = as_dir(dir_state0, f64, (9,)), as_dir(dir_list0, f64, (2, M, 3)), as_dir(dir_list_rot0, f64, (2, M, 3))
+        dpl, dplr = as_dir(dir_plan, f64, (2, M, 3)), as_dir(dir_plan_rot, f64, (2, M, 3))
+        dpush, dmod, dwr = as_dir(dir_push, f32, (3,)), as_dir(dir_models, f64, (34,)), as_dir(dir_wrench, f32, (N, 6), lead=(T,))
+        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod) if a is not None} | ({int(dwr.shape[2])} if dwr is not None else set())
+        assert len(ks) == 1, "forward_sensitivity_device: no direction, or directions of different k"
+        k = ks.pop()
+        rot = dlr is not None or dplr is not None
+        z = lambda shape, dt=f64: torch.zeros(shape, dtype=dt, device=self.dev)
+        out = dict(states=z((T + 1, B, k, 9)), status=z((T, B), torch.int32), removed=z((T, B), f32), end_tick=w["end_tick"])
+        if solutions:
+            out["X"] = z((T, B, k, L.nx), f32)
+        starts = list(tape["segments"])
+        ls = s.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            if ds is not None:
+                out["states"][0] = ds
+            push_ticks = min(T, tape["push_ticks"]) if dpush is not None else 0
+            if push_ticks > 0:      # (forward_sensitivity()'s expression, tick by tick)
+                dwr = z((T, B, k, N, 6), f32) if dwr is None else dwr.clone()
+                for i in range(push_ticks):
+                    dwr[i][:, :, :max(tape["push_ticks"] - i, 1), :3] += dpush[:, :, None, :]
+            cl = z((B, k, 2, M, 3)) if dl is None else dl.clone()
+            clr = None if not rot else z((B, k, 2, M, 3)) if dlr is None else dlr.clone()
+            for j, t0 in enumerate(starts):
+                t1 = starts[j + 1] if j + 1 < len(starts) else T
+                s.rollout_walk_jvp_device(t0, t1 - t0, tape, t0, w["end_tick"], k, out["states"], cl, out["status"], carry_list_rot=clr, dir_plan=dpl,
+                                          dir_plan_rot=dplr, dir_wrench=dwr, dir_model=dmod, dir_x=out.get("X"), removed=out["removed"])
+            out["list"] = cl
+            out["list_rot"] = clr if rot else z((B, k, 2, M, 3))
+        cur.wait_stream(ls)
+        return out
+
 
 def yaw_plan_poses(pose, plan_yaw):
     """pose[B, 2, M, 7] float32 (x y z, quaternion w x y z) with every contact yawed about its own z axis by plan_yaw[B, 2, M] float64:
@@ -578,7 +633,9 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     host read in either, and a problem may END (a failed merge, a solve that does not converge, a non-finite state) without taking the batch's gradient
     with it: nothing asserts that every tick ran.  For a problem that ended at tick e the returned states hold final_state in rows > e (row e is
     final_state already), and backward first folds the cotangents of those rows into row e, which is the derivative of the function as returned.
-    rollout.last_walk is the walk's dict (end_tick says who ended and when).  Not with plan_yaw (NotImplementedError), and no forward mode."""
+    rollout.last_walk is the walk's dict (end_tick says who ended and when).  Forward mode (torch.autograd.forward_ad over state0, push and models) is
+    WalkingRollout.forward_sensitivity_device at k = 1, its dict in rollout.last_forward: the tangent of the rows > e of a problem that ended at tick e is
+    the tangent of its row e -- a select, the transpose of backward's fold.  Not with plan_yaw (NotImplementedError)."""
     import torch
 
     if device_walk:
@@ -669,5 +726,20 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             rollout.last_backward = r
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
                     r["models"] if ctx.needs_input_grad[2] else None)
+
+        @staticmethod
+        def jvp(ctx, t_state0, t_push, t_models):
+            """torch.autograd.forward_ad: forward_sensitivity_device at k = 1 on the tape the forward left.  The returned states hold final_state in the
+            rows behind a problem's end, so those rows take the tangent of the row its final state sits in: the transpose of backward's fold."""
+            col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
+            if all(t is None for t in (t_state0, t_push, t_models)):
+                return torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
+            r = rollout.forward_sensitivity_device(ctx.walk, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
+                                                   dir_models=col(t_models, torch.float64))
+            rollout.last_forward = r
+            t = r["states"][:, :, 0]
+            e = ctx.walk["end_tick"].to(torch.int64).clamp(min=0)
+            at_end = t.gather(0, e[None, :, None].expand(1, rollout.B, 9))      # [1, B, 9]: each problem's row e (row 0 where it never ended: not selected)
+            return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
     return _Fn.apply(state0, push, models)

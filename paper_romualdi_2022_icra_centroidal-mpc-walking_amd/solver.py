@@ -914,6 +914,33 @@ class BatchSolver:
         dev = torch.device("cuda", self._device_index) if device is None else device
         self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_vjp_gate_device(self._h, C.byref(gate), st))
 
+    def rollout_walk_jvp_device(self, tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, carry_list_rot=None, dir_plan=None,
+                                dir_plan_rot=None, dir_wrench=None, dir_model=None, dir_p=None, dir_x=None, removed=None):
+        """cmpc_rollout_walk_jvp_device: rows row0 .. row0 + ticks - 1 of tape (walk_tape) forwards in k directions in ONE call.  dir_states
+        [rows + 1, B, k, 9] float64: row row0 is read, rows row0 + 1 .. row0 + ticks are written; carry_list / carry_list_rot[B, k, 2, M, 3] float64 go in as
+        the list directions entering the first row and come back as those leaving the last (carry_list_rot and dir_plan_rot both None: no rotation chain);
+        dir_plan / dir_plan_rot[B, k, 2, M, 3], dir_model[B, k, 34] float64, dir_wrench[rows, B, k, N, 6], dir_p[rows, B, k, n_p] float32 (None: zero);
+        dir_x[rows, B, k, n_x] float32 (or None), status[rows, B] int32 and removed[rows, B] float32 (or None) are written row by row.  end_tick: int32
+        [B] (a walk record's) or None."""
+        import torch
+        L, B, N, M, R, k = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"]), int(tape["rows"]), int(k)
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        g3 = (B, k, 2, M, 3)
+        d = _capi.CmpcWalkDirs(self._opt(dir_states, f64, (R + 1, B, k, 9), "dir_states"), self._opt(carry_list, f64, g3, "carry_list"),
+                               self._opt(carry_list_rot, f64, g3, "carry_list_rot"), self._opt(dir_plan, f64, g3, "dir_plan"),
+                               self._opt(dir_plan_rot, f64, g3, "dir_plan_rot"), self._opt(dir_wrench, f32, (R, B, k, N, 6), "dir_wrench"),
+                               self._opt(dir_model, f64, (B, k, _capi.MODEL_DOUBLES), "dir_model"), self._opt(dir_p, f32, (R, B, k, L.np), "dir_p"),
+                               self._opt(dir_x, f32, (R, B, k, L.nx), "dir_x"), self._opt(status, i32, (R, B), "status"),
+                               self._opt(removed, f32, (R, B), "removed"))
+        e = self._opt(end_tick, i32, (B,), "end_tick")
+        self._launch(dir_states.device, lambda st: self._lib.cmpc_rollout_walk_jvp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, k, d, st))
+
+    def rollout_walk_jvp_gate_device(self, gate, device=None):
+        """cmpc_rollout_walk_jvp_gate_device: one gate step of the forward walk as one launch; gate: a _capi.CmpcWalkJvpGate of device pointers."""
+        import torch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_jvp_gate_device(self._h, C.byref(gate), st))
+
     def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
                             wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
                             tape=None, tape_row0=None):
