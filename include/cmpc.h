@@ -869,8 +869,8 @@ int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, co
  * the forward ticks'; first_row_is_first_tick != 0: row 0 is a first tick (no merge, no previous list) -- otherwise row 0 cannot be reversed.
  * Size: 4 (n_x + n_p + n_g) + 64 M + 96 bytes per problem and tick (the three wide rows, then 2 x 32 M of times, info 32, state 36, ok 4, land and the two
  * counts 8 each), about 12 KB at N = 20 (x, p and lam_g are a thousand floats each).
- * Out of scope here: the orientation (_rot) chain of the REVERSE walk on this tape -- it can follow on the same layout (the forward-mode walk below
- * carries the orientations already).  Contact times and Gamma stay undifferentiated, as everywhere. */
+ * Both walks below carry the contacts' orientations on this layout too: nothing more is taped for them.  Contact times and Gamma stay undifferentiated,
+ * as everywhere. */
 typedef struct cmpc_walk_tape {
     int rows;
     float* dX; float* dP; float* dLamG; float* dInfo; float* dStates;
@@ -917,7 +917,8 @@ int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, i
  * behind the tick it SELECTS zero for the carries, the wrench row and the dGradP row and writes dStatus = 6: it selects and does not multiply, so stale or
  * non-finite data of an ended problem cannot leak.  For i < e the gate's add is carry = the tick's dGradState + G_i in double.  The rule is one
  * __host__ __device__ function (cmpc_walk_gate_problem / cmpc_walk_gate_wide); the gate has no barrier and no atomics; lanes past B do nothing.
- * No host wait beyond the first call's workspace allocation (4 n_x + 48 M + 108 bytes per problem: the tick's dGradState and dGradPrevList, the gated dGradX row and dOk, the tick's dTickSens; grown when a larger
+ * No host wait beyond the first call's workspace allocation (4 n_x + 96 M + 108 bytes per problem: the tick's dGradState, dGradPrevList and -- for the
+ * orientation entry below, sized for it whichever entry runs first -- dGradPrevListRot, the gated dGradX row and dOk, the tick's dTickSens; grown when a larger
  * max_contacts arrives, and that call waits for the device); calls on one handle run one after the other whatever their streams (the tick VJP's event). */
 typedef struct cmpc_walk_grads {
     const double* dGradStates; const float* dGradX;
@@ -945,6 +946,42 @@ int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g);
 /* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what cmpc_rollout_walk_vjp_device queues
  * between its ticks, for a caller who reverses a walk tick by tick.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
 int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream);
+/* The reverse walk with the contacts' ORIENTATIONS carried along (body-frame tangents, as cmpc_rollout_tick_vjp_rot_device): the same loop -- one function
+ * behind both entries -- with cmpc_rollout_tick_vjp_rot_device per row, so one launch more per tick, and still ticks + 1 gate launches.  Tape rows, the
+ * `now` of a row and the first-tick rule of row 0 are the walk's above; nothing more is taped.  g as above; the fields of cmpc_walk_grads_rot, device
+ * pointers all:
+ *     dCarryListRot[B][2][M][3] double             in: the orientation carry entering the last row of the call; out: the one leaving its first row.  It is
+ *                                                  the tick's dGradListRotOut; the tick's dGradPrevListRot is a second buffer of the walk's workspace
+ *     dGradPlanRot[B][2][M][3] double or NULL      out, +=
+ *     dGradRot[rows][B][2][N][3] double or NULL    out, per row: each tick's full per-stage dl/domega (NULL: the tick's own workspace)
+ *     dRemoved[rows][B] float or NULL              out, per row: word 6 of the tick's dTickSens
+ * Segments compose through three carries; a call over the whole walk with dCarryListRot = 0 leaves dl/d(orientations of the first tick's lists) in it.
+ * Every output the entry above also has is bit-identical to it on the same tape and seeds (the tick's own guarantee).
+ * Ended problems: the rule above, extended.  l_rot_i = [i < e] (the tick's dGradPrevListRot); row i of dGradRot is the tick's when i < e and zero
+ * otherwise; dRemoved[i] is word 6 when i < e and 0 otherwise; nothing is added to dGradPlanRot for i >= e (the gated dOk = 0 makes the tick flag the
+ * problem); the first gate step of a call also selects zero in the caller's dCarryListRot of an ended problem.  Each of these is a select, never a
+ * multiply.  A problem that has not ended but whose tick is flagged passes zeros on, as the rotation tick VJP does.  The gate writes dGradRot only where
+ * the problem has ended: the tick's bits of a walking problem are never touched.
+ * CMPC_ERR_ARG: r == NULL, r->dCarryListRot == NULL, and everything cmpc_rollout_walk_vjp_device rejects. */
+typedef struct cmpc_walk_grads_rot {
+    double* dCarryListRot;
+    double* dGradPlanRot;
+    double* dGradRot;
+    float* dRemoved;
+} cmpc_walk_grads_rot;
+int cmpc_rollout_walk_vjp_rot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                     const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream);
+/* One gate step with the orientation arrays, host form and one-launch device form as above.  base: the step above, unchanged -- its outputs are bit for bit
+ * what cmpc_rollout_walk_vjp_gate writes for the same base.  POST: carry_list_rot[B][2][M][3] from tick_list_rot (the tick's dGradPrevListRot), zero
+ * selected in rot_row[B][2][N][3] of an ended problem (may be NULL; a walking problem's row is not written), removed_row[B] (may be NULL) from tick_sens.
+ * PRE with first != 0: zero selected in carry_list_rot of an ended problem.  The base's argument check, plus: carry_list_rot is required, and tick_list_rot
+ * with do_post. */
+typedef struct cmpc_walk_gate_rot {
+    cmpc_walk_gate base;
+    const double* tick_list_rot; double* carry_list_rot; double* rot_row; float* removed_row;
+} cmpc_walk_gate_rot;
+int cmpc_rollout_walk_vjp_rot_gate(const cmpc_walk_gate_rot* g);
+int cmpc_rollout_walk_vjp_rot_gate_device(cmpc_handle h, const cmpc_walk_gate_rot* g, void* stream);
 
 /* ---- the device walk FORWARDS on the same tape, k direction columns, per-problem endings kept (derivation and the rule: DESIGN.md 7f, "Forwards") ----
  * The forward walk: `ticks` calls of cmpc_rollout_tick_jvp_device (called, not copied: its chunks of eight columns, its workspace, its internal-force rule,

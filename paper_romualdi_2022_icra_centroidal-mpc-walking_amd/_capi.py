@@ -92,6 +92,16 @@ class CmpcWalkGate(C.Structure):
         ("do_pre", C.c_int), ("tick_pre", C.c_int), ("first", C.c_int)] + [(k, C.c_void_p) for k in ("ok_row", "grad_x_row", "ok_out", "grad_x_out")]
 
 
+class CmpcWalkGradsRot(C.Structure):
+    """mirror of cmpc_walk_grads_rot (include/cmpc.h): the orientation carry and outputs of cmpc_rollout_walk_vjp_rot_device"""
+    _fields_ = [(k, C.c_void_p) for k in ("dCarryListRot", "dGradPlanRot", "dGradRot", "dRemoved")]
+
+
+class CmpcWalkGateRot(C.Structure):
+    """mirror of cmpc_walk_gate_rot (include/cmpc.h): one gate step of the reverse walk with the orientation arrays, cmpc_rollout_walk_vjp_rot_gate[_device]"""
+    _fields_ = [("base", CmpcWalkGate)] + [(k, C.c_void_p) for k in ("tick_list_rot", "carry_list_rot", "rot_row", "removed_row")]
+
+
 class CmpcWalkDirs(C.Structure):
     """mirror of cmpc_walk_dirs (include/cmpc.h): the direction columns, carries and outputs of cmpc_rollout_walk_jvp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -162,6 +172,7 @@ EXPORTS = [
     "cmpc_rollout_tape_device", "cmpc_rollout_walk_taped_device", "cmpc_rollout_walk_vjp_device", "cmpc_rollout_walk_vjp_gate",
     "cmpc_rollout_walk_vjp_gate_device",
     "cmpc_rollout_walk_jvp_device", "cmpc_rollout_walk_jvp_gate", "cmpc_rollout_walk_jvp_gate_device",
+    "cmpc_rollout_walk_vjp_rot_device", "cmpc_rollout_walk_vjp_rot_gate", "cmpc_rollout_walk_vjp_rot_gate_device",
 ]
 
 _lib = None
@@ -286,6 +297,10 @@ def lib():
             L.cmpc_rollout_walk_vjp_device.argtypes = [vp, i, i, i, tp, i, vp, C.POINTER(CmpcWalkGrads), vp]
             L.cmpc_rollout_walk_vjp_gate.argtypes = [C.POINTER(CmpcWalkGate)]
             L.cmpc_rollout_walk_vjp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkGate), vp]
+            if hasattr(L, "cmpc_rollout_walk_vjp_rot_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+                L.cmpc_rollout_walk_vjp_rot_device.argtypes = [vp, i, i, i, tp, i, vp, C.POINTER(CmpcWalkGrads), C.POINTER(CmpcWalkGradsRot), vp]
+                L.cmpc_rollout_walk_vjp_rot_gate.argtypes = [C.POINTER(CmpcWalkGateRot)]
+                L.cmpc_rollout_walk_vjp_rot_gate_device.argtypes = [vp, C.POINTER(CmpcWalkGateRot), vp]
         if hasattr(L, "cmpc_rollout_walk_jvp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             L.cmpc_rollout_walk_jvp_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs), vp]
             L.cmpc_rollout_walk_jvp_gate.argtypes = [C.POINTER(CmpcWalkJvpGate)]

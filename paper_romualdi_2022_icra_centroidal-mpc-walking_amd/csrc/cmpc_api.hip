@@ -124,9 +124,9 @@ struct cmpc_handle_s {
     char* dTickJvpWs = nullptr;  // workspace of cmpc_rollout_tick_jvp_device for tick_jvp_cols columns per problem (allocated on first use, grown when a larger k
     int tick_jvp_cols = 0;       // arrives): rotation direction [B][k][2][N][3] | its stage 0 [B][k][2][3] | a zero state direction [B][k][9] (double) |
                                  // dx [B][k][n_x] | the assembled p direction [B][k][n_p] (float) | the tick's ok words [B] (int)
-    char* dWalkWs = nullptr;     // workspace of cmpc_rollout_walk_vjp_device for lists of walk_ws_M contacts (allocated on first use, grown when a larger
-    int walk_ws_M = 0;           // max_contacts arrives): the tick's dGradState [B][9] | its dGradPrevList [B][2][M][3] (double) | the gated dGradX row [B][n_x] |
-                                 // the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
+    char* dWalkWs = nullptr;     // workspace of cmpc_rollout_walk_vjp[_rot]_device for lists of walk_ws_M contacts (allocated on first use, grown when a larger
+    int walk_ws_M = 0;           // max_contacts arrives): the tick's dGradState [B][9] | its dGradPrevList | its dGradPrevListRot [B][2][M][3] each (double) |
+                                 // the gated dGradX row [B][n_x] | the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
     char* dWalkJvpWs = nullptr;  // workspace of cmpc_rollout_walk_jvp_device for walk_jvp_cols columns and lists of walk_jvp_M contacts (allocated on first use,
     int walk_jvp_cols = 0;       // grown when a larger k or max_contacts arrives): the second buffers of the list directions, positions and orientations
     int walk_jvp_M = 0;          // [B][k][2][M][3] each (double) | the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
@@ -1682,16 +1682,65 @@ static CmpcGateArgs gate_args_of(const cmpc_walk_gate* g, int nx, int np)
 
 static int gate_check(const cmpc_walk_gate* g);
 
+// the gate with the orientation arrays: the base check, plus carry_list_rot, and tick_list_rot with the POST part
+static int gate_rot_check(const cmpc_walk_gate_rot* g)
+{
+    if (!g) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate: bad argument");
+    const int rc = gate_check(&g->base);
+    if (rc != CMPC_OK) return rc;
+    if (!g->carry_list_rot || (g->base.do_post && !g->tick_list_rot))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate: carry_list_rot is needed, and tick_list_rot with the POST part");
+    return CMPC_OK;
+}
+
+static CmpcGateArgs gate_rot_args_of(const cmpc_walk_gate_rot* g, int nx, int np)
+{
+    CmpcGateArgs a = gate_args_of(&g->base, nx, np);
+    a.t_list_rot = g->tick_list_rot; a.carry_list_rot = g->carry_list_rot; a.rot_row = g->rot_row; a.removed_row = g->removed_row;
+    return a;
+}
+
+static int gate_launch(cmpc_handle h, const CmpcGateArgs& a, void* stream)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+static void gate_on_host(const CmpcGateArgs& a)
+{
+    for (int b = 0; b < a.B; ++b) cmpc_walk_gate_problem(a, b);
+    const size_t wide = cmpc_walk_gate_wide_entries(&a);
+    for (size_t e = 0; e < wide; ++e) cmpc_walk_gate_wide(a, e);
+}
+
 int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream)
 {
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: null handle");
     const int rc = gate_check(g);
     if (rc != CMPC_OK) return rc;
     if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: batch and horizon must be the handle's");
-    HIPCHK(h, hipSetDevice(h->device));
-    const CmpcGateArgs a = gate_args_of(g, h->L.nx, h->L.np);
-    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+    return gate_launch(h, gate_args_of(g, h->L.nx, h->L.np), stream);
+}
+
+int cmpc_rollout_walk_vjp_rot_gate_device(cmpc_handle h, const cmpc_walk_gate_rot* g, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate_device: null handle");
+    const int rc = gate_rot_check(g);
+    if (rc != CMPC_OK) return rc;
+    if (g->base.batch != h->B || g->base.horizon != h->cfg.horizon)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate_device: batch and horizon must be the handle's");
+    return gate_launch(h, gate_rot_args_of(g, h->L.nx, h->L.np), stream);
+}
+
+int cmpc_rollout_walk_vjp_rot_gate(const cmpc_walk_gate_rot* g)
+{
+    const int rc = gate_rot_check(g);
+    if (rc != CMPC_OK) return rc;
+    CmpcLayout L;
+    cmpc_layout_init(L, g->base.horizon);
+    gate_on_host(gate_rot_args_of(g, L.nx, L.np));
     return CMPC_OK;
 }
 
@@ -1712,23 +1761,23 @@ int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g)
     if (rc != CMPC_OK) return rc;
     CmpcLayout L;
     cmpc_layout_init(L, g->horizon);
-    const CmpcGateArgs a = gate_args_of(g, L.nx, L.np);
-    for (int b = 0; b < g->batch; ++b) cmpc_walk_gate_problem(a, b);
-    const size_t wide = cmpc_walk_gate_wide_entries(&a);
-    for (size_t e = 0; e < wide; ++e) cmpc_walk_gate_wide(a, e);
+    gate_on_host(gate_args_of(g, L.nx, L.np));
     return CMPC_OK;
 }
 
-int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                 const cmpc_walk_grads* g, void* stream)
+// the loop of both reverse walks; r: the orientation chain of cmpc_rollout_walk_vjp_rot_device (checked by the caller), or null -- then every launch and
+// every bit is what the walk without orientations always queued and gave
+static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                    const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream)
 {
-    if (!h || !g || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: null argument or incomplete tape");
+    const std::string name(who);
+    if (!h || !g || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, name + ": null argument or incomplete tape");
     if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: bad argument (the rows must lie inside the tape)");
+        return fail(h, CMPC_ERR_ARG, name + ": bad argument (the rows must lie inside the tape)");
     if (!g->dGradStates || !g->dCarryState || !g->dCarryList || !g->dStatus)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: dGradStates, the two carries and dStatus are needed");
+        return fail(h, CMPC_ERR_ARG, name + ": dGradStates, the two carries and dStatus are needed");
     if (row0 == 0 && !tape->first_row_is_first_tick)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_device: row 0 is not a first tick and has no row before it to take the previous lists from");
+        return fail(h, CMPC_ERR_ARG, name + ": row 0 is not a first tick and has no row before it to take the previous lists from");
     HIPCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     const int B = h->B, N = h->cfg.horizon, M = max_contacts;
@@ -1739,12 +1788,14 @@ int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int
             hipFree(h->dWalkWs);
             h->dWalkWs = nullptr; h->walk_ws_M = 0;
         }
-        HIPCHK(h, hipMalloc(&h->dWalkWs, sizeof(double) * ((size_t)B * 9 + nl) + sizeof(float) * (nx + (size_t)B * CMPC_SENS) + sizeof(int) * (size_t)B));
+        // (sized for the rotation entry whichever entry runs first: the second list buffer is the tick's dGradPrevListRot)
+        HIPCHK(h, hipMalloc(&h->dWalkWs, sizeof(double) * ((size_t)B * 9 + 2 * nl) + sizeof(float) * (nx + (size_t)B * CMPC_SENS) + sizeof(int) * (size_t)B));
         h->walk_ws_M = M;
     }
     double* wsState = reinterpret_cast<double*>(h->dWalkWs);
     double* wsList = wsState + (size_t)B * 9;
-    float* wsGx = reinterpret_cast<float*>(wsList + (size_t)B * 6 * h->walk_ws_M);
+    double* wsListRot = wsList + (size_t)B * 6 * h->walk_ws_M;
+    float* wsGx = reinterpret_cast<float*>(wsListRot + (size_t)B * 6 * h->walk_ws_M);
     float* wsSens = wsGx + nx;
     int* wsOk = reinterpret_cast<int*>(wsSens + (size_t)B * CMPC_SENS);
     if (h->tick_ev) HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));   // (the gate writes workspace an earlier call on another stream may still read)
@@ -1754,6 +1805,7 @@ int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int
     a.t_state = wsState; a.t_list = wsList; a.t_sens = wsSens;
     a.carry_state = g->dCarryState; a.carry_list = g->dCarryList;
     a.ok_out = wsOk; a.gx_out = g->dGradX ? wsGx : nullptr;
+    if (r) { a.t_list_rot = wsListRot; a.carry_list_rot = r->dCarryListRot; }
     int rc = CMPC_OK;
     for (int i = ticks; i >= 0 && rc == CMPC_OK; --i) {
         // the gate step between tick i (POST: i < ticks) and tick i - 1 (PRE: i > 0), fused into one launch
@@ -1764,6 +1816,10 @@ int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int
             a.wrench_row = g->dGradWrench ? g->dGradWrench + rq * B * 6 * N : nullptr;
             a.gp_row = g->dGradP ? g->dGradP + rq * np : nullptr;
             a.status_row = g->dStatus + rq * B;
+            if (r) {
+                a.rot_row = r->dGradRot ? r->dGradRot + rq * B * 6 * N : nullptr;
+                a.removed_row = r->dRemoved ? r->dRemoved + rq * B : nullptr;
+            }
         }
         a.do_pre = i > 0; a.tick_pre = tick0 + i - 1; a.first = i == ticks;
         if (a.do_pre) {
@@ -1782,12 +1838,26 @@ int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int
         tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
         tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
         tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
-        rc = tick_vjp(h, false, M, (double)(tick0 + i - 1) * h->cfg.sampling_time, &tt, g->dCarryState, g->dCarryList, a.gx_out, wsState, wsList,
+        rc = tick_vjp(h, r != nullptr, M, (double)(tick0 + i - 1) * h->cfg.sampling_time, &tt, g->dCarryState, g->dCarryList, a.gx_out, wsState, wsList,
                       g->dGradWrench ? g->dGradWrench + rp * B * 6 * N : nullptr, g->dGradPlan, g->dGradModel, g->dGradP ? g->dGradP + rp * np : nullptr, wsSens,
-                      nullptr, nullptr, nullptr, nullptr, stream);
+                      r ? r->dCarryListRot : nullptr, r ? wsListRot : nullptr, r ? r->dGradPlanRot : nullptr,
+                      r && r->dGradRot ? r->dGradRot + rp * B * 6 * N : nullptr, stream);
     }
     if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return rc;
+}
+
+int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                 const cmpc_walk_grads* g, void* stream)
+{
+    return walk_vjp(h, "cmpc_rollout_walk_vjp_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, nullptr, stream);
+}
+
+int cmpc_rollout_walk_vjp_rot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                     const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream)
+{
+    if (!r || !r->dCarryListRot) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_device: r and its dCarryListRot are needed");
+    return walk_vjp(h, "cmpc_rollout_walk_vjp_rot_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, r, stream);
 }
 
 // ---- one tick FORWARDS in k directions (include/cmpc.h): list JVP (merge + sample) -> the p direction assembled (cmpc_tick_jvp_assemble_kernel) ->

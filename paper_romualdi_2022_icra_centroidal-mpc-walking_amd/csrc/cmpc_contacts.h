@@ -292,6 +292,12 @@ struct CmpcGateArgs {
     const int* ok_row;            // [B] tape row of row_pre
     const float* gx_row;          // [B][nx] seeds of row_pre, or null
     int* ok_out; float* gx_out;   // the gated copies the tick VJP reads (gx_out null with gx_row null)
+    // the orientation chain (cmpc_rollout_walk_vjp_rot_device), every pointer null without it: l_rot_i = [i < e] (the tick's dGradPrevListRot), the row of
+    // dGradRot and the removed word zero for i >= e
+    const double* t_list_rot;     // [B][2][M][3]: the tick's dGradPrevListRot
+    double* carry_list_rot;       // [B][2][M][3]: out (POST) / sanitised in place (PRE with `first`)
+    double* rot_row;              // [B][2][N][3] of row_post: written only where the problem has ended
+    float* removed_row;           // [B] of row_post: word 6 of the tick's dTickSens, 0 for an ended problem
 };
 __host__ __device__ inline bool cmpc_gate_ended(const int* end_tick, int b, int tick)
 {
@@ -312,7 +318,9 @@ __host__ __device__ inline void cmpc_walk_gate_problem(const CmpcGateArgs& a, in
             a.carry_state[o] = !ended ? a.t_state[o] + a.seed_state[o] : a.tick_post == e ? a.seed_state[o] : 0.0;
         }
         for (size_t i = 0; i < nl; ++i) a.carry_list[nl * b + i] = ended ? 0.0 : a.t_list[nl * b + i];
+        if (a.carry_list_rot) for (size_t i = 0; i < nl; ++i) a.carry_list_rot[nl * b + i] = ended ? 0.0 : a.t_list_rot[nl * b + i];
         a.status_row[b] = ended ? 6 : (int)a.t_sens[(size_t)b * CMPC_SENS];
+        if (a.removed_row) a.removed_row[b] = ended ? 0.f : a.t_sens[(size_t)b * CMPC_SENS + 6];
     }
     if (a.do_pre) {
         const bool ended = cmpc_gate_ended(a.end_tick, b, a.tick_pre);
@@ -320,10 +328,12 @@ __host__ __device__ inline void cmpc_walk_gate_problem(const CmpcGateArgs& a, in
         if (a.first && ended) {
             for (int i = 0; i < 9; ++i) a.carry_state[9 * (size_t)b + i] = 0.0;
             for (size_t i = 0; i < nl; ++i) a.carry_list[nl * b + i] = 0.0;
+            if (a.carry_list_rot) for (size_t i = 0; i < nl; ++i) a.carry_list_rot[nl * b + i] = 0.0;
         }
     }
 }
-// entry idx of the wide rows: [B][nx] (the gated dGradX copy), [B][N][6] (the wrench row) and [B][np] (the dGradP row); idx runs to B max(nx, np)
+// entry idx of the wide rows: [B][nx] (the gated dGradX copy), [B][N][6] (the wrench row), [B][np] (the dGradP row) and [B][2][N][3] (the dGradRot row);
+// idx runs to B max(nx, np, 6 N)
 __host__ __device__ inline void cmpc_walk_gate_wide(const CmpcGateArgs& a, size_t idx)
 {
     if (a.do_pre && a.gx_out && idx < (size_t)a.B * a.nx)
@@ -332,6 +342,7 @@ __host__ __device__ inline void cmpc_walk_gate_wide(const CmpcGateArgs& a, size_
         const size_t nw = (size_t)6 * a.N;
         if (a.wrench_row && idx < (size_t)a.B * nw && cmpc_gate_ended(a.end_tick, (int)(idx / nw), a.tick_post)) a.wrench_row[idx] = 0.f;
         if (a.gp_row && idx < (size_t)a.B * a.np && cmpc_gate_ended(a.end_tick, (int)(idx / a.np), a.tick_post)) a.gp_row[idx] = 0.f;
+        if (a.rot_row && idx < (size_t)a.B * nw && cmpc_gate_ended(a.end_tick, (int)(idx / nw), a.tick_post)) a.rot_row[idx] = 0.0;
     }
 }
 

@@ -1698,7 +1698,8 @@ extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t strea
 
 extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a)
 {
-    const int w = a->nx > a->np ? a->nx : a->np;   // (6 N < n_p)
+    int w = a->nx > a->np ? a->nx : a->np;   // (6 N < n_p: the wrench row is covered)
+    if (a->do_post && a->rot_row && 6 * a->N > w) w = 6 * a->N;
     return (size_t)a->B * w;
 }
 

@@ -460,7 +460,20 @@ class WalkingRollout:
         -> the keys of backward() -- state0, list0, wrench, push, models, plan, status -- and end_tick (w's).  A problem that ended at tick e
         (w["end_tick"]) contributes the loss over its states 0 .. e and its solutions 0 .. e - 1 (include/cmpc.h: the seeds of its later rows are not read,
         not even when they are not finite); its rows e .. of wrench are zero and of status 6.  Where nothing ended every entry is bit-equal to
-        run(tape=True) + backward()."""
+        run(tape=True) + backward().  The contacts' orientations too: backward_device_rot()."""
+        return self._backward_device(w, grad_states, grad_X, False)
+
+    def backward_device_rot(self, w, grad_states, grad_X=None):
+        """backward_device() with the contacts' orientations carried along (cmpc_rollout_walk_vjp_rot_device; body-frame tangents, as backward(rot=True)):
+        still ONE call per replan segment, no host read and no synchronisation.  The dict also holds list_rot0[B, 2, M, 3] (the first tick's lists),
+        plan_rot[B, 2, M, 3] (the planner's contacts, accumulated in one buffer over the segments as plan is), rot[ticks, B, 2, N, 3] (each tick's
+        per-stage dl/domega), float64, and removed[ticks, B] float32 (word 6 of each tick's dSens); every key backward_device() also has is bit-equal to
+        it.  A problem that ended at tick e: its rows e .. of rot are zero and of removed 0, and nothing of its later rows reaches list_rot0 or plan_rot.
+        Where nothing ended every entry is bit-equal to run(tape=True) + backward(rot=True).  (A method of its own and not an argument of
+        backward_device: that signature is pinned.)"""
+        return self._backward_device(w, grad_states, grad_X, True)
+
+    def _backward_device(self, w, grad_states, grad_X, rot):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
@@ -474,19 +487,25 @@ class WalkingRollout:
         z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=self.dev)
         out = dict(push=z((B, 3)), wrench=z((T, B, N, 6), torch.float32), models=z((B, 34)), plan=z((B, 2, M, 3)), status=z((T, B), torch.int32),
                    end_tick=w["end_tick"])
+        if rot:
+            out.update(plan_rot=z((B, 2, M, 3)), rot=z((T, B, 2, N, 3)), removed=z((T, B), torch.float32))
         starts = list(tape["segments"])
         ls = s.launch_stream
         cur = torch.cuda.current_stream(self.dev)
         ls.wait_stream(cur)
         with torch.cuda.stream(ls):
             g, gl = gS[T].clone(), z((B, 2, M, 3))    # (the gate in front of the last tick selects zero where the problem has ended)
+            glr = z((B, 2, M, 3)) if rot else None
             for j in reversed(range(len(starts))):
                 t0, t1 = starts[j], starts[j + 1] if j + 1 < len(starts) else T
                 s.rollout_walk_vjp_device(t0, t1 - t0, tape, t0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, wrench=out["wrench"],
-                                          dGradPlan=out["plan"], dGradModel=out["models"])
+                                          dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
+                                          grad_rot=out.get("rot"), removed=out.get("removed"))
             for i in reversed(range(min(T, tape["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
                 out["push"] += out["wrench"][i][:, :max(tape["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
             out["state0"], out["list0"] = g, gl
+            if rot:
+                out["list_rot0"] = glr
         cur.wait_stream(ls)
         return out
 
@@ -619,7 +638,49 @@ def yaw_plan_poses(pose, plan_yaw):
     return out
 
 
-def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None, device_walk=False, replan=None):
+def so3_right_jacobian(omega):
+    """omega[..., 3] -> Jr[..., 3, 3], the right Jacobian of SO(3): Exp(omega + d) = Exp(omega) Exp(Jr(omega) d) to first order.  Formed in float64 as
+    I + a W + b W^2 with W = [omega]x, a = -(1 - cos t) / t^2, b = (t - sin t) / t^3, t = |omega|, both by their series where t < 1e-2 (there the closed
+    forms cancel; the series' first dropped term is below 1e-20).  W and W^2 have a zero column along omega's own axis, so the z column at
+    omega = (0, 0, psi) is exactly e_z."""
+    import torch
+    om = omega.to(torch.float64)
+    x, y, z = om.unbind(-1)
+    t2 = x * x + y * y + z * z
+    small = t2 < 1e-4
+    t2s = torch.where(small, torch.ones_like(t2), t2)       # (the closed forms are not evaluated near zero)
+    t = torch.sqrt(t2s)
+    a = torch.where(small, -(0.5 - t2 / 24.0 + t2 * t2 / 720.0 - t2 * t2 * t2 / 40320.0), -(1.0 - torch.cos(t)) / t2s)
+    b = torch.where(small, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0, (t - torch.sin(t)) / (t2s * t))
+    o = torch.zeros_like(x)
+    W = torch.stack([torch.stack([o, -z, y], -1), torch.stack([z, o, -x], -1), torch.stack([-y, x, o], -1)], -2)
+    W2 = (W[..., :, None, :] * W.transpose(-1, -2)[..., None, :, :]).sum(-1)     # W2[i, j] = sum_k W[i, k] W[k, j], k in order
+    return torch.eye(3, dtype=torch.float64, device=om.device) + a[..., None, None] * W + b[..., None, None] * W2
+
+
+def rot_plan_poses(pose, plan_rot):
+    """pose[B, 2, M, 7] float32 (x y z, quaternion w x y z) with every contact rotated by the rotation vector plan_rot[B, 2, M, 3] float64 in its own
+    frame: q <- q (x) Exp(omega), Exp(omega) = (cos(t / 2), sin(t / 2) omega / t), formed in float64 (sin(t / 2) / t by its series where t < 1e-2).  An
+    entry whose x and y components are exactly 0 is yaw_plan_poses' expression for that entry, to the bit (so a zero entry keeps its bits)."""
+    import torch
+    om = plan_rot.to(torch.float64)
+    ox, oy, oz = om.unbind(-1)
+    t2 = ox * ox + oy * oy + oz * oz
+    small = t2 < 1e-4
+    t = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))
+    k = torch.where(small, 0.5 - t2 / 48.0 + t2 * t2 / 3840.0 - t2 * t2 * t2 / 645120.0, torch.sin(0.5 * t) / t)
+    rw = torch.where(small, 1.0 - t2 / 8.0 + t2 * t2 / 384.0 - t2 * t2 * t2 / 46080.0, torch.cos(0.5 * t))
+    rx, ry, rz = k * ox, k * oy, k * oz
+    w, x, y, z = pose[..., 3:7].to(torch.float64).unbind(-1)
+    qr = torch.stack([w * rw - x * rx - y * ry - z * rz, w * rx + x * rw + y * rz - z * ry, w * ry - x * rz + y * rw + z * rx,
+                      w * rz + x * ry - y * rx + z * rw], -1).to(torch.float32)
+    out = yaw_plan_poses(pose, oz)
+    out[..., 3:7] = torch.where(((ox == 0) & (oy == 0))[..., None], out[..., 3:7], qr)
+    return out
+
+
+def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None, device_walk=False, replan=None,
+                           plan_rot=None):
     """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
     state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
     (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
@@ -635,19 +696,29 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     final_state already), and backward first folds the cotangents of those rows into row e, which is the derivative of the function as returned.
     rollout.last_walk is the walk's dict (end_tick says who ended and when).  Forward mode (torch.autograd.forward_ad over state0, push and models) is
     WalkingRollout.forward_sensitivity_device at k = 1, its dict in rollout.last_forward: the tangent of the rows > e of a problem that ended at tick e is
-    the tangent of its row e -- a select, the transpose of backward's fold.  Not with plan_yaw (NotImplementedError)."""
+    the tangent of its row e -- a select, the transpose of backward's fold.  Not with plan_yaw (NotImplementedError): on the device path a yaw is
+    plan_rot[..., 2].
+    plan_rot: None, or a [B, 2, M, 3] float64 CUDA tensor, on both paths: entry (b, c, m) rotates the planner's contact m of foot c by the rotation
+    vector omega in its own frame before the run, q <- q (x) Exp(omega) (rot_plan_poses, on a copy of rollout.plan's poses and of the poses of every
+    plan in replan; an entry without x and y components is plan_yaw's rotation to the bit).  backward runs with rot=True (backward, or
+    backward_device_rot with device_walk=True) and plan_rot.grad = Jr(omega)^T (plan_rot + list_rot0), Jr the right Jacobian of SO(3)
+    (so3_right_jacobian): q (x) Exp(omega + d) = q (x) Exp(omega) (x) Exp(Jr(omega) d), and the library's gradients are in the body-frame tangent at
+    the rotated quaternion.  Its z component at omega = (0, 0, psi) is plan_yaw.grad to the bit.  Forward mode passes Jr(omega) t as dir_plan_rot and
+    dir_list_rot0.  Not together with plan_yaw (ValueError)."""
     import torch
 
+    if plan_rot is not None and plan_yaw is not None:
+        raise ValueError("rollout_differentiable: plan_rot and plan_yaw are two parametrisations of the same rotation: give one")
     if device_walk:
         if plan_yaw is not None:
-            raise NotImplementedError("rollout_differentiable(device_walk=True): the orientation chain on the device tape is not built yet")
-        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan)
+            raise NotImplementedError("rollout_differentiable(device_walk=True): plan_yaw is not taken on the device path; pass the yaw as plan_rot[..., 2]")
+        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot)
     if replan is not None:
         raise NotImplementedError("rollout_differentiable: replan needs device_walk=True")
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, state0, push, models, plan_yaw):
+        def forward(ctx, state0, push, models, plan_yaw, plan_rot):
             if models is not None:
                 rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
@@ -657,12 +728,18 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
                 psi = plan_yaw.detach().to(rollout.dev, torch.float64)
                 assert tuple(psi.shape) == tuple(plan[1].shape[:3]), f"plan_yaw: expected {tuple(plan[1].shape[:3])}"
                 rollout.plan = (plan[0], yaw_plan_poses(plan[1], psi), plan[2])
+            ctx.jr = None
+            if plan_rot is not None:
+                om = plan_rot.detach().to(rollout.dev, torch.float64)
+                assert tuple(om.shape) == tuple(plan[1].shape[:3]) + (3,), f"plan_rot: expected {tuple(plan[1].shape[:3]) + (3,)}"
+                rollout.plan = (plan[0], rot_plan_poses(plan[1], om), plan[2])
+                ctx.jr = so3_right_jacobian(om)
             try:
                 rec = rollout.run(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(torch.float32).cpu().numpy(),
                                   push_ticks=push_ticks, record="light", tape=True)
             finally:
                 rollout.plan = plan
-            ctx.rot = plan_yaw is not None
+            ctx.rot = plan_yaw is not None or plan_rot is not None
             tape = rec["tape"]
             assert len(tape["ticks"]) == ticks, f"the roll-out stopped at tick {rec.get('aborted_tick')}"
             rollout.last_tape = ctx.tape = tape
@@ -675,10 +752,11 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
             rollout.last_backward = r
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
                     r["models"] if ctx.needs_input_grad[2] else None,
-                    (r["plan_rot"][..., 2] + r["list_rot0"][..., 2]) if ctx.rot and ctx.needs_input_grad[3] else None)
+                    (r["plan_rot"][..., 2] + r["list_rot0"][..., 2]) if ctx.rot and ctx.needs_input_grad[3] else None,
+                    _jr_transposed(ctx.jr, r["plan_rot"] + r["list_rot0"]) if ctx.jr is not None and ctx.needs_input_grad[4] else None)
 
         @staticmethod
-        def jvp(ctx, t_state0, t_push, t_models, t_yaw):
+        def jvp(ctx, t_state0, t_push, t_models, t_yaw, t_rot):
             """torch.autograd.forward_ad: forward_sensitivity at k = 1 on the tape the forward left.  A yaw tangent is d psi e_z on the planner's
             orientations and on the first tick's list, the transpose of what backward returns for plan_yaw."""
             col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
@@ -686,29 +764,53 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
             if t_yaw is not None:
                 yaw = torch.zeros(tuple(t_yaw.shape[:1]) + (1,) + tuple(t_yaw.shape[1:]) + (3,), dtype=torch.float64, device=rollout.dev)
                 yaw[..., 2] = t_yaw.detach().to(rollout.dev, torch.float64)[:, None]
-            if all(t is None for t in (t_state0, t_push, t_models, t_yaw)):
+            if t_rot is not None:
+                yaw = _jr_applied(ctx.jr, t_rot.detach().to(rollout.dev, torch.float64))[:, None].contiguous()
+            if all(t is None for t in (t_state0, t_push, t_models, t_yaw, t_rot)):
                 return torch.zeros((len(ctx.tape["ticks"]) + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
             r = rollout.forward_sensitivity(ctx.tape, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
                                             dir_models=col(t_models, torch.float64), dir_plan_rot=yaw, dir_list_rot0=yaw)
             rollout.last_forward = r
             return r["states"][:, :, 0].to(torch.float32)
 
-    return _Fn.apply(state0, push, models, plan_yaw)
+    return _Fn.apply(state0, push, models, plan_yaw, plan_rot)
 
 
-def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan):
+def _jr_transposed(jr, g):
+    """Jr^T g per entry, the three products summed in index order"""
+    return (jr * g[..., :, None]).sum(-2)
+
+
+def _jr_applied(jr, t):
+    """Jr t per entry, the three products summed in index order"""
+    return (jr * t[..., None, :]).sum(-1)
+
+
+def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None):
     """rollout_differentiable(device_walk=True)"""
     import torch
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, state0, push, models):
+        def forward(ctx, state0, push, models, plan_rot):
             if models is not None:
                 rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
             s0 = state0.detach().to(rollout.dev, torch.float32)
-            w = rollout.walk_device_taped(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], push=None if push is None else push.detach().to(rollout.dev, torch.float32),
-                                          push_ticks=push_ticks, replan=replan, trace=False)
+            plan, plans = rollout.plan, replan
+            ctx.jr = None
+            if plan_rot is not None:     # (the planner's contacts of every segment turn by the same vectors: the one plan_rot buffer sums over them)
+                om = plan_rot.detach().to(rollout.dev, torch.float64)
+                assert tuple(om.shape) == tuple(plan[1].shape[:3]) + (3,), f"plan_rot: expected {tuple(plan[1].shape[:3]) + (3,)}"
+                rollout.plan = (plan[0], rot_plan_poses(plan[1], om), plan[2])
+                plans = None if replan is None else {t: (p[0], rot_plan_poses(p[1], om), p[2]) for t, p in replan.items()}
+                ctx.jr = so3_right_jacobian(om)
+            try:
+                w = rollout.walk_device_taped(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9],
+                                              push=None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks=push_ticks,
+                                              replan=plans, trace=False)
+            finally:
+                rollout.plan = plan
             rollout.last_walk = ctx.walk = w
             ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
             e = w["end_tick"]
@@ -722,24 +824,26 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             g = gStates.to(rollout.dev, torch.float64)
             folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
             g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
-            r = rollout.backward_device(ctx.walk, g)
+            r = rollout.backward_device(ctx.walk, g) if ctx.jr is None else rollout.backward_device_rot(ctx.walk, g)
             rollout.last_backward = r
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
-                    r["models"] if ctx.needs_input_grad[2] else None)
+                    r["models"] if ctx.needs_input_grad[2] else None,
+                    _jr_transposed(ctx.jr, r["plan_rot"] + r["list_rot0"]) if ctx.jr is not None and ctx.needs_input_grad[3] else None)
 
         @staticmethod
-        def jvp(ctx, t_state0, t_push, t_models):
+        def jvp(ctx, t_state0, t_push, t_models, t_rot):
             """torch.autograd.forward_ad: forward_sensitivity_device at k = 1 on the tape the forward left.  The returned states hold final_state in the
             rows behind a problem's end, so those rows take the tangent of the row its final state sits in: the transpose of backward's fold."""
             col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
-            if all(t is None for t in (t_state0, t_push, t_models)):
+            if all(t is None for t in (t_state0, t_push, t_models, t_rot)):
                 return torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
+            drot = None if t_rot is None else _jr_applied(ctx.jr, t_rot.detach().to(rollout.dev, torch.float64))[:, None].contiguous()
             r = rollout.forward_sensitivity_device(ctx.walk, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
-                                                   dir_models=col(t_models, torch.float64))
+                                                   dir_models=col(t_models, torch.float64), dir_plan_rot=drot, dir_list_rot0=drot)
             rollout.last_forward = r
             t = r["states"][:, :, 0]
             e = ctx.walk["end_tick"].to(torch.int64).clamp(min=0)
             at_end = t.gather(0, e[None, :, None].expand(1, rollout.B, 9))      # [1, B, 9]: each problem's row e (row 0 where it never ended: not selected)
             return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
-    return _Fn.apply(state0, push, models)
+    return _Fn.apply(state0, push, models, plan_rot)

@@ -892,11 +892,14 @@ class BatchSolver:
             ptr(lists[2]) if lists is not None else None, tape["_c"], st))
 
     def rollout_walk_vjp_device(self, tick0, ticks, tape, row0, end_tick, grad_states, carry_state, carry_list, status, grad_X=None, wrench=None, grad_p=None,
-                                dGradPlan=None, dGradModel=None):
+                                dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None):
         """cmpc_rollout_walk_vjp_device: rows row0 .. row0 + ticks - 1 of tape (walk_tape) in reverse in ONE call.  grad_states[rows + 1, B, 9] float64 and
         grad_X[rows, B, n_x] float32 (or None) are the seeds; carry_state[B, 9] / carry_list[B, 2, M, 3] float64 go in as the carry entering the last row
         and come back as the carry leaving the first; wrench[rows, B, N, 6] / grad_p[rows, B, n_p] float32 (or None) and status[rows, B] int32 are written
-        row by row; dGradPlan[B, 2, M, 3] / dGradModel[B, 34] float64 are added to in place.  end_tick: int32 [B] (a walk record's) or None."""
+        row by row; dGradPlan[B, 2, M, 3] / dGradModel[B, 34] float64 are added to in place.  end_tick: int32 [B] (a walk record's) or None.
+        carry_list_rot[B, 2, M, 3] float64 given: cmpc_rollout_walk_vjp_rot_device, the contacts' orientations carried along -- it is the third carry;
+        dGradPlanRot[B, 2, M, 3] float64 (or None) is added to in place, grad_rot[rows, B, 2, N, 3] float64 and removed[rows, B] float32 (or None) are
+        written row by row.  Without it the three other arguments must be None and the call is the one it always was."""
         import torch
         L, B, N, M, R = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"]), int(tape["rows"])
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
@@ -906,13 +909,27 @@ class BatchSolver:
                                 self._opt(dGradPlan, f64, (B, 2, M, 3), "dGradPlan"), self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"),
                                 self._opt(status, i32, (R, B), "status"))
         e = self._opt(end_tick, i32, (B,), "end_tick")
-        self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, st))
+        if carry_list_rot is None:
+            assert dGradPlanRot is None and grad_rot is None and removed is None, "orientation gradients need carry_list_rot"
+            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, st))
+            return
+        r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
+                                   self._opt(grad_rot, f64, (R, B, 2, N, 3), "grad_rot"), self._opt(removed, f32, (R, B), "removed"))
+        self._launch(carry_state.device,
+                     lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, r, st))
 
     def rollout_walk_vjp_gate_device(self, gate, device=None):
         """cmpc_rollout_walk_vjp_gate_device: one gate step of the reverse walk as one launch; gate: a _capi.CmpcWalkGate of device pointers."""
         import torch
         dev = torch.device("cuda", self._device_index) if device is None else device
         self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_vjp_gate_device(self._h, C.byref(gate), st))
+
+    def rollout_walk_vjp_rot_gate_device(self, gate, device=None):
+        """cmpc_rollout_walk_vjp_rot_gate_device: one gate step of the reverse walk with the orientation arrays as one launch; gate: a
+        _capi.CmpcWalkGateRot of device pointers."""
+        import torch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_vjp_rot_gate_device(self._h, C.byref(gate), st))
 
     def rollout_walk_jvp_device(self, tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, carry_list_rot=None, dir_plan=None,
                                 dir_plan_rot=None, dir_wrench=None, dir_model=None, dir_p=None, dir_x=None, removed=None):
