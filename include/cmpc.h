@@ -428,6 +428,48 @@ int cmpc_set_reference_from_planner(cmpc_handle h, const float* com_in, const fl
  * asynchronous on `stream` (NULL: the handle's) */
 int cmpc_write_reference_from_planner_device(cmpc_handle h, const float* dComIn, const float* dHIn, int n_in, double in_dt, double t_offset,
                                              double robot_mass, double com_height, float* dP, void* stream);
+/* 8f-3 differentiated in the planner's trajectories, over the rows of a walk ("References").  The map: the handle's sampling time is dt; tick
+ * number i runs at now = i * dt and reads the trajectories c, h [knots][3] (float32, a knot every pl->dt seconds, knot 0 at time pl->t_first) at
+ * t_off = now - t_first, as cmpc_rollout_walk_device does (plan_t_first).  For MPC knot k = 0 .. N
+ *     s = clamp((t_off + k dt) / pl->dt, 0, knots - 1),  i0 = min((int)s, knots - 2),  w = s - i0
+ *     comRef_k[a] = (float)((1 - w) c[i0][a] + w c[i0+1][a])                  a = 0, 1; a = 2 only if com_height is NaN
+ *     hRef_k[a]   = (float)(((1 - w) h[i0][a] + w h[i0+1][a]) / robot_mass)
+ * Times, robot_mass and com_height are not differentiated.  The weights are those of the clamped forward: a knot beyond an end puts its whole weight on the
+ * end knot.  With com_height a number the z row of comRef is a constant: its entries of the gradient are not read, its direction is 0.0f.  (i0, w) come
+ * from ONE __host__ __device__ function (cmpc_reference_weight, csrc/cmpc_contacts.h) that repeats cmpc_resample_reference_knot's arithmetic with
+ * contraction into fma off; that function itself is untouched.  All four entry points compile with contraction off; the host forms need no handle and no
+ * GPU and are bit-equal to the kernels.  A single tick at an arbitrary offset is rows = 1, tick0 = 0, t_first = -t_offset.  The array pointers point at
+ * the first row used. */
+typedef struct cmpc_planner_refs {
+    int knots;             /* knots of each trajectory, >= 2 */
+    double dt;             /* seconds between two knots (cmpc_write_reference_from_planner_device's in_dt) */
+    double t_first;        /* time of knot 0 */
+    double robot_mass;
+    double com_height;     /* NaN: the trajectory's own z row is used, and differentiated */
+} cmpc_planner_refs;
+/* Reverse: grad_p[rows][B][n_p] float, row r the dl/dp of tick tick0 + r (cmpc_walk_grads.dGradP) -> grad_com / grad_h [B][knots][3] double, ADDED TO
+ * (either may be NULL when only the other is wanted, not both).  Problem b with e = end_tick[b] (NULL or -1: never ended) contributes the rows with
+ * tick0 + r < e -- its solutions 0 .. e - 1, the rule of cmpc_rollout_walk_vjp_device.  Rows at or past e are NOT READ: a select, so NaN there cannot leak.
+ * Each output entry is owned by one thread (no atomics): it loads the entry's current value, then adds its terms in ascending (row, knot) order,
+ * (1 - w) * (double)g for i0 == j, w * (double)g for i0 + 1 == j, for h the same divided by robot_mass.  Because of that order ascending segments compose
+ * to the bit with one call over all rows.  The device form is ONE launch whatever the number of rows (one workgroup per problem and 128 planner knots,
+ * the rows' terms staged through LDS eight rows at a time; every barrier is uniform over the workgroup, an ended problem only shortens the loop), asynchronous on
+ * `stream` (NULL: the handle's), no workspace, no host wait; lanes past `knots` touch no memory.
+ * CMPC_ERR_ARG: a NULL handle, pl or grad_p, both outputs NULL, knots < 2, dt or robot_mass not > 0 or not finite, t_first not finite, rows < 1,
+ * tick0 < 0; the host form also for a horizon outside 1 .. 40, a sampling time not > 0 or a batch < 1. */
+int cmpc_reference_from_planner_vjp(int horizon, double sampling_time, int batch, int tick0, int rows, const cmpc_planner_refs* pl, const int* end_tick,
+                                    const float* grad_p, double* grad_com, double* grad_h);
+int cmpc_reference_from_planner_vjp_device(cmpc_handle h, int tick0, int rows, const cmpc_planner_refs* pl, const int* dEndTick, const float* dGradP,
+                                           double* dGradCom, double* dGradH, void* stream);
+/* Forwards: dir_com / dir_h [B][k][knots][3] double (either may be NULL: zero, not both) -> the 6 (N + 1) reference entries (comRef, hRef) of every column
+ * of dir_p[rows][B][k][n_p] float, the layout of cmpc_walk_dirs.dDirP.  Entry = the forward's expression applied to the direction in double, then cast to
+ * float; z of comRef is 0.0f when com_height is a number.  It WRITES those entries and leaves every other entry of dir_p alone.  No ending logic: the
+ * forward walk's gate discards what an ended problem is given.  One thread per written entry; asynchronous on `stream` (NULL: the handle's), no workspace.
+ * CMPC_ERR_ARG as above, and k < 1. */
+int cmpc_reference_from_planner_jvp(int horizon, double sampling_time, int batch, int tick0, int rows, int k, const cmpc_planner_refs* pl,
+                                    const double* dir_com, const double* dir_h, float* dir_p);
+int cmpc_reference_from_planner_jvp_device(cmpc_handle h, int tick0, int rows, int k, const cmpc_planner_refs* pl, const double* dDirCom, const double* dDirH,
+                                           float* dDirP, void* stream);
 /* 8f-4, WholeBodyQPBlock.cpp:805-873, 1083-1084, 1150, 1259-1262: between two MPC ticks the plant integrates the
  * centroidal dynamics under the first-knot corner forces of the active contacts + the external wrench of knot 0 (RK4,
  * `substeps` steps of `step` seconds, forces held) and reports the desired ZMP (local ZMP clamped to +-zmp_half_x/y:
@@ -751,7 +793,7 @@ int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double
  * Chain, on one stream: cmpc_plant_step_vjp_device -> the adjust part of cmpc_contacts_position_vjp_device -> cmpc_solution_vjp_model_device (called, not
  * copied: its definition, its workspace and its dSens hold) -> gState += gP[com0, dcom0, h0] (cmpc_write_state_device in reverse) -> the sample + merge part.
  * The solution map is taken as independent of x0: warm start, shift and cold restart carry no derivative.  The planner's reference rows are inputs of the
- * tick, not functions of the state: their gradient arrives in dGradP for whoever wants it.
+ * tick, not functions of the state: their gradient arrives in dGradP, which cmpc_reference_from_planner_vjp_device carries to the planner's trajectories.
  * Inputs: dGradStateOut[B][9] double, dGradListOut[B][2][max_contacts][3] double or NULL (zero), dGradX[B][n_x] float or NULL (a loss on this tick's solution).
  * Outputs: dGradState[B][9] double (may alias dGradStateOut), dGradPrevList[B][2][max_contacts][3] double (must not alias dGradListOut), dGradWrench[B][N][6]
  * float or NULL (the fExt / tauExt rows of gP, laid out as cmpc_write_state_device's dWrench), dGradPlan or NULL (+=), dGradModel[B][34] double or NULL (+=),

@@ -128,6 +128,11 @@ class CmpcTickDirsOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("dDirStateOut", "dDirList", "dDirListRot", "dDirX", "dDirRot", "dDirPFull")]
 
 
+class CmpcPlannerRefs(C.Structure):
+    """mirror of cmpc_planner_refs (include/cmpc.h): the timing, mass and height of the planner's CoM / angular-momentum trajectories"""
+    _fields_ = [("knots", C.c_int), ("dt", C.c_double), ("t_first", C.c_double), ("robot_mass", C.c_double), ("com_height", C.c_double)]
+
+
 class CmpcModel(C.Structure):
     """mirror of cmpc_model (include/cmpc.h): the per-problem part of cmpc_config, 34 packed doubles"""
     _fields_ = [
@@ -173,6 +178,7 @@ EXPORTS = [
     "cmpc_rollout_walk_vjp_gate_device",
     "cmpc_rollout_walk_jvp_device", "cmpc_rollout_walk_jvp_gate", "cmpc_rollout_walk_jvp_gate_device",
     "cmpc_rollout_walk_vjp_rot_device", "cmpc_rollout_walk_vjp_rot_gate", "cmpc_rollout_walk_vjp_rot_gate_device",
+    "cmpc_reference_from_planner_vjp", "cmpc_reference_from_planner_vjp_device", "cmpc_reference_from_planner_jvp", "cmpc_reference_from_planner_jvp_device",
 ]
 
 _lib = None
@@ -305,6 +311,12 @@ def lib():
             L.cmpc_rollout_walk_jvp_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs), vp]
             L.cmpc_rollout_walk_jvp_gate.argtypes = [C.POINTER(CmpcWalkJvpGate)]
             L.cmpc_rollout_walk_jvp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkJvpGate), vp]
+        if hasattr(L, "cmpc_reference_from_planner_vjp"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            pr = C.POINTER(CmpcPlannerRefs)
+            L.cmpc_reference_from_planner_vjp.argtypes = [i, d, i, i, i, pr, vp, vp, vp, vp]
+            L.cmpc_reference_from_planner_vjp_device.argtypes = [vp, i, i, pr, vp, vp, vp, vp, vp]
+            L.cmpc_reference_from_planner_jvp.argtypes = [i, d, i, i, i, i, pr, vp, vp, vp]
+            L.cmpc_reference_from_planner_jvp_device.argtypes = [vp, i, i, i, pr, vp, vp, vp, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -44,6 +44,8 @@ extern "C" int cmpc_launch_write_state(int B, int N, const float* state, const f
 extern "C" int cmpc_launch_compact(int N, int B, const float* dX, const float* dInfo, float* dOut, hipStream_t stream);
 extern "C" int cmpc_launch_reference_from_planner(int B, int N, int n_in, double dt, double in_dt, double t_offset, double robot_mass, double com_height,
                                                   const float* com_in, const float* h_in, float* P, hipStream_t stream);
+extern "C" int cmpc_launch_reference_vjp(const CmpcRefArgs* a, const int* end_tick, const float* grad_p, double* grad_com, double* grad_h, hipStream_t stream);
+extern "C" int cmpc_launch_reference_jvp(const CmpcRefArgs* a, const double* dir_com, const double* dir_h, float* dir_p, hipStream_t stream);
 extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose, const int* plan_n,
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
@@ -964,6 +966,112 @@ int cmpc_write_reference_from_planner_device(cmpc_handle h, const float* dComIn,
     int rc = cmpc_launch_reference_from_planner(h->B, h->cfg.horizon, n_in, h->cfg.sampling_time, in_dt, t_offset, robot_mass, com_height, dComIn, dHIn, dP,
                                                 stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference resampling launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+// ---- 8f-3 differentiated in the planner's trajectories (include/cmpc.h): the transpose of the resampling summed over the rows of a walk, and its image of
+// k directions.  The rule is cmpc_contacts.h's (cmpc_reference_weight, cmpc_reference_vjp_terms, cmpc_reference_jvp_entry), shared with the kernels. ----
+static bool ref_args(const char* name, cmpc_handle h, int horizon, double sampling_time, int batch, int tick0, int rows, int k, const cmpc_planner_refs* pl,
+                     CmpcRefArgs* a, int* rc)
+{
+    const bool good = pl && horizon >= 1 && horizon <= CMPC_NMAX && sampling_time > 0 && std::isfinite(sampling_time) && batch >= 1 && tick0 >= 0 && rows >= 1 &&
+                      (long long)tick0 + rows <= 2147483647LL && k >= 1 && pl->knots >= 2 && pl->dt > 0 && std::isfinite(pl->dt) && pl->robot_mass > 0 &&
+                      std::isfinite(pl->robot_mass) && std::isfinite(pl->t_first);
+    if (!good) {
+        *rc = fail(h, CMPC_ERR_ARG, std::string(name) + ": bad argument (rows >= 1, tick0 >= 0, k >= 1, knots >= 2, dt and robot_mass positive and finite)");
+        return false;
+    }
+    *a = CmpcRefArgs{horizon, batch, pl->knots, tick0, rows, k, sampling_time, pl->dt, pl->t_first, pl->robot_mass, pl->com_height};
+    return true;
+}
+
+int cmpc_reference_from_planner_vjp(int horizon, double sampling_time, int batch, int tick0, int rows, const cmpc_planner_refs* pl, const int* end_tick,
+                                    const float* grad_p, double* grad_com, double* grad_h)
+{
+    CmpcRefArgs a;
+    int rc = CMPC_OK;
+    if (!ref_args("cmpc_reference_from_planner_vjp", nullptr, horizon, sampling_time, batch, tick0, rows, 1, pl, &a, &rc)) return rc;
+    if (!grad_p || (!grad_com && !grad_h)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp: grad_p and one of grad_com / grad_h are needed");
+    const CmpcIdx L{horizon};
+    const int K1 = horizon + 1, np = L.np(), base = L.pComref();
+    const bool z_fixed = a.com_height == a.com_height;
+    std::vector<int> i0((size_t)rows * K1);
+    std::vector<double> w((size_t)rows * K1);
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < K1; ++k) cmpc_reference_weight(a.knots, a.in_dt, a.t_first, a.dt, tick0 + r, k, &i0[(size_t)r * K1 + k], &w[(size_t)r * K1 + k]);
+    // (in place: an entry's terms arrive in ascending (row, knot) order, which is the order its owner adds them in on the device)
+    for (int b = 0; b < batch; ++b) {
+        const int nr = cmpc_reference_rows_of(end_tick, b, tick0, rows);
+        double* gc = grad_com ? grad_com + (size_t)b * a.knots * 3 : nullptr;
+        double* gh = grad_h ? grad_h + (size_t)b * a.knots * 3 : nullptr;
+        for (int r = 0; r < nr; ++r) {
+            const float* g = grad_p + ((size_t)r * batch + b) * np + base;
+            for (int k = 0; k < K1; ++k) {
+                const int j = i0[(size_t)r * K1 + k];
+                for (int c = 0; c < 3; ++c) {
+                    const bool with_com = !(z_fixed && c == 2);
+                    double tc[2] = {0.0, 0.0}, th[2];
+                    cmpc_reference_vjp_terms(w[(size_t)r * K1 + k], with_com, with_com ? g[3 * k + c] : 0.f, g[3 * K1 + 3 * k + c], a.robot_mass, tc, th);
+                    for (int t = 0; t < 2; ++t) {
+                        if (gc && with_com) gc[3 * (j + t) + c] += tc[t];
+                        if (gh) gh[3 * (j + t) + c] += th[t];
+                    }
+                }
+            }
+        }
+    }
+    return CMPC_OK;
+}
+
+int cmpc_reference_from_planner_vjp_device(cmpc_handle h, int tick0, int rows, const cmpc_planner_refs* pl, const int* dEndTick, const float* dGradP,
+                                           double* dGradCom, double* dGradH, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp_device: null handle");
+    CmpcRefArgs a;
+    int rc = CMPC_OK;
+    if (!ref_args("cmpc_reference_from_planner_vjp_device", h, h->cfg.horizon, h->cfg.sampling_time, h->B, tick0, rows, 1, pl, &a, &rc)) return rc;
+    if (!dGradP || (!dGradCom && !dGradH))
+        return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp_device: dGradP and one of dGradCom / dGradH are needed");
+    if ((a.knots + 127) / 128 > 65535) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp_device: too many knots for one launch");
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = cmpc_launch_reference_vjp(&a, dEndTick, dGradP, dGradCom, dGradH, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference VJP launch: ") + hipGetErrorString((hipError_t)rc));
+    return CMPC_OK;
+}
+
+int cmpc_reference_from_planner_jvp(int horizon, double sampling_time, int batch, int tick0, int rows, int k, const cmpc_planner_refs* pl,
+                                    const double* dir_com, const double* dir_h, float* dir_p)
+{
+    CmpcRefArgs a;
+    int rc = CMPC_OK;
+    if (!ref_args("cmpc_reference_from_planner_jvp", nullptr, horizon, sampling_time, batch, tick0, rows, k, pl, &a, &rc)) return rc;
+    if (!dir_p || (!dir_com && !dir_h)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_reference_from_planner_jvp: dir_p and one of dir_com / dir_h are needed");
+    const CmpcIdx L{horizon};
+    const int per = 6 * (horizon + 1), np = L.np(), base = L.pComref();
+    const size_t cols = (size_t)batch * k;
+    for (int r = 0; r < rows; ++r)
+        for (size_t bk = 0; bk < cols; ++bk) {
+            const size_t in = bk * a.knots * 3;
+            float* out = dir_p + ((size_t)r * cols + bk) * np + base;
+            for (int e6 = 0; e6 < per; ++e6)
+                out[e6] = cmpc_reference_jvp_entry(a, tick0 + r, e6, dir_com ? dir_com + in : nullptr, dir_h ? dir_h + in : nullptr);
+        }
+    return CMPC_OK;
+}
+
+int cmpc_reference_from_planner_jvp_device(cmpc_handle h, int tick0, int rows, int k, const cmpc_planner_refs* pl, const double* dDirCom, const double* dDirH,
+                                           float* dDirP, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_jvp_device: null handle");
+    CmpcRefArgs a;
+    int rc = CMPC_OK;
+    if (!ref_args("cmpc_reference_from_planner_jvp_device", h, h->cfg.horizon, h->cfg.sampling_time, h->B, tick0, rows, k, pl, &a, &rc)) return rc;
+    if (!dDirP || (!dDirCom && !dDirH)) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_jvp_device: dDirP and one of dDirCom / dDirH are needed");
+    const double total = (double)rows * h->B * k * 6.0 * (h->cfg.horizon + 1);
+    if (total / 256.0 > 2147483000.0) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_jvp_device: too many entries for one launch");
+    HIPCHK(h, hipSetDevice(h->device));
+    rc = cmpc_launch_reference_jvp(&a, dDirCom, dDirH, dDirP, stream ? (hipStream_t)stream : h->stream);
+    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference JVP launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
 }
 

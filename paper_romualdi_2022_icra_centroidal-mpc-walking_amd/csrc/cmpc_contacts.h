@@ -177,6 +177,64 @@ __host__ __device__ inline void cmpc_resample_reference_knot(const float* ci, co
     }
 }
 
+// ---- the reference rows differentiated in the planner's trajectories (include/cmpc.h, cmpc_reference_from_planner_vjp / _jvp; DESIGN.md 7f, "References").
+// The map above is linear in (ci, hi); what follows is its weights, its transpose and its image of a direction, one statement each for the host forms and
+// the kernels (contraction into fma is off: the host forms are bit-equal to the kernels).  Tick number `tick` runs at now = tick * dt and reads the
+// trajectories at t_offset = now - t_first, as cmpc_rollout_walk_device does.
+struct CmpcRefArgs {
+    int N, B, knots, tick0, rows, K;     // K: direction columns (the JVP)
+    double dt, in_dt, t_first, robot_mass, com_height;
+};
+// (i0, w) of MPC knot k of tick `tick`: cmpc_resample_reference_knot's arithmetic, clamps included
+__host__ __device__ inline void cmpc_reference_weight(int n_in, double in_dt, double t_first, double dt, int tick, int k, int* i0_out, double* w_out)
+{
+#pragma clang fp contract(off)
+    const double now = (double)tick * dt;
+    const double t_offset = now - t_first;
+    double s = (t_offset + k * dt) / in_dt;
+    if (s < 0) s = 0;
+    if (s > n_in - 1) s = n_in - 1;
+    int i0 = (int)s;
+    if (i0 > n_in - 2) i0 = n_in - 2;
+    *i0_out = i0;
+    *w_out = s - i0;
+}
+// the transpose, one component: what MPC knot (i0, w) sends to planner knot i0 (index 0) and to i0 + 1 (index 1) from the gradients gc / gh of one
+// component of its comRef / hRef entry -- (1 - w) g and w g, for h divided by the mass.  with_com false (the z row under a fixed height): gc is not used.
+// The owner of a planner knot adds these in ascending (row, knot) order.
+__host__ __device__ inline void cmpc_reference_vjp_terms(double w, bool with_com, float gc, float gh, double robot_mass, double* tc, double* th)
+{
+#pragma clang fp contract(off)
+    const double c0 = 1 - w;
+    if (with_com) { tc[0] = c0 * (double)gc; tc[1] = w * (double)gc; }
+    th[0] = (c0 * (double)gh) / robot_mass;
+    th[1] = (w * (double)gh) / robot_mass;
+}
+// the image of a direction: entry e6 of the 6 (N + 1) reference rows (comRef [N + 1][3] | hRef [N + 1][3]) of tick `tick` from one column's dc / dh
+// [knots][3] (either may be null: zero)
+__host__ __device__ inline float cmpc_reference_jvp_entry(const CmpcRefArgs& r, int tick, int e6, const double* dc, const double* dh)
+{
+#pragma clang fp contract(off)
+    const int n3 = 3 * (r.N + 1);
+    const bool is_h = e6 >= n3;
+    const int q = is_h ? e6 - n3 : e6, k = q / 3, a = q - 3 * k;
+    const double* src = is_h ? dh : dc;
+    if (!src || (!is_h && a == 2 && r.com_height == r.com_height)) return 0.f;
+    int i0; double w;
+    cmpc_reference_weight(r.knots, r.in_dt, r.t_first, r.dt, tick, k, &i0, &w);
+    double v = (1 - w) * src[3 * i0 + a] + w * src[3 * (i0 + 1) + a];
+    if (is_h) v = v / r.robot_mass;
+    return (float)v;
+}
+// rows of problem b that the ending rule admits: tick0 + r < e (e < 0: never ended)
+__host__ __device__ inline int cmpc_reference_rows_of(const int* end_tick, int b, int tick0, int rows)
+{
+    const int e = end_tick ? end_tick[b] : -1;
+    if (e < 0) return rows;
+    const long long lim = (long long)e - tick0;
+    return lim <= 0 ? 0 : lim < rows ? (int)lim : rows;
+}
+
 // ---- the walk's record (include/cmpc.h, cmpc_rollout_record): what one tick left of one problem -> its trace row, its outcome and its share of the batch
 // statistics.  One statement for the host form and the kernel, so that the two are bit-equal (contraction into fma is off: the offsets are sums of
 // double products).  Plain pointers, host or device alike.

@@ -366,7 +366,96 @@ __global__ __launch_bounds__(64) void cmpc_reference_from_planner_kernel(int B, 
                                      p + L.pComref() + 3 * k, p + L.pHref() + 3 * k);
 }
 
+// The kernel above in reverse, summed over the rows of a walk (include/cmpc.h, cmpc_reference_from_planner_vjp_device): one workgroup per (problem, tile of
+// 128 planner knots), one lane per planner knot, which owns that knot's six outputs -- no atomics, and the sum in ascending (row, knot) order.  The rows
+// go through LDS in chunks of CMPC_REF_CHUNK.  Staging, one thread per (row, MPC knot, component): it loads the component's comRef / hRef gradient from
+// dGradP (consecutive threads read consecutive floats; the rows are B n_p apart, the problems n_p), forms (i0, w) and leaves the four terms the knot sends
+// to planner knots i0 and i0 + 1 (cmpc_reference_vjp_terms: the products and the divisions by the mass happen here, once, not in the divergent scan) and
+// i0 itself in LDS.  Scan: every lane walks the chunk in (row, knot) order and adds the terms of the knots whose i0 or i0 + 1 it is (all lanes read one
+// i0: a broadcast).  The loop bound is the problem's, so it is uniform over the workgroup, and both barriers sit in it unconditionally: an ended problem
+// runs fewer chunks, nobody returns in front of a barrier.  Rows at or past the problem's end and, with a fixed height, the z entries of comRef are never
+// loaded.  A lane past `knots` stages and waits with the others and touches no output.
+#define CMPC_REF_CHUNK 8
+__global__ __launch_bounds__(128) void cmpc_reference_vjp_kernel(CmpcRefArgs a, const int* __restrict__ end_tick, const float* __restrict__ grad_p,
+                                                                 double* __restrict__ grad_com, double* __restrict__ grad_h)
+{
+    const int b = blockIdx.x, tid = threadIdx.x, j = blockIdx.y * 128 + tid;
+    const CmpcIdx L{a.N};
+    const int K1 = a.N + 1, n3 = 3 * K1, np = L.np(), base = L.pComref();
+    const bool z_fixed = a.com_height == a.com_height;
+    __shared__ double st[CMPC_REF_CHUNK][CMPC_NMAX + 1][2][6];    // [row][knot][to i0 | to i0 + 1][com x y z, h x y z]
+    __shared__ int si[CMPC_REF_CHUNK][CMPC_NMAX + 1];
+    const int rows = cmpc_reference_rows_of(end_tick, b, a.tick0, a.rows);      // (one problem per workgroup: uniform)
+    const bool own = j < a.knots;
+    const size_t o = ((size_t)b * a.knots + (own ? j : 0)) * 3;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (own)
+        for (int i = 0; i < 3; ++i) {
+            if (grad_com) acc[i] = grad_com[o + i];
+            if (grad_h) acc[3 + i] = grad_h[o + i];
+        }
+    for (int r0 = 0; r0 < rows; r0 += CMPC_REF_CHUNK) {
+        const int nr = rows - r0 < CMPC_REF_CHUNK ? rows - r0 : CMPC_REF_CHUNK;
+        for (int q = tid; q < nr * n3; q += 128) {
+            const int rr = q / n3, e3 = q - rr * n3, k = e3 / 3, c = e3 - 3 * k;
+            const float* g = grad_p + ((size_t)(r0 + rr) * a.B + b) * np + base;
+            const bool with_com = !(z_fixed && c == 2);
+            int i0; double w, tc[2] = {0.0, 0.0}, th[2];
+            cmpc_reference_weight(a.knots, a.in_dt, a.t_first, a.dt, a.tick0 + r0 + rr, k, &i0, &w);
+            cmpc_reference_vjp_terms(w, with_com, with_com ? g[e3] : 0.f, g[n3 + e3], a.robot_mass, tc, th);
+            if (c == 0) si[rr][k] = i0;
+            for (int t = 0; t < 2; ++t) { st[rr][k][t][c] = tc[t]; st[rr][k][t][3 + c] = th[t]; }
+        }
+        __syncthreads();
+        if (own)
+            for (int rr = 0; rr < nr; ++rr)
+                for (int k = 0; k < K1; ++k) {
+                    const int i0 = si[rr][k];
+                    if (j != i0 && j != i0 + 1) continue;
+                    const double* t = st[rr][k][j == i0 ? 0 : 1];
+                    for (int c = 0; c < 3; ++c) {
+                        if (!(z_fixed && c == 2)) acc[c] += t[c];
+                        acc[3 + c] += t[3 + c];
+                    }
+                }
+        __syncthreads();
+    }
+    if (own && rows > 0)
+        for (int i = 0; i < 3; ++i) {
+            if (grad_com) grad_com[o + i] = acc[i];
+            if (grad_h) grad_h[o + i] = acc[3 + i];
+        }
+}
+
+// ... and forwards in K columns (cmpc_reference_from_planner_jvp_device): one thread per written entry, (row, problem, column, entry of the 6 (N + 1)
+// reference rows) with the entry fastest, so a wave writes consecutive floats; nothing else of dir_p is touched.  No LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_reference_jvp_kernel(CmpcRefArgs a, const double* __restrict__ dir_com, const double* __restrict__ dir_h,
+                                                                 float* __restrict__ dir_p)
+{
+    const CmpcIdx L{a.N};
+    const size_t per = 6 * (size_t)(a.N + 1), cols = (size_t)a.B * a.K;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)a.rows * cols * per) return;
+    const size_t col = idx / per, r = col / cols, bk = col - r * cols;    // col = (row * B + problem) * K + column
+    const int e6 = (int)(idx - col * per);
+    const size_t in = bk * a.knots * 3;
+    dir_p[col * L.np() + L.pComref() + e6] = cmpc_reference_jvp_entry(a, a.tick0 + (int)r, e6, dir_com ? dir_com + in : nullptr, dir_h ? dir_h + in : nullptr);
+}
+
 }  // namespace
+
+extern "C" int cmpc_launch_reference_vjp(const CmpcRefArgs* a, const int* end_tick, const float* grad_p, double* grad_com, double* grad_h, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_reference_vjp_kernel, dim3(a->B, (a->knots + 127) / 128), dim3(128), 0, stream, *a, end_tick, grad_p, grad_com, grad_h);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_reference_jvp(const CmpcRefArgs* a, const double* dir_com, const double* dir_h, float* dir_p, hipStream_t stream)
+{
+    const size_t total = (size_t)a->rows * a->B * a->K * 6 * (a->N + 1);
+    hipLaunchKernelGGL(cmpc_reference_jvp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, *a, dir_com, dir_h, dir_p);
+    return (int)hipGetLastError();
+}
 
 extern "C" int cmpc_launch_reference_from_planner(int B, int N, int n_in, double dt, double in_dt, double t_offset, double robot_mass, double com_height,
                                                   const float* com_in, const float* h_in, float* P, hipStream_t stream)

@@ -88,6 +88,47 @@ class WalkingRollout:
             t_last = max(c.activation_time for lst in plan.values() for c in lst)
             com_speed = last / t_last if t_last > 0 else 0.0
         self.com_speed = com_speed
+        self.references, self._ref_override = None, None
+
+    def set_references(self, com, h=None, in_dt=None, t_first=0.0, robot_mass=1.0, com_height=0.7):
+        """The planner's CoM and angular-momentum trajectories (what the reference's MANN planner emits besides the footsteps), resampled into the comRef /
+        hRef rows of p by every tick (cmpc_write_reference_from_planner_device; CentroidalMPCBlock.cpp:525-577): com / h [B, n, 3], numpy or CUDA tensors,
+        kept as float32 CUDA tensors; a knot every in_dt seconds, knot 0 at time t_first; h is divided by robot_mass; the CoM height is replaced by
+        com_height unless that is None or NaN.  Once set, run() (both tick paths) and walk_device[_taped]() pass these instead of the straight line at
+        com_speed.  set_references(None) restores that default, and with it every result's bits.  Their gradient: backward_device_refs()."""
+        torch = self.torch
+        if com is None:
+            self.references = None
+            return
+        assert h is not None and in_dt is not None and float(in_dt) > 0 and float(robot_mass) > 0, "set_references(com, h, in_dt, ...)"
+        as32 = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float32))).to(self.dev, torch.float32).contiguous()
+        com, h = as32(com), as32(h)
+        assert com.dim() == 3 and com.shape[0] == self.B and com.shape[1] >= 2 and com.shape[2] == 3 and h.shape == com.shape, \
+            f"set_references: com and h of shape [{self.B}, n >= 2, 3]"
+        self.references = dict(com=com, h=h, in_dt=float(in_dt), t_first=float(t_first), robot_mass=float(robot_mass),
+                               com_height=float("nan") if com_height is None else float(com_height))
+
+    def _planner_refs(self, ticks):
+        """(com, h, in_dt, t_first, robot_mass, com_height) of a walk of `ticks` ticks: what set_references installed, else a straight line at the plan's mean
+        speed and zero angular momentum, a knot every dt from time zero to the end of the last tick's horizon, the CoM height forced to 0.7 as the
+        reference does (CentroidalMPCBlock.cpp:534).  _ref_override = (com, h) (rollout_differentiable's ref_com / ref_h; either None) replaces the
+        trajectories for one call and keeps the timing, mass and height."""
+        torch, B, N, dt, dev = self.torch, self.B, self.cfg.N, self.cfg.sampling_time, self.dev
+        ov = self._ref_override or (None, None)
+        if self.references is not None:
+            r = self.references
+            com, h, rest = r["com"], r["h"], (r["in_dt"], r["t_first"], r["robot_mass"], r["com_height"])
+        else:
+            n_plan = ticks + N + 2 if ov[0] is None and ov[1] is None else int((ov[0] if ov[0] is not None else ov[1]).shape[1])
+            com = torch.zeros((B, n_plan, 3), dtype=torch.float32, device=dev)
+            com[:, :, 0] = (self.com_speed * dt * torch.arange(n_plan, dtype=torch.float64, device=dev)).to(torch.float32)[None, :]
+            h, rest = torch.zeros_like(com), (dt, 0.0, 1.0, 0.7)
+        if ov[0] is not None:
+            com = ov[0]
+        if ov[1] is not None:
+            h = ov[1]
+        assert com.shape == h.shape and tuple(com.shape) == (B, com.shape[1], 3) and com.shape[1] >= 2, "reference trajectories: com and h of one shape [B, n, 3]"
+        return (com, h) + rest
 
     def run(self, *args, **kwargs):
         """The roll-out (see _run for the arguments), with the solver's launch stream as torch's current stream: every device call of a tick -- the library's
@@ -128,7 +169,8 @@ class WalkingRollout:
         """walk_device(ticks, com0, dcom0, h0, **kwargs) through cmpc_rollout_walk_taped_device: every tick also writes its row of a device tape -- what
         backward_device() needs; about 12 KB per problem and tick at N = 20 -- and the dict gains "tape": the stacked tensors X, P, lam_g, info
         [ticks, B, ..], states[ticks + 1, B, 9] (row i the state tick i started from), ok, land, plan_t, list_t, plan_n, list_n, and dt, substeps,
-        force_sample_time, push_ticks, segments (the first tick of each call).  The multiplier output is turned on first, as run(tape=True) does (x and info
+        force_sample_time, push_ticks, segments (the first tick of each call), references (knots, dt, t_first, robot_mass, com_height of the planner's CoM /
+        angular-momentum trajectories: set_references', else the straight line's).  The multiplier output is turned on first, as run(tape=True) does (x and info
         are bit-identical with it on): every other returned array is bit-identical to walk_device's.  Still no host read; works with replan and skip_ended
         (an ended problem's later rows then hold its ending tick's data).  (A method of its own and not an argument of walk_device: that signature is pinned.)"""
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
@@ -168,11 +210,8 @@ class WalkingRollout:
             wrench_ticks = z((push_ticks + 1, B, N, 6))
             for i in range(push_ticks):
                 wrench_ticks[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
-        # the planner's references as in run(): a straight line at the plan's mean speed, a knot every dt from time zero
-        n_plan = ticks + N + 2
-        plan_com = z((B, n_plan, 3))
-        plan_com[:, :, 0] = (self.com_speed * dt * torch.arange(n_plan, dtype=torch.float64, device=dev)).to(torch.float32)[None, :]
-        plan_h = torch.zeros_like(plan_com)
+        # the planner's references as in run(): set_references', else a straight line at the plan's mean speed, a knot every dt from time zero
+        refs = self._planner_refs(ticks)
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         s.outcome_init_device(state, rec)
         tp = None
@@ -192,14 +231,15 @@ class WalkingRollout:
                 plan = replan.get(t0, plan)
                 wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
                 cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
-                                            wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=(plan_com, plan_h, dt, 0.0, 1.0, 0.7),
+                                            wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=refs,
                                             force_sample_time=self.force_sample_time, tape=tp)
         finally:
             if skip_ended:
                 s.set_ended_device(None)
         del rec["_c"]
         if tp is not None:
-            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, segments=starts)
+            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, segments=starts,
+                      references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
             rec["tape"] = tp
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
         return rec
@@ -299,11 +339,9 @@ class WalkingRollout:
         # references (CentroidalMPCBlock.cpp:525-577 resamples the planner's trajectories at the MPC knots): the planner here is a straight line at the plan's mean
         # speed and zero angular momentum, a knot every dt from time zero to the end of the last tick's horizon -- resampled on the device every tick
         # (cmpc_write_reference_from_planner_device; inside cmpc_rollout_tick_device for the warm ticks), CoM height forced to 0.7 as the reference does (:534)
-        n_plan = ticks + N + 2
-        plan_com = torch.zeros((B, n_plan, 3), dtype=torch.float32, device=dev)
-        plan_com[:, :, 0] = (self.com_speed * dt * torch.arange(n_plan, dtype=torch.float64, device=dev)).to(torch.float32)[None, :]
-        plan_h = torch.zeros_like(plan_com)
-        planner = lambda now: (plan_com, plan_h, dt, now, 1.0, 0.7)
+        # -- or the trajectories of set_references(), read at now - t_first as the device walk reads them
+        refs = self._planner_refs(ticks)
+        planner = lambda now: (refs[0], refs[1], refs[2], now - refs[3], refs[4], refs[5])
         import time
         rec = dict(iterations_mean=[], iterations_max=[], converged=[], merge_ok=[], com=[], land=[], landing_offset=[], solve_ms=[], zmp=[],
                    tick_ms=[], retried=[], unconverged=[])
@@ -405,7 +443,8 @@ class WalkingRollout:
         -> dict(state0[B, 9], list0[B, 2, M, 3] (the positions of the first tick's lists), push[B, 3] (the sum of the wrench gradients over the ticks and
         knots the push was written to), wrench[ticks, B, N, 6], models[B, 34], plan[B, 2, M, 3] (the planner's contact positions), status[ticks, B] int32:
         0, or why that tick of that problem passed no gradient on -- include/cmpc.h), float64 but wrench (float32).  The solution map is taken as
-        independent of the warm start; contact times and the planner's CoM references are not differentiated.
+        independent of the warm start; contact times are not differentiated, and the planner's CoM and angular-momentum references only on the device walk:
+        backward_device_refs().
         rot=True (cmpc_rollout_tick_vjp_rot_device per tick): the contacts' orientations too, in the body-frame tangent of their quaternions
         (q <- q (x) exp(omega / 2)): the dict also holds list_rot0[B, 2, M, 3] (the first tick's lists), plan_rot[B, 2, M, 3] (the planner's contacts) and
         rot[ticks, B, 2, N, 3] (each tick's per-stage dl/domega), float64; every other entry is bit-equal to rot=False.  A double-support tick under load
@@ -473,7 +512,17 @@ class WalkingRollout:
         backward_device: that signature is pinned.)"""
         return self._backward_device(w, grad_states, grad_X, True)
 
-    def _backward_device(self, w, grad_states, grad_X, rot):
+    def backward_device_refs(self, w, grad_states, grad_X=None, rot=False):
+        """backward_device() (rot=True: backward_device_rot()) with the gradient of the planner's CoM and angular-momentum trajectories -- the ones
+        set_references() installed, or the default straight line; w["tape"]["references"] says which timing: the reverse walk runs with its grad_p rows on,
+        and ONE call of cmpc_reference_from_planner_vjp_device over all rows with w["end_tick"] carries their comRef / hRef entries through the transpose
+        of every tick's resampling.  Still no host read and no synchronisation.  -> the other method's keys, bit-equal, plus ref_com, ref_h [B, n, 3]
+        float64 and grad_P [ticks, B, n_p] float32 (each tick's full dl/dp; zero rows behind a problem's end).  A problem that ended at tick e contributes
+        its solutions 0 .. e - 1: its later rows of grad_P are not read.  With a fixed CoM height (the default 0.7) ref_com[..., 2] is exactly zero.
+        Times, robot_mass and com_height are not differentiated.  (A method of its own: the signatures of backward_device / _rot are pinned.)"""
+        return self._backward_device(w, grad_states, grad_X, rot, refs=True)
+
+    def _backward_device(self, w, grad_states, grad_X, rot, refs=False):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
@@ -489,6 +538,9 @@ class WalkingRollout:
                    end_tick=w["end_tick"])
         if rot:
             out.update(plan_rot=z((B, 2, M, 3)), rot=z((T, B, 2, N, 3)), removed=z((T, B), torch.float32))
+        if refs:
+            n_ref = tape["references"]["knots"]
+            out.update(grad_P=z((T, B, L.np), torch.float32), ref_com=z((B, n_ref, 3)), ref_h=z((B, n_ref, 3)))
         starts = list(tape["segments"])
         ls = s.launch_stream
         cur = torch.cuda.current_stream(self.dev)
@@ -499,13 +551,15 @@ class WalkingRollout:
             for j in reversed(range(len(starts))):
                 t0, t1 = starts[j], starts[j + 1] if j + 1 < len(starts) else T
                 s.rollout_walk_vjp_device(t0, t1 - t0, tape, t0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, wrench=out["wrench"],
-                                          dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
+                                          grad_p=out.get("grad_P"), dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
                                           grad_rot=out.get("rot"), removed=out.get("removed"))
             for i in reversed(range(min(T, tape["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
                 out["push"] += out["wrench"][i][:, :max(tape["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
             out["state0"], out["list0"] = g, gl
             if rot:
                 out["list_rot0"] = glr
+            if refs:    # (the replan segments share the trajectories: one launch over all rows)
+                s.reference_from_planner_vjp_device(0, T, tape["references"], w["end_tick"], out["grad_P"], out["ref_com"], out["ref_h"])
         cur.wait_stream(ls)
         return out
 
@@ -577,7 +631,22 @@ class WalkingRollout:
         end_tick (w's).  A problem that ended at tick e (w["end_tick"]) keeps the directions of its states 0 .. e and of its solutions 0 .. e - 1
         (include/cmpc.h): its rows e + 1 .. of states, e .. of X and its final list directions are exactly zero, its rows e .. of status 6 and of removed 0,
         whatever its later tape rows or its rows of the directions hold -- not even NaN leaks.  Where nothing ended every entry is bit-equal to
-        run(tape=True) + forward_sensitivity()."""
+        run(tape=True) + forward_sensitivity().  Directions of the planner's reference trajectories too: forward_sensitivity_device_refs()."""
+        return self._forward_sensitivity_device(w, None, None, dir_state0, dir_list0, dir_list_rot0, dir_plan, dir_plan_rot, dir_push, dir_models, dir_wrench,
+                                                solutions)
+
+    def forward_sensitivity_device_refs(self, w, dir_ref_com=None, dir_ref_h=None, **dirs):
+        """forward_sensitivity_device(w, **dirs) with directions of the planner's CoM and angular-momentum trajectories as well: dir_ref_com / dir_ref_h
+        [B, k, n, 3] float64 (CUDA tensors or numpy; None: zero), n = w["tape"]["references"]["knots"].  ONE call of
+        cmpc_reference_from_planner_jvp_device fills the comRef / hRef entries of a zeroed dir_p[ticks, B, k, n_p], which the forward walk reads as every
+        tick's extra p direction.  The same dict comes back; the transpose of backward_device_refs(), input for output; no host read.  (A method of its
+        own: forward_sensitivity_device's signature is pinned.)"""
+        args = inspect.signature(self.forward_sensitivity_device).bind(w, **dirs)
+        args.apply_defaults()
+        return self._forward_sensitivity_device(w, dir_ref_com, dir_ref_h, *args.args[1:], **args.kwargs)
+
+    def _forward_sensitivity_device(self, w, dir_ref_com, dir_ref_h, dir_state0, dir_list0, dir_list_rot0, dir_plan, dir_plan_rot, dir_push, dir_models,
+                                    dir_wrench, solutions):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
@@ -593,7 +662,11 @@ class WalkingRollout:
         ds, dl, dlr = as_dir(dir_state0, f64, (9,)), as_dir(dir_list0, f64, (2, M, 3)), as_dir(dir_list_rot0, f64, (2, M, 3))
         dpl, dplr = as_dir(dir_plan, f64, (2, M, 3)), as_dir(dir_plan_rot, f64, (2, M, 3))
         dpush, dmod, dwr = as_dir(dir_push, f32, (3,)), as_dir(dir_models, f64, (34,)), as_dir(dir_wrench, f32, (N, 6), lead=(T,))
-        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod) if a is not None} | ({int(dwr.shape[2])} if dwr is not None else set())
+        drc = drh = None
+        if dir_ref_com is not None or dir_ref_h is not None:
+            n_ref = tape["references"]["knots"]
+            drc, drh = as_dir(dir_ref_com, f64, (n_ref, 3)), as_dir(dir_ref_h, f64, (n_ref, 3))
+        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod, drc, drh) if a is not None} | ({int(dwr.shape[2])} if dwr is not None else set())
         assert len(ks) == 1, "forward_sensitivity_device: no direction, or directions of different k"
         k = ks.pop()
         rot = dlr is not None or dplr is not None
@@ -615,10 +688,14 @@ class WalkingRollout:
                     dwr[i][:, :, :max(tape["push_ticks"] - i, 1), :3] += dpush[:, :, None, :]
             cl = z((B, k, 2, M, 3)) if dl is None else dl.clone()
             clr = None if not rot else z((B, k, 2, M, 3)) if dlr is None else dlr.clone()
+            dp = None
+            if drc is not None or drh is not None:    # (the replan segments share the trajectories: one launch over all rows)
+                dp = z((T, B, k, L.np), f32)
+                s.reference_from_planner_jvp_device(0, T, k, tape["references"], dp, drc, drh)
             for j, t0 in enumerate(starts):
                 t1 = starts[j + 1] if j + 1 < len(starts) else T
                 s.rollout_walk_jvp_device(t0, t1 - t0, tape, t0, w["end_tick"], k, out["states"], cl, out["status"], carry_list_rot=clr, dir_plan=dpl,
-                                          dir_plan_rot=dplr, dir_wrench=dwr, dir_model=dmod, dir_x=out.get("X"), removed=out["removed"])
+                                          dir_plan_rot=dplr, dir_wrench=dwr, dir_model=dmod, dir_p=dp, dir_x=out.get("X"), removed=out["removed"])
             out["list"] = cl
             out["list_rot"] = clr if rot else z((B, k, 2, M, 3))
         cur.wait_stream(ls)
@@ -680,7 +757,7 @@ def rot_plan_poses(pose, plan_rot):
 
 
 def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None, device_walk=False, replan=None,
-                           plan_rot=None):
+                           plan_rot=None, ref_com=None, ref_h=None):
     """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
     state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
     (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
@@ -704,7 +781,14 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     backward_device_rot with device_walk=True) and plan_rot.grad = Jr(omega)^T (plan_rot + list_rot0), Jr the right Jacobian of SO(3)
     (so3_right_jacobian): q (x) Exp(omega + d) = q (x) Exp(omega) (x) Exp(Jr(omega) d), and the library's gradients are in the body-frame tangent at
     the rotated quaternion.  Its z component at omega = (0, 0, psi) is plan_yaw.grad to the bit.  Forward mode passes Jr(omega) t as dir_plan_rot and
-    dir_list_rot0.  Not together with plan_yaw (ValueError)."""
+    dir_list_rot0.  Not together with plan_yaw (ValueError).
+    ref_com / ref_h: None, or CUDA tensors [B, n, 3]: the planner's CoM / angular-momentum trajectories of this call, in place of the ones
+    rollout.set_references installed (or of the default straight line); their timing, robot_mass and com_height are what it installed, or the default
+    line's (a knot every dt from time zero, mass 1, height 0.7).  The walk reads them as float32.  Only with device_walk=True (NotImplementedError
+    otherwise, before anything touches a GPU): backward is then WalkingRollout.backward_device_refs and returns ref_com.grad / ref_h.grad, forward mode
+    takes their tangents through forward_sensitivity_device_refs.  The fold and select for the rows behind a problem's end are the same."""
+    if (ref_com is not None or ref_h is not None) and not device_walk:
+        raise NotImplementedError("rollout_differentiable: ref_com / ref_h need device_walk=True")
     import torch
 
     if plan_rot is not None and plan_yaw is not None:
@@ -712,7 +796,7 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     if device_walk:
         if plan_yaw is not None:
             raise NotImplementedError("rollout_differentiable(device_walk=True): plan_yaw is not taken on the device path; pass the yaw as plan_rot[..., 2]")
-        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot)
+        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot, ref_com, ref_h)
     if replan is not None:
         raise NotImplementedError("rollout_differentiable: replan needs device_walk=True")
 
@@ -786,19 +870,24 @@ def _jr_applied(jr, t):
     return (jr * t[..., None, :]).sum(-1)
 
 
-def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None):
+def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None, ref_com=None, ref_h=None):
     """rollout_differentiable(device_walk=True)"""
     import torch
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, state0, push, models, plan_rot):
+        def forward(ctx, state0, push, models, plan_rot, ref_com, ref_h):
             if models is not None:
                 rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
             s0 = state0.detach().to(rollout.dev, torch.float32)
             plan, plans = rollout.plan, replan
             ctx.jr = None
+            ctx.refs = ref_com is not None or ref_h is not None
+            ctx.ref_dtypes = (None if ref_com is None else ref_com.dtype, None if ref_h is None else ref_h.dtype)
+            as32 = lambda a: None if a is None else a.detach().to(rollout.dev, torch.float32).contiguous()
+            if ctx.refs:
+                rollout._ref_override = (as32(ref_com), as32(ref_h))
             if plan_rot is not None:     # (the planner's contacts of every segment turn by the same vectors: the one plan_rot buffer sums over them)
                 om = plan_rot.detach().to(rollout.dev, torch.float64)
                 assert tuple(om.shape) == tuple(plan[1].shape[:3]) + (3,), f"plan_rot: expected {tuple(plan[1].shape[:3]) + (3,)}"
@@ -811,6 +900,7 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
                                               replan=plans, trace=False)
             finally:
                 rollout.plan = plan
+                rollout._ref_override = None
             rollout.last_walk = ctx.walk = w
             ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
             e = w["end_tick"]
@@ -824,26 +914,35 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             g = gStates.to(rollout.dev, torch.float64)
             folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
             g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
-            r = rollout.backward_device(ctx.walk, g) if ctx.jr is None else rollout.backward_device_rot(ctx.walk, g)
+            if ctx.refs:
+                r = rollout.backward_device_refs(ctx.walk, g, rot=ctx.jr is not None)
+            else:
+                r = rollout.backward_device(ctx.walk, g) if ctx.jr is None else rollout.backward_device_rot(ctx.walk, g)
             rollout.last_backward = r
             return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
                     r["models"] if ctx.needs_input_grad[2] else None,
-                    _jr_transposed(ctx.jr, r["plan_rot"] + r["list_rot0"]) if ctx.jr is not None and ctx.needs_input_grad[3] else None)
+                    _jr_transposed(ctx.jr, r["plan_rot"] + r["list_rot0"]) if ctx.jr is not None and ctx.needs_input_grad[3] else None,
+                    r["ref_com"].to(ctx.ref_dtypes[0]) if ctx.ref_dtypes[0] is not None and ctx.needs_input_grad[4] else None,
+                    r["ref_h"].to(ctx.ref_dtypes[1]) if ctx.ref_dtypes[1] is not None and ctx.needs_input_grad[5] else None)
 
         @staticmethod
-        def jvp(ctx, t_state0, t_push, t_models, t_rot):
+        def jvp(ctx, t_state0, t_push, t_models, t_rot, t_ref_com, t_ref_h):
             """torch.autograd.forward_ad: forward_sensitivity_device at k = 1 on the tape the forward left.  The returned states hold final_state in the
             rows behind a problem's end, so those rows take the tangent of the row its final state sits in: the transpose of backward's fold."""
             col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
-            if all(t is None for t in (t_state0, t_push, t_models, t_rot)):
+            if all(t is None for t in (t_state0, t_push, t_models, t_rot, t_ref_com, t_ref_h)):
                 return torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
             drot = None if t_rot is None else _jr_applied(ctx.jr, t_rot.detach().to(rollout.dev, torch.float64))[:, None].contiguous()
-            r = rollout.forward_sensitivity_device(ctx.walk, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
-                                                   dir_models=col(t_models, torch.float64), dir_plan_rot=drot, dir_list_rot0=drot)
+            dirs = dict(dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32), dir_models=col(t_models, torch.float64),
+                        dir_plan_rot=drot, dir_list_rot0=drot)
+            if t_ref_com is not None or t_ref_h is not None:
+                r = rollout.forward_sensitivity_device_refs(ctx.walk, dir_ref_com=col(t_ref_com, torch.float64), dir_ref_h=col(t_ref_h, torch.float64), **dirs)
+            else:
+                r = rollout.forward_sensitivity_device(ctx.walk, **dirs)
             rollout.last_forward = r
             t = r["states"][:, :, 0]
             e = ctx.walk["end_tick"].to(torch.int64).clamp(min=0)
             at_end = t.gather(0, e[None, :, None].expand(1, rollout.B, 9))      # [1, B, 9]: each problem's row e (row 0 where it never ended: not selected)
             return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
-    return _Fn.apply(state0, push, models, plan_rot)
+    return _Fn.apply(state0, push, models, plan_rot, ref_com, ref_h)

@@ -958,6 +958,35 @@ class BatchSolver:
         dev = torch.device("cuda", self._device_index) if device is None else device
         self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_jvp_gate_device(self._h, C.byref(gate), st))
 
+    @staticmethod
+    def planner_refs(knots, dt, t_first=0.0, robot_mass=1.0, com_height=0.7):
+        """a _capi.CmpcPlannerRefs (cmpc_planner_refs, include/cmpc.h); com_height None: NaN, the trajectory's own z row"""
+        return _capi.CmpcPlannerRefs(int(knots), float(dt), float(t_first), float(robot_mass), float("nan") if com_height is None else float(com_height))
+
+    def reference_from_planner_vjp_device(self, tick0, rows, refs, end_tick, grad_p, grad_com=None, grad_h=None):
+        """cmpc_reference_from_planner_vjp_device: the reference rows of grad_p[rows, B, n_p] float32 (row r = tick tick0 + r; the reverse walk's grad_p)
+        carried to the planner's trajectories in ONE launch: grad_com / grad_h[B, knots, 3] float64 are ADDED TO (either may be None, not both).
+        refs: planner_refs(...) or a dict of its arguments; end_tick: int32 [B] (a walk record's) or None -- rows at or past a problem's end are not read."""
+        import torch
+        if isinstance(refs, dict):
+            refs = self.planner_refs(**refs)
+        B, L, n = self.batch, self.layout, int(refs.knots)
+        gp = self._opt(grad_p, torch.float32, (int(rows), B, L.np), "grad_p")
+        gc, gh = self._opt(grad_com, torch.float64, (B, n, 3), "grad_com"), self._opt(grad_h, torch.float64, (B, n, 3), "grad_h")
+        e = self._opt(end_tick, torch.int32, (B,), "end_tick")
+        self._launch(grad_p.device, lambda st: self._lib.cmpc_reference_from_planner_vjp_device(self._h, int(tick0), int(rows), C.byref(refs), e, gp, gc, gh, st))
+
+    def reference_from_planner_jvp_device(self, tick0, rows, k, refs, dir_p, dir_com=None, dir_h=None):
+        """cmpc_reference_from_planner_jvp_device: dir_com / dir_h[B, k, knots, 3] float64 (either may be None: zero, not both) -> the comRef / hRef entries of
+        dir_p[rows, B, k, n_p] float32 (row r = tick tick0 + r; rollout_walk_jvp_device's dir_p), written; every other entry of dir_p is left alone."""
+        import torch
+        if isinstance(refs, dict):
+            refs = self.planner_refs(**refs)
+        B, L, n, k = self.batch, self.layout, int(refs.knots), int(k)
+        dp = self._opt(dir_p, torch.float32, (int(rows), B, k, L.np), "dir_p")
+        dc, dh = self._opt(dir_com, torch.float64, (B, k, n, 3), "dir_com"), self._opt(dir_h, torch.float64, (B, k, n, 3), "dir_h")
+        self._launch(dir_p.device, lambda st: self._lib.cmpc_reference_from_planner_jvp_device(self._h, int(tick0), int(rows), k, C.byref(refs), dc, dh, dp, st))
+
     def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
                             wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
                             tape=None, tape_row0=None):
