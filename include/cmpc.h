@@ -939,6 +939,46 @@ int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts
  * output must be on: else CMPC_ERR_ARG. */
 int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                    int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream);
+/* ---- the state of a walk between two ticks: save, restore, branch ("Snapshots") ----
+ * cmpc_walk_snapshot: everything tick `tick` of a walk reads that an earlier tick wrote, in device arrays the caller owns (BatchSolver.walk_snapshot
+ * allocates them), M = max_contacts:
+ *     dState[B][9], dP[B][n_p] (its wrench rows survive the ticks past wrench_ticks, so it belongs), dX[B][n_x], dX0[B][n_x], dInfo[B][CMPC_INFO], dZmp[B][2]   float
+ *     dOk[B], dLand[B][2]                                                                    int
+ *     both list sets, set 0 = dListT / dListPose / dListN, set 1 = dListTB / dListPoseB / dListNB (the sets of cmpc_walk_io):
+ *     t[B][2][M][2] double, pose[B][2][M][7] float, n[B][2] int, twice
+ *     the six outcome arrays of cmpc_walk_record: dEndTick, dEndCode, dIterationsSum, dIterationsMax [B] int, dFinalState[B][9], dBoxSlackMin[B] float
+ * and two host words: `tick`, the number of the next tick, and `lists_in`, the set that holds the lists of the tick before it (cmpc_rollout_walk_device's
+ * argument of that name).  dX0, dInfo and dZmp may be NULL, in the source or in the destination, and are then skipped: a walking problem's next tick
+ * overwrites all three before it reads them; they are in the struct so that an ENDED problem's rows of a resumed walk equal the unbroken walk's.  The
+ * trace and the statistics of a record are not part of it (a resumed walk writes its own rows), nor is anything in the handle: a tick reads nothing of an
+ * earlier tick through the handle (the box, the models and the warm policy are settings, the same in every tick).
+ * The live buffers of a walk are described by the same struct, so ONE copy serves as save (live -> snapshot) and as restore (snapshot -> live).
+ * Size: 4 (2 n_x + n_p) + 176 M + 160 bytes per problem (the three wide rows; 2 x (32 M + 56 M + 8) of lists; state 36, info 32, zmp 8, ok 4, land 8; the
+ * outcome 4 x 4 + 36 + 4), about 13 KB at N = 20 -- one row of the tape above: cmpc_walk_snapshot_bytes.
+ * cmpc_rollout_snapshot_device: ONE launch, asynchronous on `stream` (NULL: the handle's), no host read.  Destination problem b (b < the handle's batch)
+ * receives the bit copy of source problem dIndex[b] (dIndex: [B] device ints; NULL: source problem b, and src_batch must then equal the batch); the source
+ * arrays hold src_batch problems.  An index outside [0, src_batch) leaves that destination problem entirely unwritten and sets dOk[b] = 0 when dOk ([B]
+ * device ints, or NULL) is given, otherwise dOk[b] = 1: the idiom of cmpc_set_models_device.  Repeated indices are the normal case of branching.  The
+ * host words of dst are the caller's to set.  One workgroup per destination problem; the index is read once per row; the rows of 64 words and more go as
+ * 16-byte pieces aligned on the destination, with a head and a tail of single words (n_x and n_p are not multiples of four floats at every N); no LDS,
+ * no barrier, no atomics.
+ * CMPC_ERR_ARG: a NULL handle, src or dst; a NULL required pointer (every array but dX0, dInfo, dZmp) in either; max_contacts < 1; src_batch < 1;
+ * dIndex == NULL with src_batch != batch; any destination array that is also a source array. */
+typedef struct cmpc_walk_snapshot {
+    int tick; int lists_in;
+    float* dState; float* dP; float* dX; float* dX0; float* dInfo; float* dZmp;
+    int* dOk; int* dLand;
+    double* dListT; float* dListPose; int* dListN;
+    double* dListTB; float* dListPoseB; int* dListNB;
+    int* dEndTick; int* dEndCode; int* dIterationsSum; int* dIterationsMax; float* dFinalState; float* dBoxSlackMin;
+} cmpc_walk_snapshot;
+int cmpc_rollout_snapshot_device(cmpc_handle h, int max_contacts, int src_batch, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
+                                 const int* dIndex, int* dOk, void* stream);
+/* the same on the host: host buffers throughout; no handle, no GPU.  Bit-equal to the kernel. */
+int cmpc_rollout_snapshot(int horizon, int batch, int src_batch, int max_contacts, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
+                          const int* index, int* ok);
+/* bytes per problem of a snapshot with all its arrays (the formula above); 0 for horizon < 1 or max_contacts < 1 */
+size_t cmpc_walk_snapshot_bytes(int horizon, int max_contacts);
 /* The reverse walk: `ticks` calls of cmpc_rollout_tick_vjp_device (called, not copied: its workspace, statuses and zero rule for flagged problems hold),
  * last row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of cmpc_walk_vjp_gate_kernel).  Tick number tick0 + i is row
  * row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time.

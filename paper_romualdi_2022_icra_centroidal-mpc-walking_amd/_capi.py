@@ -79,6 +79,13 @@ class CmpcWalkTape(C.Structure):
         ("plant_step", C.c_double), ("plant_substeps", C.c_int), ("force_sample_time", C.c_int), ("first_row_is_first_tick", C.c_int)]
 
 
+class CmpcWalkSnapshot(C.Structure):
+    """mirror of cmpc_walk_snapshot (include/cmpc.h): the state of a walk between two ticks -- also the description of a walk's live buffers"""
+    _fields_ = [("tick", C.c_int), ("lists_in", C.c_int)] + [(k, C.c_void_p) for k in (
+        "dState", "dP", "dX", "dX0", "dInfo", "dZmp", "dOk", "dLand", "dListT", "dListPose", "dListN", "dListTB", "dListPoseB", "dListNB",
+        "dEndTick", "dEndCode", "dIterationsSum", "dIterationsMax", "dFinalState", "dBoxSlackMin")]
+
+
 class CmpcWalkGrads(C.Structure):
     """mirror of cmpc_walk_grads (include/cmpc.h): the seeds, carries and outputs of cmpc_rollout_walk_vjp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -179,6 +186,7 @@ EXPORTS = [
     "cmpc_rollout_walk_jvp_device", "cmpc_rollout_walk_jvp_gate", "cmpc_rollout_walk_jvp_gate_device",
     "cmpc_rollout_walk_vjp_rot_device", "cmpc_rollout_walk_vjp_rot_gate", "cmpc_rollout_walk_vjp_rot_gate_device",
     "cmpc_reference_from_planner_vjp", "cmpc_reference_from_planner_vjp_device", "cmpc_reference_from_planner_jvp", "cmpc_reference_from_planner_jvp_device",
+    "cmpc_rollout_snapshot", "cmpc_rollout_snapshot_device", "cmpc_walk_snapshot_bytes",
 ]
 
 _lib = None
@@ -317,6 +325,12 @@ def lib():
             L.cmpc_reference_from_planner_vjp_device.argtypes = [vp, i, i, pr, vp, vp, vp, vp, vp]
             L.cmpc_reference_from_planner_jvp.argtypes = [i, d, i, i, i, i, pr, vp, vp, vp]
             L.cmpc_reference_from_planner_jvp_device.argtypes = [vp, i, i, i, pr, vp, vp, vp, vp]
+        if hasattr(L, "cmpc_rollout_snapshot_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            sp = C.POINTER(CmpcWalkSnapshot)
+            L.cmpc_rollout_snapshot_device.argtypes = [vp, i, i, sp, sp, vp, vp, vp]
+            L.cmpc_rollout_snapshot.argtypes = [i, i, i, i, sp, sp, vp, vp]
+            L.cmpc_walk_snapshot_bytes.argtypes = [i, i]
+            L.cmpc_walk_snapshot_bytes.restype = C.c_size_t
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -61,6 +61,7 @@ extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tic
                                         float* slack_min, hipStream_t stream);
 extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
+extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
 extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a);
 extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t stream);
@@ -1640,6 +1641,72 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
     h->timing = timing;
     if (rc == CMPC_OK && lists_out) *lists_out = cur;
     return rc;
+}
+
+// ---- the snapshot of a walk (include/cmpc.h, cmpc_walk_snapshot): one copy kernel, destination problem b <- source problem index[b] ----
+size_t cmpc_walk_snapshot_bytes(int horizon, int max_contacts)
+{
+    if (horizon < 1 || max_contacts < 1) return 0;
+    CmpcLayout L;
+    cmpc_layout_init(L, horizon);
+    return sizeof(float) * (2 * (size_t)L.nx + L.np) + 176 * (size_t)max_contacts + 160;
+}
+
+// the table of arrays both sides have, as rows of 32-bit words; false: a required pointer is NULL, or a destination array is also a source array
+static bool snapshot_args(int N, int B, int src_B, int M, const cmpc_walk_snapshot* s, const cmpc_walk_snapshot* d, const int* index, int* ok, CmpcSnapshotArgs& a)
+{
+    if (N < 1 || B < 1 || src_B < 1 || M < 1 || !s || !d || (!index && src_B != B)) return false;
+    CmpcLayout L;
+    cmpc_layout_init(L, N);
+    a.B = B; a.src_B = src_B; a.count = 0; a.index = index; a.ok = ok;
+    bool complete = true;
+    auto add = [&](const void* sp, void* dp, int words, bool optional) {
+        if (!sp || !dp) { complete = complete && optional; return; }
+        a.src[a.count] = static_cast<const unsigned*>(sp); a.dst[a.count] = static_cast<unsigned*>(dp); a.words[a.count] = words;
+        ++a.count;
+    };
+    add(s->dState, d->dState, 9, false); add(s->dP, d->dP, L.np, false); add(s->dX, d->dX, L.nx, false); add(s->dX0, d->dX0, L.nx, true);
+    add(s->dInfo, d->dInfo, CMPC_INFO, true); add(s->dZmp, d->dZmp, 2, true); add(s->dOk, d->dOk, 1, false); add(s->dLand, d->dLand, 2, false);
+    add(s->dListT, d->dListT, 8 * M, false); add(s->dListPose, d->dListPose, 14 * M, false); add(s->dListN, d->dListN, 2, false);
+    add(s->dListTB, d->dListTB, 8 * M, false); add(s->dListPoseB, d->dListPoseB, 14 * M, false); add(s->dListNB, d->dListNB, 2, false);
+    add(s->dEndTick, d->dEndTick, 1, false); add(s->dEndCode, d->dEndCode, 1, false); add(s->dIterationsSum, d->dIterationsSum, 1, false);
+    add(s->dIterationsMax, d->dIterationsMax, 1, false); add(s->dFinalState, d->dFinalState, 9, false); add(s->dBoxSlackMin, d->dBoxSlackMin, 1, false);
+    if (!complete) return false;
+    for (int i = 0; i < a.count; ++i)
+        for (int j = 0; j < a.count; ++j)
+            if (a.dst[i] == a.src[j]) return false;
+    return true;
+}
+
+int cmpc_rollout_snapshot(int horizon, int batch, int src_batch, int max_contacts, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
+                          const int* index, int* ok)
+{
+    CmpcSnapshotArgs a;
+    if (!snapshot_args(horizon, batch, src_batch, max_contacts, src, dst, index, ok, a))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_snapshot: bad argument (a NULL array, sizes, or a destination array that is also a source array)");
+    for (int b = 0; b < batch; ++b) {
+        const int s = cmpc_snapshot_source(a, b);
+        if (ok) ok[b] = s >= 0 ? 1 : 0;
+        if (s < 0) continue;
+        for (int i = 0; i < a.count; ++i) {
+            const size_t w = (size_t)a.words[i];
+            std::memcpy(a.dst[i] + w * b, a.src[i] + w * s, sizeof(unsigned) * w);
+        }
+    }
+    return CMPC_OK;
+}
+
+int cmpc_rollout_snapshot_device(cmpc_handle h, int max_contacts, int src_batch, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
+                                 const int* dIndex, int* dOk, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_snapshot_device: null handle");
+    CmpcSnapshotArgs a;
+    if (!snapshot_args(h->cfg.horizon, h->B, src_batch, max_contacts, src, dst, dIndex, dOk, a))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_snapshot_device: bad argument (a NULL array, sizes, or a destination array that is also a source array)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_rollout_snapshot(&a, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("walk snapshot launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
 }
 
 // ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags

@@ -331,6 +331,21 @@ struct CmpcTapeArgs {
     float* t_X; float* t_P; float* t_info; float* t_states; int* t_ok; int* t_land; double* t_plan_t; double* t_list_t; int* t_plan_n; int* t_list_n;
 };
 
+// ---- the snapshot of a walk (include/cmpc.h, cmpc_walk_snapshot): destination problem b <- source problem index[b], bit copies.  Every array goes as
+// rows of 32-bit words (a double is two); the table lists the arrays both sides have, at most CMPC_SNAP_ARRAYS = the 20 of the struct.
+#define CMPC_SNAP_ARRAYS 20
+struct CmpcSnapshotArgs {
+    int B, src_B, count;
+    const int* index; int* ok;                     // either may be null
+    const unsigned* src[CMPC_SNAP_ARRAYS]; unsigned* dst[CMPC_SNAP_ARRAYS]; int words[CMPC_SNAP_ARRAYS];   // words: per problem
+};
+// the source problem of destination b, or -1: b itself without an index, else index[b] where it lies in [0, src_B)
+__host__ __device__ inline int cmpc_snapshot_source(const CmpcSnapshotArgs& a, int b)
+{
+    const int s = a.index ? a.index[b] : b;
+    return s >= 0 && s < a.src_B ? s : -1;
+}
+
 // ---- the reverse walk's rule for ended problems (include/cmpc.h, cmpc_rollout_walk_vjp_device).  One statement for the host form and the
 // kernel (contraction off: the one sum is a plain double add).  A gate step sits between two reverse ticks: its POST part finishes tick `tick_post`
 // (row_post) from what cmpc_rollout_tick_vjp_device left, its PRE part prepares tick `tick_pre` (row_pre).  Either part may be absent (do_post / do_pre).

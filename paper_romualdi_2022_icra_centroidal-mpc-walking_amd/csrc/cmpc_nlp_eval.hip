@@ -1661,6 +1661,39 @@ __global__ __launch_bounds__(256) void cmpc_rollout_tape_kernel(CmpcTapeArgs a)
     tape_copy(a.t_list_n + r * B * 2, a.list_n, B * 2, tid, stride);
 }
 
+// snapshot (cmpc_rollout_snapshot_device): one workgroup per destination problem, so the source index is one uniform read per row and every array's row
+// of that problem is a contiguous piece.  Rows of 64 words and more (x, p, x0, the lists' times and poses from M = 2 on) go as 16-byte pieces aligned on the
+// DESTINATION: n_x and n_p are not multiples of four floats at every N, so a row starts 0 .. 3 words short of a 16-byte line -- those words and the tail
+// go one by one.  The source row sits at another problem's offset and need not share the alignment: its 16-byte loads are declared 4-byte aligned.
+// Bandwidth-bound (13 KB in, 13 KB out per problem): no LDS, no barrier, no atomics.
+typedef unsigned snap_u32x4 __attribute__((ext_vector_type(4)));
+typedef snap_u32x4 snap_u32x4_a4 __attribute__((aligned(4)));
+__device__ inline void snap_row(unsigned* __restrict__ d, const unsigned* __restrict__ s, int w, int tid)
+{
+    if (w < 64) {
+        for (int e = tid; e < w; e += 256) d[e] = s[e];
+        return;
+    }
+    const int head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(d) & 15u)) & 15u) >> 2);   // words in front of the first aligned line
+    const int nv = (w - head) >> 2, tail0 = head + 4 * nv;
+    if (tid < head) d[tid] = s[tid];
+    snap_u32x4* dv = reinterpret_cast<snap_u32x4*>(d + head);
+    const snap_u32x4_a4* sv = reinterpret_cast<const snap_u32x4_a4*>(s + head);
+    for (int e = tid; e < nv; e += 256) dv[e] = sv[e];
+    if (tid < w - tail0) d[tail0 + tid] = s[tail0 + tid];
+}
+__global__ __launch_bounds__(256) void cmpc_rollout_snapshot_kernel(CmpcSnapshotArgs a)
+{
+    const int b = blockIdx.x;   // (the grid is B workgroups: nothing runs past B)
+    const int s = cmpc_snapshot_source(a, b);
+    if (a.ok && threadIdx.x == 0) a.ok[b] = s >= 0 ? 1 : 0;
+    if (s < 0) return;          // (uniform) a bad index: the problem stays unwritten
+    for (int i = 0; i < a.count; ++i) {
+        const size_t w = (size_t)a.words[i];
+        snap_row(a.dst[i] + w * b, a.src[i] + w * s, a.words[i], threadIdx.x);
+    }
+}
+
 // gate: one thread per problem for the small arrays (cmpc_walk_gate_problem; lanes past B do nothing), then every thread strides over the wide rows
 // (cmpc_walk_gate_wide).  The two parts touch disjoint arrays: no barrier, no atomics.
 __global__ __launch_bounds__(256) void cmpc_walk_vjp_gate_kernel(CmpcGateArgs a, size_t wide)
@@ -1693,6 +1726,12 @@ extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t strea
 {
     const size_t work = (a->parts & 2) ? (size_t)a->B * (a->nx > a->np ? a->nx : a->np) : (size_t)a->B * 9;
     hipLaunchKernelGGL(cmpc_rollout_tape_kernel, dim3(stride_blocks(1, work)), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_rollout_snapshot_kernel, dim3(a->B), dim3(256), 0, stream, *a);
     return (int)hipGetLastError();
 }
 

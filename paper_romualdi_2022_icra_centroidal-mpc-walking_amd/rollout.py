@@ -37,6 +37,18 @@ def walking_plan(cfg, steps=6, step_length=0.1, swing=0.48, double_support=0.12,
     return {names[0]: feet[0], names[1]: feet[1]}
 
 
+def walk_schedule(ticks, every, replan=(), tick0=0):
+    """The calls of a checkpointed walk of ticks tick0 .. tick0 + ticks - 1 -- a pure function.  The walk is cut at the multiples of `every` (tick numbers,
+    not counted from tick0) and at the replan ticks that lie strictly inside it.  -> (calls, snapshots): calls = [(t0, t1), ...], half-open and in order;
+    snapshots = the ticks k * every, k >= 1, strictly inside the walk: each is the first tick of a call, and the snapshot is taken in front of it.
+    every None, or at or beyond the walk's end: no snapshot."""
+    tick0, end = int(tick0), int(tick0) + int(ticks)
+    assert ticks >= 1 and tick0 >= 0 and (every is None or int(every) >= 1), "walk_schedule: ticks >= 1, tick0 >= 0, every >= 1"
+    snaps = [] if every is None else [t for t in range(int(every), end, int(every)) if t > tick0]
+    cuts = sorted({tick0, end} | set(snaps) | {int(t) for t in replan if tick0 < int(t) < end})
+    return list(zip(cuts[:-1], cuts[1:])), snaps
+
+
 class WalkingRollout:
     """warm_budget / retry: what a warm-started problem that does not converge costs its tick (include/cmpc.h, cmpc_set_warm_policy).
     warm_budget = iterations of the warm-started pass (0: the full budget; 14 = the library's default); retry = "kernel": such a problem starts again from the cold
@@ -563,6 +575,260 @@ class WalkingRollout:
         cur.wait_stream(ls)
         return out
 
+    # ---- snapshots: resume, branch, and the reverse walk in bounded memory (include/cmpc.h, cmpc_walk_snapshot; DESIGN.md 7f, "Snapshots") ----
+    def _queued(self, fn):
+        """fn() with the solver's launch stream as torch's current stream, as walk_device queues its ticks"""
+        torch = self.torch
+        assert self.retry != "launch", "the device walk needs retry='kernel' or None"
+        ls = self.solver.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        try:
+            with torch.cuda.stream(ls):
+                return fn()
+        finally:
+            cur.wait_stream(ls)
+
+    def _live_buffers(self, rec):
+        """the live buffers of a walk described as a snapshot (BatchSolver.walk_snapshot), zero-filled; the outcome arrays are rec's"""
+        keys = ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min")
+        live = self.solver.walk_snapshot(0, 0, self.M, device=self.dev, tensors={k: rec[k] for k in keys})
+        live["rec"] = rec
+        return live
+
+    def _live_reset(self, live, state0, plan0):
+        """the live buffers as walk_device has them in front of tick 0: zeros, ok = 1, the plan in list set 0, the outcome at its start"""
+        for k in ("P", "X", "X0", "info", "zmp", "land"):
+            live[k].zero_()
+        live["ok"].fill_(1)
+        live["state"].copy_(state0)
+        for d, a in zip(live["lists"][0], plan0):
+            d.copy_(a)
+        for d in live["lists"][1]:
+            d.zero_()
+        self.solver.outcome_init_device(live["state"], live["rec"])
+        self.solver.walk_snapshot_mark(live, 0, 0)
+
+    def _push_schedule(self, dpush, push_ticks):
+        """run()'s schedule as rows of wrench_ticks: the push on the first max(push_ticks - i, 1) knots of row i < push_ticks, zeros once in row push_ticks"""
+        wt = self.torch.zeros((push_ticks + 1, self.B, self.cfg.N, 6), dtype=self.torch.float32, device=self.dev)
+        for i in range(push_ticks):
+            wt[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
+        return wt
+
+    def _walk_live(self, live, t0, t1, row_shift, plans, base_plan, wrench, refs, skip_ended, every=None, tape=None, tape_shift=0, cold=False, states=None):
+        """Queues ticks t0 .. t1 - 1 on the live buffers (a snapshot dict whose "rec" is the walk record): one call of the C ABI per entry of
+        walk_schedule, a snapshot launch in front of each tick k * every.  Record row = tick - row_shift, tape row = tick - tape_shift.  plans {tick:
+        plan}: the latest entry at or before a tick is the plan in force (none: base_plan).  wrench = (wrench_ticks[T, B, N, 6], the tick of its row 0) or
+        None.  states[.., B, 9]: the walk is cut at every tick and row tick + 1 - row_shift receives the state that tick left.  -> {tick: snapshot}"""
+        s, dt, rec = self.solver, self.cfg.sampling_time, live["rec"]
+        calls, snaps = walk_schedule(t1 - t0, every, plans, t0)
+        if states is not None:
+            calls = [(t, t + 1) for t in range(t0, t1)]
+        plan_at = lambda t: plans[max(k for k in plans if k <= t)] if any(k <= t for k in plans) else base_plan
+        cur, out, sets = live["lists_in"], {}, live["lists"]
+        if skip_ended:    # (the queued launches keep the pointer; the tensor outlives them in the walk's dict)
+            s.set_ended_device(live["end_tick"])
+        try:
+            for a, b in calls:
+                if a in snaps:
+                    s.walk_snapshot_mark(live, a, cur)
+                    out[a] = s.rollout_snapshot_device(live, s.walk_snapshot(a, cur, self.M, device=self.dev))
+                wr = wrench[0][a - wrench[1]:] if wrench is not None and a - wrench[1] < wrench[0].shape[0] else None
+                cur = s.rollout_walk_device(a, b - a, cold and a == t0, plan_at(a), sets[0], sets[1], cur, live["ok"], live["land"], live["state"], live["P"],
+                                            live["X0"], live["X"], live["info"], live["zmp"], rec, row0=a - row_shift, wrench_ticks=wr,
+                                            step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
+                                            tape=tape, tape_row0=a - tape_shift)
+                if states is not None:
+                    states[b - row_shift].copy_(live["state"])
+        finally:
+            if skip_ended:
+                s.set_ended_device(None)
+        s.walk_snapshot_mark(live, t1, cur)
+        return out
+
+    def walk_device_checkpointed(self, ticks, com0, dcom0, h0, every, **kwargs):
+        """walk_device(ticks, com0, dcom0, h0, **kwargs) cut into calls at the multiples of `every` and at the replan ticks (walk_schedule), with ONE
+        snapshot launch (cmpc_rollout_snapshot_device, include/cmpc.h) in front of each tick k * every, k >= 1.  -> walk_device's dict, bit-equal in
+        every key, plus "checkpoints" {tick: snapshot} (BatchSolver.walk_snapshot: everything that tick reads of the ticks before it, about 13 KB per
+        problem at N = 20) and "inputs", the small things a re-run needs, by reference: state0, the wrench schedule and push_ticks, the plans of replan
+        and the plan in force at tick 0, the references, stop, skip_ended, ticks, every.  Like walk_device: no host read and no synchronisation.
+        Continue or fork from a checkpoint: walk_resume_device().  The gradient without a whole-walk tape: backward_device_checkpointed()."""
+        args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
+        args.apply_defaults()
+        return self._queued(lambda: self._walk_checkpointed(every, None, *args.args, **args.kwargs))
+
+    def _walk_checkpointed(self, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended):
+        torch, dev, s = self.torch, self.dev, self.solver
+        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
+
+        def up(a):
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, torch.float32)
+            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+            return hold[-1].to(dev, non_blocking=True)
+        state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
+        wrench = (self._push_schedule(up(push), push_ticks), 0) if push is not None else None
+        refs = self._planner_refs(ticks)
+        rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
+        live = self._live_buffers(rec)
+        plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < ticks}
+        self._live_reset(live, state0, plans.get(0, self.plan))
+        if states is not None:
+            states[0].copy_(state0)
+        inputs = dict(state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
+                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every))
+        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states)
+        for c in cps.values():
+            c["wrench"] = wrench
+        del rec["_c"]
+        rec.update(lists=live["lists"][live["lists_in"]], X=live["X"], P=live["P"], info=live["info"], state=live["state"], checkpoints=cps, inputs=inputs)
+        return rec
+
+    def walk_resume_device(self, snapshot, ticks, index=None, push=None, push_ticks=0, replan=None, trace=True, stop=("merge", "solver", "nonfinite"),
+                           skip_ended=False, taped=False, every=None):
+        """Continues, or forks, a walk from a snapshot (a value of walk_device_checkpointed's "checkpoints", or any BatchSolver.walk_snapshot filled by
+        rollout_snapshot_device): the snapshot is restored into fresh live buffers -- problem b of this roll-out receives problem index[b] of the
+        snapshot (index: int32 [B], CUDA tensor or numpy; None: problem b) -- and ticks snapshot["tick"] .. snapshot["tick"] + ticks - 1 are walked warm
+        (cold_first = 0), with no host read and no synchronisation.  -> walk_device's dict: the trace rows are those ticks only (row 0 = the resume
+        tick), the outcome CONTINUES from the snapshot's (end_tick is a tick number of the whole walk), plus index_ok[B] (0: that index lay outside the
+        snapshot's batch; the problem received nothing, its buffers keep their zero fill and it counts as ended from the start, end_tick 0 and end_code
+        0), tick0, and "checkpoints" when `every` is given (snapshots in front of the multiples of `every` behind the resume tick).
+        push[B, 3]: replaces the wrench schedule from the resume tick on; its rule is run()'s counted from that tick (the push on the first
+        max(push_ticks - i, 1) knots of resume tick + i < push_ticks, zeros once behind).  Without it a checkpoint of walk_device_checkpointed goes on
+        with its walk's schedule (gathered by index); any other snapshot leaves the wrench rows of P as they are.  replan {tick: plan}, tick numbers of
+        the whole walk: the latest entry at or before a tick is the plan in force (none: self.plan) -- pass the source walk's replan to continue it.  The
+        references are this roll-out's (set_references, else the straight line), long enough for the resumed ticks.
+        index lets B problems fork from a snapshot of another batch size, many from one (splitting: the same robot under B different pushes).
+        taped=True: "tape" as walk_device_taped's, of ticks + 1 rows: row 0 is a stub that holds the snapshot's list times and counts (the previous
+        lists of the first resumed tick), row 1 + i is resume tick + i, first_row_is_first_tick = 0 (reverse it from row 1).
+        Bit-equality with the unbroken walk is promised between handles of the same batch size and factor storage: the solver picks its kernel variant
+        from them (the round-3 note on stragglers), and another variant rounds differently.  Out of scope: refilling ended problems with new
+        robots -- a walk has no per-problem cold tick."""
+        return self._queued(lambda: self._walk_resume(snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every))
+
+    def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every):
+        torch, dev, s, B = self.torch, self.dev, self.solver, self.B
+        self._walk_inputs = hold = []
+
+        def up(a, dt, np_dt):
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, dt).contiguous()
+            hold.append(torch.from_numpy(np.ascontiguousarray(a, np_dt)))
+            return hold[-1].to(dev, non_blocking=True)
+        t0 = int(snapshot["tick"])
+        rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
+        live = self._live_buffers(rec)
+        idx = None if index is None else up(index, torch.int32, np.int32)
+        index_ok = torch.empty((B,), dtype=torch.int32, device=dev)
+        s.rollout_snapshot_device(snapshot, live, idx, index_ok)
+        wrench = None
+        if push is not None:
+            wrench = (self._push_schedule(up(push, torch.float32, np.float32), push_ticks), t0)
+        elif snapshot.get("wrench") is not None and t0 - snapshot["wrench"][1] < snapshot["wrench"][0].shape[0]:
+            wt, first = snapshot["wrench"]
+            if idx is not None:
+                wt = wt.index_select(1, idx.clamp(0, int(snapshot["batch"]) - 1).to(torch.int64)).contiguous()
+            wrench = (wt, first)
+        refs = self._planner_refs(t0 + ticks)
+        plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < t0 + ticks}
+        tp = None
+        if taped:
+            s.set_multiplier_output(True)
+            tp = s.walk_tape(ticks + 1, self.M, step=self.cfg.sampling_time / self.substeps, substeps=self.substeps,
+                             force_sample_time=self.force_sample_time, first_row_is_first_tick=False, device=dev)
+            prev = live["lists"][live["lists_in"]]
+            tp["list_t"][0].copy_(prev[0])
+            tp["list_n"][0].copy_(prev[2])
+        cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1)
+        del rec["_c"]
+        if tp is not None:
+            tp.update(dt=self.cfg.sampling_time, tick0=t0, row0=1)
+            rec["tape"] = tp
+        if every is not None:
+            rec["checkpoints"] = cps
+        rec.update(lists=live["lists"][live["lists_in"]], X=live["X"], P=live["P"], info=live["info"], state=live["state"], index_ok=index_ok, tick0=t0)
+        return rec
+
+    def backward_device_checkpointed(self, w, grad_states, grad_X=None, rot=False):
+        """backward_device (rot=True: backward_device_rot) without a whole-walk tape.  w = walk_device_checkpointed(...).  For each segment between two
+        checkpoints, last first: the segment's snapshot is restored into workspace buffers (segment 0: the start is set up again from w["inputs"]), the
+        segment is run again through cmpc_rollout_walk_taped_device into ONE re-used tape of at most every + 1 rows, and reversed through the carries
+        with cmpc_rollout_walk_vjp[_rot]_device and w["end_tick"].  A segment that does not start at tick 0 has no first tick: its tape says
+        first_row_is_first_tick = 0, its row 0 is a stub that holds the snapshot's list times and counts, and it is taped and reversed from row 1.
+        The walk is bit-reproducible and the reverse walk composes over segments to the bit, so every key equals the full-tape method's bit for bit, at
+        the cost of one more forward walk (a forward tick is about a tenth of a reverse tick).
+        grad_states[ticks + 1, B, 9] as in backward_device; grad_X: None, a [ticks, B, n_x] tensor, or a callable (t0, t1, tape_segment) -> [t1 - t0, B,
+        n_x] float32 CUDA tensor that runs once per segment with views of that segment's tape rows (X, P, lam_g, info, ok, land, states[t1 - t0 + 1]),
+        so that the dense seeds need not exist either.
+        -> the keys of backward_device (rot=True: of backward_device_rot) plus "tape_rows_peak".  No host read once the workspaces exist (the first
+        call allocates them and turns the multiplier output on).  Out of scope: the reference gradients (backward_device_refs: their one-launch sum has
+        a fixed ascending order that per-segment calls in reverse would change), the forward-mode walk, and refilling ended problems."""
+        return self._queued(lambda: self._backward_checkpointed(w, grad_states, grad_X, rot))
+
+    def _backward_checkpointed(self, w, grad_states, grad_X, rot):
+        torch, B, N, L, M, s, dev = self.torch, self.B, self.cfg.N, self.L, self.M, self.solver, self.dev
+        inp, cps = w["inputs"], w["checkpoints"]
+        T, every = inp["ticks"], inp["every"]
+        as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(dev, dt).contiguous()
+        gS = as_t(grad_states, torch.float64)
+        assert tuple(gS.shape) == (T + 1, B, 9)
+        gX = None
+        if grad_X is not None and not callable(grad_X):
+            gX = as_t(grad_X, torch.float32)
+            assert tuple(gX.shape) == (T, B, L.nx)
+        z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
+        out = dict(push=z((B, 3)), wrench=z((T, B, N, 6), torch.float32), models=z((B, 34)), plan=z((B, 2, M, 3)), status=z((T, B), torch.int32),
+                   end_tick=w["end_tick"])
+        if rot:
+            out.update(plan_rot=z((B, 2, M, 3)), rot=z((T, B, 2, N, 3)), removed=z((T, B), torch.float32))
+        rows = min(every, T) + 1
+        key = (rows, inp["stop"])
+        ws = getattr(self, "_checkpoint_ws", None)
+        if ws is None or ws["key"] != key:    # (one set of live buffers, one record without a trace and one tape, re-used by every segment and every call)
+            s.set_multiplier_output(True)
+            rec = s.walk_record(rows, stop=inp["stop"], trace=False, device=dev)
+            ws = dict(key=key, live=self._live_buffers(rec),
+                      tape=s.walk_tape(rows, M, step=self.cfg.sampling_time / self.substeps, substeps=self.substeps,
+                                       force_sample_time=self.force_sample_time, device=dev),
+                      gx=torch.zeros((rows, B, L.nx), dtype=torch.float32, device=dev))
+            self._checkpoint_ws = ws
+        live, tp = ws["live"], ws["tape"]
+        bounds = [0] + sorted(cps) + [T]
+        g, gl = gS[T].clone(), z((B, 2, M, 3))    # (the gate in front of the last tick selects zero where the problem has ended)
+        glr = z((B, 2, M, 3)) if rot else None
+        peak = 0
+        for j in reversed(range(len(bounds) - 1)):
+            c0, c1 = bounds[j], bounds[j + 1]
+            r0 = 0 if c0 == 0 else 1
+            if c0 == 0:
+                self._live_reset(live, inp["state0"], inp["replan"].get(0, inp["plan"]))
+            else:
+                s.rollout_snapshot_device(cps[c0], live)
+                prev = live["lists"][live["lists_in"]]
+                tp["list_t"][0].copy_(prev[0])
+                tp["list_n"][0].copy_(prev[2])
+            tp["_c"].first_row_is_first_tick = 1 if c0 == 0 else 0
+            self._walk_live(live, c0, c1, c0, inp["replan"], inp["plan"], inp["wrench"], inp["refs"], inp["skip_ended"], tape=tp, tape_shift=c0 - r0,
+                            cold=c0 == 0)
+            gx_rows = None
+            if callable(grad_X):
+                seg = {k: tp[k][r0:r0 + c1 - c0] for k in ("X", "P", "lam_g", "info", "ok", "land", "plan_t", "list_t", "plan_n", "list_n")}
+                seg["states"] = tp["states"][r0:r0 + c1 - c0 + 1]
+                ws["gx"][r0:r0 + c1 - c0].copy_(grad_X(c0, c1, seg))
+                gx_rows = ws["gx"]
+            s.rollout_walk_vjp_rows_device(c0, c1 - c0, tp, r0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, grad_X_rows=gx_rows, wrench=out["wrench"],
+                                           dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
+                                           grad_rot=out.get("rot"), removed=out.get("removed"))
+            peak = max(peak, r0 + c1 - c0)
+        for i in reversed(range(min(T, inp["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
+            out["push"] += out["wrench"][i][:, :max(inp["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
+        out["state0"], out["list0"] = g, gl
+        if rot:
+            out["list_rot0"] = glr
+        out["tape_rows_peak"] = peak
+        return out
+
     def forward_sensitivity(self, tape, dir_state0=None, dir_list0=None, dir_list_rot0=None, dir_plan=None, dir_plan_rot=None, dir_push=None, dir_models=None,
                             dir_wrench=None, solutions=False):
         """The taped roll-out in forward mode (cmpc_rollout_tick_jvp_device, one call per tick, first tick first): how the whole trajectory moves along k
@@ -946,3 +1212,44 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
     return _Fn.apply(state0, push, models, plan_rot, ref_com, ref_h)
+
+
+def rollout_differentiable_checkpointed(rollout: WalkingRollout, ticks, state0, every, push=None, models=None, push_ticks=0, replan=None):
+    """rollout_differentiable(device_walk=True) in bounded memory: forward is WalkingRollout.walk_device_checkpointed (cut at every tick besides, so
+    that the states [ticks + 1, B, 9] can be copied out: 36 bytes per problem and tick; still no host read), backward is
+    WalkingRollout.backward_device_checkpointed -- no whole-walk tape exists at any time, only a snapshot every `every` ticks and one tape of
+    every + 1 rows.  The returned states, and state0.grad, push.grad and models.grad, equal rollout_differentiable(device_walk=True)'s to the bit; the
+    fold of the rows behind a problem's end is the same.  rollout.last_walk / rollout.last_backward as there.  Not here: plan_rot, ref_com / ref_h
+    (backward_device_refs is out of scope of the checkpointed reverse walk) and forward mode."""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, state0, push, models):
+            if models is not None:
+                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
+                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
+            s0 = state0.detach().to(rollout.dev, torch.float32)
+            states = torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
+            w = rollout._queued(lambda: rollout._walk_checkpointed(
+                every, states, ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks,
+                replan, False, ("merge", "solver", "nonfinite"), False))
+            rollout.last_walk = ctx.walk = w
+            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
+            e = w["end_tick"]
+            row = torch.arange(ticks + 1, device=rollout.dev)[:, None]
+            ctx.past = (e[None, :] >= 0) & (row > e[None, :])         # [ticks + 1, B]: rows behind a problem's end
+            ctx.last = row == e[None, :]                                # the row its final state sits in
+            return torch.where(ctx.past[..., None], w["final_state"][None], states)
+
+        @staticmethod
+        def backward(ctx, gStates):
+            g = gStates.to(rollout.dev, torch.float64)
+            folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
+            g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
+            r = rollout.backward_device_checkpointed(ctx.walk, g)
+            rollout.last_backward = r
+            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
+                    r["models"] if ctx.needs_input_grad[2] else None)
+
+    return _Fn.apply(state0, push, models)

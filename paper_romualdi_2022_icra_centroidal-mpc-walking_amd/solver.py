@@ -918,6 +918,103 @@ class BatchSolver:
         self._launch(carry_state.device,
                      lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, r, st))
 
+    def rollout_walk_vjp_rows_device(self, tick0, ticks, tape, row0, end_tick, grad_states, carry_state, carry_list, status, grad_X=None, wrench=None,
+                                     dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None, grad_X_rows=None):
+        """rollout_walk_vjp_device on a SEGMENT tape (a few rows, re-used) with WHOLE-WALK arrays: grad_states[T + 1, B, 9], grad_X / wrench / grad_rot
+        [T, B, ..] and status / removed [T, B] are indexed by the tick number, the tape by row0 + i for tick tick0 + i.  Each array goes to the library
+        as the leading-axis view that starts tick0 - row0 rows in, so that tape row and array row coincide; the call reads and writes rows tick0 ..
+        tick0 + ticks - 1 of them (and no other), exactly as rollout_walk_vjp_device does on a whole-walk tape.  The carries and the += outputs as
+        there.  grad_X_rows[rows, B, n_x] float32 (instead of grad_X): the solutions' seeds of this segment alone, indexed like the tape."""
+        import torch
+        L, B, N, M = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"])
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        tick0, ticks, row0 = int(tick0), int(ticks), int(row0)
+        shift = tick0 - row0
+        assert shift >= 0 and ticks >= 1 and 0 <= row0 and row0 + ticks <= int(tape["rows"]), "the segment must lie inside its tape"
+
+        def view(t, dtype, tail, name, extra=0):
+            if t is None:
+                return None
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape[1:]) == tuple(tail) and t.shape[0] >= tick0 + ticks + extra, \
+                f"{name}: expected {dtype} [>= {tick0 + ticks + extra}, {tuple(tail)}]"
+            return t.data_ptr() + shift * t.stride(0) * t.element_size()
+        assert grad_X is None or grad_X_rows is None, "grad_X or grad_X_rows, not both"
+        gx = view(grad_X, f32, (B, L.nx), "grad_X") if grad_X_rows is None else self._opt(grad_X_rows, f32, (int(tape["rows"]), B, L.nx), "grad_X_rows")
+        g = _capi.CmpcWalkGrads(view(grad_states, f64, (B, 9), "grad_states", 1), gx,
+                                self._opt(carry_state, f64, (B, 9), "carry_state"), self._opt(carry_list, f64, (B, 2, M, 3), "carry_list"),
+                                view(wrench, f32, (B, N, 6), "wrench"), None,
+                                self._opt(dGradPlan, f64, (B, 2, M, 3), "dGradPlan"), self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"),
+                                view(status, i32, (B,), "status"))
+        e = self._opt(end_tick, i32, (B,), "end_tick")
+        if carry_list_rot is None:
+            assert dGradPlanRot is None and grad_rot is None and removed is None, "orientation gradients need carry_list_rot"
+            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, tick0, ticks, tape["_c"], row0, e, g, st))
+            return
+        r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
+                                   view(grad_rot, f64, (B, 2, N, 3), "grad_rot"), view(removed, f32, (B,), "removed"))
+        self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, tick0, ticks, tape["_c"], row0, e, g, r, st))
+
+    # ---- the state of a walk between two ticks (include/cmpc.h, cmpc_walk_snapshot) ----
+    def walk_snapshot(self, tick, lists_in, max_contacts, batch=None, device=None, tensors=None):
+        """The arrays of a cmpc_walk_snapshot (include/cmpc.h) as a dict of CUDA tensors -- state[B, 9], P, X, X0, info, zmp, ok[B], land[B, 2], lists = the
+        two list sets [(t, pose, n), (t, pose, n)], and the outcome end_tick, end_code, iterations_sum, iterations_max, final_state, box_slack_min --
+        plus tick, lists_in, max_contacts, batch and "_c", the C struct that points at them.  Zero-filled; batch: the snapshot's own (default: the
+        handle's).  tensors: a dict with some of these keys -- those tensors are taken as they are and not allocated (a walk's live buffers described as
+        a snapshot); X0, info or zmp given as None there are left out of the struct (NULL: skipped by the copy)."""
+        import torch
+        B, L, M = int(self.batch if batch is None else batch), self.layout, int(max_contacts)
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        shapes = dict(state=((B, 9), f32), P=((B, L.np), f32), X=((B, L.nx), f32), X0=((B, L.nx), f32), info=((B, _capi.INFO), f32), zmp=((B, 2), f32),
+                      ok=((B,), i32), land=((B, 2), i32), end_tick=((B,), i32), end_code=((B,), i32), iterations_sum=((B,), i32),
+                      iterations_max=((B,), i32), final_state=((B, 9), f32), box_slack_min=((B,), f32))
+        lshapes = (((B, 2, M, 2), f64), ((B, 2, M, 7), f32), ((B, 2), i32))
+        given = dict(tensors or {})
+
+        def chk(t, shape, dt, name):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"walk_snapshot: {name}: expected {dt} {tuple(shape)}"
+            return t
+        s = {}
+        for k, (shape, dt) in shapes.items():
+            if k in given:
+                s[k] = None if given[k] is None else chk(given[k], shape, dt, k)
+                assert s[k] is not None or k in ("X0", "info", "zmp"), f"walk_snapshot: {k} is required"
+            else:
+                s[k] = torch.zeros(shape, dtype=dt, device=dev)
+        if "lists" in given:
+            s["lists"] = [tuple(chk(a, sh, dt, "lists") for a, (sh, dt) in zip(st, lshapes)) for st in given["lists"]]
+            assert len(s["lists"]) == 2
+        else:
+            s["lists"] = [tuple(torch.zeros(sh, dtype=dt, device=dev) for sh, dt in lshapes) for _ in range(2)]
+        ptr = lambda t: None if t is None else t.data_ptr()
+        s["_c"] = _capi.CmpcWalkSnapshot(int(tick), int(lists_in), *(ptr(s[k]) for k in ("state", "P", "X", "X0", "info", "zmp", "ok", "land")),
+                                         *(ptr(a) for st in s["lists"] for a in st),
+                                         *(ptr(s[k]) for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min")))
+        s.update(tick=int(tick), lists_in=int(lists_in), max_contacts=M, batch=B)
+        return s
+
+    def walk_snapshot_mark(self, snap, tick, lists_in):
+        """the host words of a snapshot dict (walk_snapshot) and of its C struct"""
+        snap["tick"] = snap["_c"].tick = int(tick)
+        snap["lists_in"] = snap["_c"].lists_in = int(lists_in)
+
+    def rollout_snapshot_device(self, src, dst, index=None, ok=None, src_batch=None):
+        """cmpc_rollout_snapshot_device: ONE launch on torch's current stream, no host read: problem b of dst (walk_snapshot; the handle's batch) receives
+        the bit copy of problem index[b] of src (index: int32 [B] CUDA tensor; None: problem b, and src must then hold the handle's batch).  An index
+        outside [0, src_batch) leaves that problem of dst unwritten and gives ok[b] = 0 (ok: int32 [B], written when given).  src_batch: default
+        src["batch"].  dst's host words tick and lists_in become src's.  Save and restore are the same call with the arguments swapped; repeated
+        indices branch one problem into many."""
+        import torch
+        B = self.batch
+        sb = int(src["batch"] if src_batch is None else src_batch)
+        assert src["max_contacts"] == dst["max_contacts"] and dst["batch"] == B and sb <= src["batch"], "rollout_snapshot_device: snapshots of other sizes"
+        i = self._opt(index, torch.int32, (B,), "index")
+        o = self._opt(ok, torch.int32, (B,), "ok")
+        self._launch(dst["state"].device, lambda st: self._lib.cmpc_rollout_snapshot_device(
+            self._h, int(src["max_contacts"]), sb, C.byref(src["_c"]), C.byref(dst["_c"]), i, o, st))
+        self.walk_snapshot_mark(dst, src["tick"], src["lists_in"])
+        return dst
+
     def rollout_walk_vjp_gate_device(self, gate, device=None):
         """cmpc_rollout_walk_vjp_gate_device: one gate step of the reverse walk as one launch; gate: a _capi.CmpcWalkGate of device pointers."""
         import torch
