@@ -801,7 +801,7 @@ int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double
  * solution VJP with word 0 replaced by the tick's status: 0 ok; 1..3 as the solution sensitivities; 4 the solve's status is not 0 (not converged, or flagged);
  * 5 the merge failed (dOk == 0).  Precedence: 5, then 2 and 3 (they speak of the inputs), then 4, then 1.  A flagged problem gets zeros in every array (nothing is added to the += outputs); its
  * neighbours are bit for bit what they are without it.  Workspace: per-handle HBM allocated on first use by whichever of the two tick entry points runs
- * first, 4 (n_x + 2 n_p) + 48 N + 596 bytes per problem (the rotation entry's arrays, 48 N + 48, included); calls on one handle run one after the other
+ * first, 4 (n_x + 2 n_p) + 48 N + 652 bytes per problem (the rotation entry's arrays, 48 N + 48, and the mismatch entry's, 56, included); calls on one handle run one after the other
  * whatever their streams (an event, as for the solution sensitivities). */
 typedef struct cmpc_tick_tape {
     const float* dX; const float* dP; const float* dLamG;   /* [B][n_x], [B][n_p], [B][n_g] of the tick's solve */
@@ -1129,6 +1129,81 @@ int cmpc_rollout_walk_jvp_gate(const cmpc_walk_jvp_gate* g);
 /* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what the forward walk queues between its
  * ticks.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
 int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g, void* stream);
+
+/* ---- plant-model mismatch on the device walk: hidden pushes, sensor noise, force gain (derivation: DESIGN.md 7f, "Mismatch") ----
+ * In every entry point above the plant IS the model: the wrench the plant integrates is the knot-0 wrench rows of dP, which setState handed to the MPC; the
+ * MPC measures the plant's exact state; the plant applies exactly the forces the MPC asked for.  The reference has the split this section adds:
+ * CentroidalMPCBlock receives input.totalExternalWrench, an ESTIMATE, while the simulator applies the true one.  Nothing in the solver kernel changes.
+ * Per problem, at tick number t, row r = t - tick_first of the two schedules (device pointers; a problem's results depend on its own rows only):
+ *   hidden wrench (0 <= r < hidden_ticks): the plant uses a = (F + fExt_0) + fHidden - g e_z and tau0 = (tauExt_0 + tauHidden) + sum_q cp_q x f_q, in double
+ *     from the float values, in that order (the mismatch-free expression keeps its bits).  Nothing of it is written to dP: the MPC never sees it.  Outside
+ *     the range the term is NOT ADDED -- a select, not an add of zero.
+ *   state noise (0 <= r < noise_ticks): the front kernel writes com0 / dcom0 / h0 = state[e] + noise[r][b][e], ONE float32 add; the plant integrates from the
+ *     true state (dState / dStateOut, unchanged).  Outside the range it is a plain copy.
+ *   force gain: cf = on ? (double)gain * (double)f : 0 for every corner force -- fsum, tau0 and the ZMP's F, T all use the applied force, so the 0.001
+ *     thresholds see it.  A mass error is gain = m_nominal / m_true.  No device-side validation: a NaN or non-positive gain gives what the arithmetic gives, and
+ *     the record ends the problem by code 5 if the state goes non-finite.
+ * sizeof(cmpc_plant_mismatch) == 48 (LP64; the ctypes mirror is held to this number). */
+typedef struct cmpc_plant_mismatch {
+    int tick_first;                                /* tick number of row 0 of the two schedules */
+    const float* dHiddenWrench; int hidden_ticks;  /* [hidden_ticks][B][6] mass-normalised force | torque about the CoM, or NULL */
+    const float* dStateNoise;   int noise_ticks;   /* [noise_ticks][B][9] added to the MEASURED com, dcom, h, or NULL */
+    const float* dForceGain;                       /* [B] or NULL (1): the plant applies gain * f to every corner force */
+} cmpc_plant_mismatch;
+/* cmpc_plant_step_device with one tick's hidden-wrench row dHiddenWrench[B][6] (or NULL) and dForceGain[B] (or NULL).  Both NULL: cmpc_plant_step_device bit
+ * for bit (it calls this with NULL, and the kernel then is the instantiation without the mismatch); gain = 1 and a zero wrench give the same bits too, on
+ * inputs without negative zeros in the wrench sums. */
+int cmpc_plant_step_mismatch_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, double step,
+                                    int substeps, double zmp_half_x, double zmp_half_y, const float* dHiddenWrench, const float* dForceGain, void* stream);
+/* cmpc_rollout_tick_device with the explicit tick number that selects the rows of m.  Still three launches: the noise add lives in the front kernel's setState
+ * loop, the hidden wrench and the gain in the back kernel's plant step.  m == NULL: cmpc_rollout_tick_device, bit for bit (`tick` is then not looked at).
+ * CMPC_ERR_ARG, besides cmpc_rollout_tick_device's: a negative count, a non-NULL schedule with a zero count, tick < 0. */
+int cmpc_rollout_tick_mismatch_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, int tick, const cmpc_plant_mismatch* m,
+                                      void* stream);
+/* The recorded walk (tape == NULL: cmpc_rollout_walk_device) or the taped walk (cmpc_rollout_walk_taped_device) with each tick passing its own number
+ * tick0 + i to the tick above.  No launch is added per tick and nothing more is taped: dStates already holds the true state and dP the measured one.
+ * cmpc_set_ended_device, stop_mask, dWrenchTicks and the planner references compose with it unchanged.  m == NULL: the existing entry point, bit for bit.
+ * CMPC_ERR_ARG as the two walks', and the mismatch's above. */
+int cmpc_rollout_walk_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, const cmpc_plant_mismatch* m,
+                                      void* stream);
+/* Reverse.  The plant's closed form holds with f_q -> gain f_q and fExt_0 -> fExt_0 + fHidden (the same for the torque), so the partials are those of
+ * "plant-step derivatives" taken at the gained forces and the summed wrench; the VJPs above on a mismatch tape would be silently wrong.
+ * cmpc_plant_step_vjp_rot_device's arguments (dGradRot0 may be NULL) plus the inputs dHiddenWrench[B][6] / dForceGain[B] (either NULL as in the forward) and
+ * the outputs dGradHidden[B][6] double = the plant's own gradient on fExt_0 / tauExt_0 (unrounded) and dGradGain[B] double = sum_q <dl/d(gain f_q), f_q> over
+ * the gated-on corners in corner order, both WRITTEN, either may be NULL; dGradX on the 24 forces is gain * dl/d(gain f).  With both inputs NULL the outputs
+ * shared with cmpc_plant_step_vjp_rot_device are bit-equal to it. */
+int cmpc_plant_step_vjp_mismatch_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
+                                        const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
+                                        const float* dHiddenWrench, const float* dForceGain, double* dGradHidden, double* dGradGain, void* stream);
+/* One tick in reverse under a mismatch: cmpc_rollout_tick_vjp_rot_device's arguments (dGradPrevListRot == NULL: the chain without orientations, as
+ * cmpc_rollout_tick_vjp_device), the tick's own rows dHiddenWrench[B][6] / dForceGain[B] (either NULL: not applied in the forward), and three outputs, each
+ * may be NULL: dGradHidden[B][6] double, written; dGradNoise[B][9] float, written: the solve VJP's dGradP on com0 / dcom0 / h0, the part of dGradState that
+ * arrived through setState; dGradGain[B] double, += (one thread per problem, no atomics).  tape->dState is the TRUE state the tick started from, tape->dP the
+ * parameters the solve saw (the measured state in them).  A flagged problem (status != 0) gets explicit zeros in the first two and adds nothing to the third,
+ * written by the branch of the combine kernel that zeroes everything else.  With both inputs NULL every output the existing entries have is bit-identical to
+ * theirs.  Workspace: the tick VJP's, which holds 56 bytes per problem for this entry. */
+int cmpc_rollout_tick_vjp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                          const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                          double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
+                                          double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, const float* dHiddenWrench, const float* dForceGain,
+                                          double* dGradHidden, float* dGradNoise, double* dGradGain, void* stream);
+/* The reverse walk under a mismatch: the same loop as cmpc_rollout_walk_vjp[_rot]_device -- ONE function behind all three entries -- with the tick above per
+ * row; r may be NULL (no orientation chain), m is the walk's mismatch (NULL: none was applied; the gradient rows are still written), mg may be NULL.  Each
+ * pointer of mg may be NULL; rows are the tape's rows, as dGradWrench's.
+ * Ended problems: the gate structs and the gate kernel are NOT changed.  For ticks i >= e of an ended problem the gate already feeds the tick dOk = 0; the
+ * tick then flags the problem and writes zeros in its dGradHidden / dGradNoise rows and adds nothing to dGradGain -- the endings are kept by selection, with no
+ * new gate work, and stale or non-finite data behind an end cannot leak.
+ * Rows whose tick lies outside a schedule's range still get their gradient row: dGradHidden there is the gradient with respect to a wrench that was zero (not
+ * added), dGradNoise with respect to a noise that was zero.  Forward mode and the checkpointed reverse do not know the mismatch. */
+typedef struct cmpc_walk_grads_mismatch {
+    double* dGradHidden;   /* [rows][B][6], written per row */
+    float* dGradNoise;     /* [rows][B][9], written per row */
+    double* dGradGain;     /* [B], += */
+} cmpc_walk_grads_mismatch;
+int cmpc_rollout_walk_vjp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                          const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, const cmpc_plant_mismatch* m,
+                                          const cmpc_walk_grads_mismatch* mg, void* stream);
 
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */

@@ -109,6 +109,17 @@ class CmpcWalkGateRot(C.Structure):
     _fields_ = [("base", CmpcWalkGate)] + [(k, C.c_void_p) for k in ("tick_list_rot", "carry_list_rot", "rot_row", "removed_row")]
 
 
+class CmpcPlantMismatch(C.Structure):
+    """mirror of cmpc_plant_mismatch (include/cmpc.h): the schedules of hidden wrenches and state noise and the force gain of a mismatched plant"""
+    _fields_ = [("tick_first", C.c_int), ("dHiddenWrench", C.c_void_p), ("hidden_ticks", C.c_int), ("dStateNoise", C.c_void_p), ("noise_ticks", C.c_int),
+                ("dForceGain", C.c_void_p)]
+
+
+class CmpcWalkGradsMismatch(C.Structure):
+    """mirror of cmpc_walk_grads_mismatch (include/cmpc.h): the mismatch outputs of cmpc_rollout_walk_vjp_mismatch_device"""
+    _fields_ = [(k, C.c_void_p) for k in ("dGradHidden", "dGradNoise", "dGradGain")]
+
+
 class CmpcWalkDirs(C.Structure):
     """mirror of cmpc_walk_dirs (include/cmpc.h): the direction columns, carries and outputs of cmpc_rollout_walk_jvp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -187,6 +198,8 @@ EXPORTS = [
     "cmpc_rollout_walk_vjp_rot_device", "cmpc_rollout_walk_vjp_rot_gate", "cmpc_rollout_walk_vjp_rot_gate_device",
     "cmpc_reference_from_planner_vjp", "cmpc_reference_from_planner_vjp_device", "cmpc_reference_from_planner_jvp", "cmpc_reference_from_planner_jvp_device",
     "cmpc_rollout_snapshot", "cmpc_rollout_snapshot_device", "cmpc_walk_snapshot_bytes",
+    "cmpc_plant_step_mismatch_device", "cmpc_rollout_tick_mismatch_device", "cmpc_rollout_walk_mismatch_device",
+    "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
 ]
 
 _lib = None
@@ -331,6 +344,16 @@ def lib():
             L.cmpc_rollout_snapshot.argtypes = [i, i, i, i, sp, sp, vp, vp]
             L.cmpc_walk_snapshot_bytes.argtypes = [i, i]
             L.cmpc_walk_snapshot_bytes.restype = C.c_size_t
+        if hasattr(L, "cmpc_rollout_walk_mismatch_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            mp = C.POINTER(CmpcPlantMismatch)
+            L.cmpc_plant_step_mismatch_device.argtypes = [vp, fp, fp, fp, fp, fp, d, i, d, d, vp, vp, vp]
+            L.cmpc_rollout_tick_mismatch_device.argtypes = [vp, i, d, i, C.POINTER(CmpcTickIO), i, mp, vp]
+            L.cmpc_rollout_walk_mismatch_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), C.POINTER(CmpcWalkRecord), i, i, ip,
+                                                            C.POINTER(CmpcWalkTape), i, mp, vp]
+            L.cmpc_plant_step_vjp_mismatch_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp]
+            L.cmpc_rollout_tick_vjp_mismatch_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 20
+            L.cmpc_rollout_walk_vjp_mismatch_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, C.POINTER(CmpcWalkGrads),
+                                                                C.POINTER(CmpcWalkGradsRot), mp, C.POINTER(CmpcWalkGradsMismatch), vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -50,12 +50,12 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, hipStream_t stream);
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, const float* noise, hipStream_t stream);
 extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
                                              const int* ended, hipStream_t stream);
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
-                                     const double* t, float* pose, const int* n, const int* ended, hipStream_t stream);
+                                     const double* t, float* pose, const int* n, const int* ended, const float* hidden, const float* gain, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream);
 extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                                         float* slack_min, hipStream_t stream);
@@ -68,14 +68,15 @@ extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t s
 extern "C" size_t cmpc_walk_jvp_gate_wide_entries(const CmpcJvpGateArgs* a);
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
-                                      hipStream_t stream);
+                                      const float* dHidden, const float* dGain, hipStream_t stream);
 
 extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
                                      const double* dDirModel, const double* dDirRot0, double* dOut, hipStream_t stream);
 extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
-                                     double* dGradModel, double* dGradRot0, hipStream_t stream);
+                                     double* dGradModel, double* dGradRot0, int mismatch, const float* dHidden, const float* dGain, double* dGradHidden,
+                                     double* dGradGain, hipStream_t stream);
 extern "C" int cmpc_launch_contacts_orientation_vjp(int B, int N, int M, double dt, double now, long long snap_dt_ns, const double* plan_t, const int* plan_n,
                                                     const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
                                                     const int* ok, const double* g_out, const double* g_rot, double* g_prev, double* g_plan, int* status,
@@ -121,7 +122,8 @@ struct cmpc_handle_s {
     double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
     int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
     char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp[_rot]_device (allocated on first use, sized for both): model gradients of the solve and of
-                                 // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] (double) | gX[B][n_x] | gP of
+                                 // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] | the plant's gradient on the
+                                 // hidden wrench [B][6] and on the force gain [B] (the mismatch entry) (double) | gX[B][n_x] | gP of
                                  // the solve [B][n_p] | gP of the plant [B][n_p] (float) | the tick's ok words [B] (int)
     hipEvent_t tick_ev = nullptr; // recorded after the last kernel of a tick VJP or JVP: the next one, on any stream, waits for it (one workspace each)
     char* dTickJvpWs = nullptr;  // workspace of cmpc_rollout_tick_jvp_device for tick_jvp_cols columns per problem (allocated on first use, grown when a larger k
@@ -1077,16 +1079,23 @@ int cmpc_reference_from_planner_jvp_device(cmpc_handle h, int tick0, int rows, i
 }
 
 // ---- 8f-4: plant step on the device (see cmpc_plant_step_kernel) ----
-int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut, float* dZmp,
-                           double step, int substeps, double zmp_half_x, double zmp_half_y, void* stream)
+int cmpc_plant_step_mismatch_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut, float* dZmp,
+                                    double step, int substeps, double zmp_half_x, double zmp_half_y, const float* dHiddenWrench, const float* dForceGain,
+                                    void* stream)
 {
     if (!h || !dX || !dP || !dStateIn || !dStateOut || !(step > 0) || substeps < 1)
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_step(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, dStateOut, dZmp, (float)step,
-                                    substeps, (float)zmp_half_x, (float)zmp_half_y, stream ? (hipStream_t)stream : h->stream);
+                                    substeps, (float)zmp_half_x, (float)zmp_half_y, dHiddenWrench, dForceGain, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant step launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
+}
+
+int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut, float* dZmp,
+                           double step, int substeps, double zmp_half_x, double zmp_half_y, void* stream)
+{
+    return cmpc_plant_step_mismatch_device(h, dX, dP, dStateIn, dStateOut, dZmp, step, substeps, zmp_half_x, zmp_half_y, nullptr, nullptr, stream);
 }
 
 // ---- plant-step derivatives (include/cmpc.h; cmpc_plant_jvp_kernel / cmpc_plant_vjp_kernel, next to the plant kernel) ----
@@ -1108,17 +1117,34 @@ int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, 
     return cmpc_plant_step_jvp_rot_device(h, dX, dP, dStateIn, step, substeps, dDirState, dDirX, dDirP, dDirModel, nullptr, dDirStateOut, stream);
 }
 
-int cmpc_plant_step_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
-                                   const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
-                                   void* stream)
+static int plant_vjp(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dGradStateOut,
+                     double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0, bool mismatch, const float* dHiddenWrench,
+                     const float* dForceGain, double* dGradHidden, double* dGradGain, void* stream)
 {
     if (!h || !dX || !dP || !dStateIn || !dGradStateOut || !dGradState || !dGradX || !(step > 0) || substeps < 1)
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_vjp_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_vjp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                   dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, stream ? (hipStream_t)stream : h->stream);
+                                   dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, mismatch ? 1 : 0, dHiddenWrench, dForceGain, dGradHidden,
+                                   dGradGain, stream ? (hipStream_t)stream : h->stream);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant VJP launch: ") + hipGetErrorString((hipError_t)rc));
     return CMPC_OK;
+}
+
+int cmpc_plant_step_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
+                                   const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
+                                   void* stream)
+{
+    return plant_vjp(h, dX, dP, dStateIn, step, substeps, dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, false, nullptr, nullptr, nullptr,
+                     nullptr, stream);
+}
+
+int cmpc_plant_step_vjp_mismatch_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
+                                        const double* dGradStateOut, double* dGradState, float* dGradX, float* dGradP, double* dGradModel, double* dGradRot0,
+                                        const float* dHiddenWrench, const float* dForceGain, double* dGradHidden, double* dGradGain, void* stream)
+{
+    return plant_vjp(h, dX, dP, dStateIn, step, substeps, dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, true, dHiddenWrench, dForceGain,
+                     dGradHidden, dGradGain, stream);
 }
 
 int cmpc_plant_step_vjp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dGradStateOut,
@@ -1388,9 +1414,36 @@ int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, v
 // per-problem functions as the single kernels; results identical to the last bit). ----
 // cold: the solve starts from cmpc_cold_start_kernel, launched between the front kernel and the solve (the first tick of cmpc_rollout_walk_device; needs
 // warm == 0).  box_done: the caller has uploaded the box already.
-static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream, bool cold, bool box_done)
+// m: the plant mismatch (include/cmpc.h, cmpc_plant_mismatch) with `tick` selecting its rows, or null -- then every launch is the one this function always queued
+static int mismatch_check(cmpc_handle h, const char* who, const cmpc_plant_mismatch* m)
+{
+    if (m && (m->hidden_ticks < 0 || m->noise_ticks < 0 || (m->dHiddenWrench && m->hidden_ticks == 0) || (m->dStateNoise && m->noise_ticks == 0)))
+        return fail(h, CMPC_ERR_ARG, std::string(who) + ": bad mismatch (a negative count, or a schedule with no rows)");
+    return CMPC_OK;
+}
+
+// the rows of tick number `tick`: a schedule's row inside its range, else null (the term is then not applied: a select on the host, no add of zero)
+static void mismatch_rows(const cmpc_plant_mismatch* m, int B, int tick, const float** hidden, const float** noise, const float** gain)
+{
+    *hidden = nullptr; *noise = nullptr; *gain = nullptr;
+    if (!m) return;
+    const long long r = (long long)tick - m->tick_first;
+    if (m->dHiddenWrench && r >= 0 && r < m->hidden_ticks) *hidden = m->dHiddenWrench + (size_t)r * B * 6;
+    if (m->dStateNoise && r >= 0 && r < m->noise_ticks) *noise = m->dStateNoise + (size_t)r * B * 9;
+    *gain = m->dForceGain;
+}
+
+static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream, bool cold, bool box_done,
+                             int tick = 0, const cmpc_plant_mismatch* m = nullptr)
 {
     if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: null argument");
+    if (m && tick < 0) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_mismatch_device: negative tick number");
+    {
+        const int mrc = mismatch_check(h, "cmpc_rollout_tick_mismatch_device", m);
+        if (mrc != CMPC_OK) return mrc;
+    }
+    const float *mm_hidden, *mm_noise, *mm_gain;
+    mismatch_rows(m, h->B, tick, &mm_hidden, &mm_noise, &mm_gain);
     if (!io->dLand || !io->dInfo) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: dLand and dInfo are needed");
     const bool merge = io->dPrevT || io->dPrevPose || io->dPrevN;
     if (merge && (io->dPrevT == io->dListT || io->dPrevPose == io->dListPose || io->dPrevN == io->dListN))
@@ -1435,7 +1488,7 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
     int lrc = cmpc_launch_tick_pre(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, merge ? 1 : 0, plan_t, io->dPlanPose, io->dPlanN, io->dPrevT,
                                    io->dPrevPose, io->dPrevN, io->dListT, io->dListPose, io->dListN, io->dOk, io->dLand, h->dBox, io->dState, io->dWrench, io->dP,
                                    warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
-                                   io->com_height, dt_ns, snap_ok, ended, st);
+                                   io->com_height, dt_ns, snap_ok, ended, mm_noise, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
     if (cold) {
         lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, ended, st);
@@ -1445,7 +1498,7 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
     if (rc != CMPC_OK) return rc;
     lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
                                 (float)io->plant_step, io->plant_substeps, (float)io->zmp_half_x, (float)io->zmp_half_y, io->dLand, io->dListT, io->dListPose,
-                                io->dListN, ended, st);
+                                io->dListN, ended, mm_hidden, mm_gain, st);
     if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (back) launch: ") + hipGetErrorString((hipError_t)lrc));
     return CMPC_OK;
 }
@@ -1453,6 +1506,12 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream)
 {
     return rollout_tick_impl(h, max_contacts, now, warm, io, stream, false, false);
+}
+
+int cmpc_rollout_tick_mismatch_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, int tick, const cmpc_plant_mismatch* m,
+                                      void* stream)
+{
+    return rollout_tick_impl(h, max_contacts, now, warm, io, stream, false, false, tick, m);
 }
 
 // ---- the walk (include/cmpc.h): the record behind a tick, the cold start as a kernel, and `ticks` ticks queued in one call ----
@@ -1566,7 +1625,8 @@ int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts
 }
 
 static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream);
+                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream,
+                             const cmpc_plant_mismatch* m = nullptr);
 
 int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                              int row0, int lists_in, int* lists_out, void* stream)
@@ -1574,8 +1634,8 @@ int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int tic
     return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream);
 }
 
-int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                   int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
+static int walk_taped(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m)
 {
     if (!h || !io || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: null argument or incomplete tape");
     if (ticks < 1 || tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
@@ -1586,14 +1646,33 @@ int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, i
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape's scalars do not agree with the walk (or a first tick beyond row 0)");
     if (!h->mult_out || !h->dDuals)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
-    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream);
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
+}
+
+int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                   int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
+{
+    return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, nullptr);
+}
+
+int cmpc_rollout_walk_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, const cmpc_plant_mismatch* m,
+                                      void* stream)
+{
+    if (tape) return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream, m);
 }
 
 // tape != null: the tape part around the ticks (cmpc_rollout_walk_taped_device, which has checked it); null: the launches of cmpc_rollout_walk_device
+// m: the plant mismatch, every tick passing its own number tick0 + i (no launch more per tick, nothing more on the tape: dStates holds the true state, dP the measured one)
 static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
+                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m)
 {
     if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: null argument");
+    {
+        const int mrc = mismatch_check(h, "cmpc_rollout_walk_mismatch_device", m);
+        if (mrc != CMPC_OK) return mrc;
+    }
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !io->tick.dListT || !io->tick.dListPose ||
         !io->tick.dListN || !io->tick.box_upper || !io->tick.box_lower || !io->tick.dState || !io->tick.dStateOut || (io->dWrenchTicks && io->wrench_ticks < 1))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: bad argument");
@@ -1631,7 +1710,7 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
         if (tape && i == 0)   // (the ticks run in place: the state the first one starts from is copied in front of it)
             rc = rollout_tape_impl(h, max_contacts, tape_row0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, t.dState, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    tape, stream);
-        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true);
+        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true, tick0 + i, m);
         if (rc == CMPC_OK && rec)
             rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, ok_read, t.dLand, t.dStateOut, t.dZmp, rec, st, false);
         if (rc == CMPC_OK && tape)
@@ -1722,7 +1801,9 @@ __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N
                                                                     const double* __restrict__ gm_sol, const double* __restrict__ gm_plant,
                                                                     double* __restrict__ g_state, float* __restrict__ g_wrench, double* __restrict__ g_model,
                                                                     float* __restrict__ g_p, float* __restrict__ sens, int* __restrict__ ok_out,
-                                                                    const double* __restrict__ g_rot0, double* __restrict__ g_rot)
+                                                                    const double* __restrict__ g_rot0, double* __restrict__ g_rot,
+                                                                    const double* __restrict__ gh_plant, const double* __restrict__ gg_plant,
+                                                                    double* __restrict__ g_hidden, float* __restrict__ g_noise, double* __restrict__ g_gain)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     const CmpcIdx L{N};
@@ -1739,6 +1820,8 @@ __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N
         if (g_wrench) for (int e = tid; e < 6 * N; e += 128) g_wrench[(size_t)b * 6 * N + e] = 0.f;
         if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = 0.f;
         if (g_rot) for (int e = tid; e < 6 * N; e += 128) g_rot[(size_t)b * 6 * N + e] = 0.0;
+        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = 0.0;   // (the mismatch entry: zeros, and nothing added to g_gain)
+        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = 0.f;
     } else {
         for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] += (double)gs[L.pCom0() + e];
         if (g_wrench)
@@ -1751,6 +1834,10 @@ __global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N
         if (g_model) for (int e = tid; e < CMPC_MODEL_DOUBLES; e += 128)
             g_model[(size_t)b * CMPC_MODEL_DOUBLES + e] += gm_sol[(size_t)b * CMPC_MODEL_DOUBLES + e] + gm_plant[(size_t)b * CMPC_MODEL_DOUBLES + e];
         if (g_rot) for (int e = tid; e < 6; e += 128) g_rot[((size_t)b * 2 + e / 3) * 3 * N + e % 3] += g_rot0[(size_t)b * 6 + e];
+        // the mismatch entry: the hidden wrench and the gain are the plant's alone; the noise entered through setState, so its gradient is the solve's gP there
+        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = gh_plant[(size_t)b * 6 + e];
+        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = gs[L.pCom0() + e];
+        if (g_gain && tid == 0) g_gain[b] += gg_plant[b];
     }
     if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
 }
@@ -1762,11 +1849,18 @@ __global__ __launch_bounds__(256) void cmpc_axpy_float_kernel(size_t n, const fl
 }
 }  // namespace
 
+// the mismatch entry's further arguments (cmpc_rollout_tick_vjp_mismatch_device); null in tick_vjp: the launches and bits of the two entries before it
+struct TickMismatch {
+    const float* hidden; const float* gain;              // this tick's hidden-wrench row [B][6] and the gain [B], either may be null
+    double* g_hidden; float* g_noise; double* g_gain;    // outputs, each may be null
+};
+
 // rot: the rotation entry -- the plant VJP also gives dGradRot0, the solve's VJP is cmpc_solution_vjp_rot_device (its dGradP and dGradModel are
 // cmpc_solution_vjp_model_device's bit for bit), the combine kernel adds the plant's part to stage 0, and the orientation list VJP runs last
 static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut, const double* dGradListOut,
                     const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench, double* dGradPlan, double* dGradModel, float* dGradP,
-                    float* dTickSens, const double* dGradListRotOut, double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream)
+                    float* dTickSens, const double* dGradListRotOut, double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream,
+                    const TickMismatch* mm = nullptr)
 {
     if (!h || !tape || max_contacts < 1 || !dGradStateOut || !dGradState || !dGradPrevList || !dTickSens || (rot && !dGradPrevListRot))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: null argument");
@@ -1787,12 +1881,14 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
     const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, nm = (size_t)B * CMPC_MODEL_DOUBLES;
     const size_t nr = (size_t)B * 6 * N, nr0 = (size_t)B * 6;
     if (!h->dTickWs)     // (sized for the rotation entry whichever entry runs first)
-        HIPCHK(h, hipMalloc(&h->dTickWs, sizeof(double) * (2 * nm + nr + nr0) + sizeof(float) * (nx + 2 * np) + sizeof(int) * (size_t)B));
+        HIPCHK(h, hipMalloc(&h->dTickWs, sizeof(double) * (2 * nm + nr + nr0 + 7 * (size_t)B) + sizeof(float) * (nx + 2 * np) + sizeof(int) * (size_t)B));
     double* gmSol = reinterpret_cast<double*>(h->dTickWs);
     double* gmPlant = gmSol + nm;
     double* grSol = gmPlant + nm;
     double* grPlant = grSol + nr;
-    float* gX = reinterpret_cast<float*>(grPlant + nr0);
+    double* ghPlant = grPlant + nr0;            // (the mismatch entry: the plant's gradient on the hidden wrench [B][6] and on the gain [B])
+    double* ggPlant = ghPlant + 6 * (size_t)B;
+    float* gX = reinterpret_cast<float*>(ggPlant + (size_t)B);
     if (rot && dGradRot) grSol = dGradRot;     // (the solve's VJP writes the caller's array; the combine kernel finishes it in place)
     float* gpSol = gX + nx;
     float* gpPlant = gpSol + np;
@@ -1800,7 +1896,9 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
     if (!h->tick_ev) HIPCHK(h, hipEventCreateWithFlags(&h->tick_ev, hipEventDisableTiming));
     else HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));
     int rc = cmpc_launch_plant_vjp(N, B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
-                                   tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, rot ? grPlant : nullptr, st);
+                                   tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, rot ? grPlant : nullptr, mm ? 1 : 0,
+                                   mm ? mm->hidden : nullptr, mm ? mm->gain : nullptr, mm && mm->g_hidden ? ghPlant : nullptr,
+                                   mm && mm->g_gain ? ggPlant : nullptr, st);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
     if (dGradX) {
         hipLaunchKernelGGL(cmpc_axpy_float_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, nx, dGradX, gX);
@@ -1815,7 +1913,8 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
              : cmpc_solution_vjp_model_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, dTickSens, stream);
     if (rc != CMPC_OK) return rc;
     hipLaunchKernelGGL(cmpc_tick_vjp_combine_kernel, dim3(B), dim3(128), 0, st, B, N, tape->dInfo, tape->dOk, gpSol, gpPlant, gmSol, gmPlant, dGradState,
-                       dGradWrench, dGradModel, dGradP, dTickSens, okTick, rot ? grPlant : nullptr, rot ? grSol : nullptr);
+                       dGradWrench, dGradModel, dGradP, dTickSens, okTick, rot ? grPlant : nullptr, rot ? grSol : nullptr, ghPlant, ggPlant,
+                       mm ? mm->g_hidden : nullptr, mm ? mm->g_noise : nullptr, mm ? mm->g_gain : nullptr);
     HIPCHK(h, hipGetLastError());
     rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 2, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                            tape->dListT, tape->dListN, tape->dLand, okTick, dGradListOut, gpSol, nullptr, dGradPrevList, dGradPlan, nullptr, st);
@@ -1845,6 +1944,17 @@ int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now
 {
     return tick_vjp(h, true, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
                     dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream);
+}
+
+int cmpc_rollout_tick_vjp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
+                                          const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
+                                          double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
+                                          double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, const float* dHiddenWrench, const float* dForceGain,
+                                          double* dGradHidden, float* dGradNoise, double* dGradGain, void* stream)
+{
+    const TickMismatch mm{dHiddenWrench, dForceGain, dGradHidden, dGradNoise, dGradGain};
+    return tick_vjp(h, dGradPrevListRot != nullptr, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan,
+                    dGradModel, dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream, &mm);
 }
 
 // ---- the reverse walk on the device tape (include/cmpc.h, cmpc_rollout_walk_vjp_device): gate, tick VJP, gate, ..., gate ----
@@ -1943,9 +2053,14 @@ int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g)
 // the loop of both reverse walks; r: the orientation chain of cmpc_rollout_walk_vjp_rot_device (checked by the caller), or null -- then every launch and
 // every bit is what the walk without orientations always queued and gave
 static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                    const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream)
+                    const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream, bool mismatch = false, const cmpc_plant_mismatch* m = nullptr,
+                    const cmpc_walk_grads_mismatch* mg = nullptr)
 {
     const std::string name(who);
+    {
+        const int mrc = mismatch_check(h, who, m);
+        if (mrc != CMPC_OK) return mrc;
+    }
     if (!h || !g || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, name + ": null argument or incomplete tape");
     if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows)
         return fail(h, CMPC_ERR_ARG, name + ": bad argument (the rows must lie inside the tape)");
@@ -2013,10 +2128,21 @@ static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0,
         tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
         tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
         tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
+        // the mismatch entry: tick rp ran under its own schedule rows; its gradient rows are written whether or not the tick lay inside a schedule's range
+        TickMismatch mm{};
+        if (mismatch) {
+            const float* unused;
+            mismatch_rows(m, B, tick0 + i - 1, &mm.hidden, &unused, &mm.gain);
+            if (mg) {
+                mm.g_hidden = mg->dGradHidden ? mg->dGradHidden + rp * B * 6 : nullptr;
+                mm.g_noise = mg->dGradNoise ? mg->dGradNoise + rp * B * 9 : nullptr;
+                mm.g_gain = mg->dGradGain;
+            }
+        }
         rc = tick_vjp(h, r != nullptr, M, (double)(tick0 + i - 1) * h->cfg.sampling_time, &tt, g->dCarryState, g->dCarryList, a.gx_out, wsState, wsList,
                       g->dGradWrench ? g->dGradWrench + rp * B * 6 * N : nullptr, g->dGradPlan, g->dGradModel, g->dGradP ? g->dGradP + rp * np : nullptr, wsSens,
                       r ? r->dCarryListRot : nullptr, r ? wsListRot : nullptr, r ? r->dGradPlanRot : nullptr,
-                      r && r->dGradRot ? r->dGradRot + rp * B * 6 * N : nullptr, stream);
+                      r && r->dGradRot ? r->dGradRot + rp * B * 6 * N : nullptr, stream, mismatch ? &mm : nullptr);
     }
     if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return rc;
@@ -2033,6 +2159,14 @@ int cmpc_rollout_walk_vjp_rot_device(cmpc_handle h, int max_contacts, int tick0,
 {
     if (!r || !r->dCarryListRot) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_device: r and its dCarryListRot are needed");
     return walk_vjp(h, "cmpc_rollout_walk_vjp_rot_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, r, stream);
+}
+
+int cmpc_rollout_walk_vjp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                          const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, const cmpc_plant_mismatch* m,
+                                          const cmpc_walk_grads_mismatch* mg, void* stream)
+{
+    if (r && !r->dCarryListRot) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_mismatch_device: r needs its dCarryListRot");
+    return walk_vjp(h, "cmpc_rollout_walk_vjp_mismatch_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, r, stream, true, m, mg);
 }
 
 // ---- one tick FORWARDS in k directions (include/cmpc.h): list JVP (merge + sample) -> the p direction assembled (cmpc_tick_jvp_assemble_kernel) ->

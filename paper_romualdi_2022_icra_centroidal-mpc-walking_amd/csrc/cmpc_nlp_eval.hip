@@ -1137,17 +1137,28 @@ namespace {
 
 // (problem b, one thread.  state_in / state_out may alias: everything is read before anything is written)
 // corners: [2][4][3] of problem 0; problem b's are corners_stride floats further on (0: one set for the batch; per-problem models: the stride of the records)
+// MM (cmpc_plant_mismatch, include/cmpc.h): the plant is not the model -- hidden[B][6] (or null: the term is not added) is a wrench the plant feels and dP
+// does not hold, gain[B] (or null: 1, no multiply) scales every corner force the plant applies.  Both are loaded up front with the state, whatever the
+// contact flags turn out to be, for the reason given at the force load below.  MM = false is the function without either, instruction for instruction.
+template <bool MM>
 __device__ inline void plant_step_problem(int N, int b, float grav, const float* __restrict__ corners, int corners_stride, const float* __restrict__ X,
                                           const float* __restrict__ P, const float* state_in, float* state_out, float* __restrict__ zmp, float h,
-                                          int nsub, float zx, float zy)
+                                          int nsub, float zx, float zy, const float* __restrict__ hidden, const float* __restrict__ gain)
 {
     CmpcIdx L{N};
     const float* x = X + (size_t)b * L.nx();
     const float* p = P + (size_t)b * L.np();
     double com[3], v[3], hm[3], fsum[3] = {0, 0, 0}, ext_t[3];
+    float hid[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gn = 1.f;
+    if (MM) {
+        if (hidden)
+            for (int i = 0; i < 6; ++i) hid[i] = hidden[(size_t)b * 6 + i];
+        if (gain) gn = gain[b];
+    }
     for (int i = 0; i < 3; ++i) {
         com[i] = state_in[(size_t)b * 9 + i]; v[i] = state_in[(size_t)b * 9 + 3 + i]; hm[i] = state_in[(size_t)b * 9 + 6 + i];
         ext_t[i] = p[L.pText() + i];
+        if (MM && hidden) ext_t[i] += (double)hid[3 + i];   // (tauExt_0 + tauHidden) + sum_q cp_q x f_q
     }
     // contact points (world) and forces of the active contacts at knot 0
     double cp[8][3], cf[8][3];
@@ -1162,7 +1173,8 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
             for (int i = 0; i < 3; ++i) {
                 cp[4 * c + j][i] = (double)x[L.oPos(c) + i] + (double)R[i] * cn[0] + (double)R[3 + i] * cn[1] + (double)R[6 + i] * cn[2];
                 const float fv = x[L.oF(c, j) + i];   // (loaded whatever `on` is: a load behind the contact flag is a second global-memory round trip on this one-thread chain)
-                cf[4 * c + j][i] = on ? (double)fv : 0.0;
+                if (MM && gain) cf[4 * c + j][i] = on ? (double)gn * (double)fv : 0.0;   // (the applied force: fsum, tau0 and the ZMP's F, T all see it)
+                else cf[4 * c + j][i] = on ? (double)fv : 0.0;
                 fsum[i] += cf[4 * c + j][i];
             }
             for (int i = 0; i < 3; ++i) fl[i] = (double)R[3 * i] * cf[4 * c + j][0] + (double)R[3 * i + 1] * cf[4 * c + j][1] + (double)R[3 * i + 2] * cf[4 * c + j][2];
@@ -1188,7 +1200,10 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
         tau0[1] += cp[q][2] * cf[q][0] - cp[q][0] * cf[q][2];
         tau0[2] += cp[q][0] * cf[q][1] - cp[q][1] * cf[q][0];
     }
-    for (int i = 0; i < 3; ++i) acc[i] = fsum[i] + (double)p[L.pFext() + i] - (i == 2 ? (double)grav : 0.0);
+    for (int i = 0; i < 3; ++i) {
+        if (MM && hidden) acc[i] = (fsum[i] + (double)p[L.pFext() + i]) + (double)hid[i] - (i == 2 ? (double)grav : 0.0);
+        else acc[i] = fsum[i] + (double)p[L.pFext() + i] - (i == 2 ? (double)grav : 0.0);
+    }
     auto deriv = [&](const double* cm, const double* vv, double* dcm, double* dv, double* dh) {
         for (int i = 0; i < 3; ++i) { dcm[i] = vv[i]; dv[i] = acc[i]; }
         dh[0] = tau0[0] - (cm[1] * fsum[2] - cm[2] * fsum[1]);
@@ -1219,14 +1234,16 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
     }
 }
 
+template <bool MM>
 __global__ __launch_bounds__(256) void cmpc_plant_step_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                               const float* __restrict__ X, const float* __restrict__ P,
                                                               const float* state_in, float* state_out,
-                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy)
+                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy,
+                                                              const float* __restrict__ hidden, const float* __restrict__ gain)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
+    plant_step_problem<MM>(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy, hidden, gain);
 }
 
 // ---- derivatives of the plant step (include/cmpc.h, "plant-step derivatives") ----
@@ -1241,10 +1258,15 @@ struct PlantPartials {
     double cp[8][3], cf[8][3]; // contact points and (gated) corner forces
     double cn[8][3];           // the corners themselves (rotation directions: d cp_q = R_c,0 (omega_c x cn_q))
     bool on[2];
+    double gain, fr[8][3];     // mismatch (MM): the force gain and the gated forces as the MPC gave them, cf = gain fr
 };
 
+// MM: the partials of the mismatched plant -- the same closed form with f_q -> gain f_q and fExt_0 -> fExt_0 + fHidden, so the point values
+// are taken at the gained forces and the summed wrench (tauHidden is an additive constant of tau0: no partial holds it).  hidden / gain null: as in the forward.
+template <bool MM = false>
 __device__ inline void plant_partials(int N, int b, float grav, const float* __restrict__ corners, int corners_stride, const float* __restrict__ X,
-                                      const float* __restrict__ P, const float* __restrict__ state_in, float h, int nsub, PlantPartials& q)
+                                      const float* __restrict__ P, const float* __restrict__ state_in, float h, int nsub, PlantPartials& q,
+                                      const float* __restrict__ hidden = nullptr, const float* __restrict__ gain = nullptr)
 {
     const CmpcIdx L{N};
     const float* x = X + (size_t)b * L.nx();
@@ -1259,15 +1281,22 @@ __device__ inline void plant_partials(int N, int b, float grav, const float* __r
             for (int i = 0; i < 3; ++i) {
                 q.cp[4 * c + j][i] = (double)x[L.oPos(c) + i] + (double)R[i] * cn[0] + (double)R[3 + i] * cn[1] + (double)R[6 + i] * cn[2];
                 const float fv = x[L.oF(c, j) + i];
-                q.cf[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
+                if (MM) {
+                    q.fr[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
+                    if (gain) q.cf[4 * c + j][i] = q.on[c] ? (double)gain[b] * (double)fv : 0.0;
+                    else q.cf[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
+                } else q.cf[4 * c + j][i] = q.on[c] ? (double)fv : 0.0;
                 q.F[i] += q.cf[4 * c + j][i];
                 q.cn[4 * c + j][i] = (double)cn[i];
             }
         }
     }
     const double T = q.T;
+    if (MM) q.gain = gain ? (double)gain[b] : 1.0;
     for (int i = 0; i < 3; ++i) {
-        const double a = q.F[i] + (double)p[L.pFext() + i] - (i == 2 ? (double)grav : 0.0);
+        double a;
+        if (MM && hidden) a = (q.F[i] + (double)p[L.pFext() + i]) + (double)hidden[(size_t)b * 6 + i] - (i == 2 ? (double)grav : 0.0);
+        else a = q.F[i] + (double)p[L.pFext() + i] - (i == 2 ? (double)grav : 0.0);
         q.I[i] = T * (double)state_in[(size_t)b * 9 + i] + 0.5 * T * T * (double)state_in[(size_t)b * 9 + 3 + i] + T * T * T / 6.0 * a;
     }
 }
@@ -1331,10 +1360,12 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
 // transposed: gs' -> (gs, gx (the 30 entries it owns), gp (fExt_0, tauExt_0), gtheta (corners), gomega_0).  grad_state may alias grad_out; null outputs are
 // skipped.  ROT: grad_rot[B][2][3], the transpose of the JVP's rotation term: <gcp, R (omega x cn)> = <omega, cn x R^T gcp>, summed over the foot's corners
 // in corner order (a gated-off foot has gcp = 0: zeros).
-template <bool ROT>
+// MM: grad_hidden[B][6] = the plant's own gradient on fExt_0 / tauExt_0, unrounded; grad_x on the 24 forces = gain dl/d(gain f); grad_gain[B] = sum over the
+// gated-on corners, in corner order, of <dl/d(gain f_q), f_q> (both written; either may be null).
+template <bool ROT, bool MM = false>
 __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* grad_out, double* grad_state,
                                          float* __restrict__ grad_x, float* __restrict__ grad_p, double* __restrict__ grad_model,
-                                         double* __restrict__ grad_rot)
+                                         double* __restrict__ grad_rot, double* __restrict__ grad_hidden = nullptr, double* __restrict__ grad_gain = nullptr)
 {
     const CmpcIdx L{N};
     const float* p = P + (size_t)b * L.np();
@@ -1350,8 +1381,10 @@ __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__
         grad_state[(size_t)b * 9 + 3 + i] = T * gc[i] + gv[i] + 0.5 * T * T * gI[i];
         grad_state[(size_t)b * 9 + 6 + i] = gh[i];
         if (grad_p) { grad_p[(size_t)b * L.np() + L.pFext() + i] = (float)ga[i]; grad_p[(size_t)b * L.np() + L.pText() + i] = (float)(T * gh[i]); }
+        if (MM && grad_hidden) { grad_hidden[(size_t)b * 6 + i] = ga[i]; grad_hidden[(size_t)b * 6 + 3 + i] = T * gh[i]; }
     }
     double gtau[3] = {T * gh[0], T * gh[1], T * gh[2]};
+    double ggain = 0.0;
     for (int c = 0; c < 2; ++c) {
         const float* R = p + L.pR(c);
         double gpos[3] = {0, 0, 0}, grot[3] = {0, 0, 0};
@@ -1361,7 +1394,11 @@ __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__
             cross3(gtau, q.cp[4 * c + j], gf);    // <gtau, cp x df> = <df, gtau x cp>
             for (int i = 0; i < 3; ++i) {
                 gpos[i] += gcp[i];
-                if (grad_x) grad_x[(size_t)b * L.nx() + L.oF(c, j) + i] = q.on[c] ? (float)(gf[i] + gF[i]) : 0.f;
+                if (MM) {
+                    const double ga_f = gf[i] + gF[i];   // dl / d(gain f_q)
+                    if (grad_x) grad_x[(size_t)b * L.nx() + L.oF(c, j) + i] = q.on[c] ? (float)(q.gain * ga_f) : 0.f;
+                    if (q.on[c]) ggain += ga_f * q.fr[4 * c + j][i];
+                } else if (grad_x) grad_x[(size_t)b * L.nx() + L.oF(c, j) + i] = q.on[c] ? (float)(gf[i] + gF[i]) : 0.f;
             }
             if (grad_model)
                 for (int a = 0; a < 3; ++a)   // R^T gcp: column a of R (col-major) against gcp
@@ -1380,6 +1417,7 @@ __device__ inline void plant_vjp_problem(int N, int b, const float* __restrict__
     }
     if (grad_model)
         for (int i = 0; i < 10; ++i) grad_model[(size_t)b * CMPC_MODEL_DOUBLES + i] = 0.0;
+    if (MM && grad_gain) grad_gain[b] = ggain;
 }
 
 template <bool ROT>
@@ -1422,17 +1460,19 @@ __global__ __launch_bounds__(256) void cmpc_plant_jvp_cols_kernel(int N, int B, 
                            dir_model ? dir_model + col * CMPC_MODEL_DOUBLES : nullptr, ROT ? dir_rot + col * 6 : nullptr, out + col * 9);
 }
 
-template <bool ROT>
+template <bool ROT, bool MM>
 __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* __restrict__ state_in,
                                                              float h, int nsub, const double* grad_out, double* grad_state, float* __restrict__ grad_x,
-                                                             float* __restrict__ grad_p, double* __restrict__ grad_model, double* __restrict__ grad_rot)
+                                                             float* __restrict__ grad_p, double* __restrict__ grad_model, double* __restrict__ grad_rot,
+                                                             const float* __restrict__ hidden, const float* __restrict__ gain,
+                                                             double* __restrict__ grad_hidden, double* __restrict__ grad_gain)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     PlantPartials q;
-    plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
-    plant_vjp_problem<ROT>(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model, grad_rot);
+    plant_partials<MM>(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q, hidden, gain);
+    plant_vjp_problem<ROT, MM>(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model, grad_rot, grad_hidden, grad_gain);
 }
 
 // ---- the two ends of a roll-out tick as ONE launch each (cmpc_rollout_tick_device).  At B <= 256 a tick is a 0.66 ms solve between nine launches of a
@@ -1453,7 +1493,7 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
                                                             const float* __restrict__ Xprev, float* __restrict__ X0, const float* __restrict__ plan_com,
                                                             const float* __restrict__ plan_h, int plan_knots, double plan_dt, double plan_t_offset,
                                                             double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok,
-                                                            const int* __restrict__ ended)
+                                                            const int* __restrict__ ended, const float* __restrict__ noise)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device: the whole workgroup, ahead of its first barrier -- nothing of the problem is written)
@@ -1465,7 +1505,9 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
     if (tid < 2) foot_ok[tid] = snap_ok ? snap_ok[2 * b + tid] : 1;
     __syncthreads();
     // setState and the warm-start shift first (they depend on nothing the kernel computes: their memory traffic runs under the merge of threads 0, 1)
-    for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e];
+    // (noise: this tick's row [B][9] of cmpc_plant_mismatch.dStateNoise or null -- the MPC measures state + noise, one float32 add; the plant keeps the state)
+    if (noise) for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e] + noise[9 * (size_t)b + e];
+    else for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e];
     if (wrench)
         for (int e = tid; e < 3 * N; e += 256) {
             const int k = e / 3, i = e % 3;
@@ -1564,16 +1606,19 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
 }
 
 // post: one thread per problem -- the plant step, then the step adjustment of its two feet (getOutput().contactPhaseList)
+// MM: the mismatched plant (this tick's hidden-wrench row and the force gain, plant_step_problem); false is the kernel without it
+template <bool MM>
 __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy, const int* __restrict__ land,
                                                              const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n,
-                                                             const int* __restrict__ ended)
+                                                             const int* __restrict__ ended, const float* __restrict__ hidden,
+                                                             const float* __restrict__ gain)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device; per lane, as the line above: nothing behind it needs the whole wave)
-    plant_step_problem(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy);
+    plant_step_problem<MM>(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy, hidden, gain);
     const CmpcIdx L{N};
     for (int c = 0; c < 2; ++c) {
         const int e = 2 * b + c, lk = land[e];
@@ -1785,29 +1830,37 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
                                     int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, hipStream_t stream)
+                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, const float* noise, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_tick_pre_kernel, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
                        list_t, list_pose, list_n, ok, land, box, state, wrench, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, plan_t_offset, robot_mass,
-                       com_height, snap_dt_ns, snap_ok, ended);
+                       com_height, snap_dt_ns, snap_ok, ended, noise);
     return (int)hipGetLastError();
 }
 
 extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
-                                     const double* t, float* pose, const int* n, const int* ended, hipStream_t stream)
+                                     const double* t, float* pose, const int* n, const int* ended, const float* hidden, const float* gain, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_tick_post_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn, dStateOut, dZmp,
-                       h, nsub, zx, zy, land, t, pose, n, ended);
+    if (hidden || gain)
+        hipLaunchKernelGGL(cmpc_tick_post_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn,
+                           dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain);
+    else
+        hipLaunchKernelGGL(cmpc_tick_post_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn,
+                           dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain);
     return (int)hipGetLastError();
 }
 
 extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                       const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
-                                      hipStream_t stream)
+                                      const float* dHidden, const float* dGain, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_plant_step_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn,
-                       dStateOut, dZmp, h, nsub, zx, zy);
+    if (dHidden || dGain)   // (both null: the instantiation without the mismatch, which is the kernel as it was before the mismatch existed)
+        hipLaunchKernelGGL(cmpc_plant_step_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn,
+                           dStateOut, dZmp, h, nsub, zx, zy, dHidden, dGain);
+    else
+        hipLaunchKernelGGL(cmpc_plant_step_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn,
+                           dStateOut, dZmp, h, nsub, zx, zy, dHidden, dGain);
     return (int)hipGetLastError();
 }
 
@@ -1843,19 +1896,21 @@ extern "C" int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const
 // dGradX / dGradP: the whole rows are cleared first (the kernel writes the entries the plant reads, nothing else)
 extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                      const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
-                                     double* dGradModel, double* dGradRot0, hipStream_t stream)
+                                     double* dGradModel, double* dGradRot0, int mismatch, const float* dHidden, const float* dGain, double* dGradHidden,
+                                     double* dGradGain, hipStream_t stream)
 {
     const CmpcIdx L{N};
     hipError_t e = hipSuccess;
     if (dGradX) e = hipMemsetAsync(dGradX, 0, sizeof(float) * (size_t)B * L.nx(), stream);
     if (e == hipSuccess && dGradP) e = hipMemsetAsync(dGradP, 0, sizeof(float) * (size_t)B * L.np(), stream);
     if (e != hipSuccess) return (int)e;
-    if (dGradRot0)
-        hipLaunchKernelGGL(cmpc_plant_vjp_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
-                           nsub, dGradOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0);
-    else
-        hipLaunchKernelGGL(cmpc_plant_vjp_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
-                           nsub, dGradOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0);
+    // mismatch != 0: the instantiations of the mismatched plant (dHidden / dGain may still be null); 0: the kernels as they were before it existed
+#define CMPC_PLANT_VJP(ROT, MM)                                                                                                                              \
+    hipLaunchKernelGGL((cmpc_plant_vjp_kernel<ROT, MM>), dim3((B + 255) / 256), dim3(256), 0, stream, N, B, grav, dCorners, corners_stride, dX, dP, dStateIn, h, \
+                       nsub, dGradOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, dHidden, dGain, dGradHidden, dGradGain)
+    if (mismatch) { if (dGradRot0) CMPC_PLANT_VJP(true, true); else CMPC_PLANT_VJP(false, true); }
+    else { if (dGradRot0) CMPC_PLANT_VJP(true, false); else CMPC_PLANT_VJP(false, false); }
+#undef CMPC_PLANT_VJP
     return (int)hipGetLastError();
 }
 

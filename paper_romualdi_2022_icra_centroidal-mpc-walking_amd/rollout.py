@@ -146,6 +146,8 @@ class WalkingRollout:
         """The roll-out (see _run for the arguments), with the solver's launch stream as torch's current stream: every device call of a tick -- the library's
         kernels and the torch ops between them -- is then queued on ONE non-default stream, in order, without the event dependencies a call from the default
         stream needs (BatchSolver._stream_pair: two per call, ~24 us of idle GPU each time)."""
+        if kwargs.pop("mismatch", None) is not None:
+            raise NotImplementedError("run(): a plant mismatch is taken by the device walk only (walk_device_mismatch, walk_device_taped(mismatch=...))")
         torch = self.torch
         ls = self.solver.launch_stream
         cur = torch.cuda.current_stream(self.dev)
@@ -177,6 +179,27 @@ class WalkingRollout:
         included, unlike final_state).  The same walk with a device tape for backward_device(): walk_device_taped()."""
         return self._walk_on_launch_stream(False, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
 
+    def _mismatch_of(self, mismatch):
+        """mismatch (None, a dict of hidden_wrench / state_noise / force_gain / tick_first, or a BatchSolver.plant_mismatch dict) -> the solver's dict, or None
+        when nothing is set (zero-length schedules count as absent): the walk is then the plain one, call for call"""
+        if mismatch is None:
+            return None
+        m = mismatch if "_c" in mismatch else self.solver.plant_mismatch(device=self.dev, **mismatch)
+        return None if all(m[k] is None for k in ("hidden_wrench", "state_noise", "force_gain")) else m
+
+    def walk_device_mismatch(self, ticks, com0, dcom0, h0, mismatch, **kwargs):
+        """walk_device(ticks, com0, dcom0, h0, **kwargs) with a plant that is NOT the model (cmpc_rollout_walk_mismatch_device, include/cmpc.h):
+        mismatch = dict(hidden_wrench=[Th, B, 6], state_noise=[Tn, B, 9], force_gain=[B], tick_first=0), any subset, numpy or CUDA float32 --
+        hidden_wrench[r] is a mass-normalised force | torque the plant feels at tick tick_first + r and the MPC is never told about (push= is the wrench it
+        IS told about), state_noise[r] is added to the state the MPC measures at that tick (the plant keeps the true one), force_gain scales every corner
+        force the plant applies (a mass error: m_nominal / m_true).  Outside a schedule's rows the term is not applied.  Per problem; no launch more per
+        tick, no host read.  The same with a tape: walk_device_taped(mismatch=...); checkpointed: walk_device_checkpointed(mismatch=...); from a snapshot:
+        walk_resume_device_mismatch().  mismatch=None, or one with nothing set: walk_device, bit for bit.  (A method of its own and not an argument of
+        walk_device: that signature is pinned.)"""
+        args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
+        args.apply_defaults()
+        return self._walk_on_launch_stream(False, *args.args, **args.kwargs, mismatch=mismatch)
+
     def walk_device_taped(self, ticks, com0, dcom0, h0, **kwargs):
         """walk_device(ticks, com0, dcom0, h0, **kwargs) through cmpc_rollout_walk_taped_device: every tick also writes its row of a device tape -- what
         backward_device() needs; about 12 KB per problem and tick at N = 20 -- and the dict gains "tape": the stacked tensors X, P, lam_g, info
@@ -184,12 +207,15 @@ class WalkingRollout:
         force_sample_time, push_ticks, segments (the first tick of each call), references (knots, dt, t_first, robot_mass, com_height of the planner's CoM /
         angular-momentum trajectories: set_references', else the straight line's).  The multiplier output is turned on first, as run(tape=True) does (x and info
         are bit-identical with it on): every other returned array is bit-identical to walk_device's.  Still no host read; works with replan and skip_ended
-        (an ended problem's later rows then hold its ending tick's data).  (A method of its own and not an argument of walk_device: that signature is pinned.)"""
+        (an ended problem's later rows then hold its ending tick's data).  (A method of its own and not an argument of walk_device: that signature is pinned.)
+        mismatch= (walk_device_mismatch's argument): the walk runs under it, the tape keeps it alive in tape["mismatch"], and backward_device[_rot, _refs]
+        then differentiate the mismatched plant and return three more keys."""
+        mismatch = kwargs.pop("mismatch", None)
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
-        return self._walk_on_launch_stream(True, *args.args, **args.kwargs)
+        return self._walk_on_launch_stream(True, *args.args, **args.kwargs, mismatch=mismatch)
 
-    def _walk_on_launch_stream(self, tape, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended):
+    def _walk_on_launch_stream(self, tape, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
         torch = self.torch
         assert self.retry != "launch", "walk_device needs retry='kernel' or None"
         ls = self.solver.launch_stream
@@ -197,13 +223,14 @@ class WalkingRollout:
         ls.wait_stream(cur)
         try:
             with torch.cuda.stream(ls):
-                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, tape)
+                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, tape, mismatch)
         finally:
             cur.wait_stream(ls)
 
-    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False, tape=False):
+    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False, tape=False, mismatch=None):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
+        mm = self._walk_mismatch = self._mismatch_of(mismatch)    # (kept until the next call: the queued launches read its tensors)
         # (a numpy input is uploaded without the host waiting for the copy; a CUDA tensor is used as it is)
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
 
@@ -244,7 +271,7 @@ class WalkingRollout:
                 wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
                 cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
                                             wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                            force_sample_time=self.force_sample_time, tape=tp)
+                                            force_sample_time=self.force_sample_time, tape=tp, mismatch=mm)
         finally:
             if skip_ended:
                 s.set_ended_device(None)
@@ -252,6 +279,8 @@ class WalkingRollout:
         if tp is not None:
             tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, segments=starts,
                       references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
+            if mm is not None:
+                tp["mismatch"] = mm
             rec["tape"] = tp
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
         return rec
@@ -553,6 +582,9 @@ class WalkingRollout:
         if refs:
             n_ref = tape["references"]["knots"]
             out.update(grad_P=z((T, B, L.np), torch.float32), ref_com=z((B, n_ref, 3)), ref_h=z((B, n_ref, 3)))
+        mm = tape.get("mismatch")
+        if mm is not None:    # (the tape of a mismatched walk: cmpc_rollout_walk_vjp_mismatch_device, and three more keys)
+            out.update(hidden_wrench=z((T, B, 6)), state_noise=z((T, B, 9), torch.float32), force_gain=z((B,)))
         starts = list(tape["segments"])
         ls = s.launch_stream
         cur = torch.cuda.current_stream(self.dev)
@@ -564,7 +596,8 @@ class WalkingRollout:
                 t0, t1 = starts[j], starts[j + 1] if j + 1 < len(starts) else T
                 s.rollout_walk_vjp_device(t0, t1 - t0, tape, t0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, wrench=out["wrench"],
                                           grad_p=out.get("grad_P"), dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
-                                          grad_rot=out.get("rot"), removed=out.get("removed"))
+                                          grad_rot=out.get("rot"), removed=out.get("removed"), mismatch=mm, grad_hidden=out.get("hidden_wrench"),
+                                          grad_noise=out.get("state_noise"), grad_gain=out.get("force_gain"))
             for i in reversed(range(min(T, tape["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
                 out["push"] += out["wrench"][i][:, :max(tape["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
             out["state0"], out["list0"] = g, gl
@@ -616,7 +649,8 @@ class WalkingRollout:
             wt[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
         return wt
 
-    def _walk_live(self, live, t0, t1, row_shift, plans, base_plan, wrench, refs, skip_ended, every=None, tape=None, tape_shift=0, cold=False, states=None):
+    def _walk_live(self, live, t0, t1, row_shift, plans, base_plan, wrench, refs, skip_ended, every=None, tape=None, tape_shift=0, cold=False, states=None,
+                   mismatch=None):
         """Queues ticks t0 .. t1 - 1 on the live buffers (a snapshot dict whose "rec" is the walk record): one call of the C ABI per entry of
         walk_schedule, a snapshot launch in front of each tick k * every.  Record row = tick - row_shift, tape row = tick - tape_shift.  plans {tick:
         plan}: the latest entry at or before a tick is the plan in force (none: base_plan).  wrench = (wrench_ticks[T, B, N, 6], the tick of its row 0) or
@@ -638,7 +672,7 @@ class WalkingRollout:
                 cur = s.rollout_walk_device(a, b - a, cold and a == t0, plan_at(a), sets[0], sets[1], cur, live["ok"], live["land"], live["state"], live["P"],
                                             live["X0"], live["X"], live["info"], live["zmp"], rec, row0=a - row_shift, wrench_ticks=wr,
                                             step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
-                                            tape=tape, tape_row0=a - tape_shift)
+                                            tape=tape, tape_row0=a - tape_shift, mismatch=mismatch)
                 if states is not None:
                     states[b - row_shift].copy_(live["state"])
         finally:
@@ -654,12 +688,14 @@ class WalkingRollout:
         problem at N = 20) and "inputs", the small things a re-run needs, by reference: state0, the wrench schedule and push_ticks, the plans of replan
         and the plan in force at tick 0, the references, stop, skip_ended, ticks, every.  Like walk_device: no host read and no synchronisation.
         Continue or fork from a checkpoint: walk_resume_device().  The gradient without a whole-walk tape: backward_device_checkpointed()."""
+        mismatch = kwargs.pop("mismatch", None)    # (walk_device_mismatch's argument; kept in "inputs" -- the checkpointed reverse walk refuses it)
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
-        return self._queued(lambda: self._walk_checkpointed(every, None, *args.args, **args.kwargs))
+        return self._queued(lambda: self._walk_checkpointed(every, None, *args.args, **args.kwargs, mismatch=mismatch))
 
-    def _walk_checkpointed(self, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended):
+    def _walk_checkpointed(self, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
         torch, dev, s = self.torch, self.dev, self.solver
+        mm = self._mismatch_of(mismatch)
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
 
         def up(a):
@@ -677,8 +713,8 @@ class WalkingRollout:
         if states is not None:
             states[0].copy_(state0)
         inputs = dict(state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
-                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every))
-        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states)
+                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every), mismatch=mm)
+        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states, mismatch=mm)
         for c in cps.values():
             c["wrench"] = wrench
         del rec["_c"]
@@ -707,8 +743,19 @@ class WalkingRollout:
         robots -- a walk has no per-problem cold tick."""
         return self._queued(lambda: self._walk_resume(snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every))
 
-    def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every):
+    def walk_resume_device_mismatch(self, snapshot, ticks, mismatch, **kwargs):
+        """walk_resume_device(snapshot, ticks, **kwargs) under a plant mismatch (walk_device_mismatch's argument; tick_first is a tick number of the whole
+        walk, so a push from the resume tick on has tick_first = snapshot["tick"]).  The headline use: one pilot walk, one snapshot, index = zeros, and B
+        different hidden pushes -- the same mid-gait robot pushed B ways, none of which the MPC is told about.  Problem b is bit-equal to the unbroken walk
+        of a batch whose problem b carries that mismatch.  taped=True: the tape keeps the mismatch in tape["mismatch"].  (A method of its own: the
+        signature of walk_resume_device is pinned.)"""
+        args = inspect.signature(self.walk_resume_device).bind(snapshot, ticks, **kwargs)
+        args.apply_defaults()
+        return self._queued(lambda: self._walk_resume(*args.args, **args.kwargs, mismatch=mismatch))
+
+    def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every, mismatch=None):
         torch, dev, s, B = self.torch, self.dev, self.solver, self.B
+        mm = self._walk_mismatch = self._mismatch_of(mismatch)
         self._walk_inputs = hold = []
 
         def up(a, dt, np_dt):
@@ -740,10 +787,12 @@ class WalkingRollout:
             prev = live["lists"][live["lists_in"]]
             tp["list_t"][0].copy_(prev[0])
             tp["list_n"][0].copy_(prev[2])
-        cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1)
+        cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1, mismatch=mm)
         del rec["_c"]
         if tp is not None:
             tp.update(dt=self.cfg.sampling_time, tick0=t0, row0=1)
+            if mm is not None:
+                tp["mismatch"] = mm
             rec["tape"] = tp
         if every is not None:
             rec["checkpoints"] = cps
@@ -769,6 +818,8 @@ class WalkingRollout:
     def _backward_checkpointed(self, w, grad_states, grad_X, rot):
         torch, B, N, L, M, s, dev = self.torch, self.B, self.cfg.N, self.L, self.M, self.solver, self.dev
         inp, cps = w["inputs"], w["checkpoints"]
+        if inp.get("mismatch") is not None:
+            raise NotImplementedError("backward_device_checkpointed: the walk ran under a plant mismatch; its reverse is backward_device on walk_device_taped(mismatch=...)")
         T, every = inp["ticks"], inp["every"]
         as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(dev, dt).contiguous()
         gS = as_t(grad_states, torch.float64)
@@ -915,6 +966,8 @@ class WalkingRollout:
                                     dir_wrench, solutions):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
+        if tape.get("mismatch") is not None:    # (the tick JVP takes its partials at the MPC's forces and wrench: on this tape it would be silently wrong)
+            raise NotImplementedError("forward_sensitivity_device: the tape carries a plant mismatch; forward mode does not know it (use backward_device)")
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
 
         def as_dir(a, dtype, tail, lead=()):
@@ -1023,7 +1076,7 @@ def rot_plan_poses(pose, plan_rot):
 
 
 def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, plan_yaw=None, device_walk=False, replan=None,
-                           plan_rot=None, ref_com=None, ref_h=None):
+                           plan_rot=None, hidden_wrench=None, state_noise=None, force_gain=None, ref_com=None, ref_h=None):
     """The closed loop as a torch.autograd.Function, in the shape of solver.solve_differentiable: forward runs rollout.run(ticks, ..., tape=True) from
     state0[B, 9] (com, dcom, h; a CUDA tensor) under push[B, 3] (held for the first push_ticks ticks) and returns the states [ticks + 1, B, 9] float32
     (state0 first); backward is WalkingRollout.backward and returns state0.grad, push.grad and models.grad.  models: None, or a [B, 34] float64 CUDA
@@ -1052,7 +1105,15 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     rollout.set_references installed (or of the default straight line); their timing, robot_mass and com_height are what it installed, or the default
     line's (a knot every dt from time zero, mass 1, height 0.7).  The walk reads them as float32.  Only with device_walk=True (NotImplementedError
     otherwise, before anything touches a GPU): backward is then WalkingRollout.backward_device_refs and returns ref_com.grad / ref_h.grad, forward mode
-    takes their tangents through forward_sensitivity_device_refs.  The fold and select for the rows behind a problem's end are the same."""
+    takes their tangents through forward_sensitivity_device_refs.  The fold and select for the rows behind a problem's end are the same.
+    hidden_wrench [Th, B, 6] / state_noise [Tn, B, 9] / force_gain [B]: None, or torch tensors: the plant mismatch of WalkingRollout.walk_device_mismatch
+    with tick_first = 0 (a wrench the MPC is not told about, noise on the state it measures, a gain on the forces the plant applies).  Only with
+    device_walk=True (NotImplementedError otherwise, before anything touches a GPU): backward returns their .grad from the keys hidden_wrench,
+    state_noise and force_gain of backward_device (rows behind Th / Tn have no input to receive theirs).  Forward mode over a mismatched walk raises
+    NotImplementedError."""
+    mismatched = hidden_wrench is not None or state_noise is not None or force_gain is not None
+    if mismatched and not device_walk:
+        raise NotImplementedError("rollout_differentiable: hidden_wrench / state_noise / force_gain need device_walk=True")
     if (ref_com is not None or ref_h is not None) and not device_walk:
         raise NotImplementedError("rollout_differentiable: ref_com / ref_h need device_walk=True")
     import torch
@@ -1062,7 +1123,8 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     if device_walk:
         if plan_yaw is not None:
             raise NotImplementedError("rollout_differentiable(device_walk=True): plan_yaw is not taken on the device path; pass the yaw as plan_rot[..., 2]")
-        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot, ref_com, ref_h)
+        return _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot, ref_com, ref_h,
+                                              (hidden_wrench, state_noise, force_gain) if mismatched else None)
     if replan is not None:
         raise NotImplementedError("rollout_differentiable: replan needs device_walk=True")
 
@@ -1136,13 +1198,20 @@ def _jr_applied(jr, t):
     return (jr * t[..., None, :]).sum(-1)
 
 
-def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None, ref_com=None, ref_h=None):
-    """rollout_differentiable(device_walk=True)"""
+def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None, ref_com=None, ref_h=None, mismatch=None):
+    """rollout_differentiable(device_walk=True); mismatch: None, or (hidden_wrench, state_noise, force_gain), each a tensor or None"""
     import torch
+    hidden, noise, gain = mismatch if mismatch is not None else (None, None, None)
 
     class _Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, state0, push, models, plan_rot, ref_com, ref_h):
+        def forward(ctx, state0, push, models, plan_rot, ref_com, ref_h, hidden, noise, gain):
+            mm = None
+            if mismatch is not None:
+                det = lambda a: None if a is None else a.detach().to(rollout.dev, torch.float32).contiguous()
+                mm = dict(hidden_wrench=det(hidden), state_noise=det(noise), force_gain=det(gain), tick_first=0)
+            ctx.mm_meta = tuple(None if a is None else (a.dtype, int(a.shape[0])) for a in (hidden, noise, gain))
+            assert all(a is None or 1 <= a.shape[0] <= ticks for a in (hidden, noise)), "hidden_wrench / state_noise: between 1 and `ticks` rows"
             if models is not None:
                 rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
@@ -1163,7 +1232,7 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             try:
                 w = rollout.walk_device_taped(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9],
                                               push=None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks=push_ticks,
-                                              replan=plans, trace=False)
+                                              replan=plans, trace=False, mismatch=mm)
             finally:
                 rollout.plan = plan
                 rollout._ref_override = None
@@ -1189,10 +1258,16 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
                     r["models"] if ctx.needs_input_grad[2] else None,
                     _jr_transposed(ctx.jr, r["plan_rot"] + r["list_rot0"]) if ctx.jr is not None and ctx.needs_input_grad[3] else None,
                     r["ref_com"].to(ctx.ref_dtypes[0]) if ctx.ref_dtypes[0] is not None and ctx.needs_input_grad[4] else None,
-                    r["ref_h"].to(ctx.ref_dtypes[1]) if ctx.ref_dtypes[1] is not None and ctx.needs_input_grad[5] else None)
+                    r["ref_h"].to(ctx.ref_dtypes[1]) if ctx.ref_dtypes[1] is not None and ctx.needs_input_grad[5] else None,
+                    # (a schedule shorter than the walk: the rows behind it have no input; a tape without a mismatch has none of the keys)
+                    r["hidden_wrench"][:ctx.mm_meta[0][1]].to(ctx.mm_meta[0][0]) if ctx.mm_meta[0] is not None and ctx.needs_input_grad[6] else None,
+                    r["state_noise"][:ctx.mm_meta[1][1]].to(ctx.mm_meta[1][0]) if ctx.mm_meta[1] is not None and ctx.needs_input_grad[7] else None,
+                    r["force_gain"].to(ctx.mm_meta[2][0]) if ctx.mm_meta[2] is not None and ctx.needs_input_grad[8] else None)
 
         @staticmethod
-        def jvp(ctx, t_state0, t_push, t_models, t_rot, t_ref_com, t_ref_h):
+        def jvp(ctx, t_state0, t_push, t_models, t_rot, t_ref_com, t_ref_h, t_hidden=None, t_noise=None, t_gain=None):
+            if mismatch is not None:
+                raise NotImplementedError("rollout_differentiable: forward mode does not know the plant mismatch (use backward)")
             """torch.autograd.forward_ad: forward_sensitivity_device at k = 1 on the tape the forward left.  The returned states hold final_state in the
             rows behind a problem's end, so those rows take the tangent of the row its final state sits in: the transpose of backward's fold."""
             col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
@@ -1211,7 +1286,7 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             at_end = t.gather(0, e[None, :, None].expand(1, rollout.B, 9))      # [1, B, 9]: each problem's row e (row 0 where it never ended: not selected)
             return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
-    return _Fn.apply(state0, push, models, plan_rot, ref_com, ref_h)
+    return _Fn.apply(state0, push, models, plan_rot, ref_com, ref_h, hidden, noise, gain)
 
 
 def rollout_differentiable_checkpointed(rollout: WalkingRollout, ticks, state0, every, push=None, models=None, push_ticks=0, replan=None):

@@ -480,6 +480,68 @@ class BatchSolver:
         return dStateOut, dZmp
 
 
+    # ---- plant-model mismatch (include/cmpc.h, "plant-model mismatch on the device walk"; DESIGN.md 7f, "Mismatch") ----
+    def plant_mismatch(self, hidden_wrench=None, state_noise=None, force_gain=None, tick_first=0, device=None):
+        """A cmpc_plant_mismatch as a dict: hidden_wrench[Th, B, 6], state_noise[Tn, B, 9], force_gain[B] float32 (numpy or CUDA tensors, any subset; a
+        schedule of zero rows counts as absent), tick_first the tick number of row 0 of the two schedules.  The dict keeps the device tensors alive and holds
+        "_c", the C struct that points at them."""
+        import torch
+        B = self.batch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        hold = []
+
+        def up(a, tail, name):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
+                hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+                a = hold[-1].to(dev, non_blocking=True)
+            t = a
+            t = t.detach().to(dev, torch.float32).contiguous()
+            assert tuple(t.shape[-len(tail):]) == tuple(tail) and t.dim() == len(tail) + (0 if name == "force_gain" else 1), f"{name}: expected [.., {tail}]"
+            return t if t.numel() > 0 else None
+        m = dict(hidden_wrench=up(hidden_wrench, (B, 6), "hidden_wrench"), state_noise=up(state_noise, (B, 9), "state_noise"),
+                 force_gain=up(force_gain, (B,), "force_gain"), tick_first=int(tick_first))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rows = lambda t: 0 if t is None else int(t.shape[0])
+        m["_host"] = hold
+        m["_c"] = _capi.CmpcPlantMismatch(int(tick_first), ptr(m["hidden_wrench"]), rows(m["hidden_wrench"]), ptr(m["state_noise"]), rows(m["state_noise"]),
+                                          ptr(m["force_gain"]))
+        return m
+
+    def plant_step_mismatch_device(self, dX, dP, dState, dStateOut=None, dZmp=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03,
+                                   hidden_wrench=None, force_gain=None):
+        """cmpc_plant_step_mismatch_device: plant_step_device under one tick's hidden wrench hidden_wrench[B, 6] and the force gain force_gain[B] (float32
+        CUDA tensors; None: not applied -- both None is plant_step_device bit for bit); returns (state[B,9], zmp[B,2])."""
+        import torch
+        B = self.batch
+        if dStateOut is None:
+            dStateOut = torch.empty_like(dState)
+        if dZmp is None:
+            dZmp = torch.empty((B, 2), dtype=torch.float32, device=dState.device)
+        ph, pg = self._opt(hidden_wrench, torch.float32, (B, 6), "hidden_wrench"), self._opt(force_gain, torch.float32, (B,), "force_gain")
+        self._launch(dState.device, lambda st: self._lib.cmpc_plant_step_mismatch_device(
+            self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), dStateOut.data_ptr(), dZmp.data_ptr(), float(step), int(substeps), float(zmp_half_x),
+            float(zmp_half_y), ph, pg, st))
+        return dStateOut, dZmp
+
+    def plant_step_vjp_mismatch_device(self, dX, dP, dState, dGradStateOut, step=0.01, substeps=6, hidden_wrench=None, force_gain=None, grad_rot=False):
+        """cmpc_plant_step_vjp_mismatch_device: plant_step_vjp_device at the mismatched plant (hidden_wrench[B, 6], force_gain[B] float32 or None) ->
+        dict(state[B,9] f64, x[B,n_x] f32, p[B,n_p] f32, model[B,34] f64, rot0[B,2,3] f64 or None, hidden[B,6] f64, gain[B] f64)."""
+        import torch
+        L, B, dev = self.layout, self.batch, dX.device
+        f32, f64 = torch.float32, torch.float64
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(state=e((B, 9), f64), x=e((B, L.nx), f32), p=e((B, L.np), f32), model=e((B, _capi.MODEL_DOUBLES), f64),
+                   rot0=e((B, 2, 3), f64) if grad_rot else None, hidden=e((B, 6), f64), gain=e((B,), f64))
+        pg = self._opt(dGradStateOut, f64, (B, 9), "dGradStateOut")
+        ph, pk = self._opt(hidden_wrench, f32, (B, 6), "hidden_wrench"), self._opt(force_gain, f32, (B,), "force_gain")
+        self._launch(dev, lambda st: self._lib.cmpc_plant_step_vjp_mismatch_device(
+            self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step), int(substeps), pg, out["state"].data_ptr(), out["x"].data_ptr(),
+            out["p"].data_ptr(), out["model"].data_ptr(), out["rot0"].data_ptr() if grad_rot else None, ph, pk, out["hidden"].data_ptr(),
+            out["gain"].data_ptr(), st))
+        return out
+
     # ---- the roll-out tick in reverse (include/cmpc.h, "plant-step derivatives" and "the roll-out tick in reverse"; DESIGN.md 7d) ----
     def _opt(self, t, dtype, shape, name):
         """data_ptr of an optional CUDA tensor (None -> NULL), checked"""
@@ -573,7 +635,7 @@ class BatchSolver:
         return gprev, status
 
     def rollout_tick_vjp_device(self, now, tape, dGradStateOut, dGradListOut=None, dGradX=None, dGradPlan=None, dGradModel=None, wrench=True, grad_p=False,
-                                dGradListRotOut=None, rot=False, dGradPlanRot=None):
+                                dGradListRotOut=None, rot=False, dGradPlanRot=None, mismatch=False, hidden_wrench=None, force_gain=None, dGradGain=None):
         """cmpc_rollout_tick_vjp_device: one tick in reverse.  tape: dict(X, P, lam_g, state, info, ok (or None), land, plan_t, plan_n, prev_t, prev_n
         (both None on the first tick), list_t, list_n, step, substeps, force_sample_time) of CUDA tensors as the forward tick left them.
         dGradStateOut[B,9] float64, dGradListOut[B,2,M,3] float64 or None, dGradX[B,n_x] float32 or None; dGradPlan / dGradModel: float64 tensors added to
@@ -582,7 +644,10 @@ class BatchSolver:
         rot=True (cmpc_rollout_tick_vjp_rot_device): the contacts' orientations are carried along, in the body-frame tangent of their quaternions --
         dGradListRotOut[B,2,M,3] float64 or None, dGradPlanRot[B,2,M,3] float64 added to in place or None; the dict also holds prev_list_rot[B,2,M,3] and
         rot[B,2,N,3] float64 (the tick's per-stage dl/domega: the solve's, plus the plant's on stage 0), every other entry bit-equal to rot=False but
-        sens, which is the rotation VJP's."""
+        sens, which is the rotation VJP's.
+        mismatch=True (cmpc_rollout_tick_vjp_mismatch_device; with or without rot): the tick ran under hidden_wrench[B,6] / force_gain[B] float32 (its own
+        rows; None: not applied) and tape["state"] is the TRUE state; the dict also holds hidden[B,6] float64 and noise[B,9] float32, and dGradGain[B]
+        float64 (or None) is added to in place."""
         import torch
         from ._capi import CmpcTickTape
         L, B, N = self.layout, self.batch, self.cfg.N
@@ -605,15 +670,29 @@ class BatchSolver:
                 self._opt(dGradX, f32, (B, L.nx), "dGradX"), out["state"].data_ptr(), out["prev_list"].data_ptr(),
                 out["wrench"].data_ptr() if wrench else None, self._opt(dGradPlan, f64, g3, "dGradPlan"),
                 self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"), out["p"].data_ptr() if grad_p else None, out["sens"].data_ptr())
+        margs = None
+        if mismatch:
+            out["hidden"] = torch.empty((B, 6), dtype=f64, device=dev)
+            out["noise"] = torch.empty((B, 9), dtype=f32, device=dev)
+            margs = (self._opt(hidden_wrench, f32, (B, 6), "hidden_wrench"), self._opt(force_gain, f32, (B,), "force_gain"), out["hidden"].data_ptr(),
+                     out["noise"].data_ptr(), self._opt(dGradGain, f64, (B,), "dGradGain"))
+        else:
+            assert hidden_wrench is None and force_gain is None and dGradGain is None, "mismatch arguments need mismatch=True"
         if not rot:
             assert dGradListRotOut is None and dGradPlanRot is None, "orientation gradients need rot=True"
-            self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_device(self._h, M, float(now), ct, *args, st))
+            if mismatch:
+                self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_mismatch_device(self._h, M, float(now), ct, *args, None, None, None, None, *margs, st))
+            else:
+                self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_device(self._h, M, float(now), ct, *args, st))
             return out
         out["prev_list_rot"] = torch.empty(g3, dtype=f64, device=dev)
         out["rot"] = torch.empty((B, 2, N, 3), dtype=f64, device=dev)
         rargs = (self._opt(dGradListRotOut, f64, g3, "dGradListRotOut"), out["prev_list_rot"].data_ptr(), self._opt(dGradPlanRot, f64, g3, "dGradPlanRot"),
                  out["rot"].data_ptr())
-        self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_rot_device(self._h, M, float(now), ct, *args, *rargs, st))
+        if mismatch:
+            self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_mismatch_device(self._h, M, float(now), ct, *args, *rargs, *margs, st))
+        else:
+            self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_vjp_rot_device(self._h, M, float(now), ct, *args, *rargs, st))
         return out
 
     # ---- the roll-out tick forwards, in k directions (include/cmpc.h, "the roll-out tick FORWARDS") ----
@@ -818,6 +897,16 @@ class BatchSolver:
                            force_sample_time)
         self._launch(dP.device, lambda st: self._lib.cmpc_rollout_tick_device(self._h, lists[0].shape[2], float(now), 1 if warm else 0, io, st))
 
+    def rollout_tick_mismatch_device(self, tick, mismatch, now, plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, warm,
+                                     step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+        """cmpc_rollout_tick_mismatch_device: rollout_tick_device with the tick number `tick` selecting the rows of mismatch (plant_mismatch(...), or None:
+        rollout_tick_device bit for bit).  dState / dStateOut hold the TRUE state; the measured one goes into dP."""
+        io = self._tick_io(plan, prev, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dStateOut, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                           force_sample_time)
+        mc = C.byref(mismatch["_c"]) if mismatch is not None else None
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_tick_mismatch_device(self._h, lists[0].shape[2], float(now), 1 if warm else 0, io, int(tick),
+                                                                                       mc, st))
+
     # ---- the walk on the device (include/cmpc.h, "a walk of the whole batch on the device") ----
     def walk_record(self, rows, stop=("merge", "solver", "nonfinite"), trace=True, device=None):
         """The arrays of a cmpc_walk_record as a dict of CUDA tensors (trace arrays only with trace=True) plus "_c", the C struct that points at them.
@@ -892,14 +981,17 @@ class BatchSolver:
             ptr(lists[2]) if lists is not None else None, tape["_c"], st))
 
     def rollout_walk_vjp_device(self, tick0, ticks, tape, row0, end_tick, grad_states, carry_state, carry_list, status, grad_X=None, wrench=None, grad_p=None,
-                                dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None):
+                                dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None, mismatch=None,
+                                grad_hidden=None, grad_noise=None, grad_gain=None):
         """cmpc_rollout_walk_vjp_device: rows row0 .. row0 + ticks - 1 of tape (walk_tape) in reverse in ONE call.  grad_states[rows + 1, B, 9] float64 and
         grad_X[rows, B, n_x] float32 (or None) are the seeds; carry_state[B, 9] / carry_list[B, 2, M, 3] float64 go in as the carry entering the last row
         and come back as the carry leaving the first; wrench[rows, B, N, 6] / grad_p[rows, B, n_p] float32 (or None) and status[rows, B] int32 are written
         row by row; dGradPlan[B, 2, M, 3] / dGradModel[B, 34] float64 are added to in place.  end_tick: int32 [B] (a walk record's) or None.
         carry_list_rot[B, 2, M, 3] float64 given: cmpc_rollout_walk_vjp_rot_device, the contacts' orientations carried along -- it is the third carry;
         dGradPlanRot[B, 2, M, 3] float64 (or None) is added to in place, grad_rot[rows, B, 2, N, 3] float64 and removed[rows, B] float32 (or None) are
-        written row by row.  Without it the three other arguments must be None and the call is the one it always was."""
+        written row by row.  Without it the three other arguments must be None and the call is the one it always was.
+        mismatch (plant_mismatch(...)) given: cmpc_rollout_walk_vjp_mismatch_device, with or without carry_list_rot -- the walk ran under it; grad_hidden
+        [rows, B, 6] float64 and grad_noise[rows, B, 9] float32 are written row by row, grad_gain[B] float64 is added to in place (each may be None)."""
         import torch
         L, B, N, M, R = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"]), int(tape["rows"])
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
@@ -909,12 +1001,23 @@ class BatchSolver:
                                 self._opt(dGradPlan, f64, (B, 2, M, 3), "dGradPlan"), self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"),
                                 self._opt(status, i32, (R, B), "status"))
         e = self._opt(end_tick, i32, (B,), "end_tick")
+        if mismatch is None:
+            assert grad_hidden is None and grad_noise is None and grad_gain is None, "mismatch gradients need mismatch"
         if carry_list_rot is None:
             assert dGradPlanRot is None and grad_rot is None and removed is None, "orientation gradients need carry_list_rot"
-            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, st))
+            if mismatch is None:
+                self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, st))
+                return
+        r = None
+        if carry_list_rot is not None:
+            r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
+                                       self._opt(grad_rot, f64, (R, B, 2, N, 3), "grad_rot"), self._opt(removed, f32, (R, B), "removed"))
+        if mismatch is not None:
+            mg = _capi.CmpcWalkGradsMismatch(self._opt(grad_hidden, f64, (R, B, 6), "grad_hidden"), self._opt(grad_noise, f32, (R, B, 9), "grad_noise"),
+                                             self._opt(grad_gain, f64, (B,), "grad_gain"))
+            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_mismatch_device(
+                self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, C.byref(r) if r is not None else None, C.byref(mismatch["_c"]), C.byref(mg), st))
             return
-        r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
-                                   self._opt(grad_rot, f64, (R, B, 2, N, 3), "grad_rot"), self._opt(removed, f32, (R, B), "removed"))
         self._launch(carry_state.device,
                      lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, r, st))
 
@@ -1086,13 +1189,14 @@ class BatchSolver:
 
     def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
                             wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
-                            tape=None, tape_row0=None):
+                            tape=None, tape_row0=None, mismatch=None):
         """cmpc_rollout_walk_device: `ticks` ticks from tick number tick0 queued in one call, each followed by its record (rec: walk_record, or None), in
         place on dState.  lists / lists_b: the two sets of list buffers (t, pose, n), lists_in the one that holds the previous tick's lists (the first
         tick's own with cold_first); returns the set that holds the last tick's.  wrench_ticks[T, B, N, 6]: tick i < T of the call writes row i.
         planner = (dComIn, dHIn, in_dt, t_first, robot_mass, com_height), t_first the time of the trajectories' first knot.
         tape (walk_tape): cmpc_rollout_walk_taped_device -- tick i of the call also writes row tape_row0 + i (default: row0 + i) of the tape; the
-        multiplier output must be on."""
+        multiplier output must be on.
+        mismatch (plant_mismatch(...)): cmpc_rollout_walk_mismatch_device, taped or not -- tick tick0 + i runs under row tick0 + i - tick_first of its schedules."""
         io = _capi.CmpcWalkIO()
         io.tick = self._tick_io(plan, None, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
                                 force_sample_time)
@@ -1102,6 +1206,12 @@ class BatchSolver:
             assert wrench_ticks.is_contiguous() and tuple(wrench_ticks.shape[1:]) == (self.batch, self.cfg.N, 6)
             io.dWrenchTicks, io.wrench_ticks = wrench_ticks.data_ptr(), int(wrench_ticks.shape[0])
         out = C.c_int(-1)
+        if mismatch is not None:
+            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_mismatch_device(
+                self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
+                int(lists_in), C.byref(out), tape["_c"] if tape is not None else None, int(row0 if tape_row0 is None else tape_row0) if tape is not None else 0,
+                C.byref(mismatch["_c"]), st))
+            return out.value
         if tape is not None:
             self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_taped_device(
                 self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
