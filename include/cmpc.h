@@ -739,6 +739,72 @@ int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int tic
  * The record kernel needs nothing: it treats an ended problem from dEndTick alone.  No kernel gains a barrier and no tick gains a launch.  Every other
  * entry point (the single-step kernels, the NLP evaluations, the sensitivities) does not read the mask.  CMPC_ERR_ARG for a NULL handle. */
 int cmpc_set_ended_device(cmpc_handle h, const int* dEndTick);
+/* ---- refill: a queue of Q trials walked through the B slots of one walk (derivation and measurements: DESIGN.md 7f) ----
+ * A Monte-Carlo study has Q >> B trials, and a slot whose robot has fallen is dead for the rest of a walk.  Here a slot takes the next trial of a queue the
+ * tick after its robot ended or finished: one call walks Q trials through B slots, with no host read.  Three things become per problem for that: time -- a
+ * trial spawned at tick s runs tick t at its LOCAL time (double)(t - s) * sampling_time, the very double a walk of its own would use, not a shifted plan; the
+ * first tick -- a slot whose dStartTick equals the tick runs that tick as a first tick inside the merge launch (below); the wrench schedule -- per trial.
+ * All arrays are device arrays (host arrays for cmpc_rollout_refill[_init]).
+ *   per slot:   dStartTick[B] int, the tick number at which the slot's trial had local tick 0;  dTrial[B] int, the trial in the slot, -1: none
+ *   queue:      trials = Q >= 0, trial_ticks >= 1 (the length of a trial);  dNext[1] int, the next trial to hand out;  dState0[Q][9] float;
+ *               dWrenchTrials[wrench_ticks][Q][N][6] float or NULL: local tick r < wrench_ticks of trial q writes row [r][q] into dP, later ticks leave
+ *               the wrench rows alone
+ *   per trial:  dTrialEndTick (-1 while walking or walked through), dTrialEndCode, dTrialIterationsSum, dTrialIterationsMax [Q] int, dTrialFinalState
+ *               [Q][9] float, dTrialBoxSlackMin [Q] float: the words of cmpc_walk_record's outcome arrays, tick numbers LOCAL;  dTrialTicks[Q] int: local
+ *               ticks recorded so far;  dTrialSlot[Q], dTrialStart[Q] int: the slot and the start tick, -1 for a trial never started
+ *   trace:      dTrialOf[trace_rows][B] int or NULL: row tick - trace_tick_first holds the trial that occupies each slot during that tick (-1: none);
+ *               with it a caller reassembles per-trial traces from the slot-major trace of cmpc_walk_record
+ * With trials == 0 the per-trial arrays and dState0 are not read. */
+typedef struct cmpc_walk_refill_trace {
+    int rows, tick_first;
+    int* dTrialOf;
+} cmpc_walk_refill_trace;
+typedef struct cmpc_walk_refill {
+    int trials, trial_ticks;
+    int* dStartTick; int* dTrial; int* dNext;
+    const float* dState0;
+    const float* dWrenchTrials; int wrench_ticks;
+    int* dTrialEndTick; int* dTrialEndCode; int* dTrialIterationsSum; int* dTrialIterationsMax; float* dTrialFinalState; float* dTrialBoxSlackMin;
+    int* dTrialTicks; int* dTrialSlot; int* dTrialStart;
+    cmpc_walk_refill_trace trace;
+} cmpc_walk_refill;
+/* Every slot empty (dTrial -1, dStartTick 0), *dNext = 0, every trial not started: its outcome as cmpc_rollout_outcome_init_device sets a problem's (final
+ * state = dState0[q]), dTrialTicks 0, dTrialSlot and dTrialStart -1.  ONE launch / a host loop.  The refill in front of tick 0 then fills the B slots with
+ * trials 0 .. B - 1.  (rec needs no set-up of its own for slots that get a trial; set it up with cmpc_rollout_outcome_init_device all the same when Q < B.) */
+int cmpc_rollout_refill_init_device(cmpc_handle h, const cmpc_walk_refill* refill, void* stream);
+int cmpc_rollout_refill_init(int batch, const cmpc_walk_refill* refill);
+/* The refill in front of tick `tick_next`, ONE launch: two passes over the slots in ascending order.
+ *   archive:  every occupied slot copies its outcome words from rec into its trial's row and sets dTrialTicks = tick_next - dStartTick.
+ *   retire and spawn:  a slot is free if it is empty, if rec->dEndTick[b] >= 0, or if tick_next - dStartTick[b] >= trial_ticks.  Free slots, in ascending
+ *     slot order, take trials *dNext, *dNext + 1, ...  A slot that receives trial q gets dTrial = q, dStartTick = tick_next, dStateLive[b] = dState0[q], its
+ *     outcome in rec as cmpc_rollout_outcome_init_device sets it (end tick -1, code 0, iteration words 0, final state dState0[q], slack +inf), and
+ *     dTrialSlot[q] = b, dTrialStart[q] = tick_next.  A free slot with no trial left gets dTrial = -1 and -- unless it was empty already and holds one --
+ *     dEndTick = tick_next: it is out of every later launch through the ended mask.
+ * The trace row tick_next - trace.tick_first (inside [0, trace.rows), else none) then receives dTrial of every slot.
+ * dStateLive == NULL: the archive pass only -- nothing else is read or written.  A walk ends with one such call (tick_next = the tick after the last), since
+ * the record of its last tick runs behind that tick's refill.
+ * The assignment does not depend on scheduling: one workgroup walks the slots in chunks, a wave64 ballot ranks the free slots of a wave, the wave totals go
+ * through LDS and a running base is carried from chunk to chunk; no atomics, and only that workgroup reads and writes *dNext.  The host form is bit-equal,
+ * needs no handle and no GPU.  CMPC_ERR_ARG: a NULL argument or array (per-trial arrays excepted when trials == 0), trials < 0, trial_ticks < 1,
+ * tick_next < 0, dWrenchTrials with wrench_ticks < 1. */
+int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, void* stream);
+int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* state_live);
+/* `ticks` ticks of a refill walk, numbers tick0 .. tick0 + ticks - 1, queued with no host read; each tick is FIVE launches: the refill with tick_next = tick
+ * (dStateLive = io->tick.dStateOut, the buffer the walk runs in place on -- io->tick.dState must be that buffer), the tick's three, the record (row
+ * row0 + i; the tick number dEndTick takes is the local one).  There is no cold_first: every tick is queued as a merge tick (lists as
+ * cmpc_rollout_walk_device, `lists_in` / *lists_out), and a slot whose dStartTick equals the tick runs it as its first tick inside those launches:
+ *   front kernel: no merge; its lists are the PLANNER's lists of its slot, snapped with force_sample_time, written to the set the tick writes (entries in use
+ *     and the count; a foot whose snap fails gets the count 0 and no entry -- the entries of an empty list are not read); dOk = 1, or the snap's status; dX0 = the cold start of its dP (cmpc_cold_start_device's entries), in the same kernel;
+ *   solve: inside the warm launch that problem takes the cold policy for its whole solve (not warm, the cold launch's barrier scalars).
+ * Every other slot runs the merge tick it would run in a walk of its own, at its own local time, with plan_t_offset = local time - plan_t_first and the wrench
+ * row of its trial.  A trial's outcome, trace rows, dX, dP, dInfo, state and the entries in use of its lists are those of cmpc_rollout_walk_device(cold_first = 1) on a batch
+ * that holds it in the same slot; list entries past a foot's count are whatever the set held before.
+ * While the call queues, the ended mask is rec->dEndTick itself; the handle's own setting is saved and restored.  io->tick.dWrench is not read.
+ * CMPC_ERR_ARG before anything is queued: max_contacts > 16 (the first tick uses the front kernel's LDS stage), io->dWrenchTicks set (the schedule is the
+ * per-trial one), rec NULL or with too few rows, io->tick.dState != io->tick.dStateOut, no dOk, and what cmpc_rollout_walk_device and
+ * cmpc_rollout_refill_device refuse.  Tapes, plant mismatch, gradients and forward mode are out of scope: no entry point takes a refill together with them. */
+int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                    const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
  * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated; the orientations have their own entry point below
  * (cmpc_contacts_orientation_vjp_device).  The forward maps move positions

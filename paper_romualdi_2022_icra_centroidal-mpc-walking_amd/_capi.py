@@ -62,6 +62,19 @@ class CmpcWalkIO(C.Structure):
                 ("dWrenchTicks", C.c_void_p), ("wrench_ticks", C.c_int)]
 
 
+class CmpcWalkRefillTrace(C.Structure):
+    """mirror of cmpc_walk_refill_trace (include/cmpc.h): which trial occupied each slot, tick by tick"""
+    _fields_ = [("rows", C.c_int), ("tick_first", C.c_int), ("dTrialOf", C.c_void_p)]
+
+
+class CmpcWalkRefill(C.Structure):
+    """mirror of cmpc_walk_refill (include/cmpc.h): the queue of trials behind a walk's slots, cmpc_rollout_refill[_device] / cmpc_rollout_walk_refill_device"""
+    _fields_ = [("trials", C.c_int), ("trial_ticks", C.c_int), ("dStartTick", C.c_void_p), ("dTrial", C.c_void_p), ("dNext", C.c_void_p),
+                ("dState0", C.c_void_p), ("dWrenchTrials", C.c_void_p), ("wrench_ticks", C.c_int)] + [(k, C.c_void_p) for k in (
+        "dTrialEndTick", "dTrialEndCode", "dTrialIterationsSum", "dTrialIterationsMax", "dTrialFinalState", "dTrialBoxSlackMin", "dTrialTicks",
+        "dTrialSlot", "dTrialStart")] + [("trace", CmpcWalkRefillTrace)]
+
+
 STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
 
 
@@ -200,6 +213,7 @@ EXPORTS = [
     "cmpc_rollout_snapshot", "cmpc_rollout_snapshot_device", "cmpc_walk_snapshot_bytes",
     "cmpc_plant_step_mismatch_device", "cmpc_rollout_tick_mismatch_device", "cmpc_rollout_walk_mismatch_device",
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
+    "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
 ]
 
 _lib = None
@@ -354,6 +368,13 @@ def lib():
             L.cmpc_rollout_tick_vjp_mismatch_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 20
             L.cmpc_rollout_walk_vjp_mismatch_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, C.POINTER(CmpcWalkGrads),
                                                                 C.POINTER(CmpcWalkGradsRot), mp, C.POINTER(CmpcWalkGradsMismatch), vp]
+        if hasattr(L, "cmpc_rollout_walk_refill_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            fl, wr = C.POINTER(CmpcWalkRefill), C.POINTER(CmpcWalkRecord)
+            L.cmpc_rollout_refill_init.argtypes = [i, fl]
+            L.cmpc_rollout_refill_init_device.argtypes = [vp, fl, vp]
+            L.cmpc_rollout_refill.argtypes = [i, i, wr, fl, vp]
+            L.cmpc_rollout_refill_device.argtypes = [vp, i, wr, fl, vp, vp]
+            L.cmpc_rollout_walk_refill_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, i, i, ip, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -60,6 +60,18 @@ extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, h
 extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                                         float* slack_min, hipStream_t stream);
 extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);
+extern "C" int cmpc_launch_refill(const CmpcRefillArgs* a, int* next, hipStream_t stream);
+extern "C" int cmpc_launch_refill_init(const CmpcRefillArgs* a, int* next, hipStream_t stream);
+extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const double* plan_t, const float* plan_pose, const int* plan_n,
+                                           const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n,
+                                           int* ok, int* land, const float* box, const float* state, float* P, const float* Xprev, float* X0,
+                                           const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
+                                           long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
+                                           int wrench_ticks, int trials, double plan_t_first, float g8, hipStream_t stream);
+extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
+                                            const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
+                                            const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
+                                            hipStream_t stream);
 extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
@@ -395,9 +407,12 @@ static void fill_params(cmpc_handle h, CmpcParams& p)
     p.warm_budget = h->warm_budget; p.warm_no_restart = h->warm_no_restart;
     p.duals = (h->mult_out || h->warm_duals) ? h->dDuals : nullptr; p.warm_duals = h->warm_duals;
     p.ended = h->dEnded;
+    p.cold_mu_init = p.mu_init; p.cold_t_floor = p.t_floor; p.cold_mu_adapt = p.mu_adapt;   // (what a warm launch overwrites below; read only with p.start set)
 }
 
-static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm)
+// start / tick: the refill walk's per-problem first tick inside a warm launch (CmpcParams.start), or null
+static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm, const int* start = nullptr,
+                             int tick = 0)
 {
     if (!h || !dP || !dX0 || !dX) return fail(h, CMPC_ERR_ARG, "cmpc_solve_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
@@ -405,6 +420,7 @@ static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, f
     CmpcParams p;
     fill_params(h, p);
     p.P = dP; p.X0 = dX0; p.X = dX; p.info = dInfo ? dInfo : h->dInfo;
+    p.start = start; p.tick = tick;
     if (warm || h->force_warm) {  // dX0 is a previous solution shifted by one knot: start near the central path
         p.mu_init = (float)h->mu_warm; p.mu_adapt = 0.f; p.t_floor = (float)h->floor_warm; p.warm = 1;
     }
@@ -1718,6 +1734,142 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
                                    cold ? nullptr : t.dPlanN, t.dListT, t.dListN, tape, stream);
     }
     h->timing = timing;
+    if (rc == CMPC_OK && lists_out) *lists_out = cur;
+    return rc;
+}
+
+// ---- refill (include/cmpc.h, cmpc_walk_refill): the queue of trials behind a walk's slots ----
+// the argument block of the per-slot functions; false: a required pointer is NULL or a count is out of range.  rec may be NULL for the init (no slot outcome).
+static bool refill_args(int B, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* r, float* state_live, CmpcRefillArgs& a)
+{
+    if (B < 1 || tick_next < 0 || !r || r->trials < 0 || r->trial_ticks < 1 || !r->dStartTick || !r->dTrial || !r->dNext) return false;
+    if (r->dWrenchTrials && r->wrench_ticks < 1) return false;
+    if (r->trials > 0 && (!r->dState0 || !r->dTrialEndTick || !r->dTrialEndCode || !r->dTrialIterationsSum || !r->dTrialIterationsMax || !r->dTrialFinalState ||
+                          !r->dTrialBoxSlackMin || !r->dTrialTicks || !r->dTrialSlot || !r->dTrialStart))
+        return false;
+    if (rec && (!rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin)) return false;
+    if (r->trace.dTrialOf && r->trace.rows < 1) return false;
+    const long long row = (long long)tick_next - r->trace.tick_first;
+    int* const trial_of = (r->trace.dTrialOf && row >= 0 && row < r->trace.rows) ? r->trace.dTrialOf + (size_t)row * B : nullptr;
+    a = CmpcRefillArgs{B, r->trials, r->trial_ticks, tick_next, r->dStartTick, r->dTrial, r->dState0, r->dTrialEndTick, r->dTrialEndCode, r->dTrialIterationsSum,
+                       r->dTrialIterationsMax, r->dTrialFinalState, r->dTrialBoxSlackMin, r->dTrialTicks, r->dTrialSlot, r->dTrialStart,
+                       rec ? rec->dEndTick : nullptr, rec ? rec->dEndCode : nullptr, rec ? rec->dIterationsSum : nullptr, rec ? rec->dIterationsMax : nullptr,
+                       rec ? rec->dFinalState : nullptr, rec ? rec->dBoxSlackMin : nullptr, state_live, trial_of};
+    return true;
+}
+
+int cmpc_rollout_refill_init(int batch, const cmpc_walk_refill* refill)
+{
+    CmpcRefillArgs a;
+    if (!refill_args(batch, 0, nullptr, refill, nullptr, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_init: bad argument");
+    cmpc_refill_init_host(a, refill->dNext);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_refill_init_device(cmpc_handle h, const cmpc_walk_refill* refill, void* stream)
+{
+    CmpcRefillArgs a;
+    if (!h || !refill_args(h->B, 0, nullptr, refill, nullptr, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_init_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_refill_init(&a, refill->dNext, stream ? (hipStream_t)stream : h->stream);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("refill init launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* state_live)
+{
+    CmpcRefillArgs a;
+    if (!rec || !refill_args(batch, tick_next, rec, refill, state_live, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill: bad argument");
+    cmpc_refill_host(a, refill->dNext);
+    return CMPC_OK;
+}
+
+static int rollout_refill_impl(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, hipStream_t st)
+{
+    CmpcRefillArgs a;
+    if (!h || !rec || !refill_args(h->B, tick_next, rec, refill, dStateLive, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: bad argument");
+    const int lrc = cmpc_launch_refill(&a, refill->dNext, st);
+    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("refill launch: ") + hipGetErrorString((hipError_t)lrc));
+    return CMPC_OK;
+}
+
+int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    return rollout_refill_impl(h, tick_next, rec, refill, dStateLive, stream ? (hipStream_t)stream : h->stream);
+}
+
+// the refill walk: per tick the refill launch, the tick's three launches (front and back kernels in refill mode, the warm solve with the per-problem cold
+// policy) and the record with local tick numbers
+int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                    const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
+{
+    // (the refusals that need no handle come first: they are the same with and without one)
+    if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
+    const cmpc_tick_io& k = io->tick;
+    if (max_contacts < 1 || max_contacts > 16)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: max_contacts must be 1 .. 16 (a slot's first tick uses the front kernel's LDS stage)");
+    if (io->dWrenchTicks) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dWrenchTicks is not taken (the schedule is the per-trial dWrenchTrials)");
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
+    if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
+        !k.box_upper || !k.box_lower || !k.dState || !k.dStateOut || k.dState != k.dStateOut || !k.dPlanT || !k.dPlanPose || !k.dPlanN || !k.dOk || !k.dLand ||
+        !k.dInfo || !k.dP || !k.dX0 || !k.dX || !(k.plant_step > 0) || k.plant_substeps < 1)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad argument");
+    if (io->dListTB == k.dListT || io->dListPoseB == k.dListPose || io->dListNB == k.dListN)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the two sets of list buffers must not alias");
+    if ((k.dPlanCom || k.dPlanH) && (!k.dPlanCom || !k.dPlanH || k.plan_knots < 2 || !(k.plan_dt > 0) || !(k.robot_mass > 0)))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad planner trajectory");
+    if (row0 < 0 || (long long)row0 + ticks > rec->rows) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the record has too few rows");
+    CmpcRefillArgs probe;
+    if (!refill_args(h->B, tick0, rec, refill, k.dStateOut, probe)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad refill or record");
+    long long dt_ns = 0;
+    if (k.force_sample_time) {
+        dt_ns = snap_dt_ns(h->cfg.sampling_time);
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: force_sample_time needs a sampling time of at least 1 ns");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    int rc = upload_box(h, k.box_upper, k.box_lower, st);
+    if (rc != CMPC_OK) return rc;
+    if (rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
+    const bool timing = h->timing;   // (as cmpc_rollout_walk_device)
+    const int* const ended_saved = h->dEnded;
+    h->timing = false; h->timed = false;
+    h->dEnded = rec->dEndTick;
+    double* const set_t[2] = {k.dListT, io->dListTB};
+    float* const set_p[2] = {k.dListPose, io->dListPoseB};
+    int* const set_n[2] = {k.dListN, io->dListNB};
+    const int N = h->cfg.horizon, B = h->B;
+    int cur = lists_in;
+    for (int i = 0; i < ticks && rc == CMPC_OK; ++i) {
+        const int tick = tick0 + i;
+        const int prev = cur;
+        cur = 1 - cur;
+        rc = rollout_refill_impl(h, tick, rec, refill, k.dStateOut, st);
+        if (rc != CMPC_OK) break;
+        int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
+                                              set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,
+                                              k.plan_knots, k.plan_dt, k.robot_mass, k.com_height, dt_ns, h->dEnded, refill->dStartTick, refill->dTrial, tick,
+                                              refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), st);
+        if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (front) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
+        rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, refill->dStartTick, tick);
+        if (rc != CMPC_OK) break;
+        lrc = cmpc_launch_tick_post_refill(B, N, max_contacts, h->cfg.sampling_time, (float)h->cfg.gravity, model_corners(h), corners_stride(h), k.dX, k.dP,
+                                           k.dStateOut, k.dStateOut, k.dZmp, (float)k.plant_step, k.plant_substeps, (float)k.zmp_half_x, (float)k.zmp_half_y,
+                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, st);
+        if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (back) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
+        CmpcRecordArgs a;
+        if (!h->box_set || !record_args(N, B, tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {
+            rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad record");
+            break;
+        }
+        a.start = refill->dStartTick;
+        lrc = cmpc_launch_rollout_record(&a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
+        if (lrc != 0) rc = fail(h, CMPC_ERR_HIP, std::string("refill walk record launch: ") + hipGetErrorString((hipError_t)lrc));
+    }
+    h->timing = timing;
+    h->dEnded = ended_saved;
     if (rc == CMPC_OK && lists_out) *lists_out = cur;
     return rc;
 }

@@ -244,6 +244,7 @@ struct CmpcRecordArgs {
     const float* box;                                                                   // upper[2][3] | lower[2][3]
     float* t_com; float* t_zmp; int* t_land; double* t_off; int* t_iters; int* t_code;  // trace (each may be null)
     int* end_tick; int* end_code; int* it_sum; int* it_max; float* final_state; float* slack_min;
+    const int* start;   // [B] or null (the refill walk): the tick number end_tick takes is tick - start[b], the problem's local one
 };
 // tally[5]: this problem's terms of the statistics row -- not ended before the tick, ended by it, iterations (for the sum and for the max: 0 unless the
 // tick is a good one), code 2..4
@@ -295,7 +296,7 @@ __host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, int
         if (a.t_off)
             for (int i = 0; i < 3; ++i) a.t_off[(2 * r + c) * 3 + i] = off[i];
     }
-    if (ends) { a.end_tick[b] = a.tick; a.end_code[b] = code; }
+    if (ends) { a.end_tick[b] = a.start ? a.tick - a.start[b] : a.tick; a.end_code[b] = code; }
     if (good) {
         a.it_sum[b] += it;
         if (it > a.it_max[b]) a.it_max[b] = it;
@@ -320,6 +321,78 @@ __host__ __device__ inline float cmpc_cold_start_entry(int N, int e, const float
     if (q < 3 * (N + 1)) return p[L.pNom(c) + q];
     if (q < 3 * (N + 1) + 3 * N) return 0.f;          // the foot's velocity block
     return (q - 3 * (N + 1)) % 3 == 2 ? g8 : 0.f;     // corner forces [j][k][3]: 3 (N + 1) and 3 N are multiples of three
+}
+
+// ---- the refill of a walk's slots from a queue of trials (include/cmpc.h, cmpc_walk_refill): one slot's share of the two passes, one statement for the host
+// form and the kernel.  Plain pointers, host or device alike; bit copies and integer words only.
+struct CmpcRefillArgs {
+    int B, Q, trial_ticks, tick_next;
+    int* start; int* trial;                                                                   // per slot
+    const float* state0;                                                                      // [Q][9]
+    int* q_end_tick; int* q_end_code; int* q_it_sum; int* q_it_max; float* q_final_state; float* q_slack_min; int* q_ticks; int* q_slot; int* q_start;
+    int* end_tick; int* end_code; int* it_sum; int* it_max; float* final_state; float* slack_min;   // the record's outcome, per slot
+    float* state_live;                                                                        // [B][9], or null: archive only
+    int* trial_of;                                                                            // this tick's row [B] of the trace, or null
+};
+// archive: an occupied slot's outcome words into its trial's row.  -> the slot is free (empty, its trial ended, or its trial walked trial_ticks ticks)
+__host__ __device__ inline bool cmpc_refill_archive(const CmpcRefillArgs& a, int b)
+{
+    const int q = a.trial[b];
+    if (q < 0 || q >= a.Q) return true;
+    const int walked = a.tick_next - a.start[b];
+    a.q_end_tick[q] = a.end_tick[b]; a.q_end_code[q] = a.end_code[b]; a.q_it_sum[q] = a.it_sum[b]; a.q_it_max[q] = a.it_max[b];
+    for (int i = 0; i < 9; ++i) a.q_final_state[9 * (size_t)q + i] = a.final_state[9 * (size_t)b + i];
+    a.q_slack_min[q] = a.slack_min[b];
+    a.q_ticks[q] = walked;
+    return a.end_tick[b] >= 0 || walked >= a.trial_ticks;
+}
+// retire and spawn: free slot b takes trial q -- its outcome as cmpc_outcome_init_kernel sets it -- or, with the queue empty (q >= Q), leaves every later
+// launch through the ended mask (a slot that was empty already keeps the word it has)
+__host__ __device__ inline void cmpc_refill_assign(const CmpcRefillArgs& a, int b, int q)
+{
+    if (q >= a.Q) {
+        if (a.trial[b] >= 0 || a.end_tick[b] < 0) a.end_tick[b] = a.tick_next;
+        a.trial[b] = -1;
+        return;
+    }
+    a.trial[b] = q; a.start[b] = a.tick_next;
+    a.end_tick[b] = -1; a.end_code[b] = 0; a.it_sum[b] = 0; a.it_max[b] = 0;
+    for (int i = 0; i < 9; ++i) {
+        const float v = a.state0[9 * (size_t)q + i];
+        a.state_live[9 * (size_t)b + i] = v;
+        a.final_state[9 * (size_t)b + i] = v;
+    }
+    a.slack_min[b] = __builtin_inff();
+    a.q_slot[q] = b; a.q_start[q] = a.tick_next;
+}
+
+// the host form's two loops (cmpc_rollout_refill_init, cmpc_rollout_refill): the slots in ascending order, the counter a plain int.  Here, and not in
+// cmpc_api.hip, so that a stand-alone host program can run them under a sanitizer without the library.
+inline void cmpc_refill_init_host(const CmpcRefillArgs& a, int* next)
+{
+    *next = 0;
+    for (int b = 0; b < a.B; ++b) { a.start[b] = 0; a.trial[b] = -1; }
+    for (int q = 0; q < a.Q; ++q) {
+        a.q_end_tick[q] = -1; a.q_end_code[q] = 0; a.q_it_sum[q] = 0; a.q_it_max[q] = 0;
+        for (int i = 0; i < 9; ++i) a.q_final_state[9 * (size_t)q + i] = a.state0[9 * (size_t)q + i];
+        a.q_slack_min[q] = __builtin_inff();
+        a.q_ticks[q] = 0; a.q_slot[q] = -1; a.q_start[q] = -1;
+    }
+}
+inline void cmpc_refill_host(const CmpcRefillArgs& a, int* next)
+{
+    int base = 0;
+    if (a.state_live) base = *next < 0 ? 0 : *next > a.Q ? a.Q : *next;
+    for (int b = 0; b < a.B; ++b) {
+        const bool is_free = cmpc_refill_archive(a, b);
+        if (!a.state_live) continue;
+        if (is_free) {
+            cmpc_refill_assign(a, b, base);
+            base = base + 1 > a.Q ? a.Q : base + 1;
+        }
+        if (a.trial_of) a.trial_of[b] = a.trial[b];
+    }
+    if (a.state_live) *next = base;
 }
 
 // ---- the device tape of a walk (include/cmpc.h, cmpc_walk_tape): one row from what a tick left.  Bit copies only; one argument block for the kernel.

@@ -161,4 +161,7 @@ struct CmpcParams {
     int lds_words;               // 4-byte words of dynamic LDS the launch was given (set by cmpc_launch_solver)
     int kc_per_problem;          // 0: kc is the batch's one record; 1: kc[B], one record per problem (cmpc_set_models)
     const int* ended;            // [B] or null (cmpc_set_ended_device): a problem whose word is >= 0 is left out of the solve -- its workgroup returns first thing
+    const int* start;            // [B] or null (the refill walk, cmpc_rollout_walk_refill_device): inside a warm launch a problem with start[b] == tick is on
+    int tick;                    //  its first tick and takes the cold policy for its whole solve -- not warm, and the three scalars below
+    float cold_mu_init, cold_t_floor, cold_mu_adapt;   // what mu_init, t_floor and mu_adapt are in a cold launch (fill_params)
 };

@@ -1486,6 +1486,26 @@ __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float
 // (merge ticks) or on the caller's lists (first tick, written back), behind a barrier.  Lists longer than the LDS stage were snapped by
 // cmpc_force_sample_time_kernel before this launch: snap_ok[2B] then holds its per-foot status words.  A foot whose snap fails is treated as an empty list:
 // its list is emptied, land = -2, ok = 0.
+// RF: the refill walk (cmpc_rollout_walk_refill_device), always launched as a merge tick with M <= 16.  The workgroup reads its slot's start tick once: its time
+// is its own, now = (tick - start[b]) dt, its wrench row is row tick - start[b] of its trial, and with start[b] == tick this is the problem's FIRST tick -- no
+// merge, its lists are the planner's (staged in LDS, snapped there with forceSampleTime) and go out as a merge tick writes them, ok = the snap's status (1
+// without), and x0 is the cold start, written behind the barrier after the sampling.  false is the kernel without any of it.
+struct CmpcRefillTick {
+    const int* start; const int* trial;     // [B]: the slots' start ticks and trials (cmpc_walk_refill)
+    int tick;
+    const float* wrench_trials; int wrench_ticks, trials;   // [wrench_ticks][trials][N][6] or null
+    double plan_t_first;
+    float g8;                               // the cold start's f_z
+};
+// local time of a refilled slot and its offset into the planner's trajectories: the host's two roundings, (double)ticks * dt and then the difference
+__device__ inline void refill_local_time(int ticks, double dt, double t_first, double* now, double* offset)
+{
+#pragma clang fp contract(off)
+    const double t = (double)ticks * dt;
+    *now = t;
+    *offset = t - t_first;
+}
+template <bool RF>
 __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose,
                                                             const int* plan_n, const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t,
                                                             float* list_pose, int* list_n, int* ok, int* land, const float* __restrict__ box,
@@ -1493,12 +1513,22 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
                                                             const float* __restrict__ Xprev, float* __restrict__ X0, const float* __restrict__ plan_com,
                                                             const float* __restrict__ plan_h, int plan_knots, double plan_dt, double plan_t_offset,
                                                             double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok,
-                                                            const int* __restrict__ ended, const float* __restrict__ noise)
+                                                            const int* __restrict__ ended, const float* __restrict__ noise, CmpcRefillTick rf)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device: the whole workgroup, ahead of its first barrier -- nothing of the problem is written)
     const CmpcIdx L{N};
     float* p = P + (size_t)b * L.np();
+    bool fresh = false;                   // (RF: workgroup-uniform, from one scalar load)
+    const float* wrench_b = nullptr;      // (RF: the wrench row of this slot's trial, [N][6])
+    if constexpr (RF) {
+        const int local = rf.tick - rf.start[b], q = rf.trial[b];
+        fresh = local == 0;
+        refill_local_time(local, dt, rf.plan_t_first, &now, &plan_t_offset);
+        if (rf.wrench_trials && local >= 0 && local < rf.wrench_ticks && q >= 0 && q < rf.trials)
+            wrench_b = rf.wrench_trials + ((size_t)local * rf.trials + q) * N * 6;
+        if (fresh) merge = 0;
+    }
     __shared__ int okw;
     __shared__ int foot_ok[2];   // forceSampleTime status of the two feet (1 when the flag is off)
     if (tid == 0) okw = 1;
@@ -1508,13 +1538,20 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
     // (noise: this tick's row [B][9] of cmpc_plant_mismatch.dStateNoise or null -- the MPC measures state + noise, one float32 add; the plant keeps the state)
     if (noise) for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e] + noise[9 * (size_t)b + e];
     else for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e];
-    if (wrench)
+    if constexpr (RF) {
+        if (wrench_b)
+            for (int e = tid; e < 3 * N; e += 256) {
+                const int k = e / 3, i = e % 3;
+                p[L.pFext() + e] = wrench_b[k * 6 + i];
+                p[L.pText() + e] = wrench_b[k * 6 + 3 + i];
+            }
+    } else if (wrench)
         for (int e = tid; e < 3 * N; e += 256) {
             const int k = e / 3, i = e % 3;
             p[L.pFext() + e] = wrench[((size_t)b * N + k) * 6 + i];
             p[L.pText() + e] = wrench[((size_t)b * N + k) * 6 + 3 + i];
         }
-    if (Xprev) warm_shift_problem(N, Xprev + (size_t)b * L.nx(), X0 + (size_t)b * L.nx(), tid, 256);
+    if (Xprev && !fresh) warm_shift_problem(N, Xprev + (size_t)b * L.nx(), X0 + (size_t)b * L.nx(), tid, 256);
     if (plan_com)   // setReferenceTrajectory from the planner's trajectories (8f-3), one thread per knot, from the far end of the workgroup
         for (int k = 255 - tid; k <= N; k += 256)
             cmpc_resample_reference_knot(plan_com + (size_t)b * plan_knots * 3, plan_h + (size_t)b * plan_knots * 3, plan_knots, plan_dt, plan_t_offset, dt, k,
@@ -1544,10 +1581,13 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
     __shared__ int so_n[2];
     const bool lstaged = M <= MS;
     const size_t ob = (size_t)(2 * b) * M;
-    if (lstaged && !merge) {   // (first tick: the caller filled the lists)
-        for (int e = tid; e < 4 * M; e += 256) so_t[e] = list_t[2 * ob + e];
-        for (int e = tid; e < 14 * M; e += 256) so_p[e] = list_pose[7 * ob + e];
-        if (tid < 2) so_n[tid] = list_n[2 * b + tid];
+    if (lstaged && !merge) {   // (first tick: the caller filled the lists; RF: they are the planner's)
+        const double* const first_t = RF ? plan_t : list_t;
+        const float* const first_p = RF ? plan_pose : list_pose;
+        const int* const first_n = RF ? plan_n : list_n;
+        for (int e = tid; e < 4 * M; e += 256) so_t[e] = first_t[2 * ob + e];
+        for (int e = tid; e < 14 * M; e += 256) so_p[e] = first_p[7 * ob + e];
+        if (tid < 2) so_n[tid] = first_n[2 * b + tid];
         if (snap_dt_ns > 0) {   // forceSampleTime on the caller's lists, written back: what the reference passes on (contactPhaseList = mannContactPhaseList)
             __syncthreads();
             for (int e = tid; e < 2 * M; e += 256) {
@@ -1555,6 +1595,7 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
                 if (n < 0 || n > M) { if (m == 0) atomicAnd(&foot_ok[c], 0); continue; }
                 if (m >= n) continue;
                 if (!cmpc_snap_contact(so_t + 2 * e, snap_dt_ns, so_t + 2 * e)) atomicAnd(&foot_ok[c], 0);
+                if constexpr (RF) continue;   // (the whole list goes out below)
                 list_t[2 * ob + 2 * e] = so_t[2 * e]; list_t[2 * ob + 2 * e + 1] = so_t[2 * e + 1];
             }
             __syncthreads();
@@ -1581,7 +1622,7 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         if (!good) atomicAnd(&okw, 0);
     }
     __syncthreads();   // (the merged lists of the two feet are visible to the workgroup: in LDS, or in global memory when they do not fit)
-    if (lstaged && merge) {   // out to global memory, the entries in use (what the single merge kernel writes)
+    if (lstaged && (merge || RF)) {   // out to global memory, the entries in use (what the single merge kernel writes)
         for (int e = tid; e < 4 * M; e += 256) { const int c = e / (2 * M); if (e - c * 2 * M < 2 * so_n[c]) list_t[2 * ob + e] = so_t[e]; }
         for (int e = tid; e < 14 * M; e += 256) { const int c = e / (7 * M); if (e - c * 7 * M < 7 * so_n[c]) list_pose[7 * ob + e] = so_p[e]; }
         if (tid < 2) list_n[2 * b + tid] = so_n[tid];
@@ -1602,22 +1643,33 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         const int e = 2 * b + tid, n = lstaged ? so_n[tid] : list_n[e];
         land[e] = (n < 1 || n > M) ? -2 : cmpc_landing_knot(N, [&](int k) { return acts[tid][k] != 0; });
     }
-    if ((merge || snap_dt_ns > 0) && ok && tid == 0) ok[b] = okw && foot_ok[0] && foot_ok[1];
+    if ((merge || snap_dt_ns > 0 || RF) && ok && tid == 0) ok[b] = okw && foot_ok[0] && foot_ok[1];
+    if constexpr (RF) {   // (the barrier above: the state rows and the sampling's nominal positions of p are the workgroup's to read)
+        if (fresh) {
+            float* x0 = X0 + (size_t)b * L.nx();
+            for (int e = tid; e < L.nx(); e += 256) x0[e] = cmpc_cold_start_entry(N, e, p, rf.g8);
+        }
+    }
 }
 
 // post: one thread per problem -- the plant step, then the step adjustment of its two feet (getOutput().contactPhaseList)
 // MM: the mismatched plant (this tick's hidden-wrench row and the force gain, plant_step_problem); false is the kernel without it
-template <bool MM>
+// RF: the refill walk -- the step adjustment looks for the next contact at the problem's own time (tick - start[b]) dt
+template <bool MM, bool RF>
 __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy, const int* __restrict__ land,
                                                              const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n,
                                                              const int* __restrict__ ended, const float* __restrict__ hidden,
-                                                             const float* __restrict__ gain)
+                                                             const float* __restrict__ gain, const int* __restrict__ start, int tick, double dt)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device; per lane, as the line above: nothing behind it needs the whole wave)
+    if constexpr (RF) {
+        double unused;
+        refill_local_time(tick - start[b], dt, 0.0, &now, &unused);
+    }
     plant_step_problem<MM>(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy, hidden, gain);
     const CmpcIdx L{N};
     for (int c = 0; c < 2; ++c) {
@@ -1666,6 +1718,52 @@ __global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const flo
     end_tick[b] = -1; end_code[b] = 0; it_sum[b] = 0; it_max[b] = 0;
     for (int i = 0; i < 9; ++i) final_state[9 * (size_t)b + i] = state0[9 * (size_t)b + i];
     slack_min[b] = __builtin_inff();
+}
+
+// refill (cmpc_rollout_refill_device): ONE workgroup walks the slots in chunks of 256, so that the assignment does not depend on scheduling -- no atomic on the
+// counter.  Per chunk: every lane archives its slot and learns whether it is free; a wave64 ballot gives the lane its rank among its wave's free slots, the four
+// wave totals go through LDS, and the running base (the queue's counter, read once) is carried from chunk to chunk: free slots take trials base, base + 1, ...
+// in ascending slot order.  Every thread reaches the ballot and both barriers of every chunk (lanes past B hold `not free`).  Only this workgroup touches *next.
+__global__ __launch_bounds__(256) void cmpc_refill_kernel(CmpcRefillArgs a, int* __restrict__ next)
+{
+    __shared__ int wave_free[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int base = a.state_live ? min(max(*next, 0), a.Q) : 0;
+    for (int c0 = 0; c0 < a.B; c0 += 256) {
+        const int b = c0 + tid;
+        const bool is_free = b < a.B && cmpc_refill_archive(a, b);
+        const unsigned long long m = __ballot(is_free);
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_free[w] = __popcll(m);
+        __syncthreads();
+        int ahead = 0, total = 0;
+        for (int i = 0; i < 4; ++i) {
+            const int t = wave_free[i];
+            ahead += i < w ? t : 0;
+            total += t;
+        }
+        if (a.state_live && b < a.B) {
+            if (is_free) cmpc_refill_assign(a, b, min(base + ahead + rank, a.Q));
+            if (a.trial_of) a.trial_of[b] = a.trial[b];
+        }
+        base = min(base + total, a.Q);
+        __syncthreads();   // (wave_free is the next chunk's)
+    }
+    if (a.state_live && tid == 0) *next = base;
+}
+
+// the slots and the queue at their start: every slot empty, every trial not started with the outcome cmpc_outcome_init_kernel gives it, the counter 0
+__global__ __launch_bounds__(256) void cmpc_refill_init_kernel(CmpcRefillArgs a, int* __restrict__ next)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e == 0) *next = 0;
+    if (e < a.B) { a.start[e] = 0; a.trial[e] = -1; }
+    if (e < a.Q) {
+        a.q_end_tick[e] = -1; a.q_end_code[e] = 0; a.q_it_sum[e] = 0; a.q_it_max[e] = 0;
+        for (int i = 0; i < 9; ++i) a.q_final_state[9 * (size_t)e + i] = a.state0[9 * (size_t)e + i];
+        a.q_slack_min[e] = __builtin_inff();
+        a.q_ticks[e] = 0; a.q_slot[e] = -1; a.q_start[e] = -1;
+    }
 }
 
 // cold start: one workgroup per problem, one thread per entry of x (cmpc_cold_start_entry)
@@ -1820,6 +1918,19 @@ extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tic
     return (int)hipGetLastError();
 }
 
+extern "C" int cmpc_launch_refill(const CmpcRefillArgs* a, int* next, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_refill_kernel, dim3(1), dim3(256), 0, stream, *a, next);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_refill_init(const CmpcRefillArgs* a, int* next, hipStream_t stream)
+{
+    const int n = a->B > a->Q ? a->B : a->Q;
+    hipLaunchKernelGGL(cmpc_refill_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *a, next);
+    return (int)hipGetLastError();
+}
+
 extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_cold_start_kernel, dim3(B), dim3(256), 0, stream, N, g8, dP, dX0, ended);
@@ -1832,9 +1943,35 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
                                     const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
                                     double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, const float* noise, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_tick_pre_kernel, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
+    hipLaunchKernelGGL(cmpc_tick_pre_kernel<false>, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
                        list_t, list_pose, list_n, ok, land, box, state, wrench, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, plan_t_offset, robot_mass,
-                       com_height, snap_dt_ns, snap_ok, ended, noise);
+                       com_height, snap_dt_ns, snap_ok, ended, noise, CmpcRefillTick{});
+    return (int)hipGetLastError();
+}
+
+// the front and back kernels of a refill walk's tick (cmpc_rollout_walk_refill_device): a merge tick with M <= 16 in which every slot runs at its own time
+extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const double* plan_t, const float* plan_pose, const int* plan_n,
+                                           const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n,
+                                           int* ok, int* land, const float* box, const float* state, float* P, const float* Xprev, float* X0,
+                                           const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
+                                           long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
+                                           int wrench_ticks, int trials, double plan_t_first, float g8, hipStream_t stream)
+{
+    if (M > 16) return (int)hipErrorInvalidValue;
+    const CmpcRefillTick rf{start, trial, tick, wrench_trials, wrench_ticks, trials, plan_t_first, g8};
+    hipLaunchKernelGGL(cmpc_tick_pre_kernel<true>, dim3(B), dim3(256), 0, stream, B, N, M, dt, 0.0, 1, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
+                       list_t, list_pose, list_n, ok, land, box, state, (const float*)nullptr, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, 0.0,
+                       robot_mass, com_height, snap_dt_ns, (const int*)nullptr, ended, (const float*)nullptr, rf);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
+                                            const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
+                                            const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
+                                            hipStream_t stream)
+{
+    hipLaunchKernelGGL((cmpc_tick_post_kernel<false, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX, dP,
+                       dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, (const float*)nullptr, (const float*)nullptr, start, tick, dt);
     return (int)hipGetLastError();
 }
 
@@ -1843,11 +1980,11 @@ extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav
                                      const double* t, float* pose, const int* n, const int* ended, const float* hidden, const float* gain, hipStream_t stream)
 {
     if (hidden || gain)
-        hipLaunchKernelGGL(cmpc_tick_post_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn,
-                           dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain);
+        hipLaunchKernelGGL((cmpc_tick_post_kernel<true, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0);
     else
-        hipLaunchKernelGGL(cmpc_tick_post_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP, dStateIn,
-                           dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain);
+        hipLaunchKernelGGL((cmpc_tick_post_kernel<false, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0);
     return (int)hipGetLastError();
 }
 

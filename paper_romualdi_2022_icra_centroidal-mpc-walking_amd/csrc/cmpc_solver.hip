@@ -3478,6 +3478,11 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
     // an ended problem (cmpc_set_ended_device) is left out: its workgroup returns here, ahead of the LDS clear and of every barrier -- uniform over the
     // workgroup (a scalar load at blockIdx.x), nothing of the problem written, and the CU free for the next workgroup at once
     if (kp.ended && kp.ended[b] >= 0) return;
+    // a problem on its first tick inside a warm launch (the refill walk: kp.start / kp.tick) takes the cold policy for its whole solve -- the same kind of
+    // workgroup-uniform scalar load, read once here ahead of every barrier; with kp.start null `warm` is kp.warm and the three scalars the launch's
+    const bool fresh = kp.start && kp.start[b] == kp.tick;
+    const bool warm = kp.warm && !fresh;
+    const float mu_init0 = fresh ? kp.cold_mu_init : kp.mu_init, t_floor0 = fresh ? kp.cold_t_floor : kp.t_floor, mu_adapt0 = fresh ? kp.cold_mu_adapt : kp.mu_adapt;
     const int tid = threadIdx.x;
     const int N = NC > 0 ? NC : kp.N;
     // The whole LDS image starts at zero.  LDS arrives with whatever the previous workgroup -- or the previous
@@ -3514,13 +3519,13 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
     float* const dq = kp.duals ? kp.duals + (size_t)b * (NS * (N + 1) + 2 * NI * N) : nullptr;
     if (outside) {
         // outside the supported NLP subset (include/cmpc.h): no iteration; the initial iterate goes out with status 3
-        phase_init<NT, NC, FG>(lds, N, fg_base, kp.X0 + (size_t)b * L.nx(), dq, 0, kp.mu_init, kp.t_floor);
+        phase_init<NT, NC, FG>(lds, N, fg_base, kp.X0 + (size_t)b * L.nx(), dq, 0, mu_init0, t_floor0);
         status = 3;
     }
     for (int pass = 0; pass < 2 && !outside; ++pass) {
-        const float mu_init = pass ? 0.1f : kp.mu_init, t_floor = pass ? 1e-2f : kp.t_floor, mu_adapt = pass ? 3.5f : kp.mu_adapt;
+        const float mu_init = pass ? 0.1f : mu_init0, t_floor = pass ? 1e-2f : t_floor0, mu_adapt = pass ? 3.5f : mu_adapt0;
         step_out = step_prev = 0.f;
-        const bool use_duals = kp.warm && kp.warm_duals && kp.duals;
+        const bool use_duals = warm && kp.warm_duals && kp.duals;
         const int nrow = phase_init<NT, NC, FG>(lds, N, fg_base, kp.X0 + (size_t)b * L.nx(), dq,
                                                 (pass > 0 ? 1 : 0) | (use_duals ? 2 : 0) | (use_duals && kp.warm_duals > 1 ? 4 : 0), mu_init, t_floor);
         int it = 0;
@@ -3528,7 +3533,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
         bool finishing = false;
         // (a warm-started pass may be given a smaller budget: kp.warm_budget -- its stragglers are then re-solved from the cold
         // start, inside this kernel or by the caller, see CmpcParams)
-        const int budget = (kp.warm && pass == 0 && kp.warm_budget > 0 && kp.warm_budget < prm.max_iter) ? kp.warm_budget : prm.max_iter;
+        const int budget = (warm && pass == 0 && kp.warm_budget > 0 && kp.warm_budget < prm.max_iter) ? kp.warm_budget : prm.max_iter;
         for (it = 0; it < budget + 1; ++it) {
             if (it == budget && !finishing) break;
             // ---- residuals of the current iterate ----
@@ -3547,7 +3552,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
                 phase_multipliers<NT, NC, FG>(lds, N, fg_base, 0, mu0 / mu_cur, nrow);
                 mu_cur = mu0;
             }
-            if (kp.warm && pass == 0 && it > 0 && ec > 100.f * mu_cur && ec > 0.1f) {
+            if (warm && pass == 0 && it > 0 && ec > 100.f * mu_cur && ec > 0.1f) {
                 // Emergency re-centring.  Primal and dual step lengths differ; when a blocked primal step (ap ~ 0.2) meets a
                 // full dual step, the multipliers of rows that were about to become active grow while their slacks stay:
                 // products t z hundreds of times the average, and the predictor-corrector can fall into a two-cycle (seen on
@@ -3660,7 +3665,7 @@ __global__ __launch_bounds__(NT, FG ? 3 : 1) void cmpc_solve_kernel(CmpcParams k
             }
         }
         it_total += it;
-        if (status == 0 || !kp.warm || pass > 0 || kp.warm_no_restart) break;
+        if (status == 0 || !warm || pass > 0 || kp.warm_no_restart) break;
         sg += 10000;
         __syncthreads();
     }

@@ -179,6 +179,86 @@ class WalkingRollout:
         included, unlike final_state).  The same walk with a device tape for backward_device(): walk_device_taped()."""
         return self._walk_on_launch_stream(False, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
 
+    def walk_device_refill(self, ticks, trial_ticks, com0, dcom0, h0, push=None, push_ticks=0, wrench_trials=None, trace=True,
+                           stop=("merge", "solver", "nonfinite"), replan=None, mismatch=None, taped=False, every=None):
+        """A queue of Q trials walked through the B slots of this roll-out in ONE walk of `ticks` ticks (cmpc_rollout_walk_refill_device, include/cmpc.h;
+        DESIGN.md 7f "Refill"): every trial is a walk of trial_ticks ticks from its own initial state, and a slot takes the queue's next trial the tick after
+        its robot ended (per `stop`) or finished, in ascending slot order.  No host read and no synchronisation inside; five launches per tick.
+        com0 / dcom0 / h0 [Q, 3], numpy or CUDA; push [Q, 3] with run()'s schedule rule in the trial's LOCAL ticks (the push on the first max(push_ticks - i,
+        1) knots of local tick i < push_ticks, zeros once at local tick push_ticks), or wrench_trials [R, Q, N, 6] float32 taken as it is (local tick r < R of
+        trial q writes row [r, q]; later ticks leave the wrench rows alone); not both.  The references are the SLOT's (set_references, else the straight
+        line) sized for trial_ticks and read at the trial's local time; the models are the slot's.  A trial runs at its local time and its first tick is a
+        cold first tick inside the merge launches, so its bits are those of walk_device(trial_ticks, ...) on a roll-out of the same batch size and factor
+        storage that holds it in the same slot.
+        -> walk_device's slot-major dict (end_tick and the other outcome arrays are those of the slots' LAST trials, tick numbers local; a slot the queue
+        left empty has end_tick >= 0), plus trial_of [ticks, B] int32 (the trial in each slot at each tick, -1: none) and trials: the per-trial outcome
+        end_tick (-1 while walking or walked through), end_code, iterations_sum, iterations_max, final_state, box_slack_min, ticks (local ticks recorded),
+        slot, start [Q, ..] (-1: never started), and trials["trace"](q) -> trial q's trace rows com, zmp, land, landing_offset, iterations, code
+        [trial_ticks, ..] gathered out of the slot-major trace by one index_select each on the device, with valid [trial_ticks] bool (rows at or past
+        trials["ticks"][q] are not the trial's).
+        Out of scope: gradients and forward mode through a refill walk, per-trial models (a model belongs to a slot), and -- NotImplementedError, raised
+        before anything touches a GPU -- replan, a plant mismatch (hidden pushes or noise per trial), taped=True, every (snapshots and checkpoints), and
+        lists longer than 16 contacts."""
+        for name, value in (("replan", replan), ("mismatch", mismatch), ("taped", taped or None), ("every", every)):
+            if value is not None:
+                raise NotImplementedError(f"walk_device_refill: {name} is out of scope of a refill walk")
+        if self.M > 16:
+            raise NotImplementedError("walk_device_refill: lists longer than 16 contacts are out of scope (a slot's first tick uses the front kernel's LDS "
+                                      "stage; with force_sample_time the snap runs there too)")
+        if push is not None and wrench_trials is not None:
+            raise ValueError("walk_device_refill: push or wrench_trials, not both")
+        assert ticks >= 1 and trial_ticks >= 1
+        return self._queued(lambda: self._walk_refill(ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop))
+
+    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop):
+        torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
+        dt, dev, s = cfg.sampling_time, self.dev, self.solver
+        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
+
+        def up(a):
+            if isinstance(a, torch.Tensor):
+                return a.to(dev, torch.float32)
+            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+            return hold[-1].to(dev, non_blocking=True)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
+        Q = int(state0.shape[0])
+        if push is not None:
+            dpush = up(push)
+            wrench_trials = z((push_ticks + 1, Q, N, 6))
+            for i in range(push_ticks):
+                wrench_trials[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
+        elif wrench_trials is not None:
+            wrench_trials = up(wrench_trials).contiguous()
+        dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
+        state = z((B, 9))
+        ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
+        refs = self._planner_refs(trial_ticks)
+        rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
+        s.outcome_init_device(state, rec)
+        fill = s.walk_refill(state0, trial_ticks, wrench_trials, trace_rows=ticks, device=dev)
+        # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
+        sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
+        cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
+                                           step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time)
+        s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
+        del rec["_c"]
+        trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
+        if trace:
+            ar = torch.arange(trial_ticks, device=dev)
+
+            def trial_trace(q):
+                rows = (trials["start"][q].clamp(min=0) + ar).clamp(max=ticks - 1)
+                idx = rows * B + trials["slot"][q].clamp(min=0)
+                out = {k: rec[k].reshape((ticks * B,) + tuple(rec[k].shape[2:])).index_select(0, idx)
+                       for k in ("com", "zmp", "land", "landing_offset", "iterations", "code")}
+                out["valid"] = ar < trials["ticks"][q]
+                return out
+            trials["trace"] = trial_trace
+        self._walk_refill_keep = (fill, refs, wrench_trials)    # (the queued launches read these)
+        rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state, trial_of=fill["trial_of"], trials=trials)
+        return rec
+
     def _mismatch_of(self, mismatch):
         """mismatch (None, a dict of hidden_wrench / state_noise / force_gain / tick_first, or a BatchSolver.plant_mismatch dict) -> the solver's dict, or None
         when nothing is set (zero-length schedules count as absent): the walk is then the plain one, call for call"""
@@ -740,7 +820,7 @@ class WalkingRollout:
         lists of the first resumed tick), row 1 + i is resume tick + i, first_row_is_first_tick = 0 (reverse it from row 1).
         Bit-equality with the unbroken walk is promised between handles of the same batch size and factor storage: the solver picks its kernel variant
         from them (the round-3 note on stragglers), and another variant rounds differently.  Out of scope: refilling ended problems with new
-        robots -- a walk has no per-problem cold tick."""
+        robots from a snapshot -- a queue of trials behind the slots of a walk is walk_device_refill(), which takes no snapshots."""
         return self._queued(lambda: self._walk_resume(snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every))
 
     def walk_resume_device_mismatch(self, snapshot, ticks, mismatch, **kwargs):
@@ -812,7 +892,8 @@ class WalkingRollout:
         so that the dense seeds need not exist either.
         -> the keys of backward_device (rot=True: of backward_device_rot) plus "tape_rows_peak".  No host read once the workspaces exist (the first
         call allocates them and turns the multiplier output on).  Out of scope: the reference gradients (backward_device_refs: their one-launch sum has
-        a fixed ascending order that per-segment calls in reverse would change), the forward-mode walk, and refilling ended problems."""
+        a fixed ascending order that per-segment calls in reverse would change), the forward-mode walk, and refilled walks (walk_device_refill has no
+        tape and no gradient)."""
         return self._queued(lambda: self._backward_checkpointed(w, grad_states, grad_X, rot))
 
     def _backward_checkpointed(self, w, grad_states, grad_X, rot):

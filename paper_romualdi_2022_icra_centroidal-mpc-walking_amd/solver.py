@@ -1222,6 +1222,74 @@ class BatchSolver:
             int(lists_in), C.byref(out), st))
         return out.value
 
+    # ---- refill: a queue of trials behind the slots of a walk (include/cmpc.h, cmpc_walk_refill) ----
+    def _need_refill(self):
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_device")
+
+    def walk_refill(self, state0, trial_ticks, wrench_trials=None, trace_rows=0, trace_tick_first=0, device=None, init=True):
+        """The arrays of a cmpc_walk_refill as a dict of CUDA tensors plus "_c", the C struct that points at them: state0 [Q, 9] float32 (the queue, kept),
+        wrench_trials [R, Q, N, 6] float32 or None, the slots' start_tick / trial [B], next [1], the per-trial outcome end_tick, end_code, iterations_sum,
+        iterations_max, final_state, box_slack_min, ticks, slot, start [Q, ..], and trial_of [trace_rows, B] (trace_rows > 0; row r is tick trace_tick_first
+        + r).  init: cmpc_rollout_refill_init_device is queued (every slot empty, no trial started)."""
+        import torch
+        self._need_refill()
+        B = self.batch
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        assert state0.is_cuda and state0.dtype == torch.float32 and state0.is_contiguous() and state0.dim() == 2 and state0.shape[1] == 9, "state0 [Q, 9] float32"
+        Q = int(state0.shape[0])
+        z = lambda shape, dt=torch.int32: torch.zeros(shape, dtype=dt, device=dev)
+        r = dict(state0=state0, wrench_trials=wrench_trials, start_tick=z((B,)), trial=z((B,)), next=z((1,)), end_tick=z((Q,)), end_code=z((Q,)),
+                 iterations_sum=z((Q,)), iterations_max=z((Q,)), final_state=z((Q, 9), torch.float32), box_slack_min=z((Q,), torch.float32), ticks=z((Q,)),
+                 slot=z((Q,)), start=z((Q,)), trials=Q, trial_ticks=int(trial_ticks))
+        if trace_rows > 0:
+            r["trial_of"] = z((int(trace_rows), B))
+        c = _capi.CmpcWalkRefill()
+        c.trials, c.trial_ticks = Q, int(trial_ticks)
+        c.dStartTick, c.dTrial, c.dNext, c.dState0 = r["start_tick"].data_ptr(), r["trial"].data_ptr(), r["next"].data_ptr(), state0.data_ptr()
+        if wrench_trials is not None:
+            assert wrench_trials.is_cuda and wrench_trials.dtype == torch.float32 and wrench_trials.is_contiguous() and \
+                tuple(wrench_trials.shape[1:]) == (Q, self.cfg.N, 6), "wrench_trials [R, Q, N, 6] float32"
+            c.dWrenchTrials, c.wrench_ticks = wrench_trials.data_ptr(), int(wrench_trials.shape[0])
+        for field, key in (("dTrialEndTick", "end_tick"), ("dTrialEndCode", "end_code"), ("dTrialIterationsSum", "iterations_sum"),
+                           ("dTrialIterationsMax", "iterations_max"), ("dTrialFinalState", "final_state"), ("dTrialBoxSlackMin", "box_slack_min"),
+                           ("dTrialTicks", "ticks"), ("dTrialSlot", "slot"), ("dTrialStart", "start")):
+            setattr(c, field, r[key].data_ptr())
+        if trace_rows > 0:
+            c.trace = _capi.CmpcWalkRefillTrace(int(trace_rows), int(trace_tick_first), r["trial_of"].data_ptr())
+        r["_c"] = c
+        if init:
+            self._launch(dev, lambda st: self._lib.cmpc_rollout_refill_init_device(self._h, C.byref(c), st))
+        return r
+
+    def rollout_refill_device(self, tick_next, rec, refill, dStateLive):
+        """cmpc_rollout_refill_device: the refill in front of tick tick_next as ONE launch -- archive the occupied slots' outcome (rec: walk_record) into
+        their trials' rows, then free slots take the queue's next trials in ascending slot order (refill: walk_refill).  dStateLive [B, 9] float32, the walk's
+        state buffer; None: the archive pass only."""
+        self._need_refill()
+        if dStateLive is not None:
+            assert dStateLive.is_contiguous() and tuple(dStateLive.shape) == (self.batch, 9)
+        dev = refill["start_tick"].device
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_refill_device(self._h, int(tick_next), C.byref(rec["_c"]), C.byref(refill["_c"]),
+                                                                          dStateLive.data_ptr() if dStateLive is not None else None, st))
+
+    def rollout_walk_refill_device(self, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0=0,
+                                   step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+        """cmpc_rollout_walk_refill_device: `ticks` ticks of a refill walk from tick number tick0 in one call -- per tick the refill launch, the tick's three
+        launches and the record -- in place on dState; the other arguments as rollout_walk_device's (no cold_first, wrench_ticks, tape or mismatch: a slot's
+        first tick runs inside the merge launches, and the wrench schedule is refill's per-trial one).  Returns the set that holds the last tick's lists."""
+        self._need_refill()
+        io = _capi.CmpcWalkIO()
+        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                force_sample_time)
+        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
+        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        out = C.c_int(-1)
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_device(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), int(row0), int(lists_in),
+            C.byref(out), st))
+        return out.value
+
     def shift_solution_device(self, dXprev, dX0):
         """is_warm_start_enabled: dX0 = dXprev shifted by one knot; solve from it with solve_device(..., warm=True)."""
         self._launch(dX0.device, lambda st: self._lib.cmpc_shift_solution_device(self._h, dXprev.data_ptr(), dX0.data_ptr(), st))

@@ -1,0 +1,184 @@
+"""Developer probe (GPU box): what refilling ended slots from a queue of trials (cmpc_rollout_walk_refill_device, WalkingRollout.walk_device_refill) buys,
+and that nothing existing moved.  N = 20, trials of 24 ticks, Q = 4 B trials of which a quarter (--fall) end at a uniformly drawn local tick (a NaN wrench row: the
+solve returns status 2 and the record ends the trial there), B = 256 and, with --large, B = 1024.  In one process after a warm-up, the two ways alternate,
+--repeats times, the median kept:
+    plain   Q / B walks of 24 ticks with the ended problems out of the launches (cmpc_set_ended_device), one after the other: the path before this feature
+    refill  ONE walk_device_refill of as many ticks as the queue needs (the assignment rule run on the host beforehand)
+Reported: wall time per trial-tick run (a trial that ends at local tick r ran r + 1 ticks; the sum is the same on both sides), the refill walk's mean tick
+time, and how many of its ticks held at least one fresh (cold) solve.  No pass mark: at B <= the CU count a tick lasts as long as its slowest problem and
+a cold solve takes more iterations than a warm one, so refills spread over the ticks may cost much of what they save.
+With --baseline LIB (another build of the library in the package directory, e.g. the parent commit's), first, in child processes started before this one
+touches the GPU: the headline solve of bench.py through tools/ab_multi.sh, and the 24-tick walk_device at B = 256 (--walk-only children, the builds
+alternating), this build / LIB for both.  Writes its lines to --out (default profiles/r12_walk_refill.txt) as well."""
+import argparse, os, subprocess, sys, time
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_walk_refill.txt"))
+ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--baseline", default=None)
+ap.add_argument("--ab-reps", type=int, default=3)
+ap.add_argument("--fall", type=float, default=0.25, help="the fraction of the trials that end early (the study's is a quarter)")
+ap.add_argument("--append", action="store_true", help="add the lines to --out instead of replacing it")
+ap.add_argument("--large", action="store_true", help="the study at B = 1024 as well")
+ap.add_argument("--walk-only", action="store_true", help="print the median ms per tick of the 24-tick walk_device at B = 256 and leave")
+args = ap.parse_args()
+TT, lines = 24, []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def start(n, seed=5):
+    rng = np.random.default_rng(seed)
+    com0 = (np.array([0.0, 0.0, 0.7]) + rng.uniform(-0.01, 0.01, (n, 3))).astype(np.float32)
+    dcom0 = rng.uniform(-0.05, 0.05, (n, 3)).astype(np.float32)
+    h0 = rng.uniform(-0.02, 0.02, (n, 3)).astype(np.float32)
+    push = np.zeros((n, 3), np.float32)
+    push[:, :2] = rng.uniform(-20.0, 20.0, (n, 2)) / cm.synthetic.ROBOT_MASS
+    return com0, dcom0, h0, push
+
+
+ab = walk_ab = None
+if args.baseline:
+    libs = [args.baseline, "libcmpc_hip.so"]
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "ab_multi.sh"), "config2", str(args.ab_reps)] + libs, cwd=ROOT, capture_output=True, text=True,
+                         timeout=90 * args.ab_reps * len(libs)).stdout      # (a bench.py child takes about 15 s)
+    ab = {lib: [] for lib in libs}
+    for ln in out.splitlines():
+        w = ln.split()
+        if len(w) == 4 and w[0] in ab:
+            ab[w[0]].append(float(w[3]))
+    assert all(len(v) == args.ab_reps for v in ab.values()), out
+    walk_ab = {lib: [] for lib in libs}
+    for _ in range(args.ab_reps):
+        for lib in libs:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--walk-only"], cwd=ROOT, capture_output=True, text=True, env=dict(os.environ, CMPC_LIB=lib),
+                               timeout=120)      # (a child takes about 10 s)
+            assert r.returncode == 0, r.stderr[-2000:]
+            walk_ab[lib].append(float(r.stdout.split()[-1]))
+
+import torch
+import cmpc_amd as cm
+
+cfg = cm.config.ergocub_gazebo_v1(20, 0.06)
+N = cfg.N
+fmt = lambda a: ", ".join(f"{x:.4f}" for x in a)
+
+
+def timed(fn, repeats):
+    ms = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ms)), ms, out
+
+
+if args.walk_only:
+    com0, dcom0, h0, push = start(256)
+    ro = cm.rollout.WalkingRollout(cfg, 256)
+    ro.walk_device(8, com0, dcom0, h0, push=push, push_ticks=3)
+    med, _, _ = timed(lambda: ro.walk_device(TT, com0, dcom0, h0, push=push, push_ticks=3), 5)
+    print("walk_device ms per tick", med / TT)
+    sys.exit(0)
+
+
+def plain_walks(ro, B, state0, wrench):
+    """the queue as Q / B walks of TT ticks, ended problems out of the launches: WalkingRollout._walk_device's calls with the wrench rows passed through"""
+    s, L, dev, dt = ro.solver, ro.L, ro.dev, cfg.sampling_time
+    z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+    recs = []
+    refs = ro._planner_refs(TT)
+    ls = s.launch_stream
+    ls.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(ls):
+        for c in range(state0.shape[0] // B):
+            dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
+            state = state0[c * B:(c + 1) * B].clone()
+            ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
+            rec = s.walk_record(TT, trace=True)
+            s.outcome_init_device(state, rec)
+            sets = [tuple(a.clone() for a in ro.plan), tuple(torch.zeros_like(a) for a in ro.plan)]
+            wt = wrench[:, c * B:(c + 1) * B].contiguous()
+            s.set_ended_device(rec["end_tick"])
+            try:
+                s.rollout_walk_device(0, TT, True, ro.plan, sets[0], sets[1], 0, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=0, wrench_ticks=wt,
+                                      step=dt / ro.substeps, substeps=ro.substeps, planner=refs)
+            finally:
+                s.set_ended_device(None)
+            recs.append((rec, wt, state, dP, dX0, dX, dInfo))
+    torch.cuda.current_stream(dev).wait_stream(ls)
+    return recs
+
+
+def ticks_needed(B, Q, ends):
+    """the assignment rule on the host: ends[q] = the local tick trial q ends at, or -1 -> (ticks the queue needs, ticks with at least one spawn)"""
+    left = np.zeros(B, np.int64)      # ticks the slot's trial still runs
+    nxt, t, fresh = 0, 0, 0
+    while True:
+        free = np.flatnonzero(left == 0)
+        take = min(len(free), Q - nxt)
+        for b in free[:take]:
+            left[b] = TT if ends[nxt] < 0 else ends[nxt] + 1
+            nxt += 1
+        fresh += 1 if take else 0
+        if nxt >= Q and not left.any():
+            return t, fresh
+        left[left > 0] -= 1
+        t += 1
+
+
+say(f"refill of ended slots from a queue of trials: N = {N}, trials of {TT} ticks, Q = 4 B, {args.fall:g} of the trials end at a uniform local tick; plain = Q / B "
+    f"walks with the ended problems out of the launches, refill = one walk_device_refill; the two alternate, median of {args.repeats}; "
+    f"{torch.cuda.get_device_name(0)}")
+for B in (256, 1024) if args.large else (256,):
+    Q = 4 * B
+    rng = np.random.default_rng(7)
+    com0, dcom0, h0, push = start(Q)
+    ends = np.full(Q, -1)
+    falls = rng.permutation(Q)[:int(Q * args.fall)]
+    ends[falls] = rng.integers(0, TT, len(falls))
+    wrench = np.zeros((TT, Q, N, 6), np.float32)
+    for i in range(3):
+        wrench[i, :, :3 - i, :3] = push[:, None, :]
+    wrench[ends[falls], falls] = np.nan
+    run_ticks = int(np.where(ends < 0, TT, ends + 1).sum())
+    T, fresh_ticks = ticks_needed(B, Q, ends)
+    ro = cm.rollout.WalkingRollout(cfg, B)
+    dwrench = torch.from_numpy(wrench).to(ro.dev)
+    dstate0 = torch.from_numpy(np.concatenate([com0, dcom0, h0], 1)).to(ro.dev)
+    plain = lambda: plain_walks(ro, B, dstate0, dwrench)
+    refill = lambda: ro.walk_device_refill(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], wrench_trials=dwrench)
+    plain(); refill()       # warm-up (module load, allocator)
+    ms = {"plain": [], "refill": []}
+    for _ in range(args.repeats):
+        m, _, recs = timed(plain, 1)
+        ms["plain"].append(m)
+        m, _, w = timed(refill, 1)
+        ms["refill"].append(m)
+    # the two ways walked the same trials: end ticks agree, and every trial ran
+    end_plain = torch.cat([r[0]["end_tick"] for r in recs]).cpu().numpy()
+    tr = {k: v.cpu().numpy() for k, v in w["trials"].items() if hasattr(v, "cpu")}
+    same = bool((end_plain == tr["end_tick"]).all() and (tr["end_tick"] == ends).all() and int(tr["ticks"].sum()) == run_ticks)
+    fresh_seen = len(np.unique(tr["start"]))
+    mp, mr = float(np.median(ms["plain"])), float(np.median(ms["refill"]))
+    say(f"B = {B}, Q = {Q}: {len(falls)} trials end early, {run_ticks} trial-ticks run of {Q * TT}; plain {Q // B} x {TT} = {Q // B * TT} ticks, refill {T} ticks "
+        f"({fresh_seen} of them with at least one fresh solve; the host rule said {fresh_ticks}); end ticks agree and every trial ran: {same}")
+    say(f"B = {B}: plain {mp:.2f} ms ({fmt(ms['plain'])}) = {mp * 1e3 / run_ticks:.3f} us per trial-tick, {mp / (Q // B * TT):.4f} ms per tick | refill {mr:.2f} ms "
+        f"({fmt(ms['refill'])}) = {mr * 1e3 / run_ticks:.3f} us per trial-tick, {mr / T:.4f} ms per tick | refill / plain = {mr / mp:.4f}")
+if ab:
+    a, b = ab[args.baseline], ab["libcmpc_hip.so"]
+    say(f"headline solve (bench.py config2 through tools/ab_multi.sh, {args.ab_reps} rounds), ms per step: {args.baseline} {np.median(a):.4f} ({fmt(a)}) | "
+        f"this build {np.median(b):.4f} ({fmt(b)}) | this build / baseline = {np.median(b) / np.median(a):.4f}")
+    a, b = walk_ab[args.baseline], walk_ab["libcmpc_hip.so"]
+    say(f"walk_device, B = 256, {TT} ticks, ms per tick (median of 5 in a child process, {args.ab_reps} children per build, alternating): {args.baseline} "
+        f"{np.median(a):.4f} ({fmt(a)}) | this build {np.median(b):.4f} ({fmt(b)}) | this build / baseline = {np.median(b) / np.median(a):.4f}")
+with open(args.out, "a" if args.append else "w") as f:
+    f.write("\n".join(lines) + "\n")
