@@ -1,6 +1,7 @@
 """A queue of trials walked through the slots of one walk (include/cmpc.h, cmpc_walk_refill; WalkingRollout.walk_device_refill): a slot's first tick
 inside the merge launches is the cold first tick of walk_device, refilled trials are fresh walks at their own local time, neighbours do not matter, the
-queue runs dry cleanly, one call equals many, no host read, and the refill kernel against its host form.
+queue runs dry cleanly, one call equals many, no host read, the refill kernel against its host form -- at the edges of a wave and of a chunk against the
+assignment model too -- and the handle behind a refill walk.  Trials long enough to change their lists: tests/test_gpu_walk_refill_long.py.
 
 The comparison of a refill walk with refill + cmpc_rollout_tick_device-level calls is not made: a tick in refill mode has no entry point of its own (the
 front and back kernels take the slots' start ticks only inside cmpc_rollout_walk_refill_device), and the issue rules a new one out for this test."""
@@ -137,19 +138,8 @@ def test_fresh_tick_is_the_cold_tick(n, opts):
 
 # ---- 2, 3. refilled trials are fresh walks; neighbours are untouched ----
 N2, B2, Q2, TT2, T2 = 10, 4, 10, 4, 12
-# worked out by hand from the assignment rule.  Trial 1 ends at its local tick 0 (global 0), trial 4 (NaN state) at local 0 (global 1), trial 2 at local 2
-# (global 2), trial 6 at local 1 (global 4); a slot is free the tick after its trial ended, or once it has walked 4 ticks:
-#   tick 0: slots 0..3 <- 0..3 | tick 1: slot 1 <- 4 | tick 2: slot 1 <- 5 | tick 3: slot 2 <- 6 | tick 4: slots 0, 3 (walked through) <- 7, 8 |
-#   tick 5: slot 2 <- 9 | tick 6: slot 1 (trial 5 walked through) empty | tick 8: slots 0, 3 empty | tick 9: slot 2 empty
-TRIAL_OF = [[0, 1, 2, 3], [0, 4, 2, 3], [0, 5, 2, 3], [0, 5, 6, 3], [7, 5, 6, 8], [7, 5, 9, 8], [7, -1, 9, 8], [7, -1, 9, 8], [-1, -1, 9, -1],
-            [-1, -1, -1, -1], [-1, -1, -1, -1], [-1, -1, -1, -1]]
-SLOT = [0, 1, 2, 3, 1, 1, 2, 0, 3, 2]
-START = [0, 0, 0, 0, 1, 2, 3, 4, 4, 5]
-TICKS = [4, 1, 3, 4, 1, 4, 2, 4, 4, 4]
-END = [-1, 0, 2, -1, 0, -1, 1, -1, -1, -1]
-# the same queue with trials 1, 2, 4 and 6 harmless: nothing ends, the slots turn over every 4 ticks
-SLOT_CALM = [0, 1, 2, 3, 0, 1, 2, 3, 0, 1]
-START_CALM = [0, 0, 0, 0, 4, 4, 4, 4, 8, 8]
+# the hand-made tables of who sits where and when (tests/walk_refill_ref.py, where the assignment model is held to them)
+TRIAL_OF, SLOT, START, TICKS, END, SLOT_CALM, START_CALM = rf.TRIAL_OF, rf.SLOT, rf.START, rf.TICKS, rf.END, rf.SLOT_CALM, rf.START_CALM
 
 
 def _queue(harmless=False):
@@ -424,3 +414,135 @@ def test_refill_kernel_matches_the_host_form_chunks():
     assert h["next"][0] == Q and h["trial"][1::3][:7].tolist() == list(range(Q - 7, Q)) and (h["trial"][1::3][7:] == -1).all()
     assert (h["end_tick"][1::3][7:] == 3).all()
     s.close()
+
+
+# ---- 8. the kernel at the edges of a wave and of a chunk ----
+@pytest.fixture(scope="module")
+def solvers():
+    """one handle per batch size for the edge cases below (the refill launch takes nothing from a handle but its batch size and stream)"""
+    made = {}
+
+    def get(B):
+        if B not in made:
+            made[B] = cm.BatchSolver(cm.config.ergocub_gazebo_v1(10, 0.06), B)
+        return made[B]
+    yield get
+    for s in made.values():
+        s.close()
+
+
+@pytest.mark.parametrize("Qrule", ["Q0", "QB-1", "Q3B"])
+@pytest.mark.parametrize("B", [1, 63, 64, 65, 255, 256, 257, 513])
+def test_refill_kernel_at_wave_and_chunk_edges(B, Qrule, solvers):
+    """Three calls, the kernel against the host form on every array and both against the assignment model: the first fill (tick 0); tick 2 with a random third
+    of the slots ended at local tick 1 -- slot 0, the last slot and the slots either side of every multiple of 64 among them; tick 3 with every occupied slot
+    ended and at most seven trials left in the queue (the trials in between are skipped by moving *dNext, and the model's trial numbers with them), so the
+    queue runs dry inside a chunk.  trial_ticks = 50: nobody walks through."""
+    Q = {"Q0": 0, "QB-1": B - 1, "Q3B": 3 * B}[Qrule]
+    s = solvers(B)
+    rng = np.random.default_rng(100 * B + Q)
+    ended = set(rng.choice(B, B // 3, replace=False).tolist()) | {0, B - 1}
+    ended |= {b for k in range(64, B + 2, 64) for b in (k - 1, k, k + 1) if b < B}
+    ended = np.array(sorted(ended))
+    a = rf.arrays(B, Q, rows=4, seed=B + Q)
+    a["end_tick"][:] = -1
+    without = tuple(k for _, k, _, _ in rf.TRIAL) + ("state0",) if Q == 0 else ()
+    rec, f = rf.structs(a, 50, without=without)
+    assert cm._capi.lib().cmpc_rollout_refill_init(B, C.byref(f)) == 0
+
+    def call(a, tick, name):
+        h, g = _both(a, tick, 50, s)
+        for k in h:
+            _same_bits(g[k], h[k], f"{name} {k}")
+        return h
+
+    a = call(a, 0, "fill")
+    first = min(B, Q)                                   # (the trials of the first fill: trial b in slot b)
+    sat = ended[ended < first]
+    a["end_tick"][sat], a["end_code"][sat] = 1, 3
+    a = call(a, 2, "refill")
+    n2 = int(a["next"][0])
+    left = min(7, Q - n2)
+    skipped = Q - left - n2
+    a["next"][0] = Q - left
+    occupied = a["trial"] >= 0
+    a["end_tick"][occupied] = 2 - a["start_tick"][occupied]
+    a["end_code"][occupied] = 3
+    a = call(a, 3, "dry")
+    assert a["next"][0] == Q
+
+    # the model: the queue without the skipped trials; trials of the first fill end at local tick 1 or 2, the ones spawned at tick 2 at local tick 0
+    end_local = np.zeros(Q - skipped, int)
+    end_local[:first] = 2
+    end_local[sat] = 1
+    m = rf.assignment_model(B, Q - skipped, 50, 4, end_local)
+    number = lambda q: np.where(q >= n2, q + skipped, q)      # (the model's trial -> the queue's)
+    for t in (0, 2, 3):
+        np.testing.assert_array_equal(a["trial_of"][t], number(m["trial_of"][t]), err_msg=f"tick {t}")
+    np.testing.assert_array_equal(a["trial"], number(m["trial_of"][3]))
+    assert n2 == np.count_nonzero(m["start"][:n2] >= 0) and (m["start"][n2:] == 3).sum() == left
+    if Q:
+        took = number(np.arange(Q - skipped))
+        np.testing.assert_array_equal(a["q_slot"][took], m["slot"])
+        np.testing.assert_array_equal(a["q_start"][took], m["start"])
+        lost = np.setdiff1d(np.arange(Q), took)
+        assert (a["q_slot"][lost] == -1).all() and (a["q_start"][lost] == -1).all()
+        sits = a["trial"] >= 0
+        np.testing.assert_array_equal(a["start_tick"][sits], a["q_start"][a["trial"][sits]])
+    assert (a["end_tick"][a["trial"] < 0] >= 0).all()
+
+
+# ---- 9. the handle after a refill walk ----
+def test_handle_is_usable_after_a_refill_walk():
+    """the walk puts its record's end_tick in the handle's ended mask and turns the timing off, and restores both: a walk_device on the same object behind a
+    refill walk (a trial ended, the queue run dry, so slots went out through the mask) is the walk_device of a fresh object; an ended mask the caller had
+    installed is still there behind the refill walk, and a solve leaves the masked problem's rows alone"""
+    import torch
+    cfg = cm.config.ergocub_gazebo_v1(10, 0.06)
+    com0, dcom0, h0, push = _start(6, seed=51)
+    wrench = _push_rows(push.astype(np.float32), 2, 10)[:, :6]
+    wrench = np.concatenate([wrench, np.zeros((1,) + wrench.shape[1:], np.float32)])       # (4 rows = trial_ticks)
+    wrench[1, 2] = np.nan                                                                 # (trial 2 ends at its local tick 1)
+    c4, d4, h4, p4 = _start(4, seed=52)
+
+    def refill(ro):
+        w = ro.walk_device_refill(10, 4, com0, dcom0, h0, wrench_trials=wrench)
+        torch.cuda.synchronize()
+        t = w["trials"]
+        m = rf.assignment_model(4, 6, 4, 10, [-1, -1, 1, -1, -1, -1])
+        assert t["end_tick"].cpu().numpy().tolist() == m["end_tick"].tolist() == [-1, -1, 1, -1, -1, -1]
+        assert w["trial_of"].cpu().numpy().tolist() == m["trial_of"].tolist() and (m["trial_of"][-1] == -1).all()
+        assert (w["end_tick"].cpu().numpy() >= 0).all()
+        return w
+
+    want = _walk_arrays(cm.rollout.WalkingRollout(cfg, 4).walk_device(6, c4, d4, h4, push=p4, push_ticks=2))
+    torch.cuda.synchronize()
+    assert (want["end_tick"] == -1).all() and (want["iterations"] > 0).all()
+    ro = cm.rollout.WalkingRollout(cfg, 4)
+    refill(ro)
+    got = _walk_arrays(ro.walk_device(6, c4, d4, h4, push=p4, push_ticks=2))
+    torch.cuda.synchronize()
+    assert set(got) == set(want)
+    for k in want:
+        _same_bits(got[k], want[k], k)
+
+    # an ended mask of the caller's
+    def masked_solve(walk_first):
+        ro = cm.rollout.WalkingRollout(cfg, 4)
+        mask = torch.tensor([-1, 5, -1, -1], dtype=torch.int32, device="cuda")
+        ro.solver.set_ended_device(mask)
+        if walk_first:
+            refill(ro)
+        dP, dX0 = torch.from_numpy(want["P"]).cuda(), torch.from_numpy(want["X"]).cuda()
+        dX, dInfo = torch.full_like(dX0, 777.0), torch.full((4, 8), 777.0, device="cuda")
+        ro.solver.solve_device(dP, dX0, dX, dInfo)
+        torch.cuda.synchronize()
+        assert ro.solver._ended is mask and mask.cpu().numpy().tolist() == [-1, 5, -1, -1]
+        return dX.cpu().numpy(), _no_clock(dInfo.cpu().numpy())
+
+    X, info = masked_solve(True)
+    assert (X[1] == 777.0).all() and (info[1, [0, 1, 2, 3, 4, 5, 7]] == 777.0).all()
+    assert (X[[0, 2, 3]] != 777.0).any(1).all() and (info[[0, 2, 3], 5] == 0).all()
+    X0, info0 = masked_solve(False)
+    _same_bits(X, X0, "X")
+    _same_bits(info, info0, "info")

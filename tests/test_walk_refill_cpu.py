@@ -1,7 +1,7 @@
 """The refill of a walk's slots from a queue of trials without a GPU (include/cmpc.h, cmpc_walk_refill): the new symbols and the pinned signatures, the
 host form cmpc_rollout_refill on hand-made records -- assignment order, archive, the spawned slots' outcome, the edge cases Q < B and Q = 0 -- every
-refusal that must come before anything touches a GPU, and the host form once more from a stand-alone program built with the address and
-undefined-behaviour sanitizers."""
+refusal that must come before anything touches a GPU, the host form once more from a stand-alone program built with the address and
+undefined-behaviour sanitizers, and the host form tick by tick against an independent model of the assignment rule (tests/walk_refill_ref.py)."""
 import ctypes as C
 import inspect
 import os
@@ -212,3 +212,90 @@ def test_host_form_under_sanitizers(tmp_path):
     assert lines[1] == "refill next 7 trial 0 5 2 6 -1 start 1 3 1 3 0 end -1 -1 -1 -1 3 slot 0 1 2 3 4 1 3 ticks 2 2 2 2 3 0 0"
     assert lines[2] == lines[1].replace("refill", "nothing-free")
     assert lines[3] == "archive next 7 trial 0 5 2 6 -1 start 1 3 1 3 0 end -1 -1 -1 -1 3 slot 0 1 2 3 4 1 3 ticks 3 2 3 2 3 1 1"
+
+
+# ---- the assignment rule: an independent model, held to the hand-made tables, and the host form held to the model ----
+def test_assignment_model_reproduces_the_hand_made_tables():
+    """tests/walk_refill_ref.py's model against the tables of tests/test_gpu_walk_refill.py that were written down by hand: the stormy queue (trials 1, 4, 2 and
+    6 ending at local ticks 0, 0, 2 and 1), the calm one, test_queue_runs_dry's, and test_assignment_order_and_archive's B = 5 case"""
+    end = [-1] * 10
+    end[1], end[4], end[2], end[6] = 0, 0, 2, 1
+    m = rf.assignment_model(4, 10, 4, 12, end)
+    assert m["trial_of"].tolist() == rf.TRIAL_OF and m["slot"].tolist() == rf.SLOT and m["start"].tolist() == rf.START
+    assert m["ticks"].tolist() == rf.TICKS and m["end_tick"].tolist() == rf.END
+    assert rf.walk_length(4, 10, 4, end) == 9
+    m = rf.assignment_model(4, 10, 4, 12, [-1] * 10)
+    assert m["slot"].tolist() == rf.SLOT_CALM and m["start"].tolist() == rf.START_CALM and m["ticks"].tolist() == [4] * 10 and (m["end_tick"] == -1).all()
+    # test_queue_runs_dry: Q = 5, B = 4, trial_ticks = 4, 10 ticks
+    m = rf.assignment_model(4, 5, 4, 10, [-1] * 5)
+    assert m["trial_of"].tolist() == [[0, 1, 2, 3]] * 4 + [[4, -1, -1, -1]] * 4 + [[-1] * 4] * 2
+    assert m["slot"].tolist() == [0, 1, 2, 3, 0] and m["start"].tolist() == [0, 0, 0, 0, 4] and m["ticks"].tolist() == [4] * 5 and (m["end_tick"] == -1).all()
+    # a walk cut short: trial 4 has walked 2 of its 4 ticks after 6, and an ending behind the cut is not seen
+    m = rf.assignment_model(4, 5, 4, 6, [-1, -1, -1, -1, 3])
+    assert m["ticks"].tolist() == [4, 4, 4, 4, 2] and m["end_tick"].tolist() == [-1] * 5
+    # Q < B, Q = 0, and an ending at or past trial_ticks that never happens
+    m = rf.assignment_model(5, 2, 3, 2, [-1, 7])
+    assert m["trial_of"].tolist() == [[0, 1, -1, -1, -1]] * 2 and m["end_tick"].tolist() == [-1, -1]
+    m = rf.assignment_model(3, 0, 3, 2, [])
+    assert m["trial_of"].tolist() == [[-1] * 3] * 2 and m["slot"].shape == (0,)
+
+
+def _random_cases():
+    """(B, Q, trial_ticks, ticks, end_local, seed) of the property test: every B with every end probability and seven queue lengths 0 .. 4 B, seeds fixed"""
+    cases, seed = [], 1000
+    for B in (1, 2, 5, 63, 64, 65, 256, 257, 300):
+        for p_end in (0.0, 0.25, 0.75):
+            for Q in sorted({0, 1, max(B - 1, 0), B, B + 1, 2 * B + 3, 4 * B}) + [None]:
+                seed += 1
+                rng = np.random.default_rng(seed)
+                if Q is None:
+                    Q = int(rng.integers(0, 4 * B + 1))
+                trial_ticks = int(rng.integers(1, 7))
+                end = np.where(rng.random(Q) < p_end, rng.integers(0, trial_ticks, Q), -1)
+                full = rf.walk_length(B, Q, trial_ticks, end)
+                # mostly one tick past the end of the queue (the slots run dry); one walk in four is cut short
+                ticks = full + 1 if seed % 4 else max(1, full // 2)
+                cases.append((B, Q, trial_ticks, ticks, end, seed))
+    return cases
+
+
+def test_host_form_follows_the_assignment_model():
+    """cmpc_rollout_refill tick by tick against the model, over random B, Q, trial_ticks and endings: the test writes a slot's end_tick / end_code at the tick
+    the model ends its trial, as the record kernel would, and compares trial, start_tick, next and the trial_of row after every call, then q_slot,
+    q_start, q_ticks and q_end_tick behind the archive-only call.  All exact."""
+    cases = _random_cases()
+    assert len(cases) >= 200 and {c[0] for c in cases} == {1, 2, 5, 63, 64, 65, 256, 257, 300}
+    assert any(c[1] == 0 for c in cases) and any(c[1] == 4 * c[0] for c in cases) and {c[2] for c in cases} == {1, 2, 3, 4, 5, 6}
+    ended = 0
+    for B_, Q_, tt, ticks, end, seed in cases:
+        why = f"B {B_} Q {Q_} trial_ticks {tt} ticks {ticks} seed {seed}"
+        m = rf.assignment_model(B_, Q_, tt, ticks, end)
+        a = rf.arrays(B_, Q_, rows=ticks, seed=seed)
+        a["end_tick"][:] = -1        # (as cmpc_rollout_outcome_init_device leaves a record)
+        without = tuple(k for _, k, _, _ in rf.TRIAL) + ("state0",) if Q_ == 0 else ()
+        rec, f = rf.structs(a, tt, without=without)
+        lib = cm._capi.lib()
+        assert lib.cmpc_rollout_refill_init(B_, C.byref(f)) == 0, why
+        for t in range(ticks):
+            assert lib.cmpc_rollout_refill(B_, t, C.byref(rec), C.byref(f), a["state"].ctypes.data) == 0, why
+            want = m["trial_of"][t]
+            sits = want >= 0
+            assert np.array_equal(a["trial"], want) and np.array_equal(a["trial_of"][t], want), (why, t)
+            assert np.array_equal(a["start_tick"][sits], m["start"][want[sits]]), (why, t)
+            assert a["next"][0] == np.count_nonzero((m["start"] >= 0) & (m["start"] <= t)), (why, t)
+            assert (a["end_tick"][~sits] >= 0).all() and (a["end_tick"][sits] == -1).all(), (why, t)      # (an empty slot is out through the ended mask)
+            fresh = np.flatnonzero(sits)[m["start"][want[sits]] == t]        # (a spawned slot's live state is its trial's)
+            assert (rf.bits(a["state"][fresh]) == rf.bits(a["state0"][want[fresh]])).all(), (why, t)
+            # the record behind tick t: the trials the model ends at this tick
+            local = t - m["start"][want[sits]]
+            ends = np.flatnonzero(sits)[(end[want[sits]] == local) & (local < tt)]
+            a["end_tick"][ends] = end[want[ends]]
+            a["end_code"][ends] = 3
+            ended += len(ends)
+        assert (a["trial_of"][ticks:].size == 0), why
+        assert lib.cmpc_rollout_refill(B_, ticks, C.byref(rec), C.byref(f), None) == 0, why
+        if Q_:
+            for k, mk in (("q_slot", "slot"), ("q_start", "start"), ("q_ticks", "ticks"), ("q_end_tick", "end_tick")):
+                assert np.array_equal(a[k], m[mk]), (why, k)
+            assert np.array_equal(a["q_end_code"], np.where(m["end_tick"] >= 0, 3, 0)), why
+    assert ended > 1000
