@@ -33,6 +33,52 @@ def plant_step(L, corners, x, p, state, step, substeps, hidden=None, gain=1.0, *
     return plant_ref.plant_step(L, np.asarray(corners, np.float64).reshape(2, 4, 3), x2, p2, np.asarray(state, np.float64), step, substeps, **kw)
 
 
+def zmp_branches(L, corners, x, p, gain=1.0, threshold=0.001):
+    """the two thresholds of the plant's ZMP as the APPLIED force decides them -> (foot_in (bool, bool): the foot's F_z > threshold, defined: the F_z of
+    the feet that are in sum to more than threshold, margin: the smallest |F_z / threshold - 1| over the feet in contact and the sum, so that a caller can
+    require float32 and float64 to agree on the side)"""
+    x2, _ = applied_inputs(L, x, p, None, gain)
+    fz = [sum(x2[L.f[c][j] + 2] for j in range(4)) if p[L.p_gam[c]] > 0.5 else None for c in range(2)]
+    foot_in = tuple(bool(f is not None and f > threshold) for f in fz)
+    ztot = sum(f for f, on in zip(fz, foot_in) if on)
+    sides = [abs(f / threshold - 1.0) for f in fz if f is not None] + [abs(ztot / threshold - 1.0)]
+    return foot_in, bool(ztot > threshold), min(sides)
+
+
+def free_fall(state, f_ext, tau_ext, duration, gravity=ra.GRAVITY):
+    """the plant with no contact force applied (gain = 0, or both feet in the air), closed form over `duration`: a = f_ext - g e_z,
+    com' = com + T v + T^2/2 a, v' = v + T a, h' = h + T tau_ext (there is no force for the CoM to have a lever arm to)"""
+    s = np.asarray(state, np.float64)
+    a = np.asarray(f_ext, np.float64) - np.array([0.0, 0.0, gravity])
+    T = float(duration)
+    return np.concatenate([s[0:3] + T * s[3:6] + 0.5 * T * T * a, s[3:6] + T * a, s[6:9] + T * np.asarray(tau_ext, np.float64)])
+
+
+def schedule_row(schedule, tick_first, tick):
+    """row of tick number `tick` of a schedule [rows, B, .] whose row 0 is tick `tick_first`; None outside it (the term is then not applied)"""
+    r = int(tick) - int(tick_first)
+    return schedule[r] if schedule is not None and 0 <= r < len(schedule) else None
+
+
+def walk_plant_gaps(L, corners_of, tape, mismatch, problems=None):
+    """Every tick of a taped mismatched walk through the restated plant: plant_step(tape X[i], tape P[i], tape states[i] (the TRUE state), tick i's hidden
+    row or None, the gain) against tape states[i + 1].  tape: host arrays X, P [T, B, .], states [T + 1, B, 9], step (float32), substeps; corners_of(b)
+    -> [2][4][3] float64 of problem b; mismatch: host arrays.  -> (gap[T, B] largest absolute difference, gamma[T, B, 2] the contact flags of knot 0)"""
+    T, B = tape["X"].shape[0], tape["X"].shape[1]
+    problems = range(B) if problems is None else problems
+    gain = mismatch.get("force_gain")
+    gap, gamma = np.zeros((T, B)), np.zeros((T, B, 2), bool)
+    step = float(np.float32(tape["step"]))
+    for i in range(T):
+        hid = schedule_row(mismatch.get("hidden_wrench"), mismatch.get("tick_first", 0), i)
+        for b in problems:
+            ref, _ = plant_step(L, corners_of(b), tape["X"][i, b], tape["P"][i, b], tape["states"][i, b], step, int(tape["substeps"]),
+                                None if hid is None else hid[b], 1.0 if gain is None else float(gain[b]), gravity=float(np.float32(ra.GRAVITY)))
+            gap[i, b] = np.abs(np.asarray(tape["states"][i + 1, b], np.float64) - ref).max()
+            gamma[i, b] = [tape["P"][i, b, L.p_gam[c]] > 0.5 for c in range(2)]
+    return gap, gamma
+
+
 def plant_jacobian(L, corners, x, p, state, step, substeps, hidden=None, gain=1.0, gravity=ra.GRAVITY):
     """[9, 76] = d state' / d (state, pos_0, f_0 (the MPC's), fExt_0, tauExt_0, corners, hidden, gain)"""
     x2, p2 = applied_inputs(L, x, p, hidden, gain)

@@ -3,7 +3,8 @@ MPC is not told about, noise on the state it measures, a gain on the forces the 
 restatement tests/mismatch_ref.py, and everything above them as comparisons of bits: one call of the walk against the ticks composed by hand and against
 the tick entry point, off against the entry points that existed, a NaN push that ends one problem alone, a fork of one snapshot under B pushes against the
 unbroken walks, the reverse walk against the tick VJPs chained by hand through the gate, an ended problem against the shorter walk, autograd.
-N = 10, dt = 0.06, the ergoCubGazeboV1 weights, B = 8, 6 ticks unless stated."""
+N = 10, dt = 0.06, the ergoCubGazeboV1 weights, B = 8, 6 ticks unless stated.  Hand-made problems hold the two 0.001 thresholds of the ZMP and gain = 0
+(THRESHOLD_CASES).  No contact changes within 6 ticks: tests/test_gpu_mismatch_long.py walks 18 with the helpers defined here."""
 import numpy as np
 import pytest
 
@@ -91,6 +92,108 @@ def test_plant_kernel_matches_the_restatement():
     assert not np.array_equal(_h(only_h[0]), _h(only_g[0]))
 
 
+# ---- 1b. the two 0.001 thresholds of the ZMP see the APPLIED force ----
+G2 = 9.80665 / 2
+# (F_z of the left foot, of the right foot, the contact flags, the gain) as the MPC gives them; each side of 0.001 is at least 10 % away before and after the
+# gain (0.0008 * 1.5 = 0.0012, 0.0012 * 0.7 = 0.00084, 0.0006 * 1.5 = 0.0009), so that float32 and float64 agree on the side
+THRESHOLD_CASES = [
+    (0.0008, G2, (1, 1), 1.5), (0.0012, G2, (1, 1), 0.7),            # the gain puts the left foot into the ZMP / takes it out, beside a loaded right foot
+    (0.01, 0.0008, (1, 1), 1.5), (0.01, 0.0012, (1, 1), 0.7),        # the same for the right foot, beside a left foot that hardly outweighs it
+    (0.0008, 0.0008, (1, 1), 1.5), (0.0012, 0.0012, (1, 1), 0.7),    # ztot across 0.001: the ZMP appears / turns NaN
+    (G2, 0.0008, (0, 1), 1.5), (0.0012, G2, (1, 0), 0.7),            # ztot across 0.001 on one foot, the loaded one gated off
+    (G2, G2, (1, 1), 0.0), (G2, G2, (0, 1), 0.0), (G2, G2, (1, 0), 0.0),      # gain = 0: NaN ZMP, free fall plus the external wrenches
+    (0.0006, 0.0006, (1, 1), 1.5),                                   # neither foot reaches 0.001 though their sum does: NaN with and without the gain
+]
+THRESHOLD_IN = [(1, 1), (0, 1), (1, 1), (1, 0), (1, 1), (0, 0), (0, 1), (0, 0), (0, 0), (0, 0), (0, 0), (0, 0)]       # feet in the ZMP under the gain
+THRESHOLD_IN_PLAIN = [(0, 1), (1, 1), (1, 0), (1, 1), (0, 0), (1, 1), (0, 0), (1, 0), (1, 1), (0, 1), (1, 0), (0, 0)]   # ... and without it
+
+
+def _threshold_problems(cfg, seed=23):
+    """_plant_inputs' geometry, wrenches and states with the knot-0 forces of THRESHOLD_CASES: a foot's F_z spread unevenly over its corners (so that the local
+    ZMP is off-centre), lateral forces a fifth of it -> float32 (X, P, state, models, hidden[12, 6], gain[12])"""
+    L, nb = cm.Layout(cfg.N), len(THRESHOLD_CASES)
+    X, P, state, models = _plant_inputs(cfg, nb, seed)
+    share = np.array([0.4, 0.3, 0.2, 0.1])
+    for b, (fz0, fz1, gam, _) in enumerate(THRESHOLD_CASES):
+        for c, fz in enumerate((fz0, fz1)):
+            P[b, L.p_gam[c]] = float(gam[c])
+            for j in range(4):
+                X[b, L.f[c][j]:L.f[c][j] + 3] = np.float32(fz * share[j]) * np.array([0.2, -0.1, 1.0], np.float32)
+    rng = np.random.default_rng(seed + 1)
+    hidden = np.concatenate([rng.normal(0, 0.5, (nb, 3)), rng.normal(0, 0.1, (nb, 3))], 1).astype(np.float32)
+    return X, P, state, models, hidden, np.array([c[3] for c in THRESHOLD_CASES], np.float32)
+
+
+def test_plant_thresholds_see_the_applied_force():
+    """12 hand-made problems (THRESHOLD_CASES) whose gain decides F_z > 0.001 of a foot or ztot > 0.001: state and ZMP within 2e-6 of the restatement (the
+    bound of test_plant_kernel_matches_the_restatement), the ZMP's NaN pattern identical; the restatement takes the branches written down by hand, and -- in
+    the 11 problems that are pairs -- the plain plant takes the other one, on the device too; gain = 0 is free fall under the two wrenches, closed form"""
+    import torch
+    cfg = cm.config.ergocub_gazebo_v1(N, 0.06)
+    L, nb, step, nsub = cm.Layout(N), len(THRESHOLD_CASES), 0.01, 6
+    X, P, state, _, hidden, gain = _threshold_problems(cfg)
+    s = cm.BatchSolver(cfg, nb)
+    dX, dP, dS = _cu(X), _cu(P), _cu(state)
+    got_s, got_z = (_h(a) for a in s.plant_step_mismatch_device(dX, dP, dS, step=step, substeps=nsub, hidden_wrench=_cu(hidden), force_gain=_cu(gain)))
+    pl_s, pl_z = (_h(a) for a in s.plant_step_mismatch_device(dX, dP, dS, step=step, substeps=nsub, hidden_wrench=_cu(hidden)))
+    torch.cuda.synchronize()
+    corners = np.asarray([c.corners for c in cfg.contacts], np.float64).astype(np.float32).astype(np.float64)
+    kw = dict(gravity=float(np.float32(rar.GRAVITY)))
+    worst = dict(state=0.0, zmp=0.0, plain_state=0.0, plain_zmp=0.0, free_fall=0.0)
+    for b in range(nb):
+        feet, defined, margin = mr.zmp_branches(L, corners, X[b], P[b], float(gain[b]))
+        feet_p, defined_p, margin_p = mr.zmp_branches(L, corners, X[b], P[b], 1.0)
+        assert feet == tuple(map(bool, THRESHOLD_IN[b])) and feet_p == tuple(map(bool, THRESHOLD_IN_PLAIN[b])), (b, feet, feet_p)
+        assert defined == any(feet) and defined_p == any(feet_p)
+        assert margin >= 0.1 and margin_p >= 0.1, (b, margin, margin_p)
+        if b < 11:
+            assert feet != feet_p, b                   # the plain plant takes the other branch
+        for name, gs, gz, gg in (("", got_s, got_z, float(gain[b])), ("plain_", pl_s, pl_z, 1.0)):
+            ref_s, ref_z = mr.plant_step(L, corners, X[b], P[b], state[b], float(np.float32(step)), nsub, hidden[b], gg, **kw)
+            assert (np.isnan(gz[b]) == np.isnan(ref_z)).all() and np.isnan(ref_z).all() == (not (defined if name == "" else defined_p)), (b, name, gz[b], ref_z)
+            worst[name + "state"] = max(worst[name + "state"], float(np.abs(gs[b] - ref_s).max()))
+            worst[name + "zmp"] = max(worst[name + "zmp"], float(np.abs(np.where(np.isnan(ref_z), 0.0, gz[b] - ref_z)).max()))
+        if b < 11:      # ... on the device too: the ZMP with the gain is not the ZMP without it
+            assert not np.array_equal(got_z[b], pl_z[b], equal_nan=True), b
+        if gain[b] == 0.0:
+            fall = mr.free_fall(state[b], P[b, L.p_fext:L.p_fext + 3].astype(np.float64) + hidden[b, :3], P[b, L.p_text:L.p_text + 3].astype(np.float64) + hidden[b, 3:],
+                                nsub * float(np.float32(step)), **kw)
+            worst["free_fall"] = max(worst["free_fall"], float(np.abs(got_s[b] - fall).max()))
+    print("\nthreshold problems: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()) + " (bound 2e-6)")
+    assert max(worst.values()) <= 2e-6, worst
+
+
+def test_plant_vjp_kernel_at_the_thresholds_and_gain_zero():
+    """the 12 threshold problems through cmpc_plant_step_vjp_mismatch_device against the restatement within REF; at gain = 0 grad_x is exactly zero on the
+    forces (and everywhere: no force is applied, so no position or corner has a lever arm) and grad_gain is not"""
+    import torch
+    cfg = cm.config.ergocub_gazebo_v1(N, 0.06)
+    L, nb, step, nsub = cm.Layout(N), len(THRESHOLD_CASES), 0.01, 6
+    X, P, state, models, hidden, gain = _threshold_problems(cfg)
+    g = np.random.default_rng(10).normal(size=(nb, 9))
+    s = cm.BatchSolver(cfg, nb)
+    s.set_models(models)
+    r = s.plant_step_vjp_mismatch_device(_cu(X), _cu(P), _cu(state), _cu(g), step=step, substeps=nsub, hidden_wrench=_cu(hidden), force_gain=_cu(gain))
+    torch.cuda.synchronize()
+    got = {k: _h(v) for k, v in r.items() if v is not None}
+    xi, _ = rar.plant_columns(L)
+    worst = {k: 0.0 for k in ("state", "x", "p", "model", "hidden", "gain")}
+    for b in range(nb):
+        corners = models[b, 10:].astype(np.float32).astype(np.float64)
+        ref = mr.plant_vjp(L, corners, X[b], P[b], state[b], float(np.float32(step)), nsub, g[b], hidden[b], float(gain[b]), gravity=float(np.float32(rar.GRAVITY)))
+        for k, v in zip(("state", "x", "p", "model", "hidden"), ref[:5]):
+            if np.abs(v).max() == 0:       # (a group without a gradient: exact zeros are asked for, not a ratio)
+                assert not got[k][b].any(), (b, k)
+                continue
+            worst[k] = max(worst[k], _rel(got[k][b], v))
+        worst["gain"] = max(worst["gain"], abs(got["gain"][b] - ref[5]) / max(abs(ref[5]), 1e-300))
+        assert np.abs(ref[4]).max() > 0 and ref[5] != 0
+        if gain[b] == 0.0:
+            assert not got["x"][b][xi[6:]].any() and not ref[1][xi[6:]].any() and got["gain"][b] != 0, b
+    print("\nthreshold problems, plant VJP: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()) + f" (bound {REF:.0e})")
+    assert max(worst.values()) <= REF, worst
+
+
 # ---- 2. the plant VJP ----
 def test_plant_vjp_kernel_matches_the_restatement():
     """every output of cmpc_plant_step_vjp_mismatch_device against the restatement within REF (relative to the group's largest entry), with the rotation
@@ -132,6 +235,79 @@ def test_plant_vjp_kernel_matches_the_restatement():
     np.testing.assert_array_equal(_h(null["hidden"]).astype(np.float32), np.concatenate([gp[:, L.p_fext:L.p_fext + 3], gp[:, L.p_text:L.p_text + 3]], 1))
 
 
+# ---- the two compositions of a mismatched walk out of its steps, shared with tests/test_gpu_mismatch_long.py ----
+def _sched_row(sched, mm, i):
+    """row of tick i of a schedule (numpy or CUDA, or None) under mm's tick_first, None outside it"""
+    r = i - mm.get("tick_first", 0)
+    return sched[r] if sched is not None and 0 <= r < sched.shape[0] else None
+
+
+def _step_buffers(make_ro, start, ticks):
+    import torch
+    ro = make_ro()
+    L, nb = ro.L, ro.B
+    z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=ro.dev)
+    state = _cu(np.concatenate(start, 1).astype(np.float32))
+    return ro, z((nb, L.np)), z((nb, L.nx)), z((nb, L.nx)), z((nb, 8)), state, ro._planner_refs(ticks)
+
+
+def _steps_by_hand(make_ro, start, mm, ticks, tape):
+    """a walk of `ticks` ticks under mm composed by hand on a fresh roll-out of make_ro() -- merge, sample, the references, setState of state + noise added
+    by torch in float32, cold start / shift, solve, adjust, cmpc_plant_step_mismatch_device -- against the tape's P, X and states, to the bit"""
+    hidden, noise, gain = (None if mm.get(k) is None else _cu(mm[k]) for k in ("hidden_wrench", "state_noise", "force_gain"))
+    ro, dP, dX0, dX, dInfo, state, refs = _step_buffers(make_ro, start, ticks)
+    s, dt = ro.solver, ro.cfg.sampling_time
+    kw = dict(step=dt / ro.substeps, substeps=ro.substeps)
+    prev = None
+    for i in range(ticks):
+        now = i * dt
+        lists = tuple(a.clone() for a in ro.plan) if prev is None else s.contacts_merge_device(now, ro.plan, prev)[0]
+        land = s.contacts_sample_device(now, lists, dP)
+        s.write_reference_from_planner_device(refs[0], refs[1], refs[2], now - refs[3], refs[4], refs[5], dP)
+        nz = _sched_row(noise, mm, i)
+        s.write_state_device(state if nz is None else state + nz, dP, None)
+        if prev is None:
+            s.cold_start_device(dP, dX0)
+        else:
+            s.shift_solution_device(dX, dX0)
+        s.solve_device(dP, dX0, dX, dInfo, warm=prev is not None)
+        s.contacts_adjust_device(now, dX, land, lists)
+        _same_bits(tape["states"][i], state, f"by hand, tick {i}: the state the tick started from")
+        state, _ = s.plant_step_mismatch_device(dX, dP, state, hidden_wrench=_sched_row(hidden, mm, i), force_gain=gain, **kw)
+        _same_bits(tape["P"][i], dP, f"by hand, tick {i}: P")
+        _same_bits(tape["X"][i], dX, f"by hand, tick {i}: X")
+        _same_bits(tape["states"][i + 1], state, f"by hand, tick {i}: the state it left")
+        prev = lists
+
+
+def _steps_by_tick_entry(make_ro, start, mm, ticks, tape):
+    """the same walk through cmpc_rollout_tick_mismatch_device called tick by tick, against the tape's P, X and states, to the bit
+    -> (the roll-out, its solver, the plant_mismatch dict it walked under)"""
+    import torch
+    ro, dP, dX0, dX, dInfo, state, refs = _step_buffers(make_ro, start, ticks)
+    s, dt, nb = ro.solver, ro.cfg.sampling_time, ro.B
+    kw = dict(step=dt / ro.substeps, substeps=ro.substeps)
+    mmc = s.plant_mismatch(**mm)
+    ok, land, zmp = torch.ones((nb,), dtype=torch.int32, device=ro.dev), torch.zeros((nb, 2), dtype=torch.int32, device=ro.dev), torch.zeros((nb, 2), device=ro.dev)
+    sets, cur = [tuple(a.clone() for a in ro.plan), tuple(torch.zeros_like(a) for a in ro.plan)], 0
+    for i in range(ticks):
+        now = i * dt
+        planner = (refs[0], refs[1], refs[2], now - refs[3], refs[4], refs[5])
+        if i == 0:
+            s.contacts_sample_device(now, sets[0], dP)
+            s.write_state_device(state, dP, None)
+            s.cold_start_device(dP, dX0)
+            prv, lists = None, sets[0]
+        else:
+            prv, lists = sets[cur], sets[1 - cur]
+            cur = 1 - cur
+        s.rollout_tick_mismatch_device(i, mmc, now, ro.plan, prv, lists, ok, land, state, None, dP, dX0, dX, dInfo, state, zmp, i > 0, planner=planner, **kw)
+        _same_bits(tape["P"][i], dP, f"tick entry, tick {i}: P")
+        _same_bits(tape["X"][i], dX, f"tick entry, tick {i}: X")
+        _same_bits(tape["states"][i + 1], state, f"tick entry, tick {i}: state")
+    return ro, s, mmc
+
+
 # ---- 3 .. 5, 7, 8: one walk of 6 ticks under all three, taped, and the same walk plain ----
 @pytest.fixture(scope="module")
 def walk6():
@@ -162,59 +338,10 @@ def test_one_call_is_the_steps(walk6):
     com0, dcom0, h0 = walk6["start"]
     tape = w["tape"]
     untaped = cm.rollout.WalkingRollout(cfg, B).walk_device_mismatch(T, com0, dcom0, h0, mm)
-    hidden, noise, gain = _cu(mm["hidden_wrench"]), _cu(mm["state_noise"]), _cu(mm["force_gain"])
-    row = lambda sched, i: sched[i - mm["tick_first"]] if 0 <= i - mm["tick_first"] < sched.shape[0] else None
-
-    def buffers():
-        ro = cm.rollout.WalkingRollout(cfg, B)
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=ro.dev)
-        state = _cu(np.concatenate([com0, dcom0, h0], 1).astype(np.float32))
-        return ro, z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8)), state, ro._planner_refs(T)
-
-    # by hand
-    ro, dP, dX0, dX, dInfo, state, refs = buffers()
-    s, kw = ro.solver, dict(step=dt / ro.substeps, substeps=ro.substeps)
-    prev = None
-    for i in range(T):
-        now = i * dt
-        lists = tuple(a.clone() for a in ro.plan) if prev is None else s.contacts_merge_device(now, ro.plan, prev)[0]
-        land = s.contacts_sample_device(now, lists, dP)
-        s.write_reference_from_planner_device(refs[0], refs[1], refs[2], now - refs[3], refs[4], refs[5], dP)
-        nz = row(noise, i)
-        s.write_state_device(state if nz is None else state + nz, dP, None)
-        if prev is None:
-            s.cold_start_device(dP, dX0)
-        else:
-            s.shift_solution_device(dX, dX0)
-        s.solve_device(dP, dX0, dX, dInfo, warm=prev is not None)
-        s.contacts_adjust_device(now, dX, land, lists)
-        _same_bits(tape["states"][i], state, f"by hand, tick {i}: the state the tick started from")
-        state, _ = s.plant_step_mismatch_device(dX, dP, state, hidden_wrench=row(hidden, i), force_gain=gain, **kw)
-        _same_bits(tape["P"][i], dP, f"by hand, tick {i}: P")
-        _same_bits(tape["X"][i], dX, f"by hand, tick {i}: X")
-        _same_bits(tape["states"][i + 1], state, f"by hand, tick {i}: the state it left")
-        prev = lists
-    # tick by tick through the tick entry point
-    ro, dP, dX0, dX, dInfo, state, refs = buffers()
-    s = ro.solver
-    mmc = s.plant_mismatch(**mm)
-    ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=ro.dev), torch.zeros((B, 2), dtype=torch.int32, device=ro.dev), torch.zeros((B, 2), device=ro.dev)
-    sets, cur = [tuple(a.clone() for a in ro.plan), tuple(torch.zeros_like(a) for a in ro.plan)], 0
-    for i in range(T):
-        now = i * dt
-        planner = (refs[0], refs[1], refs[2], now - refs[3], refs[4], refs[5])
-        if i == 0:
-            s.contacts_sample_device(now, sets[0], dP)
-            s.write_state_device(state, dP, None)
-            s.cold_start_device(dP, dX0)
-            prv, lists = None, sets[0]
-        else:
-            prv, lists = sets[cur], sets[1 - cur]
-            cur = 1 - cur
-        s.rollout_tick_mismatch_device(i, mmc, now, ro.plan, prv, lists, ok, land, state, None, dP, dX0, dX, dInfo, state, zmp, i > 0, planner=planner, **kw)
-        _same_bits(tape["P"][i], dP, f"tick entry, tick {i}: P")
-        _same_bits(tape["X"][i], dX, f"tick entry, tick {i}: X")
-        _same_bits(tape["states"][i + 1], state, f"tick entry, tick {i}: state")
+    make_ro = lambda: cm.rollout.WalkingRollout(cfg, B)
+    _steps_by_hand(make_ro, walk6["start"], mm, T, tape)
+    ro, s, mmc = _steps_by_tick_entry(make_ro, walk6["start"], mm, T, tape)
+    hidden = _cu(mm["hidden_wrench"])
     torch.cuda.synchronize()
     for k in REC_KEYS:
         _same_bits(untaped[k], w[k], f"untaped against taped: {k}")
@@ -357,30 +484,7 @@ def test_tick_vjp_matches_the_restated_tick(walk6):
     M = tape["list_t"].shape[3]
     rng = np.random.default_rng(21)
     gain = _cu(mm["force_gain"])
-    groups = ("state", "prev_list", "wrench", "plan", "model", "p", "hidden", "noise", "gain")
-    worst = {k: 0.0 for k in groups}
-    for i in (1, 2, 4):
-        tk = _tick_tape(tape, i)
-        hid = _rows(mm, i)
-        g_state, g_list = rng.normal(size=(B, 9)), rng.normal(size=(B, 2, M, 3)) * 0.1
-        gplan, gmodel = torch.zeros((B, 2, M, 3), dtype=torch.float64, device="cuda"), torch.zeros((B, 34), dtype=torch.float64, device="cuda")
-        ggain = torch.zeros((B,), dtype=torch.float64, device="cuda")
-        now = i * cfg.sampling_time
-        r = s.rollout_tick_vjp_device(now, tk, _cu(g_state), _cu(g_list), dGradPlan=gplan, dGradModel=gmodel, grad_p=True, mismatch=True,
-                                      hidden_wrench=None if hid is None else _cu(hid), force_gain=gain, dGradGain=ggain)
-        torch.cuda.synchronize()
-        assert (_h(r["sens"])[:, 0] == 0).all(), _h(r["sens"])[:, 0]
-        got = {k: _h(v) for k, v in dict(state=r["state"], prev_list=r["prev_list"], wrench=r["wrench"], plan=gplan, model=gmodel, p=r["p"], hidden=r["hidden"],
-                                         noise=r["noise"], gain=ggain).items()}
-        for b in (0, 5):
-            ref = mr.tick_vjp(cfg, _host_tape(tk, b, None if hid is None else hid[b], float(mm["force_gain"][b])), now, g_state[b], g_list[b])
-            assert ref["status"] == 0
-            gaps = {k: _rel(got[k][b], ref[k]) for k in groups}
-            print(f"tick {i} problem {b}: " + " ".join(f"{k} {v:.1e}" for k, v in gaps.items()) +
-                  f"  |hidden| {np.abs(got['hidden'][b]).max():.1e} |noise| {np.abs(got['noise'][b]).max():.1e} |gain| {abs(got['gain'][b]):.1e}")
-            for k in groups:
-                worst[k] = max(worst[k], gaps[k])
-            assert np.abs(got["hidden"][b]).max() > 0 and np.abs(got["noise"][b]).max() > 0 and abs(got["gain"][b]) > 0
+    worst = _tick_vjp_gaps(cfg, mm, tape, s, (1, 2, 4), (0, 5), rng)
     print("mismatch tick VJP against the restated tick, worst: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()) + f" (bound {REF:.0e})")
     assert max(worst.values()) <= REF, worst
     # a flagged problem
@@ -409,14 +513,49 @@ def test_tick_vjp_matches_the_restated_tick(walk6):
         _same_bits(new[k], old[k], f"both inputs NULL: {k}")
 
 
-# ---- 8. the reverse walk ----
-def test_reverse_walk_is_the_tick_vjps_chained_by_hand(walk6):
-    """backward_device on the mismatch tape against cmpc_rollout_tick_vjp_mismatch_device chained by hand, last tick first, with one
-    cmpc_rollout_walk_vjp_gate_device step between the ticks: every key to the bit; backward_device_rot leaves the three new keys (and the old ones) bit-equal"""
+TICK_GROUPS = ("state", "prev_list", "wrench", "plan", "model", "p", "hidden", "noise", "gain")
+
+
+def _tick_vjp_gaps(cfg, mm, tape, s, ticks, problems, rng):
+    """cmpc_rollout_tick_vjp_mismatch_device on the given ticks of a taped walk against the restated tick (tests/mismatch_ref.tick_vjp) fed with the tape's own
+    float32 (x, p, lam_g), for the given problems: -> the worst relative gap per group (TICK_GROUPS); the three new groups are asserted non-zero"""
     import torch
-    cfg, mm, ro, w, gS, got = walk6["cfg"], walk6["mm"], walk6["ro"], walk6["w"], walk6["gS"], walk6["got"]
-    tape, s, M, dev, dt = w["tape"], ro.solver, ro.M, ro.dev, cfg.sampling_time
-    assert set(NEW) <= set(got) and tuple(got["hidden_wrench"].shape) == (T, B, 6) and tuple(got["state_noise"].shape) == (T, B, 9)
+    nb, M = tape["X"].shape[1], tape["list_t"].shape[3]
+    gain = _cu(mm["force_gain"])
+    groups = TICK_GROUPS
+    worst = {k: 0.0 for k in groups}
+    for i in ticks:
+        tk = _tick_tape(tape, i)
+        hid = _rows(mm, i)
+        g_state, g_list = rng.normal(size=(nb, 9)), rng.normal(size=(nb, 2, M, 3)) * 0.1
+        gplan, gmodel = torch.zeros((nb, 2, M, 3), dtype=torch.float64, device="cuda"), torch.zeros((nb, 34), dtype=torch.float64, device="cuda")
+        ggain = torch.zeros((nb,), dtype=torch.float64, device="cuda")
+        now = i * cfg.sampling_time
+        r = s.rollout_tick_vjp_device(now, tk, _cu(g_state), _cu(g_list), dGradPlan=gplan, dGradModel=gmodel, grad_p=True, mismatch=True,
+                                      hidden_wrench=None if hid is None else _cu(hid), force_gain=gain, dGradGain=ggain)
+        torch.cuda.synchronize()
+        assert (_h(r["sens"])[:, 0] == 0).all(), _h(r["sens"])[:, 0]
+        got = {k: _h(v) for k, v in dict(state=r["state"], prev_list=r["prev_list"], wrench=r["wrench"], plan=gplan, model=gmodel, p=r["p"], hidden=r["hidden"],
+                                         noise=r["noise"], gain=ggain).items()}
+        for b in problems:
+            ref = mr.tick_vjp(cfg, _host_tape(tk, b, None if hid is None else hid[b], float(mm["force_gain"][b])), now, g_state[b], g_list[b])
+            assert ref["status"] == 0
+            gaps = {k: _rel(got[k][b], ref[k]) for k in groups}
+            print(f"tick {i} problem {b}: " + " ".join(f"{k} {v:.1e}" for k, v in gaps.items()) +
+                  f"  |hidden| {np.abs(got['hidden'][b]).max():.1e} |noise| {np.abs(got['noise'][b]).max():.1e} |gain| {abs(got['gain'][b]):.1e}")
+            for k in groups:
+                worst[k] = max(worst[k], gaps[k])
+            assert np.abs(got["hidden"][b]).max() > 0 and np.abs(got["noise"][b]).max() > 0 and abs(got["gain"][b]) > 0
+    return worst
+
+
+# ---- 8. the reverse walk ----
+def _reverse_by_hand(ro, w, gS, mm):
+    """the reverse of a taped mismatched walk as cmpc_rollout_tick_vjp_mismatch_device chained by hand, last tick first, with one
+    cmpc_rollout_walk_vjp_gate_device step between the ticks -> (backward_device's row and sum outputs, the state carry, the list carry)"""
+    import torch
+    tape, s, M, dev, dt = w["tape"], ro.solver, ro.M, ro.dev, ro.cfg.sampling_time
+    T, B, N = int(tape["rows"]), ro.B, ro.cfg.N
     z = lambda shape, dtp=torch.float64: torch.zeros(shape, dtype=dtp, device=dev)
     out = dict(wrench=z((T, B, N, 6), torch.float32), models=z((B, 34)), plan=z((B, 2, M, 3)), status=z((T, B), torch.int32), hidden_wrench=z((T, B, 6)),
                state_noise=z((T, B, 9), torch.float32), force_gain=z((B,)))
@@ -446,6 +585,17 @@ def test_reverse_walk_is_the_tick_vjps_chained_by_hand(walk6):
             r = s.rollout_tick_vjp_device((i - 1) * dt, tk, carry_s, carry_l, dGradPlan=out["plan"], dGradModel=out["models"], mismatch=True,
                                           hidden_wrench=None if hid is None else _cu(hid), force_gain=gain, dGradGain=out["force_gain"])
     torch.cuda.synchronize()
+    return out, carry_s, carry_l
+
+
+def test_reverse_walk_is_the_tick_vjps_chained_by_hand(walk6):
+    """backward_device on the mismatch tape against cmpc_rollout_tick_vjp_mismatch_device chained by hand, last tick first, with one
+    cmpc_rollout_walk_vjp_gate_device step between the ticks: every key to the bit; backward_device_rot leaves the three new keys (and the old ones) bit-equal"""
+    import torch
+    cfg, mm, ro, w, gS, got = walk6["cfg"], walk6["mm"], walk6["ro"], walk6["w"], walk6["gS"], walk6["got"]
+    tape, s, M, dev, dt = w["tape"], ro.solver, ro.M, ro.dev, cfg.sampling_time
+    assert set(NEW) <= set(got) and tuple(got["hidden_wrench"].shape) == (T, B, 6) and tuple(got["state_noise"].shape) == (T, B, 9)
+    out, carry_s, carry_l = _reverse_by_hand(ro, w, gS, mm)
     _same_bits(carry_s, got["state0"], "state0")
     _same_bits(carry_l, got["list0"], "list0")
     for k in ("wrench", "models", "plan", "status") + NEW:

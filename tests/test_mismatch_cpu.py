@@ -24,9 +24,27 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 @pytest.mark.parametrize("gate_off,yaw", [(None, 0.0), (1, 0.0), (None, 0.6)])
 def test_mismatch_columns_match_central_differences(gate_off, yaw):
     """the restatement's Jacobian columns for the hidden wrench, the gain and the MPC's forces against central differences of the restated plant, step 1e-4"""
+    _check_columns(gate_off, yaw, 0.87)
+
+
+@pytest.mark.parametrize("gate_off", [None, 0])
+def test_mismatch_columns_at_gain_zero(gate_off):
+    """gain = 0, where the plant applies no contact force at all: the force columns are exactly zero on both sides, the gain column is not (the plant is
+    linear in the gain, so the central difference across zero is exact), the hidden wrench's is the plain plant's; and the state is free fall under the
+    two external wrenches, closed form"""
+    _check_columns(gate_off, 0.3, 0.0)
+    L, corners, x, p, state = _plant_case(7, gate_off, 0.3)
+    hidden = np.random.default_rng(17).normal(0, 0.4, 6)
+    got, zmp = mr.plant_step(L, corners, x, p, state, 0.01, 6, hidden, 0.0)
+    want = mr.free_fall(state, p[L.p_fext:L.p_fext + 3] + hidden[:3], p[L.p_text:L.p_text + 3] + hidden[3:], 0.06)
+    assert np.abs(got - want).max() <= 1e-13 and np.isnan(zmp).all()
+    assert mr.zmp_branches(L, corners, x, p, 0.0)[:2] == ((False, False), False)
+
+
+def _check_columns(gate_off, yaw, gain):
     L, corners, x, p, state = _plant_case(7, gate_off, yaw)
     rng = np.random.default_rng(17)
-    hidden, gain = rng.normal(0, 0.4, 6), 0.87
+    hidden = rng.normal(0, 0.4, 6)
     step, nsub, eps = 0.01, 6, 1e-4
     J = mr.plant_jacobian(L, corners, x, p, state, step, nsub, hidden, gain)
     xi, _ = ra.plant_columns(L)
@@ -47,6 +65,9 @@ def test_mismatch_columns_match_central_differences(gate_off, yaw):
     fd["gain"] = ((f(x, hidden, gain + eps) - f(x, hidden, gain - eps)) / (2 * eps))[:, None]
     got = dict(forces=J[:, ra.C_F:ra.C_FEXT], hidden=J[:, mr.C_HID:mr.C_HID + 6], gain=J[:, mr.C_GAIN:mr.C_GAIN + 1])
     for k in fd:
+        if gain == 0.0 and k == "forces":      # no force is applied: no derivative, exactly, on either side
+            assert not got[k].any() and not fd[k].any()
+            continue
         gap = np.abs(got[k] - fd[k]).max() / np.abs(fd[k]).max()
         print(f"mismatch partials gate_off={gate_off} yaw={yaw} {k}: relative gap {gap:.2e} (bound {FD:.0e})")
         assert gap <= FD, (k, gap)
