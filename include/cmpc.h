@@ -802,9 +802,38 @@ int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, c
  * While the call queues, the ended mask is rec->dEndTick itself; the handle's own setting is saved and restored.  io->tick.dWrench is not read.
  * CMPC_ERR_ARG before anything is queued: max_contacts > 16 (the first tick uses the front kernel's LDS stage), io->dWrenchTicks set (the schedule is the
  * per-trial one), rec NULL or with too few rows, io->tick.dState != io->tick.dStateOut, no dOk, and what cmpc_rollout_walk_device and
- * cmpc_rollout_refill_device refuse.  Tapes, plant mismatch, gradients and forward mode are out of scope: no entry point takes a refill together with them. */
+ * cmpc_rollout_refill_device refuse.  Tapes, gradients and forward mode are out of scope: no entry point takes a refill together with them; per-trial
+ * models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL. */
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream);
+/* Per-trial data of a refill walk; every array is a device array indexed by TRIAL q (0 <= q < refill->trials), schedules by the trial's LOCAL tick r.
+ * Each pointer may be NULL: that part is then what cmpc_rollout_walk_refill_device does today.  sizeof == 56 (LP64; the ctypes mirror is held to it). */
+typedef struct cmpc_walk_refill_trials {
+    const cmpc_model* dModels;  int* dModelOk;      /* [Q]; dModelOk [Q] or NULL: 1 / 0 written at the trial's first tick, untouched for a trial never started */
+    const float* dHiddenWrench; int hidden_ticks;   /* [hidden_ticks][Q][6] */
+    const float* dStateNoise;   int noise_ticks;    /* [noise_ticks][Q][9]  */
+    const float* dForceGain;                        /* [Q] */
+} cmpc_walk_refill_trials;
+/* cmpc_rollout_walk_refill_device with what a Monte-Carlo study randomises per TRIAL: the robot (dModels, the rows of cmpc_set_models_device) and the
+ * disturbance (the three parts of cmpc_plant_mismatch, row = the trial's local tick, column = the trial).  Still FIVE launches per tick; the solver kernel
+ * is the one of every other entry point.  trials == NULL, or every pointer in it NULL: cmpc_rollout_walk_refill_device, bit for bit.
+ *   dModels: on a slot's first tick the front kernel's workgroup writes the slot's record of the handle's per-problem table -- the handle's own record with
+ *     dModels[q] applied, bit-equal to what cmpc_set_models_device would have put there; a row that breaks the model rule keeps the handle's model, is
+ *     flagged (dModelOk[q] = 0) and ends the trial at its first tick through the solver's status 3.  The solve and the back kernel of that tick and of
+ *     every later tick of the trial read the record in stream order.  The call allocates the table if needed and switches the handle to it before it queues
+ *     anything, and leaves it switched on: AFTER THE CALL THE TABLE HOLDS EACH SLOT'S LAST TRIAL'S MODEL (a slot that never received a trial holds whatever
+ *     it held before, behind the ended mask) -- follow the call with cmpc_set_models[_device] to go on with models of one's own.
+ *   dStateNoise: the front kernel adds row [r][q] to the state the MPC measures, one float32 add, when 0 <= r < noise_ticks; else the plain copy.
+ *   dHiddenWrench, dForceGain: the back kernel's plant step uses row [r][q] when 0 <= r < hidden_ticks -- outside the range the hidden term is not
+ *     added (a select, never an add of zero) -- and dForceGain[q]; nothing of them is written to dP.
+ * A trial's outcome, trace rows, dX, dP, dInfo, state and the entries in use of its lists are those of cmpc_rollout_walk_mismatch_device(cold_first = 1,
+ * tick_first = 0) on a handle of the same batch size, factor storage and options that holds it in the same slot, with cmpc_set_models_device's row `slot`
+ * the trial's model and the schedules' column `slot` the trial's rows.
+ * CMPC_ERR_ARG before anything is queued: everything cmpc_rollout_walk_refill_device refuses, in its order; a negative count; a schedule with a zero
+ * count; dModelOk without dModels. */
+int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                           const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
+                                           void* stream);
 /* ---- the roll-out tick in reverse (derivation: DESIGN.md 7d) ----
  * Adjoint of the list path of one tick in the contacts' POSITIONS; times are not differentiated; the orientations have their own entry point below
  * (cmpc_contacts_orientation_vjp_device).  The forward maps move positions

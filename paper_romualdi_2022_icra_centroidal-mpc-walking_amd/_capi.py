@@ -75,6 +75,12 @@ class CmpcWalkRefill(C.Structure):
         "dTrialSlot", "dTrialStart")] + [("trace", CmpcWalkRefillTrace)]
 
 
+class CmpcWalkRefillTrials(C.Structure):
+    """mirror of cmpc_walk_refill_trials (include/cmpc.h): the per-trial models and plant mismatch of cmpc_rollout_walk_refill_trials_device; 56 bytes"""
+    _fields_ = [("dModels", C.c_void_p), ("dModelOk", C.c_void_p), ("dHiddenWrench", C.c_void_p), ("hidden_ticks", C.c_int), ("dStateNoise", C.c_void_p),
+                ("noise_ticks", C.c_int), ("dForceGain", C.c_void_p)]
+
+
 STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
 
 
@@ -214,6 +220,7 @@ EXPORTS = [
     "cmpc_plant_step_mismatch_device", "cmpc_rollout_tick_mismatch_device", "cmpc_rollout_walk_mismatch_device",
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
+    "cmpc_rollout_walk_refill_trials_device",
 ]
 
 _lib = None
@@ -375,6 +382,8 @@ def lib():
             L.cmpc_rollout_refill.argtypes = [i, i, wr, fl, vp]
             L.cmpc_rollout_refill_device.argtypes = [vp, i, wr, fl, vp, vp]
             L.cmpc_rollout_walk_refill_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, i, i, ip, vp]
+            if hasattr(L, "cmpc_rollout_walk_refill_trials_device"):
+                L.cmpc_rollout_walk_refill_trials_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), i, i, ip, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

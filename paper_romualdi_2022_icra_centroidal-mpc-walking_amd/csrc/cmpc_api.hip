@@ -67,11 +67,12 @@ extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const
                                            int* ok, int* land, const float* box, const float* state, float* P, const float* Xprev, float* X0,
                                            const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
                                            long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
-                                           int wrench_ticks, int trials, double plan_t_first, float g8, hipStream_t stream);
+                                           int wrench_ticks, int trials, double plan_t_first, float g8, const CmpcRefillTrialArgs* tr,
+                                           hipStream_t stream);
 extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
                                             const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                             const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
-                                            hipStream_t stream);
+                                            const int* trial, const CmpcRefillTrialArgs* tr, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
@@ -1800,10 +1801,22 @@ int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_rec
     return rollout_refill_impl(h, tick_next, rec, refill, dStateLive, stream ? (hipStream_t)stream : h->stream);
 }
 
-// the refill walk: per tick the refill launch, the tick's three launches (front and back kernels in refill mode, the warm solve with the per-problem cold
-// policy) and the record with local tick numbers
+static int ensure_models(cmpc_handle h);
+static_assert(sizeof(cmpc_walk_refill_trials) == 56, "cmpc_walk_refill_trials: the size include/cmpc.h states");
+
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
+{
+    return cmpc_rollout_walk_refill_trials_device(h, max_contacts, tick0, ticks, io, rec, refill, nullptr, row0, lists_in, lists_out, stream);
+}
+
+// the refill walk: per tick the refill launch, the tick's three launches (front and back kernels in refill mode, the warm solve with the per-problem cold
+// policy) and the record with local tick numbers.  trials (cmpc_walk_refill_trials) null, or with nothing set: the launches this function always queued;
+// else the front and back kernels' per-trial instantiations, each only when it has something to do, and the handle's per-problem table as the solve's and
+// the back kernel's records when there are per-trial models
+int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                           const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
+                                           void* stream)
 {
     // (the refusals that need no handle come first: they are the same with and without one)
     if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
@@ -1811,6 +1824,11 @@ int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, 
     if (max_contacts < 1 || max_contacts > 16)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: max_contacts must be 1 .. 16 (a slot's first tick uses the front kernel's LDS stage)");
     if (io->dWrenchTicks) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dWrenchTicks is not taken (the schedule is the per-trial dWrenchTrials)");
+    if (trials && (trials->hidden_ticks < 0 || trials->noise_ticks < 0))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: a negative count of schedule rows");
+    if (trials && ((trials->dHiddenWrench && trials->hidden_ticks == 0) || (trials->dStateNoise && trials->noise_ticks == 0)))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: a schedule with no rows");
+    if (trials && trials->dModelOk && !trials->dModels) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: dModelOk without dModels");
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
         !k.box_upper || !k.box_lower || !k.dState || !k.dStateOut || k.dState != k.dStateOut || !k.dPlanT || !k.dPlanPose || !k.dPlanN || !k.dOk || !k.dLand ||
@@ -1833,6 +1851,21 @@ int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, 
     int rc = upload_box(h, k.box_upper, k.box_lower, st);
     if (rc != CMPC_OK) return rc;
     if (rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
+    // the per-trial data as the kernels take it, or null.  With models the handle reads its per-problem table from here on (the launches below capture the
+    // table's address and the corner stride when they are queued); a slot's record is written by the front kernel of the slot's first tick, ahead of every
+    // launch that reads it, and a slot that never gets a trial stays behind the ended mask
+    CmpcRefillTrialArgs tr_args{};
+    const CmpcRefillTrialArgs* tr = nullptr;
+    if (trials && (trials->dModels || trials->dHiddenWrench || trials->dStateNoise || trials->dForceGain)) {
+        if (trials->dModels) {
+            rc = ensure_models(h);
+            if (rc != CMPC_OK) return rc;
+            h->models_set = true;
+        }
+        tr_args = CmpcRefillTrialArgs{trials->dModels, trials->dModelOk, h->dConsts, h->dExpK, h->dModels, trials->dHiddenWrench, trials->hidden_ticks,
+                                      trials->dStateNoise, trials->noise_ticks, trials->dForceGain, refill->trials};
+        tr = &tr_args;
+    }
     const bool timing = h->timing;   // (as cmpc_rollout_walk_device)
     const int* const ended_saved = h->dEnded;
     h->timing = false; h->timed = false;
@@ -1851,13 +1884,14 @@ int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, 
         int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
                                               set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,
                                               k.plan_knots, k.plan_dt, k.robot_mass, k.com_height, dt_ns, h->dEnded, refill->dStartTick, refill->dTrial, tick,
-                                              refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), st);
+                                              refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), tr,
+                                              st);
         if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (front) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
         rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, refill->dStartTick, tick);
         if (rc != CMPC_OK) break;
         lrc = cmpc_launch_tick_post_refill(B, N, max_contacts, h->cfg.sampling_time, (float)h->cfg.gravity, model_corners(h), corners_stride(h), k.dX, k.dP,
                                            k.dStateOut, k.dStateOut, k.dZmp, (float)k.plant_step, k.plant_substeps, (float)k.zmp_half_x, (float)k.zmp_half_y,
-                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, st);
+                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, refill->dTrial, tr, st);
         if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (back) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
         CmpcRecordArgs a;
         if (!h->box_set || !record_args(N, B, tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {

@@ -366,6 +366,27 @@ __host__ __device__ inline void cmpc_refill_assign(const CmpcRefillArgs& a, int 
     a.q_slot[q] = b; a.q_start[q] = a.tick_next;
 }
 
+// the per-trial data of a refill walk (include/cmpc.h, cmpc_walk_refill_trials) as the front and back kernels of a tick take it: the caller's arrays, each
+// null or indexed by trial (schedules [local tick][trial]), and for the models the handle's base record, its exp(-k) table and its per-problem table [B]
+struct CmpcRefillTrialArgs {
+    const cmpc_model* models; int* model_ok;                       // [Q]
+    const CmpcConsts* base; const double* expk; CmpcConsts* table; // read / written only with models
+    const float* hidden; int hidden_ticks;                         // [hidden_ticks][Q][6]
+    const float* noise; int noise_ticks;                           // [noise_ticks][Q][9]
+    const float* gain;                                             // [Q]
+    int Q;
+};
+// the model of trial q into a slot's record, which holds a bit copy of the base record: cmpc_models_kernel's statement (cmpc_api.hip), so that the record is
+// bit-equal to the one cmpc_set_models_device derives.  A row that breaks the model rule keeps the base model and is flagged.
+__host__ __device__ inline void cmpc_refill_trial_model(const CmpcRefillTrialArgs& a, int q, CmpcConsts& rec)
+{
+    const cmpc_model m = a.models[q];
+    const bool bad = cmpc_model_first_bad(m) >= 0;
+    if (!bad) cmpc_consts_apply_model(rec, m, a.expk);
+    rec.model_bad = bad ? 1 : 0;
+    if (a.model_ok) a.model_ok[q] = bad ? 0 : 1;
+}
+
 // the host form's two loops (cmpc_rollout_refill_init, cmpc_rollout_refill): the slots in ascending order, the counter a plain int.  Here, and not in
 // cmpc_api.hip, so that a stand-alone host program can run them under a sanitizer without the library.
 inline void cmpc_refill_init_host(const CmpcRefillArgs& a, int* next)

@@ -1140,7 +1140,9 @@ namespace {
 // MM (cmpc_plant_mismatch, include/cmpc.h): the plant is not the model -- hidden[B][6] (or null: the term is not added) is a wrench the plant feels and dP
 // does not hold, gain[B] (or null: 1, no multiply) scales every corner force the plant applies.  Both are loaded up front with the state, whatever the
 // contact flags turn out to be, for the reason given at the force load below.  MM = false is the function without either, instruction for instruction.
-template <bool MM>
+// PL (the refill walk's per-trial mismatch, cmpc_walk_refill_trials): hidden and gain are this LANE's own -- its trial's row [6] and its trial's word, or
+// null -- and not arrays over the batch; the arithmetic is the same statement for statement.
+template <bool MM, bool PL = false>
 __device__ inline void plant_step_problem(int N, int b, float grav, const float* __restrict__ corners, int corners_stride, const float* __restrict__ X,
                                           const float* __restrict__ P, const float* state_in, float* state_out, float* __restrict__ zmp, float h,
                                           int nsub, float zx, float zy, const float* __restrict__ hidden, const float* __restrict__ gain)
@@ -1152,8 +1154,8 @@ __device__ inline void plant_step_problem(int N, int b, float grav, const float*
     float hid[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gn = 1.f;
     if (MM) {
         if (hidden)
-            for (int i = 0; i < 6; ++i) hid[i] = hidden[(size_t)b * 6 + i];
-        if (gain) gn = gain[b];
+            for (int i = 0; i < 6; ++i) hid[i] = hidden[(PL ? (size_t)0 : (size_t)b * 6) + i];
+        if (gain) gn = gain[PL ? 0 : b];
     }
     for (int i = 0; i < 3; ++i) {
         com[i] = state_in[(size_t)b * 9 + i]; v[i] = state_in[(size_t)b * 9 + 3 + i]; hm[i] = state_in[(size_t)b * 9 + 6 + i];
@@ -1490,6 +1492,11 @@ __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float
 // is its own, now = (tick - start[b]) dt, its wrench row is row tick - start[b] of its trial, and with start[b] == tick this is the problem's FIRST tick -- no
 // merge, its lists are the planner's (staged in LDS, snapped there with forceSampleTime) and go out as a merge tick writes them, ok = the snap's status (1
 // without), and x0 is the cold start, written behind the barrier after the sampling.  false is the kernel without any of it.
+// TR (with RF; cmpc_rollout_walk_refill_trials_device): the per-trial data `tr` -- on its first tick the workgroup writes its slot's record of the handle's
+// per-problem table, the base record word for word and then, by one thread behind a barrier (taken by the whole workgroup: `fresh`, the trial and the
+// pointer are workgroup-uniform), trial q's model over it (cmpc_refill_trial_model: the statement of cmpc_set_models_device's kernel); the solve and the back
+// kernel of this tick are later launches on the stream.  The noise row is row [local tick][q] inside its range -- the same float32 add -- else the plain
+// copy.  false is the kernel without any of it: `tr` is not read.
 struct CmpcRefillTick {
     const int* start; const int* trial;     // [B]: the slots' start ticks and trials (cmpc_walk_refill)
     int tick;
@@ -1505,7 +1512,7 @@ __device__ inline void refill_local_time(int ticks, double dt, double t_first, d
     *now = t;
     *offset = t - t_first;
 }
-template <bool RF>
+template <bool RF, bool TR = false>
 __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose,
                                                             const int* plan_n, const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t,
                                                             float* list_pose, int* list_n, int* ok, int* land, const float* __restrict__ box,
@@ -1513,14 +1520,18 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
                                                             const float* __restrict__ Xprev, float* __restrict__ X0, const float* __restrict__ plan_com,
                                                             const float* __restrict__ plan_h, int plan_knots, double plan_dt, double plan_t_offset,
                                                             double robot_mass, double com_height, long long snap_dt_ns, const int* __restrict__ snap_ok,
-                                                            const int* __restrict__ ended, const float* __restrict__ noise, CmpcRefillTick rf)
+                                                            const int* __restrict__ ended, const float* __restrict__ noise, CmpcRefillTick rf,
+                                                            CmpcRefillTrialArgs tr)
 {
+    static_assert(RF || !TR, "the per-trial data belongs to a refill walk");
     const int b = blockIdx.x, tid = threadIdx.x;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device: the whole workgroup, ahead of its first barrier -- nothing of the problem is written)
     const CmpcIdx L{N};
     float* p = P + (size_t)b * L.np();
     bool fresh = false;                   // (RF: workgroup-uniform, from one scalar load)
     const float* wrench_b = nullptr;      // (RF: the wrench row of this slot's trial, [N][6])
+    const float* noise_q = nullptr;       // (TR: the noise row of this slot's trial at its local tick, [9])
+    int model_q = -1;                     // (TR: the trial whose model the slot takes on this tick, its first)
     if constexpr (RF) {
         const int local = rf.tick - rf.start[b], q = rf.trial[b];
         fresh = local == 0;
@@ -1528,6 +1539,10 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
         if (rf.wrench_trials && local >= 0 && local < rf.wrench_ticks && q >= 0 && q < rf.trials)
             wrench_b = rf.wrench_trials + ((size_t)local * rf.trials + q) * N * 6;
         if (fresh) merge = 0;
+        if constexpr (TR) {
+            if (tr.noise && local >= 0 && local < tr.noise_ticks && q >= 0 && q < tr.Q) noise_q = tr.noise + ((size_t)local * tr.Q + q) * 9;
+            if (tr.models && fresh && q >= 0 && q < tr.Q) model_q = q;
+        }
     }
     __shared__ int okw;
     __shared__ int foot_ok[2];   // forceSampleTime status of the two feet (1 when the flag is off)
@@ -1536,8 +1551,18 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
     __syncthreads();
     // setState and the warm-start shift first (they depend on nothing the kernel computes: their memory traffic runs under the merge of threads 0, 1)
     // (noise: this tick's row [B][9] of cmpc_plant_mismatch.dStateNoise or null -- the MPC measures state + noise, one float32 add; the plant keeps the state)
-    if (noise) for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e] + noise[9 * (size_t)b + e];
+    if (TR && noise_q) for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e] + noise_q[e];
+    else if (noise) for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e] + noise[9 * (size_t)b + e];
     else for (int e = tid; e < 9; e += 256) p[L.pCom0() + e] = state[9 * (size_t)b + e];
+    if constexpr (TR) {
+        if (model_q >= 0) {   // (uniform)
+            const int* src = reinterpret_cast<const int*>(tr.base);
+            int* dst = reinterpret_cast<int*>(tr.table + b);
+            for (int e = tid; e < (int)(sizeof(CmpcConsts) / 4); e += 256) dst[e] = src[e];
+            __syncthreads();   // (the copy is in the record before the model goes over it)
+            if (tid == 64) cmpc_refill_trial_model(tr, model_q, tr.table[b]);
+        }
+    }
     if constexpr (RF) {
         if (wrench_b)
             for (int e = tid; e < 3 * N; e += 256) {
@@ -1655,13 +1680,16 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
 // post: one thread per problem -- the plant step, then the step adjustment of its two feet (getOutput().contactPhaseList)
 // MM: the mismatched plant (this tick's hidden-wrench row and the force gain, plant_step_problem); false is the kernel without it
 // RF: the refill walk -- the step adjustment looks for the next contact at the problem's own time (tick - start[b]) dt
+// MM and RF (cmpc_rollout_walk_refill_trials_device): hidden [hidden_ticks][trials][6] and gain [trials] are per TRIAL -- the lane takes row [local
+// tick][trial[b]] inside the schedule's range, else none (the term is then not added: a select per lane, no add of zero), and its trial's gain
 template <bool MM, bool RF>
 __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
                                                              float* __restrict__ zmp, float h, int nsub, float zx, float zy, const int* __restrict__ land,
                                                              const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n,
                                                              const int* __restrict__ ended, const float* __restrict__ hidden,
-                                                             const float* __restrict__ gain, const int* __restrict__ start, int tick, double dt)
+                                                             const float* __restrict__ gain, const int* __restrict__ start, int tick, double dt,
+                                                             const int* __restrict__ trial, int hidden_ticks, int trials)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
@@ -1669,8 +1697,14 @@ __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M
     if constexpr (RF) {
         double unused;
         refill_local_time(tick - start[b], dt, 0.0, &now, &unused);
+        if constexpr (MM) {
+            const int local = tick - start[b], q = trial[b];
+            const bool known = q >= 0 && q < trials;
+            hidden = (hidden && known && local >= 0 && local < hidden_ticks) ? hidden + ((size_t)local * trials + q) * 6 : nullptr;
+            gain = (gain && known) ? gain + q : nullptr;
+        }
     }
-    plant_step_problem<MM>(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy, hidden, gain);
+    plant_step_problem<MM, MM && RF>(N, b, grav, corners, corners_stride, X, P, state_in, state_out, zmp, h, nsub, zx, zy, hidden, gain);
     const CmpcIdx L{N};
     for (int c = 0; c < 2; ++c) {
         const int e = 2 * b + c, lk = land[e];
@@ -1945,33 +1979,47 @@ extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, 
 {
     hipLaunchKernelGGL(cmpc_tick_pre_kernel<false>, dim3(B), dim3(256), 0, stream, B, N, M, dt, now, merge, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
                        list_t, list_pose, list_n, ok, land, box, state, wrench, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, plan_t_offset, robot_mass,
-                       com_height, snap_dt_ns, snap_ok, ended, noise, CmpcRefillTick{});
+                       com_height, snap_dt_ns, snap_ok, ended, noise, CmpcRefillTick{}, CmpcRefillTrialArgs{});
     return (int)hipGetLastError();
 }
 
 // the front and back kernels of a refill walk's tick (cmpc_rollout_walk_refill_device): a merge tick with M <= 16 in which every slot runs at its own time
+// tr (cmpc_rollout_walk_refill_trials_device; null: the launches of cmpc_rollout_walk_refill_device): the front kernel's per-trial instantiation when it
+// holds models or noise, the back kernel's when it holds a hidden wrench or a gain
 extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const double* plan_t, const float* plan_pose, const int* plan_n,
                                            const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n,
                                            int* ok, int* land, const float* box, const float* state, float* P, const float* Xprev, float* X0,
                                            const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
                                            long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
-                                           int wrench_ticks, int trials, double plan_t_first, float g8, hipStream_t stream)
+                                           int wrench_ticks, int trials, double plan_t_first, float g8, const CmpcRefillTrialArgs* tr,
+                                           hipStream_t stream)
 {
     if (M > 16) return (int)hipErrorInvalidValue;
     const CmpcRefillTick rf{start, trial, tick, wrench_trials, wrench_ticks, trials, plan_t_first, g8};
-    hipLaunchKernelGGL(cmpc_tick_pre_kernel<true>, dim3(B), dim3(256), 0, stream, B, N, M, dt, 0.0, 1, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
-                       list_t, list_pose, list_n, ok, land, box, state, (const float*)nullptr, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, 0.0,
-                       robot_mass, com_height, snap_dt_ns, (const int*)nullptr, ended, (const float*)nullptr, rf);
+    if (tr && (tr->models || tr->noise))
+        hipLaunchKernelGGL((cmpc_tick_pre_kernel<true, true>), dim3(B), dim3(256), 0, stream, B, N, M, dt, 0.0, 1, plan_t, plan_pose, plan_n, prev_t, prev_pose,
+                           prev_n, list_t, list_pose, list_n, ok, land, box, state, (const float*)nullptr, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt,
+                           0.0, robot_mass, com_height, snap_dt_ns, (const int*)nullptr, ended, (const float*)nullptr, rf, *tr);
+    else
+        hipLaunchKernelGGL((cmpc_tick_pre_kernel<true>), dim3(B), dim3(256), 0, stream, B, N, M, dt, 0.0, 1, plan_t, plan_pose, plan_n, prev_t, prev_pose, prev_n,
+                           list_t, list_pose, list_n, ok, land, box, state, (const float*)nullptr, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt, 0.0,
+                           robot_mass, com_height, snap_dt_ns, (const int*)nullptr, ended, (const float*)nullptr, rf, CmpcRefillTrialArgs{});
     return (int)hipGetLastError();
 }
 
 extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
                                             const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                             const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
-                                            hipStream_t stream)
+                                            const int* trial, const CmpcRefillTrialArgs* tr, hipStream_t stream)
 {
-    hipLaunchKernelGGL((cmpc_tick_post_kernel<false, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX, dP,
-                       dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, (const float*)nullptr, (const float*)nullptr, start, tick, dt);
+    if (tr && (tr->hidden || tr->gain))
+        hipLaunchKernelGGL((cmpc_tick_post_kernel<true, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX,
+                           dP, dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, tr->hidden, tr->gain, start, tick, dt, trial,
+                           tr->hidden_ticks, tr->Q);
+    else
+        hipLaunchKernelGGL((cmpc_tick_post_kernel<false, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX,
+                           dP, dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, (const float*)nullptr, (const float*)nullptr, start, tick,
+                           dt, (const int*)nullptr, 0, 0);
     return (int)hipGetLastError();
 }
 
@@ -1981,10 +2029,10 @@ extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav
 {
     if (hidden || gain)
         hipLaunchKernelGGL((cmpc_tick_post_kernel<true, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
-                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0);
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0);
     else
         hipLaunchKernelGGL((cmpc_tick_post_kernel<false, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
-                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0);
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0);
     return (int)hipGetLastError();
 }
 

@@ -196,9 +196,10 @@ class WalkingRollout:
         slot, start [Q, ..] (-1: never started), and trials["trace"](q) -> trial q's trace rows com, zmp, land, landing_offset, iterations, code
         [trial_ticks, ..] gathered out of the slot-major trace by one index_select each on the device, with valid [trial_ticks] bool (rows at or past
         trials["ticks"][q] are not the trial's).
-        Out of scope: gradients and forward mode through a refill walk, per-trial models (a model belongs to a slot), and -- NotImplementedError, raised
-        before anything touches a GPU -- replan, a plant mismatch (hidden pushes or noise per trial), taped=True, every (snapshots and checkpoints), and
-        lists longer than 16 contacts."""
+        Per-trial models and a per-trial plant mismatch (hidden pushes, noise, a force gain): walk_device_refill_trials(), a method of its own because this
+        signature is pinned; here the models are the slot's and mismatch= is refused.
+        Out of scope: gradients and forward mode through a refill walk, and -- NotImplementedError, raised before anything touches a GPU -- replan,
+        mismatch= (see above), taped=True, every (snapshots and checkpoints), and lists longer than 16 contacts."""
         for name, value in (("replan", replan), ("mismatch", mismatch), ("taped", taped or None), ("every", every)):
             if value is not None:
                 raise NotImplementedError(f"walk_device_refill: {name} is out of scope of a refill walk")
@@ -210,7 +211,59 @@ class WalkingRollout:
         assert ticks >= 1 and trial_ticks >= 1
         return self._queued(lambda: self._walk_refill(ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop))
 
-    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop):
+    def walk_device_refill_trials(self, ticks, trial_ticks, com0, dcom0, h0, models=None, mismatch=None, **kwargs):
+        """walk_device_refill(ticks, trial_ticks, com0, dcom0, h0, **kwargs) with what a Monte-Carlo study randomises per TRIAL
+        (cmpc_rollout_walk_refill_trials_device, include/cmpc.h; DESIGN.md 7f "Refill"): the robot and the disturbance.  kwargs: walk_device_refill's push,
+        push_ticks, wrench_trials, trace and stop.
+        models [Q, 34] float64, the rows of config.model_array (numpy or CUDA): trial q walks with model q -- the slot's record of the solver's per-problem
+        table is rewritten on the device at the trial's first tick, bit-equal to what set_models_device would derive; a row that breaks the model rule ends
+        its trial at local tick 0 with the solver's code (trials["model_ok"][q] = 0) and the slot goes to the next trial.
+        mismatch = dict(hidden_wrench=[Th, Q, 6], state_noise=[Tn, Q, 9], force_gain=[Q]), any subset, float32: walk_device_mismatch's three parts with
+        row = the trial's LOCAL tick and column = the trial; outside a schedule's rows the term is not applied.  A tick_first other than 0: ValueError.
+        Still five launches per tick and no host read.  A trial's bits are those of walk_device_mismatch(trial_ticks, ..., tick_first=0) on a roll-out of
+        the same batch size, factor storage and options that holds it in the same slot with models row `slot` = the trial's model and the schedules'
+        column `slot` = the trial's rows.
+        -> walk_device_refill's dict, plus trials["model_ok"] [Q] int32: 1 / 0 once the trial has started, -1 for a trial never started (and for every
+        trial when models is None).  With models=None and nothing in mismatch: walk_device_refill, bit for bit.
+        Afterwards the roll-out's own models are back (self.models through set_models_device, or none): a later walk_device on this object is bit-equal
+        to one made before the call.  Out of scope, as for walk_device_refill: gradients, tapes, forward mode, snapshots, replan, lists longer than 16
+        contacts (NotImplementedError)."""
+        mismatch = dict(mismatch or {})
+        if int(mismatch.pop("tick_first", 0)) != 0:
+            raise ValueError("walk_device_refill_trials: the schedules' rows are the trial's local ticks, so tick_first must be 0")
+        for given, known in ((kwargs, ("push", "push_ticks", "wrench_trials", "trace", "stop")), (mismatch, ("hidden_wrench", "state_noise", "force_gain"))):
+            for k in given:
+                if k not in known:
+                    raise TypeError(f"walk_device_refill_trials: unexpected argument {k!r}")
+        if self.M > 16:
+            raise NotImplementedError("walk_device_refill_trials: lists longer than 16 contacts are out of scope (a slot's first tick uses the front kernel's "
+                                      "LDS stage; with force_sample_time the snap runs there too)")
+        args = dict(push=None, push_ticks=0, wrench_trials=None, trace=True, stop=("merge", "solver", "nonfinite"))
+        args.update(kwargs)
+        if args["push"] is not None and args["wrench_trials"] is not None:
+            raise ValueError("walk_device_refill_trials: push or wrench_trials, not both")
+        assert ticks >= 1 and trial_ticks >= 1
+
+        def walk():
+            torch, s = self.torch, self.solver
+            data = s.walk_refill_trials(models=models, device=self.dev, **mismatch)
+            given = any(data[k] is not None for k in ("models", "hidden_wrench", "state_noise", "force_gain"))
+            try:
+                rec = self._walk_refill(ticks, trial_ticks, com0, dcom0, h0, args["push"], args["push_ticks"], args["wrench_trials"], args["trace"],
+                                        args["stop"], trials=data if given else None)
+            finally:
+                if data["models"] is not None:    # (the table holds each slot's last trial's model: back to the roll-out's own, in stream order)
+                    if self.models is not None:
+                        s.set_models_device(self.models)
+                    else:
+                        s.set_models(None)
+            Q = int(rec["trials"]["slot"].shape[0])
+            ok = data["model_ok"]
+            rec["trials"]["model_ok"] = ok if ok is not None else torch.full((Q,), -1, dtype=torch.int32, device=self.dev)
+            return rec
+        return self._queued(walk)
+
+    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
@@ -240,7 +293,8 @@ class WalkingRollout:
         # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
         sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
         cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
-                                           step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time)
+                                           step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
+                                           trials=trials)
         s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
         del rec["_c"]
         trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
@@ -255,7 +309,7 @@ class WalkingRollout:
                 out["valid"] = ar < trials["ticks"][q]
                 return out
             trials["trace"] = trial_trace
-        self._walk_refill_keep = (fill, refs, wrench_trials)    # (the queued launches read these)
+        self._walk_refill_keep = (fill, refs, wrench_trials, trials)    # (the queued launches read these)
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state, trial_of=fill["trial_of"], trials=trials)
         return rec
 

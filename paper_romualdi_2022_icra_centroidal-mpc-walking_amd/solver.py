@@ -1273,11 +1273,46 @@ class BatchSolver:
         self._launch(dev, lambda st: self._lib.cmpc_rollout_refill_device(self._h, int(tick_next), C.byref(rec["_c"]), C.byref(refill["_c"]),
                                                                           dStateLive.data_ptr() if dStateLive is not None else None, st))
 
+    def walk_refill_trials(self, models=None, hidden_wrench=None, state_noise=None, force_gain=None, device=None):
+        """A cmpc_walk_refill_trials as a dict: the per-TRIAL data of a refill walk over a queue of Q trials -- models [Q, 34] float64 (cmpc_model's order,
+        config.model_array's rows), hidden_wrench [Th, Q, 6], state_noise [Tn, Q, 9], force_gain [Q] float32 (numpy or CUDA tensors, any subset; a schedule
+        of zero rows counts as absent; the schedules' rows are the trial's LOCAL ticks).  With models the dict holds model_ok [Q] int32, -1 until the trial's
+        first tick writes 1 or 0.  The dict keeps the device tensors alive and holds "_c", the C struct that points at them."""
+        import torch
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_trials_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_trials_device")
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        hold = []
+
+        def up(a, dtype, tail, name):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
+                hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float64 if dtype == torch.float64 else np.float32)))
+                a = hold[-1].to(dev, non_blocking=True)
+            t = a.detach().to(dev, dtype).contiguous()
+            assert t.dim() == len(tail) and all(w is None or int(t.shape[i]) == w for i, w in enumerate(tail)), f"{name}: expected {list(tail)}"
+            return t if t.numel() > 0 else None
+        r = dict(models=up(models, torch.float64, (None, _capi.MODEL_DOUBLES), "models"), hidden_wrench=up(hidden_wrench, torch.float32, (None, None, 6), "hidden_wrench"),
+                 state_noise=up(state_noise, torch.float32, (None, None, 9), "state_noise"), force_gain=up(force_gain, torch.float32, (None,), "force_gain"))
+        counts = {int(t.shape[0 if k in ("models", "force_gain") else 1]) for k, t in r.items() if t is not None}
+        assert len(counts) <= 1, f"walk_refill_trials: the arrays disagree on the number of trials {sorted(counts)}"
+        r["trials"] = counts.pop() if counts else None
+        r["model_ok"] = torch.full((r["trials"],), -1, dtype=torch.int32, device=dev) if r["models"] is not None else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rows = lambda t: 0 if t is None else int(t.shape[0])
+        r["_host"] = hold
+        r["_c"] = _capi.CmpcWalkRefillTrials(ptr(r["models"]), ptr(r["model_ok"]), ptr(r["hidden_wrench"]), rows(r["hidden_wrench"]), ptr(r["state_noise"]),
+                                             rows(r["state_noise"]), ptr(r["force_gain"]))
+        return r
+
     def rollout_walk_refill_device(self, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0=0,
-                                   step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False):
+                                   step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False, trials=None):
         """cmpc_rollout_walk_refill_device: `ticks` ticks of a refill walk from tick number tick0 in one call -- per tick the refill launch, the tick's three
         launches and the record -- in place on dState; the other arguments as rollout_walk_device's (no cold_first, wrench_ticks, tape or mismatch: a slot's
-        first tick runs inside the merge launches, and the wrench schedule is refill's per-trial one).  Returns the set that holds the last tick's lists."""
+        first tick runs inside the merge launches, and the wrench schedule is refill's per-trial one).  Returns the set that holds the last tick's lists.
+        trials (walk_refill_trials(...)): cmpc_rollout_walk_refill_trials_device -- per-trial models and a per-trial plant mismatch; with models the handle
+        is left on its per-problem table, which then holds each slot's last trial's model (set_models[_device] afterwards to go on with one's own)."""
         self._need_refill()
         io = _capi.CmpcWalkIO()
         io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
@@ -1285,6 +1320,12 @@ class BatchSolver:
         io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
         io.plan_t_first = float(planner[3]) if planner is not None else 0.0
         out = C.c_int(-1)
+        if trials is not None:
+            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
+            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_trials_device(
+                self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), C.byref(trials["_c"]), int(row0),
+                int(lists_in), C.byref(out), st))
+            return out.value
         self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_device(
             self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), int(row0), int(lists_in),
             C.byref(out), st))

@@ -9,8 +9,11 @@ time, and how many of its ticks held at least one fresh (cold) solve.  No pass m
 a cold solve takes more iterations than a warm one, so refills spread over the ticks may cost much of what they save.
 With --baseline LIB (another build of the library in the package directory, e.g. the parent commit's), first, in child processes started before this one
 touches the GPU: the headline solve of bench.py through tools/ab_multi.sh, and the 24-tick walk_device at B = 256 (--walk-only children, the builds
-alternating), this build / LIB for both.  Writes its lines to --out (default profiles/r12_walk_refill.txt) as well."""
-import argparse, os, subprocess, sys, time
+alternating), this build / LIB for both; and, with --refill-ab, the refill study itself at B = 256 in --refill-only children, the builds alternating.
+With --trials, after the study: the same queue once more through walk_device_refill_trials with a model per trial (friction and foot size) and all three
+parts of the plant mismatch on every local tick (hidden pushes, noise, a gain per trial), alternating with the walk_device_refill above, per trial-tick
+actually run (a mismatch ends some more trials early).  Writes its lines to --out (default profiles/r12_walk_refill.txt) as well."""
+import argparse, dataclasses, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -24,6 +27,9 @@ ap.add_argument("--fall", type=float, default=0.25, help="the fraction of the tr
 ap.add_argument("--append", action="store_true", help="add the lines to --out instead of replacing it")
 ap.add_argument("--large", action="store_true", help="the study at B = 1024 as well")
 ap.add_argument("--walk-only", action="store_true", help="print the median ms per tick of the 24-tick walk_device at B = 256 and leave")
+ap.add_argument("--refill-only", action="store_true", help="print the median ms of the refill study at B = 256 (no per-trial data) and leave")
+ap.add_argument("--refill-ab", action="store_true", help="with --baseline: the refill study in child processes, this build / LIB")
+ap.add_argument("--trials", action="store_true", help="the study once more with per-trial models and the full per-trial mismatch")
 args = ap.parse_args()
 TT, lines = 24, []
 
@@ -43,7 +49,7 @@ def start(n, seed=5):
     return com0, dcom0, h0, push
 
 
-ab = walk_ab = None
+ab = walk_ab = refill_ab = None
 if args.baseline:
     libs = [args.baseline, "libcmpc_hip.so"]
     out = subprocess.run(["bash", os.path.join(ROOT, "tools", "ab_multi.sh"), "config2", str(args.ab_reps)] + libs, cwd=ROOT, capture_output=True, text=True,
@@ -61,6 +67,14 @@ if args.baseline:
                                timeout=120)      # (a child takes about 10 s)
             assert r.returncode == 0, r.stderr[-2000:]
             walk_ab[lib].append(float(r.stdout.split()[-1]))
+    if args.refill_ab:
+        refill_ab = {lib: [] for lib in libs}
+        for _ in range(args.ab_reps):
+            for lib in libs:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--refill-only"], cwd=ROOT, capture_output=True, text=True,
+                                   env=dict(os.environ, CMPC_LIB=lib), timeout=180)
+                assert r.returncode == 0, r.stderr[-2000:]
+                refill_ab[lib].append(float(r.stdout.split()[-1]))
 
 import torch
 import cmpc_amd as cm
@@ -135,6 +149,21 @@ def ticks_needed(B, Q, ends):
         t += 1
 
 
+def trial_data(Q, seed=11):
+    """a model per trial (friction 0.3 .. 0.75, foot scale 0.85 .. 1.15, periods 7 and 5) and the three mismatch parts on every local tick: pushes of about
+    0.3 m/s^2 and 0.05 N m / kg, a centimetre-scale estimator error, gains in [0.9, 1.1] (tests/test_gpu_mismatch.py's magnitudes)"""
+    rows = []
+    for q in range(7 * 5):
+        s = 0.85 + 0.075 * (q % 5)
+        contacts = [dataclasses.replace(c, corners=[tuple(s * v for v in cn) for cn in c.corners]) for c in cfg.contacts]
+        rows.append(dataclasses.replace(cfg, static_friction_coefficient=0.3 + 0.075 * (q % 7), contacts=contacts))
+    models = np.ascontiguousarray(cm.config.model_array(rows)[np.arange(Q) % 35])
+    rng = np.random.default_rng(seed)
+    hidden = np.concatenate([rng.normal(0, 0.3, (TT, Q, 3)), rng.normal(0, 0.05, (TT, Q, 3))], -1).astype(np.float32)
+    noise = np.concatenate([rng.normal(0, 3e-3, (TT, Q, 3)), rng.normal(0, 1e-2, (TT, Q, 3)), rng.normal(0, 2e-3, (TT, Q, 3))], -1).astype(np.float32)
+    return models, dict(hidden_wrench=hidden, state_noise=noise, force_gain=rng.uniform(0.9, 1.1, Q).astype(np.float32))
+
+
 say(f"refill of ended slots from a queue of trials: N = {N}, trials of {TT} ticks, Q = 4 B, {args.fall:g} of the trials end at a uniform local tick; plain = Q / B "
     f"walks with the ended problems out of the launches, refill = one walk_device_refill; the two alternate, median of {args.repeats}; "
     f"{torch.cuda.get_device_name(0)}")
@@ -156,6 +185,10 @@ for B in (256, 1024) if args.large else (256,):
     dstate0 = torch.from_numpy(np.concatenate([com0, dcom0, h0], 1)).to(ro.dev)
     plain = lambda: plain_walks(ro, B, dstate0, dwrench)
     refill = lambda: ro.walk_device_refill(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], wrench_trials=dwrench)
+    if args.refill_only:
+        refill()
+        print("refill study ms", timed(refill, 5)[0])
+        sys.exit(0)
     plain(); refill()       # warm-up (module load, allocator)
     ms = {"plain": [], "refill": []}
     for _ in range(args.repeats):
@@ -173,6 +206,36 @@ for B in (256, 1024) if args.large else (256,):
         f"({fresh_seen} of them with at least one fresh solve; the host rule said {fresh_ticks}); end ticks agree and every trial ran: {same}")
     say(f"B = {B}: plain {mp:.2f} ms ({fmt(ms['plain'])}) = {mp * 1e3 / run_ticks:.3f} us per trial-tick, {mp / (Q // B * TT):.4f} ms per tick | refill {mr:.2f} ms "
         f"({fmt(ms['refill'])}) = {mr * 1e3 / run_ticks:.3f} us per trial-tick, {mr / T:.4f} ms per tick | refill / plain = {mr / mp:.4f}")
+    if args.trials:
+        models, mm = trial_data(Q)
+        same_model = np.repeat(cm.config.model_array([cfg]), Q, 0)
+        no_mm = dict(hidden_wrench=np.zeros_like(mm["hidden_wrench"]), state_noise=np.zeros_like(mm["state_noise"]), force_gain=np.ones(Q, np.float32))
+        cu = lambda d: {k: torch.from_numpy(v).to(ro.dev) for k, v in d.items()}
+        # identity: the configuration's own model for every trial, zero pushes and noise, gain 1 -- the problems of the study, through the per-trial kernels
+        variants = {"identity": (torch.from_numpy(same_model).to(ro.dev), cu(no_mm)), "models": (torch.from_numpy(models).to(ro.dev), None),
+                    "mismatch": (None, cu(mm)), "both": (torch.from_numpy(models).to(ro.dev), cu(mm))}
+        run = lambda v: ro.walk_device_refill_trials(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], models=variants[v][0], mismatch=variants[v][1],
+                                                     wrench_trials=dwrench)
+        for v in variants:
+            run(v)
+        ms2, last = {v: [] for v in ["none"] + list(variants)}, {}
+        for _ in range(args.repeats):
+            m, _, last["none"] = timed(refill, 1)
+            ms2["none"].append(m)
+            for v in variants:
+                m, _, last[v] = timed(lambda: run(v), 1)
+                ms2[v].append(m)
+        m0 = float(np.median(ms2["none"]))
+        say(f"B = {B}, per-trial data (walk_device_refill_trials, the same queue and the same {T} ticks; the five walks alternate, median of {args.repeats}); "
+            f"identity = the configuration's model for every trial, zero pushes and noise, gain 1; models = friction 0.3 .. 0.75 and foot scale 0.85 .. 1.15; "
+            f"mismatch = pushes, noise and gains in [0.9, 1.1] on every local tick; max-sum = the sum over the ticks of the largest iteration count in the tick")
+        for v in ms2:
+            t2 = {k: x.cpu().numpy() for k, x in last[v]["trials"].items() if hasattr(x, "cpu")}
+            ran, med = int(t2["ticks"].sum()), float(np.median(ms2[v]))
+            ok = "" if v in ("none", "mismatch") else f", model_ok all 1 {bool((t2['model_ok'] == 1).all())}"
+            say(f"B = {B}, {v}: {med:.2f} ms ({fmt(ms2[v])}) = {med * 1e3 / max(ran, 1):.3f} us per trial-tick, {med / T:.4f} ms per tick, / none = {med / m0:.4f} | "
+                f"every trial started {bool((t2['start'] >= 0).all())}{ok}, {int((t2['end_tick'] >= 0).sum())} trials end early, {ran} trial-ticks run, "
+                f"{int(t2['iterations_sum'].sum()) / max(ran, 1):.2f} iterations per trial-tick, max-sum {int(last[v]['stats'][:, 3].sum().item())}")
 if ab:
     a, b = ab[args.baseline], ab["libcmpc_hip.so"]
     say(f"headline solve (bench.py config2 through tools/ab_multi.sh, {args.ab_reps} rounds), ms per step: {args.baseline} {np.median(a):.4f} ({fmt(a)}) | "
@@ -180,5 +243,9 @@ if ab:
     a, b = walk_ab[args.baseline], walk_ab["libcmpc_hip.so"]
     say(f"walk_device, B = 256, {TT} ticks, ms per tick (median of 5 in a child process, {args.ab_reps} children per build, alternating): {args.baseline} "
         f"{np.median(a):.4f} ({fmt(a)}) | this build {np.median(b):.4f} ({fmt(b)}) | this build / baseline = {np.median(b) / np.median(a):.4f}")
+if refill_ab:
+    a, b = refill_ab[args.baseline], refill_ab["libcmpc_hip.so"]
+    say(f"refill study, B = 256, no per-trial data, ms per walk (median of 5 in a child process, {args.ab_reps} children per build, alternating): "
+        f"{args.baseline} {np.median(a):.2f} ({fmt(a)}) | this build {np.median(b):.2f} ({fmt(b)}) | this build / baseline = {np.median(b) / np.median(a):.4f}")
 with open(args.out, "a" if args.append else "w") as f:
     f.write("\n".join(lines) + "\n")
