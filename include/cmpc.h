@@ -803,7 +803,8 @@ int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, c
  * CMPC_ERR_ARG before anything is queued: max_contacts > 16 (the first tick uses the front kernel's LDS stage), io->dWrenchTicks set (the schedule is the
  * per-trial one), rec NULL or with too few rows, io->tick.dState != io->tick.dStateOut, no dOk, and what cmpc_rollout_walk_device and
  * cmpc_rollout_refill_device refuse.  Tapes, gradients and forward mode are out of scope: no entry point takes a refill together with them; per-trial
- * models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL. */
+ * models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL; trials that
+ * start from a snapshot of a walk in progress instead of standing are cmpc_rollout_walk_refill_snapshot_device's (behind the snapshot section). */
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream);
 /* Per-trial data of a refill walk; every array is a device array indexed by TRIAL q (0 <= q < refill->trials), schedules by the trial's LOCAL tick r.
@@ -1074,6 +1075,54 @@ int cmpc_rollout_snapshot(int horizon, int batch, int src_batch, int max_contact
                           const int* index, int* ok);
 /* bytes per problem of a snapshot with all its arrays (the formula above); 0 for horizon < 1 or max_contacts < 1 */
 size_t cmpc_walk_snapshot_bytes(int horizon, int max_contacts);
+/* Trials that start from a snapshot of a walk in progress (DESIGN.md 7f "Refill", "Trials from a snapshot"): every trial of the queue is a fork of one row
+ * of a POOL of saved problems (cmpc_walk_snapshot arrays of pool_batch problems, filled by cmpc_rollout_snapshot_device) and walks trial_ticks RESUMED
+ * ticks from the pool's tick t_s = pool->tick.  sizeof == 32 (LP64; the ctypes mirror is held to it). */
+typedef struct cmpc_walk_refill_snapshot {
+    const cmpc_walk_snapshot* pool;   /* device arrays of pool_batch problems; pool->tick = t_s >= 1, pool->lists_in as saved */
+    int pool_batch;
+    const int* dTrialSnapshot;        /* [Q] device: the pool row trial q starts from; repeats are the normal case */
+    int* dTrialSnapshotOk;            /* [Q] device or NULL: 1 / 0 written when the trial is spawned, untouched for a trial never started */
+} cmpc_walk_refill_snapshot;
+/* cmpc_rollout_walk_refill_trials_device with trials that start mid-walk.  from == NULL: that call, bit for bit.  Otherwise, with t_s = from->pool->tick:
+ *   - Who gets which slot does not change: the refill launch, its free rule, dStartTick (the spawn tick s), dTrialTicks, dTrialSlot, dTrialStart and
+ *     trial_ticks (now the RESUMED ticks of a trial) keep their meaning.
+ *   - A tick is SIX launches: the restore launch goes between the refill launch and the front kernel, one workgroup per slot.  A workgroup whose slot
+ *     was not spawned this tick returns after one scalar load (dStartTick[b] != tick; an empty slot whose word happens to match, after a second: no
+ *     trial in it).  The gate is workgroup-uniform and comes ahead of everything.  A spawned slot with trial q receives the bit
+ *     copy of pool row dTrialSnapshot[q] into the live buffers, through cmpc_rollout_snapshot_device's row copy: state (into io->tick.dStateOut), dP, dX,
+ *     dOk, dLand; dX0, dInfo and dZmp where both sides have them; the six outcome arrays into rec, over the refill launch's fresh outcome; and both list
+ *     sets -- the pool's set pool->lists_in goes to the set THIS tick reads as "previous", the pool's other set to the other live set (the live parity
+ *     alternates with the walk tick, the pool's is fixed).  dTrialSnapshotOk[q] = 1.
+ *   - An index outside [0, pool_batch): nothing is copied, dTrialSnapshotOk[q] = 0, the slot's dEndTick = t_s and dEndCode = 0: the slot is behind the
+ *     ended mask for this tick's other launches and is archived and freed by the next refill.
+ *   - A pool row that had already ended: its outcome is restored with it, so the trial is ended at spawn the same way, with that row's outcome.
+ *   - Time: a slot spawned at s runs tick t at local tick t_s + (t - s); the integer sum is converted once, now = (double)(t_s + t - s) * sampling_time
+ *     -- the double cmpc_rollout_walk_device uses for that tick -- in the front kernel, the back kernel and the planner offset.  The outcome's tick
+ *     numbers are whole-walk numbers, t_s + (t - s).
+ *   - No cold first tick: the spawn tick is an ordinary warm merge tick on the restored lists and the restored dX (no planner lists as the slot's own, no
+ *     cold dX0, no cold policy in the solve: every problem of every solve is warm).
+ *   - Everything the trial owns is indexed by r = t - s, the ticks since spawn: dWrenchTrials, the three schedules of cmpc_walk_refill_trials, and the
+ *     per-trial model write at r == 0 -- cmpc_rollout_walk_mismatch_device's rows with tick_first = t_s.
+ *   - refill->dState0 does not reach a spawned trial (the refill launch, unchanged, still copies it into the state and the final state, and the restore
+ *     overwrites both; a trial whose index lies outside the pool keeps it as its final state).  The pool's own wrench schedule is not continued: the
+ *     restored wrench rows of dP stay until a dWrenchTrials row overwrites them.
+ * A trial's outcome, its trace rows, and the dX, dP, state and in-use list entries of each slot's last trial are those of
+ * cmpc_rollout_walk_mismatch_device(cold_first = 0, tick0 = t_s) run after a cmpc_rollout_snapshot_device restore of the same pool row, on a handle of the
+ * same batch size, factor storage and options that holds the trial in the same slot, with cmpc_set_models_device's row `slot` the trial's model and the
+ * schedules' column `slot` the trial's rows.
+ * CMPC_ERR_ARG before anything is queued: everything cmpc_rollout_walk_refill_trials_device refuses, in its order (max_contacts > 16 stays refused); and
+ * with from != NULL: pool NULL, pool->tick < 1, pool_batch < 1, a required pool array NULL (every array but dX0, dInfo, dZmp), pool->lists_in not 0 or 1,
+ * dTrialSnapshot NULL with refill->trials > 0, a pool array that is also a live array.  The refusals that need no handle come ahead of the handle check. */
+int cmpc_rollout_walk_refill_snapshot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from,
+                                             int row0, int lists_in, int* lists_out, void* stream);
+/* The restore launch of tick `tick` on the host: host buffers throughout; no handle, no GPU.  Bit-equal to the kernel.  live: the walk's live buffers
+ * described as a snapshot -- dState the state buffer the walk runs in place on, the outcome arrays the record's, live->lists_in the set this tick reads as
+ * "previous"; live->tick is not read.  Of refill only trials, dStartTick and dTrial are read.  CMPC_ERR_ARG: the new refusals above, a NULL live or refill
+ * or a NULL required array in them, horizon, batch or max_contacts < 1, tick < 0, trials < 0, live->lists_in not 0 or 1. */
+int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* refill,
+                                const cmpc_walk_refill_snapshot* from);
 /* The reverse walk: `ticks` calls of cmpc_rollout_tick_vjp_device (called, not copied: its workspace, statuses and zero rule for flagged problems hold),
  * last row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of cmpc_walk_vjp_gate_kernel).  Tick number tick0 + i is row
  * row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time.

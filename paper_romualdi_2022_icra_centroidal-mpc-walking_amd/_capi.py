@@ -81,6 +81,12 @@ class CmpcWalkRefillTrials(C.Structure):
                 ("noise_ticks", C.c_int), ("dForceGain", C.c_void_p)]
 
 
+class CmpcWalkRefillSnapshot(C.Structure):
+    """mirror of cmpc_walk_refill_snapshot (include/cmpc.h): the pool of saved problems the trials of cmpc_rollout_walk_refill_snapshot_device start from;
+    32 bytes.  (CmpcWalkSnapshot is defined below: the pool is held as a plain address.)"""
+    _fields_ = [("pool", C.c_void_p), ("pool_batch", C.c_int), ("dTrialSnapshot", C.c_void_p), ("dTrialSnapshotOk", C.c_void_p)]
+
+
 STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
 
 
@@ -220,7 +226,7 @@ EXPORTS = [
     "cmpc_plant_step_mismatch_device", "cmpc_rollout_tick_mismatch_device", "cmpc_rollout_walk_mismatch_device",
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
-    "cmpc_rollout_walk_refill_trials_device",
+    "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
 ]
 
 _lib = None
@@ -384,6 +390,10 @@ def lib():
             L.cmpc_rollout_walk_refill_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, i, i, ip, vp]
             if hasattr(L, "cmpc_rollout_walk_refill_trials_device"):
                 L.cmpc_rollout_walk_refill_trials_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), i, i, ip, vp]
+            if hasattr(L, "cmpc_rollout_walk_refill_snapshot_device"):
+                fs = C.POINTER(CmpcWalkRefillSnapshot)
+                L.cmpc_rollout_walk_refill_snapshot_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), fs, i, i, ip, vp]
+                L.cmpc_rollout_refill_restore.argtypes = [i, i, i, i, C.POINTER(CmpcWalkSnapshot), fl, fs]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

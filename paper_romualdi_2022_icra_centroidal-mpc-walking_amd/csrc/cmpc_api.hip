@@ -68,11 +68,12 @@ extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const
                                            const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
                                            long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
                                            int wrench_ticks, int trials, double plan_t_first, float g8, const CmpcRefillTrialArgs* tr,
-                                           hipStream_t stream);
+                                           int offset, hipStream_t stream);
 extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
                                             const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                             const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
-                                            const int* trial, const CmpcRefillTrialArgs* tr, hipStream_t stream);
+                                            const int* trial, const CmpcRefillTrialArgs* tr, int offset, hipStream_t stream);
+extern "C" int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
 extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
@@ -1803,6 +1804,85 @@ int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_rec
 
 static int ensure_models(cmpc_handle h);
 static_assert(sizeof(cmpc_walk_refill_trials) == 56, "cmpc_walk_refill_trials: the size include/cmpc.h states");
+static_assert(sizeof(cmpc_walk_refill_snapshot) == 32, "cmpc_walk_refill_snapshot: the size include/cmpc.h states");
+
+// ---- trials from a snapshot (include/cmpc.h, cmpc_walk_refill_snapshot): the restore step between the refill launch and the front kernel ----
+static bool snapshot_args(int N, int B, int src_B, int M, const cmpc_walk_snapshot* s, const cmpc_walk_snapshot* d, const int* index, int* ok, CmpcSnapshotArgs& a);
+// the 20 arrays of a cmpc_walk_snapshot in the struct's order
+static void snapshot_pointers(const cmpc_walk_snapshot& s, const void* out[CMPC_SNAP_ARRAYS])
+{
+    const void* const p[CMPC_SNAP_ARRAYS] = {s.dState, s.dP, s.dX, s.dX0, s.dInfo, s.dZmp, s.dOk, s.dLand, s.dListT, s.dListPose, s.dListN, s.dListTB, s.dListPoseB,
+                                             s.dListNB, s.dEndTick, s.dEndCode, s.dIterationsSum, s.dIterationsMax, s.dFinalState, s.dBoxSlackMin};
+    for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i) out[i] = p[i];
+}
+// the live buffers of a walk described as a snapshot: the state buffer the walk runs in place on, the record's outcome; prev: the set this tick reads
+static cmpc_walk_snapshot walk_live_view(const cmpc_walk_io* io, const cmpc_walk_record* rec, int prev)
+{
+    const cmpc_tick_io& k = io->tick;
+    return cmpc_walk_snapshot{0, prev, k.dStateOut, k.dP, k.dX, k.dX0, k.dInfo, k.dZmp, k.dOk, k.dLand, k.dListT, k.dListPose, k.dListN, io->dListTB,
+                              io->dListPoseB, io->dListNB, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
+                              rec->dBoxSlackMin};
+}
+// what is refused of `from` without a handle, in the header's order; null: nothing.  live (or null: not compared): the arrays a pool array must not be
+static const char* restore_refusal(const cmpc_walk_refill_snapshot* from, int trials, const cmpc_walk_snapshot* live)
+{
+    const cmpc_walk_snapshot* pool = from->pool;
+    if (!pool) return "pool is NULL";
+    if (pool->tick < 1) return "pool->tick must be at least 1 (trials from tick 0 are cmpc_rollout_walk_refill_trials_device's)";
+    if (from->pool_batch < 1) return "pool_batch must be at least 1";
+    const void* sp[CMPC_SNAP_ARRAYS];
+    snapshot_pointers(*pool, sp);
+    for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i)
+        if (!sp[i] && i != 3 && i != 4 && i != 5) return "a required pool array is NULL (every array but dX0, dInfo, dZmp)";
+    if (pool->lists_in < 0 || pool->lists_in > 1) return "pool->lists_in must be 0 or 1";
+    if (trials > 0 && !from->dTrialSnapshot) return "dTrialSnapshot is NULL";
+    if (live) {
+        const void* lp[CMPC_SNAP_ARRAYS];
+        snapshot_pointers(*live, lp);
+        for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i)
+            for (int j = 0; j < CMPC_SNAP_ARRAYS; ++j)
+                if (sp[i] && sp[i] == lp[j]) return "a pool array is also a live array";
+    }
+    return nullptr;
+}
+// the argument block of the restore step of tick `tick`: the snapshot's table, the pool's set pool->lists_in paired with the live set live->lists_in (the
+// one this tick reads as "previous") and the pool's other set with the other live set
+static bool restore_args(int N, int B, int M, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* r, const cmpc_walk_refill_snapshot* from,
+                         CmpcRefillRestoreArgs& a)
+{
+    if (tick < 0 || !live || !r || r->trials < 1 || !r->dStartTick || !r->dTrial || live->lists_in < 0 || live->lists_in > 1) return false;
+    cmpc_walk_snapshot pool = *from->pool;
+    if (pool.lists_in != live->lists_in) {
+        std::swap(pool.dListT, pool.dListTB);
+        std::swap(pool.dListPose, pool.dListPoseB);
+        std::swap(pool.dListN, pool.dListNB);
+    }
+    if (!snapshot_args(N, B, from->pool_batch, M, &pool, live, from->dTrialSnapshot, nullptr, a.copy)) return false;
+    a.start = r->dStartTick; a.trial = r->dTrial;
+    a.tick = tick; a.Q = r->trials; a.pool_tick = pool.tick;
+    a.ok = from->dTrialSnapshotOk;
+    a.end_tick = live->dEndTick; a.end_code = live->dEndCode;
+    return true;
+}
+
+int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* refill,
+                                const cmpc_walk_refill_snapshot* from)
+{
+    if (!from || !live || !refill || refill->trials < 0) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: null argument or a negative count");
+    if (const char* why = restore_refusal(from, refill->trials, live)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_refill_restore: ") + why);
+    if (horizon < 1 || batch < 1 || max_contacts < 1 || tick < 0 || !refill->dStartTick || !refill->dTrial || live->lists_in < 0 || live->lists_in > 1)
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: bad argument");
+    if (refill->trials == 0) return CMPC_OK;   // (no slot ever holds a trial)
+    CmpcRefillRestoreArgs a;
+    if (!restore_args(horizon, batch, max_contacts, tick, live, refill, from, a))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: bad argument (a NULL live array)");
+    cmpc_refill_restore_host(a);
+    return CMPC_OK;
+}
+
+static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                            const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
+                            int lists_in, int* lists_out, void* stream);
 
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
@@ -1818,6 +1898,23 @@ int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int 
                                            const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
                                            void* stream)
 {
+    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream);
+}
+
+int cmpc_rollout_walk_refill_snapshot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from,
+                                             int row0, int lists_in, int* lists_out, void* stream)
+{
+    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, from, row0, lists_in, lists_out, stream);
+}
+
+// from (cmpc_walk_refill_snapshot) null: the walk above.  Else the trials start from pool rows: a sixth launch per tick, the restore, behind the refill; the
+// front and back kernels and the record take the pool's tick as the offset of every slot's local tick, and no problem of any solve is on a first tick (the
+// solve is launched without the slots' start ticks: warm for all)
+static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                            const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
+                            int lists_in, int* lists_out, void* stream)
+{
     // (the refusals that need no handle come first: they are the same with and without one)
     if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
     const cmpc_tick_io& k = io->tick;
@@ -1829,6 +1926,11 @@ int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int 
     if (trials && ((trials->dHiddenWrench && trials->hidden_ticks == 0) || (trials->dStateNoise && trials->noise_ticks == 0)))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: a schedule with no rows");
     if (trials && trials->dModelOk && !trials->dModels) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: dModelOk without dModels");
+    if (from) {
+        const cmpc_walk_snapshot live = walk_live_view(io, rec, 0);
+        if (const char* why = restore_refusal(from, refill->trials, &live))
+            return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_refill_snapshot_device: ") + why);
+    }
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
         !k.box_upper || !k.box_lower || !k.dState || !k.dStateOut || k.dState != k.dStateOut || !k.dPlanT || !k.dPlanPose || !k.dPlanN || !k.dOk || !k.dLand ||
@@ -1874,6 +1976,7 @@ int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int 
     float* const set_p[2] = {k.dListPose, io->dListPoseB};
     int* const set_n[2] = {k.dListN, io->dListNB};
     const int N = h->cfg.horizon, B = h->B;
+    const int offset = from ? from->pool->tick : 0;
     int cur = lists_in;
     for (int i = 0; i < ticks && rc == CMPC_OK; ++i) {
         const int tick = tick0 + i;
@@ -1881,20 +1984,31 @@ int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int 
         cur = 1 - cur;
         rc = rollout_refill_impl(h, tick, rec, refill, k.dStateOut, st);
         if (rc != CMPC_OK) break;
+        if (from && refill->trials > 0) {
+            const cmpc_walk_snapshot live = walk_live_view(io, rec, prev);
+            CmpcRefillRestoreArgs ra;
+            if (!restore_args(N, B, max_contacts, tick, &live, refill, from, ra)) {
+                rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_snapshot_device: bad restore");
+                break;
+            }
+            const int rrc = cmpc_launch_refill_restore(&ra, st);
+            if (rrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill restore launch: ") + hipGetErrorString((hipError_t)rrc)); break; }
+        }
         int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
                                               set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,
                                               k.plan_knots, k.plan_dt, k.robot_mass, k.com_height, dt_ns, h->dEnded, refill->dStartTick, refill->dTrial, tick,
                                               refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), tr,
-                                              st);
+                                              offset, st);
         if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (front) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
-        rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, refill->dStartTick, tick);
+        rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, from ? nullptr : refill->dStartTick, tick);
         if (rc != CMPC_OK) break;
         lrc = cmpc_launch_tick_post_refill(B, N, max_contacts, h->cfg.sampling_time, (float)h->cfg.gravity, model_corners(h), corners_stride(h), k.dX, k.dP,
                                            k.dStateOut, k.dStateOut, k.dZmp, (float)k.plant_step, k.plant_substeps, (float)k.zmp_half_x, (float)k.zmp_half_y,
-                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, refill->dTrial, tr, st);
+                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, refill->dTrial, tr, offset, st);
         if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (back) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
         CmpcRecordArgs a;
-        if (!h->box_set || !record_args(N, B, tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {
+        // (the tick number an ending takes is tick - start[b]; with trials from a snapshot the whole-walk number offset + tick - start[b]: the offset goes in here)
+        if (!h->box_set || !record_args(N, B, offset + tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {
             rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad record");
             break;
         }

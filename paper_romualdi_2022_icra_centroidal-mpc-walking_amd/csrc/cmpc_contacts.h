@@ -440,6 +440,45 @@ __host__ __device__ inline int cmpc_snapshot_source(const CmpcSnapshotArgs& a, i
     return s >= 0 && s < a.src_B ? s : -1;
 }
 
+// ---- the restore launch of a refill walk whose trials start from a snapshot (include/cmpc.h, cmpc_walk_refill_snapshot): a slot spawned this tick receives
+// the pool row of its trial.  copy: the snapshot's table with the pool as source (src_B = pool_batch) and the live buffers as destination, the pool's list
+// sets already paired with the live sets of this tick's parity; copy.index is dTrialSnapshot, indexed by TRIAL, and copy.ok is not used.
+struct CmpcRefillRestoreArgs {
+    CmpcSnapshotArgs copy;
+    const int* start; const int* trial;   // [B]: the slots' start ticks and trials
+    int tick, Q, pool_tick;
+    int* ok;                              // [Q] or null: dTrialSnapshotOk
+    int* end_tick; int* end_code;         // [B]: the record's outcome words (a bad index ends its slot at spawn)
+};
+// the trial spawned in slot b this tick, or -1: none (one load for a slot that was not spawned)
+__host__ __device__ inline int cmpc_refill_restore_trial(const CmpcRefillRestoreArgs& a, int b)
+{
+    if (a.start[b] != a.tick) return -1;
+    const int q = a.trial[b];
+    return q >= 0 && q < a.Q ? q : -1;
+}
+// the pool row of trial q, or -1 for an index outside the pool
+__host__ __device__ inline int cmpc_refill_restore_source(const CmpcRefillRestoreArgs& a, int q)
+{
+    const int s = a.copy.index[q];
+    return s >= 0 && s < a.copy.src_B ? s : -1;
+}
+// the host form's loop (cmpc_rollout_refill_restore); here for the reason cmpc_refill_host is
+inline void cmpc_refill_restore_host(const CmpcRefillRestoreArgs& a)
+{
+    for (int b = 0; b < a.copy.B; ++b) {
+        const int q = cmpc_refill_restore_trial(a, b);
+        if (q < 0) continue;
+        const int s = cmpc_refill_restore_source(a, q);
+        if (a.ok) a.ok[q] = s >= 0 ? 1 : 0;
+        if (s < 0) { a.end_tick[b] = a.pool_tick; a.end_code[b] = 0; continue; }
+        for (int i = 0; i < a.copy.count; ++i) {
+            const size_t w = (size_t)a.copy.words[i];
+            __builtin_memcpy(a.copy.dst[i] + w * b, a.copy.src[i] + w * s, sizeof(unsigned) * w);
+        }
+    }
+}
+
 // ---- the reverse walk's rule for ended problems (include/cmpc.h, cmpc_rollout_walk_vjp_device).  One statement for the host form and the
 // kernel (contraction off: the one sum is a plain double add).  A gate step sits between two reverse ticks: its POST part finishes tick `tick_post`
 // (row_post) from what cmpc_rollout_tick_vjp_device left, its PRE part prepares tick `tick_pre` (row_pre).  Either part may be absent (do_post / do_pre).

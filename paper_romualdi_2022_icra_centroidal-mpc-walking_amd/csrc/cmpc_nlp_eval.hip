@@ -1497,9 +1497,13 @@ __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float
 // pointer are workgroup-uniform), trial q's model over it (cmpc_refill_trial_model: the statement of cmpc_set_models_device's kernel); the solve and the back
 // kernel of this tick are later launches on the stream.  The noise row is row [local tick][q] inside its range -- the same float32 add -- else the plain
 // copy.  false is the kernel without any of it: `tr` is not read.
+// rf.offset > 0 (trials from a snapshot): a slot spawned at s runs tick t at local tick offset + (t - s) -- one integer sum, converted once -- and its spawn
+// tick is NOT a first tick: an ordinary warm merge tick on the lists and the solution the restore launch put there.  What the trial owns -- its wrench and
+// noise rows, the model write at its spawn tick -- stays indexed by r = t - s.  With offset 0 every expression is the one it was.
 struct CmpcRefillTick {
     const int* start; const int* trial;     // [B]: the slots' start ticks and trials (cmpc_walk_refill)
     int tick;
+    int offset;                             // trials from a snapshot (cmpc_walk_refill_snapshot): the pool's tick t_s, the local tick at spawn; else 0
     const float* wrench_trials; int wrench_ticks, trials;   // [wrench_ticks][trials][N][6] or null
     double plan_t_first;
     float g8;                               // the cold start's f_z
@@ -1534,14 +1538,14 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
     int model_q = -1;                     // (TR: the trial whose model the slot takes on this tick, its first)
     if constexpr (RF) {
         const int local = rf.tick - rf.start[b], q = rf.trial[b];
-        fresh = local == 0;
-        refill_local_time(local, dt, rf.plan_t_first, &now, &plan_t_offset);
+        fresh = local == 0 && rf.offset == 0;
+        refill_local_time(rf.offset + local, dt, rf.plan_t_first, &now, &plan_t_offset);
         if (rf.wrench_trials && local >= 0 && local < rf.wrench_ticks && q >= 0 && q < rf.trials)
             wrench_b = rf.wrench_trials + ((size_t)local * rf.trials + q) * N * 6;
         if (fresh) merge = 0;
         if constexpr (TR) {
             if (tr.noise && local >= 0 && local < tr.noise_ticks && q >= 0 && q < tr.Q) noise_q = tr.noise + ((size_t)local * tr.Q + q) * 9;
-            if (tr.models && fresh && q >= 0 && q < tr.Q) model_q = q;
+            if (tr.models && local == 0 && q >= 0 && q < tr.Q) model_q = q;
         }
     }
     __shared__ int okw;
@@ -1682,6 +1686,7 @@ __global__ __launch_bounds__(256) void cmpc_tick_pre_kernel(int B, int N, int M,
 // RF: the refill walk -- the step adjustment looks for the next contact at the problem's own time (tick - start[b]) dt
 // MM and RF (cmpc_rollout_walk_refill_trials_device): hidden [hidden_ticks][trials][6] and gain [trials] are per TRIAL -- the lane takes row [local
 // tick][trial[b]] inside the schedule's range, else none (the term is then not added: a select per lane, no add of zero), and its trial's gain
+// offset (RF; trials from a snapshot, else 0): the problem's time is (offset + tick - start[b]) dt; the schedule's row stays tick - start[b]
 template <bool MM, bool RF>
 __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M, double now, float grav, const float* __restrict__ corners, int corners_stride,
                                                              const float* __restrict__ X, const float* __restrict__ P, const float* state_in, float* state_out,
@@ -1689,14 +1694,14 @@ __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M
                                                              const double* __restrict__ t, float* __restrict__ pose, const int* __restrict__ n,
                                                              const int* __restrict__ ended, const float* __restrict__ hidden,
                                                              const float* __restrict__ gain, const int* __restrict__ start, int tick, double dt,
-                                                             const int* __restrict__ trial, int hidden_ticks, int trials)
+                                                             const int* __restrict__ trial, int hidden_ticks, int trials, int offset)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     if (ended && ended[b] >= 0) return;   // (cmpc_set_ended_device; per lane, as the line above: nothing behind it needs the whole wave)
     if constexpr (RF) {
         double unused;
-        refill_local_time(tick - start[b], dt, 0.0, &now, &unused);
+        refill_local_time(offset + (tick - start[b]), dt, 0.0, &now, &unused);
         if constexpr (MM) {
             const int local = tick - start[b], q = trial[b];
             const bool known = q >= 0 && q < trials;
@@ -1871,6 +1876,27 @@ __global__ __launch_bounds__(256) void cmpc_rollout_snapshot_kernel(CmpcSnapshot
     }
 }
 
+// restore (cmpc_rollout_walk_refill_snapshot_device): one workgroup per slot, between the refill launch and the front kernel of a tick.  The gate comes ahead
+// of everything and is workgroup-uniform -- blockIdx and kernel arguments only: a slot that was not spawned this tick costs its workgroup one scalar load.
+// A spawned slot receives its trial's pool row through the snapshot kernel's row copy (snap_row); an index outside the pool ends the slot at spawn.  The
+// flag and the two outcome words are one thread's; on the copy path the outcome words are rows of the table.  No LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_refill_restore_kernel(CmpcRefillRestoreArgs a)
+{
+    const int b = blockIdx.x;   // (the grid is B workgroups)
+    const int q = cmpc_refill_restore_trial(a, b);
+    if (q < 0) return;          // (uniform)
+    const int s = cmpc_refill_restore_source(a, q);
+    if (a.ok && threadIdx.x == 0) a.ok[q] = s >= 0 ? 1 : 0;
+    if (s < 0) {                // (uniform)
+        if (threadIdx.x == 0) { a.end_tick[b] = a.pool_tick; a.end_code[b] = 0; }
+        return;
+    }
+    for (int i = 0; i < a.copy.count; ++i) {
+        const size_t w = (size_t)a.copy.words[i];
+        snap_row(a.copy.dst[i] + w * b, a.copy.src[i] + w * s, a.copy.words[i], threadIdx.x);
+    }
+}
+
 // gate: one thread per problem for the small arrays (cmpc_walk_gate_problem; lanes past B do nothing), then every thread strides over the wide rows
 // (cmpc_walk_gate_wide).  The two parts touch disjoint arrays: no barrier, no atomics.
 __global__ __launch_bounds__(256) void cmpc_walk_vjp_gate_kernel(CmpcGateArgs a, size_t wide)
@@ -1909,6 +1935,12 @@ extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t strea
 extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_rollout_snapshot_kernel, dim3(a->B), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_refill_restore_kernel, dim3(a->copy.B), dim3(256), 0, stream, *a);
     return (int)hipGetLastError();
 }
 
@@ -1992,10 +2024,10 @@ extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const
                                            const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
                                            long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
                                            int wrench_ticks, int trials, double plan_t_first, float g8, const CmpcRefillTrialArgs* tr,
-                                           hipStream_t stream)
+                                           int offset, hipStream_t stream)
 {
-    if (M > 16) return (int)hipErrorInvalidValue;
-    const CmpcRefillTick rf{start, trial, tick, wrench_trials, wrench_ticks, trials, plan_t_first, g8};
+    if (M > 16 || offset < 0) return (int)hipErrorInvalidValue;
+    const CmpcRefillTick rf{start, trial, tick, offset, wrench_trials, wrench_ticks, trials, plan_t_first, g8};
     if (tr && (tr->models || tr->noise))
         hipLaunchKernelGGL((cmpc_tick_pre_kernel<true, true>), dim3(B), dim3(256), 0, stream, B, N, M, dt, 0.0, 1, plan_t, plan_pose, plan_n, prev_t, prev_pose,
                            prev_n, list_t, list_pose, list_n, ok, land, box, state, (const float*)nullptr, P, Xprev, X0, plan_com, plan_h, plan_knots, plan_dt,
@@ -2010,16 +2042,16 @@ extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const
 extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
                                             const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
                                             const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
-                                            const int* trial, const CmpcRefillTrialArgs* tr, hipStream_t stream)
+                                            const int* trial, const CmpcRefillTrialArgs* tr, int offset, hipStream_t stream)
 {
     if (tr && (tr->hidden || tr->gain))
         hipLaunchKernelGGL((cmpc_tick_post_kernel<true, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX,
                            dP, dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, tr->hidden, tr->gain, start, tick, dt, trial,
-                           tr->hidden_ticks, tr->Q);
+                           tr->hidden_ticks, tr->Q, offset);
     else
         hipLaunchKernelGGL((cmpc_tick_post_kernel<false, true>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, 0.0, grav, dCorners, corners_stride, dX,
                            dP, dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, (const float*)nullptr, (const float*)nullptr, start, tick,
-                           dt, (const int*)nullptr, 0, 0);
+                           dt, (const int*)nullptr, 0, 0, offset);
     return (int)hipGetLastError();
 }
 
@@ -2029,10 +2061,10 @@ extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav
 {
     if (hidden || gain)
         hipLaunchKernelGGL((cmpc_tick_post_kernel<true, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
-                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0);
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0, 0);
     else
         hipLaunchKernelGGL((cmpc_tick_post_kernel<false, false>), dim3((B + 255) / 256), dim3(256), 0, stream, B, N, M, now, grav, dCorners, corners_stride, dX, dP,
-                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0);
+                           dStateIn, dStateOut, dZmp, h, nsub, zx, zy, land, t, pose, n, ended, hidden, gain, (const int*)nullptr, 0, 0.0, (const int*)nullptr, 0, 0, 0);
     return (int)hipGetLastError();
 }
 

@@ -197,7 +197,8 @@ class WalkingRollout:
         [trial_ticks, ..] gathered out of the slot-major trace by one index_select each on the device, with valid [trial_ticks] bool (rows at or past
         trials["ticks"][q] are not the trial's).
         Per-trial models and a per-trial plant mismatch (hidden pushes, noise, a force gain): walk_device_refill_trials(), a method of its own because this
-        signature is pinned; here the models are the slot's and mismatch= is refused.
+        signature is pinned; here the models are the slot's and mismatch= is refused.  Trials that start from a snapshot of a walk in progress instead of
+        standing at tick 0 (warm from their first tick): walk_device_refill_from_snapshot().
         Out of scope: gradients and forward mode through a refill walk, and -- NotImplementedError, raised before anything touches a GPU -- replan,
         mismatch= (see above), taped=True, every (snapshots and checkpoints), and lists longer than 16 contacts."""
         for name, value in (("replan", replan), ("mismatch", mismatch), ("taped", taped or None), ("every", every)):
@@ -263,7 +264,76 @@ class WalkingRollout:
             return rec
         return self._queued(walk)
 
-    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None):
+    def walk_device_refill_from_snapshot(self, snapshot, ticks, trial_ticks, snapshot_of, models=None, mismatch=None, **kwargs):
+        """A queue of Q = len(snapshot_of) trials that each START FROM A SNAPSHOT of a walk in progress, walked through the B slots of this roll-out in ONE
+        walk of `ticks` ticks (cmpc_rollout_walk_refill_snapshot_device, include/cmpc.h; DESIGN.md 7f "Trials from a snapshot"): trial q is a fork of
+        problem snapshot_of[q] of `snapshot` (a value of walk_device_checkpointed's "checkpoints", or any BatchSolver.walk_snapshot filled by
+        rollout_snapshot_device, of any batch size; repeated rows are the normal case) and walks trial_ticks RESUMED ticks, t_s = snapshot["tick"] ..
+        t_s + trial_ticks - 1, warm from its first one: there is no cold first tick.  A slot takes the queue's next trial the tick after its robot ended or
+        finished, as in walk_device_refill; six launches per tick (the restore of the spawned slots goes between the refill and the front kernel), no host
+        read, no synchronisation.  What walk_resume_device_mismatch(skip_ended=True) does for B robots per call, for a queue.
+        models [Q, 34] and mismatch = dict(hidden_wrench=[Th, Q, 6], state_noise=[Tn, Q, 9], force_gain=[Q]): walk_device_refill_trials' per-trial data;
+        their rows are the ticks SINCE SPAWN (row 0 is tick t_s of the trial), so a mismatch tick_first other than 0 is a ValueError.  kwargs:
+        walk_device_refill_trials' push, push_ticks, wrench_trials (rows: ticks since spawn; without them the wrench rows of P stay what the snapshot
+        holds), trace and stop; anything else is a TypeError.  A snapshot["wrench"] schedule that reaches t_s is not continued: NotImplementedError.  The
+        references are the SLOT's, sized for t_s + trial_ticks and read at the whole-walk time.
+        A trial's bits are those of walk_resume_device_mismatch(snapshot, trial_ticks, mismatch with tick_first = t_s, index = its row, skip_ended=True) on a
+        roll-out of the same batch size, factor storage and options that holds it in the same slot, with models row `slot` the trial's model.
+        -> walk_device_refill_trials' dict, with tick numbers of the whole walk in every end_tick, plus tick0 = t_s and trials["snapshot_ok"] [Q] int32:
+        1 / 0 once the trial was spawned (0: its index lay outside the snapshot's batch -- nothing was copied, the trial is ended at spawn with end_tick
+        t_s and end_code 0 and the slot goes to the next trial), -1 for a trial never started.  A trial whose snapshot row had already ended is ended at
+        spawn too, with that row's outcome.  trials["ticks"] counts the resumed ticks the record saw of the trial: 0 for a trial ended at spawn (the
+        C ABI's dTrialTicks holds 1 for it, the tick its slot was held).  Afterwards the roll-out's own models are back, as after
+        walk_device_refill_trials.  Out of scope, as there: gradients, tapes, forward mode, replan, lists longer than 16 contacts (NotImplementedError)."""
+        mismatch = dict(mismatch or {})
+        if int(mismatch.pop("tick_first", 0)) != 0:
+            raise ValueError("walk_device_refill_from_snapshot: the schedules' rows are the ticks since the trial's spawn, so tick_first must be 0")
+        for given, known in ((kwargs, ("push", "push_ticks", "wrench_trials", "trace", "stop")), (mismatch, ("hidden_wrench", "state_noise", "force_gain"))):
+            for k in given:
+                if k not in known:
+                    raise TypeError(f"walk_device_refill_from_snapshot: unexpected argument {k!r}")
+        if self.M > 16:
+            raise NotImplementedError("walk_device_refill_from_snapshot: lists longer than 16 contacts are out of scope of a refill walk")
+        args = dict(push=None, push_ticks=0, wrench_trials=None, trace=True, stop=("merge", "solver", "nonfinite"))
+        args.update(kwargs)
+        if args["push"] is not None and args["wrench_trials"] is not None:
+            raise ValueError("walk_device_refill_from_snapshot: push or wrench_trials, not both")
+        t_s = int(snapshot["tick"])
+        if t_s < 1:
+            raise ValueError("walk_device_refill_from_snapshot: the snapshot must be of tick 1 or later (trials from tick 0: walk_device_refill_trials)")
+        if snapshot.get("wrench") is not None and t_s - snapshot["wrench"][1] < snapshot["wrench"][0].shape[0]:
+            raise NotImplementedError("walk_device_refill_from_snapshot: the snapshot's wrench schedule reaches its tick and is not continued by a refill "
+                                      "walk (pass the rows as wrench_trials)")
+        Q = len(snapshot_of)
+        assert ticks >= 1 and trial_ticks >= 1 and int(snapshot["max_contacts"]) == self.M
+
+        def walk():
+            torch, s = self.torch, self.solver
+            data = s.walk_refill_trials(models=models, device=self.dev, **mismatch)
+            given = any(data[k] is not None for k in ("models", "hidden_wrench", "state_noise", "force_gain"))
+            pool = s.walk_refill_snapshot(snapshot, snapshot_of, device=self.dev)
+            z3 = torch.zeros((Q, 3), dtype=torch.float32, device=self.dev)    # (dState0: the restore overwrites what the refill launch copies from it)
+            try:
+                rec = self._walk_refill(ticks, trial_ticks, z3, z3, z3, args["push"], args["push_ticks"], args["wrench_trials"], args["trace"],
+                                        args["stop"], trials=data if given else None, pool=pool)
+            finally:
+                if data["models"] is not None:    # (the table holds each slot's last trial's model: back to the roll-out's own, in stream order)
+                    if self.models is not None:
+                        s.set_models_device(self.models)
+                    else:
+                        s.set_models(None)
+            t = rec["trials"]
+            ok = data["model_ok"]
+            t["model_ok"] = ok if ok is not None else torch.full((Q,), -1, dtype=torch.int32, device=self.dev)
+            t["snapshot_ok"] = pool["snapshot_ok"]
+            # a trial ended at spawn -- a bad index (code 0), or a row that had ended before the snapshot (end tick < t_s) -- was never seen walking by the record
+            at_spawn = (t["end_tick"] >= 0) & ((t["end_tick"] < t_s) | (t["end_code"] == 0))
+            t["ticks"].masked_fill_(at_spawn, 0)
+            rec["tick0"] = t_s
+            return rec
+        return self._queued(walk)
+
+    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
@@ -286,15 +356,20 @@ class WalkingRollout:
         dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
         state = z((B, 9))
         ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
-        refs = self._planner_refs(trial_ticks)
+        refs = self._planner_refs(trial_ticks if pool is None else pool["tick"] + trial_ticks)
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         s.outcome_init_device(state, rec)
         fill = s.walk_refill(state0, trial_ticks, wrench_trials, trace_rows=ticks, device=dev)
         # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
         sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
-        cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
-                                           step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
-                                           trials=trials)
+        if pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
+            cur = s.rollout_walk_refill_snapshot_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, pool,
+                                                        row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                                                        force_sample_time=self.force_sample_time, trials=trials)
+        else:
+            cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
+                                               step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
+                                               trials=trials)
         s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
         del rec["_c"]
         trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
@@ -309,7 +384,7 @@ class WalkingRollout:
                 out["valid"] = ar < trials["ticks"][q]
                 return out
             trials["trace"] = trial_trace
-        self._walk_refill_keep = (fill, refs, wrench_trials, trials)    # (the queued launches read these)
+        self._walk_refill_keep = (fill, refs, wrench_trials, trials, pool)    # (the queued launches read these)
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state, trial_of=fill["trial_of"], trials=trials)
         return rec
 
@@ -873,8 +948,9 @@ class WalkingRollout:
         taped=True: "tape" as walk_device_taped's, of ticks + 1 rows: row 0 is a stub that holds the snapshot's list times and counts (the previous
         lists of the first resumed tick), row 1 + i is resume tick + i, first_row_is_first_tick = 0 (reverse it from row 1).
         Bit-equality with the unbroken walk is promised between handles of the same batch size and factor storage: the solver picks its kernel variant
-        from them (the round-3 note on stragglers), and another variant rounds differently.  Out of scope: refilling ended problems with new
-        robots from a snapshot -- a queue of trials behind the slots of a walk is walk_device_refill(), which takes no snapshots."""
+        from them (the round-3 note on stragglers), and another variant rounds differently.  A queue of trials that each start from a
+        snapshot, walked through the slots with ended robots replaced: walk_device_refill_from_snapshot().  Out of scope here: refilling the ended
+        problems of THIS call -- a queue of trials behind the slots of a walk is walk_device_refill(), and from snapshots the method just named."""
         return self._queued(lambda: self._walk_resume(snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every))
 
     def walk_resume_device_mismatch(self, snapshot, ticks, mismatch, **kwargs):

@@ -1331,6 +1331,53 @@ class BatchSolver:
             C.byref(out), st))
         return out.value
 
+    def walk_refill_snapshot(self, snapshot, snapshot_of, device=None):
+        """A cmpc_walk_refill_snapshot as a dict: the pool -- snapshot, a walk_snapshot dict filled by rollout_snapshot_device (its tick >= 1 and lists_in
+        as marked; any batch size) -- and snapshot_of [Q] int32 (numpy or CUDA), the pool row each trial of the queue starts from.  The dict holds
+        snapshot_of on the device, snapshot_ok [Q] int32 (-1 until the trial's spawn writes 1 or 0), trials = Q, tick = the pool's, the pool itself (kept
+        alive) and "_c", the C struct that points at them."""
+        import torch
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_snapshot_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_snapshot_device")
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        hold = []
+        if not isinstance(snapshot_of, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
+            hold.append(torch.from_numpy(np.ascontiguousarray(snapshot_of, np.int32)))
+            snapshot_of = hold[-1].to(dev, non_blocking=True)
+        idx = snapshot_of.detach().to(dev, torch.int32).contiguous()
+        assert idx.dim() == 1, "snapshot_of: expected [Q]"
+        Q = int(idx.shape[0])
+        ok = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+        c = _capi.CmpcWalkRefillSnapshot(C.addressof(snapshot["_c"]), int(snapshot["batch"]), idx.data_ptr() if Q else None, ok.data_ptr() if Q else None)
+        return dict(pool=snapshot, snapshot_of=idx, snapshot_ok=ok, trials=Q, tick=int(snapshot["tick"]), _host=hold, _c=c)
+
+    def rollout_walk_refill_snapshot_device(self, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, snapshot,
+                                            row0=0, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
+                                            trials=None):
+        """cmpc_rollout_walk_refill_snapshot_device: rollout_walk_refill_device with trials that start from a pool of saved problems (snapshot:
+        walk_refill_snapshot(...); None: cmpc_rollout_walk_refill_trials_device through the new entry point).  Six launches per tick: the restore goes
+        between the refill and the front kernel, and a slot spawned at tick s runs tick t at the pool's tick + (t - s).  (A method of its own: the parameter
+        list of rollout_walk_refill_device is pinned.)"""
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_snapshot_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_snapshot_device")
+        io = _capi.CmpcWalkIO()
+        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                force_sample_time)
+        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
+        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        out = C.c_int(-1)
+        if snapshot is not None:
+            assert snapshot["trials"] == refill["trials"], "snapshot_of must have the queue's length"
+            assert snapshot["pool"]["max_contacts"] == lists[0].shape[2], "the pool's lists must have the walk's length"
+            assert snapshot["pool"]["_c"].tick == snapshot["tick"], "the pool was marked with another tick since walk_refill_snapshot"
+        if trials is not None:
+            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_snapshot_device(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
+            C.byref(trials["_c"]) if trials is not None else None, C.byref(snapshot["_c"]) if snapshot is not None else None, int(row0), int(lists_in),
+            C.byref(out), st))
+        return out.value
+
     def shift_solution_device(self, dXprev, dX0):
         """is_warm_start_enabled: dX0 = dXprev shifted by one knot; solve from it with solve_device(..., warm=True)."""
         self._launch(dX0.device, lambda st: self._lib.cmpc_shift_solution_device(self._h, dXprev.data_ptr(), dX0.data_ptr(), st))
