@@ -58,7 +58,7 @@ typedef struct {
     double corners[2][4][3];  /* [CONTACT_i] corner_j, contacts in alphabetical name order        */
     /* solver options (ipopt_tolerance / ipopt_max_iteration take the place of IPOPT's) */
     int max_iterations;       /* Newton iteration budget per solve (default 40)                   */
-    double tolerance;         /* on the primal residuals and on max t*z (<= 0: default 1e-6 up to N = 20, 3e-7 beyond) */
+    double tolerance;         /* on the primal residuals and on max t*z (<= 0: default 1e-6 for N = 4 .. 20, 3e-7 beyond and for N <= 3) */
     double step_tolerance;    /* on the last Newton step, max-norm over states and forces (default 1e-4) */
     double mu_init;           /* initial barrier parameter; <= 0 (default): per problem, from its
                                * initial infeasibility ep0: clamp(3.5 ep0^2, 0.03, 0.5)           */
@@ -111,15 +111,25 @@ typedef struct {
  * of the batch are untouched.  cmpc_set_contacts / cmpc_set_contact_lists write schedules inside the subset.  So does a problem whose row of a
  * per-problem model table set on the device breaks the model rule (cmpc_set_models_device, below: dOk[b] = 0). */
 void cmpc_default_config(cmpc_config* cfg);                      /* ergoCubGazeboV1 values, N=20 */
+/* sizes of the NLP at a horizon cmpc_create accepts (2 .. 40); CMPC_ERR_ARG, with the range in cmpc_last_error(NULL), outside it */
 int cmpc_dims(int horizon, int* n_x, int* n_p, int* n_g, int* nnz_jac, int* nnz_hess);
 
-/* the tolerance cmpc_create uses when cmpc_config.tolerance <= 0: 1e-6 up to N = 20, 3e-7 beyond (parity with the float64 solve
+/* the tolerance cmpc_create uses when cmpc_config.tolerance <= 0: 1e-6 for N = 4 .. 20, 3e-7 beyond and for N <= 3 (parity with the float64 solve
  * needs it).  A caller mapping the reference's ipopt_tolerance passes it only when it is tighter than this, and 0 otherwise. */
 double cmpc_default_tolerance(int horizon);
+/* Short horizons ("Both ends of the horizon range"; profiles/horizon_ends.txt).  Walking problems with pushes are inside the 1e-4 target
+ * at every horizon 2 .. 40; the 3e-7 at N <= 3 is what that takes (at 1e-6: CoM velocity up to 1.9e-4 with status 0).  Standing problems with a
+ * perturbed CoM are not, below N = 15: a weakly active friction row of the first stages stays at its barrier-floor bias, and a tighter tolerance
+ * does not remove it.  Measured on MI355X, of 256 problems outside 1e-4 against the float64 optimum: N = 2: 57 (31 of them status 1, iteration
+ * budget), N = 3: 60 (30 status 1), N = 4: 99 (CoM velocity 9.5e-3), N = 7: 21 (1.7e-3), N = 10: 4 (2.7e-4), N = 12: 0, N = 13: 1 (3.3e-4),
+ * N = 20: 0.  The CPU model of the algorithm (oracle/ipm_ref.c) shows the same family: 37, 16, 24, 5, 1, 1, 1, 0. */
 int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out);
 int cmpc_destroy(cmpc_handle h);
 const char* cmpc_last_error(cmpc_handle h);                       /* h may be NULL */
 int cmpc_batch(cmpc_handle h);
+/* the storage the handle's kernel variant really uses: CMPC_FACTORS_LDS or CMPC_FACTORS_HBM.  A CMPC_FACTORS_LDS request at a horizon whose resident
+ * image exceeds 160 KiB (N >= 23) is served by the HBM-factor variant: this is how a caller sees it. */
+int cmpc_factor_storage(cmpc_handle h);
 void* cmpc_stream(cmpc_handle h);                                 /* hipStream_t of the handle */
 
 /* ---- the hot path: solve a batch, operands resident in device memory ----

@@ -227,6 +227,7 @@ EXPORTS = [
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
+    "cmpc_factor_storage",
 ]
 
 _lib = None
@@ -257,6 +258,8 @@ def lib():
         L.cmpc_last_error.argtypes = [vp]
         L.cmpc_last_error.restype = C.c_char_p
         L.cmpc_batch.argtypes = [vp]
+        if hasattr(L, "cmpc_factor_storage"):
+            L.cmpc_factor_storage.argtypes = [vp]
         L.cmpc_stream.argtypes = [vp]
         L.cmpc_stream.restype = vp
         L.cmpc_solve_device.argtypes = [vp, fp, fp, fp, fp, vp]

@@ -220,7 +220,8 @@ void cmpc_default_config(cmpc_config* c)
 
 int cmpc_dims(int N, int* nx, int* np, int* ng, int* nnzj, int* nnzh)
 {
-    if (N < 1) return CMPC_ERR_ARG;
+    // (the range of cmpc_create: sizes of a horizon no handle can have would only size buffers nothing can fill)
+    if (N < 2 || N > CMPC_NMAX) return fail(nullptr, CMPC_ERR_ARG, "cmpc_dims: horizon must be in [2, " + std::to_string(CMPC_NMAX) + "]");
     if (nx) *nx = 45 * N + 15;
     if (np) *np = 50 * N + 27;
     if (ng) *ng = 53 * N + 15;
@@ -231,10 +232,11 @@ int cmpc_dims(int N, int* nx, int* np, int* ng, int* nnzj, int* nnzh)
 
 const char* cmpc_last_error(cmpc_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 int cmpc_batch(cmpc_handle h) { return h ? h->B : 0; }
+int cmpc_factor_storage(cmpc_handle h) { return !h ? CMPC_ERR_ARG : h->scratch_stride ? CMPC_FACTORS_HBM : CMPC_FACTORS_LDS; }
 void* cmpc_stream(cmpc_handle h) { return h ? (void*)h->stream : nullptr; }
 
 // The one statement of the default tolerance rule (include/cmpc.h); the reasons are at its use in cmpc_create.
-double cmpc_default_tolerance(int horizon) { return horizon > 20 ? 3e-7 : 1e-6; }
+double cmpc_default_tolerance(int horizon) { return (horizon > 20 || horizon <= 3) ? 3e-7 : 1e-6; }
 
 int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out)
 {
@@ -254,6 +256,10 @@ int cmpc_create(const cmpc_config* cfg, int batch, int device, cmpc_handle* out)
     // complementarity products that still lag above the barrier floor at termination (max t z <= tolerance), and it grows with the number of stages behind the
     // first knots.  Config 5 (N = 30), worst of 5 unseen seeds x 512 problems against the float64 oracle (profiles/r04_accuracy_sweep.txt), barrier floor 5e-8:
     // tolerance 1e-6 -> 1.05e-4 (round 3), 5e-7 -> 9.3e-5, 4e-7 -> 9.3e-5, 3e-7 -> 6.8e-5 at 8.57 / 8.95 / 9.08 / 9.24 iterations on the mean.
+    // N <= 3 (no tail polish exists there: tail_stages >= horizon): 3e-7 as well.  With two or three stages the lagging products of stage 0 feed the first CoM
+    // velocities directly.  Walking problems with pushes at N = 2, 3, 256 problems each, worst CoM velocity against the float64 oracle (profiles/horizon_ends.txt):
+    // device 1.9e-4 / 1.3e-4 / 1.2e-4 at 1e-6 (status 0), 4.9e-5 / 3.3e-5 / 1.9e-5 at 3e-7 for +0.4 .. 0.9 iterations; the CPU model over four seeds: up to 3.4e-4 at 1e-6,
+    // 1.0e-4 at 3e-7.  N = 4 and 7 are inside at 1e-6 (2.3e-5, 8.5e-6: the polish covers their stages).
     if (!(h->cfg.tolerance > 0)) h->cfg.tolerance = cmpc_default_tolerance(h->cfg.horizon);
     if (!(h->cfg.step_tolerance > 0)) h->cfg.step_tolerance = 100.0 * h->cfg.tolerance;
     // 0.05 x tolerance: the same iteration counts as tolerance / 10 (the barrier decreases superlinearly at the end)

@@ -37,7 +37,7 @@ def _c_config(cfg: CentroidalMPCConfig, tolerance=None, mu_min=None, max_iterati
     c.max_iterations = max_iterations or cfg.ipopt_max_iteration
     # the reference's ipopt_tolerance (1e-4 / 1e-2) is looser than the parity target; the GPU
     # solver always converges at least to 1e-6 so that its answer is reproducible to 1e-4
-    # (0: the library's default -- 1e-6 up to N = 20, 3e-7 beyond; step tolerance and barrier floor follow it)
+    # (0: the library's default -- 1e-6 for N = 4 .. 20, 3e-7 beyond and for N <= 3; step tolerance and barrier floor follow it)
     # (the ini value only when it is tighter than that default, as in the C++ facade)
     if tolerance is None:
         tolerance = cfg.ipopt_tolerance if 0 < cfg.ipopt_tolerance < _capi.lib().cmpc_default_tolerance(cfg.N) else 0.0
@@ -91,6 +91,11 @@ class BatchSolver:
     @property
     def last_error(self) -> str:
         return self._lib.cmpc_last_error(self._h).decode()
+
+    @property
+    def factor_storage(self) -> str:
+        """"lds" / "hbm": the storage the handle's kernel variant uses (an "lds" request that does not fit is served from HBM)"""
+        return {1: "lds", 2: "hbm"}[self._lib.cmpc_factor_storage(self._h)]
 
     def solve_device(self, dP, dX0, dX=None, dInfo=None, stream=None, warm=False):
         """torch CUDA tensors float32: P[B,np], X0[B,nx] -> X[B,nx], info[B,8].  Launches on

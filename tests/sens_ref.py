@@ -98,6 +98,7 @@ class Sens:
         self.sigmax = float(max(self.sig_f.max(initial=0), self.sig_u.max(initial=0), self.sig_l.max(initial=0)))
         W = H.copy()
         Jf, Jb = J[self.fric], J[self.free]
+        self.JfT, self.JbT = np.ascontiguousarray(Jf.T), np.ascontiguousarray(Jb.T)   # (rhs runs once per parameter in vjp: not sliced out of J every call)
         W += Jf.T @ (self.sig_f[:, None] * Jf) + Jb.T @ ((self.sig_u + self.sig_l)[:, None] * Jb)
         JE = J[self.eq][:, self.keep]
         nk, ne = self.keep.size, self.eq.size
@@ -121,8 +122,8 @@ class Sens:
         lb1, ub1 = problem_nlp.bounds(self.cfg, p1)
         dg, dlb, dub = g1 - self.g, lb1 - self.lb, ub1 - self.ub
         rx = gx1 - self.gx0
-        rx = rx + self.J[self.fric].T @ (self.sig_f * dg[self.fric])
-        rx = rx + self.J[self.free].T @ (self.sig_u * (dg[self.free] - dub[self.free]) + self.sig_l * (dg[self.free] - dlb[self.free]))
+        rx = rx + self.JfT @ (self.sig_f * dg[self.fric])
+        rx = rx + self.JbT @ (self.sig_u * (dg[self.free] - dub[self.free]) + self.sig_l * (dg[self.free] - dlb[self.free]))
         db = 0.5 * (dlb + dub)
         rE = dg[self.eq] - db[self.eq]
         return np.concatenate([rx[self.keep], rE])

@@ -52,7 +52,8 @@ def driver(tmp_path_factory):
 
 def test_default_tolerance_rule():
     lib = cm._capi.lib()
-    assert [lib.cmpc_default_tolerance(n) for n in (2, 13, 20)] == [1e-6] * 3
+    assert [lib.cmpc_default_tolerance(n) for n in (4, 10, 13, 20)] == [1e-6] * 4
+    assert [lib.cmpc_default_tolerance(n) for n in (2, 3)] == [3e-7] * 2   # (two and three stages: no tail polish, the first velocities need it)
     assert [lib.cmpc_default_tolerance(n) for n in (21, 22, 30)] == [3e-7] * 3
 
 

@@ -59,20 +59,25 @@ def test_callbacks_match_reference_generated_code(which, golden_dir):
         _close(H[t], d["hess_nnz"][t])
 
 
-def test_callbacks_match_oracle_at_n20():
+def check_callbacks_against_oracle(cfg, P, X0):
+    """f, g, grad f, jac g and hess L of the kernel at perturbed points of the batch (P, X0) against oracle/nlp_ref.c, 1e-5 relative, in the
+    structure of cmpc_nlp_sparsity / cmpc_dims."""
+    import ctypes as C
     from oracle import oracle_lib as ol, problem_nlp
-    cfg, P, X0 = cm.synthetic.config3_external_push(4)
+    B = P.shape[0]
     rng = np.random.default_rng(5)
     X = (X0 + 0.05 * rng.normal(size=X0.shape)).astype(np.float32)
     P32 = P.astype(np.float32)
     L = cm.Layout(cfg.N)
-    LamG = rng.normal(size=(4, L.ng)).astype(np.float32)
+    LamG = rng.normal(size=(B, L.ng)).astype(np.float32)
     F, G, GF, J, H = _eval(cfg, X, P32, 0.7, LamG)
     oc = problem_nlp.oracle_cfg(cfg)
     nnzj, nnzh = 243 * cfg.N + 15, 348 * cfg.N - 36
+    d = [C.c_int() for _ in range(5)]
+    assert cm._capi.lib().cmpc_dims(cfg.N, *[C.byref(a) for a in d]) == 0 and (d[3].value, d[4].value) == (nnzj, nnzh)
     jr = np.empty(nnzj, np.int32); jc = np.empty(nnzj, np.int32); hr = np.empty(nnzh, np.int32); hc = np.empty(nnzh, np.int32)
     cm._capi.lib().cmpc_nlp_sparsity(cfg.N, jr.ctypes.data, jc.ctypes.data, hr.ctypes.data, hc.ctypes.data)
-    for b in range(4):
+    for b in range(B):
         x, p = X[b].astype(np.float64), P32[b].astype(np.float64)
         f, g = ol.nlp_fg(oc, x, p)
         _close(F[b], f); _close(G[b], g); _close(GF[b], ol.nlp_grad_f(oc, x, p))
@@ -82,6 +87,11 @@ def test_callbacks_match_oracle_at_n20():
         r, c, v = ol.nlp_hess(oc, x, p, 0.7, LamG[b].astype(np.float64))
         Hd = np.zeros((L.nx, L.nx)); np.add.at(Hd, (r, c), v)
         _close(H[b], Hd[hr, hc])
+
+
+def test_callbacks_match_oracle_at_n20():
+    cfg, P, X0 = cm.synthetic.config3_external_push(4)
+    check_callbacks_against_oracle(cfg, P, X0)
 
 
 def _grad(cfg, X, P, lam_f, LamG):
@@ -111,16 +121,22 @@ def test_nlp_grad_matches_reference_generated_code(which, golden_dir):
         assert (GP[0][d["grad_gamma_p"][t] == 0] == 0).all()
 
 
-def test_nlp_grad_matches_oracle_at_n20_and_n30():
+def check_nlp_grad_against_oracle(cfg, P, X0):
+    """cmpc_eval_nlp_grad_device at perturbed points of the batch (P, X0) against the oracle's nlp_grad, 1e-5 relative."""
     from oracle import oracle_lib as ol, problem_nlp
+    B = P.shape[0]
+    rng = np.random.default_rng(6)
+    X = (X0 + 0.05 * rng.normal(size=X0.shape)).astype(np.float32)
+    P32 = P.astype(np.float32)
+    LamG = rng.normal(size=(B, cm.Layout(cfg.N).ng)).astype(np.float32)
+    GX, GP = _grad(cfg, X, P32, -0.6, LamG)
+    oc = problem_nlp.oracle_cfg(cfg)
+    for b in range(B):
+        gx, gp = ol.nlp_grad(oc, X[b].astype(np.float64), P32[b].astype(np.float64), -0.6, LamG[b].astype(np.float64))
+        _close(GX[b], gx); _close(GP[b], gp)
+
+
+def test_nlp_grad_matches_oracle_at_n20_and_n30():
     for gen in (cm.synthetic.config3_external_push, cm.synthetic.config5_footstep_candidates):
         cfg, P, X0 = gen(4)
-        rng = np.random.default_rng(6)
-        X = (X0 + 0.05 * rng.normal(size=X0.shape)).astype(np.float32)
-        P32 = P.astype(np.float32)
-        LamG = rng.normal(size=(4, cm.Layout(cfg.N).ng)).astype(np.float32)
-        GX, GP = _grad(cfg, X, P32, -0.6, LamG)
-        oc = problem_nlp.oracle_cfg(cfg)
-        for b in range(4):
-            gx, gp = ol.nlp_grad(oc, X[b].astype(np.float64), P32[b].astype(np.float64), -0.6, LamG[b].astype(np.float64))
-            _close(GX[b], gx); _close(GP[b], gp)
+        check_nlp_grad_against_oracle(cfg, P, X0)

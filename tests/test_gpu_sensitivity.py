@@ -61,9 +61,14 @@ def _case(name):
 def test_kernel_matches_sens_ref_and_adjoint(name, factors):
     """JVP (several directions in one call) and VJP of the kernel against sens_ref at the kernel's own float32 (x, p, lam_g); the adjoint identity on
     the device outputs; status 0 and a small residual everywhere."""
-    import torch
     cfg, P, X0 = _case(name)
-    P32, X032 = P.astype(np.float32), X0.astype(np.float32)
+    check_sens_ref_and_adjoint(cfg, P.astype(np.float32), X0.astype(np.float32), factors, name)
+
+
+def check_sens_ref_and_adjoint(cfg, P32, X032, factors, name):
+    """The body of test_kernel_matches_sens_ref_and_adjoint on any batch: solve, then JVP (k = 9) and VJP against sens_ref on problems 0, 1 and
+    B - 1, the adjoint identity on every problem, REF / ADJ / RESID as above."""
+    import torch
     s, dP, dX, dI, lam = _solve(cfg, P32, X032, factors=factors)
     X, Lm, info = dX.cpu().numpy(), lam.cpu().numpy(), dI.cpu().numpy()
     assert (info[:, 5] == 0).all()
