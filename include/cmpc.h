@@ -388,6 +388,20 @@ int cmpc_solution_jvp_rot_device(cmpc_handle h, const float* dX, const float* dP
  * all three); dGradP and dGradModel are cmpc_solution_vjp_model_device's, bit for bit */
 int cmpc_solution_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, float* dGradP,
                                  double* dGradModel, double* dGradRot, float* dSens, void* stream);
+/* Cotangent columns: the VJP of k cotangents from ONE factorisation per problem.  dGradX[B][k][n_x] (k >= 1) -> dGradP[B][k][n_p] float,
+ * dGradModel[B][k][34] double, dGradRot[B][k][2][N][3] double (each may be NULL, not all three).  The adjoint solves run in chunks of 8 columns behind
+ * the one Riccati factorisation, as the JVP's columns do.  Column j is cmpc_solution_vjp_rot_device on cotangent j bit for bit -- and therefore
+ * cmpc_solution_vjp_device and cmpc_solution_vjp_model_device on their outputs -- whatever k and the column's place in it: every cotangent loses its own
+ * component along the internal-force direction with the single call's float32 rounding, and every reduction keeps the single call's order.
+ * dSens[B][CMPC_SENS] stays one row per problem: the status, the weak-row counts, the largest Sigma and the internal-force word are the problem's;
+ * word 1 is the largest relative residual over the k columns, each measured as its single call measures it; word 6 is the largest removed component
+ * over columns and fields.  A non-finite entry in any cotangent column flags the whole problem (status 2); a flagged problem gets zeros in every column
+ * of every output, its neighbours keep their bits.  Derivatives are those of the barrier form above, weakly active rows included.
+ * CMPC_ERR_ARG, before anything is queued: a NULL handle or input, k < 1, all three outputs NULL.  No workspace beyond
+ * cmpc_sensitivity_workspace_bytes (its eight column slots); sub-batches, the event ordering, per-problem models and the bit-for-bit independence of batch
+ * position, batch size, k and sub-batching as for the entries above. */
+int cmpc_solution_vjp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, int k, float* dGradP,
+                                  double* dGradModel, double* dGradRot, float* dSens, void* stream);
 /* dV* / domega [B][2][N][3] double at (x, lam_g); zeros for a row whose model broke the model rule.  At a double-support point the entries depend
  * on the internal force the solve returned, as the corner entries of dV* / dtheta do. */
 int cmpc_rotation_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradRot, void* stream);

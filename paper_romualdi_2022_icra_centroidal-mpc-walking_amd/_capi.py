@@ -227,7 +227,7 @@ EXPORTS = [
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
-    "cmpc_factor_storage",
+    "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
 ]
 
 _lib = None
@@ -317,6 +317,8 @@ def lib():
             L.cmpc_solution_vjp_rot_device.argtypes = [vp, fp, fp, fp, fp, fp, vp, vp, fp, vp]
             L.cmpc_rotation_value_gradient_device.argtypes = [vp, fp, fp, fp, vp, vp]
             L.cmpc_contacts_rotation_vjp_device.argtypes = [vp, i, d, vp, vp, vp, vp, vp]
+        if hasattr(L, "cmpc_solution_vjp_cols_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_solution_vjp_cols_device.argtypes = [vp, fp, fp, fp, fp, C.c_int, fp, vp, vp, fp, vp]
         L.cmpc_plant_step_jvp_device.argtypes = [vp, fp, fp, fp, d, i, vp, fp, fp, vp, vp, vp]
         L.cmpc_plant_step_vjp_device.argtypes = [vp, fp, fp, fp, d, i, vp, vp, fp, fp, vp, vp]
         L.cmpc_contacts_position_vjp_device.argtypes = [vp, i, d, i, i] + [vp] * 15

@@ -939,6 +939,18 @@ int cmpc_solution_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP
     return sensitivity(h, "cmpc_solution_vjp_rot_device", dX, dP, dLamG, nullptr, dGradX, 1, dGradP, dSens, stream, nullptr, dGradModel, nullptr, dGradRot);
 }
 
+// ---- cotangent columns (include/cmpc.h): k VJPs behind one factorisation per problem ----
+int cmpc_solution_vjp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, const float* dGradX, int k, float* dGradP,
+                                  double* dGradModel, double* dGradRot, float* dSens, void* stream)
+{
+    // (what needs no handle is refused ahead of the handle check, so the message says which refusal it was)
+    if (!dX || !dP || !dLamG || !dGradX) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_cols_device: null input (dX, dP, dLamG and dGradX are required)");
+    if (k < 1) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_cols_device: k must be >= 1");
+    if (!dGradP && !dGradModel && !dGradRot) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_cols_device: no output requested");
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_solution_vjp_cols_device: null handle");
+    return sensitivity(h, "cmpc_solution_vjp_cols_device", dX, dP, dLamG, nullptr, dGradX, k, dGradP, dSens, stream, nullptr, dGradModel, nullptr, dGradRot);
+}
+
 int cmpc_rotation_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, double* dGradRot, void* stream)
 {
     if (!h || !dX || !dP || !dLamG || !dGradRot) return fail(h, CMPC_ERR_ARG, "cmpc_rotation_value_gradient_device: null argument");

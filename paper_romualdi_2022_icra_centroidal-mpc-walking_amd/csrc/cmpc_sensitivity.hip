@@ -6,7 +6,8 @@
 //   1. one Riccati factorisation (backward), the control Hessian shifted by SENS_SHIFT on the force diagonal; per stage P_{k+1}, H^-1 and the
 //      gain K = -H^-1 G go to a per-handle HBM workspace (the stage matrices are rebuilt from x, p, lam_g wherever they are needed);
 //   2. per chunk of up to SENS_KC right-hand sides: a backward and a forward pass, then SENS_NREF steps of iterative refinement against the
-//      unshifted operator, then one pass that measures the relative residual.
+//      unshifted operator, then one pass that measures the relative residual.  The right-hand sides of a chunk are JVP directions or -- the cotangent
+//      columns of cmpc_solution_vjp_cols_device -- VJP cotangents, each bit for bit the single-column VJP on that cotangent.
 // Model directions (include/cmpc.h, "model directions"): the per-problem model theta adds right-hand-side terms (model_q / model_r / model_c) to the
 // JVP's columns, and the VJP contracts the same entries with its stored adjoint into 34 sums per problem (model_vjp).
 // Rotation directions (include/cmpc.h, "rotation directions"): one omega per foot and stage moves R along R [omega]x; rot_r / rot_c add its terms to the
@@ -561,13 +562,24 @@ struct PDir {
 
 // One column's right-hand side at stage k (k == N: q only) -- the caller's definition
 struct Rhs {
-    int mode;          // 0: JVP direction dp; 1: VJP gradient v (already projected)
-    const float* dir;  // mode 0: [KC][np] rows of this chunk (stride np); mode 1: [nx]
+    int mode;          // 0: JVP direction dp; 1: VJP gradient v (already projected); 2: VJP cotangent columns (projected where an entry is read)
+    const float* dir;  // mode 0: [KC][np] rows of this chunk (stride np); mode 1: [nx]; mode 2: [KC][nx] cotangents of this chunk as the caller gave them (stride nx)
     long long stride;
     const double* dmod;   // mode 0: [KC][34] model directions of this chunk, or null
     const double* drot;   // mode 0: [KC][2][N][3] rotation directions of this chunk, or null
     const double* proj;   // with dmod or drot: e3 (3, as internal_dir) then the KC components n^T r_x removed from the columns' force entries; null: none
+                          // mode 2: e3 then the KC components n^T v of the chunk's cotangents; null: no internal-force direction
+    double* cres;         // mode 2: per column the largest residual (KC) and the largest right-hand-side entry (KC) of the measuring pass; else null
 };
+
+// force entry (i < 24 of the control: foot i / 12, axis i % 3) of one cotangent column without its component s along the internal-force direction, rounded
+// to float32 as the single-column path rounds its projected copy of v
+__host__ __device__ inline float vjp_force_entry(float gv, double s, const double* e3, int i)
+{
+    float t = gv;
+    t -= s * (i < 12 ? e3[i % 3] : -e3[i % 3]);
+    return t;
+}
 
 // (q_k, r_k, c_k) of column j, written to q[39], r[30], c[39]; k == N: q only.  x0 (k == 0 only, if non-null): the initial state
 __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs& R, int j, int k, int e, double* q, double* r, double* c, double* x0)
@@ -619,7 +631,7 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
             r[i] = rv;
         }
     } else {
-        const float* v = R.dir;
+        const float* v = R.mode == 1 ? R.dir : R.dir + j * R.stride;
         if (e < SX) {
             double qv = 0.0;
             if (e < 9) qv = -(double)v[3 * (N + 1) * (e / 3) + 3 * k + e % 3];
@@ -635,7 +647,11 @@ __host__ __device__ inline void rhs_entry(const Prob& P, const Geo& g, const Rhs
             if (k < N) c[e] = 0.0;
         } else if (k < N) {
             const int i = e - SX;
-            r[i] = i < 24 ? -(double)v[L.oF(i / 12, (i % 12) / 3) + 3 * k + i % 3] : 0.0;
+            if (R.mode == 1 || i >= 24) r[i] = i < 24 ? -(double)v[L.oF(i / 12, (i % 12) / 3) + 3 * k + i % 3] : 0.0;
+            else {
+                const float gv = v[L.oF(i / 12, (i % 12) / 3) + 3 * k + i % 3];
+                r[i] = -(double)(R.proj ? vjp_force_entry(gv, R.proj[3 + j], R.proj, i) : gv);
+            }
         }
     }
 }
@@ -765,6 +781,8 @@ __host__ __device__ __attribute__((noinline)) void chunk_pass(const Team& T, con
     const int N = P.L.N;
     Geo& g = *S.g;
     double rmax = 0.0, bmax = 0.0;
+    const bool colmax = pass == 2 && R.cres != nullptr;   // (every stage starts with build_geo's barriers, which order the slots below too)
+    if (colmax) for (int e = T.tid; e < 2 * SENS_KC; e += T.nt) R.cres[e] = 0.0;
     // backward sweep: k = N (terminal), then N-1 .. 0
     for (int k = N; k >= 0; --k) {
         build_geo(T, P, k, g);
@@ -778,6 +796,17 @@ __host__ __device__ __attribute__((noinline)) void chunk_pass(const Team& T, con
             rhs_entry(P, g, R, j, k, i, S.q + CS * j, S.r + CS * j, S.c + CS * j, k == 0 ? S.lk + CS * j : nullptr);
         }
         SENS_SYNC();
+        if (colmax)   // per column: the same entries as bmax below (one thread per column; a maximum does not depend on the order)
+            for (int j = T.tid; j < nc; j += T.nt) {
+                double b = R.cres[SENS_KC + j];
+                for (int i = 0; i < SX; ++i) {
+                    b = fmax(b, fabs(S.q[CS * j + i]));
+                    if (k < N) b = fmax(b, fabs(S.c[CS * j + i]));
+                    if (k == 0) b = fmax(b, fabs(S.lk[CS * j + i]));
+                }
+                if (k < N) for (int i = 0; i < SU; ++i) b = fmax(b, fabs(S.r[CS * j + i]));
+                R.cres[SENS_KC + j] = b;
+            }
         for (int e = T.tid; e < nc * (SX + SU); e += T.nt) {
             const int j = e / (SX + SU), i = e % (SX + SU);
             double b = 0.0;
@@ -850,6 +879,17 @@ __host__ __device__ __attribute__((noinline)) void chunk_pass(const Team& T, con
                 rmax = fmax(rmax, fabs(v));
             }
             SENS_SYNC();
+            if (colmax)   // per column: the same entries as rmax above
+                for (int j = T.tid; j < nc; j += T.nt) {
+                    double r = R.cres[j];
+                    for (int i = 0; i < SX; ++i) {
+                        r = fmax(r, fabs(S.q[CS * j + i]));
+                        if (k < N) r = fmax(r, fabs(S.c[CS * j + i]));
+                        if (k == 0) r = fmax(r, fabs(S.lk[CS * j + i]));
+                    }
+                    if (k < N) for (int i = 0; i < SU; ++i) r = fmax(r, fabs(S.r[CS * j + i]));
+                    R.cres[j] = r;
+                }
         }
         if (pass == 2) continue;
         // Riccati: t = P_{k+1} c + p_{k+1}; h = r + B^T t; kff = -H^-1 h; p_k = q + A^T t + K^T h
@@ -1025,18 +1065,18 @@ __host__ __device__ inline bool sens_outside_subset(const Prob& P, int ct, int k
     return diff;
 }
 
-// the model part of one problem's VJP after its adjoint solve (W column 0): gmod[t] = -w^T r_t for the 34 fields, each a sum over the knots in a
+// the model part of one problem's VJP after its adjoint solve (W column col): gmod[t] = -w^T r_t for the 34 fields, each a sum over the knots in a
 // fixed order.  With the internal-force direction e3 (else null), r_t loses its component along n as the JVP's columns do: -w^T r_t + (n^T w)(n^T r_t)
 // (w itself can carry a component along n: v is projected in float32 and the shifted system amplifies what is left by 1 / CMPC_SENS_SHIFT), and the
 // largest relative component |n^T r_t| / |r_t| goes to rel.  Items (t, k) spread over the team, partial sums in the free dense area of LDS (part:
 // 3 x 34 (N+1) doubles).
-__host__ __device__ inline void model_vjp(const Team& T, const Prob& P, const Ws& W, const double* e3, double* part, double* gmod, double& rel,
+__host__ __device__ inline void model_vjp(const Team& T, const Prob& P, const Ws& W, int col, const double* e3, double* part, double* gmod, double& rel,
                                           double& nonfinite)
 {
     const int N = P.L.N, nk = N + 1, M = CMPC_MODEL_DOUBLES;
-    const double* xs = W.xs(0);
-    const double* ls = W.ls(0);
-    const double* us = W.us(0);
+    const double* xs = W.xs(col);
+    const double* ls = W.ls(col);
+    const double* us = W.us(col);
     for (int e = T.tid; e < M * nk; e += T.nt) {
         const int t = e / nk, k = e % nk;
         const MDir d{nullptr, t};
@@ -1093,14 +1133,14 @@ __host__ __device__ inline void model_jvp_proj(const Team& T, const Prob& P, con
     rel = fmax(rel, team_max(T, r));   // (team_max synchronises: proj is complete for every thread)
 }
 
-// the rotation part of one problem's VJP after its adjoint solve (W column 0): grot[c][k][a] = -w^T r of the unit direction, one item per (foot, stage,
+// the rotation part of one problem's VJP after its adjoint solve (W column col): grot[c][k][a] = -w^T r of the unit direction, one item per (foot, stage,
 // axis), each a fixed-order loop over the foot's 12 + 3 control entries and the stage's 9 dynamics entries.  With the internal-force direction e3 (else null) every r loses
 // its component along n, as model_vjp's do, and the largest relative component goes to rel.
-__host__ __device__ inline void rot_vjp(const Team& T, const Prob& P, const Ws& W, const double* e3, double* grot, double& rel, double& nonfinite)
+__host__ __device__ inline void rot_vjp(const Team& T, const Prob& P, const Ws& W, int col, const double* e3, double* grot, double& rel, double& nonfinite)
 {
     const int N = P.L.N;
-    const double* ls = W.ls(0);
-    const double* us = W.us(0);
+    const double* ls = W.ls(col);
+    const double* us = W.us(col);
     double nw = 0.0;
     if (e3)   // n^T w over the force entries u_k (one thread's loop, the same order in every thread)
         for (int k = 0; k < N; ++k)
@@ -1151,8 +1191,10 @@ __host__ __device__ inline void rot_jvp_proj(const Team& T, const Prob& P, const
     rel = fmax(rel, team_max(T, r));   // (team_max synchronises: proj is complete for every thread)
 }
 
-// ---- one problem: JVP (gx == null: k directions dir[k][np] (and dmod[k][34], or null) -> out[k][nx]) or VJP (gx[nx] -> out[np] (or null) and
-// gmod[34] (or null)); drot[k][2][N][3] (or null) joins the JVP's columns, grot[2][N][3] (or null) comes from the VJP's one adjoint solve ----
+// ---- one problem: JVP (gx == null: k directions dir[k][np] (and dmod[k][34], or null) -> out[k][nx]) or VJP (k cotangents gx[k][nx] -> out[k][np]
+// (or null) and gmod[k][34] (or null)); drot[k][2][N][3] (or null) joins the JVP's columns, grot[k][2][N][3] (or null) comes from the VJP's adjoint
+// solves.  The VJP's k == 1 keeps its projected copy of v in LDS (vproj); k > 1 runs in chunks as the JVP does, every column projected where its
+// entries are read (Rhs mode 2), and column j's outputs are the k == 1 call's on cotangent j bit for bit.  proj: 3 + 3 KC doubles ----
 __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, const Prob& P, const Ws& W, const Lds& S, const float* dir, const float* gx, int kdir,
                                             float* out, float* sens, float* vproj, const double* dmod, double* gmod, double* proj,
                                             const double* drot, double* grot)
@@ -1160,7 +1202,8 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     const CmpcIdx& L = P.L;
     const int N = L.N;
     const bool vjp = gx != nullptr;
-    const int nout = vjp ? (out ? L.np() : 0) : kdir * L.nx();
+    const bool cols = vjp && kdir > 1;
+    const long long nout = vjp ? (out ? (long long)kdir * L.np() : 0) : (long long)kdir * L.nx();
     // status 3: outside the supported subset, or a model that broke the model rule; status 2: input not finite
     double flag3 = 0.0, flag2 = 0.0;
     for (int e = T.tid; e < 2 * N; e += T.nt) if (sens_outside_subset(P, e / N, e % N)) flag3 = 1.0;
@@ -1168,7 +1211,7 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(P.x[e])) flag2 = 1.0;
     for (int e = T.tid; e < L.np(); e += T.nt) if (!__builtin_isfinite(P.p[e])) flag2 = 1.0;
     for (int e = T.tid; e < L.ng(); e += T.nt) if (!__builtin_isfinite(P.lam[e])) flag2 = 1.0;
-    if (vjp) { for (int e = T.tid; e < L.nx(); e += T.nt) if (!__builtin_isfinite(gx[e])) flag2 = 1.0; }
+    if (vjp) { for (long long e = T.tid; e < (long long)kdir * L.nx(); e += T.nt) if (!__builtin_isfinite(gx[e])) flag2 = 1.0; }
     else if (dir) { for (long long e = T.tid; e < (long long)kdir * L.np(); e += T.nt) if (!__builtin_isfinite(dir[e])) flag2 = 1.0; }
     if (dmod) for (int e = T.tid; e < kdir * CMPC_MODEL_DOUBLES; e += T.nt) if (!__builtin_isfinite(dmod[e])) flag2 = 1.0;
     if (drot) for (int e = T.tid; e < kdir * 6 * N; e += T.nt) if (!__builtin_isfinite(drot[e])) flag2 = 1.0;
@@ -1185,9 +1228,17 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     double nonfinite = 0.0, mrel = 0.0;
     if (status == 0.0) {
         Rhs R;
-        R.dmod = nullptr; R.drot = nullptr; R.proj = nullptr;
+        R.dmod = nullptr; R.drot = nullptr; R.proj = nullptr; R.cres = nullptr;
         int nchunks = 1;
-        if (vjp) {   // v with no component along the internal-force direction
+        if (cols) {   // the columns lose their component along the internal-force direction where rhs_entry reads them: e3 first, then one n^T v per column
+            R.mode = 2; R.stride = L.nx();
+            R.cres = proj + 3 + SENS_KC;
+            nchunks = (kdir + SENS_KC - 1) / SENS_KC;
+            if (has_e) {
+                if (T.tid == 0) for (int i = 0; i < 3; ++i) proj[i] = e3[i];
+                R.proj = proj;
+            }
+        } else if (vjp) {   // v with no component along the internal-force direction
             double s = 0.0;
             if (has_e) s = internal_dot(L, e3, gx);
             for (int e = T.tid; e < L.nx(); e += T.nt) vproj[e] = gx[e];
@@ -1209,8 +1260,13 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
             }
         }
         for (int ch = 0; ch < nchunks; ++ch) {
-            const int nc = vjp ? 1 : (kdir - ch * SENS_KC < SENS_KC ? kdir - ch * SENS_KC : SENS_KC);
-            if (!vjp) {
+            const int nc = kdir - ch * SENS_KC < SENS_KC ? kdir - ch * SENS_KC : SENS_KC;
+            if (cols) {
+                R.dir = gx + (size_t)ch * SENS_KC * L.nx();
+                SENS_SYNC();   // (the previous chunk's readers of proj are done)
+                if (has_e) for (int j = T.tid; j < nc; j += T.nt) proj[3 + j] = internal_dot(L, e3, R.dir + (size_t)j * L.nx());
+                SENS_SYNC();
+            } else if (!vjp) {
                 R.dir = dir ? dir + (size_t)ch * SENS_KC * L.np() : nullptr;
                 R.dmod = dmod ? dmod + (size_t)ch * SENS_KC * CMPC_MODEL_DOUBLES : nullptr;
                 R.drot = drot ? drot + (size_t)ch * SENS_KC * 6 * N : nullptr;
@@ -1221,7 +1277,9 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
             chunk_pass(T, P, W, S, R, nc, 0, rn, bn);
             for (int it = 0; it < SENS_NREF; ++it) chunk_pass(T, P, W, S, R, nc, 1, rn, bn);
             chunk_pass(T, P, W, S, R, nc, 2, rn, bn);
-            resid = fmax(resid, bn > 0.0 ? rn / bn : 0.0);
+            if (cols)   // per column, as the single calls measure it
+                for (int j = 0; j < nc; ++j) resid = fmax(resid, R.cres[SENS_KC + j] > 0.0 ? R.cres[j] / R.cres[SENS_KC + j] : 0.0);
+            else resid = fmax(resid, bn > 0.0 ? rn / bn : 0.0);
             // outputs of the chunk
             if (!vjp) {
                 for (int e = T.tid; e < nc * L.nx(); e += T.nt) {
@@ -1255,12 +1313,14 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
                                     o[L.oF(c, jj) + r] = (float)((double)o[L.oF(c, jj) + r] - s * (c == 0 ? e3[r % 3] : -e3[r % 3]));
                     }
                 SENS_SYNC();
-            } else {
-                const double* xs = W.xs(0);
-                const double* ls = W.ls(0);
-                const double* us = W.us(0);
+            } else for (int jc = 0; jc < nc; ++jc) {   // column jc of the chunk: the contraction with dr/dp, then the model and rotation parts
+                const double* xs = W.xs(jc);
+                const double* ls = W.ls(jc);
+                const double* us = W.us(jc);
                 const CmpcConsts& K = *P.K;
                 const double dt = K.dt;
+                const size_t col = (size_t)ch * SENS_KC + jc;
+                float* outc = out ? out + col * L.np() : nullptr;
                 for (int e = T.tid; e < L.np(); e += T.nt) {
                     double v = 0.0;
                     if (e >= L.pCom0()) {
@@ -1318,11 +1378,15 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
                         }
                     }
                     if (!__builtin_isfinite(v)) nonfinite = 1.0;
-                    if (out) out[e] = (float)v;
+                    if (outc) outc[e] = (float)v;
                 }
                 SENS_SYNC();
-                if (gmod) model_vjp(T, P, W, has_e ? e3 : nullptr, S.P, gmod, mrel, nonfinite);
-                if (grot) rot_vjp(T, P, W, has_e ? e3 : nullptr, grot, mrel, nonfinite);
+                if (gmod) {
+                    double rel = 0.0;
+                    model_vjp(T, P, W, jc, has_e ? e3 : nullptr, S.P, gmod + col * CMPC_MODEL_DOUBLES, rel, nonfinite);
+                    mrel = fmax(mrel, rel);
+                }
+                if (grot) rot_vjp(T, P, W, jc, has_e ? e3 : nullptr, grot + col * 6 * N, mrel, nonfinite);
             }
         }
         if (!__builtin_isfinite(resid)) nonfinite = 1.0;
@@ -1331,8 +1395,9 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     }
     if (status != 0.0) {
         for (long long e = T.tid; e < nout; e += T.nt) out[e] = 0.f;
-        if (gmod) for (int e = T.tid; e < CMPC_MODEL_DOUBLES; e += T.nt) gmod[e] = 0.0;
-        if (grot) for (int e = T.tid; e < 6 * N; e += T.nt) grot[e] = 0.0;
+        const int kout = vjp ? kdir : 1;
+        if (gmod) for (int e = T.tid; e < kout * CMPC_MODEL_DOUBLES; e += T.nt) gmod[e] = 0.0;
+        if (grot) for (int e = T.tid; e < kout * 6 * N; e += T.nt) grot[e] = 0.0;
         resid = 0.0;
         mrel = 0.0;
     }
@@ -1345,7 +1410,8 @@ __host__ __device__ __attribute__((noinline)) void sens_problem(const Team& T, c
     }
 }
 
-// LDS of the kernel: constants | x | p | lam (floats) | v projected (floats) | Geo | dense doubles | 4 reduction doubles | KC + 3 projection doubles
+// LDS of the kernel: constants | x | p | lam (floats) | v projected (floats) | Geo | dense doubles | 4 reduction doubles | KC + 3 projection doubles |
+// 2 KC doubles of per-column residuals (Rhs::cres)
 __host__ __device__ inline size_t sens_lds_floats(int N)
 {
     const CmpcIdx L{N};
@@ -1353,7 +1419,7 @@ __host__ __device__ inline size_t sens_lds_floats(int N)
 }
 inline size_t sens_lds_bytes(int N)
 {
-    return sens_lds_floats(N) * 4 + ((sizeof(Geo) + 15) & ~(size_t)15) + 8 * (size_t)(Lds::doubles() + 4 + SENS_KC + 3);
+    return sens_lds_floats(N) * 4 + ((sizeof(Geo) + 15) & ~(size_t)15) + 8 * (size_t)(Lds::doubles() + 4 + 3 * SENS_KC + 3);
 }
 
 // carves the dense area: the factorisation's eight matrices; the column slots overlay PA, PB, Y (12 x 40 x 8 = 3840 doubles <= their 3861)
@@ -1417,8 +1483,9 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
     const Lds S = carve(dense, g);
     float* sens = Sens ? Sens + (size_t)b * CMPC_SENS : nullptr;
     if (GradX)
-        sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * L.nx(), 1, Out ? Out + (size_t)b * L.np() : nullptr, sens, vproj, nullptr,
-                     GradModel ? GradModel + (size_t)b * CMPC_MODEL_DOUBLES : nullptr, proj, nullptr, GradRot ? GradRot + (size_t)b * 6 * N : nullptr);
+        sens_problem(T, P, W, S, nullptr, GradX + (size_t)b * kdir * L.nx(), kdir, Out ? Out + (size_t)b * kdir * L.np() : nullptr, sens, vproj, nullptr,
+                     GradModel ? GradModel + (size_t)b * kdir * CMPC_MODEL_DOUBLES : nullptr, proj, nullptr,
+                     GradRot ? GradRot + (size_t)b * kdir * 6 * N : nullptr);
     else
         sens_problem(T, P, W, S, Dir ? Dir + (size_t)b * kdir * L.np() : nullptr, nullptr, kdir, Out + (size_t)b * kdir * L.nx(), sens, vproj,
                      DirModel ? DirModel + (size_t)b * kdir * CMPC_MODEL_DOUBLES : nullptr, nullptr, proj,
@@ -1429,7 +1496,8 @@ __global__ __launch_bounds__(256) void cmpc_sensitivity_kernel(const CmpcConsts*
 extern "C" size_t cmpc_sensitivity_workspace_bytes(int N) { return sizeof(double) * (size_t)Ws::doubles(N); }
 
 // problems [b0, b0 + nb) of the batch; the workspace holds nb problems.  JVP (dGradX null): dDir and dDirModel (each may be null), dOut = dx.
-// VJP: dOut = dl/dp (or null), dGradModel = dl/dtheta (or null), dGradRot = dl/domega (or null).  dDirRot: the JVP's rotation directions (or null).
+// VJP (kdir cotangent columns in dGradX[.][kdir][nx]): dOut = dl/dp (or null), dGradModel = dl/dtheta (or null), dGradRot = dl/domega (or null), each
+// [.][kdir][..].  dDirRot: the JVP's rotation directions (or null).
 extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
                                        const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
                                        double* dGradModel, const double* dDirRot, double* dGradRot, hipStream_t stream)

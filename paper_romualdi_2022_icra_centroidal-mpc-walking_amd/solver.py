@@ -433,6 +433,54 @@ class BatchSolver:
                              "cmpc_solution_vjp_rot_device")
         return out_rot, out_model, out_p, sens
 
+    # ---- cotangent columns: k VJPs behind one factorisation per problem (include/cmpc.h, "Cotangent columns") ----
+    def solution_vjp_cols_device(self, dX, dP, dLamG, dGradX, grad_p=True, grad_model=False, grad_rot=False, out_p=None, out_model=None, out_rot=None,
+                                 sens=None):
+        """(dx*/d(p, theta, omega))^T applied to k cotangents from one factorisation: dGradX[B, k, n_x] float32 -> (dl/dp [B, k, n_p] float32,
+        dl/dtheta [B, k, 34] float64, dl/domega [B, k, 2, N, 3] float64, sens[B, CMPC_SENS]); an output that was not requested is None.  Column j
+        equals solution_vjp_rot_device on dGradX[:, j] bit for bit.  sens is one row per problem: sens[:, 1] the largest residual over the columns,
+        sens[:, 6] the largest removed component over columns and fields; a non-finite entry in any column flags the whole problem (status 2, zeros
+        in every column)."""
+        import torch
+        L = self.layout
+        assert grad_p or grad_model or grad_rot, "solution_vjp_cols_device: no output requested"
+        assert dGradX.dim() == 3, "solution_vjp_cols_device: dGradX is [B, k, n_x]"
+        assert dGradX.dtype == torch.float32, "solution_vjp_cols_device: dGradX is float32"
+        assert dGradX.is_cuda and dGradX.is_contiguous() and tuple(dGradX.shape[::2]) == (self.batch, L.nx) and dGradX.shape[1] >= 1
+        k = int(dGradX.shape[1])
+        outs = []
+        for want, out, dt, tail in ((grad_p, out_p, torch.float32, (L.np,)), (grad_model, out_model, torch.float64, (_capi.MODEL_DOUBLES,)),
+                                    (grad_rot, out_rot, torch.float64, (2, L.N, 3))):
+            if want and out is None:
+                out = torch.empty((self.batch, k) + tail, dtype=dt, device=dX.device)
+            if not want:
+                out = None
+            if out is not None:
+                assert out.is_contiguous() and tuple(out.shape) == (self.batch, k) + tail and out.dtype == dt
+            outs.append(out)
+        pp, pm, pr = (t.data_ptr() if t is not None else None for t in outs)
+        sens = self._nlp_out(dX, dP, dLamG, sens, _capi.SENS,
+                             lambda st: lambda o: self._lib.cmpc_solution_vjp_cols_device(self._h, dX.data_ptr(), dP.data_ptr(), dLamG.data_ptr(),
+                                                                                          dGradX.data_ptr(), k, pp, pm, pr, o.data_ptr(), st),
+                             "cmpc_solution_vjp_cols_device")
+        return outs[0], outs[1], outs[2], sens
+
+    def policy_jacobian_device(self, dX, dP, dLamG, rows=None, model=False, rot=False):
+        """Rows of dx*/d(p, theta, omega): rows = indices into x (default: the 24 first-knot corner forces, in feedback_gain_device's row order,
+        that of Layout.first_forces) -> (J_p[B, len(rows), n_p] float32, J_model[B, len(rows), 34] float64 or None, J_rot[B, len(rows), 2, N, 3]
+        float64 or None, sens[B, CMPC_SENS]).  One unit cotangent per row through one solution_vjp_cols_device call: one factorisation per problem,
+        the rows in chunks of 8.  The derivatives are in the barrier form of DESIGN.md 7c, weakly active rows included; in double support the unit
+        cotangents lose their component along the internal-force direction, as every cotangent does."""
+        import torch
+        L = self.layout
+        if rows is None:
+            rows = np.concatenate([np.arange(L.f[c][j], L.f[c][j] + 3) for c in range(2) for j in range(4)])
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        assert rows.size >= 1 and rows.min() >= 0 and rows.max() < L.nx, "policy_jacobian_device: rows index x"
+        V = torch.zeros((self.batch, rows.size, L.nx), dtype=torch.float32, device=dX.device)
+        V[:, torch.arange(rows.size, device=dX.device), torch.as_tensor(rows, device=dX.device)] = 1.0
+        return self.solution_vjp_cols_device(dX, dP, dLamG, V, grad_p=True, grad_model=model, grad_rot=rot)
+
     def rotation_value_gradient_device(self, dX, dP, dLamG, out=None):
         """dV*/domega [B, 2, N, 3] float64 at a KKT point (x*, lam*): lam^T d_omega g (the cost does not depend on R).  At a double-support point
         the entries depend on the internal force the solve returned (include/cmpc.h)."""
