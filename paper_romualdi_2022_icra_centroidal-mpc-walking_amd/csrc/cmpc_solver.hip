@@ -180,6 +180,7 @@ typedef __attribute__((address_space(3))) const float* ldsf_t;
 typedef __attribute__((address_space(3))) float* ldsw_t;
 __device__ inline ldsf_t lds_opaque(const float* p) { ldsf_t q = (ldsf_t)p; asm volatile("" : "+v"(q)); return q; }
 __device__ inline ldsw_t lds_opaque_w(float* p) { ldsw_t q = (ldsw_t)p; asm volatile("" : "+v"(q)); return q; }
+__device__ inline ldsf_t lds_opaque_again(ldsf_t q) { asm volatile("" : "+v"(q)); return q; }   // (of a value that is an LDS address already)
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ inline float4 lds_ld4(ldsf_t p)
@@ -645,6 +646,41 @@ __device__ inline void all_geo(const Ctx& c, const CmpcConsts& prm, int tid)
     }
 }
 
+// the light kinds of defect() below, each on its own so that a pass can hand a whole wave one formula (phase_residuals): CoM position axis a, CoM velocity axis a,
+// position axis a of foot ct
+__device__ inline double defect_com(const Ctx& c, const CmpcConsts& prm, int k, int a)
+{
+    const float* s = c.S + NS * k;
+    const float* sn = c.S + NS * (k + 1);
+    const double dt = prm.dt;
+    return (double)s[a] + dt * (double)s[3 + a] - (double)sn[a];
+}
+__device__ inline double defect_vel(const Ctx& c, const CmpcConsts& prm, int k, int a)
+{
+    const float* s = c.S + NS * k;
+    const float* u = c.U + NU * k;
+    const float* sn = c.S + NS * (k + 1);
+    const double dt = prm.dt;
+    double acc = (double)c.sp[c.L.pFext() + 3 * k + a] - (a == 2 ? (double)prm.grav : 0.0);
+    for (int ct = 0; ct < 2; ++ct) {
+        const float* f = u + 12 * ct;
+        acc += (double)gam_of(c, ct, k) * ((double)f[a] + (double)f[3 + a] + (double)f[6 + a] + (double)f[9 + a]);
+    }
+    return (double)s[3 + a] + dt * acc - (double)sn[3 + a];
+}
+__device__ inline double defect_foot(const Ctx& c, const CmpcConsts& prm, int k, int ct, int a)
+{
+    const float* s = c.S + NS * k;
+    const float* u = c.U + NU * k;
+    const float* sn = c.S + NS * (k + 1);
+    const int i = 9 + 3 * ct + a;
+    const float* R = c.sp + c.L.pR(ct) + 9 * k;
+    const double gam = gam_of(c, ct, k);
+    double land = (double)c.sp[c.L.pNom(ct) + 3 * (k + 1) + a];
+    for (int m = 0; m < 3; ++m) land += (double)Rm(R, a, m) * (double)u[24 + 3 * ct + m];
+    return gam * (double)s[i] + (1.0 - gam) * land - (double)sn[i];
+}
+
 // dynamics defect component i of stage k in float64: phi_k(s_k,u_k)[i] - s_{k+1}[i]
 __device__ inline double defect(const Ctx& c, const CmpcConsts& prm, int k, int i)
 {
@@ -652,16 +688,8 @@ __device__ inline double defect(const Ctx& c, const CmpcConsts& prm, int k, int 
     const float* u = c.U + NU * k;
     const float* sn = c.S + NS * (k + 1);
     const double dt = prm.dt;
-    if (i < 3) return (double)s[i] + dt * (double)s[3 + i] - (double)sn[i];
-    if (i < 6) {
-        const int a = i - 3;
-        double acc = (double)c.sp[c.L.pFext() + 3 * k + a] - (a == 2 ? (double)prm.grav : 0.0);
-        for (int ct = 0; ct < 2; ++ct) {
-            const float* f = u + 12 * ct;
-            acc += (double)gam_of(c, ct, k) * ((double)f[a] + (double)f[3 + a] + (double)f[6 + a] + (double)f[9 + a]);
-        }
-        return (double)s[i] + dt * acc - (double)sn[i];
-    }
+    if (i < 3) return defect_com(c, prm, k, i);
+    if (i < 6) return defect_vel(c, prm, k, i - 3);
     if (i < 9) {
         const int a = i - 6, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
         double tor = (double)c.sp[c.L.pText() + 3 * k + a];
@@ -682,14 +710,7 @@ __device__ inline double defect(const Ctx& c, const CmpcConsts& prm, int k, int 
         }
         return (double)s[i] + dt * tor - (double)sn[i];
     }
-    {
-        const int ct = (i - 9) / 3, a = (i - 9) % 3;
-        const float* R = c.sp + c.L.pR(ct) + 9 * k;
-        const double gam = gam_of(c, ct, k);
-        double land = (double)c.sp[c.L.pNom(ct) + 3 * (k + 1) + a];
-        for (int m = 0; m < 3; ++m) land += (double)Rm(R, a, m) * (double)u[24 + 3 * ct + m];
-        return gam * (double)s[i] + (1.0 - gam) * land - (double)sn[i];
-    }
+    return defect_foot(c, prm, k, (i - 9) / 3, (i - 9) % 3);
 }
 
 // (B_k^T v)[m], closed form.  T = float or double
@@ -2564,6 +2585,21 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
     ldsf_t vN = lds_opaque(c.fpv + NS + fi), v3 = lds_opaque(c.fpv + 3 + fa), v6a = lds_opaque(c.fpv + 6 + fa1), v6b = lds_opaque(c.fpv + 6 + fa2);
     ldsf_t vq = lds_opaque(c.fpv + 9 + 3 * qct);
     ldsf_t hvj = lds_opaque(c.fpv + j), hve = lds_opaque(c.fpv + je), hv1 = lds_opaque(c.fpv + 6 + ja1), hv2 = lds_opaque(c.fpv + 6 + ja2);
+    // Resident form, compile-time horizons: a lane needs the operands of ONE role -- a force component (lanes 0..23), a landing offset (the rest of the lower half, on clamped indices) or
+    // a state row (upper half) -- but walks through all three formulas.  So the operand pointers are blended by role, set by set, and every formula reads the same
+    // registers: 11 LDS reads and 5 pointers less per stage than with a pointer set per role.  A lane's own formula sees exactly the operands it had; the others
+    // see another role's (finite) values and are not selected.  The upper half's operands (costates, force sums) are read at the head of the stage with the rest:
+    // nothing writes them before the stage's last store.
+    // (the runtime-N variant, a stage per trip, keeps a pointer set per role: the blend costs its set-up more than a 636-instruction function gains)
+    constexpr bool BLEND = !G && UNR > 1;
+    ldsf_t xa = rfp, xb = rfp, xc = rfp, wa = wp, wb = wp, y0 = vN, y1 = v3, y2 = v6a, y3 = v6b, z1 = rr1, z2 = rr2;
+    if (BLEND) {
+        xa = lds_opaque_again(isF ? rfp : rqp); xb = lds_opaque_again(isF ? rfp + 3 : rqp + 1); xc = lds_opaque_again(isF ? rfp + 6 : rqp + 2);
+        wa = lds_opaque_again(isF ? wp : wqp); wb = lds_opaque_again(isF ? wp + 2 : wqp + 5);      // (an offset's upper row at wa[0], its lower row at wb[1])
+        y0 = lds_opaque_again(half ? hvj : vN); y1 = lds_opaque_again(half ? hve : (isF ? v3 : vq)); y2 = lds_opaque_again(half ? hv1 : (isF ? v6a : vq + 1));
+        y3 = lds_opaque_again(half ? hv2 : (isF ? v6b : vq + 2));
+        z1 = lds_opaque_again(half ? hf1 : rr1); z2 = lds_opaque_again(half ? hf2 : rr2);
+    }
     ldsf_t gbp = lds_opaque(gb + 16 * half), lbp = lds_opaque(lb);
     ldsw_t gbs = lds_opaque_w(tid < NU ? gb + tid : trash + (tid & 7));
     ldsw_t lbs = lds_opaque_w(lb + r);
@@ -2575,6 +2611,7 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
     auto stage = [&](int o, int k) {      // o: strides above the trip's lowest stage
         float lm[16];
         float4 fm[8];
+        float lq0 = 0.f;
         if (G) {
             const RecRef<G> rec(c.Lf, N, k);
 #pragma unroll
@@ -2584,8 +2621,8 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         } else {
 #pragma unroll
             for (int t = 0; t < 16; ++t) lm[t] = lp[t][REC_N * o];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) fm[q] = lds_ld4(fpp[q] + REC_N * o);
+            lq0 = *lqs;       // (the lq entry that takes dl below: read with the stage's operands -- read where it is updated, it was a round trip of its own, waited
+                              //  for in full between the store of dl and the reads of dl)
         }
         const float gam0 = gm0[o], gam1 = gm1[o];
         const float dgam = gam1 - gam0;
@@ -2594,7 +2631,22 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         // (both forms on every lane, on clamped indices, and a select: the wave walks through both anyway, and a branch on the lane's role costs the exec-mask
         //  bookkeeping of two regions per stage)
         float g;
-        {
+        float hy0 = 0.f, hy1 = 0.f, hy2 = 0.f, hy3 = 0.f, hz1 = 0.f, hz2 = 0.f;   // (resident form: the upper half's operands, read here)
+        if (BLEND) {
+            const float w0 = wa[NI * o], w1 = wa[NI * o + 1], w2 = wb[NI * o], w3 = wb[NI * o + 1];
+            const float x1 = xa[9 * o], x2 = xb[9 * o], x3 = xc[9 * o];
+            hy0 = y0[0]; hy1 = y1[0]; hy2 = y2[0]; hy3 = y3[0]; hz1 = z1[GEO * o]; hz2 = z2[GEO * o];
+            const float wx = w0 - w1 - w2 + w3, wy = w0 + w1 - w2 - w3, ws = w0 + w1 + w2 + w3;
+            float gF = x1 * wx + x2 * wy - mu * x3 * ws;
+            gF += hy0 + dtc * fmaf(fsel, dgam, gam0) * (hy1 + hy2 * hz2 - hy3 * hz1);
+            const float fr = (float)((qmp[o] >> qq) & 1);
+            float gQ = w0 - w3;
+            gQ += fr * (1.f - fmaf(qsel, dgam, gam0)) * (x1 * hy1 + x2 * hy2 + x3 * hy3);
+            g = isF ? gF : gQ;
+            // (the state rows below take the same registers as values of their own: no product of the right-hand side is shared with theirs, so each expression
+            //  contracts into fused multiply-adds as it did on its own)
+            asm volatile("" : "+v"(hy0), "+v"(hy1), "+v"(hy2), "+v"(hy3), "+v"(hz1), "+v"(hz2));
+        } else {
             const float w0 = wp[NI * o], w1 = wp[NI * o + 1], w2 = wp[NI * o + 2], w3 = wp[NI * o + 3];
             // sum_f w_f R (sx_f, sy_f, -mu)^T,  (sx, sy) = (+,+), (-,+), (-,-), (+,-)
             const float wx = w0 - w1 - w2 + w3, wy = w0 + w1 - w2 - w3, ws = w0 + w1 + w2 + w3;
@@ -2612,6 +2664,12 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         float4 gv[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) gv[t] = lds_ld4(gbp + 4 * t);
+        if (!G) {
+            // (the fp-step's record rows are asked for here and not at the head of the stage: LDS answers in order, so at the head their 8 KB stood between the
+            //  right-hand side and its operands; behind the reads of g they arrive under the dl-step, and their 32 registers are not live through the right-hand side)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) fm[q] = lds_ld4(fpp[q] + REC_N * o);
+        }
         float la, lc;
         {
             // (packed multiply-add chains, as in forward_sweep)
@@ -2629,7 +2687,7 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         if (G) {
             if (tid < NU) { const RecRef<G> rec(c.Lf, N, k); const unsigned lo = wt_idx(15, tid); rec.st(lo, rec.ld(lo) + dl); }
         } else {
-            *lqs = *lqs + dl;
+            *lqs = lq0 + dl;
             lqs -= lqst;
         }
         wave_lds_sync();
@@ -2652,7 +2710,8 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         const float gamj = fmaf(hjsel, dgam, gam0);
         const float sj = fmaf(hposm, gamj - 1.f, 1.f);
         const float cg = fmaf(hcg1, gamj, hcg0);
-        const float hiv = sj * hvj[0] + hce * hve[0] + cg * (hv1[0] * hf2[GEO * o] - hv2[0] * hf1[GEO * o]) - sm;
+        const float hiv = !BLEND ? sj * hvj[0] + hce * hve[0] + cg * (hv1[0] * hf2[GEO * o] - hv2[0] * hf1[GEO * o]) - sm
+                            : sj * hy0 + hce * hy1 + cg * (hy2 * hz2 - hy3 * hz1) - sm;
         const float out = lom * (k > 0 ? Dm : 0.f) * sm + him * hiv;
         wave_lds_sync();
         *fps = out;
@@ -2666,8 +2725,20 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
 #pragma unroll
             for (int q = 0; q < 8; ++q) fpp[q] -= REC_N * n;
         }
-        wp -= NI * n; wqp -= NI * n; rfp -= 9 * n; rqp -= 9 * n; rr1 -= GEO * n; rr2 -= GEO * n; hf1 -= GEO * n; hf2 -= GEO * n;
+        if (!BLEND) { wp -= NI * n; wqp -= NI * n; rfp -= 9 * n; rqp -= 9 * n; rr1 -= GEO * n; rr2 -= GEO * n; hf1 -= GEO * n; hf2 -= GEO * n; }
+        else { wa -= NI * n; wb -= NI * n; xa -= 9 * n; xb -= 9 * n; xc -= 9 * n; z1 -= GEO * n; z2 -= GEO * n; }
         gm0 -= n; gm1 -= n; qmp -= n;
+        if (!G) {
+            // (opaque again, as in forward_sweep: otherwise the optimiser keeps the pointers of stage N-1 and re-adds a trip offset to every one of them at the head of
+            //  every trip -- 35 additions per trip and as many more live registers, which took the sweep 25 registers past the caller-saved set)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) asm volatile("" : "+v"(lp[t]));
+#pragma unroll
+            for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(fpp[q]));
+            if (BLEND) asm volatile("" : "+v"(wa), "+v"(wb), "+v"(xa), "+v"(xb), "+v"(xc), "+v"(z1), "+v"(z2));
+            else asm volatile("" : "+v"(wp), "+v"(wqp), "+v"(rfp), "+v"(rqp), "+v"(rr1), "+v"(rr2), "+v"(hf1), "+v"(hf2));
+            asm volatile("" : "+v"(gm0), "+v"(gm1), "+v"(qmp));
+        }
     };
     int k = N - 1;
     // (the stages that do not fill a trip first, one at a time)
@@ -2676,12 +2747,23 @@ __device__ __forceinline__ void delta_sweep(const Ctx& c, const CmpcConsts& prm,
         stage(0, k);
         bump(1);
     }
+    if (G) {
+        // (the HBM-factor form, held to 168 registers, keeps the two moves per trip it had: one move cost it four more callee-saved registers)
 #pragma unroll 1
-    for (; k >= UNR - 1; k -= UNR) {
-        bump(UNR - 1);               // to the trip's lowest stage
+        for (; k >= UNR - 1; k -= UNR) {
+            bump(UNR - 1);               // to the trip's lowest stage
 #pragma unroll
-        for (int i = 0; i < UNR; ++i) stage(UNR - 1 - i, k - i);
-        bump(1);                     // to the stage below the trip
+            for (int i = 0; i < UNR; ++i) stage(UNR - 1 - i, k - i);
+            bump(1);                     // to the stage below the trip
+        }
+    } else {
+        bump(UNR - 1);                   // to the lowest stage of the first trip
+#pragma unroll 1
+        for (; k >= UNR - 1; k -= UNR) {
+#pragma unroll
+            for (int i = 0; i < UNR; ++i) stage(UNR - 1 - i, k - i);
+            bump(UNR);                   // to the lowest stage of the next trip (past the start of the records behind the last trip: never dereferenced)
+        }
     }
 }
 // (no barrier: phase_delta takes it behind the sweep)
@@ -2981,12 +3063,36 @@ __device__ __attribute__((noinline)) Resid phase_residuals(lds_t lds, int Nrt, f
             l_chk += (float)dv;
         }
     }
-    for (int e = tid; e < 12 * N; e += NT) {
-        const int k = e / 12, ii = e - 12 * k, i = ii < 6 ? ii : ii + 3;
-        const double dv = defect(c, prm, k, i);
-        c.d[NS * k + i] = (float)dv;
-        l_ep = fmaxf(l_ep, fabsf((float)dv));
-        l_chk += (float)dv;
+    // The twelve light components: CoM position, CoM velocity, the position of either foot.  Resident variants with a compile-time horizon: a kind to a group of
+    // LGRP lanes (whole waves), axis-major inside it, so that every wave walks through ONE formula; the four groups sit on the highest threads, which up to N = 21 are
+    // the ones with a single row slot in use below (the lowest 12 N threads -- the ones with the most rows -- used to walk through all three formulas on top).  The
+    // defects feed the stores to c.d, two maxima and the NaN check sum only: which thread forms one does not show in the result.
+    constexpr int LGRP = (3 * NC + 63) / 64 * 64;
+    if constexpr (NC > 0 && !FG && 4 * LGRP <= NT) {
+        static_assert((LGRP & (LGRP - 1)) == 0, "the lane inside a group is taken with a mask");
+        const int tl = tid - (NT - 4 * LGRP);
+        const int grp = __builtin_amdgcn_readfirstlane(tl >= 0 ? tl / LGRP : -1);   // (uniform over a wave)
+        const int l = tl & (LGRP - 1);
+        if (grp >= 0 && l < 3 * NC) {
+            const int a = (l >= NC ? 1 : 0) + (l >= 2 * NC ? 1 : 0), k = l - NC * a;
+            double dv;
+            int i;
+            if (grp == 0) { i = a; dv = defect_com(c, prm, k, a); }
+            else if (grp == 1) { i = 3 + a; dv = defect_vel(c, prm, k, a); }
+            else { i = 9 + 3 * (grp - 2) + a; dv = defect_foot(c, prm, k, grp - 2, a); }
+            c.d[NS * k + i] = (float)dv;
+            l_ep = fmaxf(l_ep, fabsf((float)dv));
+            l_chk += (float)dv;
+        }
+    } else {
+        for (int e = tid; e < 12 * N; e += NT) {
+            const int k = e / 12, ii = e - 12 * k, i = ii < 6 ? ii : ii + 3;
+            // (by kind, not through defect(): its angular-momentum branch, never taken here, stood in every copy of this loop)
+            const double dv = ii < 3 ? defect_com(c, prm, k, ii) : (ii < 6 ? defect_vel(c, prm, k, ii - 3) : defect_foot(c, prm, k, ii < 9 ? 0 : 1, ii < 9 ? ii - 6 : ii - 9));
+            c.d[NS * k + i] = (float)dv;
+            l_ep = fmaxf(l_ep, fabsf((float)dv));
+            l_chk += (float)dv;
+        }
     }
     if constexpr (NC > 0) {
         // (the rows a kind at a time: see row_slot)
