@@ -2,6 +2,7 @@
 #include "../../include/cmpc.h"
 #include "cmpc_contacts.h"
 #include "cmpc_device.h"
+#include "cmpc_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,102 +12,6 @@
 #include <dlfcn.h>
 #include <string>
 #include <vector>
-
-extern "C" size_t cmpc_solver_lds_bytes(int N, int factors_global);
-extern "C" int cmpc_launch_solver(const CmpcParams* prm, size_t lds_bytes, hipStream_t stream);
-extern "C" int cmpc_prepare_solver(int N, int factors_global, size_t lds_bytes);
-extern "C" int cmpc_launch_nlp_eval(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG,
-                                    float lam_f, float* dF, float* dG, float* dGradF, float* dJac, float* dHess,
-                                    hipStream_t stream);
-extern "C" int cmpc_launch_nlp_grad(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float lam_f, float* dGradX,
-                                    float* dGradP, hipStream_t stream);
-extern "C" int cmpc_launch_multipliers(const CmpcParams* prm, const float* dX, const float* dP, float* dLamG, hipStream_t stream);
-extern "C" int cmpc_launch_kkt_certificate(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dCert, hipStream_t stream);
-extern "C" int cmpc_launch_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, float* dGradP, hipStream_t stream);
-extern "C" int cmpc_launch_sensitivity(const CmpcConsts* kc, int kc_per_problem, int N, int b0, int nb, const float* dX, const float* dP, const float* dLamG,
-                                       const float* dDir, const float* dGradX, int kdir, float* dOut, float* dSens, double* dWs, const double* dDirModel,
-                                       double* dGradModel, const double* dDirRot, double* dGradRot, hipStream_t stream);
-extern "C" int cmpc_launch_model_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradModel,
-                                                hipStream_t stream);
-extern "C" int cmpc_launch_rotation_value_gradient(const CmpcParams* prm, const float* dX, const float* dP, const float* dLamG, double* dGradRot,
-                                                   hipStream_t stream);
-extern "C" int cmpc_launch_contacts_rotation_vjp(int B, int N, int M, double dt, double now, const double* list_t, const int* list_n, const double* g_rot,
-                                                 double* g_list, hipStream_t stream);
-extern "C" int cmpc_launch_warm_shift(const CmpcParams* prm, const float* dXprev, float* dX0, hipStream_t stream);
-extern "C" int cmpc_launch_contacts_merge(int B, int M, double now, const double* plan_t, const float* plan_pose, const int* plan_n,
-                                          const double* mpc_t, const float* mpc_pose, const int* mpc_n, double* out_t, float* out_pose,
-                                          int* out_n, int* ok, hipStream_t stream);
-extern "C" int cmpc_launch_contacts_sample(int B, int N, int M, double dt, double now, const double* t, const float* pose, const int* n,
-                                           const float* box, float* P, int* land, hipStream_t stream);
-extern "C" int cmpc_launch_contacts_adjust(int B, int N, int M, double now, const float* X, const int* land, const double* t, float* pose,
-                                           const int* n, hipStream_t stream);
-extern "C" int cmpc_launch_write_state(int B, int N, const float* state, const float* wrench, float* P, hipStream_t stream);
-extern "C" int cmpc_launch_compact(int N, int B, const float* dX, const float* dInfo, float* dOut, hipStream_t stream);
-extern "C" int cmpc_launch_reference_from_planner(int B, int N, int n_in, double dt, double in_dt, double t_offset, double robot_mass, double com_height,
-                                                  const float* com_in, const float* h_in, float* P, hipStream_t stream);
-extern "C" int cmpc_launch_reference_vjp(const CmpcRefArgs* a, const int* end_tick, const float* grad_p, double* grad_com, double* grad_h, hipStream_t stream);
-extern "C" int cmpc_launch_reference_jvp(const CmpcRefArgs* a, const double* dir_com, const double* dir_h, float* dir_p, hipStream_t stream);
-extern "C" int cmpc_launch_tick_pre(int B, int N, int M, double dt, double now, int merge, const double* plan_t, const float* plan_pose, const int* plan_n,
-                                    const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n, int* ok,
-                                    int* land, const float* box, const float* state, const float* wrench, float* P, const float* Xprev, float* X0,
-                                    const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double plan_t_offset, double robot_mass,
-                                    double com_height, long long snap_dt_ns, const int* snap_ok, const int* ended, const float* noise, hipStream_t stream);
-extern "C" int cmpc_launch_force_sample_time(int B, int M, long long dt_ns, const double* t, const int* n, double* out_t, int* ok, int ok_per_foot,
-                                             const int* ended, hipStream_t stream);
-extern "C" int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
-                                     const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy, const int* land,
-                                     const double* t, float* pose, const int* n, const int* ended, const float* hidden, const float* gain, hipStream_t stream);
-extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream);
-extern "C" int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
-                                        float* slack_min, hipStream_t stream);
-extern "C" int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);
-extern "C" int cmpc_launch_refill(const CmpcRefillArgs* a, int* next, hipStream_t stream);
-extern "C" int cmpc_launch_refill_init(const CmpcRefillArgs* a, int* next, hipStream_t stream);
-extern "C" int cmpc_launch_tick_pre_refill(int B, int N, int M, double dt, const double* plan_t, const float* plan_pose, const int* plan_n,
-                                           const double* prev_t, const float* prev_pose, const int* prev_n, double* list_t, float* list_pose, int* list_n,
-                                           int* ok, int* land, const float* box, const float* state, float* P, const float* Xprev, float* X0,
-                                           const float* plan_com, const float* plan_h, int plan_knots, double plan_dt, double robot_mass, double com_height,
-                                           long long snap_dt_ns, const int* ended, const int* start, const int* trial, int tick, const float* wrench_trials,
-                                           int wrench_ticks, int trials, double plan_t_first, float g8, const CmpcRefillTrialArgs* tr,
-                                           int offset, hipStream_t stream);
-extern "C" int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, const float* dCorners, int corners_stride, const float* dX,
-                                            const float* dP, const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
-                                            const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
-                                            const int* trial, const CmpcRefillTrialArgs* tr, int offset, hipStream_t stream);
-extern "C" int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream);
-extern "C" int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
-extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
-extern "C" int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
-extern "C" size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a);
-extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t stream);
-extern "C" size_t cmpc_walk_jvp_gate_wide_entries(const CmpcJvpGateArgs* a);
-extern "C" int cmpc_launch_plant_step(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
-                                      const float* dStateIn, float* dStateOut, float* dZmp, float h, int nsub, float zx, float zy,
-                                      const float* dHidden, const float* dGain, hipStream_t stream);
-
-extern "C" int cmpc_launch_plant_jvp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
-                                     const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
-                                     const double* dDirModel, const double* dDirRot0, double* dOut, hipStream_t stream);
-extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
-                                     const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
-                                     double* dGradModel, double* dGradRot0, int mismatch, const float* dHidden, const float* dGain, double* dGradHidden,
-                                     double* dGradGain, hipStream_t stream);
-extern "C" int cmpc_launch_contacts_orientation_vjp(int B, int N, int M, double dt, double now, long long snap_dt_ns, const double* plan_t, const int* plan_n,
-                                                    const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
-                                                    const int* ok, const double* g_out, const double* g_rot, double* g_prev, double* g_plan, int* status,
-                                                    hipStream_t stream);
-extern "C" int cmpc_launch_contacts_position_vjp(int B, int N, int M, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
-                                                 const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n,
-                                                 const int* land, const int* ok, const double* g_out, const float* g_p, float* g_x, double* g_prev,
-                                                 double* g_plan, int* status, hipStream_t stream);
-
-extern "C" int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
-                                          const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
-                                          const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream);
-extern "C" int cmpc_launch_contacts_jvp(int B, int N, int M, int K, double dt, double now, int phase, long long snap_dt_ns, const double* plan_t,
-                                        const int* plan_n, const double* prev_t, const int* prev_n, const double* list_t, const int* list_n, const int* land,
-                                        const int* ok, const double* d_prev, const double* d_prev_rot, const double* d_plan, const double* d_plan_rot,
-                                        const float* d_x, double* d_list, double* d_list_rot, float* d_p, double* d_rot, int* status, hipStream_t stream);
 
 struct cmpc_handle_s {
     cmpc_config cfg;
@@ -184,6 +89,15 @@ static int fail(cmpc_handle h, int code, const std::string& msg)
         if (e_ != hipSuccess)                                                                 \
             return fail(h, CMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
     } while (0)
+
+// the stream of a call: the caller's, or the handle's
+static hipStream_t stream_of(cmpc_handle h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
+
+// a launcher's return code as the entry point's: CMPC_OK, or CMPC_ERR_HIP with "<what> launch: <the HIP error string>"
+static int launch_status(cmpc_handle h, const char* what, int rc)
+{
+    return rc == 0 ? CMPC_OK : fail(h, CMPC_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc));
+}
 
 static void fill_consts(cmpc_handle h, CmpcConsts& q);
 
@@ -424,7 +338,7 @@ static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, f
 {
     if (!h || !dP || !dX0 || !dX) return fail(h, CMPC_ERR_ARG, "cmpc_solve_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     CmpcParams p;
     fill_params(h, p);
     p.P = dP; p.X0 = dX0; p.X = dX; p.info = dInfo ? dInfo : h->dInfo;
@@ -434,7 +348,7 @@ static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, f
     }
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev0, st));
     int rc = cmpc_launch_solver(&p, h->lds, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("solver launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "solver", rc)) return err;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev1, st));
     h->timed = h->timing;
     return CMPC_OK;
@@ -678,7 +592,7 @@ int cmpc_advance(cmpc_handle h)
         if (h->warm) { p.mu_init = (float)h->mu_warm; p.mu_adapt = 0.f; p.t_floor = (float)h->floor_warm; p.warm = 1; }
         if (h->timing) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
         int lrc = cmpc_launch_solver(&p, h->lds, h->stream);
-        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("solver launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (const int err = launch_status(h, "solver", lrc)) return err;
         if (h->timing) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
         h->timed = h->timing;
         h->warm = false;
@@ -773,9 +687,8 @@ int cmpc_eval_nlp_device(cmpc_handle h, const float* dX, const float* dP, const 
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_nlp_eval(&p, dX, dP, dLamG, lam_f, dF, dG, dGradF, dJac, dHess, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("nlp eval launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_nlp_eval(&p, dX, dP, dLamG, lam_f, dF, dG, dGradF, dJac, dHess, stream_of(h, stream));
+    return launch_status(h, "nlp eval", rc);
 }
 
 int cmpc_eval_nlp_grad_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float lam_f, float* dGradX, float* dGradP,
@@ -785,9 +698,8 @@ int cmpc_eval_nlp_grad_device(cmpc_handle h, const float* dX, const float* dP, c
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_nlp_grad(&p, dX, dP, dLamG, lam_f, dGradX, dGradP, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("nlp grad launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_nlp_grad(&p, dX, dP, dLamG, lam_f, dGradX, dGradP, stream_of(h, stream));
+    return launch_status(h, "nlp grad", rc);
 }
 
 // ---- multipliers of the reference NLP (include/cmpc.h) ----
@@ -816,9 +728,8 @@ int cmpc_get_multipliers_device(cmpc_handle h, const float* dX, const float* dP,
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_multipliers(&p, dX, dP, dLamG, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("multipliers launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_multipliers(&p, dX, dP, dLamG, stream_of(h, stream));
+    return launch_status(h, "multipliers", rc);
 }
 
 int cmpc_get_multipliers(cmpc_handle h, float* LamG)
@@ -841,9 +752,8 @@ int cmpc_kkt_certificate_device(cmpc_handle h, const float* dX, const float* dP,
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_kkt_certificate(&p, dX, dP, dLamG, dCert, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("kkt certificate launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_kkt_certificate(&p, dX, dP, dLamG, dCert, stream_of(h, stream));
+    return launch_status(h, "kkt certificate", rc);
 }
 
 int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, const float* dLamG, float* dGradP, void* stream)
@@ -852,9 +762,8 @@ int cmpc_value_gradient_device(cmpc_handle h, const float* dX, const float* dP, 
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_value_gradient(&p, dX, dP, dLamG, dGradP, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("value gradient launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_value_gradient(&p, dX, dP, dLamG, dGradP, stream_of(h, stream));
+    return launch_status(h, "value gradient", rc);
 }
 
 // ---- solution sensitivities (include/cmpc.h; cmpc_sensitivity.hip) ----
@@ -865,7 +774,7 @@ static int sensitivity(cmpc_handle h, const char* name, const float* dX, const f
     HIPCHK(h, hipSetDevice(h->device));
     const int N = h->cfg.horizon, sb = h->B < CMPC_SENS_SUB_BATCH ? h->B : CMPC_SENS_SUB_BATCH;
     if (!h->dSensWs) HIPCHK(h, hipMalloc(&h->dSensWs, cmpc_sensitivity_workspace_bytes(N) * (size_t)sb));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const CmpcConsts* kc = h->models_set ? h->dModels : h->dConsts;
     // the workspace is the handle's: a call on another stream than the previous one is ordered after it
     if (!h->sens_ev) HIPCHK(h, hipEventCreateWithFlags(&h->sens_ev, hipEventDisableTiming));
@@ -874,7 +783,7 @@ static int sensitivity(cmpc_handle h, const char* name, const float* dX, const f
         const int nb = h->B - b0 < sb ? h->B - b0 : sb;
         int rc = cmpc_launch_sensitivity(kc, h->models_set ? 1 : 0, N, b0, nb, dX, dP, dLamG, dDirP, dGradX, k, dOut, dSens, h->dSensWs, dDirModel,
                                          dGradModel, dDirRot, dGradRot, st);
-        if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString((hipError_t)rc));
+        if (const int err = launch_status(h, name, rc)) return err;
     }
     HIPCHK(h, hipEventRecord(h->sens_ev, st));
     return CMPC_OK;
@@ -917,9 +826,8 @@ int cmpc_model_value_gradient_device(cmpc_handle h, const float* dX, const float
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_model_value_gradient(&p, dX, dP, dLamG, dGradModel, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("model value gradient launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_model_value_gradient(&p, dX, dP, dLamG, dGradModel, stream_of(h, stream));
+    return launch_status(h, "model value gradient", rc);
 }
 
 // ---- derivatives with respect to the stage rotations (include/cmpc.h, "rotation directions") ----
@@ -957,9 +865,8 @@ int cmpc_rotation_value_gradient_device(cmpc_handle h, const float* dX, const fl
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_rotation_value_gradient(&p, dX, dP, dLamG, dGradRot, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("rotation value gradient launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_rotation_value_gradient(&p, dX, dP, dLamG, dGradRot, stream_of(h, stream));
+    return launch_status(h, "rotation value gradient", rc);
 }
 
 int cmpc_contacts_rotation_vjp_device(cmpc_handle h, int max_contacts, double now, const double* dT, const int* dN, const double* dGradRot,
@@ -968,9 +875,8 @@ int cmpc_contacts_rotation_vjp_device(cmpc_handle h, int max_contacts, double no
     if (!h || max_contacts < 1 || !dT || !dN || !dGradRot || !dGradListRot) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_rotation_vjp_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_contacts_rotation_vjp(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, dT, dN, dGradRot, dGradListRot,
-                                               stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact rotation adjoint launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                               stream_of(h, stream));
+    return launch_status(h, "contact rotation adjoint", rc);
 }
 
 // ---- 8f-3: planner references -> MPC knots (CentroidalMPCBlock.cpp:525-577): angular momentum / mass, CoM height
@@ -1003,9 +909,8 @@ int cmpc_write_reference_from_planner_device(cmpc_handle h, const float* dComIn,
         return fail(h, CMPC_ERR_ARG, "cmpc_write_reference_from_planner_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_reference_from_planner(h->B, h->cfg.horizon, n_in, h->cfg.sampling_time, in_dt, t_offset, robot_mass, com_height, dComIn, dHIn, dP,
-                                                stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference resampling launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                                stream_of(h, stream));
+    return launch_status(h, "reference resampling", rc);
 }
 
 // ---- 8f-3 differentiated in the planner's trajectories (include/cmpc.h): the transpose of the resampling summed over the rows of a walk, and its image of
@@ -1073,9 +978,8 @@ int cmpc_reference_from_planner_vjp_device(cmpc_handle h, int tick0, int rows, c
         return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp_device: dGradP and one of dGradCom / dGradH are needed");
     if ((a.knots + 127) / 128 > 65535) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_vjp_device: too many knots for one launch");
     HIPCHK(h, hipSetDevice(h->device));
-    rc = cmpc_launch_reference_vjp(&a, dEndTick, dGradP, dGradCom, dGradH, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference VJP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    rc = cmpc_launch_reference_vjp(&a, dEndTick, dGradP, dGradCom, dGradH, stream_of(h, stream));
+    return launch_status(h, "reference VJP", rc);
 }
 
 int cmpc_reference_from_planner_jvp(int horizon, double sampling_time, int batch, int tick0, int rows, int k, const cmpc_planner_refs* pl,
@@ -1109,9 +1013,8 @@ int cmpc_reference_from_planner_jvp_device(cmpc_handle h, int tick0, int rows, i
     const double total = (double)rows * h->B * k * 6.0 * (h->cfg.horizon + 1);
     if (total / 256.0 > 2147483000.0) return fail(h, CMPC_ERR_ARG, "cmpc_reference_from_planner_jvp_device: too many entries for one launch");
     HIPCHK(h, hipSetDevice(h->device));
-    rc = cmpc_launch_reference_jvp(&a, dDirCom, dDirH, dDirP, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("reference JVP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    rc = cmpc_launch_reference_jvp(&a, dDirCom, dDirH, dDirP, stream_of(h, stream));
+    return launch_status(h, "reference JVP", rc);
 }
 
 // ---- 8f-4: plant step on the device (see cmpc_plant_step_kernel) ----
@@ -1123,9 +1026,8 @@ int cmpc_plant_step_mismatch_device(cmpc_handle h, const float* dX, const float*
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_step(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, dStateOut, dZmp, (float)step,
-                                    substeps, (float)zmp_half_x, (float)zmp_half_y, dHiddenWrench, dForceGain, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant step launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                    substeps, (float)zmp_half_x, (float)zmp_half_y, dHiddenWrench, dForceGain, stream_of(h, stream));
+    return launch_status(h, "plant step", rc);
 }
 
 int cmpc_plant_step_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, float* dStateOut, float* dZmp,
@@ -1142,9 +1044,8 @@ int cmpc_plant_step_jvp_rot_device(cmpc_handle h, const float* dX, const float* 
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_jvp_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_jvp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                   dDirState, dDirX, dDirP, dDirModel, dDirRot0, dDirStateOut, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant JVP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                   dDirState, dDirX, dDirP, dDirModel, dDirRot0, dDirStateOut, stream_of(h, stream));
+    return launch_status(h, "plant JVP", rc);
 }
 
 int cmpc_plant_step_jvp_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, const double* dDirState,
@@ -1162,9 +1063,8 @@ static int plant_vjp(cmpc_handle h, const float* dX, const float* dP, const floa
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_vjp(h->cfg.horizon, h->B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
                                    dGradStateOut, dGradState, dGradX, dGradP, dGradModel, dGradRot0, mismatch ? 1 : 0, dHiddenWrench, dForceGain, dGradHidden,
-                                   dGradGain, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant VJP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                   dGradGain, stream_of(h, stream));
+    return launch_status(h, "plant VJP", rc);
 }
 
 int cmpc_plant_step_vjp_rot_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps,
@@ -1194,9 +1094,8 @@ int cmpc_compact_output_device(cmpc_handle h, const float* dX, const float* dInf
 {
     if (!h || !dX || !dInfo || !dOut) return fail(h, CMPC_ERR_ARG, "cmpc_compact_output_device: null pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_compact(h->cfg.horizon, h->B, dX, dInfo, dOut, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("compact output launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_compact(h->cfg.horizon, h->B, dX, dInfo, dOut, stream_of(h, stream));
+    return launch_status(h, "compact output", rc);
 }
 
 // ---- 8f-1: contact schedules, batched (logic: cmpc_contacts.h) ----
@@ -1226,7 +1125,7 @@ int cmpc_allgather_compact_device(cmpc_handle h, void* nccl_comm, int world_size
     nccl_allgather_fn ag = load_allgather(why);
     if (!ag) return fail(h, CMPC_ERR_HIP, "cmpc_allgather_compact_device: " + why);
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     const size_t count = (size_t)h->B * (size_t)(3 * (h->cfg.horizon + 1) + 38);   // floats of this rank's compact records (cmpc_compact_output_device)
     const int rc = ag(dLocal, dAll, count, 7 /* ncclFloat32 */, nccl_comm, st);
     if (rc != 0) return fail(h, CMPC_ERR_HIP, "ncclAllGather failed with code " + std::to_string(rc));
@@ -1295,9 +1194,8 @@ int cmpc_contacts_merge_device(cmpc_handle h, int max_contacts, double now, cons
         return fail(h, CMPC_ERR_ARG, "cmpc_contacts_merge_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_contacts_merge(h->B, max_contacts, now, dPlanT, dPlanPose, dPlanN, dMpcT, dMpcPose, dMpcN, dOutT, dOutPose, dOutN, dOk,
-                                        stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact merge launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                        stream_of(h, stream));
+    return launch_status(h, "contact merge", rc);
 }
 
 // forceSampleTime (CentroidalMPCBlock.cpp:586-592): dt in integer nanoseconds, or 0 if it is not a usable grid
@@ -1335,9 +1233,8 @@ int cmpc_contacts_force_sample_time_device(cmpc_handle h, int max_contacts, doub
     const long long dt_ns = snap_dt_ns(dt);
     if (!h || max_contacts < 1 || dt_ns < 1 || !dT || !dN || !dOutT) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_force_sample_time_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, dT, dN, dOutT, dOk, 0, nullptr, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("forceSampleTime launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, dT, dN, dOutT, dOk, 0, nullptr, stream_of(h, stream));
+    return launch_status(h, "forceSampleTime", rc);
 }
 
 // ---- adjoint of the list path in the contacts' positions (include/cmpc.h; cmpc_contacts_position_vjp_kernel) ----
@@ -1360,9 +1257,8 @@ int cmpc_contacts_position_vjp_device(cmpc_handle h, int max_contacts, double no
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_contacts_position_vjp(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, phase, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
                                                dListN, dLand, dOk, dGradListOut, dGradP, dGradX, dGradPrevList, dGradPlan, dStatus,
-                                               stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact position VJP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                               stream_of(h, stream));
+    return launch_status(h, "contact position VJP", rc);
 }
 
 // ---- ... and in their orientations (include/cmpc.h; cmpc_contacts_orientation_vjp_kernel) ----
@@ -1383,9 +1279,8 @@ int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_contacts_orientation_vjp(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
                                                   dListN, dLand, dOk, dGradListRotOut, dGradRot, dGradPrevListRot, dGradPlanRot, dStatus,
-                                                  stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact orientation VJP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                                  stream_of(h, stream));
+    return launch_status(h, "contact orientation VJP", rc);
 }
 
 // the bounding boxes of the two contacts on the device (uploaded when they change)
@@ -1407,12 +1302,11 @@ int cmpc_contacts_sample_device(cmpc_handle h, int max_contacts, double now, con
 {
     if (!h || max_contacts < 1 || !dT || !dPose || !dN || !box_upper || !box_lower || !dP) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_sample_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     int rc = upload_box(h, box_upper, box_lower, st);
     if (rc != CMPC_OK) return rc;
     rc = cmpc_launch_contacts_sample(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, dT, dPose, dN, h->dBox, dP, dLand, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact sampling launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    return launch_status(h, "contact sampling", rc);
 }
 
 int cmpc_contacts_adjust_device(cmpc_handle h, int max_contacts, double now, const float* dX, const int* dLand, const double* dT, float* dPose,
@@ -1420,18 +1314,16 @@ int cmpc_contacts_adjust_device(cmpc_handle h, int max_contacts, double now, con
 {
     if (!h || max_contacts < 1 || !dX || !dLand || !dT || !dPose || !dN) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_adjust_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_contacts_adjust(h->B, h->cfg.horizon, max_contacts, now, dX, dLand, dT, dPose, dN, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("contact adjustment launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_contacts_adjust(h->B, h->cfg.horizon, max_contacts, now, dX, dLand, dT, dPose, dN, stream_of(h, stream));
+    return launch_status(h, "contact adjustment", rc);
 }
 
 int cmpc_write_state_device(cmpc_handle h, const float* dState, const float* dWrench, float* dP, void* stream)
 {
     if (!h || !dState || !dP) return fail(h, CMPC_ERR_ARG, "cmpc_write_state_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_write_state(h->B, h->cfg.horizon, dState, dWrench, dP, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("state write launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+    int rc = cmpc_launch_write_state(h->B, h->cfg.horizon, dState, dWrench, dP, stream_of(h, stream));
+    return launch_status(h, "state write", rc);
 }
 
 int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, void* stream)
@@ -1440,7 +1332,7 @@ int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, v
     HIPCHK(h, hipSetDevice(h->device));
     CmpcParams p;
     fill_params(h, p);
-    int rc = cmpc_launch_warm_shift(&p, dXprev, dX0, stream ? (hipStream_t)stream : h->stream);
+    int rc = cmpc_launch_warm_shift(&p, dXprev, dX0, stream_of(h, stream));
     if (rc != 0) return fail(h, CMPC_ERR_HIP, "warm-start shift launch failed");
     return CMPC_OK;   // (no state on the handle: the caller solves from dX0 with cmpc_solve_device_warm)
 }
@@ -1492,7 +1384,7 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
     if ((io->dPlanCom || io->dPlanH) && (!io->dPlanCom || !io->dPlanH || io->plan_knots < 2 || !(io->plan_dt > 0) || !(io->robot_mass > 0)))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: bad planner trajectory");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     const int* const ended = h->dEnded;   // cmpc_set_ended_device: every launch of the tick leaves out the problems it names (the solve reads it through fill_params)
     long long dt_ns = 0;
     if (io->force_sample_time) {
@@ -1517,7 +1409,7 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
         if (!h->dSnapOk) HIPCHK(h, hipMalloc(&h->dSnapOk, sizeof(int) * 2 * (size_t)h->B));
         const int lrc = merge ? cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dPlanT, io->dPlanN, h->dSnapT, h->dSnapOk, 1, ended, st)
                               : cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dListT, io->dListN, io->dListT, h->dSnapOk, 1, ended, st);
-        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (forceSampleTime) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (const int err = launch_status(h, "tick (forceSampleTime)", lrc)) return err;
         if (merge) plan_t = h->dSnapT;
         snap_ok = h->dSnapOk;
     }
@@ -1525,18 +1417,17 @@ static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int wa
                                    io->dPrevPose, io->dPrevN, io->dListT, io->dListPose, io->dListN, io->dOk, io->dLand, h->dBox, io->dState, io->dWrench, io->dP,
                                    warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
                                    io->com_height, dt_ns, snap_ok, ended, mm_noise, st);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (front) launch: ") + hipGetErrorString((hipError_t)lrc));
+    if (const int err = launch_status(h, "tick (front)", lrc)) return err;
     if (cold) {
         lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, ended, st);
-        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (cold start) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (const int err = launch_status(h, "tick (cold start)", lrc)) return err;
     }
     rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
     if (rc != CMPC_OK) return rc;
     lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
                                 (float)io->plant_step, io->plant_substeps, (float)io->zmp_half_x, (float)io->zmp_half_y, io->dLand, io->dListT, io->dListPose,
                                 io->dListN, ended, mm_hidden, mm_gain, st);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick (back) launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    return launch_status(h, "tick (back)", lrc);
 }
 
 int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream)
@@ -1592,8 +1483,7 @@ static int rollout_record_impl(cmpc_handle h, int tick, int row, const float* dX
     int* stats = rec->dStats ? rec->dStats + 6 * (size_t)row : nullptr;
     if (stats && clear_row) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(int) * 6, st));
     const int lrc = cmpc_launch_rollout_record(&a, stats, st);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("roll-out record launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    return launch_status(h, "roll-out record", lrc);
 }
 
 int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
@@ -1601,7 +1491,7 @@ int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX
 {
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_record_device: null handle");
     HIPCHK(h, hipSetDevice(h->device));
-    return rollout_record_impl(h, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, rec, stream ? (hipStream_t)stream : h->stream, true);
+    return rollout_record_impl(h, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, rec, stream_of(h, stream), true);
 }
 
 int cmpc_rollout_outcome_init_device(cmpc_handle h, const float* dState0, const cmpc_walk_record* rec, void* stream)
@@ -1610,18 +1500,16 @@ int cmpc_rollout_outcome_init_device(cmpc_handle h, const float* dState0, const 
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_outcome_init_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     const int lrc = cmpc_launch_outcome_init(h->B, dState0, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
-                                             rec->dBoxSlackMin, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("outcome init launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+                                             rec->dBoxSlackMin, stream_of(h, stream));
+    return launch_status(h, "outcome init", lrc);
 }
 
 int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* stream)
 {
     if (!h || !dP || !dX0) return fail(h, CMPC_ERR_ARG, "cmpc_cold_start_device: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, h->dEnded, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("cold start launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, h->dEnded, stream_of(h, stream));
+    return launch_status(h, "cold start", lrc);
 }
 
 // ---- the device tape (include/cmpc.h, cmpc_walk_tape): one row from what a tick left ----
@@ -1644,11 +1532,11 @@ static int rollout_tape_impl(cmpc_handle h, int max_contacts, int row, int parts
     if ((parts & 2) && (!h->mult_out || !h->dDuals))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: the multiplier output is off (cmpc_set_multiplier_output before the ticks)");
     HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const CmpcTapeArgs a{h->B, max_contacts, h->L.nx, h->L.np, row, parts, dX, dP, dInfo, dOk, dLand, dStateIn, dStateOut, dPlanT, dPlanN, dListT, dListN,
                          tape->dX, tape->dP, tape->dInfo, tape->dStates, tape->dOk, tape->dLand, tape->dPlanT, tape->dListT, tape->dPlanN, tape->dListN};
     const int lrc = cmpc_launch_rollout_tape(&a, st);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("roll-out tape launch: ") + hipGetErrorString((hipError_t)lrc));
+    if (const int err = launch_status(h, "roll-out tape", lrc)) return err;
     if (parts & 2) return cmpc_get_multipliers_device(h, dX, dP, tape->dLamG + (size_t)row * h->B * h->L.ng, stream);
     return CMPC_OK;
 }
@@ -1716,7 +1604,7 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the two sets of list buffers must not alias");
     if (rec && (row0 < 0 || (long long)row0 + ticks > rec->rows)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the record has too few rows");
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     int rc = upload_box(h, io->tick.box_upper, io->tick.box_lower, st);
     if (rc != CMPC_OK) return rc;
     if (rec && rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
@@ -1791,9 +1679,8 @@ int cmpc_rollout_refill_init_device(cmpc_handle h, const cmpc_walk_refill* refil
     CmpcRefillArgs a;
     if (!h || !refill_args(h->B, 0, nullptr, refill, nullptr, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_init_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_refill_init(&a, refill->dNext, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("refill init launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    const int lrc = cmpc_launch_refill_init(&a, refill->dNext, stream_of(h, stream));
+    return launch_status(h, "refill init", lrc);
 }
 
 int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* state_live)
@@ -1809,15 +1696,14 @@ static int rollout_refill_impl(cmpc_handle h, int tick_next, const cmpc_walk_rec
     CmpcRefillArgs a;
     if (!h || !rec || !refill_args(h->B, tick_next, rec, refill, dStateLive, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: bad argument");
     const int lrc = cmpc_launch_refill(&a, refill->dNext, st);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("refill launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    return launch_status(h, "refill", lrc);
 }
 
 int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, void* stream)
 {
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: null handle");
     HIPCHK(h, hipSetDevice(h->device));
-    return rollout_refill_impl(h, tick_next, rec, refill, dStateLive, stream ? (hipStream_t)stream : h->stream);
+    return rollout_refill_impl(h, tick_next, rec, refill, dStateLive, stream_of(h, stream));
 }
 
 static int ensure_models(cmpc_handle h);
@@ -1967,7 +1853,7 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
         if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: force_sample_time needs a sampling time of at least 1 ns");
     }
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    hipStream_t st = stream_of(h, stream);
     int rc = upload_box(h, k.box_upper, k.box_lower, st);
     if (rc != CMPC_OK) return rc;
     if (rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
@@ -2010,20 +1896,20 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
                 break;
             }
             const int rrc = cmpc_launch_refill_restore(&ra, st);
-            if (rrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill restore launch: ") + hipGetErrorString((hipError_t)rrc)); break; }
+            if ((rc = launch_status(h, "refill restore", rrc)) != CMPC_OK) break;
         }
         int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
                                               set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,
                                               k.plan_knots, k.plan_dt, k.robot_mass, k.com_height, dt_ns, h->dEnded, refill->dStartTick, refill->dTrial, tick,
                                               refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), tr,
                                               offset, st);
-        if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (front) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
+        if ((rc = launch_status(h, "refill tick (front)", lrc)) != CMPC_OK) break;
         rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, from ? nullptr : refill->dStartTick, tick);
         if (rc != CMPC_OK) break;
         lrc = cmpc_launch_tick_post_refill(B, N, max_contacts, h->cfg.sampling_time, (float)h->cfg.gravity, model_corners(h), corners_stride(h), k.dX, k.dP,
                                            k.dStateOut, k.dStateOut, k.dZmp, (float)k.plant_step, k.plant_substeps, (float)k.zmp_half_x, (float)k.zmp_half_y,
                                            k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, refill->dTrial, tr, offset, st);
-        if (lrc != 0) { rc = fail(h, CMPC_ERR_HIP, std::string("refill tick (back) launch: ") + hipGetErrorString((hipError_t)lrc)); break; }
+        if ((rc = launch_status(h, "refill tick (back)", lrc)) != CMPC_OK) break;
         CmpcRecordArgs a;
         // (the tick number an ending takes is tick - start[b]; with trials from a snapshot the whole-walk number offset + tick - start[b]: the offset goes in here)
         if (!h->box_set || !record_args(N, B, offset + tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {
@@ -2032,7 +1918,7 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
         }
         a.start = refill->dStartTick;
         lrc = cmpc_launch_rollout_record(&a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
-        if (lrc != 0) rc = fail(h, CMPC_ERR_HIP, std::string("refill walk record launch: ") + hipGetErrorString((hipError_t)lrc));
+        rc = launch_status(h, "refill walk record", lrc);
     }
     h->timing = timing;
     h->dEnded = ended_saved;
@@ -2101,9 +1987,8 @@ int cmpc_rollout_snapshot_device(cmpc_handle h, int max_contacts, int src_batch,
     if (!snapshot_args(h->cfg.horizon, h->B, src_batch, max_contacts, src, dst, dIndex, dOk, a))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_snapshot_device: bad argument (a NULL array, sizes, or a destination array that is also a source array)");
     HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_rollout_snapshot(&a, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("walk snapshot launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    const int lrc = cmpc_launch_rollout_snapshot(&a, stream_of(h, stream));
+    return launch_status(h, "walk snapshot", lrc);
 }
 
 // ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags
@@ -2194,7 +2079,7 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
         if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: force_sample_time needs a sampling time of at least 1 ns");
     }
     HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const int B = h->B, N = h->cfg.horizon;
     const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, nm = (size_t)B * CMPC_MODEL_DOUBLES;
     const size_t nr = (size_t)B * 6 * N, nr0 = (size_t)B * 6;
@@ -2217,7 +2102,7 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
                                    tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, rot ? grPlant : nullptr, mm ? 1 : 0,
                                    mm ? mm->hidden : nullptr, mm ? mm->gain : nullptr, mm && mm->g_hidden ? ghPlant : nullptr,
                                    mm && mm->g_gain ? ggPlant : nullptr, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "tick VJP (plant)", rc)) return err;
     if (dGradX) {
         hipLaunchKernelGGL(cmpc_axpy_float_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, nx, dGradX, gX);
         HIPCHK(h, hipGetLastError());
@@ -2225,7 +2110,7 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
     if (dGradListOut) {
         rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 1, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                                tape->dListT, tape->dListN, tape->dLand, tape->dOk, dGradListOut, nullptr, gX, nullptr, nullptr, nullptr, st);
-        if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (adjust) launch: ") + hipGetErrorString((hipError_t)rc));
+        if (const int err = launch_status(h, "tick VJP (adjust)", rc)) return err;
     }
     rc = rot ? cmpc_solution_vjp_rot_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, grSol, dTickSens, stream)
              : cmpc_solution_vjp_model_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, dTickSens, stream);
@@ -2236,12 +2121,12 @@ static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const
     HIPCHK(h, hipGetLastError());
     rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 2, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                            tape->dListT, tape->dListN, tape->dLand, okTick, dGradListOut, gpSol, nullptr, dGradPrevList, dGradPlan, nullptr, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (sample + merge) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "tick VJP (sample + merge)", rc)) return err;
     if (rot) {
         rc = cmpc_launch_contacts_orientation_vjp(B, N, max_contacts, h->cfg.sampling_time, now, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                                   tape->dListT, tape->dListN, tape->dLand, okTick, dGradListRotOut, grSol, dGradPrevListRot, dGradPlanRot,
                                                   nullptr, st);
-        if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick VJP (orientations) launch: ") + hipGetErrorString((hipError_t)rc));
+        if (const int err = launch_status(h, "tick VJP (orientations)", rc)) return err;
     }
     HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return CMPC_OK;
@@ -2306,9 +2191,8 @@ static CmpcGateArgs gate_rot_args_of(const cmpc_walk_gate_rot* g, int nx, int np
 static int gate_launch(cmpc_handle h, const CmpcGateArgs& a, void* stream)
 {
     HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream_of(h, stream));
+    return launch_status(h, "reverse walk (gate)", lrc);
 }
 
 static void gate_on_host(const CmpcGateArgs& a)
@@ -2387,7 +2271,7 @@ static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0,
     if (row0 == 0 && !tape->first_row_is_first_tick)
         return fail(h, CMPC_ERR_ARG, name + ": row 0 is not a first tick and has no row before it to take the previous lists from");
     HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const int B = h->B, N = h->cfg.horizon, M = max_contacts;
     const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nl = (size_t)B * 6 * M, nt = (size_t)B * 4 * M;
     if (!h->dWalkWs || h->walk_ws_M < M) {
@@ -2435,7 +2319,7 @@ static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0,
             a.gx_row = g->dGradX ? g->dGradX + rp * nx : nullptr;
         }
         const int lrc = cmpc_launch_walk_vjp_gate(&a, st);
-        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("reverse walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (const int err = launch_status(h, "reverse walk (gate)", lrc)) return err;
         if (i == 0) break;
         const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
         cmpc_tick_tape tt{};
@@ -2553,9 +2437,8 @@ int cmpc_plant_step_jvp_cols_device(cmpc_handle h, const float* dX, const float*
         return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_jvp_cols_device: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_plant_jvp_cols(h->cfg.horizon, h->B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                        dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("plant JVP (columns) launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                        dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, stream_of(h, stream));
+    return launch_status(h, "plant JVP (columns)", rc);
 }
 
 int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, int k, const double* dPlanT, const int* dPlanN,
@@ -2578,9 +2461,8 @@ int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int ph
     HIPCHK(h, hipSetDevice(h->device));
     int rc = cmpc_launch_contacts_jvp(h->B, h->cfg.horizon, max_contacts, k, h->cfg.sampling_time, now, phase, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
                                       dListN, dLand, dOk, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirX, dDirList, dDirListRot, dDirP, dDirRot,
-                                      dStatus, stream ? (hipStream_t)stream : h->stream);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("list JVP launch: ") + hipGetErrorString((hipError_t)rc));
-    return CMPC_OK;
+                                      dStatus, stream_of(h, stream));
+    return launch_status(h, "list JVP", rc);
 }
 
 // (shared by the public entry point and the forward walk, as tick_vjp is)
@@ -2605,7 +2487,7 @@ static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick
         if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: force_sample_time needs a sampling time of at least 1 ns");
     }
     HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const int B = h->B, N = h->cfg.horizon;
     const size_t cols = (size_t)B * k, nx = h->L.nx, np = h->L.np;
     if (k > h->tick_jvp_cols) {     // (hipFree waits for the device: no earlier call still reads the smaller workspace)
@@ -2636,7 +2518,7 @@ static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick
     int rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 1, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
                                       tape->dListT, tape->dListN, tape->dLand, tape->dOk, in->dDirPrevList, in->dDirPrevListRot, in->dDirPlan, in->dDirPlanRot,
                                       nullptr, out->dDirList, out->dDirListRot, dPF, dRot, nullptr, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (merge + sample) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "tick JVP (merge + sample)", rc)) return err;
     hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, st, N, in->dDirState, in->dDirWrench, in->dDirP, dPF);
     HIPCHK(h, hipGetLastError());
     rc = cmpc_solution_jvp_rot_device(h, tape->dX, tape->dP, tape->dLamG, dPF, in->dDirModel, dRot, k, dDX, dTickSens, stream);
@@ -2645,10 +2527,10 @@ static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick
     HIPCHK(h, hipGetLastError());
     rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 2, dt_ns, nullptr, nullptr, nullptr, nullptr, tape->dListT, tape->dListN,
                                   tape->dLand, okTick, nullptr, nullptr, nullptr, nullptr, dDX, out->dDirList, out->dDirListRot, nullptr, nullptr, nullptr, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (adjust) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "tick JVP (adjust)", rc)) return err;
     rc = cmpc_launch_plant_jvp_cols(N, B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
                                     tape->plant_substeps, dState, dDX, dPF, in->dDirModel, rot ? wsRot0 : nullptr, okTick, out->dDirStateOut, st);
-    if (rc != 0) return fail(h, CMPC_ERR_HIP, std::string("tick JVP (plant) launch: ") + hipGetErrorString((hipError_t)rc));
+    if (const int err = launch_status(h, "tick JVP (plant)", rc)) return err;
     HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return CMPC_OK;
 }
@@ -2698,9 +2580,8 @@ int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g
     if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate_device: batch and horizon must be the handle's");
     HIPCHK(h, hipSetDevice(h->device));
     const CmpcJvpGateArgs a = jvp_gate_args_of(g, h->L.nx);
-    const int lrc = cmpc_launch_walk_jvp_gate(&a, stream ? (hipStream_t)stream : h->stream);
-    if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("forward walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
-    return CMPC_OK;
+    const int lrc = cmpc_launch_walk_jvp_gate(&a, stream_of(h, stream));
+    return launch_status(h, "forward walk (gate)", lrc);
 }
 
 int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
@@ -2716,7 +2597,7 @@ int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int
     if (row0 == 0 && !tape->first_row_is_first_tick)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: row 0 is not a first tick and has no row before it to take the previous lists from");
     HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const hipStream_t st = stream_of(h, stream);
     const int B = h->B, N = h->cfg.horizon, M = max_contacts;
     const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nt = (size_t)B * 4 * M;
     const size_t cols = (size_t)B * k, nl = cols * 6 * M;
@@ -2761,7 +2642,7 @@ int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int
         a.first_list = a.first ? d->dCarryList : nullptr;
         a.first_list_rot = a.first ? curRot : nullptr;
         const int lrc = cmpc_launch_walk_jvp_gate(&a, st);
-        if (lrc != 0) return fail(h, CMPC_ERR_HIP, std::string("forward walk (gate) launch: ") + hipGetErrorString((hipError_t)lrc));
+        if (const int err = launch_status(h, "forward walk (gate)", lrc)) return err;
         if (i == ticks) break;
         const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
         cmpc_tick_tape tt{};
@@ -2898,7 +2779,7 @@ int cmpc_set_models_device(cmpc_handle h, const cmpc_model* dModels, int* dOk, v
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure_models(h);
     if (rc) return rc;
-    hipLaunchKernelGGL(cmpc_models_kernel, dim3((h->B + 255) / 256), dim3(256), 0, stream ? (hipStream_t)stream : h->stream, h->B, h->dConsts, h->dExpK,
+    hipLaunchKernelGGL(cmpc_models_kernel, dim3((h->B + 255) / 256), dim3(256), 0, stream_of(h, stream), h->B, h->dConsts, h->dExpK,
                        dModels, h->dModels, dOk);
     HIPCHK(h, hipGetLastError());
     h->models_set = true;

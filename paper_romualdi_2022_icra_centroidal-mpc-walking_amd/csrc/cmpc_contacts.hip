@@ -3,6 +3,7 @@
 // roll-out (solve -> plant -> merge -> sample -> shift, every tick) never leaves HBM, not because they are hot.
 // The logic itself is in cmpc_contacts.h, shared with the host entry points of the C ABI.
 #include "cmpc_contacts.h"
+#include "cmpc_launch.h"
 
 namespace {
 

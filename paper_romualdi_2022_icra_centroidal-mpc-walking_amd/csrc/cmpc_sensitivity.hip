@@ -14,6 +14,7 @@
 // JVP's columns, and the VJP contracts the same entries with its stored adjoint into 6 N sums per problem (rot_vjp).
 // No atomics: every reduction is a fixed tree or one thread's loop, so a problem's result depends on nothing but its own inputs.
 #include "cmpc_device.h"
+#include "cmpc_launch.h"
 
 #include <cmath>
 

@@ -40,6 +40,7 @@
 // The vector sweeps (forward, corrector right-hand side, costates) run on one wave without
 // workgroup barriers; the per-stage factors they read are stored transposed, a row per lane.
 #include "cmpc_device.h"
+#include "cmpc_launch.h"
 
 #include <cstdlib>
 #include <type_traits>
