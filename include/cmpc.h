@@ -1363,7 +1363,8 @@ int cmpc_rollout_tick_vjp_mismatch_device(cmpc_handle h, int max_contacts, doubl
  * tick then flags the problem and writes zeros in its dGradHidden / dGradNoise rows and adds nothing to dGradGain -- the endings are kept by selection, with no
  * new gate work, and stale or non-finite data behind an end cannot leak.
  * Rows whose tick lies outside a schedule's range still get their gradient row: dGradHidden there is the gradient with respect to a wrench that was zero (not
- * added), dGradNoise with respect to a noise that was zero.  Forward mode and the checkpointed reverse do not know the mismatch. */
+ * added), dGradNoise with respect to a noise that was zero.  Forward mode under a mismatch is the section below; the checkpointed reverse is this entry
+ * run segment by segment (segments compose to the bit: dGradGain accumulates in the full walk's order when they are reversed last first). */
 typedef struct cmpc_walk_grads_mismatch {
     double* dGradHidden;   /* [rows][B][6], written per row */
     float* dGradNoise;     /* [rows][B][9], written per row */
@@ -1372,6 +1373,54 @@ typedef struct cmpc_walk_grads_mismatch {
 int cmpc_rollout_walk_vjp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
                                           const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, const cmpc_plant_mismatch* m,
                                           const cmpc_walk_grads_mismatch* mg, void* stream);
+
+/* ---- the mismatch FORWARDS, in k directions (derivation: DESIGN.md 7f, "Mismatch, forwards") ----
+ * The transposes of the three reverse entries above, column for column.  On a mismatch tape the entries of "the roll-out tick FORWARDS" take the plant's
+ * partials at the MPC's forces and the MPC's wrench and would be silently wrong; these take them at the gained forces and the summed wrench.
+ *
+ * The plant: cmpc_plant_step_jvp_cols_device's arguments plus the inputs dHiddenWrench[B][6] / dForceGain[B] float (either NULL as in the forward) and the
+ * directions dDirHidden[B][k][6] / dDirGain[B][k] double (either NULL: zero).  With cf_q = gain f_q on gated-on corners:
+ *     d cf_q = dgain f_q + gain df_q,   dF = sum_q d cf_q,   da = dF + dfExt_0 + dfHidden,   dtau = dtauExt_0 + dtauHidden + sum_q (dcp_q x cf_q + cp_q x d cf_q)
+ * and the three output rows of the plant JVP unchanged -- cmpc_plant_step_vjp_mismatch_device transposed term by term.  With the four new pointers NULL it is
+ * cmpc_plant_step_jvp_cols_device bit for bit (the same kernel instantiation); column j is bit-equal to a k = 1 call on column j alone. */
+int cmpc_plant_step_jvp_mismatch_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
+                                             const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
+                                             const float* dHiddenWrench, const float* dForceGain, const double* dDirHidden, const double* dDirGain,
+                                             double* dDirStateOut, void* stream);
+/* One tick forwards under a mismatch: cmpc_rollout_tick_jvp_device's arguments, the tick's own rows dHiddenWrench[B][6] / dForceGain[B] (either NULL: not
+ * applied in the forward) and the mismatch directions, each may be NULL (zero; md itself may be NULL).  Two differences from that entry:
+ *   the noise direction enters the SOLVE only: the assembled p direction holds (float)dDirState[e] + dDirNoise[e] on com0 / dcom0 / h0, ONE float32 add as in
+ *     the forward's setState (the transpose of "dGradNoise = the solve VJP's dGradP on those rows").  The plant still receives dDirState alone, in double: it
+ *     integrates from the true state.
+ *   the plant launch is the mismatched instantiation, at the tick's hidden row and gain, with dDirHidden / dDirGain.
+ * A flagged problem gets zeros in every output, by the flags and the plant kernel's ok branch of the entry above.  With dHiddenWrench, dForceGain and md all
+ * NULL (or md without a pointer set) it is cmpc_rollout_tick_jvp_device bit for bit (which calls the same function that way).  No workspace beyond that entry's.
+ * sizeof(cmpc_tick_dirs_mismatch) == 24 (LP64; the ctypes mirror is held to this number). */
+typedef struct cmpc_tick_dirs_mismatch {
+    const double* dDirHidden;   /* [B][k][6] */
+    const float* dDirNoise;     /* [B][k][9] */
+    const double* dDirGain;     /* [B][k] */
+} cmpc_tick_dirs_mismatch;
+int cmpc_rollout_tick_jvp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
+                                          const cmpc_tick_dirs_out* out, float* dTickSens, const float* dHiddenWrench, const float* dForceGain,
+                                          const cmpc_tick_dirs_mismatch* md, void* stream);
+/* The forward walk under a mismatch: the same loop as cmpc_rollout_walk_jvp_device -- ONE function behind both entries -- with the tick above per row.  m is
+ * the walk's mismatch (NULL: none was applied; the directions still are), md may be NULL and so may each of its pointers.  Tick tick0 + i takes its hidden row
+ * by TICK NUMBER (m->tick_first) and its direction rows by TAPE ROW, the two indices of the reverse walk.  A tick outside the hidden schedule runs the
+ * partials without the hidden term (a select, as in the forward) and still applies dDirHidden: the map is linear in a wrench that was zero.  A tick with
+ * no hidden row, no gain and no direction pointer is the plain tick, by the rule of the entry above.
+ * The gate structs, the gate kernel and the host gate are NOT changed: the mismatch directions are inputs only, and for a tick at or behind a problem's end
+ * the gate already feeds the tick dOk = 0, which then writes zeros whatever the direction rows hold.  Segments compose to the bit through dDirStates and the
+ * carries.  No workspace beyond pointers.  CMPC_ERR_ARG as cmpc_rollout_walk_jvp_device's and the mismatch's own (a negative count, a non-NULL schedule with
+ * a zero count, tick0 < 0), each refused before anything is queued.
+ * sizeof(cmpc_walk_dirs_mismatch) == 24 (LP64; the ctypes mirror is held to this number). */
+typedef struct cmpc_walk_dirs_mismatch {
+    const double* dDirHidden;   /* [rows][B][k][6], rows = the tape's rows, as dGradHidden's */
+    const float* dDirNoise;     /* [rows][B][k][9] */
+    const double* dDirGain;     /* [B][k] */
+} cmpc_walk_dirs_mismatch;
+int cmpc_rollout_walk_jvp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                          int k, const cmpc_walk_dirs* d, const cmpc_plant_mismatch* m, const cmpc_walk_dirs_mismatch* md, void* stream);
 
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */

@@ -8,5 +8,6 @@ The directory name contains '-', so import it with
 from . import _capi, config, contacts, distributed, layout, rollout, solver, synthetic  # noqa: F401
 from .config import CentroidalMPCConfig, ContactConfig  # noqa: F401
 from .layout import Layout, cold_start, pack_parameters  # noqa: F401
-from .rollout import WalkingRollout, rollout_differentiable, rollout_differentiable_checkpointed, walk_schedule  # noqa: F401
+from .rollout import (WalkingRollout, rollout_differentiable, rollout_differentiable_checkpointed,  # noqa: F401
+                      rollout_differentiable_checkpointed_mismatch, walk_schedule)
 from .solver import BatchSolver, CentroidalMPC, rotate_parameters, solve_differentiable  # noqa: F401

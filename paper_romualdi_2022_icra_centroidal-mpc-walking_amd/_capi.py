@@ -145,6 +145,16 @@ class CmpcWalkGradsMismatch(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("dGradHidden", "dGradNoise", "dGradGain")]
 
 
+class CmpcTickDirsMismatch(C.Structure):
+    """mirror of cmpc_tick_dirs_mismatch (include/cmpc.h): the mismatch directions of cmpc_rollout_tick_jvp_mismatch_device, each pointer NULL = zero; 24 bytes"""
+    _fields_ = [(k, C.c_void_p) for k in ("dDirHidden", "dDirNoise", "dDirGain")]
+
+
+class CmpcWalkDirsMismatch(C.Structure):
+    """mirror of cmpc_walk_dirs_mismatch (include/cmpc.h): the mismatch directions of cmpc_rollout_walk_jvp_mismatch_device, rows as the tape's; 24 bytes"""
+    _fields_ = [(k, C.c_void_p) for k in ("dDirHidden", "dDirNoise", "dDirGain")]
+
+
 class CmpcWalkDirs(C.Structure):
     """mirror of cmpc_walk_dirs (include/cmpc.h): the direction columns, carries and outputs of cmpc_rollout_walk_jvp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -225,6 +235,7 @@ EXPORTS = [
     "cmpc_rollout_snapshot", "cmpc_rollout_snapshot_device", "cmpc_walk_snapshot_bytes",
     "cmpc_plant_step_mismatch_device", "cmpc_rollout_tick_mismatch_device", "cmpc_rollout_walk_mismatch_device",
     "cmpc_plant_step_vjp_mismatch_device", "cmpc_rollout_tick_vjp_mismatch_device", "cmpc_rollout_walk_vjp_mismatch_device",
+    "cmpc_plant_step_jvp_mismatch_cols_device", "cmpc_rollout_tick_jvp_mismatch_device", "cmpc_rollout_walk_jvp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
     "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
@@ -386,6 +397,12 @@ def lib():
             L.cmpc_rollout_tick_vjp_mismatch_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape)] + [vp] * 20
             L.cmpc_rollout_walk_vjp_mismatch_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, C.POINTER(CmpcWalkGrads),
                                                                 C.POINTER(CmpcWalkGradsRot), mp, C.POINTER(CmpcWalkGradsMismatch), vp]
+        if hasattr(L, "cmpc_rollout_walk_jvp_mismatch_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_plant_step_jvp_mismatch_cols_device.argtypes = [vp, fp, fp, fp, d, i, i, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.cmpc_rollout_tick_jvp_mismatch_device.argtypes = [vp, i, d, C.POINTER(CmpcTickTape), i, C.POINTER(CmpcTickDirs), C.POINTER(CmpcTickDirsOut), vp,
+                                                                vp, vp, C.POINTER(CmpcTickDirsMismatch), vp]
+            L.cmpc_rollout_walk_jvp_mismatch_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs),
+                                                                C.POINTER(CmpcPlantMismatch), C.POINTER(CmpcWalkDirsMismatch), vp]
         if hasattr(L, "cmpc_rollout_walk_refill_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             fl, wr = C.POINTER(CmpcWalkRefill), C.POINTER(CmpcWalkRecord)
             L.cmpc_rollout_refill_init.argtypes = [i, fl]

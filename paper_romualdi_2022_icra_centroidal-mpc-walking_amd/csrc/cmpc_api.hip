@@ -2376,9 +2376,11 @@ int cmpc_rollout_walk_vjp_mismatch_device(cmpc_handle h, int max_contacts, int t
 namespace {
 // one workgroup per (problem, column): the column's p direction, float32.  The list kernel has written the nominalPos / currentPos rows; here the state
 // direction goes to com0 / dcom0 / h0 (cmpc_write_state_device's rows, rounded to float32), the wrench direction to the fExt / tauExt rows, every other row
-// is zero, and the caller's extra p direction is added to all of them.
+// is zero, and the caller's extra p direction is added to all of them.  d_noise[B][k][9] (the mismatch entry; null otherwise): the direction of the sensor
+// noise, added to the rounded state direction in ONE float32 add as the forward's setState adds the noise -- it reaches the solve and nothing else.
 __global__ __launch_bounds__(128) void cmpc_tick_jvp_assemble_kernel(int N, const double* __restrict__ d_state, const float* __restrict__ d_wrench,
-                                                                     const float* __restrict__ d_extra, float* __restrict__ d_p)
+                                                                     const float* __restrict__ d_extra, float* __restrict__ d_p,
+                                                                     const float* __restrict__ d_noise)
 {
     const size_t col = blockIdx.x;
     const CmpcIdx L{N};
@@ -2388,7 +2390,10 @@ __global__ __launch_bounds__(128) void cmpc_tick_jvp_assemble_kernel(int N, cons
         float v = 0.f;
         const bool listed = (e >= L.pNom(0) && e < L.pNom(0) + 3 * N + 6) || (e >= L.pNom(1) && e < L.pNom(1) + 3 * N + 6);
         if (listed) v = dp[e];
-        else if (e >= L.pCom0() && e < L.pCom0() + 9) v = d_state ? (float)d_state[col * 9 + (e - L.pCom0())] : 0.f;
+        else if (e >= L.pCom0() && e < L.pCom0() + 9) {
+            v = d_state ? (float)d_state[col * 9 + (e - L.pCom0())] : 0.f;
+            if (d_noise) v = v + d_noise[col * 9 + (e - L.pCom0())];
+        }
         else if (d_wrench && e >= L.pFext() && e < L.pText()) { const int q = e - L.pFext(); v = d_wrench[(col * N + q / 3) * 6 + q % 3]; }
         else if (d_wrench && e >= L.pText()) { const int q = e - L.pText(); v = d_wrench[(col * N + q / 3) * 6 + 3 + q % 3]; }
         dp[e] = d_extra ? v + d_extra[col * np + e] : v;
@@ -2429,16 +2434,37 @@ __global__ __launch_bounds__(128) void cmpc_tick_jvp_flag_kernel(int N, int K, c
 }
 }  // namespace
 
+// (all four mismatch pointers null: the instantiation without the mismatch, which is the kernel as it was before the mismatch existed)
+static int plant_jvp_cols(cmpc_handle h, const char* who, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
+                          const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
+                          const float* dHiddenWrench, const float* dForceGain, const double* dDirHidden, const double* dDirGain, double* dDirStateOut,
+                          void* stream)
+{
+    if (!h || !dX || !dP || !dStateIn || !dDirState || !dDirStateOut || !(step > 0) || substeps < 1 || k < 1)
+        return fail(h, CMPC_ERR_ARG, std::string(who) + ": bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool mm = dHiddenWrench || dForceGain || dDirHidden || dDirGain;
+    int rc = cmpc_launch_plant_jvp_cols_mismatch(h->cfg.horizon, h->B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step,
+                                                 substeps, dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, mm ? 1 : 0, dHiddenWrench,
+                                                 dForceGain, dDirHidden, dDirGain, stream_of(h, stream));
+    return launch_status(h, "plant JVP (columns)", rc);
+}
+
 int cmpc_plant_step_jvp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
                                     const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
                                     double* dDirStateOut, void* stream)
 {
-    if (!h || !dX || !dP || !dStateIn || !dDirState || !dDirStateOut || !(step > 0) || substeps < 1 || k < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_plant_step_jvp_cols_device: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_plant_jvp_cols(h->cfg.horizon, h->B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step, substeps,
-                                        dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, stream_of(h, stream));
-    return launch_status(h, "plant JVP (columns)", rc);
+    return plant_jvp_cols(h, "cmpc_plant_step_jvp_cols_device", dX, dP, dStateIn, step, substeps, k, dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr,
+                          nullptr, nullptr, nullptr, dDirStateOut, stream);
+}
+
+int cmpc_plant_step_jvp_mismatch_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
+                                             const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
+                                             const float* dHiddenWrench, const float* dForceGain, const double* dDirHidden, const double* dDirGain,
+                                             double* dDirStateOut, void* stream)
+{
+    return plant_jvp_cols(h, "cmpc_plant_step_jvp_mismatch_cols_device", dX, dP, dStateIn, step, substeps, k, dDirState, dDirX, dDirP, dDirModel, dDirRot0,
+                          dHiddenWrench, dForceGain, dDirHidden, dDirGain, dDirStateOut, stream);
 }
 
 int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, int k, const double* dPlanT, const int* dPlanN,
@@ -2465,26 +2491,33 @@ int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int ph
     return launch_status(h, "list JVP", rc);
 }
 
-// (shared by the public entry point and the forward walk, as tick_vjp is)
+// the mismatch entry's further arguments (cmpc_rollout_tick_jvp_mismatch_device); null in tick_jvp: the launches and bits of the entry before it
+struct TickMismatchDirs {
+    const float* hidden; const float* gain;                               // this tick's hidden-wrench row [B][6] and the gain [B], either may be null
+    const double* d_hidden; const float* d_noise; const double* d_gain;   // directions [B][k][6], [B][k][9], [B][k], each may be null
+};
+
+// (shared by the public entry points and the forward walk, as tick_vjp is)
 static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in, const cmpc_tick_dirs_out* out,
-                    float* dTickSens, void* stream)
+                    float* dTickSens, void* stream, const TickMismatchDirs* mm = nullptr, const char* who = "cmpc_rollout_tick_jvp_device")
 {
+    const std::string name(who);
     if (!h || !tape || max_contacts < 1 || k < 1 || !out || !out->dDirStateOut || !out->dDirList || !dTickSens)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: null argument");
+        return fail(h, CMPC_ERR_ARG, name + ": null argument");
     if (!tape->dX || !tape->dP || !tape->dLamG || !tape->dState || !tape->dInfo || !tape->dLand || !tape->dListT || !tape->dListN ||
         !(tape->plant_step > 0) || tape->plant_substeps < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: incomplete tape");
+        return fail(h, CMPC_ERR_ARG, name + ": incomplete tape");
     const bool merge = tape->dPrevT || tape->dPrevN;
     if (merge && (!tape->dPrevT || !tape->dPrevN || !tape->dPlanT || !tape->dPlanN))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: a merge tick's tape needs the planner's and the previous tick's times and counts");
+        return fail(h, CMPC_ERR_ARG, name + ": a merge tick's tape needs the planner's and the previous tick's times and counts");
     const cmpc_tick_dirs none = {};
     if (!in) in = &none;
     if (out->dDirList == in->dDirPrevList || (out->dDirListRot && out->dDirListRot == in->dDirPrevListRot))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: the outgoing list's directions must not alias the previous list's");
+        return fail(h, CMPC_ERR_ARG, name + ": the outgoing list's directions must not alias the previous list's");
     long long dt_ns = 0;
     if (tape->force_sample_time) {
         dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_jvp_device: force_sample_time needs a sampling time of at least 1 ns");
+        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, name + ": force_sample_time needs a sampling time of at least 1 ns");
     }
     HIPCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, stream);
@@ -2519,7 +2552,8 @@ static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick
                                       tape->dListT, tape->dListN, tape->dLand, tape->dOk, in->dDirPrevList, in->dDirPrevListRot, in->dDirPlan, in->dDirPlanRot,
                                       nullptr, out->dDirList, out->dDirListRot, dPF, dRot, nullptr, st);
     if (const int err = launch_status(h, "tick JVP (merge + sample)", rc)) return err;
-    hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, st, N, in->dDirState, in->dDirWrench, in->dDirP, dPF);
+    hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, st, N, in->dDirState, in->dDirWrench, in->dDirP, dPF,
+                       mm ? mm->d_noise : (const float*)nullptr);
     HIPCHK(h, hipGetLastError());
     rc = cmpc_solution_jvp_rot_device(h, tape->dX, tape->dP, tape->dLamG, dPF, in->dDirModel, dRot, k, dDX, dTickSens, stream);
     if (rc != CMPC_OK) return rc;
@@ -2528,8 +2562,11 @@ static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick
     rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 2, dt_ns, nullptr, nullptr, nullptr, nullptr, tape->dListT, tape->dListN,
                                   tape->dLand, okTick, nullptr, nullptr, nullptr, nullptr, dDX, out->dDirList, out->dDirListRot, nullptr, nullptr, nullptr, st);
     if (const int err = launch_status(h, "tick JVP (adjust)", rc)) return err;
-    rc = cmpc_launch_plant_jvp_cols(N, B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
-                                    tape->plant_substeps, dState, dDX, dPF, in->dDirModel, rot ? wsRot0 : nullptr, okTick, out->dDirStateOut, st);
+    // (the mismatch entry: the plant's partials at the gained forces and the summed wrench, the tick's own rows; the noise direction does not come here)
+    rc = cmpc_launch_plant_jvp_cols_mismatch(N, B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState,
+                                             (float)tape->plant_step, tape->plant_substeps, dState, dDX, dPF, in->dDirModel, rot ? wsRot0 : nullptr, okTick,
+                                             out->dDirStateOut, mm ? 1 : 0, mm ? mm->hidden : nullptr, mm ? mm->gain : nullptr, mm ? mm->d_hidden : nullptr,
+                                             mm ? mm->d_gain : nullptr, st);
     if (const int err = launch_status(h, "tick JVP (plant)", rc)) return err;
     HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return CMPC_OK;
@@ -2539,6 +2576,16 @@ int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, co
                                  const cmpc_tick_dirs_out* out, float* dTickSens, void* stream)
 {
     return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream);
+}
+
+int cmpc_rollout_tick_jvp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
+                                          const cmpc_tick_dirs_out* out, float* dTickSens, const float* dHiddenWrench, const float* dForceGain,
+                                          const cmpc_tick_dirs_mismatch* md, void* stream)
+{
+    const TickMismatchDirs mm{dHiddenWrench, dForceGain, md ? md->dDirHidden : nullptr, md ? md->dDirNoise : nullptr, md ? md->dDirGain : nullptr};
+    if (!mm.hidden && !mm.gain && !mm.d_hidden && !mm.d_noise && !mm.d_gain)   // (nothing of a mismatch: the plain tick, bit for bit)
+        return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream, nullptr, "cmpc_rollout_tick_jvp_mismatch_device");
+    return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream, &mm, "cmpc_rollout_tick_jvp_mismatch_device");
 }
 
 // ---- the forward walk on the device tape (include/cmpc.h, cmpc_rollout_walk_jvp_device): gate, tick JVP, gate, ..., gate ----
@@ -2584,18 +2631,26 @@ int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g
     return launch_status(h, "forward walk (gate)", lrc);
 }
 
-int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
-                                 const cmpc_walk_dirs* d, void* stream)
+// the loop of both forward walks; m / md: the mismatch and its directions of cmpc_rollout_walk_jvp_mismatch_device, tick_who that entry's tick -- both
+// null: every launch and every bit is what the walk without a mismatch always queued and gave
+static int walk_jvp(cmpc_handle h, const char* who, const char* tick_who, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0,
+                    const int* dEndTick, int k, const cmpc_walk_dirs* d, void* stream, const cmpc_plant_mismatch* m = nullptr,
+                    const cmpc_walk_dirs_mismatch* md = nullptr)
 {
-    if (!h || !d || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: null argument or incomplete tape");
+    const std::string name(who);
+    {
+        const int mrc = mismatch_check(h, who, m);
+        if (mrc != CMPC_OK) return mrc;
+    }
+    if (!h || !d || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, name + ": null argument or incomplete tape");
     if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows || k < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: bad argument (k >= 1, and the rows must lie inside the tape)");
+        return fail(h, CMPC_ERR_ARG, name + ": bad argument (k >= 1, and the rows must lie inside the tape)");
     if (!d->dDirStates || !d->dCarryList || !d->dStatus)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: dDirStates, dCarryList and dStatus are needed");
+        return fail(h, CMPC_ERR_ARG, name + ": dDirStates, dCarryList and dStatus are needed");
     if (d->dDirPlanRot && !d->dCarryListRot)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: the planner's orientation directions need dCarryListRot to carry them");
+        return fail(h, CMPC_ERR_ARG, name + ": the planner's orientation directions need dCarryListRot to carry them");
     if (row0 == 0 && !tape->first_row_is_first_tick)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_device: row 0 is not a first tick and has no row before it to take the previous lists from");
+        return fail(h, CMPC_ERR_ARG, name + ": row 0 is not a first tick and has no row before it to take the previous lists from");
     HIPCHK(h, hipSetDevice(h->device));
     const hipStream_t st = stream_of(h, stream);
     const int B = h->B, N = h->cfg.horizon, M = max_contacts;
@@ -2664,7 +2719,19 @@ int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int
         out.dDirStateOut = d->dDirStates + (rp + 1) * cols * 9;
         out.dDirList = other; out.dDirListRot = otherRot;
         out.dDirX = d->dDirX ? d->dDirX + rp * (size_t)k * nx : nullptr;
-        rc = tick_jvp(h, M, (double)(tick0 + i) * h->cfg.sampling_time, &tt, k, &in, &out, wsSens, stream);
+        // the mismatch entry: tick rp ran under its own schedule row (selected by tick number); its direction rows are the tape row's, applied whether or
+        // not the tick lay inside the schedule's range
+        TickMismatchDirs mm{};
+        const float* unused;
+        mismatch_rows(m, B, tick0 + i, &mm.hidden, &unused, &mm.gain);
+        if (md) {
+            mm.d_hidden = md->dDirHidden ? md->dDirHidden + rp * cols * 6 : nullptr;
+            mm.d_noise = md->dDirNoise ? md->dDirNoise + rp * cols * 9 : nullptr;
+            mm.d_gain = md->dDirGain;
+        }
+        // (a tick with no row, no gain and no direction is the plain tick: the rule of cmpc_rollout_tick_jvp_mismatch_device, so walk = ticks to the bit)
+        const bool plain = !mm.hidden && !mm.gain && !mm.d_hidden && !mm.d_noise && !mm.d_gain;
+        rc = tick_jvp(h, M, (double)(tick0 + i) * h->cfg.sampling_time, &tt, k, &in, &out, wsSens, stream, plain ? nullptr : &mm, tick_who);
         std::swap(cur, other); std::swap(curRot, otherRot);
     }
     if (rc == CMPC_OK && cur != d->dCarryList) {     // (an odd number of ticks: the lists leaving the last row sit in the workspace)
@@ -2673,6 +2740,19 @@ int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int
     }
     if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
     return rc;
+}
+
+int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
+                                 const cmpc_walk_dirs* d, void* stream)
+{
+    return walk_jvp(h, "cmpc_rollout_walk_jvp_device", "cmpc_rollout_tick_jvp_device", max_contacts, tick0, ticks, tape, row0, dEndTick, k, d, stream);
+}
+
+int cmpc_rollout_walk_jvp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                          int k, const cmpc_walk_dirs* d, const cmpc_plant_mismatch* m, const cmpc_walk_dirs_mismatch* md, void* stream)
+{
+    return walk_jvp(h, "cmpc_rollout_walk_jvp_mismatch_device", "cmpc_rollout_tick_jvp_mismatch_device", max_contacts, tick0, ticks, tape, row0, dEndTick, k,
+                    d, stream, m, md);
 }
 
 // the handle's own contact blocks from contact lists (what the class facade's setContactPhaseList calls)

@@ -74,6 +74,10 @@ int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int c
 int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
                                const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream);
+int cmpc_launch_plant_jvp_cols_mismatch(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
+                                        const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
+                                        const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, int mismatch, const float* dHidden,
+                                        const float* dGain, const double* dDirHidden, const double* dDirGain, hipStream_t stream);
 
 // ---- cmpc_contacts.hip ----
 int cmpc_launch_contacts_rotation_vjp(int B, int N, int M, double dt, double now, const double* list_t, const int* list_n, const double* g_rot,

@@ -193,10 +193,14 @@ __device__ inline void cross3(const double* a, const double* b, double* o)
 // forwards: (ds, dx, dp, dtheta, omega_0) -> ds'.  Null direction groups are zero.  ROT: with the rotation direction of knot 0, dir_rot[B][2][3] in the
 // body-frame tangent dR_c,0 = R_c,0 [omega_c]x -- the contact points move by R_c,0 (omega_c x cn_q), so only the torque sees it.  ROT = false is the kernel
 // without it, instruction for instruction.
-template <bool ROT>
+// MM: the mismatched plant forwards ("Mismatch, forwards"), q from plant_partials<true>: d cf_q = dgain fr_q + gain df_q on a gated-on foot,
+// da gains dfHidden and dtau gains dtauHidden -- plant_vjp_problem<ROT, true> transposed term by term.  dir_hidden[B][6] / dir_gain[B] double, either null =
+// zero.  MM = false is the function as it was before the mismatch existed, instruction for instruction.
+template <bool ROT, bool MM = false>
 __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__ P, const PlantPartials& q, const double* __restrict__ dir_state,
                                          const float* __restrict__ dir_x, const float* __restrict__ dir_p, const double* __restrict__ dir_model,
-                                         const double* __restrict__ dir_rot, double* __restrict__ out)
+                                         const double* __restrict__ dir_rot, double* __restrict__ out, const double* __restrict__ dir_hidden = nullptr,
+                                         const double* __restrict__ dir_gain = nullptr)
 {
     const CmpcIdx L{N};
     const float* p = P + (size_t)b * L.np();
@@ -205,7 +209,9 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
     for (int i = 0; i < 3; ++i) {
         dc[i] = dir_state[(size_t)b * 9 + i]; dv[i] = dir_state[(size_t)b * 9 + 3 + i]; dh[i] = dir_state[(size_t)b * 9 + 6 + i];
         dtau[i] = dir_p ? (double)dir_p[(size_t)b * L.np() + L.pText() + i] : 0.0;
+        if (MM && dir_hidden) dtau[i] += dir_hidden[(size_t)b * 6 + 3 + i];
     }
+    const double dgain = (MM && dir_gain) ? dir_gain[b] : 0.0;
     for (int c = 0; c < 2; ++c) {
         const float* R = p + L.pR(c);
         for (int j = 0; j < 4; ++j) {
@@ -219,6 +225,7 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
                 }
                 if (ROT) dcp[i] += (double)R[i] * wn[0] + (double)R[3 + i] * wn[1] + (double)R[6 + i] * wn[2];
                 df[i] = (dir_x && q.on[c]) ? (double)dir_x[(size_t)b * L.nx() + L.oF(c, j) + i] : 0.0;
+                if (MM) df[i] = q.on[c] ? dgain * q.fr[4 * c + j][i] + q.gain * df[i] : 0.0;   // d cf_q (fr is zero on a gated-off foot; so is this)
                 dF[i] += df[i];
             }
             cross3(dcp, q.cf[4 * c + j], t);
@@ -229,6 +236,7 @@ __device__ inline void plant_jvp_problem(int N, int b, const float* __restrict__
     }
     for (int i = 0; i < 3; ++i) {
         da[i] = dF[i] + (dir_p ? (double)dir_p[(size_t)b * L.np() + L.pFext() + i] : 0.0);
+        if (MM && dir_hidden) da[i] += dir_hidden[(size_t)b * 6 + i];
         dI[i] = T * dc[i] + 0.5 * T * T * dv[i] + T * T * T / 6.0 * da[i];
     }
     double u[3], w[3];
@@ -321,13 +329,17 @@ __global__ __launch_bounds__(256) void cmpc_plant_jvp_kernel(int N, int B, float
 // k columns per problem (include/cmpc.h, cmpc_plant_step_jvp_cols_device): one thread per (problem, column), the same two device functions on direction
 // arrays [B][K][...] -- plant_jvp_problem indexes its directions by problem, so column j of problem b is handed over as the array moved by b (K - 1) + j
 // rows: entry b of that is entry b K + j of the caller's.  ok (the tick JVP's flags; null otherwise): a problem whose word is 0 gets zeros.
-template <bool ROT>
+// MM: the mismatched plant -- the partials at this tick's hidden row [B][6] and gain [B] (either null, as in the forward), and the directions
+// dir_hidden[B][K][6] / dir_gain[B][K] double, either null = zero.  MM = false reads none of the four.
+template <bool ROT, bool MM = false>
 __global__ __launch_bounds__(256) void cmpc_plant_jvp_cols_kernel(int N, int B, int K, float grav, const float* __restrict__ corners, int corners_stride,
                                                                   const float* __restrict__ X, const float* __restrict__ P,
                                                                   const float* __restrict__ state_in, float h, int nsub, const double* dir_state,
                                                                   const float* __restrict__ dir_x, const float* __restrict__ dir_p,
                                                                   const double* __restrict__ dir_model, const double* __restrict__ dir_rot,
-                                                                  const int* __restrict__ ok, double* out)
+                                                                  const int* __restrict__ ok, double* out, const float* __restrict__ hidden,
+                                                                  const float* __restrict__ gain, const double* __restrict__ dir_hidden,
+                                                                  const double* __restrict__ dir_gain)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)B * K) return;
@@ -339,6 +351,13 @@ __global__ __launch_bounds__(256) void cmpc_plant_jvp_cols_kernel(int N, int B, 
     }
     const CmpcIdx L{N};
     PlantPartials q;
+    if (MM) {
+        plant_partials<true>(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q, hidden, gain);
+        plant_jvp_problem<ROT, true>(N, b, P, q, dir_state + col * 9, dir_x ? dir_x + col * L.nx() : nullptr, dir_p ? dir_p + col * L.np() : nullptr,
+                                     dir_model ? dir_model + col * CMPC_MODEL_DOUBLES : nullptr, ROT ? dir_rot + col * 6 : nullptr, out + col * 9,
+                                     dir_hidden ? dir_hidden + col * 6 : nullptr, dir_gain ? dir_gain + col : nullptr);
+        return;
+    }
     plant_partials(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q);
     plant_jvp_problem<ROT>(N, b, P, q, dir_state + col * 9, dir_x ? dir_x + col * L.nx() : nullptr, dir_p ? dir_p + col * L.np() : nullptr,
                            dir_model ? dir_model + col * CMPC_MODEL_DOUBLES : nullptr, ROT ? dir_rot + col * 6 : nullptr, out + col * 9);
@@ -1018,13 +1037,24 @@ extern "C" int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const
                                           const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
                                           const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream)
 {
+    return cmpc_launch_plant_jvp_cols_mismatch(N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h, nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0,
+                                               dOk, dOut, 0, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// mismatch != 0: the instantiations of the mismatched plant (dHidden / dGain / dDirHidden / dDirGain may each be null); 0: the kernels as they were before it
+extern "C" int cmpc_launch_plant_jvp_cols_mismatch(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX,
+                                                   const float* dP, const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX,
+                                                   const float* dDirP, const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut,
+                                                   int mismatch, const float* dHidden, const float* dGain, const double* dDirHidden, const double* dDirGain,
+                                                   hipStream_t stream)
+{
     const unsigned blocks = (unsigned)(((long long)B * K + 255) / 256);
-    if (dDirRot0)
-        hipLaunchKernelGGL(cmpc_plant_jvp_cols_kernel<true>, dim3(blocks), dim3(256), 0, stream, N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
-                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOk, dOut);
-    else
-        hipLaunchKernelGGL(cmpc_plant_jvp_cols_kernel<false>, dim3(blocks), dim3(256), 0, stream, N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h,
-                           nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOk, dOut);
+#define CMPC_PLANT_JVP_COLS(ROT, MM)                                                                                                                          \
+    hipLaunchKernelGGL((cmpc_plant_jvp_cols_kernel<ROT, MM>), dim3(blocks), dim3(256), 0, stream, N, B, K, grav, dCorners, corners_stride, dX, dP, dStateIn, h, \
+                       nsub, dDirState, dDirX, dDirP, dDirModel, dDirRot0, dOk, dOut, dHidden, dGain, dDirHidden, dDirGain)
+    if (mismatch) { if (dDirRot0) CMPC_PLANT_JVP_COLS(true, true); else CMPC_PLANT_JVP_COLS(false, true); }
+    else { if (dDirRot0) CMPC_PLANT_JVP_COLS(true, false); else CMPC_PLANT_JVP_COLS(false, false); }
+#undef CMPC_PLANT_JVP_COLS
     return (int)hipGetLastError();
 }
 

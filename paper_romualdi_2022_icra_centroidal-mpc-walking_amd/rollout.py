@@ -897,7 +897,7 @@ class WalkingRollout:
         problem at N = 20) and "inputs", the small things a re-run needs, by reference: state0, the wrench schedule and push_ticks, the plans of replan
         and the plan in force at tick 0, the references, stop, skip_ended, ticks, every.  Like walk_device: no host read and no synchronisation.
         Continue or fork from a checkpoint: walk_resume_device().  The gradient without a whole-walk tape: backward_device_checkpointed()."""
-        mismatch = kwargs.pop("mismatch", None)    # (walk_device_mismatch's argument; kept in "inputs" -- the checkpointed reverse walk refuses it)
+        mismatch = kwargs.pop("mismatch", None)    # (walk_device_mismatch's argument; kept in "inputs" for backward_device_checkpointed_mismatch)
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
         return self._queued(lambda: self._walk_checkpointed(every, None, *args.args, **args.kwargs, mismatch=mismatch))
@@ -1023,14 +1023,25 @@ class WalkingRollout:
         -> the keys of backward_device (rot=True: of backward_device_rot) plus "tape_rows_peak".  No host read once the workspaces exist (the first
         call allocates them and turns the multiplier output on).  Out of scope: the reference gradients (backward_device_refs: their one-launch sum has
         a fixed ascending order that per-segment calls in reverse would change), the forward-mode walk, and refilled walks (walk_device_refill has no
-        tape and no gradient)."""
+        tape and no gradient).  A walk that ran under a plant mismatch is refused here (NotImplementedError): backward_device_checkpointed_mismatch()."""
         return self._queued(lambda: self._backward_checkpointed(w, grad_states, grad_X, rot))
 
-    def _backward_checkpointed(self, w, grad_states, grad_X, rot):
+    def backward_device_checkpointed_mismatch(self, w, grad_states, grad_X=None, rot=False):
+        """backward_device_checkpointed for w = walk_device_checkpointed(..., mismatch=...): the same loop, with each segment run again UNDER THE MISMATCH
+        (w["inputs"]["mismatch"], kept alive there) and reversed with cmpc_rollout_walk_vjp_mismatch_device.  -> backward_device's keys on a mismatch
+        tape -- hidden_wrench[ticks, B, 6] float64, state_noise[ticks, B, 9] float32 and force_gain[B] float64 besides the others -- plus
+        "tape_rows_peak".  The segments are reversed last first, so force_gain accumulates tick by tick in the full walk's order: every key equals
+        backward_device's on walk_device_taped(mismatch=...) bit for bit.  A walk without a mismatch gives backward_device_checkpointed's dict.  (A
+        method of its own: backward_device_checkpointed's signature and its refusal of a mismatch are pinned.)"""
+        return self._queued(lambda: self._backward_checkpointed(w, grad_states, grad_X, rot, mismatch=True))
+
+    def _backward_checkpointed(self, w, grad_states, grad_X, rot, mismatch=False):
         torch, B, N, L, M, s, dev = self.torch, self.B, self.cfg.N, self.L, self.M, self.solver, self.dev
         inp, cps = w["inputs"], w["checkpoints"]
-        if inp.get("mismatch") is not None:
-            raise NotImplementedError("backward_device_checkpointed: the walk ran under a plant mismatch; its reverse is backward_device on walk_device_taped(mismatch=...)")
+        mm = inp.get("mismatch")
+        if mm is not None and not mismatch:
+            raise NotImplementedError("backward_device_checkpointed: the walk ran under a plant mismatch; its reverse in bounded memory is "
+                                      "backward_device_checkpointed_mismatch")
         T, every = inp["ticks"], inp["every"]
         as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(dev, dt).contiguous()
         gS = as_t(grad_states, torch.float64)
@@ -1044,6 +1055,8 @@ class WalkingRollout:
                    end_tick=w["end_tick"])
         if rot:
             out.update(plan_rot=z((B, 2, M, 3)), rot=z((T, B, 2, N, 3)), removed=z((T, B), torch.float32))
+        if mm is not None:    # (backward_device's three more keys on a mismatch tape)
+            out.update(hidden_wrench=z((T, B, 6)), state_noise=z((T, B, 9), torch.float32), force_gain=z((B,)))
         rows = min(every, T) + 1
         key = (rows, inp["stop"])
         ws = getattr(self, "_checkpoint_ws", None)
@@ -1072,7 +1085,7 @@ class WalkingRollout:
                 tp["list_n"][0].copy_(prev[2])
             tp["_c"].first_row_is_first_tick = 1 if c0 == 0 else 0
             self._walk_live(live, c0, c1, c0, inp["replan"], inp["plan"], inp["wrench"], inp["refs"], inp["skip_ended"], tape=tp, tape_shift=c0 - r0,
-                            cold=c0 == 0)
+                            cold=c0 == 0, mismatch=mm)
             gx_rows = None
             if callable(grad_X):
                 seg = {k: tp[k][r0:r0 + c1 - c0] for k in ("X", "P", "lam_g", "info", "ok", "land", "plan_t", "list_t", "plan_n", "list_n")}
@@ -1081,7 +1094,8 @@ class WalkingRollout:
                 gx_rows = ws["gx"]
             s.rollout_walk_vjp_rows_device(c0, c1 - c0, tp, r0, w["end_tick"], gS, g, gl, out["status"], grad_X=gX, grad_X_rows=gx_rows, wrench=out["wrench"],
                                            dGradPlan=out["plan"], dGradModel=out["models"], carry_list_rot=glr, dGradPlanRot=out.get("plan_rot"),
-                                           grad_rot=out.get("rot"), removed=out.get("removed"))
+                                           grad_rot=out.get("rot"), removed=out.get("removed"), mismatch=mm, grad_hidden=out.get("hidden_wrench"),
+                                           grad_noise=out.get("state_noise"), grad_gain=out.get("force_gain"))
             peak = max(peak, r0 + c1 - c0)
         for i in reversed(range(min(T, inp["push_ticks"]))):    # (backward()'s expression, tick by tick in its order)
             out["push"] += out["wrench"][i][:, :max(inp["push_ticks"] - i, 1), :3].to(torch.float64).sum(1)
@@ -1159,7 +1173,8 @@ class WalkingRollout:
         end_tick (w's).  A problem that ended at tick e (w["end_tick"]) keeps the directions of its states 0 .. e and of its solutions 0 .. e - 1
         (include/cmpc.h): its rows e + 1 .. of states, e .. of X and its final list directions are exactly zero, its rows e .. of status 6 and of removed 0,
         whatever its later tape rows or its rows of the directions hold -- not even NaN leaks.  Where nothing ended every entry is bit-equal to
-        run(tape=True) + forward_sensitivity().  Directions of the planner's reference trajectories too: forward_sensitivity_device_refs()."""
+        run(tape=True) + forward_sensitivity().  Directions of the planner's reference trajectories too: forward_sensitivity_device_refs().  A tape that
+        carries a plant mismatch is refused (NotImplementedError): forward_sensitivity_device_mismatch()."""
         return self._forward_sensitivity_device(w, None, None, dir_state0, dir_list0, dir_list_rot0, dir_plan, dir_plan_rot, dir_push, dir_models, dir_wrench,
                                                 solutions)
 
@@ -1173,12 +1188,27 @@ class WalkingRollout:
         args.apply_defaults()
         return self._forward_sensitivity_device(w, dir_ref_com, dir_ref_h, *args.args[1:], **args.kwargs)
 
+    def forward_sensitivity_device_mismatch(self, w, dir_hidden_wrench=None, dir_state_noise=None, dir_force_gain=None, dir_ref_com=None, dir_ref_h=None,
+                                            **dirs):
+        """forward_sensitivity_device_refs(w, dir_ref_com, dir_ref_h, **dirs) on a walk that ran under a plant mismatch, w = walk_device_taped(...,
+        mismatch=...), with directions of the mismatch as well (cmpc_rollout_walk_jvp_mismatch_device): dir_hidden_wrench[ticks, B, k, 6] float64,
+        dir_state_noise[ticks, B, k, 9] float32, dir_force_gain[B, k] float64 (CUDA tensors or numpy; None: zero) -- row i is the direction of what tick
+        i's plant felt (hidden wrench; applied also where the schedule had no row: the wrench there was zero) or what tick i's MPC measured (noise: it
+        enters the solve only).  The plant's partials are the mismatched plant's.  The same dict comes back: the transpose of backward_device() on that
+        tape, its keys hidden_wrench, state_noise and force_gain included, input for output; ONE call per replan segment, no host read.  On a tape
+        without a mismatch and without the three directions every key is bit-equal to forward_sensitivity_device_refs.  (A method of its own:
+        forward_sensitivity_device's signature and its refusal of a mismatch tape are pinned.)"""
+        args = inspect.signature(self.forward_sensitivity_device).bind(w, **dirs)
+        args.apply_defaults()
+        return self._forward_sensitivity_device(w, dir_ref_com, dir_ref_h, *args.args[1:], **args.kwargs,
+                                                mismatch_dirs=(dir_hidden_wrench, dir_state_noise, dir_force_gain))
+
     def _forward_sensitivity_device(self, w, dir_ref_com, dir_ref_h, dir_state0, dir_list0, dir_list_rot0, dir_plan, dir_plan_rot, dir_push, dir_models,
-                                    dir_wrench, solutions):
+                                    dir_wrench, solutions, mismatch_dirs=None):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
-        if tape.get("mismatch") is not None:    # (the tick JVP takes its partials at the MPC's forces and wrench: on this tape it would be silently wrong)
-            raise NotImplementedError("forward_sensitivity_device: the tape carries a plant mismatch; forward mode does not know it (use backward_device)")
+        if tape.get("mismatch") is not None and mismatch_dirs is None:    # (the plain tick JVP takes its partials at the MPC's forces and wrench: on this tape it would be silently wrong)
+            raise NotImplementedError("forward_sensitivity_device: the tape carries a plant mismatch; its forward mode is forward_sensitivity_device_mismatch")
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
 
         def as_dir(a, dtype, tail, lead=()):
@@ -1196,7 +1226,12 @@ class WalkingRollout:
         if dir_ref_com is not None or dir_ref_h is not None:
             n_ref = tape["references"]["knots"]
             drc, drh = as_dir(dir_ref_com, f64, (n_ref, 3)), as_dir(dir_ref_h, f64, (n_ref, 3))
-        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod, drc, drh) if a is not None} | ({int(dwr.shape[2])} if dwr is not None else set())
+        dmh = dmn = dmg = None
+        if mismatch_dirs is not None:
+            dmh, dmn = as_dir(mismatch_dirs[0], f64, (6,), lead=(T,)), as_dir(mismatch_dirs[1], f32, (9,), lead=(T,))
+            dmg = as_dir(mismatch_dirs[2], f64, ())
+        ks = {int(a.shape[1]) for a in (ds, dl, dlr, dpl, dplr, dpush, dmod, drc, drh, dmg) if a is not None} | {
+            int(a.shape[2]) for a in (dwr, dmh, dmn) if a is not None}
         assert len(ks) == 1, "forward_sensitivity_device: no direction, or directions of different k"
         k = ks.pop()
         rot = dlr is not None or dplr is not None
@@ -1222,10 +1257,14 @@ class WalkingRollout:
             if drc is not None or drh is not None:    # (the replan segments share the trajectories: one launch over all rows)
                 dp = z((T, B, k, L.np), f32)
                 s.reference_from_planner_jvp_device(0, T, k, tape["references"], dp, drc, drh)
+            # (a tape without a mismatch and no direction of one: the plain entry, call for call)
+            walk, mm = s.rollout_walk_jvp_device, {}
+            if mismatch_dirs is not None and not (tape.get("mismatch") is None and dmh is None and dmn is None and dmg is None):
+                walk, mm = s.rollout_walk_jvp_mismatch_device, dict(mismatch=tape.get("mismatch"), dir_hidden=dmh, dir_noise=dmn, dir_gain=dmg)
             for j, t0 in enumerate(starts):
                 t1 = starts[j + 1] if j + 1 < len(starts) else T
-                s.rollout_walk_jvp_device(t0, t1 - t0, tape, t0, w["end_tick"], k, out["states"], cl, out["status"], carry_list_rot=clr, dir_plan=dpl,
-                                          dir_plan_rot=dplr, dir_wrench=dwr, dir_model=dmod, dir_p=dp, dir_x=out.get("X"), removed=out["removed"])
+                walk(t0, t1 - t0, tape, t0, w["end_tick"], k, out["states"], cl, out["status"], carry_list_rot=clr, dir_plan=dpl, dir_plan_rot=dplr,
+                     dir_wrench=dwr, dir_model=dmod, dir_p=dp, dir_x=out.get("X"), removed=out["removed"], **mm)
             out["list"] = cl
             out["list_rot"] = clr if rot else z((B, k, 2, M, 3))
         cur.wait_stream(ls)
@@ -1321,7 +1360,8 @@ def rollout_differentiable(rollout: WalkingRollout, ticks, state0, push=None, mo
     with tick_first = 0 (a wrench the MPC is not told about, noise on the state it measures, a gain on the forces the plant applies).  Only with
     device_walk=True (NotImplementedError otherwise, before anything touches a GPU): backward returns their .grad from the keys hidden_wrench,
     state_noise and force_gain of backward_device (rows behind Th / Tn have no input to receive theirs).  Forward mode over a mismatched walk raises
-    NotImplementedError."""
+    NotImplementedError here: call WalkingRollout.forward_sensitivity_device_mismatch on rollout.last_walk.  In bounded memory:
+    rollout_differentiable_checkpointed_mismatch."""
     mismatched = hidden_wrench is not None or state_noise is not None or force_gain is not None
     if mismatched and not device_walk:
         raise NotImplementedError("rollout_differentiable: hidden_wrench / state_noise / force_gain need device_walk=True")
@@ -1409,6 +1449,58 @@ def _jr_applied(jr, t):
     return (jr * t[..., None, :]).sum(-1)
 
 
+def rollout_differentiable_checkpointed_mismatch(rollout: WalkingRollout, ticks, state0, every, hidden_wrench=None, state_noise=None, force_gain=None,
+                                                 push=None, models=None, push_ticks=0, replan=None):
+    """rollout_differentiable_checkpointed under a plant mismatch: hidden_wrench [Th, B, 6] / state_noise [Tn, B, 9] / force_gain [B] as
+    rollout_differentiable's (tick_first = 0; each None or a torch tensor).  Forward is WalkingRollout.walk_device_checkpointed(mismatch=...) cut at every
+    tick, backward is WalkingRollout.backward_device_checkpointed_mismatch: the returned states, and state0.grad, push.grad, models.grad,
+    hidden_wrench.grad, state_noise.grad and force_gain.grad equal rollout_differentiable(device_walk=True, hidden_wrench=, state_noise=, force_gain=)'s to
+    the bit, without a whole-walk tape.  Not here, as there: plan_rot, ref_com / ref_h and forward mode.  (A function of its own:
+    rollout_differentiable_checkpointed's signature is pinned.)"""
+    import torch
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, state0, push, models, hidden, noise, gain):
+            det = lambda a: None if a is None else a.detach().to(rollout.dev, torch.float32).contiguous()
+            mm = None
+            if hidden is not None or noise is not None or gain is not None:
+                mm = dict(hidden_wrench=det(hidden), state_noise=det(noise), force_gain=det(gain), tick_first=0)
+            ctx.mm_meta = tuple(None if a is None else (a.dtype, int(a.shape[0])) for a in (hidden, noise, gain))
+            assert all(a is None or 1 <= a.shape[0] <= ticks for a in (hidden, noise)), "hidden_wrench / state_noise: between 1 and `ticks` rows"
+            if models is not None:
+                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
+                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
+            s0 = state0.detach().to(rollout.dev, torch.float32)
+            states = torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
+            w = rollout._queued(lambda: rollout._walk_checkpointed(
+                every, states, ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks,
+                replan, False, ("merge", "solver", "nonfinite"), False, mismatch=mm))
+            rollout.last_walk = ctx.walk = w
+            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
+            e = w["end_tick"]
+            row = torch.arange(ticks + 1, device=rollout.dev)[:, None]
+            ctx.past = (e[None, :] >= 0) & (row > e[None, :])         # [ticks + 1, B]: rows behind a problem's end
+            ctx.last = row == e[None, :]                                # the row its final state sits in
+            return torch.where(ctx.past[..., None], w["final_state"][None], states)
+
+        @staticmethod
+        def backward(ctx, gStates):
+            g = gStates.to(rollout.dev, torch.float64)
+            folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
+            g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
+            r = rollout.backward_device_checkpointed_mismatch(ctx.walk, g)
+            rollout.last_backward = r
+            mg = lambda i, key, rows: (r[key][:ctx.mm_meta[i][1]] if rows else r[key]).to(ctx.mm_meta[i][0]) \
+                if ctx.mm_meta[i] is not None and ctx.needs_input_grad[3 + i] else None
+            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
+                    r["models"] if ctx.needs_input_grad[2] else None,
+                    # (a schedule shorter than the walk: the rows behind it have no input)
+                    mg(0, "hidden_wrench", True), mg(1, "state_noise", True), mg(2, "force_gain", False))
+
+    return _Fn.apply(state0, push, models, hidden_wrench, state_noise, force_gain)
+
+
 def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ticks, replan, plan_rot=None, ref_com=None, ref_h=None, mismatch=None):
     """rollout_differentiable(device_walk=True); mismatch: None, or (hidden_wrench, state_noise, force_gain), each a tensor or None"""
     import torch
@@ -1478,7 +1570,8 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
         @staticmethod
         def jvp(ctx, t_state0, t_push, t_models, t_rot, t_ref_com, t_ref_h, t_hidden=None, t_noise=None, t_gain=None):
             if mismatch is not None:
-                raise NotImplementedError("rollout_differentiable: forward mode does not know the plant mismatch (use backward)")
+                raise NotImplementedError("rollout_differentiable: forward mode under a plant mismatch is WalkingRollout.forward_sensitivity_device_mismatch "
+                                          "on rollout.last_walk")
             """torch.autograd.forward_ad: forward_sensitivity_device at k = 1 on the tape the forward left.  The returned states hold final_state in the
             rows behind a problem's end, so those rows take the tangent of the row its final state sits in: the transpose of backward's fold."""
             col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
@@ -1506,36 +1599,6 @@ def rollout_differentiable_checkpointed(rollout: WalkingRollout, ticks, state0, 
     WalkingRollout.backward_device_checkpointed -- no whole-walk tape exists at any time, only a snapshot every `every` ticks and one tape of
     every + 1 rows.  The returned states, and state0.grad, push.grad and models.grad, equal rollout_differentiable(device_walk=True)'s to the bit; the
     fold of the rows behind a problem's end is the same.  rollout.last_walk / rollout.last_backward as there.  Not here: plan_rot, ref_com / ref_h
-    (backward_device_refs is out of scope of the checkpointed reverse walk) and forward mode."""
-    import torch
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, state0, push, models):
-            if models is not None:
-                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
-                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
-            s0 = state0.detach().to(rollout.dev, torch.float32)
-            states = torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
-            w = rollout._queued(lambda: rollout._walk_checkpointed(
-                every, states, ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks,
-                replan, False, ("merge", "solver", "nonfinite"), False))
-            rollout.last_walk = ctx.walk = w
-            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
-            e = w["end_tick"]
-            row = torch.arange(ticks + 1, device=rollout.dev)[:, None]
-            ctx.past = (e[None, :] >= 0) & (row > e[None, :])         # [ticks + 1, B]: rows behind a problem's end
-            ctx.last = row == e[None, :]                                # the row its final state sits in
-            return torch.where(ctx.past[..., None], w["final_state"][None], states)
-
-        @staticmethod
-        def backward(ctx, gStates):
-            g = gStates.to(rollout.dev, torch.float64)
-            folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
-            g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
-            r = rollout.backward_device_checkpointed(ctx.walk, g)
-            rollout.last_backward = r
-            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
-                    r["models"] if ctx.needs_input_grad[2] else None)
-
-    return _Fn.apply(state0, push, models)
+    (backward_device_refs is out of scope of the checkpointed reverse walk) and forward mode.  Under a plant mismatch:
+    rollout_differentiable_checkpointed_mismatch."""
+    return rollout_differentiable_checkpointed_mismatch(rollout, ticks, state0, every, push=push, models=models, push_ticks=push_ticks, replan=replan)

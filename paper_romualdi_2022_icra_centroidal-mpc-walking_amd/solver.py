@@ -766,6 +766,26 @@ class BatchSolver:
                                                                                      int(substeps), k, *args, st))
         return out
 
+    def plant_step_jvp_mismatch_cols_device(self, dX, dP, dState, dDirState, dDirX=None, dDirP=None, dDirModel=None, dDirRot0=None, hidden_wrench=None,
+                                            force_gain=None, dDirHidden=None, dDirGain=None, step=0.01, substeps=6, out=None):
+        """cmpc_plant_step_jvp_mismatch_cols_device: plant_step_jvp_cols_device at the mismatched plant (hidden_wrench[B, 6], force_gain[B] float32 or
+        None) with the directions dDirHidden[B, k, 6] and dDirGain[B, k] float64 (None: zero) -> d state'[B, k, 9] float64.  All four None: the call
+        above, bit for bit; column j is bit-equal to a k = 1 call on column j."""
+        import torch
+        L, B = self.layout, self.batch
+        assert dDirState.dim() == 3
+        k = int(dDirState.shape[1])
+        f32, f64 = torch.float32, torch.float64
+        if out is None:
+            out = torch.empty((B, k, 9), dtype=f64, device=dX.device)
+        args = (self._opt(dDirState, f64, (B, k, 9), "dDirState"), self._opt(dDirX, f32, (B, k, L.nx), "dDirX"), self._opt(dDirP, f32, (B, k, L.np), "dDirP"),
+                self._opt(dDirModel, f64, (B, k, _capi.MODEL_DOUBLES), "dDirModel"), self._opt(dDirRot0, f64, (B, k, 2, 3), "dDirRot0"),
+                self._opt(hidden_wrench, f32, (B, 6), "hidden_wrench"), self._opt(force_gain, f32, (B,), "force_gain"),
+                self._opt(dDirHidden, f64, (B, k, 6), "dDirHidden"), self._opt(dDirGain, f64, (B, k), "dDirGain"), self._opt(out, f64, (B, k, 9), "out"))
+        self._launch(dX.device, lambda st: self._lib.cmpc_plant_step_jvp_mismatch_cols_device(
+            self._h, dX.data_ptr(), dP.data_ptr(), dState.data_ptr(), float(step), int(substeps), k, *args, st))
+        return out
+
     def contacts_jvp_device(self, now, list_t, list_n, land, k, plan=None, prev=None, ok=None, dDirPrevList=None, dDirPrevListRot=None, dDirPlan=None,
                             dDirPlanRot=None, dDirX=None, phase=3, force_sample_time=False, out=None, out_rot=None, dDirP=None, rot=True):
         """The list path of one tick forwards (cmpc_contacts_jvp_device), the transpose of contacts_position_vjp_device + contacts_orientation_vjp_device
@@ -797,6 +817,21 @@ class BatchSolver:
 
     def rollout_tick_jvp_device(self, now, tape, k, dDirState=None, dDirPrevList=None, dDirPrevListRot=None, dDirPlan=None, dDirPlanRot=None, dDirWrench=None,
                                 dDirModel=None, dDirP=None, x=False, rot=False, p_full=False, out_state=None):
+        """cmpc_rollout_tick_jvp_device: one tick forwards in k directions (arguments and the returned dict: _rollout_tick_jvp)."""
+        return self._rollout_tick_jvp(now, tape, k, dDirState, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirWrench, dDirModel, dDirP, x, rot,
+                                      p_full, out_state, None)
+
+    def rollout_tick_jvp_mismatch_device(self, now, tape, k, hidden_wrench=None, force_gain=None, dDirHidden=None, dDirNoise=None, dDirGain=None,
+                                         dDirState=None, dDirPrevList=None, dDirPrevListRot=None, dDirPlan=None, dDirPlanRot=None, dDirWrench=None,
+                                         dDirModel=None, dDirP=None, x=False, rot=False, p_full=False, out_state=None):
+        """cmpc_rollout_tick_jvp_mismatch_device: rollout_tick_jvp_device on a tick that ran under a mismatch -- hidden_wrench[B, 6] / force_gain[B]
+        float32 are the tick's own rows (None: not applied), dDirHidden[B, k, 6] / dDirGain[B, k] float64 and dDirNoise[B, k, 9] float32 the mismatch
+        directions (None: zero).  The noise direction enters the solve only.  All five None: rollout_tick_jvp_device, bit for bit."""
+        return self._rollout_tick_jvp(now, tape, k, dDirState, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirWrench, dDirModel, dDirP, x, rot,
+                                      p_full, out_state, (hidden_wrench, force_gain, dDirHidden, dDirNoise, dDirGain))
+
+    def _rollout_tick_jvp(self, now, tape, k, dDirState, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirWrench, dDirModel, dDirP, x, rot, p_full,
+                          out_state, mm):
         """cmpc_rollout_tick_jvp_device: one tick forwards in k directions, on the tape of rollout_tick_vjp_device.  Directions (each None: zero), with the
         column axis behind the batch axis: dDirState[B,k,9], dDirPrevList / dDirPrevListRot / dDirPlan / dDirPlanRot[B,k,2,M,3], dDirModel[B,k,34] float64;
         dDirWrench[B,k,N,6], dDirP[B,k,n_p] float32.  Returns dict(state[B,k,9], list[B,k,2,M,3], list_rot[B,k,2,M,3] float64, x[B,k,n_x] float32 (x=True),
@@ -828,6 +863,16 @@ class BatchSolver:
                    p=torch.empty((B, k, L.np), dtype=f32, device=dev) if p_full else None, sens=torch.empty((B, _capi.SENS), dtype=f32, device=dev))
         dout = CmpcTickDirsOut(self._opt(out["state"], f64, (B, k, 9), "out_state"), out["list"].data_ptr(), out["list_rot"].data_ptr(),
                                out["x"].data_ptr() if x else None, out["rot"].data_ptr() if rot else None, out["p"].data_ptr() if p_full else None)
+        if mm is not None:   # (the mismatch entry; all of it None: the library makes the plain call)
+            hw, fg, dh, dn, dg = mm
+            md = None
+            if dh is not None or dn is not None or dg is not None:
+                md = C.byref(_capi.CmpcTickDirsMismatch(self._opt(dh, f64, (B, k, 6), "dDirHidden"), self._opt(dn, f32, (B, k, 9), "dDirNoise"),
+                                                        self._opt(dg, f64, (B, k), "dDirGain")))
+            ph, pg = self._opt(hw, f32, (B, 6), "hidden_wrench"), self._opt(fg, f32, (B,), "force_gain")
+            self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_jvp_mismatch_device(self._h, M, float(now), ct, k, din, dout, out["sens"].data_ptr(),
+                                                                                         ph, pg, md, st))
+            return out
         self._launch(dev, lambda st: self._lib.cmpc_rollout_tick_jvp_device(self._h, M, float(now), ct, k, din, dout, out["sens"].data_ptr(), st))
         return out
 
@@ -1075,12 +1120,15 @@ class BatchSolver:
                      lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, g, r, st))
 
     def rollout_walk_vjp_rows_device(self, tick0, ticks, tape, row0, end_tick, grad_states, carry_state, carry_list, status, grad_X=None, wrench=None,
-                                     dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None, grad_X_rows=None):
+                                     dGradPlan=None, dGradModel=None, carry_list_rot=None, dGradPlanRot=None, grad_rot=None, removed=None, grad_X_rows=None,
+                                     mismatch=None, grad_hidden=None, grad_noise=None, grad_gain=None):
         """rollout_walk_vjp_device on a SEGMENT tape (a few rows, re-used) with WHOLE-WALK arrays: grad_states[T + 1, B, 9], grad_X / wrench / grad_rot
         [T, B, ..] and status / removed [T, B] are indexed by the tick number, the tape by row0 + i for tick tick0 + i.  Each array goes to the library
         as the leading-axis view that starts tick0 - row0 rows in, so that tape row and array row coincide; the call reads and writes rows tick0 ..
         tick0 + ticks - 1 of them (and no other), exactly as rollout_walk_vjp_device does on a whole-walk tape.  The carries and the += outputs as
-        there.  grad_X_rows[rows, B, n_x] float32 (instead of grad_X): the solutions' seeds of this segment alone, indexed like the tape."""
+        there.  grad_X_rows[rows, B, n_x] float32 (instead of grad_X): the solutions' seeds of this segment alone, indexed like the tape.
+        mismatch (plant_mismatch(...)) given: cmpc_rollout_walk_vjp_mismatch_device -- the segment ran under it; grad_hidden[T, B, 6] float64 and
+        grad_noise[T, B, 9] float32 are whole-walk arrays written at the segment's rows, grad_gain[B] float64 is added to in place (each may be None)."""
         import torch
         L, B, N, M = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"])
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
@@ -1102,12 +1150,23 @@ class BatchSolver:
                                 self._opt(dGradPlan, f64, (B, 2, M, 3), "dGradPlan"), self._opt(dGradModel, f64, (B, _capi.MODEL_DOUBLES), "dGradModel"),
                                 view(status, i32, (B,), "status"))
         e = self._opt(end_tick, i32, (B,), "end_tick")
+        if mismatch is None:
+            assert grad_hidden is None and grad_noise is None and grad_gain is None, "mismatch gradients need mismatch"
         if carry_list_rot is None:
             assert dGradPlanRot is None and grad_rot is None and removed is None, "orientation gradients need carry_list_rot"
-            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, tick0, ticks, tape["_c"], row0, e, g, st))
+            if mismatch is None:
+                self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_device(self._h, M, tick0, ticks, tape["_c"], row0, e, g, st))
+                return
+        r = None
+        if carry_list_rot is not None:
+            r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
+                                       view(grad_rot, f64, (B, 2, N, 3), "grad_rot"), view(removed, f32, (B,), "removed"))
+        if mismatch is not None:
+            mg = _capi.CmpcWalkGradsMismatch(view(grad_hidden, f64, (B, 6), "grad_hidden"), view(grad_noise, f32, (B, 9), "grad_noise"),
+                                             self._opt(grad_gain, f64, (B,), "grad_gain"))
+            self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_mismatch_device(
+                self._h, M, tick0, ticks, tape["_c"], row0, e, g, C.byref(r) if r is not None else None, C.byref(mismatch["_c"]), C.byref(mg), st))
             return
-        r = _capi.CmpcWalkGradsRot(self._opt(carry_list_rot, f64, (B, 2, M, 3), "carry_list_rot"), self._opt(dGradPlanRot, f64, (B, 2, M, 3), "dGradPlanRot"),
-                                   view(grad_rot, f64, (B, 2, N, 3), "grad_rot"), view(removed, f32, (B,), "removed"))
         self._launch(carry_state.device, lambda st: self._lib.cmpc_rollout_walk_vjp_rot_device(self._h, M, tick0, ticks, tape["_c"], row0, e, g, r, st))
 
     # ---- the state of a walk between two ticks (include/cmpc.h, cmpc_walk_snapshot) ----
@@ -1192,6 +1251,20 @@ class BatchSolver:
         dir_plan / dir_plan_rot[B, k, 2, M, 3], dir_model[B, k, 34] float64, dir_wrench[rows, B, k, N, 6], dir_p[rows, B, k, n_p] float32 (None: zero);
         dir_x[rows, B, k, n_x] float32 (or None), status[rows, B] int32 and removed[rows, B] float32 (or None) are written row by row.  end_tick: int32
         [B] (a walk record's) or None."""
+        self._rollout_walk_jvp(tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, carry_list_rot, dir_plan, dir_plan_rot, dir_wrench,
+                               dir_model, dir_p, dir_x, removed, None)
+
+    def rollout_walk_jvp_mismatch_device(self, tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, mismatch=None, dir_hidden=None,
+                                         dir_noise=None, dir_gain=None, carry_list_rot=None, dir_plan=None, dir_plan_rot=None, dir_wrench=None, dir_model=None,
+                                         dir_p=None, dir_x=None, removed=None):
+        """cmpc_rollout_walk_jvp_mismatch_device: rollout_walk_jvp_device on a walk that ran under `mismatch` (plant_mismatch(...); None: none was applied and
+        only the directions are), with the directions of its three parts, rows as the tape's: dir_hidden[rows, B, k, 6] float64, dir_noise[rows, B, k, 9]
+        float32, dir_gain[B, k] float64 (each may be None: zero).  All four None: the call above, bit for bit."""
+        self._rollout_walk_jvp(tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, carry_list_rot, dir_plan, dir_plan_rot, dir_wrench,
+                               dir_model, dir_p, dir_x, removed, (mismatch, dir_hidden, dir_noise, dir_gain))
+
+    def _rollout_walk_jvp(self, tick0, ticks, tape, row0, end_tick, k, dir_states, carry_list, status, carry_list_rot, dir_plan, dir_plan_rot, dir_wrench,
+                          dir_model, dir_p, dir_x, removed, mm):
         import torch
         L, B, N, M, R, k = self.layout, self.batch, self.cfg.N, int(tape["max_contacts"]), int(tape["rows"]), int(k)
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
@@ -1203,7 +1276,14 @@ class BatchSolver:
                                self._opt(dir_x, f32, (R, B, k, L.nx), "dir_x"), self._opt(status, i32, (R, B), "status"),
                                self._opt(removed, f32, (R, B), "removed"))
         e = self._opt(end_tick, i32, (B,), "end_tick")
-        self._launch(dir_states.device, lambda st: self._lib.cmpc_rollout_walk_jvp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, k, d, st))
+        if mm is None:
+            self._launch(dir_states.device, lambda st: self._lib.cmpc_rollout_walk_jvp_device(self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, k, d, st))
+            return
+        mismatch, dir_hidden, dir_noise, dir_gain = mm
+        md = _capi.CmpcWalkDirsMismatch(self._opt(dir_hidden, f64, (R, B, k, 6), "dir_hidden"), self._opt(dir_noise, f32, (R, B, k, 9), "dir_noise"),
+                                        self._opt(dir_gain, f64, (B, k), "dir_gain"))
+        self._launch(dir_states.device, lambda st: self._lib.cmpc_rollout_walk_jvp_mismatch_device(
+            self._h, M, int(tick0), int(ticks), tape["_c"], int(row0), e, k, d, C.byref(mismatch["_c"]) if mismatch is not None else None, C.byref(md), st))
 
     def rollout_walk_jvp_gate_device(self, gate, device=None):
         """cmpc_rollout_walk_jvp_gate_device: one gate step of the forward walk as one launch; gate: a _capi.CmpcWalkJvpGate of device pointers."""
