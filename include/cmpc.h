@@ -826,8 +826,10 @@ int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, c
  * While the call queues, the ended mask is rec->dEndTick itself; the handle's own setting is saved and restored.  io->tick.dWrench is not read.
  * CMPC_ERR_ARG before anything is queued: max_contacts > 16 (the first tick uses the front kernel's LDS stage), io->dWrenchTicks set (the schedule is the
  * per-trial one), rec NULL or with too few rows, io->tick.dState != io->tick.dStateOut, no dOk, and what cmpc_rollout_walk_device and
- * cmpc_rollout_refill_device refuse.  Tapes, gradients and forward mode are out of scope: no entry point takes a refill together with them; per-trial
- * models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL; trials that
+ * cmpc_rollout_refill_device refuse.  Tapes, gradients and forward mode are out of scope: no entry point takes a refill together with them.  (What is
+ * now in: cmpc_rollout_walk_refill_taped_device tapes a refill walk slot-major and cmpc_rollout_tape_regroup_device gathers every trial's rows into a tape
+ * of its own, on which the reverse and the forward walks run as they are -- behind the snapshot section; orientation and reference gradients, checkpoints
+ * and trials from a snapshot stay out.)  Per-trial models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL; trials that
  * start from a snapshot of a walk in progress instead of standing are cmpc_rollout_walk_refill_snapshot_device's (behind the snapshot section). */
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream);
@@ -1147,6 +1149,55 @@ int cmpc_rollout_walk_refill_snapshot_device(cmpc_handle h, int max_contacts, in
  * or a NULL required array in them, horizon, batch or max_contacts < 1, tick < 0, trials < 0, live->lists_in not 0 or 1. */
 int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* refill,
                                 const cmpc_walk_refill_snapshot* from);
+/* ---- the refill walk taped, and its tape regrouped by trial (DESIGN.md 7f "Refill, taped") ----
+ * cmpc_rollout_walk_refill_trials_device with a row of a device tape behind every tick: behind each tick's record launch come part 2 of
+ * cmpc_rollout_tape_device -- the copy kernel -- and the multiplier call, SEVEN launches a tick.  Tick tick0 + i writes tape row tape_row0 + i, SLOT-major:
+ * column b of a row holds whatever trial sat in slot b at that tick.  Part 1 is never queued: the state a spawned trial starts from is refill->dState0[q],
+ * and the regroup below supplies it (dStates[0] of a tape that starts at tape_row0 == 0 is left as allocated).  io->tick.dOk and the planner's times are
+ * taped on every tick: every tick is queued as a merge tick.  Every output of the trials call is bit-identical; tape == NULL: the trials call itself.
+ * No existing kernel changes, and there is no snapshot variant: trials that start from a pool stay untaped.
+ * CMPC_ERR_ARG before anything is queued: what the trials call refuses without a handle, in its order; then an incomplete tape, a tape with too few rows
+ * (tape_row0 < 0 or tape_row0 + ticks > tape->rows), tape scalars that disagree with io (plant_step, plant_substeps, force_sample_time); then a NULL
+ * handle; the multiplier output off (cmpc_set_multiplier_output before the walk); and the rest of what the trials call refuses. */
+int cmpc_rollout_walk_refill_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
+                                          const cmpc_walk_tape* tape, int tape_row0, void* stream);
+/* Regroup by trial: a tape row does not need to know its trial -- the refill launch records, per trial, the slot, the start tick, the ticks recorded and
+ * the local end tick, and that is enough to gather a trial's rows out of the slot-major tape.  ONE launch copies up to B trials into a tape `dst` of
+ * refill->trial_ticks rows of B columns whose row r is the trial's LOCAL tick r and whose row 0 is a cold first tick (dst->first_row_is_first_tick = 1, the
+ * caller's to set, like its other scalars): a taped walk of its own, on which cmpc_rollout_walk_vjp[_mismatch]_device and cmpc_rollout_walk_jvp[_mismatch]_device
+ * run unchanged with tick0 = 0 and dEndTick = dEndOut.  The refill's archive pass (cmpc_rollout_refill_device with dStateLive == NULL) must have run behind
+ * the walk's last tick.  sizeof(cmpc_walk_tape_regroup) == 32 (LP64; the ctypes mirror is held to it).
+ * The rule for destination column j with trial q = dTrialIndex[j], s = dTrialSlot[q], t0 = dTrialStart[q] - tick_first, n = dTrialTicks[q],
+ * e = dTrialEndTick[q]; every choice is a select, and repeated indices are allowed:
+ *   - a started trial (n >= 1): destination row r (0 <= r < trial_ticks) takes the bit copy of source row t0 + min(r, n - 1), column s, of dX, dP, dLamG,
+ *     dInfo, dOk, dLand, dListT, dListN, dPlanT and dPlanN; the rows past the trial's last recorded one repeat that row (what a walk of its own that
+ *     takes ended problems out of its launches holds there).  Row 0's dPlanT and dPlanN are written zero: a first tick of a walk of its own leaves them as
+ *     allocated, and the reverse never reads them.  States: dst.dStates[0][j] = dState0[q], dst.dStates[r + 1][j] = src.dStates[t0 + min(r, n - 1) + 1][s].
+ *     dEndOut[j] = e if e >= 0; else n if n < trial_ticks -- the walk's end cut the trial off: its good ticks are i < n and its states 0 .. n exist, the
+ *     convention of cmpc_rollout_walk_vjp_device; else -1.  dOkOut[j] = 1.
+ *   - a trial never started (n == 0, slot -1): dStates[0][j] = dState0[q], dEndOut[j] = 0, dOkOut[j] = 1; nothing else is written.
+ *   - no trial for the column -- an index outside [0, refill->trials), a slot outside the batch, or a needed source row outside [0, src->rows):
+ *     dEndOut[j] = 0, dOkOut[j] = 0; nothing else is written.  The walks' gates select and never multiply, so the unwritten rows of a column whose end
+ *     tick is 0 cannot reach a result.
+ * The rule is one function shared by the kernel and the host form.  The kernel: one workgroup per (destination row, destination column); the four trial
+ * words are read once per workgroup; rows of 64 words and more go as 16-byte pieces aligned on the destination with single-word heads and tails (n_x, n_p
+ * and n_g are not multiples of four at every N), the scheme of cmpc_rollout_snapshot_device; no LDS, no barrier, no atomics.  Pure bandwidth: about 12 KB
+ * in and out per trial-tick at N = 20.
+ * CMPC_ERR_ARG before anything is queued, the checks that need no handle first (they are the host form's too): a NULL argument or required array
+ * (dTrialIndex, dEndOut; with trials > 0 dState0, dTrialSlot, dTrialStart, dTrialTicks, dTrialEndTick); incomplete tapes; dst->rows != refill->trial_ticks;
+ * refill->trials < 0; a destination array that is also a source array; max_contacts < 1.  Then a NULL handle, and more than 65535 rows. */
+typedef struct cmpc_walk_tape_regroup {
+    int tick_first;                 /* the tick number source row 0 holds */
+    const int* dTrialIndex;         /* [B] the trial of destination column j; outside [0, trials): none */
+    int* dEndOut;                   /* [B] the end tick the reverse / forward walk is to be given */
+    int* dOkOut;                    /* [B] or NULL: 1 / 0 */
+} cmpc_walk_tape_regroup;
+int cmpc_rollout_tape_regroup_device(cmpc_handle h, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
+                                     const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst, void* stream);
+/* the same on the host: host buffers throughout (refill's and g's arrays too); no handle, no GPU.  Bit-equal to the kernel. */
+int cmpc_rollout_tape_regroup(int horizon, int batch, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
+                              const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst);
 /* The reverse walk: `ticks` calls of cmpc_rollout_tick_vjp_device (called, not copied: its workspace, statuses and zero rule for flagged problems hold),
  * last row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of cmpc_walk_vjp_gate_kernel).  Tick number tick0 + i is row
  * row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time.

@@ -87,6 +87,12 @@ class CmpcWalkRefillSnapshot(C.Structure):
     _fields_ = [("pool", C.c_void_p), ("pool_batch", C.c_int), ("dTrialSnapshot", C.c_void_p), ("dTrialSnapshotOk", C.c_void_p)]
 
 
+class CmpcWalkTapeRegroup(C.Structure):
+    """mirror of cmpc_walk_tape_regroup (include/cmpc.h): which trial each column of a regrouped tape takes, and the end ticks and flags that come back;
+    32 bytes"""
+    _fields_ = [("tick_first", C.c_int), ("dTrialIndex", C.c_void_p), ("dEndOut", C.c_void_p), ("dOkOut", C.c_void_p)]
+
+
 STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
 
 
@@ -238,6 +244,7 @@ EXPORTS = [
     "cmpc_plant_step_jvp_mismatch_cols_device", "cmpc_rollout_tick_jvp_mismatch_device", "cmpc_rollout_walk_jvp_mismatch_device",
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
+    "cmpc_rollout_walk_refill_taped_device", "cmpc_rollout_tape_regroup_device", "cmpc_rollout_tape_regroup",
     "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
 ]
 
@@ -416,6 +423,12 @@ def lib():
                 fs = C.POINTER(CmpcWalkRefillSnapshot)
                 L.cmpc_rollout_walk_refill_snapshot_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), fs, i, i, ip, vp]
                 L.cmpc_rollout_refill_restore.argtypes = [i, i, i, i, C.POINTER(CmpcWalkSnapshot), fl, fs]
+            if hasattr(L, "cmpc_rollout_walk_refill_taped_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+                tp, rg = C.POINTER(CmpcWalkTape), C.POINTER(CmpcWalkTapeRegroup)
+                L.cmpc_rollout_walk_refill_taped_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), i, i, ip,
+                                                                    tp, i, vp]
+                L.cmpc_rollout_tape_regroup_device.argtypes = [vp, i, tp, fl, rg, tp, vp]
+                L.cmpc_rollout_tape_regroup.argtypes = [i, i, i, tp, fl, rg, tp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

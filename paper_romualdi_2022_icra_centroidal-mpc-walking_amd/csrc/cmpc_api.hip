@@ -1786,7 +1786,7 @@ int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int ti
 
 static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream);
+                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape = nullptr, int tape_row0 = 0);
 
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
@@ -1812,12 +1812,23 @@ int cmpc_rollout_walk_refill_snapshot_device(cmpc_handle h, int max_contacts, in
     return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, from, row0, lists_in, lists_out, stream);
 }
 
+// the trials call with a tape row behind every tick (include/cmpc.h); tape null: the trials call itself
+int cmpc_rollout_walk_refill_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
+                                          const cmpc_walk_tape* tape, int tape_row0, void* stream)
+{
+    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream, tape, tape_row0);
+}
+
 // from (cmpc_walk_refill_snapshot) null: the walk above.  Else the trials start from pool rows: a sixth launch per tick, the restore, behind the refill; the
 // front and back kernels and the record take the pool's tick as the offset of every slot's local tick, and no problem of any solve is on a first tick (the
 // solve is launched without the slots' start ticks: warm for all)
+// tape (cmpc_rollout_walk_refill_taped_device; never together with from) non-null: part 2 of the tape behind every tick's record -- the copy kernel and the
+// multiplier call, seven launches a tick -- tick tick0 + i into row tape_row0 + i, slot-major.  Part 1 is never queued: the state a spawned trial starts
+// from is dState0[q], which the regroup supplies.  dOk and the planner's times go on every tick: every tick is queued as a merge tick
 static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream)
+                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape, int tape_row0)
 {
     // (the refusals that need no handle come first: they are the same with and without one)
     if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
@@ -1835,7 +1846,16 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
         if (const char* why = restore_refusal(from, refill->trials, &live))
             return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_refill_snapshot_device: ") + why);
     }
+    if (tape) {
+        if (!tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: incomplete tape");
+        if (tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
+            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape has too few rows");
+        if (tape->plant_step != k.plant_step || tape->plant_substeps != k.plant_substeps || (tape->force_sample_time != 0) != (k.force_sample_time != 0))
+            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape's scalars do not agree with the walk");
+    }
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
+    if (tape && (!h->mult_out || !h->dDuals))
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
         !k.box_upper || !k.box_lower || !k.dState || !k.dStateOut || k.dState != k.dStateOut || !k.dPlanT || !k.dPlanPose || !k.dPlanN || !k.dOk || !k.dLand ||
         !k.dInfo || !k.dP || !k.dX0 || !k.dX || !(k.plant_step > 0) || k.plant_substeps < 1)
@@ -1919,6 +1939,9 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
         a.start = refill->dStartTick;
         lrc = cmpc_launch_rollout_record(&a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
         rc = launch_status(h, "refill walk record", lrc);
+        if (rc == CMPC_OK && tape)
+            rc = rollout_tape_impl(h, max_contacts, tape_row0 + i, 2, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, nullptr, k.dStateOut, k.dPlanT, k.dPlanN, set_t[cur],
+                                   set_n[cur], tape, stream);
     }
     h->timing = timing;
     h->dEnded = ended_saved;
@@ -1989,6 +2012,81 @@ int cmpc_rollout_snapshot_device(cmpc_handle h, int max_contacts, int src_batch,
     HIPCHK(h, hipSetDevice(h->device));
     const int lrc = cmpc_launch_rollout_snapshot(&a, stream_of(h, stream));
     return launch_status(h, "walk snapshot", lrc);
+}
+
+// ---- the tape of a refill walk regrouped by trial (include/cmpc.h, cmpc_walk_tape_regroup): one copy kernel ----
+static_assert(sizeof(cmpc_walk_tape_regroup) == 32, "cmpc_walk_tape_regroup: the size include/cmpc.h states");
+// the 11 arrays of a cmpc_walk_tape in the struct's order
+static void tape_pointers(const cmpc_walk_tape& t, const void* out[11])
+{
+    const void* const p[11] = {t.dX, t.dP, t.dLamG, t.dInfo, t.dStates, t.dOk, t.dLand, t.dPlanT, t.dListT, t.dPlanN, t.dListN};
+    for (int i = 0; i < 11; ++i) out[i] = p[i];
+}
+// what is refused without a handle, in the header's order; null: nothing
+static const char* regroup_refusal(int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* r, const cmpc_walk_tape_regroup* g,
+                                   const cmpc_walk_tape* dst)
+{
+    if (!src || !r || !g || !dst) return "null argument";
+    if (!g->dTrialIndex || !g->dEndOut) return "dTrialIndex or dEndOut is NULL";
+    if (r->trials > 0 && (!r->dState0 || !r->dTrialSlot || !r->dTrialStart || !r->dTrialTicks || !r->dTrialEndTick))
+        return "a required array of the refill is NULL (dState0, dTrialSlot, dTrialStart, dTrialTicks, dTrialEndTick)";
+    if (!tape_complete(src) || !tape_complete(dst)) return "incomplete tape";
+    if (dst->rows != r->trial_ticks) return "the destination tape must have refill->trial_ticks rows";
+    if (r->trials < 0) return "a negative count of trials";
+    const void* sp[11];
+    const void* dp[11];
+    tape_pointers(*src, sp);
+    tape_pointers(*dst, dp);
+    for (int i = 0; i < 11; ++i)
+        for (int j = 0; j < 11; ++j)
+            if (dp[i] == sp[j]) return "a destination array is also a source array";
+    if (max_contacts < 1) return "max_contacts must be at least 1";
+    return nullptr;
+}
+static void regroup_args(int N, int B, int M, const cmpc_walk_tape* s, const cmpc_walk_refill* r, const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* d,
+                         CmpcRegroupArgs& a)
+{
+    CmpcLayout L;
+    cmpc_layout_init(L, N);
+    a.B = B; a.rows = d->rows; a.src_rows = s->rows; a.Q = r->trials; a.tick_first = g->tick_first;
+    a.index = g->dTrialIndex;
+    a.slot = r->dTrialSlot; a.start = r->dTrialStart; a.ticks = r->dTrialTicks; a.end = r->dTrialEndTick;
+    a.state0 = reinterpret_cast<const unsigned*>(r->dState0);
+    a.end_out = g->dEndOut; a.ok_out = g->dOkOut;
+    int n = 0;
+    auto add = [&](const void* sp, void* dp, int words) {
+        a.src[n] = static_cast<const unsigned*>(sp); a.dst[n] = static_cast<unsigned*>(dp); a.words[n] = words;
+        ++n;
+    };
+    add(s->dX, d->dX, L.nx); add(s->dP, d->dP, L.np); add(s->dLamG, d->dLamG, L.ng); add(s->dInfo, d->dInfo, CMPC_INFO);
+    add(s->dOk, d->dOk, 1); add(s->dLand, d->dLand, 2); add(s->dListT, d->dListT, 8 * M); add(s->dListN, d->dListN, 2);
+    add(s->dPlanT, d->dPlanT, 8 * M); add(s->dPlanN, d->dPlanN, 2);   // (CMPC_REGROUP_PLAN: the planner's rows come last)
+    a.src_states = reinterpret_cast<const unsigned*>(s->dStates); a.dst_states = reinterpret_cast<unsigned*>(d->dStates);
+}
+
+int cmpc_rollout_tape_regroup(int horizon, int batch, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
+                              const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst)
+{
+    if (const char* why = regroup_refusal(max_contacts, src, refill, g, dst)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_tape_regroup: ") + why);
+    if (horizon < 1 || batch < 1) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup: bad horizon or batch");
+    CmpcRegroupArgs a;
+    regroup_args(horizon, batch, max_contacts, src, refill, g, dst, a);
+    cmpc_regroup_host(a);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_tape_regroup_device(cmpc_handle h, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
+                                     const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst, void* stream)
+{
+    if (const char* why = regroup_refusal(max_contacts, src, refill, g, dst))
+        return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_tape_regroup_device: ") + why);
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup_device: null handle");
+    if (dst->rows > 65535) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup_device: more than 65535 rows (one workgroup per row and column)");
+    CmpcRegroupArgs a;
+    regroup_args(h->cfg.horizon, h->B, max_contacts, src, refill, g, dst, a);
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_rollout_tape_regroup(&a, stream_of(h, stream));
+    return launch_status(h, "tape regroup", lrc);
 }
 
 // ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags

@@ -479,6 +479,68 @@ inline void cmpc_refill_restore_host(const CmpcRefillRestoreArgs& a)
     }
 }
 
+// ---- the tape of a refill walk regrouped by trial (include/cmpc.h, cmpc_walk_tape_regroup; DESIGN.md 7f "Refill, taped"): destination column j of a tape of
+// trial_ticks rows receives the rows of trial index[j] out of the slot-major tape.  Bit copies; every array goes as rows of 32-bit words (a double is two).
+// The table's order: X, P, lam_g, info, ok, land, list_t, list_n, then plan_t and plan_n (CMPC_REGROUP_PLAN .. : written zero on destination row 0).
+#define CMPC_REGROUP_ARRAYS 10
+#define CMPC_REGROUP_PLAN 8
+struct CmpcRegroupArgs {
+    int B, rows, src_rows, Q, tick_first;          // rows: the destination's = trial_ticks
+    const int* index;                              // [B] dTrialIndex
+    const int* slot; const int* start; const int* ticks; const int* end;   // [Q] dTrialSlot, dTrialStart, dTrialTicks, dTrialEndTick
+    const unsigned* state0;                        // [Q][9]
+    int* end_out; int* ok_out;                     // [B]; ok_out may be null
+    const unsigned* src[CMPC_REGROUP_ARRAYS]; unsigned* dst[CMPC_REGROUP_ARRAYS]; int words[CMPC_REGROUP_ARRAYS];   // words: per problem and row
+    const unsigned* src_states; unsigned* dst_states;   // [rows + 1][B][9]
+};
+// what column j is: kind 0 no trial (an index outside the queue, a slot outside the batch, or a needed source row outside the tape), 1 a trial never started,
+// 2 a started trial of n recorded ticks whose local tick 0 is source row t0 of column s.  end: the end tick the reverse / forward walk is given -- the
+// trial's own if it ended, n for a trial the walk's end cut off (good ticks i < n, states 0 .. n), else -1.  Every choice is a select.
+struct CmpcRegroupColumn { int kind, q, s, t0, n, end; };
+__host__ __device__ inline CmpcRegroupColumn cmpc_regroup_column(const CmpcRegroupArgs& a, int j)
+{
+    CmpcRegroupColumn c{0, a.index[j], -1, 0, 0, 0};
+    if (c.q < 0 || c.q >= a.Q) return c;
+    c.n = a.ticks[c.q];
+    c.s = a.slot[c.q];
+    if (c.n < 1) { c.kind = 1; return c; }
+    const long long t0 = (long long)a.start[c.q] - a.tick_first;
+    const int last = (c.n < a.rows ? c.n : a.rows) - 1;     // the last source row taken, local
+    if (c.s < 0 || c.s >= a.B || t0 < 0 || t0 + last >= a.src_rows) return c;
+    const int e = a.end[c.q];
+    c.kind = 2; c.t0 = (int)t0;
+    c.end = e >= 0 ? e : c.n < a.rows ? c.n : -1;
+    return c;
+}
+// the source row of destination row r of a started column: rows past the trial's last recorded one repeat that row
+__host__ __device__ inline int cmpc_regroup_source_row(const CmpcRegroupColumn& c, int r)
+{
+    return c.t0 + (r < c.n - 1 ? r : c.n - 1);
+}
+// the host form's loop (cmpc_rollout_tape_regroup); here for the reason cmpc_refill_host is
+inline void cmpc_regroup_host(const CmpcRegroupArgs& a)
+{
+    const size_t B = (size_t)a.B;
+    for (int j = 0; j < a.B; ++j) {
+        const CmpcRegroupColumn c = cmpc_regroup_column(a, j);
+        a.end_out[j] = c.kind == 2 ? c.end : 0;
+        if (a.ok_out) a.ok_out[j] = c.kind == 0 ? 0 : 1;
+        if (c.kind == 0) continue;
+        __builtin_memcpy(a.dst_states + 9 * (size_t)j, a.state0 + 9 * (size_t)c.q, sizeof(unsigned) * 9);
+        if (c.kind == 1) continue;
+        for (int r = 0; r < a.rows; ++r) {
+            const size_t sr = (size_t)cmpc_regroup_source_row(c, r);
+            for (int i = 0; i < CMPC_REGROUP_ARRAYS; ++i) {
+                const size_t w = (size_t)a.words[i];
+                unsigned* const d = a.dst[i] + w * ((size_t)r * B + j);
+                if (r == 0 && i >= CMPC_REGROUP_PLAN) __builtin_memset(d, 0, sizeof(unsigned) * w);
+                else __builtin_memcpy(d, a.src[i] + w * (sr * B + c.s), sizeof(unsigned) * w);
+            }
+            __builtin_memcpy(a.dst_states + 9 * (((size_t)r + 1) * B + j), a.src_states + 9 * ((sr + 1) * B + c.s), sizeof(unsigned) * 9);
+        }
+    }
+}
+
 // ---- the reverse walk's rule for ended problems (include/cmpc.h, cmpc_rollout_walk_vjp_device).  One statement for the host form and the
 // kernel (contraction off: the one sum is a plain double add).  A gate step sits between two reverse ticks: its POST part finishes tick `tick_post`
 // (row_post) from what cmpc_rollout_tick_vjp_device left, its PRE part prepares tick `tick_pre` (row_pre).  Either part may be absent (do_post / do_pre).

@@ -57,6 +57,7 @@ int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, con
 int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream);
 int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
+int cmpc_launch_rollout_tape_regroup(const CmpcRegroupArgs* a, hipStream_t stream);
 int cmpc_launch_walk_vjp_gate(const CmpcGateArgs* a, hipStream_t stream);
 size_t cmpc_walk_gate_wide_entries(const CmpcGateArgs* a);
 int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t stream);

@@ -828,6 +828,39 @@ __global__ __launch_bounds__(256) void cmpc_refill_restore_kernel(CmpcRefillRest
     }
 }
 
+// regroup (cmpc_rollout_tape_regroup_device): one workgroup per (destination row, destination column) of a tape of trial_ticks rows; the column's rule
+// (cmpc_regroup_column: the four trial words, read once per workgroup) is workgroup-uniform.  A started column's row r is the bit copy of source row
+// t0 + min(r, n - 1), column s, array by array through the snapshot kernel's row copy (snap_row: 16-byte pieces aligned on the destination for the rows of
+// 64 words and more); the planner's rows of destination row 0 are written zero.  The workgroup of row 0 also writes the column's words -- the end tick, the
+// flag and dStates[0] = dState0[q].  A column without a trial, and every row but 0 of a trial never started, costs its workgroup the index and at most three
+// scalar loads.  Bandwidth-bound (about 12 KB in and out per row and column at N = 20): no LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_rollout_tape_regroup_kernel(CmpcRegroupArgs a)
+{
+    const int j = blockIdx.x, r = blockIdx.y;   // (the grid is B x rows workgroups: nothing runs past either)
+    const int tid = threadIdx.x;
+    const CmpcRegroupColumn c = cmpc_regroup_column(a, j);
+    const size_t B = (size_t)a.B;
+    if (r == 0) {
+        if (tid == 0) {
+            a.end_out[j] = c.kind == 2 ? c.end : 0;
+            if (a.ok_out) a.ok_out[j] = c.kind == 0 ? 0 : 1;
+        }
+        if (c.kind != 0 && tid < 9) a.dst_states[9 * (size_t)j + tid] = a.state0[9 * (size_t)c.q + tid];
+    }
+    if (c.kind != 2) return;                    // (uniform)
+    const size_t sr = (size_t)cmpc_regroup_source_row(c, r);
+    for (int i = 0; i < CMPC_REGROUP_ARRAYS; ++i) {
+        const int w = a.words[i];
+        unsigned* const d = a.dst[i] + (size_t)w * ((size_t)r * B + j);
+        if (r == 0 && i >= CMPC_REGROUP_PLAN) {
+            for (int e = tid; e < w; e += 256) d[e] = 0u;
+        } else {
+            snap_row(d, a.src[i] + (size_t)w * (sr * B + c.s), w, tid);
+        }
+    }
+    if (tid < 9) a.dst_states[9 * (((size_t)r + 1) * B + j) + tid] = a.src_states[9 * ((sr + 1) * B + c.s) + tid];
+}
+
 // gate: one thread per problem for the small arrays (cmpc_walk_gate_problem; lanes past B do nothing), then every thread strides over the wide rows
 // (cmpc_walk_gate_wide).  The two parts touch disjoint arrays: no barrier, no atomics.
 __global__ __launch_bounds__(256) void cmpc_walk_vjp_gate_kernel(CmpcGateArgs a, size_t wide)
@@ -878,6 +911,12 @@ extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream
 extern "C" int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_refill_restore_kernel, dim3(a->copy.B), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_rollout_tape_regroup(const CmpcRegroupArgs* a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_rollout_tape_regroup_kernel, dim3(a->B, a->rows), dim3(256), 0, stream, *a);
     return (int)hipGetLastError();
 }
 

@@ -199,7 +199,8 @@ class WalkingRollout:
         Per-trial models and a per-trial plant mismatch (hidden pushes, noise, a force gain): walk_device_refill_trials(), a method of its own because this
         signature is pinned; here the models are the slot's and mismatch= is refused.  Trials that start from a snapshot of a walk in progress instead of
         standing at tick 0 (warm from their first tick): walk_device_refill_from_snapshot().
-        Out of scope: gradients and forward mode through a refill walk, and -- NotImplementedError, raised before anything touches a GPU -- replan,
+        A tape behind every tick and every trial's gradient: walk_device_refill_taped() and backward_device_refill().
+        Out of scope: gradients and forward mode through a refill walk of THIS method, and -- NotImplementedError, raised before anything touches a GPU -- replan,
         mismatch= (see above), taped=True, every (snapshots and checkpoints), and lists longer than 16 contacts."""
         for name, value in (("replan", replan), ("mismatch", mismatch), ("taped", taped or None), ("every", every)):
             if value is not None:
@@ -228,21 +229,36 @@ class WalkingRollout:
         trial when models is None).  With models=None and nothing in mismatch: walk_device_refill, bit for bit.
         Afterwards the roll-out's own models are back (self.models through set_models_device, or none): a later walk_device on this object is bit-equal
         to one made before the call.  Out of scope, as for walk_device_refill: gradients, tapes, forward mode, snapshots, replan, lists longer than 16
-        contacts (NotImplementedError)."""
+        contacts (NotImplementedError).  The same walk with a tape behind every tick, for backward_device_refill(): walk_device_refill_taped()."""
+        return WalkingRollout._walk_refill_trials(self, "walk_device_refill_trials", False, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs)
+
+    def walk_device_refill_taped(self, ticks, trial_ticks, com0, dcom0, h0, models=None, mismatch=None, **kwargs):
+        """walk_device_refill_trials(ticks, trial_ticks, com0, dcom0, h0, models, mismatch, **kwargs) through cmpc_rollout_walk_refill_taped_device
+        (include/cmpc.h; DESIGN.md 7f "Refill, taped"): every tick also writes its row of a device tape, seven launches a tick, still no host read.  The
+        multiplier output is turned on first, as walk_device_taped does (x and info are bit-identical with it on): every key walk_device_refill_trials
+        returns is bit-equal to it.  The dict gains "tape": walk_device_taped's stacked tensors, `ticks` rows, SLOT-major -- column b of row t holds whatever
+        trial sat in slot b at tick t -- plus what the reverse needs kept alive: refill (the queue's arrays), state0 [Q, 9], models [Q, 34] or None,
+        mismatch (the per-trial schedules and gains), trial_ticks, dt, push_ticks.  backward_device() does not take this dict: refill_trial_walk() regroups
+        up to B trials into a taped walk of their own, and backward_device_refill() does that for every trial of the queue.  (A method of its own:
+        walk_device_refill's signature is pinned and its taped=True keeps raising.)  Out of scope: trials from a snapshot, replan, checkpoints, lists longer
+        than 16 contacts (NotImplementedError)."""
+        return WalkingRollout._walk_refill_trials(self, "walk_device_refill_taped", True, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs)
+
+    def _walk_refill_trials(self, who, taped, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs):
         mismatch = dict(mismatch or {})
         if int(mismatch.pop("tick_first", 0)) != 0:
-            raise ValueError("walk_device_refill_trials: the schedules' rows are the trial's local ticks, so tick_first must be 0")
+            raise ValueError(f"{who}: the schedules' rows are the trial's local ticks, so tick_first must be 0")
         for given, known in ((kwargs, ("push", "push_ticks", "wrench_trials", "trace", "stop")), (mismatch, ("hidden_wrench", "state_noise", "force_gain"))):
             for k in given:
                 if k not in known:
-                    raise TypeError(f"walk_device_refill_trials: unexpected argument {k!r}")
+                    raise TypeError(f"{who}: unexpected argument {k!r}")
         if self.M > 16:
-            raise NotImplementedError("walk_device_refill_trials: lists longer than 16 contacts are out of scope (a slot's first tick uses the front kernel's "
+            raise NotImplementedError(f"{who}: lists longer than 16 contacts are out of scope (a slot's first tick uses the front kernel's "
                                       "LDS stage; with force_sample_time the snap runs there too)")
         args = dict(push=None, push_ticks=0, wrench_trials=None, trace=True, stop=("merge", "solver", "nonfinite"))
         args.update(kwargs)
         if args["push"] is not None and args["wrench_trials"] is not None:
-            raise ValueError("walk_device_refill_trials: push or wrench_trials, not both")
+            raise ValueError(f"{who}: push or wrench_trials, not both")
         assert ticks >= 1 and trial_ticks >= 1
 
         def walk():
@@ -251,7 +267,7 @@ class WalkingRollout:
             given = any(data[k] is not None for k in ("models", "hidden_wrench", "state_noise", "force_gain"))
             try:
                 rec = self._walk_refill(ticks, trial_ticks, com0, dcom0, h0, args["push"], args["push_ticks"], args["wrench_trials"], args["trace"],
-                                        args["stop"], trials=data if given else None)
+                                        args["stop"], trials=data if given else None, tape=taped)
             finally:
                 if data["models"] is not None:    # (the table holds each slot's last trial's model: back to the roll-out's own, in stream order)
                     if self.models is not None:
@@ -333,8 +349,9 @@ class WalkingRollout:
             return rec
         return self._queued(walk)
 
-    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None):
+    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None, tape=False):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
+        assert not (tape and pool is not None), "trials that start from a snapshot are not taped"
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
 
@@ -360,6 +377,10 @@ class WalkingRollout:
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         s.outcome_init_device(state, rec)
         fill = s.walk_refill(state0, trial_ticks, wrench_trials, trace_rows=ticks, device=dev)
+        tp = None
+        if tape:    # (as walk_device_taped: the multiplier output on before anything is queued)
+            s.set_multiplier_output(True)
+            tp = s.walk_tape(ticks, self.M, step=dt / self.substeps, substeps=self.substeps, force_sample_time=self.force_sample_time, device=dev)
         # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
         sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
         if pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
@@ -369,9 +390,15 @@ class WalkingRollout:
         else:
             cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
                                                step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
-                                               trials=trials)
+                                               trials=trials, **(dict(tape=tp, tape_row0=0) if tp is not None else {}))
         s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
         del rec["_c"]
+        if tp is not None:    # (slot-major: refill_trial_walk regroups it by trial; the refill's arrays and the per-trial data stay alive with it)
+            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, trial_ticks=int(trial_ticks), refill=fill, state0=state0,
+                      models=None if trials is None else trials["models"],
+                      mismatch=None if trials is None else {k: trials[k] for k in ("hidden_wrench", "state_noise", "force_gain")},
+                      references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
+            rec["tape"] = tp
         trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
         if trace:
             ar = torch.arange(trial_ticks, device=dev)
@@ -816,6 +843,106 @@ class WalkingRollout:
                 s.reference_from_planner_vjp_device(0, T, tape["references"], w["end_tick"], out["grad_P"], out["ref_com"], out["ref_h"])
         cur.wait_stream(ls)
         return out
+
+    # ---- the refill walk's tape regrouped by trial (include/cmpc.h, cmpc_walk_tape_regroup; DESIGN.md 7f, "Refill, taped") ----
+    def _refill_tape_of(self, who, w):
+        """the slot-major tape of w = walk_device_refill_taped(...), or NotImplementedError -- raised before anything touches a GPU"""
+        if "tick0" in w:
+            raise NotImplementedError(f"{who}: trials that start from a snapshot are not taped (walk_device_refill_from_snapshot's dict)")
+        tape = w.get("tape")
+        if tape is None or "refill" not in tape:
+            raise NotImplementedError(f"{who}: needs the dict of walk_device_refill_taped (a refill walk without a tape has nothing to regroup)")
+        if self.M > 16:
+            raise NotImplementedError(f"{who}: lists longer than 16 contacts are out of scope of a refill walk")
+        return tape
+
+    def refill_trial_walk(self, w, trials):
+        """Up to B trials of w = walk_device_refill_taped(...) as a taped walk of their own: ONE launch (cmpc_rollout_tape_regroup_device) gathers trial
+        trials[j]'s rows out of the slot-major tape into column j of a tape of trial_ticks rows -- row r the trial's local tick r, row 0 a cold first tick,
+        rows past the trial's last recorded one repeating it.  trials: up to B trial numbers (a list, numpy or an int32 CUDA tensor; repeats allowed);
+        fewer are padded with -1, a column without a trial.  No host read.
+        -> a dict in the form of walk_device_taped's: tape (rows = trial_ticks, segments [0], push_ticks, dt, references, and -- when the walk ran under
+        a per-trial mismatch -- mismatch: the trials' columns as a plant_mismatch with tick_first = 0), end_tick [B] int32 (the trial's own end tick; n for
+        a trial the walk's end cut off after n ticks; 0 for a trial never started and for a pad column; -1 walked through), ok [B] int32 (0: a pad
+        column) and trials [B] int32.  backward_device(view, ...) and forward_sensitivity_device_mismatch(view, ...) run on it as they are -- with the
+        solver's models set to the trials' rows first when the walk had per-trial models, which backward_device_refill() does."""
+        src = WalkingRollout._refill_tape_of(self, "refill_trial_walk", w)    # (the refusals come before self is used for anything but its list length)
+        torch, B, s = self.torch, self.B, self.solver
+        if isinstance(trials, torch.Tensor):
+            idx = trials.to(self.dev, torch.int32).reshape(-1)
+        else:
+            idx = torch.from_numpy(np.ascontiguousarray(np.asarray(trials, np.int64).reshape(-1), np.int32)).to(self.dev)
+        assert idx.numel() <= B, f"refill_trial_walk: at most {B} trials per view"
+        if idx.numel() < B:
+            idx = torch.cat([idx, torch.full((B - idx.numel(),), -1, dtype=torch.int32, device=self.dev)])
+        idx = idx.contiguous()
+
+        def regroup():
+            dst, end, ok = s.tape_regroup_device(src, src["refill"], idx)
+            dst.update(dt=src["dt"], push_ticks=src["push_ticks"], segments=[0], references=src["references"])
+            mm = src["mismatch"]
+            if mm is not None and any(v is not None for v in mm.values()):
+                Q = int(src["refill"]["trials"])
+                col = idx.clamp(0, max(Q - 1, 0)).to(torch.int64)    # (a pad column takes some trial's rows: its end tick is 0, so nothing of them is read)
+                pick = lambda t, dim: None if t is None else t.index_select(dim, col).contiguous()
+                dst["mismatch"] = s.plant_mismatch(hidden_wrench=pick(mm["hidden_wrench"], 1), state_noise=pick(mm["state_noise"], 1),
+                                                   force_gain=pick(mm["force_gain"], 0), tick_first=0, device=self.dev)
+            return dict(tape=dst, end_tick=end, ok=ok, trials=idx)
+        return self._queued(regroup)
+
+    def backward_device_refill(self, w, grad_states, grad_X=None, rot=False, refs=False, replan=None):
+        """Every trial's gradient of w = walk_device_refill_taped(...): the queue's trials in ascending order, B at a time, each group regrouped
+        (refill_trial_walk) and run through backward_device()'s reverse walk; no host read and no synchronisation.
+        grad_states [trial_ticks + 1, Q, 9] and grad_X [trial_ticks, Q, n_x] (or None): backward_device's seeds with the queue's Q for B, rows the trial's
+        LOCAL ticks.  A trial that ended at local tick e, or that the walk's end cut off after e ticks, contributes its states 0 .. e and its solutions
+        0 .. e - 1; the seeds of its later rows are not read, not even when they are not finite.  A trial never started returns state0 = grad_states[0]
+        and zeros elsewhere.
+        -> state0 [Q, 9], list0 [Q, 2, M, 3], wrench [trial_ticks, Q, N, 6], push [Q, 3], models [Q, 34], plan [Q, 2, M, 3], status [trial_ticks, Q],
+        end_tick [Q] (the effective one: refill_trial_walk's), in backward_device's dtypes; under a per-trial mismatch also hidden_wrench
+        [trial_ticks, Q, 6], state_noise [trial_ticks, Q, 9] and force_gain [Q].  Pad columns are dropped.  A trial's `plan` is the gradient with respect
+        to the planner lists of the SLOT it walked in: sum it by w["trials"]["slot"] for the gradient of a slot's lists.
+        With per-trial models the group's rows go through set_models_device first and the roll-out's own models are back afterwards, as after
+        walk_device_refill_trials.  Every trial's keys are bit-equal to backward_device on a walk_device_taped of its own that holds it in any column
+        with its model and its mismatch columns: the reverse kernels do not depend on the batch position.
+        Out of scope -- NotImplementedError, raised before anything touches a GPU: rot=True and refs=True (the orientation and reference chains read
+        per-slot data that a view does not regroup), replan, lists longer than 16 contacts, and a w of walk_device_refill_from_snapshot."""
+        for name, value in (("rot", rot or None), ("refs", refs or None), ("replan", replan)):
+            if value is not None:
+                raise NotImplementedError(f"backward_device_refill: {name} is out of scope of a taped refill walk")
+        src = WalkingRollout._refill_tape_of(self, "backward_device_refill", w)
+        torch, B, s, L = self.torch, self.B, self.solver, self.L
+        TT, Q = int(src["trial_ticks"]), int(src["refill"]["trials"])
+        as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, dt).contiguous()
+        gS = as_t(grad_states, torch.float64)
+        assert tuple(gS.shape) == (TT + 1, Q, 9)
+        gX = None
+        if grad_X is not None:
+            gX = as_t(grad_X, torch.float32)
+            assert tuple(gX.shape) == (TT, Q, L.nx)
+        batch_dim = dict(wrench=1, status=1, hidden_wrench=1, state_noise=1)    # (every other key has the batch in front)
+        parts = []
+
+        def pad(t):    # [rows, n, ..] -> [rows, B, ..] with zero seeds in the pad columns
+            n = int(t.shape[1])
+            return t if n == B else torch.cat([t, torch.zeros((t.shape[0], B - n) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)], 1).contiguous()
+        try:
+            for q0 in range(0, Q, B):
+                q1 = min(q0 + B, Q)
+                view = self.refill_trial_walk(w, list(range(q0, q1)))
+                if src["models"] is not None:
+                    rows = view["trials"].clamp(0, Q - 1).to(torch.int64)
+                    self._queued(lambda: s.set_models_device(src["models"].index_select(0, rows).contiguous()))
+                out = self._backward_device(view, pad(gS[:, q0:q1]), None if gX is None else pad(gX[:, q0:q1]), False)
+                parts.append({k: v.narrow(batch_dim.get(k, 0), 0, q1 - q0) for k, v in out.items()})
+        finally:
+            if src["models"] is not None:    # (back to the roll-out's own, in stream order)
+                if self.models is not None:
+                    self._queued(lambda: s.set_models_device(self.models))
+                else:
+                    s.set_models(None)
+        if not parts:
+            raise ValueError("backward_device_refill: the queue is empty")
+        return {k: torch.cat([p[k] for p in parts], batch_dim.get(k, 0)) for k in parts[0]}
 
     # ---- snapshots: resume, branch, and the reverse walk in bounded memory (include/cmpc.h, cmpc_walk_snapshot; DESIGN.md 7f, "Snapshots") ----
     def _queued(self, fn):

@@ -1440,12 +1440,16 @@ class BatchSolver:
         return r
 
     def rollout_walk_refill_device(self, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0=0,
-                                   step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False, trials=None):
+                                   step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False, tape=None, tape_row0=0,
+                                   trials=None):
         """cmpc_rollout_walk_refill_device: `ticks` ticks of a refill walk from tick number tick0 in one call -- per tick the refill launch, the tick's three
-        launches and the record -- in place on dState; the other arguments as rollout_walk_device's (no cold_first, wrench_ticks, tape or mismatch: a slot's
+        launches and the record -- in place on dState; the other arguments as rollout_walk_device's (no cold_first, wrench_ticks or mismatch: a slot's
         first tick runs inside the merge launches, and the wrench schedule is refill's per-trial one).  Returns the set that holds the last tick's lists.
         trials (walk_refill_trials(...)): cmpc_rollout_walk_refill_trials_device -- per-trial models and a per-trial plant mismatch; with models the handle
-        is left on its per-problem table, which then holds each slot's last trial's model (set_models[_device] afterwards to go on with one's own)."""
+        is left on its per-problem table, which then holds each slot's last trial's model (set_models[_device] afterwards to go on with one's own).
+        tape (walk_tape(...)): cmpc_rollout_walk_refill_taped_device -- tick i of the call also writes row tape_row0 + i of the tape, SLOT-major (seven
+        launches a tick; the multiplier output must be on); tape_regroup_device gathers a trial's rows out of it.  (tape and tape_row0 stand in front of
+        trials: that the parameter list ends with trials is pinned.)"""
         self._need_refill()
         io = _capi.CmpcWalkIO()
         io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
@@ -1455,6 +1459,14 @@ class BatchSolver:
         out = C.c_int(-1)
         if trials is not None:
             assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
+        if tape is not None:
+            if not hasattr(self._lib, "cmpc_rollout_walk_refill_taped_device"):
+                raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_taped_device")
+            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_taped_device(
+                self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
+                C.byref(trials["_c"]) if trials is not None else None, int(row0), int(lists_in), C.byref(out), C.byref(tape["_c"]), int(tape_row0), st))
+            return out.value
+        if trials is not None:
             self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_trials_device(
                 self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), C.byref(trials["_c"]), int(row0),
                 int(lists_in), C.byref(out), st))
@@ -1510,6 +1522,31 @@ class BatchSolver:
             C.byref(trials["_c"]) if trials is not None else None, C.byref(snapshot["_c"]) if snapshot is not None else None, int(row0), int(lists_in),
             C.byref(out), st))
         return out.value
+
+    def tape_regroup_device(self, src_tape, refill, trial_index, dst_tape=None, tick_first=0):
+        """cmpc_rollout_tape_regroup_device: ONE launch on torch's current stream, no host read -- column j of dst_tape (walk_tape of refill["trial_ticks"]
+        rows with first_row_is_first_tick; None: allocated here with src_tape's scalars) receives the rows of trial trial_index[j] out of the slot-major
+        src_tape of a taped refill walk (rollout_walk_refill_device(tape=...), whose row 0 holds tick tick_first), by the rule at cmpc_walk_tape_regroup in
+        include/cmpc.h.  trial_index: int32 [B] CUDA tensor; an entry outside the queue: no trial.  refill: the walk's walk_refill dict, its archive pass
+        (rollout_refill_device(ticks, rec, refill, None)) queued behind the last tick.
+        -> (dst_tape, end_tick [B] int32 -- what the reverse and the forward walks take as end_tick -- and ok [B] int32, 0 where the column has no trial)."""
+        import torch
+        if not hasattr(self._lib, "cmpc_rollout_tape_regroup_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_tape_regroup_device")
+        B, M = self.batch, int(src_tape["max_contacts"])
+        dev = src_tape["X"].device
+        assert trial_index.is_cuda and trial_index.dtype == torch.int32 and trial_index.is_contiguous() and tuple(trial_index.shape) == (B,), \
+            "trial_index [B] int32"
+        if dst_tape is None:
+            dst_tape = self.walk_tape(int(refill["trial_ticks"]), M, step=src_tape["step"], substeps=src_tape["substeps"],
+                                      force_sample_time=src_tape["force_sample_time"], first_row_is_first_tick=True, device=dev)
+        assert dst_tape["max_contacts"] == M and dst_tape["rows"] == int(refill["trial_ticks"]), "dst_tape: trial_ticks rows of the same list length"
+        end = torch.zeros((B,), dtype=torch.int32, device=dev)
+        ok = torch.zeros((B,), dtype=torch.int32, device=dev)
+        g = _capi.CmpcWalkTapeRegroup(int(tick_first), trial_index.data_ptr(), end.data_ptr(), ok.data_ptr())
+        self._launch(dev, lambda st: self._lib.cmpc_rollout_tape_regroup_device(self._h, M, C.byref(src_tape["_c"]), C.byref(refill["_c"]), C.byref(g),
+                                                                                C.byref(dst_tape["_c"]), st))
+        return dst_tape, end, ok
 
     def shift_solution_device(self, dXprev, dX0):
         """is_warm_start_enabled: dX0 = dXprev shifted by one knot; solve from it with solve_device(..., warm=True)."""
