@@ -161,14 +161,14 @@ struct Ctx {
     float *dS, *dU, *dT, *dZ, *d;
     float *Lf;             // per-stage factor records (REC_N floats each)
     float *geoA;           // N x GEO
-    float *P0, *Qb, *G, *QuuF, *Pan, *Bval, *Aval, *arow, *ybuf, *fpv, *fpn;
+    float *P0, *Qb, *G, *QuuF, *Pan, *Bval, *Aval, *arow, *ybuf, *fpv;
     float *idstrip;        // four strips of 68 floats, a single 1 in each: rows of the identity for the fused factorisation's panel (id_row)
     float *ZT;             // (resident variants) the published W^T of the streaming stage; there QuuF | Pan | Qb exist twice (stride MSET)
     double *QuuD1, *qs1;   // (resident variants) second set of the float64 diagonal blocks and of qs
     int *Brow, *Arow, *qmask;
     unsigned short* tri;
     double *QuuD, *pv, *pn, *qs, *Pd, *sig, *gco, *redd;
-    float* red;
+    float *red, *red1;     // slots of the block reductions: 3 per wave; red1 a second set of them (see block_maxn)
     int* flag;
     int* prog;             // (resident variants) progress words of the two factorising waves, one copy per lane
 };
@@ -312,7 +312,7 @@ __device__ inline void make_ctx(Ctx& c, char* smem, int N, float* fg_base)
     c.geoA = fp; fp += GEO * N;
     c.Bval = fp; fp += 3 * NU; c.Aval = fp; fp += 3 * NS + 3;
     c.arow = fp; fp += 96 + 12; fp += DSET_F;  // (second descriptor set)
-    c.fpv = fp; fp += 40; c.fpn = fp; fp += 40; c.red = fp; fp += 24;
+    c.fpv = fp; fp += 40; c.red1 = fp; fp += 40; c.red = fp; fp += 24;   // (red1: 24 of 40 words that nothing else uses)
     c.Brow = reinterpret_cast<int*>(fp); fp += 3 * NU;
     c.Arow = reinterpret_cast<int*>(fp); fp += 3 * NS + 3; fp += DSET_I;  // (second descriptor set)
     c.flag = reinterpret_cast<int*>(fp); fp += 4;
@@ -577,13 +577,18 @@ __device__ inline double wave_sum(double v)
     v += dpp_d<0x140>(v);
     return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
 }
+// LEAD, the barrier in front of the slot writes, only keeps the writers off slots that a slower wave may still be reading from the reduction before.  A call site
+// may drop it (LEAD = false) where every wave has passed a workgroup barrier between its last read of these slots and this call: a wave writes here only after that
+// barrier, which every wave reaches only after its reads.  The resident fused passes are built that way -- each starts with a barrier of its own, and where one
+// runs two reductions over the same kind of slot back to back they take the two slot sets in turn (c.red, c.red1), so that the barrier of the reduction in between
+// is the one that protects a set.  Each such call site says which barrier it relies on.
 // maxima of up to three values at once (red: 3 slots per wave)
-template <int NT, int NV>
+template <int NT, int NV, bool LEAD = true>
 __device__ inline void block_maxn(float (&v)[NV], float* red, int tid)
 {
 #pragma unroll
     for (int q = 0; q < NV; ++q) v[q] = wave_max(v[q]);
-    __syncthreads();
+    if (LEAD) __syncthreads();
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int q = 0; q < NV; ++q) red[3 * (tid >> 6) + q] = v[q];
@@ -597,11 +602,11 @@ __device__ inline void block_maxn(float (&v)[NV], float* red, int tid)
         v[q] = uniform_f(r);
     }
 }
-template <int NT>
+template <int NT, bool LEAD = true>
 __device__ inline double block_sum(double v, double* red, int tid)
 {
     v = wave_sum(v);
-    __syncthreads();
+    if (LEAD) __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     double r = red[0];
@@ -610,11 +615,11 @@ __device__ inline double block_sum(double v, double* red, int tid)
     return uniform_d(r);
 }
 // two maxima and one float64 sum behind one pair of barriers (the residual pass)
-template <int NT>
+template <int NT, bool LEAD = true>
 __device__ inline void block_max2_sum(float& m0, float& m1, double& sm, float* red, double* redd, int tid)
 {
     m0 = wave_max(m0); m1 = wave_max(m1); sm = wave_sum(sm);
-    __syncthreads();
+    if (LEAD) __syncthreads();
     if ((tid & 63) == 0) { red[3 * (tid >> 6)] = m0; red[3 * (tid >> 6) + 1] = m1; redd[tid >> 6] = sm; }
     __syncthreads();
     float r0 = red[0], r1 = red[1];
@@ -2842,6 +2847,85 @@ __device__ inline float suffix_lin(float g, float b, int lane)
     if (row == 0) b = fmaf(g, v16, b);
     return b;
 }
+// The term b_k of a CoM row and of a foot row, axis a; index 1 / 2: the axes a + 1 / a + 2 (cyclic).  dF: gam-weighted force step (of both feet / of the foot),
+// lo: lam_h of the next stage as the Hessian used it, vh: the new lam_h of the next stage, g: Fsum / the foot's Fc.  One copy of the arithmetic for the one-wave
+// scan (every axis a compile-time constant) and the scan by axis (the axis a per-wave index): the costates come out of the same float operations either way.
+__device__ __forceinline__ float costate_com_b(float w, float err, float egm, float dtm, float dF1, float dF2, float lo1, float lo2, float vh1, float vh2, float g1,
+                                               float g2)
+{
+    float b = w * err;
+    b += egm * (dF2 * lo1 - dF1 * lo2);               // eg = -dt:  -dt (dF_a1 lamh_a2 - dF_a2 lamh_a1)
+    b += dtm * (vh1 * g2 - vh2 * g1);
+    return b;
+}
+__device__ __forceinline__ float costate_foot_b(float w, float err, float egm, float dtm, float gam, float dF1, float dF2, float lo1, float lo2, float vh1, float vh2,
+                                                float g1, float g2)
+{
+    float b = w * err;
+    b += egm * (dF1 * lo2 - dF2 * lo1);               // eg = +dt
+    b -= dtm * gam * (vh1 * g2 - vh2 * g1);
+    return b;
+}
+__device__ __forceinline__ float sel3(const float (&v)[3], int i) { return i == 0 ? v[0] : (i == 1 ? v[1] : v[2]); }
+// ---- The same scans with the work of levels 2 and 3 split by axis over three waves (the resident fused pass, phase_final_post): wave `ax` forms the CoM row, the two
+// foot rows and the CoM-velocity row of axis ax -- which read, of the other axes, only level 1 -- and writes those and lam_h of axis ax to vout: five of the fifteen
+// components, no word written by two waves.  Level 1 (three scans) every wave runs for itself, and the force-step sums of the two other axes it forms in registers
+// (lane <-> stage, costate_force_sums' arithmetic, nothing written to c.d): no barrier and no hand-off word between the three waves.  Seven scans on a wave instead of
+// fifteen.  ax is uniform over the wave and an index, not a template argument: one copy of the code. ----
+__device__ inline void costate_scan_axis(const Ctx& c, const CmpcConsts& prm, int lane, int ax, bool use_exact, float* vout)
+{
+    const int N = c.N;
+    const bool valid = lane <= N, dyn = lane < N;
+    const int k = valid ? lane : N, kd = dyn ? lane : N - 1;
+    const int a1 = ax == 2 ? 0 : ax + 1, a2 = ax == 0 ? 2 : ax - 1;
+    const float* S = c.S + NS * k;
+    const float* dS = c.dS + NS * k;
+    const float* geo = c.geoA + GEO * kd;
+    const float* du = c.dU + NU * kd;
+    const float* lo = c.LAM + NS * (kd + 1) + 6;
+    const float dtm = dyn ? prm.dt : 0.f;
+    const float egm = use_exact ? dtm : 0.f;
+    const float on = valid ? 1.f : 0.f;
+    const float gam0 = gam_of(c, 0, kd), gam1 = gam_of(c, 1, kd);
+    // gam-weighted sums of the force step, axes a1 and a2: [0] foot 0, [1] foot 1, [2] both
+    float dF1[3], dF2[3];
+    dF1[0] = gam0 * (du[a1] + du[3 + a1] + du[6 + a1] + du[9 + a1]);
+    dF1[1] = gam1 * (du[12 + a1] + du[15 + a1] + du[18 + a1] + du[21 + a1]);
+    dF1[2] = dF1[0] + dF1[1];
+    dF2[0] = gam0 * (du[a2] + du[3 + a2] + du[6 + a2] + du[9 + a2]);
+    dF2[1] = gam1 * (du[12 + a2] + du[15 + a2] + du[18 + a2] + du[21 + a2]);
+    dF2[2] = dF2[0] + dF2[1];
+    const float lo1 = lo[a1], lo2 = lo[a2];
+    // level 1: angular momentum, all three axes
+    float vh[3], vhn[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float b = on * (2.f * prm.w_h) * ((S[6 + a] - c.sp[c.L.pHref() + a + 3 * k]) + dS[6 + a]);
+        vh[a] = suffix_sum(b, lane);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) vhn[a] = lane_next(vh[a], lane);
+    const float vh1 = sel3(vhn, a1), vh2 = sel3(vhn, a2);
+    // level 2: the CoM row and the two foot rows of the axis
+    const float w = ax == 0 ? 2.f * prm.w_com0 : (ax == 1 ? 2.f * prm.w_com1 : prm.wz2[k]);
+    const float bc = costate_com_b(w, (S[ax] - c.sp[c.L.pComref() + ax + 3 * k]) + dS[ax], egm, dtm, dF1[2], dF2[2], lo1, lo2, vh1, vh2, geo[30 + a1], geo[30 + a2]);
+    const float vc = suffix_sum(on * bc, lane);
+    float vf[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const float gam = ct ? gam1 : gam0;
+        const int j = 9 + 3 * ct + ax;
+        const float b = costate_foot_b(2.f * prm.w_pos, (S[j] - c.sp[c.L.pNom(ct) + ax + 3 * k]) + dS[j], egm, dtm, gam, dF1[ct], dF2[ct], lo1, lo2, vh1, vh2,
+                                       geo[24 + 3 * ct + a1], geo[24 + 3 * ct + a2]);
+        vf[ct] = suffix_lin(dyn ? gam : 1.f, on * b, lane);
+    }
+    // level 3: the CoM-velocity row of the axis
+    const float vv = suffix_sum(dtm * lane_next(vc, lane), lane);
+    if (valid && lane > 0) {
+        float* o = vout + NS * k + ax;
+        o[0] = vc; o[3] = vv; o[6] = sel3(vh, ax); o[9] = vf[0]; o[12] = vf[1];
+    }
+}
 template <bool DEFER>
 __device__ inline void costate_scan(const Ctx& c, const CmpcConsts& prm, int lane, float ap, bool use_exact, float* vout)
 {
@@ -2878,9 +2962,8 @@ __device__ inline void costate_scan(const Ctx& c, const CmpcConsts& prm, int lan
     for (int a = 0; a < 3; ++a) {
         const int a1 = (a + 1) % 3, a2 = (a + 2) % 3;
         const float w = a == 0 ? 2.f * prm.w_com0 : (a == 1 ? 2.f * prm.w_com1 : prm.wz2[k]);
-        float b = w * ((S[a] - c.sp[c.L.pComref() + a + 3 * k]) + dS[a]);
-        b += egm * (dF[6 + a2] * lo[a1] - dF[6 + a1] * lo[a2]);               // eg = -dt:  -dt (dF_a1 lamh_a2 - dF_a2 lamh_a1)
-        b += dtm * (vh1[a1] * geo[30 + a2] - vh1[a2] * geo[30 + a1]);
+        const float b = costate_com_b(w, (S[a] - c.sp[c.L.pComref() + a + 3 * k]) + dS[a], egm, dtm, dF[6 + a1], dF[6 + a2], lo[a1], lo[a2], vh1[a1], vh1[a2],
+                                      geo[30 + a1], geo[30 + a2]);
         v[a] = suffix_sum(on * b, lane);
     }
 #pragma unroll
@@ -2889,9 +2972,8 @@ __device__ inline void costate_scan(const Ctx& c, const CmpcConsts& prm, int lan
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, j = 9 + 3 * ct + a;
-            float b = (2.f * prm.w_pos) * ((S[j] - c.sp[c.L.pNom(ct) + a + 3 * k]) + dS[j]);
-            b += egm * (dF[3 * ct + a1] * lo[a2] - dF[3 * ct + a2] * lo[a1]);   // eg = +dt
-            b -= dtm * gam * (vh1[a1] * geo[24 + 3 * ct + a2] - vh1[a2] * geo[24 + 3 * ct + a1]);
+            const float b = costate_foot_b(2.f * prm.w_pos, (S[j] - c.sp[c.L.pNom(ct) + a + 3 * k]) + dS[j], egm, dtm, gam, dF[3 * ct + a1], dF[3 * ct + a2], lo[a1],
+                                           lo[a2], vh1[a1], vh1[a2], geo[24 + 3 * ct + a1], geo[24 + 3 * ct + a2]);
             v[j] = suffix_lin(dyn ? gam : 1.f, on * b, lane);
         }
     }
@@ -3033,6 +3115,11 @@ __device__ __attribute__((noinline)) void tail_polish(lds_t lds, int Nrt, float*
 // update pass below pushed the driver of the 168-register variants to scratch spills inside the iteration loop: -1.5 % on configs 3-5).
 // Geometry, dynamics defects (float64 from the float32 iterate), inequality residuals, max t z, mean t z. ----
 struct Resid { float ep, ec, mu; };
+// The resident eight-wave variants with a compile-time horizon: the ones whose iteration runs phase_residuals, phase_affine_post and phase_final_post and no other
+// pass with a block reduction between them.  There each reduction takes ONE barrier (block_maxn, LEAD = false) and the costates of phase_final_post run on three waves.
+// The HBM-factor variants (four waves, held to 168 registers) and the runtime-N variants (phase_update in front of phase_residuals) keep the two-barrier, one-wave form.
+template <int NT, int NC, bool FG>
+constexpr bool kLeanPasses = NT == 512 && NC > 0 && !FG;
 template <int NT, int NC, bool FG>
 __device__ __attribute__((noinline)) Resid phase_residuals(lds_t lds, int Nrt, float* fg_base, int nrow_in)
 {
@@ -3125,7 +3212,9 @@ __device__ __attribute__((noinline)) Resid phase_residuals(lds_t lds, int Nrt, f
         }
     }
     if (!(fabsf(l_chk) < INFINITY)) l_ep = INFINITY;   // (one test per thread, not per element: NaN, inf, inf - inf all end here)
-    block_max2_sum<NT>(l_ep, l_ec, l_mu, c.red, c.redd, tid);
+    // (lean form: the last reads of c.red were those of phase_final_post's first reduction, in front of the barrier of its second one, which uses c.red1; the last
+    //  reads of c.redd lie in front of the closing barrier of phase_affine_post or phase_multipliers; on the first iteration phase_init's barriers stand in between)
+    block_max2_sum<NT, !kLeanPasses<NT, NC, FG>>(l_ep, l_ec, l_mu, c.red, c.redd, tid);
     Resid r;
     r.ep = l_ep; r.ec = l_ec; r.mu = (float)(l_mu / (double)nrow);
     return r;
@@ -3426,14 +3515,16 @@ __device__ __attribute__((noinline)) Centre phase_affine_post(lds_t lds, int Nrt
             if (dz[q] < 0.f) a_d = fminf(a_d, -z[q] / dz[q]);
         }
     });
+    // (lean form, one barrier per reduction: c.red and c.redd were last read in front of the barrier this pass starts with -- one reduction over each, so one set)
+    constexpr bool LEAD = !kLeanPasses<NT, NC, FG>;
     float m[2] = {-a_p, -a_d};
-    block_maxn<NT, 2>(m, c.red, tid);
+    block_maxn<NT, 2, LEAD>(m, c.red, tid);
     const float ap = -m[0], ad = -m[1];
     double l_aff = 0.0;
 #pragma unroll
     for (int q = 0; q < R; ++q)
         if (st[q] & 2) l_aff += (double)(t[q] + ap * dt[q]) * (double)(z[q] + ad * dz[q]);
-    const float mu_aff = (float)(block_sum<NT>(l_aff, c.redd, tid) / (double)nrow);
+    const float mu_aff = (float)(block_sum<NT, LEAD>(l_aff, c.redd, tid) / (double)nrow);
     Centre r;
     r.sigma = mu_aff / mu_cur;
     r.sigma = r.sigma * r.sigma * r.sigma;
@@ -3450,15 +3541,19 @@ __device__ __attribute__((noinline)) Centre phase_affine_post(lds_t lds, int Nrt
     return r;
 }
 
-// phase_final_post: behind the last forward sweep of an iteration.  The costate recursion (one wave, serial over the stages: the longest pole of these passes) runs
-// BESIDE the slack steps and step lengths of the other waves; it leaves the full-step costates in the dT array -- dead by now: the rows' steps stay in registers -- and
+// phase_final_post: behind the last forward sweep of an iteration.  The costate recursion (scans over the stages on one wave -- on three, an axis each, in the
+// resident compile-time-horizon variants: the longest pole of these passes) runs BESIDE the slack steps and step lengths of the other waves; it leaves the full-step costates in the dT array -- dead by now: the rows' steps stay in registers -- and
 // every thread blends them in once the step length is known.  Then the iterate takes its step and the step is measured (phase_update's arithmetic and thread mapping).
 struct FinalStep { float ap, ad, step; };
 template <int NT, int NC, bool FG>
 __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int Nrt, float* fg_base, float tau_in, bool exact_in)
 {
     CMPC_PHASE_PROLOGUE;
-    constexpr int NTR = NT - 64;   // threads on the rows
+    // Lean form (kLeanPasses): the costates by axis on waves 0, 1, 2 (costate_scan_axis: seven scans each instead of fifteen on wave 0), the rows on the other five.
+    // The rows are reduced by maxima only, so which thread holds a row does not show in the result.
+    constexpr bool LEAN = kLeanPasses<NT, NC, FG>;
+    constexpr int NCW = LEAN ? 3 : 1;    // waves on the costates
+    constexpr int NTR = NT - 64 * NCW;   // threads on the rows
     typedef RowSlots<NTR, NC> RS;
     constexpr int R = RS::R;
     const float tau = uniform_f(tau_in);
@@ -3468,17 +3563,21 @@ __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int N
     float t[R], z[R], dt[R], dz[R];
     int ei[R], st[R];
     float a_p = 1.f, a_d = 1.f;
-    if (tid < 64) {
-        costate_force_sums(c, tid, 64);
-        wave_lds_sync();
-        costate_scan<true>(c, prm, tid, 0.f, use_exact, vbuf);
+    // The role branch holds NO workgroup barrier: every wave executes the same barriers below whatever its role -- a barrier inside one role would hang the workgroup.
+    if (tid < 64 * NCW) {
+        if constexpr (LEAN) costate_scan_axis(c, prm, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6), use_exact, vbuf);
+        else {
+            costate_force_sums(c, tid, 64);
+            wave_lds_sync();
+            costate_scan<true>(c, prm, tid, 0.f, use_exact, vbuf);
+        }
 #pragma unroll
         for (int q = 0; q < R; ++q) { t[q] = 1.f; z[q] = 0.f; dt[q] = 0.f; dz[q] = 0.f; ei[q] = 0; st[q] = 0; }
     } else {
         for_slots<0, R>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
             float val, dot;
-            st[q] = row_slot<NTR, NC, q, true>(c, prm, tid - 64, ei[q], val, dot);
+            st[q] = row_slot<NTR, NC, q, true>(c, prm, tid - 64 * NCW, ei[q], val, dot);
             t[q] = c.T[ei[q]]; z[q] = c.Z[ei[q]];
             const float cmu = c.dZ[ei[q]];
             const float r = val + t[q];
@@ -3491,7 +3590,8 @@ __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int N
         });
     }
     float m[2] = {-a_p, -a_d};
-    block_maxn<NT, 2>(m, c.red, tid);   // (its barriers are also what makes the costates in vbuf visible)
+    // (its barrier is also what makes the costates in vbuf visible.  Lean form, one barrier: c.red was last read in front of the barrier this pass starts with)
+    block_maxn<NT, 2, !LEAN>(m, c.red, tid);
     const float ap = -m[0], ad = -m[1];
 #pragma unroll
     for (int q = 0; q < R; ++q)
@@ -3522,7 +3622,9 @@ __device__ __attribute__((noinline)) FinalStep phase_final_post(lds_t lds, int N
     }
     if (!(fabsf(l_chk2) < INFINITY)) l_st = INFINITY;
     float m3[3] = {l_st, l_sf, l_fm};
-    block_maxn<NT, 3>(m3, c.red, tid);
+    // (lean form: the second set of slots -- a slower wave may still be reading c.red from the reduction above -- last read in the previous iteration; and this
+    //  reduction's barrier is what lets the residual pass behind it write c.red again without one)
+    block_maxn<NT, 3, !LEAN>(m3, LEAN ? c.red1 : c.red, tid);
     FinalStep r;
     r.ap = ap; r.ad = ad; r.step = ap * fmaxf(m3[0], m3[1] / m3[2]);
     return r;
