@@ -670,9 +670,10 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
  *      1  the merge (or the snap of force_sample_time) failed: dOk[b] == 0
  *  1 + s  the solve's status s != 0 (dInfo word 5): 2 budget exhausted, 3 factorisation failed / not finite, 4 outside the supported subset
  *      5  an entry of dStateOut[b] is not finite
+ *   6..9  with physical limits set (cmpc_set_walk_limits, below), behind all of the above: 6 height, 7 reach, 8 margin, 9 track out of its limit
  *      0  none of the above
  * stop_mask says which codes END a problem: bit 0 code 1 (always honoured, set or not: such a tick solved a stale problem), bit 1 codes 2..4, bit 2
- * code 5.  A code whose bit is off is recorded and the problem walks on; that tick is a good tick like one with code 0.
+ * code 5, bit 3 (value 8) codes 6..9.  A code whose bit is off is recorded and the problem walks on; that tick is a good tick like one with code 0.
  * Trace, row `row` of arrays with `rows` rows; every pointer may be NULL:
  *     dCom[rows][B][3], dZmp[rows][B][2]   float: bit copies of dStateOut[b][0..2] and dZmp[b]
  *     dLand[rows][B][2]                    int: dLand of the tick
@@ -690,7 +691,8 @@ int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int wa
  *                        dLandingOffset, the limits the handle's box (the last one a sampling or a tick uploaded), each slack formed in double and
  *                        rounded to float
  * Batch statistics, dStats[rows][6] int or NULL, row `row`: { problems not ended before the tick, problems ended by it, sum and max of dIterations over
- * the tick's good problems, problems not ended before the tick whose code is 2..4, 0 }: what a reduction of the trace row gives.  Integer atomics, so
+ * the tick's good problems, problems not ended before the tick whose code is 2..4, the same for codes 6..9 (0 without limits) }: what a reduction of
+ * the trace row gives.  Integer atomics, so
  * the result does not depend on the order: each wave reduces first, then adds once per word; lanes past B and lanes of ended problems contribute the
  * identity.  The call clears the row first.
  * Isolation: the record writes nothing a tick reads, so a recorded walk is bit-identical to an unrecorded one.  By default an ended problem stays in
@@ -720,6 +722,52 @@ int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX
 /* the same on the host: host buffers throughout (rec's pointers too), box_upper / box_lower [2][3]; no handle, no GPU.  Bit-equal to the kernel. */
 int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
                         const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec);
+
+/* ---- physical limits: a walk that can say its robot fell ----
+ * The centroidal plant has no kinematics, so codes 1..5 end a problem for numerical reasons only.  With limits set, the record launch behind a tick also
+ * forms four stability measures per problem and holds them against five limits: tick codes 6..9, behind the chain above (first match still wins, so a
+ * tick whose code is 1..5 never takes one).  The measures refer to the time of dStateOut, t + dt, which is stage 1 of the tick's problem (N >= 2):
+ * the support set S = { c : Gamma_c,1 > 0.5 }, foot c at q_c = pos_c[knot 1] of dX with the rotation R_c of stage 1 in dP and the corners the plant
+ * kernel reads (the handle's, or the problem's own model's), com = dStateOut[0..2], dcom = dStateOut[3..5]:
+ *     0 height  com_z - mean over c in S of q_c,z
+ *     1 reach   max over c in S of |com - q_c|, in 3-D
+ *     2 margin  the signed Euclidean distance of the capture point xi = com_xy + dcom_xy sqrt(max(height, 0) / gravity) to the support region, positive
+ *               inside; the region is the convex hull of the xy of q_c + R_c corner_j over c in S, j = 0..3 (a rectangle, a point foot, a segment, a
+ *               single point alike).  No hull is built: the margin is the least of max_k n.v_k - n.xi over the unit normals of every pair of the
+ *               points and the unit directions from every point to xi (lengths under 1e-12 left out; 0 if none is left)
+ *     3 track   |com_xy - comRef_xy[knot 1]|, the reference row of dP
+ * in double from the float inputs, not contracted, sums left to right, each rounded to float ONCE; the limits are compared against that float, so every
+ * ending can be recomputed from the trace exactly.  S empty: measures 0..2 are NaN.  A dStateOut that is not finite: all four are NaN.
+ *     6  height < height_min or height > height_max      7  reach > reach_max      8  margin < margin_min      9  track > track_max
+ * A NaN measure or a NaN limit never fires: NaN switches a limit off.  stop_mask bit 3 makes codes 6..9 END a problem; with the bit off they are
+ * recorded and the problem walks on as a good tick.  dStats word 5 counts the problems not ended before the tick whose code is 6..9.
+ *     dMeasures[rows][B][4] float or NULL: row `row` of every record launch.  A row is written on every tick of a problem that had not ended before it --
+ *                           the tick a code 6..9 ends included, so the value that fired can be read; later ticks, and ticks ended by codes 1..5, hold NaN
+ *     dExtremes[B][5] float or NULL: height min, height max, reach max, margin min, track max over the problem's GOOD ticks (a NaN measure is passed
+ *                           over), carried from call to call; set up by cmpc_walk_extremes_init_device (+inf in the minima, -inf in the maxima)
+ * cmpc_set_walk_limits is sticky on the handle, like cmpc_set_ended_device; lim == NULL: off (the default, and then every record launch is the one it
+ * was without this setting).  The struct is copied, and captured when a launch is queued; the arrays must stay allocated until the queued launches have
+ * run.  Every record launch of the handle then evaluates the limits: cmpc_rollout_record_device and every cmpc_rollout_walk_* call, the mismatch, taped,
+ * refill and snapshot forms included -- the gates of the reverse and forward walks, the ended mask and the refill queue read dEndTick and so inherit the
+ * physical endings.  On a refill walk dExtremes must be NULL (CMPC_ERR_ARG otherwise): a slot's extremes would span several trials, so per-trial
+ * extremes come from the measures trace and dTrialOf; snapshots do not carry extremes.  CMPC_ERR_ARG for height_min > height_max, for dMeasures with
+ * rows < 1, and, from the record calls, for a row >= rows.  Out of scope: per-trial limits, limits that must hold for n consecutive ticks, derivatives
+ * of the measures. */
+#define CMPC_WALK_MEASURES 4
+#define CMPC_WALK_EXTREMES 5   /* height min, height max, reach max, margin min, track max */
+typedef struct cmpc_walk_limits {
+    double height_min, height_max, reach_max, margin_min, track_max;   /* NaN: off */
+    float* dMeasures; int rows;     /* [rows][B][4] or NULL */
+    float* dExtremes;               /* [B][5] or NULL, over the problem's good ticks */
+} cmpc_walk_limits;
+int cmpc_set_walk_limits(cmpc_handle h, const cmpc_walk_limits* lim);
+int cmpc_walk_extremes_init_device(cmpc_handle h, float* dExtremes, void* stream);
+/* cmpc_rollout_record with the limits, on the host: host buffers throughout (lim's arrays too), corners [2][4][3] float of problem 0 with problem b's
+ * corners_stride floats further on (0: one set for the batch), gravity > 0, horizon >= 2; no handle, no GPU.  Bit-equal to the kernel.  lim == NULL:
+ * cmpc_rollout_record, to the bit (corners and gravity are not read). */
+int cmpc_rollout_record_limits(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
+                               const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec,
+                               const cmpc_walk_limits* lim, const float* corners, int corners_stride, double gravity);
 
 /* The cold start of cmpc_set_initial_guess with x0 == NULL as a kernel, from the caller's dP[B][n_p] into dX0[B][n_x]: CoM at com0 on every knot, feet at
  * nominalPos, f_z = (float)(gravity / 8) per corner and stage, every other entry zero; bit-equal to the host form.  Asynchronous on `stream` (NULL:

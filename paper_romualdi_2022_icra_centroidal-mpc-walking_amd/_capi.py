@@ -93,7 +93,16 @@ class CmpcWalkTapeRegroup(C.Structure):
     _fields_ = [("tick_first", C.c_int), ("dTrialIndex", C.c_void_p), ("dEndOut", C.c_void_p), ("dOkOut", C.c_void_p)]
 
 
-STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4}   # cmpc_walk_record.stop_mask
+STOP_BITS = {"merge": 1, "solver": 2, "nonfinite": 4, "limits": 8}   # cmpc_walk_record.stop_mask
+
+WALK_MEASURES = 4   # CMPC_WALK_MEASURES: height, reach, margin, track
+WALK_EXTREMES = 5   # CMPC_WALK_EXTREMES: height min, height max, reach max, margin min, track max
+
+
+class CmpcWalkLimits(C.Structure):
+    """mirror of cmpc_walk_limits (include/cmpc.h): the physical limits of a walk's record (NaN: off), its measures trace and its extremes; 64 bytes"""
+    _fields_ = [("height_min", C.c_double), ("height_max", C.c_double), ("reach_max", C.c_double), ("margin_min", C.c_double), ("track_max", C.c_double),
+                ("dMeasures", C.c_void_p), ("rows", C.c_int), ("dExtremes", C.c_void_p)]
 
 
 class CmpcTickTape(C.Structure):
@@ -246,6 +255,7 @@ EXPORTS = [
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
     "cmpc_rollout_walk_refill_taped_device", "cmpc_rollout_tape_regroup_device", "cmpc_rollout_tape_regroup",
     "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
+    "cmpc_set_walk_limits", "cmpc_walk_extremes_init_device", "cmpc_rollout_record_limits",
 ]
 
 _lib = None
@@ -367,6 +377,11 @@ def lib():
             L.cmpc_rollout_walk_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), rp, i, i, ip, vp]
         if hasattr(L, "cmpc_set_ended_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             L.cmpc_set_ended_device.argtypes = [vp, vp]
+        if hasattr(L, "cmpc_set_walk_limits"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            lp = C.POINTER(CmpcWalkLimits)
+            L.cmpc_set_walk_limits.argtypes = [vp, lp]
+            L.cmpc_walk_extremes_init_device.argtypes = [vp, vp, vp]
+            L.cmpc_rollout_record_limits.argtypes = [i, i, i, i] + [vp] * 9 + [C.POINTER(CmpcWalkRecord), lp, vp, i, d]
         if hasattr(L, "cmpc_rollout_walk_vjp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             tp = C.POINTER(CmpcWalkTape)
             L.cmpc_rollout_tape_device.argtypes = [vp, i, i, i] + [vp] * 11 + [tp, vp]

@@ -35,6 +35,8 @@ struct cmpc_handle_s {
     float* dDuals = nullptr;     // the dual record of the last solve [B][NS (N+1) + 2 NI N] (cmpc_set_multiplier_output, or the diagnostic knob below)
     bool mult_out = false;       // cmpc_set_multiplier_output: every solve writes dDuals
     const int* dEnded = nullptr; // cmpc_set_ended_device: the caller's [B] words, read by the launches on the device (>= 0: the problem is left out); null: off
+    bool limits_set = false;     // cmpc_set_walk_limits: every record launch evaluates `limits` (the caller's struct, copied)
+    cmpc_walk_limits limits{};
     float* dLamG = nullptr;      // [B][n_g] staging of cmpc_get_multipliers (allocated on first use)
     double* dSensWs = nullptr;   // workspace of the solution sensitivities, min(B, CMPC_SENS_SUB_BATCH) problems (allocated on first use)
     hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
@@ -376,6 +378,24 @@ int cmpc_set_ended_device(cmpc_handle h, const int* dEndTick)
 {
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_set_ended_device: null handle");
     h->dEnded = dEndTick;   // (only the pointer is kept: the words are read on the device, by each launch when it runs)
+    return CMPC_OK;
+}
+
+// what both forms of the record refuse in a cmpc_walk_limits; null: nothing.  (height_min > height_max is false when either is NaN: a limit that is off)
+static const char* limits_refusal(const cmpc_walk_limits* lim)
+{
+    if (lim->height_min > lim->height_max) return "height_min above height_max";
+    if (lim->dMeasures && lim->rows < 1) return "dMeasures with rows < 1";
+    return nullptr;
+}
+
+int cmpc_set_walk_limits(cmpc_handle h, const cmpc_walk_limits* lim)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_set_walk_limits: null handle");
+    if (!lim) { h->limits_set = false; h->limits = cmpc_walk_limits{}; return CMPC_OK; }
+    if (const char* why = limits_refusal(lim)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_set_walk_limits: ") + why);
+    h->limits = *lim;
+    h->limits_set = true;
     return CMPC_OK;
 }
 
@@ -1465,11 +1485,54 @@ int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* 
     int st[6] = {0, 0, 0, 0, 0, 0};
     for (int b = 0; b < batch; ++b) {
         int t[5];
-        cmpc_record_problem(a, b, t);
+        cmpc_record_problem<false>(a, CmpcLimitArgs{}, b, t);
         st[0] += t[0]; st[1] += t[1]; st[2] += t[2]; st[3] = std::max(st[3], t[3]); st[4] += t[4];
     }
     if (rec->dStats) std::memcpy(rec->dStats + 6 * (size_t)row, st, sizeof(st));
     return CMPC_OK;
+}
+
+// the limits as the record takes them, row `row` of the measures trace
+static CmpcLimitArgs limit_args(const cmpc_walk_limits& lim, int B, int row, const float* corners, int stride, double gravity)
+{
+    return CmpcLimitArgs{lim.height_min, lim.height_max, lim.reach_max, lim.margin_min, lim.track_max, gravity, corners, stride,
+                         lim.dMeasures ? lim.dMeasures + (size_t)row * B * CMPC_WALK_MEASURES : nullptr, lim.dExtremes};
+}
+
+int cmpc_rollout_record_limits(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
+                               const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec,
+                               const cmpc_walk_limits* lim, const float* corners, int corners_stride, double gravity)
+{
+    if (!lim) return cmpc_rollout_record(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box_upper, box_lower, rec);
+    float box[12];
+    CmpcRecordArgs a;
+    if (!box_upper || !box_lower || !record_args(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box, rec, a))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: bad argument");
+    if (horizon < 2 || !corners || corners_stride < 0 || !(gravity > 0)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: bad argument");
+    if (const char* why = limits_refusal(lim)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_record_limits: ") + why);
+    if (lim->dMeasures && row >= lim->rows) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: the measures trace has too few rows");
+    std::memcpy(box, box_upper, sizeof(float) * 6);
+    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
+    const CmpcLimitArgs lm = limit_args(*lim, batch, row, corners, corners_stride, gravity);
+    int st[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < batch; ++b) {
+        int t[6];
+        cmpc_record_problem<true>(a, lm, b, t);
+        st[0] += t[0]; st[1] += t[1]; st[2] += t[2]; st[3] = std::max(st[3], t[3]); st[4] += t[4]; st[5] += t[5];
+    }
+    if (rec->dStats) std::memcpy(rec->dStats + 6 * (size_t)row, st, sizeof(st));
+    return CMPC_OK;
+}
+
+// the record launch behind a tick: without limits the launch it has always been, with them (cmpc_set_walk_limits) the kernel that also evaluates them,
+// on the corners the plant kernel reads
+static int record_launch(cmpc_handle h, const char* who, const CmpcRecordArgs& a, int* stats, hipStream_t st)
+{
+    if (!h->limits_set) return launch_status(h, who, cmpc_launch_rollout_record(&a, stats, st));
+    if (h->limits.dMeasures && a.row >= h->limits.rows)
+        return fail(h, CMPC_ERR_ARG, std::string(who) + ": the measures trace of cmpc_set_walk_limits has too few rows");
+    const CmpcLimitArgs lm = limit_args(h->limits, a.B, a.row, model_corners(h), corners_stride(h), h->cfg.gravity);
+    return launch_status(h, who, cmpc_launch_rollout_record_limits(&a, &lm, stats, st));
 }
 
 // the record launch of one tick; clear_row: the statistics row is cleared here (the walk clears all its rows at once)
@@ -1482,8 +1545,15 @@ static int rollout_record_impl(cmpc_handle h, int tick, int row, const float* dX
                                                       : "cmpc_rollout_record_device: bad argument");
     int* stats = rec->dStats ? rec->dStats + 6 * (size_t)row : nullptr;
     if (stats && clear_row) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(int) * 6, st));
-    const int lrc = cmpc_launch_rollout_record(&a, stats, st);
-    return launch_status(h, "roll-out record", lrc);
+    return record_launch(h, "roll-out record", a, stats, st);
+}
+
+int cmpc_walk_extremes_init_device(cmpc_handle h, float* dExtremes, void* stream)
+{
+    if (!h || !dExtremes) return fail(h, CMPC_ERR_ARG, "cmpc_walk_extremes_init_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_extremes_init(h->B, dExtremes, stream_of(h, stream));
+    return launch_status(h, "extremes init", lrc);
 }
 
 int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
@@ -1603,6 +1673,8 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
     if (io->dListTB == io->tick.dListT || io->dListPoseB == io->tick.dListPose || io->dListNB == io->tick.dListN)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the two sets of list buffers must not alias");
     if (rec && (row0 < 0 || (long long)row0 + ticks > rec->rows)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the record has too few rows");
+    if (rec && h->limits_set && h->limits.dMeasures && (long long)row0 + ticks > h->limits.rows)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the measures trace of cmpc_set_walk_limits has too few rows");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = stream_of(h, stream);
     int rc = upload_box(h, io->tick.box_upper, io->tick.box_lower, st);
@@ -1854,6 +1926,9 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
             return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape's scalars do not agree with the walk");
     }
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
+    if (h->limits_set && h->limits.dExtremes)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dExtremes of cmpc_set_walk_limits must be NULL on a refill walk (a slot's extremes "
+                                     "would span several trials: take them from the measures trace and dTrialOf)");
     if (tape && (!h->mult_out || !h->dDuals))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
     if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
@@ -1865,6 +1940,8 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
     if ((k.dPlanCom || k.dPlanH) && (!k.dPlanCom || !k.dPlanH || k.plan_knots < 2 || !(k.plan_dt > 0) || !(k.robot_mass > 0)))
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad planner trajectory");
     if (row0 < 0 || (long long)row0 + ticks > rec->rows) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the record has too few rows");
+    if (h->limits_set && h->limits.dMeasures && (long long)row0 + ticks > h->limits.rows)
+        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the measures trace of cmpc_set_walk_limits has too few rows");
     CmpcRefillArgs probe;
     if (!refill_args(h->B, tick0, rec, refill, k.dStateOut, probe)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad refill or record");
     long long dt_ns = 0;
@@ -1937,8 +2014,7 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
             break;
         }
         a.start = refill->dStartTick;
-        lrc = cmpc_launch_rollout_record(&a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
-        rc = launch_status(h, "refill walk record", lrc);
+        rc = record_launch(h, "refill walk record", a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
         if (rc == CMPC_OK && tape)
             rc = rollout_tape_impl(h, max_contacts, tape_row0 + i, 2, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, nullptr, k.dStateOut, k.dPlanT, k.dPlanN, set_t[cur],
                                    set_n[cur], tape, stream);

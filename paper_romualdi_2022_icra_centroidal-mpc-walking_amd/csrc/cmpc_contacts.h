@@ -246,9 +246,129 @@ struct CmpcRecordArgs {
     int* end_tick; int* end_code; int* it_sum; int* it_max; float* final_state; float* slack_min;
     const int* start;   // [B] or null (the refill walk): the tick number end_tick takes is tick - start[b], the problem's local one
 };
-// tally[5]: this problem's terms of the statistics row -- not ended before the tick, ended by it, iterations (for the sum and for the max: 0 unless the
-// tick is a good one), code 2..4
-__host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, int b, int* tally)
+// the physical limits of a walk (include/cmpc.h, cmpc_walk_limits) as the record takes them: the five limits (NaN: off), the model corners the plant
+// kernel reads ([2][4][3] of problem 0, problem b's corners_stride floats further on), the gravity, this tick's row [B][4] of the measures trace (or
+// null) and the extremes [B][5] (or null)
+struct CmpcLimitArgs {
+    double height_min, height_max, reach_max, margin_min, track_max, gravity;
+    const float* corners; int corners_stride;
+    float* measures; float* extremes;
+};
+// the signed distance of xi to the convex hull of the 8 points (vx, vy), positive inside, with no hull built: the least of max_k n.v_k - n.xi over the unit
+// normals of every pair of points, both orientations, and the unit directions from every point to xi; pairs and directions shorter than 1e-12 are left
+// out, and with none left the margin is 0.  The two orientations of a pair share their cross products: (max_k d_k - d_xi) / |e| and (d_xi - min_k d_k) / |e|,
+// d = e_y x - e_x y.  Repeated points change nothing (the caller fills the rows of a foot that is not in the support set with the other foot's).  Constant
+// trip counts: the loops unroll, and the arrays stay in registers.
+__host__ __device__ inline double cmpc_support_margin(const double (&vx)[8], const double (&vy)[8], double xi_x, double xi_y)
+{
+#pragma clang fp contract(off)
+    double m = 0.0;
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int j = i + 1; j < 8; ++j) {
+            const double ex = vx[j] - vx[i], ey = vy[j] - vy[i];
+            const double len = __builtin_sqrt(ex * ex + ey * ey);
+            const double dxi = ey * xi_x - ex * xi_y;
+            double hi = ey * vx[0] - ex * vy[0], lo = hi;
+#pragma unroll
+            for (int k = 1; k < 8; ++k) {
+                const double d = ey * vx[k] - ex * vy[k];
+                hi = d > hi ? d : hi;
+                lo = d < lo ? d : lo;
+            }
+            const double c0 = (hi - dxi) / len, c1 = (dxi - lo) / len;
+            const double c = c1 < c0 ? c1 : c0;
+            if (len >= 1e-12 && (!any || c < m)) { m = c; any = true; }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double ex = xi_x - vx[i], ey = xi_y - vy[i];
+        const double len = __builtin_sqrt(ex * ex + ey * ey);
+        double hi = ex * (vx[0] - xi_x) + ey * (vy[0] - xi_y);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            const double d = ex * (vx[k] - xi_x) + ey * (vy[k] - xi_y);
+            hi = d > hi ? d : hi;
+        }
+        const double c = hi / len;
+        if (len >= 1e-12 && (!any || c < m)) { m = c; any = true; }
+    }
+    return m;
+}
+// the four measures of problem b at the time of state_out, stage 1 of the tick's problem (include/cmpc.h, "physical limits"): height, reach, margin,
+// track, each formed in double from the float inputs, sums left to right, and rounded to float once.  A state that is not finite: NaN in all four.
+__host__ __device__ inline void cmpc_walk_measures(const CmpcRecordArgs& a, const CmpcLimitArgs& lm, int b, bool finite, float* out)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{a.N};
+    const float qnan = __builtin_nanf("");
+    out[0] = out[1] = out[2] = out[3] = qnan;
+    if (!finite) return;
+    const float* so = a.state_out + 9 * (size_t)b;
+    const float* x = a.X + (size_t)b * L.nx();
+    const float* p = a.P + (size_t)b * L.np();
+    const double com[3] = {(double)so[0], (double)so[1], (double)so[2]};
+    const double tx = com[0] - (double)p[L.pComref() + 3], ty = com[1] - (double)p[L.pComref() + 4];
+    out[3] = (float)__builtin_sqrt(tx * tx + ty * ty);
+    const bool on0 = p[L.pGam(0) + 1] > 0.5f, on1 = p[L.pGam(1) + 1] > 0.5f;
+    if (!on0 && !on1) return;
+    double q[2][3], vx[8], vy[8];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c) + 9;   // column-major block of stage 1
+        const float* cn = lm.corners + (size_t)b * lm.corners_stride + 12 * c;
+        for (int i = 0; i < 3; ++i) q[c][i] = (double)x[L.oPos(c) + 3 + i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            vx[4 * c + j] = ((q[c][0] + (double)R[0] * (double)cn[3 * j]) + (double)R[3] * (double)cn[3 * j + 1]) + (double)R[6] * (double)cn[3 * j + 2];
+            vy[4 * c + j] = ((q[c][1] + (double)R[1] * (double)cn[3 * j]) + (double)R[4] * (double)cn[3 * j + 1]) + (double)R[7] * (double)cn[3 * j + 2];
+        }
+    }
+    double zsum = 0.0, reach = 0.0;
+    int n = 0;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const bool on = c == 0 ? on0 : on1;
+        const double dx = com[0] - q[c][0], dy = com[1] - q[c][1], dz = com[2] - q[c][2];
+        const double r = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+        if (on) {
+            zsum = zsum + q[c][2];
+            reach = (n == 0 || r > reach) ? r : reach;
+            ++n;
+        }
+    }
+    const double height = com[2] - zsum / (double)n;
+    // (a foot outside the support set takes the other foot's points: the margin's candidates are then the supporting foot's alone)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!on0) { vx[j] = vx[4 + j]; vy[j] = vy[4 + j]; }
+        if (!on1) { vx[4 + j] = vx[j]; vy[4 + j] = vy[j]; }
+    }
+    const double tau = __builtin_sqrt((height > 0.0 ? height : 0.0) / lm.gravity);
+    const double xi_x = com[0] + (double)so[3] * tau, xi_y = com[1] + (double)so[4] * tau;
+    out[0] = (float)height;
+    out[1] = (float)reach;
+    out[2] = (float)cmpc_support_margin(vx, vy, xi_x, xi_y);
+}
+// the limit code of a tick whose code is 0 so far: 6..9, first match, or 0.  Written so that a NaN measure or a NaN limit never fires.
+__host__ __device__ inline int cmpc_limit_code(const CmpcLimitArgs& lm, const float* m)
+{
+    if ((double)m[0] < lm.height_min || (double)m[0] > lm.height_max) return 6;
+    if ((double)m[1] > lm.reach_max) return 7;
+    if ((double)m[2] < lm.margin_min) return 8;
+    if ((double)m[3] > lm.track_max) return 9;
+    return 0;
+}
+
+// tally[5] (LIM: [6]): this problem's terms of the statistics row -- not ended before the tick, ended by it, iterations (for the sum and for the max: 0
+// unless the tick is a good one), code 2..4 (LIM: and code 6..9)
+// LIM (cmpc_set_walk_limits): the four measures of the tick, the codes 6..9 behind the chain, the measures row and the extremes.  LIM = false is the
+// function without any of it, and lm is not read.
+template <bool LIM>
+__host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, const CmpcLimitArgs& lm, int b, int* tally)
 {
 #pragma clang fp contract(off)
     const CmpcIdx L{a.N};
@@ -258,13 +378,34 @@ __host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, int
     const bool before = a.end_tick[b] >= 0;
     int code = -1;
     bool ends = false;
+    float ms[4];
     if (!before) {
         bool finite = true;
         for (int i = 0; i < 9; ++i) finite = finite && __builtin_isfinite(so[i]);
         code = (a.ok && !a.ok[b]) ? 1 : inf[5] != 0.f ? 1 + (int)inf[5] : !finite ? 5 : 0;
-        ends = code == 1 || (code >= 2 && code <= 4 && (a.stop_mask & 2)) || (code == 5 && (a.stop_mask & 4));
+        if (LIM) {
+            cmpc_walk_measures(a, lm, b, finite, ms);
+            if (code == 0) code = cmpc_limit_code(lm, ms);
+        }
+        ends = code == 1 || (code >= 2 && code <= 4 && (a.stop_mask & 2)) || (code == 5 && (a.stop_mask & 4)) || (LIM && code >= 6 && (a.stop_mask & 8));
     }
     const bool good = !before && !ends;
+    if (LIM) {
+        // the measures row: every tick of a problem that had not ended before it, the tick a limit ends included; NaN behind an end and on a tick that
+        // codes 1..5 end.  The extremes: good ticks only (a NaN measure leaves them alone)
+        const bool shown = good || (ends && code >= 6);
+        if (lm.measures)
+            for (int i = 0; i < 4; ++i) lm.measures[4 * (size_t)b + i] = shown ? ms[i] : __builtin_nanf("");
+        if (lm.extremes && good) {
+            float* e = lm.extremes + 5 * (size_t)b;
+            if (ms[0] < e[0]) e[0] = ms[0];
+            if (ms[0] > e[1]) e[1] = ms[0];
+            if (ms[1] > e[2]) e[2] = ms[1];
+            if (ms[2] < e[3]) e[3] = ms[2];
+            if (ms[3] > e[4]) e[4] = ms[3];
+        }
+        tally[5] = (!before && code >= 6) ? 1 : 0;
+    }
     const int it = good ? (int)inf[0] : 0;
     const size_t r = (size_t)a.row * a.B + b;
     const float qnan = __builtin_nanf("");

@@ -657,11 +657,14 @@ __global__ __launch_bounds__(256) void cmpc_tick_post_kernel(int B, int N, int M
 // record: one thread per problem (cmpc_record_problem, the host form's function).  The statistics row: every lane holds its problem's five terms (zeros, the
 // identity of the sums and of the max of non-negative counts, for lanes past B and for ended problems), the wave reduces them by butterflies -- all 256 threads
 // reach the shuffles: no lane leaves before them -- and lane 0 adds its wave's terms to the row, one integer atomic per non-zero word.
-__global__ __launch_bounds__(256) void cmpc_rollout_record_kernel(CmpcRecordArgs a, int* __restrict__ stats)
+// LIM (cmpc_set_walk_limits): the measures, the codes 6..9 and the sixth word of the row -- the problems whose code is 6..9 -- through the same reduction and
+// one more atomic; lm.measures is the tick's row.  LIM = false is the kernel without limits, and lm is not read.
+template <bool LIM>
+__global__ __launch_bounds__(256) void cmpc_rollout_record_kernel(CmpcRecordArgs a, int* __restrict__ stats, CmpcLimitArgs lm)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
-    int t[5] = {0, 0, 0, 0, 0};
-    if (b < a.B) cmpc_record_problem(a, b, t);
+    int t[LIM ? 6 : 5] = {0, 0, 0, 0, 0};
+    if (b < a.B) cmpc_record_problem<LIM>(a, lm, b, t);
     if (!stats) return;   // (uniform)
     for (int o = warpSize / 2; o > 0; o >>= 1) {
         t[0] += __shfl_xor(t[0], o);
@@ -669,6 +672,7 @@ __global__ __launch_bounds__(256) void cmpc_rollout_record_kernel(CmpcRecordArgs
         t[2] += __shfl_xor(t[2], o);
         t[3] = max(t[3], __shfl_xor(t[3], o));
         t[4] += __shfl_xor(t[4], o);
+        if (LIM) t[5] += __shfl_xor(t[5], o);
     }
     if ((threadIdx.x & (warpSize - 1)) == 0) {
         if (t[0]) atomicAdd(stats + 0, t[0]);
@@ -676,7 +680,17 @@ __global__ __launch_bounds__(256) void cmpc_rollout_record_kernel(CmpcRecordArgs
         if (t[2]) atomicAdd(stats + 2, t[2]);
         if (t[3]) atomicMax(stats + 3, t[3]);
         if (t[4]) atomicAdd(stats + 4, t[4]);
+        if (LIM && t[5]) atomicAdd(stats + 5, t[5]);
     }
+}
+
+__global__ __launch_bounds__(256) void cmpc_extremes_init_kernel(int B, float* __restrict__ ext)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float inf = __builtin_inff();
+    float* e = ext + 5 * (size_t)b;
+    e[0] = inf; e[1] = -inf; e[2] = -inf; e[3] = inf; e[4] = -inf;
 }
 
 __global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const float* __restrict__ state0, int* __restrict__ end_tick, int* __restrict__ end_code,
@@ -948,7 +962,19 @@ extern "C" int cmpc_launch_walk_jvp_gate(const CmpcJvpGateArgs* a, hipStream_t s
 
 extern "C" int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cmpc_rollout_record_kernel, dim3((a->B + 255) / 256), dim3(256), 0, stream, *a, stats);
+    hipLaunchKernelGGL(cmpc_rollout_record_kernel<false>, dim3((a->B + 255) / 256), dim3(256), 0, stream, *a, stats, CmpcLimitArgs{});
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_rollout_record_limits(const CmpcRecordArgs* a, const CmpcLimitArgs* lm, int* stats, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_rollout_record_kernel<true>, dim3((a->B + 255) / 256), dim3(256), 0, stream, *a, stats, *lm);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_extremes_init(int B, float* ext, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_extremes_init_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, ext);
     return (int)hipGetLastError();
 }
 

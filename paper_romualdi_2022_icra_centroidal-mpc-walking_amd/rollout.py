@@ -101,6 +101,41 @@ class WalkingRollout:
             com_speed = last / t_last if t_last > 0 else 0.0
         self.com_speed = com_speed
         self.references, self._ref_override = None, None
+        self.limits = None
+
+    def set_limits(self, height=(None, None), reach_max=None, margin_min=None, track_max=None):
+        """The physical limits of the device walks (cmpc_set_walk_limits, include/cmpc.h): height = (lo, hi) on the CoM height above the supporting feet,
+        reach_max on the CoM's distance from a supporting foot, margin_min on the capture point's signed distance to the support region (positive
+        inside), track_max on the horizontal distance of the CoM from its reference; None (or NaN): that limit is off.  Sticky on the object: every
+        device walk method (walk_device and its taped, mismatch, checkpointed and resumed forms, the refill walks) sets it on the handle around its
+        queued segments and clears it again, as skip_ended does, records the tick codes 6..9, accepts "limits" in stop= (a robot beyond a limit ENDS),
+        and returns measures[ticks, B, 4] (height, reach, margin, track per tick; with trace=True) and extremes[B, 5] (height min, height max, reach
+        max, margin min, track max over each problem's good ticks; not from a refill walk, whose slots hold several trials: use measures and
+        trial_of).  set_limits() with nothing given traces the measures and ends nobody.  clear_limits() restores the default, and with it every
+        result's keys and bits.  run() is untouched."""
+        lo, hi = height if height is not None else (None, None)
+        self.limits = dict(height=(lo, hi), reach_max=reach_max, margin_min=margin_min, track_max=track_max)
+
+    def clear_limits(self):
+        """No physical limits (the default): the device walks record codes 0..5 only and return neither measures nor extremes."""
+        self.limits = None
+
+    def _limits_on(self, limits, rows, trace, extremes=True):
+        """the handle's limits for the segments about to be queued -> the tensors the walk returns with them ({} without limits); _limits_off() behind them"""
+        if limits is None:
+            return {}
+        torch, s = self.torch, self.solver
+        out = {}
+        if trace:
+            out["measures"] = torch.zeros((rows, self.B, 4), dtype=torch.float32, device=self.dev)
+        if extremes:
+            out["extremes"] = s.walk_extremes_init_device(device=self.dev)
+        s.set_walk_limits(measures=out.get("measures"), extremes=out.get("extremes"), **limits)
+        return out
+
+    def _limits_off(self, limits):
+        if limits is not None:    # (the queued launches keep the struct they were queued with; the tensors go back to the caller and outlive them)
+            self.solver.set_walk_limits(off=True)
 
     def set_references(self, com, h=None, in_dt=None, t_first=0.0, robot_mass=1.0, com_height=0.7):
         """The planner's CoM and angular-momentum trajectories (what the reference's MANN planner emits besides the footsteps), resampled into the comRef /
@@ -383,14 +418,19 @@ class WalkingRollout:
             tp = s.walk_tape(ticks, self.M, step=dt / self.substeps, substeps=self.substeps, force_sample_time=self.force_sample_time, device=dev)
         # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
         sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
-        if pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
-            cur = s.rollout_walk_refill_snapshot_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, pool,
-                                                        row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                                        force_sample_time=self.force_sample_time, trials=trials)
-        else:
-            cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
-                                               step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
-                                               trials=trials, **(dict(tape=tp, tape_row0=0) if tp is not None else {}))
+        try:
+            rec.update(self._limits_on(self.limits, ticks, trace, extremes=False))    # (a slot holds several trials: no extremes)
+            if pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
+                cur = s.rollout_walk_refill_snapshot_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill,
+                                                            pool, row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                                                            force_sample_time=self.force_sample_time, trials=trials)
+            else:
+                cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
+                                                   step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                                                   force_sample_time=self.force_sample_time, trials=trials,
+                                                   **(dict(tape=tp, tape_row0=0) if tp is not None else {}))
+        finally:
+            self._limits_off(self.limits)
         s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
         del rec["_c"]
         if tp is not None:    # (slot-major: refill_trial_walk regroups it by trial; the refill's arrays and the per-trial data stay alive with it)
@@ -407,7 +447,7 @@ class WalkingRollout:
                 rows = (trials["start"][q].clamp(min=0) + ar).clamp(max=ticks - 1)
                 idx = rows * B + trials["slot"][q].clamp(min=0)
                 out = {k: rec[k].reshape((ticks * B,) + tuple(rec[k].shape[2:])).index_select(0, idx)
-                       for k in ("com", "zmp", "land", "landing_offset", "iterations", "code")}
+                       for k in ("com", "zmp", "land", "landing_offset", "iterations", "code", "measures") if k in rec}
                 out["valid"] = ar < trials["ticks"][q]
                 return out
             trials["trace"] = trial_trace
@@ -501,6 +541,7 @@ class WalkingRollout:
         if skip_ended:    # (the queued launches keep the pointer; rec["end_tick"] goes back to the caller and outlives them)
             s.set_ended_device(rec["end_tick"])
         try:
+            rec.update(self._limits_on(self.limits, ticks, trace))
             for j, t0 in enumerate(starts):
                 t1 = starts[j + 1] if j + 1 < len(starts) else ticks
                 plan = replan.get(t0, plan)
@@ -509,6 +550,7 @@ class WalkingRollout:
                                             wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=refs,
                                             force_sample_time=self.force_sample_time, tape=tp, mismatch=mm)
         finally:
+            self._limits_off(self.limits)
             if skip_ended:
                 s.set_ended_device(None)
         del rec["_c"]
@@ -986,11 +1028,13 @@ class WalkingRollout:
         return wt
 
     def _walk_live(self, live, t0, t1, row_shift, plans, base_plan, wrench, refs, skip_ended, every=None, tape=None, tape_shift=0, cold=False, states=None,
-                   mismatch=None):
+                   mismatch=None, limits=None, limits_out=None):
         """Queues ticks t0 .. t1 - 1 on the live buffers (a snapshot dict whose "rec" is the walk record): one call of the C ABI per entry of
         walk_schedule, a snapshot launch in front of each tick k * every.  Record row = tick - row_shift, tape row = tick - tape_shift.  plans {tick:
         plan}: the latest entry at or before a tick is the plan in force (none: base_plan).  wrench = (wrench_ticks[T, B, N, 6], the tick of its row 0) or
-        None.  states[.., B, 9]: the walk is cut at every tick and row tick + 1 - row_shift receives the state that tick left.  -> {tick: snapshot}"""
+        None.  states[.., B, 9]: the walk is cut at every tick and row tick + 1 - row_shift receives the state that tick left.  limits: set_limits'
+        dict, on the handle around the calls; limits_out (a dict, or None: the codes alone) receives measures (with a trace in rec) and extremes.
+        -> {tick: snapshot}"""
         s, dt, rec = self.solver, self.cfg.sampling_time, live["rec"]
         calls, snaps = walk_schedule(t1 - t0, every, plans, t0)
         if states is not None:
@@ -1000,6 +1044,10 @@ class WalkingRollout:
         if skip_ended:    # (the queued launches keep the pointer; the tensor outlives them in the walk's dict)
             s.set_ended_device(live["end_tick"])
         try:
+            if limits_out is not None:
+                limits_out.update(self._limits_on(limits, int(rec["stats"].shape[0]), "code" in rec))
+            elif limits is not None:
+                s.set_walk_limits(**limits)
             for a, b in calls:
                 if a in snaps:
                     s.walk_snapshot_mark(live, a, cur)
@@ -1012,6 +1060,7 @@ class WalkingRollout:
                 if states is not None:
                     states[b - row_shift].copy_(live["state"])
         finally:
+            self._limits_off(limits)
             if skip_ended:
                 s.set_ended_device(None)
         s.walk_snapshot_mark(live, t1, cur)
@@ -1049,8 +1098,9 @@ class WalkingRollout:
         if states is not None:
             states[0].copy_(state0)
         inputs = dict(state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
-                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every), mismatch=mm)
-        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states, mismatch=mm)
+                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every), mismatch=mm, limits=self.limits)
+        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states, mismatch=mm,
+                              limits=self.limits, limits_out=rec)
         for c in cps.values():
             c["wrench"] = wrench
         del rec["_c"]
@@ -1124,7 +1174,8 @@ class WalkingRollout:
             prev = live["lists"][live["lists_in"]]
             tp["list_t"][0].copy_(prev[0])
             tp["list_n"][0].copy_(prev[2])
-        cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1, mismatch=mm)
+        cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1, mismatch=mm,
+                              limits=self.limits, limits_out=rec)
         del rec["_c"]
         if tp is not None:
             tp.update(dt=self.cfg.sampling_time, tick0=t0, row0=1)
@@ -1212,7 +1263,7 @@ class WalkingRollout:
                 tp["list_n"][0].copy_(prev[2])
             tp["_c"].first_row_is_first_tick = 1 if c0 == 0 else 0
             self._walk_live(live, c0, c1, c0, inp["replan"], inp["plan"], inp["wrench"], inp["refs"], inp["skip_ended"], tape=tp, tape_shift=c0 - r0,
-                            cold=c0 == 0, mismatch=mm)
+                            cold=c0 == 0, mismatch=mm, limits=inp.get("limits"))
             gx_rows = None
             if callable(grad_X):
                 seg = {k: tp[k][r0:r0 + c1 - c0] for k in ("X", "P", "lam_g", "info", "ok", "land", "plan_t", "list_t", "plan_n", "list_n")}

@@ -202,6 +202,47 @@ class BatchSolver:
             raise RuntimeError(f"cmpc_set_ended_device failed ({rc}): {self.last_error}")
         self._ended = end_tick
 
+    def set_walk_limits(self, height=(None, None), reach_max=None, margin_min=None, track_max=None, measures=None, extremes=None, off=False):
+        """cmpc_set_walk_limits: the physical limits every later record launch of this handle evaluates (tick codes 6..9, include/cmpc.h) -- height =
+        (min, max), reach_max, margin_min, track_max, None or NaN: that limit is off -- with measures, a float32 CUDA tensor [rows, B, 4] or None (the
+        per-tick trace of height, reach, margin, track), and extremes, a float32 CUDA tensor [B, 5] or None (walk_extremes_init_device sets it up).
+        off=True: the setting is cleared (the default state).  The tensors are referenced from here while the setting holds; launches already queued
+        keep the pointers they were queued with."""
+        if not hasattr(self._lib, "cmpc_set_walk_limits"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_set_walk_limits")
+        if off:
+            rc = self._lib.cmpc_set_walk_limits(self._h, None)
+            self._walk_limits = None
+        else:
+            import torch
+            nan = lambda v: float("nan") if v is None else float(v)
+            rows = 0
+            if measures is not None:
+                assert measures.is_cuda and measures.dtype == torch.float32 and measures.is_contiguous() and measures.dim() == 3 and \
+                    tuple(measures.shape[1:]) == (self.batch, _capi.WALK_MEASURES)
+                rows = int(measures.shape[0])
+            if extremes is not None:
+                assert extremes.is_cuda and extremes.dtype == torch.float32 and extremes.is_contiguous() and \
+                    tuple(extremes.shape) == (self.batch, _capi.WALK_EXTREMES)
+            lim = _capi.CmpcWalkLimits(nan(height[0]), nan(height[1]), nan(reach_max), nan(margin_min), nan(track_max),
+                                       measures.data_ptr() if measures is not None else None, rows, extremes.data_ptr() if extremes is not None else None)
+            rc = self._lib.cmpc_set_walk_limits(self._h, C.byref(lim))
+            if rc == 0:
+                self._walk_limits = (measures, extremes)
+        if rc != 0:
+            raise RuntimeError(f"cmpc_set_walk_limits failed ({rc}): {self.last_error}")
+
+    def walk_extremes_init_device(self, extremes=None, device=None):
+        """cmpc_walk_extremes_init_device: extremes [B, 5] float32 (made when None) at its start -- +inf in the minima (height min, margin min), -inf in
+        the maxima (height max, reach max, track max)."""
+        import torch
+        if extremes is None:
+            dev = torch.device("cuda", self._device_index) if device is None else device
+            extremes = torch.empty((self.batch, _capi.WALK_EXTREMES), dtype=torch.float32, device=dev)
+        assert extremes.is_cuda and extremes.dtype == torch.float32 and extremes.is_contiguous() and tuple(extremes.shape) == (self.batch, _capi.WALK_EXTREMES)
+        self._launch(extremes.device, lambda st: self._lib.cmpc_walk_extremes_init_device(self._h, extremes.data_ptr(), st))
+        return extremes
+
     def last_solve_ms(self) -> float:
         return float(self._lib.cmpc_last_solve_ms(self._h))
 

@@ -12,7 +12,10 @@ touches the GPU: the headline solve of bench.py through tools/ab_multi.sh, and t
 alternating), this build / LIB for both; and, with --refill-ab, the refill study itself at B = 256 in --refill-only children, the builds alternating.
 With --trials, after the study: the same queue once more through walk_device_refill_trials with a model per trial (friction and foot size) and all three
 parts of the plant mismatch on every local tick (hidden pushes, noise, a gain per trial), alternating with the walk_device_refill above, per trial-tick
-actually run (a mismatch ends some more trials early).  Writes its lines to --out (default profiles/r12_walk_refill.txt) as well."""
+actually run (a mismatch ends some more trials early).  With --reach-max R the falling trials end for a physical reason instead of a NaN row: a hidden
+sideways push (--fall-push) from their drawn tick on, and the reach limit R (WalkingRollout.set_limits, tick code 7) on both sides; the end ticks come from
+a pilot walk.  The NaN rows stay the default, so that the recorded profiles remain comparable.  Writes its lines to --out (default
+profiles/r12_walk_refill.txt) as well."""
 import argparse, dataclasses, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +33,15 @@ ap.add_argument("--walk-only", action="store_true", help="print the median ms pe
 ap.add_argument("--refill-only", action="store_true", help="print the median ms of the refill study at B = 256 (no per-trial data) and leave")
 ap.add_argument("--refill-ab", action="store_true", help="with --baseline: the refill study in child processes, this build / LIB")
 ap.add_argument("--trials", action="store_true", help="the study once more with per-trial models and the full per-trial mismatch")
+ap.add_argument("--reach-max", type=float, default=None, help="the trials that fall end by this physical limit on the CoM's distance from a supporting foot, in m "
+                "(set_limits, tick code 7), under a hidden sideways push of --fall-push from their drawn tick on, instead of by a NaN wrench row (the "
+                "default, which the recorded profiles used); the end ticks are then read from a pilot walk")
+ap.add_argument("--fall-push", type=float, default=8.0, help="with --reach-max: the hidden push of a falling trial, m/s^2 (at N = 20, --reach-max 0.75 and "
+                "8 m/s^2 end 224 of the 256 pushed trials inside their 24 ticks, 223 by tick code 7; 0.8 m and 3 m/s^2 only 33, all at their last tick)")
 args = ap.parse_args()
+if args.reach_max is not None and (args.trials or args.refill_only or args.refill_ab):
+    ap.error("--reach-max goes with the study alone (not with --trials, --refill-only or --refill-ab)")
+STOP = ("merge", "solver", "nonfinite") + (("limits",) if args.reach_max is not None else ())
 TT, lines = 24, []
 
 
@@ -104,8 +115,9 @@ if args.walk_only:
     sys.exit(0)
 
 
-def plain_walks(ro, B, state0, wrench):
-    """the queue as Q / B walks of TT ticks, ended problems out of the launches: WalkingRollout._walk_device's calls with the wrench rows passed through"""
+def plain_walks(ro, B, state0, wrench, hidden=None):
+    """the queue as Q / B walks of TT ticks, ended problems out of the launches: WalkingRollout._walk_device's calls with the wrench rows passed through;
+    hidden [TT, Q, 6] (--reach-max): the walks run under their columns of the hidden pushes and under the reach limit"""
     s, L, dev, dt = ro.solver, ro.L, ro.dev, cfg.sampling_time
     z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
     recs = []
@@ -117,17 +129,22 @@ def plain_walks(ro, B, state0, wrench):
             dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
             state = state0[c * B:(c + 1) * B].clone()
             ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
-            rec = s.walk_record(TT, trace=True)
+            rec = s.walk_record(TT, stop=STOP, trace=True)
             s.outcome_init_device(state, rec)
             sets = [tuple(a.clone() for a in ro.plan), tuple(torch.zeros_like(a) for a in ro.plan)]
             wt = wrench[:, c * B:(c + 1) * B].contiguous()
+            held = None if hidden is None else s.plant_mismatch(hidden_wrench=hidden[:, c * B:(c + 1) * B].contiguous(), device=dev)
             s.set_ended_device(rec["end_tick"])
+            if hidden is not None:
+                s.set_walk_limits(reach_max=args.reach_max)
             try:
                 s.rollout_walk_device(0, TT, True, ro.plan, sets[0], sets[1], 0, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=0, wrench_ticks=wt,
-                                      step=dt / ro.substeps, substeps=ro.substeps, planner=refs)
+                                      step=dt / ro.substeps, substeps=ro.substeps, planner=refs, mismatch=held)
             finally:
                 s.set_ended_device(None)
-            recs.append((rec, wt, state, dP, dX0, dX, dInfo))
+                if hidden is not None:
+                    s.set_walk_limits(off=True)
+            recs.append((rec, wt, state, dP, dX0, dX, dInfo, held))
     torch.cuda.current_stream(dev).wait_stream(ls)
     return recs
 
@@ -177,14 +194,35 @@ for B in (256, 1024) if args.large else (256,):
     wrench = np.zeros((TT, Q, N, 6), np.float32)
     for i in range(3):
         wrench[i, :, :3 - i, :3] = push[:, None, :]
-    wrench[ends[falls], falls] = np.nan
+    ro = cm.rollout.WalkingRollout(cfg, B)
+    dstate0 = torch.from_numpy(np.concatenate([com0, dcom0, h0], 1)).to(ro.dev)
+    dhidden = None
+    if args.reach_max is None:
+        wrench[ends[falls], falls] = np.nan
+    else:      # the falling trials are pushed sideways from their drawn tick on, a force the MPC is never told about; a pilot walk says when each ends
+        hidden = np.zeros((TT, Q, 6), np.float32)
+        for q in falls:
+            hidden[ends[q]:, q, 1] = args.fall_push
+        dhidden = torch.from_numpy(hidden).to(ro.dev)
+        ro.set_limits(reach_max=args.reach_max)
+        pilot = ro.walk_device_refill_trials(Q // B * TT, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], mismatch=dict(hidden_wrench=dhidden),
+                                             wrench_trials=torch.from_numpy(wrench).to(ro.dev), stop=STOP)
+        torch.cuda.synchronize()
+        assert (pilot["trials"]["start"] >= 0).all().item()
+        ends = pilot["trials"]["end_tick"].cpu().numpy()
+        codes = pilot["trials"]["end_code"].cpu().numpy()
+        falls = np.flatnonzero(ends >= 0)
+        say(f"--reach-max {args.reach_max:g} m under hidden pushes of {args.fall_push:g} m/s^2: {len(falls)} trials end early, "
+            f"{int((codes[falls] == 7).sum())} of them by tick code 7")
     run_ticks = int(np.where(ends < 0, TT, ends + 1).sum())
     T, fresh_ticks = ticks_needed(B, Q, ends)
-    ro = cm.rollout.WalkingRollout(cfg, B)
     dwrench = torch.from_numpy(wrench).to(ro.dev)
-    dstate0 = torch.from_numpy(np.concatenate([com0, dcom0, h0], 1)).to(ro.dev)
-    plain = lambda: plain_walks(ro, B, dstate0, dwrench)
-    refill = lambda: ro.walk_device_refill(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], wrench_trials=dwrench)
+    plain = lambda: plain_walks(ro, B, dstate0, dwrench, dhidden)
+    if dhidden is None:
+        refill = lambda: ro.walk_device_refill(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], wrench_trials=dwrench)
+    else:
+        refill = lambda: ro.walk_device_refill_trials(T, TT, dstate0[:, 0:3], dstate0[:, 3:6], dstate0[:, 6:9], mismatch=dict(hidden_wrench=dhidden),
+                                                      wrench_trials=dwrench, stop=STOP)
     if args.refill_only:
         refill()
         print("refill study ms", timed(refill, 5)[0])

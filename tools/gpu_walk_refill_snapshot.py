@@ -11,7 +11,9 @@ iteration counts of both (no tick of the refill walk holds a cold solve).  --res
 appended to --out and nothing else is done (no GPU is touched).
 With --baseline LIB (another build of the library in the package directory, e.g. the parent commit's), first, in child processes started before this one
 touches the GPU, the builds alternating: the headline solve of bench.py through tools/ab_multi.sh, and walk_device, walk_device_refill and
-walk_device_refill_trials at B = 256 (--child walk | refill | trials), this build / LIB.  Writes its lines to --out as well."""
+walk_device_refill_trials at B = 256 (--child walk | refill | trials), this build / LIB.  With --reach-max R the study's trials end by the reach limit R
+(WalkingRollout.set_limits, tick code 7) under their hidden pushes, on both sides; without it they end as recorded so far.  Writes its lines to --out as
+well."""
 import argparse, csv, dataclasses, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +31,10 @@ ap.add_argument("--append", action="store_true", help="add the lines to --out in
 ap.add_argument("--new-only", action="store_true", help="the refill walk from the snapshot alone, three times (for a kernel trace), and leave")
 ap.add_argument("--restore-stats", default=None, help="a rocprofv3 kernel_stats.csv of a --new-only run: quote the restore kernel's row")
 ap.add_argument("--child", choices=("walk", "refill", "trials"), default=None, help="print the median ms of one existing path at B = 256 and leave")
+ap.add_argument("--reach-max", type=float, default=None, help="the study's trials end by this physical limit on the CoM's distance from a supporting foot, in m "
+                "(set_limits, tick code 7) under their hidden pushes, on both sides; default: they end when the solve or the state fails, as recorded so far")
 args = ap.parse_args()
+STOP = ("merge", "solver", "nonfinite") + (("limits",) if args.reach_max is not None else ())
 TT, TS, B, Q, lines = 24, 12, 256, 1024, []
 
 
@@ -174,8 +179,12 @@ unit[:args.push_ticks, :, 0], unit[:args.push_ticks, :, 1] = (size * np.cos(angl
 d_of = torch.from_numpy(snapshot_of).to(ro.dev)
 
 
+if args.reach_max is not None:      # (after the pilot, which walks without limits; sticky on the roll-out: both sides walk under it)
+    ro.set_limits(reach_max=args.reach_max)
+
+
 def refill_walk(hidden, T):
-    return ro.walk_device_refill_from_snapshot(pool, T, TT, d_of, mismatch=dict(hidden_wrench=hidden))
+    return ro.walk_device_refill_from_snapshot(pool, T, TT, d_of, mismatch=dict(hidden_wrench=hidden), stop=STOP)
 
 
 def ended(scale):
@@ -212,7 +221,7 @@ if args.new_only:
 
 def today():
     return [ro.walk_resume_device_mismatch(pool, TT, dict(hidden_wrench=hidden[:, c * B:(c + 1) * B].contiguous(), tick_first=TS),
-                                           index=d_of[c * B:(c + 1) * B].contiguous(), skip_ended=True) for c in range(Q // B)]
+                                           index=d_of[c * B:(c + 1) * B].contiguous(), skip_ended=True, stop=STOP) for c in range(Q // B)]
 
 
 today(); new()       # warm-up
@@ -229,7 +238,7 @@ same = bool((end_today == tr["end_tick"]).all() and (np.where(tr["end_tick"] >= 
 it_today = int(sum(int(r["iterations_sum"].sum().item()) for r in recs))
 mt, mr = float(np.median(ms["today"])), float(np.median(ms["refill"]))
 say(f"refill walk whose trials start from a snapshot: N = {N}, B = {B}, Q = {Q} trials of {TT} resumed ticks from the snapshot of tick {TS} of a {TS + 1}-tick "
-    f"pilot, rows drawn at random; a hidden push per trial on its first {args.push_ticks} resumed ticks, at most {scale:.4f} m/s^2; today = {Q // B} walk_resume_device_mismatch(skip_ended=True), "
+    f"pilot, rows drawn at random; a hidden push per trial on its first {args.push_ticks} resumed ticks, at most {scale:.4f} m/s^2; {'' if args.reach_max is None else f'trials end by reach_max = {args.reach_max:g} m (tick code 7); '}today ={Q // B} walk_resume_device_mismatch(skip_ended=True), "
     f"refill = one walk_device_refill_from_snapshot; the two alternate, median of {args.repeats}; {torch.cuda.get_device_name(0)}")
 say(f"{int((ends >= 0).sum())} trials end early ({(ends >= 0).mean():.3f}), {run_ticks} trial-ticks run of {Q * TT}; today {Q // B} x {TT} = {Q // B * TT} ticks, refill "
     f"{T} ticks ({len(np.unique(tr['start']))} of them with at least one spawn); end ticks agree, every trial ran and was restored: {same}")

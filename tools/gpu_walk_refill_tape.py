@@ -12,7 +12,9 @@ alternate, --repeats times, the median kept:
               is told about instead of the NaN row: the trials of a split walk do not end, so this side runs MORE ticks -- both counts are reported)
 Reported per trial-tick; no pass mark.  With --baseline LIB (another build of the library in the package directory, e.g. the parent commit's), first, in child
 processes started before this one touches the GPU, the builds alternating: the headline solve of bench.py through tools/ab_multi.sh, and walk_device and
-walk_device_refill_trials at B = 256 (--child walk | trials), this build / LIB.  Writes its lines to --out as well."""
+walk_device_refill_trials at B = 256 (--child walk | trials), this build / LIB.  With --reach-max R the falling trials end by the reach limit R
+(WalkingRollout.set_limits, tick code 7) under --fall-push more of hidden sideways push from their drawn tick on, on the refill side and on the split side
+alike, the end ticks read from a pilot walk; the NaN rows stay the default.  Writes its lines to --out as well."""
 import argparse, dataclasses, os, subprocess, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +27,15 @@ ap.add_argument("--regroup-reps", type=int, default=400)
 ap.add_argument("--baseline", default=None)
 ap.add_argument("--ab-reps", type=int, default=3)
 ap.add_argument("--child", choices=("walk", "trials"), default=None, help="print the median ms of one existing path at B = 256 and leave")
+ap.add_argument("--reach-max", type=float, default=None, help="the study's falling trials end by this physical limit on the CoM's distance from a supporting foot, "
+                "in m (set_limits, tick code 7), under a hidden sideways push of --fall-push more from their drawn tick on, instead of by a NaN wrench row (the "
+                "default, which the recorded profile used); the end ticks are then read from a pilot walk, and the split walks end the same way")
+ap.add_argument("--fall-push", type=float, default=8.0, help="with --reach-max: the extra hidden push of a falling trial, m/s^2 (tools/gpu_walk_refill.py's "
+                "default; with --reach-max 0.8 and 3 m/s^2 only 21 trials end)")
 args = ap.parse_args()
+if args.reach_max is not None and args.child:
+    ap.error("--reach-max goes with the study, not with --child")
+STOP = ("merge", "solver", "nonfinite") + (("limits",) if args.reach_max is not None else ())
 TT, B, Q, lines = 24, 256, 1024, []
 
 
@@ -114,9 +124,8 @@ ends[falls] = rng.integers(0, TT, len(falls))
 wrench = np.zeros((TT, Q, N, 6), np.float32)
 for i in range(3):
     wrench[i, :, :3 - i, :3] = push[:, None, :]
-wrench[ends[falls], falls] = np.nan
-T = ticks_needed(ends)
-run_ticks = int(np.where(ends < 0, TT, ends + 1).sum())
+if args.reach_max is None:
+    wrench[ends[falls], falls] = np.nan
 dwrench = torch.from_numpy(wrench).to(ro.dev)
 d0 = [torch.from_numpy(a).to(ro.dev) for a in (com0, dcom0, h0)]
 rows = []
@@ -129,13 +138,25 @@ r2 = np.random.default_rng(11)
 mm = dict(hidden_wrench=np.concatenate([r2.normal(0, 0.3, (TT, Q, 3)), r2.normal(0, 0.05, (TT, Q, 3))], -1).astype(np.float32),
           state_noise=np.concatenate([r2.normal(0, 3e-3, (TT, Q, 3)), r2.normal(0, 1e-2, (TT, Q, 3)), r2.normal(0, 2e-3, (TT, Q, 3))], -1).astype(np.float32),
           force_gain=r2.uniform(0.9, 1.1, Q).astype(np.float32))
+if args.reach_max is not None:      # the falling trials are pushed sideways from their drawn tick on; a pilot walk says when each ends
+    for q in falls:
+        mm["hidden_wrench"][ends[q]:, q, 1] += np.float32(args.fall_push)
 mm = {k: torch.from_numpy(v).to(ro.dev) for k, v in mm.items()}
-untaped = lambda: ro.walk_device_refill_trials(T, TT, *d0, models=models, mismatch=mm, wrench_trials=dwrench)
+if args.reach_max is not None:
+    ro.set_limits(reach_max=args.reach_max)
+    pilot = ro.walk_device_refill_trials(Q // B * TT, TT, *d0, models=models, mismatch=mm, wrench_trials=dwrench, stop=STOP)
+    torch.cuda.synchronize()
+    assert (pilot["trials"]["start"] >= 0).all().item()
+    ends = pilot["trials"]["end_tick"].cpu().numpy()
+    print(f"--reach-max {args.reach_max:g}: {int((ends >= 0).sum())} trials end early, {int((pilot['trials']['end_code'] == 7).sum().item())} by tick code 7", flush=True)
+T = ticks_needed(ends)
+run_ticks = int(np.where(ends < 0, TT, ends + 1).sum())
+untaped = lambda: ro.walk_device_refill_trials(T, TT, *d0, models=models, mismatch=mm, wrench_trials=dwrench, stop=STOP)
 if args.child == "trials":
     untaped()
     print("trials ms", timed(untaped, 5)[0])
     sys.exit(0)
-taped = lambda: ro.walk_device_refill_taped(T, TT, *d0, models=models, mismatch=mm, wrench_trials=dwrench)
+taped = lambda: ro.walk_device_refill_taped(T, TT, *d0, models=models, mismatch=mm, wrench_trials=dwrench, stop=STOP)
 
 # ---- the taped walk against the untaped one
 untaped(); w = taped()      # warm-up
@@ -147,8 +168,8 @@ for _ in range(args.repeats):
 tr = {k: v.cpu().numpy() for k, v in w["trials"].items() if hasattr(v, "cpu")}
 same = bool((tr["end_tick"] == ends).all() and int(tr["ticks"].sum()) == run_ticks and (tr["start"] >= 0).all())
 mu, mt = float(np.median(ms["untaped"])), float(np.median(ms["taped"]))
-say(f"refill walk taped: N = {N}, B = {B}, Q = {Q} trials of {TT} ticks, a model and the full mismatch per trial, {int((ends >= 0).sum())} trials ended early by a "
-    f"NaN wrench row, {run_ticks} trial-ticks run of {Q * TT}, {T} ticks; the variants alternate, median of {args.repeats}; {torch.cuda.get_device_name(0)}")
+say(f"refill walk taped: N = {N}, B = {B}, Q = {Q} trials of {TT} ticks, a model and the full mismatch per trial, {int((ends >= 0).sum())} trials ended early by "
+    f"{'a NaN wrench row' if args.reach_max is None else f'reach_max = {args.reach_max:g} m under hidden pushes of {args.fall_push:g} m/s^2 more'}, {run_ticks} trial-ticks run of {Q * TT}, {T} ticks; the variants alternate, median of {args.repeats}; {torch.cuda.get_device_name(0)}")
 say(f"end ticks as drawn, every trial ran: {same}")
 say(f"untaped {mu:.2f} ms ({fmt(ms['untaped'])}) = {mu * 1e3 / run_ticks:.3f} us per trial-tick | taped {mt:.2f} ms ({fmt(ms['taped'])}) = "
     f"{mt * 1e3 / run_ticks:.3f} us per trial-tick | taped / untaped = {mt / mu:.4f} (two launches more per tick: the copy kernel and the multipliers)")
@@ -179,13 +200,16 @@ gX = torch.randn((TT, Q, L.nx), dtype=torch.float32, device=ro.dev)
 reverse = lambda: ro.backward_device_refill(w, gS, gX)
 dpush = torch.from_numpy(push).to(ro.dev)
 split_ros = [cm.rollout.WalkingRollout(cfg, B, models=models[c * B:(c + 1) * B].contiguous()) for c in range(Q // B)]
+if args.reach_max is not None:      # (the split walks end the same way)
+    for r in split_ros:
+        r.set_limits(reach_max=args.reach_max)
 
 
 def split():
     out = []
     for c, r in enumerate(split_ros):
         sl = slice(c * B, (c + 1) * B)
-        o = r.walk_device_taped(TT, d0[0][sl], d0[1][sl], d0[2][sl], push=dpush[sl], push_ticks=3, skip_ended=True,
+        o = r.walk_device_taped(TT, d0[0][sl], d0[1][sl], d0[2][sl], push=dpush[sl], push_ticks=3, skip_ended=True, stop=STOP,
                                 mismatch={k: (v[sl] if k == "force_gain" else v[:, sl]).contiguous() for k, v in mm.items()})
         out.append((o, r.backward_device(o, gS[:, sl].contiguous(), gX[:, sl].contiguous())))
     return out
