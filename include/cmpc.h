@@ -751,8 +751,8 @@ int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* 
  * refill and snapshot forms included -- the gates of the reverse and forward walks, the ended mask and the refill queue read dEndTick and so inherit the
  * physical endings.  On a refill walk dExtremes must be NULL (CMPC_ERR_ARG otherwise): a slot's extremes would span several trials, so per-trial
  * extremes come from the measures trace and dTrialOf; snapshots do not carry extremes.  CMPC_ERR_ARG for height_min > height_max, for dMeasures with
- * rows < 1, and, from the record calls, for a row >= rows.  Out of scope: per-trial limits, limits that must hold for n consecutive ticks, derivatives
- * of the measures. */
+ * rows < 1, and, from the record calls, for a row >= rows.  Out of scope: per-trial limits, limits that must hold for n consecutive ticks.  (The
+ * derivatives of the measures: "the measures, differentiated", behind the forward walk.) */
 #define CMPC_WALK_MEASURES 4
 #define CMPC_WALK_EXTREMES 5   /* height min, height max, reach max, margin min, track max */
 typedef struct cmpc_walk_limits {
@@ -1396,6 +1396,86 @@ int cmpc_rollout_walk_jvp_gate(const cmpc_walk_jvp_gate* g);
 /* the same step as ONE launch of the gate kernel, device pointers throughout (batch and horizon the handle's): what the forward walk queues between its
  * ticks.  Asynchronous on `stream` (NULL: the handle's); it takes no part in the tick VJP's event. */
 int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g, void* stream);
+
+/* ---- the measures, differentiated: a loss on the stability measures of a taped walk, reverse and forward (derivation: DESIGN.md 7f, "Measures,
+ * differentiated") ----
+ * The four measures of "physical limits" above are a function of what a tick left: dStates[row + 1] (com, dcom), the knot-1 foot positions of dX, the
+ * stage-1 rotations and the knot-1 comRef row of dP, and the model's corners.  Its derivative ignores the final rounding to float.  The independent
+ * inputs per (row, problem) are CMPC_WALK_MEASURE_INPUTS = 44 numbers, in this order:
+ *     com[3], dcom[3] (dcom_z has zero derivative), q_c[2][3], omega_c[2][3], corner[2][4][3], comRef_xy[2]
+ * omega_c is the body-frame tangent of the stage-1 rotation, R <- R Exp(omega), the convention of every rotation gradient here; the margin reads rows 0
+ * and 1 of R only.  Branches -- each a SELECT, never a multiply by zero, so that NaN in what a branch does not take cannot leak:
+ *     height  d/dcom_z = 1, d/dq_c,z = -1/n for c in S
+ *     reach   (com - q_c) / r of the foot the forward's `r > reach` chain keeps (the first foot wins a tie); zero when r == 0
+ *     track   (com_xy - ref_xy) / track; zero when track == 0
+ *     margin  the derivative of a smooth branch of the forward's own comparison chain: the same candidate order, the same strict <, the same
+ *             length >= 1e-12 exclusions, the same arg-max or arg-min vertex (the first in index order), with the dependence of the unit normal on its
+ *             two defining points, or on xi, included.  The branch is the chain's winner among the FACES of the region -- a pair whose extremal
+ *             vertex lies on the pair's own line, a direction whose extremal vertex is its own point, both within 1e-9 m -- and not simply the
+ *             chain's winner: the parallel sides of a rectangular sole alias each other (one normal, one value to rounding, the last bit decides
+ *             which the forward keeps), and an alias equals the margin only while the sole stays a rectangle, so in the corners and in omega its
+ *             gradient is no element of the generalised gradient.  The least over all directions is attained at a face, so that winner has the
+ *             forward's value to rounding; with no face admitted the chain's own winner is taken.  No candidate left: 0.  A vertex the forward
+ *             filled from the other foot (single support) sends
+ *             its derivative to the foot and corner it was copied from: a foot outside S receives exactly zero.  xi = com_xy + dcom_xy tau, tau =
+ *             sqrt(max(height, 0) / g): through tau the margin also depends on com_z and q_z, dtau/dheight = 1 / (2 g tau) when height > 0 and tau > 0,
+ *             and 0 otherwise
+ *     a measure the forward reports as NaN (S empty, a state that is not finite) has a zero row, and its cotangent is not read
+ * The measures are piecewise smooth: at a tie between branches this is ONE element of the generalised gradient, the branch the forward's comparisons
+ * pick.  Nothing is smoothed.
+ *
+ * cmpc_walk_measures_vjp_device: ONE launch over rows row0 .. row0 + ticks - 1 of the tape (tick numbers tick0 ..), one thread per (row, problem); no LDS,
+ * no barrier, no atomics; lanes past ticks * B touch no memory.  It reads the tape's dX[r], dP[r], dStates[r + 1] and the corners the record launch reads
+ * (the handle's, or the installed models').  The arrays of cmpc_walk_measure_grads are indexed by tape row, as those of cmpc_walk_grads:
+ *     dGradMeasures[rows][B][4] double        in: the cotangents of height, reach, margin, track
+ *     dGradStates[rows + 1][B][9] double      +=, row r + 1, entries 0..4 (com, dcom_xy); entries 5..8 are not touched: the seeds of the reverse walk
+ *     dGradX[rows][B][n_x] float              +=, the six knot-1 foot positions only; each term formed in double, rounded once, then one float add
+ *     dDirect[rows][B][CMPC_WALK_MEASURE_DIRECT = 32] double   written whole: comRef_xy (2), omega [2][3], corner [2][4][3] -- what no seed of the
+ *                                             reverse walk carries
+ * A term that is exactly zero is not added to a += entry (the entry keeps its bits), so a zero cotangent leaves the seeds as they were to the bit.
+ * Endings, the reverse walk's convention: with e = dEndTick[b] (NULL or -1: never), the rows with tick0 + r < e count.  Row e itself -- the measure that
+ * fired -- and every later row select zero in dDirect and leave the += entries unwritten; nothing of such a row is read, so NaN there cannot leak.
+ * cmpc_walk_measures_vjp_fold_device: one small launch for behind the reverse walk, over `rows` rows from the pointers given.  It adds dDirect's comRef
+ * pair to the knot-1 comRef xy of dGradP[rows][B][n_p] float (rounded once; a zero term is not added), so that
+ * cmpc_reference_from_planner_vjp_device carries it to the planner's trajectories, and it sums dDirect's corner words over the rows, in ascending row
+ * order, into dGradModel[B][10..33] (one thread per problem and word, no atomics).  Either output may be NULL.
+ * cmpc_walk_measures_jvp_device: the transpose, k columns, in cmpc_walk_dirs' layouts, indexed by tape row, so the forward walk's outputs feed it:
+ *     dDirStates[rows + 1][B][k][9] double, dDirX[rows][B][k][n_x] float, dDirP[rows][B][k][n_p] float or NULL (its knot-1 comRef xy only),
+ *     dDirModel[B][k][34] double or NULL (its corners only)  ->  dDirMeasures[rows][B][k][4] double; rows at or past e select zero
+ * One thread per (row, problem) forms the partials once and contracts the k columns.
+ * Host forms, no handle and no GPU, bit-equal to the kernels: the arrays start at the first row of the call (X[rows][B][n_x], P[rows][B][n_p],
+ * states[rows + 1][B][9], and the gradient / direction arrays likewise); corners [2][4][3] float of problem 0 with problem b's corners_stride floats
+ * further on (0: one set for the batch), gravity > 0, as cmpc_rollout_record_limits.  cmpc_walk_measures_jacobian: the dense [rows][B][4][44], every
+ * row counted, host only (for tests; the kernels never form it).
+ * CMPC_ERR_ARG: a NULL required pointer, rows outside the tape (rows < 1 on the host), k < 1, horizon < 2.
+ * Out of scope: chaining the omega term of dDirect into the lists' or the planner's orientations (the tick VJP has no per-stage rotation seed: the term
+ * is returned and not carried); checkpointed reverse walks; per-trial corners of a regrouped refill tape (the corners are the handle's or the installed
+ * models'); derivatives of dExtremes; any smoothing of the min / max. */
+#define CMPC_WALK_MEASURE_INPUTS 44
+#define CMPC_WALK_MEASURE_DIRECT 32
+typedef struct cmpc_walk_measure_grads {
+    const double* dGradMeasures;
+    double* dGradStates; float* dGradX;
+    double* dDirect;
+} cmpc_walk_measure_grads;
+typedef struct cmpc_walk_measure_dirs {
+    const double* dDirStates; const float* dDirX; const float* dDirP; const double* dDirModel;
+    double* dDirMeasures;
+} cmpc_walk_measure_dirs;
+int cmpc_walk_measures_vjp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                  const cmpc_walk_measure_grads* g, void* stream);
+int cmpc_walk_measures_vjp_fold_device(cmpc_handle h, int rows, const double* dDirect, float* dGradP, double* dGradModel, void* stream);
+int cmpc_walk_measures_jvp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
+                                  const cmpc_walk_measure_dirs* d, void* stream);
+int cmpc_walk_measures_vjp(int horizon, int batch, int tick0, int rows, const float* X, const float* P, const float* states, const int* end_tick,
+                           const float* corners, int corners_stride, double gravity, const double* grad_measures, double* grad_states, float* grad_X,
+                           double* direct);
+int cmpc_walk_measures_vjp_fold(int horizon, int batch, int rows, const double* direct, float* grad_P, double* grad_model);
+int cmpc_walk_measures_jvp(int horizon, int batch, int tick0, int rows, int k, const float* X, const float* P, const float* states, const int* end_tick,
+                           const float* corners, int corners_stride, double gravity, const double* dir_states, const float* dir_X, const float* dir_P,
+                           const double* dir_model, double* dir_measures);
+int cmpc_walk_measures_jacobian(int horizon, int batch, int rows, const float* X, const float* P, const float* states, const float* corners,
+                                int corners_stride, double gravity, double* jacobian);
 
 /* ---- plant-model mismatch on the device walk: hidden pushes, sensor noise, force gain (derivation: DESIGN.md 7f, "Mismatch") ----
  * In every entry point above the plant IS the model: the wrench the plant integrates is the knot-0 wrench rows of dP, which setState handed to the MPC; the

@@ -9,5 +9,5 @@ from . import _capi, config, contacts, distributed, layout, rollout, solver, syn
 from .config import CentroidalMPCConfig, ContactConfig  # noqa: F401
 from .layout import Layout, cold_start, pack_parameters  # noqa: F401
 from .rollout import (WalkingRollout, rollout_differentiable, rollout_differentiable_checkpointed,  # noqa: F401
-                      rollout_differentiable_checkpointed_mismatch, walk_schedule)
+                      rollout_differentiable_checkpointed_mismatch, rollout_differentiable_measures, walk_schedule)
 from .solver import BatchSolver, CentroidalMPC, rotate_parameters, solve_differentiable  # noqa: F401

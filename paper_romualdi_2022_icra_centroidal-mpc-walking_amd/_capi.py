@@ -105,6 +105,20 @@ class CmpcWalkLimits(C.Structure):
                 ("dMeasures", C.c_void_p), ("rows", C.c_int), ("dExtremes", C.c_void_p)]
 
 
+WALK_MEASURE_INPUTS = 44   # CMPC_WALK_MEASURE_INPUTS: com 3, dcom 3, q [2][3], omega [2][3], corner [2][4][3], comRef_xy 2
+WALK_MEASURE_DIRECT = 32   # CMPC_WALK_MEASURE_DIRECT: comRef_xy 2, omega [2][3], corner [2][4][3]
+
+
+class CmpcWalkMeasureGrads(C.Structure):
+    """mirror of cmpc_walk_measure_grads (include/cmpc.h): the cotangents and outputs of cmpc_walk_measures_vjp_device"""
+    _fields_ = [(k, C.c_void_p) for k in ("dGradMeasures", "dGradStates", "dGradX", "dDirect")]
+
+
+class CmpcWalkMeasureDirs(C.Structure):
+    """mirror of cmpc_walk_measure_dirs (include/cmpc.h): the direction columns and the output of cmpc_walk_measures_jvp_device"""
+    _fields_ = [(k, C.c_void_p) for k in ("dDirStates", "dDirX", "dDirP", "dDirModel", "dDirMeasures")]
+
+
 class CmpcTickTape(C.Structure):
     """mirror of cmpc_tick_tape (include/cmpc.h): what a forward tick left behind, read by cmpc_rollout_tick_vjp_device"""
     _fields_ = [(k, C.c_void_p) for k in (
@@ -256,6 +270,8 @@ EXPORTS = [
     "cmpc_rollout_walk_refill_taped_device", "cmpc_rollout_tape_regroup_device", "cmpc_rollout_tape_regroup",
     "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
     "cmpc_set_walk_limits", "cmpc_walk_extremes_init_device", "cmpc_rollout_record_limits",
+    "cmpc_walk_measures_vjp_device", "cmpc_walk_measures_vjp_fold_device", "cmpc_walk_measures_jvp_device",
+    "cmpc_walk_measures_vjp", "cmpc_walk_measures_vjp_fold", "cmpc_walk_measures_jvp", "cmpc_walk_measures_jacobian",
 ]
 
 _lib = None
@@ -397,6 +413,14 @@ def lib():
             L.cmpc_rollout_walk_jvp_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs), vp]
             L.cmpc_rollout_walk_jvp_gate.argtypes = [C.POINTER(CmpcWalkJvpGate)]
             L.cmpc_rollout_walk_jvp_gate_device.argtypes = [vp, C.POINTER(CmpcWalkJvpGate), vp]
+        if hasattr(L, "cmpc_walk_measures_vjp_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            L.cmpc_walk_measures_vjp_device.argtypes = [vp, i, i, C.POINTER(CmpcWalkTape), i, vp, C.POINTER(CmpcWalkMeasureGrads), vp]
+            L.cmpc_walk_measures_vjp_fold_device.argtypes = [vp, i, vp, vp, vp, vp]
+            L.cmpc_walk_measures_jvp_device.argtypes = [vp, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkMeasureDirs), vp]
+            L.cmpc_walk_measures_vjp.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, i, d, vp, vp, vp, vp]
+            L.cmpc_walk_measures_vjp_fold.argtypes = [i, i, i, vp, vp, vp]
+            L.cmpc_walk_measures_jvp.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp, i, d, vp, vp, vp, vp, vp]
+            L.cmpc_walk_measures_jacobian.argtypes = [i, i, i, vp, vp, vp, vp, i, d, vp]
         if hasattr(L, "cmpc_reference_from_planner_vjp"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             pr = C.POINTER(CmpcPlannerRefs)
             L.cmpc_reference_from_planner_vjp.argtypes = [i, d, i, i, i, pr, vp, vp, vp, vp]

@@ -1556,6 +1556,116 @@ int cmpc_walk_extremes_init_device(cmpc_handle h, float* dExtremes, void* stream
     return launch_status(h, "extremes init", lrc);
 }
 
+// ---- the measures differentiated (include/cmpc.h): the host forms run the kernels' own per-entry functions ----
+static bool measures_rows_ok(int horizon, int batch, int tick0, int rows, const float* X, const float* P, const float* states, const float* corners,
+                             int corners_stride, double gravity)
+{
+    return horizon >= 2 && batch >= 1 && tick0 >= 0 && rows >= 1 && X && P && states && corners && corners_stride >= 0 && gravity > 0;
+}
+
+int cmpc_walk_measures_vjp(int horizon, int batch, int tick0, int rows, const float* X, const float* P, const float* states, const int* end_tick,
+                           const float* corners, int corners_stride, double gravity, const double* grad_measures, double* grad_states, float* grad_X,
+                           double* direct)
+{
+    if (!measures_rows_ok(horizon, batch, tick0, rows, X, P, states, corners, corners_stride, gravity) || !grad_measures || !grad_states || !grad_X || !direct)
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_vjp: bad argument");
+    const CmpcMeasureVjpArgs v{horizon, batch, tick0, rows, X, P, states, end_tick, corners, corners_stride, gravity, grad_measures, grad_states, grad_X, direct};
+    for (int r = 0; r < rows; ++r)
+        for (int b = 0; b < batch; ++b) cmpc_walk_measures_vjp_entry(v, r, b);
+    return CMPC_OK;
+}
+
+int cmpc_walk_measures_vjp_fold(int horizon, int batch, int rows, const double* direct, float* grad_P, double* grad_model)
+{
+    if (horizon < 2 || batch < 1 || rows < 1 || !direct) return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_fold: bad argument");
+    const size_t np = (size_t)rows * batch, nm = (size_t)24 * batch;
+    for (size_t e = 0; e < (np > nm ? np : nm); ++e) cmpc_walk_measures_fold_entry(horizon, batch, rows, direct, grad_P, grad_model, e);
+    return CMPC_OK;
+}
+
+int cmpc_walk_measures_jvp(int horizon, int batch, int tick0, int rows, int k, const float* X, const float* P, const float* states, const int* end_tick,
+                           const float* corners, int corners_stride, double gravity, const double* dir_states, const float* dir_X, const float* dir_P,
+                           const double* dir_model, double* dir_measures)
+{
+    if (!measures_rows_ok(horizon, batch, tick0, rows, X, P, states, corners, corners_stride, gravity) || k < 1 || !dir_states || !dir_X || !dir_measures)
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_jvp: bad argument");
+    const CmpcMeasureJvpArgs v{horizon, batch, tick0, rows, k, X, P, states, end_tick, corners, corners_stride, gravity, dir_states, dir_X, dir_P, dir_model,
+                               dir_measures};
+    for (int r = 0; r < rows; ++r)
+        for (int b = 0; b < batch; ++b) cmpc_walk_measures_jvp_entry(v, r, b);
+    return CMPC_OK;
+}
+
+int cmpc_walk_measures_jacobian(int horizon, int batch, int rows, const float* X, const float* P, const float* states, const float* corners,
+                                int corners_stride, double gravity, double* jacobian)
+{
+    if (!measures_rows_ok(horizon, batch, 0, rows, X, P, states, corners, corners_stride, gravity) || !jacobian)
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_jacobian: bad argument");
+    const int nx = 45 * horizon + 15, np = CmpcIdx{horizon}.np();
+    for (int r = 0; r < rows; ++r) {
+        const CmpcMeasureArgs a{horizon, batch, X + (size_t)r * batch * nx, P + (size_t)r * batch * np, states + (size_t)(r + 1) * batch * 9, corners,
+                                corners_stride, gravity};
+        for (int b = 0; b < batch; ++b)
+            for (int m = 0; m < 4; ++m) {   // row m: the VJP of the unit cotangent e_m (products with 1.0 and sums with 0.0 are exact)
+                double w[4] = {0.0, 0.0, 0.0, 0.0}, gs[5], gq[6], d[32];
+                w[m] = 1.0;
+                cmpc_walk_measures_vjp_problem(a, b, w, gs, gq, d);
+                double* J = jacobian + (((size_t)r * batch + b) * 4 + m) * CMPC_WALK_MEASURE_INPUTS;
+                for (int i = 0; i < 3; ++i) J[i] = gs[i];
+                J[3] = gs[3]; J[4] = gs[4]; J[5] = 0.0;
+                for (int i = 0; i < 6; ++i) J[6 + i] = gq[i];
+                for (int i = 0; i < 6; ++i) J[12 + i] = d[2 + i];
+                for (int i = 0; i < 24; ++i) J[18 + i] = d[8 + i];
+                J[42] = d[0]; J[43] = d[1];
+            }
+    }
+    return CMPC_OK;
+}
+
+// the rows of a call inside the tape, and the tape arrays the measures read
+static const char* measures_tape_refusal(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0)
+{
+    if (!h || !tape || !tape->dX || !tape->dP || !tape->dStates) return "null argument or incomplete tape";
+    if (h->cfg.horizon < 2) return "the measures refer to stage 1: the horizon must be at least 2";
+    if (tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows) return "bad argument (the rows must lie inside the tape)";
+    return nullptr;
+}
+
+int cmpc_walk_measures_vjp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
+                                  const cmpc_walk_measure_grads* g, void* stream)
+{
+    if (const char* why = measures_tape_refusal(h, tick0, ticks, tape, row0)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_walk_measures_vjp_device: ") + why);
+    if (!g || !g->dGradMeasures || !g->dGradStates || !g->dGradX || !g->dDirect)
+        return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_device: dGradMeasures, dGradStates, dGradX and dDirect are needed");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, r0 = (size_t)row0;
+    const CmpcMeasureVjpArgs v{h->cfg.horizon, h->B, tick0, ticks, tape->dX + r0 * B * h->L.nx, tape->dP + r0 * B * h->L.np, tape->dStates + r0 * B * 9,
+                               dEndTick, model_corners(h), corners_stride(h), h->cfg.gravity, g->dGradMeasures + r0 * B * CMPC_WALK_MEASURES,
+                               g->dGradStates + r0 * B * 9, g->dGradX + r0 * B * h->L.nx, g->dDirect + r0 * B * CMPC_WALK_MEASURE_DIRECT};
+    return launch_status(h, "measures VJP", cmpc_launch_walk_measures_vjp(&v, stream_of(h, stream)));
+}
+
+int cmpc_walk_measures_vjp_fold_device(cmpc_handle h, int rows, const double* dDirect, float* dGradP, double* dGradModel, void* stream)
+{
+    if (!h || !dDirect || rows < 1 || h->cfg.horizon < 2) return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_fold_device: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_status(h, "measures fold", cmpc_launch_walk_measures_fold(h->cfg.horizon, h->B, rows, dDirect, dGradP, dGradModel, stream_of(h, stream)));
+}
+
+int cmpc_walk_measures_jvp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
+                                  const cmpc_walk_measure_dirs* d, void* stream)
+{
+    if (const char* why = measures_tape_refusal(h, tick0, ticks, tape, row0)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_walk_measures_jvp_device: ") + why);
+    if (k < 1 || !d || !d->dDirStates || !d->dDirX || !d->dDirMeasures)
+        return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_jvp_device: k >= 1, dDirStates, dDirX and dDirMeasures are needed");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, r0 = (size_t)row0, K = (size_t)k;
+    const CmpcMeasureJvpArgs v{h->cfg.horizon, h->B, tick0, ticks, k, tape->dX + r0 * B * h->L.nx, tape->dP + r0 * B * h->L.np, tape->dStates + r0 * B * 9,
+                               dEndTick, model_corners(h), corners_stride(h), h->cfg.gravity, d->dDirStates + r0 * B * K * 9, d->dDirX + r0 * B * K * h->L.nx,
+                               d->dDirP ? d->dDirP + r0 * B * K * h->L.np : nullptr, d->dDirModel, d->dDirMeasures + r0 * B * K * CMPC_WALK_MEASURES};
+    return launch_status(h, "measures JVP", cmpc_launch_walk_measures_jvp(&v, stream_of(h, stream)));
+}
+
 int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
                                const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, void* stream)
 {

@@ -451,6 +451,451 @@ __host__ __device__ inline void cmpc_record_problem(const CmpcRecordArgs& a, con
     tally[4] = (!before && code >= 2 && code <= 4) ? 1 : 0;
 }
 
+// ---- the measures differentiated (include/cmpc.h, "the measures, differentiated"; DESIGN.md 7f, "Measures, differentiated") ----
+// The derivative of cmpc_walk_measures in its 44 inputs per (row, problem) -- com[3], dcom[3], q[2][3], omega[2][3] (the body-frame tangent of the stage-1
+// rotation, R <- R Exp(omega)), corner[2][4][3], comRef_xy[2] -- ignoring the final rounding to float.  Stated once, as the partials of one problem
+// (cmpc_walk_measures_partials); the VJP, the JVP and the host's dense Jacobian are contractions of them.  One statement for the host forms and the
+// kernels: double from the float inputs, contraction off, so that the two are bit-equal.  Every branch is a SELECT, never a multiply by zero: what a
+// branch does not take is not read into the result, so NaN there cannot leak.  At a tie between branches (two faces of the support region at one
+// distance, two feet at one distance, two vertices at one projection) the first in the forward's order is taken: ONE element of the generalised gradient.
+struct CmpcMeasureArgs {
+    int N, B;
+    const float* X; const float* P; const float* state_out;    // one tape row: [B][n_x], [B][n_p], and dStates[row + 1] [B][9]
+    const float* corners; int corners_stride; double gravity;  // as CmpcLimitArgs
+};
+// the gradient of cmpc_support_margin in xi and in at most three of the 8 points (idx < 0: no term)
+struct CmpcMarginGrad {
+    double gxi[2];
+    int idx[3]; double gx[3], gy[3];
+};
+// a candidate of the margin's chain as the gradient needs it: kind 1 a pair (i, j) with sign s and extremal vertex k, kind 2 the direction from point i
+struct CmpcMarginPick {
+    bool any; double m;
+    int kind, i, j, k;
+    double ex, ey, len, a, b, s;
+};
+// the chain's step: candidate c replaces the pick if it is admitted and the first, or strictly less
+__host__ __device__ inline void cmpc_margin_offer(CmpcMarginPick& p, bool admitted, double c, int kind, int i, int j, int k, double ex, double ey, double len,
+                                                  double a, double b, double s)
+{
+    if (admitted && (!p.any || c < p.m)) {
+        p.any = true; p.m = c; p.kind = kind; p.i = i; p.j = j; p.k = k;
+        p.ex = ex; p.ey = ey; p.len = len; p.a = a; p.b = b; p.s = s;
+    }
+}
+// cmpc_support_margin's comparison chain, expression for expression -- the same candidate order, the same strict <, the same len >= 1e-12 exclusions, the
+// arg-max / arg-min vertex the first in index order -- remembering a candidate, then the gradient of that smooth branch:
+//   a pair (i, j), e = v_j - v_i, s = +1 with the arg-max vertex k (c0) or -1 with the arg-min (c1): c = (e_y a - e_x b) / |e|, (a, b) = s (v_k - xi);
+//       dc/dv_k = s n, dc/dxi = -s n, n = (e_y, -e_x) / |e|;  dc/de = ((-b, a) - c e / |e|) / |e| goes to v_j and, negated, to v_i
+//   a direction from point i, e = xi - v_i, k the arg-max: c = e.r / |e|, r = v_k - xi, u = e / |e|;
+//       dc/dv_k = u, dc/de = w = (r - c u) / |e| goes to xi and, negated, to v_i, dc/dxi = w - u
+//   no candidate: zero.
+// WHICH candidate.  The chain's winner gives the VALUE, but need not be the branch that is active: the parallel sides of a rectangular sole alias each
+// other -- the pair (0, 3) taken backwards has the normal and, to rounding, the value of the pair (1, 2), with its extremal vertex k on the far side --
+// and which of the two the strict < keeps is decided by the last bit.  Such an alias equals the margin only while the sole stays a rectangle: in the
+// corners and in omega its gradient is NOT an element of the generalised gradient (nearby generic points are all governed by the true side).  So the
+// same chain is run over the FACES alone -- a pair whose extremal vertex lies on the pair's own line, a direction whose extremal vertex is its own point
+// (both within 1e-9 m: a million times the rounding, a thousandth of what a sole's geometry resolves) -- and its winner is differentiated.  The least
+// over all directions is always attained at a face (an edge's normal or a vertex's direction), so this winner has the chain's value to rounding; where
+// no face is admitted the chain's own winner is used.  Between two faces at one distance (a true kink) the first in the chain's order wins.
+__host__ __device__ inline void cmpc_support_margin_grad(const double (&vx)[8], const double (&vy)[8], double xi_x, double xi_y, CmpcMarginGrad& g)
+{
+#pragma clang fp contract(off)
+    const double on_line = 1e-9;
+    CmpcMarginPick win{false, 0.0, 0, -1, -1, -1, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0}, face = win;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int j = i + 1; j < 8; ++j) {
+            const double ex = vx[j] - vx[i], ey = vy[j] - vy[i];
+            const double len = __builtin_sqrt(ex * ex + ey * ey);
+            const double dxi = ey * xi_x - ex * xi_y;
+            double hi = ey * vx[0] - ex * vy[0], lo = hi;
+            int khi = 0, klo = 0;
+            double hx = vx[0], hy = vy[0], lx = vx[0], ly = vy[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) {
+                const double d = ey * vx[k] - ex * vy[k];
+                const bool up = d > hi, dn = d < lo;
+                hi = up ? d : hi; khi = up ? k : khi; hx = up ? vx[k] : hx; hy = up ? vy[k] : hy;
+                lo = dn ? d : lo; klo = dn ? k : klo; lx = dn ? vx[k] : lx; ly = dn ? vy[k] : ly;
+            }
+            const double c0 = (hi - dxi) / len, c1 = (dxi - lo) / len;
+            const bool second = c1 < c0, admitted = len >= 1e-12;
+            const double a0 = hx - xi_x, b0 = hy - xi_y, a1 = -(lx - xi_x), b1 = -(ly - xi_y);
+            cmpc_margin_offer(win, admitted, second ? c1 : c0, 1, i, j, second ? klo : khi, ex, ey, len, second ? a1 : a0, second ? b1 : b0,
+                              second ? -1.0 : 1.0);
+            // the pair's own line: d_i and d_j (one number but for rounding) against the extremes
+            const double di = ey * vx[i] - ex * vy[i], dj = ey * vx[j] - ex * vy[j];
+            const double top = di > dj ? di : dj, bot = di < dj ? di : dj;
+            cmpc_margin_offer(face, admitted && hi - top <= on_line * len, c0, 1, i, j, khi, ex, ey, len, a0, b0, 1.0);
+            cmpc_margin_offer(face, admitted && bot - lo <= on_line * len, c1, 1, i, j, klo, ex, ey, len, a1, b1, -1.0);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const double ex = xi_x - vx[i], ey = xi_y - vy[i];
+        const double len = __builtin_sqrt(ex * ex + ey * ey);
+        double hi = ex * (vx[0] - xi_x) + ey * (vy[0] - xi_y);
+        int khi = 0;
+        double hx = vx[0], hy = vy[0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            const double d = ex * (vx[k] - xi_x) + ey * (vy[k] - xi_y);
+            const bool up = d > hi;
+            hi = up ? d : hi; khi = up ? k : khi; hx = up ? vx[k] : hx; hy = up ? vy[k] : hy;
+        }
+        const double c = hi / len;
+        const bool admitted = len >= 1e-12;
+        cmpc_margin_offer(win, admitted, c, 2, i, -1, khi, ex, ey, len, hx - xi_x, hy - xi_y, 1.0);
+        // its own point: e.(v_i - xi) = -|e|^2 is the greatest projection
+        cmpc_margin_offer(face, admitted && hi + len * len <= on_line * len, c, 2, i, -1, khi, ex, ey, len, hx - xi_x, hy - xi_y, 1.0);
+    }
+    const CmpcMarginPick p = face.any ? face : win;
+    const int kind = p.kind, bi = p.i, bj = p.j, bk = p.k;
+    const double bex = p.ex, bey = p.ey, blen = p.len, ba = p.a, bb = p.b, bc = p.m, bs = p.s;
+    g.gxi[0] = g.gxi[1] = 0.0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) { g.idx[t] = -1; g.gx[t] = g.gy[t] = 0.0; }
+    if (kind == 1) {
+        const double nx = bey / blen, ny = -bex / blen;
+        const double dex = (-bb - (bc * bex) / blen) / blen, dey = (ba - (bc * bey) / blen) / blen;
+        g.idx[0] = bk; g.gx[0] = bs * nx; g.gy[0] = bs * ny;
+        g.idx[1] = bj; g.gx[1] = dex; g.gy[1] = dey;
+        g.idx[2] = bi; g.gx[2] = -dex; g.gy[2] = -dey;
+        g.gxi[0] = -(bs * nx); g.gxi[1] = -(bs * ny);
+    } else if (kind == 2) {
+        const double ux = bex / blen, uy = bey / blen;
+        const double wx = (ba - bc * ux) / blen, wy = (bb - bc * uy) / blen;
+        g.idx[0] = bk; g.gx[0] = ux; g.gy[0] = uy;
+        g.idx[1] = bi; g.gx[1] = -wx; g.gy[1] = -wy;
+        g.gxi[0] = wx - ux; g.gxi[1] = wy - uy;
+    }
+}
+// the partials of one problem's four measures, by what they act on:
+//   height  d/dcom_z = 1, d/dq_c,z = -inv_n for c in S
+//   reach   u = (com - q_f) / r of the foot f the forward's `r > reach` chain keeps (the first foot wins a tie), zero when r == 0: d/dcom = u, d/dq_f = -u
+//   track   t = (com_xy - ref_xy) / track, zero when track == 0: d/dcom_xy = t, d/dref_xy = -t
+//   margin  gxi = d/dxi and (gvx, gvy)[4 c + j] = d/d(xy of vertex j of foot c), hit[] where there is one.  A vertex the forward filled from the other
+//           foot (single support) is entered at the foot and corner it was copied from, so a foot outside S has no hit.  xi = com_xy + dcom_xy tau,
+//           tau = sqrt(max(height, 0) / g); tau_on (height > 0 and tau > 0): dtau = dtau/dheight = 1 / (2 g tau), else the margin does not see the height
+// alive: the state is finite (measure 3 is a number); alive && support: measures 0..2 are.  A measure the forward reports as NaN has no partials.
+struct CmpcMeasurePartials {
+    bool alive, support, on[2], tau_on;
+    double inv_n;
+    int reach_foot; double u[3];
+    double t[2];
+    double gxi[2], tau, dtau, dcx, dcy;
+    bool hit[8]; double gvx[8], gvy[8];
+};
+__host__ __device__ inline void cmpc_walk_measures_partials(const CmpcMeasureArgs& a, int b, CmpcMeasurePartials& pt)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{a.N};
+    const float* so = a.state_out + 9 * (size_t)b;
+    const float* x = a.X + (size_t)b * L.nx();
+    const float* p = a.P + (size_t)b * L.np();
+    bool finite = true;
+    for (int i = 0; i < 9; ++i) finite = finite && __builtin_isfinite(so[i]);
+    pt.alive = finite; pt.support = false; pt.on[0] = pt.on[1] = false; pt.tau_on = false;
+    pt.inv_n = 0.0; pt.reach_foot = 0; pt.u[0] = pt.u[1] = pt.u[2] = 0.0; pt.t[0] = pt.t[1] = 0.0;
+    pt.gxi[0] = pt.gxi[1] = 0.0; pt.tau = pt.dtau = pt.dcx = pt.dcy = 0.0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) { pt.hit[s] = false; pt.gvx[s] = pt.gvy[s] = 0.0; }
+    if (!finite) return;
+    const double com[3] = {(double)so[0], (double)so[1], (double)so[2]};
+    const double tx = com[0] - (double)p[L.pComref() + 3], ty = com[1] - (double)p[L.pComref() + 4];
+    const double track = __builtin_sqrt(tx * tx + ty * ty);
+    const bool moved = track != 0.0;
+    pt.t[0] = moved ? tx / track : 0.0;
+    pt.t[1] = moved ? ty / track : 0.0;
+    const bool on0 = p[L.pGam(0) + 1] > 0.5f, on1 = p[L.pGam(1) + 1] > 0.5f;
+    if (!on0 && !on1) return;
+    pt.support = true; pt.on[0] = on0; pt.on[1] = on1;
+    double q[2][3], vx[8], vy[8];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c) + 9;   // column-major block of stage 1
+        const float* cn = a.corners + (size_t)b * a.corners_stride + 12 * c;
+        for (int i = 0; i < 3; ++i) q[c][i] = (double)x[L.oPos(c) + 3 + i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            vx[4 * c + j] = ((q[c][0] + (double)R[0] * (double)cn[3 * j]) + (double)R[3] * (double)cn[3 * j + 1]) + (double)R[6] * (double)cn[3 * j + 2];
+            vy[4 * c + j] = ((q[c][1] + (double)R[1] * (double)cn[3 * j]) + (double)R[4] * (double)cn[3 * j + 1]) + (double)R[7] * (double)cn[3 * j + 2];
+        }
+    }
+    double zsum = 0.0, reach = 0.0;
+    int n = 0;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const bool on = c == 0 ? on0 : on1;
+        const double dx = com[0] - q[c][0], dy = com[1] - q[c][1], dz = com[2] - q[c][2];
+        const double r = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+        if (on) {
+            zsum = zsum + q[c][2];
+            if (n == 0 || r > reach) {
+                reach = r;
+                pt.reach_foot = c;
+                const bool apart = r != 0.0;
+                pt.u[0] = apart ? dx / r : 0.0; pt.u[1] = apart ? dy / r : 0.0; pt.u[2] = apart ? dz / r : 0.0;
+            }
+            ++n;
+        }
+    }
+    pt.inv_n = 1.0 / (double)n;
+    const double height = com[2] - zsum / (double)n;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!on0) { vx[j] = vx[4 + j]; vy[j] = vy[4 + j]; }
+        if (!on1) { vx[4 + j] = vx[j]; vy[4 + j] = vy[j]; }
+    }
+    const double tau = __builtin_sqrt((height > 0.0 ? height : 0.0) / a.gravity);
+    const double xi_x = com[0] + (double)so[3] * tau, xi_y = com[1] + (double)so[4] * tau;
+    pt.tau = tau; pt.dcx = (double)so[3]; pt.dcy = (double)so[4];
+    pt.tau_on = height > 0.0 && tau > 0.0;
+    pt.dtau = pt.tau_on ? 1.0 / ((2.0 * a.gravity) * tau) : 0.0;
+    CmpcMarginGrad mg;
+    cmpc_support_margin_grad(vx, vy, xi_x, xi_y, mg);
+    pt.gxi[0] = mg.gxi[0]; pt.gxi[1] = mg.gxi[1];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int raw = mg.idx[t] >> 2;                                                  // (idx < 0: slot < 0, no hit)
+        const int foot = mg.idx[t] < 0 ? -1 : ((raw == 0 ? on0 : on1) ? raw : 1 - raw);   // the vertex fill: the foot it was copied from
+        const int slot = mg.idx[t] < 0 ? -1 : 4 * foot + (mg.idx[t] & 3);
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+            if (slot == s) { pt.gvx[s] = pt.gvx[s] + mg.gx[t]; pt.gvy[s] = pt.gvy[s] + mg.gy[t]; pt.hit[s] = true; }
+    }
+}
+// what one vertex's xy sends on, (ax, ay) = its gradient: foot position xy, corner (rows 0 and 1 of R), omega (v = q + R Exp(omega) cn: dv_x / domega =
+// cn x R_0, dv_y / domega = cn x R_1, R_0 / R_1 the first two ROWS of R)
+__host__ __device__ inline void cmpc_measures_vertex_rows(const float* R, const float* cn, double* r0, double* r1, double* x0, double* x1)
+{
+#pragma clang fp contract(off)
+    const double c0 = (double)cn[0], c1 = (double)cn[1], c2 = (double)cn[2];
+    r0[0] = (double)R[0]; r0[1] = (double)R[3]; r0[2] = (double)R[6];
+    r1[0] = (double)R[1]; r1[1] = (double)R[4]; r1[2] = (double)R[7];
+    x0[0] = c1 * r0[2] - c2 * r0[1]; x0[1] = c2 * r0[0] - c0 * r0[2]; x0[2] = c0 * r0[1] - c1 * r0[0];
+    x1[0] = c1 * r1[2] - c2 * r1[1]; x1[1] = c2 * r1[0] - c0 * r1[2]; x1[2] = c0 * r1[1] - c1 * r1[0];
+}
+// the VJP of one problem: w[4] the cotangent of (height, reach, margin, track) -> gs[5] (com xyz, dcom xy), gq[2][3] (the knot-1 foot positions),
+// direct[32] (comRef_xy 2, omega [2][3], corner [2][4][3]), all written whole.  The cotangent of a NaN measure is not read.
+__host__ __device__ inline void cmpc_walk_measures_vjp_problem(const CmpcMeasureArgs& a, int b, const double* w, double* gs, double* gq, double* direct)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{a.N};
+    CmpcMeasurePartials pt;
+    cmpc_walk_measures_partials(a, b, pt);
+    for (int i = 0; i < 5; ++i) gs[i] = 0.0;
+    for (int i = 0; i < 6; ++i) gq[i] = 0.0;
+    for (int i = 0; i < 32; ++i) direct[i] = 0.0;
+    if (!pt.alive) return;
+    {
+        const double w3 = w[3], g0 = w3 * pt.t[0], g1 = w3 * pt.t[1];
+        gs[0] = gs[0] + g0; gs[1] = gs[1] + g1;
+        direct[0] = -g0; direct[1] = -g1;
+    }
+    if (!pt.support) return;
+    const double w0 = w[0], w1 = w[1], w2 = w[2];
+    // height
+    gs[2] = gs[2] + w0;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        if (pt.on[c]) gq[3 * c + 2] = gq[3 * c + 2] - w0 * pt.inv_n;
+    // reach
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double r = w1 * pt.u[i];
+        gs[i] = gs[i] + r;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (pt.reach_foot == c) gq[3 * c + i] = gq[3 * c + i] - r;
+    }
+    // margin: xi, and through tau the height
+    const double gxx = w2 * pt.gxi[0], gxy = w2 * pt.gxi[1];
+    gs[0] = gs[0] + gxx; gs[1] = gs[1] + gxy;
+    gs[3] = gs[3] + gxx * pt.tau; gs[4] = gs[4] + gxy * pt.tau;
+    if (pt.tau_on) {
+        const double gh = (gxx * pt.dcx + gxy * pt.dcy) * pt.dtau;
+        gs[2] = gs[2] + gh;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (pt.on[c]) gq[3 * c + 2] = gq[3 * c + 2] - gh * pt.inv_n;
+    }
+    // margin: the vertices
+    const float* p = a.P + (size_t)b * L.np();
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c) + 9;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!pt.hit[4 * c + j]) continue;
+            const float* cn = a.corners + (size_t)b * a.corners_stride + 12 * c + 3 * j;
+            double r0[3], r1[3], x0[3], x1[3];
+            cmpc_measures_vertex_rows(R, cn, r0, r1, x0, x1);
+            const double ax = w2 * pt.gvx[4 * c + j], ay = w2 * pt.gvy[4 * c + j];
+            gq[3 * c] = gq[3 * c] + ax; gq[3 * c + 1] = gq[3 * c + 1] + ay;
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+                direct[2 + 3 * c + l] = direct[2 + 3 * c + l] + (ax * x0[l] + ay * x1[l]);
+                direct[8 + 12 * c + 3 * j + l] = ax * r0[l] + ay * r1[l];
+            }
+        }
+    }
+}
+// the JVP of one problem, the transpose: ds[5] (com xyz, dcom xy), dq[6], dref[2], dcn[24] (read with has_cn only), dom[6] (NULL: zero) -> dm[4], zero for a
+// measure the forward reports as NaN
+__host__ __device__ inline void cmpc_walk_measures_jvp_problem(const CmpcMeasureArgs& a, int b, const CmpcMeasurePartials& pt, const double* ds, const double* dq,
+                                                               const double* dref, const double* dcn, bool has_cn, const double* dom, double* dm)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{a.N};
+    dm[0] = dm[1] = dm[2] = dm[3] = 0.0;
+    if (!pt.alive) return;
+    dm[3] = pt.t[0] * (ds[0] - dref[0]) + pt.t[1] * (ds[1] - dref[1]);
+    if (!pt.support) return;
+    double dh = ds[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        if (pt.on[c]) dh = dh - dq[3 * c + 2] * pt.inv_n;
+    dm[0] = dh;
+    double dr = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double dqi = 0.0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (pt.reach_foot == c) dqi = dq[3 * c + i];
+        dr = dr + pt.u[i] * (ds[i] - dqi);
+    }
+    dm[1] = dr;
+    double dxx = ds[0] + ds[3] * pt.tau, dxy = ds[1] + ds[4] * pt.tau;
+    if (pt.tau_on) {
+        const double dt = pt.dtau * dh;
+        dxx = dxx + pt.dcx * dt; dxy = dxy + pt.dcy * dt;
+    }
+    double d2 = pt.gxi[0] * dxx + pt.gxi[1] * dxy;
+    const float* p = a.P + (size_t)b * L.np();
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float* R = p + L.pR(c) + 9;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!pt.hit[4 * c + j]) continue;
+            const float* cn = a.corners + (size_t)b * a.corners_stride + 12 * c + 3 * j;
+            double r0[3], r1[3], x0[3], x1[3];
+            cmpc_measures_vertex_rows(R, cn, r0, r1, x0, x1);
+            double dvx = dq[3 * c], dvy = dq[3 * c + 1];
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+                if (has_cn) { dvx = dvx + r0[l] * dcn[12 * c + 3 * j + l]; dvy = dvy + r1[l] * dcn[12 * c + 3 * j + l]; }
+                if (dom) { dvx = dvx + x0[l] * dom[3 * c + l]; dvy = dvy + x1[l] * dom[3 * c + l]; }
+            }
+            d2 = d2 + (pt.gvx[4 * c + j] * dvx + pt.gvy[4 * c + j] * dvy);
+        }
+    }
+    dm[2] = d2;
+}
+// one (row, problem) of the measures VJP (include/cmpc.h, cmpc_walk_measures_vjp): rows of the call start at the pointers; the row counts when
+// tick0 + r < e (cmpc_reference_rows_of).  A row that does not count: zero in direct, nothing else read or written.  A term that is exactly zero is not
+// added to a += entry (a select: the entry keeps its bits, a -0.0 included).
+struct CmpcMeasureVjpArgs {
+    int N, B, tick0, rows;
+    const float* X; const float* P; const float* states;       // [rows][B][n_x], [rows][B][n_p], [rows + 1][B][9]
+    const int* end_tick;
+    const float* corners; int corners_stride; double gravity;
+    const double* grad_measures;                                 // [rows][B][4]
+    double* grad_states; float* grad_X; double* direct;         // [rows + 1][B][9] +=, [rows][B][n_x] +=, [rows][B][32]
+};
+__host__ __device__ inline void cmpc_walk_measures_vjp_entry(const CmpcMeasureVjpArgs& v, int r, int b)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{v.N};
+    const size_t rb = (size_t)r * v.B + b;
+    double* direct = v.direct + 32 * rb;
+    if (r >= cmpc_reference_rows_of(v.end_tick, b, v.tick0, v.rows)) {
+        for (int i = 0; i < 32; ++i) direct[i] = 0.0;
+        return;
+    }
+    const CmpcMeasureArgs a{v.N, v.B, v.X + (size_t)r * v.B * L.nx(), v.P + (size_t)r * v.B * L.np(), v.states + (size_t)(r + 1) * v.B * 9, v.corners,
+                            v.corners_stride, v.gravity};
+    double gs[5], gq[6], d[32];
+    cmpc_walk_measures_vjp_problem(a, b, v.grad_measures + 4 * rb, gs, gq, d);
+    for (int i = 0; i < 32; ++i) direct[i] = d[i];
+    double* s = v.grad_states + ((size_t)(r + 1) * v.B + b) * 9;
+    for (int i = 0; i < 5; ++i)
+        if (gs[i] != 0.0) s[i] = s[i] + gs[i];
+    float* gx = v.grad_X + rb * L.nx();
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 3; ++i) {
+            const float t = (float)gq[3 * c + i];
+            if (t != 0.f) gx[L.oPos(c) + 3 + i] = gx[L.oPos(c) + 3 + i] + t;
+        }
+}
+// the fold behind the reverse walk (cmpc_walk_measures_vjp_fold): entry e < rows B adds direct's comRef pair of its (row, problem) to the knot-1 comRef
+// xy of grad_p (float, each term rounded once; a zero term is not added), entry e < 24 B sums its (problem, corner word) of direct over the rows in
+// ascending order into grad_model[b][10 + word].  Either output may be null.
+__host__ __device__ inline void cmpc_walk_measures_fold_entry(int N, int B, int rows, const double* direct, float* grad_p, double* grad_model, size_t e)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{N};
+    if (grad_p && e < (size_t)rows * B) {
+        float* g = grad_p + e * L.np() + L.pComref() + 3;
+        for (int i = 0; i < 2; ++i) {
+            const float t = (float)direct[32 * e + i];
+            if (t != 0.f) g[i] = g[i] + t;
+        }
+    }
+    if (grad_model && e < (size_t)24 * B) {
+        const size_t b = e / 24, wd = e - 24 * b;
+        double s = 0.0;
+        for (int r = 0; r < rows; ++r) s = s + direct[32 * ((size_t)r * B + b) + 8 + wd];
+        if (s != 0.0) grad_model[34 * b + 10 + wd] = grad_model[34 * b + 10 + wd] + s;
+    }
+}
+// one (row, problem) of the measures JVP (cmpc_walk_measures_jvp): K columns, the layouts of cmpc_walk_dirs.  A row that does not count: zeros.
+struct CmpcMeasureJvpArgs {
+    int N, B, tick0, rows, K;
+    const float* X; const float* P; const float* states;
+    const int* end_tick;
+    const float* corners; int corners_stride; double gravity;
+    const double* dir_states; const float* dir_X; const float* dir_P; const double* dir_model;   // [rows + 1][B][K][9], [rows][B][K][n_x], [rows][B][K][n_p] or null, [B][K][34] or null
+    double* dir_measures;                                                                      // [rows][B][K][4]
+};
+__host__ __device__ inline void cmpc_walk_measures_jvp_entry(const CmpcMeasureJvpArgs& v, int r, int b)
+{
+#pragma clang fp contract(off)
+    const CmpcIdx L{v.N};
+    const size_t rb = (size_t)r * v.B + b;
+    double* out = v.dir_measures + 4 * rb * v.K;
+    if (r >= cmpc_reference_rows_of(v.end_tick, b, v.tick0, v.rows)) {
+        for (int i = 0; i < 4 * v.K; ++i) out[i] = 0.0;
+        return;
+    }
+    const CmpcMeasureArgs a{v.N, v.B, v.X + (size_t)r * v.B * L.nx(), v.P + (size_t)r * v.B * L.np(), v.states + (size_t)(r + 1) * v.B * 9, v.corners,
+                            v.corners_stride, v.gravity};
+    CmpcMeasurePartials pt;
+    cmpc_walk_measures_partials(a, b, pt);
+    for (int k = 0; k < v.K; ++k) {
+        const double* s = v.dir_states + (((size_t)(r + 1) * v.B + b) * v.K + k) * 9;
+        const float* x = v.dir_X + (rb * v.K + k) * L.nx();
+        double ds[5], dq[6], dref[2] = {0.0, 0.0}, dcn[24], dm[4];
+        for (int i = 0; i < 5; ++i) ds[i] = s[i];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            for (int i = 0; i < 3; ++i) dq[3 * c + i] = (double)x[L.oPos(c) + 3 + i];
+        if (v.dir_P) {
+            const float* p = v.dir_P + (rb * v.K + k) * L.np() + L.pComref() + 3;
+            dref[0] = (double)p[0]; dref[1] = (double)p[1];
+        }
+#pragma unroll
+        for (int i = 0; i < 24; ++i) dcn[i] = v.dir_model ? v.dir_model[((size_t)b * v.K + k) * 34 + 10 + i] : 0.0;
+        cmpc_walk_measures_jvp_problem(a, b, pt, ds, dq, dref, dcn, v.dir_model != nullptr, nullptr, dm);
+        for (int i = 0; i < 4; ++i) out[4 * k + i] = dm[i];
+    }
+}
+
 // the cold start (cmpc_api.hip, cold_start): entry e of one problem's x from its p -- CoM at com0, feet at nominalPos, f_z = g8 per corner and
 // stage, zero elsewhere
 __host__ __device__ inline float cmpc_cold_start_entry(int N, int e, const float* p, float g8)

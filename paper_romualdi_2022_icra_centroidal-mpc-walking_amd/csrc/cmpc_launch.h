@@ -40,6 +40,9 @@ int cmpc_launch_tick_post(int B, int N, int M, double now, float grav, const flo
 int cmpc_launch_rollout_record(const CmpcRecordArgs* a, int* stats, hipStream_t stream);
 int cmpc_launch_rollout_record_limits(const CmpcRecordArgs* a, const CmpcLimitArgs* lm, int* stats, hipStream_t stream);
 int cmpc_launch_extremes_init(int B, float* ext, hipStream_t stream);
+int cmpc_launch_walk_measures_vjp(const CmpcMeasureVjpArgs* v, hipStream_t stream);
+int cmpc_launch_walk_measures_fold(int N, int B, int rows, const double* direct, float* grad_p, double* grad_model, hipStream_t stream);
+int cmpc_launch_walk_measures_jvp(const CmpcMeasureJvpArgs* v, hipStream_t stream);
 int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                              float* slack_min, hipStream_t stream);
 int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);

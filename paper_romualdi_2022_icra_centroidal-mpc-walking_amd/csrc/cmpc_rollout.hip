@@ -693,6 +693,29 @@ __global__ __launch_bounds__(256) void cmpc_extremes_init_kernel(int B, float* _
     e[0] = inf; e[1] = -inf; e[2] = -inf; e[3] = inf; e[4] = -inf;
 }
 
+// the measures differentiated (include/cmpc.h, cmpc_walk_measures_vjp_device and its two companions): one thread per (row, problem) -- per (row,
+// problem) or (problem, corner word) in the fold -- running the host forms' own functions (cmpc_contacts.h).  No LDS, no barrier, no atomics: a thread
+// owns every word it writes, and lanes past the work touch no memory.
+__global__ __launch_bounds__(256) void cmpc_walk_measures_vjp_kernel(CmpcMeasureVjpArgs v)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)v.rows * v.B) return;
+    cmpc_walk_measures_vjp_entry(v, (int)(e / v.B), (int)(e % v.B));
+}
+
+__global__ __launch_bounds__(256) void cmpc_walk_measures_fold_kernel(int N, int B, int rows, const double* __restrict__ direct, float* __restrict__ grad_p,
+                                                                      double* __restrict__ grad_model)
+{
+    cmpc_walk_measures_fold_entry(N, B, rows, direct, grad_p, grad_model, (size_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void cmpc_walk_measures_jvp_kernel(CmpcMeasureJvpArgs v)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)v.rows * v.B) return;
+    cmpc_walk_measures_jvp_entry(v, (int)(e / v.B), (int)(e % v.B));
+}
+
 __global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const float* __restrict__ state0, int* __restrict__ end_tick, int* __restrict__ end_code,
                                                                 int* __restrict__ it_sum, int* __restrict__ it_max, float* __restrict__ final_state,
                                                                 float* __restrict__ slack_min)
@@ -975,6 +998,28 @@ extern "C" int cmpc_launch_rollout_record_limits(const CmpcRecordArgs* a, const 
 extern "C" int cmpc_launch_extremes_init(int B, float* ext, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_extremes_init_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, ext);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_walk_measures_vjp(const CmpcMeasureVjpArgs* v, hipStream_t stream)
+{
+    const size_t n = (size_t)v->rows * v->B;
+    hipLaunchKernelGGL(cmpc_walk_measures_vjp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *v);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_walk_measures_fold(int N, int B, int rows, const double* direct, float* grad_p, double* grad_model, hipStream_t stream)
+{
+    const size_t np = grad_p ? (size_t)rows * B : 0, nm = grad_model ? (size_t)24 * B : 0, n = np > nm ? np : nm;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(cmpc_walk_measures_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, N, B, rows, direct, grad_p, grad_model);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_walk_measures_jvp(const CmpcMeasureJvpArgs* v, hipStream_t stream)
+{
+    const size_t n = (size_t)v->rows * v->B;
+    hipLaunchKernelGGL(cmpc_walk_measures_jvp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *v);
     return (int)hipGetLastError();
 }
 

@@ -841,7 +841,44 @@ class WalkingRollout:
         Times, robot_mass and com_height are not differentiated.  (A method of its own: the signatures of backward_device / _rot are pinned.)"""
         return self._backward_device(w, grad_states, grad_X, rot, refs=True)
 
-    def _backward_device(self, w, grad_states, grad_X, rot, refs=False):
+    def backward_device_measures(self, w, grad_measures, grad_states=None, grad_X=None, refs=False):
+        """backward_device() (refs=True: backward_device_refs()) of a loss that is also seeded on the walk's stability measures (include/cmpc.h, "the
+        measures, differentiated"): grad_measures[ticks, B, 4] float64 (CUDA or numpy) is the cotangent of height, reach, margin, track of every tick, as
+        w["measures"] holds them; grad_states / grad_X as in backward_device (None: zero).  Queued on the launch stream with no host read: ONE launch of
+        cmpc_walk_measures_vjp_device adds the measures' share to copies of the two seeds, the reverse walk runs on them as it is, and one small launch
+        (cmpc_walk_measures_vjp_fold_device) adds the comRef term to grad_P -- in front of the reference VJP, which carries it into ref_com -- and the
+        corners' term to models[:, 10:34].  -> the other method's keys, plus measure_direct[ticks, B, 32] float64 (comRef_xy 2, omega [2][3], corner
+        [2][4][3] per tick: what no seed carries) and measure_rot[ticks, B, 2, 3], its omega part as a view: the stage-1 rotations' body-frame tangent,
+        returned and NOT chained into the lists' or the planner's orientations.  A problem that ended at tick e contributes the measures of its ticks
+        0 .. e - 1: the row that fired and the rows behind it are not read, whatever they hold.  With grad_measures all zero every shared key is
+        bit-equal to the other method's.  The corners are those the walk's record read (the solver's, or the installed models'); a mismatch tape works
+        as it is.  Not for checkpointed walks or a regrouped refill tape."""
+        torch, B, L, s = self.torch, self.B, self.L, self.solver
+        tape = w["tape"]
+        T = tape["rows"]
+        as_t = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, dt).contiguous()
+        gM = as_t(grad_measures, torch.float64)
+        assert tuple(gM.shape) == (T, B, 4), f"grad_measures of shape {tuple(gM.shape)}: expected {(T, B, 4)}"
+        gS0 = None if grad_states is None else as_t(grad_states, torch.float64)
+        gX0 = None if grad_X is None else as_t(grad_X, torch.float32)
+        assert gS0 is None or tuple(gS0.shape) == (T + 1, B, 9)
+        assert gX0 is None or tuple(gX0.shape) == (T, B, L.nx)
+        ls = s.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            gS = torch.zeros((T + 1, B, 9), dtype=torch.float64, device=self.dev) if gS0 is None else gS0.clone()
+            gX = torch.zeros((T, B, L.nx), dtype=torch.float32, device=self.dev) if gX0 is None else gX0.clone()
+            direct = torch.zeros((T, B, 32), dtype=torch.float64, device=self.dev)
+            s.walk_measures_vjp_device(0, T, tape, 0, w["end_tick"], gM, gS, gX, direct)
+        cur.wait_stream(ls)
+        fold = lambda out: s.walk_measures_vjp_fold_device(direct, out.get("grad_P"), out["models"])
+        out = self._backward_device(w, gS, gX, False, refs=refs, fold=fold)
+        out["measure_direct"] = direct
+        out["measure_rot"] = direct[:, :, 2:8].unflatten(2, (2, 3))
+        return out
+
+    def _backward_device(self, w, grad_states, grad_X, rot, refs=False, fold=None):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
         tape = w["tape"]
         T, M, s = tape["rows"], tape["max_contacts"], self.solver
@@ -881,6 +918,8 @@ class WalkingRollout:
             out["state0"], out["list0"] = g, gl
             if rot:
                 out["list_rot0"] = glr
+            if fold is not None:    # (backward_device_measures: what the measures send to grad_P and models directly, in front of the reference VJP)
+                fold(out)
             if refs:    # (the replan segments share the trajectories: one launch over all rows)
                 s.reference_from_planner_vjp_device(0, T, tape["references"], w["end_tick"], out["grad_P"], out["ref_com"], out["ref_h"])
         cur.wait_stream(ls)
@@ -1381,6 +1420,29 @@ class WalkingRollout:
         return self._forward_sensitivity_device(w, dir_ref_com, dir_ref_h, *args.args[1:], **args.kwargs,
                                                 mismatch_dirs=(dir_hidden_wrench, dir_state_noise, dir_force_gain))
 
+    def forward_sensitivity_device_measures(self, w, **dirs):
+        """forward_sensitivity_device(w, solutions=True, **dirs) followed by ONE launch of cmpc_walk_measures_jvp_device on what it returned: the dict
+        gains measures[ticks, B, k, 4] float64, the directions of height, reach, margin, track of every tick -- through the states, the knot-1 foot
+        positions of the solutions' directions and, with dir_models, the corners.  The transpose of backward_device_measures(), input for output; no
+        host read.  Rows at or past a problem's end are zero.  The stage-1 rotations carry no direction (their term is not chained in reverse
+        either).  (A method of its own: forward_sensitivity_device's signature is pinned.)"""
+        torch, B, s = self.torch, self.B, self.solver
+        dirs = dict(dirs, solutions=True)
+        r = self.forward_sensitivity_device(w, **dirs)
+        tape = w["tape"]
+        T, k = tape["rows"], int(r["states"].shape[2])
+        dmod = dirs.get("dir_models")
+        if dmod is not None:
+            dmod = (dmod if isinstance(dmod, torch.Tensor) else torch.from_numpy(np.asarray(dmod))).to(self.dev, torch.float64).contiguous()
+        ls = s.launch_stream
+        cur = torch.cuda.current_stream(self.dev)
+        ls.wait_stream(cur)
+        with torch.cuda.stream(ls):
+            r["measures"] = torch.zeros((T, B, k, 4), dtype=torch.float64, device=self.dev)
+            s.walk_measures_jvp_device(0, T, tape, 0, w["end_tick"], k, r["states"], r["X"], r["measures"], dir_model=dmod)
+        cur.wait_stream(ls)
+        return r
+
     def _forward_sensitivity_device(self, w, dir_ref_com, dir_ref_h, dir_state0, dir_list0, dir_list_rot0, dir_plan, dir_plan_rot, dir_push, dir_models,
                                     dir_wrench, solutions, mismatch_dirs=None):
         torch, B, N, L = self.torch, self.B, self.cfg.N, self.L
@@ -1769,6 +1831,96 @@ def _rollout_differentiable_device(rollout, ticks, state0, push, models, push_ti
             return torch.where(ctx.past[..., None], at_end, t).to(torch.float32)
 
     return _Fn.apply(state0, push, models, plan_rot, ref_com, ref_h, hidden, noise, gain)
+
+
+def rollout_differentiable_measures(rollout: WalkingRollout, ticks, state0, push=None, models=None, push_ticks=0, replan=None, ref_com=None, ref_h=None,
+                                    hidden_wrench=None, state_noise=None, force_gain=None):
+    """rollout_differentiable(device_walk=True) that also returns the walk's stability measures, differentiably: -> (states [ticks + 1, B, 9],
+    measures [ticks, B, 4]) float32 -- height, reach, margin, track of every tick (include/cmpc.h, "physical limits") as the walk's trace holds them: the
+    row that ended a problem is included, its later rows are NaN, and so are the rows a code 1..5 ended.  The device walk only.  The measures trace is
+    turned on for this walk under the roll-out's current limits -- none set: every limit off, nobody ends by one; limits set (set_limits): a robot beyond
+    one ENDS, as with "limits" in stop= -- and the setting is restored afterwards.  backward is WalkingRollout.backward_device_measures with the
+    states' fold of rollout_differentiable (refs with ref_com / ref_h): the cotangents of the measure rows at or past a problem's end are not read,
+    so a loss may mask them or not.  Forward mode (torch.autograd.forward_ad over state0, push and models) is
+    WalkingRollout.forward_sensitivity_device_measures at k = 1: the tangents of the measure rows at or past a problem's end are zero; under a plant
+    mismatch, or with tangents on ref_com / ref_h, it raises NotImplementedError.  The other arguments, rollout.last_walk / last_backward /
+    last_forward as in rollout_differentiable.  No plan_rot and no plan_yaw: the measures' own dependence on the stage-1 rotations is returned by
+    backward_device_measures (measure_rot) and not chained into the planner's orientations."""
+    import torch
+    mismatch = (hidden_wrench, state_noise, force_gain) if any(a is not None for a in (hidden_wrench, state_noise, force_gain)) else None
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, state0, push, models, ref_com, ref_h, hidden, noise, gain):
+            mm = None
+            if mismatch is not None:
+                det = lambda a: None if a is None else a.detach().to(rollout.dev, torch.float32).contiguous()
+                mm = dict(hidden_wrench=det(hidden), state_noise=det(noise), force_gain=det(gain), tick_first=0)
+            ctx.mm_meta = tuple(None if a is None else (a.dtype, int(a.shape[0])) for a in (hidden, noise, gain))
+            assert all(a is None or 1 <= a.shape[0] <= ticks for a in (hidden, noise)), "hidden_wrench / state_noise: between 1 and `ticks` rows"
+            if models is not None:
+                rollout.models = models.detach().to(rollout.dev, torch.float64).contiguous()
+                rollout.models_ok = rollout.solver.set_models_device(rollout.models)
+            s0 = state0.detach().to(rollout.dev, torch.float32)
+            ctx.refs = ref_com is not None or ref_h is not None
+            ctx.ref_dtypes = (None if ref_com is None else ref_com.dtype, None if ref_h is None else ref_h.dtype)
+            as32 = lambda a: None if a is None else a.detach().to(rollout.dev, torch.float32).contiguous()
+            if ctx.refs:
+                rollout._ref_override = (as32(ref_com), as32(ref_h))
+            limits = rollout.limits
+            stop = ("merge", "solver", "nonfinite") + (("limits",) if limits is not None else ())
+            if limits is None:
+                rollout.set_limits()
+            try:
+                w = rollout.walk_device_taped(ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9],
+                                              push=None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks=push_ticks,
+                                              replan=replan, trace=True, stop=stop, mismatch=mm)
+            finally:
+                rollout.limits = limits
+                rollout._ref_override = None
+            rollout.last_walk = ctx.walk = w
+            ctx.dtypes = (state0.dtype, None if push is None else push.dtype)
+            e = w["end_tick"]
+            row = torch.arange(ticks + 1, device=rollout.dev)[:, None]
+            ctx.past = (e[None, :] >= 0) & (row > e[None, :])         # [ticks + 1, B]: rows behind a problem's end
+            ctx.last = row == e[None, :]                                # the row its final state sits in
+            return torch.where(ctx.past[..., None], w["final_state"][None], w["tape"]["states"]), w["measures"].clone()
+
+        @staticmethod
+        def backward(ctx, gStates, gMeasures):
+            g = gStates.to(rollout.dev, torch.float64)
+            folded = torch.where(ctx.past[..., None], g, torch.zeros_like(g)).sum(0)     # (zero for a problem that walked to the end)
+            g = torch.where(ctx.last[..., None], g + folded[None], g).contiguous()
+            r = rollout.backward_device_measures(ctx.walk, gMeasures.to(rollout.dev, torch.float64).contiguous(), g, refs=ctx.refs)
+            rollout.last_backward = r
+            return (r["state0"].to(ctx.dtypes[0]), None if ctx.dtypes[1] is None else r["push"].to(ctx.dtypes[1]),
+                    r["models"] if ctx.needs_input_grad[2] else None,
+                    r["ref_com"].to(ctx.ref_dtypes[0]) if ctx.ref_dtypes[0] is not None and ctx.needs_input_grad[3] else None,
+                    r["ref_h"].to(ctx.ref_dtypes[1]) if ctx.ref_dtypes[1] is not None and ctx.needs_input_grad[4] else None,
+                    r["hidden_wrench"][:ctx.mm_meta[0][1]].to(ctx.mm_meta[0][0]) if ctx.mm_meta[0] is not None and ctx.needs_input_grad[5] else None,
+                    r["state_noise"][:ctx.mm_meta[1][1]].to(ctx.mm_meta[1][0]) if ctx.mm_meta[1] is not None and ctx.needs_input_grad[6] else None,
+                    r["force_gain"].to(ctx.mm_meta[2][0]) if ctx.mm_meta[2] is not None and ctx.needs_input_grad[7] else None)
+
+        @staticmethod
+        def jvp(ctx, t_state0, t_push, t_models, t_ref_com, t_ref_h, t_hidden=None, t_noise=None, t_gain=None):
+            if mismatch is not None:
+                raise NotImplementedError("rollout_differentiable_measures: forward mode under a plant mismatch is not implemented")
+            if t_ref_com is not None or t_ref_h is not None:
+                raise NotImplementedError("rollout_differentiable_measures: forward mode takes no tangent on ref_com / ref_h")
+            zero = (torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev),
+                    torch.zeros((ticks, rollout.B, 4), dtype=torch.float32, device=rollout.dev))
+            if all(t is None for t in (t_state0, t_push, t_models)):
+                return zero
+            col = lambda t, dt: None if t is None else t.detach().to(rollout.dev, dt)[:, None].contiguous()
+            r = rollout.forward_sensitivity_device_measures(ctx.walk, dir_state0=col(t_state0, torch.float64), dir_push=col(t_push, torch.float32),
+                                                            dir_models=col(t_models, torch.float64))
+            rollout.last_forward = r
+            t = r["states"][:, :, 0]
+            e = ctx.walk["end_tick"].to(torch.int64).clamp(min=0)
+            at_end = t.gather(0, e[None, :, None].expand(1, rollout.B, 9))      # [1, B, 9]: each problem's row e (row 0 where it never ended: not selected)
+            return torch.where(ctx.past[..., None], at_end, t).to(torch.float32), r["measures"][:, :, 0].to(torch.float32)
+
+    return _Fn.apply(state0, push, models, ref_com, ref_h, hidden_wrench, state_noise, force_gain)
 
 
 def rollout_differentiable_checkpointed(rollout: WalkingRollout, ticks, state0, every, push=None, models=None, push_ticks=0, replan=None):

@@ -1332,6 +1332,45 @@ class BatchSolver:
         dev = torch.device("cuda", self._device_index) if device is None else device
         self._launch(dev, lambda st: self._lib.cmpc_rollout_walk_jvp_gate_device(self._h, C.byref(gate), st))
 
+    def walk_measures_vjp_device(self, tick0, ticks, tape, row0, end_tick, grad_measures, grad_states, grad_X, direct):
+        """cmpc_walk_measures_vjp_device: the cotangents grad_measures[rows, B, 4] float64 of the stability measures of rows row0 .. row0 + ticks - 1 of
+        tape (walk_tape) in ONE launch -> grad_states[rows + 1, B, 9] float64 and grad_X[rows, B, n_x] float32 ADDED TO (the reverse walk's seeds), and
+        direct[rows, B, 32] float64 written (comRef_xy 2, omega [2][3], corner [2][4][3]).  The corners are the handle's or the installed models'.
+        end_tick: int32 [B] (a walk record's) or None -- rows at or past a problem's end select zero and are not read."""
+        import torch
+        L, B, R = self.layout, self.batch, int(tape["rows"])
+        f32, f64 = torch.float32, torch.float64
+        g = _capi.CmpcWalkMeasureGrads(self._opt(grad_measures, f64, (R, B, _capi.WALK_MEASURES), "grad_measures"),
+                                       self._opt(grad_states, f64, (R + 1, B, 9), "grad_states"), self._opt(grad_X, f32, (R, B, L.nx), "grad_X"),
+                                       self._opt(direct, f64, (R, B, _capi.WALK_MEASURE_DIRECT), "direct"))
+        e = self._opt(end_tick, torch.int32, (B,), "end_tick")
+        self._launch(grad_measures.device,
+                     lambda st: self._lib.cmpc_walk_measures_vjp_device(self._h, int(tick0), int(ticks), tape["_c"], int(row0), e, C.byref(g), st))
+
+    def walk_measures_vjp_fold_device(self, direct, grad_p=None, grad_model=None):
+        """cmpc_walk_measures_vjp_fold_device: behind the reverse walk, direct[rows, B, 32]'s comRef pair ADDED TO grad_p[rows, B, n_p] float32 (the
+        reverse walk's grad_p) and its corner words summed over the rows into grad_model[B, 34] float64 (entries 10..33); either may be None."""
+        import torch
+        L, B, R = self.layout, self.batch, int(direct.shape[0])
+        d = self._opt(direct, torch.float64, (R, B, _capi.WALK_MEASURE_DIRECT), "direct")
+        gp = self._opt(grad_p, torch.float32, (R, B, L.np), "grad_p")
+        gm = self._opt(grad_model, torch.float64, (B, _capi.MODEL_DOUBLES), "grad_model")
+        self._launch(direct.device, lambda st: self._lib.cmpc_walk_measures_vjp_fold_device(self._h, R, d, gp, gm, st))
+
+    def walk_measures_jvp_device(self, tick0, ticks, tape, row0, end_tick, k, dir_states, dir_x, dir_measures, dir_p=None, dir_model=None):
+        """cmpc_walk_measures_jvp_device: the transpose of walk_measures_vjp_device in k columns, in rollout_walk_jvp_device's layouts: dir_states
+        [rows + 1, B, k, 9] float64, dir_x[rows, B, k, n_x] float32, dir_p[rows, B, k, n_p] float32 or None (its knot-1 comRef xy only), dir_model
+        [B, k, 34] float64 or None (its corners only) -> dir_measures[rows, B, k, 4] float64, written; rows at or past a problem's end are zero."""
+        import torch
+        L, B, R, k = self.layout, self.batch, int(tape["rows"]), int(k)
+        f32, f64 = torch.float32, torch.float64
+        d = _capi.CmpcWalkMeasureDirs(self._opt(dir_states, f64, (R + 1, B, k, 9), "dir_states"), self._opt(dir_x, f32, (R, B, k, L.nx), "dir_x"),
+                                      self._opt(dir_p, f32, (R, B, k, L.np), "dir_p"), self._opt(dir_model, f64, (B, k, _capi.MODEL_DOUBLES), "dir_model"),
+                                      self._opt(dir_measures, f64, (R, B, k, _capi.WALK_MEASURES), "dir_measures"))
+        e = self._opt(end_tick, torch.int32, (B,), "end_tick")
+        self._launch(dir_states.device,
+                     lambda st: self._lib.cmpc_walk_measures_jvp_device(self._h, int(tick0), int(ticks), tape["_c"], int(row0), e, k, C.byref(d), st))
+
     @staticmethod
     def planner_refs(knots, dt, t_first=0.0, robot_mass=1.0, com_height=0.7):
         """a _capi.CmpcPlannerRefs (cmpc_planner_refs, include/cmpc.h); com_height None: NaN, the trajectory's own z row"""
