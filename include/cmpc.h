@@ -878,7 +878,8 @@ int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, c
  * now in: cmpc_rollout_walk_refill_taped_device tapes a refill walk slot-major and cmpc_rollout_tape_regroup_device gathers every trial's rows into a tape
  * of its own, on which the reverse and the forward walks run as they are -- behind the snapshot section; orientation and reference gradients, checkpoints
  * and trials from a snapshot stay out.)  Per-trial models and a per-trial plant mismatch are cmpc_rollout_walk_refill_trials_device's (below), of which this is the call with trials == NULL; trials that
- * start from a snapshot of a walk in progress instead of standing are cmpc_rollout_walk_refill_snapshot_device's (behind the snapshot section). */
+ * start from a snapshot of a walk in progress instead of standing are cmpc_rollout_walk_refill_snapshot_device's (behind the snapshot section); a
+ * footstep plan and reference trajectories per TRIAL instead of the slot's are cmpc_rollout_walk_refill_plans_device's (behind the regroup). */
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream);
 /* Per-trial data of a refill walk; every array is a device array indexed by TRIAL q (0 <= q < refill->trials), schedules by the trial's LOCAL tick r.
@@ -1246,6 +1247,68 @@ int cmpc_rollout_tape_regroup_device(cmpc_handle h, int max_contacts, const cmpc
 /* the same on the host: host buffers throughout (refill's and g's arrays too); no handle, no GPU.  Bit-equal to the kernel. */
 int cmpc_rollout_tape_regroup(int horizon, int batch, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
                               const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst);
+/* ---- the refill walk with a footstep plan and reference trajectories per TRIAL (DESIGN.md 7f "Refill, plans per trial") ----
+ * Which slot a trial lands in depends on who ended before it, so the planner's lists of a SLOT are nothing a study can choose.  Here every trial names a
+ * row of a POOL of plans, and the row is copied into the slot's rows when the trial is spawned.  Device arrays all.  sizeof == 104 (LP64; the ctypes
+ * mirror is held to it).
+ *   pool:  dPoolT[Pn][2][M][2] double, dPoolPose[Pn][2][M][7] float, dPoolN[Pn][2] int in the layout of the planner's lists (M = max_contacts), Pn =
+ *     pool_plans >= 1; optional dPoolCom / dPoolH[Pn][plan_knots][3] float, both or neither: the planner's trajectories of each plan, with io->tick's
+ *     plan_knots, plan_dt, robot_mass, com_height and io->plan_t_first (they need io->tick.dPlanCom / dPlanH).
+ *   index: dTrialPlan[Q] the pool row of each trial (repeats are the normal case); dTrialPlanOk[Q] or NULL: 1 / 0 written when the trial is spawned,
+ *     untouched for a trial never started.
+ *   views: dPlanT, dPlanPose, dPlanN (and dPlanCom, dPlanH with pool trajectories; not read without) are the slots' rows the walk reads through
+ *     io->tick's const pointers -- the SAME addresses: the struct only lifts the const. */
+typedef struct cmpc_walk_refill_plans {
+    int pool_plans;
+    const double* dPoolT; const float* dPoolPose; const int* dPoolN;
+    const float* dPoolCom; const float* dPoolH;
+    const int* dTrialPlan; int* dTrialPlanOk;
+    double* dPlanT; float* dPlanPose; int* dPlanN; float* dPlanCom; float* dPlanH;
+} cmpc_walk_refill_plans;
+/* cmpc_rollout_walk_refill_taped_device with `plans`.  plans == NULL: that call, bit for bit; with tape == NULL as well,
+ * cmpc_rollout_walk_refill_trials_device.  Otherwise a tick gains ONE launch, the plan select (cmpc_refill_plans_kernel), directly behind the refill
+ * launch: six launches a tick, eight when taped.  One workgroup per slot; the gate is workgroup-uniform and comes ahead of everything: a slot that was not
+ * spawned this tick (dStartTick[b] != tick, or no trial in it) costs its workgroup that load.  A spawned slot with trial q receives the bit copy of pool row
+ * dTrialPlan[q]: its rows of the three list arrays (8 M, 14 M and 2 words) and, with pool trajectories, its 3 plan_knots words of each, through
+ * cmpc_rollout_snapshot_device's row copy (rows of 64 words and more in 16-byte pieces aligned on the destination); dTrialPlanOk[q] = 1.  No LDS, no
+ * barrier, no atomics.  The front kernel of the same tick then reads the slot's rows as it always has, and so does every later tick of the trial and the
+ * tape's copy kernel: no existing kernel changes.
+ *   - An index outside [0, pool_plans): nothing is copied, dTrialPlanOk[q] = 0, rec->dEndTick[b] = 0 and dEndCode[b] = 0 -- the slot is behind the ended
+ *     mask for this tick's other launches, is archived and freed by the next refill, and takes the next trial at the next tick (the rule of a snapshot
+ *     index outside its pool).
+ *   - A pool row is copied as it is: what the front kernel makes of a count outside 0 .. M, or of a snap that fails, is what it makes of it in a walk of
+ *     its own.
+ *   - AFTER THE CALL THE SLOTS' ROWS HOLD EACH SLOT'S LAST TRIAL'S PLAN.
+ * A trial's outcome, trace rows, dX, dP, dInfo, state and the entries in use of its lists are those of cmpc_rollout_walk_mismatch_device(cold_first = 1,
+ * tick_first = 0) on a handle of the same batch size, factor storage and options that holds it in the same slot, when that slot's planner lists (and
+ * trajectory rows) are the trial's pool row, cmpc_set_models_device's row `slot` the trial's model and the schedules' column `slot` the trial's rows.
+ * On the tape every tick's planner times and counts are the trial's own, so the regroup and the reverse / forward walks run unchanged, and a trial's
+ * dGradPlan is the gradient with respect to ITS plan row (not to "the slot's lists"); cmpc_rollout_plan_fold_device sums it over the trials of a row.
+ * CMPC_ERR_ARG before anything is queued: everything cmpc_rollout_walk_refill_taped_device refuses, in its order; and with plans != NULL, ahead of the
+ * handle check: pool_plans < 1; a NULL pool list array; dTrialPlan NULL with refill->trials > 0; one of dPoolCom / dPoolH without the other, or pool
+ * trajectories without io->tick.dPlanCom / dPlanH; a writable view that is not io's pointer; a pool array that is also a live array (a view, or a list
+ * buffer of either set).  Plans together with a snapshot pool are refused: no entry point takes both.
+ * Out of scope: per-trial plans for trials from a snapshot (a replan of a walk in progress); a replan inside a refill walk; orientation and
+ * reference-trajectory gradients of a refill walk; per-trial extremes and per-trial limits; an autograd wrapper; lists longer than 16 contacts. */
+int cmpc_rollout_walk_refill_plans_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_plans* plans,
+                                          int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream);
+/* The plan select launch of tick `tick` on the host: host buffers throughout; no handle, no GPU.  Bit-equal to the kernel.  Of refill only trials,
+ * dStartTick and dTrial are read, of rec only dEndTick and dEndCode; there is no io, so the views are taken as given (non-NULL) and plan_knots -- read
+ * with pool trajectories only -- is an argument.  CMPC_ERR_ARG: the refusals above that need no io, a NULL argument or required array, batch or
+ * max_contacts < 1, tick < 0, trials < 0, pool trajectories with plan_knots < 1. */
+int cmpc_rollout_refill_plans(int batch, int max_contacts, int tick, const cmpc_walk_refill* refill, const cmpc_walk_refill_plans* plans,
+                              const cmpc_walk_record* rec, int plan_knots);
+/* The pool's gradient: dOut[p][w] = the sum of dPerTrial[q][w] over the trials with dIndex[q] == p, from +0.0 and in ASCENDING q; dOut[pool_rows][words]
+ * double is written whole, zero where no trial has the row.  A member is selected, never multiplied in: NaN in a trial that is not a member cannot reach
+ * the row, and an index outside [0, pool_rows) contributes nowhere.  One thread per entry of dOut walks the queue; no atomics -- the order is fixed, so the
+ * bits do not depend on scheduling (an index_add_ on the device is an atomic sum).  For a plan pool: words = 6 M, dPerTrial = a trial's dGradPlan + its
+ * first-tick list gradient, dIndex = dTrialPlan.
+ * CMPC_ERR_ARG: trials < 0, words < 1, pool_rows < 1, more than 2^31 - 1 entries, a NULL dOut, a NULL dIndex or dPerTrial with trials > 0, dOut ==
+ * dPerTrial; then a NULL handle. */
+int cmpc_rollout_plan_fold_device(cmpc_handle h, int trials, int words, const int* dIndex, const double* dPerTrial, int pool_rows, double* dOut, void* stream);
+/* the same on the host: host buffers; no handle, no GPU.  Bit-equal to the kernel (one function forms an entry in both). */
+int cmpc_rollout_plan_fold(int trials, int words, const int* index, const double* per_trial, int pool_rows, double* out);
 /* The reverse walk: `ticks` calls of cmpc_rollout_tick_vjp_device (called, not copied: its workspace, statuses and zero rule for flagged problems hold),
  * last row first, on one stream, with one gate launch between the ticks (ticks + 1 launches of cmpc_walk_vjp_gate_kernel).  Tick number tick0 + i is row
  * row0 + i of the tape and of every [rows] array below, now = (tick0 + i) * sampling_time.

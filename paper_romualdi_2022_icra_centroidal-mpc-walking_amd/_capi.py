@@ -87,6 +87,13 @@ class CmpcWalkRefillSnapshot(C.Structure):
     _fields_ = [("pool", C.c_void_p), ("pool_batch", C.c_int), ("dTrialSnapshot", C.c_void_p), ("dTrialSnapshotOk", C.c_void_p)]
 
 
+class CmpcWalkRefillPlans(C.Structure):
+    """mirror of cmpc_walk_refill_plans (include/cmpc.h): the pool of footstep plans (and planner trajectories) the trials of
+    cmpc_rollout_walk_refill_plans_device name a row of, and the writable views of the slots' rows; 104 bytes"""
+    _fields_ = [("pool_plans", C.c_int)] + [(k, C.c_void_p) for k in (
+        "dPoolT", "dPoolPose", "dPoolN", "dPoolCom", "dPoolH", "dTrialPlan", "dTrialPlanOk", "dPlanT", "dPlanPose", "dPlanN", "dPlanCom", "dPlanH")]
+
+
 class CmpcWalkTapeRegroup(C.Structure):
     """mirror of cmpc_walk_tape_regroup (include/cmpc.h): which trial each column of a regrouped tape takes, and the end ticks and flags that come back;
     32 bytes"""
@@ -268,6 +275,7 @@ EXPORTS = [
     "cmpc_rollout_refill_init", "cmpc_rollout_refill_init_device", "cmpc_rollout_refill", "cmpc_rollout_refill_device", "cmpc_rollout_walk_refill_device",
     "cmpc_rollout_walk_refill_trials_device", "cmpc_rollout_walk_refill_snapshot_device", "cmpc_rollout_refill_restore",
     "cmpc_rollout_walk_refill_taped_device", "cmpc_rollout_tape_regroup_device", "cmpc_rollout_tape_regroup",
+    "cmpc_rollout_walk_refill_plans_device", "cmpc_rollout_refill_plans", "cmpc_rollout_plan_fold_device", "cmpc_rollout_plan_fold",
     "cmpc_factor_storage", "cmpc_solution_vjp_cols_device",
     "cmpc_set_walk_limits", "cmpc_walk_extremes_init_device", "cmpc_rollout_record_limits",
     "cmpc_walk_measures_vjp_device", "cmpc_walk_measures_vjp_fold_device", "cmpc_walk_measures_jvp_device",
@@ -468,6 +476,13 @@ def lib():
                                                                     tp, i, vp]
                 L.cmpc_rollout_tape_regroup_device.argtypes = [vp, i, tp, fl, rg, tp, vp]
                 L.cmpc_rollout_tape_regroup.argtypes = [i, i, i, tp, fl, rg, tp]
+            if hasattr(L, "cmpc_rollout_walk_refill_plans_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+                pl = C.POINTER(CmpcWalkRefillPlans)
+                L.cmpc_rollout_walk_refill_plans_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkIO), wr, fl, C.POINTER(CmpcWalkRefillTrials), pl, i, i, ip,
+                                                                    C.POINTER(CmpcWalkTape), i, vp]
+                L.cmpc_rollout_refill_plans.argtypes = [i, i, i, fl, pl, wr, i]
+                L.cmpc_rollout_plan_fold_device.argtypes = [vp, i, i, vp, vp, i, vp, vp]
+                L.cmpc_rollout_plan_fold.argtypes = [i, i, vp, vp, i, vp]
         if hasattr(L, "cmpc_set_models"):
             L.cmpc_model_from_config.argtypes = [C.POINTER(CmpcConfig), C.POINTER(CmpcModel)]
             L.cmpc_model_from_config.restype = None

@@ -1889,6 +1889,7 @@ int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_rec
 }
 
 static int ensure_models(cmpc_handle h);
+static_assert(sizeof(cmpc_walk_refill_plans) == 104, "cmpc_walk_refill_plans: the size include/cmpc.h states");
 static_assert(sizeof(cmpc_walk_refill_trials) == 56, "cmpc_walk_refill_trials: the size include/cmpc.h states");
 static_assert(sizeof(cmpc_walk_refill_snapshot) == 32, "cmpc_walk_refill_snapshot: the size include/cmpc.h states");
 
@@ -1968,7 +1969,8 @@ int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int ti
 
 static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape = nullptr, int tape_row0 = 0);
+                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape = nullptr, int tape_row0 = 0,
+                            const cmpc_walk_refill_plans* plans = nullptr);
 
 int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                                     const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
@@ -2002,15 +2004,120 @@ int cmpc_rollout_walk_refill_taped_device(cmpc_handle h, int max_contacts, int t
     return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream, tape, tape_row0);
 }
 
+// ---- plans per trial (include/cmpc.h, cmpc_walk_refill_plans): the plan select step between the refill launch and the front kernel ----
+// what is refused of `plans` without a handle, in the header's order; null: nothing.  io (or null: the host form, which has the views only): the walk's
+// buffers the views must be and a pool array must not be
+static const char* plans_refusal(const cmpc_walk_refill_plans* p, int trials, const cmpc_walk_io* io, const cmpc_walk_refill_snapshot* from)
+{
+    if (from) return "plans together with a snapshot pool (per-trial plans for trials from a snapshot would be a replan of a walk in progress)";
+    if (p->pool_plans < 1) return "pool_plans must be at least 1";
+    if (!p->dPoolT || !p->dPoolPose || !p->dPoolN) return "a pool list array is NULL (dPoolT, dPoolPose, dPoolN)";
+    if (trials > 0 && !p->dTrialPlan) return "dTrialPlan is NULL";
+    if (!p->dPoolCom != !p->dPoolH) return "dPoolCom and dPoolH go together: both or neither";
+    const bool traj = p->dPoolCom != nullptr;
+    if (io && traj && (!io->tick.dPlanCom || !io->tick.dPlanH)) return "pool trajectories need io->tick.dPlanCom and dPlanH";
+    if (io) {
+        const cmpc_tick_io& k = io->tick;
+        if (p->dPlanT != k.dPlanT || p->dPlanPose != k.dPlanPose || p->dPlanN != k.dPlanN || (traj && (p->dPlanCom != k.dPlanCom || p->dPlanH != k.dPlanH)))
+            return "a writable view is not io's pointer (dPlanT, dPlanPose, dPlanN, and dPlanCom / dPlanH with pool trajectories)";
+    } else if (!p->dPlanT || !p->dPlanPose || !p->dPlanN || (traj && (!p->dPlanCom || !p->dPlanH))) {
+        return "a writable view is NULL";
+    }
+    const void* const pool[5] = {p->dPoolT, p->dPoolPose, p->dPoolN, p->dPoolCom, p->dPoolH};
+    const void* live[11] = {p->dPlanT, p->dPlanPose, p->dPlanN, traj ? p->dPlanCom : nullptr, traj ? p->dPlanH : nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (io) {
+        const void* const lists[6] = {io->tick.dListT, io->tick.dListPose, io->tick.dListN, io->dListTB, io->dListPoseB, io->dListNB};
+        for (int i = 0; i < 6; ++i) live[5 + i] = lists[i];
+    }
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 11; ++j)
+            if (pool[i] && pool[i] == live[j]) return "a pool array is also a live array";
+    return nullptr;
+}
+// the argument block of the select step of tick `tick`; knots: the planner trajectories' (read with pool trajectories only)
+static bool plans_args(int B, int M, int tick, int knots, const cmpc_walk_refill* r, const cmpc_walk_refill_plans* p, const cmpc_walk_record* rec,
+                       CmpcRefillPlansArgs& a)
+{
+    if (B < 1 || M < 1 || tick < 0 || !r || r->trials < 1 || !r->dStartTick || !r->dTrial || !rec || !rec->dEndTick || !rec->dEndCode) return false;
+    if (p->dPoolCom && knots < 1) return false;
+    a = CmpcRefillPlansArgs{};
+    a.B = B; a.Q = r->trials; a.tick = tick; a.pool_plans = p->pool_plans;
+    a.start = r->dStartTick; a.trial = r->dTrial; a.index = p->dTrialPlan; a.ok = p->dTrialPlanOk;
+    a.end_tick = rec->dEndTick; a.end_code = rec->dEndCode;
+    int n = 0;
+    auto add = [&](const void* sp, void* dp, int words) {
+        a.src[n] = static_cast<const unsigned*>(sp); a.dst[n] = static_cast<unsigned*>(dp); a.words[n] = words;
+        ++n;
+    };
+    add(p->dPoolT, p->dPlanT, 8 * M); add(p->dPoolPose, p->dPlanPose, 14 * M); add(p->dPoolN, p->dPlanN, 2);
+    if (p->dPoolCom) { add(p->dPoolCom, p->dPlanCom, 3 * knots); add(p->dPoolH, p->dPlanH, 3 * knots); }
+    a.count = n;
+    return true;
+}
+
+int cmpc_rollout_refill_plans(int batch, int max_contacts, int tick, const cmpc_walk_refill* refill, const cmpc_walk_refill_plans* plans,
+                              const cmpc_walk_record* rec, int plan_knots)
+{
+    if (!plans || !refill || !rec || refill->trials < 0) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: null argument or a negative count");
+    if (const char* why = plans_refusal(plans, refill->trials, nullptr, nullptr)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_refill_plans: ") + why);
+    if (batch < 1 || max_contacts < 1 || tick < 0 || !refill->dStartTick || !refill->dTrial || !rec->dEndTick || !rec->dEndCode ||
+        (plans->dPoolCom && plan_knots < 1))
+        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: bad argument");
+    if (refill->trials == 0) return CMPC_OK;   // (no slot ever holds a trial)
+    CmpcRefillPlansArgs a;
+    if (!plans_args(batch, max_contacts, tick, plan_knots, refill, plans, rec, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: bad argument");
+    cmpc_refill_plans_host(a);
+    return CMPC_OK;
+}
+
+// the taped call with a plan pool (include/cmpc.h); plans null: the taped call itself, and with tape null as well the trials call
+int cmpc_rollout_walk_refill_plans_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_plans* plans,
+                                          int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
+{
+    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream, tape, tape_row0, plans);
+}
+
+// ---- the fold of per-trial gradients onto the pool's rows (include/cmpc.h) ----
+static const char* fold_refusal(int trials, int words, const int* index, const double* per, int pool_rows, const double* out)
+{
+    if (trials < 0 || words < 1 || pool_rows < 1) return "trials < 0, words < 1 or pool_rows < 1";
+    if (!out || (trials > 0 && (!index || !per))) return "a NULL array";
+    if (out == per) return "dOut is also dPerTrial";
+    if ((long long)pool_rows * words > 0x7fffffffLL) return "more than 2^31 - 1 entries in dOut";
+    return nullptr;
+}
+
+int cmpc_rollout_plan_fold(int trials, int words, const int* index, const double* per_trial, int pool_rows, double* out)
+{
+    if (const char* why = fold_refusal(trials, words, index, per_trial, pool_rows, out)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_plan_fold: ") + why);
+    for (int p = 0; p < pool_rows; ++p)
+        for (int w = 0; w < words; ++w) out[(size_t)p * words + w] = cmpc_plan_fold_entry(trials, words, index, per_trial, p, w);
+    return CMPC_OK;
+}
+
+int cmpc_rollout_plan_fold_device(cmpc_handle h, int trials, int words, const int* dIndex, const double* dPerTrial, int pool_rows, double* dOut, void* stream)
+{
+    if (const char* why = fold_refusal(trials, words, dIndex, dPerTrial, pool_rows, dOut))
+        return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_plan_fold_device: ") + why);
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_plan_fold_device: null handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int lrc = cmpc_launch_plan_fold(trials, words, dIndex, dPerTrial, pool_rows, dOut, stream_of(h, stream));
+    return launch_status(h, "plan fold", lrc);
+}
+
 // from (cmpc_walk_refill_snapshot) null: the walk above.  Else the trials start from pool rows: a sixth launch per tick, the restore, behind the refill; the
 // front and back kernels and the record take the pool's tick as the offset of every slot's local tick, and no problem of any solve is on a first tick (the
 // solve is launched without the slots' start ticks: warm for all)
 // tape (cmpc_rollout_walk_refill_taped_device; never together with from) non-null: part 2 of the tape behind every tick's record -- the copy kernel and the
 // multiplier call, seven launches a tick -- tick tick0 + i into row tape_row0 + i, slot-major.  Part 1 is never queued: the state a spawned trial starts
 // from is dState0[q], which the regroup supplies.  dOk and the planner's times go on every tick: every tick is queued as a merge tick
+// plans (cmpc_rollout_walk_refill_plans_device; never together with from) non-null: one launch more per tick, the plan select, behind the refill -- a
+// spawned slot's rows of the planner's lists and trajectories become its trial's pool row before the front kernel reads them
 static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape, int tape_row0)
+                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape, int tape_row0, const cmpc_walk_refill_plans* plans)
 {
     // (the refusals that need no handle come first: they are the same with and without one)
     if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
@@ -2035,6 +2142,9 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
         if (tape->plant_step != k.plant_step || tape->plant_substeps != k.plant_substeps || (tape->force_sample_time != 0) != (k.force_sample_time != 0))
             return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape's scalars do not agree with the walk");
     }
+    if (plans)
+        if (const char* why = plans_refusal(plans, refill->trials, io, from))
+            return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_refill_plans_device: ") + why);
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
     if (h->limits_set && h->limits.dExtremes)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dExtremes of cmpc_set_walk_limits must be NULL on a refill walk (a slot's extremes "
@@ -2104,6 +2214,15 @@ static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int tick
             }
             const int rrc = cmpc_launch_refill_restore(&ra, st);
             if ((rc = launch_status(h, "refill restore", rrc)) != CMPC_OK) break;
+        }
+        if (plans && refill->trials > 0) {
+            CmpcRefillPlansArgs pa;
+            if (!plans_args(B, max_contacts, tick, k.plan_knots, refill, plans, rec, pa)) {
+                rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_plans_device: bad plan select");
+                break;
+            }
+            const int prc = cmpc_launch_refill_plans(&pa, st);
+            if ((rc = launch_status(h, "refill plan select", prc)) != CMPC_OK) break;
         }
         int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
                                               set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,

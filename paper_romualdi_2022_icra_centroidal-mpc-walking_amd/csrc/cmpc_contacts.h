@@ -1065,6 +1065,56 @@ inline void cmpc_refill_restore_host(const CmpcRefillRestoreArgs& a)
     }
 }
 
+// ---- the plan select launch of a refill walk with plans per trial (include/cmpc.h, cmpc_walk_refill_plans): a slot spawned this tick receives the pool row
+// of its trial into its rows of the planner's lists (and of the planner's trajectories).  Every array goes as rows of 32-bit words (a double is two); the
+// table's order: the lists' times, poses and counts, then the CoM and the angular-momentum trajectory when the pool has them (count 3 or 5).
+#define CMPC_PLAN_ARRAYS 5
+struct CmpcRefillPlansArgs {
+    int B, Q, tick, pool_plans, count;
+    const int* start; const int* trial;   // [B]: the slots' start ticks and trials
+    const int* index; int* ok;            // [Q] dTrialPlan; [Q] or null: dTrialPlanOk
+    int* end_tick; int* end_code;         // [B]: the record's outcome words (a bad index ends its slot at spawn)
+    const unsigned* src[CMPC_PLAN_ARRAYS]; unsigned* dst[CMPC_PLAN_ARRAYS]; int words[CMPC_PLAN_ARRAYS];   // words: per slot / per pool row
+};
+// the trial spawned in slot b this tick, or -1: none (one load for a slot that was not spawned)
+__host__ __device__ inline int cmpc_refill_plans_trial(const CmpcRefillPlansArgs& a, int b)
+{
+    if (a.start[b] != a.tick) return -1;
+    const int q = a.trial[b];
+    return q >= 0 && q < a.Q ? q : -1;
+}
+// the pool row of trial q, or -1 for an index outside the pool
+__host__ __device__ inline int cmpc_refill_plans_source(const CmpcRefillPlansArgs& a, int q)
+{
+    const int s = a.index[q];
+    return s >= 0 && s < a.pool_plans ? s : -1;
+}
+// the host form's loop (cmpc_rollout_refill_plans); here for the reason cmpc_refill_host is
+inline void cmpc_refill_plans_host(const CmpcRefillPlansArgs& a)
+{
+    for (int b = 0; b < a.B; ++b) {
+        const int q = cmpc_refill_plans_trial(a, b);
+        if (q < 0) continue;
+        const int s = cmpc_refill_plans_source(a, q);
+        if (a.ok) a.ok[q] = s >= 0 ? 1 : 0;
+        if (s < 0) { a.end_tick[b] = 0; a.end_code[b] = 0; continue; }
+        for (int i = 0; i < a.count; ++i) {
+            const size_t w = (size_t)a.words[i];
+            __builtin_memcpy(a.dst[i] + w * b, a.src[i] + w * s, sizeof(unsigned) * w);
+        }
+    }
+}
+
+// ---- the fold of per-trial gradients onto the rows of a pool (include/cmpc.h, cmpc_rollout_plan_fold_device): entry [p][w] is the sum, from +0.0 and in
+// ascending q, of per[q][w] over the trials with index[q] == p.  A member is selected, never multiplied in; one function for the kernel and the host form.
+__host__ __device__ inline double cmpc_plan_fold_entry(int Q, int words, const int* index, const double* per, int p, int w)
+{
+    double s = 0.0;
+    for (int q = 0; q < Q; ++q)
+        if (index[q] == p) s += per[(size_t)q * words + w];
+    return s;
+}
+
 // ---- the tape of a refill walk regrouped by trial (include/cmpc.h, cmpc_walk_tape_regroup; DESIGN.md 7f "Refill, taped"): destination column j of a tape of
 // trial_ticks rows receives the rows of trial index[j] out of the slot-major tape.  Bit copies; every array goes as rows of 32-bit words (a double is two).
 // The table's order: X, P, lam_g, info, ok, land, list_t, list_n, then plan_t and plan_n (CMPC_REGROUP_PLAN .. : written zero on destination row 0).

@@ -60,6 +60,8 @@ int cmpc_launch_tick_post_refill(int B, int N, int M, double dt, float grav, con
                                  const int* land, const double* t, float* pose, const int* n, const int* ended, const int* start, int tick,
                                  const int* trial, const CmpcRefillTrialArgs* tr, int offset, hipStream_t stream);
 int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream);
+int cmpc_launch_refill_plans(const CmpcRefillPlansArgs* a, hipStream_t stream);
+int cmpc_launch_plan_fold(int Q, int words, const int* index, const double* per, int pool_rows, double* out, hipStream_t stream);
 int cmpc_launch_rollout_tape(const CmpcTapeArgs* a, hipStream_t stream);
 int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream_t stream);
 int cmpc_launch_rollout_tape_regroup(const CmpcRegroupArgs* a, hipStream_t stream);

@@ -865,6 +865,39 @@ __global__ __launch_bounds__(256) void cmpc_refill_restore_kernel(CmpcRefillRest
     }
 }
 
+// plan select (cmpc_rollout_walk_refill_plans_device): one workgroup per slot, between the refill launch and the front kernel of a tick.  The gate is the
+// restore kernel's -- blockIdx and kernel arguments only, ahead of everything: a slot that was not spawned this tick costs its workgroup one scalar load.
+// A spawned slot receives its trial's pool row of the planner's lists (8 M, 14 M and 2 words) and, when the pool has them, of the two planner
+// trajectories (3 plan_knots words each) through the snapshot kernel's row copy (snap_row); an index outside the pool ends the slot at spawn, local tick 0.
+// The flag and the two outcome words are one thread's.  No LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_refill_plans_kernel(CmpcRefillPlansArgs a)
+{
+    const int b = blockIdx.x;   // (the grid is B workgroups)
+    const int q = cmpc_refill_plans_trial(a, b);
+    if (q < 0) return;          // (uniform)
+    const int s = cmpc_refill_plans_source(a, q);
+    if (a.ok && threadIdx.x == 0) a.ok[q] = s >= 0 ? 1 : 0;
+    if (s < 0) {                // (uniform)
+        if (threadIdx.x == 0) { a.end_tick[b] = 0; a.end_code[b] = 0; }
+        return;
+    }
+    for (int i = 0; i < a.count; ++i) {
+        const size_t w = (size_t)a.words[i];
+        snap_row(a.dst[i] + w * b, a.src[i] + w * s, a.words[i], threadIdx.x);
+    }
+}
+
+// plan fold (cmpc_rollout_plan_fold_device): one thread per entry [p][w] of the pool's gradient, which walks the queue in ascending q and adds the rows of
+// its members (cmpc_plan_fold_entry: a select per trial).  Neighbouring threads read neighbouring words of a trial's row; the index word is the same for a
+// whole row of the output.  The order is the loop's: no LDS, no barrier, no atomics.
+__global__ __launch_bounds__(256) void cmpc_plan_fold_kernel(int Q, int words, const int* __restrict__ index, const double* __restrict__ per, int pool_rows,
+                                                             double* __restrict__ out)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)pool_rows * words) return;
+    out[e] = cmpc_plan_fold_entry(Q, words, index, per, (int)(e / words), (int)(e % words));
+}
+
 // regroup (cmpc_rollout_tape_regroup_device): one workgroup per (destination row, destination column) of a tape of trial_ticks rows; the column's rule
 // (cmpc_regroup_column: the four trial words, read once per workgroup) is workgroup-uniform.  A started column's row r is the bit copy of source row
 // t0 + min(r, n - 1), column s, array by array through the snapshot kernel's row copy (snap_row: 16-byte pieces aligned on the destination for the rows of
@@ -948,6 +981,19 @@ extern "C" int cmpc_launch_rollout_snapshot(const CmpcSnapshotArgs* a, hipStream
 extern "C" int cmpc_launch_refill_restore(const CmpcRefillRestoreArgs* a, hipStream_t stream)
 {
     hipLaunchKernelGGL(cmpc_refill_restore_kernel, dim3(a->copy.B), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_refill_plans(const CmpcRefillPlansArgs* a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_refill_plans_kernel, dim3(a->B), dim3(256), 0, stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_plan_fold(int Q, int words, const int* index, const double* per, int pool_rows, double* out, hipStream_t stream)
+{
+    const size_t entries = (size_t)pool_rows * words;
+    hipLaunchKernelGGL(cmpc_plan_fold_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, stream, Q, words, index, per, pool_rows, out);
     return (int)hipGetLastError();
 }
 

@@ -233,7 +233,8 @@ class WalkingRollout:
         trials["ticks"][q] are not the trial's).
         Per-trial models and a per-trial plant mismatch (hidden pushes, noise, a force gain): walk_device_refill_trials(), a method of its own because this
         signature is pinned; here the models are the slot's and mismatch= is refused.  Trials that start from a snapshot of a walk in progress instead of
-        standing at tick 0 (warm from their first tick): walk_device_refill_from_snapshot().
+        standing at tick 0 (warm from their first tick): walk_device_refill_from_snapshot().  A footstep plan and reference trajectories per trial
+        instead of the slot's: walk_device_refill_plans().
         A tape behind every tick and every trial's gradient: walk_device_refill_taped() and backward_device_refill().
         Out of scope: gradients and forward mode through a refill walk of THIS method, and -- NotImplementedError, raised before anything touches a GPU -- replan,
         mismatch= (see above), taped=True, every (snapshots and checkpoints), and lists longer than 16 contacts."""
@@ -279,7 +280,7 @@ class WalkingRollout:
         than 16 contacts (NotImplementedError)."""
         return WalkingRollout._walk_refill_trials(self, "walk_device_refill_taped", True, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs)
 
-    def _walk_refill_trials(self, who, taped, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs):
+    def _walk_refill_trials(self, who, taped, ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs, plans=None):
         mismatch = dict(mismatch or {})
         if int(mismatch.pop("tick_first", 0)) != 0:
             raise ValueError(f"{who}: the schedules' rows are the trial's local ticks, so tick_first must be 0")
@@ -302,7 +303,7 @@ class WalkingRollout:
             given = any(data[k] is not None for k in ("models", "hidden_wrench", "state_noise", "force_gain"))
             try:
                 rec = self._walk_refill(ticks, trial_ticks, com0, dcom0, h0, args["push"], args["push_ticks"], args["wrench_trials"], args["trace"],
-                                        args["stop"], trials=data if given else None, tape=taped)
+                                        args["stop"], trials=data if given else None, tape=taped, plans=plans)
             finally:
                 if data["models"] is not None:    # (the table holds each slot's last trial's model: back to the roll-out's own, in stream order)
                     if self.models is not None:
@@ -314,6 +315,97 @@ class WalkingRollout:
             rec["trials"]["model_ok"] = ok if ok is not None else torch.full((Q,), -1, dtype=torch.int32, device=self.dev)
             return rec
         return self._queued(walk)
+
+    # ---- a footstep plan and reference trajectories per trial (include/cmpc.h, cmpc_walk_refill_plans; DESIGN.md 7f, "Refill, plans per trial") ----
+    @staticmethod
+    def _plan_speed(plan):
+        """the mean walking speed of a plan: the expression of __init__ (com_speed=None)"""
+        last = max(c.position[0] for lst in plan.values() for c in lst)
+        t_last = max(c.activation_time for lst in plan.values() for c in lst)
+        return last / t_last if t_last > 0 else 0.0
+
+    def plan_pool(self, plans):
+        """A pool of footstep plans packed for walk_device_refill_plans: plans = a list of plan dicts as walking_plan returns them, or packed arrays
+        (t [Pn, 2, m, 2], pose [Pn, 2, m, 7], n [Pn, 2]) with m <= M; -> numpy (t [Pn, 2, M, 2] float64, pose [Pn, 2, M, 7] float32, n [Pn, 2] int32),
+        padded to the roll-out's M the way the roll-out pads its own plan (zero times, the identity pose), so a pool row built from the roll-out's plan
+        has the bits of self.plan.  A plan with more than M - 1 contacts on a foot (the merged list holds the current contact besides the planner's
+        future ones) is a ValueError.  No GPU is touched.  Packed CUDA tensors of the roll-out's M are returned as they are, without a host read: their
+        counts are the caller's to keep at or below M - 1."""
+        M = self.M
+        if isinstance(plans, (list, tuple)) and len(plans) > 0 and isinstance(plans[0], dict):
+            t, pose, n = pack_lists(self.cfg, list(plans))
+        elif all(getattr(a, "is_cuda", False) for a in plans):    # (packed on the device already: taken as they are, no host read -- the counts are the caller's)
+            if len(plans) != 3 or tuple(plans[0].shape[1:]) != (2, M, 2) or tuple(plans[1].shape[1:]) != (2, M, 7) or tuple(plans[2].shape[1:]) != (2,):
+                raise ValueError(f"plans: device arrays must be padded to the roll-out's M = {M} already")
+            return tuple(plans)
+        else:
+            host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+            t, pose, n = (host(a) for a in plans)
+        t, pose, n = np.asarray(t, np.float64), np.asarray(pose, np.float32), np.asarray(n, np.int32)
+        Pn, m = int(t.shape[0]), int(t.shape[2])
+        if Pn < 1 or t.shape != (Pn, 2, m, 2) or pose.shape != (Pn, 2, m, 7) or n.shape != (Pn, 2):
+            raise ValueError("plans: plan dicts, or (t [Pn, 2, m, 2], pose [Pn, 2, m, 7], n [Pn, 2]) with Pn >= 1")
+        if int(n.max()) > M - 1:
+            raise ValueError(f"plans: a plan with {int(n.max())} contacts on a foot, more than the roll-out's M - 1 = {M - 1}")
+        k = min(m, M)
+        tt = np.zeros((Pn, 2, M, 2)); pp = np.zeros((Pn, 2, M, 7), np.float32); pp[..., 3] = 1.0
+        tt[:, :, :k] = t[:, :, :k]; pp[:, :, :k] = pose[:, :, :k]
+        return tt, pp, np.ascontiguousarray(n)
+
+    def plan_references(self, plans, trial_ticks):
+        """The straight-line references of a pool of plan dicts, one row per plan at that plan's own mean speed, sized for trials of trial_ticks ticks: the
+        very expression of _planner_refs, so row p has the bits of the default references of a roll-out constructed with plans[p].
+        -> dict(com=[Pn, n, 3], h=[Pn, n, 3] float32 on the device, in_dt, t_first, robot_mass, com_height), walk_device_refill_plans' references=."""
+        torch, N, dt, dev = self.torch, self.cfg.N, self.cfg.sampling_time, self.dev
+        n_plan = trial_ticks + N + 2
+        com = torch.zeros((len(plans), n_plan, 3), dtype=torch.float32, device=dev)
+        for p, plan in enumerate(plans):
+            com[p, :, 0] = (WalkingRollout._plan_speed(plan) * dt * torch.arange(n_plan, dtype=torch.float64, device=dev)).to(torch.float32)
+        return dict(com=com, h=torch.zeros_like(com), in_dt=dt, t_first=0.0, robot_mass=1.0, com_height=0.7)
+
+    def walk_device_refill_plans(self, ticks, trial_ticks, com0, dcom0, h0, plans, plan_of, references=None, models=None, mismatch=None, taped=False,
+                                 **kwargs):
+        """walk_device_refill_trials(ticks, trial_ticks, com0, dcom0, h0, models, mismatch, **kwargs) -- walk_device_refill_taped with taped=True -- with a
+        FOOTSTEP PLAN AND REFERENCE TRAJECTORIES PER TRIAL (cmpc_rollout_walk_refill_plans_device, include/cmpc.h; DESIGN.md 7f "Refill, plans per
+        trial"): which slot a trial lands in depends on who fell before it, so the slot's plan is nothing a study can choose; here trial q walks pool row
+        plan_of[q].  One launch more per tick (the plan select, behind the refill: six, eight when taped), still no host read.
+        plans: a list of plan dicts as walking_plan returns them, or packed arrays (plan_pool's argument), padded to the roll-out's M; a plan with more
+        than M - 1 contacts is a ValueError.  plan_of [Q] int (numpy or CUDA); repeats are the normal case.  references: None keeps the SLOT's references
+        as walk_device_refill does; else dict(com=[Pn, n, 3], h=[Pn, n, 3], in_dt, t_first, robot_mass, com_height) with set_references' meaning, row p
+        going with plan p (plan_references() builds the straight lines at each plan's own mean speed).  kwargs: walk_device_refill_trials' push,
+        push_ticks, wrench_trials, trace and stop; anything else is a TypeError.  plans=None: walk_device_refill_trials / walk_device_refill_taped.
+        A trial's bits are those of walk_device_mismatch(trial_ticks, ..., tick_first=0) on a roll-out of the same batch size, factor storage and options
+        that holds it in the same slot with that slot's plan (and references) the trial's pool row, models row `slot` the trial's model and the
+        schedules' column `slot` the trial's rows.
+        -> walk_device_refill_trials' dict (the taped one with taped=True) plus trials["plan"] [Q] int32 = plan_of and trials["plan_ok"] [Q] int32: 1 / 0
+        once the trial has started (0: its index lay outside the pool -- nothing was copied, the trial is ended at spawn with end_tick 0 and end_code 0,
+        and the slot goes to the next trial), -1 for a trial never started.  With taped=True the tape keeps plan_of and pool_plans, and
+        backward_device_refill() returns plan_pool.  The slots' planner rows passed to the walk are clones: self.plan, self.references and the
+        roll-out's models are what they were afterwards.
+        Out of scope -- NotImplementedError, raised before anything touches a GPU: replan, every (snapshots and checkpoints), a snapshot (per-trial plans
+        for trials from a snapshot would be a replan of a walk in progress), lists longer than 16 contacts."""
+        who = "walk_device_refill_plans"
+        for name in ("replan", "every", "snapshot"):
+            if kwargs.get(name) is not None:
+                raise NotImplementedError(f"{who}: {name} is out of scope of a refill walk with plans per trial")
+            kwargs.pop(name, None)
+        if self.M > 16:
+            raise NotImplementedError(f"{who}: lists longer than 16 contacts are out of scope (a slot's first tick uses the front kernel's LDS stage)")
+        if plans is None:
+            if references is not None:
+                raise ValueError(f"{who}: references go with plans")
+            return WalkingRollout._walk_refill_trials(self, who, bool(taped), ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs)
+        pool = WalkingRollout.plan_pool(self, plans)
+        Pn = int(pool[0].shape[0])
+        if references is not None:
+            unknown = set(references) - {"com", "h", "in_dt", "t_first", "robot_mass", "com_height"}
+            if unknown or "com" not in references or "h" not in references or "in_dt" not in references:
+                raise ValueError(f"{who}: references = dict(com, h, in_dt, t_first=0.0, robot_mass=1.0, com_height=0.7)")
+            if tuple(references["com"].shape) != tuple(references["h"].shape) or len(references["com"].shape) != 3 or \
+                    int(references["com"].shape[0]) != Pn or int(references["com"].shape[1]) < 2 or int(references["com"].shape[2]) != 3:
+                raise ValueError(f"{who}: references com and h of one shape [{Pn}, n >= 2, 3], a row per plan")
+        given = dict(pool=pool, plan_of=plan_of, references=references)
+        return WalkingRollout._walk_refill_trials(self, who, bool(taped), ticks, trial_ticks, com0, dcom0, h0, models, mismatch, kwargs, plans=given)
 
     def walk_device_refill_from_snapshot(self, snapshot, ticks, trial_ticks, snapshot_of, models=None, mismatch=None, **kwargs):
         """A queue of Q = len(snapshot_of) trials that each START FROM A SNAPSHOT of a walk in progress, walked through the B slots of this roll-out in ONE
@@ -384,9 +476,10 @@ class WalkingRollout:
             return rec
         return self._queued(walk)
 
-    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None, tape=False):
+    def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None, tape=False, plans=None):
         torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
         assert not (tape and pool is not None), "trials that start from a snapshot are not taped"
+        assert not (plans is not None and pool is not None), "trials that start from a snapshot keep their snapshot's lists"
         dt, dev, s = cfg.sampling_time, self.dev, self.solver
         self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
 
@@ -409,6 +502,18 @@ class WalkingRollout:
         state = z((B, 9))
         ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
         refs = self._planner_refs(trial_ticks if pool is None else pool["tick"] + trial_ticks)
+        plan_live, select = self.plan, None
+        if plans is not None:    # (the select launch writes the slots' planner rows: clones, so that self.plan and self.references stay what they are)
+            plan_live = tuple(a.clone() for a in self.plan)
+            pool_refs, r = None, plans["references"]
+            if r is not None:
+                pool_refs = (r["com"], r["h"])
+                n_ref = int(r["com"].shape[1])
+                height = r.get("com_height", 0.7)
+                refs = (z((B, n_ref, 3)), z((B, n_ref, 3)), float(r["in_dt"]), float(r.get("t_first", 0.0)), float(r.get("robot_mass", 1.0)),
+                        float("nan") if height is None else float(height))
+            select = s.walk_refill_plans(plans["pool"], plans["plan_of"], plan_live, pool_refs, planner=refs, device=dev)
+            assert select["trials"] == Q, "plan_of must have the queue's length"
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         s.outcome_init_device(state, rec)
         fill = s.walk_refill(state0, trial_ticks, wrench_trials, trace_rows=ticks, device=dev)
@@ -420,7 +525,11 @@ class WalkingRollout:
         sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
         try:
             rec.update(self._limits_on(self.limits, ticks, trace, extremes=False))    # (a slot holds several trials: no extremes)
-            if pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
+            if select is not None:    # (plans per trial: the select launch fills a spawned slot's planner rows in front of its first tick)
+                cur = s.rollout_walk_refill_plans_device(0, ticks, plan_live, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, select,
+                                                         row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                                                         force_sample_time=self.force_sample_time, tape=tp, tape_row0=0, trials=trials)
+            elif pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
                 cur = s.rollout_walk_refill_snapshot_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill,
                                                             pool, row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
                                                             force_sample_time=self.force_sample_time, trials=trials)
@@ -438,6 +547,8 @@ class WalkingRollout:
                       models=None if trials is None else trials["models"],
                       mismatch=None if trials is None else {k: trials[k] for k in ("hidden_wrench", "state_noise", "force_gain")},
                       references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
+            if select is not None:
+                tp.update(plan_of=select["plan_of"], pool_plans=select["pool_plans"])
             rec["tape"] = tp
         trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
         if trace:
@@ -451,7 +562,9 @@ class WalkingRollout:
                 out["valid"] = ar < trials["ticks"][q]
                 return out
             trials["trace"] = trial_trace
-        self._walk_refill_keep = (fill, refs, wrench_trials, trials, pool)    # (the queued launches read these)
+        if select is not None:
+            trials.update(plan=select["plan_of"], plan_ok=select["plan_ok"])
+        self._walk_refill_keep = (fill, refs, wrench_trials, trials, pool, select)    # (the queued launches read these)
         rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state, trial_of=fill["trial_of"], trials=trials)
         return rec
 
@@ -982,6 +1095,10 @@ class WalkingRollout:
         end_tick [Q] (the effective one: refill_trial_walk's), in backward_device's dtypes; under a per-trial mismatch also hidden_wrench
         [trial_ticks, Q, 6], state_noise [trial_ticks, Q, 9] and force_gain [Q].  Pad columns are dropped.  A trial's `plan` is the gradient with respect
         to the planner lists of the SLOT it walked in: sum it by w["trials"]["slot"] for the gradient of a slot's lists.
+        On the tape of walk_device_refill_plans(taped=True) a trial's `plan` is the gradient with respect to ITS OWN plan row (the tape holds the trial's
+        planner times and counts), and the dict gains plan_pool [Pn, 2, M, 3]: the sum of plan + list0 (the first tick's lists are the plan's) over the
+        trials of each pool row, in ascending trial order and without atomics (cmpc_rollout_plan_fold_device); a row no trial named is zero, and a trial
+        whose index lay outside the pool contributes nowhere.  With no plans on the tape the keys and their bits are what they were.
         With per-trial models the group's rows go through set_models_device first and the roll-out's own models are back afterwards, as after
         walk_device_refill_trials.  Every trial's keys are bit-equal to backward_device on a walk_device_taped of its own that holds it in any column
         with its model and its mismatch columns: the reverse kernels do not depend on the batch position.
@@ -1023,7 +1140,10 @@ class WalkingRollout:
                     s.set_models(None)
         if not parts:
             raise ValueError("backward_device_refill: the queue is empty")
-        return {k: torch.cat([p[k] for p in parts], batch_dim.get(k, 0)) for k in parts[0]}
+        out = {k: torch.cat([p[k] for p in parts], batch_dim.get(k, 0)) for k in parts[0]}
+        if src.get("plan_of") is not None:    # (the pool's gradient: the fold over the trials that share a row, in ascending trial order)
+            out["plan_pool"] = self._queued(lambda: s.plan_fold_device(src["plan_of"], (out["plan"] + out["list0"]).contiguous(), int(src["pool_plans"])))
+        return out
 
     # ---- snapshots: resume, branch, and the reverse walk in bounded memory (include/cmpc.h, cmpc_walk_snapshot; DESIGN.md 7f, "Snapshots") ----
     def _queued(self, fn):

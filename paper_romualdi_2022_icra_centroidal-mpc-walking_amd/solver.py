@@ -1603,6 +1603,93 @@ class BatchSolver:
             C.byref(out), st))
         return out.value
 
+    def walk_refill_plans(self, pool, plan_of, plan, pool_refs=None, planner=None, device=None):
+        """A cmpc_walk_refill_plans as a dict: pool = (t [Pn, 2, M, 2] float64, pose [Pn, 2, M, 7] float32, n [Pn, 2] int32), the pool of footstep plans
+        in the layout of the planner's lists; plan_of [Q] int32 (numpy or CUDA), the pool row of each trial of the queue; plan = (t, pose, n) [B, ..], the
+        slots' planner rows the walk is given -- WRITTEN by the walk: pass clones; pool_refs = (com, h) [Pn, n, 3] float32 or None, the planner
+        trajectories of each plan, with planner = the (com, h, ...) tuple the walk is given (com / h [B, n, 3], written too).  The dict holds plan_of on the
+        device, plan_ok [Q] int32 (-1 until the trial's spawn writes 1 or 0), trials = Q, pool_plans = Pn, the tensors (kept alive) and "_c"."""
+        import torch
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_plans_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_plans_device")
+        dev = torch.device("cuda", self._device_index) if device is None else device
+        hold = []
+
+        def up(a, dtype, npdtype):
+            if not isinstance(a, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
+                hold.append(torch.from_numpy(np.ascontiguousarray(a, npdtype)))
+                a = hold[-1].to(dev, non_blocking=True)
+            return a.detach().to(dev, dtype).contiguous()
+        pt, pp, pn = up(pool[0], torch.float64, np.float64), up(pool[1], torch.float32, np.float32), up(pool[2], torch.int32, np.int32)
+        Pn, M = int(pt.shape[0]), int(plan[0].shape[2])
+        assert Pn >= 1 and tuple(pt.shape) == (Pn, 2, M, 2) and tuple(pp.shape) == (Pn, 2, M, 7) and tuple(pn.shape) == (Pn, 2), \
+            f"pool: (t [Pn, 2, {M}, 2], pose [Pn, 2, {M}, 7], n [Pn, 2])"
+        for a, dt, shape in zip(plan, (torch.float64, torch.float32, torch.int32), ((2, M, 2), (2, M, 7), (2,))):
+            assert a.is_cuda and a.dtype == dt and a.is_contiguous() and tuple(a.shape) == (self.batch,) + shape, "plan: the slots' (t, pose, n) on the device"
+        idx = up(plan_of, torch.int32, np.int32)
+        assert idx.dim() == 1, "plan_of: expected [Q]"
+        Q = int(idx.shape[0])
+        ok = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+        c = _capi.CmpcWalkRefillPlans()
+        c.pool_plans = Pn
+        c.dPoolT, c.dPoolPose, c.dPoolN = pt.data_ptr(), pp.data_ptr(), pn.data_ptr()
+        c.dTrialPlan, c.dTrialPlanOk = (idx.data_ptr(), ok.data_ptr()) if Q else (None, None)
+        c.dPlanT, c.dPlanPose, c.dPlanN = (a.data_ptr() for a in plan)
+        refs = None
+        if pool_refs is not None:
+            assert planner is not None, "pool_refs need the walk's planner tuple (the slots' trajectories)"
+            n = int(planner[0].shape[1])
+            refs = (up(pool_refs[0], torch.float32, np.float32), up(pool_refs[1], torch.float32, np.float32))
+            assert all(tuple(a.shape) == (Pn, n, 3) for a in refs), f"pool_refs: com and h [Pn, {n}, 3] (the knots of the slots' trajectories)"
+            assert all(a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and tuple(a.shape) == (self.batch, n, 3) for a in planner[:2])
+            c.dPoolCom, c.dPoolH = refs[0].data_ptr(), refs[1].data_ptr()
+            c.dPlanCom, c.dPlanH = planner[0].data_ptr(), planner[1].data_ptr()
+        return dict(pool=(pt, pp, pn), pool_refs=refs, plan_of=idx, plan_ok=ok, trials=Q, pool_plans=Pn, plan=plan, planner=planner, _host=hold, _c=c)
+
+    def rollout_walk_refill_plans_device(self, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, plans,
+                                         row0=0, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
+                                         tape=None, tape_row0=0, trials=None):
+        """cmpc_rollout_walk_refill_plans_device: rollout_walk_refill_device with a footstep plan (and planner trajectories) per TRIAL (plans:
+        walk_refill_plans(...) over the same `plan` and `planner` tensors, which the walk WRITES; None: the taped / trials call through the new entry
+        point).  One launch more per tick, the plan select, behind the refill: six, eight when taped.  (A method of its own: the parameter list of
+        rollout_walk_refill_device is pinned.)"""
+        if not hasattr(self._lib, "cmpc_rollout_walk_refill_plans_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_plans_device")
+        io = _capi.CmpcWalkIO()
+        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                force_sample_time)
+        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
+        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        out = C.c_int(-1)
+        if plans is not None:
+            assert plans["trials"] == refill["trials"], "plan_of must have the queue's length"
+        if trials is not None:
+            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_plans_device(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
+            C.byref(trials["_c"]) if trials is not None else None, C.byref(plans["_c"]) if plans is not None else None, int(row0), int(lists_in),
+            C.byref(out), C.byref(tape["_c"]) if tape is not None else None, int(tape_row0), st))
+        return out.value
+
+    def plan_fold_device(self, index, per_trial, pool_rows, out=None):
+        """cmpc_rollout_plan_fold_device: out[p] = the sum of per_trial[q] over the trials with index[q] == p, in ascending q, without atomics (the bits do
+        not depend on scheduling).  index [Q] int32, per_trial [Q, ..] float64 CUDA tensors -> out [pool_rows, ..] float64, written whole (zero for a row
+        no trial has); an index outside the pool contributes nowhere."""
+        import torch
+        if not hasattr(self._lib, "cmpc_rollout_plan_fold_device"):
+            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_plan_fold_device")
+        Q = int(per_trial.shape[0])
+        tail = tuple(per_trial.shape[1:])
+        words = int(np.prod(tail)) if tail else 1
+        assert per_trial.is_cuda and per_trial.dtype == torch.float64 and per_trial.is_contiguous(), "per_trial [Q, ..] float64"
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and tuple(index.shape) == (Q,), "index [Q] int32"
+        if out is None:
+            out = torch.empty((int(pool_rows),) + tail, dtype=torch.float64, device=per_trial.device)
+        po = self._opt(out, torch.float64, (int(pool_rows),) + tail, "out")
+        self._launch(per_trial.device, lambda st: self._lib.cmpc_rollout_plan_fold_device(
+            self._h, Q, words, index.data_ptr() if Q else None, per_trial.data_ptr() if Q else None, int(pool_rows), po, st))
+        return out
+
     def tape_regroup_device(self, src_tape, refill, trial_index, dst_tape=None, tick_first=0):
         """cmpc_rollout_tape_regroup_device: ONE launch on torch's current stream, no host read -- column j of dst_tape (walk_tape of refill["trial_ticks"]
         rows with first_row_is_first_tick; None: allocated here with src_tape's scalars) receives the rows of trial trial_index[j] out of the slot-major
