@@ -15,7 +15,7 @@ from .config import GRAVITY
 
 from .contacts import PlannedContact, pack_lists
 from .layout import Layout
-from .solver import BatchSolver, _model_array
+from .solver import BatchSolver, _model_array, _upload
 
 FOOT_Y = 0.08
 
@@ -212,7 +212,7 @@ class WalkingRollout:
         end_tick[B] (-1: walked to the end), end_code[B], iterations_sum[B], iterations_max[B], final_state[B, 9], box_slack_min[B]; stats[ticks, 6];
         lists (t, pose, n) of the last tick; X, P, info of the last tick; state[B, 9], the batch's state buffer after the last tick (ended problems
         included, unlike final_state).  The same walk with a device tape for backward_device(): walk_device_taped()."""
-        return self._walk_on_launch_stream(False, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended)
+        return self._queued(lambda: self._walk(False, None, None, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended))
 
     def walk_device_refill(self, ticks, trial_ticks, com0, dcom0, h0, push=None, push_ticks=0, wrench_trials=None, trace=True,
                            stop=("merge", "solver", "nonfinite"), replan=None, mismatch=None, taped=False, every=None):
@@ -477,30 +477,18 @@ class WalkingRollout:
         return self._queued(walk)
 
     def _walk_refill(self, ticks, trial_ticks, com0, dcom0, h0, push, push_ticks, wrench_trials, trace, stop, trials=None, pool=None, tape=False, plans=None):
-        torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
+        torch, B = self.torch, self.B
         assert not (tape and pool is not None), "trials that start from a snapshot are not taped"
         assert not (plans is not None and pool is not None), "trials that start from a snapshot keep their snapshot's lists"
-        dt, dev, s = cfg.sampling_time, self.dev, self.solver
-        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
-
-        def up(a):
-            if isinstance(a, torch.Tensor):
-                return a.to(dev, torch.float32)
-            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-            return hold[-1].to(dev, non_blocking=True)
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+        dt, dev, s = self.cfg.sampling_time, self.dev, self.solver
+        self._walk_inputs, up = [], self._up
+        z = lambda shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
         Q = int(state0.shape[0])
-        if push is not None:
-            dpush = up(push)
-            wrench_trials = z((push_ticks + 1, Q, N, 6))
-            for i in range(push_ticks):
-                wrench_trials[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
+        if push is not None:    # (the schedule rule in the trial's local ticks)
+            wrench_trials = self._push_schedule(up(push), push_ticks, Q)
         elif wrench_trials is not None:
             wrench_trials = up(wrench_trials).contiguous()
-        dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
-        state = z((B, 9))
-        ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
         refs = self._planner_refs(trial_ticks if pool is None else pool["tick"] + trial_ticks)
         plan_live, select = self.plan, None
         if plans is not None:    # (the select launch writes the slots' planner rows: clones, so that self.plan and self.references stay what they are)
@@ -515,41 +503,30 @@ class WalkingRollout:
             select = s.walk_refill_plans(plans["pool"], plans["plan_of"], plan_live, pool_refs, planner=refs, device=dev)
             assert select["trials"] == Q, "plan_of must have the queue's length"
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
-        s.outcome_init_device(state, rec)
+        tp = self._walk_tape(ticks) if tape else None
+        # the slots start empty; the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
+        live = self._live_buffers(rec, z((B, 9)), self.plan)
         fill = s.walk_refill(state0, trial_ticks, wrench_trials, trace_rows=ticks, device=dev)
-        tp = None
-        if tape:    # (as walk_device_taped: the multiplier output on before anything is queued)
-            s.set_multiplier_output(True)
-            tp = s.walk_tape(ticks, self.M, step=dt / self.substeps, substeps=self.substeps, force_sample_time=self.force_sample_time, device=dev)
-        # the set a slot's first tick writes at tick 0 is set 0, the one walk_device's first tick keeps the caller's lists in
-        sets = [tuple(a.clone() for a in self.plan), tuple(torch.zeros_like(a) for a in self.plan)]
+        sets = live["lists"]
         try:
             rec.update(self._limits_on(self.limits, ticks, trace, extremes=False))    # (a slot holds several trials: no extremes)
-            if select is not None:    # (plans per trial: the select launch fills a spawned slot's planner rows in front of its first tick)
-                cur = s.rollout_walk_refill_plans_device(0, ticks, plan_live, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, select,
-                                                         row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                                         force_sample_time=self.force_sample_time, tape=tp, tape_row0=0, trials=trials)
-            elif pool is not None:    # (trials from a snapshot: the restore launch fills a spawned slot's rows of both sets)
-                cur = s.rollout_walk_refill_snapshot_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill,
-                                                            pool, row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                                            force_sample_time=self.force_sample_time, trials=trials)
-            else:
-                cur = s.rollout_walk_refill_device(0, ticks, self.plan, sets[0], sets[1], 1, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, fill, row0=0,
-                                                   step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                                   force_sample_time=self.force_sample_time, trials=trials,
-                                                   **(dict(tape=tp, tape_row0=0) if tp is not None else {}))
+            # (ONE call: the public method of the struct that is given -- plans per trial: the select launch fills a spawned slot's planner rows in front
+            #  of its first tick; trials from a snapshot: the restore launch fills a spawned slot's rows of both sets -- or the plain, trials or taped walk)
+            walk, struct = ((s.rollout_walk_refill_plans_device, (select,)) if select is not None else
+                            (s.rollout_walk_refill_snapshot_device, (pool,)) if pool is not None else (s.rollout_walk_refill_device, ()))
+            cur = walk(0, ticks, plan_live, sets[0], sets[1], 1, live["ok"], live["land"], live["state"], live["P"], live["X0"], live["X"], live["info"],
+                       live["zmp"], rec, fill, *struct, row0=0, step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                       force_sample_time=self.force_sample_time, trials=trials, **(dict(tape=tp, tape_row0=0) if tp is not None else {}))
         finally:
             self._limits_off(self.limits)
+        s.walk_snapshot_mark(live, ticks, cur)
         s.rollout_refill_device(ticks, rec, fill, None)    # (the last tick's record ran behind its refill: one archive pass more)
-        del rec["_c"]
         if tp is not None:    # (slot-major: refill_trial_walk regroups it by trial; the refill's arrays and the per-trial data stay alive with it)
-            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, trial_ticks=int(trial_ticks), refill=fill, state0=state0,
-                      models=None if trials is None else trials["models"],
-                      mismatch=None if trials is None else {k: trials[k] for k in ("hidden_wrench", "state_noise", "force_gain")},
-                      references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
+            tp.update(trial_ticks=int(trial_ticks), refill=fill, state0=state0, models=None if trials is None else trials["models"],
+                      mismatch=None if trials is None else {k: trials[k] for k in ("hidden_wrench", "state_noise", "force_gain")})
             if select is not None:
                 tp.update(plan_of=select["plan_of"], pool_plans=select["pool_plans"])
-            rec["tape"] = tp
+        self._walk_finish(rec, live, tp, refs, push_ticks if push is not None else 0)
         trials = {k: fill[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min", "ticks", "slot", "start")}
         if trace:
             ar = torch.arange(trial_ticks, device=dev)
@@ -565,7 +542,7 @@ class WalkingRollout:
         if select is not None:
             trials.update(plan=select["plan_of"], plan_ok=select["plan_ok"])
         self._walk_refill_keep = (fill, refs, wrench_trials, trials, pool, select)    # (the queued launches read these)
-        rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state, trial_of=fill["trial_of"], trials=trials)
+        rec.update(trial_of=fill["trial_of"], trials=trials)
         return rec
 
     def _mismatch_of(self, mismatch):
@@ -587,7 +564,7 @@ class WalkingRollout:
         walk_device: that signature is pinned.)"""
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
-        return self._walk_on_launch_stream(False, *args.args, **args.kwargs, mismatch=mismatch)
+        return self._queued(lambda: self._walk(False, None, None, *args.args, **args.kwargs, mismatch=mismatch))
 
     def walk_device_taped(self, ticks, com0, dcom0, h0, **kwargs):
         """walk_device(ticks, com0, dcom0, h0, **kwargs) through cmpc_rollout_walk_taped_device: every tick also writes its row of a device tape -- what
@@ -602,78 +579,57 @@ class WalkingRollout:
         mismatch = kwargs.pop("mismatch", None)
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
-        return self._walk_on_launch_stream(True, *args.args, **args.kwargs, mismatch=mismatch)
+        return self._queued(lambda: self._walk(True, None, None, *args.args, **args.kwargs, mismatch=mismatch))
 
-    def _walk_on_launch_stream(self, tape, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
-        torch = self.torch
-        assert self.retry != "launch", "walk_device needs retry='kernel' or None"
-        ls = self.solver.launch_stream
-        cur = torch.cuda.current_stream(self.dev)
-        ls.wait_stream(cur)
-        try:
-            with torch.cuda.stream(ls):
-                return self._walk_device(ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, tape, mismatch)
-        finally:
-            cur.wait_stream(ls)
-
-    def _walk_device(self, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended=False, tape=False, mismatch=None):
-        torch, L, cfg, B, N = self.torch, self.L, self.cfg, self.B, self.cfg.N
-        dt, dev, s = cfg.sampling_time, self.dev, self.solver
+    def _walk(self, tape, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
+        """walk_device and its mismatched, taped (tape) and checkpointed (every) forms: the start state in live buffers, the ticks queued by _walk_live.
+        every None: walk_device's dict (with "tape": walk_device_taped's); else "checkpoints" and "inputs" besides.  states: _walk_live's."""
+        torch, dev, s, up = self.torch, self.dev, self.solver, self._up
         mm = self._walk_mismatch = self._mismatch_of(mismatch)    # (kept until the next call: the queued launches read its tensors)
-        # (a numpy input is uploaded without the host waiting for the copy; a CUDA tensor is used as it is)
-        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
-
-        def up(a):
-            if isinstance(a, torch.Tensor):
-                return a.to(dev, torch.float32)
-            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-            return hold[-1].to(dev, non_blocking=True)
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
-        dP, dX0, dX, dInfo = z((B, L.np)), z((B, L.nx)), z((B, L.nx)), z((B, 8))
-        state = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
-        ok, land, zmp = torch.ones((B,), dtype=torch.int32, device=dev), z((B, 2), torch.int32), z((B, 2))
-        wrench_ticks = None
-        if push is not None:    # run()'s schedule: the push on the first max(push_ticks - i, 1) knots of tick i < push_ticks, zeros once at tick push_ticks
-            dpush = up(push)
-            wrench_ticks = z((push_ticks + 1, B, N, 6))
-            for i in range(push_ticks):
-                wrench_ticks[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
+        self._walk_inputs = []
+        state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
+        wrench = (self._push_schedule(up(push), push_ticks, self.B), 0) if push is not None else None
         # the planner's references as in run(): set_references', else a straight line at the plan's mean speed, a knot every dt from time zero
         refs = self._planner_refs(ticks)
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
-        s.outcome_init_device(state, rec)
-        tp = None
-        if tape:    # (as run(tape=True): the multiplier output on before anything is queued)
-            s.set_multiplier_output(True)
-            tp = s.walk_tape(ticks, self.M, step=dt / self.substeps, substeps=self.substeps, force_sample_time=self.force_sample_time, device=dev)
-        replan = dict(replan or {})
-        plan = replan.get(0, self.plan)
-        sets = [tuple(a.clone() for a in plan), tuple(torch.zeros_like(a) for a in plan)]
-        starts = sorted({0} | {t for t in replan if 0 < t < ticks})
-        cur = 0
-        if skip_ended:    # (the queued launches keep the pointer; rec["end_tick"] goes back to the caller and outlives them)
-            s.set_ended_device(rec["end_tick"])
-        try:
-            rec.update(self._limits_on(self.limits, ticks, trace))
-            for j, t0 in enumerate(starts):
-                t1 = starts[j + 1] if j + 1 < len(starts) else ticks
-                plan = replan.get(t0, plan)
-                wr = wrench_ticks[t0:] if wrench_ticks is not None and t0 < wrench_ticks.shape[0] else None
-                cur = s.rollout_walk_device(t0, t1 - t0, t0 == 0, plan, sets[0], sets[1], cur, ok, land, state, dP, dX0, dX, dInfo, zmp, rec, row0=t0,
-                                            wrench_ticks=wr, step=dt / self.substeps, substeps=self.substeps, planner=refs,
-                                            force_sample_time=self.force_sample_time, tape=tp, mismatch=mm)
-        finally:
-            self._limits_off(self.limits)
-            if skip_ended:
-                s.set_ended_device(None)
+        tp = self._walk_tape(ticks) if tape else None
+        plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < ticks}
+        # (the walk runs in place on its state: on state0 itself, or on a copy where "inputs" keeps state0 for a re-run)
+        live = self._live_buffers(rec, state0 if every is None else state0.clone(), plans.get(0, self.plan))
+        if states is not None:
+            states[0].copy_(state0)
+        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, cold=True, states=states, mismatch=mm,
+                              limits=self.limits, limits_out=rec)
+        if every is not None:
+            for c in cps.values():
+                c["wrench"] = wrench
+            rec.update(checkpoints=cps, inputs=dict(
+                state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
+                skip_ended=bool(skip_ended), ticks=int(ticks), every=every, mismatch=mm, limits=self.limits))
+        return self._walk_finish(rec, live, tp, refs, push_ticks if push is not None else 0, mm, segments=[a for a, _ in walk_schedule(ticks, every, plans)[0]])
+
+    def _up(self, a, dtype=None):
+        """a walk's input on the device (float32 unless dtype is given); the host array of a queued copy is kept in _walk_inputs until the next walk"""
+        return _upload(a, self.dev, dtype or self.torch.float32, self._walk_inputs)
+
+    def _walk_tape(self, rows, **kw):
+        """a device tape of `rows` rows for a walk of this roll-out, the multiplier output on before anything is queued, as run(tape=True) does"""
+        self.solver.set_multiplier_output(True)
+        return self.solver.walk_tape(rows, self.M, step=self.cfg.sampling_time / self.substeps, substeps=self.substeps,
+                                     force_sample_time=self.force_sample_time, device=self.dev, **kw)
+
+    def _walk_finish(self, rec, live, tape=None, refs=None, push_ticks=0, mismatch=None, **entries):
+        """The end every device walk shares: rec gives up its C struct and receives the live buffers of the last tick -- lists, X, P, info, state -- and
+        the tape with its host entries: dt, `entries`, push_ticks and the references' timing (with refs), mismatch (when there is one)."""
         del rec["_c"]
-        if tp is not None:
-            tp.update(dt=dt, push_ticks=push_ticks if push is not None else 0, segments=starts,
-                      references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
-            if mm is not None:
-                tp["mismatch"] = mm
-            rec["tape"] = tp
-        rec.update(lists=sets[cur], X=dX, P=dP, info=dInfo, state=state)
+        if tape is not None:
+            tape.update(dt=self.cfg.sampling_time, **entries)
+            if refs is not None:
+                tape.update(push_ticks=push_ticks, references=dict(knots=int(refs[0].shape[1]), dt=refs[2], t_first=refs[3], robot_mass=refs[4], com_height=refs[5]))
+            if mismatch is not None:
+                tape["mismatch"] = mismatch
+            rec["tape"] = tape
+        rec.update(lists=live["lists"][live["lists_in"]], X=live["X"], P=live["P"], info=live["info"], state=live["state"])
         return rec
 
     def _tick_by_steps(self, i, now, mpc_prev, warm, dump, dP, dX0, dX, dInfo, state, wrench, dpush, push_ticks, planner):
@@ -1159,15 +1115,24 @@ class WalkingRollout:
         finally:
             cur.wait_stream(ls)
 
-    def _live_buffers(self, rec):
-        """the live buffers of a walk described as a snapshot (BatchSolver.walk_snapshot), zero-filled; the outcome arrays are rec's"""
-        keys = ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min")
-        live = self.solver.walk_snapshot(0, 0, self.M, device=self.dev, tensors={k: rec[k] for k in keys})
+    def _live_buffers(self, rec, state0=None, plan0=None):
+        """The live buffers of a walk described as a snapshot (BatchSolver.walk_snapshot); the outcome arrays are rec's.  Without state0: zero-filled, for
+        a restore or _live_reset.  With state0 [B, 9] (taken as it is: the walk runs in place on it) and plan0: allocated as walk_device has them in
+        front of tick 0 -- zeros, ok = 1, a copy of the plan in list set 0 -- and the outcome queued at its start: no fill a fresh walk does not need."""
+        torch = self.torch
+        given = {k: rec[k] for k in ("end_tick", "end_code", "iterations_sum", "iterations_max", "final_state", "box_slack_min")}
+        if state0 is not None:
+            given.update(state=state0, ok=torch.ones((self.B,), dtype=torch.int32, device=self.dev),
+                         lists=[tuple(a.clone() for a in plan0), tuple(torch.zeros_like(a) for a in plan0)])
+        live = self.solver.walk_snapshot(0, 0, self.M, device=self.dev, tensors=given)
         live["rec"] = rec
+        if state0 is not None:
+            self.solver.outcome_init_device(state0, rec)
         return live
 
     def _live_reset(self, live, state0, plan0):
-        """the live buffers as walk_device has them in front of tick 0: zeros, ok = 1, the plan in list set 0, the outcome at its start"""
+        """buffers that are used again (the checkpointed reverse's workspace) put back to what walk_device has in front of tick 0: zeros, ok = 1, the plan in
+        list set 0, the outcome at its start"""
         for k in ("P", "X", "X0", "info", "zmp", "land"):
             live[k].zero_()
         live["ok"].fill_(1)
@@ -1179,9 +1144,10 @@ class WalkingRollout:
         self.solver.outcome_init_device(live["state"], live["rec"])
         self.solver.walk_snapshot_mark(live, 0, 0)
 
-    def _push_schedule(self, dpush, push_ticks):
-        """run()'s schedule as rows of wrench_ticks: the push on the first max(push_ticks - i, 1) knots of row i < push_ticks, zeros once in row push_ticks"""
-        wt = self.torch.zeros((push_ticks + 1, self.B, self.cfg.N, 6), dtype=self.torch.float32, device=self.dev)
+    def _push_schedule(self, dpush, push_ticks, columns):
+        """run()'s schedule as rows of wrench_ticks: the push on the first max(push_ticks - i, 1) knots of row i < push_ticks, zeros once in row push_ticks;
+        columns: B for a walk, the queue's Q for the trials of a refill walk (rows = the trial's local ticks)"""
+        wt = self.torch.zeros((push_ticks + 1, columns, self.cfg.N, 6), dtype=self.torch.float32, device=self.dev)
         for i in range(push_ticks):
             wt[i, :, :max(push_ticks - i, 1), :3] = dpush[:, None, :]
         return wt
@@ -1235,36 +1201,7 @@ class WalkingRollout:
         mismatch = kwargs.pop("mismatch", None)    # (walk_device_mismatch's argument; kept in "inputs" for backward_device_checkpointed_mismatch)
         args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
         args.apply_defaults()
-        return self._queued(lambda: self._walk_checkpointed(every, None, *args.args, **args.kwargs, mismatch=mismatch))
-
-    def _walk_checkpointed(self, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
-        torch, dev, s = self.torch, self.dev, self.solver
-        mm = self._mismatch_of(mismatch)
-        self._walk_inputs = hold = []    # (the host arrays of queued copies, kept until the next call)
-
-        def up(a):
-            if isinstance(a, torch.Tensor):
-                return a.to(dev, torch.float32)
-            hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-            return hold[-1].to(dev, non_blocking=True)
-        state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
-        wrench = (self._push_schedule(up(push), push_ticks), 0) if push is not None else None
-        refs = self._planner_refs(ticks)
-        rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
-        live = self._live_buffers(rec)
-        plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < ticks}
-        self._live_reset(live, state0, plans.get(0, self.plan))
-        if states is not None:
-            states[0].copy_(state0)
-        inputs = dict(state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
-                      skip_ended=bool(skip_ended), ticks=int(ticks), every=int(every), mismatch=mm, limits=self.limits)
-        cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, cold=True, states=states, mismatch=mm,
-                              limits=self.limits, limits_out=rec)
-        for c in cps.values():
-            c["wrench"] = wrench
-        del rec["_c"]
-        rec.update(lists=live["lists"][live["lists_in"]], X=live["X"], P=live["P"], info=live["info"], state=live["state"], checkpoints=cps, inputs=inputs)
-        return rec
+        return self._queued(lambda: self._walk(False, int(every), None, *args.args, **args.kwargs, mismatch=mismatch))
 
     def walk_resume_device(self, snapshot, ticks, index=None, push=None, push_ticks=0, replan=None, trace=True, stop=("merge", "solver", "nonfinite"),
                            skip_ended=False, taped=False, every=None):
@@ -1302,22 +1239,16 @@ class WalkingRollout:
     def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every, mismatch=None):
         torch, dev, s, B = self.torch, self.dev, self.solver, self.B
         mm = self._walk_mismatch = self._mismatch_of(mismatch)
-        self._walk_inputs = hold = []
-
-        def up(a, dt, np_dt):
-            if isinstance(a, torch.Tensor):
-                return a.to(dev, dt).contiguous()
-            hold.append(torch.from_numpy(np.ascontiguousarray(a, np_dt)))
-            return hold[-1].to(dev, non_blocking=True)
+        self._walk_inputs = []
         t0 = int(snapshot["tick"])
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
         live = self._live_buffers(rec)
-        idx = None if index is None else up(index, torch.int32, np.int32)
+        idx = None if index is None else self._up(index, torch.int32).contiguous()
         index_ok = torch.empty((B,), dtype=torch.int32, device=dev)
         s.rollout_snapshot_device(snapshot, live, idx, index_ok)
         wrench = None
         if push is not None:
-            wrench = (self._push_schedule(up(push, torch.float32, np.float32), push_ticks), t0)
+            wrench = (self._push_schedule(self._up(push).contiguous(), push_ticks, B), t0)
         elif snapshot.get("wrench") is not None and t0 - snapshot["wrench"][1] < snapshot["wrench"][0].shape[0]:
             wt, first = snapshot["wrench"]
             if idx is not None:
@@ -1327,24 +1258,16 @@ class WalkingRollout:
         plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < t0 + ticks}
         tp = None
         if taped:
-            s.set_multiplier_output(True)
-            tp = s.walk_tape(ticks + 1, self.M, step=self.cfg.sampling_time / self.substeps, substeps=self.substeps,
-                             force_sample_time=self.force_sample_time, first_row_is_first_tick=False, device=dev)
+            tp = self._walk_tape(ticks + 1, first_row_is_first_tick=False)
             prev = live["lists"][live["lists_in"]]
             tp["list_t"][0].copy_(prev[0])
             tp["list_n"][0].copy_(prev[2])
         cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1, mismatch=mm,
                               limits=self.limits, limits_out=rec)
-        del rec["_c"]
-        if tp is not None:
-            tp.update(dt=self.cfg.sampling_time, tick0=t0, row0=1)
-            if mm is not None:
-                tp["mismatch"] = mm
-            rec["tape"] = tp
         if every is not None:
             rec["checkpoints"] = cps
-        rec.update(lists=live["lists"][live["lists_in"]], X=live["X"], P=live["P"], info=live["info"], state=live["state"], index_ok=index_ok, tick0=t0)
-        return rec
+        rec.update(index_ok=index_ok, tick0=t0)
+        return self._walk_finish(rec, live, tp, mismatch=mm, tick0=t0, row0=1)    # (no push_ticks and no references on a resumed walk's tape)
 
     def backward_device_checkpointed(self, w, grad_states, grad_X=None, rot=False):
         """backward_device (rot=True: backward_device_rot) without a whole-walk tape.  w = walk_device_checkpointed(...).  For each segment between two
@@ -1833,8 +1756,8 @@ def rollout_differentiable_checkpointed_mismatch(rollout: WalkingRollout, ticks,
                 rollout.models_ok = rollout.solver.set_models_device(rollout.models)
             s0 = state0.detach().to(rollout.dev, torch.float32)
             states = torch.zeros((ticks + 1, rollout.B, 9), dtype=torch.float32, device=rollout.dev)
-            w = rollout._queued(lambda: rollout._walk_checkpointed(
-                every, states, ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks,
+            w = rollout._queued(lambda: rollout._walk(
+                False, int(every), states, ticks, s0[:, 0:3], s0[:, 3:6], s0[:, 6:9], None if push is None else push.detach().to(rollout.dev, torch.float32), push_ticks,
                 replan, False, ("merge", "solver", "nonfinite"), False, mismatch=mm))
             rollout.last_walk = ctx.walk = w
             ctx.dtypes = (state0.dtype, None if push is None else push.dtype)

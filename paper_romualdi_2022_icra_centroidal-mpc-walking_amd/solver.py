@@ -64,6 +64,17 @@ def _model_array(models, batch) -> np.ndarray:
     return a
 
 
+def _upload(a, dev, dtype, hold):
+    """`a` on the device in `dtype` for launches that are queued and not waited for: a torch tensor is cast as it is; anything else goes through a host
+    tensor appended to `hold` and a copy the host does not wait for, so `hold` has to outlive that copy (WalkingRollout._walk_inputs, a builder
+    dict's "_host")"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        return a.detach().to(dev, dtype)
+    hold.append(torch.from_numpy(np.ascontiguousarray(a, str(dtype).split(".")[1])))
+    return hold[-1].to(dev, non_blocking=True)
+
+
 class BatchSolver:
     """Thin RAII wrapper of a cmpc_handle: device-resident batched solve."""
 
@@ -1400,6 +1411,17 @@ class BatchSolver:
         dc, dh = self._opt(dir_com, torch.float64, (B, k, n, 3), "dir_com"), self._opt(dir_h, torch.float64, (B, k, n, 3), "dir_h")
         self._launch(dir_p.device, lambda st: self._lib.cmpc_reference_from_planner_jvp_device(self._h, int(tick0), int(rows), k, C.byref(refs), dc, dh, dp, st))
 
+    def _walk_io(self, plan, lists, lists_b, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                 force_sample_time):
+        """the cmpc_walk_io of a walk that runs in place on dState (include/cmpc.h): _tick_io's tick without previous lists, the second list set and the
+        time of the planner trajectories' first knot"""
+        io = _capi.CmpcWalkIO()
+        io.tick = self._tick_io(plan, None, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                force_sample_time)
+        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
+        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        return io
+
     def rollout_walk_device(self, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, row0=0,
                             wrench_ticks=None, dWrench=None, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
                             tape=None, tape_row0=None, mismatch=None):
@@ -1410,11 +1432,8 @@ class BatchSolver:
         tape (walk_tape): cmpc_rollout_walk_taped_device -- tick i of the call also writes row tape_row0 + i (default: row0 + i) of the tape; the
         multiplier output must be on.
         mismatch (plant_mismatch(...)): cmpc_rollout_walk_mismatch_device, taped or not -- tick tick0 + i runs under row tick0 + i - tick_first of its schedules."""
-        io = _capi.CmpcWalkIO()
-        io.tick = self._tick_io(plan, None, lists, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
-                                force_sample_time)
-        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
-        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        io = self._walk_io(plan, lists, lists_b, ok, land, dState, dWrench, dP, dX0, dX, dInfo, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                           force_sample_time)
         if wrench_ticks is not None:
             assert wrench_ticks.is_contiguous() and tuple(wrench_ticks.shape[1:]) == (self.batch, self.cfg.N, 6)
             io.dWrenchTicks, io.wrench_ticks = wrench_ticks.data_ptr(), int(wrench_ticks.shape[0])
@@ -1500,10 +1519,7 @@ class BatchSolver:
         def up(a, dtype, tail, name):
             if a is None:
                 return None
-            if not isinstance(a, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
-                hold.append(torch.from_numpy(np.ascontiguousarray(a, np.float64 if dtype == torch.float64 else np.float32)))
-                a = hold[-1].to(dev, non_blocking=True)
-            t = a.detach().to(dev, dtype).contiguous()
+            t = _upload(a, dev, dtype, hold).contiguous()    # (the host array is kept with the dict)
             assert t.dim() == len(tail) and all(w is None or int(t.shape[i]) == w for i, w in enumerate(tail)), f"{name}: expected {list(tail)}"
             return t if t.numel() > 0 else None
         r = dict(models=up(models, torch.float64, (None, _capi.MODEL_DOUBLES), "models"), hidden_wrench=up(hidden_wrench, torch.float32, (None, None, 6), "hidden_wrench"),
@@ -1530,30 +1546,31 @@ class BatchSolver:
         tape (walk_tape(...)): cmpc_rollout_walk_refill_taped_device -- tick i of the call also writes row tape_row0 + i of the tape, SLOT-major (seven
         launches a tick; the multiplier output must be on); tape_regroup_device gathers a trial's rows out of it.  (tape and tape_row0 stand in front of
         trials: that the parameter list ends with trials is pinned.)"""
-        self._need_refill()
-        io = _capi.CmpcWalkIO()
-        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
-                                force_sample_time)
-        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
-        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
+        return self._rollout_walk_refill("taped" if tape is not None else "trials" if trials is not None else "", tick0, ticks, plan, lists, lists_b, lists_in, ok,
+                                         land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0, step, substeps, zmp_half_x, zmp_half_y, planner,
+                                         force_sample_time, tape=tape, tape_row0=tape_row0, trials=trials)
+
+    def _rollout_walk_refill(self, entry, tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0=0,
+                             step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False, tape=None, tape_row0=0,
+                             trials=None, snapshot=None, plans=None):
+        """The one call behind rollout_walk_refill_device, _snapshot_device and _plans_device: the cmpc_walk_io, the queue-length checks, and the C entry
+        point cmpc_rollout_walk_refill_<entry>_device -- entry "plans", "snapshot", "taped", "trials" or "" (the plain one).  Each takes, of the
+        optional structs trials, snapshot, plans and tape, the ones its argument list has (include/cmpc.h), NULL where None."""
+        name = f"cmpc_rollout_walk_refill_{entry}{'_' if entry else ''}device"
+        if not hasattr(self._lib, name):
+            raise RuntimeError(f"this build of libcmpc_hip has no {name}")
+        io = self._walk_io(plan, lists, lists_b, ok, land, dState, None, dP, dX0, dX, dInfo, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner, force_sample_time)
+        for given, what in ((trials, "trials: the per-trial arrays"), (snapshot, "snapshot_of"), (plans, "plan_of")):
+            assert given is None or given["trials"] in (None, refill["trials"]), f"{what} must have the queue's length"    # (None: trials without an array)
+        if snapshot is not None:
+            assert snapshot["pool"]["max_contacts"] == lists[0].shape[2], "the pool's lists must have the walk's length"
+            assert snapshot["pool"]["_c"].tick == snapshot["tick"], "the pool was marked with another tick since walk_refill_snapshot"
+        ref = lambda d: C.byref(d["_c"]) if d is not None else None
         out = C.c_int(-1)
-        if trials is not None:
-            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
-        if tape is not None:
-            if not hasattr(self._lib, "cmpc_rollout_walk_refill_taped_device"):
-                raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_taped_device")
-            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_taped_device(
-                self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
-                C.byref(trials["_c"]) if trials is not None else None, int(row0), int(lists_in), C.byref(out), C.byref(tape["_c"]), int(tape_row0), st))
-            return out.value
-        if trials is not None:
-            self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_trials_device(
-                self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), C.byref(trials["_c"]), int(row0),
-                int(lists_in), C.byref(out), st))
-            return out.value
-        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_device(
-            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]), int(row0), int(lists_in),
-            C.byref(out), st))
+        structs = {"": (), "trials": (ref(trials),), "taped": (ref(trials),), "snapshot": (ref(trials), ref(snapshot)), "plans": (ref(trials), ref(plans))}[entry]
+        taped = (ref(tape), int(tape_row0)) if entry in ("taped", "plans") else ()
+        self._launch(dP.device, lambda st: getattr(self._lib, name)(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), ref(rec), ref(refill), *structs, int(row0), int(lists_in), C.byref(out), *taped, st))
         return out.value
 
     def walk_refill_snapshot(self, snapshot, snapshot_of, device=None):
@@ -1566,10 +1583,7 @@ class BatchSolver:
             raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_snapshot_device")
         dev = torch.device("cuda", self._device_index) if device is None else device
         hold = []
-        if not isinstance(snapshot_of, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
-            hold.append(torch.from_numpy(np.ascontiguousarray(snapshot_of, np.int32)))
-            snapshot_of = hold[-1].to(dev, non_blocking=True)
-        idx = snapshot_of.detach().to(dev, torch.int32).contiguous()
+        idx = _upload(snapshot_of, dev, torch.int32, hold).contiguous()    # (the host array is kept with the dict)
         assert idx.dim() == 1, "snapshot_of: expected [Q]"
         Q = int(idx.shape[0])
         ok = torch.full((Q,), -1, dtype=torch.int32, device=dev)
@@ -1583,25 +1597,8 @@ class BatchSolver:
         walk_refill_snapshot(...); None: cmpc_rollout_walk_refill_trials_device through the new entry point).  Six launches per tick: the restore goes
         between the refill and the front kernel, and a slot spawned at tick s runs tick t at the pool's tick + (t - s).  (A method of its own: the parameter
         list of rollout_walk_refill_device is pinned.)"""
-        if not hasattr(self._lib, "cmpc_rollout_walk_refill_snapshot_device"):
-            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_snapshot_device")
-        io = _capi.CmpcWalkIO()
-        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
-                                force_sample_time)
-        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
-        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
-        out = C.c_int(-1)
-        if snapshot is not None:
-            assert snapshot["trials"] == refill["trials"], "snapshot_of must have the queue's length"
-            assert snapshot["pool"]["max_contacts"] == lists[0].shape[2], "the pool's lists must have the walk's length"
-            assert snapshot["pool"]["_c"].tick == snapshot["tick"], "the pool was marked with another tick since walk_refill_snapshot"
-        if trials is not None:
-            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
-        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_snapshot_device(
-            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
-            C.byref(trials["_c"]) if trials is not None else None, C.byref(snapshot["_c"]) if snapshot is not None else None, int(row0), int(lists_in),
-            C.byref(out), st))
-        return out.value
+        return self._rollout_walk_refill("snapshot", tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0,
+                                         step, substeps, zmp_half_x, zmp_half_y, planner, force_sample_time, trials=trials, snapshot=snapshot)
 
     def walk_refill_plans(self, pool, plan_of, plan, pool_refs=None, planner=None, device=None):
         """A cmpc_walk_refill_plans as a dict: pool = (t [Pn, 2, M, 2] float64, pose [Pn, 2, M, 7] float32, n [Pn, 2] int32), the pool of footstep plans
@@ -1614,19 +1611,14 @@ class BatchSolver:
             raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_plans_device")
         dev = torch.device("cuda", self._device_index) if device is None else device
         hold = []
-
-        def up(a, dtype, npdtype):
-            if not isinstance(a, torch.Tensor):    # (uploaded without the host waiting for the copy; the host array is kept with the dict)
-                hold.append(torch.from_numpy(np.ascontiguousarray(a, npdtype)))
-                a = hold[-1].to(dev, non_blocking=True)
-            return a.detach().to(dev, dtype).contiguous()
-        pt, pp, pn = up(pool[0], torch.float64, np.float64), up(pool[1], torch.float32, np.float32), up(pool[2], torch.int32, np.int32)
+        up = lambda a, dtype: _upload(a, dev, dtype, hold).contiguous()    # (the host arrays are kept with the dict)
+        pt, pp, pn = up(pool[0], torch.float64), up(pool[1], torch.float32), up(pool[2], torch.int32)
         Pn, M = int(pt.shape[0]), int(plan[0].shape[2])
         assert Pn >= 1 and tuple(pt.shape) == (Pn, 2, M, 2) and tuple(pp.shape) == (Pn, 2, M, 7) and tuple(pn.shape) == (Pn, 2), \
             f"pool: (t [Pn, 2, {M}, 2], pose [Pn, 2, {M}, 7], n [Pn, 2])"
         for a, dt, shape in zip(plan, (torch.float64, torch.float32, torch.int32), ((2, M, 2), (2, M, 7), (2,))):
             assert a.is_cuda and a.dtype == dt and a.is_contiguous() and tuple(a.shape) == (self.batch,) + shape, "plan: the slots' (t, pose, n) on the device"
-        idx = up(plan_of, torch.int32, np.int32)
+        idx = up(plan_of, torch.int32)
         assert idx.dim() == 1, "plan_of: expected [Q]"
         Q = int(idx.shape[0])
         ok = torch.full((Q,), -1, dtype=torch.int32, device=dev)
@@ -1639,7 +1631,7 @@ class BatchSolver:
         if pool_refs is not None:
             assert planner is not None, "pool_refs need the walk's planner tuple (the slots' trajectories)"
             n = int(planner[0].shape[1])
-            refs = (up(pool_refs[0], torch.float32, np.float32), up(pool_refs[1], torch.float32, np.float32))
+            refs = (up(pool_refs[0], torch.float32), up(pool_refs[1], torch.float32))
             assert all(tuple(a.shape) == (Pn, n, 3) for a in refs), f"pool_refs: com and h [Pn, {n}, 3] (the knots of the slots' trajectories)"
             assert all(a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and tuple(a.shape) == (self.batch, n, 3) for a in planner[:2])
             c.dPoolCom, c.dPoolH = refs[0].data_ptr(), refs[1].data_ptr()
@@ -1653,23 +1645,9 @@ class BatchSolver:
         walk_refill_plans(...) over the same `plan` and `planner` tensors, which the walk WRITES; None: the taped / trials call through the new entry
         point).  One launch more per tick, the plan select, behind the refill: six, eight when taped.  (A method of its own: the parameter list of
         rollout_walk_refill_device is pinned.)"""
-        if not hasattr(self._lib, "cmpc_rollout_walk_refill_plans_device"):
-            raise RuntimeError("this build of libcmpc_hip has no cmpc_rollout_walk_refill_plans_device")
-        io = _capi.CmpcWalkIO()
-        io.tick = self._tick_io(plan, None, lists, ok, land, dState, None, dP, dX0, dX, dInfo, dState, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
-                                force_sample_time)
-        io.dListTB, io.dListPoseB, io.dListNB = (a.data_ptr() for a in lists_b)
-        io.plan_t_first = float(planner[3]) if planner is not None else 0.0
-        out = C.c_int(-1)
-        if plans is not None:
-            assert plans["trials"] == refill["trials"], "plan_of must have the queue's length"
-        if trials is not None:
-            assert trials["trials"] is None or trials["trials"] == refill["trials"], "trials: the per-trial arrays must have the queue's length"
-        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_refill_plans_device(
-            self._h, lists[0].shape[2], int(tick0), int(ticks), C.byref(io), C.byref(rec["_c"]), C.byref(refill["_c"]),
-            C.byref(trials["_c"]) if trials is not None else None, C.byref(plans["_c"]) if plans is not None else None, int(row0), int(lists_in),
-            C.byref(out), C.byref(tape["_c"]) if tape is not None else None, int(tape_row0), st))
-        return out.value
+        return self._rollout_walk_refill("plans", tick0, ticks, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo, dZmp, rec, refill, row0,
+                                         step, substeps, zmp_half_x, zmp_half_y, planner, force_sample_time, tape=tape, tape_row0=tape_row0, trials=trials,
+                                         plans=plans)
 
     def plan_fold_device(self, index, per_trial, pool_rows, out=None):
         """cmpc_rollout_plan_fold_device: out[p] = the sum of per_trial[q] over the trials with index[q] == p, in ascending q, without atomics (the bits do

@@ -159,7 +159,7 @@ def _queue(harmless=False):
 
 def _plain_walk(cfg, trials, com0, dcom0, h0, wrench):
     """walk_device(4, ...) of a batch of 4 that holds trials[b] in slot b, its wrench rows given as they are (walk_device itself builds them from a push):
-    WalkingRollout._walk_device's calls with the rows passed through"""
+    WalkingRollout._walk_live's calls with the rows passed through"""
     import torch
     ro = cm.rollout.WalkingRollout(cfg, B2)
     s, L, dev, dt = ro.solver, ro.L, ro.dev, cfg.sampling_time

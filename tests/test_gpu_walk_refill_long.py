@@ -72,7 +72,7 @@ def _rollout(cfg, B, opts, slots, trial_ticks):
 
 def _plain_walk(ro, trials, trial_ticks, com0, dcom0, h0, wrench):
     """walk_device(trial_ticks, ..., skip_ended=True) of a batch that holds trials[b] in slot b, its wrench rows given as they are (walk_device itself builds
-    them from a push): WalkingRollout._walk_device's calls with the rows passed through.  -> the record, X, P, state and BOTH list sets on the host (tick i
+    them from a push): WalkingRollout._walk_live's calls with the rows passed through.  -> the record, X, P, state and BOTH list sets on the host (tick i
     wrote set i % 2), and the plan"""
     import torch
     B = len(trials)

@@ -1,6 +1,6 @@
 """GPU: the refill walk taped, its tape regrouped by trial, and every trial's gradient (include/cmpc.h, cmpc_rollout_walk_refill_taped_device and
 cmpc_walk_tape_regroup; WalkingRollout.walk_device_refill_taped, refill_trial_walk, backward_device_refill).  Who sits where comes from the assignment model
-(tests/walk_refill_ref.py).  Every trial is held, to the bit, to a taped walk of its own -- WalkingRollout._walk_device's calls (cmpc_rollout_walk_mismatch_device
+(tests/walk_refill_ref.py).  Every trial is held, to the bit, to a taped walk of its own -- WalkingRollout._walk_live's calls (cmpc_rollout_walk_mismatch_device
 with a tape, cold_first = 1, tick_first = 0, the ended problems out of the launches) with the trial's wrench rows passed through, on a roll-out of the same batch
 size, factor storage and options that holds it in the slot the model gives it with set_models_device's row `slot` the trial's model -- and every trial's
 gradient to backward_device on that walk.  Every check is equality of bits or of integers.
@@ -31,7 +31,7 @@ def _host(d):
 
 def _own_taped_walk(ro, trials, ticks, scenario, mm):
     """walk_device_taped(ticks, ..., mismatch=<the trials' columns>, skip_ended=True) of a batch that holds trials[b] in slot b, its wrench rows given as
-    they are (walk_device_taped itself builds them from a push, and a NaN row is no push): WalkingRollout._walk_device's calls with the rows passed
+    they are (walk_device_taped itself builds them from a push, and a NaN row is no push): WalkingRollout._walk_live's calls with the rows passed
     through.  -> walk_device_taped's dict: the record, and the tape with what backward_device and forward_sensitivity_device_mismatch read of it"""
     import torch
     com0, dcom0, h0, wrench = scenario

@@ -116,7 +116,7 @@ if args.walk_only:
 
 
 def plain_walks(ro, B, state0, wrench, hidden=None):
-    """the queue as Q / B walks of TT ticks, ended problems out of the launches: WalkingRollout._walk_device's calls with the wrench rows passed through;
+    """the queue as Q / B walks of TT ticks, ended problems out of the launches: WalkingRollout._walk_live's calls with the wrench rows passed through;
     hidden [TT, Q, 6] (--reach-max): the walks run under their columns of the hidden pushes and under the reach limit"""
     s, L, dev, dt = ro.solver, ro.L, ro.dev, cfg.sampling_time
     z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
