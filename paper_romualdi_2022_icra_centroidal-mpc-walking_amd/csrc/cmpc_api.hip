@@ -1,8 +1,6 @@
-// C ABI of libcmpc_hip.so (include/cmpc.h): handle management, host<->device plumbing, launches.
-#include "../../include/cmpc.h"
-#include "cmpc_contacts.h"
-#include "cmpc_device.h"
-#include "cmpc_launch.h"
+// C ABI of libcmpc_hip.so (include/cmpc.h): handle management, host<->device plumbing, launches.  The roll-out layer's entry points are in
+// cmpc_api_rollout.hip and cmpc_api_walk_grad.hip; the helpers the three files share are defined here and there and declared in cmpc_handle.h.
+#include "cmpc_handle.h"
 
 #include <algorithm>
 #include <cmath>
@@ -13,95 +11,137 @@
 #include <string>
 #include <vector>
 
-struct cmpc_handle_s {
-    cmpc_config cfg;
-    CmpcLayout L;
-    int B = 0, device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    bool timing = true;          // record the event pair around every solve launch (cmpc_set_timing)
-    float* dP = nullptr;
-    float* dX0 = nullptr;
-    float* dX = nullptr;
-    float* dInfo = nullptr;
-    CmpcConsts* dConsts = nullptr;
-    double hExpK[CMPC_NMAX + 1];  // exp(-k), k = 0..N: the one transcendental of a model's record, computed once here (cmpc_consts_apply_model)
-    double* dExpK = nullptr;      // ... and its device copy (cmpc_set_models_device)
-    CmpcConsts* dModels = nullptr;  // [B] per-problem records (cmpc_set_models*), allocated on first use
-    bool models_set = false;      // launches read dModels[b] instead of dConsts
-    float* dScratch = nullptr;   // factor storage when the horizon's LDS image exceeds 160 KiB
-    float* dBox = nullptr;       // bounding-box limits upper[2][3] | lower[2][3] of the schedule sampler
-    float* dDuals = nullptr;     // the dual record of the last solve [B][NS (N+1) + 2 NI N] (cmpc_set_multiplier_output, or the diagnostic knob below)
-    bool mult_out = false;       // cmpc_set_multiplier_output: every solve writes dDuals
-    const int* dEnded = nullptr; // cmpc_set_ended_device: the caller's [B] words, read by the launches on the device (>= 0: the problem is left out); null: off
-    bool limits_set = false;     // cmpc_set_walk_limits: every record launch evaluates `limits` (the caller's struct, copied)
-    cmpc_walk_limits limits{};
-    float* dLamG = nullptr;      // [B][n_g] staging of cmpc_get_multipliers (allocated on first use)
-    double* dSensWs = nullptr;   // workspace of the solution sensitivities, min(B, CMPC_SENS_SUB_BATCH) problems (allocated on first use)
-    hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
-    double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
-    int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
-    char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp[_rot]_device (allocated on first use, sized for both): model gradients of the solve and of
-                                 // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] | the plant's gradient on the
-                                 // hidden wrench [B][6] and on the force gain [B] (the mismatch entry) (double) | gX[B][n_x] | gP of
-                                 // the solve [B][n_p] | gP of the plant [B][n_p] (float) | the tick's ok words [B] (int)
-    hipEvent_t tick_ev = nullptr; // recorded after the last kernel of a tick VJP or JVP: the next one, on any stream, waits for it (one workspace each)
-    char* dTickJvpWs = nullptr;  // workspace of cmpc_rollout_tick_jvp_device for tick_jvp_cols columns per problem (allocated on first use, grown when a larger k
-    int tick_jvp_cols = 0;       // arrives): rotation direction [B][k][2][N][3] | its stage 0 [B][k][2][3] | a zero state direction [B][k][9] (double) |
-                                 // dx [B][k][n_x] | the assembled p direction [B][k][n_p] (float) | the tick's ok words [B] (int)
-    char* dWalkWs = nullptr;     // workspace of cmpc_rollout_walk_vjp[_rot]_device for lists of walk_ws_M contacts (allocated on first use, grown when a larger
-    int walk_ws_M = 0;           // max_contacts arrives): the tick's dGradState [B][9] | its dGradPrevList | its dGradPrevListRot [B][2][M][3] each (double) |
-                                 // the gated dGradX row [B][n_x] | the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
-    char* dWalkJvpWs = nullptr;  // workspace of cmpc_rollout_walk_jvp_device for walk_jvp_cols columns and lists of walk_jvp_M contacts (allocated on first use,
-    int walk_jvp_cols = 0;       // grown when a larger k or max_contacts arrives): the second buffers of the list directions, positions and orientations
-    int walk_jvp_M = 0;          // [B][k][2][M][3] each (double) | the tick's dTickSens [B][CMPC_SENS] (float) | the gated dOk [B] (int)
-    size_t snap_cap = 0;         // doubles allocated at dSnapT     // costates, slacks, multipliers of the last solve (warm start with duals: allocated by cmpc_create when the developer knob CMPC_WARM_DUALS is set)
-    int warm_duals = 0;          // 0: primal shift only (default); 1: + costates; 2: + multipliers
-    float hBox[12] = {0};
-    bool box_set = false;
-    long long scratch_stride = 0;
-    std::vector<float> hP, hX0;  // host staging for the class-shaped setters
-    bool have_solution = false, x0_set = false;
-    // pinned host mirror of the handle's solution and status words, filled by cmpc_advance in the same synchronisation as the solve (the class surface's
-    // getOutput / cmpc_get_solution then cost no GPU call: a pageable device-to-host copy of their own was 25 us of a 0.83 ms tick at B = 1)
-    float* hXpin = nullptr;
-    float* hInfoPin = nullptr;
-    bool hX_valid = false;
-    bool warm = false;           // class path only (cmpc_set_initial_guess(.., 1) -> cmpc_advance): the handle's own dX0 is a shifted previous solution
-    double mu_warm = 1e-2, floor_warm = 1e-2;  // measured: 1e-2 saves 35 % (standing) / 15 % (walking) of the iterations; 1e-4 can stall
-    int warm_budget = 14, warm_no_restart = 0;  // cmpc_set_warm_policy (CmpcParams); 14: measured on the walking roll-out (profiles/r03_walking_rollout.txt)
-    bool force_warm = false;     // developer knob CMPC_FORCE_WARM (read once, at cmpc_create)
-    float mu_adapt = 3.5f;       // cold starts: mu0 = clamp(mu_adapt ep0^2, 0.03, 0.5) (developer knob CMPC_MU_ADAPT, read once)
-    size_t lds = 0;
-    std::string err;
-};
-
 static thread_local std::string g_err;
 
-static int fail(cmpc_handle h, int code, const std::string& msg)
+static void fill_consts(cmpc_handle h, CmpcConsts& q)
+{
+    const cmpc_config& c = h->cfg;
+    std::memset(&q, 0, sizeof(q));
+    q.N = c.horizon; q.max_iter = c.max_iterations;
+    q.exact_hessian = c.exact_hessian; q.final_extrap = c.final_extrapolation;
+    q.tail_stages = c.tail_stages; q.tail_iters = c.tail_iterations; q.tail_trigger = (float)c.tail_trigger;
+    q.dt = (float)c.sampling_time; q.grav = (float)c.gravity;
+    q.tol = (float)c.tolerance; q.step_tol = (float)c.step_tolerance; q.mu_init = (float)c.mu_init; q.mu_min = (float)c.mu_min;
+    // the model: friction, weights (wz2: w_z(k) = (w_cz/2)(1+exp(-k))), corners, and the Levenberg shift reg: 5e-5 of the smallest cost curvature
+    // (2 w_rate).  The shift does not move the fixed point (the right-hand side is exact); it keeps the stage Hessians factorisable in float32 along
+    // directions the cost does not see (measured on MI355X: 1e-5..1e-2 all converge in the same number of iterations, 1e-1 doubles it)
+    {
+        cmpc_model m;
+        cmpc_model_from_config(&c, &m);
+        cmpc_consts_apply_model(q, m, h->hExpK);
+#ifdef CMPC_PROFILE
+        if (const char* e = std::getenv("CMPC_REG")) q.reg = (float)std::atof(e);
+#endif
+    }
+    // Mehrotra's sigma = (mu_aff/mu)^3 can ask for a 1000-fold barrier decrease in one step; the linearisation
+    // does not hold that far and the blocked step costs the problem 3-6 extra iterations.  A floor of 0.03
+    // costs +0.3 iterations on the mean of config 2 and removes the tail (max 11 -> 8 of 4096 problems; config 3:
+    // mean 8.60 -> 8.49, max 14 -> 12), and a batch is as slow as its slowest problem.
+    q.sigma_min = 0.03f;
+#ifdef CMPC_PROFILE
+    if (const char* e = std::getenv("CMPC_SIGMA_MIN")) q.sigma_min = (float)std::atof(e);
+    if (const char* e = std::getenv("CMPC_HWID_PROBE")) q.hwid_probe = std::atoi(e);
+#endif
+}
+
+namespace cmpc_host {
+
+int fail(cmpc_handle h, int code, const std::string& msg)
 {
     if (h) h->err = msg;
     g_err = msg;
     return code;
 }
-#define HIPCHK(h, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(h, CMPC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));  \
-    } while (0)
 
 // the stream of a call: the caller's, or the handle's
-static hipStream_t stream_of(cmpc_handle h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
+hipStream_t stream_of(cmpc_handle h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
 
 // a launcher's return code as the entry point's: CMPC_OK, or CMPC_ERR_HIP with "<what> launch: <the HIP error string>"
-static int launch_status(cmpc_handle h, const char* what, int rc)
+int launch_status(cmpc_handle h, const char* what, int rc)
 {
     return rc == 0 ? CMPC_OK : fail(h, CMPC_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc));
 }
 
-static void fill_consts(cmpc_handle h, CmpcConsts& q);
+// the corners the plant step reads: problem 0's, and the distance in floats to the next problem's (0: one set for the batch).  Device pointer arithmetic only.
+const float* model_corners(cmpc_handle h) { return h->models_set ? h->dModels->corners : h->dConsts->corners; }
+int corners_stride(cmpc_handle h) { return h->models_set ? (int)(sizeof(CmpcConsts) / sizeof(float)) : 0; }
+
+void fill_params(cmpc_handle h, CmpcParams& p)
+{
+    std::memset(&p, 0, sizeof(p));
+    p.kc = h->models_set ? h->dModels : h->dConsts; p.N = h->cfg.horizon; p.B = h->B;
+    p.kc_per_problem = h->models_set ? 1 : 0;
+    p.scratch = h->dScratch; p.scratch_stride = h->scratch_stride;
+    // cold start: a fixed initial barrier parameter if the configuration names one, else per problem
+    // mu0 = clamp(3.5 ep0^2, 0.03, 0.5) from the initial primal infeasibility ep0 (measured on 4096-problem batches:
+    // config 2 wants ~0.03, config 3 ~0.3; the rule cuts the slowest problem of a 256-batch by ~0.7 iterations)
+    p.mu_init = h->cfg.mu_init > 0 ? (float)h->cfg.mu_init : 0.1f;
+    p.mu_adapt = h->cfg.mu_init > 0 ? 0.f : h->mu_adapt;
+    p.t_floor = 1e-2f;
+    p.warm_budget = h->warm_budget; p.warm_no_restart = h->warm_no_restart;
+    p.duals = (h->mult_out || h->warm_duals) ? h->dDuals : nullptr; p.warm_duals = h->warm_duals;
+    p.ended = h->dEnded;
+    p.cold_mu_init = p.mu_init; p.cold_t_floor = p.t_floor; p.cold_mu_adapt = p.mu_adapt;   // (what a warm launch overwrites below; read only with p.start set)
+}
+
+// start / tick: the refill walk's per-problem first tick inside a warm launch (CmpcParams.start), or null
+int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm, const int* start, int tick)
+{
+    if (!h || !dP || !dX0 || !dX) return fail(h, CMPC_ERR_ARG, "cmpc_solve_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = stream_of(h, stream);
+    CmpcParams p;
+    fill_params(h, p);
+    p.P = dP; p.X0 = dX0; p.X = dX; p.info = dInfo ? dInfo : h->dInfo;
+    p.start = start; p.tick = tick;
+    if (warm || h->force_warm) {  // dX0 is a previous solution shifted by one knot: start near the central path
+        p.mu_init = (float)h->mu_warm; p.mu_adapt = 0.f; p.t_floor = (float)h->floor_warm; p.warm = 1;
+    }
+    if (h->timing) HIPCHK(h, hipEventRecord(h->ev0, st));
+    int rc = cmpc_launch_solver(&p, h->lds, st);
+    if (const int err = launch_status(h, "solver", rc)) return err;
+    if (h->timing) HIPCHK(h, hipEventRecord(h->ev1, st));
+    h->timed = h->timing;
+    return CMPC_OK;
+}
+
+// what both forms of the record refuse in a cmpc_walk_limits; null: nothing.  (height_min > height_max is false when either is NaN: a limit that is off)
+const char* limits_refusal(const cmpc_walk_limits* lim)
+{
+    if (lim->height_min > lim->height_max) return "height_min above height_max";
+    if (lim->dMeasures && lim->rows < 1) return "dMeasures with rows < 1";
+    return nullptr;
+}
+
+// forceSampleTime (CentroidalMPCBlock.cpp:586-592): dt in integer nanoseconds, or 0 if it is not a usable grid
+long long snap_dt_ns(double dt)
+{
+    if (!(dt > 0) || !(dt < CMPC_TIME_NEVER)) return 0;
+    const long long dt_ns = llround(dt * 1e9);
+    return dt_ns >= 1 ? dt_ns : 0;
+}
+
+// the bounding boxes of the two contacts on the device (uploaded when they change)
+int upload_box(cmpc_handle h, const float* box_upper, const float* box_lower, hipStream_t st)
+{
+    float box[12];
+    std::memcpy(box, box_upper, sizeof(float) * 6);
+    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
+    if (!h->box_set || std::memcmp(box, h->hBox, sizeof(box)) != 0) {
+        std::memcpy(h->hBox, box, sizeof(box));
+        HIPCHK(h, hipMemcpyAsync(h->dBox, h->hBox, sizeof(box), hipMemcpyHostToDevice, st));
+        h->box_set = true;
+    }
+    return CMPC_OK;
+}
+
+int ensure_models(cmpc_handle h)
+{
+    if (!h->dModels) HIPCHK(h, hipMalloc(&h->dModels, sizeof(CmpcConsts) * (size_t)h->B));
+    return CMPC_OK;
+}
+
+}  // namespace cmpc_host
 
 extern "C" {
 
@@ -281,81 +321,6 @@ int cmpc_destroy(cmpc_handle h)
     return CMPC_OK;
 }
 
-static void fill_consts(cmpc_handle h, CmpcConsts& q)
-{
-    const cmpc_config& c = h->cfg;
-    std::memset(&q, 0, sizeof(q));
-    q.N = c.horizon; q.max_iter = c.max_iterations;
-    q.exact_hessian = c.exact_hessian; q.final_extrap = c.final_extrapolation;
-    q.tail_stages = c.tail_stages; q.tail_iters = c.tail_iterations; q.tail_trigger = (float)c.tail_trigger;
-    q.dt = (float)c.sampling_time; q.grav = (float)c.gravity;
-    q.tol = (float)c.tolerance; q.step_tol = (float)c.step_tolerance; q.mu_init = (float)c.mu_init; q.mu_min = (float)c.mu_min;
-    // the model: friction, weights (wz2: w_z(k) = (w_cz/2)(1+exp(-k))), corners, and the Levenberg shift reg: 5e-5 of the smallest cost curvature
-    // (2 w_rate).  The shift does not move the fixed point (the right-hand side is exact); it keeps the stage Hessians factorisable in float32 along
-    // directions the cost does not see (measured on MI355X: 1e-5..1e-2 all converge in the same number of iterations, 1e-1 doubles it)
-    {
-        cmpc_model m;
-        cmpc_model_from_config(&c, &m);
-        cmpc_consts_apply_model(q, m, h->hExpK);
-#ifdef CMPC_PROFILE
-        if (const char* e = std::getenv("CMPC_REG")) q.reg = (float)std::atof(e);
-#endif
-    }
-    // Mehrotra's sigma = (mu_aff/mu)^3 can ask for a 1000-fold barrier decrease in one step; the linearisation
-    // does not hold that far and the blocked step costs the problem 3-6 extra iterations.  A floor of 0.03
-    // costs +0.3 iterations on the mean of config 2 and removes the tail (max 11 -> 8 of 4096 problems; config 3:
-    // mean 8.60 -> 8.49, max 14 -> 12), and a batch is as slow as its slowest problem.
-    q.sigma_min = 0.03f;
-#ifdef CMPC_PROFILE
-    if (const char* e = std::getenv("CMPC_SIGMA_MIN")) q.sigma_min = (float)std::atof(e);
-    if (const char* e = std::getenv("CMPC_HWID_PROBE")) q.hwid_probe = std::atoi(e);
-#endif
-}
-
-// the corners the plant step reads: problem 0's, and the distance in floats to the next problem's (0: one set for the batch).  Device pointer arithmetic only.
-static const float* model_corners(cmpc_handle h) { return h->models_set ? h->dModels->corners : h->dConsts->corners; }
-static int corners_stride(cmpc_handle h) { return h->models_set ? (int)(sizeof(CmpcConsts) / sizeof(float)) : 0; }
-
-static void fill_params(cmpc_handle h, CmpcParams& p)
-{
-    std::memset(&p, 0, sizeof(p));
-    p.kc = h->models_set ? h->dModels : h->dConsts; p.N = h->cfg.horizon; p.B = h->B;
-    p.kc_per_problem = h->models_set ? 1 : 0;
-    p.scratch = h->dScratch; p.scratch_stride = h->scratch_stride;
-    // cold start: a fixed initial barrier parameter if the configuration names one, else per problem
-    // mu0 = clamp(3.5 ep0^2, 0.03, 0.5) from the initial primal infeasibility ep0 (measured on 4096-problem batches:
-    // config 2 wants ~0.03, config 3 ~0.3; the rule cuts the slowest problem of a 256-batch by ~0.7 iterations)
-    p.mu_init = h->cfg.mu_init > 0 ? (float)h->cfg.mu_init : 0.1f;
-    p.mu_adapt = h->cfg.mu_init > 0 ? 0.f : h->mu_adapt;
-    p.t_floor = 1e-2f;
-    p.warm_budget = h->warm_budget; p.warm_no_restart = h->warm_no_restart;
-    p.duals = (h->mult_out || h->warm_duals) ? h->dDuals : nullptr; p.warm_duals = h->warm_duals;
-    p.ended = h->dEnded;
-    p.cold_mu_init = p.mu_init; p.cold_t_floor = p.t_floor; p.cold_mu_adapt = p.mu_adapt;   // (what a warm launch overwrites below; read only with p.start set)
-}
-
-// start / tick: the refill walk's per-problem first tick inside a warm launch (CmpcParams.start), or null
-static int solve_device_impl(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream, bool warm, const int* start = nullptr,
-                             int tick = 0)
-{
-    if (!h || !dP || !dX0 || !dX) return fail(h, CMPC_ERR_ARG, "cmpc_solve_device: null argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream_of(h, stream);
-    CmpcParams p;
-    fill_params(h, p);
-    p.P = dP; p.X0 = dX0; p.X = dX; p.info = dInfo ? dInfo : h->dInfo;
-    p.start = start; p.tick = tick;
-    if (warm || h->force_warm) {  // dX0 is a previous solution shifted by one knot: start near the central path
-        p.mu_init = (float)h->mu_warm; p.mu_adapt = 0.f; p.t_floor = (float)h->floor_warm; p.warm = 1;
-    }
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev0, st));
-    int rc = cmpc_launch_solver(&p, h->lds, st);
-    if (const int err = launch_status(h, "solver", rc)) return err;
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev1, st));
-    h->timed = h->timing;
-    return CMPC_OK;
-}
-
 int cmpc_solve_device(cmpc_handle h, const float* dP, const float* dX0, float* dX, float* dInfo, void* stream)
 {
     return solve_device_impl(h, dP, dX0, dX, dInfo, stream, false);
@@ -379,14 +344,6 @@ int cmpc_set_ended_device(cmpc_handle h, const int* dEndTick)
     if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_set_ended_device: null handle");
     h->dEnded = dEndTick;   // (only the pointer is kept: the words are read on the device, by each launch when it runs)
     return CMPC_OK;
-}
-
-// what both forms of the record refuse in a cmpc_walk_limits; null: nothing.  (height_min > height_max is false when either is NaN: a limit that is off)
-static const char* limits_refusal(const cmpc_walk_limits* lim)
-{
-    if (lim->height_min > lim->height_max) return "height_min above height_max";
-    if (lim->dMeasures && lim->rows < 1) return "dMeasures with rows < 1";
-    return nullptr;
 }
 
 int cmpc_set_walk_limits(cmpc_handle h, const cmpc_walk_limits* lim)
@@ -1218,14 +1175,6 @@ int cmpc_contacts_merge_device(cmpc_handle h, int max_contacts, double now, cons
     return launch_status(h, "contact merge", rc);
 }
 
-// forceSampleTime (CentroidalMPCBlock.cpp:586-592): dt in integer nanoseconds, or 0 if it is not a usable grid
-static long long snap_dt_ns(double dt)
-{
-    if (!(dt > 0) || !(dt < CMPC_TIME_NEVER)) return 0;
-    const long long dt_ns = llround(dt * 1e9);
-    return dt_ns >= 1 ? dt_ns : 0;
-}
-
 int cmpc_contacts_force_sample_time(int batch, int max_contacts, double dt, const double* t, const int* n, double* out_t, int* ok)
 {
     const long long dt_ns = snap_dt_ns(dt);
@@ -1303,20 +1252,6 @@ int cmpc_contacts_orientation_vjp_device(cmpc_handle h, int max_contacts, double
     return launch_status(h, "contact orientation VJP", rc);
 }
 
-// the bounding boxes of the two contacts on the device (uploaded when they change)
-static int upload_box(cmpc_handle h, const float* box_upper, const float* box_lower, hipStream_t st)
-{
-    float box[12];
-    std::memcpy(box, box_upper, sizeof(float) * 6);
-    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
-    if (!h->box_set || std::memcmp(box, h->hBox, sizeof(box)) != 0) {
-        std::memcpy(h->hBox, box, sizeof(box));
-        HIPCHK(h, hipMemcpyAsync(h->dBox, h->hBox, sizeof(box), hipMemcpyHostToDevice, st));
-        h->box_set = true;
-    }
-    return CMPC_OK;
-}
-
 int cmpc_contacts_sample_device(cmpc_handle h, int max_contacts, double now, const double* dT, const float* dPose, const int* dN,
                                 const float* box_upper, const float* box_lower, float* dP, int* dLand, void* stream)
 {
@@ -1355,1807 +1290,6 @@ int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, v
     int rc = cmpc_launch_warm_shift(&p, dXprev, dX0, stream_of(h, stream));
     if (rc != 0) return fail(h, CMPC_ERR_HIP, "warm-start shift launch failed");
     return CMPC_OK;   // (no state on the handle: the caller solves from dX0 with cmpc_solve_device_warm)
-}
-
-// ---- 8f-1 .. 8f-4 chained: one tick of the receding-horizon loop in one call (include/cmpc.h): the steps of the entry points above in the reference's order, with the
-// same argument checks, as THREE launches -- everything in front of the solve, the solve, everything behind it (cmpc_tick_pre_kernel / cmpc_tick_post_kernel call the same
-// per-problem functions as the single kernels; results identical to the last bit). ----
-// cold: the solve starts from cmpc_cold_start_kernel, launched between the front kernel and the solve (the first tick of cmpc_rollout_walk_device; needs
-// warm == 0).  box_done: the caller has uploaded the box already.
-// m: the plant mismatch (include/cmpc.h, cmpc_plant_mismatch) with `tick` selecting its rows, or null -- then every launch is the one this function always queued
-static int mismatch_check(cmpc_handle h, const char* who, const cmpc_plant_mismatch* m)
-{
-    if (m && (m->hidden_ticks < 0 || m->noise_ticks < 0 || (m->dHiddenWrench && m->hidden_ticks == 0) || (m->dStateNoise && m->noise_ticks == 0)))
-        return fail(h, CMPC_ERR_ARG, std::string(who) + ": bad mismatch (a negative count, or a schedule with no rows)");
-    return CMPC_OK;
-}
-
-// the rows of tick number `tick`: a schedule's row inside its range, else null (the term is then not applied: a select on the host, no add of zero)
-static void mismatch_rows(const cmpc_plant_mismatch* m, int B, int tick, const float** hidden, const float** noise, const float** gain)
-{
-    *hidden = nullptr; *noise = nullptr; *gain = nullptr;
-    if (!m) return;
-    const long long r = (long long)tick - m->tick_first;
-    if (m->dHiddenWrench && r >= 0 && r < m->hidden_ticks) *hidden = m->dHiddenWrench + (size_t)r * B * 6;
-    if (m->dStateNoise && r >= 0 && r < m->noise_ticks) *noise = m->dStateNoise + (size_t)r * B * 9;
-    *gain = m->dForceGain;
-}
-
-static int rollout_tick_impl(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream, bool cold, bool box_done,
-                             int tick = 0, const cmpc_plant_mismatch* m = nullptr)
-{
-    if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: null argument");
-    if (m && tick < 0) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_mismatch_device: negative tick number");
-    {
-        const int mrc = mismatch_check(h, "cmpc_rollout_tick_mismatch_device", m);
-        if (mrc != CMPC_OK) return mrc;
-    }
-    const float *mm_hidden, *mm_noise, *mm_gain;
-    mismatch_rows(m, h->B, tick, &mm_hidden, &mm_noise, &mm_gain);
-    if (!io->dLand || !io->dInfo) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: dLand and dInfo are needed");
-    const bool merge = io->dPrevT || io->dPrevPose || io->dPrevN;
-    if (merge && (io->dPrevT == io->dListT || io->dPrevPose == io->dListPose || io->dPrevN == io->dListN))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: the merged lists must not alias the previous tick's");
-    if (merge && (!io->dPlanT || !io->dPlanPose || !io->dPlanN || !io->dPrevT || !io->dPrevPose || !io->dPrevN))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: the merge needs the planner's and the previous tick's lists");
-    if (max_contacts < 1 || !io->dListT || !io->dListPose || !io->dListN || !io->box_upper || !io->box_lower || !io->dState || !io->dP || !io->dX0 || !io->dX ||
-        !io->dStateOut || !(io->plant_step > 0) || io->plant_substeps < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: bad argument");
-    if ((io->dPlanCom || io->dPlanH) && (!io->dPlanCom || !io->dPlanH || io->plan_knots < 2 || !(io->plan_dt > 0) || !(io->robot_mass > 0)))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: bad planner trajectory");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream_of(h, stream);
-    const int* const ended = h->dEnded;   // cmpc_set_ended_device: every launch of the tick leaves out the problems it names (the solve reads it through fill_params)
-    long long dt_ns = 0;
-    if (io->force_sample_time) {
-        dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_device: force_sample_time needs a sampling time of at least 1 ns");
-    }
-    int rc = box_done ? CMPC_OK : upload_box(h, io->box_upper, io->box_lower, st);
-    if (rc != CMPC_OK) return rc;
-    // forceSampleTime: inside the front kernel when the lists fit its LDS stage (cmpc_tick_pre_kernel, M <= 16); else one launch of the standalone kernel
-    // in front of it -- the planner's lists into the handle's dSnapT (merge ticks) or the caller's lists in place (first tick), per-foot status into dSnapOk
-    const double* plan_t = io->dPlanT;
-    const int* snap_ok = nullptr;
-    if (dt_ns > 0 && max_contacts > 16) {
-        const size_t need = (size_t)h->B * 2 * max_contacts * 2;
-        if (merge && need > h->snap_cap) {
-            HIPCHK(h, hipStreamSynchronize(st));
-            hipFree(h->dSnapT);
-            h->dSnapT = nullptr; h->snap_cap = 0;
-            HIPCHK(h, hipMalloc(&h->dSnapT, sizeof(double) * need));
-            h->snap_cap = need;
-        }
-        if (!h->dSnapOk) HIPCHK(h, hipMalloc(&h->dSnapOk, sizeof(int) * 2 * (size_t)h->B));
-        const int lrc = merge ? cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dPlanT, io->dPlanN, h->dSnapT, h->dSnapOk, 1, ended, st)
-                              : cmpc_launch_force_sample_time(h->B, max_contacts, dt_ns, io->dListT, io->dListN, io->dListT, h->dSnapOk, 1, ended, st);
-        if (const int err = launch_status(h, "tick (forceSampleTime)", lrc)) return err;
-        if (merge) plan_t = h->dSnapT;
-        snap_ok = h->dSnapOk;
-    }
-    int lrc = cmpc_launch_tick_pre(h->B, h->cfg.horizon, max_contacts, h->cfg.sampling_time, now, merge ? 1 : 0, plan_t, io->dPlanPose, io->dPlanN, io->dPrevT,
-                                   io->dPrevPose, io->dPrevN, io->dListT, io->dListPose, io->dListN, io->dOk, io->dLand, h->dBox, io->dState, io->dWrench, io->dP,
-                                   warm ? io->dX : nullptr, io->dX0, io->dPlanCom, io->dPlanH, io->plan_knots, io->plan_dt, io->plan_t_offset, io->robot_mass,
-                                   io->com_height, dt_ns, snap_ok, ended, mm_noise, st);
-    if (const int err = launch_status(h, "tick (front)", lrc)) return err;
-    if (cold) {
-        lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), io->dP, io->dX0, ended, st);
-        if (const int err = launch_status(h, "tick (cold start)", lrc)) return err;
-    }
-    rc = solve_device_impl(h, io->dP, io->dX0, io->dX, io->dInfo, stream, warm != 0);
-    if (rc != CMPC_OK) return rc;
-    lrc = cmpc_launch_tick_post(h->B, h->cfg.horizon, max_contacts, now, (float)h->cfg.gravity, model_corners(h), corners_stride(h), io->dX, io->dP, io->dState, io->dStateOut, io->dZmp,
-                                (float)io->plant_step, io->plant_substeps, (float)io->zmp_half_x, (float)io->zmp_half_y, io->dLand, io->dListT, io->dListPose,
-                                io->dListN, ended, mm_hidden, mm_gain, st);
-    return launch_status(h, "tick (back)", lrc);
-}
-
-int cmpc_rollout_tick_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, void* stream)
-{
-    return rollout_tick_impl(h, max_contacts, now, warm, io, stream, false, false);
-}
-
-int cmpc_rollout_tick_mismatch_device(cmpc_handle h, int max_contacts, double now, int warm, const cmpc_tick_io* io, int tick, const cmpc_plant_mismatch* m,
-                                      void* stream)
-{
-    return rollout_tick_impl(h, max_contacts, now, warm, io, stream, false, false, tick, m);
-}
-
-// ---- the walk (include/cmpc.h): the record behind a tick, the cold start as a kernel, and `ticks` ticks queued in one call ----
-static bool record_args(int N, int B, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
-                        const float* state_out, const float* zmp, const float* box, const cmpc_walk_record* rec, CmpcRecordArgs& a)
-{
-    if (N < 1 || B < 1 || !X || !P || !info || !land || !state_out || !box || !rec || row < 0 || row >= rec->rows || (rec->dZmp && !zmp)) return false;
-    if (!rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin) return false;
-    a = CmpcRecordArgs{N, B, tick, row, rec->stop_mask, X, P, info, ok, land, state_out, zmp, box, rec->dCom, rec->dZmp, rec->dLand, rec->dLandingOffset,
-                       rec->dIterations, rec->dCode, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
-                       rec->dBoxSlackMin};
-    return true;
-}
-
-int cmpc_rollout_record(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
-                        const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec)
-{
-    float box[12];
-    CmpcRecordArgs a;
-    if (!box_upper || !box_lower || !record_args(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box, rec, a))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record: bad argument");
-    std::memcpy(box, box_upper, sizeof(float) * 6);
-    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
-    int st[6] = {0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < batch; ++b) {
-        int t[5];
-        cmpc_record_problem<false>(a, CmpcLimitArgs{}, b, t);
-        st[0] += t[0]; st[1] += t[1]; st[2] += t[2]; st[3] = std::max(st[3], t[3]); st[4] += t[4];
-    }
-    if (rec->dStats) std::memcpy(rec->dStats + 6 * (size_t)row, st, sizeof(st));
-    return CMPC_OK;
-}
-
-// the limits as the record takes them, row `row` of the measures trace
-static CmpcLimitArgs limit_args(const cmpc_walk_limits& lim, int B, int row, const float* corners, int stride, double gravity)
-{
-    return CmpcLimitArgs{lim.height_min, lim.height_max, lim.reach_max, lim.margin_min, lim.track_max, gravity, corners, stride,
-                         lim.dMeasures ? lim.dMeasures + (size_t)row * B * CMPC_WALK_MEASURES : nullptr, lim.dExtremes};
-}
-
-int cmpc_rollout_record_limits(int horizon, int batch, int tick, int row, const float* X, const float* P, const float* info, const int* ok, const int* land,
-                               const float* state_out, const float* zmp, const float* box_upper, const float* box_lower, const cmpc_walk_record* rec,
-                               const cmpc_walk_limits* lim, const float* corners, int corners_stride, double gravity)
-{
-    if (!lim) return cmpc_rollout_record(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box_upper, box_lower, rec);
-    float box[12];
-    CmpcRecordArgs a;
-    if (!box_upper || !box_lower || !record_args(horizon, batch, tick, row, X, P, info, ok, land, state_out, zmp, box, rec, a))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: bad argument");
-    if (horizon < 2 || !corners || corners_stride < 0 || !(gravity > 0)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: bad argument");
-    if (const char* why = limits_refusal(lim)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_record_limits: ") + why);
-    if (lim->dMeasures && row >= lim->rows) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_record_limits: the measures trace has too few rows");
-    std::memcpy(box, box_upper, sizeof(float) * 6);
-    std::memcpy(box + 6, box_lower, sizeof(float) * 6);
-    const CmpcLimitArgs lm = limit_args(*lim, batch, row, corners, corners_stride, gravity);
-    int st[6] = {0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < batch; ++b) {
-        int t[6];
-        cmpc_record_problem<true>(a, lm, b, t);
-        st[0] += t[0]; st[1] += t[1]; st[2] += t[2]; st[3] = std::max(st[3], t[3]); st[4] += t[4]; st[5] += t[5];
-    }
-    if (rec->dStats) std::memcpy(rec->dStats + 6 * (size_t)row, st, sizeof(st));
-    return CMPC_OK;
-}
-
-// the record launch behind a tick: without limits the launch it has always been, with them (cmpc_set_walk_limits) the kernel that also evaluates them,
-// on the corners the plant kernel reads
-static int record_launch(cmpc_handle h, const char* who, const CmpcRecordArgs& a, int* stats, hipStream_t st)
-{
-    if (!h->limits_set) return launch_status(h, who, cmpc_launch_rollout_record(&a, stats, st));
-    if (h->limits.dMeasures && a.row >= h->limits.rows)
-        return fail(h, CMPC_ERR_ARG, std::string(who) + ": the measures trace of cmpc_set_walk_limits has too few rows");
-    const CmpcLimitArgs lm = limit_args(h->limits, a.B, a.row, model_corners(h), corners_stride(h), h->cfg.gravity);
-    return launch_status(h, who, cmpc_launch_rollout_record_limits(&a, &lm, stats, st));
-}
-
-// the record launch of one tick; clear_row: the statistics row is cleared here (the walk clears all its rows at once)
-static int rollout_record_impl(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
-                               const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, hipStream_t st, bool clear_row)
-{
-    CmpcRecordArgs a;
-    if (!h || !h->box_set || !record_args(h->cfg.horizon, h->B, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, h->dBox, rec, a))
-        return fail(h, CMPC_ERR_ARG, h && !h->box_set ? "cmpc_rollout_record_device: the handle has no box yet (a sampling or a tick uploads it)"
-                                                      : "cmpc_rollout_record_device: bad argument");
-    int* stats = rec->dStats ? rec->dStats + 6 * (size_t)row : nullptr;
-    if (stats && clear_row) HIPCHK(h, hipMemsetAsync(stats, 0, sizeof(int) * 6, st));
-    return record_launch(h, "roll-out record", a, stats, st);
-}
-
-int cmpc_walk_extremes_init_device(cmpc_handle h, float* dExtremes, void* stream)
-{
-    if (!h || !dExtremes) return fail(h, CMPC_ERR_ARG, "cmpc_walk_extremes_init_device: null argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_extremes_init(h->B, dExtremes, stream_of(h, stream));
-    return launch_status(h, "extremes init", lrc);
-}
-
-// ---- the measures differentiated (include/cmpc.h): the host forms run the kernels' own per-entry functions ----
-static bool measures_rows_ok(int horizon, int batch, int tick0, int rows, const float* X, const float* P, const float* states, const float* corners,
-                             int corners_stride, double gravity)
-{
-    return horizon >= 2 && batch >= 1 && tick0 >= 0 && rows >= 1 && X && P && states && corners && corners_stride >= 0 && gravity > 0;
-}
-
-int cmpc_walk_measures_vjp(int horizon, int batch, int tick0, int rows, const float* X, const float* P, const float* states, const int* end_tick,
-                           const float* corners, int corners_stride, double gravity, const double* grad_measures, double* grad_states, float* grad_X,
-                           double* direct)
-{
-    if (!measures_rows_ok(horizon, batch, tick0, rows, X, P, states, corners, corners_stride, gravity) || !grad_measures || !grad_states || !grad_X || !direct)
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_vjp: bad argument");
-    const CmpcMeasureVjpArgs v{horizon, batch, tick0, rows, X, P, states, end_tick, corners, corners_stride, gravity, grad_measures, grad_states, grad_X, direct};
-    for (int r = 0; r < rows; ++r)
-        for (int b = 0; b < batch; ++b) cmpc_walk_measures_vjp_entry(v, r, b);
-    return CMPC_OK;
-}
-
-int cmpc_walk_measures_vjp_fold(int horizon, int batch, int rows, const double* direct, float* grad_P, double* grad_model)
-{
-    if (horizon < 2 || batch < 1 || rows < 1 || !direct) return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_fold: bad argument");
-    const size_t np = (size_t)rows * batch, nm = (size_t)24 * batch;
-    for (size_t e = 0; e < (np > nm ? np : nm); ++e) cmpc_walk_measures_fold_entry(horizon, batch, rows, direct, grad_P, grad_model, e);
-    return CMPC_OK;
-}
-
-int cmpc_walk_measures_jvp(int horizon, int batch, int tick0, int rows, int k, const float* X, const float* P, const float* states, const int* end_tick,
-                           const float* corners, int corners_stride, double gravity, const double* dir_states, const float* dir_X, const float* dir_P,
-                           const double* dir_model, double* dir_measures)
-{
-    if (!measures_rows_ok(horizon, batch, tick0, rows, X, P, states, corners, corners_stride, gravity) || k < 1 || !dir_states || !dir_X || !dir_measures)
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_jvp: bad argument");
-    const CmpcMeasureJvpArgs v{horizon, batch, tick0, rows, k, X, P, states, end_tick, corners, corners_stride, gravity, dir_states, dir_X, dir_P, dir_model,
-                               dir_measures};
-    for (int r = 0; r < rows; ++r)
-        for (int b = 0; b < batch; ++b) cmpc_walk_measures_jvp_entry(v, r, b);
-    return CMPC_OK;
-}
-
-int cmpc_walk_measures_jacobian(int horizon, int batch, int rows, const float* X, const float* P, const float* states, const float* corners,
-                                int corners_stride, double gravity, double* jacobian)
-{
-    if (!measures_rows_ok(horizon, batch, 0, rows, X, P, states, corners, corners_stride, gravity) || !jacobian)
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_walk_measures_jacobian: bad argument");
-    const int nx = 45 * horizon + 15, np = CmpcIdx{horizon}.np();
-    for (int r = 0; r < rows; ++r) {
-        const CmpcMeasureArgs a{horizon, batch, X + (size_t)r * batch * nx, P + (size_t)r * batch * np, states + (size_t)(r + 1) * batch * 9, corners,
-                                corners_stride, gravity};
-        for (int b = 0; b < batch; ++b)
-            for (int m = 0; m < 4; ++m) {   // row m: the VJP of the unit cotangent e_m (products with 1.0 and sums with 0.0 are exact)
-                double w[4] = {0.0, 0.0, 0.0, 0.0}, gs[5], gq[6], d[32];
-                w[m] = 1.0;
-                cmpc_walk_measures_vjp_problem(a, b, w, gs, gq, d);
-                double* J = jacobian + (((size_t)r * batch + b) * 4 + m) * CMPC_WALK_MEASURE_INPUTS;
-                for (int i = 0; i < 3; ++i) J[i] = gs[i];
-                J[3] = gs[3]; J[4] = gs[4]; J[5] = 0.0;
-                for (int i = 0; i < 6; ++i) J[6 + i] = gq[i];
-                for (int i = 0; i < 6; ++i) J[12 + i] = d[2 + i];
-                for (int i = 0; i < 24; ++i) J[18 + i] = d[8 + i];
-                J[42] = d[0]; J[43] = d[1];
-            }
-    }
-    return CMPC_OK;
-}
-
-// the rows of a call inside the tape, and the tape arrays the measures read
-static const char* measures_tape_refusal(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0)
-{
-    if (!h || !tape || !tape->dX || !tape->dP || !tape->dStates) return "null argument or incomplete tape";
-    if (h->cfg.horizon < 2) return "the measures refer to stage 1: the horizon must be at least 2";
-    if (tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows) return "bad argument (the rows must lie inside the tape)";
-    return nullptr;
-}
-
-int cmpc_walk_measures_vjp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                  const cmpc_walk_measure_grads* g, void* stream)
-{
-    if (const char* why = measures_tape_refusal(h, tick0, ticks, tape, row0)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_walk_measures_vjp_device: ") + why);
-    if (!g || !g->dGradMeasures || !g->dGradStates || !g->dGradX || !g->dDirect)
-        return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_device: dGradMeasures, dGradStates, dGradX and dDirect are needed");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, r0 = (size_t)row0;
-    const CmpcMeasureVjpArgs v{h->cfg.horizon, h->B, tick0, ticks, tape->dX + r0 * B * h->L.nx, tape->dP + r0 * B * h->L.np, tape->dStates + r0 * B * 9,
-                               dEndTick, model_corners(h), corners_stride(h), h->cfg.gravity, g->dGradMeasures + r0 * B * CMPC_WALK_MEASURES,
-                               g->dGradStates + r0 * B * 9, g->dGradX + r0 * B * h->L.nx, g->dDirect + r0 * B * CMPC_WALK_MEASURE_DIRECT};
-    return launch_status(h, "measures VJP", cmpc_launch_walk_measures_vjp(&v, stream_of(h, stream)));
-}
-
-int cmpc_walk_measures_vjp_fold_device(cmpc_handle h, int rows, const double* dDirect, float* dGradP, double* dGradModel, void* stream)
-{
-    if (!h || !dDirect || rows < 1 || h->cfg.horizon < 2) return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_vjp_fold_device: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    return launch_status(h, "measures fold", cmpc_launch_walk_measures_fold(h->cfg.horizon, h->B, rows, dDirect, dGradP, dGradModel, stream_of(h, stream)));
-}
-
-int cmpc_walk_measures_jvp_device(cmpc_handle h, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
-                                  const cmpc_walk_measure_dirs* d, void* stream)
-{
-    if (const char* why = measures_tape_refusal(h, tick0, ticks, tape, row0)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_walk_measures_jvp_device: ") + why);
-    if (k < 1 || !d || !d->dDirStates || !d->dDirX || !d->dDirMeasures)
-        return fail(h, CMPC_ERR_ARG, "cmpc_walk_measures_jvp_device: k >= 1, dDirStates, dDirX and dDirMeasures are needed");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, r0 = (size_t)row0, K = (size_t)k;
-    const CmpcMeasureJvpArgs v{h->cfg.horizon, h->B, tick0, ticks, k, tape->dX + r0 * B * h->L.nx, tape->dP + r0 * B * h->L.np, tape->dStates + r0 * B * 9,
-                               dEndTick, model_corners(h), corners_stride(h), h->cfg.gravity, d->dDirStates + r0 * B * K * 9, d->dDirX + r0 * B * K * h->L.nx,
-                               d->dDirP ? d->dDirP + r0 * B * K * h->L.np : nullptr, d->dDirModel, d->dDirMeasures + r0 * B * K * CMPC_WALK_MEASURES};
-    return launch_status(h, "measures JVP", cmpc_launch_walk_measures_jvp(&v, stream_of(h, stream)));
-}
-
-int cmpc_rollout_record_device(cmpc_handle h, int tick, int row, const float* dX, const float* dP, const float* dInfo, const int* dOk, const int* dLand,
-                               const float* dStateOut, const float* dZmp, const cmpc_walk_record* rec, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_record_device: null handle");
-    HIPCHK(h, hipSetDevice(h->device));
-    return rollout_record_impl(h, tick, row, dX, dP, dInfo, dOk, dLand, dStateOut, dZmp, rec, stream_of(h, stream), true);
-}
-
-int cmpc_rollout_outcome_init_device(cmpc_handle h, const float* dState0, const cmpc_walk_record* rec, void* stream)
-{
-    if (!h || !dState0 || !rec || !rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_outcome_init_device: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_outcome_init(h->B, dState0, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
-                                             rec->dBoxSlackMin, stream_of(h, stream));
-    return launch_status(h, "outcome init", lrc);
-}
-
-int cmpc_cold_start_device(cmpc_handle h, const float* dP, float* dX0, void* stream)
-{
-    if (!h || !dP || !dX0) return fail(h, CMPC_ERR_ARG, "cmpc_cold_start_device: null argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_cold_start(h->cfg.horizon, h->B, (float)(h->cfg.gravity / 8.0), dP, dX0, h->dEnded, stream_of(h, stream));
-    return launch_status(h, "cold start", lrc);
-}
-
-// ---- the device tape (include/cmpc.h, cmpc_walk_tape): one row from what a tick left ----
-static bool tape_complete(const cmpc_walk_tape* t)
-{
-    return t && t->rows >= 1 && t->dX && t->dP && t->dLamG && t->dInfo && t->dStates && t->dOk && t->dLand && t->dPlanT && t->dListT && t->dPlanN && t->dListN &&
-           t->plant_step > 0 && t->plant_substeps >= 1;
-}
-
-static int rollout_tape_impl(cmpc_handle h, int max_contacts, int row, int parts, const float* dX, const float* dP, const float* dInfo, const int* dOk,
-                             const int* dLand, const float* dStateIn, const float* dStateOut, const double* dPlanT, const int* dPlanN, const double* dListT,
-                             const int* dListN, const cmpc_walk_tape* tape, void* stream)
-{
-    if (!h || !tape_complete(tape) || max_contacts < 1 || row < 0 || row >= tape->rows || parts < 1 || parts > 3)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: bad argument");
-    if (((parts & 1) && !dStateIn) || ((parts & 2) && (!dX || !dP || !dInfo || !dLand || !dStateOut || !dListT || !dListN || (!dPlanT != !dPlanN))))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: null argument");
-    if (parts == 3 && dStateIn == dStateOut)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: a tick that ran in place needs part 1 in front of it");
-    if ((parts & 2) && (!h->mult_out || !h->dDuals))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_device: the multiplier output is off (cmpc_set_multiplier_output before the ticks)");
-    HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream_of(h, stream);
-    const CmpcTapeArgs a{h->B, max_contacts, h->L.nx, h->L.np, row, parts, dX, dP, dInfo, dOk, dLand, dStateIn, dStateOut, dPlanT, dPlanN, dListT, dListN,
-                         tape->dX, tape->dP, tape->dInfo, tape->dStates, tape->dOk, tape->dLand, tape->dPlanT, tape->dListT, tape->dPlanN, tape->dListN};
-    const int lrc = cmpc_launch_rollout_tape(&a, st);
-    if (const int err = launch_status(h, "roll-out tape", lrc)) return err;
-    if (parts & 2) return cmpc_get_multipliers_device(h, dX, dP, tape->dLamG + (size_t)row * h->B * h->L.ng, stream);
-    return CMPC_OK;
-}
-
-int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts, const float* dX, const float* dP, const float* dInfo, const int* dOk,
-                             const int* dLand, const float* dStateIn, const float* dStateOut, const double* dPlanT, const int* dPlanN, const double* dListT,
-                             const int* dListN, const cmpc_walk_tape* tape, void* stream)
-{
-    return rollout_tape_impl(h, max_contacts, row, parts, dX, dP, dInfo, dOk, dLand, dStateIn, dStateOut, dPlanT, dPlanN, dListT, dListN, tape, stream);
-}
-
-static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream,
-                             const cmpc_plant_mismatch* m = nullptr);
-
-int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                             int row0, int lists_in, int* lists_out, void* stream)
-{
-    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream);
-}
-
-static int walk_taped(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m)
-{
-    if (!h || !io || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: null argument or incomplete tape");
-    if (ticks < 1 || tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape has too few rows");
-    if (tape->plant_step != io->tick.plant_step || tape->plant_substeps != io->tick.plant_substeps ||
-        (tape->force_sample_time != 0) != (io->tick.force_sample_time != 0) ||
-        (tape_row0 == 0 ? (tape->first_row_is_first_tick != 0) != (cold_first != 0) : cold_first != 0))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape's scalars do not agree with the walk (or a first tick beyond row 0)");
-    if (!h->mult_out || !h->dDuals)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
-    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
-}
-
-int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                   int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
-{
-    return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, nullptr);
-}
-
-int cmpc_rollout_walk_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, const cmpc_plant_mismatch* m,
-                                      void* stream)
-{
-    if (tape) return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
-    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream, m);
-}
-
-// tape != null: the tape part around the ticks (cmpc_rollout_walk_taped_device, which has checked it); null: the launches of cmpc_rollout_walk_device
-// m: the plant mismatch, every tick passing its own number tick0 + i (no launch more per tick, nothing more on the tape: dStates holds the true state, dP the measured one)
-static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                             int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m)
-{
-    if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: null argument");
-    {
-        const int mrc = mismatch_check(h, "cmpc_rollout_walk_mismatch_device", m);
-        if (mrc != CMPC_OK) return mrc;
-    }
-    if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !io->tick.dListT || !io->tick.dListPose ||
-        !io->tick.dListN || !io->tick.box_upper || !io->tick.box_lower || !io->tick.dState || !io->tick.dStateOut || (io->dWrenchTicks && io->wrench_ticks < 1))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: bad argument");
-    if (io->dListTB == io->tick.dListT || io->dListPoseB == io->tick.dListPose || io->dListNB == io->tick.dListN)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the two sets of list buffers must not alias");
-    if (rec && (row0 < 0 || (long long)row0 + ticks > rec->rows)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the record has too few rows");
-    if (rec && h->limits_set && h->limits.dMeasures && (long long)row0 + ticks > h->limits.rows)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the measures trace of cmpc_set_walk_limits has too few rows");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream_of(h, stream);
-    int rc = upload_box(h, io->tick.box_upper, io->tick.box_lower, st);
-    if (rc != CMPC_OK) return rc;
-    if (rec && rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
-    const bool timing = h->timing;   // (an event record is a barrier packet on the stream: cmpc_set_timing)
-    h->timing = false; h->timed = false;
-    double* const set_t[2] = {io->tick.dListT, io->dListTB};
-    float* const set_p[2] = {io->tick.dListPose, io->dListPoseB};
-    int* const set_n[2] = {io->tick.dListN, io->dListNB};
-    const size_t wrench_row = (size_t)h->B * h->cfg.horizon * 6;
-    int cur = lists_in;
-    rc = CMPC_OK;
-    for (int i = 0; i < ticks && rc == CMPC_OK; ++i) {
-        const bool cold = cold_first && i == 0;
-        const double now = (double)(tick0 + i) * h->cfg.sampling_time;
-        cmpc_tick_io t = io->tick;
-        if (cold) {
-            t.dPrevT = nullptr; t.dPrevPose = nullptr; t.dPrevN = nullptr;
-        } else {
-            t.dPrevT = set_t[cur]; t.dPrevPose = set_p[cur]; t.dPrevN = set_n[cur];
-            cur = 1 - cur;
-        }
-        t.dListT = set_t[cur]; t.dListPose = set_p[cur]; t.dListN = set_n[cur];
-        if (i > 0) t.dState = io->tick.dStateOut;
-        if (io->dWrenchTicks) t.dWrench = i < io->wrench_ticks ? io->dWrenchTicks + wrench_row * i : nullptr;
-        t.plan_t_offset = now - io->plan_t_first;
-        const int* const ok_read = (cold && !t.force_sample_time) ? nullptr : t.dOk;
-        if (tape && i == 0)   // (the ticks run in place: the state the first one starts from is copied in front of it)
-            rc = rollout_tape_impl(h, max_contacts, tape_row0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, t.dState, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   tape, stream);
-        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true, tick0 + i, m);
-        if (rc == CMPC_OK && rec)
-            rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, ok_read, t.dLand, t.dStateOut, t.dZmp, rec, st, false);
-        if (rc == CMPC_OK && tape)
-            rc = rollout_tape_impl(h, max_contacts, tape_row0 + i, 2, t.dX, t.dP, t.dInfo, ok_read, t.dLand, nullptr, t.dStateOut, cold ? nullptr : t.dPlanT,
-                                   cold ? nullptr : t.dPlanN, t.dListT, t.dListN, tape, stream);
-    }
-    h->timing = timing;
-    if (rc == CMPC_OK && lists_out) *lists_out = cur;
-    return rc;
-}
-
-// ---- refill (include/cmpc.h, cmpc_walk_refill): the queue of trials behind a walk's slots ----
-// the argument block of the per-slot functions; false: a required pointer is NULL or a count is out of range.  rec may be NULL for the init (no slot outcome).
-static bool refill_args(int B, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* r, float* state_live, CmpcRefillArgs& a)
-{
-    if (B < 1 || tick_next < 0 || !r || r->trials < 0 || r->trial_ticks < 1 || !r->dStartTick || !r->dTrial || !r->dNext) return false;
-    if (r->dWrenchTrials && r->wrench_ticks < 1) return false;
-    if (r->trials > 0 && (!r->dState0 || !r->dTrialEndTick || !r->dTrialEndCode || !r->dTrialIterationsSum || !r->dTrialIterationsMax || !r->dTrialFinalState ||
-                          !r->dTrialBoxSlackMin || !r->dTrialTicks || !r->dTrialSlot || !r->dTrialStart))
-        return false;
-    if (rec && (!rec->dEndTick || !rec->dEndCode || !rec->dIterationsSum || !rec->dIterationsMax || !rec->dFinalState || !rec->dBoxSlackMin)) return false;
-    if (r->trace.dTrialOf && r->trace.rows < 1) return false;
-    const long long row = (long long)tick_next - r->trace.tick_first;
-    int* const trial_of = (r->trace.dTrialOf && row >= 0 && row < r->trace.rows) ? r->trace.dTrialOf + (size_t)row * B : nullptr;
-    a = CmpcRefillArgs{B, r->trials, r->trial_ticks, tick_next, r->dStartTick, r->dTrial, r->dState0, r->dTrialEndTick, r->dTrialEndCode, r->dTrialIterationsSum,
-                       r->dTrialIterationsMax, r->dTrialFinalState, r->dTrialBoxSlackMin, r->dTrialTicks, r->dTrialSlot, r->dTrialStart,
-                       rec ? rec->dEndTick : nullptr, rec ? rec->dEndCode : nullptr, rec ? rec->dIterationsSum : nullptr, rec ? rec->dIterationsMax : nullptr,
-                       rec ? rec->dFinalState : nullptr, rec ? rec->dBoxSlackMin : nullptr, state_live, trial_of};
-    return true;
-}
-
-int cmpc_rollout_refill_init(int batch, const cmpc_walk_refill* refill)
-{
-    CmpcRefillArgs a;
-    if (!refill_args(batch, 0, nullptr, refill, nullptr, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_init: bad argument");
-    cmpc_refill_init_host(a, refill->dNext);
-    return CMPC_OK;
-}
-
-int cmpc_rollout_refill_init_device(cmpc_handle h, const cmpc_walk_refill* refill, void* stream)
-{
-    CmpcRefillArgs a;
-    if (!h || !refill_args(h->B, 0, nullptr, refill, nullptr, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_init_device: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_refill_init(&a, refill->dNext, stream_of(h, stream));
-    return launch_status(h, "refill init", lrc);
-}
-
-int cmpc_rollout_refill(int batch, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* state_live)
-{
-    CmpcRefillArgs a;
-    if (!rec || !refill_args(batch, tick_next, rec, refill, state_live, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill: bad argument");
-    cmpc_refill_host(a, refill->dNext);
-    return CMPC_OK;
-}
-
-static int rollout_refill_impl(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, hipStream_t st)
-{
-    CmpcRefillArgs a;
-    if (!h || !rec || !refill_args(h->B, tick_next, rec, refill, dStateLive, a)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: bad argument");
-    const int lrc = cmpc_launch_refill(&a, refill->dNext, st);
-    return launch_status(h, "refill", lrc);
-}
-
-int cmpc_rollout_refill_device(cmpc_handle h, int tick_next, const cmpc_walk_record* rec, const cmpc_walk_refill* refill, float* dStateLive, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_refill_device: null handle");
-    HIPCHK(h, hipSetDevice(h->device));
-    return rollout_refill_impl(h, tick_next, rec, refill, dStateLive, stream_of(h, stream));
-}
-
-static int ensure_models(cmpc_handle h);
-static_assert(sizeof(cmpc_walk_refill_plans) == 104, "cmpc_walk_refill_plans: the size include/cmpc.h states");
-static_assert(sizeof(cmpc_walk_refill_trials) == 56, "cmpc_walk_refill_trials: the size include/cmpc.h states");
-static_assert(sizeof(cmpc_walk_refill_snapshot) == 32, "cmpc_walk_refill_snapshot: the size include/cmpc.h states");
-
-// ---- trials from a snapshot (include/cmpc.h, cmpc_walk_refill_snapshot): the restore step between the refill launch and the front kernel ----
-static bool snapshot_args(int N, int B, int src_B, int M, const cmpc_walk_snapshot* s, const cmpc_walk_snapshot* d, const int* index, int* ok, CmpcSnapshotArgs& a);
-// the 20 arrays of a cmpc_walk_snapshot in the struct's order
-static void snapshot_pointers(const cmpc_walk_snapshot& s, const void* out[CMPC_SNAP_ARRAYS])
-{
-    const void* const p[CMPC_SNAP_ARRAYS] = {s.dState, s.dP, s.dX, s.dX0, s.dInfo, s.dZmp, s.dOk, s.dLand, s.dListT, s.dListPose, s.dListN, s.dListTB, s.dListPoseB,
-                                             s.dListNB, s.dEndTick, s.dEndCode, s.dIterationsSum, s.dIterationsMax, s.dFinalState, s.dBoxSlackMin};
-    for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i) out[i] = p[i];
-}
-// the live buffers of a walk described as a snapshot: the state buffer the walk runs in place on, the record's outcome; prev: the set this tick reads
-static cmpc_walk_snapshot walk_live_view(const cmpc_walk_io* io, const cmpc_walk_record* rec, int prev)
-{
-    const cmpc_tick_io& k = io->tick;
-    return cmpc_walk_snapshot{0, prev, k.dStateOut, k.dP, k.dX, k.dX0, k.dInfo, k.dZmp, k.dOk, k.dLand, k.dListT, k.dListPose, k.dListN, io->dListTB,
-                              io->dListPoseB, io->dListNB, rec->dEndTick, rec->dEndCode, rec->dIterationsSum, rec->dIterationsMax, rec->dFinalState,
-                              rec->dBoxSlackMin};
-}
-// what is refused of `from` without a handle, in the header's order; null: nothing.  live (or null: not compared): the arrays a pool array must not be
-static const char* restore_refusal(const cmpc_walk_refill_snapshot* from, int trials, const cmpc_walk_snapshot* live)
-{
-    const cmpc_walk_snapshot* pool = from->pool;
-    if (!pool) return "pool is NULL";
-    if (pool->tick < 1) return "pool->tick must be at least 1 (trials from tick 0 are cmpc_rollout_walk_refill_trials_device's)";
-    if (from->pool_batch < 1) return "pool_batch must be at least 1";
-    const void* sp[CMPC_SNAP_ARRAYS];
-    snapshot_pointers(*pool, sp);
-    for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i)
-        if (!sp[i] && i != 3 && i != 4 && i != 5) return "a required pool array is NULL (every array but dX0, dInfo, dZmp)";
-    if (pool->lists_in < 0 || pool->lists_in > 1) return "pool->lists_in must be 0 or 1";
-    if (trials > 0 && !from->dTrialSnapshot) return "dTrialSnapshot is NULL";
-    if (live) {
-        const void* lp[CMPC_SNAP_ARRAYS];
-        snapshot_pointers(*live, lp);
-        for (int i = 0; i < CMPC_SNAP_ARRAYS; ++i)
-            for (int j = 0; j < CMPC_SNAP_ARRAYS; ++j)
-                if (sp[i] && sp[i] == lp[j]) return "a pool array is also a live array";
-    }
-    return nullptr;
-}
-// the argument block of the restore step of tick `tick`: the snapshot's table, the pool's set pool->lists_in paired with the live set live->lists_in (the
-// one this tick reads as "previous") and the pool's other set with the other live set
-static bool restore_args(int N, int B, int M, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* r, const cmpc_walk_refill_snapshot* from,
-                         CmpcRefillRestoreArgs& a)
-{
-    if (tick < 0 || !live || !r || r->trials < 1 || !r->dStartTick || !r->dTrial || live->lists_in < 0 || live->lists_in > 1) return false;
-    cmpc_walk_snapshot pool = *from->pool;
-    if (pool.lists_in != live->lists_in) {
-        std::swap(pool.dListT, pool.dListTB);
-        std::swap(pool.dListPose, pool.dListPoseB);
-        std::swap(pool.dListN, pool.dListNB);
-    }
-    if (!snapshot_args(N, B, from->pool_batch, M, &pool, live, from->dTrialSnapshot, nullptr, a.copy)) return false;
-    a.start = r->dStartTick; a.trial = r->dTrial;
-    a.tick = tick; a.Q = r->trials; a.pool_tick = pool.tick;
-    a.ok = from->dTrialSnapshotOk;
-    a.end_tick = live->dEndTick; a.end_code = live->dEndCode;
-    return true;
-}
-
-int cmpc_rollout_refill_restore(int horizon, int batch, int max_contacts, int tick, const cmpc_walk_snapshot* live, const cmpc_walk_refill* refill,
-                                const cmpc_walk_refill_snapshot* from)
-{
-    if (!from || !live || !refill || refill->trials < 0) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: null argument or a negative count");
-    if (const char* why = restore_refusal(from, refill->trials, live)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_refill_restore: ") + why);
-    if (horizon < 1 || batch < 1 || max_contacts < 1 || tick < 0 || !refill->dStartTick || !refill->dTrial || live->lists_in < 0 || live->lists_in > 1)
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: bad argument");
-    if (refill->trials == 0) return CMPC_OK;   // (no slot ever holds a trial)
-    CmpcRefillRestoreArgs a;
-    if (!restore_args(horizon, batch, max_contacts, tick, live, refill, from, a))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_restore: bad argument (a NULL live array)");
-    cmpc_refill_restore_host(a);
-    return CMPC_OK;
-}
-
-static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                            const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape = nullptr, int tape_row0 = 0,
-                            const cmpc_walk_refill_plans* plans = nullptr);
-
-int cmpc_rollout_walk_refill_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                    const cmpc_walk_refill* refill, int row0, int lists_in, int* lists_out, void* stream)
-{
-    return cmpc_rollout_walk_refill_trials_device(h, max_contacts, tick0, ticks, io, rec, refill, nullptr, row0, lists_in, lists_out, stream);
-}
-
-// the refill walk: per tick the refill launch, the tick's three launches (front and back kernels in refill mode, the warm solve with the per-problem cold
-// policy) and the record with local tick numbers.  trials (cmpc_walk_refill_trials) null, or with nothing set: the launches this function always queued;
-// else the front and back kernels' per-trial instantiations, each only when it has something to do, and the handle's per-problem table as the solve's and
-// the back kernel's records when there are per-trial models
-int cmpc_rollout_walk_refill_trials_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                           const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
-                                           void* stream)
-{
-    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream);
-}
-
-int cmpc_rollout_walk_refill_snapshot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                             const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from,
-                                             int row0, int lists_in, int* lists_out, void* stream)
-{
-    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, from, row0, lists_in, lists_out, stream);
-}
-
-// the trials call with a tape row behind every tick (include/cmpc.h); tape null: the trials call itself
-int cmpc_rollout_walk_refill_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, int row0, int lists_in, int* lists_out,
-                                          const cmpc_walk_tape* tape, int tape_row0, void* stream)
-{
-    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream, tape, tape_row0);
-}
-
-// ---- plans per trial (include/cmpc.h, cmpc_walk_refill_plans): the plan select step between the refill launch and the front kernel ----
-// what is refused of `plans` without a handle, in the header's order; null: nothing.  io (or null: the host form, which has the views only): the walk's
-// buffers the views must be and a pool array must not be
-static const char* plans_refusal(const cmpc_walk_refill_plans* p, int trials, const cmpc_walk_io* io, const cmpc_walk_refill_snapshot* from)
-{
-    if (from) return "plans together with a snapshot pool (per-trial plans for trials from a snapshot would be a replan of a walk in progress)";
-    if (p->pool_plans < 1) return "pool_plans must be at least 1";
-    if (!p->dPoolT || !p->dPoolPose || !p->dPoolN) return "a pool list array is NULL (dPoolT, dPoolPose, dPoolN)";
-    if (trials > 0 && !p->dTrialPlan) return "dTrialPlan is NULL";
-    if (!p->dPoolCom != !p->dPoolH) return "dPoolCom and dPoolH go together: both or neither";
-    const bool traj = p->dPoolCom != nullptr;
-    if (io && traj && (!io->tick.dPlanCom || !io->tick.dPlanH)) return "pool trajectories need io->tick.dPlanCom and dPlanH";
-    if (io) {
-        const cmpc_tick_io& k = io->tick;
-        if (p->dPlanT != k.dPlanT || p->dPlanPose != k.dPlanPose || p->dPlanN != k.dPlanN || (traj && (p->dPlanCom != k.dPlanCom || p->dPlanH != k.dPlanH)))
-            return "a writable view is not io's pointer (dPlanT, dPlanPose, dPlanN, and dPlanCom / dPlanH with pool trajectories)";
-    } else if (!p->dPlanT || !p->dPlanPose || !p->dPlanN || (traj && (!p->dPlanCom || !p->dPlanH))) {
-        return "a writable view is NULL";
-    }
-    const void* const pool[5] = {p->dPoolT, p->dPoolPose, p->dPoolN, p->dPoolCom, p->dPoolH};
-    const void* live[11] = {p->dPlanT, p->dPlanPose, p->dPlanN, traj ? p->dPlanCom : nullptr, traj ? p->dPlanH : nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (io) {
-        const void* const lists[6] = {io->tick.dListT, io->tick.dListPose, io->tick.dListN, io->dListTB, io->dListPoseB, io->dListNB};
-        for (int i = 0; i < 6; ++i) live[5 + i] = lists[i];
-    }
-    for (int i = 0; i < 5; ++i)
-        for (int j = 0; j < 11; ++j)
-            if (pool[i] && pool[i] == live[j]) return "a pool array is also a live array";
-    return nullptr;
-}
-// the argument block of the select step of tick `tick`; knots: the planner trajectories' (read with pool trajectories only)
-static bool plans_args(int B, int M, int tick, int knots, const cmpc_walk_refill* r, const cmpc_walk_refill_plans* p, const cmpc_walk_record* rec,
-                       CmpcRefillPlansArgs& a)
-{
-    if (B < 1 || M < 1 || tick < 0 || !r || r->trials < 1 || !r->dStartTick || !r->dTrial || !rec || !rec->dEndTick || !rec->dEndCode) return false;
-    if (p->dPoolCom && knots < 1) return false;
-    a = CmpcRefillPlansArgs{};
-    a.B = B; a.Q = r->trials; a.tick = tick; a.pool_plans = p->pool_plans;
-    a.start = r->dStartTick; a.trial = r->dTrial; a.index = p->dTrialPlan; a.ok = p->dTrialPlanOk;
-    a.end_tick = rec->dEndTick; a.end_code = rec->dEndCode;
-    int n = 0;
-    auto add = [&](const void* sp, void* dp, int words) {
-        a.src[n] = static_cast<const unsigned*>(sp); a.dst[n] = static_cast<unsigned*>(dp); a.words[n] = words;
-        ++n;
-    };
-    add(p->dPoolT, p->dPlanT, 8 * M); add(p->dPoolPose, p->dPlanPose, 14 * M); add(p->dPoolN, p->dPlanN, 2);
-    if (p->dPoolCom) { add(p->dPoolCom, p->dPlanCom, 3 * knots); add(p->dPoolH, p->dPlanH, 3 * knots); }
-    a.count = n;
-    return true;
-}
-
-int cmpc_rollout_refill_plans(int batch, int max_contacts, int tick, const cmpc_walk_refill* refill, const cmpc_walk_refill_plans* plans,
-                              const cmpc_walk_record* rec, int plan_knots)
-{
-    if (!plans || !refill || !rec || refill->trials < 0) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: null argument or a negative count");
-    if (const char* why = plans_refusal(plans, refill->trials, nullptr, nullptr)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_refill_plans: ") + why);
-    if (batch < 1 || max_contacts < 1 || tick < 0 || !refill->dStartTick || !refill->dTrial || !rec->dEndTick || !rec->dEndCode ||
-        (plans->dPoolCom && plan_knots < 1))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: bad argument");
-    if (refill->trials == 0) return CMPC_OK;   // (no slot ever holds a trial)
-    CmpcRefillPlansArgs a;
-    if (!plans_args(batch, max_contacts, tick, plan_knots, refill, plans, rec, a)) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_refill_plans: bad argument");
-    cmpc_refill_plans_host(a);
-    return CMPC_OK;
-}
-
-// the taped call with a plan pool (include/cmpc.h); plans null: the taped call itself, and with tape null as well the trials call
-int cmpc_rollout_walk_refill_plans_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                                          const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_plans* plans,
-                                          int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream)
-{
-    return walk_refill_impl(h, max_contacts, tick0, ticks, io, rec, refill, trials, nullptr, row0, lists_in, lists_out, stream, tape, tape_row0, plans);
-}
-
-// ---- the fold of per-trial gradients onto the pool's rows (include/cmpc.h) ----
-static const char* fold_refusal(int trials, int words, const int* index, const double* per, int pool_rows, const double* out)
-{
-    if (trials < 0 || words < 1 || pool_rows < 1) return "trials < 0, words < 1 or pool_rows < 1";
-    if (!out || (trials > 0 && (!index || !per))) return "a NULL array";
-    if (out == per) return "dOut is also dPerTrial";
-    if ((long long)pool_rows * words > 0x7fffffffLL) return "more than 2^31 - 1 entries in dOut";
-    return nullptr;
-}
-
-int cmpc_rollout_plan_fold(int trials, int words, const int* index, const double* per_trial, int pool_rows, double* out)
-{
-    if (const char* why = fold_refusal(trials, words, index, per_trial, pool_rows, out)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_plan_fold: ") + why);
-    for (int p = 0; p < pool_rows; ++p)
-        for (int w = 0; w < words; ++w) out[(size_t)p * words + w] = cmpc_plan_fold_entry(trials, words, index, per_trial, p, w);
-    return CMPC_OK;
-}
-
-int cmpc_rollout_plan_fold_device(cmpc_handle h, int trials, int words, const int* dIndex, const double* dPerTrial, int pool_rows, double* dOut, void* stream)
-{
-    if (const char* why = fold_refusal(trials, words, dIndex, dPerTrial, pool_rows, dOut))
-        return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_plan_fold_device: ") + why);
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_plan_fold_device: null handle");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_plan_fold(trials, words, dIndex, dPerTrial, pool_rows, dOut, stream_of(h, stream));
-    return launch_status(h, "plan fold", lrc);
-}
-
-// from (cmpc_walk_refill_snapshot) null: the walk above.  Else the trials start from pool rows: a sixth launch per tick, the restore, behind the refill; the
-// front and back kernels and the record take the pool's tick as the offset of every slot's local tick, and no problem of any solve is on a first tick (the
-// solve is launched without the slots' start ticks: warm for all)
-// tape (cmpc_rollout_walk_refill_taped_device; never together with from) non-null: part 2 of the tape behind every tick's record -- the copy kernel and the
-// multiplier call, seven launches a tick -- tick tick0 + i into row tape_row0 + i, slot-major.  Part 1 is never queued: the state a spawned trial starts
-// from is dState0[q], which the regroup supplies.  dOk and the planner's times go on every tick: every tick is queued as a merge tick
-// plans (cmpc_rollout_walk_refill_plans_device; never together with from) non-null: one launch more per tick, the plan select, behind the refill -- a
-// spawned slot's rows of the planner's lists and trajectories become its trial's pool row before the front kernel reads them
-static int walk_refill_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                            const cmpc_walk_refill* refill, const cmpc_walk_refill_trials* trials, const cmpc_walk_refill_snapshot* from, int row0,
-                            int lists_in, int* lists_out, void* stream, const cmpc_walk_tape* tape, int tape_row0, const cmpc_walk_refill_plans* plans)
-{
-    // (the refusals that need no handle come first: they are the same with and without one)
-    if (!io || !rec || !refill) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null argument");
-    const cmpc_tick_io& k = io->tick;
-    if (max_contacts < 1 || max_contacts > 16)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: max_contacts must be 1 .. 16 (a slot's first tick uses the front kernel's LDS stage)");
-    if (io->dWrenchTicks) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dWrenchTicks is not taken (the schedule is the per-trial dWrenchTrials)");
-    if (trials && (trials->hidden_ticks < 0 || trials->noise_ticks < 0))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: a negative count of schedule rows");
-    if (trials && ((trials->dHiddenWrench && trials->hidden_ticks == 0) || (trials->dStateNoise && trials->noise_ticks == 0)))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: a schedule with no rows");
-    if (trials && trials->dModelOk && !trials->dModels) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_trials_device: dModelOk without dModels");
-    if (from) {
-        const cmpc_walk_snapshot live = walk_live_view(io, rec, 0);
-        if (const char* why = restore_refusal(from, refill->trials, &live))
-            return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_refill_snapshot_device: ") + why);
-    }
-    if (tape) {
-        if (!tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: incomplete tape");
-        if (tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
-            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape has too few rows");
-        if (tape->plant_step != k.plant_step || tape->plant_substeps != k.plant_substeps || (tape->force_sample_time != 0) != (k.force_sample_time != 0))
-            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the tape's scalars do not agree with the walk");
-    }
-    if (plans)
-        if (const char* why = plans_refusal(plans, refill->trials, io, from))
-            return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_refill_plans_device: ") + why);
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: null handle");
-    if (h->limits_set && h->limits.dExtremes)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: dExtremes of cmpc_set_walk_limits must be NULL on a refill walk (a slot's extremes "
-                                     "would span several trials: take them from the measures trace and dTrialOf)");
-    if (tape && (!h->mult_out || !h->dDuals))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
-    if (ticks < 1 || tick0 < 0 || lists_in < 0 || lists_in > 1 || !io->dListTB || !io->dListPoseB || !io->dListNB || !k.dListT || !k.dListPose || !k.dListN ||
-        !k.box_upper || !k.box_lower || !k.dState || !k.dStateOut || k.dState != k.dStateOut || !k.dPlanT || !k.dPlanPose || !k.dPlanN || !k.dOk || !k.dLand ||
-        !k.dInfo || !k.dP || !k.dX0 || !k.dX || !(k.plant_step > 0) || k.plant_substeps < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad argument");
-    if (io->dListTB == k.dListT || io->dListPoseB == k.dListPose || io->dListNB == k.dListN)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the two sets of list buffers must not alias");
-    if ((k.dPlanCom || k.dPlanH) && (!k.dPlanCom || !k.dPlanH || k.plan_knots < 2 || !(k.plan_dt > 0) || !(k.robot_mass > 0)))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad planner trajectory");
-    if (row0 < 0 || (long long)row0 + ticks > rec->rows) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the record has too few rows");
-    if (h->limits_set && h->limits.dMeasures && (long long)row0 + ticks > h->limits.rows)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: the measures trace of cmpc_set_walk_limits has too few rows");
-    CmpcRefillArgs probe;
-    if (!refill_args(h->B, tick0, rec, refill, k.dStateOut, probe)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad refill or record");
-    long long dt_ns = 0;
-    if (k.force_sample_time) {
-        dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: force_sample_time needs a sampling time of at least 1 ns");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream_of(h, stream);
-    int rc = upload_box(h, k.box_upper, k.box_lower, st);
-    if (rc != CMPC_OK) return rc;
-    if (rec->dStats) HIPCHK(h, hipMemsetAsync(rec->dStats + 6 * (size_t)row0, 0, sizeof(int) * 6 * (size_t)ticks, st));
-    // the per-trial data as the kernels take it, or null.  With models the handle reads its per-problem table from here on (the launches below capture the
-    // table's address and the corner stride when they are queued); a slot's record is written by the front kernel of the slot's first tick, ahead of every
-    // launch that reads it, and a slot that never gets a trial stays behind the ended mask
-    CmpcRefillTrialArgs tr_args{};
-    const CmpcRefillTrialArgs* tr = nullptr;
-    if (trials && (trials->dModels || trials->dHiddenWrench || trials->dStateNoise || trials->dForceGain)) {
-        if (trials->dModels) {
-            rc = ensure_models(h);
-            if (rc != CMPC_OK) return rc;
-            h->models_set = true;
-        }
-        tr_args = CmpcRefillTrialArgs{trials->dModels, trials->dModelOk, h->dConsts, h->dExpK, h->dModels, trials->dHiddenWrench, trials->hidden_ticks,
-                                      trials->dStateNoise, trials->noise_ticks, trials->dForceGain, refill->trials};
-        tr = &tr_args;
-    }
-    const bool timing = h->timing;   // (as cmpc_rollout_walk_device)
-    const int* const ended_saved = h->dEnded;
-    h->timing = false; h->timed = false;
-    h->dEnded = rec->dEndTick;
-    double* const set_t[2] = {k.dListT, io->dListTB};
-    float* const set_p[2] = {k.dListPose, io->dListPoseB};
-    int* const set_n[2] = {k.dListN, io->dListNB};
-    const int N = h->cfg.horizon, B = h->B;
-    const int offset = from ? from->pool->tick : 0;
-    int cur = lists_in;
-    for (int i = 0; i < ticks && rc == CMPC_OK; ++i) {
-        const int tick = tick0 + i;
-        const int prev = cur;
-        cur = 1 - cur;
-        rc = rollout_refill_impl(h, tick, rec, refill, k.dStateOut, st);
-        if (rc != CMPC_OK) break;
-        if (from && refill->trials > 0) {
-            const cmpc_walk_snapshot live = walk_live_view(io, rec, prev);
-            CmpcRefillRestoreArgs ra;
-            if (!restore_args(N, B, max_contacts, tick, &live, refill, from, ra)) {
-                rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_snapshot_device: bad restore");
-                break;
-            }
-            const int rrc = cmpc_launch_refill_restore(&ra, st);
-            if ((rc = launch_status(h, "refill restore", rrc)) != CMPC_OK) break;
-        }
-        if (plans && refill->trials > 0) {
-            CmpcRefillPlansArgs pa;
-            if (!plans_args(B, max_contacts, tick, k.plan_knots, refill, plans, rec, pa)) {
-                rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_plans_device: bad plan select");
-                break;
-            }
-            const int prc = cmpc_launch_refill_plans(&pa, st);
-            if ((rc = launch_status(h, "refill plan select", prc)) != CMPC_OK) break;
-        }
-        int lrc = cmpc_launch_tick_pre_refill(B, N, max_contacts, h->cfg.sampling_time, k.dPlanT, k.dPlanPose, k.dPlanN, set_t[prev], set_p[prev], set_n[prev],
-                                              set_t[cur], set_p[cur], set_n[cur], k.dOk, k.dLand, h->dBox, k.dStateOut, k.dP, k.dX, k.dX0, k.dPlanCom, k.dPlanH,
-                                              k.plan_knots, k.plan_dt, k.robot_mass, k.com_height, dt_ns, h->dEnded, refill->dStartTick, refill->dTrial, tick,
-                                              refill->dWrenchTrials, refill->wrench_ticks, refill->trials, io->plan_t_first, (float)(h->cfg.gravity / 8.0), tr,
-                                              offset, st);
-        if ((rc = launch_status(h, "refill tick (front)", lrc)) != CMPC_OK) break;
-        rc = solve_device_impl(h, k.dP, k.dX0, k.dX, k.dInfo, (void*)st, true, from ? nullptr : refill->dStartTick, tick);
-        if (rc != CMPC_OK) break;
-        lrc = cmpc_launch_tick_post_refill(B, N, max_contacts, h->cfg.sampling_time, (float)h->cfg.gravity, model_corners(h), corners_stride(h), k.dX, k.dP,
-                                           k.dStateOut, k.dStateOut, k.dZmp, (float)k.plant_step, k.plant_substeps, (float)k.zmp_half_x, (float)k.zmp_half_y,
-                                           k.dLand, set_t[cur], set_p[cur], set_n[cur], h->dEnded, refill->dStartTick, tick, refill->dTrial, tr, offset, st);
-        if ((rc = launch_status(h, "refill tick (back)", lrc)) != CMPC_OK) break;
-        CmpcRecordArgs a;
-        // (the tick number an ending takes is tick - start[b]; with trials from a snapshot the whole-walk number offset + tick - start[b]: the offset goes in here)
-        if (!h->box_set || !record_args(N, B, offset + tick, row0 + i, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, k.dStateOut, k.dZmp, h->dBox, rec, a)) {
-            rc = fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_refill_device: bad record");
-            break;
-        }
-        a.start = refill->dStartTick;
-        rc = record_launch(h, "refill walk record", a, rec->dStats ? rec->dStats + 6 * (size_t)(row0 + i) : nullptr, st);
-        if (rc == CMPC_OK && tape)
-            rc = rollout_tape_impl(h, max_contacts, tape_row0 + i, 2, k.dX, k.dP, k.dInfo, k.dOk, k.dLand, nullptr, k.dStateOut, k.dPlanT, k.dPlanN, set_t[cur],
-                                   set_n[cur], tape, stream);
-    }
-    h->timing = timing;
-    h->dEnded = ended_saved;
-    if (rc == CMPC_OK && lists_out) *lists_out = cur;
-    return rc;
-}
-
-// ---- the snapshot of a walk (include/cmpc.h, cmpc_walk_snapshot): one copy kernel, destination problem b <- source problem index[b] ----
-size_t cmpc_walk_snapshot_bytes(int horizon, int max_contacts)
-{
-    if (horizon < 1 || max_contacts < 1) return 0;
-    CmpcLayout L;
-    cmpc_layout_init(L, horizon);
-    return sizeof(float) * (2 * (size_t)L.nx + L.np) + 176 * (size_t)max_contacts + 160;
-}
-
-// the table of arrays both sides have, as rows of 32-bit words; false: a required pointer is NULL, or a destination array is also a source array
-static bool snapshot_args(int N, int B, int src_B, int M, const cmpc_walk_snapshot* s, const cmpc_walk_snapshot* d, const int* index, int* ok, CmpcSnapshotArgs& a)
-{
-    if (N < 1 || B < 1 || src_B < 1 || M < 1 || !s || !d || (!index && src_B != B)) return false;
-    CmpcLayout L;
-    cmpc_layout_init(L, N);
-    a.B = B; a.src_B = src_B; a.count = 0; a.index = index; a.ok = ok;
-    bool complete = true;
-    auto add = [&](const void* sp, void* dp, int words, bool optional) {
-        if (!sp || !dp) { complete = complete && optional; return; }
-        a.src[a.count] = static_cast<const unsigned*>(sp); a.dst[a.count] = static_cast<unsigned*>(dp); a.words[a.count] = words;
-        ++a.count;
-    };
-    add(s->dState, d->dState, 9, false); add(s->dP, d->dP, L.np, false); add(s->dX, d->dX, L.nx, false); add(s->dX0, d->dX0, L.nx, true);
-    add(s->dInfo, d->dInfo, CMPC_INFO, true); add(s->dZmp, d->dZmp, 2, true); add(s->dOk, d->dOk, 1, false); add(s->dLand, d->dLand, 2, false);
-    add(s->dListT, d->dListT, 8 * M, false); add(s->dListPose, d->dListPose, 14 * M, false); add(s->dListN, d->dListN, 2, false);
-    add(s->dListTB, d->dListTB, 8 * M, false); add(s->dListPoseB, d->dListPoseB, 14 * M, false); add(s->dListNB, d->dListNB, 2, false);
-    add(s->dEndTick, d->dEndTick, 1, false); add(s->dEndCode, d->dEndCode, 1, false); add(s->dIterationsSum, d->dIterationsSum, 1, false);
-    add(s->dIterationsMax, d->dIterationsMax, 1, false); add(s->dFinalState, d->dFinalState, 9, false); add(s->dBoxSlackMin, d->dBoxSlackMin, 1, false);
-    if (!complete) return false;
-    for (int i = 0; i < a.count; ++i)
-        for (int j = 0; j < a.count; ++j)
-            if (a.dst[i] == a.src[j]) return false;
-    return true;
-}
-
-int cmpc_rollout_snapshot(int horizon, int batch, int src_batch, int max_contacts, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
-                          const int* index, int* ok)
-{
-    CmpcSnapshotArgs a;
-    if (!snapshot_args(horizon, batch, src_batch, max_contacts, src, dst, index, ok, a))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_snapshot: bad argument (a NULL array, sizes, or a destination array that is also a source array)");
-    for (int b = 0; b < batch; ++b) {
-        const int s = cmpc_snapshot_source(a, b);
-        if (ok) ok[b] = s >= 0 ? 1 : 0;
-        if (s < 0) continue;
-        for (int i = 0; i < a.count; ++i) {
-            const size_t w = (size_t)a.words[i];
-            std::memcpy(a.dst[i] + w * b, a.src[i] + w * s, sizeof(unsigned) * w);
-        }
-    }
-    return CMPC_OK;
-}
-
-int cmpc_rollout_snapshot_device(cmpc_handle h, int max_contacts, int src_batch, const cmpc_walk_snapshot* src, const cmpc_walk_snapshot* dst,
-                                 const int* dIndex, int* dOk, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_snapshot_device: null handle");
-    CmpcSnapshotArgs a;
-    if (!snapshot_args(h->cfg.horizon, h->B, src_batch, max_contacts, src, dst, dIndex, dOk, a))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_snapshot_device: bad argument (a NULL array, sizes, or a destination array that is also a source array)");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_rollout_snapshot(&a, stream_of(h, stream));
-    return launch_status(h, "walk snapshot", lrc);
-}
-
-// ---- the tape of a refill walk regrouped by trial (include/cmpc.h, cmpc_walk_tape_regroup): one copy kernel ----
-static_assert(sizeof(cmpc_walk_tape_regroup) == 32, "cmpc_walk_tape_regroup: the size include/cmpc.h states");
-// the 11 arrays of a cmpc_walk_tape in the struct's order
-static void tape_pointers(const cmpc_walk_tape& t, const void* out[11])
-{
-    const void* const p[11] = {t.dX, t.dP, t.dLamG, t.dInfo, t.dStates, t.dOk, t.dLand, t.dPlanT, t.dListT, t.dPlanN, t.dListN};
-    for (int i = 0; i < 11; ++i) out[i] = p[i];
-}
-// what is refused without a handle, in the header's order; null: nothing
-static const char* regroup_refusal(int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* r, const cmpc_walk_tape_regroup* g,
-                                   const cmpc_walk_tape* dst)
-{
-    if (!src || !r || !g || !dst) return "null argument";
-    if (!g->dTrialIndex || !g->dEndOut) return "dTrialIndex or dEndOut is NULL";
-    if (r->trials > 0 && (!r->dState0 || !r->dTrialSlot || !r->dTrialStart || !r->dTrialTicks || !r->dTrialEndTick))
-        return "a required array of the refill is NULL (dState0, dTrialSlot, dTrialStart, dTrialTicks, dTrialEndTick)";
-    if (!tape_complete(src) || !tape_complete(dst)) return "incomplete tape";
-    if (dst->rows != r->trial_ticks) return "the destination tape must have refill->trial_ticks rows";
-    if (r->trials < 0) return "a negative count of trials";
-    const void* sp[11];
-    const void* dp[11];
-    tape_pointers(*src, sp);
-    tape_pointers(*dst, dp);
-    for (int i = 0; i < 11; ++i)
-        for (int j = 0; j < 11; ++j)
-            if (dp[i] == sp[j]) return "a destination array is also a source array";
-    if (max_contacts < 1) return "max_contacts must be at least 1";
-    return nullptr;
-}
-static void regroup_args(int N, int B, int M, const cmpc_walk_tape* s, const cmpc_walk_refill* r, const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* d,
-                         CmpcRegroupArgs& a)
-{
-    CmpcLayout L;
-    cmpc_layout_init(L, N);
-    a.B = B; a.rows = d->rows; a.src_rows = s->rows; a.Q = r->trials; a.tick_first = g->tick_first;
-    a.index = g->dTrialIndex;
-    a.slot = r->dTrialSlot; a.start = r->dTrialStart; a.ticks = r->dTrialTicks; a.end = r->dTrialEndTick;
-    a.state0 = reinterpret_cast<const unsigned*>(r->dState0);
-    a.end_out = g->dEndOut; a.ok_out = g->dOkOut;
-    int n = 0;
-    auto add = [&](const void* sp, void* dp, int words) {
-        a.src[n] = static_cast<const unsigned*>(sp); a.dst[n] = static_cast<unsigned*>(dp); a.words[n] = words;
-        ++n;
-    };
-    add(s->dX, d->dX, L.nx); add(s->dP, d->dP, L.np); add(s->dLamG, d->dLamG, L.ng); add(s->dInfo, d->dInfo, CMPC_INFO);
-    add(s->dOk, d->dOk, 1); add(s->dLand, d->dLand, 2); add(s->dListT, d->dListT, 8 * M); add(s->dListN, d->dListN, 2);
-    add(s->dPlanT, d->dPlanT, 8 * M); add(s->dPlanN, d->dPlanN, 2);   // (CMPC_REGROUP_PLAN: the planner's rows come last)
-    a.src_states = reinterpret_cast<const unsigned*>(s->dStates); a.dst_states = reinterpret_cast<unsigned*>(d->dStates);
-}
-
-int cmpc_rollout_tape_regroup(int horizon, int batch, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
-                              const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst)
-{
-    if (const char* why = regroup_refusal(max_contacts, src, refill, g, dst)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_rollout_tape_regroup: ") + why);
-    if (horizon < 1 || batch < 1) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup: bad horizon or batch");
-    CmpcRegroupArgs a;
-    regroup_args(horizon, batch, max_contacts, src, refill, g, dst, a);
-    cmpc_regroup_host(a);
-    return CMPC_OK;
-}
-
-int cmpc_rollout_tape_regroup_device(cmpc_handle h, int max_contacts, const cmpc_walk_tape* src, const cmpc_walk_refill* refill,
-                                     const cmpc_walk_tape_regroup* g, const cmpc_walk_tape* dst, void* stream)
-{
-    if (const char* why = regroup_refusal(max_contacts, src, refill, g, dst))
-        return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_tape_regroup_device: ") + why);
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup_device: null handle");
-    if (dst->rows > 65535) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tape_regroup_device: more than 65535 rows (one workgroup per row and column)");
-    CmpcRegroupArgs a;
-    regroup_args(h->cfg.horizon, h->B, max_contacts, src, refill, g, dst, a);
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_rollout_tape_regroup(&a, stream_of(h, stream));
-    return launch_status(h, "tape regroup", lrc);
-}
-
-// ---- one tick in reverse (include/cmpc.h): plant VJP -> adjust part of the list VJP -> cmpc_solution_vjp_model_device -> the state rows of gP and the flags
-// (cmpc_tick_vjp_combine_kernel) -> sample + merge part of the list VJP [-> the orientation list VJP], on one stream ----
-namespace {
-// one workgroup per problem.  Flags first: 5 merge failed, else the sensitivity's 2 / 3 (about the inputs), else 4 when the solve's status is not 0, else the
-// sensitivity's 1; a flagged problem gets zeros
-// in every array written here and ok = 0 (the list kernel behind this one then writes zeros too and adds nothing to g_plan).  Otherwise
-// gP = gP(solve) + gP(plant: fExt_0, tauExt_0), gState += gP[com0, dcom0, h0], gWrench = the fExt / tauExt rows of gP, gModel += solve's + plant's.
-// g_rot (the rotation entry; null otherwise) holds the solve's dl/domega [B][2][N][3] and receives the plant's g_rot0[B][2][3] on stage 0.
-__global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N, const float* __restrict__ info, const int* __restrict__ ok,
-                                                                    const float* __restrict__ gp_sol, const float* __restrict__ gp_plant,
-                                                                    const double* __restrict__ gm_sol, const double* __restrict__ gm_plant,
-                                                                    double* __restrict__ g_state, float* __restrict__ g_wrench, double* __restrict__ g_model,
-                                                                    float* __restrict__ g_p, float* __restrict__ sens, int* __restrict__ ok_out,
-                                                                    const double* __restrict__ g_rot0, double* __restrict__ g_rot,
-                                                                    const double* __restrict__ gh_plant, const double* __restrict__ gg_plant,
-                                                                    double* __restrict__ g_hidden, float* __restrict__ g_noise, double* __restrict__ g_gain)
-{
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const CmpcIdx L{N};
-    const int np = L.np();
-    const float s0 = sens[(size_t)b * CMPC_SENS];
-    int status = s0 == s0 ? (int)s0 : 2;
-    if (status < 2 && info[(size_t)b * CMPC_INFO_N + 5] != 0.f) status = 4;
-    if (ok && ok[b] == 0) status = 5;
-    __syncthreads();   // (every thread has read the status word before thread 0 rewrites it)
-    const float* gs = gp_sol + (size_t)b * np;
-    const float* gq = gp_plant + (size_t)b * np;
-    if (status != 0) {
-        for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] = 0.0;
-        if (g_wrench) for (int e = tid; e < 6 * N; e += 128) g_wrench[(size_t)b * 6 * N + e] = 0.f;
-        if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = 0.f;
-        if (g_rot) for (int e = tid; e < 6 * N; e += 128) g_rot[(size_t)b * 6 * N + e] = 0.0;
-        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = 0.0;   // (the mismatch entry: zeros, and nothing added to g_gain)
-        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = 0.f;
-    } else {
-        for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] += (double)gs[L.pCom0() + e];
-        if (g_wrench)
-            for (int e = tid; e < 6 * N; e += 128) {
-                const int k = e / 6, i = e % 6;
-                const int src = (i < 3 ? L.pFext() : L.pText() - 3) + 3 * k + i;
-                g_wrench[(size_t)b * 6 * N + e] = gs[src] + gq[src];
-            }
-        if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = gs[e] + gq[e];
-        if (g_model) for (int e = tid; e < CMPC_MODEL_DOUBLES; e += 128)
-            g_model[(size_t)b * CMPC_MODEL_DOUBLES + e] += gm_sol[(size_t)b * CMPC_MODEL_DOUBLES + e] + gm_plant[(size_t)b * CMPC_MODEL_DOUBLES + e];
-        if (g_rot) for (int e = tid; e < 6; e += 128) g_rot[((size_t)b * 2 + e / 3) * 3 * N + e % 3] += g_rot0[(size_t)b * 6 + e];
-        // the mismatch entry: the hidden wrench and the gain are the plant's alone; the noise entered through setState, so its gradient is the solve's gP there
-        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = gh_plant[(size_t)b * 6 + e];
-        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = gs[L.pCom0() + e];
-        if (g_gain && tid == 0) g_gain[b] += gg_plant[b];
-    }
-    if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
-}
-
-__global__ __launch_bounds__(256) void cmpc_axpy_float_kernel(size_t n, const float* __restrict__ x, float* __restrict__ y)
-{
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) y[e] += x[e];
-}
-}  // namespace
-
-// the mismatch entry's further arguments (cmpc_rollout_tick_vjp_mismatch_device); null in tick_vjp: the launches and bits of the two entries before it
-struct TickMismatch {
-    const float* hidden; const float* gain;              // this tick's hidden-wrench row [B][6] and the gain [B], either may be null
-    double* g_hidden; float* g_noise; double* g_gain;    // outputs, each may be null
-};
-
-// rot: the rotation entry -- the plant VJP also gives dGradRot0, the solve's VJP is cmpc_solution_vjp_rot_device (its dGradP and dGradModel are
-// cmpc_solution_vjp_model_device's bit for bit), the combine kernel adds the plant's part to stage 0, and the orientation list VJP runs last
-static int tick_vjp(cmpc_handle h, bool rot, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut, const double* dGradListOut,
-                    const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench, double* dGradPlan, double* dGradModel, float* dGradP,
-                    float* dTickSens, const double* dGradListRotOut, double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream,
-                    const TickMismatch* mm = nullptr)
-{
-    if (!h || !tape || max_contacts < 1 || !dGradStateOut || !dGradState || !dGradPrevList || !dTickSens || (rot && !dGradPrevListRot))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: null argument");
-    if (!tape->dX || !tape->dP || !tape->dLamG || !tape->dState || !tape->dInfo || !tape->dLand || !tape->dListT || !tape->dListN ||
-        !(tape->plant_step > 0) || tape->plant_substeps < 1)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: incomplete tape");
-    const bool merge = tape->dPrevT || tape->dPrevN;
-    if (merge && (!tape->dPrevT || !tape->dPrevN || !tape->dPlanT || !tape->dPlanN))
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: a merge tick's tape needs the planner's and the previous tick's times and counts");
-    long long dt_ns = 0;
-    if (tape->force_sample_time) {
-        dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_tick_vjp_device: force_sample_time needs a sampling time of at least 1 ns");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream_of(h, stream);
-    const int B = h->B, N = h->cfg.horizon;
-    const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, nm = (size_t)B * CMPC_MODEL_DOUBLES;
-    const size_t nr = (size_t)B * 6 * N, nr0 = (size_t)B * 6;
-    if (!h->dTickWs)     // (sized for the rotation entry whichever entry runs first)
-        HIPCHK(h, hipMalloc(&h->dTickWs, sizeof(double) * (2 * nm + nr + nr0 + 7 * (size_t)B) + sizeof(float) * (nx + 2 * np) + sizeof(int) * (size_t)B));
-    double* gmSol = reinterpret_cast<double*>(h->dTickWs);
-    double* gmPlant = gmSol + nm;
-    double* grSol = gmPlant + nm;
-    double* grPlant = grSol + nr;
-    double* ghPlant = grPlant + nr0;            // (the mismatch entry: the plant's gradient on the hidden wrench [B][6] and on the gain [B])
-    double* ggPlant = ghPlant + 6 * (size_t)B;
-    float* gX = reinterpret_cast<float*>(ggPlant + (size_t)B);
-    if (rot && dGradRot) grSol = dGradRot;     // (the solve's VJP writes the caller's array; the combine kernel finishes it in place)
-    float* gpSol = gX + nx;
-    float* gpPlant = gpSol + np;
-    int* okTick = reinterpret_cast<int*>(gpPlant + np);
-    if (!h->tick_ev) HIPCHK(h, hipEventCreateWithFlags(&h->tick_ev, hipEventDisableTiming));
-    else HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));
-    int rc = cmpc_launch_plant_vjp(N, B, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState, (float)tape->plant_step,
-                                   tape->plant_substeps, dGradStateOut, dGradState, gX, gpPlant, gmPlant, rot ? grPlant : nullptr, mm ? 1 : 0,
-                                   mm ? mm->hidden : nullptr, mm ? mm->gain : nullptr, mm && mm->g_hidden ? ghPlant : nullptr,
-                                   mm && mm->g_gain ? ggPlant : nullptr, st);
-    if (const int err = launch_status(h, "tick VJP (plant)", rc)) return err;
-    if (dGradX) {
-        hipLaunchKernelGGL(cmpc_axpy_float_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, nx, dGradX, gX);
-        HIPCHK(h, hipGetLastError());
-    }
-    if (dGradListOut) {
-        rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 1, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
-                                               tape->dListT, tape->dListN, tape->dLand, tape->dOk, dGradListOut, nullptr, gX, nullptr, nullptr, nullptr, st);
-        if (const int err = launch_status(h, "tick VJP (adjust)", rc)) return err;
-    }
-    rc = rot ? cmpc_solution_vjp_rot_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, grSol, dTickSens, stream)
-             : cmpc_solution_vjp_model_device(h, tape->dX, tape->dP, tape->dLamG, gX, gpSol, gmSol, dTickSens, stream);
-    if (rc != CMPC_OK) return rc;
-    hipLaunchKernelGGL(cmpc_tick_vjp_combine_kernel, dim3(B), dim3(128), 0, st, B, N, tape->dInfo, tape->dOk, gpSol, gpPlant, gmSol, gmPlant, dGradState,
-                       dGradWrench, dGradModel, dGradP, dTickSens, okTick, rot ? grPlant : nullptr, rot ? grSol : nullptr, ghPlant, ggPlant,
-                       mm ? mm->g_hidden : nullptr, mm ? mm->g_noise : nullptr, mm ? mm->g_gain : nullptr);
-    HIPCHK(h, hipGetLastError());
-    rc = cmpc_launch_contacts_position_vjp(B, N, max_contacts, h->cfg.sampling_time, now, 2, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
-                                           tape->dListT, tape->dListN, tape->dLand, okTick, dGradListOut, gpSol, nullptr, dGradPrevList, dGradPlan, nullptr, st);
-    if (const int err = launch_status(h, "tick VJP (sample + merge)", rc)) return err;
-    if (rot) {
-        rc = cmpc_launch_contacts_orientation_vjp(B, N, max_contacts, h->cfg.sampling_time, now, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
-                                                  tape->dListT, tape->dListN, tape->dLand, okTick, dGradListRotOut, grSol, dGradPrevListRot, dGradPlanRot,
-                                                  nullptr, st);
-        if (const int err = launch_status(h, "tick VJP (orientations)", rc)) return err;
-    }
-    HIPCHK(h, hipEventRecord(h->tick_ev, st));
-    return CMPC_OK;
-}
-
-int cmpc_rollout_tick_vjp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
-                                 const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
-                                 double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, void* stream)
-{
-    return tick_vjp(h, false, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
-                    dGradP, dTickSens, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-int cmpc_rollout_tick_vjp_rot_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
-                                     const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
-                                     double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
-                                     double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, void* stream)
-{
-    return tick_vjp(h, true, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan, dGradModel,
-                    dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream);
-}
-
-int cmpc_rollout_tick_vjp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, const double* dGradStateOut,
-                                          const double* dGradListOut, const float* dGradX, double* dGradState, double* dGradPrevList, float* dGradWrench,
-                                          double* dGradPlan, double* dGradModel, float* dGradP, float* dTickSens, const double* dGradListRotOut,
-                                          double* dGradPrevListRot, double* dGradPlanRot, double* dGradRot, const float* dHiddenWrench, const float* dForceGain,
-                                          double* dGradHidden, float* dGradNoise, double* dGradGain, void* stream)
-{
-    const TickMismatch mm{dHiddenWrench, dForceGain, dGradHidden, dGradNoise, dGradGain};
-    return tick_vjp(h, dGradPrevListRot != nullptr, max_contacts, now, tape, dGradStateOut, dGradListOut, dGradX, dGradState, dGradPrevList, dGradWrench, dGradPlan,
-                    dGradModel, dGradP, dTickSens, dGradListRotOut, dGradPrevListRot, dGradPlanRot, dGradRot, stream, &mm);
-}
-
-// ---- the reverse walk on the device tape (include/cmpc.h, cmpc_rollout_walk_vjp_device): gate, tick VJP, gate, ..., gate ----
-static CmpcGateArgs gate_args_of(const cmpc_walk_gate* g, int nx, int np)
-{
-    return CmpcGateArgs{g->batch, g->max_contacts, g->horizon, nx, np, g->end_tick, g->do_post, g->tick_post, g->seed_state, g->tick_state, g->tick_list,
-                        g->tick_sens, g->carry_state, g->carry_list, g->wrench_row, g->grad_p_row, g->status_row, g->do_pre, g->tick_pre, g->first, g->ok_row,
-                        g->grad_x_row, g->ok_out, g->grad_x_out};
-}
-
-static int gate_check(const cmpc_walk_gate* g);
-
-// the gate with the orientation arrays: the base check, plus carry_list_rot, and tick_list_rot with the POST part
-static int gate_rot_check(const cmpc_walk_gate_rot* g)
-{
-    if (!g) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate: bad argument");
-    const int rc = gate_check(&g->base);
-    if (rc != CMPC_OK) return rc;
-    if (!g->carry_list_rot || (g->base.do_post && !g->tick_list_rot))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate: carry_list_rot is needed, and tick_list_rot with the POST part");
-    return CMPC_OK;
-}
-
-static CmpcGateArgs gate_rot_args_of(const cmpc_walk_gate_rot* g, int nx, int np)
-{
-    CmpcGateArgs a = gate_args_of(&g->base, nx, np);
-    a.t_list_rot = g->tick_list_rot; a.carry_list_rot = g->carry_list_rot; a.rot_row = g->rot_row; a.removed_row = g->removed_row;
-    return a;
-}
-
-static int gate_launch(cmpc_handle h, const CmpcGateArgs& a, void* stream)
-{
-    HIPCHK(h, hipSetDevice(h->device));
-    const int lrc = cmpc_launch_walk_vjp_gate(&a, stream_of(h, stream));
-    return launch_status(h, "reverse walk (gate)", lrc);
-}
-
-static void gate_on_host(const CmpcGateArgs& a)
-{
-    for (int b = 0; b < a.B; ++b) cmpc_walk_gate_problem(a, b);
-    const size_t wide = cmpc_walk_gate_wide_entries(&a);
-    for (size_t e = 0; e < wide; ++e) cmpc_walk_gate_wide(a, e);
-}
-
-int cmpc_rollout_walk_vjp_gate_device(cmpc_handle h, const cmpc_walk_gate* g, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: null handle");
-    const int rc = gate_check(g);
-    if (rc != CMPC_OK) return rc;
-    if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate_device: batch and horizon must be the handle's");
-    return gate_launch(h, gate_args_of(g, h->L.nx, h->L.np), stream);
-}
-
-int cmpc_rollout_walk_vjp_rot_gate_device(cmpc_handle h, const cmpc_walk_gate_rot* g, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate_device: null handle");
-    const int rc = gate_rot_check(g);
-    if (rc != CMPC_OK) return rc;
-    if (g->base.batch != h->B || g->base.horizon != h->cfg.horizon)
-        return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_gate_device: batch and horizon must be the handle's");
-    return gate_launch(h, gate_rot_args_of(g, h->L.nx, h->L.np), stream);
-}
-
-int cmpc_rollout_walk_vjp_rot_gate(const cmpc_walk_gate_rot* g)
-{
-    const int rc = gate_rot_check(g);
-    if (rc != CMPC_OK) return rc;
-    CmpcLayout L;
-    cmpc_layout_init(L, g->base.horizon);
-    gate_on_host(gate_rot_args_of(g, L.nx, L.np));
-    return CMPC_OK;
-}
-
-static int gate_check(const cmpc_walk_gate* g)
-{
-    if (!g || g->batch < 1 || g->max_contacts < 1 || g->horizon < 1 || g->horizon > CMPC_NMAX || (!g->do_post && !g->do_pre) || !g->carry_state || !g->carry_list)
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: bad argument");
-    if (g->do_post && (!g->seed_state || !g->tick_state || !g->tick_list || !g->tick_sens || !g->status_row))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: the POST part needs the seed row, the tick's outputs and the status row");
-    if (g->do_pre && (!g->ok_out || (!g->grad_x_row != !g->grad_x_out)))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_gate: the PRE part needs ok_out, and grad_x_row and grad_x_out together");
-    return CMPC_OK;
-}
-
-int cmpc_rollout_walk_vjp_gate(const cmpc_walk_gate* g)
-{
-    const int rc = gate_check(g);
-    if (rc != CMPC_OK) return rc;
-    CmpcLayout L;
-    cmpc_layout_init(L, g->horizon);
-    gate_on_host(gate_args_of(g, L.nx, L.np));
-    return CMPC_OK;
-}
-
-// the loop of both reverse walks; r: the orientation chain of cmpc_rollout_walk_vjp_rot_device (checked by the caller), or null -- then every launch and
-// every bit is what the walk without orientations always queued and gave
-static int walk_vjp(cmpc_handle h, const char* who, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                    const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream, bool mismatch = false, const cmpc_plant_mismatch* m = nullptr,
-                    const cmpc_walk_grads_mismatch* mg = nullptr)
-{
-    const std::string name(who);
-    {
-        const int mrc = mismatch_check(h, who, m);
-        if (mrc != CMPC_OK) return mrc;
-    }
-    if (!h || !g || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, name + ": null argument or incomplete tape");
-    if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows)
-        return fail(h, CMPC_ERR_ARG, name + ": bad argument (the rows must lie inside the tape)");
-    if (!g->dGradStates || !g->dCarryState || !g->dCarryList || !g->dStatus)
-        return fail(h, CMPC_ERR_ARG, name + ": dGradStates, the two carries and dStatus are needed");
-    if (row0 == 0 && !tape->first_row_is_first_tick)
-        return fail(h, CMPC_ERR_ARG, name + ": row 0 is not a first tick and has no row before it to take the previous lists from");
-    HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream_of(h, stream);
-    const int B = h->B, N = h->cfg.horizon, M = max_contacts;
-    const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nl = (size_t)B * 6 * M, nt = (size_t)B * 4 * M;
-    if (!h->dWalkWs || h->walk_ws_M < M) {
-        if (h->dWalkWs) {   // (a larger max_contacts: launches that read the old workspace may still be queued)
-            HIPCHK(h, hipDeviceSynchronize());
-            hipFree(h->dWalkWs);
-            h->dWalkWs = nullptr; h->walk_ws_M = 0;
-        }
-        // (sized for the rotation entry whichever entry runs first: the second list buffer is the tick's dGradPrevListRot)
-        HIPCHK(h, hipMalloc(&h->dWalkWs, sizeof(double) * ((size_t)B * 9 + 2 * nl) + sizeof(float) * (nx + (size_t)B * CMPC_SENS) + sizeof(int) * (size_t)B));
-        h->walk_ws_M = M;
-    }
-    double* wsState = reinterpret_cast<double*>(h->dWalkWs);
-    double* wsList = wsState + (size_t)B * 9;
-    double* wsListRot = wsList + (size_t)B * 6 * h->walk_ws_M;
-    float* wsGx = reinterpret_cast<float*>(wsListRot + (size_t)B * 6 * h->walk_ws_M);
-    float* wsSens = wsGx + nx;
-    int* wsOk = reinterpret_cast<int*>(wsSens + (size_t)B * CMPC_SENS);
-    if (h->tick_ev) HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));   // (the gate writes workspace an earlier call on another stream may still read)
-    CmpcGateArgs a{};
-    a.B = B; a.M = M; a.N = N; a.nx = h->L.nx; a.np = h->L.np;
-    a.end_tick = dEndTick;
-    a.t_state = wsState; a.t_list = wsList; a.t_sens = wsSens;
-    a.carry_state = g->dCarryState; a.carry_list = g->dCarryList;
-    a.ok_out = wsOk; a.gx_out = g->dGradX ? wsGx : nullptr;
-    if (r) { a.t_list_rot = wsListRot; a.carry_list_rot = r->dCarryListRot; }
-    int rc = CMPC_OK;
-    for (int i = ticks; i >= 0 && rc == CMPC_OK; --i) {
-        // the gate step between tick i (POST: i < ticks) and tick i - 1 (PRE: i > 0), fused into one launch
-        const size_t rq = (size_t)(row0 + i), rp = (size_t)(row0 + i - 1);
-        a.do_post = i < ticks; a.tick_post = tick0 + i;
-        if (a.do_post) {
-            a.seed_state = g->dGradStates + rq * B * 9;
-            a.wrench_row = g->dGradWrench ? g->dGradWrench + rq * B * 6 * N : nullptr;
-            a.gp_row = g->dGradP ? g->dGradP + rq * np : nullptr;
-            a.status_row = g->dStatus + rq * B;
-            if (r) {
-                a.rot_row = r->dGradRot ? r->dGradRot + rq * B * 6 * N : nullptr;
-                a.removed_row = r->dRemoved ? r->dRemoved + rq * B : nullptr;
-            }
-        }
-        a.do_pre = i > 0; a.tick_pre = tick0 + i - 1; a.first = i == ticks;
-        if (a.do_pre) {
-            a.ok_row = tape->dOk + rp * B;
-            a.gx_row = g->dGradX ? g->dGradX + rp * nx : nullptr;
-        }
-        const int lrc = cmpc_launch_walk_vjp_gate(&a, st);
-        if (const int err = launch_status(h, "reverse walk (gate)", lrc)) return err;
-        if (i == 0) break;
-        const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
-        cmpc_tick_tape tt{};
-        tt.dX = tape->dX + rp * nx; tt.dP = tape->dP + rp * np; tt.dLamG = tape->dLamG + rp * ng;
-        tt.dState = tape->dStates + rp * B * 9; tt.dInfo = tape->dInfo + rp * B * CMPC_INFO;
-        tt.dOk = wsOk; tt.dLand = tape->dLand + rp * B * 2;
-        tt.dPlanT = tape->dPlanT + rp * nt; tt.dPlanN = tape->dPlanN + rp * B * 2;
-        tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
-        tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
-        tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
-        // the mismatch entry: tick rp ran under its own schedule rows; its gradient rows are written whether or not the tick lay inside a schedule's range
-        TickMismatch mm{};
-        if (mismatch) {
-            const float* unused;
-            mismatch_rows(m, B, tick0 + i - 1, &mm.hidden, &unused, &mm.gain);
-            if (mg) {
-                mm.g_hidden = mg->dGradHidden ? mg->dGradHidden + rp * B * 6 : nullptr;
-                mm.g_noise = mg->dGradNoise ? mg->dGradNoise + rp * B * 9 : nullptr;
-                mm.g_gain = mg->dGradGain;
-            }
-        }
-        rc = tick_vjp(h, r != nullptr, M, (double)(tick0 + i - 1) * h->cfg.sampling_time, &tt, g->dCarryState, g->dCarryList, a.gx_out, wsState, wsList,
-                      g->dGradWrench ? g->dGradWrench + rp * B * 6 * N : nullptr, g->dGradPlan, g->dGradModel, g->dGradP ? g->dGradP + rp * np : nullptr, wsSens,
-                      r ? r->dCarryListRot : nullptr, r ? wsListRot : nullptr, r ? r->dGradPlanRot : nullptr,
-                      r && r->dGradRot ? r->dGradRot + rp * B * 6 * N : nullptr, stream, mismatch ? &mm : nullptr);
-    }
-    if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
-    return rc;
-}
-
-int cmpc_rollout_walk_vjp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                 const cmpc_walk_grads* g, void* stream)
-{
-    return walk_vjp(h, "cmpc_rollout_walk_vjp_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, nullptr, stream);
-}
-
-int cmpc_rollout_walk_vjp_rot_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                     const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, void* stream)
-{
-    if (!r || !r->dCarryListRot) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_rot_device: r and its dCarryListRot are needed");
-    return walk_vjp(h, "cmpc_rollout_walk_vjp_rot_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, r, stream);
-}
-
-int cmpc_rollout_walk_vjp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                          const cmpc_walk_grads* g, const cmpc_walk_grads_rot* r, const cmpc_plant_mismatch* m,
-                                          const cmpc_walk_grads_mismatch* mg, void* stream)
-{
-    if (r && !r->dCarryListRot) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_vjp_mismatch_device: r needs its dCarryListRot");
-    return walk_vjp(h, "cmpc_rollout_walk_vjp_mismatch_device", max_contacts, tick0, ticks, tape, row0, dEndTick, g, r, stream, true, m, mg);
-}
-
-// ---- one tick FORWARDS in k directions (include/cmpc.h): list JVP (merge + sample) -> the p direction assembled (cmpc_tick_jvp_assemble_kernel) ->
-// cmpc_solution_jvp_rot_device -> the flags (cmpc_tick_jvp_flag_kernel) -> list JVP (adjust) -> the k-column plant JVP, on one stream ----
-namespace {
-// one workgroup per (problem, column): the column's p direction, float32.  The list kernel has written the nominalPos / currentPos rows; here the state
-// direction goes to com0 / dcom0 / h0 (cmpc_write_state_device's rows, rounded to float32), the wrench direction to the fExt / tauExt rows, every other row
-// is zero, and the caller's extra p direction is added to all of them.  d_noise[B][k][9] (the mismatch entry; null otherwise): the direction of the sensor
-// noise, added to the rounded state direction in ONE float32 add as the forward's setState adds the noise -- it reaches the solve and nothing else.
-__global__ __launch_bounds__(128) void cmpc_tick_jvp_assemble_kernel(int N, const double* __restrict__ d_state, const float* __restrict__ d_wrench,
-                                                                     const float* __restrict__ d_extra, float* __restrict__ d_p,
-                                                                     const float* __restrict__ d_noise)
-{
-    const size_t col = blockIdx.x;
-    const CmpcIdx L{N};
-    const int np = L.np();
-    float* dp = d_p + col * np;
-    for (int e = threadIdx.x; e < np; e += 128) {
-        float v = 0.f;
-        const bool listed = (e >= L.pNom(0) && e < L.pNom(0) + 3 * N + 6) || (e >= L.pNom(1) && e < L.pNom(1) + 3 * N + 6);
-        if (listed) v = dp[e];
-        else if (e >= L.pCom0() && e < L.pCom0() + 9) {
-            v = d_state ? (float)d_state[col * 9 + (e - L.pCom0())] : 0.f;
-            if (d_noise) v = v + d_noise[col * 9 + (e - L.pCom0())];
-        }
-        else if (d_wrench && e >= L.pFext() && e < L.pText()) { const int q = e - L.pFext(); v = d_wrench[(col * N + q / 3) * 6 + q % 3]; }
-        else if (d_wrench && e >= L.pText()) { const int q = e - L.pText(); v = d_wrench[(col * N + q / 3) * 6 + 3 + q % 3]; }
-        dp[e] = d_extra ? v + d_extra[col * np + e] : v;
-    }
-}
-
-// one workgroup per problem, after the solve: the tick's status with the VJP's codes and precedence (cmpc_tick_vjp_combine_kernel; 2 also for a non-finite
-// tape state).  A flagged problem gets
-// zeros in every column of dx, of the p direction and of the rotation direction, and ok = 0 (the adjust part of the list kernel and the plant kernel behind
-// this one then write zeros too); otherwise stage 0 of the rotation direction is gathered for the plant.
-__global__ __launch_bounds__(128) void cmpc_tick_jvp_flag_kernel(int N, int K, const float* __restrict__ info, const int* __restrict__ ok,
-                                                                 const float* __restrict__ state_in, float* __restrict__ sens, float* __restrict__ d_x,
-                                                                 float* __restrict__ d_p, double* __restrict__ d_rot, double* __restrict__ d_rot0,
-                                                                 int* __restrict__ ok_out)
-{
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const CmpcIdx L{N};
-    const float s0 = sens[(size_t)b * CMPC_SENS];
-    int status = s0 == s0 ? (int)s0 : 2;
-    // (the state the tick started from is an input of the plant alone here: in reverse a non-finite one reaches the solve through the plant VJP and comes
-    //  back as status 2; forwards it is looked at directly, for the same word)
-    bool finite = true;
-    for (int e = 0; e < 9; ++e) finite = finite && __builtin_isfinite(state_in[(size_t)b * 9 + e]);
-    if (status < 2 && !finite) status = 2;
-    if (status < 2 && info[(size_t)b * CMPC_INFO_N + 5] != 0.f) status = 4;
-    if (ok && ok[b] == 0) status = 5;
-    __syncthreads();   // (every thread has read the status word before thread 0 rewrites it)
-    if (status != 0) {
-        for (size_t e = tid; e < (size_t)K * L.nx(); e += 128) d_x[(size_t)b * K * L.nx() + e] = 0.f;
-        for (size_t e = tid; e < (size_t)K * L.np(); e += 128) d_p[(size_t)b * K * L.np() + e] = 0.f;
-        if (d_rot) for (size_t e = tid; e < (size_t)K * 6 * N; e += 128) d_rot[(size_t)b * K * 6 * N + e] = 0.0;
-        if (d_rot) for (int e = tid; e < K * 6; e += 128) d_rot0[(size_t)b * K * 6 + e] = 0.0;
-    } else if (d_rot) {
-        for (int e = tid; e < K * 6; e += 128)     // e = (column * 2 + foot) * 3 + axis
-            d_rot0[(size_t)b * K * 6 + e] = d_rot[((size_t)b * K * 2 + e / 3) * 3 * N + e % 3];
-    }
-    if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
-}
-}  // namespace
-
-// (all four mismatch pointers null: the instantiation without the mismatch, which is the kernel as it was before the mismatch existed)
-static int plant_jvp_cols(cmpc_handle h, const char* who, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
-                          const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
-                          const float* dHiddenWrench, const float* dForceGain, const double* dDirHidden, const double* dDirGain, double* dDirStateOut,
-                          void* stream)
-{
-    if (!h || !dX || !dP || !dStateIn || !dDirState || !dDirStateOut || !(step > 0) || substeps < 1 || k < 1)
-        return fail(h, CMPC_ERR_ARG, std::string(who) + ": bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    const bool mm = dHiddenWrench || dForceGain || dDirHidden || dDirGain;
-    int rc = cmpc_launch_plant_jvp_cols_mismatch(h->cfg.horizon, h->B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), dX, dP, dStateIn, (float)step,
-                                                 substeps, dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr, dDirStateOut, mm ? 1 : 0, dHiddenWrench,
-                                                 dForceGain, dDirHidden, dDirGain, stream_of(h, stream));
-    return launch_status(h, "plant JVP (columns)", rc);
-}
-
-int cmpc_plant_step_jvp_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
-                                    const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
-                                    double* dDirStateOut, void* stream)
-{
-    return plant_jvp_cols(h, "cmpc_plant_step_jvp_cols_device", dX, dP, dStateIn, step, substeps, k, dDirState, dDirX, dDirP, dDirModel, dDirRot0, nullptr,
-                          nullptr, nullptr, nullptr, dDirStateOut, stream);
-}
-
-int cmpc_plant_step_jvp_mismatch_cols_device(cmpc_handle h, const float* dX, const float* dP, const float* dStateIn, double step, int substeps, int k,
-                                             const double* dDirState, const float* dDirX, const float* dDirP, const double* dDirModel, const double* dDirRot0,
-                                             const float* dHiddenWrench, const float* dForceGain, const double* dDirHidden, const double* dDirGain,
-                                             double* dDirStateOut, void* stream)
-{
-    return plant_jvp_cols(h, "cmpc_plant_step_jvp_mismatch_cols_device", dX, dP, dStateIn, step, substeps, k, dDirState, dDirX, dDirP, dDirModel, dDirRot0,
-                          dHiddenWrench, dForceGain, dDirHidden, dDirGain, dDirStateOut, stream);
-}
-
-int cmpc_contacts_jvp_device(cmpc_handle h, int max_contacts, double now, int phase, int force_sample_time, int k, const double* dPlanT, const int* dPlanN,
-                             const double* dPrevT, const int* dPrevN, const double* dListT, const int* dListN, const int* dLand, const int* dOk,
-                             const double* dDirPrevList, const double* dDirPrevListRot, const double* dDirPlan, const double* dDirPlanRot, const float* dDirX,
-                             double* dDirList, double* dDirListRot, float* dDirP, double* dDirRot, int* dStatus, void* stream)
-{
-    if (!h || max_contacts < 1 || phase < 1 || phase > 3 || k < 1 || !dListT || !dListN || !dDirList)
-        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: bad argument");
-    const bool merge = dPrevT || dPrevN;
-    if ((phase & 1) && merge && (!dPrevT || !dPrevN || !dPlanT || !dPlanN))
-        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: a merge tick needs the planner's and the previous tick's times and counts");
-    if (dDirList == dDirPrevList || (dDirListRot && dDirListRot == dDirPrevListRot))
-        return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: the outgoing list's directions must not alias the previous list's");
-    long long dt_ns = 0;
-    if (force_sample_time) {
-        dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, "cmpc_contacts_jvp_device: force_sample_time needs a sampling time of at least 1 ns");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = cmpc_launch_contacts_jvp(h->B, h->cfg.horizon, max_contacts, k, h->cfg.sampling_time, now, phase, dt_ns, dPlanT, dPlanN, dPrevT, dPrevN, dListT,
-                                      dListN, dLand, dOk, dDirPrevList, dDirPrevListRot, dDirPlan, dDirPlanRot, dDirX, dDirList, dDirListRot, dDirP, dDirRot,
-                                      dStatus, stream_of(h, stream));
-    return launch_status(h, "list JVP", rc);
-}
-
-// the mismatch entry's further arguments (cmpc_rollout_tick_jvp_mismatch_device); null in tick_jvp: the launches and bits of the entry before it
-struct TickMismatchDirs {
-    const float* hidden; const float* gain;                               // this tick's hidden-wrench row [B][6] and the gain [B], either may be null
-    const double* d_hidden; const float* d_noise; const double* d_gain;   // directions [B][k][6], [B][k][9], [B][k], each may be null
-};
-
-// (shared by the public entry points and the forward walk, as tick_vjp is)
-static int tick_jvp(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in, const cmpc_tick_dirs_out* out,
-                    float* dTickSens, void* stream, const TickMismatchDirs* mm = nullptr, const char* who = "cmpc_rollout_tick_jvp_device")
-{
-    const std::string name(who);
-    if (!h || !tape || max_contacts < 1 || k < 1 || !out || !out->dDirStateOut || !out->dDirList || !dTickSens)
-        return fail(h, CMPC_ERR_ARG, name + ": null argument");
-    if (!tape->dX || !tape->dP || !tape->dLamG || !tape->dState || !tape->dInfo || !tape->dLand || !tape->dListT || !tape->dListN ||
-        !(tape->plant_step > 0) || tape->plant_substeps < 1)
-        return fail(h, CMPC_ERR_ARG, name + ": incomplete tape");
-    const bool merge = tape->dPrevT || tape->dPrevN;
-    if (merge && (!tape->dPrevT || !tape->dPrevN || !tape->dPlanT || !tape->dPlanN))
-        return fail(h, CMPC_ERR_ARG, name + ": a merge tick's tape needs the planner's and the previous tick's times and counts");
-    const cmpc_tick_dirs none = {};
-    if (!in) in = &none;
-    if (out->dDirList == in->dDirPrevList || (out->dDirListRot && out->dDirListRot == in->dDirPrevListRot))
-        return fail(h, CMPC_ERR_ARG, name + ": the outgoing list's directions must not alias the previous list's");
-    long long dt_ns = 0;
-    if (tape->force_sample_time) {
-        dt_ns = snap_dt_ns(h->cfg.sampling_time);
-        if (dt_ns < 1) return fail(h, CMPC_ERR_ARG, name + ": force_sample_time needs a sampling time of at least 1 ns");
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream_of(h, stream);
-    const int B = h->B, N = h->cfg.horizon;
-    const size_t cols = (size_t)B * k, nx = h->L.nx, np = h->L.np;
-    if (k > h->tick_jvp_cols) {     // (hipFree waits for the device: no earlier call still reads the smaller workspace)
-        if (h->dTickJvpWs) HIPCHK(h, hipFree(h->dTickJvpWs));
-        h->dTickJvpWs = nullptr; h->tick_jvp_cols = 0;
-        HIPCHK(h, hipMalloc(&h->dTickJvpWs, cols * (sizeof(double) * (6 * (size_t)N + 15) + sizeof(float) * (nx + np)) + sizeof(int) * (size_t)B));
-        h->tick_jvp_cols = k;
-    }
-    // (carved for this call's k: the arrays are [B][k][...] without gaps)
-    double* wsRot = reinterpret_cast<double*>(h->dTickJvpWs);
-    double* wsRot0 = wsRot + cols * 6 * N;
-    double* wsState = wsRot0 + cols * 6;
-    float* wsX = reinterpret_cast<float*>(wsState + cols * 9);
-    float* wsP = wsX + cols * nx;
-    int* okTick = reinterpret_cast<int*>(wsP + cols * np);
-    const bool rot = in->dDirPrevListRot || in->dDirPlanRot;
-    double* dRot = !rot ? nullptr : out->dDirRot ? out->dDirRot : wsRot;
-    float* dDX = out->dDirX ? out->dDirX : wsX;
-    float* dPF = out->dDirPFull ? out->dDirPFull : wsP;
-    if (!h->tick_ev) HIPCHK(h, hipEventCreateWithFlags(&h->tick_ev, hipEventDisableTiming));
-    else HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));
-    const double* dState = in->dDirState;
-    if (!dState) {
-        HIPCHK(h, hipMemsetAsync(wsState, 0, sizeof(double) * cols * 9, st));
-        dState = wsState;
-    }
-    if (!rot && out->dDirRot) HIPCHK(h, hipMemsetAsync(out->dDirRot, 0, sizeof(double) * cols * 6 * N, st));
-    int rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 1, dt_ns, tape->dPlanT, tape->dPlanN, tape->dPrevT, tape->dPrevN,
-                                      tape->dListT, tape->dListN, tape->dLand, tape->dOk, in->dDirPrevList, in->dDirPrevListRot, in->dDirPlan, in->dDirPlanRot,
-                                      nullptr, out->dDirList, out->dDirListRot, dPF, dRot, nullptr, st);
-    if (const int err = launch_status(h, "tick JVP (merge + sample)", rc)) return err;
-    hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, st, N, in->dDirState, in->dDirWrench, in->dDirP, dPF,
-                       mm ? mm->d_noise : (const float*)nullptr);
-    HIPCHK(h, hipGetLastError());
-    rc = cmpc_solution_jvp_rot_device(h, tape->dX, tape->dP, tape->dLamG, dPF, in->dDirModel, dRot, k, dDX, dTickSens, stream);
-    if (rc != CMPC_OK) return rc;
-    hipLaunchKernelGGL(cmpc_tick_jvp_flag_kernel, dim3(B), dim3(128), 0, st, N, k, tape->dInfo, tape->dOk, tape->dState, dTickSens, dDX, dPF, dRot, wsRot0, okTick);
-    HIPCHK(h, hipGetLastError());
-    rc = cmpc_launch_contacts_jvp(B, N, max_contacts, k, h->cfg.sampling_time, now, 2, dt_ns, nullptr, nullptr, nullptr, nullptr, tape->dListT, tape->dListN,
-                                  tape->dLand, okTick, nullptr, nullptr, nullptr, nullptr, dDX, out->dDirList, out->dDirListRot, nullptr, nullptr, nullptr, st);
-    if (const int err = launch_status(h, "tick JVP (adjust)", rc)) return err;
-    // (the mismatch entry: the plant's partials at the gained forces and the summed wrench, the tick's own rows; the noise direction does not come here)
-    rc = cmpc_launch_plant_jvp_cols_mismatch(N, B, k, (float)h->cfg.gravity, model_corners(h), corners_stride(h), tape->dX, tape->dP, tape->dState,
-                                             (float)tape->plant_step, tape->plant_substeps, dState, dDX, dPF, in->dDirModel, rot ? wsRot0 : nullptr, okTick,
-                                             out->dDirStateOut, mm ? 1 : 0, mm ? mm->hidden : nullptr, mm ? mm->gain : nullptr, mm ? mm->d_hidden : nullptr,
-                                             mm ? mm->d_gain : nullptr, st);
-    if (const int err = launch_status(h, "tick JVP (plant)", rc)) return err;
-    HIPCHK(h, hipEventRecord(h->tick_ev, st));
-    return CMPC_OK;
-}
-
-int cmpc_rollout_tick_jvp_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
-                                 const cmpc_tick_dirs_out* out, float* dTickSens, void* stream)
-{
-    return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream);
-}
-
-int cmpc_rollout_tick_jvp_mismatch_device(cmpc_handle h, int max_contacts, double now, const cmpc_tick_tape* tape, int k, const cmpc_tick_dirs* in,
-                                          const cmpc_tick_dirs_out* out, float* dTickSens, const float* dHiddenWrench, const float* dForceGain,
-                                          const cmpc_tick_dirs_mismatch* md, void* stream)
-{
-    const TickMismatchDirs mm{dHiddenWrench, dForceGain, md ? md->dDirHidden : nullptr, md ? md->dDirNoise : nullptr, md ? md->dDirGain : nullptr};
-    if (!mm.hidden && !mm.gain && !mm.d_hidden && !mm.d_noise && !mm.d_gain)   // (nothing of a mismatch: the plain tick, bit for bit)
-        return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream, nullptr, "cmpc_rollout_tick_jvp_mismatch_device");
-    return tick_jvp(h, max_contacts, now, tape, k, in, out, dTickSens, stream, &mm, "cmpc_rollout_tick_jvp_mismatch_device");
-}
-
-// ---- the forward walk on the device tape (include/cmpc.h, cmpc_rollout_walk_jvp_device): gate, tick JVP, gate, ..., gate ----
-static CmpcJvpGateArgs jvp_gate_args_of(const cmpc_walk_jvp_gate* g, int nx)
-{
-    return CmpcJvpGateArgs{g->batch, g->max_contacts, g->k, nx, g->end_tick, g->do_post, g->tick_post, g->tick_sens, g->state_out, g->list_out,
-                           g->list_rot_out, g->x_row, g->status_row, g->removed_row, g->do_pre, g->tick_pre, g->first, g->ok_row, g->ok_out, g->first_state,
-                           g->first_list, g->first_list_rot};
-}
-
-static int jvp_gate_check(const cmpc_walk_jvp_gate* g)
-{
-    if (!g || g->batch < 1 || g->max_contacts < 1 || g->horizon < 1 || g->horizon > CMPC_NMAX || g->k < 1 || (!g->do_post && !g->do_pre))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: bad argument");
-    if (g->do_post && (!g->tick_sens || !g->state_out || !g->list_out || !g->status_row))
-        return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: the POST part needs the tick's dTickSens, state and list directions and the status row");
-    if (g->do_pre && !g->ok_out) return fail(nullptr, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate: the PRE part needs ok_out");
-    return CMPC_OK;
-}
-
-int cmpc_rollout_walk_jvp_gate(const cmpc_walk_jvp_gate* g)
-{
-    const int rc = jvp_gate_check(g);
-    if (rc != CMPC_OK) return rc;
-    CmpcLayout L;
-    cmpc_layout_init(L, g->horizon);
-    const CmpcJvpGateArgs a = jvp_gate_args_of(g, L.nx);
-    for (size_t c = 0; c < (size_t)g->batch * g->k; ++c) cmpc_walk_jvp_gate_column(a, c);
-    const size_t wide = cmpc_walk_jvp_gate_wide_entries(&a);
-    for (size_t e = 0; e < wide; ++e) cmpc_walk_jvp_gate_wide(a, e);
-    return CMPC_OK;
-}
-
-int cmpc_rollout_walk_jvp_gate_device(cmpc_handle h, const cmpc_walk_jvp_gate* g, void* stream)
-{
-    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate_device: null handle");
-    const int rc = jvp_gate_check(g);
-    if (rc != CMPC_OK) return rc;
-    if (g->batch != h->B || g->horizon != h->cfg.horizon) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_jvp_gate_device: batch and horizon must be the handle's");
-    HIPCHK(h, hipSetDevice(h->device));
-    const CmpcJvpGateArgs a = jvp_gate_args_of(g, h->L.nx);
-    const int lrc = cmpc_launch_walk_jvp_gate(&a, stream_of(h, stream));
-    return launch_status(h, "forward walk (gate)", lrc);
-}
-
-// the loop of both forward walks; m / md: the mismatch and its directions of cmpc_rollout_walk_jvp_mismatch_device, tick_who that entry's tick -- both
-// null: every launch and every bit is what the walk without a mismatch always queued and gave
-static int walk_jvp(cmpc_handle h, const char* who, const char* tick_who, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0,
-                    const int* dEndTick, int k, const cmpc_walk_dirs* d, void* stream, const cmpc_plant_mismatch* m = nullptr,
-                    const cmpc_walk_dirs_mismatch* md = nullptr)
-{
-    const std::string name(who);
-    {
-        const int mrc = mismatch_check(h, who, m);
-        if (mrc != CMPC_OK) return mrc;
-    }
-    if (!h || !d || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, name + ": null argument or incomplete tape");
-    if (max_contacts < 1 || tick0 < 0 || ticks < 1 || row0 < 0 || (long long)row0 + ticks > tape->rows || k < 1)
-        return fail(h, CMPC_ERR_ARG, name + ": bad argument (k >= 1, and the rows must lie inside the tape)");
-    if (!d->dDirStates || !d->dCarryList || !d->dStatus)
-        return fail(h, CMPC_ERR_ARG, name + ": dDirStates, dCarryList and dStatus are needed");
-    if (d->dDirPlanRot && !d->dCarryListRot)
-        return fail(h, CMPC_ERR_ARG, name + ": the planner's orientation directions need dCarryListRot to carry them");
-    if (row0 == 0 && !tape->first_row_is_first_tick)
-        return fail(h, CMPC_ERR_ARG, name + ": row 0 is not a first tick and has no row before it to take the previous lists from");
-    HIPCHK(h, hipSetDevice(h->device));
-    const hipStream_t st = stream_of(h, stream);
-    const int B = h->B, N = h->cfg.horizon, M = max_contacts;
-    const size_t nx = (size_t)B * h->L.nx, np = (size_t)B * h->L.np, ng = (size_t)B * h->L.ng, nt = (size_t)B * 4 * M;
-    const size_t cols = (size_t)B * k, nl = cols * 6 * M;
-    if (!h->dWalkJvpWs || h->walk_jvp_cols < k || h->walk_jvp_M < M) {
-        const int kk = k > h->walk_jvp_cols ? k : h->walk_jvp_cols, mm = M > h->walk_jvp_M ? M : h->walk_jvp_M;
-        if (h->dWalkJvpWs) {   // (a larger k or max_contacts: launches that read the old workspace may still be queued)
-            HIPCHK(h, hipDeviceSynchronize());
-            hipFree(h->dWalkJvpWs);
-            h->dWalkJvpWs = nullptr; h->walk_jvp_cols = 0; h->walk_jvp_M = 0;
-        }
-        HIPCHK(h, hipMalloc(&h->dWalkJvpWs, sizeof(double) * 2 * (size_t)B * kk * 6 * mm + sizeof(float) * (size_t)B * CMPC_SENS + sizeof(int) * (size_t)B));
-        h->walk_jvp_cols = kk; h->walk_jvp_M = mm;
-    }
-    // (the two list buffers carved for this call's k and M; the per-problem words sit behind the full allocation)
-    double* wsList = reinterpret_cast<double*>(h->dWalkJvpWs);
-    double* wsListRot = wsList + nl;
-    float* wsSens = reinterpret_cast<float*>(wsList + 2 * (size_t)B * h->walk_jvp_cols * 6 * h->walk_jvp_M);
-    int* wsOk = reinterpret_cast<int*>(wsSens + (size_t)B * CMPC_SENS);
-    if (h->tick_ev) HIPCHK(h, hipStreamWaitEvent(st, h->tick_ev, 0));   // (the gate writes workspace an earlier call on another stream may still read)
-    const bool rot = d->dCarryListRot || d->dDirPlanRot;
-    double* cur = d->dCarryList;  double* other = wsList;               // cur: the list directions entering the next tick; the tick writes `other`
-    double* curRot = rot ? d->dCarryListRot : nullptr;  double* otherRot = rot ? wsListRot : nullptr;
-    CmpcJvpGateArgs a{};
-    a.B = B; a.M = M; a.K = k; a.nx = h->L.nx;
-    a.end_tick = dEndTick;
-    a.t_sens = wsSens; a.ok_out = wsOk;
-    int rc = CMPC_OK;
-    for (int i = 0; i <= ticks && rc == CMPC_OK; ++i) {
-        // the gate step between tick i - 1 (POST: i > 0) and tick i (PRE: i < ticks), fused into one launch
-        const size_t rq = (size_t)(row0 + i - 1), rp = (size_t)(row0 + i);
-        a.do_post = i > 0; a.tick_post = tick0 + i - 1;
-        if (a.do_post) {
-            a.state_out = d->dDirStates + (rq + 1) * cols * 9;
-            a.list_out = cur; a.list_rot_out = curRot;     // (what tick i - 1 wrote: the buffers were swapped behind it)
-            a.x_row = d->dDirX ? d->dDirX + rq * (size_t)k * nx : nullptr;
-            a.status_row = d->dStatus + rq * B;
-            a.removed_row = d->dRemoved ? d->dRemoved + rq * B : nullptr;
-        }
-        a.do_pre = i < ticks; a.tick_pre = tick0 + i; a.first = i == 0;
-        a.ok_row = a.do_pre ? tape->dOk + rp * B : nullptr;
-        a.first_state = a.first ? d->dDirStates + rp * cols * 9 : nullptr;
-        a.first_list = a.first ? d->dCarryList : nullptr;
-        a.first_list_rot = a.first ? curRot : nullptr;
-        const int lrc = cmpc_launch_walk_jvp_gate(&a, st);
-        if (const int err = launch_status(h, "forward walk (gate)", lrc)) return err;
-        if (i == ticks) break;
-        const bool first_tick = rp == 0;   // (row 0 of a tape whose first row is a first tick: checked above)
-        cmpc_tick_tape tt{};
-        tt.dX = tape->dX + rp * nx; tt.dP = tape->dP + rp * np; tt.dLamG = tape->dLamG + rp * ng;
-        tt.dState = tape->dStates + rp * B * 9; tt.dInfo = tape->dInfo + rp * B * CMPC_INFO;
-        tt.dOk = wsOk; tt.dLand = tape->dLand + rp * B * 2;
-        tt.dPlanT = tape->dPlanT + rp * nt; tt.dPlanN = tape->dPlanN + rp * B * 2;
-        tt.dPrevT = first_tick ? nullptr : tape->dListT + (rp - 1) * nt; tt.dPrevN = first_tick ? nullptr : tape->dListN + (rp - 1) * B * 2;
-        tt.dListT = tape->dListT + rp * nt; tt.dListN = tape->dListN + rp * B * 2;
-        tt.plant_step = tape->plant_step; tt.plant_substeps = tape->plant_substeps; tt.force_sample_time = tape->force_sample_time;
-        cmpc_tick_dirs in{};
-        in.dDirState = d->dDirStates + rp * cols * 9;
-        in.dDirPrevList = cur; in.dDirPrevListRot = curRot;
-        in.dDirPlan = d->dDirPlan; in.dDirPlanRot = d->dDirPlanRot;
-        in.dDirWrench = d->dDirWrench ? d->dDirWrench + rp * cols * 6 * N : nullptr;
-        in.dDirModel = d->dDirModel;
-        in.dDirP = d->dDirP ? d->dDirP + rp * (size_t)k * np : nullptr;
-        cmpc_tick_dirs_out out{};
-        out.dDirStateOut = d->dDirStates + (rp + 1) * cols * 9;
-        out.dDirList = other; out.dDirListRot = otherRot;
-        out.dDirX = d->dDirX ? d->dDirX + rp * (size_t)k * nx : nullptr;
-        // the mismatch entry: tick rp ran under its own schedule row (selected by tick number); its direction rows are the tape row's, applied whether or
-        // not the tick lay inside the schedule's range
-        TickMismatchDirs mm{};
-        const float* unused;
-        mismatch_rows(m, B, tick0 + i, &mm.hidden, &unused, &mm.gain);
-        if (md) {
-            mm.d_hidden = md->dDirHidden ? md->dDirHidden + rp * cols * 6 : nullptr;
-            mm.d_noise = md->dDirNoise ? md->dDirNoise + rp * cols * 9 : nullptr;
-            mm.d_gain = md->dDirGain;
-        }
-        // (a tick with no row, no gain and no direction is the plain tick: the rule of cmpc_rollout_tick_jvp_mismatch_device, so walk = ticks to the bit)
-        const bool plain = !mm.hidden && !mm.gain && !mm.d_hidden && !mm.d_noise && !mm.d_gain;
-        rc = tick_jvp(h, M, (double)(tick0 + i) * h->cfg.sampling_time, &tt, k, &in, &out, wsSens, stream, plain ? nullptr : &mm, tick_who);
-        std::swap(cur, other); std::swap(curRot, otherRot);
-    }
-    if (rc == CMPC_OK && cur != d->dCarryList) {     // (an odd number of ticks: the lists leaving the last row sit in the workspace)
-        HIPCHK(h, hipMemcpyAsync(d->dCarryList, cur, sizeof(double) * nl, hipMemcpyDeviceToDevice, st));
-        if (rot) HIPCHK(h, hipMemcpyAsync(d->dCarryListRot, curRot, sizeof(double) * nl, hipMemcpyDeviceToDevice, st));
-    }
-    if (rc == CMPC_OK && h->tick_ev) HIPCHK(h, hipEventRecord(h->tick_ev, st));
-    return rc;
-}
-
-int cmpc_rollout_walk_jvp_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick, int k,
-                                 const cmpc_walk_dirs* d, void* stream)
-{
-    return walk_jvp(h, "cmpc_rollout_walk_jvp_device", "cmpc_rollout_tick_jvp_device", max_contacts, tick0, ticks, tape, row0, dEndTick, k, d, stream);
-}
-
-int cmpc_rollout_walk_jvp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
-                                          int k, const cmpc_walk_dirs* d, const cmpc_plant_mismatch* m, const cmpc_walk_dirs_mismatch* md, void* stream)
-{
-    return walk_jvp(h, "cmpc_rollout_walk_jvp_mismatch_device", "cmpc_rollout_tick_jvp_mismatch_device", max_contacts, tick0, ticks, tape, row0, dEndTick, k,
-                    d, stream, m, md);
 }
 
 // the handle's own contact blocks from contact lists (what the class facade's setContactPhaseList calls)
@@ -3207,12 +1341,6 @@ int cmpc_check_models(const cmpc_model* models, int batch)
         std::snprintf(val, sizeof(val), "%.17g", (&models[b].friction_coefficient)[i]);
         return fail(nullptr, CMPC_ERR_ARG, "model " + std::to_string(b) + ": " + model_field_name(i) + " = " + val + " " + rule);
     }
-    return CMPC_OK;
-}
-
-static int ensure_models(cmpc_handle h)
-{
-    if (!h->dModels) HIPCHK(h, hipMalloc(&h->dModels, sizeof(CmpcConsts) * (size_t)h->B));
     return CMPC_OK;
 }
 

@@ -974,7 +974,7 @@ __host__ __device__ inline void cmpc_refill_trial_model(const CmpcRefillTrialArg
 }
 
 // the host form's two loops (cmpc_rollout_refill_init, cmpc_rollout_refill): the slots in ascending order, the counter a plain int.  Here, and not in
-// cmpc_api.hip, so that a stand-alone host program can run them under a sanitizer without the library.
+// cmpc_api_rollout.hip, so that a stand-alone host program can run them under a sanitizer without the library.
 inline void cmpc_refill_init_host(const CmpcRefillArgs& a, int* next)
 {
     *next = 0;

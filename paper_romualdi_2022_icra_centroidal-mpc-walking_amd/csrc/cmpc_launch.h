@@ -1,6 +1,7 @@
-// The launchers and size queries that cross a translation unit: declared once, here.  cmpc_api.hip calls them; every file that
-// defines one includes this header too, so that a definition that drifts from its declaration is a compile error (extern "C" functions cannot be
-// overloaded) and not a wrong address in a kernel argument.
+// The launchers and size queries that cross a translation unit: declared once, here.  The three files of the C ABI call them (cmpc_api.hip,
+// cmpc_api_rollout.hip and cmpc_api_walk_grad.hip, through cmpc_handle.h), and no launcher reads a handle; every file that defines one includes
+// this header too, so that a definition that drifts from its declaration is a compile error (extern "C" functions cannot be overloaded) and not
+// a wrong address in a kernel argument.
 #pragma once
 #include "cmpc_contacts.h"
 #include "cmpc_device.h"
@@ -79,6 +80,15 @@ int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCorners, int c
                           const float* dStateIn, float h, int nsub, const double* dGradOut, double* dGradState, float* dGradX, float* dGradP,
                           double* dGradModel, double* dGradRot0, int mismatch, const float* dHidden, const float* dGain, double* dGradHidden,
                           double* dGradGain, hipStream_t stream);
+int cmpc_launch_axpy_float(size_t n, const float* x, float* y, hipStream_t stream);
+int cmpc_launch_tick_vjp_combine(int B, int N, const float* info, const int* ok, const float* gp_sol, const float* gp_plant, const double* gm_sol,
+                                 const double* gm_plant, double* g_state, float* g_wrench, double* g_model, float* g_p, float* sens, int* ok_out,
+                                 const double* g_rot0, double* g_rot, const double* gh_plant, const double* gg_plant, double* g_hidden, float* g_noise,
+                                 double* g_gain, hipStream_t stream);
+int cmpc_launch_tick_jvp_assemble(size_t cols, int N, const double* d_state, const float* d_wrench, const float* d_extra, float* d_p, const float* d_noise,
+                                  hipStream_t stream);
+int cmpc_launch_tick_jvp_flag(int B, int N, int K, const float* info, const int* ok, const float* state_in, float* sens, float* d_x, float* d_p, double* d_rot,
+                              double* d_rot0, int* ok_out, hipStream_t stream);
 int cmpc_launch_plant_jvp_cols(int N, int B, int K, float grav, const float* dCorners, int corners_stride, const float* dX, const float* dP,
                                const float* dStateIn, float h, int nsub, const double* dDirState, const float* dDirX, const float* dDirP,
                                const double* dDirModel, const double* dDirRot0, const int* dOk, double* dOut, hipStream_t stream);

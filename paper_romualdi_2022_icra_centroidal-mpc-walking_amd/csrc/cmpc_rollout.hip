@@ -1,8 +1,8 @@
 // The kernels of the closed-loop roll-out on gfx950 and their launchers: the plant step between two MPC ticks and its JVP / VJP, the front and back
 // kernels of a tick (everything in front of the solve, everything behind it, in plain, refill and per-trial form), the record and the outcome arrays of a
 // walk, the refill of ended slots and its restore from a snapshot, the cold start, the tape, the snapshot copy, the gates of the reverse and the forward
-// walk, the warm shift, and the compact per-problem output.  The per-problem logic they share with the host entry points is in cmpc_contacts.h; the entry points that
-// queue them are in cmpc_api.hip.
+// walk, the kernels of a tick's derivative chains, the warm shift, and the compact per-problem output.  The per-problem logic they share with the host entry
+// points is in cmpc_contacts.h; the entry points that queue them are in cmpc_api.hip, cmpc_api_rollout.hip and cmpc_api_walk_grad.hip.
 #include "cmpc_contacts.h"
 #include "cmpc_device.h"
 #include "cmpc_launch.h"
@@ -377,6 +377,126 @@ __global__ __launch_bounds__(256) void cmpc_plant_vjp_kernel(int N, int B, float
     plant_partials<MM>(N, b, grav, corners, corners_stride, X, P, state_in, h, nsub, q, hidden, gain);
     plant_vjp_problem<ROT, MM>(N, b, P, q, grad_out, grad_state, grad_x, grad_p, grad_model, grad_rot, grad_hidden, grad_gain);
 }
+
+// ---- the kernels of a tick's derivative chains that run between the plant's and the solve's (cmpc_rollout_tick_vjp_device, cmpc_rollout_tick_jvp_device) ----
+// (extern "C": the four keep the unmangled names they have in kernel traces; the enclosing namespace still keeps them out of the symbol table)
+extern "C" {
+// one workgroup per problem.  Flags first: 5 merge failed, else the sensitivity's 2 / 3 (about the inputs), else 4 when the solve's status is not 0, else the
+// sensitivity's 1; a flagged problem gets zeros
+// in every array written here and ok = 0 (the list kernel behind this one then writes zeros too and adds nothing to g_plan).  Otherwise
+// gP = gP(solve) + gP(plant: fExt_0, tauExt_0), gState += gP[com0, dcom0, h0], gWrench = the fExt / tauExt rows of gP, gModel += solve's + plant's.
+// g_rot (the rotation entry; null otherwise) holds the solve's dl/domega [B][2][N][3] and receives the plant's g_rot0[B][2][3] on stage 0.
+__global__ __launch_bounds__(128) void cmpc_tick_vjp_combine_kernel(int B, int N, const float* __restrict__ info, const int* __restrict__ ok,
+                                                                    const float* __restrict__ gp_sol, const float* __restrict__ gp_plant,
+                                                                    const double* __restrict__ gm_sol, const double* __restrict__ gm_plant,
+                                                                    double* __restrict__ g_state, float* __restrict__ g_wrench, double* __restrict__ g_model,
+                                                                    float* __restrict__ g_p, float* __restrict__ sens, int* __restrict__ ok_out,
+                                                                    const double* __restrict__ g_rot0, double* __restrict__ g_rot,
+                                                                    const double* __restrict__ gh_plant, const double* __restrict__ gg_plant,
+                                                                    double* __restrict__ g_hidden, float* __restrict__ g_noise, double* __restrict__ g_gain)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const CmpcIdx L{N};
+    const int np = L.np();
+    const float s0 = sens[(size_t)b * CMPC_SENS];
+    int status = s0 == s0 ? (int)s0 : 2;
+    if (status < 2 && info[(size_t)b * CMPC_INFO_N + 5] != 0.f) status = 4;
+    if (ok && ok[b] == 0) status = 5;
+    __syncthreads();   // (every thread has read the status word before thread 0 rewrites it)
+    const float* gs = gp_sol + (size_t)b * np;
+    const float* gq = gp_plant + (size_t)b * np;
+    if (status != 0) {
+        for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] = 0.0;
+        if (g_wrench) for (int e = tid; e < 6 * N; e += 128) g_wrench[(size_t)b * 6 * N + e] = 0.f;
+        if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = 0.f;
+        if (g_rot) for (int e = tid; e < 6 * N; e += 128) g_rot[(size_t)b * 6 * N + e] = 0.0;
+        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = 0.0;   // (the mismatch entry: zeros, and nothing added to g_gain)
+        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = 0.f;
+    } else {
+        for (int e = tid; e < 9; e += 128) g_state[(size_t)b * 9 + e] += (double)gs[L.pCom0() + e];
+        if (g_wrench)
+            for (int e = tid; e < 6 * N; e += 128) {
+                const int k = e / 6, i = e % 6;
+                const int src = (i < 3 ? L.pFext() : L.pText() - 3) + 3 * k + i;
+                g_wrench[(size_t)b * 6 * N + e] = gs[src] + gq[src];
+            }
+        if (g_p) for (int e = tid; e < np; e += 128) g_p[(size_t)b * np + e] = gs[e] + gq[e];
+        if (g_model) for (int e = tid; e < CMPC_MODEL_DOUBLES; e += 128)
+            g_model[(size_t)b * CMPC_MODEL_DOUBLES + e] += gm_sol[(size_t)b * CMPC_MODEL_DOUBLES + e] + gm_plant[(size_t)b * CMPC_MODEL_DOUBLES + e];
+        if (g_rot) for (int e = tid; e < 6; e += 128) g_rot[((size_t)b * 2 + e / 3) * 3 * N + e % 3] += g_rot0[(size_t)b * 6 + e];
+        // the mismatch entry: the hidden wrench and the gain are the plant's alone; the noise entered through setState, so its gradient is the solve's gP there
+        if (g_hidden) for (int e = tid; e < 6; e += 128) g_hidden[(size_t)b * 6 + e] = gh_plant[(size_t)b * 6 + e];
+        if (g_noise) for (int e = tid; e < 9; e += 128) g_noise[(size_t)b * 9 + e] = gs[L.pCom0() + e];
+        if (g_gain && tid == 0) g_gain[b] += gg_plant[b];
+    }
+    if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
+}
+
+__global__ __launch_bounds__(256) void cmpc_axpy_float_kernel(size_t n, const float* __restrict__ x, float* __restrict__ y)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) y[e] += x[e];
+}
+
+// one workgroup per (problem, column): the column's p direction, float32.  The list kernel has written the nominalPos / currentPos rows; here the state
+// direction goes to com0 / dcom0 / h0 (cmpc_write_state_device's rows, rounded to float32), the wrench direction to the fExt / tauExt rows, every other row
+// is zero, and the caller's extra p direction is added to all of them.  d_noise[B][k][9] (the mismatch entry; null otherwise): the direction of the sensor
+// noise, added to the rounded state direction in ONE float32 add as the forward's setState adds the noise -- it reaches the solve and nothing else.
+__global__ __launch_bounds__(128) void cmpc_tick_jvp_assemble_kernel(int N, const double* __restrict__ d_state, const float* __restrict__ d_wrench,
+                                                                     const float* __restrict__ d_extra, float* __restrict__ d_p,
+                                                                     const float* __restrict__ d_noise)
+{
+    const size_t col = blockIdx.x;
+    const CmpcIdx L{N};
+    const int np = L.np();
+    float* dp = d_p + col * np;
+    for (int e = threadIdx.x; e < np; e += 128) {
+        float v = 0.f;
+        const bool listed = (e >= L.pNom(0) && e < L.pNom(0) + 3 * N + 6) || (e >= L.pNom(1) && e < L.pNom(1) + 3 * N + 6);
+        if (listed) v = dp[e];
+        else if (e >= L.pCom0() && e < L.pCom0() + 9) {
+            v = d_state ? (float)d_state[col * 9 + (e - L.pCom0())] : 0.f;
+            if (d_noise) v = v + d_noise[col * 9 + (e - L.pCom0())];
+        }
+        else if (d_wrench && e >= L.pFext() && e < L.pText()) { const int q = e - L.pFext(); v = d_wrench[(col * N + q / 3) * 6 + q % 3]; }
+        else if (d_wrench && e >= L.pText()) { const int q = e - L.pText(); v = d_wrench[(col * N + q / 3) * 6 + 3 + q % 3]; }
+        dp[e] = d_extra ? v + d_extra[col * np + e] : v;
+    }
+}
+
+// one workgroup per problem, after the solve: the tick's status with the VJP's codes and precedence (cmpc_tick_vjp_combine_kernel; 2 also for a non-finite
+// tape state).  A flagged problem gets
+// zeros in every column of dx, of the p direction and of the rotation direction, and ok = 0 (the adjust part of the list kernel and the plant kernel behind
+// this one then write zeros too); otherwise stage 0 of the rotation direction is gathered for the plant.
+__global__ __launch_bounds__(128) void cmpc_tick_jvp_flag_kernel(int N, int K, const float* __restrict__ info, const int* __restrict__ ok,
+                                                                 const float* __restrict__ state_in, float* __restrict__ sens, float* __restrict__ d_x,
+                                                                 float* __restrict__ d_p, double* __restrict__ d_rot, double* __restrict__ d_rot0,
+                                                                 int* __restrict__ ok_out)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const CmpcIdx L{N};
+    const float s0 = sens[(size_t)b * CMPC_SENS];
+    int status = s0 == s0 ? (int)s0 : 2;
+    // (the state the tick started from is an input of the plant alone here: in reverse a non-finite one reaches the solve through the plant VJP and comes
+    //  back as status 2; forwards it is looked at directly, for the same word)
+    bool finite = true;
+    for (int e = 0; e < 9; ++e) finite = finite && __builtin_isfinite(state_in[(size_t)b * 9 + e]);
+    if (status < 2 && !finite) status = 2;
+    if (status < 2 && info[(size_t)b * CMPC_INFO_N + 5] != 0.f) status = 4;
+    if (ok && ok[b] == 0) status = 5;
+    __syncthreads();   // (every thread has read the status word before thread 0 rewrites it)
+    if (status != 0) {
+        for (size_t e = tid; e < (size_t)K * L.nx(); e += 128) d_x[(size_t)b * K * L.nx() + e] = 0.f;
+        for (size_t e = tid; e < (size_t)K * L.np(); e += 128) d_p[(size_t)b * K * L.np() + e] = 0.f;
+        if (d_rot) for (size_t e = tid; e < (size_t)K * 6 * N; e += 128) d_rot[(size_t)b * K * 6 * N + e] = 0.0;
+        if (d_rot) for (int e = tid; e < K * 6; e += 128) d_rot0[(size_t)b * K * 6 + e] = 0.0;
+    } else if (d_rot) {
+        for (int e = tid; e < K * 6; e += 128)     // e = (column * 2 + foot) * 3 + axis
+            d_rot0[(size_t)b * K * 6 + e] = d_rot[((size_t)b * K * 2 + e / 3) * 3 * N + e % 3];
+    }
+    if (tid == 0) { sens[(size_t)b * CMPC_SENS] = (float)status; ok_out[b] = status == 0 ? 1 : 0; }
+}
+}  // extern "C"
 
 // ---- the warm shift (cmpc_shift_solution_device, and the front kernel of a tick below) ----
 // warm start: previous solution shifted by one knot (last knot repeated); is_warm_start_enabled of
@@ -1232,6 +1352,38 @@ extern "C" int cmpc_launch_plant_vjp(int N, int B, float grav, const float* dCor
     if (mismatch) { if (dGradRot0) CMPC_PLANT_VJP(true, true); else CMPC_PLANT_VJP(false, true); }
     else { if (dGradRot0) CMPC_PLANT_VJP(true, false); else CMPC_PLANT_VJP(false, false); }
 #undef CMPC_PLANT_VJP
+    return (int)hipGetLastError();
+}
+
+// y[n] += x[n]
+extern "C" int cmpc_launch_axpy_float(size_t n, const float* x, float* y, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_axpy_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, x, y);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_tick_vjp_combine(int B, int N, const float* info, const int* ok, const float* gp_sol, const float* gp_plant, const double* gm_sol,
+                                            const double* gm_plant, double* g_state, float* g_wrench, double* g_model, float* g_p, float* sens, int* ok_out,
+                                            const double* g_rot0, double* g_rot, const double* gh_plant, const double* gg_plant, double* g_hidden,
+                                            float* g_noise, double* g_gain, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_tick_vjp_combine_kernel, dim3(B), dim3(128), 0, stream, B, N, info, ok, gp_sol, gp_plant, gm_sol, gm_plant, g_state, g_wrench,
+                       g_model, g_p, sens, ok_out, g_rot0, g_rot, gh_plant, gg_plant, g_hidden, g_noise, g_gain);
+    return (int)hipGetLastError();
+}
+
+// cols = B k workgroups
+extern "C" int cmpc_launch_tick_jvp_assemble(size_t cols, int N, const double* d_state, const float* d_wrench, const float* d_extra, float* d_p,
+                                             const float* d_noise, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_tick_jvp_assemble_kernel, dim3((unsigned)cols), dim3(128), 0, stream, N, d_state, d_wrench, d_extra, d_p, d_noise);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_tick_jvp_flag(int B, int N, int K, const float* info, const int* ok, const float* state_in, float* sens, float* d_x, float* d_p,
+                                         double* d_rot, double* d_rot0, int* ok_out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cmpc_tick_jvp_flag_kernel, dim3(B), dim3(128), 0, stream, N, K, info, ok, state_in, sens, d_x, d_p, d_rot, d_rot0, ok_out);
     return (int)hipGetLastError();
 }
 
