@@ -1664,6 +1664,74 @@ typedef struct cmpc_walk_dirs_mismatch {
 int cmpc_rollout_walk_jvp_mismatch_device(cmpc_handle h, int max_contacts, int tick0, int ticks, const cmpc_walk_tape* tape, int row0, const int* dEndTick,
                                           int k, const cmpc_walk_dirs* d, const cmpc_plant_mismatch* m, const cmpc_walk_dirs_mismatch* md, void* stream);
 
+/* ---- sensed pushes: a wrench sensor between the hidden schedule and the MPC (derivation: DESIGN.md 7f, "Sensed pushes") ----
+ * The two ends of the split above exist: cmpc_walk_io.dWrenchTicks tells the MPC the exact wrench and how many knots it lasts (foresight), and
+ * cmpc_plant_mismatch.dHiddenWrench is never told.  The reference does neither: WholeBodyQPBlock reads the F/T sensors each tick, mass-normalises the sum,
+ * zeroes it when the force's norm is below 0.7, and hands that reading to setState; the MPC re-plans under a wrench it measured NOW and ASSUMES into the
+ * horizon.  This section is that sensor, per problem and tick, as one small launch in front of each tick and no host read.
+ * At tick number t, problem b, with m the walk's cmpc_plant_mismatch -- every step a select, never a product with zero:
+ *   true_t    = hidden row t - m->tick_first when it is in range, else six zeros
+ *   src_t     = hidden row t - delay_ticks - m->tick_first when it is in range, else six zeros
+ *   reading_t = src_t + noise row t - m->tick_first when that is in range (ONE float32 add per component), else src_t
+ *   pass_t    = !(n2 < deadband * deadband): n2 the sum of squares of the three FORCE components, in double from the floats, left to right, not contracted;
+ *               the square of deadband formed once in double.  A force exactly on the threshold passes; a NaN reading passes, and the solve then reports
+ *               it as it does a NaN state
+ *   est_t     = pass_t ? reading_t : 0, all six components (the reference zeroes the whole wrench)
+ *   wrench rows of dP: knot k < hold_knots gets est_t (force | torque), the knots beyond get zero; all N knots are written every tick
+ *   plant_t   = pass_t ? true_t - est_t : true_t (ONE float32 subtract per component): the part of the disturbance the MPC was not told
+ * The plant integrates (F + fExt_0) + fHidden, so with plant_t as the tick's hidden row it feels est_t + (true_t - est_t): the true wrench up to the rounding
+ * of that one subtraction -- exact when the sensor is perfect, when the dead-band zeroed the reading, and whenever Sterbenz's lemma applies (est within a
+ * factor two of true).  That is why no plant kernel changes.  How the reference spreads the wrench over the horizon is inside BLF ("parity
+ * unpinned"); hold_knots is this library's documented rule, like the sampling rule for contacts.
+ * sizeof(cmpc_wrench_sensor) == 32 (LP64; the ctypes mirror is held to this number). */
+typedef struct cmpc_wrench_sensor {
+    int delay_ticks;            /* >= 0: the reading of tick t is the hidden wrench of tick t - delay_ticks */
+    int hold_knots;             /* 1 .. N: knots 0 .. hold_knots-1 of fExt / tauExt get the estimate, the rest zero */
+    double deadband;            /* the reference's 0.7 (WholeBodyQPBlock.cpp:1018); 0: off */
+    const float* dSensorNoise; int noise_ticks;   /* [noise_ticks][B][6] added to the reading, row t - m->tick_first; or NULL */
+} cmpc_wrench_sensor;
+/* Rows tick0 .. tick0 + rows - 1 of the rule.  Outputs dWrenchRows[rows][B][N][6] float (may be NULL), dPlantWrench[rows][B][6] float, dPass[rows][B] int
+ * (may be NULL).  The host form needs no handle and no GPU (its pointers, m's and s's included, are host pointers); the device form is ONE launch, one thread
+ * per (row, problem, knot), no LDS, no atomics; the two are bit-equal (one __host__ __device__ function).  Of m only tick_first, dHiddenWrench and
+ * hidden_ticks are read.  CMPC_ERR_ARG: hold_knots outside 1..N, delay_ticks < 0, a negative or NaN deadband, a noise pointer with a count < 1, a negative
+ * count, m without dHiddenWrench (or with hidden_ticks < 1), tick0 < 0, rows < 1, no dPlantWrench. */
+int cmpc_wrench_sense(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, float* wrench_rows,
+                      float* plant_wrench, int* pass);
+int cmpc_wrench_sense_device(cmpc_handle h, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, float* dWrenchRows,
+                             float* dPlantWrench, int* dPass, void* stream);
+/* cmpc_rollout_walk_mismatch_device with one sense launch (rows = 1, tick tick0 + i) in front of each tick.  The launch writes the tick's wrench rows into a
+ * [B][N][6] buffer of the handle's workspace (allocated on first use, freed with the handle; the [ticks][B][N][6] array is never materialised) and row i of
+ * the caller's dPlantWrench[ticks][B][6]; the tick then runs with that buffer as tick.dWrench and that row as its hidden row.  State noise and force gain of
+ * m apply as before.  Tick numbers are explicit, so segments, resumed walks and cmpc_set_ended_device compose with it.  s == NULL:
+ * cmpc_rollout_walk_mismatch_device bit for bit, and dPlantWrench is not written.  CMPC_ERR_ARG before anything is queued, besides that entry's and the sense
+ * entry's: io->dWrenchTicks or io->tick.dWrench set (a known push and a sensed one are not summed); s without m->dHiddenWrench or without dPlantWrench.
+ * The reverse and forward walks of a sensed tape are cmpc_rollout_walk_vjp_mismatch_device / cmpc_rollout_walk_jvp_mismatch_device with a cmpc_plant_mismatch
+ * whose hidden schedule is dPlantWrench (tick_first = tick0, hidden_ticks = ticks) and whose gain is the walk's (neither walk reads the state-noise values:
+ * the tape's dP holds the measured state); the tape already holds the wrench rows the solve saw. */
+int cmpc_rollout_walk_sensed_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                    int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, const cmpc_plant_mismatch* m,
+                                    const cmpc_wrench_sensor* s, float* dPlantWrench, void* stream);
+/* The transpose.  Inputs: the reverse walk's dGradWrench[rows][B][N][6] (float) and its dGradHidden[rows][B][6] (double) taken on the plant rows.  Outputs,
+ * both double, of the shape of the schedules themselves, written whole: dGradHiddenTrue[hidden_ticks][B][6], dGradSensorNoise[noise_ticks][B][6] (may be
+ * NULL).  With g_j = pass_j ? (sum over k < hold_knots of dGradWrench[j][k], ascending, in double) - dGradHidden[j] : 0, hidden row r receives dGradHidden of
+ * tick r + tick_first plus g of tick r + tick_first + delay_ticks, each only where that tick lies inside the call's rows; noise row r receives g of tick
+ * r + tick_first.  A gather: one thread per output element, no atomics; the branch is recomputed by the shared function, not stored.  Ended problems need no
+ * gate: the reverse walk has selected zero in both inputs from the ending tick on, and g selects. */
+int cmpc_wrench_sense_vjp(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, const float* grad_wrench,
+                          const double* grad_hidden, double* grad_hidden_true, double* grad_sensor_noise);
+int cmpc_wrench_sense_vjp_device(cmpc_handle h, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, const float* dGradWrench,
+                                 const double* dGradHidden, double* dGradHiddenTrue, double* dGradSensorNoise, void* stream);
+/* The tangent, in k columns.  Inputs dDirHidden[hidden_ticks][B][k][6] and dDirSensorNoise[noise_ticks][B][k][6] (or NULL), double; outputs
+ * dDirWrench[rows][B][k][N][6] (float: the estimate's direction rounded once) and dDirPlantWrench[rows][B][k][6] (double) -- exactly the arrays
+ * cmpc_walk_dirs.dDirWrench and cmpc_walk_dirs_mismatch.dDirHidden take.  Column j is bit-equal to a k = 1 call on column j.
+ * NOT here ("next"): per-trial sensors on refill walks; the checkpointed reverse (the delay couples rows across segments, so the fold must run
+ * once over the whole arrays); an autograd wrapper; a low-pass filter; a state-residual disturbance observer (state-dependent: a new carry in the gates);
+ * derivatives in deadband, delay_ticks and hold_knots (discrete). */
+int cmpc_wrench_sense_jvp(int horizon, int batch, int tick0, int rows, int k, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s,
+                          const double* dir_hidden, const double* dir_sensor_noise, float* dir_wrench, double* dir_plant_wrench);
+int cmpc_wrench_sense_jvp_device(cmpc_handle h, int tick0, int rows, int k, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s,
+                                 const double* dDirHidden, const double* dDirSensorNoise, float* dDirWrench, double* dDirPlantWrench, void* stream);
+
 /* is_warm_start_enabled on the device: dX0 = dXprev shifted by one knot; solve from it with cmpc_solve_device_warm
  * (cmpc_set_initial_guess(NULL, 1) + cmpc_advance do the same for the handle's own buffers) */
 int cmpc_shift_solution_device(cmpc_handle h, const float* dXprev, float* dX0, void* stream);

@@ -176,6 +176,11 @@ class CmpcPlantMismatch(C.Structure):
                 ("dForceGain", C.c_void_p)]
 
 
+class CmpcWrenchSensor(C.Structure):
+    """mirror of cmpc_wrench_sensor (include/cmpc.h): the sensor between the hidden-wrench schedule and the MPC of a sensed walk; 32 bytes"""
+    _fields_ = [("delay_ticks", C.c_int), ("hold_knots", C.c_int), ("deadband", C.c_double), ("dSensorNoise", C.c_void_p), ("noise_ticks", C.c_int)]
+
+
 class CmpcWalkGradsMismatch(C.Structure):
     """mirror of cmpc_walk_grads_mismatch (include/cmpc.h): the mismatch outputs of cmpc_rollout_walk_vjp_mismatch_device"""
     _fields_ = [(k, C.c_void_p) for k in ("dGradHidden", "dGradNoise", "dGradGain")]
@@ -280,6 +285,8 @@ EXPORTS = [
     "cmpc_set_walk_limits", "cmpc_walk_extremes_init_device", "cmpc_rollout_record_limits",
     "cmpc_walk_measures_vjp_device", "cmpc_walk_measures_vjp_fold_device", "cmpc_walk_measures_jvp_device",
     "cmpc_walk_measures_vjp", "cmpc_walk_measures_vjp_fold", "cmpc_walk_measures_jvp", "cmpc_walk_measures_jacobian",
+    "cmpc_wrench_sense", "cmpc_wrench_sense_device", "cmpc_rollout_walk_sensed_device", "cmpc_wrench_sense_vjp", "cmpc_wrench_sense_vjp_device",
+    "cmpc_wrench_sense_jvp", "cmpc_wrench_sense_jvp_device",
 ]
 
 _lib = None
@@ -457,6 +464,16 @@ def lib():
                                                                 vp, vp, C.POINTER(CmpcTickDirsMismatch), vp]
             L.cmpc_rollout_walk_jvp_mismatch_device.argtypes = [vp, i, i, i, C.POINTER(CmpcWalkTape), i, vp, i, C.POINTER(CmpcWalkDirs),
                                                                 C.POINTER(CmpcPlantMismatch), C.POINTER(CmpcWalkDirsMismatch), vp]
+        if hasattr(L, "cmpc_rollout_walk_sensed_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
+            mp, sn = C.POINTER(CmpcPlantMismatch), C.POINTER(CmpcWrenchSensor)
+            L.cmpc_wrench_sense.argtypes = [i, i, i, i, mp, sn, vp, vp, vp]
+            L.cmpc_wrench_sense_device.argtypes = [vp, i, i, mp, sn, vp, vp, vp, vp]
+            L.cmpc_rollout_walk_sensed_device.argtypes = [vp, i, i, i, i, C.POINTER(CmpcWalkIO), C.POINTER(CmpcWalkRecord), i, i, ip,
+                                                          C.POINTER(CmpcWalkTape), i, mp, sn, vp, vp]
+            L.cmpc_wrench_sense_vjp.argtypes = [i, i, i, i, mp, sn, vp, vp, vp, vp]
+            L.cmpc_wrench_sense_vjp_device.argtypes = [vp, i, i, mp, sn, vp, vp, vp, vp, vp]
+            L.cmpc_wrench_sense_jvp.argtypes = [i, i, i, i, i, mp, sn, vp, vp, vp, vp]
+            L.cmpc_wrench_sense_jvp_device.argtypes = [vp, i, i, i, mp, sn, vp, vp, vp, vp, vp]
         if hasattr(L, "cmpc_rollout_walk_refill_device"):   # (absent from earlier builds, which tools/ab_*.sh may load as a baseline)
             fl, wr = C.POINTER(CmpcWalkRefill), C.POINTER(CmpcWalkRecord)
             L.cmpc_rollout_refill_init.argtypes = [i, fl]

@@ -313,7 +313,7 @@ int cmpc_destroy(cmpc_handle h)
     if (h->hInfoPin) hipHostFree(h->hInfoPin);
     hipFree(h->dP); hipFree(h->dX0); hipFree(h->dX); hipFree(h->dInfo); hipFree(h->dConsts); hipFree(h->dScratch); hipFree(h->dBox); hipFree(h->dDuals); hipFree(h->dLamG); hipFree(h->dSensWs);
     if (h->sens_ev) hipEventDestroy(h->sens_ev);
-    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); hipFree(h->dWalkWs); hipFree(h->dWalkJvpWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
+    hipFree(h->dSnapT); hipFree(h->dSnapOk); hipFree(h->dSenseWrench); hipFree(h->dTickWs); hipFree(h->dTickJvpWs); hipFree(h->dWalkWs); hipFree(h->dWalkJvpWs); if (h->tick_ev) hipEventDestroy(h->tick_ev); hipFree(h->dExpK); hipFree(h->dModels);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);

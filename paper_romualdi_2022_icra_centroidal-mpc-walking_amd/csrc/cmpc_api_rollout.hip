@@ -9,6 +9,7 @@
 static_assert(sizeof(cmpc_walk_refill_plans) == 104, "cmpc_walk_refill_plans: the size include/cmpc.h states");
 static_assert(sizeof(cmpc_walk_refill_trials) == 56, "cmpc_walk_refill_trials: the size include/cmpc.h states");
 static_assert(sizeof(cmpc_walk_refill_snapshot) == 32, "cmpc_walk_refill_snapshot: the size include/cmpc.h states");
+static_assert(sizeof(cmpc_wrench_sensor) == 32, "cmpc_wrench_sensor: the size include/cmpc.h states");
 
 namespace cmpc_host {
 
@@ -34,6 +35,25 @@ bool tape_complete(const cmpc_walk_tape* t)
 {
     return t && t->rows >= 1 && t->dX && t->dP && t->dLamG && t->dInfo && t->dStates && t->dOk && t->dLand && t->dPlanT && t->dListT && t->dPlanN && t->dListN &&
            t->plant_step > 0 && t->plant_substeps >= 1;
+}
+
+// the wrench sensor (include/cmpc.h, cmpc_wrench_sensor): why a sensor and the schedule it reads are refused, or null.  N <= 0: the horizon is not known yet
+// (the upper end of hold_knots is then the caller's to check again)
+const char* sensor_refusal(int N, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s)
+{
+    if (!s || !m) return "null sensor or mismatch";
+    if (!m->dHiddenWrench || m->hidden_ticks < 1) return "a sensor needs the hidden-wrench schedule it reads (dHiddenWrench, hidden_ticks >= 1)";
+    if (s->delay_ticks < 0) return "delay_ticks is negative";
+    if (s->hold_knots < 1 || (N > 0 && s->hold_knots > N)) return "hold_knots lies outside 1..N";
+    if (!(s->deadband >= 0.0)) return "deadband is negative or NaN";
+    if (s->noise_ticks < 0 || (s->dSensorNoise && s->noise_ticks < 1)) return "bad sensor noise (a negative count, or a schedule with no rows)";
+    return nullptr;
+}
+
+CmpcSenseArgs sense_args(int N, int B, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s)
+{
+    return CmpcSenseArgs{N, B, tick0, rows, m->tick_first, m->dHiddenWrench, m->hidden_ticks, s->delay_ticks, s->hold_knots, s->deadband * s->deadband,
+                         s->dSensorNoise, s->dSensorNoise ? s->noise_ticks : 0};
 }
 
 }  // namespace cmpc_host
@@ -391,7 +411,7 @@ int cmpc_rollout_tape_device(cmpc_handle h, int max_contacts, int row, int parts
 // m: the plant mismatch, every tick passing its own number tick0 + i (no launch more per tick, nothing more on the tape: dStates holds the true state, dP the measured one)
 static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
                              int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream,
-                             const cmpc_plant_mismatch* m = nullptr)
+                             const cmpc_plant_mismatch* m = nullptr, const cmpc_wrench_sensor* s = nullptr, float* dPlantWrench = nullptr)
 {
     if (!h || !io) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: null argument");
     {
@@ -407,6 +427,7 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
     if (rec && h->limits_set && h->limits.dMeasures && (long long)row0 + ticks > h->limits.rows)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_device: the measures trace of cmpc_set_walk_limits has too few rows");
     HIPCHK(h, hipSetDevice(h->device));
+    if (s && !h->dSenseWrench) HIPCHK(h, hipMalloc(&h->dSenseWrench, sizeof(float) * (size_t)h->B * h->cfg.horizon * 6));
     hipStream_t st = stream_of(h, stream);
     int rc = upload_box(h, io->tick.box_upper, io->tick.box_lower, st);
     if (rc != CMPC_OK) return rc;
@@ -433,11 +454,27 @@ static int rollout_walk_impl(cmpc_handle h, int max_contacts, int tick0, int tic
         if (i > 0) t.dState = io->tick.dStateOut;
         if (io->dWrenchTicks) t.dWrench = i < io->wrench_ticks ? io->dWrenchTicks + wrench_row * i : nullptr;
         t.plan_t_offset = now - io->plan_t_first;
+        // s: the sense launch writes this tick's wrench rows and its plant row; the tick then takes its hidden row from there and its noise row and gain from m
+        cmpc_plant_mismatch sensed{};
+        if (s) {
+            const float *m_hidden, *m_noise, *m_gain;
+            mismatch_rows(m, h->B, tick0 + i, &m_hidden, &m_noise, &m_gain);
+            float* const plant_row = dPlantWrench + (size_t)i * h->B * 6;
+            const CmpcSenseArgs sa = sense_args(h->cfg.horizon, h->B, tick0 + i, 1, m, s);
+            rc = launch_status(h, "walk (wrench sensor)", cmpc_launch_wrench_sense(&sa, h->dSenseWrench, plant_row, nullptr, st));
+            if (rc != CMPC_OK) break;
+            t.dWrench = h->dSenseWrench;
+            sensed.tick_first = tick0 + i;
+            sensed.dHiddenWrench = plant_row; sensed.hidden_ticks = 1;
+            sensed.dStateNoise = m_noise; sensed.noise_ticks = m_noise ? 1 : 0;
+            sensed.dForceGain = m_gain;
+        }
+        const cmpc_plant_mismatch* const mt = s ? &sensed : m;
         const int* const ok_read = (cold && !t.force_sample_time) ? nullptr : t.dOk;
         if (tape && i == 0)   // (the ticks run in place: the state the first one starts from is copied in front of it)
             rc = rollout_tape_impl(h, max_contacts, tape_row0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, t.dState, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    tape, stream);
-        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true, tick0 + i, m);
+        if (rc == CMPC_OK) rc = rollout_tick_impl(h, max_contacts, now, cold ? 0 : 1, &t, stream, cold, true, tick0 + i, mt);
         if (rc == CMPC_OK && rec)
             rc = rollout_record_impl(h, tick0 + i, row0 + i, t.dX, t.dP, t.dInfo, ok_read, t.dLand, t.dStateOut, t.dZmp, rec, st, false);
         if (rc == CMPC_OK && tape)
@@ -456,7 +493,8 @@ int cmpc_rollout_walk_device(cmpc_handle h, int max_contacts, int tick0, int tic
 }
 
 static int walk_taped(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
-                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m)
+                      int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, void* stream, const cmpc_plant_mismatch* m,
+                      const cmpc_wrench_sensor* s = nullptr, float* dPlantWrench = nullptr)
 {
     if (!h || !io || !tape_complete(tape)) return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: null argument or incomplete tape");
     if (ticks < 1 || tape_row0 < 0 || (long long)tape_row0 + ticks > tape->rows)
@@ -467,7 +505,7 @@ static int walk_taped(cmpc_handle h, int max_contacts, int tick0, int ticks, int
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the tape's scalars do not agree with the walk (or a first tick beyond row 0)");
     if (!h->mult_out || !h->dDuals)
         return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_taped_device: the multiplier output is off (cmpc_set_multiplier_output before the walk)");
-    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m, s, dPlantWrench);
 }
 
 int cmpc_rollout_walk_taped_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
@@ -482,6 +520,54 @@ int cmpc_rollout_walk_mismatch_device(cmpc_handle h, int max_contacts, int tick0
 {
     if (tape) return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m);
     return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream, m);
+}
+
+// ---- sensed pushes (include/cmpc.h, cmpc_wrench_sensor): the sensor's rows on the host and in one launch, and the walk with a sense launch per tick ----
+static const char* sense_rows_refusal(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s)
+{
+    if (horizon < 1 || batch < 1 || tick0 < 0 || rows < 1) return "bad argument";
+    return sensor_refusal(horizon, m, s);
+}
+
+int cmpc_wrench_sense(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, float* wrench_rows,
+                      float* plant_wrench, int* pass)
+{
+    if (const char* why = sense_rows_refusal(horizon, batch, tick0, rows, m, s)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_wrench_sense: ") + why);
+    if (!plant_wrench) return fail(nullptr, CMPC_ERR_ARG, "cmpc_wrench_sense: plant_wrench is needed");
+    const CmpcSenseArgs a = sense_args(horizon, batch, tick0, rows, m, s);
+    const int knots = wrench_rows ? horizon : 1;
+    for (int r = 0; r < rows; ++r)
+        for (int b = 0; b < batch; ++b)
+            for (int k = 0; k < knots; ++k) cmpc_wrench_sense_entry(a, wrench_rows, plant_wrench, pass, r, b, k);
+    return CMPC_OK;
+}
+
+int cmpc_wrench_sense_device(cmpc_handle h, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, float* dWrenchRows,
+                             float* dPlantWrench, int* dPass, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_device: null handle");
+    if (const char* why = sense_rows_refusal(h->cfg.horizon, h->B, tick0, rows, m, s))
+        return fail(h, CMPC_ERR_ARG, std::string("cmpc_wrench_sense_device: ") + why);
+    if (!dPlantWrench) return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_device: dPlantWrench is needed");
+    HIPCHK(h, hipSetDevice(h->device));
+    const CmpcSenseArgs a = sense_args(h->cfg.horizon, h->B, tick0, rows, m, s);
+    return launch_status(h, "wrench sensor", cmpc_launch_wrench_sense(&a, dWrenchRows, dPlantWrench, dPass, stream_of(h, stream)));
+}
+
+// (the checks that need no handle come first, so that each is refused without a device too)
+int cmpc_rollout_walk_sensed_device(cmpc_handle h, int max_contacts, int tick0, int ticks, int cold_first, const cmpc_walk_io* io, const cmpc_walk_record* rec,
+                                    int row0, int lists_in, int* lists_out, const cmpc_walk_tape* tape, int tape_row0, const cmpc_plant_mismatch* m,
+                                    const cmpc_wrench_sensor* s, float* dPlantWrench, void* stream)
+{
+    if (s) {
+        if (io && (io->dWrenchTicks || io->tick.dWrench))
+            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_sensed_device: dWrenchTicks or tick.dWrench is set (a known push and a sensed one are not summed)");
+        if (!m || !m->dHiddenWrench || !dPlantWrench)
+            return fail(h, CMPC_ERR_ARG, "cmpc_rollout_walk_sensed_device: a sensor needs m->dHiddenWrench and dPlantWrench");
+        if (const char* why = sensor_refusal(h ? h->cfg.horizon : 0, m, s)) return fail(h, CMPC_ERR_ARG, std::string("cmpc_rollout_walk_sensed_device: ") + why);
+    }
+    if (tape) return walk_taped(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, tape, tape_row0, stream, m, s, dPlantWrench);
+    return rollout_walk_impl(h, max_contacts, tick0, ticks, cold_first, io, rec, row0, lists_in, lists_out, nullptr, 0, stream, m, s, dPlantWrench);
 }
 
 // ---- refill (include/cmpc.h, cmpc_walk_refill): the queue of trials behind a walk's slots ----

@@ -648,4 +648,70 @@ int cmpc_rollout_walk_jvp_mismatch_device(cmpc_handle h, int max_contacts, int t
                     d, stream, m, md);
 }
 
+// ---- sensed pushes (include/cmpc.h, cmpc_wrench_sensor): the sensor's transpose and its tangent; the host forms run the kernels' own per-entry functions ----
+static const char* sense_grad_refusal(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s)
+{
+    if (horizon < 1 || batch < 1 || tick0 < 0 || rows < 1) return "bad argument";
+    return sensor_refusal(horizon, m, s);
+}
+
+static CmpcSenseVjpArgs sense_vjp_args(int N, int B, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, const float* gw,
+                                       const double* gh, double* gt, double* gn)
+{
+    return CmpcSenseVjpArgs{sense_args(N, B, tick0, rows, m, s), gw, gh, gt, s->dSensorNoise ? gn : nullptr};
+}
+
+int cmpc_wrench_sense_vjp(int horizon, int batch, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, const float* grad_wrench,
+                          const double* grad_hidden, double* grad_hidden_true, double* grad_sensor_noise)
+{
+    if (const char* why = sense_grad_refusal(horizon, batch, tick0, rows, m, s)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_wrench_sense_vjp: ") + why);
+    if (!grad_wrench || !grad_hidden || !grad_hidden_true) return fail(nullptr, CMPC_ERR_ARG, "cmpc_wrench_sense_vjp: null argument");
+    const CmpcSenseVjpArgs v = sense_vjp_args(horizon, batch, tick0, rows, m, s, grad_wrench, grad_hidden, grad_hidden_true, grad_sensor_noise);
+    const int out_rows = std::max(v.s.hidden_ticks, v.grad_noise ? v.s.noise_ticks : 0);
+    for (int r = 0; r < out_rows; ++r)
+        for (int b = 0; b < batch; ++b)
+            for (int c = 0; c < 6; ++c) cmpc_wrench_sense_vjp_entry(v, r, b, c);
+    return CMPC_OK;
+}
+
+int cmpc_wrench_sense_vjp_device(cmpc_handle h, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s, const float* dGradWrench,
+                                 const double* dGradHidden, double* dGradHiddenTrue, double* dGradSensorNoise, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_vjp_device: null handle");
+    if (const char* why = sense_grad_refusal(h->cfg.horizon, h->B, tick0, rows, m, s))
+        return fail(h, CMPC_ERR_ARG, std::string("cmpc_wrench_sense_vjp_device: ") + why);
+    if (!dGradWrench || !dGradHidden || !dGradHiddenTrue) return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_vjp_device: null argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    const CmpcSenseVjpArgs v = sense_vjp_args(h->cfg.horizon, h->B, tick0, rows, m, s, dGradWrench, dGradHidden, dGradHiddenTrue, dGradSensorNoise);
+    return launch_status(h, "wrench sensor VJP", cmpc_launch_wrench_sense_vjp(&v, stream_of(h, stream)));
+}
+
+int cmpc_wrench_sense_jvp(int horizon, int batch, int tick0, int rows, int k, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s,
+                          const double* dir_hidden, const double* dir_sensor_noise, float* dir_wrench, double* dir_plant_wrench)
+{
+    if (const char* why = sense_grad_refusal(horizon, batch, tick0, rows, m, s)) return fail(nullptr, CMPC_ERR_ARG, std::string("cmpc_wrench_sense_jvp: ") + why);
+    if (k < 1 || !dir_hidden || !dir_wrench || !dir_plant_wrench) return fail(nullptr, CMPC_ERR_ARG, "cmpc_wrench_sense_jvp: k >= 1 and the arrays are needed");
+    const CmpcSenseJvpArgs v{sense_args(horizon, batch, tick0, rows, m, s), k, dir_hidden, s->dSensorNoise ? dir_sensor_noise : nullptr, dir_wrench,
+                             dir_plant_wrench};
+    for (int r = 0; r < rows; ++r)
+        for (int b = 0; b < batch; ++b)
+            for (int j = 0; j < k; ++j)
+                for (int q = 0; q < horizon; ++q) cmpc_wrench_sense_jvp_entry(v, r, b, j, q);
+    return CMPC_OK;
+}
+
+int cmpc_wrench_sense_jvp_device(cmpc_handle h, int tick0, int rows, int k, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s,
+                                 const double* dDirHidden, const double* dDirSensorNoise, float* dDirWrench, double* dDirPlantWrench, void* stream)
+{
+    if (!h) return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_jvp_device: null handle");
+    if (const char* why = sense_grad_refusal(h->cfg.horizon, h->B, tick0, rows, m, s))
+        return fail(h, CMPC_ERR_ARG, std::string("cmpc_wrench_sense_jvp_device: ") + why);
+    if (k < 1 || !dDirHidden || !dDirWrench || !dDirPlantWrench)
+        return fail(h, CMPC_ERR_ARG, "cmpc_wrench_sense_jvp_device: k >= 1 and the arrays are needed");
+    HIPCHK(h, hipSetDevice(h->device));
+    const CmpcSenseJvpArgs v{sense_args(h->cfg.horizon, h->B, tick0, rows, m, s), k, dDirHidden, s->dSensorNoise ? dDirSensorNoise : nullptr, dDirWrench,
+                             dDirPlantWrench};
+    return launch_status(h, "wrench sensor JVP", cmpc_launch_wrench_sense_jvp(&v, stream_of(h, stream)));
+}
+
 }  // extern "C"

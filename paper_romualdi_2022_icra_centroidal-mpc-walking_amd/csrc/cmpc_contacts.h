@@ -1300,3 +1300,133 @@ __host__ __device__ inline void cmpc_walk_jvp_gate_wide(const CmpcJvpGateArgs& a
 {
     if (a.do_post && a.x_row && idx < (size_t)a.B * a.K * a.nx && cmpc_gate_ended(a.end_tick, (int)(idx / ((size_t)a.K * a.nx)), a.tick_post)) a.x_row[idx] = 0.f;
 }
+
+// ---- the wrench sensor of a walk under hidden pushes (include/cmpc.h, cmpc_wrench_sensor; DESIGN.md 7f, "Sensed pushes"): what the MPC is told of the
+// hidden-wrench schedule and what only the plant feels.  One statement of the rule for the host forms and the kernels (contraction off): every step is a
+// select, so a value outside a schedule's range is never read and a zeroed reading is +0, not a product with zero.
+struct CmpcSenseArgs {
+    int N, B, tick0, rows;
+    int tick_first; const float* hidden; int hidden_ticks;   // cmpc_plant_mismatch: the true schedule [hidden_ticks][B][6]
+    int delay, hold; double band2;                            // cmpc_wrench_sensor; band2 = deadband * deadband, formed once in double
+    const float* noise; int noise_ticks;                      // [noise_ticks][B][6] or null
+};
+// row `row` of schedule [ticks][B][6] (problem b) when it is inside the schedule, else null
+__host__ __device__ inline const float* cmpc_sense_row(const float* sched, int ticks, long long row, int B, int b)
+{
+    return sched && row >= 0 && row < ticks ? sched + ((size_t)row * B + b) * 6 : nullptr;
+}
+// the reading of tick t and whether it passes the dead-band: !(n2 < band2), so a force on the threshold passes and so does a NaN
+__host__ __device__ inline bool cmpc_wrench_reading(const CmpcSenseArgs& a, int t, int b, float* reading)
+{
+#pragma clang fp contract(off)
+    const float* src = cmpc_sense_row(a.hidden, a.hidden_ticks, (long long)t - a.delay - a.tick_first, a.B, b);
+    const float* nz = cmpc_sense_row(a.noise, a.noise_ticks, (long long)t - a.tick_first, a.B, b);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const float s = src ? src[e] : 0.f;
+        reading[e] = nz ? s + nz[e] : s;
+    }
+    const double x = (double)reading[0], y = (double)reading[1], z = (double)reading[2];
+    const double n2 = (x * x + y * y) + z * z;
+    return !(n2 < a.band2);
+}
+// tick tick0 + r, problem b: est[6] (the wrench every knot k < hold receives) and plant[6] (the tick's hidden row); returns pass
+__host__ __device__ inline bool cmpc_wrench_sense_problem(const CmpcSenseArgs& a, int r, int b, float* est, float* plant)
+{
+#pragma clang fp contract(off)
+    const int t = a.tick0 + r;
+    float reading[6];
+    const bool pass = cmpc_wrench_reading(a, t, b, reading);
+    const float* tr = cmpc_sense_row(a.hidden, a.hidden_ticks, (long long)t - a.tick_first, a.B, b);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const float tv = tr ? tr[e] : 0.f;
+        est[e] = pass ? reading[e] : 0.f;
+        plant[e] = pass ? tv - reading[e] : tv;
+    }
+    return pass;
+}
+// entry (r, b, k) of the forward: knot k of the wrench rows; the thread of knot 0 writes the plant row and the pass word too
+__host__ __device__ inline void cmpc_wrench_sense_entry(const CmpcSenseArgs& a, float* wrench_rows, float* plant_rows, int* pass_rows, int r, int b, int k)
+{
+    float est[6], plant[6];
+    const bool pass = cmpc_wrench_sense_problem(a, r, b, est, plant);
+    const size_t rb = (size_t)r * a.B + b;
+    if (wrench_rows) {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) wrench_rows[(rb * a.N + k) * 6 + e] = k < a.hold ? est[e] : 0.f;
+    }
+    if (k == 0) {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) plant_rows[rb * 6 + e] = plant[e];
+        if (pass_rows) pass_rows[rb] = pass ? 1 : 0;
+    }
+}
+// the transpose.  g of tick t, component c: pass ? (sum over k < hold of grad_wrench, ascending, in double) - grad_hidden : 0; the branch is recomputed
+struct CmpcSenseVjpArgs {
+    CmpcSenseArgs s;
+    const float* grad_wrench;    // [rows][B][N][6]
+    const double* grad_hidden;   // [rows][B][6], taken on the plant rows
+    double* grad_true;           // [hidden_ticks][B][6]
+    double* grad_noise;          // [noise_ticks][B][6] or null
+};
+__host__ __device__ inline bool cmpc_sense_in_rows(const CmpcSenseArgs& a, long long t) { return t >= a.tick0 && t < (long long)a.tick0 + a.rows; }
+__host__ __device__ inline double cmpc_wrench_sense_g(const CmpcSenseVjpArgs& v, int t, int b, int c)
+{
+#pragma clang fp contract(off)
+    float reading[6];
+    if (!cmpc_wrench_reading(v.s, t, b, reading)) return 0.0;
+    const size_t rb = (size_t)(t - v.s.tick0) * v.s.B + b;
+    double sum = 0.0;
+    for (int k = 0; k < v.s.hold; ++k) sum = sum + (double)v.grad_wrench[(rb * v.s.N + k) * 6 + c];
+    return sum - v.grad_hidden[rb * 6 + c];
+}
+// output element (r, b, c) of both gradients: a gather, no atomics
+__host__ __device__ inline void cmpc_wrench_sense_vjp_entry(const CmpcSenseVjpArgs& v, int r, int b, int c)
+{
+#pragma clang fp contract(off)
+    const CmpcSenseArgs& a = v.s;
+    const long long t = (long long)r + a.tick_first, td = t + a.delay;
+    if (r < a.hidden_ticks) {
+        const bool own = cmpc_sense_in_rows(a, t), read = cmpc_sense_in_rows(a, td);
+        const double gh = own ? v.grad_hidden[((size_t)(t - a.tick0) * a.B + b) * 6 + c] : 0.0;
+        const double g = read ? cmpc_wrench_sense_g(v, (int)td, b, c) : 0.0;
+        v.grad_true[((size_t)r * a.B + b) * 6 + c] = own && read ? gh + g : own ? gh : g;
+    }
+    if (v.grad_noise && r < a.noise_ticks)
+        v.grad_noise[((size_t)r * a.B + b) * 6 + c] = cmpc_sense_in_rows(a, t) ? cmpc_wrench_sense_g(v, (int)t, b, c) : 0.0;
+}
+// the tangent in K columns: column j depends on column j of the directions alone
+struct CmpcSenseJvpArgs {
+    CmpcSenseArgs s;
+    int K;
+    const double* dir_hidden;    // [hidden_ticks][B][K][6]
+    const double* dir_noise;     // [noise_ticks][B][K][6] or null
+    float* dir_wrench;           // [rows][B][K][N][6]
+    double* dir_plant;           // [rows][B][K][6]
+};
+__host__ __device__ inline const double* cmpc_sense_dir_row(const double* sched, int ticks, long long row, int B, int K, int b, int j)
+{
+    return sched && row >= 0 && row < ticks ? sched + (((size_t)row * B + b) * K + j) * 6 : nullptr;
+}
+// entry (r, b, j, k): knot k of column j's wrench direction; the thread of knot 0 writes the plant direction too
+__host__ __device__ inline void cmpc_wrench_sense_jvp_entry(const CmpcSenseJvpArgs& v, int r, int b, int j, int k)
+{
+#pragma clang fp contract(off)
+    const CmpcSenseArgs& a = v.s;
+    const int t = a.tick0 + r;
+    float reading[6];
+    const bool pass = cmpc_wrench_reading(a, t, b, reading);
+    const double* dt = cmpc_sense_dir_row(v.dir_hidden, a.hidden_ticks, (long long)t - a.tick_first, a.B, v.K, b, j);
+    const double* ds = cmpc_sense_dir_row(v.dir_hidden, a.hidden_ticks, (long long)t - a.delay - a.tick_first, a.B, v.K, b, j);
+    const double* dn = cmpc_sense_dir_row(v.dir_noise, a.noise_ticks, (long long)t - a.tick_first, a.B, v.K, b, j);
+    const size_t col = ((size_t)r * a.B + b) * v.K + j;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const double s = ds ? ds[e] : 0.0;
+        const double rd = dn ? s + dn[e] : s;
+        const double tv = dt ? dt[e] : 0.0;
+        v.dir_wrench[(col * a.N + k) * 6 + e] = pass && k < a.hold ? (float)rd : 0.f;
+        if (k == 0) v.dir_plant[col * 6 + e] = pass ? tv - rd : tv;
+    }
+}

@@ -38,6 +38,7 @@ struct cmpc_handle_s {
     hipEvent_t sens_ev = nullptr; // recorded after the last sensitivity launch: the next one, on any stream, waits for it (one workspace)
     double* dSnapT = nullptr;    // the planner's lists snapped to the grid (cmpc_rollout_tick_device with force_sample_time, lists beyond the LDS stage)
     int* dSnapOk = nullptr;      // ... and the per-foot status words [B][2]
+    float* dSenseWrench = nullptr; // the wrench rows [B][N][6] a sensed walk's tick reads (cmpc_rollout_walk_sensed_device, allocated on first use)
     char* dTickWs = nullptr;     // workspace of cmpc_rollout_tick_vjp[_rot]_device (allocated on first use, sized for both): model gradients of the solve and of
                                  // the plant [B][34] each | rotation gradients of the solve [B][2][N][3] and of the plant [B][2][3] | the plant's gradient on the
                                  // hidden wrench [B][6] and on the force gain [B] (the mismatch entry) (double) | gX[B][n_x] | gP of
@@ -103,6 +104,8 @@ int ensure_models(cmpc_handle h);
 int mismatch_check(cmpc_handle h, const char* who, const cmpc_plant_mismatch* m);
 void mismatch_rows(const cmpc_plant_mismatch* m, int B, int tick, const float** hidden, const float** noise, const float** gain);
 bool tape_complete(const cmpc_walk_tape* t);
+const char* sensor_refusal(int N, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s);
+CmpcSenseArgs sense_args(int N, int B, int tick0, int rows, const cmpc_plant_mismatch* m, const cmpc_wrench_sensor* s);
 
 }  // namespace cmpc_host
 #pragma GCC visibility pop

@@ -44,6 +44,9 @@ int cmpc_launch_extremes_init(int B, float* ext, hipStream_t stream);
 int cmpc_launch_walk_measures_vjp(const CmpcMeasureVjpArgs* v, hipStream_t stream);
 int cmpc_launch_walk_measures_fold(int N, int B, int rows, const double* direct, float* grad_p, double* grad_model, hipStream_t stream);
 int cmpc_launch_walk_measures_jvp(const CmpcMeasureJvpArgs* v, hipStream_t stream);
+int cmpc_launch_wrench_sense(const CmpcSenseArgs* a, float* wrench_rows, float* plant_rows, int* pass_rows, hipStream_t stream);
+int cmpc_launch_wrench_sense_vjp(const CmpcSenseVjpArgs* v, hipStream_t stream);
+int cmpc_launch_wrench_sense_jvp(const CmpcSenseJvpArgs* v, hipStream_t stream);
 int cmpc_launch_outcome_init(int B, const float* state0, int* end_tick, int* end_code, int* it_sum, int* it_max, float* final_state,
                              float* slack_min, hipStream_t stream);
 int cmpc_launch_cold_start(int N, int B, float g8, const float* dP, float* dX0, const int* ended, hipStream_t stream);

@@ -836,6 +836,33 @@ __global__ __launch_bounds__(256) void cmpc_walk_measures_jvp_kernel(CmpcMeasure
     cmpc_walk_measures_jvp_entry(v, (int)(e / v.B), (int)(e % v.B));
 }
 
+// ---- the wrench sensor (include/cmpc.h, cmpc_wrench_sensor): one thread per (row, problem, knot) of the forward and the tangent, one per output element of
+// the transpose; the rule is cmpc_contacts.h's, the host forms run the same functions.  No LDS, no atomics. ----
+__global__ __launch_bounds__(256) void cmpc_wrench_sense_kernel(CmpcSenseArgs a, int knots, float* __restrict__ wrench_rows, float* __restrict__ plant_rows,
+                                                                int* __restrict__ pass_rows)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)a.rows * a.B * knots) return;
+    const size_t rb = e / knots;
+    cmpc_wrench_sense_entry(a, wrench_rows, plant_rows, pass_rows, (int)(rb / a.B), (int)(rb % a.B), (int)(e % knots));
+}
+
+__global__ __launch_bounds__(256) void cmpc_wrench_sense_vjp_kernel(CmpcSenseVjpArgs v, int out_rows)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)out_rows * v.s.B * 6) return;
+    const size_t rb = e / 6;
+    cmpc_wrench_sense_vjp_entry(v, (int)(rb / v.s.B), (int)(rb % v.s.B), (int)(e % 6));
+}
+
+__global__ __launch_bounds__(256) void cmpc_wrench_sense_jvp_kernel(CmpcSenseJvpArgs v)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)v.s.rows * v.s.B * v.K * v.s.N) return;
+    const size_t col = e / v.s.N, rb = col / v.K;
+    cmpc_wrench_sense_jvp_entry(v, (int)(rb / v.s.B), (int)(rb % v.s.B), (int)(col % v.K), (int)(e % v.s.N));
+}
+
 __global__ __launch_bounds__(256) void cmpc_outcome_init_kernel(int B, const float* __restrict__ state0, int* __restrict__ end_tick, int* __restrict__ end_code,
                                                                 int* __restrict__ it_sum, int* __restrict__ it_max, float* __restrict__ final_state,
                                                                 float* __restrict__ slack_min)
@@ -1186,6 +1213,30 @@ extern "C" int cmpc_launch_walk_measures_jvp(const CmpcMeasureJvpArgs* v, hipStr
 {
     const size_t n = (size_t)v->rows * v->B;
     hipLaunchKernelGGL(cmpc_walk_measures_jvp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *v);
+    return (int)hipGetLastError();
+}
+
+// wrench_rows null: one thread per (row, problem), which writes the plant row and the pass word alone
+extern "C" int cmpc_launch_wrench_sense(const CmpcSenseArgs* a, float* wrench_rows, float* plant_rows, int* pass_rows, hipStream_t stream)
+{
+    const int knots = wrench_rows ? a->N : 1;
+    const size_t n = (size_t)a->rows * a->B * knots;
+    hipLaunchKernelGGL(cmpc_wrench_sense_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *a, knots, wrench_rows, plant_rows, pass_rows);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_wrench_sense_vjp(const CmpcSenseVjpArgs* v, hipStream_t stream)
+{
+    const int out_rows = v->grad_noise && v->s.noise_ticks > v->s.hidden_ticks ? v->s.noise_ticks : v->s.hidden_ticks;
+    const size_t n = (size_t)out_rows * v->s.B * 6;
+    hipLaunchKernelGGL(cmpc_wrench_sense_vjp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *v, out_rows);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cmpc_launch_wrench_sense_jvp(const CmpcSenseJvpArgs* v, hipStream_t stream)
+{
+    const size_t n = (size_t)v->s.rows * v->s.B * v->K * v->s.N;
+    hipLaunchKernelGGL(cmpc_wrench_sense_jvp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *v);
     return (int)hipGetLastError();
 }
 

@@ -566,6 +566,98 @@ class WalkingRollout:
         args.apply_defaults()
         return self._queued(lambda: self._walk(False, None, None, *args.args, **args.kwargs, mismatch=mismatch))
 
+    # ---- sensed pushes (include/cmpc.h, cmpc_wrench_sensor; DESIGN.md 7f, "Sensed pushes") ----
+    def wrench_sensor(self, delay=0, hold_knots=1, deadband=0.7, noise=None):
+        """A wrench sensor for walk_device_sensed, as a dict with the C struct and its tensors: the reading of tick t is the hidden wrench of tick t - delay
+        plus noise[t - tick_first] ([Tn, B, 6] float32, numpy or CUDA; None: none), zeroed as a whole when its force is shorter than deadband (the
+        reference's 0.7; 0: off; inf: a blind sensor), and handed to the MPC on knots 0 .. hold_knots - 1 of fExt / tauExt."""
+        return self.solver._wrench_sensor(delay, hold_knots, deadband, noise, device=self.dev)
+
+    @staticmethod
+    def _sensor_of(sensor, mm, push):
+        """the sensor of a walk (None: none), checked against the walk's other inputs before anything is queued"""
+        if sensor is None:
+            return None
+        if push is not None:
+            raise ValueError("push= with a sensor: a known push and a sensed one are not summed (hidden_wrench is what the sensor reads)")
+        if mm is None or mm["hidden_wrench"] is None:
+            raise ValueError("a sensor needs mismatch['hidden_wrench'], the schedule it reads")
+        return sensor
+
+    def walk_device_sensed(self, ticks, com0, dcom0, h0, mismatch, sensor, tape=False, every=None, **kwargs):
+        """walk_device_mismatch(ticks, com0, dcom0, h0, mismatch, **kwargs) with a wrench sensor between mismatch["hidden_wrench"] and the MPC
+        (cmpc_rollout_walk_sensed_device): sensor = wrench_sensor(...).  ONE small launch in front of each tick turns the hidden schedule into the wrench
+        rows the MPC sees (delayed, noisy, dead-banded, held for hold_knots knots) and the remainder only the plant feels; no host read.  The dict gains
+        plant_wrench[ticks, B, 6] float32, that remainder.  tape=True: walk_device_taped's tape, which keeps mismatch, sensor and plant_wrench for
+        backward_device_sensed() / forward_sensitivity_device_sensed().  every= (without a tape): walk_device_checkpointed's snapshots in front of the
+        multiples of `every`, to resume from with walk_resume_device_sensed(); the checkpointed REVERSE of a sensed walk is refused (the delay couples
+        rows across segments).  push= raises ValueError (the MPC's wrench is the sensed one).  sensor=None: walk_device_mismatch (tape=True:
+        walk_device_taped(mismatch=...); every: walk_device_checkpointed(mismatch=...)), bit for bit, and no sensor key."""
+        if sensor is not None and kwargs.get("push") is not None:
+            raise ValueError("push= with a sensor: a known push and a sensed one are not summed (hidden_wrench is what the sensor reads)")
+        if tape and every is not None:
+            raise ValueError("walk_device_sensed: tape=True or every=, not both")
+        args = inspect.signature(self.walk_device).bind(ticks, com0, dcom0, h0, **kwargs)
+        args.apply_defaults()
+        return self._queued(lambda: self._walk(bool(tape), None if every is None else int(every), None, *args.args, **args.kwargs, mismatch=mismatch,
+                                               sensor=sensor))
+
+    def walk_resume_device_sensed(self, snapshot, ticks, mismatch, sensor, **kwargs):
+        """walk_resume_device_mismatch(snapshot, ticks, mismatch, **kwargs) with a wrench sensor (walk_device_sensed's): one pilot walk, one snapshot,
+        index = zeros, and B hidden pushes, each sensed.  Tick numbers are those of the whole walk, so a delay reaches across the cut: ticks 0 .. c - 1
+        and a resume at c under the same mismatch and sensor equal the unbroken walk bit for bit.  The dict gains plant_wrench[ticks, B, 6] (row 0 = the
+        resume tick).  push= raises ValueError, and so does a snapshot that carries a wrench schedule of its own."""
+        if sensor is not None and kwargs.get("push") is not None:
+            raise ValueError("push= with a sensor: a known push and a sensed one are not summed (hidden_wrench is what the sensor reads)")
+        args = inspect.signature(self.walk_resume_device).bind(snapshot, ticks, **kwargs)
+        args.apply_defaults()
+        return self._queued(lambda: self._walk_resume(*args.args, **args.kwargs, mismatch=mismatch, sensor=sensor))
+
+    def _sensed_tape(self, who, w):
+        """(w with the tape's mismatch replaced by the one the plant ran under -- hidden schedule plant_wrench from tick 0, the walk's gain --, the walk's
+        mismatch, the sensor)"""
+        tape = w.get("tape")
+        if tape is None or tape.get("sensor") is None or "segments" not in tape:
+            raise ValueError(f"{who}: w is not walk_device_sensed(..., tape=True) with a sensor")
+        mm = tape["mismatch"]
+        plant_mm = self.solver.plant_mismatch(hidden_wrench=tape["plant_wrench"], force_gain=mm["force_gain"], tick_first=0, device=self.dev)
+        return dict(w, tape=dict(tape, mismatch=plant_mm)), mm, tape["sensor"]
+
+    def backward_device_sensed(self, w, grad_states, grad_X=None):
+        """backward_device(w, grad_states, grad_X) on w = walk_device_sensed(..., tape=True): the reverse walk runs on the tape with the plant's own
+        schedule (plant_wrench) as its hidden wrench, then ONE launch of cmpc_wrench_sense_vjp_device carries the wrench rows' and the plant rows'
+        gradients through the transpose of the sensor.  -> backward_device's keys on that tape, in which plant_wrench[ticks, B, 6] is what backward_device
+        calls hidden_wrench; hidden_wrench[Th, B, 6] float64 is the TOTAL gradient with respect to the true pushes, shaped as the schedule; sensor_noise
+        [Tn, B, 6] float64 (None without sensor noise).  A problem that ended at tick e: its rows from e on (shifted by the delay) are exactly zero.  No
+        host read."""
+        w2, mm, sn = self._sensed_tape("backward_device_sensed", w)
+        out = self._backward_device(w2, grad_states, grad_X, False)
+        out["plant_wrench"] = out["hidden_wrench"]
+        T = w["tape"]["rows"]
+        out["hidden_wrench"], out["sensor_noise"] = self._queued(
+            lambda: self.solver._wrench_sense_vjp_device(0, T, mm, sn, out["wrench"], out["plant_wrench"]))
+        return out
+
+    def forward_sensitivity_device_sensed(self, w, k, dir_hidden_wrench=None, dir_sensor_noise=None, dir_state_noise=None, dir_force_gain=None,
+                                          dir_ref_com=None, dir_ref_h=None, **dirs):
+        """forward_sensitivity_device_mismatch on w = walk_device_sensed(..., tape=True), in k columns, with directions of the TRUE pushes and of the sensor
+        noise: dir_hidden_wrench[Th, B, k, 6] and dir_sensor_noise[Tn, B, k, 6] float64 (CUDA or numpy; None: zero), shaped as the schedules.  ONE launch of
+        cmpc_wrench_sense_jvp_device turns them into the wrench rows' and the plant rows' directions, which the forward walk takes as dir_wrench and
+        dir_hidden_wrench; the other direction groups as in forward_sensitivity_device_mismatch (dir_wrench itself is refused: the MPC's wrench is the
+        sensed one).  The transpose of backward_device_sensed(), input for output; no host read."""
+        torch = self.torch
+        if dirs.get("dir_wrench") is not None:
+            raise ValueError("forward_sensitivity_device_sensed: dir_wrench is the sensor's output here; give dir_hidden_wrench / dir_sensor_noise")
+        w2, mm, sn = self._sensed_tape("forward_sensitivity_device_sensed", w)
+        T, k = w["tape"]["rows"], int(k)
+        as_t = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))).to(self.dev, torch.float64).contiguous()
+        dh = torch.zeros(tuple(mm["hidden_wrench"].shape[:2]) + (k, 6), dtype=torch.float64, device=self.dev) if dir_hidden_wrench is None \
+            else as_t(dir_hidden_wrench)
+        dn = None if dir_sensor_noise is None or sn["noise"] is None else as_t(dir_sensor_noise)
+        dw, dp = self._queued(lambda: self.solver._wrench_sense_jvp_device(0, T, k, mm, sn, dh, dn))
+        return self.forward_sensitivity_device_mismatch(w2, dir_hidden_wrench=dp, dir_state_noise=dir_state_noise, dir_force_gain=dir_force_gain,
+                                                        dir_ref_com=dir_ref_com, dir_ref_h=dir_ref_h, **dict(dirs, dir_wrench=dw))
+
     def walk_device_taped(self, ticks, com0, dcom0, h0, **kwargs):
         """walk_device(ticks, com0, dcom0, h0, **kwargs) through cmpc_rollout_walk_taped_device: every tick also writes its row of a device tape -- what
         backward_device() needs; about 12 KB per problem and tick at N = 20 -- and the dict gains "tape": the stacked tensors X, P, lam_g, info
@@ -581,11 +673,13 @@ class WalkingRollout:
         args.apply_defaults()
         return self._queued(lambda: self._walk(True, None, None, *args.args, **args.kwargs, mismatch=mismatch))
 
-    def _walk(self, tape, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None):
+    def _walk(self, tape, every, states, ticks, com0, dcom0, h0, push, push_ticks, replan, trace, stop, skip_ended, mismatch=None, sensor=None):
         """walk_device and its mismatched, taped (tape) and checkpointed (every) forms: the start state in live buffers, the ticks queued by _walk_live.
         every None: walk_device's dict (with "tape": walk_device_taped's); else "checkpoints" and "inputs" besides.  states: _walk_live's."""
         torch, dev, s, up = self.torch, self.dev, self.solver, self._up
         mm = self._walk_mismatch = self._mismatch_of(mismatch)    # (kept until the next call: the queued launches read its tensors)
+        sn = self._walk_sensor = self._sensor_of(sensor, mm, push)
+        plant = torch.zeros((ticks, self.B, 6), dtype=torch.float32, device=dev) if sn is not None else None
         self._walk_inputs = []
         state0 = torch.cat([up(com0), up(dcom0), up(h0)], 1).contiguous()
         wrench = (self._push_schedule(up(push), push_ticks, self.B), 0) if push is not None else None
@@ -599,14 +693,17 @@ class WalkingRollout:
         if states is not None:
             states[0].copy_(state0)
         cps = self._walk_live(live, 0, ticks, 0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, cold=True, states=states, mismatch=mm,
-                              limits=self.limits, limits_out=rec)
+                              limits=self.limits, limits_out=rec, sensor=sn, plant=plant)
+        if sn is not None:
+            rec["plant_wrench"] = plant
         if every is not None:
             for c in cps.values():
                 c["wrench"] = wrench
             rec.update(checkpoints=cps, inputs=dict(
                 state0=state0, wrench=wrench, push_ticks=push_ticks if push is not None else 0, replan=plans, plan=self.plan, refs=refs, stop=tuple(stop),
-                skip_ended=bool(skip_ended), ticks=int(ticks), every=every, mismatch=mm, limits=self.limits))
-        return self._walk_finish(rec, live, tp, refs, push_ticks if push is not None else 0, mm, segments=[a for a, _ in walk_schedule(ticks, every, plans)[0]])
+                skip_ended=bool(skip_ended), ticks=int(ticks), every=every, mismatch=mm, limits=self.limits, **(dict(sensor=sn) if sn is not None else {})))
+        return self._walk_finish(rec, live, tp, refs, push_ticks if push is not None else 0, mm, segments=[a for a, _ in walk_schedule(ticks, every, plans)[0]],
+                                 **(dict(sensor=sn, plant_wrench=plant) if sn is not None else {}))
 
     def _up(self, a, dtype=None):
         """a walk's input on the device (float32 unless dtype is given); the host array of a queued copy is kept in _walk_inputs until the next walk"""
@@ -1153,12 +1250,14 @@ class WalkingRollout:
         return wt
 
     def _walk_live(self, live, t0, t1, row_shift, plans, base_plan, wrench, refs, skip_ended, every=None, tape=None, tape_shift=0, cold=False, states=None,
-                   mismatch=None, limits=None, limits_out=None):
+                   mismatch=None, limits=None, limits_out=None, sensor=None, plant=None):
         """Queues ticks t0 .. t1 - 1 on the live buffers (a snapshot dict whose "rec" is the walk record): one call of the C ABI per entry of
         walk_schedule, a snapshot launch in front of each tick k * every.  Record row = tick - row_shift, tape row = tick - tape_shift.  plans {tick:
         plan}: the latest entry at or before a tick is the plan in force (none: base_plan).  wrench = (wrench_ticks[T, B, N, 6], the tick of its row 0) or
         None.  states[.., B, 9]: the walk is cut at every tick and row tick + 1 - row_shift receives the state that tick left.  limits: set_limits'
         dict, on the handle around the calls; limits_out (a dict, or None: the codes alone) receives measures (with a trace in rec) and extremes.
+        sensor (BatchSolver._wrench_sensor, with a mismatch that has a hidden schedule and no wrench): every call is cmpc_rollout_walk_sensed_device, and
+        row tick - t0 of plant[t1 - t0, B, 6] receives what only the plant felt.
         -> {tick: snapshot}"""
         s, dt, rec = self.solver, self.cfg.sampling_time, live["rec"]
         calls, snaps = walk_schedule(t1 - t0, every, plans, t0)
@@ -1178,6 +1277,15 @@ class WalkingRollout:
                     s.walk_snapshot_mark(live, a, cur)
                     out[a] = s.rollout_snapshot_device(live, s.walk_snapshot(a, cur, self.M, device=self.dev))
                 wr = wrench[0][a - wrench[1]:] if wrench is not None and a - wrench[1] < wrench[0].shape[0] else None
+                if sensor is not None:
+                    assert wr is None, "a known push and a sensed one are not summed"
+                    cur = s._rollout_walk_sensed_device(sensor, plant[a - t0:], a, b - a, cold and a == t0, plan_at(a), sets[0], sets[1], cur, live["ok"],
+                                                        live["land"], live["state"], live["P"], live["X0"], live["X"], live["info"], live["zmp"], rec,
+                                                        row0=a - row_shift, step=dt / self.substeps, substeps=self.substeps, planner=refs,
+                                                        force_sample_time=self.force_sample_time, tape=tape, tape_row0=a - tape_shift, mismatch=mismatch)
+                    if states is not None:
+                        states[b - row_shift].copy_(live["state"])
+                    continue
                 cur = s.rollout_walk_device(a, b - a, cold and a == t0, plan_at(a), sets[0], sets[1], cur, live["ok"], live["land"], live["state"], live["P"],
                                             live["X0"], live["X"], live["info"], live["zmp"], rec, row0=a - row_shift, wrench_ticks=wr,
                                             step=dt / self.substeps, substeps=self.substeps, planner=refs, force_sample_time=self.force_sample_time,
@@ -1236,9 +1344,11 @@ class WalkingRollout:
         args.apply_defaults()
         return self._queued(lambda: self._walk_resume(*args.args, **args.kwargs, mismatch=mismatch))
 
-    def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every, mismatch=None):
+    def _walk_resume(self, snapshot, ticks, index, push, push_ticks, replan, trace, stop, skip_ended, taped, every, mismatch=None, sensor=None):
         torch, dev, s, B = self.torch, self.dev, self.solver, self.B
         mm = self._walk_mismatch = self._mismatch_of(mismatch)
+        sn = self._walk_sensor = self._sensor_of(sensor, mm, push)
+        plant = torch.zeros((ticks, B, 6), dtype=torch.float32, device=dev) if sn is not None else None
         self._walk_inputs = []
         t0 = int(snapshot["tick"])
         rec = s.walk_record(ticks, stop=stop, trace=trace, device=dev)
@@ -1254,6 +1364,8 @@ class WalkingRollout:
             if idx is not None:
                 wt = wt.index_select(1, idx.clamp(0, int(snapshot["batch"]) - 1).to(torch.int64)).contiguous()
             wrench = (wt, first)
+        if sn is not None and wrench is not None:
+            raise ValueError("walk_resume_device_sensed: the snapshot carries a wrench schedule the MPC is told about; a known push and a sensed one are not summed")
         refs = self._planner_refs(t0 + ticks)
         plans = {int(t): p for t, p in dict(replan or {}).items() if 0 <= int(t) < t0 + ticks}
         tp = None
@@ -1263,10 +1375,13 @@ class WalkingRollout:
             tp["list_t"][0].copy_(prev[0])
             tp["list_n"][0].copy_(prev[2])
         cps = self._walk_live(live, t0, t0 + ticks, t0, plans, self.plan, wrench, refs, skip_ended, every=every, tape=tp, tape_shift=t0 - 1, mismatch=mm,
-                              limits=self.limits, limits_out=rec)
+                              limits=self.limits, limits_out=rec, sensor=sn, plant=plant)
         if every is not None:
             rec["checkpoints"] = cps
         rec.update(index_ok=index_ok, tick0=t0)
+        if sn is not None:
+            rec["plant_wrench"] = plant
+            return self._walk_finish(rec, live, tp, mismatch=mm, tick0=t0, row0=1, sensor=sn, plant_wrench=plant)
         return self._walk_finish(rec, live, tp, mismatch=mm, tick0=t0, row0=1)    # (no push_ticks and no references on a resumed walk's tape)
 
     def backward_device_checkpointed(self, w, grad_states, grad_X=None, rot=False):
@@ -1299,6 +1414,8 @@ class WalkingRollout:
         torch, B, N, L, M, s, dev = self.torch, self.B, self.cfg.N, self.L, self.M, self.solver, self.dev
         inp, cps = w["inputs"], w["checkpoints"]
         mm = inp.get("mismatch")
+        if inp.get("sensor") is not None:    # (the sensor's delay couples rows across segments: its fold must run once over the whole arrays)
+            raise NotImplementedError("backward_device_checkpointed: the walk ran under a wrench sensor; its reverse is backward_device_sensed on a tape")
         if mm is not None and not mismatch:
             raise NotImplementedError("backward_device_checkpointed: the walk ran under a plant mismatch; its reverse in bounded memory is "
                                       "backward_device_checkpointed_mismatch")

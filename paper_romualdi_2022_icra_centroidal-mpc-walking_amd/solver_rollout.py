@@ -300,6 +300,51 @@ class RolloutCalls:
             int(lists_in), C.byref(out), st))
         return out.value
 
+    # ---- sensed pushes (include/cmpc.h, cmpc_wrench_sensor; DESIGN.md 7f, "Sensed pushes").  Private: the public names are WalkingRollout's ----
+    def _wrench_sensor(self, delay=0, hold_knots=1, deadband=0.7, noise=None, device=None):
+        """A cmpc_wrench_sensor as a dict: noise[Tn, B, 6] float32 (numpy or a CUDA tensor; zero rows count as absent) is added to the reading of tick
+        tick_first + r of the walk's mismatch.  The dict keeps the device tensor alive and holds "_c", the C struct that points at it."""
+        import torch
+        hold = []
+        t = None
+        if noise is not None:
+            t = _upload(noise, self._dev(device), torch.float32, hold).contiguous()
+            if t.dim() != 3 or tuple(t.shape[1:]) != (self.batch, 6):
+                raise AssertionError(f"noise: expected [.., {(self.batch, 6)}]")
+            t = t if t.numel() > 0 else None
+        return dict(delay=int(delay), hold_knots=int(hold_knots), deadband=float(deadband), noise=t, _host=hold,
+                    _c=_capi.CmpcWrenchSensor(int(delay), int(hold_knots), float(deadband), opt_ptr(t), 0 if t is None else int(t.shape[0])))
+
+    def _wrench_sense_device(self, tick0, rows, mismatch, sensor, wrench_rows=True, passed=True):
+        """cmpc_wrench_sense_device: rows tick0 .. tick0 + rows - 1 of the sensor's rule in one launch -> (wrench_rows[rows, B, N, 6] or None,
+        plant_wrench[rows, B, 6] float32, pass[rows, B] int32 or None)"""
+        import torch
+        B, N, dev = self.batch, self.cfg.N, mismatch["hidden_wrench"].device
+        wr = torch.empty((rows, B, N, 6), dtype=torch.float32, device=dev) if wrench_rows else None
+        pl = torch.empty((rows, B, 6), dtype=torch.float32, device=dev)
+        ps = torch.empty((rows, B), dtype=torch.int32, device=dev) if passed else None
+        self._launch(dev, lambda st: self._lib.cmpc_wrench_sense_device(self._h, int(tick0), int(rows), C.byref(mismatch["_c"]), C.byref(sensor["_c"]),
+                                                                        opt_ptr(wr), pl.data_ptr(), opt_ptr(ps), st), "cmpc_wrench_sense_device")
+        return wr, pl, ps
+
+    def _rollout_walk_sensed_device(self, sensor, plant_wrench, tick0, ticks, cold_first, plan, lists, lists_b, lists_in, ok, land, dState, dP, dX0, dX, dInfo,
+                                    dZmp, rec, row0=0, step=0.01, substeps=6, zmp_half_x=0.08, zmp_half_y=0.03, planner=None, force_sample_time=False,
+                                    tape=None, tape_row0=None, mismatch=None):
+        """cmpc_rollout_walk_sensed_device: rollout_walk_device(mismatch=...) with a sense launch in front of each tick (sensor: _wrench_sensor(...)); tick i
+        of the call writes row i of plant_wrench[ticks.., B, 6] float32.  No wrench_ticks and no dWrench: the MPC's wrench is the sensed one."""
+        import torch
+        io = self._walk_io(plan, lists, lists_b, ok, land, dState, None, dP, dX0, dX, dInfo, dZmp, step, substeps, zmp_half_x, zmp_half_y, planner,
+                           force_sample_time)
+        out = C.c_int(-1)
+        pw = ptr(plant_wrench, torch.float32, (None, self.batch, 6), "plant_wrench", required=True)
+        if plant_wrench.shape[0] < ticks:
+            raise AssertionError("plant_wrench: fewer rows than ticks")
+        self._launch(dP.device, lambda st: self._lib.cmpc_rollout_walk_sensed_device(
+            self._h, lists[0].shape[2], int(tick0), int(ticks), 1 if cold_first else 0, C.byref(io), rec["_c"] if rec is not None else None, int(row0),
+            int(lists_in), C.byref(out), tape["_c"] if tape is not None else None, int(row0 if tape_row0 is None else tape_row0) if tape is not None else 0,
+            C.byref(mismatch["_c"]) if mismatch is not None else None, C.byref(sensor["_c"]), pw, st), "cmpc_rollout_walk_sensed_device")
+        return out.value
+
     # ---- refill: a queue of trials behind the slots of a walk (include/cmpc.h, cmpc_walk_refill) ----
     def _need_refill(self):
         if not hasattr(self._lib, "cmpc_rollout_walk_refill_device"):

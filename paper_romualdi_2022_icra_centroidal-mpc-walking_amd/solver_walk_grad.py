@@ -334,3 +334,36 @@ class WalkGradCalls:
         """cmpc_rollout_walk_jvp_gate_device: one gate step of the forward walk as one launch; gate: a _capi.CmpcWalkJvpGate of device pointers."""
         self._launch(self._dev(device), lambda st: self._lib.cmpc_rollout_walk_jvp_gate_device(self._h, C.byref(gate), st))
 
+
+    # ---- sensed pushes: the sensor's transpose and tangent (include/cmpc.h, cmpc_wrench_sensor).  Private: the public names are WalkingRollout's ----
+    def _wrench_sense_vjp_device(self, tick0, rows, mismatch, sensor, grad_wrench, grad_hidden):
+        """cmpc_wrench_sense_vjp_device: the reverse walk's wrench[rows, B, N, 6] float32 and hidden_wrench[rows, B, 6] float64 (taken on the plant rows)
+        -> (hidden_wrench[Th, B, 6], sensor_noise[Tn, B, 6] or None) float64, shaped as the schedules of mismatch and sensor, in one launch"""
+        import torch
+        B, N, f64 = self.batch, self.cfg.N, torch.float64
+        gw = ptr(grad_wrench, torch.float32, (rows, B, N, 6), "grad_wrench", required=True)
+        gh = ptr(grad_hidden, f64, (rows, B, 6), "grad_hidden", required=True)
+        dev = grad_wrench.device
+        gt = torch.empty(tuple(mismatch["hidden_wrench"].shape), dtype=f64, device=dev)
+        gn = None if sensor["noise"] is None else torch.empty(tuple(sensor["noise"].shape), dtype=f64, device=dev)
+        self._launch(dev, lambda st: self._lib.cmpc_wrench_sense_vjp_device(
+            self._h, int(tick0), int(rows), C.byref(mismatch["_c"]), C.byref(sensor["_c"]), gw, gh, gt.data_ptr(), None if gn is None else gn.data_ptr(), st),
+            "cmpc_wrench_sense_vjp_device")
+        return gt, gn
+
+    def _wrench_sense_jvp_device(self, tick0, rows, k, mismatch, sensor, dir_hidden, dir_noise=None):
+        """cmpc_wrench_sense_jvp_device: dir_hidden[Th, B, k, 6] and dir_noise[Tn, B, k, 6] (or None) float64 -> (dir_wrench[rows, B, k, N, 6] float32,
+        dir_plant_wrench[rows, B, k, 6] float64): what cmpc_walk_dirs.dDirWrench and cmpc_walk_dirs_mismatch.dDirHidden take, in one launch"""
+        import torch
+        B, N, f64, k = self.batch, self.cfg.N, torch.float64, int(k)
+        dh = ptr(dir_hidden, f64, (int(mismatch["hidden_wrench"].shape[0]), B, k, 6), "dir_hidden", required=True)
+        dn = None
+        if sensor["noise"] is not None:
+            dn = ptr(dir_noise, f64, (int(sensor["noise"].shape[0]), B, k, 6), "dir_noise")
+        dev = dir_hidden.device
+        dw = torch.empty((rows, B, k, N, 6), dtype=torch.float32, device=dev)
+        dp = torch.empty((rows, B, k, 6), dtype=f64, device=dev)
+        self._launch(dev, lambda st: self._lib.cmpc_wrench_sense_jvp_device(
+            self._h, int(tick0), int(rows), k, C.byref(mismatch["_c"]), C.byref(sensor["_c"]), dh, dn, dw.data_ptr(), dp.data_ptr(), st),
+            "cmpc_wrench_sense_jvp_device")
+        return dw, dp
